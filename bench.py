@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark: audio samples/s (+ RTF) for 128-phoneme zero-shot synthesis @22.05 kHz.
 
-    python bench.py --gpus N --steps K --warmup W [--config 2|4|5]
+    python bench.py --gpus N --steps K --warmup W [--config 2|4|5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
@@ -16,6 +16,14 @@
 Timing: W untimed steps, then exactly K steps bracketed by a barrier + full device drain on both sides; MAX over ranks.
 Rank 0 prints ONE JSON line.  No GPU runtime other than libzvx (and, for N > 1, the system librccl it dlopens) is loaded and
 torch is never imported; for N > 1 the 128-byte RCCL id travels over a plain TCP socket from rank 0.
+
+A plain run does only what the headline needs: set-up, warm-up, the K timed steps (no profiling events), the line.  --full adds
+everything else: the instrumented step and per-launch events behind `roofline` / `roofline_per_stage` / `kernels_one_step` /
+`stage_ms_*`, the vocoder-arithmetic A/B, the `output_ok` check, and unless --no-cpu-baseline the busy tail, the exact-f32 mode and
+the CPU baseline.
+--dump-outputs DIR: what the last timed step handed its caller (rank 0: the gathered rows for N > 1), written right behind the
+timed region as DIR/<name>.npy (float32; float64 for 32-bit integers), at most 64 MB in all; inputs and weights are seeded, so two
+builds run with the same options can be compared output for output.
 """
 import argparse
 import hashlib
@@ -33,6 +41,7 @@ HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s
 MFMA_PEAK = {"bf16": 2500.0, "f32": 157.3}   # dense TFLOP/s (MI355X_MICROARCH.md)
 F32_STAGES = ("variance",)                    # exact-f32 MFMA in both precision modes (its outputs are the discrete decisions)
 SPLIT_STAGES = ("encoder",)                   # 16-bit mode: f32-class results from 3 half-precision products per multiply
+DUMP_BYTES = 64_000_000                       # --dump-outputs: everything written, .npy headers included
 
 
 def src_sha16():
@@ -173,6 +182,29 @@ class SmiClockSampler:
         self.th.join(timeout=15)
 
 
+def dump_outputs(path, arrays):
+    """--dump-outputs: one <path>/<name>.npy per array, float32 (float64 for float64 and 32/64-bit integers), DUMP_BYTES in all.  An
+    array larger than what is left keeps a fixed sample of its rows (seed 0, ascending), whose indices go to <name>_rows.npy."""
+    os.makedirs(path, exist_ok=True)
+    conv = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        wide = a.dtype == np.float64 or (a.dtype.kind in "iu" and a.dtype.itemsize > 2)
+        conv[name] = a.astype(np.float64 if wide else np.float32)
+    left, hdr = DUMP_BYTES, 1024                  # (an .npy header is 128 bytes)
+    for name, a in sorted(conv.items(), key=lambda kv: kv[1].nbytes):      # the small arrays whole, the largest last
+        if a.nbytes + hdr > left:
+            k = (left - 2 * hdr - 8 * len(a)) // (a.nbytes // len(a))
+            if k < 1:
+                raise SystemExit(f"--dump-outputs: one row of {name} {a.shape} is larger than the {DUMP_BYTES} bytes left")
+            rows = np.sort(np.random.default_rng(0).choice(len(a), k, replace=False))
+            np.save(os.path.join(path, name + "_rows.npy"), rows.astype(np.float64))
+            left -= rows.nbytes + hdr
+            a = a[rows]
+        np.save(os.path.join(path, name + ".npy"), a)
+        left -= a.nbytes + hdr
+
+
 def flush_c_stdio():
     import ctypes
     ctypes.CDLL(None).fflush(None)
@@ -274,8 +306,12 @@ def main(argv=None, ctx_factory=default_ctx_factory):
     ap.add_argument("--host-out-sync", action="store_true", help="with --host-out: the round-5 form, every call waits for its own D2H copy (A/B)")
     ap.add_argument("--in-flight", type=int, default=1, help="config 2, one GPU: steps alternate over this many contexts (A/B of round 3; since round 4 ONE context overlaps batch i+1's front end with batch i's vocoder by itself: zvx_set_int front_overlap)")
     ap.add_argument("--set", action="append", default=[], metavar="KEY=INT", help="zvx_set_int(KEY, INT) on every context before the first step (A/B of a runtime switch; echoed in config.overrides)")
-    ap.add_argument("--profile", type=int, default=2, help="0 none, 1 stage events, 2 + per-launch events on the dominant kernel")
+    ap.add_argument("--profile", type=int, default=None, help="0 none, 1 stage events, 2 + per-launch events on the dominant kernel (default: 2 with --full, else 0)")
+    ap.add_argument("--full", action="store_true", help="beyond the headline: roofline / per-stage figures, A/B, busy tail, f32 mode, output check, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, <= 64 MB)")
     args = ap.parse_args(argv)
+    if args.profile is None:
+        args.profile = 2 if args.full else 0
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         return spawn_ranks(args.gpus, list(sys.argv[1:] if argv is None else argv))
@@ -340,15 +376,18 @@ def main(argv=None, ctx_factory=default_ctx_factory):
             c2.comm_init(None, 0, 1)
             more_ctx.append((c2, [c2.dev_alloc(B * row_bytes) for _ in range(2)]))
 
+        last = [None, None]                              # --dump-outputs: the latest step's (context, waveform buffer) and returned dict
+
         def step():
             if args.host_out and args.host_out_sync:    # the reference's contract: tts_ex returns host NumPy (synthesize.py:233-239)
-                host_wav[0] = ctx.synthesize(ph, pu, Tlen, spk, dur, pad_to, want_mel=False, pcm16=args.pcm16)["wav"]
+                last[1] = ctx.synthesize(ph, pu, Tlen, spk, dur, pad_to, want_mel=False, pcm16=args.pcm16)
+                host_wav[0] = last[1]["wav"]
                 return
             if args.host_out:
                 # same contract, pipelined: step i is queued (ZVX_HOST_ASYNC: its rows travel to a pinned host slot on the context's
                 # copy stream), then the host takes delivery of step i - 1's rows -- every step's waveform is in host memory when
                 # the closing fence returns
-                r = ctx.synthesize(ph, pu, Tlen, spk, dur, pad_to, want_mel=False, pcm16=args.pcm16, host_async=True)
+                r = last[1] = ctx.synthesize(ph, pu, Tlen, spk, dur, pad_to, want_mel=False, pcm16=args.pcm16, host_async=True)
                 if host_prev[0] is not None:
                     host_wav[0] = ctx.wait_host(host_prev[0], pcm16=args.pcm16)
                 host_prev[0] = r["slot"]
@@ -357,9 +396,21 @@ def main(argv=None, ctx_factory=default_ctx_factory):
             nf = 1 + len(more_ctx)
             c, bufs = (ctx, wav) if i % nf == 0 else more_ctx[i % nf - 1]
             buf = bufs[(i // nf) & 1]
-            c.synthesize(ph, pu, Tlen, spk, dur, pad_to, want_mel=False, wav_device_ptr=buf, wav_stride=N, no_sync=True, pcm16=args.pcm16)
+            last[0] = (c, buf)
+            last[1] = c.synthesize(ph, pu, Tlen, spk, dur, pad_to, want_mel=False, wav_device_ptr=buf, wav_stride=N, no_sync=True, pcm16=args.pcm16)
             if world > 1:
                 ctx.comm_gather(buf, B * row_bytes, gathered, root=0, no_sync=True)
+
+        def outputs():                                   # after the closing fence: the rows the caller holds, and the lengths it was told
+            if world > 1:
+                return {"wav": ctx.dev_to_host(gathered, (world * B, N), wdt)}          # (every rank's rows; mel_len is per rank)
+            if args.host_out:
+                out = {"wav": np.array(host_wav[0])}
+            else:
+                out = {"wav": last[0][0].dev_to_host(last[0][1], (B, N), wdt)}
+            if isinstance(last[1], dict) and last[1].get("mel_len") is not None:
+                out["mel_len"] = last[1]["mel_len"]
+            return out
         workload = (f"batch={B}/GPU x {T}-phoneme utterances, precomputed spk-embed, forced durations=7 -> {L} frames -> {N} samples each; "
                     f"tts_medium_{'styledec' if args.decoder == 'styletts' else 'fs2'} + HiFi-GAN {args.vocoder.upper()}, end-to-end phoneme->waveform"
                     + (f", RCCL waveform gather ({'int16' if args.pcm16 else 'f32'}) to rank 0 each step" if world > 1 else ""))
@@ -393,6 +444,9 @@ def main(argv=None, ctx_factory=default_ctx_factory):
 
         def step():
             ctx.vocode_mel_device(mel_d, Pn, P, wav[0], N, no_sync=True, pcm16=args.pcm16)
+
+        def outputs():
+            return {"wav": ctx.dev_to_host(wav[0], (B, N), wdt)}
         workload = f"HiFi-GAN {args.vocoder.upper()} generator alone: batch={B} x 1024-frame N(0,1) mels (seed 7, device-resident) -> {N} samples each"
         cfg_extra = {"global_batch": B, "frames": P, "samples_per_utt": N, "vocoder": args.vocoder}
     else:
@@ -406,6 +460,9 @@ def main(argv=None, ctx_factory=default_ctx_factory):
 
         def step():
             ctx.spkemb_device(mel_d, lens, B, Tr, emb_d, no_sync=True)
+
+        def outputs():
+            return {"embedding": ctx.dev_to_host(emb_d, (B, ctx.hidden), np.float32)}
         workload = (f"ResNetSE34V2 speaker encoder: batches of {B} device-resident 3 s reference mels [258, 80] "
                     f"({args.steps} steps = {args.steps * B} clips; BASELINE configs[4] = 1000 clips = 4 steps of 250)")
         cfg_extra = {"global_batch": B, "ref_frames": Tr}
@@ -439,7 +496,7 @@ def main(argv=None, ctx_factory=default_ctx_factory):
     ctx.set_int("profile", args.profile)
     ctx.reset_stats()
     fence()
-    smi = SmiClockSampler(local_rank) if rank == 0 else None
+    smi = SmiClockSampler(local_rank) if (rank == 0 and args.full) else None
     if smi:
         smi.__enter__()
     t0 = time.perf_counter()
@@ -449,6 +506,8 @@ def main(argv=None, ctx_factory=default_ctx_factory):
     elapsed = time.perf_counter() - t0
     if smi:
         smi.__exit__()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, outputs())    # before anything below runs another step into the same buffers
     stage_ms = ctx.stage_times()
     kstats = ctx.kernel_stats()
     ctx.set_int("profile", 0)
@@ -456,7 +515,7 @@ def main(argv=None, ctx_factory=default_ctx_factory):
     # IEEE half (8x less rounding noise in the waveform); the bf16 kernels of rounds 1-4 stay behind zvx_set_int("voc_f16", 0) and are
     # ~4-5 % faster at the board's power limit.  Untimed for the line's `value`; reported beside it so that one run carries both figures.
     voc_ab = None
-    if world == 1 and args.config in (2, 4) and args.precision == "bf16" and "voc_f16" not in overrides and "voc_f16_stages" not in overrides \
+    if args.full and world == 1 and args.config in (2, 4) and args.precision == "bf16" and "voc_f16" not in overrides and "voc_f16_stages" not in overrides \
             and not args.host_out and args.in_flight <= 1 and not os.environ.get("ZVX_BENCH_NO_AB") and args.steps >= 10:
         # measured error of each choice at the headline shape (tools/ab_voc_stages.py, profiles/r06_ab_voc_stages.txt): waveform error against
         # the f32 oracle end to end / the generator alone, max | rms
@@ -485,7 +544,7 @@ def main(argv=None, ctx_factory=default_ctx_factory):
     # more, OUTSIDE the timed region and before the CPU baseline (VERDICT r4 #8d, r5 #6b: 2 s was still shorter than a 5 s sampler); the
     # tail is itself timed and reported (`busy_tail`: a second, longer measurement of the same steps on the same box), counted in nothing
     busy_steps, busy_tail = 0, None
-    if world == 1 and elapsed < 6.0 and not args.no_cpu_baseline and not os.environ.get("ZVX_BENCH_NO_BUSY_TAIL"):   # (the default command; profiling passes use --no-cpu-baseline)
+    if args.full and world == 1 and elapsed < 6.0 and not args.no_cpu_baseline and not os.environ.get("ZVX_BENCH_NO_BUSY_TAIL"):   # (profiling passes use --no-cpu-baseline)
         per = max(elapsed / max(args.steps, 1), 1e-4)
         busy_steps = int(min(6.5 / per, 20000))
         tb = time.perf_counter()
@@ -497,9 +556,9 @@ def main(argv=None, ctx_factory=default_ctx_factory):
                      "note": "untimed for `value`: the same step() right behind the timed region, long enough for a 5 s utilisation sampler to see the GPU busy"}
     # The reference computes in fp32 everywhere (synthesize.py:228-233, no autocast): the same workload once more in the library's
     # exact-f32 mode (every contraction on v_mfma_f32_32x32x2_f32, the mode every parity test holds to 2e-4) -- a few steps on a second
-    # context, untimed for `value`, quoted beside it as `f32_mode` (VERDICT r5 #6a).  The default command only.
+    # context, untimed for `value`, quoted beside it as `f32_mode` (VERDICT r5 #6a).  The default --full command only.
     f32_mode = None
-    if world == 1 and args.config == 2 and args.precision == "bf16" and not args.no_cpu_baseline and not overrides and not args.host_out \
+    if args.full and world == 1 and args.config == 2 and args.precision == "bf16" and not args.no_cpu_baseline and not overrides and not args.host_out \
             and args.in_flight <= 1 and not os.environ.get("ZVX_BENCH_NO_F32"):
         try:
             import copy
@@ -524,10 +583,11 @@ def main(argv=None, ctx_factory=default_ctx_factory):
     elapsed = ctx.comm_max(elapsed)                  # MAX over ranks
 
     # sanity on the produced data (not timed)
-    if args.config == 5:
+    ok = None
+    if args.full and args.config == 5:
         e = ctx.dev_to_host(emb_d, (B, ctx.hidden), np.float32)
         ok = bool(np.isfinite(e).all()) and float(np.abs(np.linalg.norm(e, axis=1) - 1).max()) < 1e-3
-    else:
+    elif args.full:
         if world > 1 and rank == 0:
             g = ctx.dev_to_host(gathered, (world * B, N), wdt)
             own = ctx.dev_to_host(wav[(it[0] - 1) & 1], (B, N), wdt)           # (world > 1 runs one context: it[0] counts its steps)
@@ -560,9 +620,14 @@ def main(argv=None, ctx_factory=default_ctx_factory):
             "ms_per_step": 1e3 * elapsed / args.steps, "timed_region_s": elapsed, "higher_is_better": True, "scaling": "weak",
             "vs_baseline": None, "dtype": dtype_name, "data": "synthetic",
             "config": {"workload": workload, **cfg_extra, **({"overrides": overrides} if overrides else {})},
-            "stage_ms_last_step": stage_ms, "output_ok": ok, "src_sha16": src_sha16(), "untimed_busy_tail_steps": busy_steps,
+            "src_sha16": src_sha16(),
             "steps_for_2s": int(np.ceil(2.0 / max(elapsed / max(args.steps, 1), 1e-6))),      # --steps that would make the timed region 2 s on this box
         }
+        if args.profile:
+            res["stage_ms_last_step"] = stage_ms
+        if args.full:
+            res["output_ok"] = ok
+            res["untimed_busy_tail_steps"] = busy_steps
         if busy_tail is not None:
             res["busy_tail"] = busy_tail
         if f32_mode is not None:
@@ -659,7 +724,7 @@ def main(argv=None, ctx_factory=default_ctx_factory):
                     row["note"] = "algorithmic (f32-equivalent) FLOPs; issued on the f16 MFMA as ~3x that (hi.wh + hi.wl + lo.wh)"
                 per_stage.append(row)
             res["roofline_per_stage"] = per_stage
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(args.config, model, T, 896 if args.config == 2 else 0, args.decoder, args.vocoder, numpy_leg=args.cpu_numpy)
         flush_c_stdio()
         print(json.dumps(res), flush=True)

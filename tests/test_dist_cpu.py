@@ -163,7 +163,7 @@ def _bench_worker(rank, world, port, q):
     buf = io.StringIO()
     with contextlib.redirect_stdout(buf):
         rc = bench.main(["--gpus", str(world), "--steps", "3", "--warmup", "1", "--batch", "4", "--phonemes", "8", "--profile", "0",
-                         "--no-cpu-baseline"], ctx_factory=factory)
+                         "--no-cpu-baseline", "--full"], ctx_factory=factory)
     assert rc == 0
     # double buffering: consecutive steps alternate between the two waveform buffers, every step is followed by its gather
     synth = [c for c in stub.calls if c[0] == "synthesize"]
@@ -205,8 +205,8 @@ def test_bench_in_flight_two_contexts_round_robin(capsys):
 
     old = {k: os.environ.pop(k, None) for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
     try:
-        rc = bench.main(["--in-flight", "2", "--steps", "4", "--warmup", "2", "--batch", "4", "--phonemes", "8", "--profile", "0", "--no-cpu-baseline"],
-                        ctx_factory=factory)
+        rc = bench.main(["--in-flight", "2", "--steps", "4", "--warmup", "2", "--batch", "4", "--phonemes", "8", "--profile", "0", "--no-cpu-baseline",
+                         "--full"], ctx_factory=factory)
     finally:
         os.environ.update({k: v for k, v in old.items() if v is not None})
     assert rc == 0 and len(made) == 2
@@ -249,6 +249,62 @@ def test_bench_set_overrides_reach_every_context_and_the_line(capsys):
     assert r["config"]["overrides"] == {"voc_overlap_maxb": 0, "norm_fuse_maxb": 7}
 
 
+def test_bench_plain_run_times_exactly_its_steps_and_dumps_the_last_one(capsys, tmp_path):
+    """A plain `bench.py --gpus 1 --steps K --warmup W` runs W + K steps and nothing else (no instrumented step, A/B, busy tail,
+    f32 mode or CPU baseline: those are --full's); --dump-outputs DIR holds the rows of the last timed step as float32."""
+    import bench
+    from zerovox_amd import config as zcfg
+    made = []
+
+    def factory(args, local_rank):
+        c = StubContext(); c._first = 0
+        made.append(c)
+        return c, (zcfg.medium_modelcfg("styletts"), None, None, None)
+
+    old = {k: os.environ.pop(k, None) for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE")}
+    try:
+        rc = bench.main(["--gpus", "1", "--steps", "12", "--warmup", "2", "--batch", "3", "--phonemes", "8", "--dump-outputs", str(tmp_path)],
+                        ctx_factory=factory)
+    finally:
+        os.environ.update({k: v for k, v in old.items() if v is not None})
+    assert rc == 0 and len(made) == 1
+    assert len([c for c in made[0].calls if c[0] == "synthesize"]) == 14
+    r = json.loads([l for l in capsys.readouterr().out.splitlines() if l.strip()][-1])
+    assert r["steps"] == 12 and r["warmup"] == 2 and r["unit"] == "samples/s" and r["higher_is_better"] is True and r["dtype"] == "f16+bf16"
+    assert r["metric"].startswith("audio samples/sec") and r["ms_per_step"] > 0
+    total = 3 * r["config"]["samples_per_utt"] * 12
+    assert abs(r["value"] * r["ms_per_step"] * 1e-3 * 12 - total) < 1e-6 * total
+    for k in ("roofline", "cpu_baseline", "busy_tail", "f32_mode", "ab_vocoder_arithmetic", "output_ok", "stage_ms_last_step"):
+        assert k not in r, k
+    assert sorted(os.listdir(tmp_path)) == ["wav.npy"]
+    w = np.load(tmp_path / "wav.npy")
+    assert w.dtype == np.float32 and w.shape == (3, r["config"]["samples_per_utt"])
+    assert np.array_equal(w, np.broadcast_to((np.arange(3, dtype=np.float32) + 1)[:, None] / 1000.0, w.shape))
+
+
+def test_bench_dump_keeps_a_fixed_sample_of_rows_within_its_budget(tmp_path, monkeypatch):
+    """--dump-outputs: integers become float64, int16 PCM float32; an array larger than the budget keeps a seeded, ascending sample
+    of its rows (indices in <name>_rows.npy), the same on every run."""
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 60_000)
+    rng = np.random.default_rng(5)
+    wav = rng.standard_normal((40, 500)).astype(np.float32)                    # 80 000 bytes: over the budget
+    lens = np.arange(40, dtype=np.int32)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"wav": wav, "mel_len": lens})
+    assert sorted(os.listdir(tmp_path / "a")) == ["mel_len.npy", "wav.npy", "wav_rows.npy"]
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a")) <= 60_000
+    ml, w, rows = (np.load(tmp_path / "a" / f) for f in ("mel_len.npy", "wav.npy", "wav_rows.npy"))
+    assert ml.dtype == np.float64 and np.array_equal(ml, lens)
+    assert rows.dtype == np.float64 and np.all(np.diff(rows) > 0) and 20 <= len(rows) < 40
+    assert w.dtype == np.float32 and np.array_equal(w, wav[rows.astype(int)])
+    for f in ("mel_len.npy", "wav.npy", "wav_rows.npy"):
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f))
+    bench.dump_outputs(str(tmp_path / "c"), {"wav": np.array([[-32760, 7]], np.int16)})
+    c = np.load(tmp_path / "c" / "wav.npy")
+    assert c.dtype == np.float32 and c.tolist() == [[-32760.0, 7.0]]
+
+
 def test_bench_under_torchrun_with_stub_context():
     """The driver's own launch line (python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1
     --master-port P bench.py --gpus N ...): env parsing, the TCPStore rendezvous against the elastic agent's store, one JSON line."""
@@ -256,7 +312,7 @@ def test_bench_under_torchrun_with_stub_context():
     port = 29700 + (os.getpid() % 200)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "tests", "_bench_stub_main.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "3", "--phonemes", "8", "--profile", "0", "--no-cpu-baseline"]
+           "--batch", "3", "--phonemes", "8", "--profile", "0", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -297,14 +353,14 @@ def test_comm_id_rendezvous_world8_over_plain_sockets(monkeypatch):
     assert sorted(got) == list(range(8)) and all(got[r] == cid for r in range(8))
 
 
-def test_bench_spawns_its_own_ranks_when_launched_bare():
+def test_bench_spawns_its_own_ranks_when_launched_bare(tmp_path):
     """`python bench.py --gpus 2 ...` with no launcher (WORLD_SIZE unset), as the driver starts the N = 1 line: bench.py starts
-    the ranks itself and still prints exactly one JSON line."""
+    the ranks itself and still prints exactly one JSON line; --dump-outputs on rank 0 holds every rank's rows of the last step."""
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env["ZVX_BENCH_ENTRY"] = os.path.join(ROOT, "tests", "_bench_stub_main.py")      # the ranks run bench.main with the stub context
     cmd = [sys.executable, os.path.join(ROOT, "tests", "_bench_stub_main.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-           "--batch", "3", "--phonemes", "8", "--profile", "0", "--no-cpu-baseline"]
+           "--batch", "3", "--phonemes", "8", "--profile", "0", "--no-cpu-baseline", "--full", "--dump-outputs", str(tmp_path)]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT, env=env)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
@@ -312,6 +368,9 @@ def test_bench_spawns_its_own_ranks_when_launched_bare():
     r = json.loads(lines[0])
     assert r["n_gpus"] == 2 and r["steps"] == 2 and r["config"]["global_batch"] == 6 and r["output_ok"] is True
     assert r["config"]["wav_delivery"].startswith("device")
+    w = np.load(tmp_path / "wav.npy")
+    assert sorted(os.listdir(tmp_path)) == ["wav.npy"] and w.dtype == np.float32 and w.shape == (6, r["config"]["samples_per_utt"])
+    assert np.array_equal(w, np.broadcast_to((np.arange(6, dtype=np.float32) + 1)[:, None] / 1000.0, w.shape))
 
 
 def test_comm_id_rendezvous_ignores_stray_connections(monkeypatch):

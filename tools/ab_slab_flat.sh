@@ -3,7 +3,7 @@
 # then a bit-equality check of a ragged synthesis call under both settings.   usage (on the GPU box): bash tools/ab_slab_flat.sh
 ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 cd $ROOT
-line() { python bench.py --no-cpu-baseline "$@" 2>/dev/null | python -c "
+line() { python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); s=d['stage_ms_last_step']; print('%.3f ms/step  enc %.3f dec %.3f voc %.3f spk %.3f  ok=%s' % (d['ms_per_step'], s['encoder'], s['decoder'], s['vocoder'], s['spkemb'], d['output_ok']))"; }
 for rep in 1 2; do
   for f in 0 1; do echo -n "headline     slab_flat=$f: "; line --set slab_flat=$f; done

@@ -5,9 +5,9 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/r6f; mkdir -p $OUT; rm -f $OUT/*
 cd $ROOT
 for V in v2 v1; do for N in 1 2 3; do
-  GPU_MAX_HW_QUEUES=8 timeout 300 python bench.py --vocoder $V --in-flight $N --no-cpu-baseline > $OUT/bench_${V}_inflight$N.json 2>> $OUT/bench.err
+  GPU_MAX_HW_QUEUES=8 timeout 300 python bench.py --full --vocoder $V --in-flight $N --no-cpu-baseline > $OUT/bench_${V}_inflight$N.json 2>> $OUT/bench.err
 done; done
-timeout 300 python bench.py --vocoder v2 --in-flight 2 --no-cpu-baseline > $OUT/bench_v2_inflight2_q4.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --vocoder v2 --in-flight 2 --no-cpu-baseline > $OUT/bench_v2_inflight2_q4.json 2>> $OUT/bench.err
 python - <<'PY'
 import json,glob,os
 for f in sorted(glob.glob(os.environ.get("GRAFT_REPO_ROOT",".")+"/gpurun_out/r6f/bench_*.json")):

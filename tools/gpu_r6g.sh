@@ -6,10 +6,10 @@ OUT=$ROOT/gpurun_out/r6g; mkdir -p $OUT; rm -f $OUT/*
 cd $ROOT
 timeout 900 python -m pytest tests -m gpu -q -x -k "v3 or resblock2 or tiny2 or single_request_overlap or golden" > $OUT/pytest_sel.txt 2>&1; tail -5 $OUT/pytest_sel.txt
 for i in 1 2; do
-timeout 300 python bench.py --vocoder v3 --no-cpu-baseline > $OUT/bench_v3_fused_$i.json 2>> $OUT/bench.err
-timeout 300 python bench.py --vocoder v3 --set rb2fuse=0 --no-cpu-baseline > $OUT/bench_v3_unfused_$i.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --vocoder v3 --no-cpu-baseline > $OUT/bench_v3_fused_$i.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --vocoder v3 --set rb2fuse=0 --no-cpu-baseline > $OUT/bench_v3_unfused_$i.json 2>> $OUT/bench.err
 done
-timeout 300 python bench.py --vocoder v3 --set front_overlap=0 --no-cpu-baseline > $OUT/bench_v3_fused_serial.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --vocoder v3 --set front_overlap=0 --no-cpu-baseline > $OUT/bench_v3_fused_serial.json 2>> $OUT/bench.err
 ZVX_VOCODER=v3 timeout 300 python tools/shape_log_b32.py > $OUT/shape_v3.txt 2>&1
 python - <<'PY'
 import json,glob,os

@@ -6,11 +6,11 @@ OUT=$ROOT/gpurun_out/r6h; mkdir -p $OUT; rm -f $OUT/*
 cd $ROOT
 ZVX_ERR_LOG=$OUT/errlog.txt timeout 1500 python -m pytest tests -m gpu -q > $OUT/pytest_gpu.txt 2>&1; tail -8 $OUT/pytest_gpu.txt
 for i in 1 2; do
-timeout 300 python bench.py --decoder fastspeech2 --no-cpu-baseline > $OUT/bench_fs2_y16_$i.json 2>> $OUT/bench.err
-timeout 300 python bench.py --decoder fastspeech2 --set dec_y16=0 --no-cpu-baseline > $OUT/bench_fs2_y32_$i.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --decoder fastspeech2 --no-cpu-baseline > $OUT/bench_fs2_y16_$i.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --decoder fastspeech2 --set dec_y16=0 --no-cpu-baseline > $OUT/bench_fs2_y32_$i.json 2>> $OUT/bench.err
 done
-timeout 300 python bench.py --config 5 --no-cpu-baseline > $OUT/bench_cfg5.json 2>> $OUT/bench.err
-timeout 300 python bench.py --no-cpu-baseline > $OUT/bench_dev.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --config 5 --no-cpu-baseline > $OUT/bench_cfg5.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --no-cpu-baseline > $OUT/bench_dev.json 2>> $OUT/bench.err
 python - <<'PY'
 import json,glob,os
 for f in sorted(glob.glob(os.environ.get("GRAFT_REPO_ROOT",".")+"/gpurun_out/r6h/bench_*.json")):

@@ -6,7 +6,7 @@ OUT=$ROOT/gpurun_out/r6j; mkdir -p $OUT; rm -f $OUT/*
 cd $ROOT
 timeout 1200 python -m pytest tests -m gpu -q -x -k "v1 or ieee or config2 or config4 or pair_kernel or golden or audit or saturat or queued or history or invariance" > $OUT/pytest_sel.txt 2>&1; tail -4 $OUT/pytest_sel.txt
 timeout 300 python tools/shape_log_b32.py > $OUT/shape_v1.txt 2>&1
-for i in 1 2; do timeout 300 python bench.py --no-cpu-baseline > $OUT/bench_dev_$i.json 2>> $OUT/bench.err; done
+for i in 1 2; do timeout 300 python bench.py --full --no-cpu-baseline > $OUT/bench_dev_$i.json 2>> $OUT/bench.err; done
 python - <<'PY'
 import json,glob,os
 for f in sorted(glob.glob(os.environ.get("GRAFT_REPO_ROOT",".")+"/gpurun_out/r6j/bench_*.json")):

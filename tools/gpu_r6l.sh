@@ -6,8 +6,8 @@ OUT=$ROOT/gpurun_out/r6l; mkdir -p $OUT; rm -f $OUT/*
 cd $ROOT
 timeout 1200 python -m pytest tests -m gpu -q -x -k "decoder or golden or ragged or overlap or speaker or spk or tiny_utter or config2" > $OUT/pytest_sel.txt 2>&1; tail -3 $OUT/pytest_sel.txt
 for i in 1 2; do
-timeout 300 python bench.py --no-cpu-baseline > $OUT/bench_dev_$i.json 2>> $OUT/bench.err
-timeout 300 python bench.py --vocoder v2 --no-cpu-baseline > $OUT/bench_v2_$i.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --no-cpu-baseline > $OUT/bench_dev_$i.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --vocoder v2 --no-cpu-baseline > $OUT/bench_v2_$i.json 2>> $OUT/bench.err
 done
 python - <<'PY'
 import json,glob,os

@@ -8,8 +8,8 @@ ZVX_ERR_LOG=$OUT/errlog.txt timeout 1500 python -m pytest tests -m gpu -q > $OUT
 timeout 300 python tools/shape_log_b32.py > $OUT/shape_v1.txt 2>&1
 grep -n "helper.*encoder" $OUT/shape_v1.txt | head -12
 for i in 1 2; do
-timeout 300 python bench.py --no-cpu-baseline > $OUT/bench_dev_$i.json 2>> $OUT/bench.err
-timeout 300 python bench.py --vocoder v2 --no-cpu-baseline > $OUT/bench_v2_$i.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --no-cpu-baseline > $OUT/bench_dev_$i.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --vocoder v2 --no-cpu-baseline > $OUT/bench_v2_$i.json 2>> $OUT/bench.err
 done
 python - <<'PY'
 import json,glob,os

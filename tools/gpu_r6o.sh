@@ -6,8 +6,8 @@ OUT=$ROOT/gpurun_out/r6o; mkdir -p $OUT; rm -f $OUT/*
 cd $ROOT
 ZVX_ERR_LOG=$OUT/errlog.txt timeout 1200 python -m pytest tests -m gpu -q -x -k "fs2 or fastspeech2 or decoder or golden or attention or ragged or flattened or padding or long_seq" > $OUT/pytest_sel.txt 2>&1; tail -3 $OUT/pytest_sel.txt
 for i in 1 2; do
-timeout 300 python bench.py --decoder fastspeech2 --no-cpu-baseline > $OUT/bench_fs2_qkv1_$i.json 2>> $OUT/bench.err
-timeout 300 python bench.py --decoder fastspeech2 --set dec_qkv=0 --no-cpu-baseline > $OUT/bench_fs2_qkv0_$i.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --decoder fastspeech2 --no-cpu-baseline > $OUT/bench_fs2_qkv1_$i.json 2>> $OUT/bench.err
+timeout 300 python bench.py --full --decoder fastspeech2 --set dec_qkv=0 --no-cpu-baseline > $OUT/bench_fs2_qkv0_$i.json 2>> $OUT/bench.err
 done
 python - <<'PY'
 import json,glob,os

@@ -67,6 +67,6 @@ for o, d in (("--decoder", "styletts"), ("--vocoder", "v1"), ("--precision", "bf
     ap.add_argument(o, default=d)
 ap.add_argument("--exact-encoder", action="store_true")
 bargs, _ = ap.parse_known_args((sys.argv[4] if len(sys.argv) > 4 else "").split())
-json.dump({"source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE on `python bench.py --steps 3 --warmup 1 --no-cpu-baseline " + (sys.argv[4] if len(sys.argv) > 4 else "") + "`",
+json.dump({"source": "rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE on `python bench.py --steps 3 --warmup 1 --no-cpu-baseline --full " + (sys.argv[4] if len(sys.argv) > 4 else "") + "`",
            "src_sha16": bench.src_sha16(), "workload_key": bench.workload_key(bargs), **res}, open(sys.argv[3], "w"), indent=1)
 print(json.dumps(res, indent=1))
