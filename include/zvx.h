@@ -108,6 +108,38 @@ zvx_status zvx_encode(zvx_ctx* ctx, const int32_t* phoneme, const int32_t* punct
                       const int32_t* T, int B, int Tmax, const float* spk,
                       int32_t* mel_len, float* log_duration, float* pitch, float* energy);
 
+/* Prosody control (opt-in; every pointer may be NULL = neutral).  nb = ve_n_bins, T_b = utterance b's phoneme count, p_t / e_t the
+ * pitch / energy predictions, d_t today's integer duration (predicted max(rint(exp(logd)-1),0) or forced, clamped as without control).
+ *   pitch:  m_b = mean of p_t over t < T_b (accumulated in f64, rounded once to f32);
+ *           p'_t = (p_t + (pitch_range[b] - 1) * (p_t - m_b)) + pitch_shift[b], every operation a separately rounded f32 op (no FMA),
+ *           so range 1 / shift 0 gives p_t bit for bit; pitch_target[b][t], where not NaN, replaces p'_t (the reference's train-time
+ *           target path, fs2.py:631); bucket = clamp(rint(v * (nb-1)), 0, nb-1).
+ *   energy: the same with energy_shift / energy_range / energy_target on e_t.  The energy predictor reads x + pitch_embedding[the
+ *           CONTROLLED pitch bucket] (fs2.py:665-671): a pitch control changes the energy prediction.
+ *   duration: q_t = dur_scale_q16[b][t] (65536 = unchanged; a factor of q / 65536 on the duration, i.e. speed = 65536 / q).
+ *           P_t = sum_{u<=t} (int64) d_u * q_u, C_t = (P_t + 32768) >> 16, d'_t = C_t - C_{t-1}, mel_len = C_{T_b-1}: the running sum
+ *           is rounded, not each phoneme, so the total is exact to half a frame.  Applies to predicted and forced durations (forced:
+ *           the host computes mel_len with the same integer rule, the queued path stays free of syncs).
+ *   outputs: log_duration / pitch / energy stay the RAW predictions; zvx_fetch "pitch_idx" / "energy_idx" / "duration" report the
+ *           controlled values.
+ *   validation (before anything is queued, ZVX_E_INVALID, the context stays usable): shifts and ranges finite, ranges in [0, 4],
+ *           targets NaN or in [0, 1], q in [4096, 1048576] (factor 1/16 ... 16), over t < T_b.  A slowed utterance past Lmax_cap /
+ *           max_frames is ZVX_E_BUFFER as for any predicted length. */
+typedef struct zvx_prosody {
+    const float*   pitch_shift;   /* [B] */
+    const float*   pitch_range;   /* [B] */
+    const float*   energy_shift;  /* [B] */
+    const float*   energy_range;  /* [B] */
+    const float*   pitch_target;  /* [B][Tmax], NaN = predicted */
+    const float*   energy_target; /* [B][Tmax], NaN = predicted */
+    const int32_t* dur_scale_q16; /* [B][Tmax], 65536 = 1.0 */
+} zvx_prosody;
+
+/* zvx_encode with prosody control; prosody == NULL is zvx_encode.  The control arrays are copied before the call returns. */
+zvx_status zvx_encode_ex(zvx_ctx* ctx, const int32_t* phoneme, const int32_t* puncts, const int32_t* duration,
+                         const int32_t* T, int B, int Tmax, const float* spk,
+                         int32_t* mel_len, float* log_duration, float* pitch, float* energy, const zvx_prosody* prosody);
+
 /* Mel decoder on the context's features; mel_out [B][Lstride][n_mels] may be NULL; rows in [mel_len[b], max_b mel_len)
  * of utterance b are written as zeros.
  * Replaces FS2Decoder.forward (fs2.py:281-315) / StyleTTSDecoder.forward (styletts.py:181-205). */
@@ -152,6 +184,12 @@ zvx_status zvx_synthesize(zvx_ctx* ctx, const int32_t* phoneme, const int32_t* p
                           const int32_t* T, int B, int Tmax, const float* spk, const int32_t* pad_to,
                           int Lmax_cap, void* wav, int64_t wav_stride, int32_t* mel_len,
                           float* mel_out, int Lstride, float* log_duration, int flags);
+/* zvx_synthesize with prosody control (see zvx_prosody); prosody == NULL is zvx_synthesize.  Queued calls stay queued: the control
+ * arrays travel in the call's one input upload (pinned staging) and may be reused as soon as the call returns. */
+zvx_status zvx_synthesize_ex(zvx_ctx* ctx, const int32_t* phoneme, const int32_t* puncts, const int32_t* duration,
+                             const int32_t* T, int B, int Tmax, const float* spk, const int32_t* pad_to,
+                             int Lmax_cap, void* wav, int64_t wav_stride, int32_t* mel_len,
+                             float* mel_out, int Lstride, float* log_duration, int flags, const zvx_prosody* prosody);
 
 /* Host side of ZVX_HOST_ASYNC: blocks until the waveform copy into `slot` (0 / 1) has landed, then hands out the slot's pinned rows:
  * *rows -> [*nrows][*stride] samples (f32, or int16 for a ZVX_PCM16 call), the first *valid samples of a row defined as for zvx_vocode

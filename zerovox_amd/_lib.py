@@ -20,7 +20,8 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_decode", "zvx_decode_features", "zvx_vocode", "zvx_vocode_mel", "zvx_synthesize", "zvx_fetch",
            "zvx_sync", "zvx_stage_times", "zvx_kernel_stats", "zvx_tag_stats", "zvx_reset_stats",
            "zvx_comm_unique_id", "zvx_comm_init", "zvx_comm_gather", "zvx_comm_barrier", "zvx_comm_max_f64", "zvx_comm_info", "zvx_comm_destroy",
-           "zvx_dev_alloc", "zvx_dev_free", "zvx_dev_from_host", "zvx_dev_to_host", "zvx_spkemb_ex", "zvx_wait_host")
+           "zvx_dev_alloc", "zvx_dev_free", "zvx_dev_from_host", "zvx_dev_to_host", "zvx_spkemb_ex", "zvx_wait_host",
+           "zvx_encode_ex", "zvx_synthesize_ex")
 ZVX_COMM_ID_BYTES = 128
 
 
@@ -59,12 +60,14 @@ def load():
     lib.zvx_spkemb.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp]
     lib.zvx_melspec.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp]
     lib.zvx_encode.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    lib.zvx_encode_ex.argtypes = lib.zvx_encode.argtypes + [vp]
     lib.zvx_decode.argtypes = [vp, vp, C.c_int, C.c_int]
     lib.zvx_decode_features.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int]
     lib.zvx_vocode.argtypes = [vp, vp, vp, C.c_int64, C.c_int]
     lib.zvx_vocode_mel.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int64, C.c_int]
     lib.zvx_synthesize.argtypes = [vp, vp, vp, vp, vp, C.c_int, C.c_int, vp, vp, C.c_int, vp, C.c_int64, vp, vp,
                                    C.c_int, vp, C.c_int]
+    lib.zvx_synthesize_ex.argtypes = lib.zvx_synthesize.argtypes + [vp]
     lib.zvx_fetch.argtypes = [vp, C.c_char_p, vp, C.c_size_t]
     lib.zvx_sync.argtypes = [vp]
     lib.zvx_stage_times.argtypes = [vp, vp]
@@ -166,7 +169,14 @@ class Context:
         self._chk(self._lib.zvx_melspec(self._h, _ptr(wav), _ptr(n), B, Nmax, _ptr(mel), Tmax, _ptr(frames)))
         return mel, frames
 
-    def encode(self, phoneme, puncts, T, spk, duration=None):
+    def _prosody(self, prosody, B, Tmax):
+        """-> (struct, keep-alive) for the _ex entry points, or (None, None): the plain ones run."""
+        from .prosody import resolve
+        p = resolve(prosody, B, Tmax)
+        return (None, None) if p is None else (p.struct(), p)
+
+    def encode(self, phoneme, puncts, T, spk, duration=None, prosody=None):
+        """prosody: None, a prosody.Prosody or a dict of Prosody.create keywords (zvx_encode_ex)."""
         phoneme = _i32(phoneme)
         B, Tmax = phoneme.shape
         puncts = _i32(puncts, (B, Tmax))
@@ -177,8 +187,9 @@ class Context:
         logd = np.zeros((B, Tmax), np.float32)
         pitch = np.zeros((B, Tmax), np.float32)
         energy = np.zeros((B, Tmax), np.float32)
-        self._chk(self._lib.zvx_encode(self._h, _ptr(phoneme), _ptr(puncts), _ptr(dur), _ptr(T), B, Tmax, _ptr(spk),
-                                       _ptr(mel_len), _ptr(logd), _ptr(pitch), _ptr(energy)))
+        ps, _keep = self._prosody(prosody, B, Tmax)
+        args = (self._h, _ptr(phoneme), _ptr(puncts), _ptr(dur), _ptr(T), B, Tmax, _ptr(spk), _ptr(mel_len), _ptr(logd), _ptr(pitch), _ptr(energy))
+        self._chk(self._lib.zvx_encode(*args) if ps is None else self._lib.zvx_encode_ex(*args, C.byref(ps)))
         return mel_len, logd, pitch, energy
 
     def decode(self, B, Lmax):
@@ -224,12 +235,14 @@ class Context:
         return wav
 
     def synthesize(self, phoneme, puncts, T, spk, duration=None, pad_to=None, want_mel=True, Lmax_cap=0,
-                   wav_device_ptr=None, wav_stride=None, no_sync=False, pcm16=False, mel_device_ptr=None, host_async=False):
+                   wav_device_ptr=None, wav_stride=None, no_sync=False, pcm16=False, mel_device_ptr=None, host_async=False, prosody=None):
         """Batched phoneme -> waveform.  Returns dict(wav [B][N] (None if device output), mel_len, mel, log_duration).
         host_async: the call only queues work and returns dict(..., slot=s); wait_host(s) hands out the waveform rows in the
         context's pinned host memory (ZVX_HOST_ASYNC: forced durations, no mel / log-duration output).
         With a device waveform (wav_device_ptr) the mel, if wanted, is a device buffer too (ZVX_DEVICE_OUT covers both outputs):
-        mel_device_ptr -> [B][Lmax][n_mels] f32 with Lmax = the longest utterance's forced-duration sum (or Lmax_cap)."""
+        mel_device_ptr -> [B][Lmax][n_mels] f32 with Lmax = the longest utterance's forced-duration sum (or Lmax_cap).
+        prosody: None, a prosody.Prosody or a dict of Prosody.create keywords (zvx_synthesize_ex); forced durations are then sized
+        by the scaled lengths."""
         phoneme = _i32(phoneme)
         B, Tmax = phoneme.shape
         puncts = _i32(puncts, (B, Tmax))
@@ -237,8 +250,9 @@ class Context:
         spk = _f32(spk).reshape(B, self.hidden)
         dur = _i32(duration, (B, Tmax)) if duration is not None else None
         pt = _i32(pad_to, (B,)) if pad_to is not None else None
+        ps, keep = self._prosody(prosody, B, Tmax)
         if dur is not None:
-            Lmax = int(max(np.maximum(dur[b, :T[b]], 0).sum() for b in range(B)))
+            Lmax = int(max(np.maximum(dur[b, :T[b]], 0).sum() for b in range(B))) if ps is None else int(keep.scaled_lengths(dur, T).max())
         else:
             Lmax = int(Lmax_cap)
             if Lmax <= 0:
@@ -247,9 +261,9 @@ class Context:
         if host_async:
             if want_mel or wav_device_ptr is not None:
                 raise ZvxError(ZVX_E_INVALID, "host_async delivers the waveform only (want_mel=False, no device pointer)")
-            self._chk(self._lib.zvx_synthesize(self._h, _ptr(phoneme), _ptr(puncts), _ptr(dur), _ptr(T), B, Tmax, _ptr(spk),
-                                               _ptr(pt), Lmax, None, 0, _ptr(mel_len), None, max(Lmax, 1), None,
-                                               ZVX_HOST_ASYNC | (ZVX_PCM16 if pcm16 else 0)))
+            args = (self._h, _ptr(phoneme), _ptr(puncts), _ptr(dur), _ptr(T), B, Tmax, _ptr(spk), _ptr(pt), Lmax, None, 0, _ptr(mel_len),
+                    None, max(Lmax, 1), None, ZVX_HOST_ASYNC | (ZVX_PCM16 if pcm16 else 0))
+            self._chk(self._lib.zvx_synthesize(*args) if ps is None else self._lib.zvx_synthesize_ex(*args, C.byref(ps)))
             return dict(wav=None, mel_len=mel_len, mel=None, log_duration=None, slot=self.get_int("host_slot"))
         # a queued call (device output, no_sync) must not ask for host outputs: a copy into pageable memory would wait for the stream
         logd = None if (wav_device_ptr is not None and no_sync) else np.zeros((B, Tmax), np.float32)
@@ -267,9 +281,9 @@ class Context:
             stride = max(Lmax * self.hop, 1)
             wav = np.zeros((B, stride), np.int16 if pcm16 else np.float32)
             wptr = _ptr(wav)
-        self._chk(self._lib.zvx_synthesize(self._h, _ptr(phoneme), _ptr(puncts), _ptr(dur), _ptr(T), B, Tmax, _ptr(spk),
-                                           _ptr(pt), Lmax, wptr, stride, _ptr(mel_len), mptr, max(Lmax, 1),
-                                           _ptr(logd), flags))
+        args = (self._h, _ptr(phoneme), _ptr(puncts), _ptr(dur), _ptr(T), B, Tmax, _ptr(spk), _ptr(pt), Lmax, wptr, stride, _ptr(mel_len),
+                mptr, max(Lmax, 1), _ptr(logd), flags)
+        self._chk(self._lib.zvx_synthesize(*args) if ps is None else self._lib.zvx_synthesize_ex(*args, C.byref(ps)))
         return dict(wav=wav, mel_len=mel_len, mel=mel, log_duration=logd)
 
     def wait_host(self, slot: int, pcm16=False):

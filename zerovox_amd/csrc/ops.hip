@@ -348,6 +348,48 @@ void launch_bucket_embed_add(const float* pred, const float* table, int nbins, f
     hipLaunchKernelGGL(k_bucket_embed_add, dim3((Tmax + 3) / 4, B), dim3(256), 0, s, pred, table, nbins, x, ldx, C, idx_out, Tmax, T);
 }
 
+// ---------------------------------------------------------------- prosody control: controlled bucketise + embedding add
+// The launch geometry of k_bucket_embed_add (4 phonemes per workgroup).  With a range, wave 0 of every workgroup first forms the
+// utterance mean of the predictions (f64 accumulation in a fixed order, rounded once to f32: every workgroup of the utterance gets
+// the same value; T_b floats, a few hundred bytes from cache) -- one pass instead of a mean pass and a [B] buffer.
+// Each wave then controls its row: v = (p + (range - 1) * (p - m)) + shift, replaced by a non-NaN target, bucketised as above.
+// Each operation is its own rounded f32 op (no contraction), so range 1 / shift 0 gives back p bit for bit (include/zvx.h).
+__global__ void k_bucket_embed_add_ctl(const float* pred, const float* shift, const float* range, const float* target,
+                                       const float* table, int nb, float* x, int ldx, int C, int* idx_out, int Tmax, const int* T) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.y, t = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+    const int n = T[b];
+    const float* pb = pred + (long)b * Tmax;
+    if (blockIdx.x * 4 >= n) return;                            // (whole workgroup: no barrier is skipped by only some waves)
+    __shared__ float mean_s;
+    if (range) {
+        if (threadIdx.x < 64) {
+            double s = 0.0;
+            for (int u = lane; u < n; u += 64) s += (double)pb[u];
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+            if (lane == 0) mean_s = (float)(s / (double)n);
+        }
+        __syncthreads();
+    }
+    if (t >= n) return;
+    const float r1 = range ? range[b] - 1.0f : 0.f, sh = shift ? shift[b] : 0.f;
+    float v = pb[t];
+    if (range) v = v + r1 * (v - mean_s);
+    if (shift) v = v + sh;
+    if (target) { const float g = target[(long)b * Tmax + t]; if (g == g) v = g; }
+    float p = rintf(v * (float)(nb - 1));
+    p = fminf(fmaxf(p, 0.f), (float)(nb - 1));
+    const int idx = (int)p;
+    if (lane == 0 && idx_out) idx_out[b * Tmax + t] = idx;
+    float* row = x + ((long)b * Tmax + t) * ldx;
+    for (int c = lane; c < C; c += 64) row[c] += table[(long)idx * C + c];
+}
+void launch_bucket_embed_add_ctl(const float* pred, const float* shift, const float* range, const float* target, const float* table,
+                                 int nbins, float* x, int ldx, int C, int* idx_out, int B, int Tmax, const int* T, hipStream_t s) {
+    hipLaunchKernelGGL(k_bucket_embed_add_ctl, dim3((Tmax + 3) / 4, B), dim3(256), 0, s, pred, shift, range, target, table, nbins, x, ldx, C, idx_out, Tmax, T);
+}
+
 // ---------------------------------------------------------------- durations + inclusive scan (one wave / utterance)
 __global__ void k_durations(const int* forced, const float* logd, int* dur, int* cum, int* mel_len, int Tmax, const int* T) {
     const int b = blockIdx.x, lane = threadIdx.x;
@@ -373,6 +415,39 @@ __global__ void k_durations(const int* forced, const float* logd, int* dur, int*
 void launch_durations(const int* forced, const float* logd, int* dur, int* cum, int* mel_len, int B, int Tmax,
                       const int* T, hipStream_t s) {
     hipLaunchKernelGGL(k_durations, dim3(B), dim3(64), 0, s, forced, logd, dur, cum, mel_len, Tmax, T);
+}
+
+// Same durations scaled by per-phoneme Q16 factors q (65536 = 1): P_t = sum_{u<=t} d_u q_u (int64 wave scan), C_t = (P_t + 2^15) >> 16,
+// dur = C_t - C_{t-1}, cum = C_t (saturated to int32), mel_len = C_{T-1}.  Rounding the running sum keeps the total within half a frame.
+__global__ void k_durations_q16(const int* forced, const float* logd, const int* q, int* dur, int* cum, int* mel_len, int Tmax, const int* T) {
+    const int b = blockIdx.x, lane = threadIdx.x;
+    const int n = T[b];
+    long long carry = 0;                                        // P of the previous chunk's last phoneme
+    for (int t0 = 0; t0 < n; t0 += 64) {
+        const int t = t0 + lane;
+        long long wgt = 0;
+        if (t < n) {
+            int d;
+            if (forced) d = min(max(forced[b * Tmax + t], 0), 65536);
+            else d = (int)fminf(fmaxf(rintf(expf(logd[b * Tmax + t]) - 1.0f), 0.f), 65536.f);
+            wgt = (long long)d * q[b * Tmax + t];
+        }
+        long long v = wgt;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { long long u = __shfl_up(v, o, 64); if (lane >= o) v += u; }
+        if (t < n) {
+            const long long P = carry + v;
+            const long long Cn = (P + 32768) >> 16, Cp = (P - wgt + 32768) >> 16;
+            dur[b * Tmax + t] = (int)(Cn - Cp);
+            cum[b * Tmax + t] = (int)min(Cn, 0x7fffffffLL);
+        }
+        carry += __shfl(v, 63, 64);
+    }
+    if (lane == 0) mel_len[b] = (int)min((carry + 32768) >> 16, 0x7fffffffLL);
+}
+void launch_durations_q16(const int* forced, const float* logd, const int* q, int* dur, int* cum, int* mel_len, int B, int Tmax,
+                          const int* T, hipStream_t s) {
+    hipLaunchKernelGGL(k_durations_q16, dim3(B), dim3(64), 0, s, forced, logd, q, dur, cum, mel_len, Tmax, T);
 }
 
 // ---------------------------------------------------------------- length regulator: scan-indexed coalesced row gather

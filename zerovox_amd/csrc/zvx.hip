@@ -52,7 +52,7 @@ struct Tensor {
 
 struct DevBuf { void* p = nullptr; void* base = nullptr; size_t cap = 0; };
 
-struct GemmEvent { hipEvent_t a, b; int variant; double flops, bytes; long rows; int N, K, taps, res, fused; std::string tag; };
+struct GemmEvent { hipEvent_t a, b; int variant; double flops, bytes; long rows; int N, K, taps, res, fused; std::string tag, kname; };
 
 }  // namespace
 
@@ -162,6 +162,7 @@ struct zvx_ctx {
     std::vector<zvx_kernel_stat> stats;
     std::string tag = "other";             // stage label of the launches being issued (per-stage roofline accounting, profile 2)
     std::map<std::string, zvx_kernel_stat> tagstats;
+    std::map<std::string, zvx_kernel_stat> namedstats;   // helper kernels timed under a name of their own (the prosody-control kernels)
     std::vector<hipEvent_t> event_pool;
 
     // ------------------------------------------------------------------ helpers
@@ -321,13 +322,14 @@ struct zvx_ctx {
         return true;
     }
     // the HBM-bound helpers (norms, gathers, conv_post ...): event-timed as a group when every launch is being profiled
+    // kname: also counted under that name in zvx_kernel_stats
     template <typename F>
-    void timed(double flops, double bytes, F&& f) {
+    void timed(double flops, double bytes, F&& f, const char* kname = nullptr) {
         const bool prof = profile >= 2 && profile_only < 0;
         GemmEvent ev{};
         if (prof) { ev.a = new_event(); ev.b = new_event(); HIPCHK(hipEventRecord(ev.a, stream)); }
         f();
-        if (prof) { HIPCHK(hipEventRecord(ev.b, stream)); ev.variant = -1; ev.flops = flops; ev.bytes = bytes; ev.tag = tag; pending.push_back(ev); }
+        if (prof) { HIPCHK(hipEventRecord(ev.b, stream)); ev.variant = -1; ev.flops = flops; ev.bytes = bytes; ev.tag = tag; if (kname) ev.kname = kname; pending.push_back(ev); }
     }
     void resolve_events() {
         if (stats.empty()) {
@@ -344,6 +346,11 @@ struct zvx_ctx {
             auto& ts = tagstats[e.tag];
             if (!ts.name[0]) snprintf(ts.name, 64, "%s", e.tag.c_str());
             ts.launches++; ts.ms += ms; ts.flops += e.flops; ts.bytes += e.bytes;
+            if (!e.kname.empty()) {
+                auto& ks = namedstats[e.kname];
+                if (!ks.name[0]) snprintf(ks.name, 64, "%s", e.kname.c_str());
+                ks.launches++; ks.ms += ms; ks.flops += e.flops; ks.bytes += e.bytes;
+            }
             event_pool.push_back(e.a); event_pool.push_back(e.b);
         }
         pending.clear();
@@ -886,8 +893,35 @@ void variance_predictor(zvx_ctx* c, const char* nm, const float* x, int B, int T
     launch_rowdot(h2, Fv, c->pf(p + ".lw"), c->t(p + ".lb").host[0], pred, B, Tmax, T_dev, Fv, c->stream);
 }
 
+// zvx_prosody checks (include/zvx.h), over the valid phonemes only: before anything is queued
+void check_prosody(const zvx_prosody* p, const int32_t* T, int B, int Tmax) {
+    const float* per_utt[4] = {p->pitch_shift, p->pitch_range, p->energy_shift, p->energy_range};
+    const char* nm[4] = {"pitch_shift", "pitch_range", "energy_shift", "energy_range"};
+    for (int i = 0; i < 4; i++)
+        if (per_utt[i])
+            for (int b = 0; b < B; b++) {
+                const float v = per_utt[i][b];
+                if (!std::isfinite(v)) fail(ZVX_E_INVALID, "prosody %s[%d] is not finite", nm[i], b);
+                if ((i & 1) && (v < 0.f || v > 4.f)) fail(ZVX_E_INVALID, "prosody %s[%d]=%g outside [0, 4]", nm[i], b, v);
+            }
+    const float* tg[2] = {p->pitch_target, p->energy_target};
+    for (int i = 0; i < 2; i++)
+        if (tg[i])
+            for (int b = 0; b < B; b++)
+                for (int t = 0; t < T[b]; t++) {
+                    const float v = tg[i][(size_t)b * Tmax + t];
+                    if (v == v && !(v >= 0.f && v <= 1.f)) fail(ZVX_E_INVALID, "prosody %s_target[%d][%d]=%g is neither NaN nor in [0, 1]", i ? "energy" : "pitch", b, t, v);
+                }
+    if (p->dur_scale_q16)
+        for (int b = 0; b < B; b++)
+            for (int t = 0; t < T[b]; t++) {
+                const int q = p->dur_scale_q16[(size_t)b * Tmax + t];
+                if (q < 4096 || q > 1048576) fail(ZVX_E_INVALID, "prosody dur_scale_q16[%d][%d]=%d outside [4096, 1048576]", b, t, q);
+            }
+}
+
 void run_encode(zvx_ctx* c, const int32_t* phoneme, const int32_t* puncts, const int32_t* duration, const int32_t* T,
-                int B, int Tmax, const float* spk, int32_t* mel_len_out, int Lmax_cap) {
+                int B, int Tmax, const float* spk, int32_t* mel_len_out, int Lmax_cap, const zvx_prosody* pros = nullptr) {
     const int H = c->H;
     c->have_features = false; c->have_mel = false;
     if (c->stream != c->front_stream) c->front_dirty_main = true;
@@ -902,13 +936,23 @@ void run_encode(zvx_ctx* c, const int32_t* phoneme, const int32_t* puncts, const
             if (pu < 0 || pu >= c->n_punct_rows) fail(ZVX_E_INVALID, "punct id %d out of range at [%d][%d]", pu, b, t);
         }
     }
+    if (pros) check_prosody(pros, T, B, Tmax);
     c->B = B; c->Tmax = Tmax; c->have_features = false; c->have_mel = false;
     const size_t nid = (size_t)B * Tmax;
-    // the call's small inputs (ids, lengths, forced durations, speaker embeddings) travel as ONE upload
+    // the call's small inputs (ids, lengths, forced durations, speaker embeddings, the prosody controls present) travel as ONE upload
+    std::vector<std::string> planes = {"in.phoneme", "in.puncts", "in.duration", "in.T", "in.spk"};
+    // prosody: one plane for the four per-utterance vectors ([4][B] floats), one per per-phoneme array given
+    const void* pros_src[3] = {pros ? pros->pitch_target : nullptr, pros ? pros->energy_target : nullptr, pros ? pros->dur_scale_q16 : nullptr};
+    int pros_plane[3] = {-1, -1, -1};
+    if (pros) {
+        planes.push_back("in.pros_utt");
+        const char* nm[3] = {"in.pitch_target", "in.energy_target", "in.dur_scale"};
+        for (int i = 0; i < 3; i++) if (pros_src[i]) { pros_plane[i] = (int)planes.size(); planes.push_back(nm[i]); }
+    }
+    const size_t np = planes.size();
     size_t in_stride = 0;
-    char* in_base = c->carve("in.all", {"in.phoneme", "in.puncts", "in.duration", "in.T", "in.spk"},
-                             std::max(std::max(nid, (size_t)B), (size_t)B * H) * 4, &in_stride);
-    c->in_stage.resize(in_stride * 5 / sizeof(int));
+    char* in_base = c->carve("in.all", planes, std::max(std::max(nid, (size_t)B * 4), (size_t)B * H) * 4, &in_stride);
+    c->in_stage.resize(in_stride * np / sizeof(int));
     {
         int* hs = c->in_stage.data();
         const size_t st = in_stride / sizeof(int);
@@ -916,12 +960,27 @@ void run_encode(zvx_ctx* c, const int32_t* phoneme, const int32_t* puncts, const
         if (duration) memcpy(hs + 2 * st, duration, nid * 4);
         memcpy(hs + 3 * st, T, (size_t)B * 4);
         memcpy(hs + 4 * st, spk, (size_t)B * H * 4);
-        c->upload(in_base, hs, in_stride * 5);
+        if (pros) {
+            const float* per_utt[4] = {pros->pitch_shift, pros->pitch_range, pros->energy_shift, pros->energy_range};
+            for (int i = 0; i < 4; i++) if (per_utt[i]) memcpy(hs + 5 * st + (size_t)i * B, per_utt[i], (size_t)B * 4);
+            for (int i = 0; i < 3; i++) if (pros_src[i]) memcpy(hs + pros_plane[i] * st, pros_src[i], nid * 4);
+        }
+        c->upload(in_base, hs, in_stride * np);
     }
     int* ph_d = (int*)in_base; int* pu_d = (int*)(in_base + in_stride);
     int* dur_in = duration ? (int*)(in_base + 2 * in_stride) : nullptr;
     int* T_d = (int*)(in_base + 3 * in_stride);
     float* spk_d = (float*)(in_base + 4 * in_stride);
+    // device views of the controls (NULL: neutral)
+    const float* pros_utt = pros ? (const float*)(in_base + 5 * in_stride) : nullptr;
+    const float* p_shift = (pros && pros->pitch_shift) ? pros_utt : nullptr;
+    const float* p_range = (pros && pros->pitch_range) ? pros_utt + B : nullptr;
+    const float* e_shift = (pros && pros->energy_shift) ? pros_utt + 2 * B : nullptr;
+    const float* e_range = (pros && pros->energy_range) ? pros_utt + 3 * B : nullptr;
+    const float* p_tgt = pros_src[0] ? (const float*)(in_base + pros_plane[0] * in_stride) : nullptr;
+    const float* e_tgt = pros_src[1] ? (const float*)(in_base + pros_plane[1] * in_stride) : nullptr;
+    const int* dq = pros_src[2] ? (const int*)(in_base + pros_plane[2] * in_stride) : nullptr;
+    const bool pitch_ctl = p_shift || p_range || p_tgt, energy_ctl = e_shift || e_range || e_tgt;
 
     c->stage_begin(ZVX_T_ENCODER);
     c->tag = "encoder";
@@ -982,21 +1041,31 @@ void run_encode(zvx_ctx* c, const int32_t* phoneme, const int32_t* puncts, const
         variance_predictor(c, "dur", x, B, Tmax, T_d, logd);                                           // fs2.py:663
         variance_predictor(c, "pitch", x, B, Tmax, T_d, pitch);                                        // fs2.py:665-668
     }
-    launch_bucket_embed_add(pitch, c->pf("va.pitch_emb"), c->n_bins, x, H, H, pidx, B, Tmax, T_d, c->stream);
+    // the energy predictor reads x with the CONTROLLED pitch embedding (fs2.py:665-671)
+    if (pitch_ctl) c->timed(0, (double)nid * H * 12.0, [&] { launch_bucket_embed_add_ctl(pitch, p_shift, p_range, p_tgt, c->pf("va.pitch_emb"), c->n_bins, x, H, H, pidx, B, Tmax, T_d, c->stream); }, "bucket_embed_add_ctl");
+    else launch_bucket_embed_add(pitch, c->pf("va.pitch_emb"), c->n_bins, x, H, H, pidx, B, Tmax, T_d, c->stream);
     variance_predictor(c, "energy", x, B, Tmax, T_d, energy);                                          // fs2.py:669-672
-    launch_bucket_embed_add(energy, c->pf("va.energy_emb"), c->n_bins, x, H, H, eidx, B, Tmax, T_d, c->stream);
+    if (energy_ctl) c->timed(0, (double)nid * H * 12.0, [&] { launch_bucket_embed_add_ctl(energy, e_shift, e_range, e_tgt, c->pf("va.energy_emb"), c->n_bins, x, H, H, eidx, B, Tmax, T_d, c->stream); }, "bucket_embed_add_ctl");
+    else launch_bucket_embed_add(energy, c->pf("va.energy_emb"), c->n_bins, x, H, H, eidx, B, Tmax, T_d, c->stream);
     c->stage_end(ZVX_T_VARIANCE);
 
     c->stage_begin(ZVX_T_LENREG);
     c->tag = "lenreg";
     int* dur = (int*)(va_base + 5 * va_stride); int* cum = c->ibuf("va.cum", nid); int* ml = c->ibuf("va.mel_len", B);
-    launch_durations(dur_in, logd, dur, cum, ml, B, Tmax, T_d, c->stream);
+    if (dq) c->timed(0, (double)nid * 16.0, [&] { launch_durations_q16(dur_in, logd, dq, dur, cum, ml, B, Tmax, T_d, c->stream); }, "durations_q16");
+    else launch_durations(dur_in, logd, dur, cum, ml, B, Tmax, T_d, c->stream);
     c->mel_len_host.resize(B);
     if (duration) {
-        // forced durations: the mel lengths are their sums (same clamps as k_durations) -- nothing to wait for
+        // forced durations: the mel lengths are their sums (same clamps as k_durations; with dur_scale_q16 the same Q16 rule as
+        // k_durations_q16) -- nothing to wait for
+        const int32_t* q = pros ? pros->dur_scale_q16 : nullptr;
         for (int b = 0; b < B; b++) {
             long long sum = 0;
-            for (int t = 0; t < T[b]; t++) sum += std::min(std::max(duration[(size_t)b * Tmax + t], 0), 65536);
+            for (int t = 0; t < T[b]; t++) {
+                const long long d = std::min(std::max(duration[(size_t)b * Tmax + t], 0), 65536);
+                sum += q ? d * q[(size_t)b * Tmax + t] : d;
+            }
+            if (q) sum = (sum + 32768) >> 16;
             c->mel_len_host[b] = (int)std::min(sum, 0x7fffffffLL);
         }
     } else {
@@ -2073,9 +2142,15 @@ zvx_status zvx_melspec(zvx_ctx* c, const float* wav, const int32_t* nsamples, in
 
 zvx_status zvx_encode(zvx_ctx* c, const int32_t* phoneme, const int32_t* puncts, const int32_t* duration, const int32_t* T,
                       int B, int Tmax, const float* spk, int32_t* mel_len, float* log_duration, float* pitch, float* energy) {
+    return zvx_encode_ex(c, phoneme, puncts, duration, T, B, Tmax, spk, mel_len, log_duration, pitch, energy, nullptr);
+}
+
+zvx_status zvx_encode_ex(zvx_ctx* c, const int32_t* phoneme, const int32_t* puncts, const int32_t* duration, const int32_t* T,
+                         int B, int Tmax, const float* spk, int32_t* mel_len, float* log_duration, float* pitch, float* energy,
+                         const zvx_prosody* prosody) {
     return guarded(c, [&] {
         if (!phoneme || !puncts || !T || !spk) fail(ZVX_E_INVALID, "zvx_encode: NULL input");
-        run_encode(c, phoneme, puncts, duration, T, B, Tmax, spk, mel_len, 0);
+        run_encode(c, phoneme, puncts, duration, T, B, Tmax, spk, mel_len, 0, prosody);
         const size_t nid = (size_t)B * Tmax;
         if (log_duration) HIPCHK(hipMemcpyAsync(log_duration, c->fbuf("va.logd", nid), nid * 4, hipMemcpyDeviceToHost, c->stream));
         if (pitch) HIPCHK(hipMemcpyAsync(pitch, c->fbuf("va.pitch", nid), nid * 4, hipMemcpyDeviceToHost, c->stream));
@@ -2137,12 +2212,19 @@ zvx_status zvx_vocode_mel(zvx_ctx* c, const float* mel, const int32_t* P, int B,
 zvx_status zvx_synthesize(zvx_ctx* c, const int32_t* phoneme, const int32_t* puncts, const int32_t* duration, const int32_t* T,
                           int B, int Tmax, const float* spk, const int32_t* pad_to, int Lmax_cap, void* wav, int64_t wav_stride,
                           int32_t* mel_len, float* mel_out, int Lstride, float* log_duration, int flags) {
+    return zvx_synthesize_ex(c, phoneme, puncts, duration, T, B, Tmax, spk, pad_to, Lmax_cap, wav, wav_stride, mel_len, mel_out, Lstride,
+                             log_duration, flags, nullptr);
+}
+
+zvx_status zvx_synthesize_ex(zvx_ctx* c, const int32_t* phoneme, const int32_t* puncts, const int32_t* duration, const int32_t* T,
+                             int B, int Tmax, const float* spk, const int32_t* pad_to, int Lmax_cap, void* wav, int64_t wav_stride,
+                             int32_t* mel_len, float* mel_out, int Lstride, float* log_duration, int flags, const zvx_prosody* prosody) {
     return guarded(c, [&] {
         const bool host_async = flags & ZVX_HOST_ASYNC;
         if (!phoneme || !puncts || !T || !spk || (!wav && !host_async)) fail(ZVX_E_INVALID, "zvx_synthesize: NULL input");
         if (host_async && ((mel_out && !(flags & ZVX_DEVICE_OUT)) || log_duration)) fail(ZVX_E_INVALID, "zvx_synthesize: ZVX_HOST_ASYNC takes no host mel / log_duration output (they would make the call wait)");
         auto front_end = [&] {
-            run_encode(c, phoneme, puncts, duration, T, B, Tmax, spk, mel_len, Lmax_cap);
+            run_encode(c, phoneme, puncts, duration, T, B, Tmax, spk, mel_len, Lmax_cap, prosody);
             if (log_duration) HIPCHK(hipMemcpyAsync(log_duration, c->fbuf("va.logd", 0), (size_t)B * Tmax * 4, hipMemcpyDeviceToHost, c->stream));
             int* L_d = c->upload_ints("dec.L", c->mel_len_host.data(), B);
             run_decode(c, c->fbuf("features", 0), c->fbuf("in.spk", 0), L_d, B, c->Lmax);
@@ -2436,6 +2518,7 @@ int zvx_kernel_stats(zvx_ctx* c, zvx_kernel_stat* out, int max_out) {
     guarded(c, [&] {
         c->sync();
         for (auto& s : c->stats) if (s.launches > 0 && n < max_out) out[n++] = s;
+        for (auto& kv : c->namedstats) if (kv.second.launches > 0 && n < max_out) out[n++] = kv.second;
     });
     return n;
 }
@@ -2451,7 +2534,7 @@ int zvx_tag_stats(zvx_ctx* c, zvx_kernel_stat* out, int max_out) {
 }
 
 zvx_status zvx_reset_stats(zvx_ctx* c) {
-    return guarded(c, [&] { c->sync(); for (auto& s : c->stats) { s.launches = 0; s.ms = s.flops = s.bytes = 0; } c->tagstats.clear(); });
+    return guarded(c, [&] { c->sync(); for (auto& s : c->stats) { s.launches = 0; s.ms = s.flops = s.bytes = 0; } c->tagstats.clear(); c->namedstats.clear(); });
 }
 
 }  // extern "C"

@@ -284,6 +284,14 @@ void launch_bucket_embed_add(const float* pred, const float* table, int nbins, f
 void launch_durations(const int* forced, const float* logd, int* dur, int* cum, int* mel_len, int B, int Tmax,
                       const int* T, hipStream_t s);
 
+// prosody control (include/zvx.h, zvx_prosody): the bucketise + embedding add on v = (p + (range[b]-1)*(p - mean_b(p))) + shift[b],
+// replaced by target[b][t] where that is not NaN (NULL pointers: neutral)
+void launch_bucket_embed_add_ctl(const float* pred, const float* shift, const float* range, const float* target, const float* table,
+                                 int nbins, float* x, int ldx, int C, int* idx_out, int B, int Tmax, const int* T, hipStream_t s);
+// launch_durations with per-phoneme Q16 factors q[b][t] applied to the running sum: cum = (sum d*q + 2^15) >> 16, dur its differences
+void launch_durations_q16(const int* forced, const float* logd, const int* q, int* dur, int* cum, int* mel_len, int B, int Tmax,
+                          const int* T, hipStream_t s);
+
 // length regulator (fs2.py:447-455): feats[b][l][:] = x[b][src(l)][:]; optional positional table add
 // into a second output of dtype dt (decoder input): dec[b][l][:] = feats + pe[l]
 void launch_length_regulate(const float* x, int ldx, const int* cum, const int* T, const int* mel_len,

@@ -21,6 +21,11 @@ def main():
     ap.add_argument("--iter", type=int, default=1)
     ap.add_argument("--refmel-frames", type=int, default=258, help="synthetic 3 s reference mel for the speaker encoder")
     ap.add_argument("--wav-filename", default=None)
+    ap.add_argument("--speed", type=float, default=1.0, help="speaking-rate factor (2.0: twice as fast)")
+    ap.add_argument("--pitch-shift", type=float, default=0.0, help="added to the normalised pitch prediction")
+    ap.add_argument("--pitch-range", type=float, default=1.0, help="pitch spread about the utterance mean (0: flat, 1: as predicted)")
+    ap.add_argument("--energy-shift", type=float, default=0.0)
+    ap.add_argument("--energy-range", type=float, default=1.0)
     args = ap.parse_args()
 
     modelcfg, synth = ZeroVoxTTS.load_model(args.model, args.meldec_model, infer_device=args.infer_device, precision=args.precision)
@@ -31,7 +36,8 @@ def main():
     rtf, warmup = [], 10
     for i in range(args.iter):
         t0 = time.time()
-        wav, phoneme, length = synth.tts(args.text, spkemb)
+        wav, phoneme, length = synth.tts(args.text, spkemb, speed=args.speed, pitch_shift=args.pitch_shift, pitch_range=args.pitch_range,
+                                         energy_shift=args.energy_shift, energy_range=args.energy_range)
         elapsed = time.time() - t0
         wav_len = wav.shape[0] / sr
         print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")

@@ -116,9 +116,10 @@ class ZeroVox:
         lens = np.full(x.shape[0], x.shape[1], np.int32)
         return self._ctx.spkemb(x, lens)[:, None, :]
 
-    def inference_ex(self, x, style_embed, normalize_before=True, force_duration=False):
+    def inference_ex(self, x, style_embed, normalize_before=True, force_duration=False, prosody=None):
         """model.py:308-347.  x = {"phoneme" [1,T], "puncts" [1,T], "duration" [1,T]|None}; returns
-        (wav[:mel_len*hop], mel_len, log_duration [1,T], mel [n_mels, mel_len]).  Batch-1 like the reference."""
+        (wav[:mel_len*hop], mel_len, log_duration [1,T], mel [n_mels, mel_len]).  Batch-1 like the reference.
+        prosody: None, a prosody.Prosody or a dict of Prosody.create keywords (speed, pitch / energy shift and range, targets)."""
         phoneme = np.asarray(x["phoneme"], np.int32)
         puncts = np.asarray(x["puncts"], np.int32)
         if phoneme.ndim != 2 or phoneme.shape[0] != 1:
@@ -126,7 +127,7 @@ class ZeroVox:
         T = np.array([phoneme.shape[1]], np.int32)
         dur = np.asarray(x["duration"], np.int32) if (force_duration and x.get("duration") is not None) else None
         spk = np.asarray(style_embed, np.float32).reshape(1, -1)
-        mel_len, logd, _, _ = self._ctx.encode(phoneme, puncts, T, spk, dur)
+        mel_len, logd, _, _ = self._ctx.encode(phoneme, puncts, T, spk, dur, prosody=prosody)
         ml = int(mel_len[0])
         if ml < 2:
             # the reference raises inside InstanceNorm1d / conv stacks for degenerate lengths
@@ -174,7 +175,7 @@ class ZeroVox:
         vocoder, which holds the chip at its power limit.  Measured at 32 x 128 phonemes with the waveforms delivered to host memory
         (tools/two_contexts.py): 24.5 ms per batch sequentially, 23.5 with two in flight, 22.5 with three (device-resident outputs
         through the C-ABI: 23.4 -> 21.4 with two).  `batches` yields dicts of synthesize_batch arguments (phoneme, puncts, T, style_embed[, duration, pad_to,
-        Lmax_cap]); results come back IN ORDER, each bit-identical to synthesize_batch on the same arguments."""
+        Lmax_cap, prosody]); results come back IN ORDER, each bit-identical to synthesize_batch on the same arguments."""
         from collections import deque
         from concurrent.futures import ThreadPoolExecutor
         n = max(1, int(in_flight))
@@ -214,7 +215,8 @@ class ZeroVox:
             pad_to = kw.get("pad_to")
             if pad_to is None:
                 pad_to = np.full(B, 689, np.int32)
-            return c.synthesize(kw["phoneme"], kw["puncts"], kw["T"], kw["style_embed"], kw.get("duration"), pad_to, want_mel, kw.get("Lmax_cap", 0))
+            return c.synthesize(kw["phoneme"], kw["puncts"], kw["T"], kw["style_embed"], kw.get("duration"), pad_to, want_mel, kw.get("Lmax_cap", 0),
+                                prosody=kw.get("prosody"))
 
         with ThreadPoolExecutor(max_workers=n) as ex:
             pending = deque()
@@ -225,12 +227,13 @@ class ZeroVox:
             while pending:
                 yield pending.popleft().result()
 
-    def synthesize_batch(self, phoneme, puncts, T, style_embed, duration=None, pad_to=None, want_mel=True, Lmax_cap=0):
+    def synthesize_batch(self, phoneme, puncts, T, style_embed, duration=None, pad_to=None, want_mel=True, Lmax_cap=0, prosody=None):
         """B independent utterances in one launch sequence; each equals a batch-1 ``inference_ex`` call with
-        ``_min_mel_len == pad_to[b]`` (default: the fresh-model value 689).  Padded [B, Tmax] id arrays."""
+        ``_min_mel_len == pad_to[b]`` (default: the fresh-model value 689).  Padded [B, Tmax] id arrays.  prosody: as for inference_ex,
+        per utterance ([B] / [B, Tmax] controls)."""
         B = np.asarray(phoneme).shape[0]
         if pad_to is None:
             pad_to = np.full(B, 689, np.int32)
         if self._streaming:
             raise RuntimeError("synthesize_batch while a synthesize_batches generator is active: the context is not re-entrant")
-        return self._ctx.synthesize(phoneme, puncts, T, style_embed, duration, pad_to, want_mel, Lmax_cap)
+        return self._ctx.synthesize(phoneme, puncts, T, style_embed, duration, pad_to, want_mel, Lmax_cap, prosody=prosody)

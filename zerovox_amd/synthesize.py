@@ -112,9 +112,17 @@ class ZeroVoxTTS:
             print(f"Phoneme IDs      : {phone_ids}\nPunct IDs        : {punct_ids}")
         return phone_ids, punct_ids
 
-    def tts_ex(self, text: str, spkemb, duration=None):
+    @staticmethod
+    def _prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range):
+        """the keyword scalars as Prosody.create keywords, or None when all are at their defaults (the uncontrolled call)"""
+        kw = dict(speed=speed, pitch_shift=pitch_shift, pitch_range=pitch_range, energy_shift=energy_shift, energy_range=energy_range)
+        return None if kw == dict(speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0) else kw
+
+    def tts_ex(self, text: str, spkemb, duration=None, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0):
         """-> (wav f32[N], phoneme i32[1,T], length, mel f32[n_mels, L]); empty text -> the reference's sentinel
-        (synthesize.py:213-239)."""
+        (synthesize.py:213-239).  Prosody (include/zvx.h, zvx_prosody): speed = speaking-rate factor (2.0: half the frames),
+        pitch / energy shift (in normalised predictor units) and range (spread about the utterance mean)."""
+        prosody = self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range)
         text = text.strip()
         t0 = time.time()
         phone_ids, punct_ids = self.text2phonemeids(text)
@@ -126,26 +134,30 @@ class ZeroVoxTTS:
         duration = np.array([duration], dtype=np.int32) if duration is not None else None
         t1 = time.time()
         wav, length, _, mel = self._model.inference_ex({"phoneme": phoneme, "puncts": puncts, "duration": duration},
-                                                       style_embed=spkemb, force_duration=duration is not None)
+                                                       style_embed=spkemb, force_duration=duration is not None, prosody=prosody)
         if self._verbose:
             print(f"tts timing stats: g2p={t1 - t0}s, synth={time.time() - t1}s")
         return wav, phoneme, length, mel
 
-    def tts(self, text: str, spkemb):
-        wav, phoneme, length, _ = self.tts_ex(text=text, spkemb=spkemb)
+    def tts(self, text: str, spkemb, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0):
+        wav, phoneme, length, _ = self.tts_ex(text=text, spkemb=spkemb, speed=speed, pitch_shift=pitch_shift, pitch_range=pitch_range,
+                                              energy_shift=energy_shift, energy_range=energy_range)
         return wav, phoneme, length
 
-    def tts_stream(self, text: str, spkemb, chunk_frames=64, chunks_per_call=1):
+    def tts_stream(self, text: str, spkemb, chunk_frames=64, chunks_per_call=1, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0,
+                   energy_shift=0.0, energy_range=1.0):
         """Streaming variant of ``tts`` (not in the reference): encoder + mel decoder run once, the vocoder
         runs chunk by chunk (16-frame halo), yielding float32 waveform pieces that concatenate to ``tts(text, spkemb)[0]``
         up to the reference's `_min_mel_len` zero-padding of short utterances."""
+        prosody = self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range)
         text = text.strip()
         phone_ids, punct_ids = self.text2phonemeids(text)
         if not phone_ids:
             return
         phoneme, puncts = np.array([phone_ids], np.int32), np.array([punct_ids], np.int32)
         ctx = self._model.ctx
-        mel_len, _, _, _ = ctx.encode(phoneme, puncts, np.array([len(phone_ids)], np.int32), np.asarray(spkemb, np.float32).reshape(1, -1))
+        mel_len, _, _, _ = ctx.encode(phoneme, puncts, np.array([len(phone_ids)], np.int32), np.asarray(spkemb, np.float32).reshape(1, -1),
+                                   prosody=prosody)
         ml = int(mel_len[0])
         if ml < 2:
             raise ValueError(f"predicted mel length {ml} is too short to synthesise")
