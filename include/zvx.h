@@ -73,16 +73,18 @@ const char* zvx_last_error(const zvx_ctx* ctx);
  *   LDS-resident intermediate; same arithmetic per convolution, ~3x the time: a debug mode) and every 16-bit tensor it writes is
  *   scanned for clamped values.  This key drains the context and returns how many were seen since the switch was last set: 0 means no
  *   clamp engaged on the inputs run so far -- the check to make once on a real checkpoint (the reference, fp32, has no such failure
- *   mode).  "f16_sat_check" returns the switch. */
+ *   mode).
+ * Every key of zvx_set_int returns its current value. */
 int64_t    zvx_get_int(const zvx_ctx* ctx, const char* key);
 /* "profile" 0/1/2 (0 off, 1 per-stage events, 2 + per-GEMM-launch events); "profile_only" variant id (-1 = all);
  * "shape_log" 0/1 (one stderr line per timed launch); "max_frames" hard cap on a predicted mel length (default 2^18:
  * the reference has none, fs2.py:678-681 -- a garbage log-duration must not drive an allocation -> ZVX_E_BUFFER).
  * "f16_sat_check" 0/1: the saturation audit of the half mode (see zvx_get_int "f16_sat_events"); setting it (re)zeroes the counter.
- * Every other key is an A/B switch of a scheduling / tiling / arithmetic choice (INTEGRATION.md has the table: "enc_split",
- * "front_overlap", "front_prio", "dec_flat", "dec_sc_fuse", "dec_f16", "dec_y16", "dec_qkv", "voc_f16", "voc_f16_stages", "stagefuse", "rb2fuse", "pairstream", "resstream", "slab_small", "slab_flat",
- * "poison_pads", "spk_pool_fuse", "spk_s2_fuse", ...);
- * all of them live in the context.  Unknown keys: ZVX_E_INVALID. */
+ * Every other key is an A/B switch of a scheduling / tiling / arithmetic choice (INTEGRATION.md has the table and each key's values:
+ * "enc_split", "attn_f32", "flash", "front_overlap", "va_overlap_maxb", "dec_f16", "dec_flat", "dec_sc_fuse", "norm_fuse_maxb", "voc_f16",
+ * "voc_f16_stages", "voc_overlap_maxb", "voc_overlap_frames", "stagefuse", "rb2fuse", "resstream", "rs_seg_min", "pairstream", "slab_small",
+ * "slab_flat", "spk_pool_fuse", "spk_s2_fuse", "poison_pads", "rs_prof");
+ * all of them live in the context.  Unknown keys and values outside a key's set: ZVX_E_INVALID. */
 zvx_status zvx_set_int(zvx_ctx* ctx, const char* key, int64_t value);
 
 /* Speaker encoder: ref_mels [B][Tmax][80] log-mels, lens[B] frames -> out [B][hidden], L2-normalised.

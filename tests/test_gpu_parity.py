@@ -598,6 +598,28 @@ def test_error_behaviour():
         _lib.Context(man.replace("tensor enc.emb ", "tensor enc.embx "), blob, 0).encode(ph, pu, T, spk, dur)
 
 
+def test_switches_reject_retired_keys_and_values_and_read_back():
+    """zvx_set_int rejects the retired A/B switches and retired values of kept ones like an unknown key, leaving the switch as it
+    was; zvx_get_int returns the live value of a switch."""
+    cfg, sd = tts_sd("styletts")
+    h, hsd = voc_sd("tiny")
+    man, blob = pack.pack_model(cfg, sd, h, hsd, "f32")
+    ctx = _lib.Context(man, blob, 0)
+    try:
+        for key, value in (("voc_chunk", 4), ("rs_opt", 3), ("front_prio", 1), ("dec_y16", 1), ("dec_qkv", 1), ("pairstream", 4),
+                           ("pairstream", 2), ("slab_small", 16), ("slab_small", 2 | 64), ("dec_sc_fuse", 2), ("max_frames", 0)):
+            with pytest.raises(_lib.ZvxError) as e:
+                ctx.set_int(key, value)
+            assert e.value.code == _lib.ZVX_E_INVALID, (key, value)
+        for key, value, default in (("pairstream", 3, 1), ("slab_small", 2 | 32, 2), ("rs_seg_min", 512, 0),
+                                    ("voc_f16_stages", 0b11011, -1), ("front_overlap", 0, 1), ("max_frames", 4096, 1 << 18)):
+            assert ctx.get_int(key) == default, key
+            ctx.set_int(key, value)
+            assert ctx.get_int(key) == value, key
+    finally:
+        ctx.close()
+
+
 def test_host_api_tts_ex_roundtrip():
     """ZeroVoxTTS mirror (synthesize.py:213-243): forced durations, stateful _min_mel_len, sentinel."""
     from zerovox_amd.synthesize import ZeroVoxTTS

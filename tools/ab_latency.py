@@ -1,5 +1,5 @@
 """Single-request sizing A/B: vocoder alone (B = 1, 448 / 1024 frames) and the whole 64-phoneme utterance under
-   rs_seg_min (streaming-ResBlock segment floor) and pairstream modes 1 (decline small jobs) / 3 (1024-row segments) / 4 (256-row segments);
+   rs_seg_min (streaming-ResBlock segment floor), the single-request tile and overlap switches, pairstream 1 (decline small jobs);
    bit-equality of every variant against the default.   python tools/ab_latency.py"""
 import os, sys, time
 import numpy as np
@@ -15,8 +15,7 @@ variants = (("round-2 sizing", {"rs_seg_min": -1, "pairstream": 1, "slab_small":
             ("+ one-launch InstanceNorm", {"rs_seg_min": 0, "pairstream": 1, "slab_small": 2, "norm_fuse_maxb": 1 << 20}),
             ("+ duration beside pitch predictor", {"rs_seg_min": 0, "pairstream": 1, "slab_small": 2, "norm_fuse_maxb": 1 << 20, "va_overlap_maxb": 1 << 20}),
             ("+ ResBlocks side by side, B <= 2", {"rs_seg_min": 0, "pairstream": 1, "slab_small": 2, "norm_fuse_maxb": 1 << 20, "va_overlap_maxb": 1 << 20, "voc_overlap_maxb": 2}),
-            ("+ ResBlocks side by side (default)", {"rs_seg_min": 0, "pairstream": 1, "slab_small": 2, "norm_fuse_maxb": 1 << 20, "va_overlap_maxb": 1 << 20, "voc_overlap_maxb": 1 << 20}),
-            ("+ pair kernel, 256-row segments", {"rs_seg_min": 0, "pairstream": 4, "slab_small": 2, "norm_fuse_maxb": 1 << 20, "va_overlap_maxb": 1 << 20, "voc_overlap_maxb": 1 << 20}))
+            ("+ ResBlocks side by side (default)", {"rs_seg_min": 0, "pairstream": 1, "slab_small": 2, "norm_fuse_maxb": 1 << 20, "va_overlap_maxb": 1 << 20, "voc_overlap_maxb": 1 << 20}))
 for (B, P) in ((1, 448), (1, 1024), (2, 448), (4, 448)):
     mel = rng.standard_normal((B, P, 80)).astype(np.float32); L = np.full(B, P, np.int32)
     ref = None

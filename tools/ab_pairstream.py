@@ -18,7 +18,7 @@ for (B, Pmax) in ((3, 23), (5, 70), (2, 300), (1, 9), (1, 1), (32, 40), (1, 1100
     mel = np.zeros((B, Pmax, 80), np.float32)
     for b in range(B): mel[b, :P[b]] = rng.standard_normal((P[b], 80)).astype(np.float32)
     ctx.set_int("pairstream", -1); w0 = ctx.vocode_mel(mel, P)
-    for mode in (3, 4):
+    for mode in (3,):
         ctx.set_int("pairstream", mode); w1 = ctx.vocode_mel(mel, P)
         same = np.array_equal(w0, w1)
         d = np.abs(w0 - w1)

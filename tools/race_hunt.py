@@ -14,7 +14,7 @@ ph, pu, T, spk, dur = synthetic.batch(32, 128, 192, "const7")
 pad_to = np.full(32, 896, np.int32)
 r = ctx.synthesize(ph, pu, T, spk, dur, pad_to, want_mel=True)
 mel0, P = r["mel"], r["mel_len"]
-defaults = (("attn_f32", 1), ("resstream", 1), ("pairstream", 1), ("rs_opt", 3))
+defaults = (("attn_f32", 1), ("resstream", 1), ("pairstream", 1))
 def reset(sets):
     for k, v in defaults: ctx.set_int(k, v)
     for k, v in sets.items(): ctx.set_int(k, v)

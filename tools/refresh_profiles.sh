@@ -51,7 +51,6 @@ if [ "$QUICK" = "extra" ]; then
   profile_workload v3 --vocoder v3
   python $ROOT/bench.py --full --vocoder v3 --no-cpu-baseline > $OUT/bench_v3.json 2> $OUT/bench_v3.err
   python $ROOT/bench.py --full --vocoder v3 --set rb2fuse=0 --no-cpu-baseline > $OUT/bench_v3_unfused.json 2> $OUT/bench_v3_unfused.err          # A/B (round 6): every convolution of a ResBlock2 its own launch
-  python $ROOT/bench.py --full --decoder fastspeech2 --set dec_y16=0 --no-cpu-baseline > $OUT/bench_fs2dec_y32.json 2> $OUT/bench_fs2dec_y32.err  # A/B (round 6): f32 pre-norm sums
   profile_workload b1_t64 --batch 1 --phonemes 64
   python $ROOT/bench.py --full --batch 1 --phonemes 64 --no-cpu-baseline > $OUT/bench_b1_t64.json 2> $OUT/bench_b1_t64.err
   profile_workload cfg4_b1 --config 4 --batch 1

@@ -10,7 +10,6 @@ ctx = _lib.Context(man, blob, 0)
 rng = np.random.default_rng(5)
 mel = rng.standard_normal((32, 896, 80)).astype(np.float32); P = np.full(32, 896, np.int32)
 ctx.set_int("rs_prof", 1)
-if len(sys.argv) > 1: ctx.set_int("rs_opt", int(sys.argv[1]))
 for _ in range(2): ctx.vocode_mel(mel, P)
 names = ["stage 3 k3", "k7a", "k7b", "k11a", "k11b", "stage 4 k3", "k7", "k11a", "k11b"]
 for rbi, t0s in ((6, [0]), (7, [0, 2]), (8, [0, 2]), (9, [0]), (10, [0]), (11, [0])):

@@ -1080,20 +1080,13 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN * WGPC / 4) void conv2d_persi
         }
         asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
         const int tn = tile_of(++r);
-#ifdef C2D_CUT
-        if (tn < ntiles && !(a.slab_small & 64)) request(tn);
-#else
         if (tn < ntiles) request(tn);
-#endif
 
         f32x16 acc[1][TM];
 #pragma unroll
         for (int j = 0; j < TM; j++)
 #pragma unroll
             for (int e = 0; e < 16; e++) acc[0][j][e] = 0.f;
-#ifdef C2D_CUT
-        if (!(a.slab_small & 128))
-#endif
 #pragma unroll
         for (int tp = 0; tp < NT; tp++) {
             const unsigned char* rowp = slab + (xrow0 + a.dv[tp]) * PITCH_ + koff;
@@ -1105,9 +1098,6 @@ __global__ __launch_bounds__(WM * WN * 64, WM * WN * WGPC / 4) void conv2d_persi
                     acc[0][j] = mfma16<false>(w[tp][kk], xf, acc[0][j]);
                 }
         }
-#ifdef C2D_CUT
-        if (!(a.slab_small & 256))
-#endif
         {
             unsigned short* const ob = (unsigned short*)a.out + (long)b * a.o_bs + wc * 32 + (EC_LDS ? 4 * (lane >> 5) : 0);
             const int row0 = m0 + wr * (BM / WM) + (lane & 31);
@@ -1956,7 +1946,7 @@ int launch_resfuse(GemmArgs a, hipStream_t stream) {
             p.accum = a.accum; p.a_bs = a.a_bs; p.lda = a.lda; p.accum_mode = a.accum ? a.accum_mode : 0;
             p.slope1 = a.slope1; p.res_inv_slope = a.res_inv_slope; p.out_scale = a.out_scale; p.slope = a.act == ACT_LRELU ? a.slope : 1.f;
             p.f16 = a.dtype == DT_F16;
-            p.len = a.out_len; p.M = a.M; p.nbatch = a.nbatch; p.force = a.no_pairstream >= 2 ? a.no_pairstream - 1 : 0;       // 2 -> force, 3 -> force with short segments
+            p.len = a.out_len; p.M = a.M; p.nbatch = a.nbatch; p.force = a.no_pairstream == 2;
             if (launch_pairstream(p, stream, g_dry_run, g_dry_run ? nullptr : g_ev_start, g_ev_stop)) return 23;
         }
     }
@@ -2078,9 +2068,9 @@ static int launch_convslab(GemmArgs a, hipStream_t stream) {
         // maps whose rows fill 256-row tiles badly (the last level of the speaker encoder: 10 x 34 = 340 positions are 1.33 tiles of
         // 256 -- a third of the matrix steps on padding -- and 2.66 of 128): 128-row tiles of the same kernel (same K order per output
         // row: bit-identical): config 5 6.44 -> 6.32 ms.  The level before it (1340 positions: 9 % padding against 5 %) measured 1.85 -> 1.88 ms with
-        // 128-row tiles: not taken.  slab_small bit 10: off (A/B)
+        // 128-row tiles: not taken.
         const int pad256 = ((a.M + 255) / 256) * 256, pad128 = ((a.M + 127) / 128) * 128;
-        if (!(a.slab_small & 1024) && (long)pad256 * 100 > (long)pad128 * 115) {
+        if ((long)pad256 * 100 > (long)pad128 * 115) {
             dim3 g128((a.N / 128) * (pad128 / 128), a.nbatch);
             size_t lds128 = ((size_t)(128 + hl + hr) * SLAB_PITCH + 1023) & ~(size_t)1023;
             const size_t stage128 = (size_t)4 * 32 * (2 * 128 + 16);
@@ -2192,15 +2182,14 @@ static int launch_convslab(GemmArgs a, hipStream_t stream) {
         // count of rounds stays, the per-utterance launch (whose partial tiles stage and store less) is kept
         const long slots = 2L * ncu;
         const long wg_utt = (long)ntn * ((a.M + bm - 1) / bm) * a.nbatch, wg_flat = (long)ntn * (((long)a.nbatch * a.bflat + bm - 1) / bm);
-        // (slab_small bit 4: A/B switch, flatten whenever possible)
-        if ((a.slab_small & 16) || (wg_flat + slots - 1) / slots < (wg_utt + slots - 1) / slots) { a.flat_win = a.bflat; a.flat_rows = a.nbatch * a.bflat; a.M = a.flat_rows; a.nbatch = 1; }
+        if ((wg_flat + slots - 1) / slots < (wg_utt + slots - 1) / slots) { a.flat_win = a.bflat; a.flat_rows = a.nbatch * a.bflat; a.M = a.flat_rows; a.nbatch = 1; }
         else a.bflat = 0;
     }
     // 256 x 128 tiles whose count quantises badly over the chip's 2 x CUs workgroup slots (N = 528 over 32 x 896 frames: 565 flattened
     // tiles = one full round and a tenth of a second one; per utterance 640 tiles, every utterance ending in a half-empty tile): 128-row
     // tiles of the same kernel (same K order per output row: bit-identical) where they take less time by the slot count -- a round of
-    // 128-row tiles counts half a round of 256-row ones.  (slab_small bit 3: A/B switch, off)
-    if (best == 1 && bflat_hint && !(a.slab_small & 8) && a.M > 256 && hl + hr <= 64) {   // (the mel decoders' launches: the vocoder's 256 x 128 launches are power-, not slot-limited)
+    // 128-row tiles counts half a round of 256-row ones.
+    if (best == 1 && bflat_hint && a.M > 256 && hl + hr <= 64) {   // (the mel decoders' launches: the vocoder's 256 x 128 launches are power-, not slot-limited)
         const long slots = 2L * ncu;
         const long t256 = (long)ntn * ((a.M + 255) / 256) * a.nbatch, t128 = (long)ntn * ((a.M + 127) / 128) * a.nbatch;
         const long eff256 = 2 * ((t256 + slots - 1) / slots), eff128 = (t128 + slots - 1) / slots;

@@ -64,9 +64,8 @@ __device__ __forceinline__ void rs_mma_steps(uint4 (&xf)[PD + 1], const uint4 (&
 // 12 waves: the conv2 roles carry the long epilogues (residual + two activations) and the last one also the HBM store phase,
 // so SIMDs 0 / 2 get {conv2_0, conv2_1, conv1_0 (+ DMA issue)} and SIMDs 1 / 3 get {conv2_2 (+ stores), conv1_1, conv1_2}.
 template <int NR, int WPR>
-__device__ __forceinline__ void role_of_wave(int w, int& role, int& sub, bool balanced) {
-    if (NR == 6 && WPR == 2 && balanced) { role = (int)((0x404023235151ull >> (4 * w)) & 15); sub = (w >> 1) & 1; }
-    else if (NR == 6 && WPR == 2) { role = (int)((0x452301453210ull >> (4 * w)) & 15); sub = w >= 6; }
+__device__ __forceinline__ void role_of_wave(int w, int& role, int& sub) {
+    if (NR == 6 && WPR == 2) { role = (int)((0x404023235151ull >> (4 * w)) & 15); sub = (w >> 1) & 1; }
     else if (NR == 4 && WPR == 2) { role = (int)((0x23013210u >> (4 * w)) & 15); sub = w >= 4; }
     else if (NR == 2 && WPR == 4) { role = (int)((0x01011010u >> (4 * w)) & 15); sub = w >> 1; }
     else { role = w % NR; sub = w / NR; }
@@ -77,8 +76,8 @@ __device__ __forceinline__ void role_of_wave(int w, int& role, int& sub, bool ba
 // distinct priorities the chains run one after the other and the epilogue of an earlier wave overlaps the MFMAs of the next;
 // the waves with the long epilogue (conv2: residual + two activations) go first.
 template <int NR, int WPR>
-__device__ __forceinline__ int prio_of_wave(int w, bool balanced) {
-    if (NR == 6 && WPR == 2) return balanced ? 3 - (w >> 2) : (int)((0x122223133131ull >> (4 * w)) & 15);
+__device__ __forceinline__ int prio_of_wave(int w) {
+    if (NR == 6 && WPR == 2) return 3 - (w >> 2);
     return w < 4 ? 2 : 1;
 }
 
@@ -454,12 +453,10 @@ __global__ __launch_bounds__(128 * NPAIR * (C / 32) * RSPLIT) void resstream_ker
 
     const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     int role, sub;
-    role_of_wave<NR, WPR>(wave, role, sub, (a.opt & 2) != 0);
+    role_of_wave<NR, WPR>(wave, role, sub);
     role = __builtin_amdgcn_readfirstlane(role); sub = __builtin_amdgcn_readfirstlane(sub);
-    if (a.opt & 1) {
-        const int pr = __builtin_amdgcn_readfirstlane(prio_of_wave<NR, WPR>(wave, (a.opt & 2) != 0));
-        if (pr == 3) __builtin_amdgcn_s_setprio(3); else if (pr == 2) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1);
-    }
+    const int pr = __builtin_amdgcn_readfirstlane(prio_of_wave<NR, WPR>(wave));
+    if (pr == 3) __builtin_amdgcn_s_setprio(3); else if (pr == 2) __builtin_amdgcn_s_setprio(2); else __builtin_amdgcn_s_setprio(1);
     if (role == 0) rs_role<C, NT, NPAIR, RSPLIT, AM, HAS_OUT, DP, H16, 0>(a, lds, lane, sub, wave);
     else if (role == 1) rs_role<C, NT, NPAIR, RSPLIT, AM, HAS_OUT, DP, H16, 1>(a, lds, lane, sub, wave);
     else if (NR > 2 && role == 2) rs_role<C, NT, NPAIR, RSPLIT, AM, HAS_OUT, DP, H16, (NR > 2 ? 2 : 0)>(a, lds, lane, sub, wave);

@@ -65,7 +65,7 @@ struct zvx_ctx {
     hipStream_t voc_aux[2] = {nullptr, nullptr};   // single requests: the non-final pairs of the 2nd / 3rd ResBlock of a vocoder stage run beside the 1st
     hipEvent_t voc_ev[3] = {nullptr, nullptr, nullptr};
     int voc_overlap_maxb = 1 << 20;        // zvx_set_int("voc_overlap_maxb", n): batches of at most n utterances use them (0: never; A/B)
-    long voc_overlap_frames = 28672;       // zvx_set_int("voc_overlap_frames", n): ... and only below n mel frames per call (B x Pmax)
+    int voc_overlap_frames = 28672;        // zvx_set_int("voc_overlap_frames", n): ... and only below n mel frames per call (B x Pmax)
     // Front end of call i+1 under the vocoder of call i (zvx_synthesize): encoder / variance adaptor / length regulator / mel decoder are
     // issued on front_stream, the vocoder on `stream`.  The two meet in ONE buffer, "mel": the vocoder waits for ev_front_done, the
     // next call's front end waits for ev_mel_free (recorded behind the vocoder's first kernel, which copies the mel into its padded
@@ -126,15 +126,11 @@ struct zvx_ctx {
     int voc_f16_stages = -1;               // zvx_set_int("voc_f16_stages", mask): which domains of the generator (bit 0: mel / conv_pre, bit i: upsampling stage i) compute in IEEE half when voc_f16 is on, the others in bf16; -1 (default): all but a 128-channel ResBlock1 stage
     int voc_h16_ok = -1;                   // every contraction weight of the generator has an IEEE-half copy (decided on the first vocoder call)
     int voc_f16 = 1;                       // zvx_set_int("voc_f16", 0): the vocoder's activations / weights / running sum in bf16 instead of IEEE half (A/B; round 5)
-    int dec_qkv = 1;                       // zvx_set_int("dec_qkv", 0): the half FFT-block decoder's Q | K and V projections as two launches (A/B; round 6)
-    int dec_y16 = 1;                       // zvx_set_int("dec_y16", 0): the half FFT-block decoder's pre-norm sums in f32 instead of half (A/B; round 6)
     int dec_f16 = 1;                       // zvx_set_int("dec_f16", 0): StyleTTS decoder activations / weights in bf16 instead of IEEE half (A/B)
     int use_attn_f32 = 1;                  // zvx_set_int("attn_f32", 0): the encoder's attention as V^T / score / P.V GEMMs + softmax (A/B)
     int use_flash = 1;                     // zvx_set_int("flash", 0): the decoder's attention as score GEMM + softmax + PV GEMM (A/B)
-    int voc_chunk = 0;                     // utterances per vocoder ResBlock sub-batch (0 = whole batch)
     int use_resstream = 1;                 // zvx_set_int("resstream", 0): ResBlocks of the narrow stages as per-pair launches (A/B, bit-equal)
     int rs_seg_min = 0;                    // zvx_set_int("rs_seg_min", -1): streaming ResBlock segments never shorter than 2048 rows (A/B of the single-request sizing)
-    int rs_opt = 3;                        // zvx_set_int("rs_opt", v): StreamArgs.opt of the streaming ResBlock kernels (bit 0: staggered wave priorities)
     int spk_s2_fuse = 1;                   // zvx_set_int("spk_s2_fuse", 0): the level transitions as two launches of the gathered-row GEMM (A/B)
     int spk_pool_fuse = 1;                 // zvx_set_int("spk_pool_fuse", 0): the speaker encoder's SE pool as its own pass everywhere (A/B)
     int slab_small = 2, slab_flat = 1;     // zvx_set_int("slab_small" / "slab_flat", v): conv-slab tile choice for single requests / whole-grid XCD remap (A/B; per context)
@@ -152,7 +148,7 @@ struct zvx_ctx {
     int use_stagefuse = 1;                 // zvx_set_int("stagefuse", 0): narrow vocoder stages (C = 16 / 8) as per-pair launches instead of ONE launch per stage (narrowstage.hip; A/B)
     struct NsWeights { void* W = nullptr; float* bias = nullptr; int woff[18] = {0}; };
     std::map<std::string, NsWeights> ns_weights;   // narrowstage.hip fragment order, per (stage, dtype), built on first use
-    int use_pairstream = 1;                // zvx_set_int("pairstream", v): C = 128 ResBlock pairs on pairstream.hip: 1 = every k (default; jobs under ~200 k rows run the bit-identical two-launch path), 3 = every k and every job size (tests), 4 = like 3 with 256-row segments for small jobs, <= 0 = two conv-slab launches per pair (the bit-equality reference)
+    int use_pairstream = 1;                // zvx_set_int("pairstream", v): C = 128 ResBlock pairs on pairstream.hip: 1 = every k (default; jobs under ~200 k rows run the bit-identical two-launch path), 3 = every k and every job size (tests), -1 / 0 = two conv-slab launches per pair (the bit-equality reference)
     int shape_log = 0;                     // zvx_set_int("shape_log", 1): one stderr line per timed launch (profile 2)
     int max_frames = 1 << 18;              // hard cap on a predicted mel length (guards the allocation, fs2.py:678-681 has none)
     hipEvent_t stage_ev[ZVX_T_COUNT][2];
@@ -372,15 +368,11 @@ struct zvx_ctx {
         for (int i = 0; i < 2; i++) if (voc_aux[i]) (void)hipStreamSynchronize(voc_aux[i]);
         front_dirty_main = true; mel_free_pending = false;
     }
-    int front_prio = 1;                    // zvx_set_int("front_prio", v): priority of the front stream: 1 = highest the device offers, -1 = lowest, 0 = default
-    void front_setup() {
+    void front_setup() {                   // the front stream runs at the highest priority the device offers
         if (front_stream) return;
-        if (front_prio) {
-            int least = 0, greatest = 0;                                     // (numerically: greatest priority = the smaller value)
-            HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-            HIPCHK(hipStreamCreateWithPriority(&front_stream, hipStreamNonBlocking, front_prio > 0 ? greatest : least));
-        } else
-        HIPCHK(hipStreamCreateWithFlags(&front_stream, hipStreamNonBlocking));
+        int least = 0, greatest = 0;                                         // (numerically: greatest priority = the smaller value)
+        HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
+        HIPCHK(hipStreamCreateWithPriority(&front_stream, hipStreamNonBlocking, greatest));
         HIPCHK(hipEventCreateWithFlags(&ev_front_done, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&ev_mel_free, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&ev_main_join, hipEventDisableTiming));
@@ -681,10 +673,8 @@ void fft_block(zvx_ctx* c, void* x, int dt, int B, int Lmax, const int* len_dev,
     // half blocks (the FS2 / SCLN decoder in the 16-bit mode; round 6): the pre-norm sums y = fc(O) + x and y = conv_k1(h) + x leave their GEMMs
     // as IEEE half through the compile-time decoder epilogue (raw 16-bit residual, ZVX_EPI_DEC) instead of f32 through the run-time one, and the
     // LayerNorm / SCLN pass reads 2 bytes per element instead of 4: one more rounding at 2^-11 of a value the norm then rescales
-    // (zvx_set_int("dec_y16", 0): f32, A/B)
-    const bool y16 = h16 && c->dec_y16;
-    void* const yv = y16 ? c->buf("fft.y16", (size_t)B * Ls * H * 2) : (void*)y;
-    const int ydt = y16 ? (int)DT_F16 : (int)DT_F32;
+    void* const yv = h16 ? c->buf("fft.y16", (size_t)B * Ls * H * 2) : (void*)y;
+    const int ydt = h16 ? (int)DT_F16 : (int)DT_F32;
     void* hbuf = c->buf("fft.h", (size_t)B * Ls * F * es);
 
     // f32 blocks (phoneme encoder) in bf16 mode: the static-weight GEMMs take bf16 split planes [hi | hi | lo] of their f32 input
@@ -727,9 +717,10 @@ void fft_block(zvx_ctx* c, void* x, int dt, int B, int Lmax, const int* len_dev,
         c->timed(4.0 * B * nheads * (double)Lmax * Lmax * d, (double)B * Lmax * 4.0 * H * 4, [&] { launch_attention_f32(af, c->stream, false); });
     } else {
     if (split) split_of((const float*)x, H, xs);
-    const bool qkv16 = h16 && c->dec_qkv && c->has(w.p + ".wqkv.h16") && c->has(w.p + ".bqkv");
-    void* qkvbuf = qkv16 ? c->buf("fft.qkv16", (size_t)B * Ls * 3 * H * es) : nullptr;
-    if (qkv16) {   // half blocks: [Q | K | V] = x [Wq; Wk; Wv]^T + b in ONE launch (round 6), then the 16-bit transpose of its V columns
+    // half blocks: [Q | K | V] = x [Wq; Wk; Wv]^T + b in ONE launch (round 6), then the 16-bit transpose of its V columns
+    // (upload_weights builds ".wqkv.h16" for every half block the packer writes)
+    void* qkvbuf = h16 ? c->buf("fft.qkv16", (size_t)B * Ls * 3 * H * es) : nullptr;
+    if (h16) {
         GemmArgs a = gemm_base(dt);
         a.X = x; a.x_bs = (long)Ls * H; a.ldx = H; a.W = c->t(w.p + ".wqkv.h16").dev; a.ldw = H;
         a.M = Lmax; a.N = 3 * H; a.K = H; a.nbatch = B; a.in_len = len_dev; a.out_len = len_dev; if (flat) a.bflat = Ls;
@@ -737,7 +728,7 @@ void fft_block(zvx_ctx* c, void* x, int dt, int B, int Lmax, const int* len_dev,
         a.out = qkvbuf; a.o_bs = (long)Ls * 3 * H; a.ldo = 3 * H;
         c->gemm(a);
         c->timed(0, (double)B * Lmax * H * 4.0, [&] { launch_transpose16((const char*)qkvbuf + (size_t)2 * H * es, 3 * H, vt, Lp, B, Ls, H, c->stream, len_dev); });
-    } else
+    } else {
     {   // [Q | K] = x Wqk^T + b                                       fs2.py:143-144
         GemmArgs a = gemm_base(dt);
         a.X = x; a.x_bs = (long)Ls * H; a.ldx = H; a.W = wdev(".wqk"); a.ldw = H;
@@ -747,17 +738,6 @@ void fft_block(zvx_ctx* c, void* x, int dt, int B, int Lmax, const int* len_dev,
         a.out = qk; a.o_bs = (long)Ls * 2 * H; a.ldo = 2 * H;
         c->gemm(a);
     }
-    if (qkv16) {
-    } else if (h16) {   // half: V = x Wv^T + b on the conv-slab kernel (static weights), then one 16-bit transpose to the key-contiguous layout
-        void* vrow = hbuf;                                                       // [B][Lmax][H]: the FFN buffer is idle here
-        GemmArgs a = gemm_base(dt);
-        a.X = x; a.x_bs = (long)Ls * H; a.ldx = H; a.W = wdev(".wv"); a.ldw = H;
-        a.M = Lmax; a.N = H; a.K = H; a.nbatch = B; a.in_len = len_dev; a.out_len = len_dev; if (flat) a.bflat = Ls;
-        a.bias = c->pf(w.p + ".bv"); a.bias_mode = 1;
-        a.out = vrow; a.o_bs = (long)Ls * H; a.ldo = H;
-        c->gemm(a);
-        c->timed(0, (double)B * Lmax * H * 4.0, [&] { launch_transpose16(vrow, H, vt, Lp, B, Ls, H, c->stream, len_dev); });   // V^T columns >= len[b]: zeros (stale rows of the shared FFN buffer)
-    } else
     {   // V^T[h*d + j][l] = Wv x^T + b  (stored transposed so that P.V is K-contiguous)   fs2.py:145
         GemmArgs a = gemm_base(dt);
         a.X = c->t(w.p + ".wv").dev; a.x_bs = 0; a.ldx = H; a.W = x; a.w_bs = (long)Ls * H; a.ldw = H;
@@ -774,10 +754,11 @@ void fft_block(zvx_ctx* c, void* x, int dt, int B, int Lmax, const int* len_dev,
         // utterance's length had been defined by something; nothing guarantees that (tests: zvx_set_int("poison_pads", 1))
         launch_zero_tail_cols(vt, (int)es, Lp, (long)H * Lp, B, H, Lmax, len_dev, c->stream);
     }
+    }
     FlashArgs fa;
     memset(&fa, 0, sizeof fa);
     fa.qk = qk; fa.qk_bs = (long)Ls * 2 * H; fa.ldq = 2 * H; fa.k_off = H; fa.vt = vt;
-    if (qkv16) { fa.qk = qkvbuf; fa.qk_bs = (long)Ls * 3 * H; fa.ldq = 3 * H; } fa.vt_bs = (long)H * Lp; fa.ldv = Lp;
+    if (h16) { fa.qk = qkvbuf; fa.qk_bs = (long)Ls * 3 * H; fa.ldq = 3 * H; } fa.vt_bs = (long)H * Lp; fa.ldv = Lp;
     fa.out = o; fa.o_bs = (long)Ls * H; fa.ldo = H; fa.len = len_dev; fa.L = Lmax; fa.D = d; fa.nheads = nheads; fa.nbatch = B;
     fa.scale = (float)(1.0 / pow((double)d, 0.5));
     fa.f16 = h16;
@@ -820,7 +801,7 @@ void fft_block(zvx_ctx* c, void* x, int dt, int B, int Lmax, const int* len_dev,
         if (split) { if (!fused_f32) split_of((const float*)o, H, xs); as_split(a, xs, H, w.p + ".wo"); }
         c->gemm(a);
     }
-    const double ln_bytes = (double)B * Lmax * H * ((y16 ? 2.0 : 4.0) + es);
+    const double ln_bytes = (double)B * Lmax * H * ((h16 ? 2.0 : 4.0) + es);
     c->timed(0, ln_bytes, [&] {
         if (w.scln) launch_layernorm(yv, ydt, H, x, dt, H, B, Ls, len_dev, H, 1, 1e-8f, nullptr, nullptr, w.bg, w.bg_bs, nullptr, c->stream);
         else launch_layernorm(yv, ydt, H, x, dt, H, B, Ls, len_dev, H, 0, 1e-5f, c->pf(w.p + ".ln1_g"), c->pf(w.p + ".ln1_b"), nullptr, 0, nullptr, c->stream, split ? xs : nullptr, sp16);
@@ -1210,10 +1191,6 @@ void decoder_styletts(zvx_ctx* c, const float* feats, const float* spk_d, const 
     sty_conv(s, "sty.enc0.c1", t0, H, H, t1, H, dt, H, nullptr, 0, 1.f);
     sty_norm(s, t1, H, H, t0, H, c->pf("sty.enc0.norm2_g"), c->pf("sty.enc0.norm2_b"), 0, 0, ACT_LRELU);
     auto can_fuse_shortcut = [&](const std::string& blk) {
-        if (c->dec_sc_fuse >= 2) {                            // development: bits 1.. select the blocks (enc0, dec0, dec1, dec2) that may fuse
-            const int bi = blk == "sty.enc0" ? 0 : (blk.size() == 8 ? 1 + (blk[7] - '0') : 9);
-            if (!((c->dec_sc_fuse >> (1 + bi)) & 1)) return false;
-        }
         return c->dec_sc_fuse && dt != DT_F32 && c->has(blk + ".c2") && c->pair_packed.count(c->t(dt == DT_F16 ? blk + ".c2.h16" : blk + ".c2").dev) != 0;
     };
     if (can_fuse_shortcut("sty.enc0")) {
@@ -1349,7 +1326,7 @@ void run_vocoder(zvx_ctx* c, const float* mel, int ldm, int Lmel_max, const int*
     // on the main stream, which the side streams only follow from the stage-input event on
     // tools/ab_voc_overlap.py: -5 ... -24 % for every batch below the headline's size (most where B leaves a ragged last round of
     // workgroups: B = 6 / 12), +-1 % at 32 x 896 frames, which therefore keeps the serial schedule
-    const bool side_ok = nk >= 2 && nk <= 3 && B <= c->voc_overlap_maxb && (long)B * Pmax < c->voc_overlap_frames && !(c->voc_chunk > 0 && c->voc_chunk < B);
+    const bool side_ok = nk >= 2 && nk <= 3 && B <= c->voc_overlap_maxb && (long)B * Pmax < c->voc_overlap_frames;
     void* sideT1[2] = {nullptr, nullptr}; void* sidePP[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
     if (side_ok)
         for (int j = 1; j < nk; j++) {
@@ -1412,15 +1389,9 @@ void run_vocoder(zvx_ctx* c, const float* mel, int ldm, int Lmel_max, const int*
         }
         const float next_slope = (i == ns - 1) ? 0.01f : 0.1f;          // hifigan.py:126 uses the default slope 0.01
         c->tag = "voc.res" + std::to_string(i + 1);
-        // The stage's ResBlocks can run on sub-batches of utterances (zvx_set_int("voc_chunk", n)) so that the tensors one
-        // sub-batch touches stay in the 256 MB Infinity Cache between launches.  Measured on B = 32 x 896 frames: no gain at
-        // any size (stage 2: 7.70 ms whole batch, 7.70 / 7.74 / 8.40 ms at 16 / 8 / 4 utterances) -- these stages are bound by
-        // MFMA issue, not by HBM -- so the default is the whole batch.  Results are bit-identical for any sub-batch size.
-        const size_t utt_bytes = (size_t)rows * Cout * es;
-        const int CH = (c->voc_chunk > 0 && c->voc_chunk < B) ? c->voc_chunk : B;
         // narrow stages (C = 16 / 8: HiFi-GAN V2's last two): all ResBlocks of the stage, their mean and the next stage's activation in ONE
         // launch -- the stage tensor crosses HBM once in, once out (narrowstage.hip)
-        if (c->use_stagefuse && !c->sat_check && c->voc_resblock == 1 && dt != DT_F32 && (Cout == 16 || Cout == 8) && nk >= 1 && nk <= 3 && CH == B) {
+        if (c->use_stagefuse && !c->sat_check && c->voc_resblock == 1 && dt != DT_F32 && (Cout == 16 || Cout == 8) && nk >= 1 && nk <= 3) {
             bool ok = true;
             for (int j = 0; j < nk; j++) ok = ok && c->voc_rb_d[j].size() == 3;
             StageArgs sa;
@@ -1474,197 +1445,186 @@ void run_vocoder(zvx_ctx* c, const float* mel, int ldm, int Lmel_max, const int*
                 continue;
             }
         }
-        for (int b0 = 0; b0 < B; b0 += CH) {
-            const int Bs = std::min(CH, B - b0);
-            const size_t boff = (size_t)b0 * utt_bytes;
-            const void* X0s = (const char*)X0 + boff;
-            void* T1s = (char*)T1 + boff; void* XSs = (char*)XS + boff; void* As = (char*)A + boff;
-            void* PPs[2] = {(char*)PP[0] + boff, (char*)PP[1] + boff};
-            const int* lens = len + b0;
-            // Single requests: the ResBlocks of a stage only meet in the running sum, which their LAST pair updates.  Everything
-            // before that (two of three pairs) runs on a stream of its own for the 2nd and 3rd ResBlock, with its own temporaries;
-            // the last pairs stay on the main stream in the order 1, 2, 3, so xs accumulates exactly as before (bit-identical).
-            // The critical path of a per-pair stage drops from 18 to 10 launches.
-            const bool overlap = side_ok;
-            hipStream_t const main_stream = c->stream;
-            struct Restore { zvx_ctx* c; hipStream_t keep; ~Restore() { c->stream = keep; } } restore{c, main_stream};
-            if (overlap) {
-                for (int q = 0; q < 2; q++) if (!c->voc_aux[q]) HIPCHK(hipStreamCreateWithFlags(&c->voc_aux[q], hipStreamNonBlocking));
-                for (int q = 0; q < 3; q++) if (!c->voc_ev[q]) HIPCHK(hipEventCreateWithFlags(&c->voc_ev[q], hipEventDisableTiming));
-                HIPCHK(hipEventRecord(c->voc_ev[0], main_stream));      // the stage input (and everything the previous stage read) is settled
-            }
-            for (int j = 0; j < nk; j++) {
-                hipStream_t const my_aux = (overlap && j >= 1) ? c->voc_aux[j - 1] : nullptr;
-                bool on_aux = false;
-                if (my_aux) {
-                    HIPCHK(hipStreamWaitEvent(my_aux, c->voc_ev[0], 0));
-                    T1s = sideT1[j - 1]; PPs[0] = sidePP[j - 1][0]; PPs[1] = sidePP[j - 1][1];
-                } else {
-                    T1s = (char*)T1 + boff; PPs[0] = (char*)PP[0] + boff; PPs[1] = (char*)PP[1] + boff;
+        // Single requests: the ResBlocks of a stage only meet in the running sum, which their LAST pair updates.  Everything
+        // before that (two of three pairs) runs on a stream of its own for the 2nd and 3rd ResBlock, with its own temporaries;
+        // the last pairs stay on the main stream in the order 1, 2, 3, so xs accumulates exactly as before (bit-identical).
+        // The critical path of a per-pair stage drops from 18 to 10 launches.
+        const bool overlap = side_ok;
+        hipStream_t const main_stream = c->stream;
+        struct Restore { zvx_ctx* c; hipStream_t keep; ~Restore() { c->stream = keep; } } restore{c, main_stream};
+        if (overlap) {
+            for (int q = 0; q < 2; q++) if (!c->voc_aux[q]) HIPCHK(hipStreamCreateWithFlags(&c->voc_aux[q], hipStreamNonBlocking));
+            for (int q = 0; q < 3; q++) if (!c->voc_ev[q]) HIPCHK(hipEventCreateWithFlags(&c->voc_ev[q], hipEventDisableTiming));
+            HIPCHK(hipEventRecord(c->voc_ev[0], main_stream));      // the stage input (and everything the previous stage read) is settled
+        }
+        for (int j = 0; j < nk; j++) {
+            hipStream_t const my_aux = (overlap && j >= 1) ? c->voc_aux[j - 1] : nullptr;
+            bool on_aux = false;
+            void* const T1s = my_aux ? sideT1[j - 1] : T1;
+            void* const* const PPs = my_aux ? sidePP[j - 1] : PP;
+            if (my_aux) HIPCHK(hipStreamWaitEvent(my_aux, c->voc_ev[0], 0));
+            auto to_aux = [&] { if (my_aux && !on_aux) { c->stream = my_aux; on_aux = true; } };
+            auto to_main = [&] {
+                if (on_aux) {
+                    HIPCHK(hipEventRecord(c->voc_ev[j], my_aux));
+                    c->stream = main_stream; on_aux = false;
+                    HIPCHK(hipStreamWaitEvent(main_stream, c->voc_ev[j], 0));
                 }
-                auto to_aux = [&] { if (my_aux && !on_aux) { c->stream = my_aux; on_aux = true; } };
-                auto to_main = [&] {
-                    if (on_aux) {
-                        HIPCHK(hipEventRecord(c->voc_ev[j], my_aux));
-                        c->stream = main_stream; on_aux = false;
-                        HIPCHK(hipStreamWaitEvent(main_stream, c->voc_ev[j], 0));
+            };
+            const int k = c->voc_rb_k[j];
+            const std::vector<int>& dil = c->voc_rb_d[j];
+            const int nd = (int)dil.size();
+            const std::string rb = "voc.rb" + std::to_string(i * nk + j);
+            const void* cur = X0;
+            int pp = 0;
+            int t_first = 0;
+            if (c->voc_resblock == 1 && dt != DT_F32 && c->use_resstream && !c->sat_check && nd >= 1 && nd <= 3) {
+                // whole ResBlock (or its first two pairs + the last one) as streaming launches: the stage tensor crosses HBM once
+                bool packed_ok = true;
+                for (int t = 0; t < nd; t++)
+                    packed_ok = packed_ok && c->packed.count(vt(rb + ".c1_" + std::to_string(t) + "_w").dev) && c->packed.count(vt(rb + ".c2_" + std::to_string(t) + "_w").dev);
+                auto chain = [&](int t0, int np, const void* in, bool closes) {
+                    StreamArgs sa;
+                    memset(&sa, 0, sizeof sa);
+                    sa.X = in; sa.x_bs = (long)rows * Cout; sa.ldx = Cout; sa.C = Cout; sa.ntaps = k; sa.npair = np;
+                    for (int q = 0; q < np; q++) {
+                        const std::string ts = std::to_string(t0 + q);
+                        sa.W1[q] = c->packed[vt(rb + ".c1_" + ts + "_w").dev]; sa.W2[q] = c->packed[vt(rb + ".c2_" + ts + "_w").dev];
+                        sa.b1[q] = c->pf(rb + ".c1_" + ts + "_b"); sa.b2[q] = c->pf(rb + ".c2_" + ts + "_b");
+                        sa.dil[q] = dil[t0 + q];
                     }
+                    sa.seg_min = c->rs_seg_min; sa.f16 = h16;
+                    if (c->rs_prof) sa.prof = (long long*)c->buf("rs.prof." + rb + "." + std::to_string(t0), 16 * 16 * 8);   // RS_PROFILE builds only
+                    sa.slope1 = 0.1f; sa.res_inv_slope = 10.0f; sa.out_scale = 1.f; sa.slope = 0.1f;
+                    sa.len = len; sa.M = rows; sa.nbatch = B; sa.o_bs = (long)rows * Cout; sa.ldo = Cout; sa.a_bs = (long)rows * Cout; sa.lda = Cout;
+                    if (!closes) { sa.out = PPs[pp]; }
+                    else if (nk == 1) { sa.out = A; sa.slope = next_slope; }
+                    else {
+                        sa.accum = XS; sa.accum_mode = j == 0 ? 2 : (j < nk - 1 ? 3 : 1);
+                        if (j == nk - 1) { sa.out = A; sa.out_scale = 1.0f / nk; sa.slope = next_slope; }
+                    }
+                    return sa;
                 };
-                const int k = c->voc_rb_k[j];
-                const std::vector<int>& dil = c->voc_rb_d[j];
-                const int nd = (int)dil.size();
-                const std::string rb = "voc.rb" + std::to_string(i * nk + j);
-                const void* cur = X0s;
-                int pp = 0;
-                int t_first = 0;
-                if (c->voc_resblock == 1 && dt != DT_F32 && c->use_resstream && !c->sat_check && nd >= 1 && nd <= 3) {
-                    // whole ResBlock (or its first two pairs + the last one) as streaming launches: the stage tensor crosses HBM once
-                    bool packed_ok = true;
-                    for (int t = 0; t < nd; t++)
-                        packed_ok = packed_ok && c->packed.count(vt(rb + ".c1_" + std::to_string(t) + "_w").dev) && c->packed.count(vt(rb + ".c2_" + std::to_string(t) + "_w").dev);
-                    auto chain = [&](int t0, int np, const void* in, bool closes) {
-                        StreamArgs sa;
-                        memset(&sa, 0, sizeof sa);
-                        sa.X = in; sa.x_bs = (long)rows * Cout; sa.ldx = Cout; sa.C = Cout; sa.ntaps = k; sa.npair = np;
-                        for (int q = 0; q < np; q++) {
-                            const std::string ts = std::to_string(t0 + q);
-                            sa.W1[q] = c->packed[vt(rb + ".c1_" + ts + "_w").dev]; sa.W2[q] = c->packed[vt(rb + ".c2_" + ts + "_w").dev];
-                            sa.b1[q] = c->pf(rb + ".c1_" + ts + "_b"); sa.b2[q] = c->pf(rb + ".c2_" + ts + "_b");
-                            sa.dil[q] = dil[t0 + q];
-                        }
-                        sa.opt = c->rs_opt; sa.seg_min = c->rs_seg_min; sa.f16 = h16;
-                        if (c->rs_prof) sa.prof = (long long*)c->buf("rs.prof." + rb + "." + std::to_string(t0), 16 * 16 * 8);   // RS_PROFILE builds only
-                        sa.slope1 = 0.1f; sa.res_inv_slope = 10.0f; sa.out_scale = 1.f; sa.slope = 0.1f;
-                        sa.len = lens; sa.M = rows; sa.nbatch = Bs; sa.o_bs = (long)rows * Cout; sa.ldo = Cout; sa.a_bs = (long)rows * Cout; sa.lda = Cout;
-                        if (!closes) { sa.out = PPs[pp]; }
-                        else if (nk == 1) { sa.out = As; sa.slope = next_slope; }
-                        else {
-                            sa.accum = XSs; sa.accum_mode = j == 0 ? 2 : (j < nk - 1 ? 3 : 1);
-                            if (j == nk - 1) { sa.out = As; sa.out_scale = 1.0f / nk; sa.slope = next_slope; }
-                        }
-                        return sa;
-                    };
-                    if (packed_ok) {
-                        StreamArgs whole = chain(0, nd, X0s, true);
-                        to_main();
-                        if (c->run_stream(whole)) t_first = nd;
-                        else if (nd == 3) {
-                            StreamArgs head = chain(0, 2, X0s, false);
-                            StreamArgs probe = chain(2, 1, PPs[pp], true);
-                            if (launch_resstream(head, c->stream, true) >= 0 && launch_resstream(probe, c->stream, true) >= 0) {
-                                to_aux();
-                                c->run_stream(head);
-                                cur = PPs[pp]; pp ^= 1;
-                                StreamArgs tail = chain(2, 1, cur, true);
-                                to_main();
-                                c->run_stream(tail);
-                                t_first = nd;
-                            }
+                if (packed_ok) {
+                    StreamArgs whole = chain(0, nd, X0, true);
+                    to_main();
+                    if (c->run_stream(whole)) t_first = nd;
+                    else if (nd == 3) {
+                        StreamArgs head = chain(0, 2, X0, false);
+                        StreamArgs probe = chain(2, 1, PPs[pp], true);
+                        if (launch_resstream(head, c->stream, true) >= 0 && launch_resstream(probe, c->stream, true) >= 0) {
+                            to_aux();
+                            c->run_stream(head);
+                            cur = PPs[pp]; pp ^= 1;
+                            StreamArgs tail = chain(2, 1, cur, true);
+                            to_main();
+                            c->run_stream(tail);
+                            t_first = nd;
                         }
                     }
                 }
-                if (c->voc_resblock == 2 && nd == 2 && dt != DT_F32 && c->use_rb2fuse && !c->sat_check && (Cout == 32 || Cout == 64)) {
-                    // a whole ResBlock2 (hifigan.py:77-82: x1 = x + c_0(lrelu(x)); x2 = x1 + c_1(lrelu(x1))) as ONE launch: lrelu(x1) stays in LDS
-                    // (rb2fuse_kernel, round 6) -- two trips of the stage tensor per block instead of six
-                    const Tensor& w1 = vt(rb + ".c_0_w"); const Tensor& w2 = vt(rb + ".c_1_w");
-                    if (c->packed.count(w1.dev) && c->packed.count(w2.dev)) {
-                        GemmArgs a = gemm_base(dt);
-                        a.M = rows; a.N = Cout; a.K = Cout; a.nbatch = Bs; a.in_len = lens; a.out_len = lens; a.ldw = Cout; a.w_ts = (long)Cout * Cout;
-                        a.x_bs = (long)rows * Cout; a.ldx = Cout; a.o_bs = (long)rows * Cout; a.ldo = Cout;
-                        a.X = X0s; a.W = w2.dev; a.Wp = c->packed[w2.dev]; a.Wp2 = c->packed[w1.dev];
-                        a.bias1 = c->pf(rb + ".c_0_b"); a.slope1 = 0.1f; a.fused = 2;
-                        set_taps_1d(a, k, dil[1]);
-                        for (int q = 0; q < k; q++) a.dv1[q] = (q - (k - 1) / 2) * dil[0];
-                        a.bias = c->pf(rb + ".c_1_b"); a.bias_mode = 1;
-                        a.res = X0s; a.r_bs = (long)rows * Cout; a.ldr = Cout; a.res_mode = 2; a.res_inv_slope = 10.0f; a.res_dtype = dt;
-                        a.accum = XSs; a.accum_dtype = dt; a.a_bs = (long)rows * Cout; a.lda = Cout;
+            }
+            if (c->voc_resblock == 2 && nd == 2 && dt != DT_F32 && c->use_rb2fuse && !c->sat_check && (Cout == 32 || Cout == 64)) {
+                // a whole ResBlock2 (hifigan.py:77-82: x1 = x + c_0(lrelu(x)); x2 = x1 + c_1(lrelu(x1))) as ONE launch: lrelu(x1) stays in LDS
+                // (rb2fuse_kernel, round 6) -- two trips of the stage tensor per block instead of six
+                const Tensor& w1 = vt(rb + ".c_0_w"); const Tensor& w2 = vt(rb + ".c_1_w");
+                if (c->packed.count(w1.dev) && c->packed.count(w2.dev)) {
+                    GemmArgs a = gemm_base(dt);
+                    a.M = rows; a.N = Cout; a.K = Cout; a.nbatch = B; a.in_len = len; a.out_len = len; a.ldw = Cout; a.w_ts = (long)Cout * Cout;
+                    a.x_bs = (long)rows * Cout; a.ldx = Cout; a.o_bs = (long)rows * Cout; a.ldo = Cout;
+                    a.X = X0; a.W = w2.dev; a.Wp = c->packed[w2.dev]; a.Wp2 = c->packed[w1.dev];
+                    a.bias1 = c->pf(rb + ".c_0_b"); a.slope1 = 0.1f; a.fused = 2;
+                    set_taps_1d(a, k, dil[1]);
+                    for (int q = 0; q < k; q++) a.dv1[q] = (q - (k - 1) / 2) * dil[0];
+                    a.bias = c->pf(rb + ".c_1_b"); a.bias_mode = 1;
+                    a.res = X0; a.r_bs = (long)rows * Cout; a.ldr = Cout; a.res_mode = 2; a.res_inv_slope = 10.0f; a.res_dtype = dt;
+                    a.accum = XS; a.accum_dtype = dt; a.a_bs = (long)rows * Cout; a.lda = Cout;
+                    if (nk == 1) { a.accum_mode = 0; a.accum = nullptr; }
+                    else if (j == 0) a.accum_mode = 2;
+                    else if (j < nk - 1) a.accum_mode = 3;
+                    else a.accum_mode = 1;
+                    if (j == nk - 1 || nk == 1) { a.out = A; a.out_scale = 1.0f / nk; a.act = ACT_LRELU; a.slope = next_slope; }
+                    else a.out = nullptr;
+                    a.flops = 2.0 * 2.0 * B * (double)rows * Cout * Cout * k;
+                    if (gemm_variant_of(a) >= 0) { to_main(); c->gemm(a); t_first = nd; }
+                }
+            }
+            for (int t = t_first; t < nd; t++) {
+                const bool last = (t == nd - 1);
+                if (last) to_main(); else to_aux();
+                const void* cin_buf = cur;
+                auto rb_base = [&] {
+                    GemmArgs a = gemm_base(dt);
+                    a.M = rows; a.N = Cout; a.K = Cout; a.nbatch = B; a.in_len = len; a.out_len = len; a.ldw = Cout; a.w_ts = (long)Cout * Cout;
+                    a.x_bs = (long)rows * Cout; a.ldx = Cout; a.o_bs = (long)rows * Cout; a.ldo = Cout;
+                    return a;
+                };
+                // what the LAST conv of the iteration does with its result: + bias + x (raw residual recovered from the activated
+                // input), then either the next iteration's input (activated) or the stage's running sum / mean
+                int pp_next = pp;
+                auto rb_tail = [&](GemmArgs& a) {
+                    a.bias_mode = 1;
+                    a.res = cin_buf; a.r_bs = (long)rows * Cout; a.ldr = Cout; a.res_mode = 2; a.res_inv_slope = 10.0f; a.res_dtype = dt;
+                    if (!last) {
+                        a.act = ACT_LRELU; a.slope = 0.1f; a.out = PPs[pp];
+                        pp_next = pp ^ 1;
+                    } else {
+                        // xs (+)= resblock output; last kernel size: x = xs / num_kernels, stored activated for the next stage
+                        a.accum = XS; a.accum_dtype = dt; a.a_bs = (long)rows * Cout; a.lda = Cout;
                         if (nk == 1) { a.accum_mode = 0; a.accum = nullptr; }
                         else if (j == 0) a.accum_mode = 2;
                         else if (j < nk - 1) a.accum_mode = 3;
                         else a.accum_mode = 1;
-                        if (j == nk - 1 || nk == 1) { a.out = As; a.out_scale = 1.0f / nk; a.act = ACT_LRELU; a.slope = next_slope; }
+                        if (j == nk - 1) { a.out = A; a.out_scale = 1.0f / nk; a.act = ACT_LRELU; a.slope = next_slope; }
                         else a.out = nullptr;
-                        a.flops = 2.0 * 2.0 * Bs * (double)rows * Cout * Cout * k;
-                        if (gemm_variant_of(a) >= 0) { to_main(); c->gemm(a); t_first = nd; }
                     }
-                }
-                for (int t = t_first; t < nd; t++) {
-                    const bool last = (t == nd - 1);
-                    if (last) to_main(); else to_aux();
-                    const void* cin_buf = cur;
-                    auto rb_base = [&] {
-                        GemmArgs a = gemm_base(dt);
-                        a.M = rows; a.N = Cout; a.K = Cout; a.nbatch = Bs; a.in_len = lens; a.out_len = lens; a.ldw = Cout; a.w_ts = (long)Cout * Cout;
-                        a.x_bs = (long)rows * Cout; a.ldx = Cout; a.o_bs = (long)rows * Cout; a.ldo = Cout;
-                        return a;
-                    };
-                    // what the LAST conv of the iteration does with its result: + bias + x (raw residual recovered from the activated
-                    // input), then either the next iteration's input (activated) or the stage's running sum / mean
-                    int pp_next = pp;
-                    auto rb_tail = [&](GemmArgs& a) {
-                        a.bias_mode = 1;
-                        a.res = cin_buf; a.r_bs = (long)rows * Cout; a.ldr = Cout; a.res_mode = 2; a.res_inv_slope = 10.0f; a.res_dtype = dt;
-                        if (!last) {
-                            a.act = ACT_LRELU; a.slope = 0.1f; a.out = PPs[pp];
-                            pp_next = pp ^ 1;
-                        } else {
-                            // xs (+)= resblock output; last kernel size: x = xs / num_kernels, stored activated for the next stage
-                            a.accum = XSs; a.accum_dtype = dt; a.a_bs = (long)rows * Cout; a.lda = Cout;
-                            if (nk == 1) { a.accum_mode = 0; a.accum = nullptr; }
-                            else if (j == 0) a.accum_mode = 2;
-                            else if (j < nk - 1) a.accum_mode = 3;
-                            else a.accum_mode = 1;
-                            if (j == nk - 1) { a.out = As; a.out_scale = 1.0f / nk; a.act = ACT_LRELU; a.slope = next_slope; }
-                            else a.out = nullptr;
-                        }
-                    };
-                    GemmArgs a = rb_base();
-                    if (c->voc_resblock == 1) {
-                        const std::string ts = std::to_string(t);
-                        const Tensor& w1 = vt(rb + ".c1_" + ts + "_w");
-                        const Tensor& w2 = vt(rb + ".c2_" + ts + "_w");
-                        bool fuse = dt != DT_F32 && !c->sat_check && c->packed.count(w1.dev) && c->packed.count(w2.dev);
-                        if (fuse) {
-                            // one launch: xt = lrelu(c1(x_act)+b1) stays in LDS; x' = c2(xt) + b2 + x      hifigan.py:51-55
-                            a.X = cur; a.W = w2.dev; a.Wp = c->packed[w2.dev]; a.Wp2 = c->packed[w1.dev];
-                            a.bias1 = c->pf(rb + ".c1_" + ts + "_b"); a.slope1 = 0.1f; a.fused = 1;
-                            a.no_pairstream = c->use_pairstream <= 0 ? 1 : (c->use_pairstream == 3 ? 2 : (c->use_pairstream == 4 ? 3 : 0));
-                            set_taps_1d(a, k, 1);
-                            for (int q = 0; q < k; q++) a.dv1[q] = (q - (k - 1) / 2) * dil[t];
-                            a.bias = c->pf(rb + ".c2_" + ts + "_b");
-                            a.flops = 2.0 * 2.0 * Bs * (double)rows * Cout * Cout * k;
-                            rb_tail(a);
-                            // the fused kernels cover a subset of (C, k, dilation, LDS footprint): ask the launcher (dry run) first
-                            const int fv = gemm_variant_of(a);
-                            // C = 128: the pair kernel, or -- where it declines (small jobs) -- the two conv-slab launches it is bit-identical to:
-                            // an utterance must come out the same alone and inside a large batch
-                            fuse = fv >= 0 && !(Cout == 128 && fv != 23);
-                        }
-                        if (!fuse) {
-                            // xt = c1(lrelu(x)); stored as lrelu(xt)                       hifigan.py:51-53
-                            a = rb_base();
-                            a.X = cur; a.W = w1.dev;
-                            set_taps_1d(a, k, dil[t]);
-                            a.bias = c->pf(rb + ".c1_" + ts + "_b"); a.bias_mode = 1; a.act = ACT_LRELU; a.slope = 0.1f;
-                            a.out = T1s;
-                            c->gemm(a);
-                            // x = c2(.) + x                                                hifigan.py:54-55
-                            a = rb_base();
-                            a.X = T1s; a.W = w2.dev;
-                            set_taps_1d(a, k, 1);
-                            a.bias = c->pf(rb + ".c2_" + ts + "_b");
-                            rb_tail(a);
-                        }
-                    } else {
-                        // x = c(lrelu(x)) + x                                          hifigan.py:78-81
-                        a.X = cur; a.W = vt(rb + ".c_" + std::to_string(t) + "_w").dev;
+                };
+                GemmArgs a = rb_base();
+                if (c->voc_resblock == 1) {
+                    const std::string ts = std::to_string(t);
+                    const Tensor& w1 = vt(rb + ".c1_" + ts + "_w");
+                    const Tensor& w2 = vt(rb + ".c2_" + ts + "_w");
+                    bool fuse = dt != DT_F32 && !c->sat_check && c->packed.count(w1.dev) && c->packed.count(w2.dev);
+                    if (fuse) {
+                        // one launch: xt = lrelu(c1(x_act)+b1) stays in LDS; x' = c2(xt) + b2 + x      hifigan.py:51-55
+                        a.X = cur; a.W = w2.dev; a.Wp = c->packed[w2.dev]; a.Wp2 = c->packed[w1.dev];
+                        a.bias1 = c->pf(rb + ".c1_" + ts + "_b"); a.slope1 = 0.1f; a.fused = 1;
+                        a.no_pairstream = c->use_pairstream <= 0 ? 1 : (c->use_pairstream == 3 ? 2 : 0);
+                        set_taps_1d(a, k, 1);
+                        for (int q = 0; q < k; q++) a.dv1[q] = (q - (k - 1) / 2) * dil[t];
+                        a.bias = c->pf(rb + ".c2_" + ts + "_b");
+                        a.flops = 2.0 * 2.0 * B * (double)rows * Cout * Cout * k;
+                        rb_tail(a);
+                        // the fused kernels cover a subset of (C, k, dilation, LDS footprint): ask the launcher (dry run) first
+                        const int fv = gemm_variant_of(a);
+                        // C = 128: the pair kernel, or -- where it declines (small jobs) -- the two conv-slab launches it is bit-identical to:
+                        // an utterance must come out the same alone and inside a large batch
+                        fuse = fv >= 0 && !(Cout == 128 && fv != 23);
+                    }
+                    if (!fuse) {
+                        // xt = c1(lrelu(x)); stored as lrelu(xt)                       hifigan.py:51-53
+                        a = rb_base();
+                        a.X = cur; a.W = w1.dev;
                         set_taps_1d(a, k, dil[t]);
-                        a.bias = c->pf(rb + ".c_" + std::to_string(t) + "_b");
+                        a.bias = c->pf(rb + ".c1_" + ts + "_b"); a.bias_mode = 1; a.act = ACT_LRELU; a.slope = 0.1f;
+                        a.out = T1s;
+                        c->gemm(a);
+                        // x = c2(.) + x                                                hifigan.py:54-55
+                        a = rb_base();
+                        a.X = T1s; a.W = w2.dev;
+                        set_taps_1d(a, k, 1);
+                        a.bias = c->pf(rb + ".c2_" + ts + "_b");
                         rb_tail(a);
                     }
-                    c->gemm(a);
-                    if (!last) { cur = PPs[pp]; pp = pp_next; }
+                } else {
+                    // x = c(lrelu(x)) + x                                          hifigan.py:78-81
+                    a.X = cur; a.W = vt(rb + ".c_" + std::to_string(t) + "_w").dev;
+                    set_taps_1d(a, k, dil[t]);
+                    a.bias = c->pf(rb + ".c_" + std::to_string(t) + "_b");
+                    rb_tail(a);
                 }
+                c->gemm(a);
+                if (!last) { cur = PPs[pp]; pp = pp_next; }
             }
         }
         Cin = Cout; mul *= u;
@@ -2038,8 +1998,53 @@ void zvx_destroy(zvx_ctx* c) {
 
 const char* zvx_last_error(const zvx_ctx* c) { return c ? c->err.c_str() : g_create_error.c_str(); }
 
+namespace {
+
+// The run-time switches of zvx_set_int / zvx_get_int: the context member behind each key and the values it accepts
+struct Switch { const char* key; int zvx_ctx::*v; bool (*ok)(int64_t); };
+bool flag(int64_t v) { return v == 0 || v == 1; }
+bool count(int64_t v) { return v >= 0 && v <= INT32_MAX; }
+const Switch kSwitches[] = {
+    {"profile", &zvx_ctx::profile, [](int64_t v) { return v >= 0 && v <= 2; }},
+    {"profile_only", &zvx_ctx::profile_only, [](int64_t v) { return v >= -1 && v < gemm_num_variants(); }},
+    {"shape_log", &zvx_ctx::shape_log, flag},
+    {"rs_prof", &zvx_ctx::rs_prof, flag},
+    {"f16_sat_check", &zvx_ctx::sat_check, flag},
+    {"poison_pads", &zvx_ctx::poison_pads, flag},
+    {"max_frames", &zvx_ctx::max_frames, [](int64_t v) { return v >= 1 && v <= (1 << 24); }},
+    {"enc_split", &zvx_ctx::enc_split, [](int64_t v) { return v >= 0 && v <= 2; }},
+    {"attn_f32", &zvx_ctx::use_attn_f32, flag},
+    {"flash", &zvx_ctx::use_flash, flag},
+    {"front_overlap", &zvx_ctx::front_overlap, [](int64_t v) { return v >= 0 && v <= 2; }},
+    {"va_overlap_maxb", &zvx_ctx::va_overlap_maxb, count},
+    {"dec_f16", &zvx_ctx::dec_f16, flag},
+    {"dec_flat", &zvx_ctx::dec_flat, flag},
+    {"dec_sc_fuse", &zvx_ctx::dec_sc_fuse, flag},
+    {"norm_fuse_maxb", &zvx_ctx::norm_fuse_maxb, count},
+    {"voc_f16", &zvx_ctx::voc_f16, flag},
+    {"voc_f16_stages", &zvx_ctx::voc_f16_stages, [](int64_t v) { return v >= -1 && v <= INT32_MAX; }},
+    {"voc_overlap_maxb", &zvx_ctx::voc_overlap_maxb, count},
+    {"voc_overlap_frames", &zvx_ctx::voc_overlap_frames, count},
+    {"stagefuse", &zvx_ctx::use_stagefuse, flag},
+    {"rb2fuse", &zvx_ctx::use_rb2fuse, flag},
+    {"resstream", &zvx_ctx::use_resstream, flag},
+    {"rs_seg_min", &zvx_ctx::rs_seg_min, [](int64_t v) { return v >= -1 && v <= INT32_MAX; }},
+    {"pairstream", &zvx_ctx::use_pairstream, [](int64_t v) { return v == -1 || v == 0 || v == 1 || v == 3; }},
+    {"slab_small", &zvx_ctx::slab_small, [](int64_t v) { return (v & ~32) >= 0 && (v & ~32) <= 2; }},
+    {"slab_flat", &zvx_ctx::slab_flat, flag},
+    {"spk_pool_fuse", &zvx_ctx::spk_pool_fuse, flag},
+    {"spk_s2_fuse", &zvx_ctx::spk_s2_fuse, flag},
+};
+const Switch* find_switch(const char* key) {
+    for (const Switch& s : kSwitches) if (!strcmp(s.key, key)) return &s;
+    return nullptr;
+}
+
+}  // namespace
+
 int64_t zvx_get_int(const zvx_ctx* c, const char* key) {
     if (!c || !key) return -1;
+    if (const Switch* s = find_switch(key)) return c->*s->v;
     const std::string k(key);
     if (k == "precision") return c->dt == DT_F32 ? 1 : 0;
     if (k == "hidden") return c->H;
@@ -2048,9 +2053,6 @@ int64_t zvx_get_int(const zvx_ctx* c, const char* key) {
     if (k == "device") return c->device;
     if (k == "dec_kind") return c->dec_kind;
     if (k == "Lmax") return c->Lmax;
-    if (k == "profile") return c->profile;
-    if (k == "profile_only") return c->profile_only;
-    if (k == "f16_sat_check") return c->sat_check;
     if (k == "f16_sat_events") {                             // clamped 16-bit stores seen since zvx_set_int("f16_sat_check", 1); drains the context's streams
         zvx_ctx* m = const_cast<zvx_ctx*>(c);
         unsigned long long n = 0;
@@ -2068,54 +2070,18 @@ int64_t zvx_get_int(const zvx_ctx* c, const char* key) {
 zvx_status zvx_set_int(zvx_ctx* c, const char* key, int64_t value) {
     return guarded(c, [&] {
         if (!key) fail(ZVX_E_INVALID, "key is NULL");
-        if (std::string(key) == "profile") { c->sync(); c->profile = (int)value; }
-        else if (std::string(key) == "profile_only") { c->sync(); c->profile_only = (int)value; }
-        else if (std::string(key) == "shape_log") c->shape_log = (int)value;
-        else if (std::string(key) == "resstream") c->use_resstream = (int)value;
-        else if (std::string(key) == "pairstream") { if (value == 2) fail(ZVX_E_INVALID, "pairstream 2 (k = 3 on the register-resident pair kernel) was removed in round 6"); c->use_pairstream = (int)value; }
-        else if (std::string(key) == "voc_chunk") c->voc_chunk = (int)value;
-        else if (std::string(key) == "flash") c->use_flash = (int)value;
-        else if (std::string(key) == "attn_f32") c->use_attn_f32 = (int)value;
-        else if (std::string(key) == "dec_f16") c->dec_f16 = (int)value;
-        else if (std::string(key) == "dec_y16") c->dec_y16 = (int)value;
-        else if (std::string(key) == "dec_qkv") c->dec_qkv = (int)value;
-        else if (std::string(key) == "voc_f16") c->voc_f16 = (int)value;
-        else if (std::string(key) == "voc_f16_stages") c->voc_f16_stages = (int)value;
-        else if (std::string(key) == "stagefuse") c->use_stagefuse = (int)value;
-        else if (std::string(key) == "rb2fuse") c->use_rb2fuse = (int)value;
-        else if (std::string(key) == "f16_sat_check") {       // (re)arms the audit and zeroes its counter
-            c->sync(); c->sat_check = value ? 1 : 0;
-            HIPCHK(hipMemsetAsync(c->sat_count_dev(), 0, 64, c->stream));
-        }
-        else if (std::string(key) == "poison_pads") c->poison_pads = (int)value;
-        else if (std::string(key) == "dec_flat") c->dec_flat = (int)value;
-        else if (std::string(key) == "dec_sc_fuse") c->dec_sc_fuse = (int)value;
-        else if (std::string(key) == "norm_fuse_maxb") c->norm_fuse_maxb = (int)value;
-        else if (std::string(key) == "va_overlap_maxb") c->va_overlap_maxb = (int)value;
-        else if (std::string(key) == "voc_overlap_maxb") c->voc_overlap_maxb = (int)value;
-        else if (std::string(key) == "voc_overlap_frames") c->voc_overlap_frames = (long)value;
-        else if (std::string(key) == "enc_split") {
-            if (value < 0 || value > 2) fail(ZVX_E_INVALID, "enc_split: 0 (exact f32), 1 (bf16 planes) or 2 (half planes)");
-            c->enc_split = c->dt == DT_BF16 ? (int)value : 0;
+        const Switch* s = find_switch(key);
+        if (!s) fail(ZVX_E_INVALID, "unknown option '%s'", key);
+        if (!s->ok(value)) fail(ZVX_E_INVALID, "option '%s' does not take the value %lld", key, (long long)value);
+        const std::string k(key);
+        if (k == "profile" || k == "profile_only" || k == "f16_sat_check" || k == "front_overlap") c->sync();
+        c->*s->v = (int)value;
+        if (k == "f16_sat_check") HIPCHK(hipMemsetAsync(c->sat_count_dev(), 0, 64, c->stream));      // (re)arms the audit and zeroes its counter
+        if (k == "front_overlap") c->front_dirty_main = true;
+        if (k == "enc_split") {
+            if (c->dt != DT_BF16) c->enc_split = 0;                                                   // the f32 mode has no split planes
             if (c->enc_split) { c->sync(); build_split_weights(c, c->enc_split == 2); }
         }
-        else if (std::string(key) == "front_overlap") { c->sync(); c->front_overlap = (int)value; c->front_dirty_main = true; }
-        else if (std::string(key) == "front_prio") {
-            c->sync(); c->front_prio = (int)value; c->front_dirty_main = true; c->mel_free_pending = false;
-            if (c->front_stream) {                                           // re-created with the new priority on the next zvx_synthesize
-                (void)hipStreamDestroy(c->front_stream); c->front_stream = nullptr;
-                (void)hipEventDestroy(c->ev_front_done); (void)hipEventDestroy(c->ev_mel_free); (void)hipEventDestroy(c->ev_main_join);
-            }
-        }
-        else if (std::string(key) == "rs_prof") c->rs_prof = (int)value;
-        else if (std::string(key) == "rs_opt") c->rs_opt = (int)value;
-        else if (std::string(key) == "rs_seg_min") c->rs_seg_min = (int)value;
-        else if (std::string(key) == "slab_small") c->slab_small = (int)value;
-        else if (std::string(key) == "spk_pool_fuse") c->spk_pool_fuse = (int)value;
-        else if (std::string(key) == "spk_s2_fuse") c->spk_s2_fuse = (int)value;
-        else if (std::string(key) == "slab_flat") c->slab_flat = (int)value;
-        else if (std::string(key) == "max_frames") { if (value < 1 || value > (1 << 24)) fail(ZVX_E_INVALID, "max_frames out of range"); c->max_frames = (int)value; }
-        else fail(ZVX_E_INVALID, "unknown option '%s'", key);
     });
 }
 
