@@ -1,0 +1,165 @@
+"""Host-side checks of the float64 kernel reference (tests/kernel_ref.py) that tests/test_kernels_gpu.py holds the kernels to:
+  * the ctypes mirror of GemmArgs / FlashArgs / AttnF32Args has the compiled layout (read from the shim without opening a device);
+  * gemm_ref / attn_ref agree with an independent formulation (torch.nn.functional on the CPU) for each row-map kind;
+  * the references discriminate: every mutation of the reference (a dropped or shifted tap, a lost K chunk, an off-by-one length,
+    the wrong residual slope, a dropped bias, a skipped accumulator add) leaves the bound of every case it applies to."""
+import ctypes
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+import kernel_ref as K
+
+
+def _needs_lib():
+    if not os.path.exists(K.KTEST_LIB):
+        pytest.fail(f"{K.KTEST_LIB} is missing: run zerovox_amd.build first")
+
+
+def test_struct_layout():
+    """Every field of the three argument structs sits where the compiled shim says, and the sizes agree."""
+    _needs_lib()
+    lib = K.load_ktest()
+    seen = set()
+    for i in range(lib.zvxk_num_fields()):
+        st, name = lib.zvxk_field(i, 0).decode(), lib.zvxk_field(i, 1).decode()
+        cls = K.STRUCTS[st]
+        assert getattr(cls, name).offset == lib.zvxk_offsetof(st.encode(), name.encode()), (st, name)
+        seen.add((st, name))
+    for st, cls in K.STRUCTS.items():
+        assert ctypes.sizeof(cls) == lib.zvxk_sizeof(st.encode()), st
+        for f, _t in cls._fields_:
+            assert (st, f) in seen, f"{st}.{f} is mirrored in Python but not reported by the shim"
+
+
+def _ref_out(p):
+    r, t, m = K.gemm_ref(p)["out"]
+    return r, m
+
+
+def test_ref_conv1d_dilated_vs_torch():
+    """1-D taps with dilation, ragged lengths (zero padding past in_len): F.conv1d per utterance."""
+    p = K.make_gemm("t", 1, dtype=K.DT_F32, M=50, N=24, K=16, nbatch=2, lens=[50, 9], taps=K.taps_1d(5, 3), packed=False, bias_mode=0)
+    r, m = _ref_out(p)
+    d = p.d
+    X = p.bufs["X"]["v"].reshape(2, -1, d["ldx"])
+    W = p.bufs["W"]["v"].reshape(5, d["N"], d["ldw"])
+    w = torch.tensor(W[:, :, :16]).permute(1, 2, 0)                 # [N][K][tap]
+    for b, l in enumerate([50, 9]):
+        x = torch.tensor(np.nan_to_num(X[b, :l, :16])).T[None]
+        y = F.conv1d(x, w, padding=6, dilation=3)[0].T.numpy()
+        got = r[b * d["o_bs"]:b * d["o_bs"] + l * d["ldo"]].reshape(l, d["ldo"])[:, :24]
+        np.testing.assert_allclose(got, y, rtol=1e-12, atol=1e-12)
+
+
+def test_ref_conv_transpose_polyphase_vs_torch():
+    """Polyphase ConvTranspose1d (stride 4, kernel 8, padding 2) as one 1-tap-per-weight-column launch per output phase."""
+    rng = np.random.default_rng(3)
+    Cin, Cout, k, s, pad, L = 16, 8, 8, 4, 2, 12
+    x = rng.standard_normal((Cin, L))
+    w = rng.standard_normal((Cin, Cout, k))
+    y = F.conv_transpose1d(torch.tensor(x)[None], torch.tensor(w), stride=s, padding=pad)[0].numpy()   # [Cout][(L-1)s - 2p + k]
+    Lout = y.shape[1]
+    for ph in range(s):
+        r0, q = (ph + pad) % s, (ph + pad) // s
+        ms = list(range(r0, k, s))
+        taps = [q - j for j in range(len(ms))]
+        T = (Lout - ph + s - 1) // s
+        p = K.make_gemm("ct", 0, dtype=K.DT_F32, M=T, N=Cout, K=Cin, lens=[L], out_lens=[T], taps=taps, packed=False, bias_mode=0)
+        Xv = np.full(len(p.bufs["X"]["v"]), np.nan)
+        Xv[:L * Cin] = x.T.reshape(-1)
+        p.bufs["X"]["v"] = Xv
+        p.bufs["W"]["v"] = np.stack([w[:, :, m].T for m in ms]).reshape(-1)
+        r, msk = _ref_out(p)
+        got = r[:T * Cout].reshape(T, Cout)
+        np.testing.assert_allclose(got, y[:, ph::s].T, rtol=1e-12, atol=1e-12)
+
+
+def test_ref_conv2d_stride2_and_flat_vs_torch():
+    """2-D taps with stride 2 (ResNet level transition) and the flattened stride-1 map: F.conv2d with padding 1."""
+    for stride, flat in ((2, False), (1, True)):
+        hin, win, C, N, lens = 6, 11, 8, 16, [10, 3]
+        wout = (win - 1) // stride + 1
+        hout = (hin - 1) // stride + 1
+        p = K.make_gemm("c2", 2, dtype=K.DT_F32, M=hout * wout, N=N, K=C, nbatch=2, lens=lens, taps=[t % 3 - 1 for t in range(9)],
+                        du=[t // 3 - 1 for t in range(9)], stride=stride, wout=wout, hin=hin, win=win, flat=flat, packed=False, bias_mode=0)
+        r, m = _ref_out(p)
+        d = p.d
+        X = p.bufs["X"]["v"].reshape(2, hin, win, C)
+        W = p.bufs["W"]["v"].reshape(9, N, C)
+        w = torch.tensor(W.reshape(3, 3, N, C)).permute(2, 3, 0, 1)
+        for b, l in enumerate(lens):
+            x = torch.tensor(np.nan_to_num(X[b, :, :l])).permute(2, 0, 1)[None]
+            y = F.conv2d(x, w, padding=1, stride=stride)[0].permute(1, 2, 0).numpy()       # [hout][wo][N]
+            got = r[b * d["o_bs"]:b * d["o_bs"] + hout * wout * d["ldo"]].reshape(hout, wout, d["ldo"])[:, :, :N]
+            wv = (l + stride - 1) // stride
+            np.testing.assert_allclose(got[:, :wv], y[:, :wv], rtol=1e-12, atol=1e-12)
+
+
+def test_ref_linear_heads_klen_vs_torch():
+    """Batched product with per-utterance k_len (attention P.V): F.linear over the first k_len columns."""
+    p = K.make_gemm("pv", 4, dtype=K.DT_F32, M=20, N=12, K=24, nbatch=3, lens=[20, 1, 13], k_len=[20, 1, 13], packed=False, bias_mode=0, alpha=0.5)
+    r, m = _ref_out(p)
+    d = p.d
+    X = p.bufs["X"]["v"].reshape(3, -1, d["ldx"])
+    W = p.bufs["W"]["v"].reshape(3, d["N"], d["ldw"])
+    for b, l in enumerate([20, 1, 13]):
+        y = 0.5 * F.linear(torch.tensor(X[b, :l, :l]), torch.tensor(W[b, :, :l])).numpy()
+        got = r[b * d["o_bs"]:b * d["o_bs"] + l * d["ldo"]].reshape(l, d["ldo"])[:, :12]
+        np.testing.assert_allclose(got, y, rtol=1e-12, atol=1e-12)
+
+
+@pytest.mark.parametrize("flash", [True, False])
+def test_attn_ref_vs_torch(flash):
+    """Masked softmax attention (keys < len, 1 / sqrt(D)) per utterance and head: torch softmax in float64."""
+    p = K.make_attn("a", 5, flash=flash, B=2, nheads=2, lens=[9, 1])
+    r, t, m = K.attn_ref(p)["out"]
+    d = p.d
+    D = 264
+    for b, l in enumerate([9, 1]):
+        for h in range(2):
+            if flash:
+                QK = p.bufs["qk"]["v"].reshape(2, d["L"], d["ldq"])
+                Q, Kt = QK[b, :l, h * D:(h + 1) * D], QK[b, :l, d["k_off"] + h * D:d["k_off"] + (h + 1) * D]
+                V = p.bufs["vt"]["v"].reshape(2, -1, d["ldv"])[b, h * D:(h + 1) * D, :l].T
+            else:
+                A = p.bufs["qkv"]["v"].reshape(2, d["L"], d["ld"])
+                Q, Kt, V = (A[b, :l, o + h * D:o + (h + 1) * D] for o in (d["q_off"], d["k_off"], d["v_off"]))
+            s = torch.tensor(Q) @ torch.tensor(Kt).T * d["scale"]          # (1 / sqrt(D) as the f32 the launcher gets)
+            y = (torch.softmax(s, dim=1) @ torch.tensor(V)).numpy()
+            got = r[b * d["o_bs"]:b * d["o_bs"] + l * d["ldo"]].reshape(l, d["ldo"])[:, h * D:(h + 1) * D]
+            np.testing.assert_allclose(got, y, rtol=1e-10, atol=1e-12)
+
+
+def _exceeds(ref, tol, mask, mut):
+    diff = np.abs(mut[mask] - ref[mask])
+    return bool(np.any(~(diff <= tol[mask])))
+
+
+@pytest.mark.parametrize("entry", K.GEMM_CASES, ids=[e[0] for e in K.GEMM_CASES])
+def test_mutations_leave_bound(entry):
+    """Each applicable mutation of the reference exceeds the case's own bound on the case's own data somewhere: a kernel wrong in
+    that way would fail test_kernels_gpu."""
+    p = K.build_case(entry)
+    true = K.gemm_ref(p)
+    weak = []
+    for mut in K.applicable_mutations(p):
+        got = K.gemm_ref(p, mut)
+        if not any(_exceeds(true[f][0], true[f][1], true[f][2], got[f][0]) for f in true if true[f][2].any()):
+            weak.append(mut)
+    assert not weak, f"{entry[0]}: mutations within the bound: {weak}"
+
+
+@pytest.mark.parametrize("entry", K.ATTN_CASES, ids=[e[0] for e in K.ATTN_CASES])
+def test_attention_mutations_leave_bound(entry):
+    """One key fewer and a 2 % wrong softmax scale leave the attention bound (wherever an utterance has two or more keys: over a
+    single key the softmax is 1 whatever the scores)."""
+    p = K.build_case(entry)
+    r, t, m = K.attn_ref(p)["out"]
+    if max(p.d["_lens"]) > 1:
+        assert _exceeds(r, t, m, K.attn_ref(p, "len_minus1")["out"][0])
+        p.d["scale"] *= 1.02
+        assert _exceeds(r, t, m, K.attn_ref(p)["out"][0])

@@ -6,6 +6,9 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 LIB = os.path.join(HERE, "libzvx.so")
+# test-only launcher shim (tests/native/zvx_ktest.hip): tests/test_kernels_gpu.py drives the launchers through it
+KTEST_SRC = os.path.join(os.path.dirname(HERE), "tests", "native", "zvx_ktest.hip")
+KTEST_LIB = os.path.join(HERE, "libzvx_ktest.so")
 SOURCES = ["gemm.hip", "resstream.hip", "pairstream.hip", "narrowstage.hip", "attention.hip", "ops.hip", "zvx.hip"]
 # translation units: (object stem, source, extra -D flags).  gemm.hip is compiled as two units side by side (its fused ResBlock-pair kernels are
 # a third of its instantiations): a clean build takes the time of the larger half
@@ -95,6 +98,19 @@ def build(force: bool = False, verbose: bool = True) -> str:
         objs = list(ex.map(compile_one, UNITS))
     if force or _stale(LIB, objs):
         cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC"] + objs + ["-ldl", "-o", LIB]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+    # the test-only launcher shim (tests/native): its own host-code object, linked with the SAME kernel objects as libzvx.so (no
+    # recompile -- the kernels under test are the shipped ones).  Not a UNIT: libzvx.so keeps exactly its zvx_* exports.
+    ko = os.path.join(CSRC, "zvx_ktest.o")
+    if force or _stale(ko, [KTEST_SRC] + headers):
+        cmd = [hipcc] + FLAGS + ["-c", KTEST_SRC, "-o", ko]
+        if verbose:
+            print(" ".join(cmd), flush=True)
+        subprocess.check_call(cmd)
+    if force or _stale(KTEST_LIB, objs + [ko]):
+        cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", ko] + objs + ["-ldl", "-o", KTEST_LIB]
         if verbose:
             print(" ".join(cmd), flush=True)
         subprocess.check_call(cmd)

@@ -2002,12 +2002,12 @@ static void launch_slab_variant(const GemmArgs& a, dim3 grid, size_t lds, hipStr
     }
     if constexpr (EPI < 0 || !(EPI & 16)) {                        // (the decoders' compile-time form exists in half only)
         if (fullk) ZVX_LAUNCH((convslab_kernel<BM, BN, WM, WN, true, MINW, R, EPI>), grid, dim3(256), lds, stream, a);
-        else if constexpr (EPI != ZVX_EPI_FLIP) ZVX_LAUNCH((convslab_kernel<BM, BN, WM, WN, false, MINW, R, EPI>), grid, dim3(256), lds, stream, a);   // (the flipped-output form: whole K chunks only, epi_mode_of)
+        else if constexpr (EPI != ZVX_EPI_FLIP) ZVX_LAUNCH((convslab_kernel<BM, BN, WM, WN, false, MINW, R, EPI>), grid, dim3(256), lds, stream, a);   // (the flipped-output form: whole K chunks only, gemm_epi_mode_of)
     }
 }
 
 // compile-time epilogue mode of a launch (see ZVX_EPI / ZVX_EPI_DEC), or -1 when it needs the run-time epilogue
-static int epi_mode_of(const GemmArgs& a) {
+int gemm_epi_mode_of(const GemmArgs& a) {
     if (a.alpha == 1.f && !a.post_scale && a.out && a.out_dtype != a.dtype && a.dtype != DT_F32 && a.out_dtype != DT_F32 && !a.out_split3 && a.bias_mode == 1 && a.bias &&
         (a.act == ACT_NONE || a.act == ACT_LRELU) && !a.res_mode && !(a.accum && a.accum_mode) && a.out_scale == 1.f && a.K % SLAB_KC == 0 && !a.K2) return ZVX_EPI_FLIP;
     if (a.alpha != 1.f || a.post_scale || (a.out && a.out_dtype != a.dtype) || a.dtype == DT_F32 || a.out_split3 || a.bias_mode == 2) return -1;
@@ -2090,7 +2090,7 @@ static int launch_convslab(GemmArgs a, hipStream_t stream) {
     if (hl + hr > 64) {
         // every tile kernel below stages at most 64 halo rows -- but for the 256 x 128 register-ring tile with the 160-row budget of the
         // flattened 2-D convolutions, here for the closing launch of V3's first stage (C = 128, k = 7, dilation 12: residual + running sum + output)
-        if (hl + hr <= 160 && a.N % 128 == 0 && a.K % SLAB_KC == 0 && !a.K2 && !a.bflat && !a.flat_win && epi_mode_of(a) == ZVX_EPI(1, 1, 1)) {
+        if (hl + hr <= 160 && a.N % 128 == 0 && a.K % SLAB_KC == 0 && !a.K2 && !a.bflat && !a.flat_win && gemm_epi_mode_of(a) == ZVX_EPI(1, 1, 1)) {
             dim3 grid((a.N / 128) * ((a.M + 255) / 256), a.nbatch);
             const size_t lds = ((size_t)(256 + hl + hr) * SLAB_PITCH + 1023) & ~(size_t)1023;
             if (a.dtype == DT_F16) ZVX_LAUNCH((convslab_kernel<256, 128, 2, 2, true, 2, 0, ZVX_EPI(1, 1, 1), 160, true>), grid, dim3(256), lds, stream, a);
@@ -2198,7 +2198,7 @@ static int launch_convslab(GemmArgs a, hipStream_t stream) {
             size_t lds128 = ((size_t)(128 + hl + hr) * SLAB_PITCH + 1023) & ~(size_t)1023;
             const size_t stage128 = (size_t)4 * 32 * (2 * 128 + 16);
             if (lds128 < stage128) lds128 = stage128;
-            switch (epi_mode_of(a)) {
+            switch (gemm_epi_mode_of(a)) {
                 case ZVX_EPI(0, 0, 1): launch_slab_variant<128, 128, 2, 2, 2, 0, ZVX_EPI(0, 0, 1)>(a, g128, lds128, stream); break;
                 case ZVX_EPI_DEC(0): launch_slab_variant<128, 128, 2, 2, 2, 0, ZVX_EPI_DEC(0)>(a, g128, lds128, stream); break;
                 case ZVX_EPI_DEC(1): launch_slab_variant<128, 128, 2, 2, 2, 0, ZVX_EPI_DEC(1)>(a, g128, lds128, stream); break;
@@ -2210,13 +2210,13 @@ static int launch_convslab(GemmArgs a, hipStream_t stream) {
     const int ntm = (a.M + bm - 1) / bm;
     dim3 grid(ntn * ntm, a.nbatch);
     const int tn = (bn >= 128) ? 2 : 1;
-    if (a.accum_mode && a.accum && a.accum_dtype == DT_F16 && tn == 2 && !(best == 1 && epi_mode_of(a) >= 0)) return -6;   // (see epilogue_rows: acc_f16; the small-tile shapes above take it)
+    if (a.accum_mode && a.accum && a.accum_dtype == DT_F16 && tn == 2 && !(best == 1 && gemm_epi_mode_of(a) >= 0)) return -6;   // (see epilogue_rows: acc_f16; the small-tile shapes above take it)
     size_t lds = (((size_t)(bm + hl + hr) * SLAB_PITCH + 1023) & ~(size_t)1023) + (size_t)ring_slots * (bn / 32) * 1024;      // slab + weight ring (R slots x bn/32 KiB)
     const size_t stage = (size_t)4 * 32 * (tn * 128 + 16);
     if (lds < stage) lds = stage;
     switch (best) {
         case 0: launch_slab_variant<128, 256, 1, 4, 2, 0>(a, grid, lds, stream); break;      // (register-ring variant)
-        case 1: switch (epi_mode_of(a)) {                   // (always the register-ring variant: wreg)
+        case 1: switch (gemm_epi_mode_of(a)) {                   // (always the register-ring variant: wreg)
                     case ZVX_EPI(0, 0, 1): launch_slab_variant<256, 128, 2, 2, 2, 0, ZVX_EPI(0, 0, 1)>(a, grid, lds, stream); break;
                     case ZVX_EPI_FLIP: launch_slab_variant<256, 128, 2, 2, 2, 0, ZVX_EPI_FLIP>(a, grid, lds, stream); break;
                     case ZVX_EPI(1, 0, 1): launch_slab_variant<256, 128, 2, 2, 2, 0, ZVX_EPI(1, 0, 1)>(a, grid, lds, stream); break;

@@ -126,6 +126,9 @@ int launch_gemm(const GemmArgs& a, hipStream_t stream);
 void gemm_profile_events(hipEvent_t start, hipEvent_t stop);
 // the kernel variant launch_gemm / launch_resfuse would pick for these arguments (nothing is dispatched)
 int gemm_variant_of(const GemmArgs& a);
+// the compile-time epilogue a conv-slab launch of these arguments selects (ZVX_EPI / ZVX_EPI_DEC / ZVX_EPI_FLIP of gemm.hip), -1 = the
+// run-time epilogue.  Which tiles have the compile-time form is launch_convslab's choice; this is the mode it asks them for.
+int gemm_epi_mode_of(const GemmArgs& a);
 // fused HiFi-GAN ResBlock1 pair (conv1 -> lrelu -> conv2 -> + x) for C = 32 / 64 bf16; -1 if the shape is not covered
 int launch_resfuse(GemmArgs a, hipStream_t stream);
 // fused HiFi-GAN ResBlock2 (two dilated convolutions with their residuals, hifigan.py:77-82) for C = 32 / 64, k = 3 / 5 / 7; -1 if not covered
