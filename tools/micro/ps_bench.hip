@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <vector>
 using namespace zvx;
+thread_local hipEvent_t zvx_gemm_ev_start = nullptr, zvx_gemm_ev_stop = nullptr;     // the launchers' event pair (zvx_kernels.h); never armed here
 static unsigned short rbf(unsigned& s, float scale) {
     s = s * 1664525u + 1013904223u;
     float f = ((int)(s >> 8) % 2001 - 1000) * 0.001f * scale;
@@ -36,10 +37,10 @@ int main(int argc, char** argv) {
     p.slope1 = 0.1f; p.res_inv_slope = 10.f; p.out_scale = am == 1 ? 1.f / 3 : 1.f; p.slope = 0.1f; p.len = len; p.M = M; p.nbatch = B; p.prof = prof;
     hipStream_t st; hipStreamCreate(&st);
     hipEvent_t e0, e1; hipEventCreate(&e0); hipEventCreate(&e1);
-    for (int i = 0; i < 10; i++) if (!launch_pairstream(p, st, false, nullptr, nullptr)) { printf("rejected\n"); return 1; }
+    for (int i = 0; i < 10; i++) if (!launch_pairstream(p, st, false)) { printf("rejected\n"); return 1; }
     hipStreamSynchronize(st);
     hipEventRecord(e0, st);
-    for (int i = 0; i < iters; i++) launch_pairstream(p, st, false, nullptr, nullptr);
+    for (int i = 0; i < iters; i++) launch_pairstream(p, st, false);
     hipEventRecord(e1, st); hipStreamSynchronize(st);
     float ms = 0; hipEventElapsedTime(&ms, e0, e1); ms /= iters;
     const double fl = 2.0 * 2.0 * (double)B * M * C * C * nt;

@@ -17,14 +17,9 @@
 #include "mfma_util.h"
 #include "zvx_kernels.h"
 
-#include <hip/hip_ext.h>
-
 #include <type_traits>
 
 namespace zvx {
-
-static thread_local hipEvent_t g_fa_ev_start = nullptr, g_fa_ev_stop = nullptr;
-void flash_profile_events(hipEvent_t start, hipEvent_t stop) { g_fa_ev_start = start; g_fa_ev_stop = stop; }
 
 // Development switches (tools/micro/fa_bench.hip): FA_PROFILE = per-phase s_memtime totals of workgroup 0 / wave 0 -> a.prof;
 // FA_EXP cuts pieces OUT (wrong results by design, only the timing means something): 1 no softmax arithmetic, 2 no staging (global
@@ -338,13 +333,8 @@ bool launch_flash_attention(const FlashArgs& a, hipStream_t stream, bool dry_run
     const dim3 grid(((a.L + FA_BQ - 1) / FA_BQ) * a.nbatch * a.nheads), block(256);      // 1-D: the kernel deals (utterance, head, query tile) to the XCDs itself
     if (lds > 160 * 1024) return false;
     if (!lds_opt_in(a.f16 ? (const void*)flash_attn_kernel<264, true> : (const void*)flash_attn_kernel<264, false>)) return false;
-    if (a.f16) {
-        if (g_fa_ev_start) hipExtLaunchKernelGGL((flash_attn_kernel<264, true>), grid, block, lds, stream, g_fa_ev_start, g_fa_ev_stop, 0, a);
-        else hipLaunchKernelGGL((flash_attn_kernel<264, true>), grid, block, lds, stream, a);
-    } else {
-        if (g_fa_ev_start) hipExtLaunchKernelGGL((flash_attn_kernel<264, false>), grid, block, lds, stream, g_fa_ev_start, g_fa_ev_stop, 0, a);
-        else hipLaunchKernelGGL((flash_attn_kernel<264, false>), grid, block, lds, stream, a);
-    }
+    if (a.f16) hipLaunchKernelGGL((flash_attn_kernel<264, true>), grid, block, lds, stream, a);
+    else hipLaunchKernelGGL((flash_attn_kernel<264, false>), grid, block, lds, stream, a);
     return true;
 }
 
@@ -567,8 +557,7 @@ bool launch_attention_f32(const AttnF32Args& a, hipStream_t stream, bool dry_run
     auto kfn = attn_f32_kernel<264>;
     if (!lds_opt_in((const void*)kfn)) return false;
     const dim3 grid((a.L + AF_BQ - 1) / AF_BQ, a.nbatch * a.nheads), block(256);
-    if (g_fa_ev_start) hipExtLaunchKernelGGL(kfn, grid, block, lds, stream, g_fa_ev_start, g_fa_ev_stop, 0, a);
-    else hipLaunchKernelGGL(kfn, grid, block, lds, stream, a);
+    hipLaunchKernelGGL(kfn, grid, block, lds, stream, a);
     return true;
 }
 

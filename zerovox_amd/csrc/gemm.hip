@@ -24,12 +24,9 @@
 #include "mfma_util.h"
 #include "zvx_kernels.h"
 
-#include <hip/hip_ext.h>
 #include <cstring>
 #include <type_traits>
 
-// Per-launch timing without marker packets: when the caller has armed a pair of events (gemm_profile_events), the
-// dispatch itself carries them (hipExtLaunchKernelGGL start/stop events = the kernel's own begin/end timestamps).
 // (gemm.hip is compiled as TWO translation units -- zerovox_amd/build.py: -DZVX_GEMM_PART=1 = everything but the fused ResBlock-pair kernels,
 // -DZVX_GEMM_PART=2 = those kernels and launch_resfuse() -- so that a clean build takes the time of the larger half; no macro: one unit)
 #ifndef ZVX_GEMM_PART
@@ -38,20 +35,14 @@
 #define ZVX_PART_MAIN (ZVX_GEMM_PART != 2)
 #define ZVX_PART_RESFUSE (ZVX_GEMM_PART != 1)
 #if ZVX_GEMM_PART == 2
-extern thread_local hipEvent_t zvx_gemm_ev_start, zvx_gemm_ev_stop;
 extern thread_local bool zvx_gemm_dry_run;
 #else
-thread_local hipEvent_t zvx_gemm_ev_start = nullptr, zvx_gemm_ev_stop = nullptr;
+thread_local hipEvent_t zvx_gemm_ev_start = nullptr, zvx_gemm_ev_stop = nullptr;     // the launchers' shared event pair (zvx_kernels.h)
 thread_local bool zvx_gemm_dry_run = false;     // gemm_variant_of(): walk the launcher's decisions without dispatching
 #endif
-#define g_ev_start zvx_gemm_ev_start
-#define g_ev_stop zvx_gemm_ev_stop
 #define g_dry_run zvx_gemm_dry_run
 
-#define ZVX_LAUNCH(kernel, grid, block, lds, stream, ...) \
-    do { if (g_dry_run) break; \
-         if (g_ev_start) hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, g_ev_start, g_ev_stop, 0, __VA_ARGS__); \
-         else hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__); } while (0)
+#define ZVX_LAUNCH(...) do { if (!g_dry_run) ZVX_DISPATCH(__VA_ARGS__); } while (0)
 
 namespace zvx {
 
@@ -1947,7 +1938,7 @@ int launch_resfuse(GemmArgs a, hipStream_t stream) {
             p.slope1 = a.slope1; p.res_inv_slope = a.res_inv_slope; p.out_scale = a.out_scale; p.slope = a.act == ACT_LRELU ? a.slope : 1.f;
             p.f16 = a.dtype == DT_F16;
             p.len = a.out_len; p.M = a.M; p.nbatch = a.nbatch; p.force = a.no_pairstream == 2;
-            if (launch_pairstream(p, stream, g_dry_run, g_dry_run ? nullptr : g_ev_start, g_ev_stop)) return 23;
+            if (launch_pairstream(p, stream, g_dry_run)) return 23;
         }
     }
     {
@@ -2234,7 +2225,6 @@ static int launch_convslab(GemmArgs a, hipStream_t stream) {
     return 6 + best;
 }
 
-void gemm_profile_events(hipEvent_t start, hipEvent_t stop) { g_ev_start = start; g_ev_stop = stop; }
 
 int launch_gemm(const GemmArgs& a, hipStream_t stream) {
     if (a.N <= 0 || a.M <= 0 || a.nbatch <= 0) return -1;

@@ -21,14 +21,9 @@
 #include "mfma_util.h"
 #include "zvx_kernels.h"
 
-#include <hip/hip_ext.h>
-
 #include <type_traits>
 
 namespace zvx {
-
-static thread_local hipEvent_t g_ns_ev_start = nullptr, g_ns_ev_stop = nullptr;
-void narrowstage_profile_events(hipEvent_t start, hipEvent_t stop) { g_ns_ev_start = start; g_ns_ev_stop = stop; }
 
 #define NS_HB 64          // halo rows kept either side of a tile (a multiple of the 16-row block)
 #define NS_GUARD 16       // rows in front of / behind the halo that block-rounded convolutions may touch (never consumed)
@@ -298,8 +293,7 @@ static bool launch_ns(const StageArgs& a, hipStream_t stream, bool dry_run) {
     const dim3 grid(ntiles < ncu ? ntiles : ncu), block(64 * NW);
 #define NS_GO(H_) do { auto kfn = narrowstage_kernel<C, R, NW, WGPC, H_>; \
         if (!lds_opt_in((const void*)kfn)) return false; \
-        if (g_ns_ev_start) hipExtLaunchKernelGGL(kfn, grid, block, lds, stream, g_ns_ev_start, g_ns_ev_stop, 0, a, wbytes, ntm, ntiles); \
-        else hipLaunchKernelGGL(kfn, grid, block, lds, stream, a, wbytes, ntm, ntiles); } while (0)
+        ZVX_DISPATCH(kfn, grid, block, lds, stream, a, wbytes, ntm, ntiles); } while (0)
     if (a.f16) NS_GO(true); else NS_GO(false);
 #undef NS_GO
     return true;

@@ -22,8 +22,6 @@
 #include "mfma_util.h"
 #include "zvx_kernels.h"
 
-#include <hip/hip_ext.h>
-
 #include <algorithm>
 #include <type_traits>
 
@@ -455,7 +453,7 @@ __global__ __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2))) voi
 
 static int ps_ncu() { return persistent_cus(); }
 
-bool launch_pairstream(PairArgs a, hipStream_t stream, bool dry_run, hipEvent_t ev_start, hipEvent_t ev_stop) {
+bool launch_pairstream(PairArgs a, hipStream_t stream, bool dry_run) {
     if (a.C != 128 || a.ldx != a.C || a.dil < 1 || !a.W1 || !a.W2 || !a.b1 || !a.b2) return false;
     if (!(a.ntaps == 3 || a.ntaps == 7 || a.ntaps == 11)) return false;
     if ((a.out && a.ldo != a.ldx) || (a.accum && a.lda != a.ldx)) return false;     // one row offset serves x, xs and the output
@@ -483,8 +481,7 @@ bool launch_pairstream(PairArgs a, hipStream_t stream, bool dry_run, hipEvent_t 
     const dim3 grid(nsegs < nwg ? nsegs : nwg), block(512);
 #define PS_GO1(NT_, AM_, HO_, H_) do { auto kfn = pairstream128_kernel<NT_, AM_, HO_, H_>; \
         if (!lds_opt_in((const void*)kfn)) return false; \
-        if (ev_start) hipExtLaunchKernelGGL(kfn, grid, block, lds, stream, ev_start, ev_stop, 0, a); \
-        else hipLaunchKernelGGL(kfn, grid, block, lds, stream, a); return true; } while (0)
+        ZVX_DISPATCH(kfn, grid, block, lds, stream, a); return true; } while (0)
 #define PS_GO(NT_, AM_, HO_) do { if (a.f16) PS_GO1(NT_, AM_, HO_, true); else PS_GO1(NT_, AM_, HO_, false); } while (0)
 #define PS_MODE(NT_) do { if (a.out) { if (am == 0) PS_GO(NT_, 0, true); if (am == 1) PS_GO(NT_, 1, true); return false; } \
         if (am == 2) PS_GO(NT_, 2, false); if (am == 3) PS_GO(NT_, 3, false); return false; } while (0)

@@ -20,15 +20,10 @@
 #include "mfma_util.h"
 #include "zvx_kernels.h"
 
-#include <hip/hip_ext.h>
-
 #include <algorithm>
 #include <type_traits>
 
 namespace zvx {
-
-static thread_local hipEvent_t g_rs_ev_start = nullptr, g_rs_ev_stop = nullptr;
-void resstream_profile_events(hipEvent_t start, hipEvent_t stop) { g_rs_ev_start = start; g_rs_ev_stop = stop; }
 
 #define RS_RD 64          // rows per DMA block
 #define RS_PF 2           // DMA blocks are requested this many steps before role 0 needs them
@@ -507,8 +502,7 @@ static bool launch_rs(StreamArgs& a, hipStream_t stream, bool dry_run) {
     const int am = a.accum ? a.accum_mode : 0;
 #define RS_GO1(AM_, HO_, H_) do { auto kfn = resstream_kernel<C, NT, NPAIR, RSPLIT, AM_, HO_, DP, H_>; \
         if (!lds_opt_in((const void*)kfn)) return false; \
-        if (g_rs_ev_start) hipExtLaunchKernelGGL(kfn, grid, block, lds, stream, g_rs_ev_start, g_rs_ev_stop, 0, a); \
-        else hipLaunchKernelGGL(kfn, grid, block, lds, stream, a); return true; } while (0)
+        ZVX_DISPATCH(kfn, grid, block, lds, stream, a); return true; } while (0)
 #define RS_GO(AM_, HO_) do { if (a.f16) RS_GO1(AM_, HO_, true); else RS_GO1(AM_, HO_, false); } while (0)
     if (a.out) { if (am == 0) RS_GO(0, true); if (am == 1) RS_GO(1, true); return false; }
     if (am == 2) RS_GO(2, false);

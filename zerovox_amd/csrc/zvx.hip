@@ -6,7 +6,6 @@
 #include "../../include/zvx.h"
 #include "zvx_kernels.h"
 
-#include <hip/hip_ext.h>
 #include <dlfcn.h>
 #include <math.h>
 #include <cmath>
@@ -271,50 +270,58 @@ struct zvx_ctx {
     void stage_begin(int s) { if (profile) { HIPCHK(hipEventRecord(stage_ev[s][0], stream)); } }
     void stage_end(int s) { if (profile) { HIPCHK(hipEventRecord(stage_ev[s][1], stream)); stage_used[s] = true; } }
 
+    // One dispatch that carries its own start / stop events (profile 2; no marker packets on the stream): arm the launchers' event pair,
+    // launch, disarm on every way out (a throwing `launch` included), and queue the GemmEvent that `describe` fills in.  `vid` names the
+    // variant the profile_only filter compares (asked only while that filter is set); `launch` returns the variant id that ran and throws
+    // where it cannot.
+    template <typename V, typename L, typename D>
+    void profiled(V&& vid, L&& launch, D&& describe) {
+        const bool prof = profile >= 2 && (profile_only < 0 || vid() == profile_only);
+        if (!prof) { launch(); return; }
+        GemmEvent ev{};
+        ev.a = new_event(); ev.b = new_event();
+        struct Armed { Armed(hipEvent_t a, hipEvent_t b) { profile_events(a, b); } ~Armed() { profile_events(nullptr, nullptr); } };
+        ev.variant = [&] { Armed armed(ev.a, ev.b); return launch(); }();
+        describe(ev);
+        ev.tag = tag;
+        pending.push_back(ev);
+    }
     void gemm(GemmArgs& a) {
         if (a.flops <= 0) a.flops = 2.0 * (double)a.M * a.nbatch * a.nheads * (double)a.N * ((double)a.K * a.ntaps + (double)a.K2);
         if (!a.Wp && a.dtype != DT_F32) { auto it = packed.find(a.W); if (it != packed.end()) a.Wp = it->second; }
         a.slab_small = slab_small | (spk_s2_fuse ? 0 : 32); a.xcd_flat = slab_flat;      // (bit 5: no conv2d_s2_kernel -- spk_s2_fuse 0 is the gathered-row launch set for BOTH level transitions)
-        GemmEvent ev{};
-        const bool prof = profile >= 2 && (profile_only < 0 || gemm_variant_of(a) == profile_only);
-        if (prof) { ev.a = new_event(); ev.b = new_event(); gemm_profile_events(ev.a, ev.b); }
-        int id = a.fused == 2 ? launch_rb2fuse(a, stream) : (a.fused ? launch_resfuse(a, stream) : launch_gemm(a, stream));
-        if (prof) gemm_profile_events(nullptr, nullptr);
-        if (id < 0) fail(ZVX_E_INVALID, "launch_gemm rejected shape M=%d N=%d K=%d taps=%d", a.M, a.N, a.K, a.ntaps);
-        if (sat_check && a.nheads == 1) {                   // (audit mode: the attention products run fused, their output is scanned by fft_block)
-            sat_scan(a.out, a.out_dtype, a.o_bs, a.ldo, a.nbatch, a.M, a.out_len, a.N);
-            if (a.accum && (a.accum_mode & 2)) sat_scan(a.accum, a.accum_dtype, a.a_bs, a.lda, a.nbatch, a.M, a.out_len, a.N);
-        }
-        if (prof) {
-            ev.variant = id; ev.flops = a.flops; ev.rows = (long)a.M * a.nbatch * a.nheads; ev.N = a.N; ev.K = a.K; ev.taps = a.ntaps; ev.res = a.res_mode; ev.fused = a.fused;
+        profiled([&] { return gemm_variant_of(a); }, [&] {
+            const int id = a.fused == 2 ? launch_rb2fuse(a, stream) : (a.fused ? launch_resfuse(a, stream) : launch_gemm(a, stream));
+            if (id < 0) fail(ZVX_E_INVALID, "launch_gemm rejected shape M=%d N=%d K=%d taps=%d", a.M, a.N, a.K, a.ntaps);
+            return id;
+        }, [&](GemmEvent& ev) {
+            ev.flops = a.flops; ev.rows = (long)a.M * a.nbatch * a.nheads; ev.N = a.N; ev.K = a.K; ev.taps = a.ntaps; ev.res = a.res_mode; ev.fused = a.fused;
             const double esz = dtype_size(a.dtype);
             // algorithmic bytes: input rows + weights + everything the epilogue reads and writes (output, residual, running sum)
             const double cells = (double)a.M * a.nbatch * a.nheads * a.N;
             ev.bytes = ((double)a.M * a.nbatch * a.nheads) * (double)(a.K + a.K2) * esz + (double)a.N * ((double)a.K * a.ntaps + a.K2) * esz * (a.fused ? 2 : 1) +
                        (a.out ? cells * dtype_size(a.out_dtype) : 0.0) + ((a.res_mode && !a.fused) ? cells * dtype_size(a.res_dtype) : 0.0) +
                        ((a.accum && (a.accum_mode & 1)) ? cells * dtype_size(a.accum_dtype) : 0.0) + ((a.accum && (a.accum_mode & 2)) ? cells * dtype_size(a.accum_dtype) : 0.0);
-            ev.tag = tag;
-            pending.push_back(ev);
+        });
+        if (sat_check && a.nheads == 1) {                   // (audit mode: the attention products run fused, their output is scanned by fft_block)
+            sat_scan(a.out, a.out_dtype, a.o_bs, a.ldo, a.nbatch, a.M, a.out_len, a.N);
+            if (a.accum && (a.accum_mode & 2)) sat_scan(a.accum, a.accum_dtype, a.a_bs, a.lda, a.nbatch, a.M, a.out_len, a.N);
         }
     }
     // streaming ResBlock chain (resstream.hip); returns false (nothing launched) when the shape is not covered
     bool run_stream(StreamArgs& a) {
         const int id = launch_resstream(a, this->stream, true);
         if (id < 0) return false;
-        GemmEvent ev{};
-        const bool prof = profile >= 2 && (profile_only < 0 || id == profile_only);
-        if (prof) { ev.a = new_event(); ev.b = new_event(); resstream_profile_events(ev.a, ev.b); }
-        const int id2 = launch_resstream(a, this->stream, false);
-        if (prof) resstream_profile_events(nullptr, nullptr);
-        if (id2 < 0) fail(ZVX_E_INVALID, "launch_resstream rejected a shape its dry run accepted (C=%d k=%d pairs=%d)", a.C, a.ntaps, a.npair);
-        if (prof) {
+        profiled([&] { return id; }, [&] {
+            const int id2 = launch_resstream(a, this->stream, false);
+            if (id2 < 0) fail(ZVX_E_INVALID, "launch_resstream rejected a shape its dry run accepted (C=%d k=%d pairs=%d)", a.C, a.ntaps, a.npair);
+            return id2;
+        }, [&](GemmEvent& ev) {
             const double rows = (double)a.M * a.nbatch;
-            ev.variant = id2; ev.flops = 2.0 * 2.0 * a.npair * rows * a.C * a.C * a.ntaps; ev.rows = (long)rows; ev.N = a.C; ev.K = a.C; ev.taps = a.ntaps;
+            ev.flops = 2.0 * 2.0 * a.npair * rows * a.C * a.C * a.ntaps; ev.rows = (long)rows; ev.N = a.C; ev.K = a.C; ev.taps = a.ntaps;
             ev.res = a.accum_mode; ev.fused = 10 + a.npair;
             ev.bytes = rows * a.C * 2.0 * (1 + (a.out ? 1 : 0) + ((a.accum && (a.accum_mode & 1)) ? 1 : 0) + ((a.accum && (a.accum_mode & 2)) ? 1 : 0));
-            ev.tag = tag;
-            pending.push_back(ev);
-        }
+        });
         return true;
     }
     // the HBM-bound helpers (norms, gathers, conv_post ...): event-timed as a group when every launch is being profiled
@@ -1272,10 +1279,17 @@ void run_decode(zvx_ctx* c, const float* feats, const float* spk_d, const int* L
 // every tensor a later conv consumes through leaky_relu(., 0.1) is written as leaky_relu(x); the raw
 // residual is recovered exactly-enough by the inverse map in the consumer's epilogue (res_mode 2).
 // ------------------------------------------------------------------------------------------------
-void run_vocoder(zvx_ctx* c, const float* mel, int ldm, int Lmel_max, const int* mel_len_host, const int* P_host, int B,
-                 void* wav_dev, long wav_stride, int pcm16) {
-    // 16-bit mode: IEEE half (round 5) -- f16 copies of the weights, f16 activations / running sum, the f16 MFMA at the bf16 rate and 8x
-    // less rounding error per tensor; every store saturates (MODE.FP16_OVFL inside the kernels).  zvx_set_int("voc_f16", 0): bf16 (A/B)
+// The dtype of every arithmetic domain of the generator (0 .. number of stages).
+// 16-bit mode: IEEE half -- f16 copies of the weights, f16 activations / running sum, the f16 MFMA at the bf16 rate and 8x
+// less rounding error per tensor; every store saturates (MODE.FP16_OVFL inside the kernels).  zvx_set_int("voc_f16", 0): bf16 (A/B)
+// The 16-bit arithmetic is chosen PER STAGE (zvx_set_int("voc_f16_stages", mask)): domain 0 = the padded mel, conv_pre and its
+// output; domain i = everything of upsampling stage i (the ConvTranspose's OUTPUT, the ResBlocks' tensors, weights and running sum, the
+// stage's result).  A ConvTranspose reads domain i - 1 with that domain's weights and writes domain i (the run-time epilogue converts:
+// one rounding either way).  Bit k of the mask: domain k in IEEE half, else bf16.
+// Default (mask -1): half everywhere except a ResBlock1 stage of 128 channels -- the pair kernel's stage (HiFi-GAN V1's second): 43 % of
+// that generator's matrix work, where the f16 multiplier array's extra power is 0.3 of the 0.8-1.0 ms the all-half generator costs at
+// the board's power limit, for 1/5 of the error budget (tools/ab_voc_stages.py, tools/vocoder_error_budget.py)
+std::vector<int> voc_domains(zvx_ctx* c) {
     if (c->voc_h16_ok < 0) {
         // decided once: the half copies exist only for 3-D weights with K % 8 == 0 (upload_weights); a generator with a narrower tensor
         // (e.g. a 4-channel last stage) runs entirely on the bf16 kernels, which need no packed copies
@@ -1284,24 +1298,338 @@ void run_vocoder(zvx_ctx* c, const float* mel, int ldm, int Lmel_max, const int*
             if (kv.first.rfind("voc.", 0) == 0 && kv.second.kind == 'w' && kv.second.dims.size() == 3 && !c->has(kv.first + ".h16")) c->voc_h16_ok = 0;
     }
     const bool half_ok = c->dt == DT_BF16 && c->voc_f16 && c->voc_h16_ok == 1 && c->has("voc.pre_w.h16");
-    const int nm = c->n_mels;
-    // The 16-bit arithmetic is chosen PER STAGE (round 6; zvx_set_int("voc_f16_stages", mask)): domain 0 = the padded mel, conv_pre and its
-    // output; domain i = everything of upsampling stage i (the ConvTranspose's OUTPUT, the ResBlocks' tensors, weights and running sum, the
-    // stage's result).  A ConvTranspose reads domain i - 1 with that domain's weights and writes domain i (the run-time epilogue converts:
-    // one rounding either way).  Bit k of the mask: domain k in IEEE half, else bf16.
-    // Default (mask -1): half everywhere except a ResBlock1 stage of 128 channels -- the pair kernel's stage (HiFi-GAN V1's second): 43 % of
-    // that generator's matrix work, where the f16 multiplier array's extra power is 0.3 of the 0.8-1.0 ms the all-half generator costs at
-    // the board's power limit, for 1/5 of the error budget (tools/ab_voc_stages.py, tools/vocoder_error_budget.py)
     int mask = c->voc_f16_stages;
     if (mask < 0) {
         mask = 0x7fffffff;
         int cw = c->voc_c0;
         for (int i = 0; i < (int)c->voc_rates.size(); i++) { cw /= 2; if (cw == 128 && c->voc_resblock == 1) mask &= ~(1 << (i + 1)); }
     }
-    auto dom = [&](int k) -> int { return (half_ok && ((mask >> k) & 1)) ? (int)DT_F16 : c->dt; };
-    auto vtd = [&](const std::string& n, int d) -> const Tensor& { return c->t(d == DT_F16 ? n + ".h16" : n); };      // a contraction weight in a domain's dtype
+    std::vector<int> dom(c->voc_rates.size() + 1);
+    for (size_t k = 0; k < dom.size(); k++) dom[k] = (half_ok && ((mask >> k) & 1)) ? (int)DT_F16 : c->dt;
+    return dom;
+}
+const Tensor& voc_weight(zvx_ctx* c, const std::string& n, int d) { return c->t(d == DT_F16 ? n + ".h16" : n); }      // a contraction weight in a domain's dtype
+
+// what the steps of one run_vocoder call share: the batch, the ResBlocks per stage, the per-stage row counts and the work buffers
+struct VocCall {
+    int B, Pmax, nk;
+    const int* lens_d;                     // [mel_len | P | P x rate_0 | P x rate_0 x rate_1 ...][B]: the input rows of stage i start at (i + 1) B
+    void *A, *X0, *T1, *PP[2], *XS;        // stage input / upsampled stage tensor (both activated), pair temporaries, running sum over the ResBlocks of a stage
+    bool side_ok;                          // single requests: the 2nd / 3rd ResBlock of a stage run beside the 1st (SideHop), on temporaries of their own
+    void* sideT1[2]; void* sidePP[2][2];
+};
+// upsampling stage i: Cin channels x rows_in rows (valid: len_in[b]) of domain dt_in -> Cout x rows (len[b]) of domain dt
+struct VocStage {
+    int i, Cin, Cout, rows_in, rows;
+    const int* len_in; const int* len;
+    int dt_in, dt;
+    float next_slope;                      // the leaky-ReLU the stage's result is stored under (its consumer's)
+};
+
+// The convolutions of ResBlock j of a stage, in the stage's dtype: per dilation t the (c1, c2) pair of a ResBlock1 (hifigan.py:49-56) or
+// the one convolution of a ResBlock2 (c1; c2 stays empty -- hifigan.py:77-82).  The ONE place that spells the tensors' names.
+struct RbConv { std::string name; const Tensor* w = nullptr; const void* packed = nullptr; const float* bias = nullptr; };   // packed: the fragment-order copy, if any
+struct RbWeights { std::string name; std::vector<RbConv> c1, c2; };
+RbWeights voc_rb_weights(zvx_ctx* c, const VocCall& v, const VocStage& s, int j) {
+    RbWeights w;
+    w.name = "voc.rb" + std::to_string(s.i * v.nk + j);
+    auto conv = [&](const char* which, int t) {
+        RbConv r;
+        r.name = w.name + which + std::to_string(t);
+        r.w = &voc_weight(c, r.name + "_w", s.dt);
+        auto it = c->packed.find(r.w->dev);
+        if (it != c->packed.end()) r.packed = it->second;
+        r.bias = c->pf(r.name + "_b");
+        return r;
+    };
+    for (int t = 0; t < (int)c->voc_rb_d[j].size(); t++) {
+        if (c->voc_resblock == 1) { w.c1.push_back(conv(".c1_", t)); w.c2.push_back(conv(".c2_", t)); }
+        else w.c1.push_back(conv(".c_", t));
+    }
+    return w;
+}
+
+// How the LAST launch of ResBlock j closes a stage of nk blocks: xs (+)= resblock output -- the first block writes the running sum, the
+// middle ones add to it, the last adds, scales by 1 / nk, applies the next stage's leaky-ReLU and writes the stage output (x = xs /
+// num_kernels, stored activated for the next stage); a single block needs no running sum.
+struct StageClose { int accum_mode; bool writes_out; };   // accum_mode: bit 0 v += xs, bit 1 xs = v
+StageClose stage_close(int j, int nk) {
+    if (nk == 1) return {0, true};
+    return {j == 0 ? 2 : (j < nk - 1 ? 3 : 1), j == nk - 1};
+}
+template <typename Args>                                  // GemmArgs or StreamArgs (which has no act / accum_dtype: its output is always activated with `slope`)
+void close_stage(Args& a, const StageClose& cl, const VocCall& v, const VocStage& s) {
+    a.accum = cl.accum_mode ? v.XS : nullptr; a.accum_mode = cl.accum_mode; a.a_bs = (long)s.rows * s.Cout; a.lda = s.Cout;
+    if (cl.writes_out) { a.out = v.A; a.out_scale = 1.0f / v.nk; a.slope = s.next_slope; }
+    else a.out = nullptr;
+    if constexpr (std::is_same<Args, GemmArgs>::value) { a.accum_dtype = s.dt; if (cl.writes_out) a.act = ACT_LRELU; }
+}
+
+// conv_pre, stored as leaky_relu(x, 0.1) (its only consumer, hifigan.py:115-117)
+void voc_conv_pre(zvx_ctx* c, const VocCall& v, const void* vin, int dt) {
+    const int nm = c->n_mels, Pmax = v.Pmax;
+    const int* P_d = v.lens_d + v.B;
+    GemmArgs a = gemm_base(dt);
+    a.X = vin; a.x_bs = (long)Pmax * nm; a.ldx = nm; a.W = voc_weight(c, "voc.pre_w", dt).dev; a.ldw = nm; a.w_ts = (long)c->voc_c0 * nm;
+    a.M = Pmax; a.N = c->voc_c0; a.K = nm; a.nbatch = v.B; a.in_len = P_d; a.out_len = P_d;
+    set_taps_1d(a, c->t("voc.pre_w").dim(0), 1);
+    a.bias = c->pf("voc.pre_b"); a.bias_mode = 1; a.act = ACT_LRELU; a.slope = 0.1f;
+    a.out = v.A; a.o_bs = (long)Pmax * c->voc_c0; a.ldo = c->voc_c0;
+    c->gemm(a);
+}
+
+// ConvTranspose1d as a polyphase GEMM: out[t][ph*Cout+co]                  hifigan.py:118
+void voc_upsample(zvx_ctx* c, const VocCall& v, const VocStage& s) {
+    const int u = c->voc_rates[s.i], ku = c->voc_ksizes[s.i], B = v.B, Cin = s.Cin, Cout = s.Cout, rows_in = s.rows_in, dt_in = s.dt_in;
+    const std::string up = "voc.up" + std::to_string(s.i);
+    GemmArgs a = gemm_base(dt_in);
+    a.out_dtype = s.dt;
+    a.X = v.A; a.x_bs = (long)rows_in * Cin; a.ldx = Cin; a.ldw = Cin;
+    a.M = rows_in; a.K = Cin; a.nbatch = B; a.in_len = s.len_in; a.out_len = s.len_in;
+    a.bias_mode = 1; a.act = ACT_LRELU; a.slope = 0.1f;
+    a.o_bs = (long)rows_in * u * Cout; a.ldo = u * Cout;
+    if (dt_in != DT_F32 && c->has(up + "_wlo")) {
+        // k = 2u: two 2-tap GEMMs over half the phases each (rows t-1, t / rows t, t+1) instead of one 3-tap GEMM
+        const int hc = (u / 2) * Cout;
+        a.N = hc; a.ntaps = 2; a.w_ts = (long)hc * Cin; a.flops = 2.0 * B * (double)rows_in * Cin * Cout * ku / 2;
+        a.W = voc_weight(c, up + "_wlo", dt_in).dev; a.dv[0] = -1; a.dv[1] = 0;
+        a.bias = c->pf(up + "_b"); a.out = v.X0;
+        c->gemm(a);
+        a.Wp = nullptr;
+        a.W = voc_weight(c, up + "_whi", dt_in).dev; a.dv[0] = 0; a.dv[1] = 1;
+        a.bias = c->pf(up + "_b") + hc; a.out = (char*)v.X0 + (size_t)hc * c->es();
+        c->gemm(a);
+    } else {
+        a.W = voc_weight(c, up + "_w", dt_in).dev; a.w_ts = (long)u * Cout * Cin; a.N = u * Cout;
+        a.ntaps = 3; a.dv[0] = -1; a.dv[1] = 0; a.dv[2] = 1;
+        a.bias = c->pf(up + "_b"); a.out = v.X0;
+        a.flops = 2.0 * B * (double)rows_in * Cin * Cout * ku;
+        c->gemm(a);
+    }
+}
+
+// narrowstage.hip's fragment-order weights and biases of a stage (convolution 6 j + 2 t + {0: conv1, 1: conv2}), per (stage, dtype): built on first use
+const zvx_ctx::NsWeights& voc_narrow_weights(zvx_ctx* c, const VocCall& v, const VocStage& s) {
+    const int Cout = s.Cout, nk = v.nk;
+    const std::string key = "voc.ns." + std::to_string(s.i) + (s.dt == DT_F16 ? ".h16" : "");
+    auto it = c->ns_weights.find(key);
+    if (it != c->ns_weights.end()) return it->second;
+    zvx_ctx::NsWeights nw;
+    int nfrag = 0;
+    for (int j = 0; j < nk; j++) for (int q = 0; q < 6; q++) { nw.woff[6 * j + q] = nfrag; nfrag += narrowstage_steps(Cout, c->voc_rb_k[j]); }
+    nw.W = c->buf(key + ".w", (size_t)nfrag * 1024);
+    nw.bias = c->fbuf(key + ".b", (size_t)6 * nk * Cout);
+    for (int j = 0; j < nk; j++) {
+        const RbWeights w = voc_rb_weights(c, v, s, j);
+        for (int t = 0; t < 3; t++)
+            for (int q = 0; q < 2; q++) {
+                const RbConv& cv = q ? w.c2[t] : w.c1[t];
+                if (cv.w->dims.size() != 3 || cv.w->dim(0) != c->voc_rb_k[j] || cv.w->dim(1) != Cout || cv.w->dim(2) != Cout) fail(ZVX_E_MANIFEST, "weights: '%s' has an unexpected shape", cv.name.c_str());
+                const int ci = 6 * j + 2 * t + q;
+                launch_pack_narrow(cv.w->dev, c->voc_rb_k[j], Cout, (char*)nw.W + (size_t)nw.woff[ci] * 1024, c->stream);
+                HIPCHK(hipMemcpyAsync(nw.bias + (size_t)ci * Cout, cv.bias, (size_t)Cout * 4, hipMemcpyDeviceToDevice, c->stream));
+            }
+    }
+    return c->ns_weights.emplace(key, nw).first->second;
+}
+
+// narrow stages (C = 16 / 8: HiFi-GAN V2's last two): all ResBlocks of the stage, their mean and the next stage's activation in ONE
+// launch -- the stage tensor crosses HBM once in, once out (narrowstage.hip).  false: not covered, nothing launched
+bool voc_narrow_stage(zvx_ctx* c, const VocCall& v, const VocStage& s) {
+    const int Cout = s.Cout, nk = v.nk, rows = s.rows;
+    if (!c->use_stagefuse || c->sat_check || c->voc_resblock != 1 || s.dt == DT_F32 || (Cout != 16 && Cout != 8) || nk < 1 || nk > 3) return false;
+    for (int j = 0; j < nk; j++) if (c->voc_rb_d[j].size() != 3) return false;
+    const zvx_ctx::NsWeights& nw = voc_narrow_weights(c, v, s);
+    StageArgs sa;
+    memset(&sa, 0, sizeof sa);
+    sa.X = v.X0; sa.x_bs = (long)rows * Cout; sa.ldx = Cout; sa.W = nw.W; sa.bias = nw.bias;
+    memcpy(sa.woff, nw.woff, sizeof sa.woff);
+    sa.C = Cout; sa.nk = nk;
+    for (int j = 0; j < nk; j++) { sa.ks[j] = c->voc_rb_k[j]; for (int t = 0; t < 3; t++) sa.dil[j][t] = c->voc_rb_d[j][t]; }
+    sa.out = v.A; sa.o_bs = (long)rows * Cout; sa.ldo = Cout;
+    sa.slope1 = 0.1f; sa.res_inv_slope = 10.0f; sa.slope = s.next_slope;
+    sa.len = s.len; sa.M = rows; sa.nbatch = v.B; sa.f16 = s.dt == DT_F16;
+    if (!launch_narrowstage(sa, c->stream, true)) return false;
+    const int vid = Cout == 16 ? 24 : 25;
+    c->profiled([&] { return vid; }, [&] {
+        if (!launch_narrowstage(sa, c->stream, false)) fail(ZVX_E_INVALID, "launch_narrowstage rejected a stage its dry run accepted (C=%d)", Cout);
+        return vid;
+    }, [&](GemmEvent& ev) {
+        double ksum = 0; for (int j = 0; j < nk; j++) ksum += c->voc_rb_k[j];
+        const double rws = (double)rows * v.B;
+        ev.flops = 2.0 * rws * Cout * Cout * 6.0 * ksum; ev.rows = (long)rws; ev.N = Cout; ev.K = Cout; ev.taps = (int)ksum; ev.fused = 100 + nk;
+        ev.bytes = rws * Cout * 2.0 * 2.0;
+    });
+    return true;
+}
+
+// Single requests: the ResBlocks of a stage only meet in the running sum, which their LAST pair updates.  Everything
+// before that (two of three pairs) runs on a stream of its own for the 2nd and 3rd ResBlock, with its own temporaries;
+// the last pairs stay on the main stream in the order 1, 2, 3, so xs accumulates exactly as before (bit-identical).
+// The critical path of a per-pair stage drops from 18 to 10 launches.
+// voc_side_begin: once per stage, behind the upsampling; SideHop: one per ResBlock, owns c->stream while the block is issued and puts
+// the main stream back when it leaves scope (an exception included).  aux == nullptr: the block stays on the main stream.
+void voc_side_begin(zvx_ctx* c) {
+    for (int q = 0; q < 2; q++) if (!c->voc_aux[q]) HIPCHK(hipStreamCreateWithFlags(&c->voc_aux[q], hipStreamNonBlocking));
+    for (int q = 0; q < 3; q++) if (!c->voc_ev[q]) HIPCHK(hipEventCreateWithFlags(&c->voc_ev[q], hipEventDisableTiming));
+    HIPCHK(hipEventRecord(c->voc_ev[0], c->stream));      // the stage input (and everything the previous stage read) is settled
+}
+struct SideHop {
+    zvx_ctx* const c; hipStream_t const main_stream, aux; hipEvent_t const done; bool on_aux = false;
+    SideHop(zvx_ctx* c_, hipStream_t aux_, hipEvent_t done_) : c(c_), main_stream(c_->stream), aux(aux_), done(done_) {
+        if (aux) HIPCHK(hipStreamWaitEvent(aux, c->voc_ev[0], 0));
+    }
+    ~SideHop() { c->stream = main_stream; }
+    void to_aux() { if (aux && !on_aux) { c->stream = aux; on_aux = true; } }
+    void to_main() {
+        if (on_aux) {
+            HIPCHK(hipEventRecord(done, aux));
+            c->stream = main_stream; on_aux = false;
+            HIPCHK(hipStreamWaitEvent(main_stream, done, 0));
+        }
+    }
+};
+
+// ResBlock j of a stage: reads X0, and closes the stage (stage_close) with its last launch.  Tried in this order: the whole block as one
+// streaming launch; for three pairs the first two + the last one as streaming launches; a fused ResBlock2; then pair by pair (a fused pair
+// or two launches each).  A new way to run a block belongs HERE, on top of voc_rb_weights, close_stage and the context's profiled launches.
+void voc_resblock(zvx_ctx* c, const VocCall& v, const VocStage& s, int j) {
+    const int B = v.B, rows = s.rows, Cout = s.Cout, dt = s.dt;
+    const bool side = v.side_ok && j >= 1;
+    SideHop hop(c, side ? c->voc_aux[j - 1] : nullptr, side ? c->voc_ev[j] : nullptr);
+    void* const T1s = side ? v.sideT1[j - 1] : v.T1;
+    void* const* const PPs = side ? v.sidePP[j - 1] : v.PP;
+    const int k = c->voc_rb_k[j];
+    const std::vector<int>& dil = c->voc_rb_d[j];
+    const int nd = (int)dil.size();
+    const RbWeights w = voc_rb_weights(c, v, s, j);
+    const StageClose close = stage_close(j, v.nk);
+    const void* cur = v.X0;
+    int pp = 0;
+    int t_first = 0;
+    if (c->voc_resblock == 1 && dt != DT_F32 && c->use_resstream && !c->sat_check && nd >= 1 && nd <= 3) {
+        // whole ResBlock (or its first two pairs + the last one) as streaming launches: the stage tensor crosses HBM once
+        bool packed_ok = true;
+        for (int t = 0; t < nd; t++) packed_ok = packed_ok && w.c1[t].packed && w.c2[t].packed;
+        auto chain = [&](int t0, int np, const void* in, bool closes) {
+            StreamArgs sa;
+            memset(&sa, 0, sizeof sa);
+            sa.X = in; sa.x_bs = (long)rows * Cout; sa.ldx = Cout; sa.C = Cout; sa.ntaps = k; sa.npair = np;
+            for (int q = 0; q < np; q++) {
+                sa.W1[q] = w.c1[t0 + q].packed; sa.W2[q] = w.c2[t0 + q].packed;
+                sa.b1[q] = w.c1[t0 + q].bias; sa.b2[q] = w.c2[t0 + q].bias;
+                sa.dil[q] = dil[t0 + q];
+            }
+            sa.seg_min = c->rs_seg_min; sa.f16 = dt == DT_F16;
+            if (c->rs_prof) sa.prof = (long long*)c->buf("rs.prof." + w.name + "." + std::to_string(t0), 16 * 16 * 8);   // RS_PROFILE builds only
+            sa.slope1 = 0.1f; sa.res_inv_slope = 10.0f; sa.out_scale = 1.f; sa.slope = 0.1f;
+            sa.len = s.len; sa.M = rows; sa.nbatch = B; sa.o_bs = (long)rows * Cout; sa.ldo = Cout; sa.a_bs = (long)rows * Cout; sa.lda = Cout;
+            if (closes) close_stage(sa, close, v, s);
+            else sa.out = PPs[pp];
+            return sa;
+        };
+        if (packed_ok) {
+            StreamArgs whole = chain(0, nd, v.X0, true);
+            hop.to_main();
+            if (c->run_stream(whole)) t_first = nd;
+            else if (nd == 3) {
+                StreamArgs head = chain(0, 2, v.X0, false);
+                StreamArgs probe = chain(2, 1, PPs[pp], true);
+                if (launch_resstream(head, c->stream, true) >= 0 && launch_resstream(probe, c->stream, true) >= 0) {
+                    hop.to_aux();
+                    c->run_stream(head);
+                    cur = PPs[pp]; pp ^= 1;
+                    StreamArgs tail = chain(2, 1, cur, true);
+                    hop.to_main();
+                    c->run_stream(tail);
+                    t_first = nd;
+                }
+            }
+        }
+    }
+    auto rb_base = [&] {
+        GemmArgs a = gemm_base(dt);
+        a.M = rows; a.N = Cout; a.K = Cout; a.nbatch = B; a.in_len = s.len; a.out_len = s.len; a.ldw = Cout; a.w_ts = (long)Cout * Cout;
+        a.x_bs = (long)rows * Cout; a.ldx = Cout; a.o_bs = (long)rows * Cout; a.ldo = Cout;
+        return a;
+    };
+    if (c->voc_resblock == 2 && nd == 2 && dt != DT_F32 && c->use_rb2fuse && !c->sat_check && (Cout == 32 || Cout == 64) && w.c1[0].packed && w.c1[1].packed) {
+        // a whole ResBlock2 (hifigan.py:77-82: x1 = x + c_0(lrelu(x)); x2 = x1 + c_1(lrelu(x1))) as ONE launch: lrelu(x1) stays in LDS
+        // (rb2fuse_kernel) -- two trips of the stage tensor per block instead of six
+        GemmArgs a = rb_base();
+        a.X = v.X0; a.W = w.c1[1].w->dev; a.Wp = w.c1[1].packed; a.Wp2 = w.c1[0].packed;
+        a.bias1 = w.c1[0].bias; a.slope1 = 0.1f; a.fused = 2;
+        set_taps_1d(a, k, dil[1]);
+        for (int q = 0; q < k; q++) a.dv1[q] = (q - (k - 1) / 2) * dil[0];
+        a.bias = w.c1[1].bias; a.bias_mode = 1;
+        a.res = v.X0; a.r_bs = (long)rows * Cout; a.ldr = Cout; a.res_mode = 2; a.res_inv_slope = 10.0f; a.res_dtype = dt;
+        close_stage(a, close, v, s);
+        a.flops = 2.0 * 2.0 * B * (double)rows * Cout * Cout * k;
+        if (gemm_variant_of(a) >= 0) { hop.to_main(); c->gemm(a); t_first = nd; }
+    }
+    for (int t = t_first; t < nd; t++) {
+        const bool last = (t == nd - 1);
+        if (last) hop.to_main(); else hop.to_aux();
+        // what the LAST conv of the iteration does with its result: + bias + x (raw residual recovered from the activated
+        // input), then either the next iteration's input (activated) or the stage's running sum / mean
+        auto rb_tail = [&](GemmArgs& a) {
+            a.bias_mode = 1;
+            a.res = cur; a.r_bs = (long)rows * Cout; a.ldr = Cout; a.res_mode = 2; a.res_inv_slope = 10.0f; a.res_dtype = dt;
+            if (last) close_stage(a, close, v, s);
+            else { a.act = ACT_LRELU; a.slope = 0.1f; a.out = PPs[pp]; }
+        };
+        GemmArgs a = rb_base();
+        if (c->voc_resblock == 1) {
+            const RbConv& c1 = w.c1[t]; const RbConv& c2 = w.c2[t];
+            bool fuse = dt != DT_F32 && !c->sat_check && c1.packed && c2.packed;
+            if (fuse) {
+                // one launch: xt = lrelu(c1(x_act)+b1) stays in LDS; x' = c2(xt) + b2 + x      hifigan.py:51-55
+                a.X = cur; a.W = c2.w->dev; a.Wp = c2.packed; a.Wp2 = c1.packed;
+                a.bias1 = c1.bias; a.slope1 = 0.1f; a.fused = 1;
+                a.no_pairstream = c->use_pairstream <= 0 ? 1 : (c->use_pairstream == 3 ? 2 : 0);
+                set_taps_1d(a, k, 1);
+                for (int q = 0; q < k; q++) a.dv1[q] = (q - (k - 1) / 2) * dil[t];
+                a.bias = c2.bias;
+                a.flops = 2.0 * 2.0 * B * (double)rows * Cout * Cout * k;
+                rb_tail(a);
+                // the fused kernels cover a subset of (C, k, dilation, LDS footprint): ask the launcher (dry run) first
+                const int fv = gemm_variant_of(a);
+                // C = 128: the pair kernel, or -- where it declines (small jobs) -- the two conv-slab launches it is bit-identical to:
+                // an utterance must come out the same alone and inside a large batch
+                fuse = fv >= 0 && !(Cout == 128 && fv != 23);
+            }
+            if (!fuse) {
+                // xt = c1(lrelu(x)); stored as lrelu(xt)                       hifigan.py:51-53
+                a = rb_base();
+                a.X = cur; a.W = c1.w->dev;
+                set_taps_1d(a, k, dil[t]);
+                a.bias = c1.bias; a.bias_mode = 1; a.act = ACT_LRELU; a.slope = 0.1f;
+                a.out = T1s;
+                c->gemm(a);
+                // x = c2(.) + x                                                hifigan.py:54-55
+                a = rb_base();
+                a.X = T1s; a.W = c2.w->dev;
+                set_taps_1d(a, k, 1);
+                a.bias = c2.bias;
+                rb_tail(a);
+            }
+        } else {
+            // x = c(lrelu(x)) + x                                          hifigan.py:78-81
+            a.X = cur; a.W = w.c1[t].w->dev;
+            set_taps_1d(a, k, dil[t]);
+            a.bias = w.c1[t].bias;
+            rb_tail(a);
+        }
+        c->gemm(a);
+        if (!last) { cur = PPs[pp]; pp ^= 1; }
+    }
+}
+
+void run_vocoder(zvx_ctx* c, const float* mel, int ldm, int Lmel_max, const int* mel_len_host, const int* P_host, int B,
+                 void* wav_dev, long wav_stride, int pcm16) {
+    const std::vector<int> dom = voc_domains(c);
+    const int nm = c->n_mels;
     const size_t es = dtype_size(c->dt);
-    int dt = dom(0);                                                  // the domain of the launches being issued
     int Pmax = 0; for (int b = 0; b < B; b++) Pmax = std::max(Pmax, P_host[b]);
     if (Pmax <= 0) return;
     const int ns = (int)c->voc_rates.size(), nk = (int)c->voc_rb_k.size();
@@ -1310,328 +1638,57 @@ void run_vocoder(zvx_ctx* c, const float* mel, int ldm, int Lmel_max, const int*
     for (int b = 0; b < B; b++) { lens[b] = mel_len_host[b]; lens[B + b] = P_host[b]; }
     int mul = 1;
     for (int i = 0; i < ns; i++) { mul *= c->voc_rates[i]; for (int b = 0; b < B; b++) lens[(size_t)(i + 2) * B + b] = P_host[b] * mul; }
-    int* lens_d = c->upload_ints("voc.lens", lens.data(), lens.size());
-    const int* mel_len_d = lens_d; const int* P_d = lens_d + B;
+    VocCall v{};
+    v.B = B; v.Pmax = Pmax; v.nk = nk;
+    v.lens_d = c->upload_ints("voc.lens", lens.data(), lens.size());
+    const int* mel_len_d = v.lens_d; const int* P_d = v.lens_d + B;
 
     size_t maxel = (size_t)Pmax * c->voc_c0; mul = 1;
     for (int i = 0; i < ns; i++) { mul *= c->voc_rates[i]; maxel = std::max(maxel, (size_t)Pmax * mul * (size_t)(c->voc_c0 >> (i + 1))); }
     maxel *= B;
     void* vin = c->buf("voc.in", (size_t)B * Pmax * nm * es);
-    void* A = c->buf("voc.A", maxel * es);        // stage input (activated)
-    void* X0 = c->buf("voc.X0", maxel * es);      // upsampled stage tensor (activated)
-    void* T1 = c->buf("voc.T1", maxel * es);
-    void* PP[2] = {c->buf("voc.PP0", maxel * es), c->buf("voc.PP1", maxel * es)};
-    void* XS = c->buf("voc.XS", maxel * es);     // running sum over the resblocks of a stage, in the activation dtype
-    // temporaries of the ResBlocks that run beside the first one (single requests, below).  Taken HERE: a new buffer is zero-filled
+    v.A = c->buf("voc.A", maxel * es);
+    v.X0 = c->buf("voc.X0", maxel * es);
+    v.T1 = c->buf("voc.T1", maxel * es);
+    v.PP[0] = c->buf("voc.PP0", maxel * es); v.PP[1] = c->buf("voc.PP1", maxel * es);
+    v.XS = c->buf("voc.XS", maxel * es);         // in the activation dtype
+    // temporaries of the ResBlocks that run beside the first one (single requests, SideHop).  Taken HERE: a new buffer is zero-filled
     // on the main stream, which the side streams only follow from the stage-input event on
     // tools/ab_voc_overlap.py: -5 ... -24 % for every batch below the headline's size (most where B leaves a ragged last round of
     // workgroups: B = 6 / 12), +-1 % at 32 x 896 frames, which therefore keeps the serial schedule
-    const bool side_ok = nk >= 2 && nk <= 3 && B <= c->voc_overlap_maxb && (long)B * Pmax < c->voc_overlap_frames;
-    void* sideT1[2] = {nullptr, nullptr}; void* sidePP[2][2] = {{nullptr, nullptr}, {nullptr, nullptr}};
-    if (side_ok)
+    v.side_ok = nk >= 2 && nk <= 3 && B <= c->voc_overlap_maxb && (long)B * Pmax < c->voc_overlap_frames;
+    if (v.side_ok)
         for (int j = 1; j < nk; j++) {
-            sideT1[j - 1] = c->buf("voc.T1." + std::to_string(j), maxel * es);
-            sidePP[j - 1][0] = c->buf("voc.PP0." + std::to_string(j), maxel * es); sidePP[j - 1][1] = c->buf("voc.PP1." + std::to_string(j), maxel * es);
+            v.sideT1[j - 1] = c->buf("voc.T1." + std::to_string(j), maxel * es);
+            v.sidePP[j - 1][0] = c->buf("voc.PP0." + std::to_string(j), maxel * es); v.sidePP[j - 1][1] = c->buf("voc.PP1." + std::to_string(j), maxel * es);
         }
 
     c->tag = "voc.pre";
-    launch_mel_pad(mel, DT_F32, ldm, Lmel_max, mel_len_d, vin, dt, nm, Pmax, P_d, B, nm, c->stream);     // model.py:331-335
-    c->sat_scan(vin, dt, (long)Pmax * nm, nm, B, Pmax, P_d, nm);
+    launch_mel_pad(mel, DT_F32, ldm, Lmel_max, mel_len_d, vin, dom[0], nm, Pmax, P_d, B, nm, c->stream);     // model.py:331-335
+    c->sat_scan(vin, dom[0], (long)Pmax * nm, nm, B, Pmax, P_d, nm);
     if (c->front_stream && c->stream != c->front_stream) {   // the mel buffer is free again: a queued call's decoder (front stream) may overwrite it
         HIPCHK(hipEventRecord(c->ev_mel_free, c->stream));
         c->mel_free_pending = true;
     }
-    {   // conv_pre, stored as leaky_relu(x, 0.1) (its only consumer, hifigan.py:115-117)
-        GemmArgs a = gemm_base(dt);
-        a.X = vin; a.x_bs = (long)Pmax * nm; a.ldx = nm; a.W = vtd("voc.pre_w", dt).dev; a.ldw = nm; a.w_ts = (long)c->voc_c0 * nm;
-        a.M = Pmax; a.N = c->voc_c0; a.K = nm; a.nbatch = B; a.in_len = P_d; a.out_len = P_d;
-        set_taps_1d(a, c->t("voc.pre_w").dim(0), 1);
-        a.bias = c->pf("voc.pre_b"); a.bias_mode = 1; a.act = ACT_LRELU; a.slope = 0.1f;
-        a.out = A; a.o_bs = (long)Pmax * c->voc_c0; a.ldo = c->voc_c0;
-        c->gemm(a);
-    }
-    int Cin = c->voc_c0; mul = 1;
+    voc_conv_pre(c, v, vin, dom[0]);
+    int Cin = c->voc_c0, rows = Pmax;
     for (int i = 0; i < ns; i++) {
-        const int u = c->voc_rates[i], ku = c->voc_ksizes[i], Cout = Cin / 2;
-        const int rows_in = Pmax * mul, rows = rows_in * u;
-        const int* len_in = lens_d + (size_t)(i + 1) * B; const int* len = lens_d + (size_t)(i + 2) * B;
+        VocStage s;
+        s.i = i; s.Cin = Cin; s.Cout = Cin / 2; s.rows_in = rows; s.rows = rows * c->voc_rates[i];
+        s.len_in = v.lens_d + (size_t)(i + 1) * B; s.len = v.lens_d + (size_t)(i + 2) * B;
+        s.dt_in = dom[i]; s.dt = dom[i + 1];
+        s.next_slope = (i == ns - 1) ? 0.01f : 0.1f;          // hifigan.py:126 uses the default slope 0.01
         c->tag = "voc.up" + std::to_string(i + 1);
-        const int dt_in = dom(i);
-        dt = dom(i + 1);
-        const bool h16 = dt == DT_F16;
-        auto vt = [&](const std::string& n) -> const Tensor& { return vtd(n, dt); };                // a contraction weight in this stage's dtype
-        {   // ConvTranspose1d as a polyphase GEMM: out[t][ph*Cout+co]                  hifigan.py:118
-            const std::string up = "voc.up" + std::to_string(i);
-            GemmArgs a = gemm_base(dt_in);
-            a.out_dtype = dt;
-            a.X = A; a.x_bs = (long)rows_in * Cin; a.ldx = Cin; a.ldw = Cin;
-            a.M = rows_in; a.K = Cin; a.nbatch = B; a.in_len = len_in; a.out_len = len_in;
-            a.bias_mode = 1; a.act = ACT_LRELU; a.slope = 0.1f;
-            a.o_bs = (long)rows_in * u * Cout; a.ldo = u * Cout;
-            if (dt_in != DT_F32 && c->has(up + "_wlo")) {
-                // k = 2u: two 2-tap GEMMs over half the phases each (rows t-1, t / rows t, t+1) instead of one 3-tap GEMM
-                const int hc = (u / 2) * Cout;
-                a.N = hc; a.ntaps = 2; a.w_ts = (long)hc * Cin; a.flops = 2.0 * B * (double)rows_in * Cin * Cout * ku / 2;
-                a.W = vtd(up + "_wlo", dt_in).dev; a.dv[0] = -1; a.dv[1] = 0;
-                a.bias = c->pf(up + "_b"); a.out = X0;
-                c->gemm(a);
-                a.Wp = nullptr;
-                a.W = vtd(up + "_whi", dt_in).dev; a.dv[0] = 0; a.dv[1] = 1;
-                a.bias = c->pf(up + "_b") + hc; a.out = (char*)X0 + (size_t)hc * es;
-                c->gemm(a);
-            } else {
-                a.W = vtd(up + "_w", dt_in).dev; a.w_ts = (long)u * Cout * Cin; a.N = u * Cout;
-                a.ntaps = 3; a.dv[0] = -1; a.dv[1] = 0; a.dv[2] = 1;
-                a.bias = c->pf(up + "_b"); a.out = X0;
-                a.flops = 2.0 * B * (double)rows_in * Cin * Cout * ku;
-                c->gemm(a);
-            }
-        }
-        const float next_slope = (i == ns - 1) ? 0.01f : 0.1f;          // hifigan.py:126 uses the default slope 0.01
+        voc_upsample(c, v, s);
         c->tag = "voc.res" + std::to_string(i + 1);
-        // narrow stages (C = 16 / 8: HiFi-GAN V2's last two): all ResBlocks of the stage, their mean and the next stage's activation in ONE
-        // launch -- the stage tensor crosses HBM once in, once out (narrowstage.hip)
-        if (c->use_stagefuse && !c->sat_check && c->voc_resblock == 1 && dt != DT_F32 && (Cout == 16 || Cout == 8) && nk >= 1 && nk <= 3) {
-            bool ok = true;
-            for (int j = 0; j < nk; j++) ok = ok && c->voc_rb_d[j].size() == 3;
-            StageArgs sa;
-            memset(&sa, 0, sizeof sa);
-            if (ok) {
-                const std::string key = "voc.ns." + std::to_string(i) + (h16 ? ".h16" : "");
-                auto it = c->ns_weights.find(key);
-                if (it == c->ns_weights.end()) {
-                    zvx_ctx::NsWeights nw;
-                    int nfrag = 0;
-                    for (int j = 0; j < nk; j++) for (int q = 0; q < 6; q++) { nw.woff[6 * j + q] = nfrag; nfrag += narrowstage_steps(Cout, c->voc_rb_k[j]); }
-                    nw.W = c->buf(key + ".w", (size_t)nfrag * 1024);
-                    nw.bias = c->fbuf(key + ".b", (size_t)6 * nk * Cout);
-                    for (int j = 0; j < nk; j++)
-                        for (int t = 0; t < 3; t++)
-                            for (int q = 0; q < 2; q++) {
-                                const std::string nm = "voc.rb" + std::to_string(i * nk + j) + (q ? ".c2_" : ".c1_") + std::to_string(t);
-                                const Tensor& w = vt(nm + "_w");
-                                if (w.dims.size() != 3 || w.dim(0) != c->voc_rb_k[j] || w.dim(1) != Cout || w.dim(2) != Cout) fail(ZVX_E_MANIFEST, "weights: '%s' has an unexpected shape", nm.c_str());
-                                const int ci = 6 * j + 2 * t + q;
-                                launch_pack_narrow(w.dev, c->voc_rb_k[j], Cout, (char*)nw.W + (size_t)nw.woff[ci] * 1024, c->stream);
-                                HIPCHK(hipMemcpyAsync(nw.bias + (size_t)ci * Cout, c->pf(nm + "_b"), (size_t)Cout * 4, hipMemcpyDeviceToDevice, c->stream));
-                            }
-                    it = c->ns_weights.emplace(key, nw).first;
-                }
-                sa.X = X0; sa.x_bs = (long)rows * Cout; sa.ldx = Cout; sa.W = it->second.W; sa.bias = it->second.bias;
-                memcpy(sa.woff, it->second.woff, sizeof sa.woff);
-                sa.C = Cout; sa.nk = nk;
-                for (int j = 0; j < nk; j++) { sa.ks[j] = c->voc_rb_k[j]; for (int t = 0; t < 3; t++) sa.dil[j][t] = c->voc_rb_d[j][t]; }
-                sa.out = A; sa.o_bs = (long)rows * Cout; sa.ldo = Cout;
-                sa.slope1 = 0.1f; sa.res_inv_slope = 10.0f; sa.slope = next_slope;
-                sa.len = len; sa.M = rows; sa.nbatch = B; sa.f16 = h16;
-                ok = launch_narrowstage(sa, c->stream, true);
-            }
-            if (ok) {
-                GemmEvent ev{};
-                const int vid = Cout == 16 ? 24 : 25;
-                const bool prof = c->profile >= 2 && (c->profile_only < 0 || c->profile_only == vid);
-                if (prof) { ev.a = c->new_event(); ev.b = c->new_event(); narrowstage_profile_events(ev.a, ev.b); }
-                const bool launched = launch_narrowstage(sa, c->stream, false);
-                if (prof) narrowstage_profile_events(nullptr, nullptr);
-                if (!launched) fail(ZVX_E_INVALID, "launch_narrowstage rejected a stage its dry run accepted (C=%d)", Cout);
-                if (prof) {
-                    double ksum = 0; for (int j = 0; j < nk; j++) ksum += c->voc_rb_k[j];
-                    const double rws = (double)rows * B;
-                    ev.variant = vid; ev.flops = 2.0 * rws * Cout * Cout * 6.0 * ksum; ev.rows = (long)rws; ev.N = Cout; ev.K = Cout; ev.taps = (int)ksum; ev.fused = 100 + nk;
-                    ev.bytes = rws * Cout * 2.0 * 2.0; ev.tag = c->tag;
-                    c->pending.push_back(ev);
-                }
-                Cin = Cout; mul *= u;
-                continue;
-            }
+        if (!voc_narrow_stage(c, v, s)) {
+            if (v.side_ok) voc_side_begin(c);
+            for (int j = 0; j < nk; j++) voc_resblock(c, v, s, j);
         }
-        // Single requests: the ResBlocks of a stage only meet in the running sum, which their LAST pair updates.  Everything
-        // before that (two of three pairs) runs on a stream of its own for the 2nd and 3rd ResBlock, with its own temporaries;
-        // the last pairs stay on the main stream in the order 1, 2, 3, so xs accumulates exactly as before (bit-identical).
-        // The critical path of a per-pair stage drops from 18 to 10 launches.
-        const bool overlap = side_ok;
-        hipStream_t const main_stream = c->stream;
-        struct Restore { zvx_ctx* c; hipStream_t keep; ~Restore() { c->stream = keep; } } restore{c, main_stream};
-        if (overlap) {
-            for (int q = 0; q < 2; q++) if (!c->voc_aux[q]) HIPCHK(hipStreamCreateWithFlags(&c->voc_aux[q], hipStreamNonBlocking));
-            for (int q = 0; q < 3; q++) if (!c->voc_ev[q]) HIPCHK(hipEventCreateWithFlags(&c->voc_ev[q], hipEventDisableTiming));
-            HIPCHK(hipEventRecord(c->voc_ev[0], main_stream));      // the stage input (and everything the previous stage read) is settled
-        }
-        for (int j = 0; j < nk; j++) {
-            hipStream_t const my_aux = (overlap && j >= 1) ? c->voc_aux[j - 1] : nullptr;
-            bool on_aux = false;
-            void* const T1s = my_aux ? sideT1[j - 1] : T1;
-            void* const* const PPs = my_aux ? sidePP[j - 1] : PP;
-            if (my_aux) HIPCHK(hipStreamWaitEvent(my_aux, c->voc_ev[0], 0));
-            auto to_aux = [&] { if (my_aux && !on_aux) { c->stream = my_aux; on_aux = true; } };
-            auto to_main = [&] {
-                if (on_aux) {
-                    HIPCHK(hipEventRecord(c->voc_ev[j], my_aux));
-                    c->stream = main_stream; on_aux = false;
-                    HIPCHK(hipStreamWaitEvent(main_stream, c->voc_ev[j], 0));
-                }
-            };
-            const int k = c->voc_rb_k[j];
-            const std::vector<int>& dil = c->voc_rb_d[j];
-            const int nd = (int)dil.size();
-            const std::string rb = "voc.rb" + std::to_string(i * nk + j);
-            const void* cur = X0;
-            int pp = 0;
-            int t_first = 0;
-            if (c->voc_resblock == 1 && dt != DT_F32 && c->use_resstream && !c->sat_check && nd >= 1 && nd <= 3) {
-                // whole ResBlock (or its first two pairs + the last one) as streaming launches: the stage tensor crosses HBM once
-                bool packed_ok = true;
-                for (int t = 0; t < nd; t++)
-                    packed_ok = packed_ok && c->packed.count(vt(rb + ".c1_" + std::to_string(t) + "_w").dev) && c->packed.count(vt(rb + ".c2_" + std::to_string(t) + "_w").dev);
-                auto chain = [&](int t0, int np, const void* in, bool closes) {
-                    StreamArgs sa;
-                    memset(&sa, 0, sizeof sa);
-                    sa.X = in; sa.x_bs = (long)rows * Cout; sa.ldx = Cout; sa.C = Cout; sa.ntaps = k; sa.npair = np;
-                    for (int q = 0; q < np; q++) {
-                        const std::string ts = std::to_string(t0 + q);
-                        sa.W1[q] = c->packed[vt(rb + ".c1_" + ts + "_w").dev]; sa.W2[q] = c->packed[vt(rb + ".c2_" + ts + "_w").dev];
-                        sa.b1[q] = c->pf(rb + ".c1_" + ts + "_b"); sa.b2[q] = c->pf(rb + ".c2_" + ts + "_b");
-                        sa.dil[q] = dil[t0 + q];
-                    }
-                    sa.seg_min = c->rs_seg_min; sa.f16 = h16;
-                    if (c->rs_prof) sa.prof = (long long*)c->buf("rs.prof." + rb + "." + std::to_string(t0), 16 * 16 * 8);   // RS_PROFILE builds only
-                    sa.slope1 = 0.1f; sa.res_inv_slope = 10.0f; sa.out_scale = 1.f; sa.slope = 0.1f;
-                    sa.len = len; sa.M = rows; sa.nbatch = B; sa.o_bs = (long)rows * Cout; sa.ldo = Cout; sa.a_bs = (long)rows * Cout; sa.lda = Cout;
-                    if (!closes) { sa.out = PPs[pp]; }
-                    else if (nk == 1) { sa.out = A; sa.slope = next_slope; }
-                    else {
-                        sa.accum = XS; sa.accum_mode = j == 0 ? 2 : (j < nk - 1 ? 3 : 1);
-                        if (j == nk - 1) { sa.out = A; sa.out_scale = 1.0f / nk; sa.slope = next_slope; }
-                    }
-                    return sa;
-                };
-                if (packed_ok) {
-                    StreamArgs whole = chain(0, nd, X0, true);
-                    to_main();
-                    if (c->run_stream(whole)) t_first = nd;
-                    else if (nd == 3) {
-                        StreamArgs head = chain(0, 2, X0, false);
-                        StreamArgs probe = chain(2, 1, PPs[pp], true);
-                        if (launch_resstream(head, c->stream, true) >= 0 && launch_resstream(probe, c->stream, true) >= 0) {
-                            to_aux();
-                            c->run_stream(head);
-                            cur = PPs[pp]; pp ^= 1;
-                            StreamArgs tail = chain(2, 1, cur, true);
-                            to_main();
-                            c->run_stream(tail);
-                            t_first = nd;
-                        }
-                    }
-                }
-            }
-            if (c->voc_resblock == 2 && nd == 2 && dt != DT_F32 && c->use_rb2fuse && !c->sat_check && (Cout == 32 || Cout == 64)) {
-                // a whole ResBlock2 (hifigan.py:77-82: x1 = x + c_0(lrelu(x)); x2 = x1 + c_1(lrelu(x1))) as ONE launch: lrelu(x1) stays in LDS
-                // (rb2fuse_kernel, round 6) -- two trips of the stage tensor per block instead of six
-                const Tensor& w1 = vt(rb + ".c_0_w"); const Tensor& w2 = vt(rb + ".c_1_w");
-                if (c->packed.count(w1.dev) && c->packed.count(w2.dev)) {
-                    GemmArgs a = gemm_base(dt);
-                    a.M = rows; a.N = Cout; a.K = Cout; a.nbatch = B; a.in_len = len; a.out_len = len; a.ldw = Cout; a.w_ts = (long)Cout * Cout;
-                    a.x_bs = (long)rows * Cout; a.ldx = Cout; a.o_bs = (long)rows * Cout; a.ldo = Cout;
-                    a.X = X0; a.W = w2.dev; a.Wp = c->packed[w2.dev]; a.Wp2 = c->packed[w1.dev];
-                    a.bias1 = c->pf(rb + ".c_0_b"); a.slope1 = 0.1f; a.fused = 2;
-                    set_taps_1d(a, k, dil[1]);
-                    for (int q = 0; q < k; q++) a.dv1[q] = (q - (k - 1) / 2) * dil[0];
-                    a.bias = c->pf(rb + ".c_1_b"); a.bias_mode = 1;
-                    a.res = X0; a.r_bs = (long)rows * Cout; a.ldr = Cout; a.res_mode = 2; a.res_inv_slope = 10.0f; a.res_dtype = dt;
-                    a.accum = XS; a.accum_dtype = dt; a.a_bs = (long)rows * Cout; a.lda = Cout;
-                    if (nk == 1) { a.accum_mode = 0; a.accum = nullptr; }
-                    else if (j == 0) a.accum_mode = 2;
-                    else if (j < nk - 1) a.accum_mode = 3;
-                    else a.accum_mode = 1;
-                    if (j == nk - 1 || nk == 1) { a.out = A; a.out_scale = 1.0f / nk; a.act = ACT_LRELU; a.slope = next_slope; }
-                    else a.out = nullptr;
-                    a.flops = 2.0 * 2.0 * B * (double)rows * Cout * Cout * k;
-                    if (gemm_variant_of(a) >= 0) { to_main(); c->gemm(a); t_first = nd; }
-                }
-            }
-            for (int t = t_first; t < nd; t++) {
-                const bool last = (t == nd - 1);
-                if (last) to_main(); else to_aux();
-                const void* cin_buf = cur;
-                auto rb_base = [&] {
-                    GemmArgs a = gemm_base(dt);
-                    a.M = rows; a.N = Cout; a.K = Cout; a.nbatch = B; a.in_len = len; a.out_len = len; a.ldw = Cout; a.w_ts = (long)Cout * Cout;
-                    a.x_bs = (long)rows * Cout; a.ldx = Cout; a.o_bs = (long)rows * Cout; a.ldo = Cout;
-                    return a;
-                };
-                // what the LAST conv of the iteration does with its result: + bias + x (raw residual recovered from the activated
-                // input), then either the next iteration's input (activated) or the stage's running sum / mean
-                int pp_next = pp;
-                auto rb_tail = [&](GemmArgs& a) {
-                    a.bias_mode = 1;
-                    a.res = cin_buf; a.r_bs = (long)rows * Cout; a.ldr = Cout; a.res_mode = 2; a.res_inv_slope = 10.0f; a.res_dtype = dt;
-                    if (!last) {
-                        a.act = ACT_LRELU; a.slope = 0.1f; a.out = PPs[pp];
-                        pp_next = pp ^ 1;
-                    } else {
-                        // xs (+)= resblock output; last kernel size: x = xs / num_kernels, stored activated for the next stage
-                        a.accum = XS; a.accum_dtype = dt; a.a_bs = (long)rows * Cout; a.lda = Cout;
-                        if (nk == 1) { a.accum_mode = 0; a.accum = nullptr; }
-                        else if (j == 0) a.accum_mode = 2;
-                        else if (j < nk - 1) a.accum_mode = 3;
-                        else a.accum_mode = 1;
-                        if (j == nk - 1) { a.out = A; a.out_scale = 1.0f / nk; a.act = ACT_LRELU; a.slope = next_slope; }
-                        else a.out = nullptr;
-                    }
-                };
-                GemmArgs a = rb_base();
-                if (c->voc_resblock == 1) {
-                    const std::string ts = std::to_string(t);
-                    const Tensor& w1 = vt(rb + ".c1_" + ts + "_w");
-                    const Tensor& w2 = vt(rb + ".c2_" + ts + "_w");
-                    bool fuse = dt != DT_F32 && !c->sat_check && c->packed.count(w1.dev) && c->packed.count(w2.dev);
-                    if (fuse) {
-                        // one launch: xt = lrelu(c1(x_act)+b1) stays in LDS; x' = c2(xt) + b2 + x      hifigan.py:51-55
-                        a.X = cur; a.W = w2.dev; a.Wp = c->packed[w2.dev]; a.Wp2 = c->packed[w1.dev];
-                        a.bias1 = c->pf(rb + ".c1_" + ts + "_b"); a.slope1 = 0.1f; a.fused = 1;
-                        a.no_pairstream = c->use_pairstream <= 0 ? 1 : (c->use_pairstream == 3 ? 2 : 0);
-                        set_taps_1d(a, k, 1);
-                        for (int q = 0; q < k; q++) a.dv1[q] = (q - (k - 1) / 2) * dil[t];
-                        a.bias = c->pf(rb + ".c2_" + ts + "_b");
-                        a.flops = 2.0 * 2.0 * B * (double)rows * Cout * Cout * k;
-                        rb_tail(a);
-                        // the fused kernels cover a subset of (C, k, dilation, LDS footprint): ask the launcher (dry run) first
-                        const int fv = gemm_variant_of(a);
-                        // C = 128: the pair kernel, or -- where it declines (small jobs) -- the two conv-slab launches it is bit-identical to:
-                        // an utterance must come out the same alone and inside a large batch
-                        fuse = fv >= 0 && !(Cout == 128 && fv != 23);
-                    }
-                    if (!fuse) {
-                        // xt = c1(lrelu(x)); stored as lrelu(xt)                       hifigan.py:51-53
-                        a = rb_base();
-                        a.X = cur; a.W = w1.dev;
-                        set_taps_1d(a, k, dil[t]);
-                        a.bias = c->pf(rb + ".c1_" + ts + "_b"); a.bias_mode = 1; a.act = ACT_LRELU; a.slope = 0.1f;
-                        a.out = T1s;
-                        c->gemm(a);
-                        // x = c2(.) + x                                                hifigan.py:54-55
-                        a = rb_base();
-                        a.X = T1s; a.W = w2.dev;
-                        set_taps_1d(a, k, 1);
-                        a.bias = c->pf(rb + ".c2_" + ts + "_b");
-                        rb_tail(a);
-                    }
-                } else {
-                    // x = c(lrelu(x)) + x                                          hifigan.py:78-81
-                    a.X = cur; a.W = vt(rb + ".c_" + std::to_string(t) + "_w").dev;
-                    set_taps_1d(a, k, dil[t]);
-                    a.bias = c->pf(rb + ".c_" + std::to_string(t) + "_b");
-                    rb_tail(a);
-                }
-                c->gemm(a);
-                if (!last) { cur = PPs[pp]; pp = pp_next; }
-            }
-        }
-        Cin = Cout; mul *= u;
+        Cin = s.Cout; rows = s.rows;
     }
     // conv_post + tanh on the first mel_len*hop samples            hifigan.py:127-128, model.py:347
     c->tag = "voc.post";
-    dt = dom(ns);
     {
         double nout = 0; for (int b = 0; b < B; b++) nout += (double)mel_len_host[b] * c->hop;
         // rows are zero-filled up to max_b(mel_len) * hop, the extent include/zvx.h promises (and the caller's wav_stride covers):
@@ -1640,7 +1697,7 @@ void run_vocoder(zvx_ctx* c, const float* mel, int ldm, int Lmel_max, const int*
         if ((long)nmax > wav_stride) nmax = (int)wav_stride;
         const int kp = c->t("voc.post_w").dim(0);
         c->timed(2.0 * nout * Cin * kp, nout * (Cin * es + (pcm16 ? 2.0 : 4.0)), [&] {
-            launch_conv_post_tanh(A, dt, Cin, (long)Pmax * mul * Cin, c->pf("voc.post_w"), c->t("voc.post_b").host[0], kp,
+            launch_conv_post_tanh(v.A, dom[ns], Cin, (long)rows * Cin, c->pf("voc.post_w"), c->t("voc.post_b").host[0], kp,
                                   Cin, wav_dev, wav_stride, pcm16, B, nmax, P_d, c->hop, mel_len_d, c->hop, c->stream);
         });
     }

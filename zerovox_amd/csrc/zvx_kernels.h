@@ -2,13 +2,26 @@
 // Activations are time-major [row = time][channel] in HBM, fp32 or bf16 (precision mode).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <hip/hip_ext.h>
 #include <stdint.h>
 #include <atomic>
 #include <mutex>
 #include <set>
 #include <utility>
 
+// Per-launch timing without marker packets: when the caller has armed a pair of events (profile_events), the dispatch itself
+// carries them (hipExtLaunchKernelGGL start / stop events = the kernel's own begin / end timestamps).  ONE thread-local pair serves
+// every launcher (defined in gemm.hip); each launcher dispatches through ZVX_DISPATCH, and a dry run never reads the pair.
+extern thread_local hipEvent_t zvx_gemm_ev_start, zvx_gemm_ev_stop;
+#define ZVX_DISPATCH(kernel, grid, block, lds, stream, ...) \
+    do { if (zvx_gemm_ev_start) hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, zvx_gemm_ev_start, zvx_gemm_ev_stop, 0, __VA_ARGS__); \
+         else hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__); } while (0)
+
 namespace zvx {
+
+// arm (or disarm with nullptrs) the pair of events that the NEXT dispatch of a launch_gemm / launch_resfuse / launch_rb2fuse /
+// launch_resstream / launch_pairstream / launch_narrowstage carries as its own start / stop timestamps
+inline void profile_events(hipEvent_t start, hipEvent_t stop) { zvx_gemm_ev_start = start; zvx_gemm_ev_stop = stop; }
 
 typedef unsigned short bf16_t;   // raw bf16 bits
 
@@ -121,9 +134,6 @@ struct GemmArgs {
 
 // Returns the kernel-variant id used (index into gemm_variant_name) or <0 on error.
 int launch_gemm(const GemmArgs& a, hipStream_t stream);
-// arm (or disarm with nullptrs) a pair of events that the NEXT launch_gemm / launch_resfuse dispatch carries as its own
-// start / stop timestamps (no marker packets on the stream)
-void gemm_profile_events(hipEvent_t start, hipEvent_t stop);
 // the kernel variant launch_gemm / launch_resfuse would pick for these arguments (nothing is dispatched)
 int gemm_variant_of(const GemmArgs& a);
 // the compile-time epilogue a conv-slab launch of these arguments selects (ZVX_EPI / ZVX_EPI_DEC / ZVX_EPI_FLIP of gemm.hip), -1 = the
@@ -165,7 +175,6 @@ struct StreamArgs {
 };
 // variant id (index into gemm_variant_name) or -1 when the shape is not covered; dry_run: decide only, launch nothing
 int launch_resstream(StreamArgs a, hipStream_t stream, bool dry_run);
-void resstream_profile_events(hipEvent_t start, hipEvent_t stop);     // like gemm_profile_events, for the next launch_resstream
 
 // ------------------------------------------------------------------------------------------------
 // Streaming ResBlock1 PAIR for the wide stages (pairstream.hip): x' = conv2(lrelu(conv1_dilated(x_act) + b1)) + b2 + x in ONE
@@ -187,7 +196,7 @@ struct PairArgs {
     long long* prof;                               // PS_PROFILE builds: [8 waves][main, epilogue, barrier, -] cycle totals of workgroup 0
 };
 // true when the shape is covered (and, unless dry_run, launched); ev_start / ev_stop: optional dispatch-carried events
-bool launch_pairstream(PairArgs a, hipStream_t stream, bool dry_run, hipEvent_t ev_start, hipEvent_t ev_stop);
+bool launch_pairstream(PairArgs a, hipStream_t stream, bool dry_run);
 
 // ------------------------------------------------------------------------------------------------
 // A whole narrow HiFi-GAN stage (narrowstage.hip): the nk ResBlock1 blocks (three dilated pairs each) of a stage with C = 16 / 8
@@ -208,7 +217,6 @@ struct StageArgs {
 bool launch_narrowstage(const StageArgs& a, hipStream_t stream, bool dry_run);
 int narrowstage_steps(int C, int k);               // 1-KiB fragments per convolution
 void launch_pack_narrow(const void* w16 /*[k][C][C] 16-bit*/, int k, int C, void* out, hipStream_t s);
-void narrowstage_profile_events(hipEvent_t start, hipEvent_t stop);
 
 // ------------------------------------------------------------------------------------------------
 // Fused attention of the FS2 / SCLN decoder (attention.hip): out = softmax(Q K^T * scale, keys < len) V per (utterance, head),
@@ -234,8 +242,8 @@ struct AttnF32Args {
     const int* len; int L, D, nheads, nbatch;
     float scale;
 };
-bool launch_attention_f32(const AttnF32Args& a, hipStream_t stream, bool dry_run);   // timed through flash_profile_events
-void flash_profile_events(hipEvent_t start, hipEvent_t stop);
+bool launch_attention_f32(const AttnF32Args& a, hipStream_t stream, bool dry_run);
+// (both attention launches are plain dispatches: the caller records its events around the call)
 
 // ------------------------------------------------------------------------------------------------
 // Small kernels (ops.hip).  T-typed pointers are void* + dtype.
