@@ -46,17 +46,21 @@ enum {                   /* flags */
     ZVX_DEVICE_IN = 8,   /* the bulk input (zvx_vocode_mel: mel, zvx_spkemb_ex: ref_mels) is a device pointer */
     ZVX_PCM16 = 4,       /* wav rows are int16 PCM: (int16)(sample * 32760), truncated like numpy astype (demo.py:29-35,
                             model.py:44-63); halves the bytes of the multi-GPU waveform gather.  wav_stride stays in samples */
-    ZVX_HOST_ASYNC = 16  /* zvx_synthesize / zvx_vocode / zvx_vocode_mel: the waveform is delivered to HOST memory without the call waiting
+    ZVX_HOST_ASYNC = 16, /* zvx_synthesize / zvx_vocode / zvx_vocode_mel: the waveform is delivered to HOST memory without the call waiting
                             for it (round 6) -- `wav` / `wav_stride` are ignored (wav may be NULL): the rows go to one of the context's two
                             pinned host slots on a copy stream of their own, the call returns after queueing (as with
                             ZVX_DEVICE_OUT | ZVX_NO_SYNC; no host mel / log_duration output), zvx_get_int("host_slot") names the slot
                             and zvx_wait_host(ctx, slot, ...) is where the host meets the rows.  Slots alternate (call i: slot i & 1);
                             a slot's rows stay valid until the second next ZVX_HOST_ASYNC call */
+    ZVX_NATIVE_RATE = 32 /* zvx_vocode / zvx_vocode_mel / zvx_synthesize / zvx_synthesize_ex: this call ignores zvx_set_int("out_rate") and delivers
+                            the generator's own samples at the model's rate (chunked streaming vocodes at the native rate and converts the
+                            stream itself, zvx_resample_ex; it is also how a caller gets both) */
 };
 
 enum {                   /* zvx_stage_times indices (milliseconds, hipEvent-timed on the ctx stream) */
     ZVX_T_ENCODER = 0, ZVX_T_VARIANCE = 1, ZVX_T_LENREG = 2, ZVX_T_DECODER = 3, ZVX_T_VOCODER = 4,
-    ZVX_T_SPKEMB = 5, ZVX_T_COUNT = 8
+    ZVX_T_SPKEMB = 5, ZVX_T_RESAMPLE = 6,   /* the sample-rate conversion of the last waveform call (0 when that call ran none) or zvx_resample */
+    ZVX_T_COUNT = 8
 };
 
 /* Build a synthesis context on HIP device `device` from a text manifest + fp32 weight blob produced
@@ -80,6 +84,9 @@ int64_t    zvx_get_int(const zvx_ctx* ctx, const char* key);
  * "shape_log" 0/1 (one stderr line per timed launch); "max_frames" hard cap on a predicted mel length (default 2^18:
  * the reference has none, fs2.py:678-681 -- a garbage log-duration must not drive an allocation -> ZVX_E_BUFFER).
  * "f16_sat_check" 0/1: the saturation audit of the half mode (see zvx_get_int "f16_sat_events"); setting it (re)zeroes the counter.
+ * "out_rate" hz: the sampling rate of every waveform the context hands back (0, the default = the model's "sampling_rate": nothing changes, no
+ *   extra launch or buffer).  Checked when set, against the model's rate, as zvx_resample checks a pair (ZVX_E_INVALID / ZVX_E_UNSUPPORTED,
+ *   the switch keeps its value); see "Output rate" below.
  * Every other key is an A/B switch of a scheduling / tiling / arithmetic choice (INTEGRATION.md has the table and each key's values:
  * "enc_split", "attn_f32", "flash", "front_overlap", "va_overlap_maxb", "dec_f16", "dec_flat", "dec_sc_fuse", "norm_fuse_maxb", "voc_f16",
  * "voc_f16_stages", "voc_overlap_maxb", "voc_overlap_frames", "stagefuse", "rb2fuse", "resstream", "rs_seg_min", "pairstream", "slab_small",
@@ -200,6 +207,37 @@ zvx_status zvx_synthesize_ex(zvx_ctx* ctx, const int32_t* phoneme, const int32_t
  * Replaces the `.cpu().numpy()` hand-over of ZeroVoxTTS.tts_ex (synthesize.py:233-239) for a host that keeps calls in flight. */
 zvx_status zvx_wait_host(zvx_ctx* ctx, int slot, const void** rows, int64_t* stride, int32_t* nrows, int64_t* valid);
 
+/* Sample-rate conversion on the device: in [B][Nmax] f32 with nsamples[b] valid samples at rate_in -> row b of out: out_len[b] =
+ * ceil(nsamples[b] * L / M) samples at rate_out, then zeros up to max_b out_len[b]; nothing beyond that is touched.  out_stride samples
+ * between rows (ZVX_E_BUFFER if smaller than the longest row); float rows, or int16 rows with ZVX_PCM16; out_len may be NULL.
+ * The filter, with g = gcd(rate_in, rate_out), L = rate_out / g, M = rate_in / g, mx = max(L, M), half = 10 mx, fc = 1 / mx, m = -half .. half:
+ *     w[m] = I0(5 sqrt(1 - (m / half)^2)) / I0(5)                 (Kaiser window, beta = 5)
+ *     h[m] = fc sinc(fc m) w[m];  h /= sum(h);  h *= L             (sinc(x) = sin(pi x) / (pi x))
+ *     y[n] = sum_k h[n M - k L] x[k],  x = 0 outside the given samples
+ * -- what scipy.signal.resample_poly(x, L, M) computes with its defaults (stop band about -54 dB).  The taps are designed in double on the
+ * host, rounded once to f32 and cached in the context per (L, M); the sum of one output runs in f32 over its ceil((2 half + 1) / L) taps in one
+ * fixed order, so an output sample's bits depend on nothing but (L, M) and the samples under the filter: not on the batch, the row's
+ * neighbours or the window of zvx_resample_ex.  Rates outside [4000, 192000]: ZVX_E_INVALID; mx > 640: ZVX_E_UNSUPPORTED (the message
+ * names L and M; every pair between 22050 and 8000 / 11025 / 12000 / 16000 / 24000 / 32000 / 44100 / 48000 is inside).  Equal rates: a copy.
+ * ZVX_PCM16: (int16) trunc(clamp(v * 32760, -32768, 32767)) -- clamped, because a band-limited interpolation of samples in [-1, 1]
+ * overshoots (a full-scale 300 Hz square wave reaches 1.28 after 22050 -> 48000).
+ * Flags: ZVX_DEVICE_IN (in on the device), ZVX_DEVICE_OUT, ZVX_NO_SYNC (device output only), ZVX_PCM16.  nsamples / out_len are host arrays.
+ * Replaces librosa.load(sr=...) of ZeroVoxTTS.get_speakerref (synthesize.py:112-121) and any host-side conversion of a finished waveform. */
+zvx_status zvx_resample(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, int rate_in, int rate_out,
+                        void* out, int64_t out_stride, int32_t* out_len, int flags);
+/* The same filter over a window, so that a stream converts piece by piece and comes out bit-identical to one whole-signal call: row b
+ * holds samples [in_origin, in_origin + nsamples[b]) of a signal that is zero everywhere else; outputs [out_begin, out_begin + out_count)
+ * go to positions [0, out_count) of the row.  out_count = -1: to the end, ceil((in_origin + nsamples[b]) * L / M) - out_begin outputs for
+ * row b, zeros up to the longest row; out_len (may be NULL) receives the per-row counts.  zvx_resample is origin 0, begin 0, count -1. */
+zvx_status zvx_resample_ex(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, int rate_in, int rate_out,
+                           void* out, int64_t out_stride, int32_t* out_len, int flags, int64_t in_origin, int64_t out_begin, int64_t out_count);
+/* Output rate: after zvx_set_int(ctx, "out_rate", hz) zvx_vocode, zvx_vocode_mel, zvx_synthesize and zvx_synthesize_ex deliver their rows at
+ * hz: the generator writes f32 into a work buffer of the context and the resampler, one more launch on the main stream behind conv_post,
+ * writes the caller's rows.  wav_stride, the ZVX_E_BUFFER bound and the `valid` of zvx_wait_host are then in OUTPUT samples: row b carries
+ * ceil(mel_len[b] * hop * L / M) samples, then zeros up to the longest row's count; pad_to still only pads the mel.  Each utterance is
+ * resampled as a signal of its own length: no filter tap sees padding or a neighbour.  Every flag keeps its meaning (ZVX_PCM16 rows
+ * are clamped as above); ZVX_NATIVE_RATE takes one call out of it. */
+
 /* Debug/parity taps: copy an intermediate of the last call to host fp32.
  * what: "encoder_out" [B][Tmax][hidden] (after the style add), "features" [B][Lmax][hidden],
  *       "mel" [B][Lmax][n_mels], "pitch_idx"/"energy_idx"/"duration" [B][Tmax] (as float). */
@@ -252,7 +290,7 @@ typedef struct {
 } zvx_kernel_stat;
 int        zvx_kernel_stats(zvx_ctx* ctx, zvx_kernel_stat* out, int max_out);
 /* The same counters grouped by pipeline stage ("encoder", "variance", "lenreg", "decoder", "decoder.norm", "voc.pre",
- * "voc.up1".."voc.res4", "voc.post", "spkemb"; name = stage): every launch of the stage, including the HBM-bound helper
+ * "voc.up1".."voc.res4", "voc.post", "voc.resample", "spkemb"; name = stage): every launch of the stage, including the HBM-bound helper
  * kernels, while "profile" == 2 and "profile_only" == -1.  Feeds the per-stage roofline fractions of bench.py. */
 int        zvx_tag_stats(zvx_ctx* ctx, zvx_kernel_stat* out, int max_out);
 zvx_status zvx_reset_stats(zvx_ctx* ctx);

@@ -12,8 +12,9 @@ LIB_PATH = os.path.join(HERE, "libzvx.so")
 
 ZVX_OK = 0
 ZVX_E_INVALID, ZVX_E_MANIFEST, ZVX_E_HIP, ZVX_E_STATE, ZVX_E_BUFFER, ZVX_E_UNSUPPORTED = 1, 2, 3, 4, 5, 6
-ZVX_DEVICE_OUT, ZVX_NO_SYNC, ZVX_PCM16, ZVX_DEVICE_IN, ZVX_HOST_ASYNC = 1, 2, 4, 8, 16
+ZVX_DEVICE_OUT, ZVX_NO_SYNC, ZVX_PCM16, ZVX_DEVICE_IN, ZVX_HOST_ASYNC, ZVX_NATIVE_RATE = 1, 2, 4, 8, 16, 32
 STAGES = ("encoder", "variance", "lenreg", "decoder", "vocoder", "spkemb")
+ZVX_T_RESAMPLE = 6                                   # its own accessor (Context.resample_ms): stage_times() keeps exactly STAGES
 ZVX_T_COUNT = 8
 
 EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_set_int", "zvx_spkemb", "zvx_melspec", "zvx_encode",
@@ -21,8 +22,16 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_sync", "zvx_stage_times", "zvx_kernel_stats", "zvx_tag_stats", "zvx_reset_stats",
            "zvx_comm_unique_id", "zvx_comm_init", "zvx_comm_gather", "zvx_comm_barrier", "zvx_comm_max_f64", "zvx_comm_info", "zvx_comm_destroy",
            "zvx_dev_alloc", "zvx_dev_free", "zvx_dev_from_host", "zvx_dev_to_host", "zvx_spkemb_ex", "zvx_wait_host",
-           "zvx_encode_ex", "zvx_synthesize_ex")
+           "zvx_encode_ex", "zvx_synthesize_ex", "zvx_resample", "zvx_resample_ex")
 ZVX_COMM_ID_BYTES = 128
+
+
+def resampled_len(n, rate_in, rate_out):
+    """ceil(n * L / M) with L / M = rate_out / rate_in in lowest terms: the samples zvx_resample makes of n (exact integers)."""
+    from math import gcd
+    g = gcd(int(rate_in), int(rate_out))
+    L, M = int(rate_out) // g, int(rate_in) // g
+    return (int(n) * L + M - 1) // M
 
 
 class ZvxError(RuntimeError):
@@ -88,6 +97,8 @@ def load():
     lib.zvx_dev_from_host.argtypes = [vp, vp, vp, C.c_size_t]
     lib.zvx_spkemb_ex.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int]
     lib.zvx_wait_host.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    lib.zvx_resample.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int]
+    lib.zvx_resample_ex.argtypes = lib.zvx_resample.argtypes + [C.c_int64, C.c_int64, C.c_int64]
     _lib = lib
     return lib
 
@@ -169,6 +180,37 @@ class Context:
         self._chk(self._lib.zvx_melspec(self._h, _ptr(wav), _ptr(n), B, Nmax, _ptr(mel), Tmax, _ptr(frames)))
         return mel, frames
 
+    def resample(self, rows, rate_in, rate_out, pcm16=False, lengths=None):
+        """zvx_resample: a list of 1-D float waveforms (or a padded 2-D array + lengths) at rate_in -> (out [B][max out_len], out_len [B])
+        at rate_out: float32, or int16 PCM (x32760, clamped, truncated) with pcm16; row b holds out_len[b] samples, then zeros."""
+        return self.resample_window(rows, rate_in, rate_out, pcm16=pcm16, lengths=lengths)
+
+    def resample_window(self, rows, rate_in, rate_out, in_origin=0, out_begin=0, out_count=-1, pcm16=False, lengths=None):
+        """zvx_resample_ex: the rows hold samples [in_origin, in_origin + len) of signals that are zero elsewhere; outputs
+        [out_begin, out_begin + out_count) (out_count -1: to the end of each row's signal) -> (out [B][n], out_len [B])."""
+        if lengths is None:
+            B = len(rows)
+            n = np.array([len(w) for w in rows], np.int32)
+            Nmax = max(int(n.max()), 1)
+            x = np.zeros((B, Nmax), np.float32)
+            for b, w in enumerate(rows):
+                x[b, :n[b]] = np.asarray(w, np.float32)
+        else:
+            x = _f32(rows)
+            B, Nmax = x.shape
+            n = _i32(lengths, (B,))
+        if out_count >= 0:
+            cols = int(out_count)
+        else:
+            cols = max(0, max(resampled_len(int(in_origin) + int(v), rate_in, rate_out) for v in n) - int(out_begin))
+        out = np.empty((B, max(cols, 1)), np.int16 if pcm16 else np.float32)
+        if cols == 0:
+            out[:] = 0
+        out_len = np.zeros(B, np.int32)
+        self._chk(self._lib.zvx_resample_ex(self._h, _ptr(x), _ptr(n), B, Nmax, int(rate_in), int(rate_out), _ptr(out), max(cols, 1), _ptr(out_len),
+                                            ZVX_PCM16 if pcm16 else 0, int(in_origin), int(out_begin), int(out_count)))
+        return out[:, :cols], out_len
+
     def _prosody(self, prosody, B, Tmax):
         """-> (struct, keep-alive) for the _ex entry points, or (None, None): the plain ones run."""
         from .prosody import resolve
@@ -208,30 +250,40 @@ class Context:
         self._chk(self._lib.zvx_decode_features(self._h, _ptr(features), _ptr(L), B, Lmax, _ptr(spk), _ptr(mel), Lmax))
         return mel
 
-    def vocode(self, B, mel_len, pad_to=None, pcm16=False):
+    def out_samples(self, n_native, native_rate=False):
+        """samples a waveform call hands back for n_native generator samples: the same at the model's rate (out_rate 0 or native_rate),
+        else resampled_len to the context's out_rate"""
+        rate = 0 if native_rate else self.get_int("out_rate")
+        return int(n_native) if not rate else resampled_len(n_native, self.get_int("sampling_rate"), rate)
+
+    def vocode(self, B, mel_len, pad_to=None, pcm16=False, native_rate=False):
         """wav [B][max(mel_len)*hop]: float32, or int16 PCM (x32760, truncated) with pcm16.  The array is created with
-        np.empty on purpose: the library owns every byte it hands back (valid samples, then zeros)."""
-        n0 = int(np.max(mel_len)) * self.hop
+        np.empty on purpose: the library owns every byte it hands back (valid samples, then zeros).  Under an output rate
+        (set_int("out_rate", hz)) the rows are out_samples(mel_len*hop) long; native_rate=True (ZVX_NATIVE_RATE) ignores it."""
+        n0 = self.out_samples(int(np.max(mel_len)) * self.hop, native_rate)
         n = max(n0, 1)
         wav = (np.empty if n0 > 0 else np.zeros)((B, n), np.int16 if pcm16 else np.float32)    # all lengths 0: nothing is copied back
         pt = _i32(pad_to, (B,)) if pad_to is not None else None
-        self._chk(self._lib.zvx_vocode(self._h, _ptr(pt), _ptr(wav), n, ZVX_PCM16 if pcm16 else 0))
+        self._chk(self._lib.zvx_vocode(self._h, _ptr(pt), _ptr(wav), n, (ZVX_PCM16 if pcm16 else 0) | (ZVX_NATIVE_RATE if native_rate else 0)))
         return wav
 
-    def vocode_mel(self, mel, P, pcm16=False, host_async=False):
-        """host_async: the call only queues work and returns the pinned host slot (wait_host(slot) hands out the rows)."""
+    def vocode_mel(self, mel, P, pcm16=False, host_async=False, native_rate=False):
+        """host_async: the call only queues work and returns the pinned host slot (wait_host(slot) hands out the rows).
+        Rows are in samples of the context's out_rate unless native_rate (ZVX_NATIVE_RATE)."""
+        fl = (ZVX_PCM16 if pcm16 else 0) | (ZVX_NATIVE_RATE if native_rate else 0)
         mel = _f32(mel)
         B, Pmax, nm = mel.shape
         assert nm == self.n_mels
         P = _i32(P, (B,))
         if host_async:
-            self._chk(self._lib.zvx_vocode_mel(self._h, _ptr(mel), _ptr(P), B, Pmax, None, 0, ZVX_HOST_ASYNC | (ZVX_PCM16 if pcm16 else 0)))
+            self._chk(self._lib.zvx_vocode_mel(self._h, _ptr(mel), _ptr(P), B, Pmax, None, 0, ZVX_HOST_ASYNC | fl))
             return self.get_int("host_slot")
-        n = int(P.max()) * self.hop
+        n = self.out_samples(int(P.max()) * self.hop, native_rate)
         wav = np.empty((B, n), np.int16 if pcm16 else np.float32)
-        self._chk(self._lib.zvx_vocode_mel(self._h, _ptr(mel), _ptr(P), B, Pmax, _ptr(wav), n, ZVX_PCM16 if pcm16 else 0))
-        if n < Pmax * self.hop:                                      # callers index rows up to Pmax*hop
-            wav = np.concatenate([wav, np.zeros((B, Pmax * self.hop - n), wav.dtype)], axis=1)
+        self._chk(self._lib.zvx_vocode_mel(self._h, _ptr(mel), _ptr(P), B, Pmax, _ptr(wav), n, fl))
+        nfull = self.out_samples(Pmax * self.hop, native_rate)
+        if n < nfull:                                                # callers index rows up to Pmax*hop (in output samples)
+            wav = np.concatenate([wav, np.zeros((B, nfull - n), wav.dtype)], axis=1)
         return wav
 
     def synthesize(self, phoneme, puncts, T, spk, duration=None, pad_to=None, want_mel=True, Lmax_cap=0,
@@ -242,7 +294,8 @@ class Context:
         With a device waveform (wav_device_ptr) the mel, if wanted, is a device buffer too (ZVX_DEVICE_OUT covers both outputs):
         mel_device_ptr -> [B][Lmax][n_mels] f32 with Lmax = the longest utterance's forced-duration sum (or Lmax_cap).
         prosody: None, a prosody.Prosody or a dict of Prosody.create keywords (zvx_synthesize_ex); forced durations are then sized
-        by the scaled lengths."""
+        by the scaled lengths.  Under an output rate (set_int("out_rate", hz)) the waveform rows, wav_stride and wait_host's rows are
+        in samples of that rate: row b carries out_samples(mel_len[b] * hop) of them."""
         phoneme = _i32(phoneme)
         B, Tmax = phoneme.shape
         puncts = _i32(puncts, (B, Tmax))
@@ -278,7 +331,7 @@ class Context:
                     raise ZvxError(ZVX_E_INVALID, "a device waveform output takes a device mel output (mel_device_ptr) or want_mel=False")
                 mptr = C.c_void_p(int(mel_device_ptr))
         else:
-            stride = max(Lmax * self.hop, 1)
+            stride = max(self.out_samples(Lmax * self.hop), 1)
             wav = np.zeros((B, stride), np.int16 if pcm16 else np.float32)
             wptr = _ptr(wav)
         args = (self._h, _ptr(phoneme), _ptr(puncts), _ptr(dur), _ptr(T), B, Tmax, _ptr(spk), _ptr(pt), Lmax, wptr, stride, _ptr(mel_len),
@@ -309,6 +362,12 @@ class Context:
         ms = np.zeros(ZVX_T_COUNT, np.float32)
         self._chk(self._lib.zvx_stage_times(self._h, _ptr(ms)))
         return {n: float(ms[i]) for i, n in enumerate(STAGES)}
+
+    def resample_ms(self):
+        """hipEvent time of the resample stage of the last waveform call or resample() (profile >= 1; 0.0: that call ran none)"""
+        ms = np.zeros(ZVX_T_COUNT, np.float32)
+        self._chk(self._lib.zvx_stage_times(self._h, _ptr(ms)))
+        return float(ms[ZVX_T_RESAMPLE])
 
     def kernel_stats(self):
         arr = (KernelStat * 32)()

@@ -3,6 +3,8 @@
 // channel-contiguous vector loads elsewhere.
 #include "zvx_kernels.h"
 
+#include <algorithm>
+
 namespace zvx {
 
 __device__ __forceinline__ float ld(const void* p, int dt, long i) {
@@ -1294,6 +1296,118 @@ __global__ __launch_bounds__(64) void k_fc_rows4(const float* x, int ldx, const 
 void launch_fc_rows(const float* x, int ldx, const float* w, int ldw, const float* bias, float* out, int ldo, int B, int N, int K, hipStream_t s) {
     if (B > 32) hipLaunchKernelGGL(k_fc_rows4, dim3((N + 3) / 4, (B + 15) / 16), dim3(64), 0, s, x, ldx, w, ldw, bias, out, ldo, B, N, K);
     else hipLaunchKernelGGL(k_fc_rows, dim3(N, (B + 15) / 16), dim3(64), 0, s, x, ldx, w, ldw, bias, out, ldo, B, N, K);
+}
+
+// ---------------------------------------------------------------- band-limited rational resampler (polyphase FIR)
+// y[n] = sum_k h[n M - k L] x[k] over the window described in zvx_kernels.h (ResampleArgs).  One workgroup loads the polyphase bank
+// [L][pitch] into LDS once and then produces `tpb` tiles of `tile` consecutive outputs of one row; per tile the input span
+// [kstart(first n), kstart(last n) + T) is staged in LDS with 16-byte loads (zeros outside the row's samples), every thread computes 4
+// consecutive outputs (which 4: see `strided` below).  kstart(n) = ceil((n M - half) / L) = k0 - joff[p] with n M = k0 L + p; joff[p] sits
+// in column T of the bank row, so a thread divides once per tile (64 bits) and steps (k0, p) from there by its output stride times M.
+// The sum of one output: acc = bank[p][0] * x[ks]; acc = fma(bank[p][t], x[ks + t], acc) for t = 1 .. T-1 -- one order, fixed by (L, M)
+// alone; a tap outside the row's samples multiplies a staged 0.0f.  Nothing in it depends on the tile, the batch or the window.
+__global__ __launch_bounds__(256) void k_resample_poly(const ResampleArgs a, int tile, int tpb, int xcap) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
+    float* bk = (float*)sm;
+    const int nbank = (a.L * a.pitch + 3) & ~3;
+    float* xs = bk + nbank;
+    const int b = blockIdx.y, tid = threadIdx.x;
+    for (int i = tid * 4; i < nbank; i += 1024) *(float4*)(bk + i) = *(const float4*)(a.bank + i);      // (the device bank is padded to 4 floats)
+    const long nin = (long)a.in_len[b] * a.in_mul;
+    long cnt = a.out_count;                                  // outputs of this row, counted from out_begin
+    if (cnt < 0) { cnt = ((a.in_origin + nin) * a.L + a.M - 1) / a.M - a.out_begin; if (cnt < 0) cnt = 0; }
+    if (cnt > a.out_max) cnt = a.out_max;
+    const float* xrow = a.x + (long)b * a.x_bs;
+    const bool vec_in = (((size_t)a.x & 15) == 0) && ((a.x_bs & 3) == 0);
+    const bool vec_out = (a.out_bs & 3) == 0 && (((size_t)a.out & (a.pcm16 ? 7 : 15)) == 0);
+    // which 4 outputs of a tile a lane takes.  Up-conversion (M < L): tid + 256 q -- neighbouring lanes take neighbouring outputs, whose input
+    // windows start at most one sample apart (LDS reads of one address broadcast) and whose phases step by M mod L; each lane stores 4 bytes of
+    // a 256-byte run.  Down-conversion: 4 tid + q -- a lane's windows start 4 M / L samples after its neighbour's, and the lane stores its
+    // 4 outputs as one vector.  The bank's pitch is chosen for the same step (zvx.hip, rs_pick_pitch); an output's sum does not depend on it.
+    const bool strided = a.M < a.L;
+    const int step = strided ? 256 * a.M : a.M, dk = step / a.L, dp = step % a.L;
+    auto put = [&](long i, float v) {
+        if (a.pcm16) ((short*)a.out)[b * a.out_bs + i] = (short)fminf(fmaxf(v * 32760.0f, -32768.0f), 32767.0f);     // clamp, then truncate
+        else ((float*)a.out)[b * a.out_bs + i] = v;
+    };
+    for (int tt = 0; tt < tpb; tt++) {
+        const long i0 = ((long)blockIdx.x * tpb + tt) * tile;
+        if (i0 >= a.out_max) break;
+        const long iend = i0 + tile < a.out_max ? i0 + tile : a.out_max;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        auto idx = [&](int q) { return strided ? i0 + tid + 256 * q : i0 + 4 * tid + q; };
+        if (i0 < cnt) {                                      // (uniform over the workgroup)
+            const long ilast = (iend < cnt ? iend : cnt) - 1;
+            auto kstart_floor = [&](long n) { const long t = n * a.M - a.half; return t >= 0 ? t / a.L : -((-t + a.L - 1) / a.L); };
+            const long k_lo = kstart_floor(a.out_begin + i0) & ~3L;                // a lower bound of kstart, on a 4-sample boundary of the signal
+            const long k_hi = kstart_floor(a.out_begin + ilast) + 1 + a.T;         // exclusive upper bound
+            const long li_lo = k_lo - a.in_origin;                                 // row index of xs[0]
+            const bool vin = vec_in && (a.in_origin & 3) == 0;
+            const int span = (int)(k_hi - k_lo);                                   // <= xcap by the launcher's choice of `tile`
+            __syncthreads();                                                        // the previous tile's readers are done (first tile: the bank is in)
+            for (int j = tid * 4; j < span && j < xcap; j += 1024) {
+                const long li = li_lo + j;
+                float4 t = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (vin && li >= 0 && li + 3 < nin) t = *(const float4*)(xrow + li);
+                else {
+                    if (li >= 0 && li < nin) t.x = xrow[li];
+                    if (li + 1 >= 0 && li + 1 < nin) t.y = xrow[li + 1];
+                    if (li + 2 >= 0 && li + 2 < nin) t.z = xrow[li + 2];
+                    if (li + 3 >= 0 && li + 3 < nin) t.w = xrow[li + 3];
+                }
+                *(float4*)(xs + j) = t;
+            }
+            __syncthreads();
+            if (idx(0) < iend && idx(0) < cnt) {
+                const unsigned long nM = (unsigned long)(a.out_begin + idx(0)) * (unsigned long)a.M;
+                long k0 = (long)(nM / (unsigned long)a.L);
+                int p = (int)(nM - (unsigned long)k0 * (unsigned long)a.L);
+#pragma unroll
+                for (int q = 0; q < 4; q++) {
+                    if (idx(q) < iend && idx(q) < cnt) {
+                        const float* br = bk + p * a.pitch;
+                        const float* xp = xs + (int)(k0 - __float_as_int(br[a.T]) - k_lo);
+                        float acc = br[0] * xp[0];
+                        for (int t = 1; t < a.T; t++) acc = __builtin_fmaf(br[t], xp[t], acc);
+                        v[q] = acc;
+                    }
+                    k0 += dk; p += dp;
+                    if (p >= a.L) { p -= a.L; k0++; }
+                }
+            }
+        }
+        if (idx(0) >= iend) continue;
+        if (!strided && vec_out && idx(3) < iend) {
+            const long i = idx(0);
+            if (a.pcm16) {
+                short4 o;
+                o.x = (short)fminf(fmaxf(v[0] * 32760.0f, -32768.0f), 32767.0f); o.y = (short)fminf(fmaxf(v[1] * 32760.0f, -32768.0f), 32767.0f);
+                o.z = (short)fminf(fmaxf(v[2] * 32760.0f, -32768.0f), 32767.0f); o.w = (short)fminf(fmaxf(v[3] * 32760.0f, -32768.0f), 32767.0f);
+                *(short4*)((short*)a.out + b * a.out_bs + i) = o;
+            } else *(float4*)((float*)a.out + b * a.out_bs + i) = make_float4(v[0], v[1], v[2], v[3]);
+        } else {
+            for (int q = 0; q < 4; q++) if (idx(q) < iend) put(idx(q), v[q]);
+        }
+    }
+}
+// false (nothing launched): the bank and one tile's input span do not fit the LDS a workgroup may have
+bool launch_resample_poly(const ResampleArgs& a, hipStream_t s) {
+    if (a.B <= 0 || a.out_max <= 0) return true;
+    const size_t nbank = ((size_t)a.L * a.pitch + 3) & ~(size_t)3;
+    // tile: outputs per pass (a multiple of 4, 1024 where the span fits); its input span is at most (tile - 1) M / L + T + 2 samples, + 3 for
+    // the aligned start, rounded up to whole float4s
+    int tile = 1024;
+    auto cap = [&](int t) { return (int)((((long)(t - 1) * a.M) / a.L + a.T + 2 + 3 + 4 + 3) & ~3L); };
+    while (tile > 4 && (nbank + cap(tile)) * 4 > 96 * 1024) tile >>= 1;
+    const int xcap = cap(tile);
+    const size_t lds = (nbank + xcap) * 4;
+    if (lds > 160 * 1024) return false;
+    if (lds > 64 * 1024 && !lds_opt_in((const void*)k_resample_poly)) return false;
+    // the bank is read once per workgroup: long rows take several tiles per workgroup, short ones keep the grid wide
+    const long tiles = (a.out_max + tile - 1) / tile;
+    int tpb = (int)std::min<long>(8, std::max<long>(1, tiles * a.B / 2048));
+    hipLaunchKernelGGL(k_resample_poly, dim3((unsigned)((tiles + tpb - 1) / tpb), a.B), dim3(256), lds, s, a, tile, tpb, xcap);
+    return true;
 }
 
 }  // namespace zvx

@@ -150,6 +150,11 @@ struct zvx_ctx {
     int use_pairstream = 1;                // zvx_set_int("pairstream", v): C = 128 ResBlock pairs on pairstream.hip: 1 = every k (default; jobs under ~200 k rows run the bit-identical two-launch path), 3 = every k and every job size (tests), -1 / 0 = two conv-slab launches per pair (the bit-equality reference)
     int shape_log = 0;                     // zvx_set_int("shape_log", 1): one stderr line per timed launch (profile 2)
     int max_frames = 1 << 18;              // hard cap on a predicted mel length (guards the allocation, fs2.py:678-681 has none)
+    // Output rate (zvx_set_int("out_rate", hz); 0 = the model's own rate): the waveform calls resample their rows on the device as
+    // their last launch (do_vocode).  The polyphase banks are designed on the host in double, rounded once to f32 and kept per (L, M).
+    int out_rate = 0;
+    struct RsBank { int L = 0, M = 0, half = 0, T = 0, pitch = 0; const float* dev = nullptr; };
+    std::map<std::pair<int, int>, RsBank> rs_banks;
     hipEvent_t stage_ev[ZVX_T_COUNT][2];
     bool stage_used[ZVX_T_COUNT];
     float stage_ms[ZVX_T_COUNT];
@@ -1911,16 +1916,174 @@ void run_melspec(zvx_ctx* c, const float* wav, const int32_t* nsamples, int B, i
     c->sync();
 }
 
+// ------------------------------------------------------------------------------------------------
+// sample-rate conversion (include/zvx.h: zvx_resample, "out_rate")
+// ------------------------------------------------------------------------------------------------
+constexpr int RS_MAX_PHASES = 640;       // max(L, M) a bank is built for: every pair between 22050 and 8000 ... 48000
+constexpr int RS_ZEROS = 10;             // half = RS_ZEROS * max(L, M): the filter spans 10 zero crossings of the sinc on each side
+constexpr double RS_BETA = 5.0;          // Kaiser window (both as scipy.signal.resample_poly's defaults)
+
+// rate_in -> rate_out as (L, M); equal rates: (1, 1).  ZVX_E_INVALID / ZVX_E_UNSUPPORTED as include/zvx.h states them.
+void rs_pair(int rate_in, int rate_out, int* L, int* M) {
+    for (int r : {rate_in, rate_out}) if (r < 4000 || r > 192000) fail(ZVX_E_INVALID, "sampling rate %d Hz outside [4000, 192000]", r);
+    int a = rate_in, b = rate_out;
+    while (b) { const int t = a % b; a = b; b = t; }
+    *L = rate_out / a; *M = rate_in / a;
+    if (std::max(*L, *M) > RS_MAX_PHASES)
+        fail(ZVX_E_UNSUPPORTED, "resampling %d -> %d Hz needs L = %d, M = %d: the polyphase bank is built for max(L, M) <= %d", rate_in, rate_out, *L, *M, RS_MAX_PHASES);
+}
+long rs_out_len(long n, int L, int M) { return (n * L + M - 1) / M; }
+
+double bessel_i0(double x) {
+    double s = 1.0, t = 1.0;
+    for (int k = 1; k < 64; k++) { t *= (x / (2.0 * k)) * (x / (2.0 * k)); s += t; if (t < 1e-20 * s) break; }
+    return s;
+}
+// The row pitch of the bank in LDS: lanes of a wave read bank[p_i][t] with one t and phases p_i stepping by M mod L (up-conversion:
+// neighbouring lanes take neighbouring outputs) or 4 M mod L (down-conversion: 4 consecutive outputs per lane), 32 lanes per
+// ds_read_b32 group over 32 banks.  The worst pile-up over all start phases is counted for each pitch in
+// [T + 1, T + 8] and the smallest sum wins (an odd pitch spreads distinct phases over the banks; which odd one depends on L and M).
+int rs_pick_pitch(int L, int M, int T) {
+    const int step = (int)(((M < L ? 1L : 4L) * M) % L);
+    int best = T + 1; long best_cost = -1;
+    for (int pitch = T + 1; pitch <= T + 8; pitch++) {
+        long cost = 0;
+        for (int p0 = 0; p0 < L; p0++) {
+            int owner[32][8], n[32] = {0}, worst = 1;
+            for (int i = 0, p = p0; i < 32; i++, p = (p + step) % L) {
+                const int bank = (int)(((long)p * pitch) % 32);
+                bool seen = false;
+                for (int j = 0; j < n[bank] && j < 8; j++) seen |= owner[bank][j] == p;      // one address: a broadcast
+                if (!seen) { if (n[bank] < 8) owner[bank][n[bank]] = p; n[bank]++; worst = std::max(worst, n[bank]); }
+            }
+            cost += worst;
+        }
+        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = pitch; }
+    }
+    return best;
+}
+// The filter of include/zvx.h, designed in double and rounded once to f32, as the polyphase bank launch_resample_poly reads
+// (zvx_kernels.h).  Built and uploaded on first use of (L, M), then kept for the life of the context.
+const zvx_ctx::RsBank& rs_bank(zvx_ctx* c, int L, int M) {
+    auto it = c->rs_banks.find({L, M});
+    if (it != c->rs_banks.end()) return it->second;
+    zvx_ctx::RsBank bk;
+    bk.L = L; bk.M = M;
+    std::vector<float> host;
+    if (L == 1 && M == 1) {                                  // equal rates: one tap of 1.0f, a copy
+        bk.half = 0; bk.T = 1; bk.pitch = 2;
+        host = {1.0f, 0.0f, 0.0f, 0.0f};
+    } else {
+        const int mx = std::max(L, M), half = RS_ZEROS * mx, N = 2 * half + 1;
+        std::vector<double> h(N);
+        const double fc = 1.0 / mx, i0b = bessel_i0(RS_BETA);
+        double sum = 0.0;
+        for (int i = 0; i < N; i++) {
+            const double m = i - half, r = m / half, px = M_PI * fc * m;
+            const double w = bessel_i0(RS_BETA * sqrt(std::max(0.0, 1.0 - r * r))) / i0b;
+            h[i] = fc * (m == 0 ? 1.0 : sin(px) / px) * w;
+            sum += h[i];
+        }
+        for (double& v : h) v = v / sum * L;
+        bk.half = half; bk.T = (N + L - 1) / L; bk.pitch = rs_pick_pitch(L, M, bk.T);
+        host.assign(((size_t)L * bk.pitch + 3) & ~(size_t)3, 0.0f);
+        for (int p = 0; p < L; p++) {
+            const int joff = (half - p) / L;
+            for (int t = 0; t < bk.T; t++) {
+                const long m = p + (long)(joff - t) * L;
+                if (m >= -half) host[(size_t)p * bk.pitch + t] = (float)h[m + half];
+            }
+            memcpy(&host[(size_t)p * bk.pitch + bk.T], &joff, 4);
+        }
+    }
+    float* d = c->fbuf("rs.bank." + std::to_string(L) + "." + std::to_string(M), host.size());
+    HIPCHK(hipMemcpyAsync(d, host.data(), host.size() * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                 // `host` goes away; once per (L, M)
+    bk.dev = d;
+    return c->rs_banks[{L, M}] = bk;
+}
+
+// The one resampling launch: stage tag "voc.resample", slot ZVX_T_RESAMPLE, algorithmic bytes = samples read + samples written.
+void run_resample(zvx_ctx* c, const zvx_ctx::RsBank& bk, const float* x_dev, long x_bs, const int* in_len_d, int in_mul, int B, void* out_dev,
+                  long out_bs, int pcm16, long in_origin, long out_begin, long out_count, long out_max, double nin, double nout) {
+    if (out_max <= 0) return;
+    ResampleArgs a{};
+    a.x = x_dev; a.x_bs = x_bs; a.in_len = in_len_d; a.in_mul = in_mul; a.out = out_dev; a.out_bs = out_bs; a.pcm16 = pcm16;
+    a.B = B; a.L = bk.L; a.M = bk.M; a.half = bk.half; a.T = bk.T; a.pitch = bk.pitch; a.bank = bk.dev;
+    a.in_origin = in_origin; a.out_begin = out_begin; a.out_count = out_count; a.out_max = out_max;
+    const std::string keep = c->tag;
+    c->tag = "voc.resample";
+    c->stage_begin(ZVX_T_RESAMPLE);
+    c->timed(2.0 * nout * bk.T, nin * 4.0 + nout * (pcm16 ? 2.0 : 4.0), [&] {
+        if (!launch_resample_poly(a, c->stream)) fail(ZVX_E_UNSUPPORTED, "resampler: L = %d, M = %d does not fit the LDS of a workgroup", bk.L, bk.M);
+    });
+    c->stage_end(ZVX_T_RESAMPLE);
+    c->tag = keep;
+}
+
+int model_rate(const zvx_ctx* c) {
+    auto it = c->cfg.find("sampling_rate");
+    if (it == c->cfg.end()) fail(ZVX_E_MANIFEST, "manifest: missing cfg 'sampling_rate'");
+    return atoi(it->second.c_str());
+}
+
+// zvx_resample / zvx_resample_ex
+void do_resample(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate_in, int rate_out, void* out, int64_t out_stride,
+                 int32_t* out_len, int flags, int64_t in_origin, int64_t out_begin, int64_t out_count) {
+    if (!in || !nsamples || !out || B <= 0 || Nmax <= 0) fail(ZVX_E_INVALID, "zvx_resample: bad arguments");
+    if (flags & ~(ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16)) fail(ZVX_E_INVALID, "zvx_resample: unknown flag in %d", flags);
+    if ((flags & ZVX_NO_SYNC) && !(flags & ZVX_DEVICE_OUT)) fail(ZVX_E_INVALID, "zvx_resample: ZVX_NO_SYNC needs ZVX_DEVICE_OUT");
+    if (in_origin < 0 || out_begin < 0 || out_count < -1 || in_origin > ((int64_t)1 << 40) || out_begin > ((int64_t)1 << 40) || out_count > INT32_MAX)
+        fail(ZVX_E_INVALID, "zvx_resample_ex: window out of range");
+    int L = 1, M = 1;
+    rs_pair(rate_in, rate_out, &L, &M);
+    for (int b = 0; b < B; b++) if (nsamples[b] < 0 || nsamples[b] > Nmax) fail(ZVX_E_INVALID, "nsamples[%d]=%d out of range (0..%d)", b, nsamples[b], Nmax);
+    std::vector<long> cnt(B);
+    long out_max = 0; double nin = 0, nout = 0;
+    for (int b = 0; b < B; b++) {
+        cnt[b] = out_count >= 0 ? (long)out_count : std::max(0L, rs_out_len((long)in_origin + nsamples[b], L, M) - (long)out_begin);
+        out_max = std::max(out_max, cnt[b]); nin += nsamples[b]; nout += (double)cnt[b];
+    }
+    if (out_max > INT32_MAX) fail(ZVX_E_INVALID, "zvx_resample: %ld output samples per row", out_max);
+    if (out_stride < out_max) fail(ZVX_E_BUFFER, "out_stride %lld < %ld samples", (long long)out_stride, out_max);
+    const zvx_ctx::RsBank& bk = rs_bank(c, L, M);
+    const int pcm16 = (flags & ZVX_PCM16) ? 1 : 0;
+    const size_t ss = pcm16 ? 2 : 4;
+    const float* x_dev = in;
+    if (!(flags & ZVX_DEVICE_IN)) {
+        float* xd = c->fbuf("rs.in", (size_t)B * Nmax);
+        HIPCHK(hipMemcpyAsync(xd, in, (size_t)B * Nmax * 4, hipMemcpyHostToDevice, c->stream));
+        x_dev = xd;
+    }
+    const int* len_d = c->upload_ints("rs.len", nsamples, B);
+    void* odev = out; long ostride = out_stride;
+    if (!(flags & ZVX_DEVICE_OUT)) { ostride = (std::max(out_max, 1L) + 7) & ~7L; odev = c->buf("rs.out", (size_t)B * ostride * ss); }
+    run_resample(c, bk, x_dev, Nmax, len_d, 1, B, odev, ostride, pcm16, in_origin, out_begin, out_count, out_max, nin, nout);
+    if (!(flags & ZVX_DEVICE_OUT) && out_max > 0)
+        HIPCHK(hipMemcpy2DAsync(out, (size_t)out_stride * ss, odev, (size_t)ostride * ss, (size_t)out_max * ss, B, hipMemcpyDeviceToHost, c->stream));
+    if (out_len) for (int b = 0; b < B; b++) out_len[b] = (int32_t)cnt[b];
+    if (!((flags & ZVX_DEVICE_OUT) && (flags & ZVX_NO_SYNC))) c->sync();
+}
+
 // wav: float rows, or int16 PCM rows with ZVX_PCM16 (stride counted in samples either way).  Row b receives
 // mel_len[b]*hop samples followed by zeros up to max_b(mel_len[b])*hop; nothing beyond that is touched.
 void do_vocode(zvx_ctx* c, const int32_t* pad_to, void* wav, int64_t wav_stride, int flags) {
     if (!c->have_mel) fail(ZVX_E_STATE, "zvx_vocode: no mel in the context (call zvx_decode first)");
     const int B = c->B;
+    // an output rate (zvx_set_int "out_rate") other than the model's: the generator writes f32 rows into a work buffer and the resampler
+    // writes the rows the caller sees -- `need`, the strides and the host slot's `valid` are then in OUTPUT samples.  ZVX_NATIVE_RATE
+    // takes the call out of it.
+    int rs_L = 1, rs_M = 1;
+    const bool rs = c->out_rate && !(flags & ZVX_NATIVE_RATE) && c->out_rate != model_rate(c);
+    if (rs) rs_pair(model_rate(c), c->out_rate, &rs_L, &rs_M);
+    else { c->stage_used[ZVX_T_RESAMPLE] = false; c->stage_ms[ZVX_T_RESAMPLE] = 0.f; }
     std::vector<int> P(B);
-    int need = 0;
-    for (int b = 0; b < B; b++) { P[b] = std::max(pad_to ? pad_to[b] : 0, c->mel_len_host[b]); need = std::max(need, c->mel_len_host[b] * c->hop); }
+    int need = 0, need_native = 0;
+    for (int b = 0; b < B; b++) { P[b] = std::max(pad_to ? pad_to[b] : 0, c->mel_len_host[b]); need_native = std::max(need_native, c->mel_len_host[b] * c->hop); }
+    need = rs ? (int)rs_out_len(need_native, rs_L, rs_M) : need_native;
     const bool host_async = flags & ZVX_HOST_ASYNC;
     if (!host_async && wav_stride < need) fail(ZVX_E_BUFFER, "wav_stride %lld < %d samples", (long long)wav_stride, need);
+    const zvx_ctx::RsBank* bank = rs ? &rs_bank(c, rs_L, rs_M) : nullptr;
     c->stage_begin(ZVX_T_VOCODER);
     void* wdev; long wstride;
     const bool dev_out = (flags & ZVX_DEVICE_OUT) && !host_async;
@@ -1955,8 +2118,20 @@ void do_vocode(zvx_ctx* c, const int32_t* pad_to, void* wav, int64_t wav_stride,
         if (f != c->gather_fence.end()) HIPCHK(hipStreamWaitEvent(c->stream, f->second, 0));
     }
     else { wstride = (std::max(need, 1) + 7) & ~7; wdev = c->buf("wav", (size_t)B * wstride * ss); }
-    run_vocoder(c, c->fbuf("mel", 0), c->n_mels, c->Lmax, c->mel_len_host.data(), P.data(), B, wdev, wstride, pcm16);
-    c->stage_end(ZVX_T_VOCODER);
+    if (rs) {
+        // on the main stream behind conv_post (no stream of its own: the context's four fill the hardware queues a process gets, see above)
+        const long nstride = (std::max(need_native, 1) + 7) & ~7;
+        float* native = c->fbuf("wav.native", (size_t)B * nstride);
+        run_vocoder(c, c->fbuf("mel", 0), c->n_mels, c->Lmax, c->mel_len_host.data(), P.data(), B, native, nstride, 0);
+        c->stage_end(ZVX_T_VOCODER);
+        double nin = 0, nout = 0;
+        for (int b = 0; b < B; b++) { nin += (double)c->mel_len_host[b] * c->hop; nout += (double)rs_out_len((long)c->mel_len_host[b] * c->hop, rs_L, rs_M); }
+        // each utterance is resampled as a signal of its own length, mel_len[b] * hop (the first B words of the vocoder's length table)
+        if (need > 0) run_resample(c, *bank, native, nstride, c->ibuf("voc.lens", 0), c->hop, B, wdev, wstride, pcm16, 0, 0, -1, need, nin, nout);
+    } else {
+        run_vocoder(c, c->fbuf("mel", 0), c->n_mels, c->Lmax, c->mel_len_host.data(), P.data(), B, wdev, wstride, pcm16);
+        c->stage_end(ZVX_T_VOCODER);
+    }
     if (host_async) {
         HIPCHK(hipEventRecord(hs->ready, c->stream));
         HIPCHK(hipStreamWaitEvent(c->copy_stream, hs->ready, 0));
@@ -2091,6 +2266,7 @@ const Switch kSwitches[] = {
     {"slab_flat", &zvx_ctx::slab_flat, flag},
     {"spk_pool_fuse", &zvx_ctx::spk_pool_fuse, flag},
     {"spk_s2_fuse", &zvx_ctx::spk_s2_fuse, flag},
+    {"out_rate", &zvx_ctx::out_rate, count},
 };
 const Switch* find_switch(const char* key) {
     for (const Switch& s : kSwitches) if (!strcmp(s.key, key)) return &s;
@@ -2131,6 +2307,11 @@ zvx_status zvx_set_int(zvx_ctx* c, const char* key, int64_t value) {
         if (!s) fail(ZVX_E_INVALID, "unknown option '%s'", key);
         if (!s->ok(value)) fail(ZVX_E_INVALID, "option '%s' does not take the value %lld", key, (long long)value);
         const std::string k(key);
+        if (k == "out_rate" && value) {                       // the predicate sees only the value: this key is checked against the model's rate,
+            int L = 1, M = 1;                                  // and its bank is built here, so that a queued call never designs or uploads one
+            rs_pair(model_rate(c), (int)value, &L, &M);
+            if ((int)value != model_rate(c)) rs_bank(c, L, M);
+        }
         if (k == "profile" || k == "profile_only" || k == "f16_sat_check" || k == "front_overlap") c->sync();
         c->*s->v = (int)value;
         if (k == "f16_sat_check") HIPCHK(hipMemsetAsync(c->sat_count_dev(), 0, 64, c->stream));      // (re)arms the audit and zeroes its counter
@@ -2230,6 +2411,16 @@ zvx_status zvx_vocode_mel(zvx_ctx* c, const float* mel, const int32_t* P, int B,
         c->have_mel = true;
         do_vocode(c, nullptr, wav, wav_stride, flags);
     });
+}
+
+zvx_status zvx_resample(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate_in, int rate_out, void* out,
+                        int64_t out_stride, int32_t* out_len, int flags) {
+    return guarded(c, [&] { do_resample(c, in, nsamples, B, Nmax, rate_in, rate_out, out, out_stride, out_len, flags, 0, 0, -1); });
+}
+
+zvx_status zvx_resample_ex(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate_in, int rate_out, void* out,
+                           int64_t out_stride, int32_t* out_len, int flags, int64_t in_origin, int64_t out_begin, int64_t out_count) {
+    return guarded(c, [&] { do_resample(c, in, nsamples, B, Nmax, rate_in, rate_out, out, out_stride, out_len, flags, in_origin, out_begin, out_count); });
 }
 
 zvx_status zvx_synthesize(zvx_ctx* c, const int32_t* phoneme, const int32_t* puncts, const int32_t* duration, const int32_t* T,

@@ -330,6 +330,24 @@ void launch_copy_rows_f32(const void* src, int s_dt, int lds, long s_bs, float* 
 void launch_conv_post_tanh(const void* x, int x_dt, int ldx, long x_bs, const float* w /*[k][C]*/, float bias,
                            int ktaps, int C, void* wav, long wav_bs, int pcm16, int B, int Nmax, const int* in_len,
                            int len_mul, const int* out_len, int out_mul, hipStream_t s);
+// Band-limited rational resampler, rate_in -> rate_out with L = rate_out / gcd, M = rate_in / gcd (include/zvx.h, zvx_resample):
+//   y[n] = sum_k h[n M - k L] x[k],  h = the Kaiser-windowed sinc of 2 * half + 1 taps designed by the context (zvx.hip, rs_bank).
+// Row b of x holds samples [in_origin, in_origin + in_len[b] * in_mul) of a signal that is zero elsewhere (in_len on the DEVICE, like
+// launch_conv_post_tanh's lengths: queued calls stay free of syncs); the launch writes outputs [out_begin, out_begin + cnt_b) to
+// positions [0, cnt_b) of row b of out, cnt_b = out_count, or with out_count < 0 ceil((in_origin + n_b) L / M) - out_begin, then zeros
+// up to out_max; nothing beyond out_max is written.  out: f32, or with pcm16 int16 = trunc(clamp(v * 32760, -32768, 32767)).
+// bank: [L][pitch] f32 on the device (padded to a multiple of 4 floats): row p holds the T = ceil((2 half + 1) / L) taps of phase p in
+// ascending input order, bank[p][t] = h[p + (joff[p] - t) L] (0 where that index is below -half), and in column T the integer
+// joff[p] = (half - p) / L as raw bits.  L = M = T = 1, half = 0, bank = {1.0f, 0}: a copy.
+struct ResampleArgs {
+    const float* x; long x_bs; const int* in_len; int in_mul;
+    void* out; long out_bs; int pcm16;
+    int B, L, M, half, T, pitch;
+    const float* bank;
+    long in_origin, out_begin, out_count, out_max;
+};
+// false (nothing launched) when the bank and one tile's input span exceed the LDS of a workgroup
+bool launch_resample_poly(const ResampleArgs& a, hipStream_t s);
 // half-mode saturation audit: *count += number of elements of x[b][r < rows[b]][0:C] (16-bit, batch stride bs, row stride ld) whose
 // magnitude bits are >= 0x7BFF (+-65504 = a clamped store, or Inf / NaN)
 void launch_count_sat16(const void* x, long bs, int ld, int B, int rows_max, const int* rows, int C, unsigned long long* count, hipStream_t s);

@@ -26,10 +26,13 @@ def main():
     ap.add_argument("--pitch-range", type=float, default=1.0, help="pitch spread about the utterance mean (0: flat, 1: as predicted)")
     ap.add_argument("--energy-shift", type=float, default=0.0)
     ap.add_argument("--energy-range", type=float, default=1.0)
+    ap.add_argument("--out-rate", type=int, default=0, help="output sampling rate in Hz, converted on the device (0: the model's rate)")
     args = ap.parse_args()
 
     modelcfg, synth = ZeroVoxTTS.load_model(args.model, args.meldec_model, infer_device=args.infer_device, precision=args.precision)
-    sr = modelcfg["audio"]["sampling_rate"]
+    if args.out_rate:
+        synth.output_rate = args.out_rate
+    sr = synth.output_rate                                  # RTF and the WAV header follow the rate of the samples handed back
     print("computing speaker embedding...")
     refmel = np.random.default_rng(0).standard_normal((args.refmel_frames, modelcfg["audio"]["num_mels"])).astype(np.float32)
     spkemb = synth.speaker_embed_from_mel(refmel)
@@ -42,7 +45,8 @@ def main():
         wav_len = wav.shape[0] / sr
         print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")
         if args.wav_filename:
-            write_wav_to_file(wav, length=length, filename=args.wav_filename, sample_rate=sr, hop_length=modelcfg["audio"]["hop_size"])
+            write_wav_to_file(wav, length=length, filename=args.wav_filename, sample_rate=sr, hop_length=modelcfg["audio"]["hop_size"],
+                              samples=len(wav))
         if i > warmup:
             rtf.append(wav_len / elapsed)
     if rtf:

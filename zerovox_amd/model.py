@@ -110,6 +110,22 @@ class ZeroVox:
     def ctx(self):
         return self._ctx
 
+    @property
+    def output_rate(self):
+        """sampling rate of every waveform the model hands back: the model's own by default; another rate is converted on the
+        device as the last launch of each waveform call (zvx_set_int "out_rate")"""
+        return self._ctx.get_int("out_rate") or self._ctx.get_int("sampling_rate")
+
+    @output_rate.setter
+    def output_rate(self, hz):
+        if self._streaming:
+            raise RuntimeError("output_rate while a synthesize_batches generator is active: its contexts are in use")
+        hz = int(hz or 0)
+        if hz == self._ctx.get_int("sampling_rate"):
+            hz = 0
+        for c in [self._ctx] + self._more_ctx:
+            c.set_int("out_rate", hz)
+
     def _spkemb(self, x):
         """ResNetSE34V2.forward: x [B, Tr, 80] -> [B, 1, hidden] (ResNetSE34V2.py:176-212)."""
         x = np.asarray(x, np.float32)
@@ -119,6 +135,7 @@ class ZeroVox:
     def inference_ex(self, x, style_embed, normalize_before=True, force_duration=False, prosody=None):
         """model.py:308-347.  x = {"phoneme" [1,T], "puncts" [1,T], "duration" [1,T]|None}; returns
         (wav[:mel_len*hop], mel_len, log_duration [1,T], mel [n_mels, mel_len]).  Batch-1 like the reference.
+        Under an output_rate the waveform holds resampled_len(mel_len*hop) samples of that rate; mel_len stays in frames.
         prosody: None, a prosody.Prosody or a dict of Prosody.create keywords (speed, pitch / energy shift and range, targets)."""
         phoneme = np.asarray(x["phoneme"], np.int32)
         puncts = np.asarray(x["puncts"], np.int32)
@@ -137,7 +154,7 @@ class ZeroVox:
         if ml > self._min_mel_len:
             self._min_mel_len = ml
         wav = self._ctx.vocode(1, mel_len, np.array([pad_to], np.int32))
-        return wav[0, : ml * self._hop_length], ml, logd, np.ascontiguousarray(mel[0, :ml].T)
+        return wav[0, : self._ctx.out_samples(ml * self._hop_length)], ml, logd, np.ascontiguousarray(mel[0, :ml].T)
 
     def inference(self, x, style_embed, normalize_before=True):
         wav, mel_len, log_duration, _ = self.inference_ex(x=x, style_embed=style_embed, normalize_before=normalize_before)
@@ -151,7 +168,20 @@ class ZeroVox:
     def vocode_stream(self, mel, chunk_frames=64, halo=STREAM_HALO, chunks_per_call=1):
         """Chunked vocoding for first-audio latency: mel [L, n_mels] -> yields waveform chunks (np.float32) that
         concatenate to ``vocode_mel(mel)``.  Every chunk is vocoded with ``halo`` extra frames on each side and only its
-        interior is kept; ``chunks_per_call`` chunks ride in one launch sequence as independent batch rows."""
+        interior is kept; ``chunks_per_call`` chunks ride in one launch sequence as independent batch rows.
+        Under an output rate (the context's "out_rate") the chunks are still vocoded at the native rate (ZVX_NATIVE_RATE) and the
+        stream is converted window by window (zerovox_amd.resample): the pieces concatenate bit for bit to the conversion of the
+        whole native stream; a piece is yielded once every sample under its filter has arrived."""
+        rate, native = self._ctx.get_int("out_rate"), self._ctx.get_int("sampling_rate")
+        if rate > 0 and rate != native:
+            from .resample import stream_resample
+            ctx = self._ctx
+            yield from stream_resample(self._vocode_stream_native(mel, chunk_frames, halo, chunks_per_call, True), native, rate,
+                                       lambda x, o, b, n: ctx.resample_window([x], native, rate, o, b, n)[0][0].copy())
+        else:
+            yield from self._vocode_stream_native(mel, chunk_frames, halo, chunks_per_call, False)
+
+    def _vocode_stream_native(self, mel, chunk_frames, halo, chunks_per_call, native_rate):
         mel = np.asarray(mel, np.float32)
         L, hop = mel.shape[0], self._hop_length
         starts = list(range(0, L, chunk_frames))
@@ -162,7 +192,7 @@ class ZeroVox:
             batch = np.zeros((len(grp), int(P.max()), mel.shape[1]), np.float32)
             for i, (lo, hi) in enumerate(spans):
                 batch[i, :hi - lo] = mel[lo:hi]
-            wav = self._ctx.vocode_mel(batch, P)
+            wav = self._ctx.vocode_mel(batch, P, native_rate=native_rate)
             for i, s in enumerate(grp):
                 lo = spans[i][0]
                 n = min(chunk_frames, L - s)
@@ -184,6 +214,7 @@ class ZeroVox:
                                "(exhaust or close() it first; a context is not re-entrant, include/zvx.h)")
         while len(self._more_ctx) < n - 1:
             self._more_ctx.append(_lib.Context(self._packed[0], self._packed[1], self._device))
+            self._more_ctx[-1].set_int("out_rate", self._ctx.get_int("out_rate"))       # every context of the model delivers at its output_rate
         ctxs = [self._ctx] + self._more_ctx[:n - 1]
         self._streaming = True
         try:

@@ -53,12 +53,9 @@ class ZeroVoxTTS:
         return sorted((f for f in os.listdir(refdir) if f.endswith(".wav")), key=str.casefold)
 
     @staticmethod
-    def get_speakerref(speakerref, sampling_rate):
-        """Load a reference wav (8/16/32-bit PCM) as float32 mono at ``sampling_rate`` (synthesize.py:112-121).  The reference
-        goes through ``librosa.load(sr=sampling_rate)``, which resamples with soxr_hq; here a file at another rate is
-        resampled with a polyphase Kaiser filter (scipy.signal.resample_poly) -- the same band-limited signal, not
-        bit-identical to soxr (parity of resampled references is unpinned: librosa/soxr are not installable here)."""
-        with wave.open(str(speakerref), "rb") as w:
+    def _read_pcm(path):
+        """a wav file (8/16/32-bit PCM) -> (float32 mono in [-1, 1), its sampling rate)"""
+        with wave.open(str(path), "rb") as w:
             sr, nch, sw = w.getframerate(), w.getnchannels(), w.getsampwidth()
             raw = w.readframes(w.getnframes())
         dt = {1: np.uint8, 2: np.int16, 4: np.int32}[sw]
@@ -66,6 +63,15 @@ class ZeroVoxTTS:
         a = (a - 128.0) / 128.0 if sw == 1 else a / float(2 ** (8 * sw - 1))
         if nch > 1:
             a = a.reshape(-1, nch).mean(axis=1)
+        return a, sr
+
+    @staticmethod
+    def get_speakerref(speakerref, sampling_rate):
+        """Load a reference wav (8/16/32-bit PCM) as float32 mono at ``sampling_rate`` (synthesize.py:112-121).  The reference
+        goes through ``librosa.load(sr=sampling_rate)``, which resamples with soxr_hq; here a file at another rate is
+        resampled with a polyphase Kaiser filter (scipy.signal.resample_poly) -- the same band-limited signal, not
+        bit-identical to soxr (parity of resampled references is unpinned: librosa/soxr are not installable here)."""
+        a, sr = ZeroVoxTTS._read_pcm(speakerref)
         if sr != sampling_rate:
             from math import gcd
             from scipy.signal import resample_poly
@@ -73,8 +79,23 @@ class ZeroVoxTTS:
             a = resample_poly(a.astype(np.float64), int(sampling_rate) // g, int(sr) // g).astype(np.float32)
         return a
 
-    def speaker_embed(self, wav: np.ndarray):
-        """wav -> [1, 1, hidden] speaker embedding (synthesize.py:123-143)."""
+    def speakerref_samples(self, path):
+        """A reference wav file as float32 mono at the model's rate: read at its own rate and converted on the device (zvx_resample),
+        where ``get_speakerref`` -- a static method without a context -- converts on the host."""
+        a, sr = self._read_pcm(path)
+        if sr != self._sampling_rate:
+            a = self._model.ctx.resample([a], sr, self._sampling_rate)[0][0]
+        return a
+
+    def speaker_embed_file(self, path):
+        """reference wav file -> [1, 1, hidden] speaker embedding; every step after the PCM decoding runs in libzvx"""
+        return self.speaker_embed(self.speakerref_samples(path))
+
+    def speaker_embed(self, wav: np.ndarray, sampling_rate=None):
+        """wav -> [1, 1, hidden] speaker embedding (synthesize.py:123-143).  ``sampling_rate``: the rate of ``wav`` where it is not the
+        model's; it is converted on the device before the trim, as librosa.load(sr=...) converts before librosa.effects.trim."""
+        if sampling_rate is not None and int(sampling_rate) != int(self._sampling_rate):
+            wav = self._model.ctx.resample([np.asarray(wav, np.float32)], int(sampling_rate), self._sampling_rate)[0][0]
         wav = trim_silence(wav, top_db=40)
         mel, frames = self._model.ctx.melspec([wav])                      # get_mel_from_wav on the device (zvx_melspec)
         return self._model._spkemb(mel[:, :int(frames[0])])
@@ -165,6 +186,16 @@ class ZeroVoxTTS:
         yield from self._model.vocode_stream(mel, chunk_frames=chunk_frames, chunks_per_call=chunks_per_call)
 
     @property
+    def output_rate(self):
+        """sampling rate of the waveforms tts / tts_ex / tts_stream hand back (default: the model's); set it to have them converted
+        on the device.  The returned ``length`` stays in mel frames; the waveform holds resampled_len(length * hop) samples."""
+        return self._model.output_rate
+
+    @output_rate.setter
+    def output_rate(self, hz):
+        self._model.output_rate = hz
+
+    @property
     def normalizer(self):
         return self._normalizer
 
@@ -202,9 +233,13 @@ class ZeroVoxTTS:
         return modelcfg, synth
 
 
-def write_wav_to_file(wav, length, filename, sample_rate, hop_length):
-    """demo.py:29-35: int16 PCM, x32760, cut to length*hop."""
-    pcm = (np.asarray(wav) * 32760).astype("int16")[: length * hop_length]
+def write_wav_to_file(wav, length, filename, sample_rate, hop_length, samples=None):
+    """demo.py:29-35: int16 PCM, x32760, cut to length*hop -- or to `samples` where the waveform is not at the model's rate
+    (ZeroVoxTTS.output_rate: length stays in mel frames, the rows are resampled_len(length*hop) long and may overshoot [-1, 1])."""
+    if samples is not None:
+        pcm = np.clip(np.asarray(wav, np.float32) * np.float32(32760), -32768, 32767).astype("int16")[: int(samples)]
+    else:
+        pcm = (np.asarray(wav) * 32760).astype("int16")[: length * hop_length]
     with wave.open(str(filename), "wb") as w:
         w.setnchannels(1); w.setsampwidth(2); w.setframerate(sample_rate)
         w.writeframes(pcm.tobytes())
