@@ -60,6 +60,7 @@ enum {                   /* flags */
 enum {                   /* zvx_stage_times indices (milliseconds, hipEvent-timed on the ctx stream) */
     ZVX_T_ENCODER = 0, ZVX_T_VARIANCE = 1, ZVX_T_LENREG = 2, ZVX_T_DECODER = 3, ZVX_T_VOCODER = 4,
     ZVX_T_SPKEMB = 5, ZVX_T_RESAMPLE = 6,   /* the sample-rate conversion of the last waveform call (0 when that call ran none) or zvx_resample */
+    ZVX_T_JOIN = 7,                         /* the launches of the last zvx_join / zvx_trim_bounds (bounds, layout, copy) */
     ZVX_T_COUNT = 8
 };
 
@@ -238,6 +239,55 @@ zvx_status zvx_resample_ex(zvx_ctx* ctx, const float* in, const int32_t* nsample
  * resampled as a signal of its own length: no filter tap sees padding or a neighbour.  Every flag keeps its meaning (ZVX_PCM16 rows
  * are clamped as above); ZVX_NATIVE_RATE takes one call out of it. */
 
+/* Long-form output: the B padded rows of a batch, in [B][Nmax] f32 with nsamples[b] valid samples, become ONE contiguous row on the device:
+ * every row trimmed of its leading and trailing silence, faded at the cuts, with gap[b] zeros behind segment b.
+ *     out = segment 0, gap[0] zeros, segment 1, gap[1] zeros, ... segment B-1, gap[B-1] zeros
+ * Bounds of row b (the decisions of zerovox_amd.mels.trim_silence, i.e. of librosa.effects.trim, restated so that they are decidable): with
+ *   n = nsamples[b], pad = frame / 2 zeros on both sides of the n samples and nf = 1 + (n + 2 pad - frame) / hop frames, frame f covers padded
+ *   samples [f hop, f hop + frame);  p[f] = the sum of the squares of its samples ACCUMULATED IN DOUBLE (each f32 sample converted to double
+ *   first; any summation order), pmax = max_f p[f], k = 10^(-top_db / 10) computed once on the host in double (top_db converted to double first):
+ *   frame f is audio when p[f] > pmax * k (a double compare; no log, no sqrt).  With first / last the first and last audio frame:
+ *       begin = max(0, first * hop - keep),   end = min(n, (last + 1) * hop + keep).
+ *   A row is left whole (begin = 0, end = n) when top_db <= 0, when n < frame, or when pmax < 1e-20 * frame (the host function's 1e-10 floor on
+ *   the RMS); n = 0 gives an empty segment.  No audio frame at all (only possible where k rounds to 1): begin = end = 0, as trim_silence hands
+ *   back an empty array.  A frame whose p[f] / (pmax k) lies within 1e-9 of 1 is AMBIGUOUS: either decision is then allowed (the order of
+ *   the double summation is not fixed); everywhere else begin / end are defined exactly.
+ * Segment b has m = end - begin samples and F = min(fade, m / 2).  Sample i of it is x[begin + i] * g(i), ONE f32 multiply, with
+ *       g(i) = (float)(2 i + 1) / (float)(2 F)   for i < F        (one IEEE-correct f32 division: a linear ramp, defined to the bit)
+ *       g(i) = g(m - 1 - i)                      for i >= m - F
+ *   and no multiply at all -- the input's bits -- in between.
+ * Layout (int64, computed on the device): pos[0] = 0, pos[b + 1] = pos[b] + m_b + gap[b]; segment b starts at pos[b]; the gaps are written as
+ *   zeros: the call owns every sample in [0, out_len), the trailing gap included; *out_len = pos[B].  Samples in [out_len, out_capacity) are not
+ *   touched.  out_len > out_capacity: ZVX_E_BUFFER, nothing at all is written, the message names both numbers, the layout outputs are still filled.
+ *   float row, or with ZVX_PCM16 an int16 row by the resampler's rule, (int16) trunc(clamp(v * 32760, -32768, 32767)).
+ *   seg_pos[b] = pos[b], seg_begin[b] = begin, seg_len[b] = m_b (host arrays, each may be NULL).
+ * Syncs: the bounds, the prefix sum over the B segments and the copy all run on the context's main stream without the host in between; the call
+ *   waits ONCE, for the layout (out_len, seg_pos, seg_begin, seg_len) -- a host output row arrives through pinned memory of the context under
+ *   that same wait -- as zvx_synthesize waits once for predicted lengths.  With ZVX_DEVICE_IN the rows may be the ZVX_DEVICE_OUT | ZVX_NO_SYNC
+ *   output of a synthesis call queued just before on the same context: stream order is the only fence needed.
+ * Validation, before anything is queued (ZVX_E_INVALID, the context stays usable): B <= 0, Nmax <= 0, a NULL ctx / in / nsamples / params / out /
+ *   out_len (zvx_trim_bounds: begin / end), frame < 2, hop < 1, hop > frame, keep < 0, fade < 0, a negative gap or length, nsamples[b] > Nmax,
+ *   out_capacity < 0, unknown flags, top_db not finite.
+ * Flags of zvx_join: ZVX_DEVICE_IN (in on the device), ZVX_DEVICE_OUT (out on the device), ZVX_PCM16.  nsamples and gap are host arrays.
+ * Stage slot ZVX_T_JOIN, stage tag "post.join" in zvx_tag_stats: algorithmic bytes = samples read (once for the bounds where top_db > 0, once for
+ *   the copy) + samples written.
+ * Replaces the loop a caller of ZeroVoxTTS.tts writes around it for a paragraph: librosa.effects.trim per sentence, pauses and np.concatenate on
+ * the host (the reference has no long-form entry point, synthesize.py:213-239 is one utterance). */
+typedef struct zvx_join_params {
+    int32_t frame, hop;   /* trim analysis window and step in samples (librosa.effects.trim's 2048 / 512 are the Python defaults) */
+    float   top_db;       /* a frame is audio when its power is within top_db of the row's loudest frame; <= 0: no trimming */
+    int32_t keep;         /* samples kept outside the detected bounds on either side (clamped to the row) */
+    int32_t fade;         /* linear fade-in / fade-out length at every segment edge, samples; 0: none */
+} zvx_join_params;
+
+/* per row: [begin[b], end[b]) = the samples zvx_join would keep (host int32 arrays); fade is not looked at.  flags: ZVX_DEVICE_IN */
+zvx_status zvx_trim_bounds(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_join_params* params,
+                           int32_t* begin, int32_t* end, int flags);
+/* rows in [B][Nmax] f32, nsamples[b] valid -> ONE row of *out_len samples; gap [B], >= 0, NULL = none */
+zvx_status zvx_join(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, const int32_t* gap,
+                    const zvx_join_params* params, void* out, int64_t out_capacity, int64_t* out_len,
+                    int64_t* seg_pos, int32_t* seg_begin, int32_t* seg_len, int flags);
+
 /* Debug/parity taps: copy an intermediate of the last call to host fp32.
  * what: "encoder_out" [B][Tmax][hidden] (after the style add), "features" [B][Lmax][hidden],
  *       "mel" [B][Lmax][n_mels], "pitch_idx"/"energy_idx"/"duration" [B][Tmax] (as float). */
@@ -290,7 +340,7 @@ typedef struct {
 } zvx_kernel_stat;
 int        zvx_kernel_stats(zvx_ctx* ctx, zvx_kernel_stat* out, int max_out);
 /* The same counters grouped by pipeline stage ("encoder", "variance", "lenreg", "decoder", "decoder.norm", "voc.pre",
- * "voc.up1".."voc.res4", "voc.post", "voc.resample", "spkemb"; name = stage): every launch of the stage, including the HBM-bound helper
+ * "voc.up1".."voc.res4", "voc.post", "voc.resample", "post.join", "spkemb"; name = stage): every launch of the stage, including the HBM-bound helper
  * kernels, while "profile" == 2 and "profile_only" == -1.  Feeds the per-stage roofline fractions of bench.py. */
 int        zvx_tag_stats(zvx_ctx* ctx, zvx_kernel_stat* out, int max_out);
 zvx_status zvx_reset_stats(zvx_ctx* ctx);

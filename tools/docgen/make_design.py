@@ -31,6 +31,16 @@ sub = {
     "V3U": ms("v3_unfused"), "V2": ms("v2"), "V3": ms("v3"), "B1T64": ms("b1_t64"),
     "STAGE_ALONE": ", ".join(f"{k} {v:.2f}" for k, v in n1["stage_ms_one_step_alone"].items() if v) + " ms",
 }
+# long-form synthesis (tools/longform_bench.py -> profiles/longform_join.json; not tied to a round)
+try:
+    lf = {r["sentences"]: r for r in json.loads(open(os.path.join(P, "longform_join.json")).read().strip().splitlines()[-1])["paragraphs"]}
+    sub["LONGFORM_README"] = ("paragraphs of 8 / 32 / 128 sentences of 64 phonemes take " + " / ".join(f"{lf[n]['tts_long_ms']:.1f}" for n in (8, 32, 128)) +
+                              " ms against " + " / ".join(f"{lf[n]['loop_tts_trim_concat_ms']:.1f}" for n in (8, 32, 128)) +
+                              " ms for one `tts()` per sentence plus `trim_silence` and `np.concatenate` (same process, one box; HiFi-GAN V1, host waveform out).")
+    sub["LONGFORM_TABLE"] = "\n".join(["| sentences | loop ms | `tts_long` ms | `post.join` ms | MB | of 8 TB/s | vocoder ms |", "|---|---|---|---|---|---|---|"] +
+        [f"| {n} | {r['loop_tts_trim_concat_ms']:.1f} | {r['tts_long_ms']:.1f} | {r['post_join_ms']:.3f} | {r['post_join_bytes'] / 1e6:.0f} | {100 * r['post_join_frac_of_8TBps']:.0f} % | {r['vocoder_ms_last_batch']:.2f} |" for n, r in sorted(lf.items())])
+except Exception:
+    sub["LONGFORM_README"] = sub["LONGFORM_TABLE"] = "n/a"
 names = {"voc.res2": "vocoder stage 2 ResBlocks (C = 128, `pairstream`, bf16)", "voc.res3": "vocoder stage 3 ResBlocks (C = 64, `resstream`)",
          "voc.res1": "vocoder stage 1 ResBlocks (C = 256, conv-slab × 18)", "decoder": "StyleTTS decoder convolutions", "voc.res4": "vocoder stage 4 ResBlocks (C = 32)",
          "encoder": "phoneme encoder (split products on half planes; ≈ 3× issued)", "decoder.norm": "decoder InstanceNorm / AdaIN passes", "variance": "variance adaptor (exact f32)"}
@@ -54,5 +64,6 @@ print("DESIGN.md", len(out.encode()), "bytes")
 rt = open(os.path.join(ROOT, "tools/docgen/readme_numbers.tmpl.md")).read()
 for k in sorted(sub, key=len, reverse=True):
     rt = rt.replace("@" + k + "@", sub[k])
-open(os.path.join(ROOT, "README.md"), "w").write(open(os.path.join(ROOT, "tools/docgen/readme_head.md")).read() + rt)
+rh = open(os.path.join(ROOT, "tools/docgen/readme_head.md")).read().replace("@LONGFORM_README@", sub["LONGFORM_README"])
+open(os.path.join(ROOT, "README.md"), "w").write(rh + rt)
 print("README.md written")

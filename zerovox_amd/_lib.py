@@ -15,6 +15,7 @@ ZVX_E_INVALID, ZVX_E_MANIFEST, ZVX_E_HIP, ZVX_E_STATE, ZVX_E_BUFFER, ZVX_E_UNSUP
 ZVX_DEVICE_OUT, ZVX_NO_SYNC, ZVX_PCM16, ZVX_DEVICE_IN, ZVX_HOST_ASYNC, ZVX_NATIVE_RATE = 1, 2, 4, 8, 16, 32
 STAGES = ("encoder", "variance", "lenreg", "decoder", "vocoder", "spkemb")
 ZVX_T_RESAMPLE = 6                                   # its own accessor (Context.resample_ms): stage_times() keeps exactly STAGES
+ZVX_T_JOIN = 7                                       # likewise (Context.join_ms)
 ZVX_T_COUNT = 8
 
 EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_set_int", "zvx_spkemb", "zvx_melspec", "zvx_encode",
@@ -22,7 +23,7 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_sync", "zvx_stage_times", "zvx_kernel_stats", "zvx_tag_stats", "zvx_reset_stats",
            "zvx_comm_unique_id", "zvx_comm_init", "zvx_comm_gather", "zvx_comm_barrier", "zvx_comm_max_f64", "zvx_comm_info", "zvx_comm_destroy",
            "zvx_dev_alloc", "zvx_dev_free", "zvx_dev_from_host", "zvx_dev_to_host", "zvx_spkemb_ex", "zvx_wait_host",
-           "zvx_encode_ex", "zvx_synthesize_ex", "zvx_resample", "zvx_resample_ex")
+           "zvx_encode_ex", "zvx_synthesize_ex", "zvx_resample", "zvx_resample_ex", "zvx_trim_bounds", "zvx_join")
 ZVX_COMM_ID_BYTES = 128
 
 
@@ -38,6 +39,11 @@ class ZvxError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"zvx error {code}: {msg}")
         self.code = code
+
+
+class JoinParams(C.Structure):
+    """zvx_join_params (include/zvx.h)"""
+    _fields_ = [("frame", C.c_int32), ("hop", C.c_int32), ("top_db", C.c_float), ("keep", C.c_int32), ("fade", C.c_int32)]
 
 
 class KernelStat(C.Structure):
@@ -99,6 +105,8 @@ def load():
     lib.zvx_wait_host.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     lib.zvx_resample.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int64, vp, C.c_int]
     lib.zvx_resample_ex.argtypes = lib.zvx_resample.argtypes + [C.c_int64, C.c_int64, C.c_int64]
+    lib.zvx_trim_bounds.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(JoinParams), vp, vp, C.c_int]
+    lib.zvx_join.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(JoinParams), vp, C.c_int64, C.POINTER(C.c_int64), vp, vp, vp, C.c_int]
     _lib = lib
     return lib
 
@@ -211,6 +219,70 @@ class Context:
                                             ZVX_PCM16 if pcm16 else 0, int(in_origin), int(out_begin), int(out_count)))
         return out[:, :cols], out_len
 
+    @staticmethod
+    def _rows(rows, lengths):
+        """a list of 1-D waveforms, or a padded 2-D array + lengths -> (x [B][Nmax] f32, n [B] i32)"""
+        if lengths is None:
+            B = len(rows)
+            n = np.array([len(w) for w in rows], np.int32)
+            x = np.zeros((B, max(int(n.max()) if B else 0, 1)), np.float32)
+            for b, w in enumerate(rows):
+                x[b, :n[b]] = np.asarray(w, np.float32)
+            return x, n
+        x = _f32(rows)
+        return x, _i32(lengths, (x.shape[0],))
+
+    def trim_bounds(self, rows, frame=2048, hop=512, top_db=40.0, keep=0, lengths=None):
+        """zvx_trim_bounds: per row the samples [begin, end) that join keeps (the decisions of mels.trim_silence, made on the device)
+        -> (begin [B], end [B]) int32.  rows: a list of 1-D float waveforms, or a padded 2-D array + lengths."""
+        x, n = self._rows(rows, lengths)
+        B, Nmax = x.shape
+        prm = JoinParams(int(frame), int(hop), float(top_db), int(keep), 0)
+        begin, end = np.zeros(B, np.int32), np.zeros(B, np.int32)
+        self._chk(self._lib.zvx_trim_bounds(self._h, _ptr(x), _ptr(n), B, Nmax, C.byref(prm), _ptr(begin), _ptr(end), 0))
+        return begin, end
+
+    def join(self, rows, gaps=None, *, frame=2048, hop=512, top_db=40.0, keep=0, fade=0, pcm16=False, lengths=None):
+        """zvx_join on host rows: every row trimmed (top_db <= 0: not), faded over `fade` samples at both cuts and written with gaps[b]
+        zeros behind it into ONE row -> (wav 1-D float32 / int16, seg_pos [B] int64, seg_begin [B], seg_len [B])."""
+        x, n = self._rows(rows, lengths)
+        return self._join(_ptr(x), n, x.shape[1], gaps, frame, hop, top_db, keep, fade, pcm16, 0)
+
+    def join_device(self, ptr, lengths, Nmax, gaps=None, *, frame=2048, hop=512, top_db=40.0, keep=0, fade=0, pcm16=False,
+                    out_device_ptr=None, out_capacity=None):
+        """zvx_join on device rows [B][Nmax] f32 at `ptr` (ZVX_DEVICE_IN; they may be the output of a synthesize(..., no_sync=True) call
+        queued just before: stream order is the fence).  Returns as join(); with out_device_ptr (ZVX_DEVICE_OUT, out_capacity samples)
+        the row stays on the device and (out_len, seg_pos, seg_begin, seg_len) comes back."""
+        n = _i32(lengths)
+        return self._join(C.c_void_p(int(ptr)), n, int(Nmax), gaps, frame, hop, top_db, keep, fade, pcm16, ZVX_DEVICE_IN,
+                          out_device_ptr, out_capacity)
+
+    def _join(self, xptr, n, Nmax, gaps, frame, hop, top_db, keep, fade, pcm16, flags, out_device_ptr=None, out_capacity=None):
+        B = len(n)
+        g = _i32(gaps, (B,)) if gaps is not None else None
+        prm = JoinParams(int(frame), int(hop), float(top_db), int(keep), int(fade))
+        out_len = C.c_int64(0)
+        pos, begin, ln = np.zeros(B, np.int64), np.zeros(B, np.int32), np.zeros(B, np.int32)
+        flags |= ZVX_PCM16 if pcm16 else 0
+        if out_device_ptr is not None:
+            self._chk(self._lib.zvx_join(self._h, xptr, _ptr(n), B, Nmax, _ptr(g), C.byref(prm), C.c_void_p(int(out_device_ptr)), int(out_capacity),
+                                         C.byref(out_len), _ptr(pos), _ptr(begin), _ptr(ln), flags | ZVX_DEVICE_OUT))
+            return int(out_len.value), pos, begin, ln
+        cap = int(n.astype(np.int64).sum()) + (int(g.astype(np.int64).sum()) if g is not None else 0)      # nothing trimmed: the most it can be
+        out = np.empty(max(cap, 1), np.int16 if pcm16 else np.float32)
+        self._chk(self._lib.zvx_join(self._h, xptr, _ptr(n), B, Nmax, _ptr(g), C.byref(prm), _ptr(out), cap, C.byref(out_len), _ptr(pos), _ptr(begin),
+                                     _ptr(ln), flags))
+        return out[:int(out_len.value)], pos, begin, ln
+
+    def resample_device(self, ptr, n, rate_in, rate_out, pcm16=False):
+        """zvx_resample of ONE device-resident row of n f32 samples (ZVX_DEVICE_IN) -> host row at rate_out"""
+        cols = resampled_len(int(n), rate_in, rate_out)
+        out = np.empty(max(cols, 1), np.int16 if pcm16 else np.float32)
+        nn = np.array([int(n)], np.int32)
+        self._chk(self._lib.zvx_resample(self._h, C.c_void_p(int(ptr)), _ptr(nn), 1, max(int(n), 1), int(rate_in), int(rate_out), _ptr(out), max(cols, 1),
+                                         None, ZVX_DEVICE_IN | (ZVX_PCM16 if pcm16 else 0)))
+        return out[:cols]
+
     def _prosody(self, prosody, B, Tmax):
         """-> (struct, keep-alive) for the _ex entry points, or (None, None): the plain ones run."""
         from .prosody import resolve
@@ -287,7 +359,8 @@ class Context:
         return wav
 
     def synthesize(self, phoneme, puncts, T, spk, duration=None, pad_to=None, want_mel=True, Lmax_cap=0,
-                   wav_device_ptr=None, wav_stride=None, no_sync=False, pcm16=False, mel_device_ptr=None, host_async=False, prosody=None):
+                   wav_device_ptr=None, wav_stride=None, no_sync=False, pcm16=False, mel_device_ptr=None, host_async=False, prosody=None,
+                   native_rate=False):
         """Batched phoneme -> waveform.  Returns dict(wav [B][N] (None if device output), mel_len, mel, log_duration).
         host_async: the call only queues work and returns dict(..., slot=s); wait_host(s) hands out the waveform rows in the
         context's pinned host memory (ZVX_HOST_ASYNC: forced durations, no mel / log-duration output).
@@ -295,7 +368,8 @@ class Context:
         mel_device_ptr -> [B][Lmax][n_mels] f32 with Lmax = the longest utterance's forced-duration sum (or Lmax_cap).
         prosody: None, a prosody.Prosody or a dict of Prosody.create keywords (zvx_synthesize_ex); forced durations are then sized
         by the scaled lengths.  Under an output rate (set_int("out_rate", hz)) the waveform rows, wav_stride and wait_host's rows are
-        in samples of that rate: row b carries out_samples(mel_len[b] * hop) of them."""
+        in samples of that rate: row b carries out_samples(mel_len[b] * hop) of them; native_rate=True (ZVX_NATIVE_RATE) takes this
+        call out of it."""
         phoneme = _i32(phoneme)
         B, Tmax = phoneme.shape
         puncts = _i32(puncts, (B, Tmax))
@@ -315,14 +389,14 @@ class Context:
             if want_mel or wav_device_ptr is not None:
                 raise ZvxError(ZVX_E_INVALID, "host_async delivers the waveform only (want_mel=False, no device pointer)")
             args = (self._h, _ptr(phoneme), _ptr(puncts), _ptr(dur), _ptr(T), B, Tmax, _ptr(spk), _ptr(pt), Lmax, None, 0, _ptr(mel_len),
-                    None, max(Lmax, 1), None, ZVX_HOST_ASYNC | (ZVX_PCM16 if pcm16 else 0))
+                    None, max(Lmax, 1), None, ZVX_HOST_ASYNC | (ZVX_PCM16 if pcm16 else 0) | (ZVX_NATIVE_RATE if native_rate else 0))
             self._chk(self._lib.zvx_synthesize(*args) if ps is None else self._lib.zvx_synthesize_ex(*args, C.byref(ps)))
             return dict(wav=None, mel_len=mel_len, mel=None, log_duration=None, slot=self.get_int("host_slot"))
         # a queued call (device output, no_sync) must not ask for host outputs: a copy into pageable memory would wait for the stream
         logd = None if (wav_device_ptr is not None and no_sync) else np.zeros((B, Tmax), np.float32)
         mel = np.zeros((B, max(Lmax, 1), self.n_mels), np.float32) if (want_mel and wav_device_ptr is None) else None
         mptr = _ptr(mel)
-        flags = ZVX_PCM16 if pcm16 else 0
+        flags = (ZVX_PCM16 if pcm16 else 0) | (ZVX_NATIVE_RATE if native_rate else 0)
         if wav_device_ptr is not None:
             wav, wptr, stride = None, C.c_void_p(int(wav_device_ptr)), int(wav_stride)
             flags |= ZVX_DEVICE_OUT | (ZVX_NO_SYNC if no_sync else 0)
@@ -331,7 +405,7 @@ class Context:
                     raise ZvxError(ZVX_E_INVALID, "a device waveform output takes a device mel output (mel_device_ptr) or want_mel=False")
                 mptr = C.c_void_p(int(mel_device_ptr))
         else:
-            stride = max(self.out_samples(Lmax * self.hop), 1)
+            stride = max(self.out_samples(Lmax * self.hop, native_rate), 1)
             wav = np.zeros((B, stride), np.int16 if pcm16 else np.float32)
             wptr = _ptr(wav)
         args = (self._h, _ptr(phoneme), _ptr(puncts), _ptr(dur), _ptr(T), B, Tmax, _ptr(spk), _ptr(pt), Lmax, wptr, stride, _ptr(mel_len),
@@ -368,6 +442,12 @@ class Context:
         ms = np.zeros(ZVX_T_COUNT, np.float32)
         self._chk(self._lib.zvx_stage_times(self._h, _ptr(ms)))
         return float(ms[ZVX_T_RESAMPLE])
+
+    def join_ms(self):
+        """hipEvent time of the launches of the last join() / join_device() / trim_bounds() (profile >= 1)"""
+        ms = np.zeros(ZVX_T_COUNT, np.float32)
+        self._chk(self._lib.zvx_stage_times(self._h, _ptr(ms)))
+        return float(ms[ZVX_T_JOIN])
 
     def kernel_stats(self):
         arr = (KernelStat * 32)()

@@ -1410,4 +1410,196 @@ bool launch_resample_poly(const ResampleArgs& a, hipStream_t s) {
     return true;
 }
 
+// ---------------------------------------------------------------- trim-and-join of waveform rows (zvx_kernels.h, include/zvx.h: zvx_join)
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+constexpr int JOIN_UNITS_PER_WAVE = 2;       // k_join_powers: 4 waves x 2 units per workgroup
+// One wave per unit.  The unit's samples [lo, hi) of the row are walked in groups of 4 that are 16-byte aligned as ADDRESSES (the row may
+// start anywhere: odd Nmax, an offset pointer): a group wholly inside [lo, hi) is one float4 load, a group that straddles an end is read
+// sample by sample.
+__global__ __launch_bounds__(256) void k_join_powers(const JoinBoundsArgs a) {
+    const int b = blockIdx.y, wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int n = a.nsamples[b];
+    if (n < a.frame) return;
+    const int pad = a.frame / 2;
+    const long nf = 1 + ((long)n + 2 * pad - a.frame) / a.hop;
+    const long units = a.tiled ? nf - 1 + a.frame / a.hop : nf;
+    const int ulen = a.tiled ? a.hop : a.frame;
+    const float* xrow = a.x + (long)b * a.x_bs;
+    const int mis = (int)(((size_t)xrow >> 2) & 3);          // xrow - mis is 16-byte aligned
+    for (int j = 0; j < JOIN_UNITS_PER_WAVE; j++) {
+        const long q = ((long)blockIdx.x * 4 + wave) * JOIN_UNITS_PER_WAVE + j;
+        if (q >= units) return;                               // (uniform over the wave)
+        long lo = q * a.hop - pad, hi = lo + ulen;
+        if (lo < 0) lo = 0;
+        if (hi > n) hi = n;
+        double acc = 0.0;
+        if (lo < hi) {
+            const long g1 = (hi + mis + 3) >> 2;
+            for (long g = ((lo + mis) >> 2) + lane; g < g1; g += 64) {
+                const long i = 4 * g - mis;
+                if (i >= lo && i + 4 <= hi) {
+                    const float4 t = *(const float4*)(xrow + i);
+                    acc += (double)t.x * (double)t.x + (double)t.y * (double)t.y + (double)t.z * (double)t.z + (double)t.w * (double)t.w;
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; e++)
+                        if (i + e >= lo && i + e < hi) { const double v = (double)xrow[i + e]; acc += v * v; }
+                }
+            }
+        }
+        acc = wave_sum_f64(acc);
+        if (lane == 0) a.unit[(long)b * a.upitch + q] = acc;
+    }
+}
+void launch_join_powers(const JoinBoundsArgs& a, long units_max, hipStream_t s) {
+    if (a.B <= 0 || units_max <= 0 || !a.trim) return;
+    const long per = 4 * JOIN_UNITS_PER_WAVE;
+    hipLaunchKernelGGL(k_join_powers, dim3((unsigned)((units_max + per - 1) / per), a.B), dim3(256), 0, s, a);
+}
+
+// One workgroup per row.  Pass 1: pmax over the nf frame powers; pass 2: first / last frame above pmax * k.  A frame's power is the sum of
+// its units in ascending order, the same in both passes.
+__global__ __launch_bounds__(256) void k_join_bounds(const JoinBoundsArgs a) {
+    __shared__ double red_d[4];
+    __shared__ long red_lo[4], red_hi[4];
+    const int b = blockIdx.x, tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int n = a.nsamples[b];
+    int begin = 0, end = n;
+    if (a.trim && n >= a.frame) {                            // (uniform over the workgroup)
+        const int pad = a.frame / 2, r = a.tiled ? a.frame / a.hop : 1;
+        const long nf = 1 + ((long)n + 2 * pad - a.frame) / a.hop;
+        const double* u = a.unit + (long)b * a.upitch;
+        auto power = [&](long f) { double p = u[f]; for (int j = 1; j < r; j++) p += u[f + j]; return p; };
+        double pm = 0.0;
+        for (long f = tid; f < nf; f += 256) pm = fmax(pm, power(f));
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) pm = fmax(pm, __shfl_xor(pm, o, 64));
+        if (lane == 0) red_d[wave] = pm;
+        __syncthreads();
+        const double pmax = fmax(fmax(red_d[0], red_d[1]), fmax(red_d[2], red_d[3]));
+        if (!(pmax < a.floor)) {
+            const double thr = pmax * a.k;
+            long first = nf, last = -1;
+            for (long f = tid; f < nf; f += 256)
+                if (power(f) > thr) { if (f < first) first = f; last = f; }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const long of = __shfl_xor(first, o, 64), ol = __shfl_xor(last, o, 64);
+                first = of < first ? of : first; last = ol > last ? ol : last;
+            }
+            if (lane == 0) { red_lo[wave] = first; red_hi[wave] = last; }
+            __syncthreads();
+            for (int w = 0; w < 4; w++) { first = red_lo[w] < first ? red_lo[w] : first; last = red_hi[w] > last ? red_hi[w] : last; }
+            if (last < 0) { begin = 0; end = 0; }
+            else {
+                const long bb = first * a.hop - a.keep, ee = (last + 1) * a.hop + a.keep;
+                begin = (int)(bb < 0 ? 0 : bb); end = (int)(ee > n ? n : ee);
+            }
+        }
+    }
+    if (tid == 0) { a.bounds[2 * b] = begin; a.bounds[2 * b + 1] = end; }
+}
+void launch_join_bounds(const JoinBoundsArgs& a, hipStream_t s) {
+    if (a.B <= 0) return;
+    hipLaunchKernelGGL(k_join_bounds, dim3(a.B), dim3(256), 0, s, a);
+}
+
+// pos: an inclusive scan of len[b] + gap[b] in chunks of 256 (shuffle scan per wave, the four wave totals through LDS, a running carry)
+__global__ __launch_bounds__(256) void k_join_layout(const int* bounds, const int* gap, int B, long* pos, int* seg_begin, int* seg_len) {
+    __shared__ long wsum[4];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    long carry = 0;
+    if (tid == 0) pos[0] = 0;
+    for (int b0 = 0; b0 < B; b0 += 256) {
+        const int b = b0 + tid;
+        long v = 0;
+        if (b < B) {
+            const int bg = bounds[2 * b], m = bounds[2 * b + 1] - bg;
+            seg_begin[b] = bg; seg_len[b] = m;
+            v = (long)m + (gap ? gap[b] : 0);
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const long t = __shfl_up(v, o, 64); if (lane >= o) v += t; }
+        __syncthreads();                                      // the previous chunk's readers of wsum are done
+        if (lane == 63) wsum[wave] = v;
+        __syncthreads();
+        long base = carry;
+        for (int w = 0; w < wave; w++) base += wsum[w];
+        if (b < B) pos[b + 1] = base + v;
+        carry += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    }
+}
+void launch_join_layout(const int* bounds, const int* gap, int B, long* pos, int* seg_begin, int* seg_len, hipStream_t s) {
+    if (B <= 0) return;
+    hipLaunchKernelGGL(k_join_layout, dim3(1), dim3(256), 0, s, bounds, gap, B, pos, seg_begin, seg_len);
+}
+
+constexpr int JOIN_LDS_B = 2047;             // position tables of up to this many segments are searched in LDS, longer ones in global memory
+constexpr int JOIN_TILE = 4096;              // outputs per workgroup: 4 groups of 4 per thread
+__device__ __forceinline__ float join_gain(long i, int F) { return __fdiv_rn((float)(2 * i + 1), (float)(2 * (long)F)); }
+__device__ __forceinline__ short join_pcm(float v) { return (short)fminf(fmaxf(v * 32760.0f, -32768.0f), 32767.0f); }   // clamp, then truncate
+// Output groups of 4 are aligned as ADDRESSES of the destination (v = o + omis): a group wholly inside [0, pos[B]) is one vector store.  A
+// group wholly inside the untouched middle of one segment is one float4 load when the source address allows, else 4 scalar loads; every other
+// group (a fade, a segment edge, a gap, the ends of the row) is built sample by sample.
+__global__ __launch_bounds__(256) void k_join_copy(const JoinCopyArgs a) {
+    __shared__ long tab[JOIN_LDS_B + 1];
+    const int tid = threadIdx.x;
+    const bool in_lds = a.B <= JOIN_LDS_B;
+    if (in_lds) for (int i = tid; i <= a.B; i += 256) tab[i] = a.pos[i];
+    __syncthreads();
+    const long* pos = in_lds ? tab : a.pos;
+    const long total = pos[a.B];
+    if (total > a.cap) return;
+    const int omis = a.pcm16 ? (int)(((size_t)a.out >> 1) & 3) : (int)(((size_t)a.out >> 2) & 3);
+    const long v0 = (long)blockIdx.x * JOIN_TILE;
+    for (long v = v0 + 4 * tid; v < v0 + JOIN_TILE; v += 1024) {
+        const long o = v - omis;
+        if (o >= total) break;
+        const long oo = o < 0 ? 0 : o;
+        int s = 0, hi = a.B;                                  // the last s with pos[s] <= oo (pos[s + 1] > oo then holds: pos[B] = total > oo)
+        while (hi - s > 1) { const int mid = (s + hi) >> 1; if (pos[mid] <= oo) s = mid; else hi = mid; }
+        float r[4] = {0.f, 0.f, 0.f, 0.f};
+        const bool whole = o >= 0 && o + 4 <= total;
+        const long rel = o - pos[s];
+        int m = a.seg_len[s], F = a.fade < m / 2 ? a.fade : m / 2;
+        if (whole && rel >= F && rel + 4 <= (long)m - F) {
+            const float* src = a.x + (long)s * a.x_bs + a.seg_begin[s] + rel;
+            if (((size_t)src & 15) == 0) { const float4 t = *(const float4*)src; r[0] = t.x; r[1] = t.y; r[2] = t.z; r[3] = t.w; }
+            else { r[0] = src[0]; r[1] = src[1]; r[2] = src[2]; r[3] = src[3]; }
+        } else {
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const long oe = o + e;
+                if (oe < 0 || oe >= total) continue;
+                while (oe >= pos[s + 1]) s++;
+                const long i = oe - pos[s];
+                m = a.seg_len[s];
+                if (i < m) {
+                    F = a.fade < m / 2 ? a.fade : m / 2;
+                    const float x = a.x[(long)s * a.x_bs + a.seg_begin[s] + i];
+                    r[e] = i < F ? x * join_gain(i, F) : (i >= (long)m - F ? x * join_gain(m - 1 - i, F) : x);
+                }
+            }
+        }
+        if (whole) {
+            if (a.pcm16) { short4 q; q.x = join_pcm(r[0]); q.y = join_pcm(r[1]); q.z = join_pcm(r[2]); q.w = join_pcm(r[3]); *(short4*)((short*)a.out + o) = q; }
+            else *(float4*)((float*)a.out + o) = make_float4(r[0], r[1], r[2], r[3]);
+        } else {
+            for (int e = 0; e < 4; e++) {
+                if (o + e < 0 || o + e >= total) continue;
+                if (a.pcm16) ((short*)a.out)[o + e] = join_pcm(r[e]); else ((float*)a.out)[o + e] = r[e];
+            }
+        }
+    }
+}
+void launch_join_copy(const JoinCopyArgs& a, long upper, hipStream_t s) {
+    if (a.B <= 0 || upper <= 0) return;
+    const long tiles = (upper + 3 + JOIN_TILE - 1) / JOIN_TILE;        // (+ 3: the address alignment shifts the groups by up to 3 outputs)
+    hipLaunchKernelGGL(k_join_copy, dim3((unsigned)tiles), dim3(256), 0, s, a);
+}
+
 }  // namespace zvx

@@ -155,6 +155,18 @@ struct zvx_ctx {
     int out_rate = 0;
     struct RsBank { int L = 0, M = 0, half = 0, T = 0, pitch = 0; const float* dev = nullptr; };
     std::map<std::pair<int, int>, RsBank> rs_banks;
+    // zvx_join / zvx_trim_bounds: pinned host memory the layout words (and a host output row) land in under the call's one wait
+    void* join_host = nullptr;
+    size_t join_host_cap = 0;
+    void* join_pinned(size_t bytes) {
+        if (bytes > join_host_cap) {
+            if (join_host) { HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipHostFree(join_host)); join_host = nullptr; join_host_cap = 0; }
+            const size_t cap = bytes + bytes / 8 + 256;
+            HIPCHK(hipHostMalloc(&join_host, cap, hipHostMallocDefault));
+            join_host_cap = cap;
+        }
+        return join_host;
+    }
     hipEvent_t stage_ev[ZVX_T_COUNT][2];
     bool stage_used[ZVX_T_COUNT];
     float stage_ms[ZVX_T_COUNT];
@@ -2065,6 +2077,130 @@ void do_resample(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, in
     if (!((flags & ZVX_DEVICE_OUT) && (flags & ZVX_NO_SYNC))) c->sync();
 }
 
+// ------------------------------------------------------------------------------------------------
+// trim-and-join of a batch's waveform rows (include/zvx.h: zvx_join, zvx_trim_bounds)
+// ------------------------------------------------------------------------------------------------
+constexpr int JOIN_MAX_UNITS_PER_FRAME = 32;   // hop-block sums serve frames of up to this many blocks; longer ratios take the per-frame path
+
+void join_check(const char* who, const void* in, const int32_t* nsamples, int B, int Nmax, const int32_t* gap, const zvx_join_params* p) {
+    if (!in || !nsamples || !p || B <= 0 || Nmax <= 0) fail(ZVX_E_INVALID, "%s: bad arguments (NULL pointer, B = %d, Nmax = %d)", who, B, Nmax);
+    if (p->frame < 2 || p->hop < 1 || p->hop > p->frame) fail(ZVX_E_INVALID, "%s: frame %d / hop %d (frame >= 2, 1 <= hop <= frame)", who, p->frame, p->hop);
+    if (p->keep < 0 || p->fade < 0) fail(ZVX_E_INVALID, "%s: keep %d / fade %d must not be negative", who, p->keep, p->fade);
+    if (!std::isfinite(p->top_db)) fail(ZVX_E_INVALID, "%s: top_db is not finite", who);
+    for (int b = 0; b < B; b++) {
+        if (nsamples[b] < 0 || nsamples[b] > Nmax) fail(ZVX_E_INVALID, "%s: nsamples[%d]=%d out of range (0..%d)", who, b, nsamples[b], Nmax);
+        if (gap && gap[b] < 0) fail(ZVX_E_INVALID, "%s: gap[%d]=%d is negative", who, b, gap[b]);
+    }
+}
+
+// queues the frame-power and bounds launches; "join.bounds" then holds {begin, end} per row.  Returns the device rows and the samples read.
+const float* join_bounds(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_join_params* p, int flags, double* read) {
+    const float* x_dev = in;
+    if (!(flags & ZVX_DEVICE_IN)) {
+        float* xd = c->fbuf("join.in", (size_t)B * Nmax);
+        HIPCHK(hipMemcpyAsync(xd, in, (size_t)B * Nmax * 4, hipMemcpyHostToDevice, c->stream));
+        x_dev = xd;
+    }
+    JoinBoundsArgs a{};
+    a.x = x_dev; a.x_bs = Nmax; a.nsamples = c->upload_ints("join.len", nsamples, B); a.B = B;
+    a.frame = p->frame; a.hop = p->hop; a.keep = p->keep;
+    a.tiled = (p->frame % p->hop == 0 && p->frame / p->hop <= JOIN_MAX_UNITS_PER_FRAME) ? 1 : 0;
+    a.trim = p->top_db > 0.f ? 1 : 0;
+    a.k = pow(10.0, -(double)p->top_db / 10.0); a.floor = 1e-20 * (double)p->frame;
+    long units_max = 0; double nin = 0;
+    for (int b = 0; b < B; b++) {
+        if (nsamples[b] < p->frame) continue;
+        const long nf = 1 + ((long)nsamples[b] + 2 * (p->frame / 2) - p->frame) / p->hop;
+        units_max = std::max(units_max, a.tiled ? nf - 1 + p->frame / p->hop : nf);
+        nin += nsamples[b];
+    }
+    a.upitch = units_max;
+    a.unit = a.trim && units_max > 0 ? (double*)c->buf("join.unit", (size_t)B * units_max * sizeof(double)) : nullptr;
+    a.bounds = c->ibuf("join.bounds", (size_t)2 * B);
+    launch_join_powers(a, units_max, c->stream);
+    launch_join_bounds(a, c->stream);
+    *read = a.trim ? nin : 0.0;
+    return x_dev;
+}
+
+// the launches of one call as ONE timed group under "post.join"; its byte count is only known after the call's wait
+struct JoinTimer {
+    zvx_ctx* c; GemmEvent ev{}; bool prof; std::string keep;
+    explicit JoinTimer(zvx_ctx* c_) : c(c_), prof(c_->profile >= 2 && c_->profile_only < 0), keep(c_->tag) {
+        c->tag = "post.join";
+        c->stage_begin(ZVX_T_JOIN);
+        if (prof) { ev.a = c->new_event(); ev.b = c->new_event(); HIPCHK(hipEventRecord(ev.a, c->stream)); }
+    }
+    ~JoinTimer() { c->tag = keep; }
+    void stop() { if (prof) HIPCHK(hipEventRecord(ev.b, c->stream)); c->stage_end(ZVX_T_JOIN); c->tag = keep; }
+    void commit(double bytes) { if (prof) { ev.variant = -1; ev.flops = 0; ev.bytes = bytes; ev.tag = "post.join"; c->pending.push_back(ev); prof = false; } }
+};
+
+void do_trim_bounds(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_join_params* p, int32_t* begin, int32_t* end, int flags) {
+    join_check("zvx_trim_bounds", in, nsamples, B, Nmax, nullptr, p);
+    if (!begin || !end) fail(ZVX_E_INVALID, "zvx_trim_bounds: NULL output");
+    if (flags & ~ZVX_DEVICE_IN) fail(ZVX_E_INVALID, "zvx_trim_bounds: unknown flag in %d", flags);
+    int* host = (int*)c->join_pinned((size_t)2 * B * sizeof(int));
+    JoinTimer t(c);
+    double read = 0;
+    join_bounds(c, in, nsamples, B, Nmax, p, flags, &read);
+    t.stop();
+    HIPCHK(hipMemcpyAsync(host, c->ibuf("join.bounds", 0), (size_t)2 * B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));
+    for (int b = 0; b < B; b++) { begin[b] = host[2 * b]; end[b] = host[2 * b + 1]; }
+    t.commit(read * 4.0);
+    c->sync();
+}
+
+void do_join(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const int32_t* gap, const zvx_join_params* p, void* out,
+             int64_t out_capacity, int64_t* out_len, int64_t* seg_pos, int32_t* seg_begin, int32_t* seg_len, int flags) {
+    join_check("zvx_join", in, nsamples, B, Nmax, gap, p);
+    if (!out || !out_len || out_capacity < 0) fail(ZVX_E_INVALID, "zvx_join: bad output arguments");
+    if (flags & ~(ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_PCM16)) fail(ZVX_E_INVALID, "zvx_join: unknown flag in %d", flags);
+    const int pcm16 = (flags & ZVX_PCM16) ? 1 : 0;
+    const size_t ss = pcm16 ? 2 : 4;
+    long upper = 0;                                          // what the row can hold at most: nothing trimmed
+    for (int b = 0; b < B; b++) upper += (long)nsamples[b] + (gap ? gap[b] : 0);
+    // layout words in one block: pos [B + 1] int64, then seg_begin [B], seg_len [B]
+    const size_t lay_bytes = (size_t)(B + 1) * 8 + (size_t)B * 8;
+    const bool host_out = !(flags & ZVX_DEVICE_OUT);
+    const long stage = std::min<long>(upper, out_capacity);  // a host row is staged: at most this much can be delivered
+    const size_t lay_pad = (lay_bytes + 255) & ~(size_t)255;
+    char* host = (char*)c->join_pinned(lay_pad + (host_out ? (size_t)stage * ss : 0));
+    char* lay = (char*)c->buf("join.layout", lay_bytes);
+    long* pos_d = (long*)lay; int* begin_d = (int*)(lay + (size_t)(B + 1) * 8); int* len_d = begin_d + B;
+    const int* gap_d = gap ? c->upload_ints("join.gap", gap, B) : nullptr;
+    void* odev = host_out ? c->buf("join.out", (size_t)std::max(stage, 1L) * ss + 16) : out;
+    JoinTimer t(c);
+    double read = 0;
+    const float* x_dev = join_bounds(c, in, nsamples, B, Nmax, p, flags, &read);
+    launch_join_layout(c->ibuf("join.bounds", 0), gap_d, B, pos_d, begin_d, len_d, c->stream);
+    JoinCopyArgs a{};
+    a.x = x_dev; a.x_bs = Nmax; a.B = B; a.pos = pos_d; a.seg_begin = begin_d; a.seg_len = len_d;
+    a.out = odev; a.cap = out_capacity; a.pcm16 = pcm16; a.fade = p->fade;
+    launch_join_copy(a, upper, c->stream);
+    t.stop();
+    HIPCHK(hipMemcpyAsync(host, lay, lay_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (host_out && stage > 0) HIPCHK(hipMemcpyAsync(host + lay_pad, odev, (size_t)stage * ss, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                 // the call's one wait
+    const int64_t* pos_h = (const int64_t*)host;
+    const int32_t* begin_h = (const int32_t*)(host + (size_t)(B + 1) * 8); const int32_t* len_h = begin_h + B;
+    const int64_t total = pos_h[B];
+    *out_len = total;
+    double kept = 0;
+    for (int b = 0; b < B; b++) {
+        if (seg_pos) seg_pos[b] = pos_h[b];
+        if (seg_begin) seg_begin[b] = begin_h[b];
+        if (seg_len) seg_len[b] = len_h[b];
+        kept += len_h[b];
+    }
+    const bool fits = total <= out_capacity;
+    t.commit(read * 4.0 + (fits ? kept * 4.0 + (double)total * ss : 0.0));
+    c->sync();
+    if (!fits) fail(ZVX_E_BUFFER, "zvx_join: the joined row has %lld samples, out_capacity is %lld", (long long)total, (long long)out_capacity);
+    if (host_out && total > 0) memcpy(out, host + lay_pad, (size_t)total * ss);
+}
+
 // wav: float rows, or int16 PCM rows with ZVX_PCM16 (stride counted in samples either way).  Row b receives
 // mel_len[b]*hop samples followed by zeros up to max_b(mel_len[b])*hop; nothing beyond that is touched.
 void do_vocode(zvx_ctx* c, const int32_t* pad_to, void* wav, int64_t wav_stride, int flags) {
@@ -2212,6 +2348,7 @@ void zvx_destroy(zvx_ctx* c) {
     for (int i = 0; i < 2; i++) { if (c->arena[i].p) (void)hipHostFree(c->arena[i].p); if (c->arena[i].ev) (void)hipEventDestroy(c->arena[i].ev); }
     if (c->copy_stream && !c->copy_is_comm) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
     for (auto& hs : c->host_slot) { if (hs.p) (void)hipHostFree(hs.p); if (hs.ready) (void)hipEventDestroy(hs.ready); if (hs.done) (void)hipEventDestroy(hs.done); }
+    if (c->join_host) (void)hipHostFree(c->join_host);
     for (int i = 0; i < 2; i++) if (c->voc_aux[i]) { (void)hipStreamSynchronize(c->voc_aux[i]); (void)hipStreamDestroy(c->voc_aux[i]); }
     for (int i = 0; i < 3; i++) if (c->voc_ev[i]) (void)hipEventDestroy(c->voc_ev[i]);
     if (c->aux_stream) { (void)hipStreamSynchronize(c->aux_stream); (void)hipStreamDestroy(c->aux_stream); (void)hipEventDestroy(c->ev_aux[0]); (void)hipEventDestroy(c->ev_aux[1]); }
@@ -2421,6 +2558,16 @@ zvx_status zvx_resample(zvx_ctx* c, const float* in, const int32_t* nsamples, in
 zvx_status zvx_resample_ex(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate_in, int rate_out, void* out,
                            int64_t out_stride, int32_t* out_len, int flags, int64_t in_origin, int64_t out_begin, int64_t out_count) {
     return guarded(c, [&] { do_resample(c, in, nsamples, B, Nmax, rate_in, rate_out, out, out_stride, out_len, flags, in_origin, out_begin, out_count); });
+}
+
+zvx_status zvx_trim_bounds(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_join_params* params, int32_t* begin,
+                           int32_t* end, int flags) {
+    return guarded(c, [&] { do_trim_bounds(c, in, nsamples, B, Nmax, params, begin, end, flags); });
+}
+
+zvx_status zvx_join(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const int32_t* gap, const zvx_join_params* params,
+                    void* out, int64_t out_capacity, int64_t* out_len, int64_t* seg_pos, int32_t* seg_begin, int32_t* seg_len, int flags) {
+    return guarded(c, [&] { do_join(c, in, nsamples, B, Nmax, gap, params, out, out_capacity, out_len, seg_pos, seg_begin, seg_len, flags); });
 }
 
 zvx_status zvx_synthesize(zvx_ctx* c, const int32_t* phoneme, const int32_t* puncts, const int32_t* duration, const int32_t* T,

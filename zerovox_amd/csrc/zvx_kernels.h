@@ -348,6 +348,36 @@ struct ResampleArgs {
 };
 // false (nothing launched) when the bank and one tile's input span exceed the LDS of a workgroup
 bool launch_resample_poly(const ResampleArgs& a, hipStream_t s);
+// Trim-and-join of a batch's waveform rows (include/zvx.h, zvx_join): three launches, every length and position read on the DEVICE.
+// Frame powers.  In padded coordinates (pad = frame / 2 zeros in front of the row) frame f of row b covers [f hop, f hop + frame).  With
+// `tiled` (hop divides frame) unit q is the hop-block [q hop, (q + 1) hop) and a frame is the sum of frame / hop neighbouring units, so the
+// row is read once; otherwise unit q is frame q itself.  unit[b][q] (pitch upitch doubles) = the sum of the squares of the unit's samples
+// inside [0, nsamples[b]), each f32 converted to double first; one wave per unit, 16-byte loads wherever the ADDRESS allows, a shuffle
+// reduction in double -- no atomics.  Rows with nsamples[b] < frame are skipped (left whole by launch_join_bounds).
+struct JoinBoundsArgs {
+    const float* x; long x_bs; const int* nsamples; int B;
+    int frame, hop, tiled;                   // tiled: frame % hop == 0 and a frame is few enough units
+    double* unit; long upitch;
+    double k, floor;                         // k = 10^(-top_db / 10), floor = 1e-20 * frame
+    int trim, keep;                          // trim 0: every row whole, `unit` is not read
+    int* bounds;                             // [B][2] = begin, end
+};
+void launch_join_powers(const JoinBoundsArgs& a, long units_max, hipStream_t s);
+// pmax, first / last audio frame and bounds[b] = {begin, end} of every row: one workgroup per row over its nf frame powers (two passes in a
+// fixed order: the result does not depend on scheduling)
+void launch_join_bounds(const JoinBoundsArgs& a, hipStream_t s);
+// One workgroup: pos[0] = 0, pos[b + 1] = pos[b] + (end - begin) + gap[b] in int64 (gap may be NULL), seg_begin[b], seg_len[b]
+void launch_join_layout(const int* bounds, const int* gap, int B, long* pos, int* seg_begin, int* seg_len, hipStream_t s);
+// The copy: out[pos[b] + i] = x[b][seg_begin[b] + i] * g(i) for i < seg_len[b] (g: the linear ramp of include/zvx.h over the F = min(fade,
+// len / 2) edge samples, no multiply in between), zeros in the gaps, for every output index below pos[B]; NOTHING is written when pos[B] >
+// cap.  The grid covers `upper` >= pos[B] outputs (the host's bound: it does not know pos[B]).  out: f32, or int16 with pcm16.  16-byte
+// loads / stores where source and destination addresses allow, scalar at segment edges; vector stores only.
+struct JoinCopyArgs {
+    const float* x; long x_bs; int B;
+    const long* pos; const int* seg_begin; const int* seg_len;
+    void* out; long cap; int pcm16, fade;
+};
+void launch_join_copy(const JoinCopyArgs& a, long upper, hipStream_t s);
 // half-mode saturation audit: *count += number of elements of x[b][r < rows[b]][0:C] (16-bit, batch stride bs, row stride ld) whose
 // magnitude bits are >= 0x7BFF (+-65504 = a clamped store, or Inf / NaN)
 void launch_count_sat16(const void* x, long bs, int ld, int B, int rows_max, const int* rows, int C, unsigned long long* count, hipStream_t s);

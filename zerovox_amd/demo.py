@@ -2,8 +2,12 @@
 same RTF definition (audio seconds / synthesis seconds), same warm-up rule (iterations i <= 10 discarded), same prints.
 
     python -m zerovox_amd.demo --model synthetic:styletts --meldec-model synthetic:v1 --iter 30 "hello world, this is a test."
+
+`--long`: the text (or, where the argument names a file, the file's contents) is a paragraph: ZeroVoxTTS.tts_long synthesises it
+sentence by sentence in batches and joins the sentences on the device; --wav-filename receives the joined waveform.
 """
 import argparse
+import os
 import time
 
 import numpy as np
@@ -27,6 +31,7 @@ def main():
     ap.add_argument("--energy-shift", type=float, default=0.0)
     ap.add_argument("--energy-range", type=float, default=1.0)
     ap.add_argument("--out-rate", type=int, default=0, help="output sampling rate in Hz, converted on the device (0: the model's rate)")
+    ap.add_argument("--long", action="store_true", help="long-form: split the text (or the file it names) into sentences and join them on the device")
     args = ap.parse_args()
 
     modelcfg, synth = ZeroVoxTTS.load_model(args.model, args.meldec_model, infer_device=args.infer_device, precision=args.precision)
@@ -37,8 +42,20 @@ def main():
     refmel = np.random.default_rng(0).standard_normal((args.refmel_frames, modelcfg["audio"]["num_mels"])).astype(np.float32)
     spkemb = synth.speaker_embed_from_mel(refmel)
     rtf, warmup = [], 10
+    text = open(args.text, encoding="utf-8").read() if (args.long and os.path.isfile(args.text)) else args.text
     for i in range(args.iter):
         t0 = time.time()
+        if args.long:
+            wav, segments = synth.tts_long(text, spkemb, speed=args.speed, pitch_shift=args.pitch_shift, pitch_range=args.pitch_range,
+                                           energy_shift=args.energy_shift, energy_range=args.energy_range)
+            elapsed = time.time() - t0
+            wav_len = (wav.shape[0] if segments else 0) / sr
+            print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, {len(segments)} sentences, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")
+            if args.wav_filename and segments:
+                write_wav_to_file(wav, length=0, filename=args.wav_filename, sample_rate=sr, hop_length=modelcfg["audio"]["hop_size"], samples=len(wav))
+            if i > warmup:
+                rtf.append(wav_len / elapsed)
+            continue
         wav, phoneme, length = synth.tts(args.text, spkemb, speed=args.speed, pitch_shift=args.pitch_shift, pitch_range=args.pitch_range,
                                          energy_shift=args.energy_shift, energy_range=args.energy_range)
         elapsed = time.time() - t0

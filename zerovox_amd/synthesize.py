@@ -185,6 +185,24 @@ class ZeroVoxTTS:
         mel = ctx.decode(1, ml)[0, :ml]
         yield from self._model.vocode_stream(mel, chunk_frames=chunk_frames, chunks_per_call=chunks_per_call)
 
+    def tts_long(self, text: str, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20, fade_ms=5, max_batch=32, max_frames=2048, pcm16=False,
+                 durations=None, max_chars=200, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0):
+        """A paragraph -> (wav, segments): one waveform with every sentence in text order (not in the reference).  The text is split by
+        longform.split_sentences; the sentences run in batches of at most max_batch, each batch ONE queued synthesize call into
+        consecutive rows of one device buffer (every row is the fresh-model ``tts`` of its sentence; a sentence of more than max_frames
+        mel frames is an error); then ONE zvx_join trims each row's silence (trim_db, as librosa.effects.trim's top_db; <= 0: off;
+        keep_ms kept around the cut, fade_ms of linear fade at both cuts) and writes the rows with the pauses between them on the
+        device; under an ``output_rate`` the joined row is converted by one zvx_resample.  pauses: ms by closing class, default
+        longform.PAUSES_MS ('.' 350, ';' 250, ',' 120, ' ' 0; nothing behind the last sentence).  The prosody keywords apply to every
+        sentence; durations: None or one list of per-phoneme frame counts per sentence, forced as tts_ex(duration=...) does.
+        wav: float32, or int16 with pcm16.  segments: one dict per sentence -- text, start / samples (its place in wav, in output
+        samples), mel_len, trim (samples cut in front, at the model's rate) and durations (the per-phoneme frame counts as
+        synthesised): what subtitles or lip-sync need.  Empty or phone-less text: the reference's sentinel waveform and []."""
+        from .longform import synthesize_long
+        return synthesize_long(self, text, spkemb, pauses=pauses, trim_db=trim_db, keep_ms=keep_ms, fade_ms=fade_ms, max_batch=max_batch,
+                               max_frames=max_frames, pcm16=pcm16, durations=durations, max_chars=max_chars,
+                               prosody=self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range))
+
     @property
     def output_rate(self):
         """sampling rate of the waveforms tts / tts_ex / tts_stream hand back (default: the model's); set it to have them converted
