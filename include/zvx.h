@@ -288,6 +288,62 @@ zvx_status zvx_join(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int 
                     const zvx_join_params* params, void* out, int64_t out_capacity, int64_t* out_len,
                     int64_t* seg_pos, int32_t* seg_begin, int32_t* seg_len, int flags);
 
+/* Loudness: the integrated loudness (ITU-R BS.1770-4 / EBU R128, mono) and the sample peak of every row of a batch, in [B][Nmax] f32 with
+ * nsamples[b] valid samples at `rate` Hz, measured on the device; zvx_normalize also applies the gain that brings a row (or the whole batch
+ * as one programme) to a target.  Nothing is normalised unless one of these two is called.  Every decision is made in the power domain, in
+ * double, so that it is decidable the way the trim bounds are.
+ * K-weighting, fs = rate, coefficients designed on the host in double and cached per rate:
+ *   stage 1, high shelf: f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196, K = tan(pi f0 / fs), Vh = 10^(G / 20),
+ *       Vb = Vh^0.4996667741545416, a0 = 1 + K / Q + K^2;  b = [(Vh + Vb K / Q + K^2) / a0, 2 (K^2 - Vh) / a0, (Vh - Vb K / Q + K^2) / a0],
+ *       a1 = 2 (K^2 - 1) / a0, a2 = (1 - K / Q + K^2) / a0;
+ *   stage 2, high pass: f0 = 38.13547087602444, Q = 0.5003270373238773;  b = [1, -2, 1], a1 = 2 (K^2 - 1) / (1 + K / Q + K^2),
+ *       a2 = (1 - K / Q + K^2) / (1 + K / Q + K^2)
+ *   (at 48 kHz the table of BS.1770-4: 1.53512486, -2.69169619, 1.19839281 / -1.69065929, 0.73248077 / -1.99004745, 0.99007225).
+ *   Each stage is a transposed direct form II in DOUBLE on the f32 samples converted to double:  y = b0 x + s1;  s1 = b1 x - a1 y + s2;
+ *   s2 = b2 x - a2 y;  stage 1 feeds stage 2; the state is zero at sample 0 of the row (the signal is zero before it).
+ * Units, blocks, gates: h = (fs + 5) / 10 samples (integer: 100 ms), U = n / h whole units (a shorter tail is not measured), u[q] = the
+ *   double sum of y^2 over samples [q h, (q + 1) h); block j = 0 .. U - 4 has z[j] = (u[j] + u[j + 1] + u[j + 2] + u[j + 3]) / (4 h).
+ *   Absolute gate: z[j] > 10^((-70 + 0.691) / 10) (computed once on the host in double); Gamma = the mean of z over the blocks that pass it;
+ *   relative gate: z[j] > 0.1 Gamma (-10 LU is exactly a factor 0.1 in power);  L = -0.691 + 10 log10(mean of z over the blocks that pass
+ *   both).  No block (n < 4 h) or none above the absolute gate: L = -INFINITY.  peak = max |x[i]| over the n samples, exact.
+ *   A block whose z lies within a relative 2.3e-4 (1e-3 LU) of either threshold is AMBIGUOUS: either decision is allowed there; L is otherwise
+ *   defined to within 1e-7 LU of the sequential double recurrence.  (An implementation may start a unit's recurrence from zero state some
+ *   way before the unit instead of carrying state, provided it stays within that figure: this one starts two units, 0.2 s, early, which
+ *   leaves 1e-12 dB.)
+ * Gain, in double on the device, rounded once to f32: g = 10^((target - L) / 20); g = min(g, 10^(max_gain_db / 20)); then, if peak_ceiling > 0
+ *   and peak g > peak_ceiling, g = peak_ceiling / peak.  L = -INFINITY or peak = 0: g = 1.  Output sample i is x[i] * g, ONE f32 multiply;
+ *   with ZVX_PCM16 the resampler's rule follows, (int16) trunc(clamp(v * 32760, -32768, 32767)).
+ *   ZVX_LOUD_COMMON: both gates run over the union of all rows' blocks (blocks never span two rows), peak is the maximum over the rows, ONE g
+ *   is computed and gain[b] = g for every row; lufs[b] / peak[b] still report the per-row values.
+ * Syncs: measurement, gates, gain and multiply run on the context's main stream without the host in between; the call waits once, for the
+ *   host outputs.  With ZVX_DEVICE_OUT | ZVX_NO_SYNC and lufs == peak == gain == NULL zvx_normalize only queues.  With ZVX_DEVICE_IN the rows
+ *   may be the output of a synthesis call queued just before on the same context: stream order is the fence, as for zvx_join.
+ * Validation, before anything is queued (ZVX_E_INVALID, the context stays usable): a NULL ctx / in / nsamples (zvx_normalize: params / out),
+ *   B <= 0, Nmax <= 0, a negative length, nsamples[b] > Nmax, rate outside [4000, 192000], out_stride < Nmax, unknown flags, ZVX_NO_SYNC
+ *   without ZVX_DEVICE_OUT, ZVX_PCM16 with out == in, out == in with another stride or on another side than in, target_lufs not finite or
+ *   outside [-70, 0], max_gain_db not finite or negative, peak_ceiling NaN, an unknown mode.  More than 65535 rows: ZVX_E_UNSUPPORTED.
+ * Stage tag "post.loudness" in zvx_tag_stats (one timed group per call; no stage slot): algorithmic bytes = 4 sum(n) for the measurement;
+ *   zvx_normalize adds 4 sum(n) read and the bytes written.
+ * Replaces a host-side meter and gain (pyloudnorm and the like) behind ZeroVoxTTS.tts; the reference hands its waveform back at whatever
+ * level the model gives (synthesize.py:213-239).  Not here: true-peak metering, limiting, momentary / short-term loudness, several channels. */
+enum { ZVX_LOUD_PER_ROW = 0, ZVX_LOUD_COMMON = 1 };
+typedef struct zvx_loudness_params {
+    float   target_lufs;   /* integrated loudness to reach, finite, in [-70, 0] */
+    float   peak_ceiling;  /* linear sample-peak ceiling after the gain (0.891 = -1 dBFS); <= 0: none */
+    float   max_gain_db;   /* upper bound on the gain in dB, finite, >= 0 (keeps a near-silent row from being blown up) */
+    int32_t mode;          /* PER_ROW: each row its own gain; COMMON: one gain from all rows measured as one programme */
+} zvx_loudness_params;
+
+/* measure: lufs[B] (double; -INFINITY where undefined), peak[B] (float) -- host arrays, either may be NULL.  flags: ZVX_DEVICE_IN */
+zvx_status zvx_loudness(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, int rate,
+                        double* lufs, float* peak, int flags);
+/* measure + gain: row b of out receives nsamples[b] samples x[i] * gain[b]; nothing else is touched.  out_stride samples between rows;
+ * out == in (same stride) is allowed for float rows: in place.  lufs / peak / gain: host arrays, each may be NULL.
+ * flags: ZVX_DEVICE_IN, ZVX_DEVICE_OUT, ZVX_NO_SYNC (device out only), ZVX_PCM16 (not in place) */
+zvx_status zvx_normalize(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, int rate,
+                         const zvx_loudness_params* params, void* out, int64_t out_stride,
+                         double* lufs, float* peak, float* gain, int flags);
+
 /* Debug/parity taps: copy an intermediate of the last call to host fp32.
  * what: "encoder_out" [B][Tmax][hidden] (after the style add), "features" [B][Lmax][hidden],
  *       "mel" [B][Lmax][n_mels], "pitch_idx"/"energy_idx"/"duration" [B][Tmax] (as float). */
@@ -340,7 +396,7 @@ typedef struct {
 } zvx_kernel_stat;
 int        zvx_kernel_stats(zvx_ctx* ctx, zvx_kernel_stat* out, int max_out);
 /* The same counters grouped by pipeline stage ("encoder", "variance", "lenreg", "decoder", "decoder.norm", "voc.pre",
- * "voc.up1".."voc.res4", "voc.post", "voc.resample", "post.join", "spkemb"; name = stage): every launch of the stage, including the HBM-bound helper
+ * "voc.up1".."voc.res4", "voc.post", "voc.resample", "post.join", "post.loudness", "spkemb"; name = stage): every launch of the stage, including the HBM-bound helper
  * kernels, while "profile" == 2 and "profile_only" == -1.  Feeds the per-stage roofline fractions of bench.py. */
 int        zvx_tag_stats(zvx_ctx* ctx, zvx_kernel_stat* out, int max_out);
 zvx_status zvx_reset_stats(zvx_ctx* ctx);

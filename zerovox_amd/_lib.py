@@ -23,8 +23,10 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_sync", "zvx_stage_times", "zvx_kernel_stats", "zvx_tag_stats", "zvx_reset_stats",
            "zvx_comm_unique_id", "zvx_comm_init", "zvx_comm_gather", "zvx_comm_barrier", "zvx_comm_max_f64", "zvx_comm_info", "zvx_comm_destroy",
            "zvx_dev_alloc", "zvx_dev_free", "zvx_dev_from_host", "zvx_dev_to_host", "zvx_spkemb_ex", "zvx_wait_host",
-           "zvx_encode_ex", "zvx_synthesize_ex", "zvx_resample", "zvx_resample_ex", "zvx_trim_bounds", "zvx_join")
+           "zvx_encode_ex", "zvx_synthesize_ex", "zvx_resample", "zvx_resample_ex", "zvx_trim_bounds", "zvx_join",
+           "zvx_loudness", "zvx_normalize")
 ZVX_COMM_ID_BYTES = 128
+ZVX_LOUD_PER_ROW, ZVX_LOUD_COMMON = 0, 1
 
 
 def resampled_len(n, rate_in, rate_out):
@@ -44,6 +46,11 @@ class ZvxError(RuntimeError):
 class JoinParams(C.Structure):
     """zvx_join_params (include/zvx.h)"""
     _fields_ = [("frame", C.c_int32), ("hop", C.c_int32), ("top_db", C.c_float), ("keep", C.c_int32), ("fade", C.c_int32)]
+
+
+class LoudnessParams(C.Structure):
+    """zvx_loudness_params (include/zvx.h)"""
+    _fields_ = [("target_lufs", C.c_float), ("peak_ceiling", C.c_float), ("max_gain_db", C.c_float), ("mode", C.c_int32)]
 
 
 class KernelStat(C.Structure):
@@ -107,6 +114,8 @@ def load():
     lib.zvx_resample_ex.argtypes = lib.zvx_resample.argtypes + [C.c_int64, C.c_int64, C.c_int64]
     lib.zvx_trim_bounds.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(JoinParams), vp, vp, C.c_int]
     lib.zvx_join.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(JoinParams), vp, C.c_int64, C.POINTER(C.c_int64), vp, vp, vp, C.c_int]
+    lib.zvx_loudness.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int]
+    lib.zvx_normalize.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(LoudnessParams), vp, C.c_int64, vp, vp, vp, C.c_int]
     _lib = lib
     return lib
 
@@ -274,6 +283,47 @@ class Context:
                                      _ptr(ln), flags))
         return out[:int(out_len.value)], pos, begin, ln
 
+    def _rate(self, rate):
+        return self.get_int("sampling_rate") if rate is None else int(rate)
+
+    def loudness(self, rows, rate=None, lengths=None):
+        """zvx_loudness: integrated loudness (BS.1770 / R128, LUFS; -inf where undefined) and sample peak of every row -> (lufs [B] float64,
+        peak [B] float32).  rows: a list of 1-D float waveforms, or a padded 2-D array + lengths; rate None: the model's sampling rate."""
+        x, n = self._rows(rows, lengths)
+        B, Nmax = x.shape
+        lufs, peak = np.zeros(B, np.float64), np.zeros(B, np.float32)
+        self._chk(self._lib.zvx_loudness(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), _ptr(lufs), _ptr(peak), 0))
+        return lufs, peak
+
+    def normalize(self, rows, target, *, peak_ceiling=0.891, max_gain_db=20.0, common=False, pcm16=False, rate=None, lengths=None):
+        """zvx_normalize on host rows: every row (common: all rows as one programme, one gain) brought to `target` LUFS, the gain bounded by
+        max_gain_db and by the linear sample-peak ceiling (<= 0: none) -> (rows_out [B][Nmax] float32 / int16 -- row b holds its samples
+        times gain[b], then zeros --, lufs [B] float64, peak [B], gain [B] float32)."""
+        x, n = self._rows(rows, lengths)
+        B, Nmax = x.shape
+        prm = LoudnessParams(float(target), float(peak_ceiling), float(max_gain_db), ZVX_LOUD_COMMON if common else ZVX_LOUD_PER_ROW)
+        out = np.zeros((B, Nmax), np.int16 if pcm16 else np.float32)
+        lufs, peak, gain = np.zeros(B, np.float64), np.zeros(B, np.float32), np.zeros(B, np.float32)
+        self._chk(self._lib.zvx_normalize(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), Nmax, _ptr(lufs), _ptr(peak),
+                                          _ptr(gain), ZVX_PCM16 if pcm16 else 0))
+        return out, lufs, peak, gain
+
+    def normalize_device(self, ptr, lengths, Nmax, target, *, peak_ceiling=0.891, max_gain_db=20.0, common=False, rate=None, no_sync=False):
+        """zvx_normalize IN PLACE on device rows [B][Nmax] f32 at `ptr` (they may be the output of a synthesize(..., no_sync=True) call queued
+        just before: stream order is the fence) -> (lufs, peak, gain); with no_sync the call only queues and returns None."""
+        n = _i32(lengths)
+        B = len(n)
+        prm = LoudnessParams(float(target), float(peak_ceiling), float(max_gain_db), ZVX_LOUD_COMMON if common else ZVX_LOUD_PER_ROW)
+        p = C.c_void_p(int(ptr))
+        if no_sync:
+            self._chk(self._lib.zvx_normalize(self._h, p, _ptr(n), B, int(Nmax), self._rate(rate), C.byref(prm), p, int(Nmax), None, None, None,
+                                              ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC))
+            return None
+        lufs, peak, gain = np.zeros(B, np.float64), np.zeros(B, np.float32), np.zeros(B, np.float32)
+        self._chk(self._lib.zvx_normalize(self._h, p, _ptr(n), B, int(Nmax), self._rate(rate), C.byref(prm), p, int(Nmax), _ptr(lufs), _ptr(peak),
+                                          _ptr(gain), ZVX_DEVICE_IN | ZVX_DEVICE_OUT))
+        return lufs, peak, gain
+
     def resample_device(self, ptr, n, rate_in, rate_out, pcm16=False):
         """zvx_resample of ONE device-resident row of n f32 samples (ZVX_DEVICE_IN) -> host row at rate_out"""
         cols = resampled_len(int(n), rate_in, rate_out)
@@ -338,6 +388,13 @@ class Context:
         pt = _i32(pad_to, (B,)) if pad_to is not None else None
         self._chk(self._lib.zvx_vocode(self._h, _ptr(pt), _ptr(wav), n, (ZVX_PCM16 if pcm16 else 0) | (ZVX_NATIVE_RATE if native_rate else 0)))
         return wav
+
+    def vocode_device(self, mel_len, pad_to, wav_ptr, wav_stride, native_rate=False, no_sync=False):
+        """zvx_vocode into device rows [B][wav_stride] f32 at wav_ptr (ZVX_DEVICE_OUT); with no_sync the call only queues"""
+        B = len(mel_len)
+        pt = _i32(pad_to, (B,)) if pad_to is not None else None
+        self._chk(self._lib.zvx_vocode(self._h, _ptr(pt), C.c_void_p(int(wav_ptr)), int(wav_stride),
+                                       ZVX_DEVICE_OUT | (ZVX_NO_SYNC if no_sync else 0) | (ZVX_NATIVE_RATE if native_rate else 0)))
 
     def vocode_mel(self, mel, P, pcm16=False, host_async=False, native_rate=False):
         """host_async: the call only queues work and returns the pinned host slot (wait_host(slot) hands out the rows).

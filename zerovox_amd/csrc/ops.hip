@@ -1602,4 +1602,211 @@ void launch_join_copy(const JoinCopyArgs& a, long upper, hipStream_t s) {
     hipLaunchKernelGGL(k_join_copy, dim3((unsigned)tiles), dim3(256), 0, s, a);
 }
 
+// ---------------------------------------------------------------- integrated loudness and gain (zvx_kernels.h, include/zvx.h: zvx_loudness)
+constexpr int LOUD_T = 32;                   // samples per lane in one staged chunk
+constexpr int LOUD_G = LOUD_T / 4 + 1;       // 16-byte groups that cover LOUD_T samples whatever their alignment
+constexpr int LOUD_LD = 4 * LOUD_G + 1;      // LDS floats per lane: odd, so that the 64 lanes' reads of one step fall on distinct banks
+// The recurrence is a dependent chain of double FMAs per sample, so the parallelism is (row, unit): lane l of workgroup (blk, b) owns unit
+// q = 64 blk + l of row b and walks samples [(q - 2) h, (q + 1) h) from zero state -- two units of warm-up, samples in front of the row are
+// the zeros the definition puts there -- summing y^2 over the last h of them.  A lane's samples are h floats from its neighbour's: per chunk
+// of LOUD_T steps the wave loads the 64 spans as 16-byte groups aligned as ADDRESSES (a group that straddles an end of the row is read
+// sample by sample, nothing outside [0, n) is read), next chunk's loads in flight under this chunk's arithmetic, and the lanes walk LDS.
+__global__ __launch_bounds__(64) void k_loud_units(const LoudArgs a) {
+    __shared__ float st[64 * LOUD_LD];
+    const int b = blockIdx.y, lane = threadIdx.x;
+    const int n = a.nsamples[b], h = a.h;
+    const long U = n / h, q0 = (long)blockIdx.x * 64, q = q0 + lane;
+    const float* xrow = a.x + (long)b * a.x_bs;
+    const int mis = (int)(((size_t)xrow >> 2) & 3);          // xrow - mis is 16-byte aligned
+    float pk = 0.f;
+    if (q0 < U) {                                            // (uniform over the workgroup)
+        const int nact = (int)(U - q0 < 64 ? U - q0 : 64);
+        const bool active = lane < nact;
+        const long steps = 3L * h, nchunks = (steps + LOUD_T - 1) / LOUD_T;
+        const int off = (int)(((q - 2) * h + mis) & 3);      // where the lane's span begins inside its first group (LOUD_T % 4 == 0: in every chunk)
+        float4 r[LOUD_G];
+        auto fetch = [&](long c) {
+#pragma unroll
+            for (int k = 0; k < LOUD_G; k++) {
+                const int item = k * 64 + lane, seg = item / LOUD_G, g = item - seg * LOUD_G;
+                float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+                if (seg < nact) {
+                    const long sp = (q0 + seg - 2) * h + c * LOUD_T;
+                    const long pg = sp - ((sp + mis) & 3) + 4 * g;
+                    if (pg >= 0 && pg + 4 <= n) v = *(const float4*)(xrow + pg);
+                    else {
+                        if (pg >= 0 && pg < n) v.x = xrow[pg];
+                        if (pg + 1 >= 0 && pg + 1 < n) v.y = xrow[pg + 1];
+                        if (pg + 2 >= 0 && pg + 2 < n) v.z = xrow[pg + 2];
+                        if (pg + 3 >= 0 && pg + 3 < n) v.w = xrow[pg + 3];
+                    }
+                }
+                r[k] = v;
+            }
+        };
+        const LoudCoef k = a.k;
+        double s1 = 0.0, s2 = 0.0, r1 = 0.0, r2 = 0.0, acc = 0.0;
+        fetch(0);
+        for (long c = 0; c < nchunks; c++) {
+#pragma unroll
+            for (int kk = 0; kk < LOUD_G; kk++) {
+                const int item = kk * 64 + lane, seg = item / LOUD_G, g = item - seg * LOUD_G;
+                float* d = st + seg * LOUD_LD + 4 * g;
+                d[0] = r[kk].x; d[1] = r[kk].y; d[2] = r[kk].z; d[3] = r[kk].w;
+            }
+            __syncthreads();
+            if (c + 1 < nchunks) fetch(c + 1);
+            if (active) {
+                const float* my = st + lane * LOUD_LD + off;
+                const long t0 = c * LOUD_T;
+#pragma unroll 8
+                for (int t = 0; t < LOUD_T; t++) {
+                    const float xf = my[t];
+                    const double x = (double)xf;
+                    const double y1 = fma(k.b0, x, s1);
+                    s1 = fma(-k.a1, y1, fma(k.b1, x, s2));
+                    s2 = fma(-k.a2, y1, k.b2 * x);
+                    const double y2 = y1 + r1;
+                    r1 = fma(-k.c1, y2, fma(-2.0, y1, r2));
+                    r2 = fma(-k.c2, y2, y1);
+                    if (t0 + t >= 2L * h && t0 + t < steps) { acc = fma(y2, y2, acc); pk = fmaxf(pk, fabsf(xf)); }
+                }
+            }
+            __syncthreads();
+        }
+        if (active) a.unit[(long)b * a.upitch + q] = acc;
+    }
+    if (blockIdx.x == 0)                                     // the tail behind the last whole unit counts for the peak only
+        for (long i = U * h + lane; i < n; i += 64) pk = fmaxf(pk, fabsf(xrow[i]));
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) pk = fmaxf(pk, __shfl_xor(pk, o, 64));
+    if (lane == 0) a.part_peak[(long)b * a.ppitch + blockIdx.x] = pk;
+}
+void launch_loud_units(const LoudArgs& a, long units_max, hipStream_t s) {
+    if (a.B <= 0) return;
+    hipLaunchKernelGGL(k_loud_units, dim3((unsigned)a.ppitch, a.B), dim3(64), 0, s, a);
+    (void)units_max;
+}
+
+// sum over the workgroup's 256 threads in a fixed order (shuffle tree per wave, the four wave sums through LDS)
+__device__ __forceinline__ double wg_sum_f64(double v, double* red) {
+    v = wave_sum_f64(v);
+    __syncthreads();                                          // the previous sum's readers are done
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+__device__ __forceinline__ double loud_block(const double* u, long j, double four_h) { return (((u[j] + u[j + 1]) + u[j + 2]) + u[j + 3]) / four_h; }
+__device__ __forceinline__ double loud_lufs(double sum, double cnt) { return cnt > 0.0 ? -0.691 + 10.0 * log10(sum / cnt) : -INFINITY; }
+__device__ double loud_gain(double L, double peak, const LoudArgs& a) {
+    if (!(L > -INFINITY) || !(peak > 0.0)) return 1.0;
+    double g = pow(10.0, (a.target - L) / 20.0);
+    g = fmin(g, pow(10.0, a.max_gain_db / 20.0));
+    if (a.ceiling > 0.0 && peak * g > a.ceiling) g = a.ceiling / peak;
+    return g;
+}
+// One workgroup per row.  Pass 1: sum and count of the blocks above the absolute gate; pass 2: of those also above a tenth of their mean.
+__global__ __launch_bounds__(256) void k_loud_gates(const LoudArgs a) {
+    __shared__ double red[4];
+    __shared__ float redp[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n = a.nsamples[b];
+    const long U = n / a.h, nb = U >= 4 ? U - 3 : 0;
+    const double* u = a.unit + (long)b * a.upitch;
+    const double four_h = 4.0 * (double)a.h;
+    float pk = 0.f;
+    for (int i = tid; i < a.ppitch; i += 256) pk = fmaxf(pk, a.part_peak[(long)b * a.ppitch + i]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) pk = fmaxf(pk, __shfl_xor(pk, o, 64));
+    if ((tid & 63) == 0) redp[tid >> 6] = pk;
+    double s = 0.0, cnt = 0.0;
+    for (long j = tid; j < nb; j += 256) { const double z = loud_block(u, j, four_h); if (z > a.abs_gate) { s += z; cnt += 1.0; } }
+    const double S1 = wg_sum_f64(s, red), C1 = wg_sum_f64(cnt, red);
+    pk = fmaxf(fmaxf(redp[0], redp[1]), fmaxf(redp[2], redp[3]));
+    double L = -INFINITY;
+    if (C1 > 0.0) {                                          // (uniform over the workgroup)
+        const double thr = 0.1 * (S1 / C1);
+        s = 0.0; cnt = 0.0;
+        for (long j = tid; j < nb; j += 256) { const double z = loud_block(u, j, four_h); if (z > a.abs_gate && z > thr) { s += z; cnt += 1.0; } }
+        const double S2 = wg_sum_f64(s, red), C2 = wg_sum_f64(cnt, red);
+        L = loud_lufs(S2, C2);
+    }
+    if (tid == 0) {
+        a.lufs[b] = L; a.peak[b] = pk; a.row_sum[b] = S1; a.row_cnt[b] = (long)C1;
+        a.gain[b] = a.want_gain ? (float)loud_gain(L, (double)pk, a) : 1.0f;
+    }
+}
+void launch_loud_gates(const LoudArgs& a, hipStream_t s) {
+    if (a.B <= 0) return;
+    hipLaunchKernelGGL(k_loud_gates, dim3(a.B), dim3(256), 0, s, a);
+}
+// One workgroup over all rows: the rows measured as one programme (blocks never span two rows).
+__global__ __launch_bounds__(256) void k_loud_common(const LoudArgs a) {
+    __shared__ double red[4];
+    const int tid = threadIdx.x;
+    double s = 0.0, cnt = 0.0, pk = 0.0;
+    for (int b = tid; b < a.B; b += 256) { s += a.row_sum[b]; cnt += (double)a.row_cnt[b]; pk = fmax(pk, (double)a.peak[b]); }
+    const double S1 = wg_sum_f64(s, red), C1 = wg_sum_f64(cnt, red);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) pk = fmax(pk, __shfl_xor(pk, o, 64));
+    __syncthreads();
+    if ((tid & 63) == 0) red[tid >> 6] = pk;
+    __syncthreads();
+    pk = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+    double L = -INFINITY;
+    if (C1 > 0.0) {
+        const double thr = 0.1 * (S1 / C1), four_h = 4.0 * (double)a.h;
+        s = 0.0; cnt = 0.0;
+        for (int b = 0; b < a.B; b++) {
+            const long U = a.nsamples[b] / a.h, nb = U >= 4 ? U - 3 : 0;
+            const double* u = a.unit + (long)b * a.upitch;
+            for (long j = tid; j < nb; j += 256) { const double z = loud_block(u, j, four_h); if (z > a.abs_gate && z > thr) { s += z; cnt += 1.0; } }
+        }
+        const double S2 = wg_sum_f64(s, red), C2 = wg_sum_f64(cnt, red);
+        L = loud_lufs(S2, C2);
+    }
+    const float g = (float)loud_gain(L, pk, a);
+    for (int b = tid; b < a.B; b += 256) a.gain[b] = g;
+}
+void launch_loud_common(const LoudArgs& a, hipStream_t s) {
+    if (a.B <= 0) return;
+    hipLaunchKernelGGL(k_loud_common, dim3(1), dim3(256), 0, s, a);
+}
+
+constexpr int LOUD_TILE = 4096;              // samples per workgroup: 4 groups of 4 per thread
+__global__ __launch_bounds__(256) void k_loud_apply(const LoudApplyArgs a) {
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int n = a.nsamples[b];
+    const float g = a.gain[b];
+    const float* x = a.x + (long)b * a.x_bs;
+    float* of = (float*)a.out + (long)b * a.out_bs;
+    short* os = (short*)a.out + (long)b * a.out_bs;
+    const int omis = a.pcm16 ? (int)(((size_t)os >> 1) & 3) : (int)(((size_t)of >> 2) & 3);
+    const long v0 = (long)blockIdx.x * LOUD_TILE;
+    for (long v = v0 + 4 * tid; v < v0 + LOUD_TILE; v += 1024) {
+        const long o = v - omis;
+        if (o >= n) break;
+        if (o >= 0 && o + 4 <= n) {
+            const float* src = x + o;
+            float4 t;
+            if (((size_t)src & 15) == 0) t = *(const float4*)src;
+            else { t.x = src[0]; t.y = src[1]; t.z = src[2]; t.w = src[3]; }
+            t.x *= g; t.y *= g; t.z *= g; t.w *= g;
+            if (a.pcm16) { short4 q; q.x = join_pcm(t.x); q.y = join_pcm(t.y); q.z = join_pcm(t.z); q.w = join_pcm(t.w); *(short4*)(os + o) = q; }
+            else *(float4*)(of + o) = t;
+        } else {
+            for (int e = 0; e < 4; e++) {
+                if (o + e < 0 || o + e >= n) continue;
+                const float r = x[o + e] * g;
+                if (a.pcm16) os[o + e] = join_pcm(r); else of[o + e] = r;
+            }
+        }
+    }
+}
+void launch_loud_apply(const LoudApplyArgs& a, long n_max, hipStream_t s) {
+    if (a.B <= 0 || n_max <= 0) return;
+    const long tiles = (n_max + 3 + LOUD_TILE - 1) / LOUD_TILE;        // (+ 3: the address alignment shifts the groups by up to 3 samples)
+    hipLaunchKernelGGL(k_loud_apply, dim3((unsigned)tiles, a.B), dim3(256), 0, s, a);
+}
+
 }  // namespace zvx

@@ -155,7 +155,9 @@ struct zvx_ctx {
     int out_rate = 0;
     struct RsBank { int L = 0, M = 0, half = 0, T = 0, pitch = 0; const float* dev = nullptr; };
     std::map<std::pair<int, int>, RsBank> rs_banks;
-    // zvx_join / zvx_trim_bounds: pinned host memory the layout words (and a host output row) land in under the call's one wait
+    std::map<int, LoudCoef> loud_coefs;    // zvx_loudness / zvx_normalize: the K-weighting biquads, designed in double, per sampling rate
+    // zvx_join / zvx_trim_bounds / zvx_loudness / zvx_normalize: pinned host memory the layout or result words (and host output rows) land
+    // in under the call's one wait
     void* join_host = nullptr;
     size_t join_host_cap = 0;
     void* join_pinned(size_t bytes) {
@@ -2201,6 +2203,113 @@ void do_join(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nm
     if (host_out && total > 0) memcpy(out, host + lay_pad, (size_t)total * ss);
 }
 
+// ------------------------------------------------------------------------------------------------
+// integrated loudness and gain of a batch's waveform rows (include/zvx.h: zvx_loudness, zvx_normalize)
+// ------------------------------------------------------------------------------------------------
+const LoudCoef& loud_coef(zvx_ctx* c, int rate) {
+    auto it = c->loud_coefs.find(rate);
+    if (it != c->loud_coefs.end()) return it->second;
+    const double pi = 3.14159265358979323846, fs = (double)rate;
+    LoudCoef k{};
+    {   // stage 1: high shelf
+        const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
+        const double K = tan(pi * f0 / fs), Vh = pow(10.0, G / 20.0), Vb = pow(Vh, 0.4996667741545416), a0 = 1.0 + K / Q + K * K;
+        k.b0 = (Vh + Vb * K / Q + K * K) / a0; k.b1 = 2.0 * (K * K - Vh) / a0; k.b2 = (Vh - Vb * K / Q + K * K) / a0;
+        k.a1 = 2.0 * (K * K - 1.0) / a0; k.a2 = (1.0 - K / Q + K * K) / a0;
+    }
+    {   // stage 2: high pass, b = [1, -2, 1]
+        const double f0 = 38.13547087602444, Q = 0.5003270373238773;
+        const double K = tan(pi * f0 / fs), a0 = 1.0 + K / Q + K * K;
+        k.c1 = 2.0 * (K * K - 1.0) / a0; k.c2 = (1.0 - K / Q + K * K) / a0;
+    }
+    return c->loud_coefs[rate] = k;
+}
+
+// zvx_loudness (p == nullptr: measure only) and zvx_normalize
+void do_loudness(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_loudness_params* p,
+                 void* out, int64_t out_stride, double* lufs, float* peak, float* gain, int flags) {
+    const bool norm = p != nullptr;
+    if (!in || !nsamples || B <= 0 || Nmax <= 0) fail(ZVX_E_INVALID, "%s: bad arguments (NULL pointer, B = %d, Nmax = %d)", who, B, Nmax);
+    if (B > 65535) fail(ZVX_E_UNSUPPORTED, "%s: B = %d rows (at most 65535 per call)", who, B);
+    if (rate < 4000 || rate > 192000) fail(ZVX_E_INVALID, "%s: rate %d outside [4000, 192000]", who, rate);
+    if (flags & ~(norm ? (ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16) : ZVX_DEVICE_IN)) fail(ZVX_E_INVALID, "%s: unknown flag in %d", who, flags);
+    const int pcm16 = (flags & ZVX_PCM16) ? 1 : 0;
+    if (norm) {
+        if (!out) fail(ZVX_E_INVALID, "%s: out is NULL", who);
+        if (out_stride < Nmax) fail(ZVX_E_INVALID, "%s: out_stride %lld is smaller than Nmax %d", who, (long long)out_stride, Nmax);
+        if ((flags & ZVX_NO_SYNC) && !(flags & ZVX_DEVICE_OUT)) fail(ZVX_E_INVALID, "%s: ZVX_NO_SYNC needs ZVX_DEVICE_OUT", who);
+        if (out == (const void*)in && pcm16) fail(ZVX_E_INVALID, "%s: ZVX_PCM16 cannot run in place", who);
+        if (out == (const void*)in && (out_stride != Nmax || !(flags & ZVX_DEVICE_IN) != !(flags & ZVX_DEVICE_OUT)))
+            fail(ZVX_E_INVALID, "%s: in place needs out_stride == Nmax and both pointers on the same side", who);
+        if (!std::isfinite(p->target_lufs) || p->target_lufs < -70.f || p->target_lufs > 0.f) fail(ZVX_E_INVALID, "%s: target_lufs must lie in [-70, 0]", who);
+        if (!std::isfinite(p->max_gain_db) || p->max_gain_db < 0.f) fail(ZVX_E_INVALID, "%s: max_gain_db must be finite and not negative", who);
+        if (std::isnan(p->peak_ceiling)) fail(ZVX_E_INVALID, "%s: peak_ceiling is NaN", who);
+        if (p->mode != ZVX_LOUD_PER_ROW && p->mode != ZVX_LOUD_COMMON) fail(ZVX_E_INVALID, "%s: unknown mode %d", who, p->mode);
+    }
+    long n_max = 0; double n_sum = 0;
+    for (int b = 0; b < B; b++) {
+        if (nsamples[b] < 0 || nsamples[b] > Nmax) fail(ZVX_E_INVALID, "%s: nsamples[%d]=%d out of range (0..%d)", who, b, nsamples[b], Nmax);
+        n_max = std::max<long>(n_max, nsamples[b]); n_sum += nsamples[b];
+    }
+    const size_t ss = pcm16 ? 2 : 4;
+    const bool host_out = norm && !(flags & ZVX_DEVICE_OUT);
+    const bool want_host = lufs || peak || gain;
+    // result words in one block: lufs [B] double, then peak [B], gain [B] float; a host output row set is staged behind them
+    const size_t res_bytes = (size_t)B * 16, res_pad = (res_bytes + 255) & ~(size_t)255;
+    const long ostage = (n_max + 7) & ~7L;                    // row stride of the staged host output
+    char* host = (want_host || host_out) ? (char*)c->join_pinned(res_pad + (host_out ? (size_t)B * ostage * ss : 0)) : nullptr;
+    LoudArgs a{};
+    a.h = (rate + 5) / 10;
+    a.k = loud_coef(c, rate);
+    const long units_max = std::max(n_max / a.h, 1L);
+    a.upitch = units_max; a.ppitch = (int)((units_max + 63) / 64);
+    const float* x_dev = in;
+    if (!(flags & ZVX_DEVICE_IN)) {
+        float* xd = c->fbuf("loud.in", (size_t)B * Nmax);
+        HIPCHK(hipMemcpyAsync(xd, in, (size_t)B * Nmax * 4, hipMemcpyHostToDevice, c->stream));
+        x_dev = xd;
+    }
+    a.x = x_dev; a.x_bs = Nmax; a.nsamples = c->upload_ints("loud.len", nsamples, B); a.B = B;
+    a.unit = (double*)c->buf("loud.unit", (size_t)B * units_max * sizeof(double));
+    a.part_peak = c->fbuf("loud.ppeak", (size_t)B * a.ppitch);
+    char* res = (char*)c->buf("loud.res", res_bytes + (size_t)B * 16);
+    a.lufs = (double*)res; a.peak = (float*)(res + (size_t)B * 8); a.gain = a.peak + B;
+    a.row_sum = (double*)(res + res_bytes); a.row_cnt = (long*)(res + res_bytes + (size_t)B * 8);
+    a.abs_gate = pow(10.0, (-70.0 + 0.691) / 10.0);
+    a.want_gain = norm ? 1 : 0;
+    if (norm) { a.target = (double)p->target_lufs; a.max_gain_db = (double)p->max_gain_db; a.ceiling = (double)p->peak_ceiling; }
+    void* odev = host_out ? c->buf("loud.out", (size_t)B * ostage * ss + 16) : out;
+    const std::string keep = c->tag;
+    c->tag = "post.loudness";
+    struct Untag { zvx_ctx* c; const std::string& keep; ~Untag() { c->tag = keep; } } untag{c, keep};
+    c->timed(0.0, 4.0 * n_sum + (norm ? (4.0 + (double)ss) * n_sum : 0.0), [&] {
+        launch_loud_units(a, units_max, c->stream);
+        launch_loud_gates(a, c->stream);
+        if (norm && p->mode == ZVX_LOUD_COMMON) launch_loud_common(a, c->stream);
+        if (norm) {
+            LoudApplyArgs w{};
+            w.x = x_dev; w.x_bs = Nmax; w.nsamples = a.nsamples; w.B = B; w.gain = a.gain;
+            w.out = odev; w.out_bs = host_out ? ostage : (long)out_stride; w.pcm16 = pcm16;
+            launch_loud_apply(w, n_max, c->stream);
+        }
+    });
+    if (want_host) HIPCHK(hipMemcpyAsync(host, res, res_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (host_out && n_max > 0) HIPCHK(hipMemcpyAsync(host + res_pad, odev, (size_t)B * ostage * ss, hipMemcpyDeviceToHost, c->stream));
+    if (!want_host && (flags & ZVX_NO_SYNC)) return;         // device output, nothing for the host: the call only queues
+    c->sync();                                               // the call's one wait
+    if (want_host) {
+        const double* l_h = (const double*)host; const float* p_h = (const float*)(host + (size_t)B * 8); const float* g_h = p_h + B;
+        for (int b = 0; b < B; b++) {
+            if (lufs) lufs[b] = l_h[b];
+            if (peak) peak[b] = p_h[b];
+            if (gain) gain[b] = g_h[b];
+        }
+    }
+    if (host_out)
+        for (int b = 0; b < B; b++)
+            if (nsamples[b] > 0) memcpy((char*)out + (size_t)b * out_stride * ss, host + res_pad + (size_t)b * ostage * ss, (size_t)nsamples[b] * ss);
+}
+
 // wav: float rows, or int16 PCM rows with ZVX_PCM16 (stride counted in samples either way).  Row b receives
 // mel_len[b]*hop samples followed by zeros up to max_b(mel_len[b])*hop; nothing beyond that is touched.
 void do_vocode(zvx_ctx* c, const int32_t* pad_to, void* wav, int64_t wav_stride, int flags) {
@@ -2568,6 +2677,18 @@ zvx_status zvx_trim_bounds(zvx_ctx* c, const float* in, const int32_t* nsamples,
 zvx_status zvx_join(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const int32_t* gap, const zvx_join_params* params,
                     void* out, int64_t out_capacity, int64_t* out_len, int64_t* seg_pos, int32_t* seg_begin, int32_t* seg_len, int flags) {
     return guarded(c, [&] { do_join(c, in, nsamples, B, Nmax, gap, params, out, out_capacity, out_len, seg_pos, seg_begin, seg_len, flags); });
+}
+
+zvx_status zvx_loudness(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, double* lufs, float* peak, int flags) {
+    return guarded(c, [&] { do_loudness(c, "zvx_loudness", in, nsamples, B, Nmax, rate, nullptr, nullptr, 0, lufs, peak, nullptr, flags); });
+}
+
+zvx_status zvx_normalize(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_loudness_params* params,
+                         void* out, int64_t out_stride, double* lufs, float* peak, float* gain, int flags) {
+    return guarded(c, [&] {
+        if (!params) fail(ZVX_E_INVALID, "zvx_normalize: params is NULL");
+        do_loudness(c, "zvx_normalize", in, nsamples, B, Nmax, rate, params, out, out_stride, lufs, peak, gain, flags);
+    });
 }
 
 zvx_status zvx_synthesize(zvx_ctx* c, const int32_t* phoneme, const int32_t* puncts, const int32_t* duration, const int32_t* T,

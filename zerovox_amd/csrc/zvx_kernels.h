@@ -378,6 +378,37 @@ struct JoinCopyArgs {
     void* out; long cap; int pcm16, fade;
 };
 void launch_join_copy(const JoinCopyArgs& a, long upper, hipStream_t s);
+// Integrated loudness (ITU-R BS.1770 / EBU R128) and gain of a batch's waveform rows (include/zvx.h, zvx_loudness / zvx_normalize): every
+// decision is made on the DEVICE, in double, in the power domain.
+// K-weighting: two biquads in transposed direct form II, double state.  Stage 1 b0..b2, a1, a2; stage 2 has b = [1, -2, 1].
+struct LoudCoef { double b0, b1, b2, a1, a2, c1, c2; };
+struct LoudArgs {
+    const float* x; long x_bs; const int* nsamples; int B;
+    int h;                                   // samples per 100 ms unit
+    LoudCoef k;
+    double* unit; long upitch;               // unit[b][q]: sum of the squares of the K-weighted samples [q h, (q + 1) h), q < nsamples[b] / h
+    float* part_peak; int ppitch;            // part_peak[b][workgroup of launch_loud_units]: max |x| over what that workgroup looked at
+    double abs_gate;                         // 10^((-70 + 0.691) / 10)
+    double* row_sum; long* row_cnt;          // [B]: sum and count of the row's blocks above the absolute gate (the pooled gate's input)
+    double* lufs; float* peak; float* gain;  // [B] results
+    double target; double max_gain_db; double ceiling;   // ceiling <= 0: none
+    int want_gain;                           // 0: measure only, gain stays 1
+};
+// unit powers and partial peaks: one LANE per unit, started from zero state two units early (or at the row's first sample); a workgroup is
+// one wave over 64 neighbouring units of one row and stages its lanes' spans through LDS in chunks of LOUD_T samples, loaded as 16-byte
+// groups aligned as ADDRESSES.  Workgroup 0 of a row also takes the peak of the tail behind the last whole unit.  grid.x covers units_max.
+void launch_loud_units(const LoudArgs& a, long units_max, hipStream_t s);
+// one workgroup per row: both gates over the row's blocks -> lufs[b], peak[b], row_sum / row_cnt, and gain[b] of ZVX_LOUD_PER_ROW
+void launch_loud_gates(const LoudArgs& a, hipStream_t s);
+// ZVX_LOUD_COMMON, one workgroup: both gates over the blocks of all rows, the maximum of the peaks, one gain written to every gain[b]
+void launch_loud_common(const LoudArgs& a, hipStream_t s);
+// out[b][i] = x[b][i] * gain[b] for i < nsamples[b], ONE f32 multiply; f32 rows, or int16 by the resampler's rule with pcm16.  Groups of 4
+// aligned as ADDRESSES of the destination; a thread reads its group before it writes it and no other thread touches it: safe in place.
+struct LoudApplyArgs {
+    const float* x; long x_bs; const int* nsamples; int B;
+    const float* gain; void* out; long out_bs; int pcm16;
+};
+void launch_loud_apply(const LoudApplyArgs& a, long n_max, hipStream_t s);
 // half-mode saturation audit: *count += number of elements of x[b][r < rows[b]][0:C] (16-bit, batch stride bs, row stride ld) whose
 // magnitude bits are >= 0x7BFF (+-65504 = a clamped store, or Inf / NaN)
 void launch_count_sat16(const void* x, long bs, int ld, int B, int rows_max, const int* rows, int C, unsigned long long* count, hipStream_t s);

@@ -5,6 +5,8 @@ same RTF definition (audio seconds / synthesis seconds), same warm-up rule (iter
 
 `--long`: the text (or, where the argument names a file, the file's contents) is a paragraph: ZeroVoxTTS.tts_long synthesises it
 sentence by sentence in batches and joins the sentences on the device; --wav-filename receives the joined waveform.
+`--loudness LUFS` (with `--peak-db DB`) brings the waveform -- with `--long` the paragraph as one programme -- to an integrated loudness on
+the device (zvx_normalize).
 """
 import argparse
 import os
@@ -31,6 +33,9 @@ def main():
     ap.add_argument("--energy-shift", type=float, default=0.0)
     ap.add_argument("--energy-range", type=float, default=1.0)
     ap.add_argument("--out-rate", type=int, default=0, help="output sampling rate in Hz, converted on the device (0: the model's rate)")
+    ap.add_argument("--loudness", type=float, default=None, metavar="LUFS",
+                    help="integrated loudness (BS.1770 / R128) the waveform is brought to on the device, e.g. -16 or -23 (default: as the model gives it)")
+    ap.add_argument("--peak-db", type=float, default=-1.0, metavar="DB", help="sample-peak ceiling of the loudness gain in dBFS")
     ap.add_argument("--long", action="store_true", help="long-form: split the text (or the file it names) into sentences and join them on the device")
     args = ap.parse_args()
 
@@ -47,7 +52,8 @@ def main():
         t0 = time.time()
         if args.long:
             wav, segments = synth.tts_long(text, spkemb, speed=args.speed, pitch_shift=args.pitch_shift, pitch_range=args.pitch_range,
-                                           energy_shift=args.energy_shift, energy_range=args.energy_range)
+                                           energy_shift=args.energy_shift, energy_range=args.energy_range, loudness=args.loudness,
+                                           peak_db=args.peak_db)
             elapsed = time.time() - t0
             wav_len = (wav.shape[0] if segments else 0) / sr
             print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, {len(segments)} sentences, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")
@@ -57,7 +63,8 @@ def main():
                 rtf.append(wav_len / elapsed)
             continue
         wav, phoneme, length = synth.tts(args.text, spkemb, speed=args.speed, pitch_shift=args.pitch_shift, pitch_range=args.pitch_range,
-                                         energy_shift=args.energy_shift, energy_range=args.energy_range)
+                                         energy_shift=args.energy_shift, energy_range=args.energy_range, loudness=args.loudness,
+                                         peak_db=args.peak_db)
         elapsed = time.time() - t0
         wav_len = wav.shape[0] / sr
         print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")

@@ -9,6 +9,12 @@ MAX_CHARS = 200                  # BASELINE's workload is 7 frames per phoneme: 
 PAUSES_MS = {".": 350, ";": 250, ",": 120, " ": 0}     # pause behind a piece, by the class of the character that closed it
 _CLOSING = {".": ".", "!": ".", "?": ".", ";": ";", ":": ";"}
 TRIM_FRAME, TRIM_HOP = 2048, 512                       # librosa.effects.trim's defaults, as mels.trim_silence
+LOUDNESS_MODES = {"paragraph": True, "sentence": False}   # -> zvx_normalize's ZVX_LOUD_COMMON / ZVX_LOUD_PER_ROW
+
+
+def peak_ceiling(peak_db):
+    """sample-peak ceiling in dBFS -> the linear ceiling of zvx_loudness_params (None: no ceiling)"""
+    return 0.0 if peak_db is None else float(10.0 ** (float(peak_db) / 20.0))
 
 
 def _has_phone(s):
@@ -61,9 +67,11 @@ def split_sentences(text, max_chars=MAX_CHARS):
 
 
 def synthesize_long(tts, text, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20, fade_ms=5, max_batch=32, max_frames=2048, pcm16=False,
-                    durations=None, max_chars=MAX_CHARS, prosody=None):
+                    durations=None, max_chars=MAX_CHARS, prosody=None, loudness=None, peak_db=-1.0, loudness_mode="paragraph"):
     """The body of ZeroVoxTTS.tts_long (see there).  prosody: Prosody.create keywords applied to every sentence, or None."""
     from . import _lib
+    if loudness_mode not in LOUDNESS_MODES:
+        raise ValueError(f"loudness_mode: {loudness_mode!r} is none of {sorted(LOUDNESS_MODES)}")
     ctx = tts.model.ctx
     native = ctx.get_int("sampling_rate")
     out_rate = ctx.get_int("out_rate") or native
@@ -114,6 +122,11 @@ def synthesize_long(tts, text, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20,
         keep, fade = int(round(keep_ms * native / 1000.0)), int(round(fade_ms * native / 1000.0))
         kw = dict(frame=frame, hop=hp, top_db=float(trim_db), keep=keep, fade=fade)
         lengths = mel_len.astype(np.int64) * hop
+        lufs, gain = [None] * N, [None] * N
+        if loudness is not None:                                 # ONE call over all rows, in place, behind the queued synthesis calls
+            lufs, _, gain = ctx.normalize_device(buf, lengths, stride, loudness, peak_ceiling=peak_ceiling(peak_db),
+                                                 common=LOUDNESS_MODES[loudness_mode], rate=native)
+            lufs, gain = [float(v) for v in lufs], [float(v) for v in gain]
         if out_rate == native:
             wav, pos, begin, ln = ctx.join_device(buf, lengths, stride, gaps, pcm16=pcm16, **kw)
             start = [int(p) for p in pos]
@@ -135,4 +148,7 @@ def synthesize_long(tts, text, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20,
             ctx.dev_free(buf)
     segments = [dict(text=items[i][0], start=start[i], samples=count[i], mel_len=int(mel_len[i]), trim=int(begin[i]), durations=durs[i])
                 for i in range(N)]
+    if loudness is not None:
+        for i, s in enumerate(segments):
+            s["lufs"], s["gain"] = lufs[i], gain[i]
     return wav, segments

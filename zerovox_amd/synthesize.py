@@ -139,10 +139,21 @@ class ZeroVoxTTS:
         kw = dict(speed=speed, pitch_shift=pitch_shift, pitch_range=pitch_range, energy_shift=energy_shift, energy_range=energy_range)
         return None if kw == dict(speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0) else kw
 
-    def tts_ex(self, text: str, spkemb, duration=None, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0):
+    @staticmethod
+    def _loudness(loudness, peak_db):
+        """the loudness keywords as Context.normalize_device keywords, or None (nothing is normalised)"""
+        from .longform import peak_ceiling
+        return None if loudness is None else dict(target=float(loudness), peak_ceiling=peak_ceiling(peak_db))
+
+    def tts_ex(self, text: str, spkemb, duration=None, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0,
+               loudness=None, peak_db=-1.0):
         """-> (wav f32[N], phoneme i32[1,T], length, mel f32[n_mels, L]); empty text -> the reference's sentinel
         (synthesize.py:213-239).  Prosody (include/zvx.h, zvx_prosody): speed = speaking-rate factor (2.0: half the frames),
-        pitch / energy shift (in normalised predictor units) and range (spread about the utterance mean)."""
+        pitch / energy shift (in normalised predictor units) and range (spread about the utterance mean).
+        loudness: None (the default: the level the model gives), or the integrated loudness in LUFS (BS.1770 / R128) the waveform is
+        brought to on the device (include/zvx.h, zvx_normalize): the vocoder's row stays there, is measured and multiplied by one gain in
+        place -- at most +20 dB, and no sample above peak_db dBFS (None: no ceiling) --, an ``output_rate`` converts it afterwards (the
+        ceiling applies before that conversion) and only then it comes to the host; ``last_loudness`` reports dict(lufs, peak, gain)."""
         prosody = self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range)
         text = text.strip()
         t0 = time.time()
@@ -155,22 +166,34 @@ class ZeroVoxTTS:
         duration = np.array([duration], dtype=np.int32) if duration is not None else None
         t1 = time.time()
         wav, length, _, mel = self._model.inference_ex({"phoneme": phoneme, "puncts": puncts, "duration": duration},
-                                                       style_embed=spkemb, force_duration=duration is not None, prosody=prosody)
+                                                       style_embed=spkemb, force_duration=duration is not None, prosody=prosody,
+                                                       **({} if loudness is None else dict(loudness=self._loudness(loudness, peak_db))))
         if self._verbose:
             print(f"tts timing stats: g2p={t1 - t0}s, synth={time.time() - t1}s")
         return wav, phoneme, length, mel
 
-    def tts(self, text: str, spkemb, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0):
+    def tts(self, text: str, spkemb, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0, loudness=None,
+            peak_db=-1.0):
         wav, phoneme, length, _ = self.tts_ex(text=text, spkemb=spkemb, speed=speed, pitch_shift=pitch_shift, pitch_range=pitch_range,
-                                              energy_shift=energy_shift, energy_range=energy_range)
+                                              energy_shift=energy_shift, energy_range=energy_range, loudness=loudness, peak_db=peak_db)
         return wav, phoneme, length
 
+    @property
+    def last_loudness(self):
+        """dict(lufs, peak, gain) of the last tts / tts_ex call that asked for a loudness (None before the first)"""
+        return self._model.last_loudness
+
     def tts_stream(self, text: str, spkemb, chunk_frames=64, chunks_per_call=1, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0,
-                   energy_shift=0.0, energy_range=1.0):
+                   energy_shift=0.0, energy_range=1.0, loudness=None):
         """Streaming variant of ``tts`` (not in the reference): encoder + mel decoder run once, the vocoder
         runs chunk by chunk (16-frame halo), yielding float32 waveform pieces that concatenate to ``tts(text, spkemb)[0]``
-        up to the reference's `_min_mel_len` zero-padding of short utterances."""
-        prosody = self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range)
+        up to the reference's `_min_mel_len` zero-padding of short utterances.  A stream cannot be loudness-normalised: the gain is not
+        known before the last chunk, so ``loudness`` other than None raises ValueError (use tts / tts_long)."""
+        if loudness is not None:
+            raise ValueError("tts_stream cannot normalise loudness: the gain is unknown until the last chunk (use tts or tts_long)")
+        return self._tts_stream(text, spkemb, chunk_frames, chunks_per_call, self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range))
+
+    def _tts_stream(self, text, spkemb, chunk_frames, chunks_per_call, prosody):
         text = text.strip()
         phone_ids, punct_ids = self.text2phonemeids(text)
         if not phone_ids:
@@ -186,7 +209,8 @@ class ZeroVoxTTS:
         yield from self._model.vocode_stream(mel, chunk_frames=chunk_frames, chunks_per_call=chunks_per_call)
 
     def tts_long(self, text: str, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20, fade_ms=5, max_batch=32, max_frames=2048, pcm16=False,
-                 durations=None, max_chars=200, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0):
+                 durations=None, max_chars=200, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0,
+                 loudness=None, peak_db=-1.0, loudness_mode="paragraph"):
         """A paragraph -> (wav, segments): one waveform with every sentence in text order (not in the reference).  The text is split by
         longform.split_sentences; the sentences run in batches of at most max_batch, each batch ONE queued synthesize call into
         consecutive rows of one device buffer (every row is the fresh-model ``tts`` of its sentence; a sentence of more than max_frames
@@ -197,11 +221,19 @@ class ZeroVoxTTS:
         sentence; durations: None or one list of per-phoneme frame counts per sentence, forced as tts_ex(duration=...) does.
         wav: float32, or int16 with pcm16.  segments: one dict per sentence -- text, start / samples (its place in wav, in output
         samples), mel_len, trim (samples cut in front, at the model's rate) and durations (the per-phoneme frame counts as
-        synthesised): what subtitles or lip-sync need.  Empty or phone-less text: the reference's sentinel waveform and []."""
+        synthesised): what subtitles or lip-sync need.  Empty or phone-less text: the reference's sentinel waveform and [].
+        loudness: None, or the integrated loudness in LUFS the paragraph is brought to: ONE zvx_normalize over all rows of the device
+        buffer, in place, between the synthesis calls and the join.  loudness_mode "paragraph": the sentences are measured as one
+        programme and share one gain (their relative levels stay); "sentence": every sentence gets its own gain.  The gain is at most
+        +20 dB and leaves no sample above peak_db dBFS (None: no ceiling).  The measurement is at the model's rate, untrimmed, before any
+        output-rate conversion: the ceiling applies BEFORE resampling, whose band-limited interpolation may overshoot it -- pcm16
+        still clamps what does.  Every segment dict then also carries lufs (the sentence's own measured loudness, -inf where it is
+        shorter than 0.4 s or silent) and gain (the linear factor applied)."""
         from .longform import synthesize_long
         return synthesize_long(self, text, spkemb, pauses=pauses, trim_db=trim_db, keep_ms=keep_ms, fade_ms=fade_ms, max_batch=max_batch,
                                max_frames=max_frames, pcm16=pcm16, durations=durations, max_chars=max_chars,
-                               prosody=self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range))
+                               prosody=self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range),
+                               loudness=loudness, peak_db=peak_db, loudness_mode=loudness_mode)
 
     @property
     def output_rate(self):
