@@ -325,7 +325,8 @@ zvx_status zvx_join(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int 
  * Stage tag "post.loudness" in zvx_tag_stats (one timed group per call; no stage slot): algorithmic bytes = 4 sum(n) for the measurement;
  *   zvx_normalize adds 4 sum(n) read and the bytes written.
  * Replaces a host-side meter and gain (pyloudnorm and the like) behind ZeroVoxTTS.tts; the reference hands its waveform back at whatever
- * level the model gives (synthesize.py:213-239).  Not here: true-peak metering, limiting, momentary / short-term loudness, several channels. */
+ * level the model gives (synthesize.py:213-239).  True-peak metering and a limiter: zvx_true_peak / zvx_limit below.  Not here: momentary /
+ * short-term loudness, several channels. */
 enum { ZVX_LOUD_PER_ROW = 0, ZVX_LOUD_COMMON = 1 };
 typedef struct zvx_loudness_params {
     float   target_lufs;   /* integrated loudness to reach, finite, in [-70, 0] */
@@ -343,6 +344,61 @@ zvx_status zvx_loudness(zvx_ctx* ctx, const float* in, const int32_t* nsamples, 
 zvx_status zvx_normalize(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, int rate,
                          const zvx_loudness_params* params, void* out, int64_t out_stride,
                          double* lufs, float* peak, float* gain, int flags);
+
+/* True-peak metering and a look-ahead limiter for rows in [B][Nmax] f32 with nsamples[b] valid samples at `rate` Hz.  Rows are independent;
+ * nothing sees a neighbouring row or the padding.  The algorithm has finite support and no recurrence, so it is defined to the bit where
+ * the other post-processing is.  Per row of n samples:
+ * Oversampled signal: y[m], m < os n, is what zvx_resample computes for (L, M) = (os, 1): the same taps (half = 10 os, 21 per output), the
+ *   same f32 sum in the same order, x = 0 outside the row.  The bank depends on (L, M) only -- `rate` does not enter it, so os * rate may
+ *   exceed 192000.  y is never written to memory.  os = 1 uses no filter at all.
+ * Envelope (f32): e[i] = max(|x[i]|, |y[m]| for os (i - 1) < m < os (i + 1), 0 <= m < os n): an inter-sample peak between i and i + 1
+ *   counts for both neighbours.  os = 1: e[i] = |x[i]|.
+ * Depth, in double: d[i] = e[i] > c ? 1 - (double) c / (double) e[i] : 0;  r[i] = 1 - d[i].
+ * Hold: D[i] = the maximum of d[j] over |j - i| <= W, 0 <= j < n (exact: any order).
+ * Smooth: w[k] = (1 + cos(pi k / (W + 1))) / (2 (W + 1)), k = -W .. W, designed on the host in double, divided by their own sum (in exact
+ *   arithmetic they sum to 1 already) and cached per W;  s[i] = 1 - sum_k w[k] D[clamp(i + k, 0, n - 1)], a double sum in any order.
+ * Gain: g[i] = min(s[i], r[i]);  g32[i] = g[i] rounded toward zero to f32;  out[i] = x[i] * g32[i], ONE f32 multiply; with ZVX_PCM16 the
+ *   resampler's rule follows.
+ * What follows from that:
+ *   (a) the ceiling holds exactly: |out[i]| <= c, no tolerance.  Every D under the sum has i in its window, so s <= r up to rounding; the
+ *       min and the rounding toward zero remove the rest, and c is an f32.
+ *   (b) untouched samples keep their bits: where no e[j] > c within 2 W of i every term is exactly 0, g32 = 1 and out[i] has the bits of
+ *       x[i]; a row that never exceeds the ceiling passes through bit for bit.
+ *   (c) the TRUE peak after limiting is not an exact guarantee: the gain is applied at the base rate, so the oversampled output only stays
+ *       near c.  Measured by the float64 reference (tests/test_limiter.py: speech-like rows at a peak of 1.6, c = 0.891, os = 4): at most
+ *       0.0033 dB over c with a 1 ms window (W = 22 at 22.05 kHz: 0.00321 dB) and below 1e-4 dB with 5 ms (W = 110: 0.000024 dB); with
+ *       os = 1 (sample peaks only) the same rows end up to 3.0 dB over it.
+ *   (d) non-finite input: the call succeeds and nothing faults; that row is unspecified, every other row is bit for bit what it is without
+ *       it (zvx_vocode_mel's rule).
+ *   (e) n = 0 writes nothing (peak_in = 0, min_gain = 1); n <= W is legal: the clamped index handles it.
+ * zvx_true_peak: tpeak[b] = max_i e[i] = max(max_i |x[i]|, max_m |y[m]|); 0 for an empty row.
+ * Launches: the envelope (a tile plus a halo of 10 / 11 samples staged in LDS) into a work buffer of the context; hold, smooth, gain and
+ *   multiply over a tile plus a halo of 2 W envelope samples in LDS -- it reads the envelope, never a neighbour's x, so out == in is safe --;
+ *   a reduction per row.  Lengths are read on the device, nothing syncs in between.
+ * Syncs: as for zvx_normalize -- the call waits once, for the host outputs; with ZVX_DEVICE_OUT | ZVX_NO_SYNC and peak_in == min_gain == NULL
+ *   zvx_limit only queues; with ZVX_DEVICE_IN the rows may be the output of a zvx_synthesize / zvx_normalize call queued just before on the
+ *   same context.  (The first use of an oversampling factor or of a window W uploads its table and waits for that once.)
+ * Validation, before anything is queued (ZVX_E_INVALID, the context stays usable): a NULL ctx / in / nsamples / params / out (zvx_true_peak:
+ *   tpeak), B <= 0, Nmax <= 0, a negative length, nsamples[b] > Nmax, out_stride < Nmax, rate outside [4000, 192000], unknown flags,
+ *   ZVX_NO_SYNC without ZVX_DEVICE_OUT, ZVX_PCM16 with out == in, out == in with another stride or on another side than in, a ceiling that
+ *   is not finite or outside (0, 8], a window_ms that is not finite or <= 0, an oversample outside {1, 2, 4, 8}.  ZVX_E_UNSUPPORTED: more
+ *   than 65535 rows, W > 4096.
+ * Stage tag "post.limit" in zvx_tag_stats (one timed group per call; no stage slot): algorithmic bytes = 4 sum(n) for zvx_true_peak;
+ *   4 sum(n) read plus the bytes written for zvx_limit.
+ * Replaces a host-side true-peak meter and limiter behind zvx_normalize, whose gain a sample-peak ceiling otherwise bounds. */
+typedef struct zvx_limit_params {
+    float   ceiling;     /* linear ceiling c, finite, 0 < c <= 8 (0.891 = -1 dBFS) */
+    float   window_ms;   /* W = max(1, rint(rate * window_ms / 1000)), on the host in double; W > 4096: ZVX_E_UNSUPPORTED */
+    int32_t oversample;  /* os: 1 = sample peaks, 2 / 4 / 8 = true-peak detection */
+} zvx_limit_params;
+
+/* tpeak[b] (host float[B]) = max(max_i |x[i]|, max_m |y[m]|), y = the os-times oversampled row.  flags: ZVX_DEVICE_IN */
+zvx_status zvx_true_peak(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, int oversample,
+                         float* tpeak, int flags);
+/* out row b = x[i] * g32[i]; peak_in[b] = max_i e[i], min_gain[b] = min_i g32[i] (host arrays, each may be NULL).
+ * flags: ZVX_DEVICE_IN, ZVX_DEVICE_OUT, ZVX_NO_SYNC (device out only), ZVX_PCM16 (not in place); out == in (same stride) allowed for f32 */
+zvx_status zvx_limit(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, int rate,
+                     const zvx_limit_params* params, void* out, int64_t out_stride, float* peak_in, float* min_gain, int flags);
 
 /* Debug/parity taps: copy an intermediate of the last call to host fp32.
  * what: "encoder_out" [B][Tmax][hidden] (after the style add), "features" [B][Lmax][hidden],
@@ -396,7 +452,7 @@ typedef struct {
 } zvx_kernel_stat;
 int        zvx_kernel_stats(zvx_ctx* ctx, zvx_kernel_stat* out, int max_out);
 /* The same counters grouped by pipeline stage ("encoder", "variance", "lenreg", "decoder", "decoder.norm", "voc.pre",
- * "voc.up1".."voc.res4", "voc.post", "voc.resample", "post.join", "post.loudness", "spkemb"; name = stage): every launch of the stage, including the HBM-bound helper
+ * "voc.up1".."voc.res4", "voc.post", "voc.resample", "post.join", "post.loudness", "post.limit", "spkemb"; name = stage): every launch of the stage, including the HBM-bound helper
  * kernels, while "profile" == 2 and "profile_only" == -1.  Feeds the per-stage roofline fractions of bench.py. */
 int        zvx_tag_stats(zvx_ctx* ctx, zvx_kernel_stat* out, int max_out);
 zvx_status zvx_reset_stats(zvx_ctx* ctx);

@@ -1,6 +1,7 @@
 """Long-form synthesis against the loop a caller writes without it: paragraphs of 8, 32 and 128 sentences of 64 phonemes each,
 StyleTTS decoder + HiFi-GAN V1, bf16, synthetic weights.
    python tools/longform_bench.py [out.json] [--loudness [LUFS]]
+   python tools/longform_bench.py --limit [out.txt]
 Per paragraph, host wall time (median of 20 after 3 warm-ups, same process, same device) of
   (a) one tts() per sentence, mels.trim_silence and np.concatenate on the host -- what the API offered before tts_long, and
   (b) tts_long (batched synthesis into one device buffer, zvx_join on the device, one copy out),
@@ -8,7 +9,13 @@ then from one profiled call of (b): the post.join stage time, its algorithmic by
 rate, and the vocoder stage time of the same call (the last batch's, where the paragraph needs several).  The ratio (b) / (a) and the
 HBM fraction are reported, not gated; the one condition -- post.join below the vocoder's stage time at 32 sentences -- fails the run.
 --loudness [LUFS] (default -23): also (c) tts_long(..., loudness=LUFS), timed right after (b) in the same process, the "post.loudness"
-launch group of one profiled call of (c), and zvx_normalize alone, in place on 32 x 229 376 device samples (both modes)."""
+launch group of one profiled call of (c), and zvx_normalize alone, in place on 32 x 229 376 device samples (both modes).
+--limit [out.txt]: ONLY the limiter, no paragraph is synthesised: the "post.limit" launch group of zvx_limit in place on 32 x 229 376
+device samples at 22050 Hz, W = 110 (5 ms), os = 4 and os = 1, on Gaussian rows of sigma 0.3 (a sample over the 0.891 ceiling in nearly
+every tile) and of sigma 0.05 (none: every tile takes the copy path); beside it the apply pass of zvx_normalize on the same rows -- the
+"post.loudness" group of zvx_normalize minus that of zvx_loudness, the same bytes read and written once -- and the float64 NumPy
+reference of tests/limit_ref.py on the same rows on this host.  Medians of 5 after 3 warm-ups; written as text (default
+profiles/limiter_bench.txt)."""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -19,6 +26,7 @@ from zerovox_amd.synthesize import ZeroVoxTTS
 ap = argparse.ArgumentParser()
 ap.add_argument("out", nargs="?", default=None)
 ap.add_argument("--loudness", type=float, nargs="?", const=-23.0, default=None, metavar="LUFS")
+ap.add_argument("--limit", action="store_true")
 args = ap.parse_args()
 HBM_BYTES_PER_S = 8e12
 _, synth = ZeroVoxTTS.load_model("synthetic:styletts", "synthetic:v1", infer_device="cuda:0", precision="bf16")
@@ -50,6 +58,56 @@ def loop(sents):
     return np.concatenate(parts)
 
 
+def limiter_bench(out_path):
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
+    import limit_ref
+    B, n, ceiling, ms = 32, 229376, 0.891, 5.0
+    W = limit_ref.window(rate, ms)
+    lens = np.full(B, n, np.int32)
+    lines = [f"zvx_limit in place on {B} rows x {n} device samples, {rate} Hz, ceiling {ceiling}, W = {W} ({ms} ms); hipEvent time of the launch group,",
+             "median of 5 calls after 3 warm-ups; every call starts from fresh rows.  apply pass = post.loudness(zvx_normalize) - post.loudness(zvx_loudness).", ""]
+    buf = ctx.dev_alloc(B * n * 4)
+    try:
+        for name, sigma in (("dense (sigma 0.3)", 0.3), ("quiet (sigma 0.05)", 0.05)):
+            x = (np.random.default_rng(1).standard_normal((B, n)) * sigma).astype(np.float32)
+
+            def group(tag, call):
+                ts = []
+                ctx.set_int("profile", 2)
+                for _ in range(8):
+                    ctx.dev_from_host(buf, x)
+                    ctx.reset_stats()
+                    call()
+                    ts.append({t["name"]: t for t in ctx.tag_stats()}[tag]["ms"])
+                ctx.set_int("profile", 0)
+                return float(np.median(ts[3:]))
+
+            norm = group("post.loudness", lambda: ctx.normalize_device(buf, lens, n, -23.0, rate=rate))
+            meas = group("post.loudness", lambda: ctx._chk(ctx._lib.zvx_loudness(ctx._h, buf, lens.ctypes.data, B, n, rate, None, None, _DEVICE_IN)))
+            apply_ms = norm - meas
+            lines.append(f"{name}: zvx_normalize {norm:.4f} ms, zvx_loudness {meas:.4f} ms -> apply pass {apply_ms:.4f} ms")
+            for os_ in (4, 1):
+                t = group("post.limit", lambda: ctx.limit_device(buf, lens, n, ceiling, window_ms=ms, oversample=os_, rate=rate))
+                lines.append(f"{name}: post.limit os = {os_}: {t:.4f} ms = {t / apply_ms:.2f} x the apply pass "
+                             f"({8.0 * B * n / (t * 1e-3) / HBM_BYTES_PER_S:.3f} of 8 TB/s by its 8 bytes per sample)")
+            t0 = time.perf_counter()
+            for b in range(B):
+                limit_ref.limit(x[b], ceiling, W, 4)
+            t4 = time.perf_counter() - t0
+            t0 = time.perf_counter()
+            for b in range(B):
+                limit_ref.limit(x[b], ceiling, W, 1)
+            t1 = time.perf_counter() - t0
+            lines.append(f"{name}: NumPy reference on this host, all rows: os = 4 {t4 * 1e3:.0f} ms, os = 1 {t1 * 1e3:.0f} ms")
+            lines.append("")
+    finally:
+        ctx.dev_free(buf)
+    text = "\n".join(lines)
+    print(text)
+    with open(out_path, "w") as f:
+        f.write(text)
+
+
 def median_ms(f, n=20, warm=3):
     for _ in range(warm):
         f()
@@ -59,6 +117,10 @@ def median_ms(f, n=20, warm=3):
     return float(np.median(ts)) * 1e3
 
 
+if args.limit:
+    from zerovox_amd._lib import ZVX_DEVICE_IN as _DEVICE_IN
+    limiter_bench(args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "limiter_bench.txt"))
+    sys.exit(0)
 res = {"workload": "paragraphs of N sentences x 64 phonemes, StyleTTS decoder + HiFi-GAN V1 bf16, synthetic weights, predicted durations, "
                    "host waveform out; ms = host wall time, median of 20 after 3 warm-ups", "paragraphs": []}
 ok = True

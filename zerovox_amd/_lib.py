@@ -24,9 +24,11 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_comm_unique_id", "zvx_comm_init", "zvx_comm_gather", "zvx_comm_barrier", "zvx_comm_max_f64", "zvx_comm_info", "zvx_comm_destroy",
            "zvx_dev_alloc", "zvx_dev_free", "zvx_dev_from_host", "zvx_dev_to_host", "zvx_spkemb_ex", "zvx_wait_host",
            "zvx_encode_ex", "zvx_synthesize_ex", "zvx_resample", "zvx_resample_ex", "zvx_trim_bounds", "zvx_join",
-           "zvx_loudness", "zvx_normalize")
+           "zvx_loudness", "zvx_normalize", "zvx_true_peak", "zvx_limit")
 ZVX_COMM_ID_BYTES = 128
 ZVX_LOUD_PER_ROW, ZVX_LOUD_COMMON = 0, 1
+LIMIT_TILE = 1024                                    # samples per workgroup of both limiter kernels (csrc/zvx_kernels.h, LIMIT_TILE)
+LIMIT_MAX_W = 4096                                   # the longest window, in samples (LIMIT_MAX_W)
 
 
 def resampled_len(n, rate_in, rate_out):
@@ -51,6 +53,11 @@ class JoinParams(C.Structure):
 class LoudnessParams(C.Structure):
     """zvx_loudness_params (include/zvx.h)"""
     _fields_ = [("target_lufs", C.c_float), ("peak_ceiling", C.c_float), ("max_gain_db", C.c_float), ("mode", C.c_int32)]
+
+
+class LimitParams(C.Structure):
+    """zvx_limit_params (include/zvx.h)"""
+    _fields_ = [("ceiling", C.c_float), ("window_ms", C.c_float), ("oversample", C.c_int32)]
 
 
 class KernelStat(C.Structure):
@@ -116,6 +123,8 @@ def load():
     lib.zvx_join.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(JoinParams), vp, C.c_int64, C.POINTER(C.c_int64), vp, vp, vp, C.c_int]
     lib.zvx_loudness.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int]
     lib.zvx_normalize.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(LoudnessParams), vp, C.c_int64, vp, vp, vp, C.c_int]
+    lib.zvx_true_peak.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int]
+    lib.zvx_limit.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(LimitParams), vp, C.c_int64, vp, vp, C.c_int]
     _lib = lib
     return lib
 
@@ -323,6 +332,44 @@ class Context:
         self._chk(self._lib.zvx_normalize(self._h, p, _ptr(n), B, int(Nmax), self._rate(rate), C.byref(prm), p, int(Nmax), _ptr(lufs), _ptr(peak),
                                           _ptr(gain), ZVX_DEVICE_IN | ZVX_DEVICE_OUT))
         return lufs, peak, gain
+
+    def true_peak(self, rows, oversample=4, rate=None, lengths=None):
+        """zvx_true_peak: per row max(max |x|, max |y|), y the row oversampled `oversample` (1, 2, 4, 8) times by zvx_resample's filter
+        -> [B] float32.  rows: a list of 1-D float waveforms, or a padded 2-D array + lengths; rate None: the model's sampling rate."""
+        x, n = self._rows(rows, lengths)
+        B, Nmax = x.shape
+        tp = np.zeros(B, np.float32)
+        self._chk(self._lib.zvx_true_peak(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), int(oversample), _ptr(tp), 0))
+        return tp
+
+    def limit(self, rows, ceiling, window_ms=5.0, oversample=4, pcm16=False, rate=None, lengths=None):
+        """zvx_limit on host rows: a look-ahead limiter that leaves no sample above the linear `ceiling`, its gain smoothed over
+        window_ms on either side and driven by the `oversample`-times oversampled envelope -> (rows_out [B][Nmax] float32 / int16 -- row
+        b holds its limited samples, then zeros --, peak_in [B] float32: the envelope's maximum, min_gain [B] float32)."""
+        x, n = self._rows(rows, lengths)
+        B, Nmax = x.shape
+        prm = LimitParams(float(ceiling), float(window_ms), int(oversample))
+        out = np.zeros((B, Nmax), np.int16 if pcm16 else np.float32)
+        peak, gmin = np.zeros(B, np.float32), np.zeros(B, np.float32)
+        self._chk(self._lib.zvx_limit(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), Nmax, _ptr(peak), _ptr(gmin),
+                                      ZVX_PCM16 if pcm16 else 0))
+        return out, peak, gmin
+
+    def limit_device(self, ptr, lengths, Nmax, ceiling, *, window_ms=5.0, oversample=4, rate=None, no_sync=False):
+        """zvx_limit IN PLACE on device rows [B][Nmax] f32 at `ptr` (they may be the output of a synthesize / normalize_device call queued
+        just before: stream order is the fence) -> (peak_in, min_gain); with no_sync the call only queues and returns None."""
+        n = _i32(lengths)
+        B = len(n)
+        prm = LimitParams(float(ceiling), float(window_ms), int(oversample))
+        p = C.c_void_p(int(ptr))
+        if no_sync:
+            self._chk(self._lib.zvx_limit(self._h, p, _ptr(n), B, int(Nmax), self._rate(rate), C.byref(prm), p, int(Nmax), None, None,
+                                          ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC))
+            return None
+        peak, gmin = np.zeros(B, np.float32), np.zeros(B, np.float32)
+        self._chk(self._lib.zvx_limit(self._h, p, _ptr(n), B, int(Nmax), self._rate(rate), C.byref(prm), p, int(Nmax), _ptr(peak), _ptr(gmin),
+                                      ZVX_DEVICE_IN | ZVX_DEVICE_OUT))
+        return peak, gmin
 
     def resample_device(self, ptr, n, rate_in, rate_out, pcm16=False):
         """zvx_resample of ONE device-resident row of n f32 samples (ZVX_DEVICE_IN) -> host row at rate_out"""

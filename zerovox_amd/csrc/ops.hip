@@ -1809,4 +1809,204 @@ void launch_loud_apply(const LoudApplyArgs& a, long n_max, hipStream_t s) {
     hipLaunchKernelGGL(k_loud_apply, dim3((unsigned)tiles, a.B), dim3(256), 0, s, a);
 }
 
+// ---------------------------------------------------------------- true-peak envelope and look-ahead limiter (zvx_kernels.h, include/zvx.h: zvx_limit)
+constexpr int LIM_T = 21;                    // taps per oversampled point: ceil((20 os + 1) / os) for every os
+constexpr int LIM_LO = 10, LIM_HI = 11;      // phase 0 starts 10 samples in front of its sample; the others 9 in front, 11 behind (the last tap is a 0)
+constexpr int LIM_XS = LIMIT_TILE + 1 + LIM_LO + LIM_HI;
+constexpr int LIM_BP = 24;                   // pitch of the bank's copy in LDS
+__device__ __forceinline__ float wg_max_f32(float v, float* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
+    __syncthreads();                                          // the previous reduction's readers are done
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+}
+// the largest f32 of magnitude <= |g|
+__device__ __forceinline__ float f32_toward_zero(double g) {
+    float f = (float)g;
+    if (fabs((double)f) > fabs(g)) f = __uint_as_float(__float_as_uint(f) - 1u);
+    return f;
+}
+// Oversampled point m = os k0 + p is the resampler's output for (L, M) = (os, 1): its window starts at x[k0 - 10] for p = 0 and at
+// x[k0 - 9] otherwise, and it is summed as k_resample_poly sums it -- acc = bank[p][0] * x[ks]; acc = fma(bank[p][t], x[ks + t], acc).
+// The workgroup evaluates the points of samples t0 - 1 .. t0 + LIMIT_TILE - 1 (those of t0 - 1 count for the envelope of t0) and keeps,
+// per sample, eo = max(|x|, |y[os k0]|) and uo = the largest |y| strictly between k0 and k0 + 1.
+template <int OS>
+__global__ __launch_bounds__(256) void k_limit_env(const LimitArgs a) {
+    __shared__ float xs[LIM_XS];
+    __shared__ float eo[LIMIT_TILE + 1], uo[LIMIT_TILE + 1];
+    __shared__ __attribute__((aligned(16))) float bks[8 * LIM_BP];
+    __shared__ float red[4];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int n = a.nsamples[b];
+    const long t0 = (long)blockIdx.x * LIMIT_TILE;
+    float pk = 0.f;
+    if (t0 < n) {                                            // (uniform over the workgroup)
+        const float* xrow = a.x + (long)b * a.x_bs;
+        const long base = t0 - 1 - LIM_LO;                   // xs[j] = x[base + j], 0 outside the row
+        for (int j = tid; j < LIM_XS; j += 256) { const long g = base + j; xs[j] = (g >= 0 && g < n) ? xrow[g] : 0.f; }
+        if (OS > 1)
+            for (int i = tid; i < OS * LIM_T; i += 256) { const int p = i / LIM_T, t = i - p * LIM_T; bks[p * LIM_BP + t] = a.bank[p * a.pitch + t]; }
+        __syncthreads();
+        for (int j = tid; j < LIMIT_TILE + 1; j += 256) {
+            const long k0 = t0 - 1 + j;
+            float e = 0.f, u = 0.f;
+            if (k0 >= 0 && k0 < n) {
+                float xr[LIM_T + 1];                         // x[k0 - 10 .. k0 + 11]
+#pragma unroll
+                for (int t = 0; t < LIM_T + 1; t++) xr[t] = xs[j + t];
+                e = fabsf(xr[LIM_LO]);
+#pragma unroll
+                for (int p = 0; p < (OS > 1 ? OS : 0); p++) {
+                    const float* br = bks + p * LIM_BP;
+                    const int sh = p ? 1 : 0;
+                    float acc = br[0] * xr[sh];
+#pragma unroll
+                    for (int t = 1; t < LIM_T; t++) acc = __builtin_fmaf(br[t], xr[sh + t], acc);
+                    if (p == 0) e = fmaxf(e, fabsf(acc)); else u = fmaxf(u, fabsf(acc));
+                }
+            }
+            eo[j] = e; uo[j] = u;
+        }
+        __syncthreads();
+        float* erow = a.env ? a.env + (long)b * a.e_bs : nullptr;
+#pragma unroll
+        for (int q = 0; q < LIMIT_TILE / 256; q++) {
+            const int j = 1 + tid + 256 * q;
+            const long i = t0 + j - 1;
+            if (i < n) {
+                const float e = fmaxf(fmaxf(eo[j], uo[j]), uo[j - 1]);
+                if (erow) erow[i] = e;
+                pk = fmaxf(pk, e);
+            }
+        }
+    }
+    pk = wg_max_f32(pk, red);
+    if (tid == 0) a.part_max[(long)b * a.ppitch + blockIdx.x] = pk;
+}
+void launch_limit_env(const LimitArgs& a, hipStream_t s) {
+    if (a.B <= 0) return;
+    const dim3 grid((unsigned)a.ppitch, a.B), block(256);
+    if (a.os == 1) hipLaunchKernelGGL(k_limit_env<1>, grid, block, 0, s, a);
+    else if (a.os == 2) hipLaunchKernelGGL(k_limit_env<2>, grid, block, 0, s, a);
+    else if (a.os == 4) hipLaunchKernelGGL(k_limit_env<4>, grid, block, 0, s, a);
+    else hipLaunchKernelGGL(k_limit_env<8>, grid, block, 0, s, a);
+}
+
+// LDS (all of it dynamic): Ds[LIMIT_TILE + 2 W] doubles -- the held depths of samples t0 - W .. t0 + LIMIT_TILE + W - 1, at the clamped index where that lies
+// outside the row --, then es[LIMIT_TILE + 4 W] floats -- the envelope of samples t0 - 2 W .. t0 + LIMIT_TILE + 2 W - 1, 0 outside the row.
+// Running maximum by doubling, in place: after the pass with step p, es[j] = max e over [j, j + 2 p).  A pass goes through es in chunks of
+// 1024 in ascending order; a chunk reads es[j] and es[j + p] into registers, waits, and writes es[j]: what it reads ahead of itself has not
+// been written in this pass.  With P the largest power of two <= 2 W + 1 the window [g - W, g + W] is the union of [g - W, g - W + P) and
+// [g + W + 1 - P, g + W + 1).
+__global__ __launch_bounds__(256) void k_limit_gain(const LimitArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sm[];
+    const int W = a.W, SE = LIMIT_TILE + 4 * W, SD = LIMIT_TILE + 2 * W;
+    double* Ds = (double*)sm;
+    float* es = (float*)(Ds + SD);
+    float* red = es + SE;                                    // (no static LDS: the opt-in beyond 64 KiB covers the dynamic part alone)
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const int n = a.nsamples[b];
+    const long t0 = (long)blockIdx.x * LIMIT_TILE;
+    constexpr int Q = LIMIT_TILE / 256;
+    float gmin = 1.f;
+    if (t0 < n) {                                            // (uniform over the workgroup)
+        const float* erow = a.env + (long)b * a.e_bs;
+        const float* xrow = a.x + (long)b * a.x_bs;
+        const long eb = t0 - 2L * W;                         // es[j] = e[eb + j]
+        float mx = 0.f;
+        for (int j = tid; j < SE; j += 256) {
+            const long g = eb + j;
+            const float v = (g >= 0 && g < n) ? erow[g] : 0.f;
+            es[j] = v; mx = fmaxf(mx, v);
+        }
+        mx = wg_max_f32(mx, red);                            // (its barriers also complete es)
+        float g32[Q];
+#pragma unroll
+        for (int q = 0; q < Q; q++) g32[q] = 1.f;
+        if (mx > a.c) {                                      // otherwise every depth in reach is 0: s = r = 1 exactly
+            float eown[Q];
+#pragma unroll
+            for (int q = 0; q < Q; q++) eown[q] = es[2 * W + tid + 256 * q];
+            int P = 1;
+            for (; 2 * P <= 2 * W + 1; P *= 2) {
+                for (int c0 = 0; c0 < SE; c0 += 1024) {
+                    float r[4];
+#pragma unroll
+                    for (int q = 0; q < 4; q++) {
+                        const int j = c0 + tid + 256 * q;
+                        r[q] = 0.f;
+                        if (j < SE) { r[q] = es[j]; if (j + P < SE) r[q] = fmaxf(r[q], es[j + P]); }
+                    }
+                    __syncthreads();
+#pragma unroll
+                    for (int q = 0; q < 4; q++) { const int j = c0 + tid + 256 * q; if (j < SE) es[j] = r[q]; }
+                }
+                __syncthreads();
+            }
+            for (int j = tid; j < SD; j += 256) {
+                long g = t0 - W + j;
+                g = g < 0 ? 0 : (g > n - 1 ? n - 1 : g);
+                const int a1 = (int)(g - W - eb), a2 = a1 + 2 * W + 1 - P;
+                const float H = fmaxf(es[a1], es[a2]);
+                Ds[j] = H > a.c ? 1.0 - (double)a.c / (double)H : 0.0;
+            }
+            __syncthreads();
+            double acc[Q];
+#pragma unroll
+            for (int q = 0; q < Q; q++) acc[q] = 0.0;
+            const double* dp = Ds + tid;
+            for (int kk = 0; kk <= 2 * W; kk++) {
+                const double w = a.win[kk];
+#pragma unroll
+                for (int q = 0; q < Q; q++) acc[q] = fma(w, dp[kk + 256 * q], acc[q]);
+            }
+#pragma unroll
+            for (int q = 0; q < Q; q++) {
+                const double sm1 = 1.0 - acc[q];
+                const double d = eown[q] > a.c ? 1.0 - (double)a.c / (double)eown[q] : 0.0;
+                g32[q] = f32_toward_zero(fmin(sm1, 1.0 - d));
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < Q; q++) {
+            const long i = t0 + tid + 256 * q;
+            if (i < n) {
+                const float v = xrow[i] * g32[q];
+                if (a.pcm16) ((short*)a.out)[(long)b * a.out_bs + i] = join_pcm(v);
+                else ((float*)a.out)[(long)b * a.out_bs + i] = v;
+                gmin = fminf(gmin, g32[q]);
+            }
+        }
+    }
+    gmin = -wg_max_f32(-gmin, red);
+    if (tid == 0) a.part_min[(long)b * a.ppitch + blockIdx.x] = gmin;
+}
+bool launch_limit_gain(const LimitArgs& a, hipStream_t s) {
+    if (a.B <= 0) return true;
+    const size_t lds = (size_t)(LIMIT_TILE + 2 * a.W) * 8 + (size_t)(LIMIT_TILE + 4 * a.W) * 4 + 16;
+    if (lds > 160 * 1024) return false;
+    if (lds > 64 * 1024 && !lds_opt_in((const void*)k_limit_gain)) return false;
+    hipLaunchKernelGGL(k_limit_gain, dim3((unsigned)a.ppitch, a.B), dim3(256), lds, s, a);
+    return true;
+}
+
+__global__ __launch_bounds__(256) void k_limit_reduce(const LimitArgs a) {
+    __shared__ float red[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    float mx = 0.f, mn = 1.f;
+    for (int i = tid; i < a.ppitch; i += 256) {
+        mx = fmaxf(mx, a.part_max[(long)b * a.ppitch + i]);
+        if (a.part_min) mn = fminf(mn, a.part_min[(long)b * a.ppitch + i]);
+    }
+    mx = wg_max_f32(mx, red);
+    mn = -wg_max_f32(-mn, red);
+    if (tid == 0) { a.res[b] = mx; a.res[a.B + b] = mn; }
+}
+void launch_limit_reduce(const LimitArgs& a, hipStream_t s) {
+    if (a.B <= 0) return;
+    hipLaunchKernelGGL(k_limit_reduce, dim3(a.B), dim3(256), 0, s, a);
+}
+
 }  // namespace zvx

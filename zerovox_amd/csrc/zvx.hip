@@ -155,6 +155,7 @@ struct zvx_ctx {
     int out_rate = 0;
     struct RsBank { int L = 0, M = 0, half = 0, T = 0, pitch = 0; const float* dev = nullptr; };
     std::map<std::pair<int, int>, RsBank> rs_banks;
+    std::map<int, const double*> lim_wins;  // zvx_limit: the smoothing weights on the device, designed in double, per window W
     std::map<int, LoudCoef> loud_coefs;    // zvx_loudness / zvx_normalize: the K-weighting biquads, designed in double, per sampling rate
     // zvx_join / zvx_trim_bounds / zvx_loudness / zvx_normalize: pinned host memory the layout or result words (and host output rows) land
     // in under the call's one wait
@@ -2310,6 +2311,109 @@ void do_loudness(zvx_ctx* c, const char* who, const float* in, const int32_t* ns
             if (nsamples[b] > 0) memcpy((char*)out + (size_t)b * out_stride * ss, host + res_pad + (size_t)b * ostage * ss, (size_t)nsamples[b] * ss);
 }
 
+// ------------------------------------------------------------------------------------------------
+// true-peak metering and the look-ahead limiter (include/zvx.h: zvx_true_peak, zvx_limit)
+// ------------------------------------------------------------------------------------------------
+// w[k] = (1 + cos(pi k / (W + 1))) / (2 (W + 1)), k = -W .. W, divided by their own sum; uploaded on first use of W, then kept.
+const double* limit_win(zvx_ctx* c, int W) {
+    auto it = c->lim_wins.find(W);
+    if (it != c->lim_wins.end()) return it->second;
+    std::vector<double> w(2 * (size_t)W + 1);
+    double sum = 0.0;
+    for (int k = -W; k <= W; k++) sum += w[k + W] = (1.0 + cos(M_PI * (double)k / (double)(W + 1))) / (2.0 * (double)(W + 1));
+    for (double& v : w) v /= sum;
+    double* d = (double*)c->buf("lim.win." + std::to_string(W), w.size() * sizeof(double));
+    HIPCHK(hipMemcpyAsync(d, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                 // `w` goes away; once per W
+    return c->lim_wins[W] = d;
+}
+
+// zvx_true_peak (p == nullptr: the envelope's maximum only, results in tpeak) and zvx_limit
+void do_limit(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_limit_params* p,
+              int oversample, void* out, int64_t out_stride, float* peak_in, float* min_gain, int flags) {
+    const bool lim = p != nullptr;
+    if (!in || !nsamples || B <= 0 || Nmax <= 0) fail(ZVX_E_INVALID, "%s: bad arguments (NULL pointer, B = %d, Nmax = %d)", who, B, Nmax);
+    if (!lim && !peak_in) fail(ZVX_E_INVALID, "%s: tpeak is NULL", who);
+    if (B > 65535) fail(ZVX_E_UNSUPPORTED, "%s: B = %d rows (at most 65535 per call)", who, B);
+    if (rate < 4000 || rate > 192000) fail(ZVX_E_INVALID, "%s: rate %d outside [4000, 192000]", who, rate);
+    if (flags & ~(lim ? (ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16) : ZVX_DEVICE_IN)) fail(ZVX_E_INVALID, "%s: unknown flag in %d", who, flags);
+    const int os = lim ? p->oversample : oversample;
+    if (os != 1 && os != 2 && os != 4 && os != 8) fail(ZVX_E_INVALID, "%s: oversample %d is none of 1, 2, 4, 8", who, os);
+    const int pcm16 = (flags & ZVX_PCM16) ? 1 : 0;
+    int W = 0;
+    if (lim) {
+        if (!out) fail(ZVX_E_INVALID, "%s: out is NULL", who);
+        if (out_stride < Nmax) fail(ZVX_E_INVALID, "%s: out_stride %lld is smaller than Nmax %d", who, (long long)out_stride, Nmax);
+        if ((flags & ZVX_NO_SYNC) && !(flags & ZVX_DEVICE_OUT)) fail(ZVX_E_INVALID, "%s: ZVX_NO_SYNC needs ZVX_DEVICE_OUT", who);
+        if (out == (const void*)in && pcm16) fail(ZVX_E_INVALID, "%s: ZVX_PCM16 cannot run in place", who);
+        if (out == (const void*)in && (out_stride != Nmax || !(flags & ZVX_DEVICE_IN) != !(flags & ZVX_DEVICE_OUT)))
+            fail(ZVX_E_INVALID, "%s: in place needs out_stride == Nmax and both pointers on the same side", who);
+        if (!std::isfinite(p->ceiling) || !(p->ceiling > 0.f) || p->ceiling > 8.f) fail(ZVX_E_INVALID, "%s: ceiling must be finite and lie in (0, 8]", who);
+        if (!std::isfinite(p->window_ms) || !(p->window_ms > 0.f)) fail(ZVX_E_INVALID, "%s: window_ms must be finite and positive", who);
+    }
+    long n_max = 0; double n_sum = 0;
+    for (int b = 0; b < B; b++) {
+        if (nsamples[b] < 0 || nsamples[b] > Nmax) fail(ZVX_E_INVALID, "%s: nsamples[%d]=%d out of range (0..%d)", who, b, nsamples[b], Nmax);
+        n_max = std::max<long>(n_max, nsamples[b]); n_sum += nsamples[b];
+    }
+    if (lim) {
+        const double w = std::max(1.0, rint((double)rate * (double)p->window_ms / 1000.0));
+        if (w > (double)LIMIT_MAX_W) fail(ZVX_E_UNSUPPORTED, "%s: window of %.0f samples (at most %d)", who, w, LIMIT_MAX_W);
+        W = (int)w;
+    }
+    const size_t ss = pcm16 ? 2 : 4;
+    const bool host_out = lim && !(flags & ZVX_DEVICE_OUT);
+    const bool want_host = peak_in || min_gain;
+    const size_t res_bytes = (size_t)B * 8, res_pad = (res_bytes + 255) & ~(size_t)255;     // peak [B], then min gain [B]
+    const long ostage = (n_max + 7) & ~7L;                    // row stride of the staged host output
+    char* host = (want_host || host_out) ? (char*)c->join_pinned(res_pad + (host_out ? (size_t)B * ostage * ss : 0)) : nullptr;
+    LimitArgs a{};
+    a.os = os;
+    if (os > 1) {
+        const zvx_ctx::RsBank& bk = rs_bank(c, os, 1);
+        if (bk.T != 21 || bk.half != 10 * os) fail(ZVX_E_STATE, "%s: the (%d, 1) bank has %d taps per output", who, os, bk.T);
+        a.T = bk.T; a.pitch = bk.pitch; a.bank = bk.dev;
+    }
+    if (lim) { a.c = p->ceiling; a.W = W; a.win = limit_win(c, W); }
+    const float* x_dev = in;
+    if (!(flags & ZVX_DEVICE_IN)) {
+        float* xd = c->fbuf("lim.in", (size_t)B * Nmax);
+        HIPCHK(hipMemcpyAsync(xd, in, (size_t)B * Nmax * 4, hipMemcpyHostToDevice, c->stream));
+        x_dev = xd;
+    }
+    a.x = x_dev; a.x_bs = Nmax; a.nsamples = c->upload_ints("lim.len", nsamples, B); a.B = B;
+    a.ppitch = (int)std::max(1L, (n_max + LIMIT_TILE - 1) / LIMIT_TILE);
+    a.e_bs = std::max(n_max, 1L);
+    a.env = lim ? c->fbuf("lim.env", (size_t)B * a.e_bs) : nullptr;
+    a.part_max = c->fbuf("lim.part", (size_t)2 * B * a.ppitch);
+    a.part_min = lim ? a.part_max + (size_t)B * a.ppitch : nullptr;
+    a.res = c->fbuf("lim.res", (size_t)2 * B);
+    void* odev = host_out ? c->buf("lim.out", (size_t)B * ostage * ss + 16) : out;
+    a.out = odev; a.out_bs = host_out ? ostage : (long)out_stride; a.pcm16 = pcm16;
+    const std::string keep = c->tag;
+    c->tag = "post.limit";
+    struct Untag { zvx_ctx* c; const std::string& keep; ~Untag() { c->tag = keep; } } untag{c, keep};
+    c->timed(0.0, 4.0 * n_sum + (lim ? (double)ss * n_sum : 0.0), [&] {
+        launch_limit_env(a, c->stream);
+        if (lim && !launch_limit_gain(a, c->stream)) fail(ZVX_E_UNSUPPORTED, "%s: a window of %d samples does not fit the LDS of a workgroup", who, W);
+        launch_limit_reduce(a, c->stream);
+    });
+    if (want_host) HIPCHK(hipMemcpyAsync(host, a.res, res_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (host_out && n_max > 0) HIPCHK(hipMemcpyAsync(host + res_pad, odev, (size_t)B * ostage * ss, hipMemcpyDeviceToHost, c->stream));
+    if (!want_host && (flags & ZVX_NO_SYNC)) return;         // device output, nothing for the host: the call only queues
+    c->sync();                                               // the call's one wait
+    if (want_host) {
+        const float* r_h = (const float*)host;
+        for (int b = 0; b < B; b++) {
+            if (peak_in) peak_in[b] = r_h[b];
+            if (min_gain) min_gain[b] = r_h[B + b];
+        }
+    }
+    if (host_out)
+        for (int b = 0; b < B; b++)
+            if (nsamples[b] > 0) memcpy((char*)out + (size_t)b * out_stride * ss, host + res_pad + (size_t)b * ostage * ss, (size_t)nsamples[b] * ss);
+}
+
 // wav: float rows, or int16 PCM rows with ZVX_PCM16 (stride counted in samples either way).  Row b receives
 // mel_len[b]*hop samples followed by zeros up to max_b(mel_len[b])*hop; nothing beyond that is touched.
 void do_vocode(zvx_ctx* c, const int32_t* pad_to, void* wav, int64_t wav_stride, int flags) {
@@ -2688,6 +2792,18 @@ zvx_status zvx_normalize(zvx_ctx* c, const float* in, const int32_t* nsamples, i
     return guarded(c, [&] {
         if (!params) fail(ZVX_E_INVALID, "zvx_normalize: params is NULL");
         do_loudness(c, "zvx_normalize", in, nsamples, B, Nmax, rate, params, out, out_stride, lufs, peak, gain, flags);
+    });
+}
+
+zvx_status zvx_true_peak(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, int oversample, float* tpeak, int flags) {
+    return guarded(c, [&] { do_limit(c, "zvx_true_peak", in, nsamples, B, Nmax, rate, nullptr, oversample, nullptr, 0, tpeak, nullptr, flags); });
+}
+
+zvx_status zvx_limit(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_limit_params* params,
+                     void* out, int64_t out_stride, float* peak_in, float* min_gain, int flags) {
+    return guarded(c, [&] {
+        if (!params) fail(ZVX_E_INVALID, "zvx_limit: params is NULL");
+        do_limit(c, "zvx_limit", in, nsamples, B, Nmax, rate, params, 0, out, out_stride, peak_in, min_gain, flags);
     });
 }
 

@@ -17,6 +17,15 @@ def peak_ceiling(peak_db):
     return 0.0 if peak_db is None else float(10.0 ** (float(peak_db) / 20.0))
 
 
+def limit_keywords(limiter, limiter_ms, peak_db):
+    """the limiter keywords of tts / tts_long -> Context.limit_device keywords, or None (limiter off)"""
+    if not limiter:
+        return None
+    if peak_db is None:
+        raise ValueError("limiter=True needs a ceiling: peak_db is None")
+    return dict(ceiling=peak_ceiling(peak_db), window_ms=float(limiter_ms), oversample=4)
+
+
 def _has_phone(s):
     return any(ch.isalnum() for ch in s)
 
@@ -67,11 +76,13 @@ def split_sentences(text, max_chars=MAX_CHARS):
 
 
 def synthesize_long(tts, text, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20, fade_ms=5, max_batch=32, max_frames=2048, pcm16=False,
-                    durations=None, max_chars=MAX_CHARS, prosody=None, loudness=None, peak_db=-1.0, loudness_mode="paragraph"):
+                    durations=None, max_chars=MAX_CHARS, prosody=None, loudness=None, peak_db=-1.0, loudness_mode="paragraph",
+                    limiter=False, limiter_ms=5.0):
     """The body of ZeroVoxTTS.tts_long (see there).  prosody: Prosody.create keywords applied to every sentence, or None."""
     from . import _lib
     if loudness_mode not in LOUDNESS_MODES:
         raise ValueError(f"loudness_mode: {loudness_mode!r} is none of {sorted(LOUDNESS_MODES)}")
+    lim = limit_keywords(limiter, limiter_ms, peak_db)
     ctx = tts.model.ctx
     native = ctx.get_int("sampling_rate")
     out_rate = ctx.get_int("out_rate") or native
@@ -124,9 +135,11 @@ def synthesize_long(tts, text, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20,
         lengths = mel_len.astype(np.int64) * hop
         lufs, gain = [None] * N, [None] * N
         if loudness is not None:                                 # ONE call over all rows, in place, behind the queued synthesis calls
-            lufs, _, gain = ctx.normalize_device(buf, lengths, stride, loudness, peak_ceiling=peak_ceiling(peak_db),
+            lufs, _, gain = ctx.normalize_device(buf, lengths, stride, loudness, peak_ceiling=0.0 if lim else peak_ceiling(peak_db),
                                                  common=LOUDNESS_MODES[loudness_mode], rate=native)
             lufs, gain = [float(v) for v in lufs], [float(v) for v in gain]
+        if lim:                                                  # likewise, behind the gain: which then has no peak ceiling
+            _, min_gain = ctx.limit_device(buf, lengths, stride, rate=native, **lim)
         if out_rate == native:
             wav, pos, begin, ln = ctx.join_device(buf, lengths, stride, gaps, pcm16=pcm16, **kw)
             start = [int(p) for p in pos]
@@ -151,4 +164,7 @@ def synthesize_long(tts, text, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20,
     if loudness is not None:
         for i, s in enumerate(segments):
             s["lufs"], s["gain"] = lufs[i], gain[i]
+    if lim:
+        for i, s in enumerate(segments):
+            s["min_gain"] = float(min_gain[i])
     return wav, segments

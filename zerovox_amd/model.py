@@ -105,6 +105,7 @@ class ZeroVox:
         self._streaming = False                         # a synthesize_batches generator is live: self._ctx belongs to its worker threads
         self._min_mel_len = 689                         # model.py:254 -- stateful, see inference_ex
         self.last_loudness = None                       # dict(lufs, peak, gain) of the last inference_ex(..., loudness=...) call
+        self.last_limit = None                          # dict(peak_in, min_gain) of the last inference_ex(..., limiter=...) call
         self.hidden = self._ctx.hidden
 
     @property
@@ -133,12 +134,13 @@ class ZeroVox:
         lens = np.full(x.shape[0], x.shape[1], np.int32)
         return self._ctx.spkemb(x, lens)[:, None, :]
 
-    def inference_ex(self, x, style_embed, normalize_before=True, force_duration=False, prosody=None, loudness=None):
+    def inference_ex(self, x, style_embed, normalize_before=True, force_duration=False, prosody=None, loudness=None, limiter=None):
         """model.py:308-347.  x = {"phoneme" [1,T], "puncts" [1,T], "duration" [1,T]|None}; returns
         (wav[:mel_len*hop], mel_len, log_duration [1,T], mel [n_mels, mel_len]).  Batch-1 like the reference.
         Under an output_rate the waveform holds resampled_len(mel_len*hop) samples of that rate; mel_len stays in frames.
         prosody: None, a prosody.Prosody or a dict of Prosody.create keywords (speed, pitch / energy shift and range, targets).
-        loudness: None (the path above, untouched) or Context.normalize_device keywords (target, peak_ceiling, max_gain_db)."""
+        loudness: None (the path above, untouched) or Context.normalize_device keywords (target, peak_ceiling, max_gain_db).
+        limiter: None (likewise) or Context.limit_device keywords (ceiling, window_ms, oversample); it runs behind the loudness gain."""
         phoneme = np.asarray(x["phoneme"], np.int32)
         puncts = np.asarray(x["puncts"], np.int32)
         if phoneme.ndim != 2 or phoneme.shape[0] != 1:
@@ -155,16 +157,17 @@ class ZeroVox:
         pad_to = self._min_mel_len                       # model.py:331-335: pad up, or raise the floor
         if ml > self._min_mel_len:
             self._min_mel_len = ml
-        if loudness is not None:
-            wav = self._vocode_normalized(mel_len, pad_to, loudness)
+        if loudness is not None or limiter is not None:
+            wav = self._vocode_normalized(mel_len, pad_to, loudness, limiter)
             return wav, ml, logd, np.ascontiguousarray(mel[0, :ml].T)
         wav = self._ctx.vocode(1, mel_len, np.array([pad_to], np.int32))
         return wav[0, : self._ctx.out_samples(ml * self._hop_length)], ml, logd, np.ascontiguousarray(mel[0, :ml].T)
 
-    def _vocode_normalized(self, mel_len, pad_to, loudness):
+    def _vocode_normalized(self, mel_len, pad_to, loudness, limiter=None):
         """The vocoder writes its row on the device at the model's rate, zvx_normalize brings it to loudness["target"] in place (queued
-        behind the vocoder: stream order is the fence), an output rate converts it, and only then the row comes to the host.
-        self.last_loudness reports dict(lufs, peak, gain)."""
+        behind the vocoder: stream order is the fence), zvx_limit holds it under limiter["ceiling"] in place, an output rate converts it,
+        and only then the row comes to the host.  Either step may be absent.  self.last_loudness reports dict(lufs, peak, gain),
+        self.last_limit dict(peak_in, min_gain)."""
         ctx = self._ctx
         n = int(mel_len[0]) * self._hop_length
         native = ctx.get_int("sampling_rate")
@@ -172,8 +175,12 @@ class ZeroVox:
         buf = ctx.dev_alloc(n * 4)
         try:
             ctx.vocode_device(mel_len, np.array([pad_to], np.int32), buf, n, native_rate=True, no_sync=True)
-            lufs, peak, gain = ctx.normalize_device(buf, [n], n, rate=native, **loudness)
-            self.last_loudness = dict(lufs=float(lufs[0]), peak=float(peak[0]), gain=float(gain[0]))
+            if loudness is not None:
+                lufs, peak, gain = ctx.normalize_device(buf, [n], n, rate=native, **loudness)
+                self.last_loudness = dict(lufs=float(lufs[0]), peak=float(peak[0]), gain=float(gain[0]))
+            if limiter is not None:
+                peak_in, min_gain = ctx.limit_device(buf, [n], n, rate=native, **limiter)
+                self.last_limit = dict(peak_in=float(peak_in[0]), min_gain=float(min_gain[0]))
             return ctx.dev_to_host(buf, (n,), np.float32) if out_rate == native else ctx.resample_device(buf, n, native, out_rate)
         finally:
             try:

@@ -145,15 +145,25 @@ class ZeroVoxTTS:
         from .longform import peak_ceiling
         return None if loudness is None else dict(target=float(loudness), peak_ceiling=peak_ceiling(peak_db))
 
+    @staticmethod
+    def _limiter(limiter, limiter_ms, peak_db):
+        """the limiter keywords as Context.limit_device keywords, or None (nothing is limited)"""
+        from .longform import limit_keywords
+        return limit_keywords(limiter, limiter_ms, peak_db)
+
     def tts_ex(self, text: str, spkemb, duration=None, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0,
-               loudness=None, peak_db=-1.0):
+               loudness=None, peak_db=-1.0, limiter=False, limiter_ms=5.0):
         """-> (wav f32[N], phoneme i32[1,T], length, mel f32[n_mels, L]); empty text -> the reference's sentinel
         (synthesize.py:213-239).  Prosody (include/zvx.h, zvx_prosody): speed = speaking-rate factor (2.0: half the frames),
         pitch / energy shift (in normalised predictor units) and range (spread about the utterance mean).
         loudness: None (the default: the level the model gives), or the integrated loudness in LUFS (BS.1770 / R128) the waveform is
         brought to on the device (include/zvx.h, zvx_normalize): the vocoder's row stays there, is measured and multiplied by one gain in
         place -- at most +20 dB, and no sample above peak_db dBFS (None: no ceiling) --, an ``output_rate`` converts it afterwards (the
-        ceiling applies before that conversion) and only then it comes to the host; ``last_loudness`` reports dict(lufs, peak, gain)."""
+        ceiling applies before that conversion) and only then it comes to the host; ``last_loudness`` reports dict(lufs, peak, gain).
+        limiter: with True a look-ahead limiter (include/zvx.h, zvx_limit) holds the row under peak_db dBFS on the device, its gain
+        smoothed over limiter_ms on either side and driven by the 4x oversampled (true-peak) envelope.  With ``loudness`` the gain is
+        then NOT bounded by the peak (only by +20 dB), so the target is reached and the limiter takes the peaks; without it the row is
+        just limited.  Order: gain, limiter, output-rate conversion, copy to the host.  ``last_limit`` reports dict(peak_in, min_gain)."""
         prosody = self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range)
         text = text.strip()
         t0 = time.time()
@@ -167,16 +177,32 @@ class ZeroVoxTTS:
         t1 = time.time()
         wav, length, _, mel = self._model.inference_ex({"phoneme": phoneme, "puncts": puncts, "duration": duration},
                                                        style_embed=spkemb, force_duration=duration is not None, prosody=prosody,
-                                                       **({} if loudness is None else dict(loudness=self._loudness(loudness, peak_db))))
+                                                       **self._post(loudness, peak_db, limiter, limiter_ms))
         if self._verbose:
             print(f"tts timing stats: g2p={t1 - t0}s, synth={time.time() - t1}s")
         return wav, phoneme, length, mel
 
+    def _post(self, loudness, peak_db, limiter, limiter_ms):
+        """the inference_ex keywords of the loudness / limiter steps ({}: neither, the plain path)"""
+        lim = self._limiter(limiter, limiter_ms, peak_db)
+        kw = {}
+        if loudness is not None:
+            kw["loudness"] = self._loudness(loudness, None if lim else peak_db)      # under a limiter the gain has no peak ceiling
+        if lim:
+            kw["limiter"] = lim
+        return kw
+
     def tts(self, text: str, spkemb, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0, loudness=None,
-            peak_db=-1.0):
+            peak_db=-1.0, limiter=False, limiter_ms=5.0):
         wav, phoneme, length, _ = self.tts_ex(text=text, spkemb=spkemb, speed=speed, pitch_shift=pitch_shift, pitch_range=pitch_range,
-                                              energy_shift=energy_shift, energy_range=energy_range, loudness=loudness, peak_db=peak_db)
+                                              energy_shift=energy_shift, energy_range=energy_range, loudness=loudness, peak_db=peak_db,
+                                              limiter=limiter, limiter_ms=limiter_ms)
         return wav, phoneme, length
+
+    @property
+    def last_limit(self):
+        """dict(peak_in, min_gain) of the last tts / tts_ex call that ran the limiter (None before the first)"""
+        return self._model.last_limit
 
     @property
     def last_loudness(self):
@@ -184,13 +210,16 @@ class ZeroVoxTTS:
         return self._model.last_loudness
 
     def tts_stream(self, text: str, spkemb, chunk_frames=64, chunks_per_call=1, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0,
-                   energy_shift=0.0, energy_range=1.0, loudness=None):
+                   energy_shift=0.0, energy_range=1.0, loudness=None, limiter=False):
         """Streaming variant of ``tts`` (not in the reference): encoder + mel decoder run once, the vocoder
         runs chunk by chunk (16-frame halo), yielding float32 waveform pieces that concatenate to ``tts(text, spkemb)[0]``
         up to the reference's `_min_mel_len` zero-padding of short utterances.  A stream cannot be loudness-normalised: the gain is not
-        known before the last chunk, so ``loudness`` other than None raises ValueError (use tts / tts_long)."""
+        known before the last chunk, so ``loudness`` other than None raises ValueError (use tts / tts_long); so does ``limiter=True``
+        (a windowed limiter is possible -- its support is finite -- but not built)."""
         if loudness is not None:
             raise ValueError("tts_stream cannot normalise loudness: the gain is unknown until the last chunk (use tts or tts_long)")
+        if limiter:
+            raise ValueError("tts_stream has no limiter (use tts or tts_long)")
         return self._tts_stream(text, spkemb, chunk_frames, chunks_per_call, self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range))
 
     def _tts_stream(self, text, spkemb, chunk_frames, chunks_per_call, prosody):
@@ -210,7 +239,7 @@ class ZeroVoxTTS:
 
     def tts_long(self, text: str, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20, fade_ms=5, max_batch=32, max_frames=2048, pcm16=False,
                  durations=None, max_chars=200, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0,
-                 loudness=None, peak_db=-1.0, loudness_mode="paragraph"):
+                 loudness=None, peak_db=-1.0, loudness_mode="paragraph", limiter=False, limiter_ms=5.0):
         """A paragraph -> (wav, segments): one waveform with every sentence in text order (not in the reference).  The text is split by
         longform.split_sentences; the sentences run in batches of at most max_batch, each batch ONE queued synthesize call into
         consecutive rows of one device buffer (every row is the fresh-model ``tts`` of its sentence; a sentence of more than max_frames
@@ -228,12 +257,15 @@ class ZeroVoxTTS:
         +20 dB and leaves no sample above peak_db dBFS (None: no ceiling).  The measurement is at the model's rate, untrimmed, before any
         output-rate conversion: the ceiling applies BEFORE resampling, whose band-limited interpolation may overshoot it -- pcm16
         still clamps what does.  Every segment dict then also carries lufs (the sentence's own measured loudness, -inf where it is
-        shorter than 0.4 s or silent) and gain (the linear factor applied)."""
+        shorter than 0.4 s or silent) and gain (the linear factor applied).
+        limiter: with True ONE zvx_limit over all rows, in place, between the normalise and the join, at peak_db dBFS with a 4x
+        oversampled envelope and limiter_ms of smoothing on either side; the loudness gain then has no peak ceiling (see tts_ex).
+        Every segment dict then also carries min_gain (the limiter's smallest gain in that sentence; 1.0: untouched)."""
         from .longform import synthesize_long
         return synthesize_long(self, text, spkemb, pauses=pauses, trim_db=trim_db, keep_ms=keep_ms, fade_ms=fade_ms, max_batch=max_batch,
                                max_frames=max_frames, pcm16=pcm16, durations=durations, max_chars=max_chars,
                                prosody=self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range),
-                               loudness=loudness, peak_db=peak_db, loudness_mode=loudness_mode)
+                               loudness=loudness, peak_db=peak_db, loudness_mode=loudness_mode, limiter=limiter, limiter_ms=limiter_ms)
 
     @property
     def output_rate(self):
