@@ -52,9 +52,15 @@ enum {                   /* flags */
                             ZVX_DEVICE_OUT | ZVX_NO_SYNC; no host mel / log_duration output), zvx_get_int("host_slot") names the slot
                             and zvx_wait_host(ctx, slot, ...) is where the host meets the rows.  Slots alternate (call i: slot i & 1);
                             a slot's rows stay valid until the second next ZVX_HOST_ASYNC call */
-    ZVX_NATIVE_RATE = 32 /* zvx_vocode / zvx_vocode_mel / zvx_synthesize / zvx_synthesize_ex: this call ignores zvx_set_int("out_rate") and delivers
+    ZVX_NATIVE_RATE = 32,/* zvx_vocode / zvx_vocode_mel / zvx_synthesize / zvx_synthesize_ex: this call ignores zvx_set_int("out_rate") and delivers
                             the generator's own samples at the model's rate (chunked streaming vocodes at the native rate and converts the
                             stream itself, zvx_resample_ex; it is also how a caller gets both) */
+    ZVX_DEVICE_SPK = 64  /* zvx_synthesize / zvx_synthesize_ex only: `spk` is a device pointer on the context's device ([B][hidden] f32, e.g. the
+                            ZVX_DEVICE_OUT | ZVX_NO_SYNC output of zvx_spkemb_wav / zvx_spkemb_ex queued just before).  It is copied device to device
+                            into the call's speaker plane instead of travelling in the pinned input upload, behind everything issued so far on
+                            the context's main stream (an event fences the front stream: no host wait); queued calls stay queued, and the
+                            waveform is bit for bit that of the same floats passed from the host.  The buffer must stay alive until the call
+                            has run (zvx_sync) */
 };
 
 enum {                   /* zvx_stage_times indices (milliseconds, hipEvent-timed on the ctx stream) */
@@ -101,6 +107,45 @@ zvx_status zvx_set_int(zvx_ctx* ctx, const char* key, int64_t value);
 zvx_status zvx_spkemb(zvx_ctx* ctx, const float* ref_mels, const int32_t* lens, int B, int Tmax, float* out);
 /* same with flags: ZVX_DEVICE_IN (ref_mels on the device), ZVX_DEVICE_OUT (out on the device), ZVX_NO_SYNC */
 zvx_status zvx_spkemb_ex(zvx_ctx* ctx, const float* ref_mels, const int32_t* lens, int B, int Tmax, float* out, int flags);
+
+/* Speaker enrolment from raw audio, on the device: wav [B][Nmax] f32 with nsamples[b] valid samples at `rate` Hz -> out [B][hidden].
+ * Defined as a composition of the calls of this header, run on the same batch of B rows:
+ *   1. rate: rate == the model's "sampling_rate": the rows as given; otherwise row b is what zvx_resample(rate -> sampling_rate) computes
+ *      for it, a signal of its own length ceil(n L / M), converted into a work buffer of the context (rate checks and ZVX_E_UNSUPPORTED as
+ *      for zvx_resample).  Everything below is in samples at the model's rate.
+ *   2. bounds: [begin, end) is what zvx_trim_bounds defines for (frame, hop, top_db, keep) -- its ambiguity band and its rules for rows
+ *      left whole included.
+ *   3. crop: max_samples > 0: end = min(end, begin + max_samples).
+ *   4. mel: the m = end - begin samples of the window are a signal of their own; the mel is what zvx_melspec computes for it (the reflect
+ *      padding mirrors about the window's own first and last sample and reads nothing outside [begin, end)); frames[b] = 1 + (m + 2 pad -
+ *      n_fft) / hop.
+ *   5. embedding: what zvx_spkemb computes on those mels with lens = frames.
+ * Outside ambiguous trim frames `out` is bit for bit what zvx_resample, zvx_trim_bounds, a slice (and crop), zvx_melspec and zvx_spkemb
+ * hand back for the same B rows: the same kernels in the same launch shapes; the one new launch cuts the reflect-padded windows at bounds
+ * only the device knows.
+ * Host traffic: the audio never goes to the host.  The call waits ONCE, for the bounds (as zvx_join waits for its layout): they give the host
+ * the frame counts that validate the windows and size the GEMMs.  Everything behind that wait is queued on the main stream; with
+ * ZVX_DEVICE_OUT | ZVX_NO_SYNC the call returns once it has queued.  begin / end / frames: host int32 [B], each may be NULL.
+ * Flags: ZVX_DEVICE_IN (wav on the device: the rows may be the output of a synthesis call queued just before, stream order is the fence),
+ *   ZVX_DEVICE_OUT (out on the device), ZVX_NO_SYNC (device out only).
+ * Validation, before anything is queued (ZVX_E_INVALID, the context stays usable): a NULL ctx / wav / nsamples / params / out, B <= 0,
+ *   Nmax <= 0, a negative length, nsamples[b] > Nmax, frame / hop / keep / top_db as for zvx_trim_bounds, max_samples < 0, unknown flags,
+ *   ZVX_NO_SYNC without ZVX_DEVICE_OUT.  After the wait: a window that does not meet zvx_melspec's length conditions or has fewer than the 2
+ *   frames zvx_spkemb needs is ZVX_E_INVALID (the message names the row, its bounds and the minimum); nothing is written to out, begin / end /
+ *   frames are still filled, the context stays usable.
+ * Accounting: stage slot ZVX_T_SPKEMB over the window cut, the front end and the encoder (the front end's launches counted as zvx_melspec's
+ *   are); the conversion and the bounds as zvx_resample (ZVX_T_RESAMPLE) and zvx_trim_bounds (ZVX_T_JOIN, "post.join") count theirs.
+ * Replaces ZeroVoxTTS.speaker_embed (synthesize.py:123-143) for a batch of reference clips: librosa.load(sr=...), librosa.effects.trim,
+ * get_mel_from_wav and ResNetSE34V2.forward without the audio, the mel or the embedding crossing to the host in between. */
+typedef struct zvx_ref_params {
+    int32_t frame, hop;    /* trim analysis window and step in samples at the MODEL's rate (ZeroVoxTTS.speaker_embed: 2048 / 512) */
+    float   top_db;        /* as zvx_join_params.top_db (speaker_embed: 40); <= 0: no trimming */
+    int32_t keep;          /* as zvx_join_params.keep */
+    int32_t max_samples;   /* > 0: the window is cut to its first max_samples samples after trimming; 0: no cut */
+} zvx_ref_params;
+zvx_status zvx_spkemb_wav(zvx_ctx* ctx, const float* wav, const int32_t* nsamples, int B, int Nmax, int rate,
+                          const zvx_ref_params* params, float* out /* [B][hidden] */,
+                          int32_t* begin, int32_t* end, int32_t* frames /* host [B], each may be NULL */, int flags);
 
 /* Log-mel front end of reference audio: wav [B][Nmax] f32 in [-1, 1] with nsamples[b] valid samples ->
  * mel [B][Tmax][n_mels] = log(clip(mel_basis . |STFT|, 1e-5)) (reflect padding (n_fft-hop)/2, hann window, center=False)

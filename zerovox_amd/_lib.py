@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(HERE, "libzvx.so")
 ZVX_OK = 0
 ZVX_E_INVALID, ZVX_E_MANIFEST, ZVX_E_HIP, ZVX_E_STATE, ZVX_E_BUFFER, ZVX_E_UNSUPPORTED = 1, 2, 3, 4, 5, 6
 ZVX_DEVICE_OUT, ZVX_NO_SYNC, ZVX_PCM16, ZVX_DEVICE_IN, ZVX_HOST_ASYNC, ZVX_NATIVE_RATE = 1, 2, 4, 8, 16, 32
+ZVX_DEVICE_SPK = 64                                  # zvx_synthesize / zvx_synthesize_ex: spk is a device pointer
 STAGES = ("encoder", "variance", "lenreg", "decoder", "vocoder", "spkemb")
 ZVX_T_RESAMPLE = 6                                   # its own accessor (Context.resample_ms): stage_times() keeps exactly STAGES
 ZVX_T_JOIN = 7                                       # likewise (Context.join_ms)
@@ -24,7 +25,7 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_comm_unique_id", "zvx_comm_init", "zvx_comm_gather", "zvx_comm_barrier", "zvx_comm_max_f64", "zvx_comm_info", "zvx_comm_destroy",
            "zvx_dev_alloc", "zvx_dev_free", "zvx_dev_from_host", "zvx_dev_to_host", "zvx_spkemb_ex", "zvx_wait_host",
            "zvx_encode_ex", "zvx_synthesize_ex", "zvx_resample", "zvx_resample_ex", "zvx_trim_bounds", "zvx_join",
-           "zvx_loudness", "zvx_normalize", "zvx_true_peak", "zvx_limit")
+           "zvx_loudness", "zvx_normalize", "zvx_true_peak", "zvx_limit", "zvx_spkemb_wav")
 ZVX_COMM_ID_BYTES = 128
 ZVX_LOUD_PER_ROW, ZVX_LOUD_COMMON = 0, 1
 LIMIT_TILE = 1024                                    # samples per workgroup of both limiter kernels (csrc/zvx_kernels.h, LIMIT_TILE)
@@ -48,6 +49,11 @@ class ZvxError(RuntimeError):
 class JoinParams(C.Structure):
     """zvx_join_params (include/zvx.h)"""
     _fields_ = [("frame", C.c_int32), ("hop", C.c_int32), ("top_db", C.c_float), ("keep", C.c_int32), ("fade", C.c_int32)]
+
+
+class RefParams(C.Structure):
+    """zvx_ref_params (include/zvx.h)"""
+    _fields_ = [("frame", C.c_int32), ("hop", C.c_int32), ("top_db", C.c_float), ("keep", C.c_int32), ("max_samples", C.c_int32)]
 
 
 class LoudnessParams(C.Structure):
@@ -125,6 +131,7 @@ def load():
     lib.zvx_normalize.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(LoudnessParams), vp, C.c_int64, vp, vp, vp, C.c_int]
     lib.zvx_true_peak.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int]
     lib.zvx_limit.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(LimitParams), vp, C.c_int64, vp, vp, C.c_int]
+    lib.zvx_spkemb_wav.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(RefParams), vp, vp, vp, vp, C.c_int]
     _lib = lib
     return lib
 
@@ -190,6 +197,34 @@ class Context:
         out = np.empty((B, self.hidden), np.float32)
         self._chk(self._lib.zvx_spkemb(self._h, _ptr(ref_mels), _ptr(lens), B, Tmax, _ptr(out)))
         return out
+
+    def spkemb_wav(self, rows, rate=None, *, frame=2048, hop=512, top_db=40.0, keep=0, max_samples=0, lengths=None):
+        """zvx_spkemb_wav on host rows: reference clips at `rate` Hz (None: the model's) -> speaker embeddings, every step on the device:
+        conversion to the model's rate, the silence trim of mels.trim_silence (frame / hop / top_db / keep as for trim_bounds; top_db <= 0:
+        none), a cut to the first max_samples samples of the trimmed clip (0: none), the log-mel front end and the speaker encoder
+        -> (emb [B][hidden] float32, begin [B], end [B], frames [B] int32; the bounds are in samples at the model's rate).
+        rows: a list of 1-D float waveforms, or a padded 2-D array + lengths."""
+        x, n = self._rows(rows, lengths)
+        B, Nmax = x.shape
+        prm = RefParams(int(frame), int(hop), float(top_db), int(keep), int(max_samples))
+        out = np.empty((B, self.hidden), np.float32)
+        begin, end, frames = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+        self._chk(self._lib.zvx_spkemb_wav(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), _ptr(begin), _ptr(end),
+                                           _ptr(frames), 0))
+        return out, begin, end, frames
+
+    def spkemb_wav_device(self, ptr, lengths, Nmax, out_ptr, rate=None, *, frame=2048, hop=512, top_db=40.0, keep=0, max_samples=0, no_sync=False):
+        """zvx_spkemb_wav on device rows [B][Nmax] f32 at `ptr` (ZVX_DEVICE_IN; they may be the output of a synthesize(..., no_sync=True)
+        call queued just before: stream order is the fence) into device embeddings [B][hidden] f32 at out_ptr (ZVX_DEVICE_OUT) -- what
+        synthesize(..., spk=out_ptr) takes.  The call waits once, for the bounds; with no_sync everything behind that wait is only queued.
+        -> (begin, end, frames)."""
+        n = _i32(lengths)
+        B = len(n)
+        prm = RefParams(int(frame), int(hop), float(top_db), int(keep), int(max_samples))
+        begin, end, frames = np.zeros(B, np.int32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+        self._chk(self._lib.zvx_spkemb_wav(self._h, C.c_void_p(int(ptr)), _ptr(n), B, int(Nmax), self._rate(rate), C.byref(prm), C.c_void_p(int(out_ptr)),
+                                           _ptr(begin), _ptr(end), _ptr(frames), ZVX_DEVICE_IN | ZVX_DEVICE_OUT | (ZVX_NO_SYNC if no_sync else 0)))
+        return begin, end, frames
 
     def melspec(self, wavs):
         """list of 1-D float waveforms -> (log-mel [B][Tmax][n_mels], frames [B])   (get_mel_from_wav on the device)"""
@@ -468,6 +503,8 @@ class Context:
         """Batched phoneme -> waveform.  Returns dict(wav [B][N] (None if device output), mel_len, mel, log_duration).
         host_async: the call only queues work and returns dict(..., slot=s); wait_host(s) hands out the waveform rows in the
         context's pinned host memory (ZVX_HOST_ASYNC: forced durations, no mel / log-duration output).
+        spk: [B][hidden] floats, or an int: a device pointer to them (ZVX_DEVICE_SPK, e.g. what spkemb_wav_device wrote; the copy is
+        ordered behind everything queued so far on the context).
         With a device waveform (wav_device_ptr) the mel, if wanted, is a device buffer too (ZVX_DEVICE_OUT covers both outputs):
         mel_device_ptr -> [B][Lmax][n_mels] f32 with Lmax = the longest utterance's forced-duration sum (or Lmax_cap).
         prosody: None, a prosody.Prosody or a dict of Prosody.create keywords (zvx_synthesize_ex); forced durations are then sized
@@ -478,7 +515,11 @@ class Context:
         B, Tmax = phoneme.shape
         puncts = _i32(puncts, (B, Tmax))
         T = _i32(T, (B,))
-        spk = _f32(spk).reshape(B, self.hidden)
+        if isinstance(spk, (int, np.integer)):
+            sptr, sflag = C.c_void_p(int(spk)), ZVX_DEVICE_SPK
+        else:
+            spk = _f32(spk).reshape(B, self.hidden)
+            sptr, sflag = _ptr(spk), 0
         dur = _i32(duration, (B, Tmax)) if duration is not None else None
         pt = _i32(pad_to, (B,)) if pad_to is not None else None
         ps, keep = self._prosody(prosody, B, Tmax)
@@ -492,15 +533,15 @@ class Context:
         if host_async:
             if want_mel or wav_device_ptr is not None:
                 raise ZvxError(ZVX_E_INVALID, "host_async delivers the waveform only (want_mel=False, no device pointer)")
-            args = (self._h, _ptr(phoneme), _ptr(puncts), _ptr(dur), _ptr(T), B, Tmax, _ptr(spk), _ptr(pt), Lmax, None, 0, _ptr(mel_len),
-                    None, max(Lmax, 1), None, ZVX_HOST_ASYNC | (ZVX_PCM16 if pcm16 else 0) | (ZVX_NATIVE_RATE if native_rate else 0))
+            args = (self._h, _ptr(phoneme), _ptr(puncts), _ptr(dur), _ptr(T), B, Tmax, sptr, _ptr(pt), Lmax, None, 0, _ptr(mel_len),
+                    None, max(Lmax, 1), None, ZVX_HOST_ASYNC | (ZVX_PCM16 if pcm16 else 0) | (ZVX_NATIVE_RATE if native_rate else 0) | sflag)
             self._chk(self._lib.zvx_synthesize(*args) if ps is None else self._lib.zvx_synthesize_ex(*args, C.byref(ps)))
             return dict(wav=None, mel_len=mel_len, mel=None, log_duration=None, slot=self.get_int("host_slot"))
         # a queued call (device output, no_sync) must not ask for host outputs: a copy into pageable memory would wait for the stream
         logd = None if (wav_device_ptr is not None and no_sync) else np.zeros((B, Tmax), np.float32)
         mel = np.zeros((B, max(Lmax, 1), self.n_mels), np.float32) if (want_mel and wav_device_ptr is None) else None
         mptr = _ptr(mel)
-        flags = (ZVX_PCM16 if pcm16 else 0) | (ZVX_NATIVE_RATE if native_rate else 0)
+        flags = (ZVX_PCM16 if pcm16 else 0) | (ZVX_NATIVE_RATE if native_rate else 0) | sflag
         if wav_device_ptr is not None:
             wav, wptr, stride = None, C.c_void_p(int(wav_device_ptr)), int(wav_stride)
             flags |= ZVX_DEVICE_OUT | (ZVX_NO_SYNC if no_sync else 0)
@@ -512,7 +553,7 @@ class Context:
             stride = max(self.out_samples(Lmax * self.hop, native_rate), 1)
             wav = np.zeros((B, stride), np.int16 if pcm16 else np.float32)
             wptr = _ptr(wav)
-        args = (self._h, _ptr(phoneme), _ptr(puncts), _ptr(dur), _ptr(T), B, Tmax, _ptr(spk), _ptr(pt), Lmax, wptr, stride, _ptr(mel_len),
+        args = (self._h, _ptr(phoneme), _ptr(puncts), _ptr(dur), _ptr(T), B, Tmax, sptr, _ptr(pt), Lmax, wptr, stride, _ptr(mel_len),
                 mptr, max(Lmax, 1), _ptr(logd), flags)
         self._chk(self._lib.zvx_synthesize(*args) if ps is None else self._lib.zvx_synthesize_ex(*args, C.byref(ps)))
         return dict(wav=wav, mel_len=mel_len, mel=mel, log_duration=logd)

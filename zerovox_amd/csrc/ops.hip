@@ -1206,6 +1206,48 @@ void launch_reflect_pad(const float* wav, long w_bs, const int* n, float* out, l
     hipLaunchKernelGGL(k_reflect_pad, grid, dim3(256), 0, s, wav, w_bs, n, out, o_bs, pad, out_cols);
 }
 
+// One thread per 16-byte group of the destination row (rows and out_cols are multiples of 4 floats).  Groups wholly inside the window copy 4
+// consecutive source samples; the groups over the mirrored edges and the zero tail are built sample by sample.
+__global__ __launch_bounds__(256) void k_window_pad(const float* wav, long w_bs, const int* bounds, int max_samples, float* out, long o_bs, int pad,
+                                                    int out_cols) {
+    const int b = blockIdx.y, begin = bounds[2 * b];
+    int m = bounds[2 * b + 1] - begin;
+    if (max_samples > 0 && m > max_samples) m = max_samples;
+    if (m <= pad) m = 0;                                      // no mirror exists (refused on the host): zeros, nothing is read
+    const float* src = wav + (long)b * w_bs + begin;
+    float* row = out + (long)b * o_bs;
+    const long total = m > 0 ? (long)m + 2 * pad : 0;
+    for (long i = 4L * (blockIdx.x * blockDim.x + threadIdx.x); i < out_cols; i += 4L * gridDim.x * blockDim.x) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (i >= pad && i + 4 <= (long)pad + m) {
+            const float* p = src + (i - pad);
+            if (((size_t)p & 15) == 0) v = *(const float4*)p;
+            else { v.x = p[0]; v.y = p[1]; v.z = p[2]; v.w = p[3]; }
+        } else if (i < total) {
+            float r[4];
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                r[e] = 0.f;
+                if (i + e < total) {
+                    long k = i + e - pad;
+                    if (k < 0) k = -k;
+                    if (k >= m) k = 2L * (m - 1) - k;
+                    r[e] = src[k];
+                }
+            }
+            v = make_float4(r[0], r[1], r[2], r[3]);
+        }
+        *(float4*)(row + i) = v;
+    }
+}
+void launch_window_pad(const float* wav, long w_bs, const int* bounds, int max_samples, float* out, long o_bs, int pad, int B, int out_cols,
+                       hipStream_t s) {
+    if (B <= 0 || out_cols <= 0) return;
+    const int groups = (out_cols + 3) / 4;
+    dim3 grid((groups + 255) / 256 < 1024 ? (groups + 255) / 256 : 1024, B);
+    hipLaunchKernelGGL(k_window_pad, grid, dim3(256), 0, s, wav, w_bs, bounds, max_samples, out, o_bs, pad, out_cols);
+}
+
 __global__ void k_stft_mag(const float* spec, int lds_, float* mag, int ldm, int nf, int Tmax, const int* frames) {
     const int b = blockIdx.z, t = blockIdx.y;
     const bool live = t < frames[b];

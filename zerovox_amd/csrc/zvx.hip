@@ -929,7 +929,7 @@ void check_prosody(const zvx_prosody* p, const int32_t* T, int B, int Tmax) {
 }
 
 void run_encode(zvx_ctx* c, const int32_t* phoneme, const int32_t* puncts, const int32_t* duration, const int32_t* T,
-                int B, int Tmax, const float* spk, int32_t* mel_len_out, int Lmax_cap, const zvx_prosody* pros = nullptr) {
+                int B, int Tmax, const float* spk, int32_t* mel_len_out, int Lmax_cap, const zvx_prosody* pros = nullptr, bool spk_dev = false) {
     const int H = c->H;
     c->have_features = false; c->have_mel = false;
     if (c->stream != c->front_stream) c->front_dirty_main = true;
@@ -967,7 +967,7 @@ void run_encode(zvx_ctx* c, const int32_t* phoneme, const int32_t* puncts, const
         memcpy(hs, phoneme, nid * 4); memcpy(hs + st, puncts, nid * 4);
         if (duration) memcpy(hs + 2 * st, duration, nid * 4);
         memcpy(hs + 3 * st, T, (size_t)B * 4);
-        memcpy(hs + 4 * st, spk, (size_t)B * H * 4);
+        if (!spk_dev) memcpy(hs + 4 * st, spk, (size_t)B * H * 4);
         if (pros) {
             const float* per_utt[4] = {pros->pitch_shift, pros->pitch_range, pros->energy_shift, pros->energy_range};
             for (int i = 0; i < 4; i++) if (per_utt[i]) memcpy(hs + 5 * st + (size_t)i * B, per_utt[i], (size_t)B * 4);
@@ -979,6 +979,8 @@ void run_encode(zvx_ctx* c, const int32_t* phoneme, const int32_t* puncts, const
     int* dur_in = duration ? (int*)(in_base + 2 * in_stride) : nullptr;
     int* T_d = (int*)(in_base + 3 * in_stride);
     float* spk_d = (float*)(in_base + 4 * in_stride);
+    // ZVX_DEVICE_SPK: the embeddings are on the device already -- into their plane behind the upload, in stream order
+    if (spk_dev) HIPCHK(hipMemcpyAsync(spk_d, spk, (size_t)B * H * 4, hipMemcpyDeviceToDevice, c->stream));
     // device views of the controls (NULL: neutral)
     const float* pros_utt = pros ? (const float*)(in_base + 5 * in_stride) : nullptr;
     const float* p_shift = (pros && pros->pitch_shift) ? pros_utt : nullptr;
@@ -1727,14 +1729,11 @@ void run_vocoder(zvx_ctx* c, const float* mel, int ldm, int Lmel_max, const int*
 // ------------------------------------------------------------------------------------------------
 // speaker encoder (ResNetSE34V2.py:176-212)
 // ------------------------------------------------------------------------------------------------
-void run_spkemb(zvx_ctx* c, const float* ref_mels, const int32_t* lens, int B, int Tmax, float* out, int flags) {
+// The encoder behind the mels: mels_d [B][Tmax][n_mels] f32 on the device, lens[b] in 2..Tmax (checked by the caller) -> "spk.emb" [B][hidden],
+// queued on the context's stream.  Shared by zvx_spkemb / zvx_spkemb_ex (run_spkemb) and zvx_spkemb_wav.
+float* spkemb_from_mels(zvx_ctx* c, const float* mels_d, const int32_t* lens, int B, int Tmax) {
     const int dt = c->dt, F0 = c->n_mels, H = c->H;
     const size_t es = c->es();
-    for (int b = 0; b < B; b++) if (lens[b] < 2 || lens[b] > Tmax) fail(ZVX_E_INVALID, "ref mel length %d out of range (2..%d)", lens[b], Tmax);
-    c->stage_begin(ZVX_T_SPKEMB);
-    c->tag = "spkemb";
-    float* mels_d = c->fbuf("spk.mels", (size_t)B * Tmax * F0);
-    HIPCHK(hipMemcpyAsync(mels_d, ref_mels, (size_t)B * Tmax * F0 * 4, (flags & ZVX_DEVICE_IN) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     // widths per resolution level: w0 = T, w_{l+1} = (w_l - 1)/2 + 1  (3x3 stride-2 pad-1 conv)
     std::vector<int> W(4 * (size_t)B);
     int Wmax[4] = {Tmax, 0, 0, 0};
@@ -1863,6 +1862,17 @@ void run_spkemb(zvx_ctx* c, const float* ref_mels, const int32_t* lens, int B, i
     // Linear(PD -> hidden): a few rows against a 5120-long K -- one wave per output column      ResNetSE34V2.py:207
     launch_fc_rows(pooled, PD, (const float*)c->t("spk.fc_w").dev, PD, c->pf("spk.fc_b"), emb, H, B, H, PD, c->stream);
     launch_l2norm_rows(emb, B, H, c->stream);                                  // F.normalize   :209-210
+    return emb;
+}
+
+void run_spkemb(zvx_ctx* c, const float* ref_mels, const int32_t* lens, int B, int Tmax, float* out, int flags) {
+    const int F0 = c->n_mels, H = c->H;
+    for (int b = 0; b < B; b++) if (lens[b] < 2 || lens[b] > Tmax) fail(ZVX_E_INVALID, "ref mel length %d out of range (2..%d)", lens[b], Tmax);
+    c->stage_begin(ZVX_T_SPKEMB);
+    c->tag = "spkemb";
+    float* mels_d = c->fbuf("spk.mels", (size_t)B * Tmax * F0);
+    HIPCHK(hipMemcpyAsync(mels_d, ref_mels, (size_t)B * Tmax * F0 * 4, (flags & ZVX_DEVICE_IN) ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
+    const float* emb = spkemb_from_mels(c, mels_d, lens, B, Tmax);
     c->stage_end(ZVX_T_SPKEMB);
     HIPCHK(hipMemcpyAsync(out, emb, (size_t)B * H * 4, (flags & ZVX_DEVICE_OUT) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
     if (!((flags & ZVX_DEVICE_OUT) && (flags & ZVX_NO_SYNC))) c->sync();
@@ -1881,28 +1891,12 @@ void copy_out_rows(zvx_ctx* c, const float* src, int rows_max, int C, float* dst
 // reflect pad -> |STFT| as a GEMM against the windowed DFT basis (rows = hop-strided frames of the padded signal)
 // -> mel basis GEMM -> log(clip(., 1e-5))
 // ------------------------------------------------------------------------------------------------
-void run_melspec(zvx_ctx* c, const float* wav, const int32_t* nsamples, int B, int Nmax, float* mel_out, int Tmax, int32_t* frames_out) {
+// The front end behind the padding: padded [B][Npad] f32 (row b: its reflect-padded signal, then zeros), fr_d[b] frames on the device, Tf = the
+// most frames of a row -> "mel.out" [B][Tf][n_mels], queued on the context's stream.  Shared by zvx_melspec (run_melspec) and zvx_spkemb_wav.
+float* mel_from_padded(zvx_ctx* c, const float* padded, long Npad, const int* fr_d, int B, int Tf) {
     const Tensor& dft = c->t("mel.dft");
     const Tensor& basis = c->t("mel.basis");
     const int n_fft = dft.dim(2), NR = dft.dim(1), KP = basis.dim(2), nf = n_fft / 2 + 1, nm = c->n_mels, hop = c->hop;
-    const int pad = (n_fft - hop) / 2;
-    std::vector<int> frames(B);
-    int Tf = 0;
-    for (int b = 0; b < B; b++) {
-        const int n = nsamples[b];
-        if (n > Nmax || n < pad + 1 || n + 2 * pad < n_fft) fail(ZVX_E_INVALID, "zvx_melspec: utterance %d has %d samples (need %d..%d)", b, n, std::max(pad + 1, n_fft - 2 * pad), Nmax);
-        frames[b] = 1 + (n + 2 * pad - n_fft) / hop;
-        Tf = std::max(Tf, frames[b]);
-    }
-    if (Tf > Tmax) fail(ZVX_E_BUFFER, "zvx_melspec: %d frames do not fit Tmax = %d", Tf, Tmax);
-    c->stage_begin(ZVX_T_SPKEMB);
-    const long Npad = ((long)Nmax + 2 * pad + 3) & ~3L;
-    float* wav_d = c->fbuf("mel.wav", (size_t)B * Nmax);
-    HIPCHK(hipMemcpyAsync(wav_d, wav, (size_t)B * Nmax * 4, hipMemcpyHostToDevice, c->stream));
-    int* n_d = c->upload_ints("mel.n", nsamples, B);
-    int* fr_d = c->upload_ints("mel.frames", frames.data(), B);
-    float* padded = c->fbuf("mel.pad", (size_t)B * Npad);
-    launch_reflect_pad(wav_d, Nmax, n_d, padded, Npad, pad, B, (int)Npad, c->stream);
     float* spec = c->fbuf("mel.spec", (size_t)B * Tf * NR);
     {
         GemmArgs a = gemm_base(DT_F32);
@@ -1922,6 +1916,30 @@ void run_melspec(zvx_ctx* c, const float* wav, const int32_t* nsamples, int B, i
         c->gemm(a);
     }
     launch_log_clip(mel_d, nm, nm, 1e-5f, B, Tf, fr_d, c->stream);
+    return mel_d;
+}
+
+void run_melspec(zvx_ctx* c, const float* wav, const int32_t* nsamples, int B, int Nmax, float* mel_out, int Tmax, int32_t* frames_out) {
+    const int n_fft = c->t("mel.dft").dim(2), nm = c->n_mels, hop = c->hop;
+    const int pad = (n_fft - hop) / 2;
+    std::vector<int> frames(B);
+    int Tf = 0;
+    for (int b = 0; b < B; b++) {
+        const int n = nsamples[b];
+        if (n > Nmax || n < pad + 1 || n + 2 * pad < n_fft) fail(ZVX_E_INVALID, "zvx_melspec: utterance %d has %d samples (need %d..%d)", b, n, std::max(pad + 1, n_fft - 2 * pad), Nmax);
+        frames[b] = 1 + (n + 2 * pad - n_fft) / hop;
+        Tf = std::max(Tf, frames[b]);
+    }
+    if (Tf > Tmax) fail(ZVX_E_BUFFER, "zvx_melspec: %d frames do not fit Tmax = %d", Tf, Tmax);
+    c->stage_begin(ZVX_T_SPKEMB);
+    const long Npad = ((long)Nmax + 2 * pad + 3) & ~3L;
+    float* wav_d = c->fbuf("mel.wav", (size_t)B * Nmax);
+    HIPCHK(hipMemcpyAsync(wav_d, wav, (size_t)B * Nmax * 4, hipMemcpyHostToDevice, c->stream));
+    int* n_d = c->upload_ints("mel.n", nsamples, B);
+    int* fr_d = c->upload_ints("mel.frames", frames.data(), B);
+    float* padded = c->fbuf("mel.pad", (size_t)B * Npad);
+    launch_reflect_pad(wav_d, Nmax, n_d, padded, Npad, pad, B, (int)Npad, c->stream);
+    float* mel_d = mel_from_padded(c, padded, Npad, fr_d, B, Tf);
     c->stage_end(ZVX_T_SPKEMB);
     if (mel_out) {
         if (Tmax > Tf) memset(mel_out, 0, (size_t)B * Tmax * nm * 4);
@@ -2202,6 +2220,92 @@ void do_join(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nm
     c->sync();
     if (!fits) fail(ZVX_E_BUFFER, "zvx_join: the joined row has %lld samples, out_capacity is %lld", (long long)total, (long long)out_capacity);
     if (host_out && total > 0) memcpy(out, host + lay_pad, (size_t)total * ss);
+}
+
+// ------------------------------------------------------------------------------------------------
+// speaker enrolment from raw audio (include/zvx.h: zvx_spkemb_wav): resample -> trim bounds -> [the call's one wait] -> window cut with
+// reflect padding -> log-mel -> speaker encoder.  Every step but the window cut is the launch sequence of the entry point that defines it.
+// ------------------------------------------------------------------------------------------------
+void do_spkemb_wav(zvx_ctx* c, const float* wav, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_ref_params* p, float* out,
+                   int32_t* begin, int32_t* end, int32_t* frames_out, int flags) {
+    if (!out) fail(ZVX_E_INVALID, "zvx_spkemb_wav: out is NULL");
+    zvx_join_params jp{};
+    if (p) { jp.frame = p->frame; jp.hop = p->hop; jp.top_db = p->top_db; jp.keep = p->keep; }
+    join_check("zvx_spkemb_wav", wav, nsamples, B, Nmax, nullptr, p ? &jp : nullptr);
+    if (p->max_samples < 0) fail(ZVX_E_INVALID, "zvx_spkemb_wav: max_samples %d must not be negative", p->max_samples);
+    if (flags & ~(ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC)) fail(ZVX_E_INVALID, "zvx_spkemb_wav: unknown flag in %d", flags);
+    if ((flags & ZVX_NO_SYNC) && !(flags & ZVX_DEVICE_OUT)) fail(ZVX_E_INVALID, "zvx_spkemb_wav: ZVX_NO_SYNC needs ZVX_DEVICE_OUT");
+    const int native = model_rate(c);
+    int L = 1, M = 1;
+    rs_pair(rate, native, &L, &M);
+    const int n_fft = c->t("mel.dft").dim(2), hop = c->hop, pad = (n_fft - hop) / 2, H = c->H;
+    // 1. the rows at the model's rate: as given, or each converted as a signal of its own length into a work buffer
+    const float* rows = wav; long rows_bs = Nmax;
+    if (!(flags & ZVX_DEVICE_IN)) {
+        float* xd = c->fbuf("ref.in", (size_t)B * Nmax);
+        HIPCHK(hipMemcpyAsync(xd, wav, (size_t)B * Nmax * 4, hipMemcpyHostToDevice, c->stream));
+        rows = xd;
+    }
+    std::vector<int> n(nsamples, nsamples + B);
+    if (rate != native) {
+        long out_max = 0; double nin = 0, nout = 0;
+        for (int b = 0; b < B; b++) {
+            const long cnt = rs_out_len(nsamples[b], L, M);
+            if (cnt > INT32_MAX - 8) fail(ZVX_E_INVALID, "zvx_spkemb_wav: row %d has %ld samples at the model's rate", b, cnt);
+            n[b] = (int)cnt; out_max = std::max(out_max, cnt); nin += nsamples[b]; nout += (double)cnt;
+        }
+        const zvx_ctx::RsBank& bk = rs_bank(c, L, M);
+        const int* len_d = c->upload_ints("rs.len", nsamples, B);
+        const long ostride = (std::max(out_max, 1L) + 7) & ~7L;
+        float* conv = c->fbuf("ref.rs", (size_t)B * ostride);
+        run_resample(c, bk, rows, rows_bs, len_d, 1, B, conv, ostride, 0, 0, 0, -1, out_max, nin, nout);
+        rows = conv; rows_bs = ostride;
+    }
+    // 2. the bounds, and the call's one wait
+    int* host = (int*)c->join_pinned((size_t)2 * B * sizeof(int));
+    {
+        JoinTimer t(c);
+        double read = 0;
+        join_bounds(c, rows, n.data(), B, (int)rows_bs, &jp, ZVX_DEVICE_IN, &read);
+        t.stop();
+        HIPCHK(hipMemcpyAsync(host, c->ibuf("join.bounds", 0), (size_t)2 * B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+        t.commit(read * 4.0);
+    }
+    // 3. / 4. crop, frame counts, and what zvx_melspec / zvx_spkemb ask of a signal
+    std::vector<int> frames(B);
+    int Mmax = 0, Tf = 0, bad = -1;
+    const int m_min = std::max(std::max(pad + 1, n_fft - 2 * pad), n_fft - 2 * pad + hop);      // melspec's conditions, and 2 frames
+    for (int b = 0; b < B; b++) {
+        const int bg = host[2 * b];
+        int en = host[2 * b + 1];
+        if (p->max_samples > 0 && en - bg > p->max_samples) en = bg + p->max_samples;
+        const int m = en - bg;
+        frames[b] = m + 2 * pad >= n_fft ? 1 + (m + 2 * pad - n_fft) / hop : 0;
+        if (begin) begin[b] = bg;
+        if (end) end[b] = en;
+        if (frames_out) frames_out[b] = frames[b];
+        if (bad < 0 && (m < pad + 1 || frames[b] < 2)) bad = b;
+        Mmax = std::max(Mmax, m); Tf = std::max(Tf, frames[b]);
+    }
+    if (bad >= 0) {
+        const int bg = host[2 * bad], en = std::min(host[2 * bad + 1], p->max_samples > 0 ? bg + p->max_samples : INT32_MAX);
+        c->sync();
+        fail(ZVX_E_INVALID, "zvx_spkemb_wav: row %d is left with samples [%d, %d) of %d at the model's rate: %d, the speaker encoder needs at least %d",
+             bad, bg, en, n[bad], en - bg, m_min);
+    }
+    // 5. everything behind the wait is queued: the window cut, the front end, the encoder, the copy of the result
+    c->stage_begin(ZVX_T_SPKEMB);
+    const long Npad = ((long)Mmax + 2 * pad + 3) & ~3L;
+    int* fr_d = c->upload_ints("mel.frames", frames.data(), B);
+    float* padded = c->fbuf("mel.pad", (size_t)B * Npad);
+    launch_window_pad(rows, rows_bs, c->ibuf("join.bounds", 0), p->max_samples, padded, Npad, pad, B, (int)Npad, c->stream);
+    const float* mel_d = mel_from_padded(c, padded, Npad, fr_d, B, Tf);
+    c->tag = "spkemb";
+    const float* emb = spkemb_from_mels(c, mel_d, frames.data(), B, Tf);
+    c->stage_end(ZVX_T_SPKEMB);
+    HIPCHK(hipMemcpyAsync(out, emb, (size_t)B * H * 4, (flags & ZVX_DEVICE_OUT) ? hipMemcpyDeviceToDevice : hipMemcpyDeviceToHost, c->stream));
+    if (!((flags & ZVX_DEVICE_OUT) && (flags & ZVX_NO_SYNC))) c->sync();
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2694,6 +2798,11 @@ zvx_status zvx_melspec(zvx_ctx* c, const float* wav, const int32_t* nsamples, in
     });
 }
 
+zvx_status zvx_spkemb_wav(zvx_ctx* c, const float* wav, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_ref_params* params, float* out,
+                          int32_t* begin, int32_t* end, int32_t* frames, int flags) {
+    return guarded(c, [&] { do_spkemb_wav(c, wav, nsamples, B, Nmax, rate, params, out, begin, end, frames, flags); });
+}
+
 zvx_status zvx_encode(zvx_ctx* c, const int32_t* phoneme, const int32_t* puncts, const int32_t* duration, const int32_t* T,
                       int B, int Tmax, const float* spk, int32_t* mel_len, float* log_duration, float* pitch, float* energy) {
     return zvx_encode_ex(c, phoneme, puncts, duration, T, B, Tmax, spk, mel_len, log_duration, pitch, energy, nullptr);
@@ -2822,7 +2931,7 @@ zvx_status zvx_synthesize_ex(zvx_ctx* c, const int32_t* phoneme, const int32_t* 
         if (!phoneme || !puncts || !T || !spk || (!wav && !host_async)) fail(ZVX_E_INVALID, "zvx_synthesize: NULL input");
         if (host_async && ((mel_out && !(flags & ZVX_DEVICE_OUT)) || log_duration)) fail(ZVX_E_INVALID, "zvx_synthesize: ZVX_HOST_ASYNC takes no host mel / log_duration output (they would make the call wait)");
         auto front_end = [&] {
-            run_encode(c, phoneme, puncts, duration, T, B, Tmax, spk, mel_len, Lmax_cap, prosody);
+            run_encode(c, phoneme, puncts, duration, T, B, Tmax, spk, mel_len, Lmax_cap, prosody, flags & ZVX_DEVICE_SPK);
             if (log_duration) HIPCHK(hipMemcpyAsync(log_duration, c->fbuf("va.logd", 0), (size_t)B * Tmax * 4, hipMemcpyDeviceToHost, c->stream));
             int* L_d = c->upload_ints("dec.L", c->mel_len_host.data(), B);
             run_decode(c, c->fbuf("features", 0), c->fbuf("in.spk", 0), L_d, B, c->Lmax);
@@ -2835,6 +2944,8 @@ zvx_status zvx_synthesize_ex(zvx_ctx* c, const int32_t* phoneme, const int32_t* 
             // front-end buffers on the main stream, (2) the previous vocoder's read of the mel buffer -- and NOT behind that vocoder
             c->front_setup();
             hipStream_t const main_stream = c->stream;
+            // (3) with ZVX_DEVICE_SPK, whatever wrote the embeddings on the main stream: the same join, an event and no host wait
+            if (flags & ZVX_DEVICE_SPK) c->front_dirty_main = true;
             if (c->front_dirty_main) {
                 HIPCHK(hipEventRecord(c->ev_main_join, main_stream));
                 HIPCHK(hipStreamWaitEvent(c->front_stream, c->ev_main_join, 0));

@@ -465,6 +465,14 @@ void launch_l2norm_rows(float* x, int B, int C, hipStream_t s);
 // ---- log-mel front end (mels.py:357-395) ----
 // out[b][i] = wav[b][reflect(i - pad)] for i < n[b] + 2*pad (numpy 'reflect': no edge repeat), 0 beyond
 void launch_reflect_pad(const float* wav, long w_bs, const int* n, float* out, long o_bs, int pad, int B, int out_cols, hipStream_t s);
+// The same for a WINDOW of each row that only the device knows (include/zvx.h, zvx_spkemb_wav): with begin = bounds[2 b], end = bounds[2 b + 1]
+// (as launch_join_bounds leaves them), cut to end = min(end, begin + max_samples) where max_samples > 0, and m = end - begin,
+// out[b][i] = wav[b][begin + reflect(i - pad)] for i < m + 2 pad with the mirror about the window's own samples 0 and m - 1, 0 for
+// m + 2 pad <= i < out_cols; nothing outside [begin, end) is read.  out rows are 16-byte aligned (o_bs % 4 == 0, out_cols % 4 == 0) and
+// written as 16-byte groups; the source may start at any alignment: a group inside the window is one 16-byte load where its ADDRESS
+// allows, four scalar loads otherwise.  A window of m <= pad samples (the host refuses it before the launch) is written as zeros.
+void launch_window_pad(const float* wav, long w_bs, const int* bounds, int max_samples, float* out, long o_bs, int pad, int B, int out_cols,
+                       hipStream_t s);
 // mag[b][t][f] = sqrt(re^2 + im^2), re = spec[b][t][f], im = spec[b][t][nf + f]; columns [nf, ldm) and rows >= frames[b] -> 0
 void launch_stft_mag(const float* spec, int lds_, float* mag, int ldm, int nf, int B, int Tmax, const int* frames, hipStream_t s);
 // x[b][t][c] = log(max(x, lo)) for t < frames[b], 0 beyond

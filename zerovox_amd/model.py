@@ -293,7 +293,8 @@ class ZeroVox:
     def synthesize_batch(self, phoneme, puncts, T, style_embed, duration=None, pad_to=None, want_mel=True, Lmax_cap=0, prosody=None):
         """B independent utterances in one launch sequence; each equals a batch-1 ``inference_ex`` call with
         ``_min_mel_len == pad_to[b]`` (default: the fresh-model value 689).  Padded [B, Tmax] id arrays.  prosody: as for inference_ex,
-        per utterance ([B] / [B, Tmax] controls)."""
+        per utterance ([B] / [B, Tmax] controls).  style_embed: [B, hidden] floats, or an int -- a device pointer to them, e.g. what
+        Context.spkemb_wav_device wrote (ZVX_DEVICE_SPK)."""
         B = np.asarray(phoneme).shape[0]
         if pad_to is None:
             pad_to = np.full(B, 689, np.int32)

@@ -100,6 +100,35 @@ class ZeroVoxTTS:
         mel, frames = self._model.ctx.melspec([wav])                      # get_mel_from_wav on the device (zvx_melspec)
         return self._model._spkemb(mel[:, :int(frames[0])])
 
+    def speaker_embed_batch(self, wavs, sampling_rate=None, *, top_db=40.0, max_seconds=None):
+        """reference clips -> [B, 1, hidden] speaker embeddings, enrolled on the device (include/zvx.h, zvx_spkemb_wav): conversion to the
+        model's rate, the silence trim of ``speaker_embed`` (top_db; <= 0: none), the log-mel front end and the speaker encoder run there
+        for the whole batch, and only the embeddings come back.  ``sampling_rate``: None (the model's), one rate for all clips, or one per
+        clip; the clips are grouped by rate, one call per distinct rate, and the results come back in input order.  ``max_seconds``: None,
+        or the length each clip is cut to after trimming.  A clip that trims to less than two mel frames raises ZvxError, as
+        ``speaker_embed`` does for it."""
+        wavs = [np.asarray(w, np.float32).reshape(-1) for w in wavs]
+        B = len(wavs)
+        if sampling_rate is None or np.ndim(sampling_rate) == 0:
+            rates = [int(self._sampling_rate if sampling_rate is None else sampling_rate)] * B
+        else:
+            rates = [int(r) for r in sampling_rate]
+            if len(rates) != B:
+                raise ValueError(f"speaker_embed_batch: {B} clips, {len(rates)} sampling rates")
+        cut = 0 if max_seconds is None else max(1, int(round(float(max_seconds) * self._sampling_rate)))
+        ctx = self._model.ctx
+        out = np.zeros((B, 1, ctx.hidden), np.float32)
+        for rate in sorted(set(rates)):
+            idx = [i for i in range(B) if rates[i] == rate]
+            emb = ctx.spkemb_wav([wavs[i] for i in idx], rate, top_db=top_db, max_samples=cut)[0]
+            out[idx, 0, :] = emb
+        return out
+
+    def speaker_embed_files(self, paths):
+        """reference wav files -> [B, 1, hidden]: ``speaker_embed_batch`` over the decoded PCM, every file at its own rate"""
+        clips = [self._read_pcm(p) for p in paths]
+        return self.speaker_embed_batch([a for a, _ in clips], [sr for _, sr in clips])
+
     def speaker_embed_from_mel(self, mel: np.ndarray):
         """[Tr, n_mels] log-mel -> [1, 1, hidden] (precomputed-mel entry used by the benchmarks)."""
         return self._model._spkemb(np.asarray(mel, np.float32)[None])
