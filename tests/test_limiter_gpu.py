@@ -349,7 +349,9 @@ def test_limiter_errors_leave_the_context_usable():
     assert lim(flags=_lib.ZVX_NO_SYNC) == inv
     xf = np.array(x)                                       # a writable copy for the in-place forms
     assert lim(x_=xf, out_=xf, flags=_lib.ZVX_PCM16) == inv
-    assert lim(x_=xf, out_=xf, stride=Nmax + 2) == inv
+    # in place: the stride is Nmax, and both pointers lie on the same side
+    for kw in (dict(stride=Nmax + 2), dict(flags=_lib.ZVX_DEVICE_IN), dict(flags=_lib.ZVX_DEVICE_OUT)):
+        assert lim(x_=xf, out_=xf, **kw) == inv and b"zvx_limit" in lib.zvx_last_error(h), kw
     for c in (nan, inf, -inf, 0.0, -0.5, 8.5):
         assert lim(prm_=params(ceiling=c)) == inv, c
     for ms in (nan, inf, -inf, 0.0, -1.0):

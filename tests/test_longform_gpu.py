@@ -237,6 +237,7 @@ def test_join_errors_leave_the_context_usable():
     assert ctx._lib.zvx_join(ctx._h, vp(x), vp(n), B, Nmax, vp(gaps), C.byref(prm), vp(out), total, None, None, None, None, 0) == inv
     assert ctx._lib.zvx_trim_bounds(ctx._h, vp(x), vp(n), B, Nmax, C.byref(prm), None, None, 0) == inv
     assert raw_bounds(ctx, x, n, Nmax, prm, _lib.ZVX_DEVICE_OUT)[0] == inv
+    assert raw_bounds(ctx, x, n, Nmax, prm, 64)[0] == inv and b"zvx_trim_bounds" in ctx._lib.zvx_last_error(ctx._h)
     rc, out_len = raw_join(ctx, x, n, Nmax, gaps, prm, buf, total)[:2]
     assert rc == 0 and np.array_equal(buf[:total], ref.view(np.uint32))
 

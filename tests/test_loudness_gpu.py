@@ -273,6 +273,9 @@ def test_loudness_errors_leave_the_context_usable():
     assert norm(flags=_lib.ZVX_NO_SYNC) == inv
     xf = np.array(x)                                       # a writable copy for the in-place forms
     assert norm(x_=xf, out_=xf, flags=_lib.ZVX_PCM16) == inv
+    # in place: the stride is Nmax, and both pointers lie on the same side
+    for kw in (dict(stride=Nmax + 2), dict(flags=_lib.ZVX_DEVICE_IN), dict(flags=_lib.ZVX_DEVICE_OUT)):
+        assert norm(x_=xf, out_=xf, **kw) == inv and b"zvx_normalize" in lib.zvx_last_error(h), kw
     for t in (nan, inf, -inf, -70.5, 0.5):
         assert norm(prm_=params(target=t)) == inv, t
     for g in (nan, inf, -0.5):

@@ -170,6 +170,9 @@ def test_errors_leave_the_context_usable():
     assert raw_resample(ctx, x, n, 22050, 48000, out, need - 1) == _lib.ZVX_E_BUFFER
     assert raw_resample(ctx, x, n, 22050, 48000, out, need) == 0
     assert raw_resample(ctx, x, np.array([101], np.int32), 22050, 48000, out, 400) == _lib.ZVX_E_INVALID
+    for fl in (_lib.ZVX_NO_SYNC, 64):                         # ZVX_NO_SYNC without ZVX_DEVICE_OUT; a flag the call does not know
+        assert raw_resample(ctx, x, n, 22050, 48000, out, 400, fl) == _lib.ZVX_E_INVALID, fl
+        assert b"zvx_resample" in ctx._lib.zvx_last_error(ctx._h), fl
     assert ctx.get_int("out_rate") == 0
     ctx.set_int("out_rate", 16000)
     try:

@@ -359,14 +359,11 @@ class Context:
         B = len(n)
         prm = LoudnessParams(float(target), float(peak_ceiling), float(max_gain_db), ZVX_LOUD_COMMON if common else ZVX_LOUD_PER_ROW)
         p = C.c_void_p(int(ptr))
-        if no_sync:
-            self._chk(self._lib.zvx_normalize(self._h, p, _ptr(n), B, int(Nmax), self._rate(rate), C.byref(prm), p, int(Nmax), None, None, None,
-                                              ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC))
-            return None
-        lufs, peak, gain = np.zeros(B, np.float64), np.zeros(B, np.float32), np.zeros(B, np.float32)
+        res = None if no_sync else (np.zeros(B, np.float64), np.zeros(B, np.float32), np.zeros(B, np.float32))      # lufs, peak, gain
+        lufs, peak, gain = res or (None, None, None)
         self._chk(self._lib.zvx_normalize(self._h, p, _ptr(n), B, int(Nmax), self._rate(rate), C.byref(prm), p, int(Nmax), _ptr(lufs), _ptr(peak),
-                                          _ptr(gain), ZVX_DEVICE_IN | ZVX_DEVICE_OUT))
-        return lufs, peak, gain
+                                          _ptr(gain), ZVX_DEVICE_IN | ZVX_DEVICE_OUT | (ZVX_NO_SYNC if no_sync else 0)))
+        return res
 
     def true_peak(self, rows, oversample=4, rate=None, lengths=None):
         """zvx_true_peak: per row max(max |x|, max |y|), y the row oversampled `oversample` (1, 2, 4, 8) times by zvx_resample's filter
@@ -397,14 +394,11 @@ class Context:
         B = len(n)
         prm = LimitParams(float(ceiling), float(window_ms), int(oversample))
         p = C.c_void_p(int(ptr))
-        if no_sync:
-            self._chk(self._lib.zvx_limit(self._h, p, _ptr(n), B, int(Nmax), self._rate(rate), C.byref(prm), p, int(Nmax), None, None,
-                                          ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC))
-            return None
-        peak, gmin = np.zeros(B, np.float32), np.zeros(B, np.float32)
+        res = None if no_sync else (np.zeros(B, np.float32), np.zeros(B, np.float32))                                # peak_in, min_gain
+        peak, gmin = res or (None, None)
         self._chk(self._lib.zvx_limit(self._h, p, _ptr(n), B, int(Nmax), self._rate(rate), C.byref(prm), p, int(Nmax), _ptr(peak), _ptr(gmin),
-                                      ZVX_DEVICE_IN | ZVX_DEVICE_OUT))
-        return peak, gmin
+                                      ZVX_DEVICE_IN | ZVX_DEVICE_OUT | (ZVX_NO_SYNC if no_sync else 0)))
+        return res
 
     def resample_device(self, ptr, n, rate_in, rate_out, pcm16=False):
         """zvx_resample of ONE device-resident row of n f32 samples (ZVX_DEVICE_IN) -> host row at rate_out"""
@@ -577,22 +571,23 @@ class Context:
     def sync(self):
         self._chk(self._lib.zvx_sync(self._h))
 
-    def stage_times(self):
+    def _stage_ms(self):
+        """zvx_stage_times: every stage slot's hipEvent time, [ZVX_T_COUNT] float32"""
         ms = np.zeros(ZVX_T_COUNT, np.float32)
         self._chk(self._lib.zvx_stage_times(self._h, _ptr(ms)))
+        return ms
+
+    def stage_times(self):
+        ms = self._stage_ms()
         return {n: float(ms[i]) for i, n in enumerate(STAGES)}
 
     def resample_ms(self):
         """hipEvent time of the resample stage of the last waveform call or resample() (profile >= 1; 0.0: that call ran none)"""
-        ms = np.zeros(ZVX_T_COUNT, np.float32)
-        self._chk(self._lib.zvx_stage_times(self._h, _ptr(ms)))
-        return float(ms[ZVX_T_RESAMPLE])
+        return float(self._stage_ms()[ZVX_T_RESAMPLE])
 
     def join_ms(self):
         """hipEvent time of the launches of the last join() / join_device() / trim_bounds() (profile >= 1)"""
-        ms = np.zeros(ZVX_T_COUNT, np.float32)
-        self._chk(self._lib.zvx_stage_times(self._h, _ptr(ms)))
-        return float(ms[ZVX_T_JOIN])
+        return float(self._stage_ms()[ZVX_T_JOIN])
 
     def kernel_stats(self):
         arr = (KernelStat * 32)()

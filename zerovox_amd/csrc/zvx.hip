@@ -157,8 +157,8 @@ struct zvx_ctx {
     std::map<std::pair<int, int>, RsBank> rs_banks;
     std::map<int, const double*> lim_wins;  // zvx_limit: the smoothing weights on the device, designed in double, per window W
     std::map<int, LoudCoef> loud_coefs;    // zvx_loudness / zvx_normalize: the K-weighting biquads, designed in double, per sampling rate
-    // zvx_join / zvx_trim_bounds / zvx_loudness / zvx_normalize: pinned host memory the layout or result words (and host output rows) land
-    // in under the call's one wait
+    // zvx_join / zvx_trim_bounds / zvx_spkemb_wav / zvx_loudness / zvx_normalize / zvx_true_peak / zvx_limit: pinned host memory the
+    // layout, bounds or result words (and host output rows) land in under the call's one wait
     void* join_host = nullptr;
     size_t join_host_cap = 0;
     void* join_pinned(size_t bytes) {
@@ -1950,6 +1950,88 @@ void run_melspec(zvx_ctx* c, const float* wav, const int32_t* nsamples, int B, i
 }
 
 // ------------------------------------------------------------------------------------------------
+// the rows-call contract of the post-processing entry points (include/zvx.h): a batch of waveform rows [B][Nmax] f32 + nsamples[B], on
+// the host or on the device.  The checks are pure: an entry point runs all of its checks before it allocates, uploads or launches.
+// ------------------------------------------------------------------------------------------------
+// (on its own in zvx_resample, whose ZVX_E_UNSUPPORTED rate pairs rank between this and the lengths)
+void rows_args(const char* who, const void* in, const int32_t* nsamples, int B, int Nmax) {
+    if (!in || !nsamples || B <= 0 || Nmax <= 0) fail(ZVX_E_INVALID, "%s: bad arguments (NULL pointer, B = %d, Nmax = %d)", who, B, Nmax);
+}
+struct RowsInfo { long n_max = 0; double n_sum = 0; };      // the longest row, and all samples of the batch
+RowsInfo rows_check(const char* who, const void* in, const int32_t* nsamples, int B, int Nmax, int max_rows = INT32_MAX) {
+    rows_args(who, in, nsamples, B, Nmax);
+    if (B > max_rows) fail(ZVX_E_UNSUPPORTED, "%s: B = %d rows (at most %d per call)", who, B, max_rows);
+    RowsInfo r;
+    for (int b = 0; b < B; b++) {
+        if (nsamples[b] < 0 || nsamples[b] > Nmax) fail(ZVX_E_INVALID, "%s: nsamples[%d]=%d out of range (0..%d)", who, b, nsamples[b], Nmax);
+        r.n_max = std::max<long>(r.n_max, nsamples[b]); r.n_sum += nsamples[b];
+    }
+    return r;
+}
+void flags_check(const char* who, int flags, int allowed) {
+    if (flags & ~allowed) fail(ZVX_E_INVALID, "%s: unknown flag in %d", who, flags);
+    if ((flags & ZVX_NO_SYNC) && !(flags & ZVX_DEVICE_OUT)) fail(ZVX_E_INVALID, "%s: ZVX_NO_SYNC needs ZVX_DEVICE_OUT", who);
+}
+// output rows [B][out_stride] of the input's shape (zvx_normalize, zvx_limit), which may be the input rows themselves
+void out_rows_check(const char* who, const void* in, const void* out, int64_t out_stride, int Nmax, int flags) {
+    if (!out) fail(ZVX_E_INVALID, "%s: out is NULL", who);
+    if (out_stride < Nmax) fail(ZVX_E_INVALID, "%s: out_stride %lld is smaller than Nmax %d", who, (long long)out_stride, Nmax);
+    if (out != in) return;
+    if (flags & ZVX_PCM16) fail(ZVX_E_INVALID, "%s: ZVX_PCM16 cannot run in place", who);
+    if (out_stride != Nmax || !(flags & ZVX_DEVICE_IN) != !(flags & ZVX_DEVICE_OUT))
+        fail(ZVX_E_INVALID, "%s: in place needs out_stride == Nmax and both pointers on the same side", who);
+}
+
+// host rows go to "<prefix>.in" on the device, device rows (ZVX_DEVICE_IN) are used where they are
+const float* rows_to_device(zvx_ctx* c, const std::string& prefix, const float* in, int B, int Nmax, int flags) {
+    if (flags & ZVX_DEVICE_IN) return in;
+    float* xd = c->fbuf(prefix + ".in", (size_t)B * Nmax);
+    HIPCHK(hipMemcpyAsync(xd, in, (size_t)B * Nmax * 4, hipMemcpyHostToDevice, c->stream));
+    return xd;
+}
+struct DevRows { const float* x; const int* len; };
+DevRows stage_rows(zvx_ctx* c, const std::string& prefix, const float* in, const int32_t* nsamples, int B, int Nmax, int flags) {
+    const float* x = rows_to_device(c, prefix, in, B, Nmax, flags);
+    return {x, c->upload_ints(prefix + ".len", nsamples, B)};
+}
+// "issue the following under tag T", between the stage slot's events where one is given; the tag is restored on every way out
+struct TagScope {
+    zvx_ctx* c; std::string keep; int slot;
+    TagScope(zvx_ctx* c_, const char* tag, int slot_ = -1) : c(c_), keep(c_->tag), slot(slot_) {
+        c->tag = tag;
+        if (slot >= 0) c->stage_begin(slot);
+    }
+    ~TagScope() { c->tag = keep; }
+    void close() { if (slot >= 0) c->stage_end(slot); c->tag = keep; }
+};
+// What zvx_normalize / zvx_limit and their measuring forms hand back: `res_bytes` of result words (padded to 256 bytes in the pinned
+// block) and, with a host output, the rows: staged on the device at a stride of their own, brought over behind the words, one wait.
+struct RowsReturn {
+    zvx_ctx* c; int B; size_t res_bytes, res_pad, ss; long n_max, ostage; bool want_host, host_out; char* host = nullptr; void* odev = nullptr;
+    RowsReturn(zvx_ctx* c_, int B_, size_t res_bytes_, bool want_host_, bool writes_rows, long n_max_, int flags)
+        : c(c_), B(B_), res_bytes(res_bytes_), res_pad((res_bytes_ + 255) & ~(size_t)255), ss((flags & ZVX_PCM16) ? 2 : 4), n_max(n_max_),
+          ostage((n_max_ + 7) & ~7L), want_host(want_host_), host_out(writes_rows && !(flags & ZVX_DEVICE_OUT)) {
+        if (want_host || host_out) host = (char*)c->join_pinned(res_pad + (host_out ? (size_t)B * ostage * ss : 0));
+    }
+    // where the launches write the rows, and at which stride: the staging buffer `name`, or the caller's device rows
+    void* out_rows(const char* name, void* out, int64_t out_stride, long* bs) {
+        *bs = host_out ? ostage : (long)out_stride;
+        return odev = host_out ? c->buf(name, (size_t)B * ostage * ss + 16) : out;
+    }
+    // -> the result words on the host; nullptr where none were asked for (with ZVX_NO_SYNC the call has then only queued)
+    const char* finish(const void* res_dev, void* out, int64_t out_stride, const int32_t* nsamples, int flags) {
+        if (want_host) HIPCHK(hipMemcpyAsync(host, res_dev, res_bytes, hipMemcpyDeviceToHost, c->stream));
+        if (host_out && n_max > 0) HIPCHK(hipMemcpyAsync(host + res_pad, odev, (size_t)B * ostage * ss, hipMemcpyDeviceToHost, c->stream));
+        if (!want_host && (flags & ZVX_NO_SYNC)) return nullptr;     // device output, nothing for the host: the call only queues
+        c->sync();                                                   // the call's one wait
+        if (host_out)
+            for (int b = 0; b < B; b++)
+                if (nsamples[b] > 0) memcpy((char*)out + (size_t)b * out_stride * ss, host + res_pad + (size_t)b * ostage * ss, (size_t)nsamples[b] * ss);
+        return want_host ? host : nullptr;
+    }
+};
+
+// ------------------------------------------------------------------------------------------------
 // sample-rate conversion (include/zvx.h: zvx_resample, "out_rate")
 // ------------------------------------------------------------------------------------------------
 constexpr int RS_MAX_PHASES = 640;       // max(L, M) a bank is built for: every pair between 22050 and 8000 ... 48000
@@ -1966,6 +2048,19 @@ void rs_pair(int rate_in, int rate_out, int* L, int* M) {
         fail(ZVX_E_UNSUPPORTED, "resampling %d -> %d Hz needs L = %d, M = %d: the polyphase bank is built for max(L, M) <= %d", rate_in, rate_out, *L, *M, RS_MAX_PHASES);
 }
 long rs_out_len(long n, int L, int M) { return (n * L + M - 1) / M; }
+// Every row converted as a signal of its own length len[b] * mul, held from sample in_origin on and zero elsewhere: per row the outputs
+// [out_begin, out_begin + cnt[b]) (out_count -1: to the end of the row's signal), the longest of them, and the samples read and written.
+struct RsPlan { long in_origin = 0, out_begin = 0, out_count = -1, out_max = 0; std::vector<long> cnt; double nin = 0, nout = 0; };
+RsPlan rs_plan(const int* len, int mul, int B, int L, int M, long in_origin = 0, long out_begin = 0, long out_count = -1) {
+    RsPlan p;
+    p.in_origin = in_origin; p.out_begin = out_begin; p.out_count = out_count; p.cnt.resize(B);
+    for (int b = 0; b < B; b++) {
+        const long n = (long)len[b] * mul;
+        p.cnt[b] = out_count >= 0 ? out_count : std::max(0L, rs_out_len(in_origin + n, L, M) - out_begin);
+        p.out_max = std::max(p.out_max, p.cnt[b]); p.nin += (double)n; p.nout += (double)p.cnt[b];
+    }
+    return p;
+}
 
 double bessel_i0(double x) {
     double s = 1.0, t = 1.0;
@@ -2038,20 +2133,17 @@ const zvx_ctx::RsBank& rs_bank(zvx_ctx* c, int L, int M) {
 
 // The one resampling launch: stage tag "voc.resample", slot ZVX_T_RESAMPLE, algorithmic bytes = samples read + samples written.
 void run_resample(zvx_ctx* c, const zvx_ctx::RsBank& bk, const float* x_dev, long x_bs, const int* in_len_d, int in_mul, int B, void* out_dev,
-                  long out_bs, int pcm16, long in_origin, long out_begin, long out_count, long out_max, double nin, double nout) {
-    if (out_max <= 0) return;
+                  long out_bs, int pcm16, const RsPlan& p) {
+    if (p.out_max <= 0) return;
     ResampleArgs a{};
     a.x = x_dev; a.x_bs = x_bs; a.in_len = in_len_d; a.in_mul = in_mul; a.out = out_dev; a.out_bs = out_bs; a.pcm16 = pcm16;
     a.B = B; a.L = bk.L; a.M = bk.M; a.half = bk.half; a.T = bk.T; a.pitch = bk.pitch; a.bank = bk.dev;
-    a.in_origin = in_origin; a.out_begin = out_begin; a.out_count = out_count; a.out_max = out_max;
-    const std::string keep = c->tag;
-    c->tag = "voc.resample";
-    c->stage_begin(ZVX_T_RESAMPLE);
-    c->timed(2.0 * nout * bk.T, nin * 4.0 + nout * (pcm16 ? 2.0 : 4.0), [&] {
+    a.in_origin = p.in_origin; a.out_begin = p.out_begin; a.out_count = p.out_count; a.out_max = p.out_max;
+    TagScope scope(c, "voc.resample", ZVX_T_RESAMPLE);
+    c->timed(2.0 * p.nout * bk.T, p.nin * 4.0 + p.nout * (pcm16 ? 2.0 : 4.0), [&] {
         if (!launch_resample_poly(a, c->stream)) fail(ZVX_E_UNSUPPORTED, "resampler: L = %d, M = %d does not fit the LDS of a workgroup", bk.L, bk.M);
     });
-    c->stage_end(ZVX_T_RESAMPLE);
-    c->tag = keep;
+    scope.close();
 }
 
 int model_rate(const zvx_ctx* c) {
@@ -2063,38 +2155,28 @@ int model_rate(const zvx_ctx* c) {
 // zvx_resample / zvx_resample_ex
 void do_resample(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate_in, int rate_out, void* out, int64_t out_stride,
                  int32_t* out_len, int flags, int64_t in_origin, int64_t out_begin, int64_t out_count) {
-    if (!in || !nsamples || !out || B <= 0 || Nmax <= 0) fail(ZVX_E_INVALID, "zvx_resample: bad arguments");
-    if (flags & ~(ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16)) fail(ZVX_E_INVALID, "zvx_resample: unknown flag in %d", flags);
-    if ((flags & ZVX_NO_SYNC) && !(flags & ZVX_DEVICE_OUT)) fail(ZVX_E_INVALID, "zvx_resample: ZVX_NO_SYNC needs ZVX_DEVICE_OUT");
+    rows_args("zvx_resample", in, nsamples, B, Nmax);
+    if (!out) fail(ZVX_E_INVALID, "zvx_resample: out is NULL");
+    flags_check("zvx_resample", flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16);
     if (in_origin < 0 || out_begin < 0 || out_count < -1 || in_origin > ((int64_t)1 << 40) || out_begin > ((int64_t)1 << 40) || out_count > INT32_MAX)
         fail(ZVX_E_INVALID, "zvx_resample_ex: window out of range");
     int L = 1, M = 1;
-    rs_pair(rate_in, rate_out, &L, &M);
-    for (int b = 0; b < B; b++) if (nsamples[b] < 0 || nsamples[b] > Nmax) fail(ZVX_E_INVALID, "nsamples[%d]=%d out of range (0..%d)", b, nsamples[b], Nmax);
-    std::vector<long> cnt(B);
-    long out_max = 0; double nin = 0, nout = 0;
-    for (int b = 0; b < B; b++) {
-        cnt[b] = out_count >= 0 ? (long)out_count : std::max(0L, rs_out_len((long)in_origin + nsamples[b], L, M) - (long)out_begin);
-        out_max = std::max(out_max, cnt[b]); nin += nsamples[b]; nout += (double)cnt[b];
-    }
+    rs_pair(rate_in, rate_out, &L, &M);                     // (its ZVX_E_UNSUPPORTED ranks before a bad length)
+    rows_check("zvx_resample", in, nsamples, B, Nmax);
+    const RsPlan plan = rs_plan(nsamples, 1, B, L, M, in_origin, out_begin, out_count);
+    const long out_max = plan.out_max;
     if (out_max > INT32_MAX) fail(ZVX_E_INVALID, "zvx_resample: %ld output samples per row", out_max);
-    if (out_stride < out_max) fail(ZVX_E_BUFFER, "out_stride %lld < %ld samples", (long long)out_stride, out_max);
+    if (out_stride < out_max) fail(ZVX_E_BUFFER, "zvx_resample: out_stride %lld < %ld samples", (long long)out_stride, out_max);
     const zvx_ctx::RsBank& bk = rs_bank(c, L, M);
     const int pcm16 = (flags & ZVX_PCM16) ? 1 : 0;
     const size_t ss = pcm16 ? 2 : 4;
-    const float* x_dev = in;
-    if (!(flags & ZVX_DEVICE_IN)) {
-        float* xd = c->fbuf("rs.in", (size_t)B * Nmax);
-        HIPCHK(hipMemcpyAsync(xd, in, (size_t)B * Nmax * 4, hipMemcpyHostToDevice, c->stream));
-        x_dev = xd;
-    }
-    const int* len_d = c->upload_ints("rs.len", nsamples, B);
+    const DevRows rows = stage_rows(c, "rs", in, nsamples, B, Nmax, flags);
     void* odev = out; long ostride = out_stride;
     if (!(flags & ZVX_DEVICE_OUT)) { ostride = (std::max(out_max, 1L) + 7) & ~7L; odev = c->buf("rs.out", (size_t)B * ostride * ss); }
-    run_resample(c, bk, x_dev, Nmax, len_d, 1, B, odev, ostride, pcm16, in_origin, out_begin, out_count, out_max, nin, nout);
+    run_resample(c, bk, rows.x, Nmax, rows.len, 1, B, odev, ostride, pcm16, plan);
     if (!(flags & ZVX_DEVICE_OUT) && out_max > 0)
         HIPCHK(hipMemcpy2DAsync(out, (size_t)out_stride * ss, odev, (size_t)ostride * ss, (size_t)out_max * ss, B, hipMemcpyDeviceToHost, c->stream));
-    if (out_len) for (int b = 0; b < B; b++) out_len[b] = (int32_t)cnt[b];
+    if (out_len) for (int b = 0; b < B; b++) out_len[b] = (int32_t)plan.cnt[b];
     if (!((flags & ZVX_DEVICE_OUT) && (flags & ZVX_NO_SYNC))) c->sync();
 }
 
@@ -2104,26 +2186,19 @@ void do_resample(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, in
 constexpr int JOIN_MAX_UNITS_PER_FRAME = 32;   // hop-block sums serve frames of up to this many blocks; longer ratios take the per-frame path
 
 void join_check(const char* who, const void* in, const int32_t* nsamples, int B, int Nmax, const int32_t* gap, const zvx_join_params* p) {
-    if (!in || !nsamples || !p || B <= 0 || Nmax <= 0) fail(ZVX_E_INVALID, "%s: bad arguments (NULL pointer, B = %d, Nmax = %d)", who, B, Nmax);
+    rows_check(who, in, nsamples, B, Nmax);
+    if (!p) fail(ZVX_E_INVALID, "%s: params is NULL", who);
     if (p->frame < 2 || p->hop < 1 || p->hop > p->frame) fail(ZVX_E_INVALID, "%s: frame %d / hop %d (frame >= 2, 1 <= hop <= frame)", who, p->frame, p->hop);
     if (p->keep < 0 || p->fade < 0) fail(ZVX_E_INVALID, "%s: keep %d / fade %d must not be negative", who, p->keep, p->fade);
     if (!std::isfinite(p->top_db)) fail(ZVX_E_INVALID, "%s: top_db is not finite", who);
-    for (int b = 0; b < B; b++) {
-        if (nsamples[b] < 0 || nsamples[b] > Nmax) fail(ZVX_E_INVALID, "%s: nsamples[%d]=%d out of range (0..%d)", who, b, nsamples[b], Nmax);
-        if (gap && gap[b] < 0) fail(ZVX_E_INVALID, "%s: gap[%d]=%d is negative", who, b, gap[b]);
-    }
+    for (int b = 0; gap && b < B; b++) if (gap[b] < 0) fail(ZVX_E_INVALID, "%s: gap[%d]=%d is negative", who, b, gap[b]);
 }
 
 // queues the frame-power and bounds launches; "join.bounds" then holds {begin, end} per row.  Returns the device rows and the samples read.
 const float* join_bounds(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_join_params* p, int flags, double* read) {
-    const float* x_dev = in;
-    if (!(flags & ZVX_DEVICE_IN)) {
-        float* xd = c->fbuf("join.in", (size_t)B * Nmax);
-        HIPCHK(hipMemcpyAsync(xd, in, (size_t)B * Nmax * 4, hipMemcpyHostToDevice, c->stream));
-        x_dev = xd;
-    }
+    const DevRows rows = stage_rows(c, "join", in, nsamples, B, Nmax, flags);
     JoinBoundsArgs a{};
-    a.x = x_dev; a.x_bs = Nmax; a.nsamples = c->upload_ints("join.len", nsamples, B); a.B = B;
+    a.x = rows.x; a.x_bs = Nmax; a.nsamples = rows.len; a.B = B;
     a.frame = p->frame; a.hop = p->hop; a.keep = p->keep;
     a.tiled = (p->frame % p->hop == 0 && p->frame / p->hop <= JOIN_MAX_UNITS_PER_FRAME) ? 1 : 0;
     a.trim = p->top_db > 0.f ? 1 : 0;
@@ -2141,26 +2216,21 @@ const float* join_bounds(zvx_ctx* c, const float* in, const int32_t* nsamples, i
     launch_join_powers(a, units_max, c->stream);
     launch_join_bounds(a, c->stream);
     *read = a.trim ? nin : 0.0;
-    return x_dev;
+    return rows.x;
 }
 
 // the launches of one call as ONE timed group under "post.join"; its byte count is only known after the call's wait
 struct JoinTimer {
-    zvx_ctx* c; GemmEvent ev{}; bool prof; std::string keep;
-    explicit JoinTimer(zvx_ctx* c_) : c(c_), prof(c_->profile >= 2 && c_->profile_only < 0), keep(c_->tag) {
-        c->tag = "post.join";
-        c->stage_begin(ZVX_T_JOIN);
+    zvx_ctx* c; TagScope scope; GemmEvent ev{}; bool prof;
+    explicit JoinTimer(zvx_ctx* c_) : c(c_), scope(c_, "post.join", ZVX_T_JOIN), prof(c_->profile >= 2 && c_->profile_only < 0) {
         if (prof) { ev.a = c->new_event(); ev.b = c->new_event(); HIPCHK(hipEventRecord(ev.a, c->stream)); }
     }
-    ~JoinTimer() { c->tag = keep; }
-    void stop() { if (prof) HIPCHK(hipEventRecord(ev.b, c->stream)); c->stage_end(ZVX_T_JOIN); c->tag = keep; }
+    void stop() { if (prof) HIPCHK(hipEventRecord(ev.b, c->stream)); scope.close(); }
     void commit(double bytes) { if (prof) { ev.variant = -1; ev.flops = 0; ev.bytes = bytes; ev.tag = "post.join"; c->pending.push_back(ev); prof = false; } }
 };
 
-void do_trim_bounds(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_join_params* p, int32_t* begin, int32_t* end, int flags) {
-    join_check("zvx_trim_bounds", in, nsamples, B, Nmax, nullptr, p);
-    if (!begin || !end) fail(ZVX_E_INVALID, "zvx_trim_bounds: NULL output");
-    if (flags & ~ZVX_DEVICE_IN) fail(ZVX_E_INVALID, "zvx_trim_bounds: unknown flag in %d", flags);
+// join_bounds as a call's whole timed group, then the wait for its result.  Returns the pinned {begin, end} words of every row.
+const int* bounds_to_host(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_join_params* p, int flags) {
     int* host = (int*)c->join_pinned((size_t)2 * B * sizeof(int));
     JoinTimer t(c);
     double read = 0;
@@ -2168,8 +2238,16 @@ void do_trim_bounds(zvx_ctx* c, const float* in, const int32_t* nsamples, int B,
     t.stop();
     HIPCHK(hipMemcpyAsync(host, c->ibuf("join.bounds", 0), (size_t)2 * B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(hipStreamSynchronize(c->stream));
-    for (int b = 0; b < B; b++) { begin[b] = host[2 * b]; end[b] = host[2 * b + 1]; }
     t.commit(read * 4.0);
+    return host;
+}
+
+void do_trim_bounds(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_join_params* p, int32_t* begin, int32_t* end, int flags) {
+    join_check("zvx_trim_bounds", in, nsamples, B, Nmax, nullptr, p);
+    if (!begin || !end) fail(ZVX_E_INVALID, "zvx_trim_bounds: NULL output");
+    flags_check("zvx_trim_bounds", flags, ZVX_DEVICE_IN);
+    const int* host = bounds_to_host(c, in, nsamples, B, Nmax, p, flags);
+    for (int b = 0; b < B; b++) { begin[b] = host[2 * b]; end[b] = host[2 * b + 1]; }
     c->sync();
 }
 
@@ -2177,7 +2255,7 @@ void do_join(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nm
              int64_t out_capacity, int64_t* out_len, int64_t* seg_pos, int32_t* seg_begin, int32_t* seg_len, int flags) {
     join_check("zvx_join", in, nsamples, B, Nmax, gap, p);
     if (!out || !out_len || out_capacity < 0) fail(ZVX_E_INVALID, "zvx_join: bad output arguments");
-    if (flags & ~(ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_PCM16)) fail(ZVX_E_INVALID, "zvx_join: unknown flag in %d", flags);
+    flags_check("zvx_join", flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_PCM16);
     const int pcm16 = (flags & ZVX_PCM16) ? 1 : 0;
     const size_t ss = pcm16 ? 2 : 4;
     long upper = 0;                                          // what the row can hold at most: nothing trimmed
@@ -2233,45 +2311,30 @@ void do_spkemb_wav(zvx_ctx* c, const float* wav, const int32_t* nsamples, int B,
     if (p) { jp.frame = p->frame; jp.hop = p->hop; jp.top_db = p->top_db; jp.keep = p->keep; }
     join_check("zvx_spkemb_wav", wav, nsamples, B, Nmax, nullptr, p ? &jp : nullptr);
     if (p->max_samples < 0) fail(ZVX_E_INVALID, "zvx_spkemb_wav: max_samples %d must not be negative", p->max_samples);
-    if (flags & ~(ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC)) fail(ZVX_E_INVALID, "zvx_spkemb_wav: unknown flag in %d", flags);
-    if ((flags & ZVX_NO_SYNC) && !(flags & ZVX_DEVICE_OUT)) fail(ZVX_E_INVALID, "zvx_spkemb_wav: ZVX_NO_SYNC needs ZVX_DEVICE_OUT");
+    flags_check("zvx_spkemb_wav", flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC);
     const int native = model_rate(c);
     int L = 1, M = 1;
     rs_pair(rate, native, &L, &M);
+    const RsPlan plan = rs_plan(nsamples, 1, B, L, M);
+    std::vector<int> n(B);                                   // the rows' lengths at the model's rate
+    for (int b = 0; b < B; b++) {
+        if (rate != native && plan.cnt[b] > INT32_MAX - 8) fail(ZVX_E_INVALID, "zvx_spkemb_wav: row %d has %ld samples at the model's rate", b, plan.cnt[b]);
+        n[b] = (int)plan.cnt[b];
+    }
     const int n_fft = c->t("mel.dft").dim(2), hop = c->hop, pad = (n_fft - hop) / 2, H = c->H;
     // 1. the rows at the model's rate: as given, or each converted as a signal of its own length into a work buffer
-    const float* rows = wav; long rows_bs = Nmax;
-    if (!(flags & ZVX_DEVICE_IN)) {
-        float* xd = c->fbuf("ref.in", (size_t)B * Nmax);
-        HIPCHK(hipMemcpyAsync(xd, wav, (size_t)B * Nmax * 4, hipMemcpyHostToDevice, c->stream));
-        rows = xd;
-    }
-    std::vector<int> n(nsamples, nsamples + B);
+    const float* rows = rows_to_device(c, "ref", wav, B, Nmax, flags);      // (each step uploads the lengths it reads)
+    long rows_bs = Nmax;
     if (rate != native) {
-        long out_max = 0; double nin = 0, nout = 0;
-        for (int b = 0; b < B; b++) {
-            const long cnt = rs_out_len(nsamples[b], L, M);
-            if (cnt > INT32_MAX - 8) fail(ZVX_E_INVALID, "zvx_spkemb_wav: row %d has %ld samples at the model's rate", b, cnt);
-            n[b] = (int)cnt; out_max = std::max(out_max, cnt); nin += nsamples[b]; nout += (double)cnt;
-        }
         const zvx_ctx::RsBank& bk = rs_bank(c, L, M);
         const int* len_d = c->upload_ints("rs.len", nsamples, B);
-        const long ostride = (std::max(out_max, 1L) + 7) & ~7L;
+        const long ostride = (std::max(plan.out_max, 1L) + 7) & ~7L;
         float* conv = c->fbuf("ref.rs", (size_t)B * ostride);
-        run_resample(c, bk, rows, rows_bs, len_d, 1, B, conv, ostride, 0, 0, 0, -1, out_max, nin, nout);
+        run_resample(c, bk, rows, rows_bs, len_d, 1, B, conv, ostride, 0, plan);
         rows = conv; rows_bs = ostride;
     }
     // 2. the bounds, and the call's one wait
-    int* host = (int*)c->join_pinned((size_t)2 * B * sizeof(int));
-    {
-        JoinTimer t(c);
-        double read = 0;
-        join_bounds(c, rows, n.data(), B, (int)rows_bs, &jp, ZVX_DEVICE_IN, &read);
-        t.stop();
-        HIPCHK(hipMemcpyAsync(host, c->ibuf("join.bounds", 0), (size_t)2 * B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipStreamSynchronize(c->stream));
-        t.commit(read * 4.0);
-    }
+    const int* host = bounds_to_host(c, rows, n.data(), B, (int)rows_bs, &jp, ZVX_DEVICE_IN);
     // 3. / 4. crop, frame counts, and what zvx_melspec / zvx_spkemb ask of a signal
     std::vector<int> frames(B);
     int Mmax = 0, Tf = 0, bad = -1;
@@ -2334,47 +2397,26 @@ const LoudCoef& loud_coef(zvx_ctx* c, int rate) {
 void do_loudness(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_loudness_params* p,
                  void* out, int64_t out_stride, double* lufs, float* peak, float* gain, int flags) {
     const bool norm = p != nullptr;
-    if (!in || !nsamples || B <= 0 || Nmax <= 0) fail(ZVX_E_INVALID, "%s: bad arguments (NULL pointer, B = %d, Nmax = %d)", who, B, Nmax);
-    if (B > 65535) fail(ZVX_E_UNSUPPORTED, "%s: B = %d rows (at most 65535 per call)", who, B);
+    const RowsInfo r = rows_check(who, in, nsamples, B, Nmax, 65535);
     if (rate < 4000 || rate > 192000) fail(ZVX_E_INVALID, "%s: rate %d outside [4000, 192000]", who, rate);
-    if (flags & ~(norm ? (ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16) : ZVX_DEVICE_IN)) fail(ZVX_E_INVALID, "%s: unknown flag in %d", who, flags);
-    const int pcm16 = (flags & ZVX_PCM16) ? 1 : 0;
+    flags_check(who, flags, norm ? (ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16) : ZVX_DEVICE_IN);
     if (norm) {
-        if (!out) fail(ZVX_E_INVALID, "%s: out is NULL", who);
-        if (out_stride < Nmax) fail(ZVX_E_INVALID, "%s: out_stride %lld is smaller than Nmax %d", who, (long long)out_stride, Nmax);
-        if ((flags & ZVX_NO_SYNC) && !(flags & ZVX_DEVICE_OUT)) fail(ZVX_E_INVALID, "%s: ZVX_NO_SYNC needs ZVX_DEVICE_OUT", who);
-        if (out == (const void*)in && pcm16) fail(ZVX_E_INVALID, "%s: ZVX_PCM16 cannot run in place", who);
-        if (out == (const void*)in && (out_stride != Nmax || !(flags & ZVX_DEVICE_IN) != !(flags & ZVX_DEVICE_OUT)))
-            fail(ZVX_E_INVALID, "%s: in place needs out_stride == Nmax and both pointers on the same side", who);
+        out_rows_check(who, in, out, out_stride, Nmax, flags);
         if (!std::isfinite(p->target_lufs) || p->target_lufs < -70.f || p->target_lufs > 0.f) fail(ZVX_E_INVALID, "%s: target_lufs must lie in [-70, 0]", who);
         if (!std::isfinite(p->max_gain_db) || p->max_gain_db < 0.f) fail(ZVX_E_INVALID, "%s: max_gain_db must be finite and not negative", who);
         if (std::isnan(p->peak_ceiling)) fail(ZVX_E_INVALID, "%s: peak_ceiling is NaN", who);
         if (p->mode != ZVX_LOUD_PER_ROW && p->mode != ZVX_LOUD_COMMON) fail(ZVX_E_INVALID, "%s: unknown mode %d", who, p->mode);
     }
-    long n_max = 0; double n_sum = 0;
-    for (int b = 0; b < B; b++) {
-        if (nsamples[b] < 0 || nsamples[b] > Nmax) fail(ZVX_E_INVALID, "%s: nsamples[%d]=%d out of range (0..%d)", who, b, nsamples[b], Nmax);
-        n_max = std::max<long>(n_max, nsamples[b]); n_sum += nsamples[b];
-    }
-    const size_t ss = pcm16 ? 2 : 4;
-    const bool host_out = norm && !(flags & ZVX_DEVICE_OUT);
-    const bool want_host = lufs || peak || gain;
-    // result words in one block: lufs [B] double, then peak [B], gain [B] float; a host output row set is staged behind them
-    const size_t res_bytes = (size_t)B * 16, res_pad = (res_bytes + 255) & ~(size_t)255;
-    const long ostage = (n_max + 7) & ~7L;                    // row stride of the staged host output
-    char* host = (want_host || host_out) ? (char*)c->join_pinned(res_pad + (host_out ? (size_t)B * ostage * ss : 0)) : nullptr;
+    // result words in one block: lufs [B] double, then peak [B], gain [B] float
+    const size_t res_bytes = (size_t)B * 16;
+    RowsReturn ret(c, B, res_bytes, lufs || peak || gain, norm, r.n_max, flags);
     LoudArgs a{};
     a.h = (rate + 5) / 10;
     a.k = loud_coef(c, rate);
-    const long units_max = std::max(n_max / a.h, 1L);
+    const long units_max = std::max(r.n_max / a.h, 1L);
     a.upitch = units_max; a.ppitch = (int)((units_max + 63) / 64);
-    const float* x_dev = in;
-    if (!(flags & ZVX_DEVICE_IN)) {
-        float* xd = c->fbuf("loud.in", (size_t)B * Nmax);
-        HIPCHK(hipMemcpyAsync(xd, in, (size_t)B * Nmax * 4, hipMemcpyHostToDevice, c->stream));
-        x_dev = xd;
-    }
-    a.x = x_dev; a.x_bs = Nmax; a.nsamples = c->upload_ints("loud.len", nsamples, B); a.B = B;
+    const DevRows rows = stage_rows(c, "loud", in, nsamples, B, Nmax, flags);
+    a.x = rows.x; a.x_bs = Nmax; a.nsamples = rows.len; a.B = B;
     a.unit = (double*)c->buf("loud.unit", (size_t)B * units_max * sizeof(double));
     a.part_peak = c->fbuf("loud.ppeak", (size_t)B * a.ppitch);
     char* res = (char*)c->buf("loud.res", res_bytes + (size_t)B * 16);
@@ -2383,36 +2425,24 @@ void do_loudness(zvx_ctx* c, const char* who, const float* in, const int32_t* ns
     a.abs_gate = pow(10.0, (-70.0 + 0.691) / 10.0);
     a.want_gain = norm ? 1 : 0;
     if (norm) { a.target = (double)p->target_lufs; a.max_gain_db = (double)p->max_gain_db; a.ceiling = (double)p->peak_ceiling; }
-    void* odev = host_out ? c->buf("loud.out", (size_t)B * ostage * ss + 16) : out;
-    const std::string keep = c->tag;
-    c->tag = "post.loudness";
-    struct Untag { zvx_ctx* c; const std::string& keep; ~Untag() { c->tag = keep; } } untag{c, keep};
-    c->timed(0.0, 4.0 * n_sum + (norm ? (4.0 + (double)ss) * n_sum : 0.0), [&] {
+    LoudApplyArgs w{};
+    w.x = rows.x; w.x_bs = Nmax; w.nsamples = a.nsamples; w.B = B; w.gain = a.gain; w.pcm16 = (flags & ZVX_PCM16) ? 1 : 0;
+    w.out = ret.out_rows("loud.out", out, out_stride, &w.out_bs);
+    TagScope scope(c, "post.loudness");
+    c->timed(0.0, 4.0 * r.n_sum + (norm ? (4.0 + (double)ret.ss) * r.n_sum : 0.0), [&] {
         launch_loud_units(a, units_max, c->stream);
         launch_loud_gates(a, c->stream);
         if (norm && p->mode == ZVX_LOUD_COMMON) launch_loud_common(a, c->stream);
-        if (norm) {
-            LoudApplyArgs w{};
-            w.x = x_dev; w.x_bs = Nmax; w.nsamples = a.nsamples; w.B = B; w.gain = a.gain;
-            w.out = odev; w.out_bs = host_out ? ostage : (long)out_stride; w.pcm16 = pcm16;
-            launch_loud_apply(w, n_max, c->stream);
-        }
+        if (norm) launch_loud_apply(w, r.n_max, c->stream);
     });
-    if (want_host) HIPCHK(hipMemcpyAsync(host, res, res_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (host_out && n_max > 0) HIPCHK(hipMemcpyAsync(host + res_pad, odev, (size_t)B * ostage * ss, hipMemcpyDeviceToHost, c->stream));
-    if (!want_host && (flags & ZVX_NO_SYNC)) return;         // device output, nothing for the host: the call only queues
-    c->sync();                                               // the call's one wait
-    if (want_host) {
-        const double* l_h = (const double*)host; const float* p_h = (const float*)(host + (size_t)B * 8); const float* g_h = p_h + B;
-        for (int b = 0; b < B; b++) {
-            if (lufs) lufs[b] = l_h[b];
-            if (peak) peak[b] = p_h[b];
-            if (gain) gain[b] = g_h[b];
-        }
+    const char* words = ret.finish(res, out, out_stride, nsamples, flags);
+    if (!words) return;
+    const double* l_h = (const double*)words; const float* p_h = (const float*)(words + (size_t)B * 8); const float* g_h = p_h + B;
+    for (int b = 0; b < B; b++) {
+        if (lufs) lufs[b] = l_h[b];
+        if (peak) peak[b] = p_h[b];
+        if (gain) gain[b] = g_h[b];
     }
-    if (host_out)
-        for (int b = 0; b < B; b++)
-            if (nsamples[b] > 0) memcpy((char*)out + (size_t)b * out_stride * ss, host + res_pad + (size_t)b * ostage * ss, (size_t)nsamples[b] * ss);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2436,41 +2466,24 @@ const double* limit_win(zvx_ctx* c, int W) {
 void do_limit(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_limit_params* p,
               int oversample, void* out, int64_t out_stride, float* peak_in, float* min_gain, int flags) {
     const bool lim = p != nullptr;
-    if (!in || !nsamples || B <= 0 || Nmax <= 0) fail(ZVX_E_INVALID, "%s: bad arguments (NULL pointer, B = %d, Nmax = %d)", who, B, Nmax);
     if (!lim && !peak_in) fail(ZVX_E_INVALID, "%s: tpeak is NULL", who);
-    if (B > 65535) fail(ZVX_E_UNSUPPORTED, "%s: B = %d rows (at most 65535 per call)", who, B);
+    const RowsInfo r = rows_check(who, in, nsamples, B, Nmax, 65535);
     if (rate < 4000 || rate > 192000) fail(ZVX_E_INVALID, "%s: rate %d outside [4000, 192000]", who, rate);
-    if (flags & ~(lim ? (ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16) : ZVX_DEVICE_IN)) fail(ZVX_E_INVALID, "%s: unknown flag in %d", who, flags);
+    flags_check(who, flags, lim ? (ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16) : ZVX_DEVICE_IN);
     const int os = lim ? p->oversample : oversample;
     if (os != 1 && os != 2 && os != 4 && os != 8) fail(ZVX_E_INVALID, "%s: oversample %d is none of 1, 2, 4, 8", who, os);
-    const int pcm16 = (flags & ZVX_PCM16) ? 1 : 0;
     int W = 0;
     if (lim) {
-        if (!out) fail(ZVX_E_INVALID, "%s: out is NULL", who);
-        if (out_stride < Nmax) fail(ZVX_E_INVALID, "%s: out_stride %lld is smaller than Nmax %d", who, (long long)out_stride, Nmax);
-        if ((flags & ZVX_NO_SYNC) && !(flags & ZVX_DEVICE_OUT)) fail(ZVX_E_INVALID, "%s: ZVX_NO_SYNC needs ZVX_DEVICE_OUT", who);
-        if (out == (const void*)in && pcm16) fail(ZVX_E_INVALID, "%s: ZVX_PCM16 cannot run in place", who);
-        if (out == (const void*)in && (out_stride != Nmax || !(flags & ZVX_DEVICE_IN) != !(flags & ZVX_DEVICE_OUT)))
-            fail(ZVX_E_INVALID, "%s: in place needs out_stride == Nmax and both pointers on the same side", who);
+        out_rows_check(who, in, out, out_stride, Nmax, flags);
         if (!std::isfinite(p->ceiling) || !(p->ceiling > 0.f) || p->ceiling > 8.f) fail(ZVX_E_INVALID, "%s: ceiling must be finite and lie in (0, 8]", who);
         if (!std::isfinite(p->window_ms) || !(p->window_ms > 0.f)) fail(ZVX_E_INVALID, "%s: window_ms must be finite and positive", who);
-    }
-    long n_max = 0; double n_sum = 0;
-    for (int b = 0; b < B; b++) {
-        if (nsamples[b] < 0 || nsamples[b] > Nmax) fail(ZVX_E_INVALID, "%s: nsamples[%d]=%d out of range (0..%d)", who, b, nsamples[b], Nmax);
-        n_max = std::max<long>(n_max, nsamples[b]); n_sum += nsamples[b];
     }
     if (lim) {
         const double w = std::max(1.0, rint((double)rate * (double)p->window_ms / 1000.0));
         if (w > (double)LIMIT_MAX_W) fail(ZVX_E_UNSUPPORTED, "%s: window of %.0f samples (at most %d)", who, w, LIMIT_MAX_W);
         W = (int)w;
     }
-    const size_t ss = pcm16 ? 2 : 4;
-    const bool host_out = lim && !(flags & ZVX_DEVICE_OUT);
-    const bool want_host = peak_in || min_gain;
-    const size_t res_bytes = (size_t)B * 8, res_pad = (res_bytes + 255) & ~(size_t)255;     // peak [B], then min gain [B]
-    const long ostage = (n_max + 7) & ~7L;                    // row stride of the staged host output
-    char* host = (want_host || host_out) ? (char*)c->join_pinned(res_pad + (host_out ? (size_t)B * ostage * ss : 0)) : nullptr;
+    RowsReturn ret(c, B, (size_t)B * 8, peak_in || min_gain, lim, r.n_max, flags);      // words: peak [B], then min gain [B]
     LimitArgs a{};
     a.os = os;
     if (os > 1) {
@@ -2479,43 +2492,27 @@ void do_limit(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamp
         a.T = bk.T; a.pitch = bk.pitch; a.bank = bk.dev;
     }
     if (lim) { a.c = p->ceiling; a.W = W; a.win = limit_win(c, W); }
-    const float* x_dev = in;
-    if (!(flags & ZVX_DEVICE_IN)) {
-        float* xd = c->fbuf("lim.in", (size_t)B * Nmax);
-        HIPCHK(hipMemcpyAsync(xd, in, (size_t)B * Nmax * 4, hipMemcpyHostToDevice, c->stream));
-        x_dev = xd;
-    }
-    a.x = x_dev; a.x_bs = Nmax; a.nsamples = c->upload_ints("lim.len", nsamples, B); a.B = B;
-    a.ppitch = (int)std::max(1L, (n_max + LIMIT_TILE - 1) / LIMIT_TILE);
-    a.e_bs = std::max(n_max, 1L);
+    const DevRows rows = stage_rows(c, "lim", in, nsamples, B, Nmax, flags);
+    a.x = rows.x; a.x_bs = Nmax; a.nsamples = rows.len; a.B = B;
+    a.ppitch = (int)std::max(1L, (r.n_max + LIMIT_TILE - 1) / LIMIT_TILE);
+    a.e_bs = std::max(r.n_max, 1L);
     a.env = lim ? c->fbuf("lim.env", (size_t)B * a.e_bs) : nullptr;
     a.part_max = c->fbuf("lim.part", (size_t)2 * B * a.ppitch);
     a.part_min = lim ? a.part_max + (size_t)B * a.ppitch : nullptr;
     a.res = c->fbuf("lim.res", (size_t)2 * B);
-    void* odev = host_out ? c->buf("lim.out", (size_t)B * ostage * ss + 16) : out;
-    a.out = odev; a.out_bs = host_out ? ostage : (long)out_stride; a.pcm16 = pcm16;
-    const std::string keep = c->tag;
-    c->tag = "post.limit";
-    struct Untag { zvx_ctx* c; const std::string& keep; ~Untag() { c->tag = keep; } } untag{c, keep};
-    c->timed(0.0, 4.0 * n_sum + (lim ? (double)ss * n_sum : 0.0), [&] {
+    a.out = ret.out_rows("lim.out", out, out_stride, &a.out_bs); a.pcm16 = (flags & ZVX_PCM16) ? 1 : 0;
+    TagScope scope(c, "post.limit");
+    c->timed(0.0, 4.0 * r.n_sum + (lim ? (double)ret.ss * r.n_sum : 0.0), [&] {
         launch_limit_env(a, c->stream);
         if (lim && !launch_limit_gain(a, c->stream)) fail(ZVX_E_UNSUPPORTED, "%s: a window of %d samples does not fit the LDS of a workgroup", who, W);
         launch_limit_reduce(a, c->stream);
     });
-    if (want_host) HIPCHK(hipMemcpyAsync(host, a.res, res_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (host_out && n_max > 0) HIPCHK(hipMemcpyAsync(host + res_pad, odev, (size_t)B * ostage * ss, hipMemcpyDeviceToHost, c->stream));
-    if (!want_host && (flags & ZVX_NO_SYNC)) return;         // device output, nothing for the host: the call only queues
-    c->sync();                                               // the call's one wait
-    if (want_host) {
-        const float* r_h = (const float*)host;
-        for (int b = 0; b < B; b++) {
-            if (peak_in) peak_in[b] = r_h[b];
-            if (min_gain) min_gain[b] = r_h[B + b];
-        }
+    const float* r_h = (const float*)ret.finish(a.res, out, out_stride, nsamples, flags);
+    if (!r_h) return;
+    for (int b = 0; b < B; b++) {
+        if (peak_in) peak_in[b] = r_h[b];
+        if (min_gain) min_gain[b] = r_h[B + b];
     }
-    if (host_out)
-        for (int b = 0; b < B; b++)
-            if (nsamples[b] > 0) memcpy((char*)out + (size_t)b * out_stride * ss, host + res_pad + (size_t)b * ostage * ss, (size_t)nsamples[b] * ss);
 }
 
 // wav: float rows, or int16 PCM rows with ZVX_PCM16 (stride counted in samples either way).  Row b receives
@@ -2533,7 +2530,9 @@ void do_vocode(zvx_ctx* c, const int32_t* pad_to, void* wav, int64_t wav_stride,
     std::vector<int> P(B);
     int need = 0, need_native = 0;
     for (int b = 0; b < B; b++) { P[b] = std::max(pad_to ? pad_to[b] : 0, c->mel_len_host[b]); need_native = std::max(need_native, c->mel_len_host[b] * c->hop); }
-    need = rs ? (int)rs_out_len(need_native, rs_L, rs_M) : need_native;
+    // each utterance is resampled as a signal of its own length, mel_len[b] * hop
+    const RsPlan plan = rs ? rs_plan(c->mel_len_host.data(), c->hop, B, rs_L, rs_M) : RsPlan{};
+    need = rs ? (int)plan.out_max : need_native;
     const bool host_async = flags & ZVX_HOST_ASYNC;
     if (!host_async && wav_stride < need) fail(ZVX_E_BUFFER, "wav_stride %lld < %d samples", (long long)wav_stride, need);
     const zvx_ctx::RsBank* bank = rs ? &rs_bank(c, rs_L, rs_M) : nullptr;
@@ -2577,10 +2576,8 @@ void do_vocode(zvx_ctx* c, const int32_t* pad_to, void* wav, int64_t wav_stride,
         float* native = c->fbuf("wav.native", (size_t)B * nstride);
         run_vocoder(c, c->fbuf("mel", 0), c->n_mels, c->Lmax, c->mel_len_host.data(), P.data(), B, native, nstride, 0);
         c->stage_end(ZVX_T_VOCODER);
-        double nin = 0, nout = 0;
-        for (int b = 0; b < B; b++) { nin += (double)c->mel_len_host[b] * c->hop; nout += (double)rs_out_len((long)c->mel_len_host[b] * c->hop, rs_L, rs_M); }
-        // each utterance is resampled as a signal of its own length, mel_len[b] * hop (the first B words of the vocoder's length table)
-        if (need > 0) run_resample(c, *bank, native, nstride, c->ibuf("voc.lens", 0), c->hop, B, wdev, wstride, pcm16, 0, 0, -1, need, nin, nout);
+        // (the lengths on the device: the first B words of the vocoder's length table)
+        run_resample(c, *bank, native, nstride, c->ibuf("voc.lens", 0), c->hop, B, wdev, wstride, pcm16, plan);
     } else {
         run_vocoder(c, c->fbuf("mel", 0), c->n_mels, c->Lmax, c->mel_len_host.data(), P.data(), B, wdev, wstride, pcm16);
         c->stage_end(ZVX_T_VOCODER);
