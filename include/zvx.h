@@ -401,7 +401,8 @@ zvx_status zvx_normalize(zvx_ctx* ctx, const float* in, const int32_t* nsamples,
  * Depth, in double: d[i] = e[i] > c ? 1 - (double) c / (double) e[i] : 0;  r[i] = 1 - d[i].
  * Hold: D[i] = the maximum of d[j] over |j - i| <= W, 0 <= j < n (exact: any order).
  * Smooth: w[k] = (1 + cos(pi k / (W + 1))) / (2 (W + 1)), k = -W .. W, designed on the host in double, divided by their own sum (in exact
- *   arithmetic they sum to 1 already) and cached per W;  s[i] = 1 - sum_k w[k] D[clamp(i + k, 0, n - 1)], a double sum in any order.
+ *   arithmetic they sum to 1 already) and cached per W;  s[i] = 1 - sum_k w[k] D[clamp(i + k, 0, n - 1)], a double sum (one fma per term, from 0) in
+ *   ascending k = -W .. W -- the order is part of the contract: it is what makes the windows of zvx_limit_ex concatenate to the bit.
  * Gain: g[i] = min(s[i], r[i]);  g32[i] = g[i] rounded toward zero to f32;  out[i] = x[i] * g32[i], ONE f32 multiply; with ZVX_PCM16 the
  *   resampler's rule follows.
  * What follows from that:
@@ -429,7 +430,7 @@ zvx_status zvx_normalize(zvx_ctx* ctx, const float* in, const int32_t* nsamples,
  *   is not finite or outside (0, 8], a window_ms that is not finite or <= 0, an oversample outside {1, 2, 4, 8}.  ZVX_E_UNSUPPORTED: more
  *   than 65535 rows, W > 4096.
  * Stage tag "post.limit" in zvx_tag_stats (one timed group per call; no stage slot): algorithmic bytes = 4 sum(n) for zvx_true_peak;
- *   4 sum(n) read plus the bytes written for zvx_limit.
+ *   4 sum(n) read plus the bytes written for zvx_limit and zvx_limit_ex (4 or, with ZVX_PCM16, 2 per emitted sample).
  * Replaces a host-side true-peak meter and limiter behind zvx_normalize, whose gain a sample-peak ceiling otherwise bounds. */
 typedef struct zvx_limit_params {
     float   ceiling;     /* linear ceiling c, finite, 0 < c <= 8 (0.891 = -1 dBFS) */
@@ -444,6 +445,30 @@ zvx_status zvx_true_peak(zvx_ctx* ctx, const float* in, const int32_t* nsamples,
  * flags: ZVX_DEVICE_IN, ZVX_DEVICE_OUT, ZVX_NO_SYNC (device out only), ZVX_PCM16 (not in place); out == in (same stride) allowed for f32 */
 zvx_status zvx_limit(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, int rate,
                      const zvx_limit_params* params, void* out, int64_t out_stride, float* peak_in, float* min_gain, int flags);
+/* The same limiter over a window, so that a stream is limited piece by piece and comes out bit-identical to one whole-signal call (as
+ * zvx_resample_ex converts one).  Row b holds samples [in_origin, in_origin + nsamples[b]) of a signal x that starts at sample 0; with
+ * last != 0 x ends at N_b = in_origin + nsamples[b], with last == 0 it continues past the window.  The outputs [out_begin, out_begin + cnt_b)
+ * of zvx_limit on the WHOLE signal go to positions [0, cnt_b) of out row b; nothing else in out is touched.  cnt_b = out_count; with
+ * out_count == -1, which needs last, cnt_b = in_origin + nsamples[b] - out_begin (to the end of the row's signal; none where that is <= 0).
+ * Reach: R = 2 W + H, H = 11 for oversample > 1 and H = 0 for oversample 1: e[j] reads x[j - 11 .. j + 11], hold and smoothing reach W each.
+ * Support condition, per row with cnt_b > 0 (otherwise ZVX_E_INVALID; the message names the row, R and the missing samples):
+ *     in_origin <= out_begin  and  out_begin + cnt_b <= in_origin + nsamples[b];
+ *     left:  in_origin == 0  or  out_begin - R >= in_origin;
+ *     right: last  or  out_begin + cnt_b - 1 + R <= in_origin + nsamples[b] - 1.
+ *   Under it no emitted sample sees a cut edge: the clamps at 0 and N - 1 and the zeros outside the row are then the true signal's.
+ * Results: the emitted samples are bit for bit those of zvx_limit on the whole signal (f32, and int16 with ZVX_PCM16): the oversampled
+ *   sums run in the fixed tap order, the hold is an exact maximum and the smoothing sum runs in ascending k whatever the window.
+ *   peak_in[b] = max e[i] and min_gain[b] = min g32[i] over the EMITTED range only, so the max / min over a stream's pieces are the whole
+ *   call's values; an empty range writes nothing and gives 0 and 1.
+ * zvx_limit is zvx_limit_ex(..., 0, 0, -1, 1).  Validation: every check of zvx_limit (out_stride >= Nmax included), and ZVX_E_INVALID for a
+ *   negative in_origin or out_begin, out_count < -1, out_count == -1 without last, last outside {0, 1}, out_stride smaller than the
+ *   longest cnt_b, out == in unless out_begin == in_origin (then zvx_limit's in-place conditions apply).  Flags, syncs, the queued form,
+ *   the non-finite rule and the "post.limit" tag are zvx_limit's; `last` is a parameter, not a flag bit.
+ * A stream: zerovox_amd/limiter.py plans the windows -- a non-last push emits up to received - R, the last one everything, the history
+ *   before next_out - R is dropped -- so a limited stream runs R samples behind its input (231 samples for 5 ms at 22.05 kHz, os 4). */
+zvx_status zvx_limit_ex(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, int rate,
+                        const zvx_limit_params* params, void* out, int64_t out_stride, float* peak_in, float* min_gain, int flags,
+                        int64_t in_origin, int64_t out_begin, int64_t out_count, int last);
 
 /* Debug/parity taps: copy an intermediate of the last call to host fp32.
  * what: "encoder_out" [B][Tmax][hidden] (after the style add), "features" [B][Lmax][hidden],

@@ -1,11 +1,20 @@
 """First-audio latency of the chunked vocoder: one 896-frame mel, HiFi-GAN V1, batch 1.
    python tools/stream_latency.py [out.json]   -> per chunk size: time to the first waveform chunk, time for all chunks, and
-   the whole-utterance call for comparison (host mel in, host waveform out: the PCIe copies are inside every figure)."""
-import json, os, sys, time
+   the whole-utterance call for comparison (host mel in, host waveform out: the PCIe copies are inside every figure).
+   python tools/stream_latency.py --peak-db DB [--limiter-ms MS] [out.json]   -> the same stream WITH and WITHOUT the windowed limiter
+   (zvx_limit_ex at DB dBFS, 4x oversampled envelope), in this one process: first audio, all chunks and the median time between two
+   pieces for both, and the samples the limited stream runs behind (limiter.reach)."""
+import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from zerovox_amd import config as zcfg, weights as zw
 from zerovox_amd.model import ZeroVox
+
+ap = argparse.ArgumentParser()
+ap.add_argument("out", nargs="?", help="write the result as JSON here")
+ap.add_argument("--peak-db", type=float, default=None, metavar="DB", help="also time the stream limited at this ceiling (dBFS)")
+ap.add_argument("--limiter-ms", type=float, default=5.0, metavar="MS")
+args = ap.parse_args()
 
 cfg = zcfg.medium_modelcfg("styletts"); sd = zw.tts_state_dict(cfg, 0)
 h = zcfg.hifigan_config("v1"); hsd = zw.hifigan_state_dict(h, 0)
@@ -25,6 +34,17 @@ def best(f, n=20):
     return float(np.median(ts)) * 1e3
 
 
+def piece_gap(make_stream, n=5):
+    """median time between two successive pieces of a stream, ms, over n runs (the first piece, which carries the start-up, is not counted)"""
+    gaps = []
+    for _ in range(n):
+        ts = [time.perf_counter()]
+        for _ in make_stream():
+            ts.append(time.perf_counter())
+        gaps += list(np.diff(ts)[1:])
+    return float(np.median(gaps)) * 1e3 if gaps else 0.0
+
+
 res = {"workload": f"one {L}-frame mel ({L * 256 / 22050:.2f} s of audio), HiFi-GAN V1 bf16, batch 1, halo {STREAM_HALO} frames per side",
        "whole_utterance_ms": best(lambda: ctx.vocode_mel(mel[None], np.array([L], np.int32))), "chunks": []}
 for cf in (16, 32, 64, 128, 256):
@@ -33,7 +53,23 @@ for cf in (16, 32, 64, 128, 256):
     total = best(lambda: list(model.vocode_stream(mel, chunk_frames=cf)), n=5)
     res["chunks"].append({"chunk_frames": cf, "chunk_audio_ms": round(cf * 256 / 22.05, 1), "first_chunk_ms": round(first, 3), "all_chunks_ms": round(total, 3),
                           "bit_equal_to_whole": bool(np.array_equal(got, whole)), "max_abs_diff": float(np.abs(got - whole).max())})
+    if args.peak_db is not None:
+        from zerovox_amd.limiter import reach, window_samples
+        from zerovox_amd.longform import limit_keywords
+        lim = limit_keywords(True, args.limiter_ms, args.peak_db)
+        native = ctx.get_int("sampling_rate")
+        limited = np.concatenate(list(model.vocode_stream(mel, chunk_frames=cf, limiter=lim)))
+        want = ctx.limit([whole], rate=native, **lim)[0][0]
+        res["chunks"][-1].update({
+            "piece_gap_ms": round(piece_gap(lambda: model.vocode_stream(mel, chunk_frames=cf)), 3),
+            "limited": {"peak_db": args.peak_db, "limiter_ms": args.limiter_ms,
+                        "delay_samples": reach(window_samples(native, args.limiter_ms), lim["oversample"]),
+                        "first_piece_ms": round(best(lambda: next(iter(model.vocode_stream(mel, chunk_frames=cf, limiter=lim)))), 3),
+                        "all_pieces_ms": round(best(lambda: list(model.vocode_stream(mel, chunk_frames=cf, limiter=lim)), n=5), 3),
+                        "piece_gap_ms": round(piece_gap(lambda: model.vocode_stream(mel, chunk_frames=cf, limiter=lim)), 3),
+                        "bit_equal_to_whole_limit": bool(np.array_equal(limited, want)),
+                        "samples_changed": int(np.count_nonzero(limited != got))}})
     print(res["chunks"][-1], flush=True)
 print(json.dumps(res))
-if len(sys.argv) > 1:
-    json.dump(res, open(sys.argv[1], "w"), indent=1)
+if args.out:
+    json.dump(res, open(args.out, "w"), indent=1)

@@ -25,11 +25,12 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_comm_unique_id", "zvx_comm_init", "zvx_comm_gather", "zvx_comm_barrier", "zvx_comm_max_f64", "zvx_comm_info", "zvx_comm_destroy",
            "zvx_dev_alloc", "zvx_dev_free", "zvx_dev_from_host", "zvx_dev_to_host", "zvx_spkemb_ex", "zvx_wait_host",
            "zvx_encode_ex", "zvx_synthesize_ex", "zvx_resample", "zvx_resample_ex", "zvx_trim_bounds", "zvx_join",
-           "zvx_loudness", "zvx_normalize", "zvx_true_peak", "zvx_limit", "zvx_spkemb_wav")
+           "zvx_loudness", "zvx_normalize", "zvx_true_peak", "zvx_limit", "zvx_spkemb_wav", "zvx_limit_ex")
 ZVX_COMM_ID_BYTES = 128
 ZVX_LOUD_PER_ROW, ZVX_LOUD_COMMON = 0, 1
 LIMIT_TILE = 1024                                    # samples per workgroup of both limiter kernels (csrc/zvx_kernels.h, LIMIT_TILE)
 LIMIT_MAX_W = 4096                                   # the longest window, in samples (LIMIT_MAX_W)
+LIMIT_ENV_REACH = 11                                 # samples the oversampled envelope reads to either side (LIMIT_ENV_REACH; limiter.reach)
 
 
 def resampled_len(n, rate_in, rate_out):
@@ -131,6 +132,7 @@ def load():
     lib.zvx_normalize.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(LoudnessParams), vp, C.c_int64, vp, vp, vp, C.c_int]
     lib.zvx_true_peak.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int]
     lib.zvx_limit.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(LimitParams), vp, C.c_int64, vp, vp, C.c_int]
+    lib.zvx_limit_ex.argtypes = lib.zvx_limit.argtypes + [C.c_int64, C.c_int64, C.c_int64, C.c_int]
     lib.zvx_spkemb_wav.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(RefParams), vp, vp, vp, vp, C.c_int]
     _lib = lib
     return lib
@@ -386,6 +388,24 @@ class Context:
         self._chk(self._lib.zvx_limit(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), Nmax, _ptr(peak), _ptr(gmin),
                                       ZVX_PCM16 if pcm16 else 0))
         return out, peak, gmin
+
+    def limit_window(self, rows, ceiling, window_ms=5.0, oversample=4, in_origin=0, out_begin=0, out_count=-1, last=True, pcm16=False,
+                     rate=None, lengths=None):
+        """zvx_limit_ex on host rows: the rows hold samples [in_origin, in_origin + len) of signals that start at sample 0 and, with
+        `last`, end with the row; the outputs [out_begin, out_begin + out_count) of the whole-signal limiter (out_count -1, which needs
+        last: to the end of each row's signal) -> (out [B][n] float32 / int16 -- row b holds its emitted samples, then zeros --,
+        peak_in [B], min_gain [B] float32, both over the emitted samples only).  The window must carry limiter.reach(W, oversample)
+        samples of support on either side of the outputs, except at the signal's own ends (include/zvx.h)."""
+        x, n = self._rows(rows, lengths)
+        B, Nmax = x.shape
+        prm = LimitParams(float(ceiling), float(window_ms), int(oversample))
+        cols = int(out_count) if out_count >= 0 else max(0, int(in_origin) + int(n.max() if B else 0) - int(out_begin))
+        stride = max(cols, Nmax)
+        out = np.zeros((B, stride), np.int16 if pcm16 else np.float32)
+        peak, gmin = np.zeros(B, np.float32), np.zeros(B, np.float32)
+        self._chk(self._lib.zvx_limit_ex(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), stride, _ptr(peak), _ptr(gmin),
+                                         ZVX_PCM16 if pcm16 else 0, int(in_origin), int(out_begin), int(out_count), 1 if last else 0))
+        return out[:, :cols], peak, gmin
 
     def limit_device(self, ptr, lengths, Nmax, ceiling, *, window_ms=5.0, oversample=4, rate=None, no_sync=False):
         """zvx_limit IN PLACE on device rows [B][Nmax] f32 at `ptr` (they may be the output of a synthesize / normalize_device call queued

@@ -1853,7 +1853,7 @@ void launch_loud_apply(const LoudApplyArgs& a, long n_max, hipStream_t s) {
 
 // ---------------------------------------------------------------- true-peak envelope and look-ahead limiter (zvx_kernels.h, include/zvx.h: zvx_limit)
 constexpr int LIM_T = 21;                    // taps per oversampled point: ceil((20 os + 1) / os) for every os
-constexpr int LIM_LO = 10, LIM_HI = 11;      // phase 0 starts 10 samples in front of its sample; the others 9 in front, 11 behind (the last tap is a 0)
+constexpr int LIM_LO = 10, LIM_HI = LIMIT_ENV_REACH;      // phase 0 starts 10 samples in front of its sample; the others 9 in front, 11 behind (the last tap is a 0)
 constexpr int LIM_XS = LIMIT_TILE + 1 + LIM_LO + LIM_HI;
 constexpr int LIM_BP = 24;                   // pitch of the bank's copy in LDS
 __device__ __forceinline__ float wg_max_f32(float v, float* red) {
@@ -1913,6 +1913,7 @@ __global__ __launch_bounds__(256) void k_limit_env(const LimitArgs a) {
         }
         __syncthreads();
         float* erow = a.env ? a.env + (long)b * a.e_bs : nullptr;
+        const long o0 = a.off, o1 = o0 + a.cnt[b];           // the partial maximum runs over the emitted samples only
 #pragma unroll
         for (int q = 0; q < LIMIT_TILE / 256; q++) {
             const int j = 1 + tid + 256 * q;
@@ -1920,7 +1921,7 @@ __global__ __launch_bounds__(256) void k_limit_env(const LimitArgs a) {
             if (i < n) {
                 const float e = fmaxf(fmaxf(eo[j], uo[j]), uo[j - 1]);
                 if (erow) erow[i] = e;
-                pk = fmaxf(pk, e);
+                if (i >= o0 && i < o1) pk = fmaxf(pk, e);
             }
         }
     }
@@ -1950,10 +1951,11 @@ __global__ __launch_bounds__(256) void k_limit_gain(const LimitArgs a) {
     float* red = es + SE;                                    // (no static LDS: the opt-in beyond 64 KiB covers the dynamic part alone)
     const int b = blockIdx.y, tid = threadIdx.x;
     const int n = a.nsamples[b];
-    const long t0 = (long)blockIdx.x * LIMIT_TILE;
+    const long t0 = a.off + (long)blockIdx.x * LIMIT_TILE;   // the tiles cover the emitted range [off, iend), wherever `off` lies
+    const long iend = min((long)n, (long)a.off + a.cnt[b]);
     constexpr int Q = LIMIT_TILE / 256;
     float gmin = 1.f;
-    if (t0 < n) {                                            // (uniform over the workgroup)
+    if (t0 < iend) {                                         // (uniform over the workgroup)
         const float* erow = a.env + (long)b * a.e_bs;
         const float* xrow = a.x + (long)b * a.x_bs;
         const long eb = t0 - 2L * W;                         // es[j] = e[eb + j]
@@ -2014,10 +2016,10 @@ __global__ __launch_bounds__(256) void k_limit_gain(const LimitArgs a) {
 #pragma unroll
         for (int q = 0; q < Q; q++) {
             const long i = t0 + tid + 256 * q;
-            if (i < n) {
+            if (i < iend) {
                 const float v = xrow[i] * g32[q];
-                if (a.pcm16) ((short*)a.out)[(long)b * a.out_bs + i] = join_pcm(v);
-                else ((float*)a.out)[(long)b * a.out_bs + i] = v;
+                if (a.pcm16) ((short*)a.out)[(long)b * a.out_bs + (i - a.off)] = join_pcm(v);
+                else ((float*)a.out)[(long)b * a.out_bs + (i - a.off)] = v;
                 gmin = fminf(gmin, g32[q]);
             }
         }
@@ -2030,7 +2032,7 @@ bool launch_limit_gain(const LimitArgs& a, hipStream_t s) {
     const size_t lds = (size_t)(LIMIT_TILE + 2 * a.W) * 8 + (size_t)(LIMIT_TILE + 4 * a.W) * 4 + 16;
     if (lds > 160 * 1024) return false;
     if (lds > 64 * 1024 && !lds_opt_in((const void*)k_limit_gain)) return false;
-    hipLaunchKernelGGL(k_limit_gain, dim3((unsigned)a.ppitch, a.B), dim3(256), lds, s, a);
+    hipLaunchKernelGGL(k_limit_gain, dim3((unsigned)a.gtiles, a.B), dim3(256), lds, s, a);
     return true;
 }
 
@@ -2040,7 +2042,7 @@ __global__ __launch_bounds__(256) void k_limit_reduce(const LimitArgs a) {
     float mx = 0.f, mn = 1.f;
     for (int i = tid; i < a.ppitch; i += 256) {
         mx = fmaxf(mx, a.part_max[(long)b * a.ppitch + i]);
-        if (a.part_min) mn = fminf(mn, a.part_min[(long)b * a.ppitch + i]);
+        if (a.part_min && i < a.gtiles) mn = fminf(mn, a.part_min[(long)b * a.ppitch + i]);
     }
     mx = wg_max_f32(mx, red);
     mn = -wg_max_f32(-mn, red);

@@ -2462,9 +2462,40 @@ const double* limit_win(zvx_ctx* c, int W) {
     return c->lim_wins[W] = d;
 }
 
-// zvx_true_peak (p == nullptr: the envelope's maximum only, results in tpeak) and zvx_limit
+// The window of zvx_limit_ex: the rows hold samples [in_origin, in_origin + nsamples[b]) of their signals, the outputs [out_begin,
+// out_begin + cnt_b) are emitted.  The whole-row calls are {0, 0, -1, 1}.
+struct LimitWindow { int64_t in_origin = 0, out_begin = 0, out_count = -1; int last = 1; };
+// per row the emitted count, after the window's own checks and the support condition of include/zvx.h (R = 2 W + H)
+std::vector<int32_t> limit_window_counts(const char* who, const LimitWindow& w, const int32_t* nsamples, int B, int W, int os) {
+    if (w.in_origin < 0 || w.out_begin < 0) fail(ZVX_E_INVALID, "%s: in_origin %lld / out_begin %lld is negative", who, (long long)w.in_origin, (long long)w.out_begin);
+    if (w.out_count < -1) fail(ZVX_E_INVALID, "%s: out_count %lld (-1: to the end of the signal)", who, (long long)w.out_count);
+    if (w.last != 0 && w.last != 1) fail(ZVX_E_INVALID, "%s: last is %d (0 or 1)", who, w.last);
+    if (w.out_count == -1 && !w.last) fail(ZVX_E_INVALID, "%s: out_count -1 needs last: the signal's end is not in the window", who);
+    const int64_t R = 2 * (int64_t)W + (os > 1 ? LIMIT_ENV_REACH : 0);
+    std::vector<int32_t> cnt(B);
+    for (int b = 0; b < B; b++) {
+        const int64_t end_in = w.in_origin + nsamples[b];
+        const int64_t n = w.out_count >= 0 ? w.out_count : std::max<int64_t>(0, end_in - w.out_begin);
+        if (n > 0) {
+            const int64_t end_out = w.out_begin + n;
+            if (w.in_origin > w.out_begin || end_out > end_in)
+                fail(ZVX_E_INVALID, "%s: row %d: outputs [%lld, %lld) lie outside the window's samples [%lld, %lld)", who, b, (long long)w.out_begin,
+                     (long long)end_out, (long long)w.in_origin, (long long)end_in);
+            if (w.in_origin != 0 && w.out_begin - R < w.in_origin)
+                fail(ZVX_E_INVALID, "%s: row %d: the reach R = %lld needs %lld more samples in front of the window (in_origin %lld, out_begin %lld)", who, b,
+                     (long long)R, (long long)(w.in_origin - (w.out_begin - R)), (long long)w.in_origin, (long long)w.out_begin);
+            if (!w.last && end_out - 1 + R > end_in - 1)
+                fail(ZVX_E_INVALID, "%s: row %d: the reach R = %lld needs %lld more samples behind the window (outputs end at %lld, samples at %lld; or last)", who, b,
+                     (long long)R, (long long)(end_out + R - end_in), (long long)end_out, (long long)end_in);
+        }
+        cnt[b] = (int32_t)n;                                 // n <= nsamples[b] where n > 0
+    }
+    return cnt;
+}
+
+// zvx_true_peak (p == nullptr: the envelope's maximum only, results in tpeak), zvx_limit and zvx_limit_ex (win != nullptr)
 void do_limit(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_limit_params* p,
-              int oversample, void* out, int64_t out_stride, float* peak_in, float* min_gain, int flags) {
+              int oversample, void* out, int64_t out_stride, float* peak_in, float* min_gain, int flags, const LimitWindow* win = nullptr) {
     const bool lim = p != nullptr;
     if (!lim && !peak_in) fail(ZVX_E_INVALID, "%s: tpeak is NULL", who);
     const RowsInfo r = rows_check(who, in, nsamples, B, Nmax, 65535);
@@ -2483,7 +2514,19 @@ void do_limit(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamp
         if (w > (double)LIMIT_MAX_W) fail(ZVX_E_UNSUPPORTED, "%s: window of %.0f samples (at most %d)", who, w, LIMIT_MAX_W);
         W = (int)w;
     }
-    RowsReturn ret(c, B, (size_t)B * 8, peak_in || min_gain, lim, r.n_max, flags);      // words: peak [B], then min gain [B]
+    // the emitted range: [off, off + cnt[b]) of row b; the whole row unless a window is given
+    std::vector<int32_t> cnt_win;
+    const int32_t* cnt = nsamples;
+    long off = 0, cnt_max = r.n_max; double cnt_sum = r.n_sum;
+    if (win) {
+        cnt_win = limit_window_counts(who, *win, nsamples, B, W, os);
+        cnt = cnt_win.data(); off = (long)(win->out_begin - win->in_origin); cnt_max = 0; cnt_sum = 0;
+        for (int b = 0; b < B; b++) { cnt_max = std::max<long>(cnt_max, cnt[b]); cnt_sum += cnt[b]; }
+        if (cnt_max == 0) off = 0;
+        if (out_stride < cnt_max) fail(ZVX_E_INVALID, "%s: out_stride %lld is smaller than the longest output row %ld", who, (long long)out_stride, cnt_max);
+        if (out == (const void*)in && off != 0) fail(ZVX_E_INVALID, "%s: in place needs out_begin == in_origin", who);
+    }
+    RowsReturn ret(c, B, (size_t)B * 8, peak_in || min_gain, lim, cnt_max, flags);      // words: peak [B], then min gain [B]
     LimitArgs a{};
     a.os = os;
     if (os > 1) {
@@ -2495,6 +2538,8 @@ void do_limit(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamp
     const DevRows rows = stage_rows(c, "lim", in, nsamples, B, Nmax, flags);
     a.x = rows.x; a.x_bs = Nmax; a.nsamples = rows.len; a.B = B;
     a.ppitch = (int)std::max(1L, (r.n_max + LIMIT_TILE - 1) / LIMIT_TILE);
+    a.off = (int)off; a.cnt = win ? c->upload_ints("lim.cnt", cnt, B) : rows.len;
+    a.gtiles = (int)std::max(1L, (cnt_max + LIMIT_TILE - 1) / LIMIT_TILE);                // <= ppitch: cnt[b] <= nsamples[b]
     a.e_bs = std::max(r.n_max, 1L);
     a.env = lim ? c->fbuf("lim.env", (size_t)B * a.e_bs) : nullptr;
     a.part_max = c->fbuf("lim.part", (size_t)2 * B * a.ppitch);
@@ -2502,12 +2547,12 @@ void do_limit(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamp
     a.res = c->fbuf("lim.res", (size_t)2 * B);
     a.out = ret.out_rows("lim.out", out, out_stride, &a.out_bs); a.pcm16 = (flags & ZVX_PCM16) ? 1 : 0;
     TagScope scope(c, "post.limit");
-    c->timed(0.0, 4.0 * r.n_sum + (lim ? (double)ret.ss * r.n_sum : 0.0), [&] {
+    c->timed(0.0, 4.0 * r.n_sum + (lim ? (double)ret.ss * cnt_sum : 0.0), [&] {
         launch_limit_env(a, c->stream);
         if (lim && !launch_limit_gain(a, c->stream)) fail(ZVX_E_UNSUPPORTED, "%s: a window of %d samples does not fit the LDS of a workgroup", who, W);
         launch_limit_reduce(a, c->stream);
     });
-    const float* r_h = (const float*)ret.finish(a.res, out, out_stride, nsamples, flags);
+    const float* r_h = (const float*)ret.finish(a.res, out, out_stride, cnt, flags);
     if (!r_h) return;
     for (int b = 0; b < B; b++) {
         if (peak_in) peak_in[b] = r_h[b];
@@ -2910,6 +2955,16 @@ zvx_status zvx_limit(zvx_ctx* c, const float* in, const int32_t* nsamples, int B
     return guarded(c, [&] {
         if (!params) fail(ZVX_E_INVALID, "zvx_limit: params is NULL");
         do_limit(c, "zvx_limit", in, nsamples, B, Nmax, rate, params, 0, out, out_stride, peak_in, min_gain, flags);
+    });
+}
+
+zvx_status zvx_limit_ex(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_limit_params* params,
+                        void* out, int64_t out_stride, float* peak_in, float* min_gain, int flags,
+                        int64_t in_origin, int64_t out_begin, int64_t out_count, int last) {
+    return guarded(c, [&] {
+        if (!params) fail(ZVX_E_INVALID, "zvx_limit_ex: params is NULL");
+        const LimitWindow win{in_origin, out_begin, out_count, last};
+        do_limit(c, "zvx_limit_ex", in, nsamples, B, Nmax, rate, params, 0, out, out_stride, peak_in, min_gain, flags, &win);
     });
 }
 

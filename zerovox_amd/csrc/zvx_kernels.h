@@ -411,26 +411,31 @@ struct LoudApplyArgs {
 void launch_loud_apply(const LoudApplyArgs& a, long n_max, hipStream_t s);
 // True-peak envelope and look-ahead limiter of a batch's waveform rows (include/zvx.h, zvx_true_peak / zvx_limit).  Both kernels work on
 // tiles of LIMIT_TILE samples of one row, 256 threads each; lengths are read on the DEVICE and nothing outside [0, nsamples[b]) is read
-// or written.
+// or written.  The windowed form (zvx_limit_ex) emits the samples [off, off + cnt[b]) of the row only: the envelope is still evaluated over
+// the whole row, the gain tiles start at `off` -- any sample offset from the envelope's tile grid -- and write out[b][i - off]; the
+// arithmetic of a sample depends on neither grid.  The whole-row form is off = 0, cnt = nsamples.
 constexpr int LIMIT_TILE = 1024;             // (zerovox_amd/_lib.py carries the same figure for the tests' tile-edge rows)
 constexpr int LIMIT_MAX_W = 4096;
+constexpr int LIMIT_ENV_REACH = 11;          // e[j] reads x[j - 11 .. j + 11] where os > 1 (include/zvx.h, zvx_limit_ex: H; _lib.py: LIMIT_ENV_REACH)
 struct LimitArgs {
     const float* x; long x_bs; const int* nsamples; int B;
     int os, T, pitch; const float* bank;     // os > 1: the resampler's bank of (L, M) = (os, 1) (ResampleArgs), T = 21; os == 1: unused
     float* env; long e_bs;                   // e[b][i], the envelope (f32); NULL: only the partial maxima are wanted (zvx_true_peak)
-    float* part_max; float* part_min; int ppitch;   // [b][tile]: max e / min g32 over the tile (0 / 1 where the tile lies behind the row)
+    float* part_max; float* part_min; int ppitch;   // [b][tile]: max e / min g32 over the tile's EMITTED samples (0 / 1 where it has none)
+    int off; const int* cnt; int gtiles;     // the emitted range [off, off + cnt[b]) of row b (device array); tiles of the gain launch (<= ppitch)
     float c; int W; const double* win;       // the ceiling; the smoothing weights win[k + W], k = -W .. W
     void* out; long out_bs; int pcm16;
     float* res;                              // launch_limit_reduce: res[b] = max over part_max[b][.], res[B + b] = min over part_min[b][.]
 };
 // e[b][i] = max(|x[i]|, |y[m]| for os (i - 1) < m < os (i + 1), 0 <= m < os n): the tile plus a halo of 10 samples in front and 11 behind
 // is staged in LDS, every thread holds one sample's 22 inputs in registers and sums the os phases in the resampler's own order (so y has
-// the bits zvx_resample gives), nothing of y reaches memory.  grid.x = ppitch tiles.
+// the bits zvx_resample gives), nothing of y reaches memory.  grid.x = ppitch tiles over the whole row.
 void launch_limit_env(const LimitArgs& a, hipStream_t s);
 // hold, smooth, gain and multiply of one tile: the envelope of the tile and 2 W samples on either side is held in LDS, its running maximum
 // over 2 W + 1 samples is built by doubling (the depth is monotone in e, so the maximum of the depths is the depth of the maximum), the
 // depths D of the tile and W on either side follow in double, then s, g, g32 and out = x * g32.  A tile whose whole span stays at or
-// below the ceiling copies its samples.  It reads e, never a neighbour's x: safe in place.  false: the span does not fit the LDS.
+// below the ceiling copies its samples.  It reads e, never a neighbour's x: safe in place (off = 0).  grid.x = gtiles tiles from `off` on.
+// false: the span does not fit the LDS.
 bool launch_limit_gain(const LimitArgs& a, hipStream_t s);
 // one workgroup per row over the tiles' partial results
 void launch_limit_reduce(const LimitArgs& a, hipStream_t s);

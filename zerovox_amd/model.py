@@ -197,21 +197,29 @@ class ZeroVox:
     # each side makes a chunk's interior identical to the same samples of a whole-utterance pass.
     STREAM_HALO = 16
 
-    def vocode_stream(self, mel, chunk_frames=64, halo=STREAM_HALO, chunks_per_call=1):
+    def vocode_stream(self, mel, chunk_frames=64, halo=STREAM_HALO, chunks_per_call=1, limiter=None):
         """Chunked vocoding for first-audio latency: mel [L, n_mels] -> yields waveform chunks (np.float32) that
         concatenate to ``vocode_mel(mel)``.  Every chunk is vocoded with ``halo`` extra frames on each side and only its
         interior is kept; ``chunks_per_call`` chunks ride in one launch sequence as independent batch rows.
         Under an output rate (the context's "out_rate") the chunks are still vocoded at the native rate (ZVX_NATIVE_RATE) and the
         stream is converted window by window (zerovox_amd.resample): the pieces concatenate bit for bit to the conversion of the
-        whole native stream; a piece is yielded once every sample under its filter has arrived."""
-        rate, native = self._ctx.get_int("out_rate"), self._ctx.get_int("sampling_rate")
-        if rate > 0 and rate != native:
+        whole native stream; a piece is yielded once every sample under its filter has arrived.
+        limiter: None, or the keywords longform.limit_keywords builds (ceiling, window_ms, oversample): the native-rate chunks pass
+        through the windowed limiter (zerovox_amd.limiter, zvx_limit_ex) and concatenate bit for bit to zvx_limit of the whole native
+        stream; the limited stream runs limiter.reach(W, oversample) samples behind the vocoder.  Limiter first, conversion second."""
+        ctx = self._ctx
+        rate, native = ctx.get_int("out_rate"), ctx.get_int("sampling_rate")
+        convert = rate > 0 and rate != native
+        chunks = self._vocode_stream_native(mel, chunk_frames, halo, chunks_per_call, convert or limiter is not None)
+        if limiter is not None:
+            from .limiter import LimitPlanner, stream_limit, window_samples
+            plan = LimitPlanner(window_samples(native, limiter["window_ms"]), limiter["oversample"])
+            chunks = stream_limit(chunks, plan, lambda x, o, b, n, last: ctx.limit_window(
+                [x], in_origin=o, out_begin=b, out_count=n, last=last, rate=native, **limiter)[0][0].copy())
+        if convert:
             from .resample import stream_resample
-            ctx = self._ctx
-            yield from stream_resample(self._vocode_stream_native(mel, chunk_frames, halo, chunks_per_call, True), native, rate,
-                                       lambda x, o, b, n: ctx.resample_window([x], native, rate, o, b, n)[0][0].copy())
-        else:
-            yield from self._vocode_stream_native(mel, chunk_frames, halo, chunks_per_call, False)
+            chunks = stream_resample(chunks, native, rate, lambda x, o, b, n: ctx.resample_window([x], native, rate, o, b, n)[0][0].copy())
+        yield from chunks
 
     def _vocode_stream_native(self, mel, chunk_frames, halo, chunks_per_call, native_rate):
         mel = np.asarray(mel, np.float32)

@@ -239,19 +239,31 @@ class ZeroVoxTTS:
         return self._model.last_loudness
 
     def tts_stream(self, text: str, spkemb, chunk_frames=64, chunks_per_call=1, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0,
-                   energy_shift=0.0, energy_range=1.0, loudness=None, limiter=False):
+                   energy_shift=0.0, energy_range=1.0, loudness=None, limiter=False, peak_db=None, limiter_ms=5.0):
         """Streaming variant of ``tts`` (not in the reference): encoder + mel decoder run once, the vocoder
         runs chunk by chunk (16-frame halo), yielding float32 waveform pieces that concatenate to ``tts(text, spkemb)[0]``
         up to the reference's `_min_mel_len` zero-padding of short utterances.  A stream cannot be loudness-normalised: the gain is not
-        known before the last chunk, so ``loudness`` other than None raises ValueError (use tts / tts_long); so does ``limiter=True``
-        (a windowed limiter is possible -- its support is finite -- but not built)."""
+        known before the last chunk, so ``loudness`` other than None raises ValueError (use tts / tts_long).
+        peak_db: None (the default: nothing is limited), or the ceiling in dBFS the stream is held under by the windowed look-ahead
+        limiter (include/zvx.h, zvx_limit_ex; zerovox_amd.limiter), its gain smoothed over limiter_ms on either side and driven by the
+        4x oversampled envelope.  The pieces then concatenate bit for bit to zvx_limit of the unlimited stream's own concatenation
+        -- not to ``tts(limiter=True)``, which pads a short utterance first -- and run limiter.reach(W, 4) samples behind the vocoder
+        (2 W + 11: 231 samples for 5 ms at 22.05 kHz); under an ``output_rate`` the conversion follows the limiter, as in ``tts``.
+        That delay is why the ceiling is asked for by name: ``limiter=True`` still raises ValueError and points here."""
         if loudness is not None:
             raise ValueError("tts_stream cannot normalise loudness: the gain is unknown until the last chunk (use tts or tts_long)")
         if limiter:
-            raise ValueError("tts_stream has no limiter (use tts or tts_long)")
-        return self._tts_stream(text, spkemb, chunk_frames, chunks_per_call, self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range))
+            raise ValueError("tts_stream takes its ceiling by name: pass peak_db=<dBFS> (the stream is then limited window by window, "
+                             "2 W + 11 samples behind the vocoder); limiter=True is the whole-utterance switch of tts and tts_long")
+        lim = None
+        if peak_db is not None:
+            if not np.isfinite(peak_db):
+                raise ValueError(f"tts_stream: peak_db must be finite, not {peak_db}")
+            lim = self._limiter(True, limiter_ms, peak_db)
+        return self._tts_stream(text, spkemb, chunk_frames, chunks_per_call, self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range),
+                                lim)
 
-    def _tts_stream(self, text, spkemb, chunk_frames, chunks_per_call, prosody):
+    def _tts_stream(self, text, spkemb, chunk_frames, chunks_per_call, prosody, limiter=None):
         text = text.strip()
         phone_ids, punct_ids = self.text2phonemeids(text)
         if not phone_ids:
@@ -264,7 +276,7 @@ class ZeroVoxTTS:
         if ml < 2:
             raise ValueError(f"predicted mel length {ml} is too short to synthesise")
         mel = ctx.decode(1, ml)[0, :ml]
-        yield from self._model.vocode_stream(mel, chunk_frames=chunk_frames, chunks_per_call=chunks_per_call)
+        yield from self._model.vocode_stream(mel, chunk_frames=chunk_frames, chunks_per_call=chunks_per_call, limiter=limiter)
 
     def tts_long(self, text: str, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20, fade_ms=5, max_batch=32, max_frames=2048, pcm16=False,
                  durations=None, max_chars=200, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0,
