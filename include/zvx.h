@@ -470,6 +470,59 @@ zvx_status zvx_limit_ex(zvx_ctx* ctx, const float* in, const int32_t* nsamples, 
                         const zvx_limit_params* params, void* out, int64_t out_stride, float* peak_in, float* min_gain, int flags,
                         int64_t in_origin, int64_t out_begin, int64_t out_count, int last);
 
+/* Vocoder-bias denoiser: spectral subtraction of the vocoder's own constant hum from rows in [B][Nmax] f32 with nsamples[b] valid samples at
+ * the model's rate.  The vocoder is run on a silent mel, the magnitude spectrum of what it emits is the bias, and a multiple of it is taken
+ * off the magnitude of every STFT frame of real output, the phase kept (NVIDIA's WaveGlow / HiFi-GAN inference scripts: --denoising-strength).
+ * Whether this is audible on a real checkpoint is NOT measured here: the arithmetic is pinned against a float64 restatement, nothing more.
+ * With n_fft, hop, win_length the model's mel parameters, nf = n_fft / 2 + 1, pad = (n_fft - hop) / 2, per row of n samples:
+ * Framing: exactly zvx_melspec's.  xp = the row reflect-padded by pad on both sides; F = 1 + (n + 2 pad - n_fft) / hop frames; frame f covers
+ *   xp[f hop .. f hop + n_fft); w[t] = the periodic Hann of win_length centred in n_fft (the window inside mel.dft), designed in double on
+ *   the host; the transforms use it rounded once to f32.
+ * Analysis:  X[f][k] = sum_t w[t] xp[f hop + t] e^(-2 pi i k t / n_fft), k < nf.
+ * Gain (f32): m = sqrtf(re^2 + im^2);  G = m > 0 ? fmaxf(floor, 1 - strength * bias[k] / m) : floor;  X' = G X -- spectral subtraction of
+ *   strength * bias from the magnitude with the phase kept; no atan2.
+ * Synthesis: y_f[t] = (1 / n_fft) sum_k c_k Re(X'[f][k] e^(+2 pi i k t / n_fft)), c_0 = c_(n_fft / 2) = 1, otherwise c_k = 2; the imaginary
+ *   parts of DC and Nyquist are ignored.
+ * Overlap-add, for padded position p = i + pad:  num[p] = sum_f w[p - f hop] y_f[p - f hop] (f32, from +0),  den[p] = sum_f w[p - f hop]^2
+ *   (from the DOUBLE window, summed in double, rounded once to f32), both over the frames f < F that cover p in ASCENDING f -- the order is
+ *   part of the contract, as in the limiter's smoothing sum.  out[i] = num / den, one f32 division, where den[p] (the double sum) >= 1e-3 *
+ *   max_t sum_j w[t + j hop]^2; elsewhere out[i] = x[i], the input's bits.  At 1024 / 256 every sample is covered; the rule serves other
+ *   configurations.  With ZVX_PCM16 the resampler's rule follows.
+ * Exact corners: strength == 0 is a copy (the bits of x, nothing is transformed, as equal rates in zvx_resample).  Where every G under a
+ *   sample is 0, out[i] == +0.0f exactly.  Rows are independent: a row's bits depend on its own samples, bias, strength and floor only, not
+ *   on B, Nmax or a neighbour.  Non-finite input: zvx_vocode_mel's rule (that row unspecified, nothing faults, the others untouched).
+ *   out == in (f32, same stride) is allowed: the overlap-add reads the frame buffer, and x only at its own index.  n == 0 writes nothing.
+ * The error against the float64 restatement is that of an f32 FFT pair: measured at most 2.5e-7 on rows with |x| <= 1 (1024 / 256;
+ *   tests/test_denoise_gpu.py holds 4x that).
+ * Launches: one launch loads, windows and transforms the frames -- an FFT in LDS, several frames per workgroup, twiddles from a table
+ *   designed in double, rounded once and cached in the context like the resampler's taps --, applies the gain, transforms back and stores
+ *   w[t] y_f[t] into a work buffer of the context (F n_fft f32 per row, 4x the audio at 1024 / 256); no spectrum goes to memory.  A second
+ *   launch is the gather-form overlap-add.  Lengths are read on the device.
+ * Bias: zvx_denoise_bias runs the context's vocoder, at the native rate and under the current precision switches, on 88 all-zero mel frames
+ *   (what zvx_vocode_mel hands back for them), frames the 88 hop samples as above, and bias[k] = the mean over ALL frames of |X[f][k]|,
+ *   accumulated in double and rounded once to f32.  NVIDIA's script takes frame 0 alone; the mean does not hinge on one reflect-padded
+ *   frame.  Recompute it after a switch that changes the vocoder's arithmetic ("voc_f16", "voc_f16_stages").  The call waits for the bias.
+ * Flags, syncs, validation: the rows-call contract as zvx_limit uses it.  ZVX_DEVICE_IN, ZVX_DEVICE_OUT, ZVX_NO_SYNC (device out only),
+ *   ZVX_PCM16 (not in place); with ZVX_DEVICE_OUT | ZVX_NO_SYNC the call only queues (the first call of a context uploads its tables and
+ *   waits for that once).  bias is a HOST array [nf]; it travels through pinned staging and may be reused when the call returns.
+ *   ZVX_E_INVALID, before anything is queued, the context stays usable: every check of zvx_limit on ctx / in / nsamples / out / B / Nmax /
+ *   lengths / out_stride / flags / in-place use; a NULL bias or params; a strength that is not finite or negative; a floor outside [0, 1]; a
+ *   bias entry that is negative or NaN; a row with 0 < n that fails zvx_melspec's length conditions (n >= pad + 1 and n + 2 pad >= n_fft:
+ *   the message names the row and the minimum).  ZVX_E_UNSUPPORTED: n_fft not a power of two, below 4 or above 4096; more than 65535 rows.
+ * Stage tag "post.denoise" in zvx_tag_stats (one timed group per call; no stage slot): algorithmic bytes = 4 sum(n) read plus the bytes
+ *   written.  zvx_get_int("fft_size") gives n_fft.
+ * Replaces a host-side torch.stft / istft round trip between the vocoder and zvx_normalize / zvx_limit. */
+typedef struct zvx_denoise_params {
+    float strength;   /* finite, >= 0: the multiple of the bias taken off every magnitude (0: a copy) */
+    float floor;      /* in [0, 1]: the smallest gain of a bin */
+} zvx_denoise_params;
+/* bias: host [nf] */
+zvx_status zvx_denoise_bias(zvx_ctx* ctx, float* bias);
+/* out row b = the denoised nsamples[b] samples of in row b; nothing else is touched.  out_stride samples between rows.
+ * flags: ZVX_DEVICE_IN, ZVX_DEVICE_OUT, ZVX_NO_SYNC (device out only), ZVX_PCM16 (not in place); out == in (same stride) allowed for f32 */
+zvx_status zvx_denoise(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias,
+                       const zvx_denoise_params* params, void* out, int64_t out_stride, int flags);
+
 /* Debug/parity taps: copy an intermediate of the last call to host fp32.
  * what: "encoder_out" [B][Tmax][hidden] (after the style add), "features" [B][Lmax][hidden],
  *       "mel" [B][Lmax][n_mels], "pitch_idx"/"energy_idx"/"duration" [B][Tmax] (as float). */
@@ -522,7 +575,7 @@ typedef struct {
 } zvx_kernel_stat;
 int        zvx_kernel_stats(zvx_ctx* ctx, zvx_kernel_stat* out, int max_out);
 /* The same counters grouped by pipeline stage ("encoder", "variance", "lenreg", "decoder", "decoder.norm", "voc.pre",
- * "voc.up1".."voc.res4", "voc.post", "voc.resample", "post.join", "post.loudness", "post.limit", "spkemb"; name = stage): every launch of the stage, including the HBM-bound helper
+ * "voc.up1".."voc.res4", "voc.post", "voc.resample", "post.join", "post.loudness", "post.limit", "post.denoise", "spkemb"; name = stage): every launch of the stage, including the HBM-bound helper
  * kernels, while "profile" == 2 and "profile_only" == -1.  Feeds the per-stage roofline fractions of bench.py. */
 int        zvx_tag_stats(zvx_ctx* ctx, zvx_kernel_stat* out, int max_out);
 zvx_status zvx_reset_stats(zvx_ctx* ctx);

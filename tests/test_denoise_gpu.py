@@ -1,0 +1,351 @@
+"""The vocoder-bias denoiser on the MI355X: zvx_denoise / zvx_denoise_bias against tests/denoise_ref.py (float64 NumPy, never the library),
+the exact corners of include/zvx.h on the device's own output, row independence, every form of the call, errors, and the denoise keyword
+of ZeroVoxTTS.tts / tts_long end to end.
+The bound.  Nothing here is exact but the corners: an f32 FFT of 1024 points, a gain, the inverse FFT and an overlap-add of 4 frames.  The
+limit is 4x the largest error MEASURED over the parity cases below (f32 round-off differs between FFT radices and between boxes), and
+must not exceed 1e-4 -- a 1024-point f32 FFT pair cannot justify more."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+import denoise_ref as D
+from zerovox_amd import _lib, config as zcfg, pack, weights as zw
+
+SENTINEL32 = np.uint32(0xDEADBEEF)
+SENTINEL16 = np.int16(0x5A5B)
+N_FFT, HOP, NF = 1024, 256, 513
+LENGTHS = (700, 1024, 5000)
+CASES = [(0.5, 0.0), (0.5, 0.1), (2.0, 0.0), (2.0, 0.1)]  # (strength, floor): many bins clamp
+# Largest |out - ref| measured over CASES on the ragged batch (MI355X, rows with |x| <= 1): 2.475e-7 (strength 0.5, floor 0.1, the row of
+# 700 samples; per case 2.33e-7 / 2.48e-7 / 1.03e-7 / 0.99e-7).  LIMIT = 4x that: 9.9e-7.
+MEASURED = 2.475e-7
+LIMIT = 4.0 * MEASURED
+assert LIMIT <= 1e-4
+_ctx, _batch, _ref = {}, {}, {}
+
+
+def ctx_for(n_fft=N_FFT, hop=HOP, win_length=None):
+    """a tiny synthetic context (reduced model, tiny vocoder) with the given STFT parameters"""
+    key = (n_fft, hop, win_length or n_fft)
+    if key not in _ctx:
+        cfg = zcfg.reduced_modelcfg("styletts")
+        cfg["audio"].update(fft_size=n_fft, hop_size=hop, win_length=win_length or n_fft)
+        h = zcfg.hifigan_config("tiny")
+        man, blob = pack.pack_model(cfg, zw.tts_state_dict(cfg, 0), h, zw.hifigan_state_dict(h, 0), "bf16")
+        _ctx[key] = _lib.Context(man, blob, 0)
+    return _ctx[key]
+
+
+def signal(rng, n, n_fft=N_FFT):
+    i = np.arange(n)
+    x = 0.3 * rng.standard_normal(n) + 0.3 * np.sin(2 * np.pi * 37.3 * i / n_fft + 0.4) + 0.2 * np.sin(2 * np.pi * 120.0 * i / n_fft + 1.1)
+    return np.clip(x, -1.0, 1.0).astype(np.float32)
+
+
+def batch(n_fft=N_FFT, hop=HOP, win_length=None, lengths=LENGTHS):
+    """(rows, x [B][odd Nmax] with the sentinel behind every row, n, bias), computed once and left unchanged"""
+    key = (n_fft, hop, win_length or n_fft, tuple(lengths))
+    if key not in _batch:
+        rng = np.random.default_rng(2024 + n_fft)
+        rows = [signal(rng, k, n_fft) for k in lengths]
+        n = np.array(lengths, np.int32)
+        nmax = int(n.max())
+        x = np.full((len(rows), nmax + (nmax % 2 == 0)), SENTINEL32, np.uint32).view(np.float32)      # nothing behind a row's end may be read
+        for b, r in enumerate(rows):
+            x[b, :n[b]] = r
+        med = np.median(np.concatenate([np.abs(D.analysis(r, n_fft, hop, win_length or n_fft)).ravel() for r in rows]))
+        bias = (med * rng.uniform(0.5, 1.5, n_fft // 2 + 1)).astype(np.float32)
+        for a in (x, n, bias):
+            a.setflags(write=False)
+        _batch[key] = (rows, x, n, bias)
+    return _batch[key]
+
+
+def reference(strength, floor, n_fft=N_FFT, hop=HOP, win_length=None, lengths=LENGTHS):
+    key = (strength, floor, n_fft, hop, win_length or n_fft, tuple(lengths))
+    if key not in _ref:
+        rows, _, _, bias = batch(n_fft, hop, win_length, lengths)
+        _ref[key] = [D.denoise(r, bias, np.float32(strength), np.float32(floor), n_fft, hop, win_length or n_fft) for r in rows]
+    return _ref[key]
+
+
+def vp(a):
+    if a is None:
+        return None
+    return C.c_void_p(int(a)) if isinstance(a, (int, np.integer)) else a.ctypes.data_as(C.c_void_p)
+
+
+def raw(ctx, x, n, Nmax, bias, prm, out, stride, flags=0, B=None):
+    B = len(n) if B is None else B
+    return ctx._lib.zvx_denoise(ctx._h, vp(x), vp(n), B, Nmax, vp(bias), C.byref(prm) if prm is not None else None, vp(out), stride, flags)
+
+
+def run(ctx, x, n, bias, strength, floor, pcm16=False, stride=None, out=None):
+    """zvx_denoise on host rows into a sentinel-filled buffer -> out [B][stride]"""
+    B, Nmax = x.shape
+    stride = Nmax + 3 if stride is None else stride
+    if out is None:
+        out = np.full((B, stride), SENTINEL16, np.int16) if pcm16 else np.full((B, stride), SENTINEL32, np.uint32).view(np.float32)
+    rc = raw(ctx, x, n, Nmax, bias, _lib.DenoiseParams(strength, floor), out, stride, _lib.ZVX_PCM16 if pcm16 else 0)
+    assert rc == 0, ctx._lib.zvx_last_error(ctx._h)
+    return out
+
+
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
+
+
+def untouched(out, n):
+    """everything behind a row's samples still holds the sentinel"""
+    s = SENTINEL16 if out.dtype == np.int16 else SENTINEL32
+    v = out if out.dtype == np.int16 else out.view(np.uint32)
+    return all(np.all(v[b, n[b]:] == s) for b in range(len(n)))
+
+
+@pytest.mark.parametrize("strength,floor", CASES)
+def test_parity_with_the_float64_reference(strength, floor):
+    ctx = ctx_for()
+    assert ctx.get_int("fft_size") == N_FFT and ctx.hop == HOP
+    rows, x, n, bias = batch()
+    out = run(ctx, x, n, bias, strength, floor)
+    assert untouched(out, n)
+    ref = reference(strength, floor)
+    worst = 0.0
+    for b, r in enumerate(ref):
+        err = float(np.max(np.abs(out[b, :n[b]].astype(np.float64) - r)))
+        changed = float(np.max(np.abs(r - rows[b].astype(np.float64))))
+        print(f"strength {strength} floor {floor} row {b} (n = {n[b]}): max |out - ref| = {err:.3e}, the denoiser moves the row by up to {changed:.3f}")
+        assert changed > 0.05, (b, changed)                  # the cases do subtract: many bins clamp
+        worst = max(worst, err)
+    print(f"strength {strength} floor {floor}: worst {worst:.3e} against the limit {LIMIT:.3e}")
+    assert worst <= LIMIT, (strength, floor, worst)
+
+
+@pytest.mark.parametrize("n_fft,hop,wl", [(512, 256, 512), (2048, 256, 2048), (256, 256, 128)])
+def test_parity_at_other_transform_sizes(n_fft, hop, wl):
+    """an odd log2 n_fft takes the radix-2 pass first (512, 2048: 8 and 2 frames per workgroup); 256 / 256 with a window of 128 has
+    win_length < n_fft, 16 frames per workgroup, no padding at all and samples no window reaches: the pass-through rule runs on the
+    device (the hop stays the vocoder's 256).  The bound: LIMIT is what the round-off of the synthesised frames comes to where four
+    windows overlap, i.e. behind a factor sum w / sum w^2 = 4 / 3; a sample under fewer or smaller windows sees the same round-off behind
+    its own factor (up to 1 / sqrt(1e-3) where one window's skirt is all that covers it), so its bound is LIMIT scaled by that ratio."""
+    ctx = ctx_for(n_fft, hop, wl)
+    lengths = (D.min_samples(n_fft, hop), n_fft + 1, 4 * n_fft + 77)
+    rows, x, n, bias = batch(n_fft, hop, wl, lengths)
+    out = run(ctx, x, n, bias, 2.0, 0.1)
+    assert untouched(out, n)
+    ref = reference(2.0, 0.1, n_fft, hop, wl, lengths)
+    covered = [D.denoise(r, bias, 2.0, 0.1, n_fft, hop, wl, with_cover=True)[1] for r in rows]
+    assert all(c.all() for c in covered) == (wl == n_fft)
+    for b, c in enumerate(covered):                           # where no window reaches: the input's bits
+        assert same_bits(out[b, :n[b]][~c], rows[b][~c]), b
+    for b, r in enumerate(ref):
+        err = np.abs(out[b, :n[b]].astype(np.float64) - r)
+        bound = LIMIT * np.maximum(1.0, D.amplification(int(n[b]), n_fft, hop, wl) / (4.0 / 3.0))
+        print(f"n_fft {n_fft} hop {hop} win {wl} row {b} (n = {n[b]}): max |out - ref| = {err.max():.3e}, worst err / bound = {float(np.max(err / bound)):.3f}")
+        assert np.all(err <= bound), (b, float(np.max(err / bound)))
+
+
+def test_exact_corners():
+    ctx = ctx_for()
+    rows, x, n, bias = batch()
+    B, Nmax = x.shape
+    # strength 0: the input's bits, whatever the bias and the floor
+    out = run(ctx, x, n, bias, 0.0, 0.3)
+    assert untouched(out, n) and all(same_bits(out[b, :n[b]], rows[b]) for b in range(B))
+    # a bias nothing survives, floor 0: +0.0 everywhere
+    out = run(ctx, x, n, np.full(NF, 1e30, np.float32), 1.0, 0.0)
+    assert untouched(out, n) and all(not out.view(np.uint32)[b, :n[b]].any() for b in range(B))
+    # in place gives the bits of out of place
+    want = run(ctx, x, n, bias, 2.0, 0.1, stride=Nmax)
+    xf = np.array(x)
+    run(ctx, xf, n, bias, 2.0, 0.1, stride=Nmax, out=xf)
+    assert untouched(xf, n) and all(same_bits(xf[b, :n[b]], want[b, :n[b]]) for b in range(B))
+    # an empty row writes nothing, its neighbour is what it is alone
+    n0 = np.array([0, 700, 0], np.int32)
+    out0 = run(ctx, x, n0, bias, 2.0, 0.1)
+    alone = run(ctx, np.ascontiguousarray(x[1:2, :701]), n0[1:2], bias, 2.0, 0.1)
+    assert untouched(out0, n0) and same_bits(out0[1, :700], alone[0, :700])
+
+
+def test_rows_do_not_depend_on_the_batch():
+    ctx = ctx_for()
+    rows, x, n, bias = batch()
+    Nmax = x.shape[1]
+    want = run(ctx, x, n, bias, 2.0, 0.1)[1, :1024]
+    one, n1 = np.ascontiguousarray(rows[1][None, :]), np.array([1024], np.int32)
+    assert one.shape == (1, 1024)
+    assert same_bits(run(ctx, one, n1, bias, 2.0, 0.1, stride=1024)[0], want)
+    # the same on device rows, queued: in place behind an upload, nothing syncs before the rows are fetched
+    prm = _lib.DenoiseParams(2.0, 0.1)
+    queued = _lib.ZVX_DEVICE_IN | _lib.ZVX_DEVICE_OUT | _lib.ZVX_NO_SYNC
+    d1, d3 = ctx.dev_alloc(1024 * 4), ctx.dev_alloc(x.nbytes)
+    try:
+        ctx.dev_from_host(d1, one)
+        assert raw(ctx, d1, n1, 1024, bias, prm, d1, 1024, queued) == 0
+        ctx.dev_from_host(d3, x)
+        assert raw(ctx, d3, n, Nmax, bias, prm, d3, Nmax, queued) == 0
+        got1 = ctx.dev_to_host(d1, (1, 1024), np.float32)
+        got3 = ctx.dev_to_host(d3, x.shape, np.float32)
+        assert same_bits(got1[0], want) and same_bits(got3[1, :1024], want) and untouched(got3, n)
+        # the binding's in-place form
+        ctx.dev_from_host(d1, one)
+        assert ctx.denoise_device(d1, n1, 1024, bias, 2.0, floor=0.1, no_sync=True) is None
+        assert same_bits(ctx.dev_to_host(d1, (1, 1024), np.float32)[0], want)
+    finally:
+        ctx.dev_free(d1)
+        ctx.dev_free(d3)
+    assert same_bits(ctx.denoise(rows, bias, 2.0, 0.1)[1, :1024], want)       # and the binding on host rows
+
+
+def test_pcm16_rows_follow_the_resamplers_rule():
+    ctx = ctx_for()
+    rows, x, n, bias = batch()
+    loud = np.array(x)
+    loud[2, :n[2]] *= np.float32(1.3)                         # some samples leave [-1, 1]: the rule clamps
+    f32 = run(ctx, loud, n, bias, 0.5, 0.0)
+    i16 = run(ctx, loud, n, bias, 0.5, 0.0, pcm16=True)
+    assert untouched(i16, n) and np.abs(f32[2, :n[2]]).max() > 1.0
+    for b in range(len(n)):
+        assert np.array_equal(i16[b, :n[b]], D.pcm16(f32[b, :n[b]])), b
+    assert np.array_equal(run(ctx, loud, n, bias, 0.0, 0.0, pcm16=True)[2, :n[2]], D.pcm16(loud[2, :n[2]]))     # the copy as well
+
+
+def test_errors_leave_the_context_usable():
+    ctx = ctx_for()
+    rows, x, n, bias = batch()
+    B, Nmax = x.shape
+    inv, uns = _lib.ZVX_E_INVALID, _lib.ZVX_E_UNSUPPORTED
+    lib, h = ctx._lib, ctx._h
+    prm = _lib.DenoiseParams(2.0, 0.1)
+    out = np.zeros((B, Nmax), np.float32)
+    good = run(ctx, x, n, bias, 2.0, 0.1, stride=Nmax)
+    nan, inf = float("nan"), float("inf")
+
+    def refused(code, x_=x, n_=n, B_=None, Nmax_=Nmax, bias_=bias, prm_=prm, out_=out, stride=Nmax, flags=0, says=None):
+        """the call is refused with `code`, and a valid call on the same context then gives the bits it gave before"""
+        assert raw(ctx, x_, n_, Nmax_, bias_, prm_, out_, stride, flags, B=B_) == code
+        if says is not None:
+            msg = lib.zvx_last_error(h)
+            assert all(s in msg for s in says), msg
+        assert same_bits(run(ctx, x, n, bias, 2.0, 0.1, stride=Nmax), good)
+
+    assert lib.zvx_denoise(None, vp(x), vp(n), B, Nmax, vp(bias), C.byref(prm), vp(out), Nmax, 0) == inv
+    assert lib.zvx_denoise_bias(None, vp(np.zeros(NF, np.float32))) == inv and lib.zvx_denoise_bias(h, None) == inv
+    refused(inv, x_=None)
+    refused(inv, n_=None, B_=B)
+    refused(inv, out_=None)
+    refused(inv, bias_=None, says=[b"bias"])
+    refused(inv, prm_=None, says=[b"params"])
+    for bad in (0, -1):
+        refused(inv, B_=bad)
+    refused(inv, Nmax_=0)
+    neg, big, short = n.copy(), n.copy(), n.copy()
+    neg[1], big[1], short[1] = -1, Nmax + 1, D.min_samples(N_FFT, HOP) - 1
+    refused(inv, n_=neg)
+    refused(inv, n_=big)
+    refused(inv, n_=short, says=[b"row 1", b"385"])           # names the row and the minimum
+    short[1] = 1
+    refused(inv, n_=short, says=[b"row 1", b"385"])
+    refused(inv, stride=Nmax - 1)
+    for flags in (64, _lib.ZVX_HOST_ASYNC, _lib.ZVX_NATIVE_RATE, _lib.ZVX_NO_SYNC):
+        refused(inv, flags=flags)
+    xf = np.array(x)
+    refused(inv, x_=xf, out_=xf, flags=_lib.ZVX_PCM16)
+    for kw in (dict(stride=Nmax + 2), dict(flags=_lib.ZVX_DEVICE_IN), dict(flags=_lib.ZVX_DEVICE_OUT)):
+        refused(inv, x_=xf, out_=xf, **kw)
+    assert same_bits(xf, x)                                   # nothing was written by any of them
+    for s in (nan, inf, -inf, -0.01):
+        refused(inv, prm_=_lib.DenoiseParams(s, 0.0), says=[b"strength"])
+    for f in (nan, inf, -0.01, 1.01):
+        refused(inv, prm_=_lib.DenoiseParams(1.0, f), says=[b"floor"])
+    for k, v in ((0, -1e-3), (7, nan), (NF - 1, -inf)):
+        bad = np.array(bias)
+        bad[k] = v
+        refused(inv, bias_=bad, says=[b"bias[%d]" % k])
+    z = np.zeros((65536, 1), np.float32)
+    refused(uns, x_=z, n_=np.zeros(65536, np.int32), Nmax_=1, out_=np.zeros((65536, 1), np.float32), stride=1)
+    # the limits of the valid ranges are accepted
+    edge = n.copy()
+    edge[1] = D.min_samples(N_FFT, HOP)
+    for p in (_lib.DenoiseParams(0.0, 1.0), _lib.DenoiseParams(1e30, 0.0), _lib.DenoiseParams(1.0, 1.0)):
+        assert raw(ctx, x, edge, Nmax, bias, p, out, Nmax) == 0
+    assert raw(ctx, x, n, Nmax, np.full(NF, inf, np.float32), prm, out, Nmax) == 0       # an infinite bias entry just silences its bin
+    assert np.all(np.isfinite(out[0, :n[0]]))
+
+
+@pytest.mark.parametrize("n_fft,hop", [(768, 256), (8192, 256)])
+def test_unsupported_transform_sizes(n_fft, hop):
+    ctx = ctx_for(n_fft, hop)
+    nf = n_fft // 2 + 1
+    n = np.array([3 * n_fft], np.int32)
+    x = np.zeros((1, 3 * n_fft), np.float32)
+    out = np.zeros_like(x)
+    uns = _lib.ZVX_E_UNSUPPORTED
+    before = ctx.true_peak([x[0] + 0.25], 4)
+    assert raw(ctx, x, n, x.shape[1], np.zeros(nf, np.float32), _lib.DenoiseParams(1.0, 0.0), out, x.shape[1]) == uns
+    assert b"n_fft" in ctx._lib.zvx_last_error(ctx._h)
+    assert same_bits(ctx.true_peak([x[0] + 0.25], 4), before)                            # the context still works
+    assert ctx._lib.zvx_denoise_bias(ctx._h, vp(np.zeros(nf, np.float32))) == uns
+    assert same_bits(ctx.true_peak([x[0] + 0.25], 4), before)
+    ctx.close()
+    _ctx.pop((n_fft, hop, n_fft))
+
+
+def test_bias_of_the_contexts_vocoder():
+    ctx = ctx_for()
+    before = ctx.vocode_mel(np.zeros((1, 88, ctx.get_int("n_mels")), np.float32), np.array([88], np.int32), native_rate=True)
+    wav = np.asarray(before[0] if isinstance(before, (tuple, list)) else before)[0, :88 * HOP]
+    bias = ctx.denoise_bias()
+    assert bias.shape == (NF,) and bias.dtype == np.float32 and np.all(np.isfinite(bias)) and np.all(bias >= 0) and bias.max() > 0
+    ref = D.bias_of(wav)
+    err = float(np.max(np.abs(bias.astype(np.float64) - ref)))
+    print(f"bias: max {bias.max():.4e}, max |bias - ref| = {err:.3e} against {LIMIT * 88:.3e}")
+    assert err <= LIMIT * 88                                  # the tolerance of the parity test scaled by the frame count
+    assert same_bits(ctx.denoise_bias(), bias)                # two successive calls: identical bits
+    ctx.set_int("profile", 2)
+    try:
+        ctx.reset_stats()
+        rows, x, n, b2 = batch()
+        ctx.denoise(rows, b2, 0.5)
+        tags = {t["name"]: t for t in ctx.tag_stats()}
+        total = float(sum(len(r) for r in rows))
+        assert tags["post.denoise"]["launches"] == 1 and tags["post.denoise"]["bytes"] == 8.0 * total and tags["post.denoise"]["ms"] > 0
+    finally:
+        ctx.set_int("profile", 0)
+
+
+THREE = "The quick brown fox jumps over the lazy dog; does it, really? Pack my box with five dozen liquor jugs"
+
+
+def test_tts_and_tts_long_with_the_denoiser():
+    from zerovox_amd.synthesize import ZeroVoxTTS
+    _, synth = ZeroVoxTTS.load_model("synthetic:styletts", "synthetic:tiny", infer_device="cuda:0", precision="bf16")
+    ctx = synth.model.ctx
+    spk = synth.speaker_embed_from_mel(np.random.default_rng(0).standard_normal((96, 80)).astype(np.float32))
+    text = "The quick brown fox jumps over the lazy dog"
+    plain, ph, length = synth.tts(text, spk)
+    assert synth.model._denoise_bias is None                  # the default path creates nothing of the denoiser
+    den, ph2, length2 = synth.tts(text, spk, denoise=0.5)
+    bias = synth.denoise_bias
+    assert bias.shape == (NF,) and bias.max() > 0 and length2 == length and np.array_equal(ph, ph2) and den.dtype == np.float32
+    assert same_bits(den, ctx.denoise([plain], bias, 0.5)[0, :len(plain)])
+    print(f"tts: bias max {bias.max():.3e}; denoise=0.5 moves the row by up to {float(np.abs(den - plain).max()):.3e} (peak {float(np.abs(plain).max()):.3f})")
+    assert same_bits(synth.tts(text, spk, denoise=None)[0], plain) and same_bits(synth.tts(text, spk)[0], plain)
+    assert same_bits(synth.tts(text, spk, denoise=0.0)[0], plain)                        # strength 0 is a copy
+    assert same_bits(synth.refresh_denoise_bias(), bias)
+    # tts_long: the same layout whenever nothing is trimmed; every sentence is its own row denoised
+    kw = dict(trim_db=0.0, fade_ms=0, pauses={".": 0, ";": 0, ",": 0, " ": 0})
+    wav0, seg0 = synth.tts_long(THREE, spk, **kw)
+    wav1, seg1 = synth.tts_long(THREE, spk, denoise=0.5, **kw)
+    assert len(seg0) == 3 and [(s["start"], s["samples"], s["mel_len"], s["trim"]) for s in seg1] == [(s["start"], s["samples"], s["mel_len"], s["trim"]) for s in seg0]
+    assert len(wav1) == len(wav0)
+    rows = [wav0[s["start"]:s["start"] + s["samples"]] for s in seg0]
+    want = ctx.denoise(rows, bias, 0.5)
+    for i, s in enumerate(seg1):
+        assert same_bits(wav1[s["start"]:s["start"] + s["samples"]], want[i, :s["samples"]]), i
+    with pytest.raises(ValueError):
+        next(iter(synth.tts_stream(text, spk, denoise=0.01)))

@@ -25,7 +25,7 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_comm_unique_id", "zvx_comm_init", "zvx_comm_gather", "zvx_comm_barrier", "zvx_comm_max_f64", "zvx_comm_info", "zvx_comm_destroy",
            "zvx_dev_alloc", "zvx_dev_free", "zvx_dev_from_host", "zvx_dev_to_host", "zvx_spkemb_ex", "zvx_wait_host",
            "zvx_encode_ex", "zvx_synthesize_ex", "zvx_resample", "zvx_resample_ex", "zvx_trim_bounds", "zvx_join",
-           "zvx_loudness", "zvx_normalize", "zvx_true_peak", "zvx_limit", "zvx_spkemb_wav", "zvx_limit_ex")
+           "zvx_loudness", "zvx_normalize", "zvx_true_peak", "zvx_limit", "zvx_spkemb_wav", "zvx_limit_ex", "zvx_denoise_bias", "zvx_denoise")
 ZVX_COMM_ID_BYTES = 128
 ZVX_LOUD_PER_ROW, ZVX_LOUD_COMMON = 0, 1
 LIMIT_TILE = 1024                                    # samples per workgroup of both limiter kernels (csrc/zvx_kernels.h, LIMIT_TILE)
@@ -65,6 +65,11 @@ class LoudnessParams(C.Structure):
 class LimitParams(C.Structure):
     """zvx_limit_params (include/zvx.h)"""
     _fields_ = [("ceiling", C.c_float), ("window_ms", C.c_float), ("oversample", C.c_int32)]
+
+
+class DenoiseParams(C.Structure):
+    """zvx_denoise_params (include/zvx.h)"""
+    _fields_ = [("strength", C.c_float), ("floor", C.c_float)]
 
 
 class KernelStat(C.Structure):
@@ -134,6 +139,8 @@ def load():
     lib.zvx_limit.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(LimitParams), vp, C.c_int64, vp, vp, C.c_int]
     lib.zvx_limit_ex.argtypes = lib.zvx_limit.argtypes + [C.c_int64, C.c_int64, C.c_int64, C.c_int]
     lib.zvx_spkemb_wav.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(RefParams), vp, vp, vp, vp, C.c_int]
+    lib.zvx_denoise_bias.argtypes = [vp, vp]
+    lib.zvx_denoise.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(DenoiseParams), vp, C.c_int64, C.c_int]
     _lib = lib
     return lib
 
@@ -419,6 +426,42 @@ class Context:
         self._chk(self._lib.zvx_limit(self._h, p, _ptr(n), B, int(Nmax), self._rate(rate), C.byref(prm), p, int(Nmax), _ptr(peak), _ptr(gmin),
                                       ZVX_DEVICE_IN | ZVX_DEVICE_OUT | (ZVX_NO_SYNC if no_sync else 0)))
         return res
+
+    def denoise_bias(self):
+        """zvx_denoise_bias: the magnitude spectrum of what the context's vocoder emits for 88 silent mel frames, the mean over the STFT
+        frames -> [fft_size / 2 + 1] float32.  Recompute it after a switch that changes the vocoder's arithmetic."""
+        bias = np.zeros(self.get_int("fft_size") // 2 + 1, np.float32)
+        self._chk(self._lib.zvx_denoise_bias(self._h, _ptr(bias)))
+        return bias
+
+    def _denoise_bias_arg(self, bias):
+        bias = _f32(bias).reshape(-1)
+        nf = self.get_int("fft_size") // 2 + 1
+        if bias.shape[0] != nf:
+            raise ValueError(f"denoise: bias has {bias.shape[0]} entries, the model's STFT has {nf} bins")
+        return bias
+
+    def denoise(self, rows, bias, strength, floor=0.0, pcm16=False, lengths=None):
+        """zvx_denoise on host rows: strength * bias[k] is taken off the magnitude of every STFT bin of every frame (never below floor
+        times the magnitude), the phase kept, and the frames are overlap-added back -> rows_out [B][Nmax] float32 / int16 -- row b holds
+        its denoised samples, then zeros.  rows: a list of 1-D float waveforms, or a padded 2-D array + lengths, at the model's rate."""
+        x, n = self._rows(rows, lengths)
+        B, Nmax = x.shape
+        bias = self._denoise_bias_arg(bias)
+        prm = DenoiseParams(float(strength), float(floor))
+        out = np.zeros((B, Nmax), np.int16 if pcm16 else np.float32)
+        self._chk(self._lib.zvx_denoise(self._h, _ptr(x), _ptr(n), B, Nmax, _ptr(bias), C.byref(prm), _ptr(out), Nmax, ZVX_PCM16 if pcm16 else 0))
+        return out
+
+    def denoise_device(self, ptr, lengths, Nmax, bias, strength, *, floor=0.0, no_sync=False):
+        """zvx_denoise IN PLACE on device rows [B][Nmax] f32 at `ptr` (they may be the output of a synthesize / vocode_device call queued
+        just before: stream order is the fence); with no_sync the call only queues.  bias is a host array and may be reused at once."""
+        n = _i32(lengths)
+        bias = self._denoise_bias_arg(bias)
+        prm = DenoiseParams(float(strength), float(floor))
+        p = C.c_void_p(int(ptr))
+        self._chk(self._lib.zvx_denoise(self._h, p, _ptr(n), len(n), int(Nmax), _ptr(bias), C.byref(prm), p, int(Nmax),
+                                        ZVX_DEVICE_IN | ZVX_DEVICE_OUT | (ZVX_NO_SYNC if no_sync else 0)))
 
     def resample_device(self, ptr, n, rate_in, rate_out, pcm16=False):
         """zvx_resample of ONE device-resident row of n f32 samples (ZVX_DEVICE_IN) -> host row at rate_out"""

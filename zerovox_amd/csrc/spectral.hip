@@ -1,0 +1,169 @@
+// spectral.hip -- the vocoder-bias denoiser (include/zvx.h: zvx_denoise, zvx_denoise_bias): STFT frames of a waveform row through an FFT
+// that lives in LDS, a per-bin gain, the inverse FFT, and the overlap-add of the windowed frames.  zvx_kernels.h: DenoiseArgs.
+//
+// The transform: Stockham autosort, radix 4 (one radix-2 pass first where log2 n_fft is odd), decimation in time.  A pass with sub-transform
+// size p takes butterfly j < n_fft / 4, k = j mod p: inputs x[j + r n_fft / 4] times e^(-+ 2 pi i r k / (4 p)), r = 0 .. 3, outputs
+// y[4 (j - k) + k + r p]; the result of the last pass is in natural order, so the gain reads bin k at index k.  In place: every thread reads
+// the inputs of its 4 butterflies into registers, the workgroup synchronises, then the outputs are written.
+//
+// LDS: split re / im planes of DENOISE_POINTS floats, index i stored at i + (i >> 5): the reads of a pass are consecutive (conflict-free);
+// the writes of the first radix-4 pass have stride 4, which the extra word per 32 spreads over all 32 banks of a ds_write_b32 group (later
+// passes write runs of p consecutive words: at most 2-way).  33 KB per workgroup: 4 workgroups, 16 waves, per CU of 160 KB.
+#include "zvx_kernels.h"
+
+namespace zvx {
+
+constexpr int DN_THREADS = 256;
+constexpr int DN_PLANE = DENOISE_POINTS + DENOISE_POINTS / 32;
+
+__device__ __forceinline__ int dn_at(int i) { return i + (i >> 5); }
+
+// All DENOISE_POINTS / n_fft frames of the workgroup at once: 1024 radix-4 butterflies per pass, 4 per thread.
+template <bool INV>
+__device__ __forceinline__ void dn_fft(float* sre, float* sim, const float2* __restrict__ twid, int log2n, int tid) {
+    const int N = 1 << log2n;
+    int p = 1, log2p = 0;
+    if (log2n & 1) {                                         // radix 2, p = 1: no twiddles; 2048 butterflies, 8 per thread
+        const int half = N >> 1;
+        float ar[8], ai[8], br[8], bi[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            const int g = tid + DN_THREADS * u, base = (g >> (log2n - 1)) << log2n, j = g & (half - 1);
+            ar[u] = sre[dn_at(base + j)]; ai[u] = sim[dn_at(base + j)];
+            br[u] = sre[dn_at(base + j + half)]; bi[u] = sim[dn_at(base + j + half)];
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            const int g = tid + DN_THREADS * u, base = (g >> (log2n - 1)) << log2n, j = g & (half - 1);
+            sre[dn_at(base + 2 * j)] = ar[u] + br[u]; sim[dn_at(base + 2 * j)] = ai[u] + bi[u];
+            sre[dn_at(base + 2 * j + 1)] = ar[u] - br[u]; sim[dn_at(base + 2 * j + 1)] = ai[u] - bi[u];
+        }
+        __syncthreads();
+        p = 2; log2p = 1;
+    }
+    const int quarter = N >> 2;
+    for (; p < N; p <<= 2, log2p += 2) {
+        float vr[4][4], vi[4][4];
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int g = tid + DN_THREADS * u, base = (g >> (log2n - 2)) << log2n, j = g & (quarter - 1);
+#pragma unroll
+            for (int r = 0; r < 4; r++) { vr[u][r] = sre[dn_at(base + j + r * quarter)]; vi[u][r] = sim[dn_at(base + j + r * quarter)]; }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int g = tid + DN_THREADS * u, base = (g >> (log2n - 2)) << log2n, j = g & (quarter - 1), k = j & (p - 1);
+            if (p > 1) {                                     // e^(-+ 2 pi i r k / (4 p)) = twid[r k n_fft / (4 p)] (conjugated for the inverse)
+                const int sh = log2n - 2 - log2p;
+#pragma unroll
+                for (int r = 1; r < 4; r++) {
+                    const float2 w = twid[(r * k) << sh];
+                    const float wr = w.x, wi = INV ? -w.y : w.y, xr = vr[u][r], xi = vi[u][r];
+                    vr[u][r] = xr * wr - xi * wi; vi[u][r] = xr * wi + xi * wr;
+                }
+            }
+            const float t0r = vr[u][0] + vr[u][2], t0i = vi[u][0] + vi[u][2], t1r = vr[u][0] - vr[u][2], t1i = vi[u][0] - vi[u][2];
+            const float t2r = vr[u][1] + vr[u][3], t2i = vi[u][1] + vi[u][3];
+            float t3r = vr[u][1] - vr[u][3], t3i = vi[u][1] - vi[u][3];
+            // forward: -i t3 = (t3i, -t3r); inverse: +i t3 = (-t3i, t3r)
+            const float qr = INV ? -t3i : t3i, qi = INV ? t3r : -t3r;
+            const int o = base + ((j - k) << 2) + k;
+            sre[dn_at(o)] = t0r + t2r;         sim[dn_at(o)] = t0i + t2i;
+            sre[dn_at(o + p)] = t1r + qr;      sim[dn_at(o + p)] = t1i + qi;
+            sre[dn_at(o + 2 * p)] = t0r - t2r; sim[dn_at(o + 2 * p)] = t0i - t2i;
+            sre[dn_at(o + 3 * p)] = t1r - qr;  sim[dn_at(o + 3 * p)] = t1i - qi;
+        }
+        __syncthreads();
+    }
+}
+
+__global__ __launch_bounds__(DN_THREADS) void k_denoise_frames(const DenoiseArgs a) {
+    __shared__ float sre[DN_PLANE], sim[DN_PLANE];
+    const int tid = threadIdx.x, b = blockIdx.y, N = a.n_fft, lg = a.log2n;
+    const int n = a.nsamples[b];
+    const int F = n > 0 ? 1 + (n + 2 * a.pad - N) / a.hop : 0;
+    const int f0 = blockIdx.x * (DENOISE_POINTS >> lg);
+    if (f0 >= F) return;                                     // (uniform over the workgroup)
+    const float* x = a.x + (long)b * a.x_bs;
+    for (int i = tid; i < DENOISE_POINTS; i += DN_THREADS) {
+        const int f = f0 + (i >> lg), t = i & (N - 1);
+        float v = 0.f;
+        if (f < F) {
+            int s = f * a.hop + t - a.pad;                   // numpy 'reflect'; inside the row for every validated length, clamped all the same
+            if (s < 0) s = -s;
+            if (s >= n) s = 2 * (n - 1) - s;
+            s = min(max(s, 0), n - 1);
+            v = a.win[t] * x[s];
+        }
+        sre[dn_at(i)] = v; sim[dn_at(i)] = 0.f;
+    }
+    __syncthreads();
+    dn_fft<false>(sre, sim, (const float2*)a.twid, lg, tid);
+    const int nf = N / 2 + 1, items = (DENOISE_POINTS >> lg) * nf;
+    if (a.mag) {                                             // magnitude-out mode (zvx_denoise_bias)
+        for (int g = tid; g < items; g += DN_THREADS) {
+            const int q = g / nf, k = g - q * nf, i = dn_at((q << lg) + k);
+            if (f0 + q < F) a.mag[((long)b * a.Fmax + f0 + q) * nf + k] = sqrtf(sre[i] * sre[i] + sim[i] * sim[i]);
+        }
+        return;
+    }
+    // X' = G X on bins 0 .. n_fft / 2, mirrored as the conjugate into the upper half (DC and Nyquist: imaginary part dropped); item (q, k)
+    // touches entries k and n_fft - k of frame q only
+    for (int g = tid; g < items; g += DN_THREADS) {
+        const int q = g / nf, k = g - q * nf, i1 = dn_at((q << lg) + k), i2 = dn_at((q << lg) + ((N - k) & (N - 1)));
+        float re = sre[i1], im = sim[i1];
+        const float m = sqrtf(re * re + im * im);
+        const float G = m > 0.f ? fmaxf(a.floor, 1.f - a.strength * a.bias[k] / m) : a.floor;
+        re *= G; im *= G;
+        if (k == 0 || 2 * k == N) im = 0.f;
+        sre[i1] = re; sim[i1] = im;
+        if (i2 != i1) { sre[i2] = re; sim[i2] = -im; }
+    }
+    __syncthreads();
+    dn_fft<true>(sre, sim, (const float2*)a.twid, lg, tid);
+    const float inv_n = 1.f / (float)N;                      // a power of two: exact
+    for (int i = tid; i < DENOISE_POINTS; i += DN_THREADS) {
+        const int f = f0 + (i >> lg), t = i & (N - 1);
+        if (f < F) a.work[((long)b * a.Fmax + f) * N + t] = a.win[t] * (sre[dn_at(i)] * inv_n);
+    }
+}
+
+__device__ __forceinline__ short dn_pcm(float v) { return (short)fminf(fmaxf(v * 32760.0f, -32768.0f), 32767.0f); }   // the resampler's rule
+
+__global__ __launch_bounds__(256) void k_denoise_ola(const DenoiseArgs a) {
+    const int b = blockIdx.y, n = a.nsamples[b], N = a.n_fft;
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float xi = a.x[(long)b * a.x_bs + i];
+    float v = xi;
+    if (!a.copy) {
+        const int F = 1 + (n + 2 * a.pad - N) / a.hop, p = i + a.pad;
+        const int f_hi = min(F - 1, p / a.hop), f_lo = p < N ? 0 : (p - N) / a.hop + 1;      // frames f with f hop <= p < f hop + n_fft
+        const float* w = a.work + (long)b * a.Fmax * N;
+        float num = 0.f;
+        double den = 0.0;
+        for (int f = f_lo; f <= f_hi; f++) {                 // ascending f: the order is part of the contract
+            const int t = p - f * a.hop;
+            num += w[(long)f * N + t];
+            den += a.win2[t];
+        }
+        if (den >= a.den_min) v = num / (float)den;
+    }
+    if (a.pcm16) ((short*)a.out)[(long)b * a.out_bs + i] = dn_pcm(v);
+    else ((float*)a.out)[(long)b * a.out_bs + i] = v;
+}
+
+void launch_denoise_frames(const DenoiseArgs& a, hipStream_t s) {
+    if (a.B <= 0 || a.Fmax <= 0) return;
+    const int per = DENOISE_POINTS >> a.log2n;
+    hipLaunchKernelGGL(k_denoise_frames, dim3((unsigned)((a.Fmax + per - 1) / per), (unsigned)a.B), dim3(DN_THREADS), 0, s, a);
+}
+
+void launch_denoise_ola(const DenoiseArgs& a, long n_max, hipStream_t s) {
+    if (a.B <= 0 || n_max <= 0) return;
+    hipLaunchKernelGGL(k_denoise_ola, dim3((unsigned)((n_max + 255) / 256), (unsigned)a.B), dim3(256), 0, s, a);
+}
+
+}  // namespace zvx

@@ -157,6 +157,10 @@ struct zvx_ctx {
     std::map<std::pair<int, int>, RsBank> rs_banks;
     std::map<int, const double*> lim_wins;  // zvx_limit: the smoothing weights on the device, designed in double, per window W
     std::map<int, LoudCoef> loud_coefs;    // zvx_loudness / zvx_normalize: the K-weighting biquads, designed in double, per sampling rate
+    // zvx_denoise / zvx_denoise_bias: twiddles, window and squared window on the device, designed in double on first use (n_fft, hop and
+    // win_length are the model's: one set per context); nothing exists before the first call
+    struct DnTables { int n_fft = 0, log2n = 0, win_length = 0; const float* twid = nullptr; const float* win = nullptr; const double* win2 = nullptr; double den_min = 0; };
+    DnTables dn_tab;
     // zvx_join / zvx_trim_bounds / zvx_spkemb_wav / zvx_loudness / zvx_normalize / zvx_true_peak / zvx_limit: pinned host memory the
     // layout, bounds or result words (and host output rows) land in under the call's one wait
     void* join_host = nullptr;
@@ -2560,6 +2564,131 @@ void do_limit(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamp
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// vocoder-bias denoiser (include/zvx.h: zvx_denoise, zvx_denoise_bias; kernels: spectral.hip)
+// ------------------------------------------------------------------------------------------------
+struct DnGeom { int n_fft, log2n, hop, pad, nf; };
+DnGeom dn_geom(const zvx_ctx* c, const char* who) {
+    const int n_fft = c->t("mel.dft").dim(2), hop = c->hop;
+    int lg = 0;
+    while ((1 << lg) < n_fft && lg < 30) lg++;
+    if (n_fft < 4 || n_fft > DENOISE_POINTS || (1 << lg) != n_fft)
+        fail(ZVX_E_UNSUPPORTED, "%s: the model's n_fft = %d is not a power of two in 4 .. %d", who, n_fft, DENOISE_POINTS);
+    if (hop < 1 || hop > n_fft) fail(ZVX_E_UNSUPPORTED, "%s: hop %d with n_fft %d", who, hop, n_fft);
+    return {n_fft, lg, hop, (n_fft - hop) / 2, n_fft / 2 + 1};
+}
+// the least length of a non-empty row: zvx_melspec's conditions (a mirror exists on both sides, one whole frame)
+int dn_min_samples(const DnGeom& g) { return std::max(g.pad + 1, g.n_fft - 2 * g.pad); }
+int dn_frames(const DnGeom& g, long n) { return n > 0 ? (int)(1 + (n + 2 * g.pad - g.n_fft) / g.hop) : 0; }
+
+// Twiddles, window and squared window, designed in double and kept for the life of the context.  win_length is not a manifest key: it is
+// read off the window inside mel.dft (row 0 of the cosine block is the window itself; a periodic Hann is zero at its first sample only).
+const zvx_ctx::DnTables& dn_tables(zvx_ctx* c, const DnGeom& g) {
+    if (c->dn_tab.n_fft == g.n_fft) return c->dn_tab;
+    const int N = g.n_fft;
+    const float* row0 = c->t("mel.dft").host;
+    int t0 = -1, t1 = -1;
+    for (int t = 0; row0 && t < N; t++) if (row0[t] != 0.f) { if (t0 < 0) t0 = t; t1 = t; }
+    const int WL = t1 - t0 + 2, lp = t0 - 1;
+    if (t0 < 1 || WL > N || lp != (N - WL) / 2) fail(ZVX_E_MANIFEST, "zvx_denoise: mel.dft does not carry a centred periodic Hann window");
+    std::vector<double> w(N, 0.0), w2(N);
+    for (int i = 0; i < WL; i++) w[lp + i] = 0.5 + 0.5 * cos(M_PI * (double)(2 * i - WL) / (double)WL);     // numpy.hanning(WL + 1)[:-1]
+    w[lp] = 0.0;
+    for (int t = 0; t < N; t++) w2[t] = w[t] * w[t];
+    double top = 0.0;
+    for (int t = 0; t < g.hop; t++) { double s = 0.0; for (int u = t; u < N; u += g.hop) s += w2[u]; top = std::max(top, s); }
+    std::vector<float> f(3 * (size_t)N);
+    for (int m = 0; m < N; m++) {
+        const double ang = 2.0 * M_PI * (double)m / (double)N;
+        f[2 * (size_t)m] = (float)cos(ang); f[2 * (size_t)m + 1] = (float)-sin(ang);
+        f[2 * (size_t)N + m] = (float)w[m];
+    }
+    char* d = (char*)c->buf("dn.tab", (size_t)N * 8 + (size_t)N * 12);
+    HIPCHK(hipMemcpyAsync(d, w2.data(), (size_t)N * 8, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(d + (size_t)N * 8, f.data(), (size_t)N * 12, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipStreamSynchronize(c->stream));                 // the host vectors go away; once per context
+    zvx_ctx::DnTables& tb = c->dn_tab;
+    tb.n_fft = N; tb.log2n = g.log2n; tb.win_length = WL; tb.den_min = 1e-3 * top;
+    tb.win2 = (const double*)d; tb.twid = (const float*)(d + (size_t)N * 8); tb.win = tb.twid + 2 * (size_t)N;
+    return tb;
+}
+void dn_fill(DenoiseArgs& a, const DnGeom& g, const zvx_ctx::DnTables& tb) {
+    a.n_fft = g.n_fft; a.log2n = g.log2n; a.hop = g.hop; a.pad = g.pad;
+    a.twid = tb.twid; a.win = tb.win; a.win2 = tb.win2; a.den_min = tb.den_min;
+}
+double dn_fft_flops(const DnGeom& g, double frames, int transforms) { return transforms * frames * 5.0 * g.n_fft * g.log2n; }
+
+void do_denoise(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias, const zvx_denoise_params* p, void* out,
+                int64_t out_stride, int flags) {
+    const char* who = "zvx_denoise";
+    const RowsInfo r = rows_check(who, in, nsamples, B, Nmax, 65535);
+    flags_check(who, flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16);
+    out_rows_check(who, in, out, out_stride, Nmax, flags);
+    if (!bias || !p) fail(ZVX_E_INVALID, "%s: %s is NULL", who, !bias ? "bias" : "params");
+    if (!std::isfinite(p->strength) || p->strength < 0.f) fail(ZVX_E_INVALID, "%s: strength must be finite and not negative", who);
+    if (!(p->floor >= 0.f && p->floor <= 1.f)) fail(ZVX_E_INVALID, "%s: floor must lie in [0, 1]", who);
+    const DnGeom g = dn_geom(c, who);
+    for (int k = 0; k < g.nf; k++) if (!(bias[k] >= 0.f)) fail(ZVX_E_INVALID, "%s: bias[%d] is negative or NaN", who, k);
+    double frames = 0;
+    for (int b = 0; b < B; b++) {
+        if (nsamples[b] > 0 && nsamples[b] < dn_min_samples(g))
+            fail(ZVX_E_INVALID, "%s: row %d has %d samples; a row that is not empty needs at least %d (zvx_melspec's conditions)", who, b, nsamples[b], dn_min_samples(g));
+        frames += dn_frames(g, nsamples[b]);
+    }
+    RowsReturn ret(c, B, 0, false, true, r.n_max, flags);
+    DenoiseArgs a{};
+    a.copy = p->strength == 0.f;                             // a copy: the input's bits, nothing is transformed
+    a.Fmax = dn_frames(g, r.n_max);
+    if (!a.copy) {
+        dn_fill(a, g, dn_tables(c, g));
+        float* bias_d = c->fbuf("dn.bias", g.nf);
+        c->upload(bias_d, bias, (size_t)g.nf * 4);
+        a.bias = bias_d; a.strength = p->strength; a.floor = p->floor;
+        a.work = c->fbuf("dn.work", (size_t)B * a.Fmax * g.n_fft);
+    } else { a.n_fft = g.n_fft; a.log2n = g.log2n; a.hop = g.hop; a.pad = g.pad; }
+    const DevRows rows = stage_rows(c, "dn", in, nsamples, B, Nmax, flags);
+    a.x = rows.x; a.x_bs = Nmax; a.nsamples = rows.len; a.B = B;
+    a.out = ret.out_rows("dn.out", out, out_stride, &a.out_bs); a.pcm16 = (flags & ZVX_PCM16) ? 1 : 0;
+    TagScope scope(c, "post.denoise");
+    c->timed(a.copy ? 0.0 : dn_fft_flops(g, frames, 2), 4.0 * r.n_sum + (double)ret.ss * r.n_sum, [&] {
+        if (!a.copy) launch_denoise_frames(a, c->stream);
+        launch_denoise_ola(a, r.n_max, c->stream);
+    });
+    ret.finish(nullptr, out, out_stride, nsamples, flags);
+}
+
+constexpr int DN_BIAS_FRAMES = 88;       // mel frames of silence the bias is measured on
+
+void do_denoise_bias(zvx_ctx* c, float* bias) {
+    const char* who = "zvx_denoise_bias";
+    if (!bias) fail(ZVX_E_INVALID, "%s: bias is NULL", who);
+    const DnGeom g = dn_geom(c, who);
+    const int P = DN_BIAS_FRAMES, nm = c->n_mels, n = P * c->hop;
+    if (n < dn_min_samples(g)) fail(ZVX_E_UNSUPPORTED, "%s: %d samples of silence are shorter than one frame (%d)", who, n, dn_min_samples(g));
+    const zvx_ctx::DnTables& tb = dn_tables(c, g);
+    float* zmel = c->fbuf("dn.zmel", (size_t)P * nm);
+    HIPCHK(hipMemsetAsync(zmel, 0, (size_t)P * nm * 4, c->stream));
+    float* wav = c->fbuf("dn.bwav", (size_t)n);
+    run_vocoder(c, zmel, nm, P, &P, &P, 1, wav, n, 0);       // what zvx_vocode_mel runs for one row of P zero frames at the native rate
+    const int F = dn_frames(g, n);
+    DenoiseArgs a{};
+    dn_fill(a, g, tb);
+    a.x = wav; a.x_bs = n; a.nsamples = c->upload_ints("dn.len", &n, 1); a.B = 1; a.Fmax = F;
+    a.mag = c->fbuf("dn.mag", (size_t)F * g.nf);
+    {
+        TagScope scope(c, "post.denoise");
+        c->timed(dn_fft_flops(g, F, 1), 4.0 * n + 4.0 * F * g.nf, [&] { launch_denoise_frames(a, c->stream); });
+    }
+    const float* host = (const float*)c->join_pinned((size_t)F * g.nf * 4);
+    HIPCHK(hipMemcpyAsync((void*)host, a.mag, (size_t)F * g.nf * 4, hipMemcpyDeviceToHost, c->stream));
+    c->sync();
+    for (int k = 0; k < g.nf; k++) {                         // the mean over all frames, in double, rounded once
+        double s = 0.0;
+        for (int f = 0; f < F; f++) s += (double)host[(size_t)f * g.nf + k];
+        bias[k] = (float)(s / (double)F);
+    }
+}
+
 // wav: float rows, or int16 PCM rows with ZVX_PCM16 (stride counted in samples either way).  Row b receives
 // mel_len[b]*hop samples followed by zeros up to max_b(mel_len[b])*hop; nothing beyond that is touched.
 void do_vocode(zvx_ctx* c, const int32_t* pad_to, void* wav, int64_t wav_stride, int flags) {
@@ -2966,6 +3095,15 @@ zvx_status zvx_limit_ex(zvx_ctx* c, const float* in, const int32_t* nsamples, in
         const LimitWindow win{in_origin, out_begin, out_count, last};
         do_limit(c, "zvx_limit_ex", in, nsamples, B, Nmax, rate, params, 0, out, out_stride, peak_in, min_gain, flags, &win);
     });
+}
+
+zvx_status zvx_denoise_bias(zvx_ctx* c, float* bias) {
+    return guarded(c, [&] { do_denoise_bias(c, bias); });
+}
+
+zvx_status zvx_denoise(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias,
+                       const zvx_denoise_params* params, void* out, int64_t out_stride, int flags) {
+    return guarded(c, [&] { do_denoise(c, in, nsamples, B, Nmax, bias, params, out, out_stride, flags); });
 }
 
 zvx_status zvx_synthesize(zvx_ctx* c, const int32_t* phoneme, const int32_t* puncts, const int32_t* duration, const int32_t* T,

@@ -439,6 +439,31 @@ void launch_limit_env(const LimitArgs& a, hipStream_t s);
 bool launch_limit_gain(const LimitArgs& a, hipStream_t s);
 // one workgroup per row over the tiles' partial results
 void launch_limit_reduce(const LimitArgs& a, hipStream_t s);
+// Vocoder-bias denoiser (include/zvx.h, zvx_denoise; spectral.hip): spectral subtraction over the STFT frames of zvx_melspec, the frames
+// transformed by an FFT that lives in LDS.  A workgroup of 256 threads holds DENOISE_POINTS complex f32 points, i.e. DENOISE_POINTS / n_fft
+// frames of ONE row (4 at 1024), as split re / im planes; every pass of the radix-4 Stockham transform (one radix-2 pass first where
+// log2 n_fft is odd) reads its inputs into registers, synchronises, and writes its outputs to the same planes.  Lengths are read on the
+// DEVICE; the host has validated them (zvx_melspec's conditions), so every reflected index lies inside the row.
+constexpr int DENOISE_POINTS = 4096;         // also the largest n_fft
+struct DenoiseArgs {
+    const float* x; long x_bs; const int* nsamples; int B;
+    int n_fft, log2n, hop, pad, Fmax;        // Fmax: the most frames of a row (the frame buffers' row pitch, in frames)
+    const float* twid;                       // [n_fft][2]: cos, -sin of 2 pi m / n_fft, designed in double, rounded once
+    const float* win;                        // [n_fft]: the analysis / synthesis window, likewise
+    const double* win2;                      // [n_fft]: its square, from the double window
+    double den_min;                          // the pass-through threshold on den (include/zvx.h)
+    const float* bias; float strength, floor;
+    float* work;                             // [B][Fmax][n_fft]: w[t] y_f[t]
+    float* mag;                              // launch_denoise_frames: non-NULL = magnitude-out mode, |X[f][k]| -> mag[B][Fmax][n_fft / 2 + 1], nothing else
+    void* out; long out_bs; int pcm16;
+    int copy;                                // launch_denoise_ola: strength == 0, out[i] = x[i] and `work` is not read
+};
+// frame load (reflect padding, window), forward FFT, gain, inverse FFT, window, store of w[t] y_f[t]; no spectrum goes to memory.
+// grid = (ceil(Fmax / frames per workgroup), B): B <= 65535.
+void launch_denoise_frames(const DenoiseArgs& a, hipStream_t s);
+// gather-form overlap-add: one thread per output sample sums the frames that cover it in ascending f (num in f32 from +0, den in double
+// from win2), divides once, or passes x[i] through where den < den_min.  Reads x at its own index only: safe in place.  n_max: the longest row.
+void launch_denoise_ola(const DenoiseArgs& a, long n_max, hipStream_t s);
 // half-mode saturation audit: *count += number of elements of x[b][r < rows[b]][0:C] (16-bit, batch stride bs, row stride ld) whose
 // magnitude bits are >= 0x7BFF (+-65504 = a clamped store, or Inf / NaN)
 void launch_count_sat16(const void* x, long bs, int ld, int B, int rows_max, const int* rows, int C, unsigned long long* count, hipStream_t s);

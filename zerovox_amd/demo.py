@@ -7,7 +7,8 @@ same RTF definition (audio seconds / synthesis seconds), same warm-up rule (iter
 sentence by sentence in batches and joins the sentences on the device; --wav-filename receives the joined waveform.
 `--loudness LUFS` (with `--peak-db DB`) brings the waveform -- with `--long` the paragraph as one programme -- to an integrated loudness on
 the device (zvx_normalize).  `--limiter` (with `--limiter-ms MS`) holds it under `--peak-db` with the true-peak look-ahead limiter
-(zvx_limit); the loudness gain is then no longer bounded by the peak.
+(zvx_limit); the loudness gain is then no longer bounded by the peak.  `--denoise S` takes S times the vocoder's bias spectrum off the
+waveform on the device, directly behind the vocoder (zvx_denoise; 0.01 is the usual strength; its audible benefit is not measured here).
 """
 import argparse
 import os
@@ -39,6 +40,8 @@ def main():
     ap.add_argument("--peak-db", type=float, default=-1.0, metavar="DB", help="sample-peak ceiling of the loudness gain in dBFS")
     ap.add_argument("--limiter", action="store_true", help="limit the waveform to --peak-db on the device (true-peak detection, look-ahead)")
     ap.add_argument("--limiter-ms", type=float, default=5.0, metavar="MS", help="smoothing window of the limiter's gain on either side of a peak")
+    ap.add_argument("--denoise", type=float, default=None, metavar="S",
+                    help="strength of the vocoder-bias denoiser on the device, e.g. 0.01 (default: off)")
     ap.add_argument("--long", action="store_true", help="long-form: split the text (or the file it names) into sentences and join them on the device")
     args = ap.parse_args()
 
@@ -56,7 +59,7 @@ def main():
         if args.long:
             wav, segments = synth.tts_long(text, spkemb, speed=args.speed, pitch_shift=args.pitch_shift, pitch_range=args.pitch_range,
                                            energy_shift=args.energy_shift, energy_range=args.energy_range, loudness=args.loudness,
-                                           peak_db=args.peak_db, limiter=args.limiter, limiter_ms=args.limiter_ms)
+                                           peak_db=args.peak_db, limiter=args.limiter, limiter_ms=args.limiter_ms, denoise=args.denoise)
             elapsed = time.time() - t0
             wav_len = (wav.shape[0] if segments else 0) / sr
             print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, {len(segments)} sentences, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")
@@ -67,7 +70,7 @@ def main():
             continue
         wav, phoneme, length = synth.tts(args.text, spkemb, speed=args.speed, pitch_shift=args.pitch_shift, pitch_range=args.pitch_range,
                                          energy_shift=args.energy_shift, energy_range=args.energy_range, loudness=args.loudness,
-                                         peak_db=args.peak_db, limiter=args.limiter, limiter_ms=args.limiter_ms)
+                                         peak_db=args.peak_db, limiter=args.limiter, limiter_ms=args.limiter_ms, denoise=args.denoise)
         elapsed = time.time() - t0
         wav_len = wav.shape[0] / sr
         print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")

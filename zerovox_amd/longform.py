@@ -77,8 +77,9 @@ def split_sentences(text, max_chars=MAX_CHARS):
 
 def synthesize_long(tts, text, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20, fade_ms=5, max_batch=32, max_frames=2048, pcm16=False,
                     durations=None, max_chars=MAX_CHARS, prosody=None, loudness=None, peak_db=-1.0, loudness_mode="paragraph",
-                    limiter=False, limiter_ms=5.0):
-    """The body of ZeroVoxTTS.tts_long (see there).  prosody: Prosody.create keywords applied to every sentence, or None."""
+                    limiter=False, limiter_ms=5.0, denoise=None):
+    """The body of ZeroVoxTTS.tts_long (see there).  prosody: Prosody.create keywords applied to every sentence, or None.  denoise: None or
+    Context.denoise_device keywords (strength, floor)."""
     from . import _lib
     if loudness_mode not in LOUDNESS_MODES:
         raise ValueError(f"loudness_mode: {loudness_mode!r} is none of {sorted(LOUDNESS_MODES)}")
@@ -106,6 +107,7 @@ def synthesize_long(tts, text, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20,
     spk = np.asarray(spkemb, np.float32).reshape(1, -1)
     mel_len = np.zeros(N, np.int32)
     durs = []
+    bias = tts.model.denoise_bias if denoise is not None else None      # (first use runs the vocoder: before anything is queued)
     buf = ctx.dev_alloc(N * stride * 4)
     try:
         for b0 in range(0, N, max_batch):
@@ -134,6 +136,8 @@ def synthesize_long(tts, text, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20,
         kw = dict(frame=frame, hop=hp, top_db=float(trim_db), keep=keep, fade=fade)
         lengths = mel_len.astype(np.int64) * hop
         lufs, gain = [None] * N, [None] * N
+        if denoise is not None:                                  # ONE call over all rows, in place, directly behind the vocoder's rows
+            ctx.denoise_device(buf, lengths, stride, bias, no_sync=True, **denoise)
         if loudness is not None:                                 # ONE call over all rows, in place, behind the queued synthesis calls
             lufs, _, gain = ctx.normalize_device(buf, lengths, stride, loudness, peak_ceiling=0.0 if lim else peak_ceiling(peak_db),
                                                  common=LOUDNESS_MODES[loudness_mode], rate=native)

@@ -106,6 +106,7 @@ class ZeroVox:
         self._min_mel_len = 689                         # model.py:254 -- stateful, see inference_ex
         self.last_loudness = None                       # dict(lufs, peak, gain) of the last inference_ex(..., loudness=...) call
         self.last_limit = None                          # dict(peak_in, min_gain) of the last inference_ex(..., limiter=...) call
+        self._denoise_bias = None                       # zvx_denoise_bias of the main context, computed on first use (denoise_bias)
         self.hidden = self._ctx.hidden
 
     @property
@@ -128,19 +129,36 @@ class ZeroVox:
         for c in [self._ctx] + self._more_ctx:
             c.set_int("out_rate", hz)
 
+    @property
+    def denoise_bias(self):
+        """[fft_size / 2 + 1] float32: the vocoder's bias spectrum (include/zvx.h, zvx_denoise_bias), computed once, on first use.  It
+        runs the vocoder, so it is taken BEFORE a call's encoder, never between a decode and its vocode."""
+        if self._denoise_bias is None:
+            self._denoise_bias = self._ctx.denoise_bias()
+        return self._denoise_bias
+
+    def refresh_denoise_bias(self):
+        """recompute the bias, e.g. after a switch that changes the vocoder's arithmetic (set_int "voc_f16") -> the new bias"""
+        self._denoise_bias = None
+        return self.denoise_bias
+
     def _spkemb(self, x):
         """ResNetSE34V2.forward: x [B, Tr, 80] -> [B, 1, hidden] (ResNetSE34V2.py:176-212)."""
         x = np.asarray(x, np.float32)
         lens = np.full(x.shape[0], x.shape[1], np.int32)
         return self._ctx.spkemb(x, lens)[:, None, :]
 
-    def inference_ex(self, x, style_embed, normalize_before=True, force_duration=False, prosody=None, loudness=None, limiter=None):
+    def inference_ex(self, x, style_embed, normalize_before=True, force_duration=False, prosody=None, loudness=None, limiter=None,
+                     denoise=None):
         """model.py:308-347.  x = {"phoneme" [1,T], "puncts" [1,T], "duration" [1,T]|None}; returns
         (wav[:mel_len*hop], mel_len, log_duration [1,T], mel [n_mels, mel_len]).  Batch-1 like the reference.
         Under an output_rate the waveform holds resampled_len(mel_len*hop) samples of that rate; mel_len stays in frames.
         prosody: None, a prosody.Prosody or a dict of Prosody.create keywords (speed, pitch / energy shift and range, targets).
         loudness: None (the path above, untouched) or Context.normalize_device keywords (target, peak_ceiling, max_gain_db).
-        limiter: None (likewise) or Context.limit_device keywords (ceiling, window_ms, oversample); it runs behind the loudness gain."""
+        limiter: None (likewise) or Context.limit_device keywords (ceiling, window_ms, oversample); it runs behind the loudness gain.
+        denoise: None (likewise) or Context.denoise_device keywords (strength, floor): the bias denoiser, directly behind the vocoder."""
+        if denoise is not None:
+            denoise = dict(denoise, bias=self.denoise_bias)          # (first use runs the vocoder: before this call's encoder)
         phoneme = np.asarray(x["phoneme"], np.int32)
         puncts = np.asarray(x["puncts"], np.int32)
         if phoneme.ndim != 2 or phoneme.shape[0] != 1:
@@ -157,16 +175,17 @@ class ZeroVox:
         pad_to = self._min_mel_len                       # model.py:331-335: pad up, or raise the floor
         if ml > self._min_mel_len:
             self._min_mel_len = ml
-        if loudness is not None or limiter is not None:
-            wav = self._vocode_normalized(mel_len, pad_to, loudness, limiter)
+        if loudness is not None or limiter is not None or denoise is not None:
+            wav = self._vocode_normalized(mel_len, pad_to, loudness, limiter, denoise)
             return wav, ml, logd, np.ascontiguousarray(mel[0, :ml].T)
         wav = self._ctx.vocode(1, mel_len, np.array([pad_to], np.int32))
         return wav[0, : self._ctx.out_samples(ml * self._hop_length)], ml, logd, np.ascontiguousarray(mel[0, :ml].T)
 
-    def _vocode_normalized(self, mel_len, pad_to, loudness, limiter=None):
-        """The vocoder writes its row on the device at the model's rate, zvx_normalize brings it to loudness["target"] in place (queued
-        behind the vocoder: stream order is the fence), zvx_limit holds it under limiter["ceiling"] in place, an output rate converts it,
-        and only then the row comes to the host.  Either step may be absent.  self.last_loudness reports dict(lufs, peak, gain),
+    def _vocode_normalized(self, mel_len, pad_to, loudness, limiter=None, denoise=None):
+        """The vocoder writes its row on the device at the model's rate, zvx_denoise takes denoise["strength"] times the bias off it in
+        place (queued behind the vocoder: stream order is the fence), zvx_normalize brings it to loudness["target"] in place,
+        zvx_limit holds it under limiter["ceiling"] in place, an output rate converts it,
+        and only then the row comes to the host.  Every step may be absent.  self.last_loudness reports dict(lufs, peak, gain),
         self.last_limit dict(peak_in, min_gain)."""
         ctx = self._ctx
         n = int(mel_len[0]) * self._hop_length
@@ -175,6 +194,8 @@ class ZeroVox:
         buf = ctx.dev_alloc(n * 4)
         try:
             ctx.vocode_device(mel_len, np.array([pad_to], np.int32), buf, n, native_rate=True, no_sync=True)
+            if denoise is not None:
+                ctx.denoise_device(buf, [n], n, no_sync=True, **denoise)
             if loudness is not None:
                 lufs, peak, gain = ctx.normalize_device(buf, [n], n, rate=native, **loudness)
                 self.last_loudness = dict(lufs=float(lufs[0]), peak=float(peak[0]), gain=float(gain[0]))

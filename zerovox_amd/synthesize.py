@@ -175,13 +175,23 @@ class ZeroVoxTTS:
         return None if loudness is None else dict(target=float(loudness), peak_ceiling=peak_ceiling(peak_db))
 
     @staticmethod
+    def _denoise(denoise):
+        """the denoise keyword as Context.denoise_device keywords, or None (nothing is denoised); checked without a device"""
+        if denoise is None:
+            return None
+        s = float(denoise)
+        if not np.isfinite(s) or s < 0:
+            raise ValueError(f"denoise must be None or a finite strength >= 0, not {denoise!r}")
+        return dict(strength=s, floor=0.0)
+
+    @staticmethod
     def _limiter(limiter, limiter_ms, peak_db):
         """the limiter keywords as Context.limit_device keywords, or None (nothing is limited)"""
         from .longform import limit_keywords
         return limit_keywords(limiter, limiter_ms, peak_db)
 
     def tts_ex(self, text: str, spkemb, duration=None, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0,
-               loudness=None, peak_db=-1.0, limiter=False, limiter_ms=5.0):
+               loudness=None, peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None):
         """-> (wav f32[N], phoneme i32[1,T], length, mel f32[n_mels, L]); empty text -> the reference's sentinel
         (synthesize.py:213-239).  Prosody (include/zvx.h, zvx_prosody): speed = speaking-rate factor (2.0: half the frames),
         pitch / energy shift (in normalised predictor units) and range (spread about the utterance mean).
@@ -192,8 +202,13 @@ class ZeroVoxTTS:
         limiter: with True a look-ahead limiter (include/zvx.h, zvx_limit) holds the row under peak_db dBFS on the device, its gain
         smoothed over limiter_ms on either side and driven by the 4x oversampled (true-peak) envelope.  With ``loudness`` the gain is
         then NOT bounded by the peak (only by +20 dB), so the target is reached and the limiter takes the peaks; without it the row is
-        just limited.  Order: gain, limiter, output-rate conversion, copy to the host.  ``last_limit`` reports dict(peak_in, min_gain)."""
+        just limited.  Order: gain, limiter, output-rate conversion, copy to the host.  ``last_limit`` reports dict(peak_in, min_gain).
+        denoise: None (the default: no launch, buffer or table of it exists), or the strength of the vocoder-bias denoiser (include/zvx.h,
+        zvx_denoise; NVIDIA's scripts use 0.01): that multiple of ``denoise_bias`` is taken off the magnitude of every STFT bin of the
+        vocoder's row, on the device, in place, directly behind the vocoder -- before the gain, the limiter and the rate conversion.
+        Its audible benefit on a real checkpoint is not measured here."""
         prosody = self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range)
+        dn = self._denoise(denoise)
         text = text.strip()
         t0 = time.time()
         phone_ids, punct_ids = self.text2phonemeids(text)
@@ -206,15 +221,15 @@ class ZeroVoxTTS:
         t1 = time.time()
         wav, length, _, mel = self._model.inference_ex({"phoneme": phoneme, "puncts": puncts, "duration": duration},
                                                        style_embed=spkemb, force_duration=duration is not None, prosody=prosody,
-                                                       **self._post(loudness, peak_db, limiter, limiter_ms))
+                                                       **self._post(loudness, peak_db, limiter, limiter_ms, dn))
         if self._verbose:
             print(f"tts timing stats: g2p={t1 - t0}s, synth={time.time() - t1}s")
         return wav, phoneme, length, mel
 
-    def _post(self, loudness, peak_db, limiter, limiter_ms):
-        """the inference_ex keywords of the loudness / limiter steps ({}: neither, the plain path)"""
+    def _post(self, loudness, peak_db, limiter, limiter_ms, denoise=None):
+        """the inference_ex keywords of the denoise / loudness / limiter steps ({}: none of them, the plain path)"""
         lim = self._limiter(limiter, limiter_ms, peak_db)
-        kw = {}
+        kw = {} if denoise is None else {"denoise": denoise}
         if loudness is not None:
             kw["loudness"] = self._loudness(loudness, None if lim else peak_db)      # under a limiter the gain has no peak ceiling
         if lim:
@@ -222,11 +237,22 @@ class ZeroVoxTTS:
         return kw
 
     def tts(self, text: str, spkemb, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0, loudness=None,
-            peak_db=-1.0, limiter=False, limiter_ms=5.0):
+            peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None):
         wav, phoneme, length, _ = self.tts_ex(text=text, spkemb=spkemb, speed=speed, pitch_shift=pitch_shift, pitch_range=pitch_range,
                                               energy_shift=energy_shift, energy_range=energy_range, loudness=loudness, peak_db=peak_db,
-                                              limiter=limiter, limiter_ms=limiter_ms)
+                                              limiter=limiter, limiter_ms=limiter_ms, denoise=denoise)
         return wav, phoneme, length
+
+    @property
+    def denoise_bias(self):
+        """[fft_size / 2 + 1] float32: the bias spectrum ``denoise=`` subtracts (include/zvx.h, zvx_denoise_bias): what the vocoder emits
+        for silence, computed once per context on first use.  It depends on the vocoder's arithmetic: call ``refresh_denoise_bias()``
+        after a vocoder precision switch (set_int "voc_f16" / "voc_f16_stages")."""
+        return self._model.denoise_bias
+
+    def refresh_denoise_bias(self):
+        """recompute ``denoise_bias`` under the context's current switches -> the new bias"""
+        return self._model.refresh_denoise_bias()
 
     @property
     def last_limit(self):
@@ -239,7 +265,7 @@ class ZeroVoxTTS:
         return self._model.last_loudness
 
     def tts_stream(self, text: str, spkemb, chunk_frames=64, chunks_per_call=1, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0,
-                   energy_shift=0.0, energy_range=1.0, loudness=None, limiter=False, peak_db=None, limiter_ms=5.0):
+                   energy_shift=0.0, energy_range=1.0, loudness=None, limiter=False, peak_db=None, limiter_ms=5.0, denoise=None):
         """Streaming variant of ``tts`` (not in the reference): encoder + mel decoder run once, the vocoder
         runs chunk by chunk (16-frame halo), yielding float32 waveform pieces that concatenate to ``tts(text, spkemb)[0]``
         up to the reference's `_min_mel_len` zero-padding of short utterances.  A stream cannot be loudness-normalised: the gain is not
@@ -249,7 +275,10 @@ class ZeroVoxTTS:
         4x oversampled envelope.  The pieces then concatenate bit for bit to zvx_limit of the unlimited stream's own concatenation
         -- not to ``tts(limiter=True)``, which pads a short utterance first -- and run limiter.reach(W, 4) samples behind the vocoder
         (2 W + 11: 231 samples for 5 ms at 22.05 kHz); under an ``output_rate`` the conversion follows the limiter, as in ``tts``.
-        That delay is why the ceiling is asked for by name: ``limiter=True`` still raises ValueError and points here."""
+        That delay is why the ceiling is asked for by name: ``limiter=True`` still raises ValueError and points here.
+        A stream is not denoised either: zvx_denoise has no windowed form, so ``denoise`` other than None raises ValueError."""
+        if denoise is not None:
+            raise ValueError("tts_stream cannot denoise: zvx_denoise has no windowed form (use tts or tts_long)")
         if loudness is not None:
             raise ValueError("tts_stream cannot normalise loudness: the gain is unknown until the last chunk (use tts or tts_long)")
         if limiter:
@@ -280,7 +309,7 @@ class ZeroVoxTTS:
 
     def tts_long(self, text: str, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20, fade_ms=5, max_batch=32, max_frames=2048, pcm16=False,
                  durations=None, max_chars=200, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0,
-                 loudness=None, peak_db=-1.0, loudness_mode="paragraph", limiter=False, limiter_ms=5.0):
+                 loudness=None, peak_db=-1.0, loudness_mode="paragraph", limiter=False, limiter_ms=5.0, denoise=None):
         """A paragraph -> (wav, segments): one waveform with every sentence in text order (not in the reference).  The text is split by
         longform.split_sentences; the sentences run in batches of at most max_batch, each batch ONE queued synthesize call into
         consecutive rows of one device buffer (every row is the fresh-model ``tts`` of its sentence; a sentence of more than max_frames
@@ -301,12 +330,16 @@ class ZeroVoxTTS:
         shorter than 0.4 s or silent) and gain (the linear factor applied).
         limiter: with True ONE zvx_limit over all rows, in place, between the normalise and the join, at peak_db dBFS with a 4x
         oversampled envelope and limiter_ms of smoothing on either side; the loudness gain then has no peak ceiling (see tts_ex).
-        Every segment dict then also carries min_gain (the limiter's smallest gain in that sentence; 1.0: untouched)."""
+        Every segment dict then also carries min_gain (the limiter's smallest gain in that sentence; 1.0: untouched).
+        denoise: None, or the strength of the vocoder-bias denoiser (see tts_ex): ONE zvx_denoise over all rows of the device buffer, in
+        place, behind the synthesis calls and before the normalise.  The segments' layout is that of the same call without it whenever
+        trim_db <= 0 (the trim decides on the denoised rows)."""
         from .longform import synthesize_long
         return synthesize_long(self, text, spkemb, pauses=pauses, trim_db=trim_db, keep_ms=keep_ms, fade_ms=fade_ms, max_batch=max_batch,
                                max_frames=max_frames, pcm16=pcm16, durations=durations, max_chars=max_chars,
                                prosody=self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range),
-                               loudness=loudness, peak_db=peak_db, loudness_mode=loudness_mode, limiter=limiter, limiter_ms=limiter_ms)
+                               loudness=loudness, peak_db=peak_db, loudness_mode=loudness_mode, limiter=limiter, limiter_ms=limiter_ms,
+                               denoise=self._denoise(denoise))
 
     @property
     def output_rate(self):
