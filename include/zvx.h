@@ -522,6 +522,42 @@ zvx_status zvx_denoise_bias(zvx_ctx* ctx, float* bias);
  * flags: ZVX_DEVICE_IN, ZVX_DEVICE_OUT, ZVX_NO_SYNC (device out only), ZVX_PCM16 (not in place); out == in (same stride) allowed for f32 */
 zvx_status zvx_denoise(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias,
                        const zvx_denoise_params* params, void* out, int64_t out_stride, int flags);
+/* The same denoiser over a window, so that a stream is denoised piece by piece and comes out bit-identical to one whole-signal call (as
+ * zvx_limit_ex limits one).  Row b holds samples [in_origin, in_origin + nsamples[b]) of a signal x that starts at sample 0; with
+ * last != 0 x ends at N_b = in_origin + nsamples[b], with last == 0 it continues past the window.  The outputs [out_begin, out_begin + cnt_b)
+ * of zvx_denoise on the WHOLE signal go to positions [0, cnt_b) of out row b; nothing else in out is touched.  cnt_b = out_count; with
+ * out_count == -1, which needs last, cnt_b = in_origin + nsamples[b] - out_begin (to the end of the row's signal; none where that is <= 0).
+ * Frame grid: the whole signal's -- frame f covers padded positions [f hop, f hop + n_fft), i.e. samples [f hop - pad, f hop - pad + n_fft),
+ *   whatever in_origin is.  The reflect at sample 0 exists only in a window with in_origin == 0, the reflect at N_b - 1 only with last.  F
+ *   comes from N_b with last and is unbounded otherwise.
+ * Reach: R = n_fft - 1: a frame that covers sample i begins after i - n_fft and ends before i + n_fft (four frames cover a sample at 1024 /
+ *   256; 1023 samples to either side).
+ * Support condition, per row with cnt_b > 0 (otherwise ZVX_E_INVALID; the message names the row, R and the missing samples):
+ *     in_origin <= out_begin  and  out_begin + cnt_b <= in_origin + nsamples[b];
+ *     left:  in_origin == 0  or  out_begin - R >= in_origin;
+ *     right: last  or  out_begin + cnt_b - 1 + R <= in_origin + nsamples[b] - 1.
+ *   Under it every frame that covers an emitted sample reads inside the window, or in a mirror that is the true signal's.
+ * Results: the emitted samples are bit for bit those of zvx_denoise on the whole signal (f32, and int16 with ZVX_PCM16), because (1) a
+ *   frame's transform depends on its own n_fft samples only, not on which slot of a workgroup it lands in; (2) the overlap-add runs over the
+ *   same frames in ascending f; (3) den comes from the same double table.  (1) is kept by construction, not left to the compiler: a
+ *   workgroup holds 4096 / n_fft frames and its unrolled butterfly copies serve different slots, so frame f is always given slot
+ *   f mod (4096 / n_fft), the one it has in the whole call -- the work buffer is indexed from the first needed frame rounded down to a
+ *   multiple of that, and the slots in front of the first needed frame stay empty.  Only the frames that cover an emitted sample are
+ *   transformed.  The den < den_min rule (out = x) uses the whole signal's F, so the uncovered tail of the last window behaves as in the
+ *   whole call.  strength == 0 is still a copy, of the emitted range, after the same validation.
+ * zvx_denoise is zvx_denoise_ex(..., 0, 0, -1, 1).  Validation: every check of zvx_denoise (out_stride >= Nmax included), and ZVX_E_INVALID
+ *   for a negative in_origin or out_begin, out_count < -1, out_count == -1 without last, last outside {0, 1}, out_stride smaller than the
+ *   longest cnt_b, out == in unless out_begin == in_origin (then zvx_denoise's in-place conditions apply).  zvx_melspec's length conditions
+ *   apply to the whole SIGNAL: they are checked on N_b with last; a window that is not the last needs the support condition only.  Flags,
+ *   syncs, the queued form, the non-finite rule and the "post.denoise" tag are zvx_denoise's (bytes: 4 per sample read plus the bytes written
+ *   per emitted sample); `last` is a parameter, not a flag bit.  No sample or frame index is formed in 32 bits from an absolute position:
+ *   in_origin and out_begin may lie beyond 2^32.
+ * A stream: zerovox_amd/denoiser.py plans the windows -- a non-last push emits up to received - R, the last one everything, the history
+ *   before next_out - R is dropped -- so a denoised stream runs R samples behind its input (1023 samples, 46 ms, at 1024 / 22.05 kHz).  Each
+ *   window transforms again the up to 2 (n_fft / hop) frames that reach into its history; no frame state is carried between calls. */
+zvx_status zvx_denoise_ex(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias,
+                          const zvx_denoise_params* params, void* out, int64_t out_stride, int flags,
+                          int64_t in_origin, int64_t out_begin, int64_t out_count, int last);
 
 /* Debug/parity taps: copy an intermediate of the last call to host fp32.
  * what: "encoder_out" [B][Tmax][hidden] (after the style add), "features" [B][Lmax][hidden],

@@ -3,7 +3,11 @@
    the whole-utterance call for comparison (host mel in, host waveform out: the PCIe copies are inside every figure).
    python tools/stream_latency.py --peak-db DB [--limiter-ms MS] [out.json]   -> the same stream WITH and WITHOUT the windowed limiter
    (zvx_limit_ex at DB dBFS, 4x oversampled envelope), in this one process: first audio, all chunks and the median time between two
-   pieces for both, and the samples the limited stream runs behind (limiter.reach)."""
+   pieces for both, and the samples the limited stream runs behind (limiter.reach).
+   python tools/stream_latency.py --denoise S [--peak-db DB] [out.json]   -> the same stream WITH and WITHOUT the windowed denoiser
+   (zvx_denoise_ex at strength S with the model's own bias), in this one process: first piece, all pieces, the median piece gap, the
+   samples the denoised stream runs behind (denoiser.reach) and whether the pieces equal zvx_denoise of the whole stream bit for bit;
+   with --peak-db as well also the combined chain, limit(denoise(stream))."""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -14,6 +18,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("out", nargs="?", help="write the result as JSON here")
 ap.add_argument("--peak-db", type=float, default=None, metavar="DB", help="also time the stream limited at this ceiling (dBFS)")
 ap.add_argument("--limiter-ms", type=float, default=5.0, metavar="MS")
+ap.add_argument("--denoise", type=float, default=None, metavar="S", help="also time the stream denoised at this strength")
 args = ap.parse_args()
 
 cfg = zcfg.medium_modelcfg("styletts"); sd = zw.tts_state_dict(cfg, 0)
@@ -69,6 +74,31 @@ for cf in (16, 32, 64, 128, 256):
                         "piece_gap_ms": round(piece_gap(lambda: model.vocode_stream(mel, chunk_frames=cf, limiter=lim)), 3),
                         "bit_equal_to_whole_limit": bool(np.array_equal(limited, want)),
                         "samples_changed": int(np.count_nonzero(limited != got))}})
+    if args.denoise is not None:
+        from zerovox_amd.denoiser import reach as denoise_reach
+        den = dict(strength=float(args.denoise), floor=0.0)
+        bias = model.denoise_bias                            # (first use runs the vocoder: outside every timed region)
+        R = denoise_reach(ctx.get_int("fft_size"))
+        denoised = np.concatenate(list(model.vocode_stream(mel, chunk_frames=cf, denoise=den)))
+        want = ctx.denoise([whole], bias, **den)[0]
+        if "piece_gap_ms" not in res["chunks"][-1]:
+            res["chunks"][-1]["piece_gap_ms"] = round(piece_gap(lambda: model.vocode_stream(mel, chunk_frames=cf)), 3)
+        res["chunks"][-1]["denoised"] = {
+            "strength": args.denoise, "delay_samples": R,
+            "first_piece_ms": round(best(lambda: next(iter(model.vocode_stream(mel, chunk_frames=cf, denoise=den)))), 3),
+            "all_pieces_ms": round(best(lambda: list(model.vocode_stream(mel, chunk_frames=cf, denoise=den)), n=5), 3),
+            "piece_gap_ms": round(piece_gap(lambda: model.vocode_stream(mel, chunk_frames=cf, denoise=den)), 3),
+            "bit_equal_to_whole_denoise": bool(np.array_equal(denoised.view(np.uint32), want.view(np.uint32))),
+            "samples_changed": int(np.count_nonzero(denoised != got))}
+        if args.peak_db is not None:
+            both = np.concatenate(list(model.vocode_stream(mel, chunk_frames=cf, denoise=den, limiter=lim)))
+            want_both = ctx.limit([want], rate=native, **lim)[0][0]
+            res["chunks"][-1]["denoised_limited"] = {
+                "delay_samples": R + reach(window_samples(native, args.limiter_ms), lim["oversample"]),
+                "first_piece_ms": round(best(lambda: next(iter(model.vocode_stream(mel, chunk_frames=cf, denoise=den, limiter=lim)))), 3),
+                "all_pieces_ms": round(best(lambda: list(model.vocode_stream(mel, chunk_frames=cf, denoise=den, limiter=lim)), n=5), 3),
+                "piece_gap_ms": round(piece_gap(lambda: model.vocode_stream(mel, chunk_frames=cf, denoise=den, limiter=lim)), 3),
+                "bit_equal_to_whole_limit_of_denoise": bool(np.array_equal(both.view(np.uint32), want_both.view(np.uint32)))}
     print(res["chunks"][-1], flush=True)
 print(json.dumps(res))
 if args.out:

@@ -25,7 +25,8 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_comm_unique_id", "zvx_comm_init", "zvx_comm_gather", "zvx_comm_barrier", "zvx_comm_max_f64", "zvx_comm_info", "zvx_comm_destroy",
            "zvx_dev_alloc", "zvx_dev_free", "zvx_dev_from_host", "zvx_dev_to_host", "zvx_spkemb_ex", "zvx_wait_host",
            "zvx_encode_ex", "zvx_synthesize_ex", "zvx_resample", "zvx_resample_ex", "zvx_trim_bounds", "zvx_join",
-           "zvx_loudness", "zvx_normalize", "zvx_true_peak", "zvx_limit", "zvx_spkemb_wav", "zvx_limit_ex", "zvx_denoise_bias", "zvx_denoise")
+           "zvx_loudness", "zvx_normalize", "zvx_true_peak", "zvx_limit", "zvx_spkemb_wav", "zvx_limit_ex", "zvx_denoise_bias", "zvx_denoise",
+           "zvx_denoise_ex")
 ZVX_COMM_ID_BYTES = 128
 ZVX_LOUD_PER_ROW, ZVX_LOUD_COMMON = 0, 1
 LIMIT_TILE = 1024                                    # samples per workgroup of both limiter kernels (csrc/zvx_kernels.h, LIMIT_TILE)
@@ -141,6 +142,7 @@ def load():
     lib.zvx_spkemb_wav.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(RefParams), vp, vp, vp, vp, C.c_int]
     lib.zvx_denoise_bias.argtypes = [vp, vp]
     lib.zvx_denoise.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(DenoiseParams), vp, C.c_int64, C.c_int]
+    lib.zvx_denoise_ex.argtypes = lib.zvx_denoise.argtypes + [C.c_int64, C.c_int64, C.c_int64, C.c_int]
     _lib = lib
     return lib
 
@@ -452,6 +454,23 @@ class Context:
         out = np.zeros((B, Nmax), np.int16 if pcm16 else np.float32)
         self._chk(self._lib.zvx_denoise(self._h, _ptr(x), _ptr(n), B, Nmax, _ptr(bias), C.byref(prm), _ptr(out), Nmax, ZVX_PCM16 if pcm16 else 0))
         return out
+
+    def denoise_window(self, rows, bias, strength, floor=0.0, in_origin=0, out_begin=0, out_count=-1, last=True, pcm16=False, lengths=None):
+        """zvx_denoise_ex on host rows: the rows hold samples [in_origin, in_origin + len) of signals that start at sample 0 and, with
+        `last`, end with the row; the outputs [out_begin, out_begin + out_count) of the whole-signal denoiser (out_count -1, which needs
+        last: to the end of each row's signal) -> out [B][n] float32 / int16 -- row b holds its emitted samples, then zeros.  The window
+        must carry denoiser.reach(fft_size) = fft_size - 1 samples of support on either side of the outputs, except at the signal's own
+        ends (include/zvx.h)."""
+        x, n = self._rows(rows, lengths)
+        B, Nmax = x.shape
+        bias = self._denoise_bias_arg(bias)
+        prm = DenoiseParams(float(strength), float(floor))
+        cols = int(out_count) if out_count >= 0 else max(0, int(in_origin) + int(n.max() if B else 0) - int(out_begin))
+        stride = max(cols, Nmax)
+        out = np.zeros((B, stride), np.int16 if pcm16 else np.float32)
+        self._chk(self._lib.zvx_denoise_ex(self._h, _ptr(x), _ptr(n), B, Nmax, _ptr(bias), C.byref(prm), _ptr(out), stride, ZVX_PCM16 if pcm16 else 0,
+                                           int(in_origin), int(out_begin), int(out_count), 1 if last else 0))
+        return out[:, :cols]
 
     def denoise_device(self, ptr, lengths, Nmax, bias, strength, *, floor=0.0, no_sync=False):
         """zvx_denoise IN PLACE on device rows [B][Nmax] f32 at `ptr` (they may be the output of a synthesize / vocode_device call queued

@@ -1,4 +1,4 @@
-// spectral.hip -- the vocoder-bias denoiser (include/zvx.h: zvx_denoise, zvx_denoise_bias): STFT frames of a waveform row through an FFT
+// spectral.hip -- the vocoder-bias denoiser (include/zvx.h: zvx_denoise, zvx_denoise_ex, zvx_denoise_bias): STFT frames of a waveform row through an FFT
 // that lives in LDS, a per-bin gain, the inverse FFT, and the overlap-add of the windowed frames.  zvx_kernels.h: DenoiseArgs.
 //
 // The transform: Stockham autosort, radix 4 (one radix-2 pass first where log2 n_fft is odd), decimation in time.  A pass with sub-transform
@@ -10,6 +10,7 @@
 // the writes of the first radix-4 pass have stride 4, which the extra word per 32 spreads over all 32 banks of a ds_write_b32 group (later
 // passes write runs of p consecutive words: at most 2-way).  33 KB per workgroup: 4 workgroups, 16 waves, per CU of 160 KB.
 #include "zvx_kernels.h"
+#include <climits>
 
 namespace zvx {
 
@@ -79,21 +80,40 @@ __device__ __forceinline__ void dn_fft(float* sre, float* sim, const float2* __r
     }
 }
 
+// The window of a row of n samples (zvx_kernels.h, DenoiseArgs): the emitted count; the signal's frames from f_first on (all there will be
+// where the signal goes on); the frames transformed, i.e. those up to the last one that begins at or before the last emitted sample.
+__device__ __forceinline__ int dn_count(const DenoiseArgs& a, int n) {
+    const int room = max(0, n - a.off);
+    return a.cnt >= 0 ? min(a.cnt, room) : room;
+}
+__device__ __forceinline__ int dn_frames_from_first(const DenoiseArgs& a, int n) {
+    if (n <= 0) return 0;
+    if (!a.right) return INT_MAX;
+    const long span = a.origin + n + 2 * a.pad - a.n_fft;   // absolute: 64 bits
+    const long F = span >= 0 ? 1 + span / a.hop - a.f_first : 0;
+    return (int)min(max(F, 0L), (long)INT_MAX);
+}
+__device__ __forceinline__ int dn_frames_used(const DenoiseArgs& a, int n) {
+    const int cnt = dn_count(a, n);
+    if (cnt <= 0) return 0;
+    return min(dn_frames_from_first(a, n), (a.off + cnt - 1 - a.rel) / a.hop + 1);
+}
+
 __global__ __launch_bounds__(DN_THREADS) void k_denoise_frames(const DenoiseArgs a) {
     __shared__ float sre[DN_PLANE], sim[DN_PLANE];
     const int tid = threadIdx.x, b = blockIdx.y, N = a.n_fft, lg = a.log2n;
     const int n = a.nsamples[b];
-    const int F = n > 0 ? 1 + (n + 2 * a.pad - N) / a.hop : 0;
+    const int F = dn_frames_used(a, n);                      // frames f_first .. f_first + F - 1 of the signal, f below counted from f_first
     const int f0 = blockIdx.x * (DENOISE_POINTS >> lg);
     if (f0 >= F) return;                                     // (uniform over the workgroup)
     const float* x = a.x + (long)b * a.x_bs;
     for (int i = tid; i < DENOISE_POINTS; i += DN_THREADS) {
         const int f = f0 + (i >> lg), t = i & (N - 1);
         float v = 0.f;
-        if (f < F) {
-            int s = f * a.hop + t - a.pad;                   // numpy 'reflect'; inside the row for every validated length, clamped all the same
-            if (s < 0) s = -s;
-            if (s >= n) s = 2 * (n - 1) - s;
+        if (f < F && f >= a.skip) {
+            int s = a.rel + f * a.hop + t;                   // numpy 'reflect' where the signal's end is in the window; inside the window for every
+            if (a.left && s < 0) s = -s;                     // validated length and support, clamped all the same
+            if (a.right && s >= n) s = 2 * (n - 1) - s;
             s = min(max(s, 0), n - 1);
             v = a.win[t] * x[s];
         }
@@ -105,7 +125,7 @@ __global__ __launch_bounds__(DN_THREADS) void k_denoise_frames(const DenoiseArgs
     if (a.mag) {                                             // magnitude-out mode (zvx_denoise_bias)
         for (int g = tid; g < items; g += DN_THREADS) {
             const int q = g / nf, k = g - q * nf, i = dn_at((q << lg) + k);
-            if (f0 + q < F) a.mag[((long)b * a.Fmax + f0 + q) * nf + k] = sqrtf(sre[i] * sre[i] + sim[i] * sim[i]);
+            if (f0 + q < F && f0 + q >= a.skip) a.mag[((long)b * a.Fmax + f0 + q) * nf + k] = sqrtf(sre[i] * sre[i] + sim[i] * sim[i]);
         }
         return;
     }
@@ -126,7 +146,7 @@ __global__ __launch_bounds__(DN_THREADS) void k_denoise_frames(const DenoiseArgs
     const float inv_n = 1.f / (float)N;                      // a power of two: exact
     for (int i = tid; i < DENOISE_POINTS; i += DN_THREADS) {
         const int f = f0 + (i >> lg), t = i & (N - 1);
-        if (f < F) a.work[((long)b * a.Fmax + f) * N + t] = a.win[t] * (sre[dn_at(i)] * inv_n);
+        if (f < F && f >= a.skip) a.work[((long)b * a.Fmax + f) * N + t] = a.win[t] * (sre[dn_at(i)] * inv_n);
     }
 }
 
@@ -134,12 +154,13 @@ __device__ __forceinline__ short dn_pcm(float v) { return (short)fminf(fmaxf(v *
 
 __global__ __launch_bounds__(256) void k_denoise_ola(const DenoiseArgs a) {
     const int b = blockIdx.y, n = a.nsamples[b], N = a.n_fft;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
+    const int e = blockIdx.x * 256 + threadIdx.x;
+    if (e >= dn_count(a, n)) return;
+    const int i = a.off + e;                                 // the sample's index in the window
     const float xi = a.x[(long)b * a.x_bs + i];
     float v = xi;
     if (!a.copy) {
-        const int F = 1 + (n + 2 * a.pad - N) / a.hop, p = i + a.pad;
+        const int F = dn_frames_from_first(a, n), p = i - a.rel;                             // p: the padded position, counted from frame f_first's
         const int f_hi = min(F - 1, p / a.hop), f_lo = p < N ? 0 : (p - N) / a.hop + 1;      // frames f with f hop <= p < f hop + n_fft
         const float* w = a.work + (long)b * a.Fmax * N;
         float num = 0.f;
@@ -151,8 +172,8 @@ __global__ __launch_bounds__(256) void k_denoise_ola(const DenoiseArgs a) {
         }
         if (den >= a.den_min) v = num / (float)den;
     }
-    if (a.pcm16) ((short*)a.out)[(long)b * a.out_bs + i] = dn_pcm(v);
-    else ((float*)a.out)[(long)b * a.out_bs + i] = v;
+    if (a.pcm16) ((short*)a.out)[(long)b * a.out_bs + e] = dn_pcm(v);
+    else ((float*)a.out)[(long)b * a.out_bs + e] = v;
 }
 
 void launch_denoise_frames(const DenoiseArgs& a, hipStream_t s) {

@@ -2469,13 +2469,13 @@ const double* limit_win(zvx_ctx* c, int W) {
 // The window of zvx_limit_ex: the rows hold samples [in_origin, in_origin + nsamples[b]) of their signals, the outputs [out_begin,
 // out_begin + cnt_b) are emitted.  The whole-row calls are {0, 0, -1, 1}.
 struct LimitWindow { int64_t in_origin = 0, out_begin = 0, out_count = -1; int last = 1; };
-// per row the emitted count, after the window's own checks and the support condition of include/zvx.h (R = 2 W + H)
-std::vector<int32_t> limit_window_counts(const char* who, const LimitWindow& w, const int32_t* nsamples, int B, int W, int os) {
+// per row the emitted count, after the window's own checks and the support condition of include/zvx.h for the reach R (zvx_limit_ex:
+// 2 W + H; zvx_denoise_ex: n_fft - 1)
+std::vector<int32_t> window_counts(const char* who, const LimitWindow& w, const int32_t* nsamples, int B, int64_t R) {
     if (w.in_origin < 0 || w.out_begin < 0) fail(ZVX_E_INVALID, "%s: in_origin %lld / out_begin %lld is negative", who, (long long)w.in_origin, (long long)w.out_begin);
     if (w.out_count < -1) fail(ZVX_E_INVALID, "%s: out_count %lld (-1: to the end of the signal)", who, (long long)w.out_count);
     if (w.last != 0 && w.last != 1) fail(ZVX_E_INVALID, "%s: last is %d (0 or 1)", who, w.last);
     if (w.out_count == -1 && !w.last) fail(ZVX_E_INVALID, "%s: out_count -1 needs last: the signal's end is not in the window", who);
-    const int64_t R = 2 * (int64_t)W + (os > 1 ? LIMIT_ENV_REACH : 0);
     std::vector<int32_t> cnt(B);
     for (int b = 0; b < B; b++) {
         const int64_t end_in = w.in_origin + nsamples[b];
@@ -2495,6 +2495,9 @@ std::vector<int32_t> limit_window_counts(const char* who, const LimitWindow& w, 
         cnt[b] = (int32_t)n;                                 // n <= nsamples[b] where n > 0
     }
     return cnt;
+}
+std::vector<int32_t> limit_window_counts(const char* who, const LimitWindow& w, const int32_t* nsamples, int B, int W, int os) {
+    return window_counts(who, w, nsamples, B, 2 * (int64_t)W + (os > 1 ? LIMIT_ENV_REACH : 0));
 }
 
 // zvx_true_peak (p == nullptr: the envelope's maximum only, results in tpeak), zvx_limit and zvx_limit_ex (win != nullptr)
@@ -2615,12 +2618,13 @@ const zvx_ctx::DnTables& dn_tables(zvx_ctx* c, const DnGeom& g) {
 void dn_fill(DenoiseArgs& a, const DnGeom& g, const zvx_ctx::DnTables& tb) {
     a.n_fft = g.n_fft; a.log2n = g.log2n; a.hop = g.hop; a.pad = g.pad;
     a.twid = tb.twid; a.win = tb.win; a.win2 = tb.win2; a.den_min = tb.den_min;
+    a.origin = 0; a.f_first = 0; a.skip = 0; a.rel = -g.pad; a.left = a.right = 1; a.off = 0; a.cnt = -1;      // the whole rows
 }
 double dn_fft_flops(const DnGeom& g, double frames, int transforms) { return transforms * frames * 5.0 * g.n_fft * g.log2n; }
 
-void do_denoise(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias, const zvx_denoise_params* p, void* out,
-                int64_t out_stride, int flags) {
-    const char* who = "zvx_denoise";
+// zvx_denoise (win == nullptr: the whole rows) and zvx_denoise_ex
+void do_denoise(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias, const zvx_denoise_params* p,
+                void* out, int64_t out_stride, int flags, const LimitWindow* win = nullptr) {
     const RowsInfo r = rows_check(who, in, nsamples, B, Nmax, 65535);
     flags_check(who, flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16);
     out_rows_check(who, in, out, out_stride, Nmax, flags);
@@ -2629,32 +2633,66 @@ void do_denoise(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int
     if (!(p->floor >= 0.f && p->floor <= 1.f)) fail(ZVX_E_INVALID, "%s: floor must lie in [0, 1]", who);
     const DnGeom g = dn_geom(c, who);
     for (int k = 0; k < g.nf; k++) if (!(bias[k] >= 0.f)) fail(ZVX_E_INVALID, "%s: bias[%d] is negative or NaN", who, k);
-    double frames = 0;
-    for (int b = 0; b < B; b++) {
-        if (nsamples[b] > 0 && nsamples[b] < dn_min_samples(g))
-            fail(ZVX_E_INVALID, "%s: row %d has %d samples; a row that is not empty needs at least %d (zvx_melspec's conditions)", who, b, nsamples[b], dn_min_samples(g));
-        frames += dn_frames(g, nsamples[b]);
+    // the emitted range: [off, off + cnt[b]) of row b; the whole row unless a window is given
+    const LimitWindow whole;
+    const LimitWindow& w = win ? *win : whole;
+    std::vector<int32_t> cnt_win;
+    const int32_t* cnt = nsamples;
+    long off = 0, cnt_max = r.n_max; double cnt_sum = r.n_sum;
+    if (win) {
+        cnt_win = window_counts(who, w, nsamples, B, g.n_fft - 1);
+        cnt = cnt_win.data(); off = (long)(w.out_begin - w.in_origin); cnt_max = 0; cnt_sum = 0;
+        for (int b = 0; b < B; b++) { cnt_max = std::max<long>(cnt_max, cnt[b]); cnt_sum += cnt[b]; }
+        if (cnt_max == 0) off = 0;
+        if (out_stride < cnt_max) fail(ZVX_E_INVALID, "%s: out_stride %lld is smaller than the longest output row %ld", who, (long long)out_stride, cnt_max);
+        if (out == (const void*)in && off != 0) fail(ZVX_E_INVALID, "%s: in place needs out_begin == in_origin", who);
     }
-    RowsReturn ret(c, B, 0, false, true, r.n_max, flags);
+    // zvx_melspec's length conditions hold for the whole SIGNAL: known where it ends with the window
+    if (w.last)
+        for (int b = 0; b < B; b++)
+            if (nsamples[b] > 0 && w.in_origin + nsamples[b] < dn_min_samples(g))
+                fail(ZVX_E_INVALID, "%s: row %d has %lld samples; a row that is not empty needs at least %d (zvx_melspec's conditions)", who, b,
+                     (long long)(w.in_origin + nsamples[b]), dn_min_samples(g));
+    // the frames transformed: from the first one that covers sample out_begin (the same for every row) to the last one that begins at or
+    // before a row's last emitted sample, on the signal's grid.  The kernels count frames from f_first, that first frame rounded DOWN to
+    // a multiple of the frames per workgroup: every frame then sits in the slot of its workgroup it has in the whole-row call and runs
+    // through the same instructions (the unrolled copies of a pass need not contract their multiply-adds alike), which is what makes the
+    // bits equal.  The `skip` frames in front are neither loaded nor stored.  (spectral.hip, dn_frames_used)
+    const int per = DENOISE_POINTS >> g.log2n;
+    const int64_t p0 = w.out_begin + g.pad;
+    const int64_t f_need = cnt_max > 0 && p0 >= g.n_fft ? (p0 - g.n_fft) / g.hop + 1 : 0;
+    const int64_t f_first = f_need - f_need % per;
+    // where frame f_first begins, as an index into the window: in (off - n_fft - per hop, off + hop - n_fft], an int
+    const int64_t rel = cnt_max > 0 ? f_first * g.hop - g.pad - w.in_origin : -(int64_t)g.pad;
+    double frames = 0; long Fmax = 0;
+    for (int b = 0; b < B; b++) {
+        if (cnt[b] <= 0) continue;
+        int64_t F = (off + cnt[b] - 1 - rel) / g.hop + 1;
+        if (w.last) F = std::min<int64_t>(F, std::max<int64_t>(0, dn_frames(g, w.in_origin + nsamples[b]) - f_first));
+        frames += (double)std::max<int64_t>(0, F - (f_need - f_first)); Fmax = std::max<long>(Fmax, (long)F);
+    }
+    RowsReturn ret(c, B, 0, false, true, cnt_max, flags);
     DenoiseArgs a{};
     a.copy = p->strength == 0.f;                             // a copy: the input's bits, nothing is transformed
-    a.Fmax = dn_frames(g, r.n_max);
     if (!a.copy) {
         dn_fill(a, g, dn_tables(c, g));
         float* bias_d = c->fbuf("dn.bias", g.nf);
         c->upload(bias_d, bias, (size_t)g.nf * 4);
         a.bias = bias_d; a.strength = p->strength; a.floor = p->floor;
-        a.work = c->fbuf("dn.work", (size_t)B * a.Fmax * g.n_fft);
+        a.work = c->fbuf("dn.work", (size_t)B * Fmax * g.n_fft);
     } else { a.n_fft = g.n_fft; a.log2n = g.log2n; a.hop = g.hop; a.pad = g.pad; }
+    a.Fmax = (int)Fmax;
+    a.origin = (long)w.in_origin; a.f_first = (long)f_first; a.skip = (int)(f_need - f_first); a.rel = (int)rel; a.left = w.in_origin == 0; a.right = w.last;
+    a.off = (int)off; a.cnt = (int)w.out_count;
     const DevRows rows = stage_rows(c, "dn", in, nsamples, B, Nmax, flags);
     a.x = rows.x; a.x_bs = Nmax; a.nsamples = rows.len; a.B = B;
     a.out = ret.out_rows("dn.out", out, out_stride, &a.out_bs); a.pcm16 = (flags & ZVX_PCM16) ? 1 : 0;
     TagScope scope(c, "post.denoise");
-    c->timed(a.copy ? 0.0 : dn_fft_flops(g, frames, 2), 4.0 * r.n_sum + (double)ret.ss * r.n_sum, [&] {
+    c->timed(a.copy ? 0.0 : dn_fft_flops(g, frames, 2), 4.0 * r.n_sum + (double)ret.ss * cnt_sum, [&] {
         if (!a.copy) launch_denoise_frames(a, c->stream);
-        launch_denoise_ola(a, r.n_max, c->stream);
+        launch_denoise_ola(a, cnt_max, c->stream);
     });
-    ret.finish(nullptr, out, out_stride, nsamples, flags);
+    ret.finish(nullptr, out, out_stride, cnt, flags);
 }
 
 constexpr int DN_BIAS_FRAMES = 88;       // mel frames of silence the bias is measured on
@@ -3103,7 +3141,16 @@ zvx_status zvx_denoise_bias(zvx_ctx* c, float* bias) {
 
 zvx_status zvx_denoise(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias,
                        const zvx_denoise_params* params, void* out, int64_t out_stride, int flags) {
-    return guarded(c, [&] { do_denoise(c, in, nsamples, B, Nmax, bias, params, out, out_stride, flags); });
+    return guarded(c, [&] { do_denoise(c, "zvx_denoise", in, nsamples, B, Nmax, bias, params, out, out_stride, flags); });
+}
+
+zvx_status zvx_denoise_ex(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias,
+                          const zvx_denoise_params* params, void* out, int64_t out_stride, int flags,
+                          int64_t in_origin, int64_t out_begin, int64_t out_count, int last) {
+    return guarded(c, [&] {
+        const LimitWindow win{in_origin, out_begin, out_count, last};
+        do_denoise(c, "zvx_denoise_ex", in, nsamples, B, Nmax, bias, params, out, out_stride, flags, &win);
+    });
 }
 
 zvx_status zvx_synthesize(zvx_ctx* c, const int32_t* phoneme, const int32_t* puncts, const int32_t* duration, const int32_t* T,

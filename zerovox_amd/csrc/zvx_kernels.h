@@ -444,25 +444,37 @@ void launch_limit_reduce(const LimitArgs& a, hipStream_t s);
 // frames of ONE row (4 at 1024), as split re / im planes; every pass of the radix-4 Stockham transform (one radix-2 pass first where
 // log2 n_fft is odd) reads its inputs into registers, synchronises, and writes its outputs to the same planes.  Lengths are read on the
 // DEVICE; the host has validated them (zvx_melspec's conditions), so every reflected index lies inside the row.
+// The window (zvx_denoise_ex): the rows hold samples [origin, origin + nsamples[b]) of their signals and the frame grid is the SIGNAL's.  The
+// kernels work in window-relative ints: frame j of the work buffer is frame f_first + j of the signal and reads the window from sample
+// rel + j hop on; the one absolute quantity, the signal's frame count, is formed in 64 bits from origin and f_first.  f_first is a
+// multiple of the frames per workgroup, so that a frame sits in the slot it has in the whole-row call and runs through the same
+// instructions: the first `skip` frames cover no emitted sample and are neither loaded nor stored.  The whole-row call is origin 0,
+// f_first 0, skip 0, rel -pad, both mirrors, off 0, cnt -1: the indices it forms are the ones it always formed.
 constexpr int DENOISE_POINTS = 4096;         // also the largest n_fft
 struct DenoiseArgs {
     const float* x; long x_bs; const int* nsamples; int B;
-    int n_fft, log2n, hop, pad, Fmax;        // Fmax: the most frames of a row (the frame buffers' row pitch, in frames)
+    int n_fft, log2n, hop, pad, Fmax;        // Fmax: the most frames transformed of a row (the frame buffers' row pitch, in frames)
+    long origin, f_first;                    // the window's first sample; frame 0 of the work buffer on the signal's grid (the same for every row)
+    int skip;                                // frames f_first .. f_first + skip - 1 cover no emitted sample: not transformed
+    int rel;                                 // f_first hop - pad - origin: where frame f_first begins, as an index into the window (negative: in the left mirror)
+    int left, right;                         // the reflect at sample 0 exists (origin == 0); the signal ends with the window (last): the reflect at its end exists
+    int off, cnt;                            // the emitted range: [off, off + cnt) of every row, cnt -1: to the end of the row
     const float* twid;                       // [n_fft][2]: cos, -sin of 2 pi m / n_fft, designed in double, rounded once
     const float* win;                        // [n_fft]: the analysis / synthesis window, likewise
     const double* win2;                      // [n_fft]: its square, from the double window
     double den_min;                          // the pass-through threshold on den (include/zvx.h)
     const float* bias; float strength, floor;
-    float* work;                             // [B][Fmax][n_fft]: w[t] y_f[t]
+    float* work;                             // [B][Fmax][n_fft]: w[t] y_f[t], indexed from f_first
     float* mag;                              // launch_denoise_frames: non-NULL = magnitude-out mode, |X[f][k]| -> mag[B][Fmax][n_fft / 2 + 1], nothing else
     void* out; long out_bs; int pcm16;
     int copy;                                // launch_denoise_ola: strength == 0, out[i] = x[i] and `work` is not read
 };
-// frame load (reflect padding, window), forward FFT, gain, inverse FFT, window, store of w[t] y_f[t]; no spectrum goes to memory.
-// grid = (ceil(Fmax / frames per workgroup), B): B <= 65535.
+// frame load (reflect padding, window), forward FFT, gain, inverse FFT, window, store of w[t] y_f[t]; no spectrum goes to memory.  Only the
+// frames that cover an emitted sample are transformed.  grid = (ceil(Fmax / frames per workgroup), B): B <= 65535.
 void launch_denoise_frames(const DenoiseArgs& a, hipStream_t s);
 // gather-form overlap-add: one thread per output sample sums the frames that cover it in ascending f (num in f32 from +0, den in double
-// from win2), divides once, or passes x[i] through where den < den_min.  Reads x at its own index only: safe in place.  n_max: the longest row.
+// from win2), divides once, or passes x[i] through where den < den_min; emitted sample e of a row goes to out[e].  Reads x at its own index
+// only: safe in place where off == 0.  n_max: the longest emitted range.
 void launch_denoise_ola(const DenoiseArgs& a, long n_max, hipStream_t s);
 // half-mode saturation audit: *count += number of elements of x[b][r < rows[b]][0:C] (16-bit, batch stride bs, row stride ld) whose
 // magnitude bits are >= 0x7BFF (+-65504 = a clamped store, or Inf / NaN)

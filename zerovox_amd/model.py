@@ -218,7 +218,7 @@ class ZeroVox:
     # each side makes a chunk's interior identical to the same samples of a whole-utterance pass.
     STREAM_HALO = 16
 
-    def vocode_stream(self, mel, chunk_frames=64, halo=STREAM_HALO, chunks_per_call=1, limiter=None):
+    def vocode_stream(self, mel, chunk_frames=64, halo=STREAM_HALO, chunks_per_call=1, limiter=None, denoise=None):
         """Chunked vocoding for first-audio latency: mel [L, n_mels] -> yields waveform chunks (np.float32) that
         concatenate to ``vocode_mel(mel)``.  Every chunk is vocoded with ``halo`` extra frames on each side and only its
         interior is kept; ``chunks_per_call`` chunks ride in one launch sequence as independent batch rows.
@@ -227,11 +227,21 @@ class ZeroVox:
         whole native stream; a piece is yielded once every sample under its filter has arrived.
         limiter: None, or the keywords longform.limit_keywords builds (ceiling, window_ms, oversample): the native-rate chunks pass
         through the windowed limiter (zerovox_amd.limiter, zvx_limit_ex) and concatenate bit for bit to zvx_limit of the whole native
-        stream; the limited stream runs limiter.reach(W, oversample) samples behind the vocoder.  Limiter first, conversion second."""
+        stream; the limited stream runs limiter.reach(W, oversample) samples behind the vocoder.  Limiter first, conversion second.
+        denoise: None (nothing of the denoiser is created), or the keywords ZeroVoxTTS._denoise builds (strength, floor): the native-rate
+        chunks pass through the windowed denoiser (zerovox_amd.denoiser, zvx_denoise_ex) with ``denoise_bias`` and concatenate bit for
+        bit to zvx_denoise of the whole native stream; the denoised stream runs denoiser.reach(fft_size) = fft_size - 1 samples behind
+        the vocoder.  Denoiser first, then the limiter, then the conversion -- the order of ``inference_ex``; the delays add up."""
         ctx = self._ctx
         rate, native = ctx.get_int("out_rate"), ctx.get_int("sampling_rate")
         convert = rate > 0 and rate != native
-        chunks = self._vocode_stream_native(mel, chunk_frames, halo, chunks_per_call, convert or limiter is not None)
+        if denoise is not None:
+            denoise = dict(denoise, bias=self.denoise_bias)          # (first use runs the vocoder: before this stream's first chunk)
+        chunks = self._vocode_stream_native(mel, chunk_frames, halo, chunks_per_call, convert or limiter is not None or denoise is not None)
+        if denoise is not None:
+            from .denoiser import DenoisePlanner, stream_denoise
+            chunks = stream_denoise(chunks, DenoisePlanner(ctx.get_int("fft_size")), lambda x, o, b, n, last: ctx.denoise_window(
+                [x], in_origin=o, out_begin=b, out_count=n, last=last, **denoise)[0].copy())
         if limiter is not None:
             from .limiter import LimitPlanner, stream_limit, window_samples
             plan = LimitPlanner(window_samples(native, limiter["window_ms"]), limiter["oversample"])

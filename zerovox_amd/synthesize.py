@@ -265,7 +265,8 @@ class ZeroVoxTTS:
         return self._model.last_loudness
 
     def tts_stream(self, text: str, spkemb, chunk_frames=64, chunks_per_call=1, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0,
-                   energy_shift=0.0, energy_range=1.0, loudness=None, limiter=False, peak_db=None, limiter_ms=5.0, denoise=None):
+                   energy_shift=0.0, energy_range=1.0, loudness=None, limiter=False, peak_db=None, limiter_ms=5.0, denoise=None,
+                   denoise_strength=None):
         """Streaming variant of ``tts`` (not in the reference): encoder + mel decoder run once, the vocoder
         runs chunk by chunk (16-frame halo), yielding float32 waveform pieces that concatenate to ``tts(text, spkemb)[0]``
         up to the reference's `_min_mel_len` zero-padding of short utterances.  A stream cannot be loudness-normalised: the gain is not
@@ -276,9 +277,17 @@ class ZeroVoxTTS:
         -- not to ``tts(limiter=True)``, which pads a short utterance first -- and run limiter.reach(W, 4) samples behind the vocoder
         (2 W + 11: 231 samples for 5 ms at 22.05 kHz); under an ``output_rate`` the conversion follows the limiter, as in ``tts``.
         That delay is why the ceiling is asked for by name: ``limiter=True`` still raises ValueError and points here.
-        A stream is not denoised either: zvx_denoise has no windowed form, so ``denoise`` other than None raises ValueError."""
+        denoise_strength: None (the default: nothing of the denoiser is created), or the strength of the vocoder-bias denoiser (see
+        tts_ex) the stream is put through window by window (include/zvx.h, zvx_denoise_ex; zerovox_amd.denoiser), directly behind the
+        vocoder.  The pieces then concatenate bit for bit to zvx_denoise of the undenoised stream's own concatenation -- not to
+        ``tts(denoise=...)``, which pads a short utterance first -- and run n_fft - 1 samples behind the vocoder (1023: 46 ms at 22.05
+        kHz).  With ``peak_db`` as well the stream is limit(denoise(stream)) and runs n_fft - 1 + limiter.reach(W, 4) samples behind;
+        an ``output_rate`` converts last.  That delay is why the strength is asked for by this name: ``denoise=...``, the
+        whole-utterance keyword of tts and tts_long, still raises ValueError and points here."""
         if denoise is not None:
-            raise ValueError("tts_stream cannot denoise: zvx_denoise has no windowed form (use tts or tts_long)")
+            raise ValueError("tts_stream does not take denoise=: pass denoise_strength=<strength> (the stream is then denoised window by window, "
+                             "n_fft - 1 samples behind the vocoder); denoise= is the whole-utterance keyword of tts and tts_long")
+        den = self._denoise(denoise_strength)
         if loudness is not None:
             raise ValueError("tts_stream cannot normalise loudness: the gain is unknown until the last chunk (use tts or tts_long)")
         if limiter:
@@ -290,22 +299,25 @@ class ZeroVoxTTS:
                 raise ValueError(f"tts_stream: peak_db must be finite, not {peak_db}")
             lim = self._limiter(True, limiter_ms, peak_db)
         return self._tts_stream(text, spkemb, chunk_frames, chunks_per_call, self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range),
-                                lim)
+                                lim, den)
 
-    def _tts_stream(self, text, spkemb, chunk_frames, chunks_per_call, prosody, limiter=None):
+    def _tts_stream(self, text, spkemb, chunk_frames, chunks_per_call, prosody, limiter=None, denoise=None):
         text = text.strip()
         phone_ids, punct_ids = self.text2phonemeids(text)
         if not phone_ids:
             return
         phoneme, puncts = np.array([phone_ids], np.int32), np.array([punct_ids], np.int32)
         ctx = self._model.ctx
+        if denoise is not None:
+            self._model.denoise_bias                                 # (first use runs the vocoder: before this call's encoder)
         mel_len, _, _, _ = ctx.encode(phoneme, puncts, np.array([len(phone_ids)], np.int32), np.asarray(spkemb, np.float32).reshape(1, -1),
                                    prosody=prosody)
         ml = int(mel_len[0])
         if ml < 2:
             raise ValueError(f"predicted mel length {ml} is too short to synthesise")
         mel = ctx.decode(1, ml)[0, :ml]
-        yield from self._model.vocode_stream(mel, chunk_frames=chunk_frames, chunks_per_call=chunks_per_call, limiter=limiter)
+        yield from self._model.vocode_stream(mel, chunk_frames=chunk_frames, chunks_per_call=chunks_per_call, limiter=limiter,
+                                             denoise=denoise)
 
     def tts_long(self, text: str, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20, fade_ms=5, max_batch=32, max_frames=2048, pcm16=False,
                  durations=None, max_chars=200, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0,
