@@ -6,27 +6,11 @@ project has no denoiser; nothing here is taken from it."""
 import numpy as np
 
 import denoise_ref as D
+from stream_util import supported
 
 
 def reach(n_fft):
     return n_fft - 1
-
-
-def supported(n_fft, in_origin, n_in, out_begin, cnt, last):
-    """the support condition of include/zvx.h (zvx_denoise_ex), restated: R = n_fft - 1"""
-    R = n_fft - 1
-    if cnt <= 0:
-        return True
-    inside = in_origin <= out_begin and out_begin + cnt <= in_origin + n_in
-    left = in_origin == 0 or out_begin - R >= in_origin
-    right = bool(last) or out_begin + cnt - 1 + R <= in_origin + n_in - 1
-    return inside and left and right
-
-
-def window_of(n, begin, end, R):
-    """the window with EXACTLY R samples of support around outputs [begin, end) of an n-sample signal: (in_origin, samples end, last)"""
-    o = max(0, begin - R)
-    return (o, end + R, 0) if end + R <= n else (o, n, 1)
 
 
 def cuts(n, n_fft, hop):
@@ -54,7 +38,7 @@ def denoise_window(samples, bias, strength, floor, in_origin, out_begin, out_cou
     cnt = out_count if out_count >= 0 else max(0, in_origin + k - out_begin)
     if cnt == 0:
         return np.zeros(0)
-    assert supported(n_fft, in_origin, k, out_begin, cnt, last), (in_origin, k, out_begin, cnt, last)
+    assert supported(reach(n_fft), in_origin, k, out_begin, cnt, last), (in_origin, k, out_begin, cnt, last)
     a = out_begin - in_origin
     if strength == 0:
         return x[a:a + cnt].copy()

@@ -12,6 +12,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import denoise_ref as D
+from stream_util import same_bits, vp
 from zerovox_amd import _lib, config as zcfg, pack, weights as zw
 
 SENTINEL32 = np.uint32(0xDEADBEEF)
@@ -72,12 +73,6 @@ def reference(strength, floor, n_fft=N_FFT, hop=HOP, win_length=None, lengths=LE
     return _ref[key]
 
 
-def vp(a):
-    if a is None:
-        return None
-    return C.c_void_p(int(a)) if isinstance(a, (int, np.integer)) else a.ctypes.data_as(C.c_void_p)
-
-
 def raw(ctx, x, n, Nmax, bias, prm, out, stride, flags=0, B=None):
     B = len(n) if B is None else B
     return ctx._lib.zvx_denoise(ctx._h, vp(x), vp(n), B, Nmax, vp(bias), C.byref(prm) if prm is not None else None, vp(out), stride, flags)
@@ -92,11 +87,6 @@ def run(ctx, x, n, bias, strength, floor, pcm16=False, stride=None, out=None):
     rc = raw(ctx, x, n, Nmax, bias, _lib.DenoiseParams(strength, floor), out, stride, _lib.ZVX_PCM16 if pcm16 else 0)
     assert rc == 0, ctx._lib.zvx_last_error(ctx._h)
     return out
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 def untouched(out, n):

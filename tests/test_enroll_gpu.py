@@ -11,6 +11,7 @@ pytestmark = pytest.mark.gpu
 
 import enroll_ref as E
 import join_ref as J
+from stream_util import vp
 from zerovox_amd import _lib, config as zcfg, pack, synthetic, weights as zw
 
 SENTINEL32 = np.uint32(0xDEADBEEF)
@@ -45,12 +46,6 @@ def padded(rows, odd=False):
     for b, r in enumerate(rows):
         x[b, :n[b]] = r
     return x, n
-
-
-def vp(a):
-    if a is None:
-        return None
-    return C.c_void_p(int(a)) if isinstance(a, (int, np.integer)) else a.ctypes.data_as(C.c_void_p)
 
 
 def params(frame=2048, hop=512, top_db=40.0, keep=0, max_samples=0):

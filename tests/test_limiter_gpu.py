@@ -17,7 +17,8 @@ import join_ref as J
 import limit_ref as L
 import loudness_ref as R
 import resample_ref as RS
-from zerovox_amd import _lib, config as zcfg, pack, synthetic, weights as zw
+from stream_util import _ragged_case, vp
+from zerovox_amd import _lib, config as zcfg, pack, weights as zw
 
 SENTINEL32 = np.uint32(0xDEADBEEF)
 SENTINEL16 = np.int16(0x5A5B)
@@ -78,12 +79,6 @@ def reference(seed, W, os_):
         rows = make_case(seed, W)[0]
         _ref[key] = [L.limit(r, CEILING, W, os_) for r in rows]
     return _ref[key]
-
-
-def vp(a):
-    if a is None:
-        return None
-    return C.c_void_p(int(a)) if isinstance(a, (int, np.integer)) else a.ctypes.data_as(C.c_void_p)
 
 
 def raw_true_peak(ctx, x, n, Nmax, rate, os_, flags=0, B=None, out=True):
@@ -262,14 +257,6 @@ def test_a_non_finite_row_leaves_the_others_alone():
         assert same_bits(tc[[0, 2]], tb[[0, 2]])
     again = ctx.limit(rows, CEILING, 1.0, 4, rate=22050)[0]
     assert same_bits(again, clean)
-
-
-def _ragged_case(B, T, seed):
-    ph, pu, Tl, spk, dur = synthetic.batch(B, T, seed, "uniform")
-    Tl = np.array([T] + [max(1, T - 3 * b - 1) for b in range(1, B)], np.int32)
-    for b in range(B):
-        ph[b, Tl[b]:] = 0; pu[b, Tl[b]:] = 0; dur[b, Tl[b]:] = 0
-    return ph, pu, Tl, spk, dur
 
 
 def test_queued_synthesis_and_normalise_feed_the_limiter_in_stream_order():

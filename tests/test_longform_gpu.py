@@ -10,7 +10,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import join_ref as J
-from zerovox_amd import _lib, config as zcfg, pack, synthetic, weights as zw
+from stream_util import _ragged_case, vp
+from zerovox_amd import _lib, config as zcfg, pack, weights as zw
 
 SENTINEL32 = np.uint32(0xDEADBEEF)
 SENTINEL16 = np.int16(0x5A5B)
@@ -37,12 +38,6 @@ def padded(rows, odd=False):
     for b, r in enumerate(rows):
         x[b, :n[b]] = r
     return x, n
-
-
-def vp(a):
-    if a is None:
-        return None
-    return C.c_void_p(int(a)) if isinstance(a, (int, np.integer)) else a.ctypes.data_as(C.c_void_p)
 
 
 def params(frame=2048, hop=512, top_db=40.0, keep=0, fade=0):
@@ -240,14 +235,6 @@ def test_join_errors_leave_the_context_usable():
     assert raw_bounds(ctx, x, n, Nmax, prm, 64)[0] == inv and b"zvx_trim_bounds" in ctx._lib.zvx_last_error(ctx._h)
     rc, out_len = raw_join(ctx, x, n, Nmax, gaps, prm, buf, total)[:2]
     assert rc == 0 and np.array_equal(buf[:total], ref.view(np.uint32))
-
-
-def _ragged_case(B, T, seed):
-    ph, pu, Tl, spk, dur = synthetic.batch(B, T, seed, "uniform")
-    Tl = np.array([T] + [max(1, T - 3 * b - 1) for b in range(1, B)], np.int32)
-    for b in range(B):
-        ph[b, Tl[b]:] = 0; pu[b, Tl[b]:] = 0; dur[b, Tl[b]:] = 0
-    return ph, pu, Tl, spk, dur
 
 
 TIGHT_DB = (6.0, 1.0)      # synthetic weights make noise-like audio: a tight threshold is what makes the trimmer cut something

@@ -13,7 +13,8 @@ pytestmark = pytest.mark.gpu
 
 import join_ref as J
 import loudness_ref as R
-from zerovox_amd import _lib, config as zcfg, pack, synthetic, weights as zw
+from stream_util import _ragged_case, vp
+from zerovox_amd import _lib, config as zcfg, pack, weights as zw
 
 SENTINEL32 = np.uint32(0xDEADBEEF)
 SENTINEL16 = np.int16(0x5A5B)
@@ -56,12 +57,6 @@ def case(seed, fs):
 def assert_unambiguous(m, what):
     assert np.all(m["margin"] > MARGIN), (what, m["margin"])
     assert m["margin_common"] > MARGIN, (what, m["margin_common"])
-
-
-def vp(a):
-    if a is None:
-        return None
-    return C.c_void_p(int(a)) if isinstance(a, (int, np.integer)) else a.ctypes.data_as(C.c_void_p)
 
 
 def raw_loudness(ctx, x, n, Nmax, rate, flags=0, B=None):
@@ -200,14 +195,6 @@ def test_normalised_rows_are_the_product_with_the_reported_gain(seed):
     out, lufs, peak, gain = ctx.normalize(rows, -23.0, rate=22050)
     assert within_one_ulp(gain, R.gains(m, -23.0)[0]) and all(same_bits(out[b, :n[b]], x[b, :n[b]] * gain[b]) for b in range(len(rows)))
     assert all(not out[b, n[b]:].any() for b in range(len(rows)))
-
-
-def _ragged_case(B, T, seed):
-    ph, pu, Tl, spk, dur = synthetic.batch(B, T, seed, "uniform")
-    Tl = np.array([T] + [max(1, T - 3 * b - 1) for b in range(1, B)], np.int32)
-    for b in range(B):
-        ph[b, Tl[b]:] = 0; pu[b, Tl[b]:] = 0; dur[b, Tl[b]:] = 0
-    return ph, pu, Tl, spk, dur
 
 
 def test_queued_synthesis_feeds_the_normaliser_in_stream_order():

@@ -60,13 +60,39 @@ def test_stream_planner_pieces_concatenate_to_the_whole_signal(rate_out, chunk_f
 
     emitted, kept = [], []
 
+    class Feed:
+        """the chunks as an iterator that counts what the driver has taken from it"""
+        def __init__(self):
+            self.it, self.nexts, self.received, self.done = iter(chunks), 0, 0, False
+
+        def __iter__(self):
+            return self
+
+        def __next__(self):
+            self.nexts += 1
+            try:
+                c = next(self.it)
+            except StopIteration:
+                self.done = True
+                raise
+            self.received += len(c)
+            return c
+
+    feed = Feed()
+
     def window(samples, in_origin, out_begin, out_count):
         assert not emitted or out_begin == emitted[-1][0] + emitted[-1][1], "an output is skipped or emitted twice"
+        if not feed.done:                                     # every piece but the closing one: final by the samples received so far
+            assert (out_begin + out_count - 1) * M + half <= (feed.received - 1) * L, (out_begin, out_count, feed.received)
         emitted.append((out_begin, out_count))
         kept.append(len(samples))
         return R.resample_window(samples, rate_in, rate_out, in_origin, out_begin, out_count)
 
-    pieces = list(stream_resample(chunks, rate_in, rate_out, window))
+    stream = stream_resample(feed, rate_in, rate_out, window)
+    pieces = [next(stream)]
+    assert len(chunks) > 2 and feed.nexts == 1 and feed.received == len(chunks[0])      # no chunk is held back for the next one
+    pieces += list(stream)
+    assert feed.done and feed.nexts == len(chunks) + 1
     got = np.concatenate(pieces)
     assert emitted[0][0] == 0 and sum(c for _, c in emitted) == len(whole) == R.out_len(n, rate_in, rate_out)
     assert got.shape == whole.shape and np.array_equal(got, whole)

@@ -11,7 +11,8 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import resample_ref as R
-from zerovox_amd import _lib, config as zcfg, pack, synthetic, weights as zw
+from stream_util import _ragged_case
+from zerovox_amd import _lib, config as zcfg, pack, weights as zw
 
 PAIRS = [(22050, 48000), (22050, 44100), (22050, 24000), (22050, 16000), (22050, 8000),
          (16000, 22050), (24000, 22050), (44100, 22050), (48000, 22050), (22050, 32000), (32000, 22050)]
@@ -185,14 +186,6 @@ def test_errors_leave_the_context_usable():
     assert ctx.get_int("out_rate") == 0
     got, _ = ctx.resample([np.ones(50, np.float32)], 22050, 48000)
     check_float(got[0], np.ones(50, np.float32), 22050, 48000, "after the errors")
-
-
-def _ragged_case(B, T, seed):
-    ph, pu, Tl, spk, dur = synthetic.batch(B, T, seed, "uniform")
-    Tl = np.array([T] + [max(1, T - 3 * b - 1) for b in range(1, B)], np.int32)
-    for b in range(B):
-        ph[b, Tl[b]:] = 0; pu[b, Tl[b]:] = 0; dur[b, Tl[b]:] = 0
-    return ph, pu, Tl, spk, dur
 
 
 @pytest.mark.parametrize("voc", ["tiny", "v1"])

@@ -1,10 +1,8 @@
 """The windowed denoiser, the parts that need no GPU: the float64 windowed restatement (tests/denoise_window_ref.py) against
-denoise_ref.denoise of the whole row, bit for bit, over every geometry and cut; zerovox_amd.denoiser's planner (every sample once and in
-order, the support condition of include/zvx.h restated on every planned window, latency, history); a stream driven through that
-reference; and the surface of the feature (header, exports, keywords, refusals)."""
+denoise_ref.denoise of the whole row, bit for bit, over every geometry and cut; a stream driven by zerovox_amd.denoiser through that
+reference (the support condition of include/zvx.h restated on every planned window); and the surface of the feature (header, exports, keywords, refusals)."""
 import ctypes as C
 import inspect
-import os
 import re
 
 import numpy as np
@@ -12,17 +10,12 @@ import pytest
 
 import denoise_ref as D
 import denoise_window_ref as DW
+from stream_util import cut, header, supported, window_of
 from zerovox_amd import _lib, denoiser as DN
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GEOMETRIES = [(1024, 256, 1024), (512, 256, 512), (256, 256, 128), (2048, 256, 2048), (64, 16, 64)]      # (n_fft, hop, win_length)
 STRENGTH, FLOOR = 0.5, 0.1
 _rows, _whole = {}, {}
-
-
-def header():
-    with open(os.path.join(ROOT, "include", "zvx.h")) as f:
-        return f.read()
 
 
 def lengths(n_fft, hop):
@@ -74,14 +67,14 @@ def test_windows_with_exactly_R_of_support_reproduce_the_whole_row(n_fft, hop, w
         moved += int(np.count_nonzero(want != x))
         edges = DW.cuts(n, n_fft, hop)
         for begin, end in zip(edges[:-1], edges[1:]):
-            o, w_end, last = DW.window_of(n, begin, end, R)
+            o, w_end, last = window_of(n, begin, end, R)
             reads = []
             got = DW.denoise_window(x[o:w_end], bias, STRENGTH, FLOOR, o, begin, end - begin, last, n_fft, hop, wl, reads=reads)
             assert same_f64(got, want[begin:end]), (n, begin, end, o, w_end, last, int(np.count_nonzero(got != want[begin:end])))
             assert 0 <= reads[0][0] and reads[0][1] < w_end - o                       # (the restatement asserts it on every frame as well)
             pieces += 1
         # out_count -1: to the end of the signal, from the last cut
-        o, w_end, last = DW.window_of(n, edges[-2], n, R)
+        o, w_end, last = window_of(n, edges[-2], n, R)
         assert last == 1 and same_f64(DW.denoise_window(x[o:], bias, STRENGTH, FLOOR, o, edges[-2], -1, 1, n_fft, hop, wl), want[edges[-2]:])
     assert pieces >= 15 and moved > 0, (pieces, moved)                 # (hop == n_fft: some of the cuts coincide)
 
@@ -90,9 +83,9 @@ def test_one_sample_short_of_support_is_refused_by_the_restatement():
     n_fft, hop, wl = 1024, 256, 1024
     R, n = DW.reach(n_fft), 3 * 1024 + 77
     x, bias = row(n, n_fft), bias_for(n_fft, hop, wl)
-    assert DW.supported(n_fft, 100, 2 * R + 10, 100 + R, 10, 0) and not DW.supported(n_fft, 100, 2 * R + 10, 99 + R, 10, 0)
-    assert not DW.supported(n_fft, 100, 2 * R + 10, 100 + R, 11, 0) and DW.supported(n_fft, 100, 2 * R + 10, 100 + R, 11, 1)
-    assert DW.supported(n_fft, 0, R + 10, 0, 10, 0) and not DW.supported(n_fft, 0, R + 10, 0, 11, 0)
+    assert supported(R, 100, 2 * R + 10, 100 + R, 10, 0) and not supported(R, 100, 2 * R + 10, 99 + R, 10, 0)
+    assert not supported(R, 100, 2 * R + 10, 100 + R, 11, 0) and supported(R, 100, 2 * R + 10, 100 + R, 11, 1)
+    assert supported(R, 0, R + 10, 0, 10, 0) and not supported(R, 0, R + 10, 0, 11, 0)
     with pytest.raises(AssertionError):
         DW.denoise_window(x[100:100 + 2 * R + 10], bias, STRENGTH, FLOOR, 100, 99 + R, 10, 0)
     # the condition is tight on the grid: an output at a frame's last sample reads R samples back, one at its first sample R ahead
@@ -105,15 +98,6 @@ def test_one_sample_short_of_support_is_refused_by_the_restatement():
     reads = []
     DW.denoise_window(x[i - R:i + R + 1], bias, STRENGTH, FLOOR, i - R, i, 1, 0, reads=reads)
     assert reads[0][1] == 2 * R
-
-
-def cut(x, sizes):
-    out, at, i = [], 0, 0
-    while at < len(x):
-        out.append(x[at:at + sizes[i % len(sizes)]])
-        at += len(out[-1])
-        i += 1
-    return out
 
 
 @pytest.mark.parametrize("n_fft,hop,wl", GEOMETRIES)
@@ -136,37 +120,15 @@ def test_stream_concatenates_to_the_whole_row(n_fft, hop, wl):
             pieces = list(DN.stream_denoise(cut(x, sizes), DN.DenoisePlanner(n_fft), window_fn))
             got = np.concatenate(pieces)
             assert same_f64(got, want), (n, name, len(got))
-            assert all(DW.supported(n_fft, *w) for w in windows), (n, name)
+            assert all(supported(R, *w) for w in windows), (n, name)
             assert max(k for (_, k, _, _, _) in windows) <= max(sizes) + 2 * R
 
 
-@pytest.mark.parametrize("n_fft", [64, 256, 1024, 4096])
-def test_planner_emits_every_sample_once_with_latency_R(n_fft):
-    R = DN.reach(n_fft)
-    rng = np.random.default_rng(n_fft)
-    for sizes in ([1] * (2 * n_fft + 50), [64] * 80, [int(v) for v in rng.integers(1, 3 * R + 5, 60)], [5 * n_fft]):
-        p = DN.DenoisePlanner(n_fft)
-        assert p.R == R and p.n_fft == n_fft
-        received = emitted = origin = 0
-        for k in sizes:
-            o, b, c, keep = p.push(k, False)
-            received += k
-            assert o == origin and b == emitted and c >= 0                            # in order, nothing twice, nothing skipped
-            emitted += c
-            assert emitted == max(0, received - R), (sizes[:3], received)             # a non-last push emits up to received - R
-            assert received - o <= k + 2 * R and DW.supported(n_fft, o, received - o, b, c, False)
-            assert keep == max(o, emitted - R) and keep >= o                          # the history before next_out - R is dropped
-            origin = keep
-        o, b, c, keep = p.push(0, True)                                               # push(0, True) flushes the rest
-        assert o == origin and b == emitted and b + c == received and DW.supported(n_fft, o, received - o, b, c, True) and received - o <= 2 * R
-    p = DN.DenoisePlanner(n_fft)
-    assert p.push(0, True) == (0, 0, 0, 0)                   # an empty stream
-    assert list(DN.stream_denoise([], DN.DenoisePlanner(n_fft), None)) == []
-
-
 def test_limiter_module_is_untouched_by_the_shared_planner():
-    from zerovox_amd import limiter as LM
-    assert issubclass(DN.DenoisePlanner, LM.LimitPlanner) and LM.LimitPlanner(110, 4).R == 231 and LM.reach(110, 4) == 231
+    from zerovox_amd import limiter as LM, stream
+    assert issubclass(DN.DenoisePlanner, stream.ReachPlanner) and issubclass(LM.LimitPlanner, stream.ReachPlanner)
+    assert not issubclass(DN.DenoisePlanner, LM.LimitPlanner)
+    assert LM.LimitPlanner(110, 4).R == 231 and LM.reach(110, 4) == 231
     assert DN.reach(1024) == 1023
 
 

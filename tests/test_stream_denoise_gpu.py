@@ -12,6 +12,7 @@ pytestmark = pytest.mark.gpu
 
 import denoise_ref as D
 import denoise_window_ref as DW
+from stream_util import err, same_bits, supported, vp, window_of
 from zerovox_amd import _lib, config as zcfg, denoiser as DN, pack, weights as zw
 
 SENTINEL32 = np.uint32(0xDEADBEEF)
@@ -66,26 +67,11 @@ def whole(geom, lengths, floor, pcm16=False):
     return _whole[key]
 
 
-def vp(a):
-    if a is None:
-        return None
-    return C.c_void_p(int(a)) if isinstance(a, (int, np.integer)) else a.ctypes.data_as(C.c_void_p)
-
-
 def raw_ex(ctx, x, n, Nmax, bias, prm, out, stride, win, flags=0, B=None):
     """zvx_denoise_ex; win = (in_origin, out_begin, out_count, last) -> rc"""
     B = len(n) if B is None else B
     return ctx._lib.zvx_denoise_ex(ctx._h, vp(x), vp(n), B, Nmax, vp(bias), C.byref(prm) if prm is not None else None, vp(out), stride, flags,
                                    *[int(v) for v in win])
-
-
-def err(ctx):
-    return ctx._lib.zvx_last_error(ctx._h)
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 def first_frame(begin, n_fft, hop):
@@ -108,10 +94,10 @@ def pieces_equal_whole(geom, lengths, floor):
         assert not same_bits(want[b, :n], x)                                          # the denoiser acts
         edges = [c for c in DW.cuts(n, n_fft, hop) if c < n] + [n]                    # 0, 1, hop - 1, hop, hop + 1, n_fft, n_fft + 1, n / 2 + 1, n - 1; n
         for begin, end in zip(edges[:-1], edges[1:]):
-            o, w_end, last = DW.window_of(n, begin, end, R)
+            o, w_end, last = window_of(n, begin, end, R)
             xin = np.ascontiguousarray(x[o:w_end])
             k, cnt = len(xin), end - begin
-            assert DW.supported(n_fft, o, k, begin, cnt, last)
+            assert supported(R, o, k, begin, cnt, last)
             stride = k + 5
             out = np.full((2, stride), SENTINEL32, np.uint32)                         # one row more than the call owns
             rc = raw_ex(ctx, xin, np.array([k], np.int32), k, bias, prm, out, stride, (o, begin, cnt, last))

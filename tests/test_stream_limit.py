@@ -1,6 +1,6 @@
 """The windowed limiter, the parts that need no GPU: zerovox_amd.limiter's planner against the float64 reference of tests/limit_ref.py
 (a stream limited window by window concatenates to the whole-row result: equal f32 bits, equal f64 gains), the support condition of
-include/zvx.h restated on every planned window, the planner's latency, and the surface of the feature (header, exports, constants,
+include/zvx.h restated on every planned window, and the surface of the feature (header, exports, constants,
 keywords, refusals)."""
 import ctypes as C
 import inspect
@@ -11,17 +11,12 @@ import numpy as np
 import pytest
 
 import limit_ref as L
+from stream_util import ROOT, cut, header, supported
 from zerovox_amd import _lib, limiter as LM
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CEILING = 0.891
 CONFIGS = [(1, 1), (5, 1), (22, 4), (110, 4), (40, 8), (110, 2)]          # (W, os)
 _rows, _ref = {}, {}
-
-
-def header():
-    with open(os.path.join(ROOT, "include", "zvx.h")) as f:
-        return f.read()
 
 
 def bits(a):
@@ -45,27 +40,6 @@ def whole(n, W, os_):
     if key not in _ref:
         _ref[key] = L.limit(row(n), CEILING, W, os_)
     return _ref[key]
-
-
-def cut(x, sizes):
-    """x in chunks of the given sizes (cycled), the last one as short as it comes"""
-    out, at, i = [], 0, 0
-    while at < len(x):
-        out.append(x[at:at + sizes[i % len(sizes)]])
-        at += len(out[-1])
-        i += 1
-    return out
-
-
-def supported(W, os_, in_origin, n_in, out_begin, cnt, last):
-    """the support condition of include/zvx.h (zvx_limit_ex), restated: R = 2 W + H, H = 11 where the envelope is oversampled"""
-    R = 2 * W + (11 if os_ > 1 else 0)
-    if cnt <= 0:
-        return True
-    inside = in_origin <= out_begin and out_begin + cnt <= in_origin + n_in
-    left = in_origin == 0 or out_begin - R >= in_origin
-    right = bool(last) or out_begin + cnt - 1 + R <= in_origin + n_in - 1
-    return inside and left and right
 
 
 def run_stream(x, W, os_, sizes):
@@ -104,7 +78,7 @@ def test_stream_concatenates_to_the_whole_row(W, os_):
             assert len(out) == n and np.array_equal(bits(out), bits(ref["out"])), (n, name)
             assert np.array_equal(g, ref["g"]), (n, name)
             for (o, k, b, c, last) in windows:
-                assert supported(W, os_, o, k, b, c, last), (n, name, o, k, b, c, last)
+                assert supported(R, o, k, b, c, last), (n, name, o, k, b, c, last)
     assert acted > 4400, acted                                # the limiter acts on most samples of these rows
 
 
@@ -114,8 +88,9 @@ def test_one_sample_chunks(W, os_):
     ref = whole(n, W, os_)
     out, g, windows = run_stream(row(n), W, os_, [1])
     assert np.array_equal(bits(out), bits(ref["out"])) and np.array_equal(g, ref["g"])
-    assert all(supported(W, os_, *w) for w in windows)
-    assert max(k for (_, k, _, _, _) in windows) <= 1 + 2 * LM.reach(W, os_)
+    R = LM.reach(W, os_)
+    assert all(supported(R, *w) for w in windows)
+    assert max(k for (_, k, _, _, _) in windows) <= 1 + 2 * R
 
 
 def test_a_window_one_sample_short_is_not_supported_and_may_differ():
@@ -123,9 +98,9 @@ def test_a_window_one_sample_short_is_not_supported_and_may_differ():
     W, os_, n = 22, 4, 2500
     R = LM.reach(W, os_)
     ref, x = whole(n, W, os_), row(n)
-    assert supported(W, os_, 501, 1200, 501 + R, 100, False) and not supported(W, os_, 501, 1200, 500 + R, 100, False)
-    assert supported(W, os_, 501, 1200, 900, 1200 - 399 - R, False) and not supported(W, os_, 501, 1200, 900, 1201 - 399 - R, False)
-    assert supported(W, os_, 0, 700, 0, 700 - R, False) and supported(W, os_, 900, n - 900, 900 + R, n - 900 - R, True)
+    assert supported(R, 501, 1200, 501 + R, 100, False) and not supported(R, 501, 1200, 500 + R, 100, False)
+    assert supported(R, 501, 1200, 900, 1200 - 399 - R, False) and not supported(R, 501, 1200, 900, 1201 - 399 - R, False)
+    assert supported(R, 0, 700, 0, 700 - R, False) and supported(R, 900, n - 900, 900 + R, n - 900 - R, True)
     differs = 0
     for begin in range(300, 1500, 7):                        # emit ONE sample whose support is short by one on the left
         o = begin - (R - 1)
@@ -134,30 +109,6 @@ def test_a_window_one_sample_short_is_not_supported_and_may_differ():
         ok = L.limit(x[o - 1:begin + R + 1], CEILING, W, os_)
         assert ok["g"][begin - o + 1] == ref["g"][begin] and bits(ok["out"])[begin - o + 1] == bits(ref["out"])[begin]
     print(f"{differs} of {len(range(300, 1500, 7))} samples differ when the window is one sample short")
-
-
-@pytest.mark.parametrize("W,os_", CONFIGS)
-def test_planner_latency_and_history(W, os_):
-    R = LM.reach(W, os_)
-    rng = np.random.default_rng(W + os_)
-    for sizes in ([1] * 700, [64] * 40, [int(v) for v in rng.integers(1, 3 * R + 5, 60)], [5000]):
-        p = LM.LimitPlanner(W, os_)
-        received = emitted = 0
-        origin = 0
-        for k in sizes:
-            o, b, c, keep = p.push(k, False)
-            received += k
-            assert o == origin and b == emitted and c >= 0
-            emitted += c
-            assert emitted == max(0, received - R), (sizes[:3], received)
-            assert received - o <= k + 2 * R and supported(W, os_, o, received - o, b, c, False)
-            assert keep == max(o, emitted - R) and keep >= o
-            origin = keep
-        o, b, c, keep = p.push(0, True)
-        assert b + c == received and supported(W, os_, o, received - o, b, c, True) and received - o <= 2 * R
-    p = LM.LimitPlanner(W, os_)
-    assert p.push(0, True) == (0, 0, 0, 0)                   # an empty stream
-    assert list(LM.stream_limit([], LM.LimitPlanner(W, os_), None)) == []
 
 
 def test_window_rule():

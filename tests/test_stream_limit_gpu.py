@@ -12,7 +12,8 @@ pytestmark = pytest.mark.gpu
 import join_ref as J
 import limit_ref as L
 import resample_ref as RS
-from zerovox_amd import _lib, config as zcfg, limiter as LM, pack, synthetic, weights as zw
+from stream_util import _ragged_case, same_bits, vp, window_of
+from zerovox_amd import _lib, config as zcfg, limiter as LM, pack, weights as zw
 
 SENTINEL32 = np.uint32(0xDEADBEEF)
 SENTINEL16 = np.int16(0x5A5B)
@@ -33,12 +34,6 @@ def ctx_for(voc="tiny", prec="bf16"):
     return _ctx[key]
 
 
-def vp(a):
-    if a is None:
-        return None
-    return C.c_void_p(int(a)) if isinstance(a, (int, np.integer)) else a.ctypes.data_as(C.c_void_p)
-
-
 def params(W, os_, ceiling=CEILING):
     ms = W * 1000.0 / RATE
     assert L.window(RATE, ms) == W == LM.window_samples(RATE, ms), (W, ms)
@@ -52,11 +47,6 @@ def raw_ex(ctx, x, n, Nmax, prm, out, stride, win, flags=0, B=None, results=True
     rc = ctx._lib.zvx_limit_ex(ctx._h, vp(x), vp(n), B, Nmax, rate, C.byref(prm) if prm is not None else None, vp(out), stride,
                                vp(peak) if results else None, vp(gmin) if results else None, flags, *[int(v) for v in win])
     return rc, peak, gmin
-
-
-def same_bits(a, b):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
 
 
 def spike_rows(rng):
@@ -100,12 +90,6 @@ def whole(ctx, seed, os_, W):
             a.setflags(write=False)
         _whole[key] = (out, peak, gmin)
     return _whole[key]
-
-
-def window_of(n, begin, end, R):
-    """the window with EXACTLY R samples of support around outputs [begin, end) of an n-sample signal: (in_origin, samples end, last)"""
-    o = max(0, begin - R)
-    return (o, end + R, 0) if end + R <= n else (o, n, 1)
 
 
 def cuts_for(n, R):
@@ -271,14 +255,6 @@ def test_origin_zero_to_the_end_is_zvx_limit(os_, W):
     assert np.all(out[B] == SENTINEL32)
     o2, p2, g2 = ctx.limit_window(rows, CEILING, params(W, os_).window_ms, os_, rate=RATE)      # the binding's defaults are that call
     assert same_bits(o2, want) and same_bits(p2, peak_w) and same_bits(g2, gmin_w)
-
-
-def _ragged_case(B, T, seed):
-    ph, pu, Tl, spk, dur = synthetic.batch(B, T, seed, "uniform")
-    Tl = np.array([T] + [max(1, T - 3 * b - 1) for b in range(1, B)], np.int32)
-    for b in range(B):
-        ph[b, Tl[b]:] = 0; pu[b, Tl[b]:] = 0; dur[b, Tl[b]:] = 0
-    return ph, pu, Tl, spk, dur
 
 
 def test_window_errors_leave_the_context_usable():

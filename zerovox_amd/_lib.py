@@ -260,17 +260,8 @@ class Context:
     def resample_window(self, rows, rate_in, rate_out, in_origin=0, out_begin=0, out_count=-1, pcm16=False, lengths=None):
         """zvx_resample_ex: the rows hold samples [in_origin, in_origin + len) of signals that are zero elsewhere; outputs
         [out_begin, out_begin + out_count) (out_count -1: to the end of each row's signal) -> (out [B][n], out_len [B])."""
-        if lengths is None:
-            B = len(rows)
-            n = np.array([len(w) for w in rows], np.int32)
-            Nmax = max(int(n.max()), 1)
-            x = np.zeros((B, Nmax), np.float32)
-            for b, w in enumerate(rows):
-                x[b, :n[b]] = np.asarray(w, np.float32)
-        else:
-            x = _f32(rows)
-            B, Nmax = x.shape
-            n = _i32(lengths, (B,))
+        x, n = self._rows(rows, lengths)
+        B, Nmax = x.shape
         if out_count >= 0:
             cols = int(out_count)
         else:
@@ -295,6 +286,24 @@ class Context:
             return x, n
         x = _f32(rows)
         return x, _i32(lengths, (x.shape[0],))
+
+    @staticmethod
+    def _window_out(n, Nmax, in_origin, out_begin, out_count, pcm16):
+        """the output rows of a zvx_limit_ex / zvx_denoise_ex call -> (out [B][stride] of zeros, cols: the longest emitted row)"""
+        cols = int(out_count) if out_count >= 0 else max(0, int(in_origin) + int(n.max() if len(n) else 0) - int(out_begin))
+        return np.zeros((len(n), max(cols, Nmax)), np.int16 if pcm16 else np.float32), cols
+
+    @staticmethod
+    def _flags(pcm16=False, device=False, no_sync=False):
+        return (ZVX_PCM16 if pcm16 else 0) | (ZVX_DEVICE_IN | ZVX_DEVICE_OUT if device else 0) | (ZVX_NO_SYNC if no_sync else 0)
+
+    @classmethod
+    def _limit_args(cls, ceiling, window_ms, oversample, **flags):
+        return LimitParams(float(ceiling), float(window_ms), int(oversample)), cls._flags(**flags)
+
+    @classmethod
+    def _denoise_args(cls, strength, floor, **flags):
+        return DenoiseParams(float(strength), float(floor)), cls._flags(**flags)
 
     def trim_bounds(self, rows, frame=2048, hop=512, top_db=40.0, keep=0, lengths=None):
         """zvx_trim_bounds: per row the samples [begin, end) that join keeps (the decisions of mels.trim_silence, made on the device)
@@ -391,11 +400,10 @@ class Context:
         b holds its limited samples, then zeros --, peak_in [B] float32: the envelope's maximum, min_gain [B] float32)."""
         x, n = self._rows(rows, lengths)
         B, Nmax = x.shape
-        prm = LimitParams(float(ceiling), float(window_ms), int(oversample))
+        prm, flags = self._limit_args(ceiling, window_ms, oversample, pcm16=pcm16)
         out = np.zeros((B, Nmax), np.int16 if pcm16 else np.float32)
         peak, gmin = np.zeros(B, np.float32), np.zeros(B, np.float32)
-        self._chk(self._lib.zvx_limit(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), Nmax, _ptr(peak), _ptr(gmin),
-                                      ZVX_PCM16 if pcm16 else 0))
+        self._chk(self._lib.zvx_limit(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), Nmax, _ptr(peak), _ptr(gmin), flags))
         return out, peak, gmin
 
     def limit_window(self, rows, ceiling, window_ms=5.0, oversample=4, in_origin=0, out_begin=0, out_count=-1, last=True, pcm16=False,
@@ -407,13 +415,11 @@ class Context:
         samples of support on either side of the outputs, except at the signal's own ends (include/zvx.h)."""
         x, n = self._rows(rows, lengths)
         B, Nmax = x.shape
-        prm = LimitParams(float(ceiling), float(window_ms), int(oversample))
-        cols = int(out_count) if out_count >= 0 else max(0, int(in_origin) + int(n.max() if B else 0) - int(out_begin))
-        stride = max(cols, Nmax)
-        out = np.zeros((B, stride), np.int16 if pcm16 else np.float32)
+        prm, flags = self._limit_args(ceiling, window_ms, oversample, pcm16=pcm16)
+        out, cols = self._window_out(n, Nmax, in_origin, out_begin, out_count, pcm16)
         peak, gmin = np.zeros(B, np.float32), np.zeros(B, np.float32)
-        self._chk(self._lib.zvx_limit_ex(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), stride, _ptr(peak), _ptr(gmin),
-                                         ZVX_PCM16 if pcm16 else 0, int(in_origin), int(out_begin), int(out_count), 1 if last else 0))
+        self._chk(self._lib.zvx_limit_ex(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), out.shape[1], _ptr(peak), _ptr(gmin),
+                                         flags, int(in_origin), int(out_begin), int(out_count), 1 if last else 0))
         return out[:, :cols], peak, gmin
 
     def limit_device(self, ptr, lengths, Nmax, ceiling, *, window_ms=5.0, oversample=4, rate=None, no_sync=False):
@@ -421,12 +427,11 @@ class Context:
         just before: stream order is the fence) -> (peak_in, min_gain); with no_sync the call only queues and returns None."""
         n = _i32(lengths)
         B = len(n)
-        prm = LimitParams(float(ceiling), float(window_ms), int(oversample))
+        prm, flags = self._limit_args(ceiling, window_ms, oversample, device=True, no_sync=no_sync)
         p = C.c_void_p(int(ptr))
         res = None if no_sync else (np.zeros(B, np.float32), np.zeros(B, np.float32))                                # peak_in, min_gain
         peak, gmin = res or (None, None)
-        self._chk(self._lib.zvx_limit(self._h, p, _ptr(n), B, int(Nmax), self._rate(rate), C.byref(prm), p, int(Nmax), _ptr(peak), _ptr(gmin),
-                                      ZVX_DEVICE_IN | ZVX_DEVICE_OUT | (ZVX_NO_SYNC if no_sync else 0)))
+        self._chk(self._lib.zvx_limit(self._h, p, _ptr(n), B, int(Nmax), self._rate(rate), C.byref(prm), p, int(Nmax), _ptr(peak), _ptr(gmin), flags))
         return res
 
     def denoise_bias(self):
@@ -450,9 +455,9 @@ class Context:
         x, n = self._rows(rows, lengths)
         B, Nmax = x.shape
         bias = self._denoise_bias_arg(bias)
-        prm = DenoiseParams(float(strength), float(floor))
+        prm, flags = self._denoise_args(strength, floor, pcm16=pcm16)
         out = np.zeros((B, Nmax), np.int16 if pcm16 else np.float32)
-        self._chk(self._lib.zvx_denoise(self._h, _ptr(x), _ptr(n), B, Nmax, _ptr(bias), C.byref(prm), _ptr(out), Nmax, ZVX_PCM16 if pcm16 else 0))
+        self._chk(self._lib.zvx_denoise(self._h, _ptr(x), _ptr(n), B, Nmax, _ptr(bias), C.byref(prm), _ptr(out), Nmax, flags))
         return out
 
     def denoise_window(self, rows, bias, strength, floor=0.0, in_origin=0, out_begin=0, out_count=-1, last=True, pcm16=False, lengths=None):
@@ -464,11 +469,9 @@ class Context:
         x, n = self._rows(rows, lengths)
         B, Nmax = x.shape
         bias = self._denoise_bias_arg(bias)
-        prm = DenoiseParams(float(strength), float(floor))
-        cols = int(out_count) if out_count >= 0 else max(0, int(in_origin) + int(n.max() if B else 0) - int(out_begin))
-        stride = max(cols, Nmax)
-        out = np.zeros((B, stride), np.int16 if pcm16 else np.float32)
-        self._chk(self._lib.zvx_denoise_ex(self._h, _ptr(x), _ptr(n), B, Nmax, _ptr(bias), C.byref(prm), _ptr(out), stride, ZVX_PCM16 if pcm16 else 0,
+        prm, flags = self._denoise_args(strength, floor, pcm16=pcm16)
+        out, cols = self._window_out(n, Nmax, in_origin, out_begin, out_count, pcm16)
+        self._chk(self._lib.zvx_denoise_ex(self._h, _ptr(x), _ptr(n), B, Nmax, _ptr(bias), C.byref(prm), _ptr(out), out.shape[1], flags,
                                            int(in_origin), int(out_begin), int(out_count), 1 if last else 0))
         return out[:, :cols]
 
@@ -477,10 +480,9 @@ class Context:
         just before: stream order is the fence); with no_sync the call only queues.  bias is a host array and may be reused at once."""
         n = _i32(lengths)
         bias = self._denoise_bias_arg(bias)
-        prm = DenoiseParams(float(strength), float(floor))
+        prm, flags = self._denoise_args(strength, floor, device=True, no_sync=no_sync)
         p = C.c_void_p(int(ptr))
-        self._chk(self._lib.zvx_denoise(self._h, p, _ptr(n), len(n), int(Nmax), _ptr(bias), C.byref(prm), p, int(Nmax),
-                                        ZVX_DEVICE_IN | ZVX_DEVICE_OUT | (ZVX_NO_SYNC if no_sync else 0)))
+        self._chk(self._lib.zvx_denoise(self._h, p, _ptr(n), len(n), int(Nmax), _ptr(bias), C.byref(prm), p, int(Nmax), flags))
 
     def resample_device(self, ptr, n, rate_in, rate_out, pcm16=False):
         """zvx_resample of ONE device-resident row of n f32 samples (ZVX_DEVICE_IN) -> host row at rate_out"""

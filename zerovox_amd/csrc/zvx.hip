@@ -2466,12 +2466,13 @@ const double* limit_win(zvx_ctx* c, int W) {
     return c->lim_wins[W] = d;
 }
 
-// The window of zvx_limit_ex: the rows hold samples [in_origin, in_origin + nsamples[b]) of their signals, the outputs [out_begin,
-// out_begin + cnt_b) are emitted.  The whole-row calls are {0, 0, -1, 1}.
-struct LimitWindow { int64_t in_origin = 0, out_begin = 0, out_count = -1; int last = 1; };
+// The window of zvx_limit_ex and zvx_denoise_ex: the rows hold samples [in_origin, in_origin + nsamples[b]) of their signals, the outputs
+// [out_begin, out_begin + cnt_b) are emitted.  The whole-row calls are {0, 0, -1, 1}.
+// (do_resample's window is another contract -- its rows are zero outside the window and it has no support condition -- and stays on its own.)
+struct RowsWindow { int64_t in_origin = 0, out_begin = 0, out_count = -1; int last = 1; };
 // per row the emitted count, after the window's own checks and the support condition of include/zvx.h for the reach R (zvx_limit_ex:
 // 2 W + H; zvx_denoise_ex: n_fft - 1)
-std::vector<int32_t> window_counts(const char* who, const LimitWindow& w, const int32_t* nsamples, int B, int64_t R) {
+std::vector<int32_t> window_counts(const char* who, const RowsWindow& w, const int32_t* nsamples, int B, int64_t R) {
     if (w.in_origin < 0 || w.out_begin < 0) fail(ZVX_E_INVALID, "%s: in_origin %lld / out_begin %lld is negative", who, (long long)w.in_origin, (long long)w.out_begin);
     if (w.out_count < -1) fail(ZVX_E_INVALID, "%s: out_count %lld (-1: to the end of the signal)", who, (long long)w.out_count);
     if (w.last != 0 && w.last != 1) fail(ZVX_E_INVALID, "%s: last is %d (0 or 1)", who, w.last);
@@ -2496,13 +2497,24 @@ std::vector<int32_t> window_counts(const char* who, const LimitWindow& w, const 
     }
     return cnt;
 }
-std::vector<int32_t> limit_window_counts(const char* who, const LimitWindow& w, const int32_t* nsamples, int B, int W, int os) {
-    return window_counts(who, w, nsamples, B, 2 * (int64_t)W + (os > 1 ? LIMIT_ENV_REACH : 0));
+// the emitted range: [off, off + cnt[b]) of row b.  Without a window the whole rows; with one, window_counts for the reach R, then the checks
+// of the output stride and of the in-place form.  `own` holds cnt under a window.
+struct EmittedRange { std::vector<int32_t> own; const int32_t* cnt; long off, cnt_max; double cnt_sum; };
+EmittedRange emitted_range(const char* who, const RowsWindow* win, const int32_t* nsamples, int B, int64_t R, const RowsInfo& r, const float* in,
+                           const void* out, int64_t out_stride) {
+    if (!win) return {{}, nsamples, 0, r.n_max, r.n_sum};
+    EmittedRange e{window_counts(who, *win, nsamples, B, R), nullptr, (long)(win->out_begin - win->in_origin), 0, 0};
+    e.cnt = e.own.data();                                    // (the vector's storage moves with the struct)
+    for (int b = 0; b < B; b++) { e.cnt_max = std::max<long>(e.cnt_max, e.cnt[b]); e.cnt_sum += e.cnt[b]; }
+    if (e.cnt_max == 0) e.off = 0;
+    if (out_stride < e.cnt_max) fail(ZVX_E_INVALID, "%s: out_stride %lld is smaller than the longest output row %ld", who, (long long)out_stride, e.cnt_max);
+    if (out == (const void*)in && e.off != 0) fail(ZVX_E_INVALID, "%s: in place needs out_begin == in_origin", who);
+    return e;
 }
 
 // zvx_true_peak (p == nullptr: the envelope's maximum only, results in tpeak), zvx_limit and zvx_limit_ex (win != nullptr)
 void do_limit(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_limit_params* p,
-              int oversample, void* out, int64_t out_stride, float* peak_in, float* min_gain, int flags, const LimitWindow* win = nullptr) {
+              int oversample, void* out, int64_t out_stride, float* peak_in, float* min_gain, int flags, const RowsWindow* win = nullptr) {
     const bool lim = p != nullptr;
     if (!lim && !peak_in) fail(ZVX_E_INVALID, "%s: tpeak is NULL", who);
     const RowsInfo r = rows_check(who, in, nsamples, B, Nmax, 65535);
@@ -2521,18 +2533,9 @@ void do_limit(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamp
         if (w > (double)LIMIT_MAX_W) fail(ZVX_E_UNSUPPORTED, "%s: window of %.0f samples (at most %d)", who, w, LIMIT_MAX_W);
         W = (int)w;
     }
-    // the emitted range: [off, off + cnt[b]) of row b; the whole row unless a window is given
-    std::vector<int32_t> cnt_win;
-    const int32_t* cnt = nsamples;
-    long off = 0, cnt_max = r.n_max; double cnt_sum = r.n_sum;
-    if (win) {
-        cnt_win = limit_window_counts(who, *win, nsamples, B, W, os);
-        cnt = cnt_win.data(); off = (long)(win->out_begin - win->in_origin); cnt_max = 0; cnt_sum = 0;
-        for (int b = 0; b < B; b++) { cnt_max = std::max<long>(cnt_max, cnt[b]); cnt_sum += cnt[b]; }
-        if (cnt_max == 0) off = 0;
-        if (out_stride < cnt_max) fail(ZVX_E_INVALID, "%s: out_stride %lld is smaller than the longest output row %ld", who, (long long)out_stride, cnt_max);
-        if (out == (const void*)in && off != 0) fail(ZVX_E_INVALID, "%s: in place needs out_begin == in_origin", who);
-    }
+    const EmittedRange er = emitted_range(who, win, nsamples, B, 2 * (int64_t)W + (os > 1 ? LIMIT_ENV_REACH : 0), r, in, out, out_stride);
+    const int32_t* cnt = er.cnt;
+    const long off = er.off, cnt_max = er.cnt_max; const double cnt_sum = er.cnt_sum;
     RowsReturn ret(c, B, (size_t)B * 8, peak_in || min_gain, lim, cnt_max, flags);      // words: peak [B], then min gain [B]
     LimitArgs a{};
     a.os = os;
@@ -2624,7 +2627,7 @@ double dn_fft_flops(const DnGeom& g, double frames, int transforms) { return tra
 
 // zvx_denoise (win == nullptr: the whole rows) and zvx_denoise_ex
 void do_denoise(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias, const zvx_denoise_params* p,
-                void* out, int64_t out_stride, int flags, const LimitWindow* win = nullptr) {
+                void* out, int64_t out_stride, int flags, const RowsWindow* win = nullptr) {
     const RowsInfo r = rows_check(who, in, nsamples, B, Nmax, 65535);
     flags_check(who, flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16);
     out_rows_check(who, in, out, out_stride, Nmax, flags);
@@ -2633,20 +2636,11 @@ void do_denoise(zvx_ctx* c, const char* who, const float* in, const int32_t* nsa
     if (!(p->floor >= 0.f && p->floor <= 1.f)) fail(ZVX_E_INVALID, "%s: floor must lie in [0, 1]", who);
     const DnGeom g = dn_geom(c, who);
     for (int k = 0; k < g.nf; k++) if (!(bias[k] >= 0.f)) fail(ZVX_E_INVALID, "%s: bias[%d] is negative or NaN", who, k);
-    // the emitted range: [off, off + cnt[b]) of row b; the whole row unless a window is given
-    const LimitWindow whole;
-    const LimitWindow& w = win ? *win : whole;
-    std::vector<int32_t> cnt_win;
-    const int32_t* cnt = nsamples;
-    long off = 0, cnt_max = r.n_max; double cnt_sum = r.n_sum;
-    if (win) {
-        cnt_win = window_counts(who, w, nsamples, B, g.n_fft - 1);
-        cnt = cnt_win.data(); off = (long)(w.out_begin - w.in_origin); cnt_max = 0; cnt_sum = 0;
-        for (int b = 0; b < B; b++) { cnt_max = std::max<long>(cnt_max, cnt[b]); cnt_sum += cnt[b]; }
-        if (cnt_max == 0) off = 0;
-        if (out_stride < cnt_max) fail(ZVX_E_INVALID, "%s: out_stride %lld is smaller than the longest output row %ld", who, (long long)out_stride, cnt_max);
-        if (out == (const void*)in && off != 0) fail(ZVX_E_INVALID, "%s: in place needs out_begin == in_origin", who);
-    }
+    const RowsWindow whole;
+    const RowsWindow& w = win ? *win : whole;
+    const EmittedRange er = emitted_range(who, win, nsamples, B, g.n_fft - 1, r, in, out, out_stride);
+    const int32_t* cnt = er.cnt;
+    const long off = er.off, cnt_max = er.cnt_max; const double cnt_sum = er.cnt_sum;
     // zvx_melspec's length conditions hold for the whole SIGNAL: known where it ends with the window
     if (w.last)
         for (int b = 0; b < B; b++)
@@ -3130,7 +3124,7 @@ zvx_status zvx_limit_ex(zvx_ctx* c, const float* in, const int32_t* nsamples, in
                         int64_t in_origin, int64_t out_begin, int64_t out_count, int last) {
     return guarded(c, [&] {
         if (!params) fail(ZVX_E_INVALID, "zvx_limit_ex: params is NULL");
-        const LimitWindow win{in_origin, out_begin, out_count, last};
+        const RowsWindow win{in_origin, out_begin, out_count, last};
         do_limit(c, "zvx_limit_ex", in, nsamples, B, Nmax, rate, params, 0, out, out_stride, peak_in, min_gain, flags, &win);
     });
 }
@@ -3148,7 +3142,7 @@ zvx_status zvx_denoise_ex(zvx_ctx* c, const float* in, const int32_t* nsamples, 
                           const zvx_denoise_params* params, void* out, int64_t out_stride, int flags,
                           int64_t in_origin, int64_t out_begin, int64_t out_count, int last) {
     return guarded(c, [&] {
-        const LimitWindow win{in_origin, out_begin, out_count, last};
+        const RowsWindow win{in_origin, out_begin, out_count, last};
         do_denoise(c, "zvx_denoise_ex", in, nsamples, B, Nmax, bias, params, out, out_stride, flags, &win);
     });
 }

@@ -13,6 +13,10 @@ import numpy as np
 import yaml
 
 from . import _lib, config as zcfg, pack, weights as zw
+from .denoiser import DenoisePlanner
+from .limiter import LimitPlanner, window_samples
+from .resample import stream_resample
+from .stream import stream_windows
 
 DEFAULT_MELDEC_MODEL_NAME = "zerovox-hifigan-vctk-v2-en-1"      # model.py:84
 
@@ -239,16 +243,13 @@ class ZeroVox:
             denoise = dict(denoise, bias=self.denoise_bias)          # (first use runs the vocoder: before this stream's first chunk)
         chunks = self._vocode_stream_native(mel, chunk_frames, halo, chunks_per_call, convert or limiter is not None or denoise is not None)
         if denoise is not None:
-            from .denoiser import DenoisePlanner, stream_denoise
-            chunks = stream_denoise(chunks, DenoisePlanner(ctx.get_int("fft_size")), lambda x, o, b, n, last: ctx.denoise_window(
+            chunks = stream_windows(chunks, DenoisePlanner(ctx.get_int("fft_size")), lambda x, o, b, n, last: ctx.denoise_window(
                 [x], in_origin=o, out_begin=b, out_count=n, last=last, **denoise)[0].copy())
         if limiter is not None:
-            from .limiter import LimitPlanner, stream_limit, window_samples
             plan = LimitPlanner(window_samples(native, limiter["window_ms"]), limiter["oversample"])
-            chunks = stream_limit(chunks, plan, lambda x, o, b, n, last: ctx.limit_window(
+            chunks = stream_windows(chunks, plan, lambda x, o, b, n, last: ctx.limit_window(
                 [x], in_origin=o, out_begin=b, out_count=n, last=last, rate=native, **limiter)[0][0].copy())
         if convert:
-            from .resample import stream_resample
             chunks = stream_resample(chunks, native, rate, lambda x, o, b, n: ctx.resample_window([x], native, rate, o, b, n)[0][0].copy())
         yield from chunks
 

@@ -7,13 +7,13 @@ of an output, so output ``n`` needs the input samples ``k`` with ``|n M - k L| <
 * the next output ``n_next`` needs no sample before ``ceil((n_next M - half) / L)``: the history before it can go.
 
 A stream converted in these windows is bit-identical to one whole-signal call, because the sum of an output runs over the same
-samples in the same order wherever the window was cut.
+samples in the same order wherever the window was cut.  The loop that drives the planner is zerovox_amd.stream's.
 """
 from __future__ import annotations
 
 from math import gcd
 
-import numpy as np
+from .stream import stream_windows
 
 ZEROS = 10                                    # half = ZEROS * max(L, M), as the library designs its filter
 
@@ -58,20 +58,6 @@ class StreamPlanner:
 def stream_resample(chunks, rate_in, rate_out, window_fn):
     """chunks: an iterable of 1-D float32 pieces of one signal at rate_in -> yields its pieces at rate_out, which concatenate to the
     whole-signal conversion bit for bit.  ``window_fn(samples, in_origin, out_begin, out_count)`` is the resampler over a window
-    (Context.resample_window on one row); a piece is yielded as soon as its samples are final."""
-    plan = StreamPlanner(rate_in, rate_out)
-    hist = np.zeros(0, np.float32)
-    it = iter(chunks)
-    try:
-        cur = next(it)
-    except StopIteration:
-        return
-    while cur is not None:
-        nxt = next(it, None)
-        cur = np.asarray(cur, np.float32)
-        hist = np.concatenate([hist, cur])
-        in_origin, out_begin, out_count, keep_from = plan.push(len(cur), last=nxt is None)
-        if out_count > 0:
-            yield window_fn(hist, in_origin, out_begin, out_count)
-        hist = hist[keep_from - in_origin:]
-        cur = nxt
+    (Context.resample_window on one row); a piece is yielded as soon as its samples are final, and the outputs that wait for the
+    signal's end come in a closing window when ``chunks`` ends (zerovox_amd.stream)."""
+    return stream_windows(chunks, StreamPlanner(rate_in, rate_out), lambda x, o, b, n, last: window_fn(x, o, b, n))
