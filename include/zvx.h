@@ -559,6 +559,70 @@ zvx_status zvx_denoise_ex(zvx_ctx* ctx, const float* in, const int32_t* nsamples
                           const zvx_denoise_params* params, void* out, int64_t out_stride, int flags,
                           int64_t in_origin, int64_t out_begin, int64_t out_count, int last);
 
+/* Stream sessions: chunked vocoding of ONE utterance with the planning inside the library.  A session owns the utterance's mel on the
+ * device, vocodes it group by group and runs the new samples device to device through the optional denoiser, limiter and rate conversion;
+ * each zvx_stream_next hands out one finished piece with one wait.  It is what ZeroVox.vocode_stream does with three Python planners and
+ * up to four host round trips per piece (zerovox_amd/stream.py, denoiser.py, limiter.py, resample.py), moved behind this header; the
+ * planners are restated in zerovox_amd/csrc/stream_plan.h (host integer arithmetic, int64 positions).
+ * Contract: the concatenation of a session's pieces is bit for bit the concatenation of ZeroVox.vocode_stream(mel, chunk_frames, halo,
+ *   chunks_per_call, limiter=, denoise=) on the same context under the same "out_rate", and that equals resample(limit(denoise(plain))),
+ *   plain being the concatenation of the stream without post steps and every absent step dropped from the chain.  It follows from three
+ *   things: the rows of each vocoder call are the same, in the same batch; the window contract of zvx_denoise_ex / zvx_limit_ex /
+ *   zvx_resample_ex holds wherever a stream is cut; the stage order is the same.  Where the pieces are CUT may differ from the Python
+ *   stream (a session flags its last group `last` instead of closing with an empty push); their concatenation does not.
+ * zvx_stream_open: mel != NULL: [frames][n_mels] f32 on the host, or on the device with ZVX_DEVICE_IN, copied into a buffer of the session
+ *   (a host mel may be reused when the call returns).  mel == NULL: utterance 0 of the mel the context holds after zvx_decode, taken with a
+ *   device-to-device copy; frames must be 0; no mel in the context: ZVX_E_STATE; a context batch other than 1: ZVX_E_UNSUPPORTED.
+ *   Captured at open: the context's "out_rate", the model's rate and hop, the denoiser's and limiter's parameters (a copy of the bias
+ *   included); every table a stage needs on first use (the limiter's window, its oversampling bank, the FFT tables, the resampler's bank)
+ *   is uploaded here, so no zvx_stream_next waits for an upload, and a later zvx_set_int("out_rate") does not touch an open session.
+ *   Validation, before anything is allocated (ZVX_E_INVALID, the context stays usable): a NULL ctx / params / out, frames < 2, frames != 0
+ *   with a NULL mel, chunk_frames < 1, chunks_per_call outside 1 .. 64, halo < 0, denoise without denoise_bias or the reverse, every check
+ *   zvx_denoise and zvx_limit make on their own parameters and bias, frames * hop samples that fail zvx_melspec's length conditions while a
+ *   denoiser is asked for, unknown flags.  ZVX_E_UNSUPPORTED: ZVX_PCM16, what the stages themselves call unsupported (W > 4096, n_fft),
+ *   a group of more than 2^28 samples.
+ * zvx_stream_next: vocodes exactly one group -- the next chunks_per_call chunks, fewer at the end -- and pushes its samples through the
+ *   stages.  Chunk s is vocoded on mel frames [max(0, s - halo), min(frames, s + chunk_frames + halo)), a row of its own in one batch of
+ *   the group's rows at the native rate (the rows ZeroVox._vocode_stream_native builds), and only its chunk_frames * hop interior samples
+ *   are kept.  The group's interiors, as ONE run of new samples, go through denoiser, then limiter, then rate conversion, each under the
+ *   two rules of a stream of its reach (a non-last push emits what is final, the history before next_out - R is dropped); the call that
+ *   vocodes the last group pushes with `last`: everything left comes out in it and *done becomes 1.  *n_out samples, f32 at the session's
+ *   output rate, are written to out; *n_out may be 0 while a stage is still filling its reach (out may then be NULL).  After *done:
+ *   ZVX_E_STATE.  *n_out is known before anything is queued: capacity < *n_out is ZVX_E_BUFFER with NOTHING consumed -- *n_out is still
+ *   filled, the message names both numbers, and the same call with a larger buffer succeeds and yields the same bits.
+ *   Flags: ZVX_DEVICE_OUT (out on the device), ZVX_NO_SYNC (device out only: the call only queues).  Without ZVX_DEVICE_OUT the piece
+ *   reaches the host through pinned memory of the session under the call's ONE wait.  Everything is queued on the context's main stream;
+ *   a session creates no stream of its own.  A zvx_stream_next voids the context's intermediates as zvx_vocode_mel does.  Between two
+ *   calls of a session the context may serve any other call, calls of other open sessions included: the session's bits do not depend on it.
+ * Device state: per stage two buffers [history | new], sized at open from chunks_per_call * chunk_frames * hop plus the history the stage
+ *   retains (2 R; 2 half / L + 2 for the conversion) plus the reaches in front of it; a stage writes straight behind the next stage's
+ *   history through the internal form of its _ex call (device in, device out, no sync); dropping history copies the retained tail into
+ *   the stage's other buffer, never over itself.  zvx_stream_next allocates nothing of the session's (the context's own work buffers
+ *   grow on first use, as in every call).  New launches: the gather of the group's mel rows with halo, zero-padded to the longest row,
+ *   and the gather of the rows' interiors into one run -- stage tag "voc.stream" in zvx_tag_stats, counted only when a session runs
+ *   (bytes read plus bytes written); the stages' launches count as their _ex calls count them.
+ * zvx_stream_info fills, in order and as far as n_info reaches: the stream's total output samples, the output samples emitted so far,
+ *   the output rate, the native samples the output runs behind the vocoder (the sum of the stages' reaches: n_fft - 1, 2 W + H,
+ *   ceil(half / L) + 1; 0 without any), and max_piece = ceil((chunks_per_call * chunk_frames * hop + delay) * L / M) + 1, an upper bound
+ *   on any single *n_out, so that a caller sizes one buffer.
+ * zvx_stream_close frees everything (NULL: ZVX_E_INVALID); zvx_destroy closes the context's open sessions first.  Errors of session calls
+ *   are reported through zvx_last_error of the session's context.
+ * Not here: ZVX_PCM16 pieces, several utterances per session, a streamed loudness gain (it is not known before the last chunk). */
+typedef struct zvx_stream zvx_stream;
+typedef struct zvx_stream_params {
+    int32_t chunk_frames;              /* mel frames per chunk, >= 1 */
+    int32_t chunks_per_call;           /* chunks vocoded per zvx_stream_next as independent batch rows, 1 .. 64 */
+    int32_t halo;                      /* mel frames vocoded on either side of a chunk and dropped, >= 0 (ZeroVox.STREAM_HALO is 16) */
+    const zvx_denoise_params* denoise; /* NULL: no denoiser */
+    const float* denoise_bias;         /* host [n_fft / 2 + 1], copied at open; required iff denoise != NULL */
+    const zvx_limit_params* limit;     /* NULL: no limiter */
+} zvx_stream_params;
+
+zvx_status zvx_stream_open(zvx_ctx* ctx, const float* mel, int frames, const zvx_stream_params* params, int flags, zvx_stream** out);
+zvx_status zvx_stream_next(zvx_stream* s, void* out, int64_t capacity, int64_t* n_out, int32_t* done, int flags);
+zvx_status zvx_stream_info(const zvx_stream* s, int64_t* info, int n_info);
+zvx_status zvx_stream_close(zvx_stream* s);
+
 /* Debug/parity taps: copy an intermediate of the last call to host fp32.
  * what: "encoder_out" [B][Tmax][hidden] (after the style add), "features" [B][Lmax][hidden],
  *       "mel" [B][Lmax][n_mels], "pitch_idx"/"energy_idx"/"duration" [B][Tmax] (as float). */
@@ -611,7 +675,7 @@ typedef struct {
 } zvx_kernel_stat;
 int        zvx_kernel_stats(zvx_ctx* ctx, zvx_kernel_stat* out, int max_out);
 /* The same counters grouped by pipeline stage ("encoder", "variance", "lenreg", "decoder", "decoder.norm", "voc.pre",
- * "voc.up1".."voc.res4", "voc.post", "voc.resample", "post.join", "post.loudness", "post.limit", "post.denoise", "spkemb"; name = stage): every launch of the stage, including the HBM-bound helper
+ * "voc.up1".."voc.res4", "voc.post", "voc.resample", "voc.stream", "post.join", "post.loudness", "post.limit", "post.denoise", "spkemb"; name = stage): every launch of the stage, including the HBM-bound helper
  * kernels, while "profile" == 2 and "profile_only" == -1.  Feeds the per-stage roofline fractions of bench.py. */
 int        zvx_tag_stats(zvx_ctx* ctx, zvx_kernel_stat* out, int max_out);
 zvx_status zvx_reset_stats(zvx_ctx* ctx);

@@ -7,7 +7,10 @@
    python tools/stream_latency.py --denoise S [--peak-db DB] [out.json]   -> the same stream WITH and WITHOUT the windowed denoiser
    (zvx_denoise_ex at strength S with the model's own bias), in this one process: first piece, all pieces, the median piece gap, the
    samples the denoised stream runs behind (denoiser.reach) and whether the pieces equal zvx_denoise of the whole stream bit for bit;
-   with --peak-db as well also the combined chain, limit(denoise(stream))."""
+   with --peak-db as well also the combined chain, limit(denoise(stream)).
+   python tools/stream_latency.py --resident [--denoise S] [--peak-db DB] [out.json]   -> next to every chain above, in the same process,
+   the figures of the same stream run by a stream session of the library (zvx_stream_open; vocode_stream(resident=True)): first piece,
+   all pieces, the median piece gap, and whether its concatenation equals the host-planned one bit for bit."""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -19,6 +22,7 @@ ap.add_argument("out", nargs="?", help="write the result as JSON here")
 ap.add_argument("--peak-db", type=float, default=None, metavar="DB", help="also time the stream limited at this ceiling (dBFS)")
 ap.add_argument("--limiter-ms", type=float, default=5.0, metavar="MS")
 ap.add_argument("--denoise", type=float, default=None, metavar="S", help="also time the stream denoised at this strength")
+ap.add_argument("--resident", action="store_true", help="also time every chain run by a stream session of the library")
 args = ap.parse_args()
 
 cfg = zcfg.medium_modelcfg("styletts"); sd = zw.tts_state_dict(cfg, 0)
@@ -50,6 +54,16 @@ def piece_gap(make_stream, n=5):
     return float(np.median(gaps)) * 1e3 if gaps else 0.0
 
 
+def resident(cf, host_planned, **kw):
+    """the figures of one chain run by a stream session, and whether it hands out the host-planned stream's bits"""
+    def make():
+        return model.vocode_stream(mel, chunk_frames=cf, resident=True, **kw)
+    got = np.concatenate(list(make()))
+    return {"first_piece_ms": round(best(lambda: next(iter(make()))), 3), "all_pieces_ms": round(best(lambda: list(make()), n=5), 3),
+            "piece_gap_ms": round(piece_gap(make), 3),
+            "bit_equal_to_host_planned": bool(got.shape == host_planned.shape and np.array_equal(got.view(np.uint32), host_planned.view(np.uint32)))}
+
+
 res = {"workload": f"one {L}-frame mel ({L * 256 / 22050:.2f} s of audio), HiFi-GAN V1 bf16, batch 1, halo {STREAM_HALO} frames per side",
        "whole_utterance_ms": best(lambda: ctx.vocode_mel(mel[None], np.array([L], np.int32))), "chunks": []}
 for cf in (16, 32, 64, 128, 256):
@@ -58,6 +72,9 @@ for cf in (16, 32, 64, 128, 256):
     total = best(lambda: list(model.vocode_stream(mel, chunk_frames=cf)), n=5)
     res["chunks"].append({"chunk_frames": cf, "chunk_audio_ms": round(cf * 256 / 22.05, 1), "first_chunk_ms": round(first, 3), "all_chunks_ms": round(total, 3),
                           "bit_equal_to_whole": bool(np.array_equal(got, whole)), "max_abs_diff": float(np.abs(got - whole).max())})
+    if args.resident:
+        res["chunks"][-1]["piece_gap_ms"] = round(piece_gap(lambda: model.vocode_stream(mel, chunk_frames=cf)), 3)
+        res["chunks"][-1]["resident"] = resident(cf, got)
     if args.peak_db is not None:
         from zerovox_amd.limiter import reach, window_samples
         from zerovox_amd.longform import limit_keywords
@@ -74,6 +91,8 @@ for cf in (16, 32, 64, 128, 256):
                         "piece_gap_ms": round(piece_gap(lambda: model.vocode_stream(mel, chunk_frames=cf, limiter=lim)), 3),
                         "bit_equal_to_whole_limit": bool(np.array_equal(limited, want)),
                         "samples_changed": int(np.count_nonzero(limited != got))}})
+        if args.resident:
+            res["chunks"][-1]["limited"]["resident"] = resident(cf, limited, limiter=lim)
     if args.denoise is not None:
         from zerovox_amd.denoiser import reach as denoise_reach
         den = dict(strength=float(args.denoise), floor=0.0)
@@ -90,6 +109,8 @@ for cf in (16, 32, 64, 128, 256):
             "piece_gap_ms": round(piece_gap(lambda: model.vocode_stream(mel, chunk_frames=cf, denoise=den)), 3),
             "bit_equal_to_whole_denoise": bool(np.array_equal(denoised.view(np.uint32), want.view(np.uint32))),
             "samples_changed": int(np.count_nonzero(denoised != got))}
+        if args.resident:
+            res["chunks"][-1]["denoised"]["resident"] = resident(cf, denoised, denoise=den)
         if args.peak_db is not None:
             both = np.concatenate(list(model.vocode_stream(mel, chunk_frames=cf, denoise=den, limiter=lim)))
             want_both = ctx.limit([want], rate=native, **lim)[0][0]
@@ -99,6 +120,8 @@ for cf in (16, 32, 64, 128, 256):
                 "all_pieces_ms": round(best(lambda: list(model.vocode_stream(mel, chunk_frames=cf, denoise=den, limiter=lim)), n=5), 3),
                 "piece_gap_ms": round(piece_gap(lambda: model.vocode_stream(mel, chunk_frames=cf, denoise=den, limiter=lim)), 3),
                 "bit_equal_to_whole_limit_of_denoise": bool(np.array_equal(both.view(np.uint32), want_both.view(np.uint32)))}
+            if args.resident:
+                res["chunks"][-1]["denoised_limited"]["resident"] = resident(cf, both, denoise=den, limiter=lim)
     print(res["chunks"][-1], flush=True)
 print(json.dumps(res))
 if args.out:

@@ -26,7 +26,7 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_dev_alloc", "zvx_dev_free", "zvx_dev_from_host", "zvx_dev_to_host", "zvx_spkemb_ex", "zvx_wait_host",
            "zvx_encode_ex", "zvx_synthesize_ex", "zvx_resample", "zvx_resample_ex", "zvx_trim_bounds", "zvx_join",
            "zvx_loudness", "zvx_normalize", "zvx_true_peak", "zvx_limit", "zvx_spkemb_wav", "zvx_limit_ex", "zvx_denoise_bias", "zvx_denoise",
-           "zvx_denoise_ex")
+           "zvx_denoise_ex", "zvx_stream_open", "zvx_stream_next", "zvx_stream_info", "zvx_stream_close")
 ZVX_COMM_ID_BYTES = 128
 ZVX_LOUD_PER_ROW, ZVX_LOUD_COMMON = 0, 1
 LIMIT_TILE = 1024                                    # samples per workgroup of both limiter kernels (csrc/zvx_kernels.h, LIMIT_TILE)
@@ -71,6 +71,12 @@ class LimitParams(C.Structure):
 class DenoiseParams(C.Structure):
     """zvx_denoise_params (include/zvx.h)"""
     _fields_ = [("strength", C.c_float), ("floor", C.c_float)]
+
+
+class StreamParams(C.Structure):
+    """zvx_stream_params (include/zvx.h)"""
+    _fields_ = [("chunk_frames", C.c_int32), ("chunks_per_call", C.c_int32), ("halo", C.c_int32), ("denoise", C.POINTER(DenoiseParams)),
+                ("denoise_bias", C.c_void_p), ("limit", C.POINTER(LimitParams))]
 
 
 class KernelStat(C.Structure):
@@ -143,6 +149,10 @@ def load():
     lib.zvx_denoise_bias.argtypes = [vp, vp]
     lib.zvx_denoise.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(DenoiseParams), vp, C.c_int64, C.c_int]
     lib.zvx_denoise_ex.argtypes = lib.zvx_denoise.argtypes + [C.c_int64, C.c_int64, C.c_int64, C.c_int]
+    lib.zvx_stream_open.argtypes = [vp, vp, C.c_int, C.POINTER(StreamParams), C.c_int, C.POINTER(vp)]
+    lib.zvx_stream_next.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int]
+    lib.zvx_stream_info.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
+    lib.zvx_stream_close.argtypes = [vp]
     _lib = lib
     return lib
 
@@ -160,6 +170,63 @@ def _i32(a, shape=None):
 
 def _f32(a):
     return np.ascontiguousarray(a, dtype=np.float32)
+
+
+class Stream:
+    """One stream session (wraps zvx_stream*; Context.stream_open makes it).  Iterating yields the float32 pieces, skipping empty ones;
+    the session closes itself when exhausted or collected.  It belongs to its context and must not outlive it."""
+
+    def __init__(self, ctx, handle, keep):
+        self._ctx, self._h, self._keep, self.done = ctx, handle, keep, False
+
+    def info(self):
+        """-> dict(total, emitted, rate, delay, max_piece): zvx_stream_info's five values"""
+        v = (C.c_int64 * 5)()
+        self._ctx._chk(self._ctx._lib.zvx_stream_info(self._h, v, 5))
+        return dict(zip(("total", "emitted", "rate", "delay", "max_piece"), (int(x) for x in v)))
+
+    def next_piece(self, capacity=None):
+        """one zvx_stream_next into host memory -> the piece (np.float32, possibly empty); self.done tells whether it was the last.
+        capacity: samples of the buffer handed in (None: max_piece); too small raises ZvxError(ZVX_E_BUFFER) with nothing consumed,
+        its ``n_out`` attribute carrying the size the piece needs."""
+        cap = self.info()["max_piece"] if capacity is None else int(capacity)
+        out = np.empty(max(cap, 1), np.float32)
+        n, done = self._next(_ptr(out), cap, 0)
+        return out[:n]
+
+    def next_device(self, ptr, capacity, no_sync=False):
+        """one zvx_stream_next into device memory at ``ptr`` (ZVX_DEVICE_OUT; with no_sync the call only queues) -> samples written"""
+        return self._next(C.c_void_p(int(ptr)), int(capacity), ZVX_DEVICE_OUT | (ZVX_NO_SYNC if no_sync else 0))[0]
+
+    def _next(self, out, capacity, flags):
+        n, done = C.c_int64(-1), C.c_int32(0)
+        rc = self._ctx._lib.zvx_stream_next(self._h, out, capacity, C.byref(n), C.byref(done), flags)
+        if rc != ZVX_OK:
+            e = ZvxError(rc, self._ctx._lib.zvx_last_error(self._ctx._h).decode())
+            e.n_out = int(n.value)
+            raise e
+        self.done = bool(done.value)
+        return int(n.value), self.done
+
+    def __iter__(self):
+        try:
+            while self._h and not self.done:
+                piece = self.next_piece()
+                if len(piece):
+                    yield piece
+        finally:
+            self.close()
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self._ctx, "_h", None):
+            self._ctx._lib.zvx_stream_close(self._h)
+        self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
 
 
 class Context:
@@ -483,6 +550,37 @@ class Context:
         prm, flags = self._denoise_args(strength, floor, device=True, no_sync=no_sync)
         p = C.c_void_p(int(ptr))
         self._chk(self._lib.zvx_denoise(self._h, p, _ptr(n), len(n), int(Nmax), _ptr(bias), C.byref(prm), p, int(Nmax), flags))
+
+    def stream_open(self, mel=None, frames=0, *, chunk_frames, chunks_per_call=1, halo=16, denoise=None, bias=None, limit=None, flags=0):
+        """zvx_stream_open -> Stream.  mel: [frames, n_mels] float32 on the host; an int, a device pointer to ``frames`` rows
+        (ZVX_DEVICE_IN); or None: the mel the context holds after decode (frames 0).  denoise: None or dict(strength, floor) with ``bias``
+        (denoise_bias()); limit: None or dict(ceiling, window_ms, oversample).  The context's out_rate at this moment is the stream's."""
+        keep = []
+        if mel is None:
+            mptr = None
+        elif isinstance(mel, (int, np.integer)):
+            mptr, flags = C.c_void_p(int(mel)), flags | ZVX_DEVICE_IN
+        else:
+            mel = _f32(mel)
+            if mel.ndim != 2 or mel.shape[1] != self.n_mels:
+                raise ValueError(f"stream_open: mel must be [frames, {self.n_mels}], not {mel.shape}")
+            frames, mptr = mel.shape[0], _ptr(mel)
+        prm = StreamParams(int(chunk_frames), int(chunks_per_call), int(halo), None, None, None)
+        if denoise is not None:
+            dn = DenoiseParams(float(denoise["strength"]), float(denoise.get("floor", 0.0)))
+            keep.append(dn)
+            prm.denoise = C.pointer(dn)
+        if bias is not None:
+            b = self._denoise_bias_arg(bias)
+            keep.append(b)
+            prm.denoise_bias = b.ctypes.data
+        if limit is not None:
+            lm = LimitParams(float(limit["ceiling"]), float(limit.get("window_ms", 5.0)), int(limit.get("oversample", 4)))
+            keep.append(lm)
+            prm.limit = C.pointer(lm)
+        h = C.c_void_p()
+        self._chk(self._lib.zvx_stream_open(self._h, mptr, int(frames), C.byref(prm), int(flags), C.byref(h)))
+        return Stream(self, h, keep)
 
     def resample_device(self, ptr, n, rate_in, rate_out, pcm16=False):
         """zvx_resample of ONE device-resident row of n f32 samples (ZVX_DEVICE_IN) -> host row at rate_out"""

@@ -57,7 +57,7 @@ def resources():
 
 def build(force: bool = False, verbose: bool = True) -> str:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(CSRC, "zvx_kernels.h"), os.path.join(CSRC, "mfma_util.h"), os.path.join(os.path.dirname(HERE), "include", "zvx.h")]
+    headers = [os.path.join(CSRC, "zvx_kernels.h"), os.path.join(CSRC, "mfma_util.h"), os.path.join(CSRC, "stream_plan.h"), os.path.join(os.path.dirname(HERE), "include", "zvx.h")]
     def compile_one(unit):
         stem, src, defs = unit
         s = os.path.join(CSRC, src)

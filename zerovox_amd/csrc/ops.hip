@@ -1644,6 +1644,63 @@ void launch_join_copy(const JoinCopyArgs& a, long upper, hipStream_t s) {
     hipLaunchKernelGGL(k_join_copy, dim3((unsigned)tiles), dim3(256), 0, s, a);
 }
 
+// ---------------------------------------------------------------- the gathers of a stream session (zvx_kernels.h, include/zvx.h: zvx_stream_next)
+// One thread per group of 4 floats, groups aligned as addresses of the destination (as k_join_copy aligns its): a whole group is one
+// vector store, and one vector load where the source address allows; a group at an edge is built element by element.
+__global__ __launch_bounds__(256) void k_stream_rows(const StreamRowsArgs a) {
+    const int b = blockIdx.y;
+    const long row = (long)a.Pmax * a.nm, valid = (long)a.P[b] * a.nm;
+    const float* src = a.mel + (long)a.lo[b] * a.nm;
+    float* dst = a.out + (long)b * row;
+    const int mis = (int)(((size_t)dst >> 2) & 3);
+    const long e = ((long)blockIdx.x * 256 + threadIdx.x) * 4 - mis;
+    if (e >= row) return;
+    if (e >= 0 && e + 4 <= row) {
+        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (e + 4 <= valid) {
+            if (((size_t)(src + e) & 15) == 0) v = *(const float4*)(src + e);
+            else v = make_float4(src[e], src[e + 1], src[e + 2], src[e + 3]);
+        } else if (e < valid) {
+            v.x = src[e];
+            if (e + 1 < valid) v.y = src[e + 1];
+            if (e + 2 < valid) v.z = src[e + 2];
+        }
+        *(float4*)(dst + e) = v;
+    } else {
+        for (int k = 0; k < 4; k++)
+            if (e + k >= 0 && e + k < row) dst[e + k] = e + k < valid ? src[e + k] : 0.f;
+    }
+}
+void launch_stream_rows(const StreamRowsArgs& a, hipStream_t s) {
+    if (a.B <= 0 || a.Pmax <= 0) return;
+    const long groups = ((long)a.Pmax * a.nm + 3 + 3) / 4;             // (+ 3: the address alignment shifts the groups by up to 3 elements)
+    hipLaunchKernelGGL(k_stream_rows, dim3((unsigned)((groups + 255) / 256), a.B), dim3(256), 0, s, a);
+}
+
+__global__ __launch_bounds__(256) void k_stream_interiors(const StreamInteriorArgs a) {
+    const int b = blockIdx.y;
+    const long cnt = a.cnt[b];
+    const float* src = a.wav + (long)b * a.w_bs + a.off[b];
+    float* dst = a.out + a.pos[b];
+    const int mis = (int)(((size_t)dst >> 2) & 3);
+    const long o = ((long)blockIdx.x * 256 + threadIdx.x) * 4 - mis;
+    if (o >= cnt) return;
+    if (o >= 0 && o + 4 <= cnt) {
+        float4 v;
+        if (((size_t)(src + o) & 15) == 0) v = *(const float4*)(src + o);
+        else v = make_float4(src[o], src[o + 1], src[o + 2], src[o + 3]);
+        *(float4*)(dst + o) = v;
+    } else {
+        for (int k = 0; k < 4; k++)
+            if (o + k >= 0 && o + k < cnt) dst[o + k] = src[o + k];
+    }
+}
+void launch_stream_interiors(const StreamInteriorArgs& a, long cnt_max, hipStream_t s) {
+    if (a.B <= 0 || cnt_max <= 0) return;
+    const long groups = (cnt_max + 3 + 3) / 4;
+    hipLaunchKernelGGL(k_stream_interiors, dim3((unsigned)((groups + 255) / 256), a.B), dim3(256), 0, s, a);
+}
+
 // ---------------------------------------------------------------- integrated loudness and gain (zvx_kernels.h, include/zvx.h: zvx_loudness)
 constexpr int LOUD_T = 32;                   // samples per lane in one staged chunk
 constexpr int LOUD_G = LOUD_T / 4 + 1;       // 16-byte groups that cover LOUD_T samples whatever their alignment

@@ -1,0 +1,71 @@
+// stream_plan.h -- the window planners of a stream session (include/zvx.h: zvx_stream_next), header-only and free of HIP so that they
+// compile with any host C++ compiler (tests/native/stream_plan_main.cpp checks them against the Python planners on the CPU).
+//
+// A literal restatement of zerovox_amd/stream.py (ReachPlanner: the limiter's and the denoiser's windows) and zerovox_amd/resample.py
+// (StreamPlanner: the rate conversion's).  push(n_new, last) takes the count of newly received input samples and returns
+// (in_origin, out_begin, out_count, keep_from): run the step on the retained samples [in_origin, received) for the outputs
+// [out_begin, out_begin + out_count) -- nothing to do when out_count is 0 -- then drop the history before keep_from.
+// Every position is an int64_t: a stream may run past 2^32 samples.
+#ifndef ZVX_STREAM_PLAN_H
+#define ZVX_STREAM_PLAN_H
+
+#include <stdint.h>
+
+namespace zvx_plan {
+
+struct Step { int64_t in_origin, out_begin, out_count, keep_from; };
+
+inline int64_t imax(int64_t a, int64_t b) { return a > b ? a : b; }
+inline int64_t imin(int64_t a, int64_t b) { return a < b ? a : b; }
+// ceil(a / b) for b > 0 and any sign of a (Python's -((-a) // b))
+inline int64_t ceil_div(int64_t a, int64_t b) { return a / b + ((a % b != 0 && a > 0) ? 1 : 0); }
+
+// A step of fixed reach R: output i is final once i + R <= received - 1 (everything on the last push); the next output next_out
+// needs no sample before next_out - R.
+struct ReachPlanner {
+    int64_t R = 0, received = 0, next_out = 0, origin = 0;
+    explicit ReachPlanner(int64_t R_ = 0) : R(R_) {}
+    Step push(int64_t n_new, bool last) {
+        received += n_new;
+        const int64_t end = last ? received : imax(next_out, received - R);
+        const Step s{origin, next_out, end - next_out, imax(origin, imin(end - R, received))};
+        next_out = end;
+        origin = s.keep_from;
+        return s;
+    }
+};
+
+// rate_in -> rate_out in lowest terms, half = 10 max(L, M) as the library designs its filter; equal rates are a copy: (1, 1, 0)
+struct RatePair { int64_t L = 1, M = 1, half = 0; };
+inline RatePair rate_pair(int64_t rate_in, int64_t rate_out) {
+    int64_t a = rate_in, b = rate_out;
+    while (b) { const int64_t t = a % b; a = b; b = t; }
+    RatePair p;
+    p.L = rate_out / a; p.M = rate_in / a;
+    p.half = p.L == p.M ? 0 : 10 * imax(p.L, p.M);
+    return p;
+}
+
+// The rate conversion: output n needs the input samples k with |n M - k L| <= half, so n is final once n M + half <= (received - 1) L
+// (everything, ceil(received L / M) outputs, on the last push); the next output n_next needs no sample before
+// ceil((n_next M - half) / L).
+struct ResamplePlanner {
+    int64_t L = 1, M = 1, half = 0, received = 0, n_next = 0, origin = 0;
+    ResamplePlanner() {}
+    ResamplePlanner(int64_t rate_in, int64_t rate_out) { const RatePair p = rate_pair(rate_in, rate_out); L = p.L; M = p.M; half = p.half; }
+    Step push(int64_t n_new, bool last) {
+        received += n_new;
+        int64_t end;
+        if (last) end = ceil_div(received * L, M);
+        else { const int64_t top = (received - 1) * L - half; end = top >= 0 ? top / M + 1 : 0; }
+        end = imax(end, n_next);
+        const int64_t keep = imax(origin, ceil_div(end * M - half, L));
+        const Step s{origin, n_next, end - n_next, imin(keep, received)};
+        n_next = end;
+        origin = s.keep_from;
+        return s;
+    }
+};
+
+}  // namespace zvx_plan
+#endif /* ZVX_STREAM_PLAN_H */

@@ -5,6 +5,7 @@
 // Reference call structure being replaced: ZeroVox.inference_ex (model.py:308-347).
 #include "../../include/zvx.h"
 #include "zvx_kernels.h"
+#include "stream_plan.h"
 
 #include <dlfcn.h>
 #include <math.h>
@@ -183,6 +184,7 @@ struct zvx_ctx {
     std::map<std::string, zvx_kernel_stat> tagstats;
     std::map<std::string, zvx_kernel_stat> namedstats;   // helper kernels timed under a name of their own (the prosody-control kernels)
     std::vector<hipEvent_t> event_pool;
+    std::vector<zvx_stream*> streams;       // the open stream sessions (zvx_stream_open); zvx_destroy closes what is left
 
     // ------------------------------------------------------------------ helpers
     int cfg_int(const char* k) const {
@@ -408,6 +410,39 @@ struct zvx_ctx {
         HIPCHK(hipEventCreateWithFlags(&ev_mel_free, hipEventDisableTiming));
         HIPCHK(hipEventCreateWithFlags(&ev_main_join, hipEventDisableTiming));
     }
+};
+
+// A stream session (include/zvx.h: zvx_stream_open): one utterance's mel on the device, the planners of its post stages and, per stage,
+// two device buffers laid out [history | new].  A stage's output is written straight behind the next stage's history; dropping the history
+// before keep_from copies the retained tail into the stage's OTHER buffer (never an overlapping copy) and swaps the two.
+struct zvx_stream {
+    zvx_ctx* c = nullptr;
+    int frames = 0, chunk = 0, cpc = 0, halo = 0, hop = 0, native = 0, out_rate = 0;
+    int nchunks = 0, next_chunk = 0, done = 0;
+    int Pcap = 0;                          // the longest row a group can have, in mel frames
+    long wstride = 0;                      // samples between the vocoder's rows
+    int64_t total = 0, emitted = 0, delay = 0, max_piece = 0;
+    enum { DENOISE = 0, LIMIT = 1, RESAMPLE = 2 };
+    struct Stage {
+        int kind = DENOISE;
+        zvx_plan::ReachPlanner reach;
+        zvx_plan::ResamplePlanner rate;
+        float* buf[2] = {nullptr, nullptr};
+        int cur = 0;
+        int64_t cap = 0, hist = 0;         // samples a buffer holds; retained samples [origin, received) at the front of buf[cur]
+        zvx_plan::Step push(int64_t n, bool last) { return kind == RESAMPLE ? rate.push(n, last) : reach.push(n, last); }
+        int64_t received() const { return kind == RESAMPLE ? rate.received : reach.received; }
+    };
+    std::vector<Stage> stages;             // in the order they run: denoiser, limiter, rate conversion
+    zvx_denoise_params dn{};
+    std::vector<float> bias;
+    zvx_limit_params lim{};
+    char* dev = nullptr;                   // ONE device allocation: the mel, a group's rows, the vocoder's rows, the stage buffers, the host piece's staging
+    float* mel = nullptr;
+    float* rows = nullptr;
+    float* wav = nullptr;
+    float* ostage = nullptr;
+    float* pinned = nullptr;               // host piece: [max_piece] f32
 };
 
 namespace {
@@ -2512,6 +2547,18 @@ EmittedRange emitted_range(const char* who, const RowsWindow* win, const int32_t
     return e;
 }
 
+// the checks of the limiter's own parameters (zvx_limit, zvx_limit_ex, zvx_stream_open) -> W
+void limit_os_check(const char* who, int os) {
+    if (os != 1 && os != 2 && os != 4 && os != 8) fail(ZVX_E_INVALID, "%s: oversample %d is none of 1, 2, 4, 8", who, os);
+}
+int limit_params_check(const char* who, int rate, const zvx_limit_params* p) {
+    if (!std::isfinite(p->ceiling) || !(p->ceiling > 0.f) || p->ceiling > 8.f) fail(ZVX_E_INVALID, "%s: ceiling must be finite and lie in (0, 8]", who);
+    if (!std::isfinite(p->window_ms) || !(p->window_ms > 0.f)) fail(ZVX_E_INVALID, "%s: window_ms must be finite and positive", who);
+    const double w = std::max(1.0, rint((double)rate * (double)p->window_ms / 1000.0));
+    if (w > (double)LIMIT_MAX_W) fail(ZVX_E_UNSUPPORTED, "%s: window of %.0f samples (at most %d)", who, w, LIMIT_MAX_W);
+    return (int)w;
+}
+
 // zvx_true_peak (p == nullptr: the envelope's maximum only, results in tpeak), zvx_limit and zvx_limit_ex (win != nullptr)
 void do_limit(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_limit_params* p,
               int oversample, void* out, int64_t out_stride, float* peak_in, float* min_gain, int flags, const RowsWindow* win = nullptr) {
@@ -2521,18 +2568,9 @@ void do_limit(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamp
     if (rate < 4000 || rate > 192000) fail(ZVX_E_INVALID, "%s: rate %d outside [4000, 192000]", who, rate);
     flags_check(who, flags, lim ? (ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16) : ZVX_DEVICE_IN);
     const int os = lim ? p->oversample : oversample;
-    if (os != 1 && os != 2 && os != 4 && os != 8) fail(ZVX_E_INVALID, "%s: oversample %d is none of 1, 2, 4, 8", who, os);
-    int W = 0;
-    if (lim) {
-        out_rows_check(who, in, out, out_stride, Nmax, flags);
-        if (!std::isfinite(p->ceiling) || !(p->ceiling > 0.f) || p->ceiling > 8.f) fail(ZVX_E_INVALID, "%s: ceiling must be finite and lie in (0, 8]", who);
-        if (!std::isfinite(p->window_ms) || !(p->window_ms > 0.f)) fail(ZVX_E_INVALID, "%s: window_ms must be finite and positive", who);
-    }
-    if (lim) {
-        const double w = std::max(1.0, rint((double)rate * (double)p->window_ms / 1000.0));
-        if (w > (double)LIMIT_MAX_W) fail(ZVX_E_UNSUPPORTED, "%s: window of %.0f samples (at most %d)", who, w, LIMIT_MAX_W);
-        W = (int)w;
-    }
+    limit_os_check(who, os);
+    if (lim) out_rows_check(who, in, out, out_stride, Nmax, flags);
+    const int W = lim ? limit_params_check(who, rate, p) : 0;
     const EmittedRange er = emitted_range(who, win, nsamples, B, 2 * (int64_t)W + (os > 1 ? LIMIT_ENV_REACH : 0), r, in, out, out_stride);
     const int32_t* cnt = er.cnt;
     const long off = er.off, cnt_max = er.cnt_max; const double cnt_sum = er.cnt_sum;
@@ -2625,17 +2663,23 @@ void dn_fill(DenoiseArgs& a, const DnGeom& g, const zvx_ctx::DnTables& tb) {
 }
 double dn_fft_flops(const DnGeom& g, double frames, int transforms) { return transforms * frames * 5.0 * g.n_fft * g.log2n; }
 
+// the checks of the denoiser's own parameters and bias (zvx_denoise, zvx_denoise_ex, zvx_stream_open) -> the model's STFT geometry
+DnGeom denoise_params_check(const zvx_ctx* c, const char* who, const float* bias, const zvx_denoise_params* p) {
+    if (!bias || !p) fail(ZVX_E_INVALID, "%s: %s is NULL", who, !bias ? "bias" : "params");
+    if (!std::isfinite(p->strength) || p->strength < 0.f) fail(ZVX_E_INVALID, "%s: strength must be finite and not negative", who);
+    if (!(p->floor >= 0.f && p->floor <= 1.f)) fail(ZVX_E_INVALID, "%s: floor must lie in [0, 1]", who);
+    const DnGeom g = dn_geom(c, who);
+    for (int k = 0; k < g.nf; k++) if (!(bias[k] >= 0.f)) fail(ZVX_E_INVALID, "%s: bias[%d] is negative or NaN", who, k);
+    return g;
+}
+
 // zvx_denoise (win == nullptr: the whole rows) and zvx_denoise_ex
 void do_denoise(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias, const zvx_denoise_params* p,
                 void* out, int64_t out_stride, int flags, const RowsWindow* win = nullptr) {
     const RowsInfo r = rows_check(who, in, nsamples, B, Nmax, 65535);
     flags_check(who, flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16);
     out_rows_check(who, in, out, out_stride, Nmax, flags);
-    if (!bias || !p) fail(ZVX_E_INVALID, "%s: %s is NULL", who, !bias ? "bias" : "params");
-    if (!std::isfinite(p->strength) || p->strength < 0.f) fail(ZVX_E_INVALID, "%s: strength must be finite and not negative", who);
-    if (!(p->floor >= 0.f && p->floor <= 1.f)) fail(ZVX_E_INVALID, "%s: floor must lie in [0, 1]", who);
-    const DnGeom g = dn_geom(c, who);
-    for (int k = 0; k < g.nf; k++) if (!(bias[k] >= 0.f)) fail(ZVX_E_INVALID, "%s: bias[%d] is negative or NaN", who, k);
+    const DnGeom g = denoise_params_check(c, who, bias, p);
     const RowsWindow whole;
     const RowsWindow& w = win ? *win : whole;
     const EmittedRange er = emitted_range(who, win, nsamples, B, g.n_fft - 1, r, in, out, out_stride);
@@ -2801,6 +2845,230 @@ void do_vocode(zvx_ctx* c, const int32_t* pad_to, void* wav, int64_t wav_stride,
     if (!(dev_out && (flags & ZVX_NO_SYNC))) c->sync();
 }
 
+// ------------------------------------------------------------------------------------------------
+// stream sessions (include/zvx.h: zvx_stream_open / zvx_stream_next / zvx_stream_info / zvx_stream_close)
+// ------------------------------------------------------------------------------------------------
+void stream_free(zvx_stream* s) {
+    zvx_ctx* c = s->c;
+    auto it = std::find(c->streams.begin(), c->streams.end(), s);
+    if (it != c->streams.end()) c->streams.erase(it);
+    if (s->dev || s->pinned) {                               // work queued on the context may still read or write the session's memory
+        (void)hipStreamSynchronize(c->stream);
+        for (hipStream_t s2 : {c->main0, c->voc_aux[0], c->voc_aux[1]}) if (s2 && s2 != c->stream) (void)hipStreamSynchronize(s2);
+    }
+    if (s->dev) (void)hipFree(s->dev);
+    if (s->pinned) (void)hipHostFree(s->pinned);
+    delete s;
+}
+
+// the native samples the rate conversion runs behind its input: output n is final once n M + half <= (received - 1) L
+int64_t rs_reach(const zvx_plan::RatePair& p) { return p.half ? zvx_plan::ceil_div(p.half, p.L) + 1 : 0; }
+
+void do_stream_open(zvx_ctx* c, const float* mel, int frames, const zvx_stream_params* p, int flags, zvx_stream** out) {
+    const char* who = "zvx_stream_open";
+    // ---- every check, before anything is allocated
+    if (!p || !out) fail(ZVX_E_INVALID, "%s: %s is NULL", who, !p ? "params" : "out");
+    *out = nullptr;
+    if (flags & ~(ZVX_DEVICE_IN | ZVX_PCM16)) fail(ZVX_E_INVALID, "%s: unknown flag in %d", who, flags);
+    if (flags & ZVX_PCM16) fail(ZVX_E_UNSUPPORTED, "%s: a session hands out f32 pieces (no ZVX_PCM16)", who);
+    if (!mel) {
+        if (frames != 0) fail(ZVX_E_INVALID, "%s: mel is NULL (the context's mel) and frames is %d, not 0", who, frames);
+        if (!c->have_mel) fail(ZVX_E_STATE, "%s: no mel in the context (call zvx_decode first, or pass a mel)", who);
+        if (c->B != 1) fail(ZVX_E_UNSUPPORTED, "%s: the context holds a batch of %d utterances (a session streams one)", who, c->B);
+        frames = c->mel_len_host[0];
+    }
+    if (frames < 2) fail(ZVX_E_INVALID, "%s: %d mel frames (at least 2)", who, frames);
+    if (p->chunk_frames < 1) fail(ZVX_E_INVALID, "%s: chunk_frames %d (at least 1)", who, p->chunk_frames);
+    if (p->chunks_per_call < 1 || p->chunks_per_call > STREAM_MAX_ROWS)
+        fail(ZVX_E_INVALID, "%s: chunks_per_call %d outside 1 .. %d", who, p->chunks_per_call, STREAM_MAX_ROWS);
+    if (p->halo < 0) fail(ZVX_E_INVALID, "%s: halo %d is negative", who, p->halo);
+    if (!p->denoise != !p->denoise_bias) fail(ZVX_E_INVALID, "%s: denoise and denoise_bias go together (one of them is NULL)", who);
+    const int native = model_rate(c), hop = c->hop, nm = c->n_mels;
+    const int out_rate = c->out_rate && c->out_rate != native ? c->out_rate : native;
+    const int64_t total_native = (int64_t)frames * hop;
+    DnGeom g{};
+    if (p->denoise) {
+        g = denoise_params_check(c, who, p->denoise_bias, p->denoise);
+        if (total_native < dn_min_samples(g))
+            fail(ZVX_E_INVALID, "%s: %d frames are %lld samples; the denoiser needs at least %d (zvx_melspec's conditions)", who, frames,
+                 (long long)total_native, dn_min_samples(g));
+    }
+    int W = 0;
+    if (p->limit) { limit_os_check(who, p->limit->oversample); W = limit_params_check(who, native, p->limit); }
+    zvx_plan::RatePair rp;
+    if (out_rate != native) {
+        int L = 1, M = 1;
+        rs_pair(native, out_rate, &L, &M);
+        rp = zvx_plan::rate_pair(native, out_rate);
+    }
+    // ---- geometry: a group's rows, the stages' buffers, the longest piece
+    const int chunk = std::min(p->chunk_frames, frames), halo = std::min(p->halo, frames);
+    const int nchunks = (int)(((int64_t)frames + p->chunk_frames - 1) / p->chunk_frames);
+    const int rows = std::min(p->chunks_per_call, nchunks);
+    const int Pcap = (int)std::min<int64_t>(frames, (int64_t)chunk + 2 * (int64_t)halo);
+    const int64_t G = (int64_t)rows * chunk * hop;           // the most new samples one call brings
+    struct Want { int kind; int64_t R, keep; };              // keep: the most history a stage retains between two calls
+    std::vector<Want> want;
+    if (p->denoise) want.push_back({zvx_stream::DENOISE, (int64_t)g.n_fft - 1, 2 * ((int64_t)g.n_fft - 1)});
+    if (p->limit) { const int64_t R = 2 * (int64_t)W + (p->limit->oversample > 1 ? LIMIT_ENV_REACH : 0); want.push_back({zvx_stream::LIMIT, R, 2 * R}); }
+    if (out_rate != native) want.push_back({zvx_stream::RESAMPLE, rs_reach(rp), 2 * rp.half / rp.L + 2});
+    int64_t delay = 0;
+    for (const Want& w : want) delay += w.R;
+    if (G + delay > (int64_t)1 << 28 || (int64_t)rows * Pcap * std::max(hop, nm) > (int64_t)1 << 28)
+        fail(ZVX_E_UNSUPPORTED, "%s: a group of %d chunks of %d frames is %lld samples (at most 2^28 per call)", who, rows, chunk, (long long)G);
+    const int64_t max_piece = zvx_plan::ceil_div((G + delay) * rp.L, rp.M) + 1;
+    const long wstride = ((long)Pcap * hop + 7) & ~7L;
+    // ---- the tables a stage needs on first use: no zvx_stream_next waits for an upload
+    if (p->denoise && p->denoise->strength != 0.f) dn_tables(c, g);
+    if (p->limit) { limit_win(c, W); if (p->limit->oversample > 1) rs_bank(c, p->limit->oversample, 1); }
+    if (out_rate != native) rs_bank(c, (int)rp.L, (int)rp.M);
+    // ---- the session and its memory
+    zvx_stream* s = new zvx_stream();
+    s->c = c;
+    try {
+        s->frames = frames; s->chunk = p->chunk_frames; s->cpc = p->chunks_per_call; s->halo = p->halo; s->hop = hop; s->native = native; s->out_rate = out_rate;
+        s->nchunks = nchunks; s->Pcap = Pcap; s->wstride = wstride; s->delay = delay; s->max_piece = max_piece;
+        s->total = zvx_plan::ceil_div(total_native * rp.L, rp.M);
+        if (p->denoise) { s->dn = *p->denoise; s->bias.assign(p->denoise_bias, p->denoise_bias + g.nf); }
+        if (p->limit) s->lim = *p->limit;
+        auto pad = [](int64_t floats) { return (size_t)((floats * 4 + 255) & ~(int64_t)255); };
+        size_t bytes = pad((int64_t)frames * nm) + pad((int64_t)rows * Pcap * nm) + pad((int64_t)rows * wstride) + pad(max_piece);
+        int64_t in_max = G;
+        for (const Want& w : want) {
+            zvx_stream::Stage st;
+            st.kind = w.kind;
+            if (w.kind == zvx_stream::RESAMPLE) st.rate = zvx_plan::ResamplePlanner(native, out_rate); else st.reach = zvx_plan::ReachPlanner(w.R);
+            st.cap = w.keep + in_max + 8;
+            in_max += w.R;
+            bytes += 2 * pad(st.cap);
+            s->stages.push_back(st);
+        }
+        HIPCHK(hipMalloc((void**)&s->dev, bytes));
+        HIPCHK(hipHostMalloc((void**)&s->pinned, (size_t)max_piece * 4, hipHostMallocDefault));
+        HIPCHK(hipMemsetAsync(s->dev, 0, bytes, c->stream));
+        char* q = s->dev;
+        auto take = [&](int64_t floats) { float* r = (float*)q; q += pad(floats); return r; };
+        s->mel = take((int64_t)frames * nm); s->rows = take((int64_t)rows * Pcap * nm); s->wav = take((int64_t)rows * wstride); s->ostage = take(max_piece);
+        for (auto& st : s->stages) { st.buf[0] = take(st.cap); st.buf[1] = take(st.cap); }
+        const size_t mbytes = (size_t)frames * nm * 4;
+        if (!mel) HIPCHK(hipMemcpyAsync(s->mel, c->fbuf("mel", 0), mbytes, hipMemcpyDeviceToDevice, c->stream));       // utterance 0: the first rows
+        else if (flags & ZVX_DEVICE_IN) HIPCHK(hipMemcpyAsync(s->mel, mel, mbytes, hipMemcpyDeviceToDevice, c->stream));
+        else {
+            HIPCHK(hipMemcpyAsync(s->mel, mel, mbytes, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(hipStreamSynchronize(c->stream));         // the caller's mel may be reused when the call returns
+        }
+    } catch (...) {
+        stream_free(s);
+        throw;
+    }
+    c->streams.push_back(s);
+    *out = s;
+}
+
+void do_stream_next(zvx_stream* s, void* out, int64_t capacity, int64_t* n_out, int32_t* done, int flags) {
+    const char* who = "zvx_stream_next";
+    zvx_ctx* c = s->c;
+    if (!n_out || !done) fail(ZVX_E_INVALID, "%s: %s is NULL", who, !n_out ? "n_out" : "done");
+    if (flags & ~(ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16)) fail(ZVX_E_INVALID, "%s: unknown flag in %d", who, flags);
+    if (flags & ZVX_PCM16) fail(ZVX_E_UNSUPPORTED, "%s: a session hands out f32 pieces (no ZVX_PCM16)", who);
+    if ((flags & ZVX_NO_SYNC) && !(flags & ZVX_DEVICE_OUT)) fail(ZVX_E_INVALID, "%s: ZVX_NO_SYNC needs ZVX_DEVICE_OUT", who);
+    if (capacity < 0) fail(ZVX_E_INVALID, "%s: capacity %lld is negative", who, (long long)capacity);
+    if (s->done) fail(ZVX_E_STATE, "%s: the stream is done (its last piece has been handed out)", who);
+    // ---- the group: chunk st is vocoded on frames [max(0, st - halo), min(frames, st + chunk + halo)), its interior kept
+    const int g0 = s->next_chunk, g1 = std::min(s->nchunks, g0 + s->cpc), B = g1 - g0, nm = c->n_mels;
+    const bool last = g1 == s->nchunks;
+    StreamRowsArgs ra{};
+    StreamInteriorArgs ia{};
+    int P[STREAM_MAX_ROWS];
+    int Pmax = 0; long cnt_max = 0; int64_t n_new = 0;
+    for (int i = 0; i < B; i++) {
+        const int64_t st = (int64_t)(g0 + i) * s->chunk;
+        const int64_t lo = std::max<int64_t>(0, st - s->halo), hi = std::min<int64_t>(s->frames, st + s->chunk + s->halo);
+        const int64_t n = std::min<int64_t>(s->chunk, s->frames - st);
+        P[i] = (int)(hi - lo); Pmax = std::max(Pmax, P[i]);
+        ra.lo[i] = (int)lo; ra.P[i] = P[i];
+        ia.off[i] = (int)((st - lo) * s->hop); ia.cnt[i] = (int)(n * s->hop); ia.pos[i] = (long)n_new;
+        cnt_max = std::max<long>(cnt_max, ia.cnt[i]); n_new += n * s->hop;
+    }
+    if (Pmax > s->Pcap) fail(ZVX_E_STATE, "%s: a row of %d frames exceeds the session's %d", who, Pmax, s->Pcap);
+    // ---- the plan, on copies of the planners: host integer arithmetic, so the piece's size is known before anything is queued
+    const size_t K = s->stages.size();
+    std::vector<zvx_stream::Stage> plan(s->stages);
+    std::vector<zvx_plan::Step> steps(K);
+    int64_t n = n_new;
+    for (size_t k = 0; k < K; k++) {
+        steps[k] = plan[k].push(n, last);
+        const int64_t held = plan[k].hist + n;
+        if (held != plan[k].received() - steps[k].in_origin || held > plan[k].cap)
+            fail(ZVX_E_STATE, "%s: stage %zu holds %lld samples (buffer %lld, window from %lld)", who, k, (long long)held, (long long)plan[k].cap, (long long)steps[k].in_origin);
+        n = steps[k].out_count;
+    }
+    *n_out = n;
+    if (n > s->max_piece) fail(ZVX_E_STATE, "%s: a piece of %lld samples exceeds max_piece %lld", who, (long long)n, (long long)s->max_piece);
+    if (n > 0 && !out) fail(ZVX_E_INVALID, "%s: out is NULL", who);
+    if (capacity < n) fail(ZVX_E_BUFFER, "%s: capacity %lld < %lld samples of this piece (nothing was consumed)", who, (long long)capacity, (long long)n);
+    // ---- from here on the call consumes the group; a failure past this point ends the session
+    try {
+        c->have_features = false; c->have_mel = false;      // as zvx_vocode_mel: the context's intermediates are void
+        ra.mel = s->mel; ra.out = s->rows; ra.B = B; ra.Pmax = Pmax; ra.nm = nm;
+        {
+            TagScope scope(c, "voc.stream");
+            double rd = 0; for (int i = 0; i < B; i++) rd += (double)P[i] * nm * 4.0;
+            c->timed(0.0, rd + (double)B * Pmax * nm * 4.0, [&] { launch_stream_rows(ra, c->stream); });
+        }
+        c->stage_begin(ZVX_T_VOCODER);
+        run_vocoder(c, s->rows, nm, Pmax, P, P, B, s->wav, s->wstride, 0);       // the rows of ZeroVox._vocode_stream_native, at the native rate
+        c->stage_end(ZVX_T_VOCODER);
+        float* final_dst = (flags & ZVX_DEVICE_OUT) ? (float*)out : s->ostage;
+        ia.wav = s->wav; ia.w_bs = s->wstride; ia.B = B;
+        ia.out = K ? s->stages[0].buf[s->stages[0].cur] + s->stages[0].hist : final_dst;
+        {
+            TagScope scope(c, "voc.stream");
+            c->timed(0.0, 8.0 * (double)n_new, [&] { launch_stream_interiors(ia, cnt_max, c->stream); });
+        }
+        const int f = ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC;
+        int64_t n_in = n_new;
+        for (size_t k = 0; k < K; k++) {
+            zvx_stream::Stage& st = s->stages[k];
+            const zvx_plan::Step& sp = steps[k];
+            const int64_t held = st.hist + n_in;
+            const float* in = st.buf[st.cur];
+            float* dst = k + 1 < K ? s->stages[k + 1].buf[s->stages[k + 1].cur] + s->stages[k + 1].hist : final_dst;
+            if (sp.out_count > 0 && held > 0) {
+                const int32_t n32 = (int32_t)held;
+                const int64_t stride = std::max(held, sp.out_count);
+                const RowsWindow w{sp.in_origin, sp.out_begin, sp.out_count, last ? 1 : 0};
+                if (st.kind == zvx_stream::DENOISE) do_denoise(c, who, in, &n32, 1, n32, s->bias.data(), &s->dn, dst, stride, f, &w);
+                else if (st.kind == zvx_stream::LIMIT) do_limit(c, who, in, &n32, 1, n32, s->native, &s->lim, 0, dst, stride, nullptr, nullptr, f, &w);
+                else do_resample(c, in, &n32, 1, n32, s->native, s->out_rate, dst, stride, nullptr, f, sp.in_origin, sp.out_begin, sp.out_count);
+            }
+            const int64_t drop = sp.keep_from - sp.in_origin, keep = held - drop;
+            if (drop > 0) {                                  // into the other buffer: never an overlapping copy
+                if (keep > 0) HIPCHK(hipMemcpyAsync(st.buf[st.cur ^ 1], in + drop, (size_t)keep * 4, hipMemcpyDeviceToDevice, c->stream));
+                st.cur ^= 1;
+            }
+            st.hist = keep; st.reach = plan[k].reach; st.rate = plan[k].rate;
+            n_in = sp.out_count;
+        }
+        s->next_chunk = g1; s->emitted += n; s->done = last ? 1 : 0;
+        *done = s->done;
+        if (!(flags & ZVX_DEVICE_OUT)) {
+            if (n > 0) HIPCHK(hipMemcpyAsync(s->pinned, s->ostage, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
+            c->sync();                                       // the call's one wait
+            if (n > 0) memcpy(out, s->pinned, (size_t)n * 4);
+        } else if (!(flags & ZVX_NO_SYNC)) c->sync();
+    } catch (...) {
+        s->done = 1;
+        throw;
+    }
+}
+
+void do_stream_info(const zvx_stream* s, int64_t* info, int n_info) {
+    if (!info || n_info < 1) fail(ZVX_E_INVALID, "zvx_stream_info: info is NULL or n_info %d < 1", n_info);
+    const int64_t v[5] = {s->total, s->emitted, s->out_rate, s->delay, s->max_piece};
+    for (int i = 0; i < n_info && i < 5; i++) info[i] = v[i];
+}
+
 template <typename F>
 zvx_status guarded(zvx_ctx* ctx, F&& f) {
     if (!ctx) return ZVX_E_INVALID;
@@ -2864,6 +3132,7 @@ void zvx_destroy(zvx_ctx* c) {
     (void)hipSetDevice(c->device);
     if (c->front_stream) (void)hipStreamSynchronize(c->front_stream);
     if (c->stream) (void)hipStreamSynchronize(c->stream);
+    while (!c->streams.empty()) stream_free(c->streams.back());      // the open stream sessions go first
     zvx_comm_destroy(c);
     for (int i = 0; i < 2; i++) { if (c->arena[i].p) (void)hipHostFree(c->arena[i].p); if (c->arena[i].ev) (void)hipEventDestroy(c->arena[i].ev); }
     if (c->copy_stream && !c->copy_is_comm) { (void)hipStreamSynchronize(c->copy_stream); (void)hipStreamDestroy(c->copy_stream); }
@@ -3145,6 +3414,25 @@ zvx_status zvx_denoise_ex(zvx_ctx* c, const float* in, const int32_t* nsamples, 
         const RowsWindow win{in_origin, out_begin, out_count, last};
         do_denoise(c, "zvx_denoise_ex", in, nsamples, B, Nmax, bias, params, out, out_stride, flags, &win);
     });
+}
+
+zvx_status zvx_stream_open(zvx_ctx* c, const float* mel, int frames, const zvx_stream_params* params, int flags, zvx_stream** out) {
+    return guarded(c, [&] { do_stream_open(c, mel, frames, params, flags, out); });
+}
+
+zvx_status zvx_stream_next(zvx_stream* s, void* out, int64_t capacity, int64_t* n_out, int32_t* done, int flags) {
+    if (!s) return ZVX_E_INVALID;
+    return guarded(s->c, [&] { do_stream_next(s, out, capacity, n_out, done, flags); });
+}
+
+zvx_status zvx_stream_info(const zvx_stream* s, int64_t* info, int n_info) {
+    if (!s) return ZVX_E_INVALID;
+    return guarded(s->c, [&] { do_stream_info(s, info, n_info); });
+}
+
+zvx_status zvx_stream_close(zvx_stream* s) {
+    if (!s) return ZVX_E_INVALID;
+    return guarded(s->c, [&] { stream_free(s); });
 }
 
 zvx_status zvx_synthesize(zvx_ctx* c, const int32_t* phoneme, const int32_t* puncts, const int32_t* duration, const int32_t* T,

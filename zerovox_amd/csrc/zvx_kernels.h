@@ -378,6 +378,22 @@ struct JoinCopyArgs {
     void* out; long cap; int pcm16, fade;
 };
 void launch_join_copy(const JoinCopyArgs& a, long upper, hipStream_t s);
+// The two gathers of a stream session (include/zvx.h, zvx_stream_next): pure data movement, 16-byte loads / stores where source and
+// destination addresses allow, scalar otherwise.  The per-row tables travel in the kernel arguments (a group has at most
+// STREAM_MAX_ROWS rows), so no call uploads one.
+constexpr int STREAM_MAX_ROWS = 64;          // zvx_stream_params.chunks_per_call
+// Rows: row b of out [B][Pmax][nm] = mel frames [lo[b], lo[b] + P[b]) of mel [frames][nm], then zeros up to Pmax frames.
+struct StreamRowsArgs {
+    const float* mel; float* out; int B, Pmax, nm;
+    int lo[STREAM_MAX_ROWS], P[STREAM_MAX_ROWS];
+};
+void launch_stream_rows(const StreamRowsArgs& a, hipStream_t s);
+// Interiors: out[pos[b] + i] = wav[b][off[b] + i] for i < cnt[b]: the rows' kept samples as one contiguous run (pos: the prefix sum of cnt).
+struct StreamInteriorArgs {
+    const float* wav; long w_bs; float* out; int B;
+    int off[STREAM_MAX_ROWS], cnt[STREAM_MAX_ROWS]; long pos[STREAM_MAX_ROWS];
+};
+void launch_stream_interiors(const StreamInteriorArgs& a, long cnt_max, hipStream_t s);
 // Integrated loudness (ITU-R BS.1770 / EBU R128) and gain of a batch's waveform rows (include/zvx.h, zvx_loudness / zvx_normalize): every
 // decision is made on the DEVICE, in double, in the power domain.
 // K-weighting: two biquads in transposed direct form II, double state.  Stage 1 b0..b2, a1, a2; stage 2 has b = [1, -2, 1].

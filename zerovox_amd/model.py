@@ -222,7 +222,7 @@ class ZeroVox:
     # each side makes a chunk's interior identical to the same samples of a whole-utterance pass.
     STREAM_HALO = 16
 
-    def vocode_stream(self, mel, chunk_frames=64, halo=STREAM_HALO, chunks_per_call=1, limiter=None, denoise=None):
+    def vocode_stream(self, mel, chunk_frames=64, halo=STREAM_HALO, chunks_per_call=1, limiter=None, denoise=None, resident=False):
         """Chunked vocoding for first-audio latency: mel [L, n_mels] -> yields waveform chunks (np.float32) that
         concatenate to ``vocode_mel(mel)``.  Every chunk is vocoded with ``halo`` extra frames on each side and only its
         interior is kept; ``chunks_per_call`` chunks ride in one launch sequence as independent batch rows.
@@ -235,7 +235,14 @@ class ZeroVox:
         denoise: None (nothing of the denoiser is created), or the keywords ZeroVoxTTS._denoise builds (strength, floor): the native-rate
         chunks pass through the windowed denoiser (zerovox_amd.denoiser, zvx_denoise_ex) with ``denoise_bias`` and concatenate bit for
         bit to zvx_denoise of the whole native stream; the denoised stream runs denoiser.reach(fft_size) = fft_size - 1 samples behind
-        the vocoder.  Denoiser first, then the limiter, then the conversion -- the order of ``inference_ex``; the delays add up."""
+        the vocoder.  Denoiser first, then the limiter, then the conversion -- the order of ``inference_ex``; the delays add up.
+        resident: False (the default: the host-planned stream above), or True: the same keywords drive a stream session of the library
+        (include/zvx.h, zvx_stream_open) -- the mel is uploaded once, the samples stay on the device between the steps and every piece
+        costs one wait.  The pieces concatenate to the same bits; where they are cut may differ.  mel None (resident only): the mel the
+        context holds after decode."""
+        if resident:
+            yield from self._vocode_stream_resident(mel, chunk_frames, halo, chunks_per_call, limiter, denoise)
+            return
         ctx = self._ctx
         rate, native = ctx.get_int("out_rate"), ctx.get_int("sampling_rate")
         convert = rate > 0 and rate != native
@@ -252,6 +259,11 @@ class ZeroVox:
         if convert:
             chunks = stream_resample(chunks, native, rate, lambda x, o, b, n: ctx.resample_window([x], native, rate, o, b, n)[0][0].copy())
         yield from chunks
+
+    def _vocode_stream_resident(self, mel, chunk_frames, halo, chunks_per_call, limiter, denoise):
+        bias = self.denoise_bias if denoise is not None else None           # (first use runs the vocoder: before the session opens)
+        yield from self._ctx.stream_open(mel, chunk_frames=chunk_frames, chunks_per_call=max(1, chunks_per_call), halo=halo, denoise=denoise,
+                                         bias=bias, limit=limiter)
 
     def _vocode_stream_native(self, mel, chunk_frames, halo, chunks_per_call, native_rate):
         mel = np.asarray(mel, np.float32)

@@ -266,7 +266,7 @@ class ZeroVoxTTS:
 
     def tts_stream(self, text: str, spkemb, chunk_frames=64, chunks_per_call=1, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0,
                    energy_shift=0.0, energy_range=1.0, loudness=None, limiter=False, peak_db=None, limiter_ms=5.0, denoise=None,
-                   denoise_strength=None):
+                   denoise_strength=None, resident=False):
         """Streaming variant of ``tts`` (not in the reference): encoder + mel decoder run once, the vocoder
         runs chunk by chunk (16-frame halo), yielding float32 waveform pieces that concatenate to ``tts(text, spkemb)[0]``
         up to the reference's `_min_mel_len` zero-padding of short utterances.  A stream cannot be loudness-normalised: the gain is not
@@ -283,7 +283,10 @@ class ZeroVoxTTS:
         ``tts(denoise=...)``, which pads a short utterance first -- and run n_fft - 1 samples behind the vocoder (1023: 46 ms at 22.05
         kHz).  With ``peak_db`` as well the stream is limit(denoise(stream)) and runs n_fft - 1 + limiter.reach(W, 4) samples behind;
         an ``output_rate`` converts last.  That delay is why the strength is asked for by this name: ``denoise=...``, the
-        whole-utterance keyword of tts and tts_long, still raises ValueError and points here."""
+        whole-utterance keyword of tts and tts_long, still raises ValueError and points here.
+        resident: False (the default: the stream is planned on the host), or True: a stream session of the library runs it (include/zvx.h,
+        zvx_stream_open; ZeroVox.vocode_stream(resident=True)) -- the decoder's mel never leaves the device and every piece costs one
+        wait.  The concatenation is the same to the bit; the pieces may be cut elsewhere."""
         if denoise is not None:
             raise ValueError("tts_stream does not take denoise=: pass denoise_strength=<strength> (the stream is then denoised window by window, "
                              "n_fft - 1 samples behind the vocoder); denoise= is the whole-utterance keyword of tts and tts_long")
@@ -299,9 +302,9 @@ class ZeroVoxTTS:
                 raise ValueError(f"tts_stream: peak_db must be finite, not {peak_db}")
             lim = self._limiter(True, limiter_ms, peak_db)
         return self._tts_stream(text, spkemb, chunk_frames, chunks_per_call, self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range),
-                                lim, den)
+                                lim, den, resident)
 
-    def _tts_stream(self, text, spkemb, chunk_frames, chunks_per_call, prosody, limiter=None, denoise=None):
+    def _tts_stream(self, text, spkemb, chunk_frames, chunks_per_call, prosody, limiter=None, denoise=None, resident=False):
         text = text.strip()
         phone_ids, punct_ids = self.text2phonemeids(text)
         if not phone_ids:
@@ -315,6 +318,11 @@ class ZeroVoxTTS:
         ml = int(mel_len[0])
         if ml < 2:
             raise ValueError(f"predicted mel length {ml} is too short to synthesise")
+        if resident:                                                 # no host mel: the session takes the context's with a device copy
+            ctx._chk(ctx._lib.zvx_decode(ctx._h, None, 0, 0))
+            yield from self._model.vocode_stream(None, chunk_frames=chunk_frames, chunks_per_call=chunks_per_call, limiter=limiter,
+                                                 denoise=denoise, resident=True)
+            return
         mel = ctx.decode(1, ml)[0, :ml]
         yield from self._model.vocode_stream(mel, chunk_frames=chunk_frames, chunks_per_call=chunks_per_call, limiter=limiter,
                                              denoise=denoise)
