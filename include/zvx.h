@@ -607,7 +607,8 @@ zvx_status zvx_denoise_ex(zvx_ctx* ctx, const float* in, const int32_t* nsamples
  *   on any single *n_out, so that a caller sizes one buffer.
  * zvx_stream_close frees everything (NULL: ZVX_E_INVALID); zvx_destroy closes the context's open sessions first.  Errors of session calls
  *   are reported through zvx_last_error of the session's context.
- * Not here: ZVX_PCM16 pieces, several utterances per session, a streamed loudness gain (it is not known before the last chunk). */
+ * Not here: ZVX_PCM16 pieces, several utterances per session (a session is one utterance; zvx_stream_next_many below steps many sessions
+ *   in one call), a streamed loudness gain (it is not known before the last chunk). */
 typedef struct zvx_stream zvx_stream;
 typedef struct zvx_stream_params {
     int32_t chunk_frames;              /* mel frames per chunk, >= 1 */
@@ -622,6 +623,43 @@ zvx_status zvx_stream_open(zvx_ctx* ctx, const float* mel, int frames, const zvx
 zvx_status zvx_stream_next(zvx_stream* s, void* out, int64_t capacity, int64_t* n_out, int32_t* done, int flags);
 zvx_status zvx_stream_info(const zvx_stream* s, int64_t* info, int n_info);
 zvx_status zvx_stream_close(zvx_stream* s);
+
+/* Many streams in one call: continuous batching of stream sessions.  Sessions stay independent objects -- opened and closed at any time,
+ * different in every parameter --; zvx_stream_next_many steps any subset of ONE context's open sessions, and the groups of all of them
+ * travel through the vocoder as one batch.  A step of a single stream is a launch-bound job on one short row; n of them in one batch cost
+ * one launch sequence instead of n.
+ * Result: for every i, out[i], n_out[i] and done[i] are exactly what zvx_stream_next(sessions[i], out[i], capacity[i], &n_out[i],
+ *   &done[i], flags) would have produced, and the session's state afterwards is the same: the same piece boundaries and the same bits,
+ *   piece by piece.  A session's results do not depend on which other sessions share the call, on their order or on their parameters
+ *   (chunk_frames, chunks_per_call, halo, chain, captured "out_rate", length, progress): a waveform's bits do not depend on the batch its
+ *   rows travel in, which is what the rows of a chunks_per_call group already rest on.
+ * One vocoder run: session i contributes min(chunks_per_call, chunks left) rows; the rows go in session order, within a session in chunk
+ *   order, zero-padded to the longest row of the call, through ONE run of the vocoder at the native rate.  The rows and the vocoder's output
+ *   rows are work buffers of the context (they grow on first use like every other); the call allocates nothing of a session's.
+ * Two new launches per call, whatever n is, both under the stage tag "voc.stream" with the bytes the single-session gathers would count in
+ *   sum: a gather builds the batch's mel rows from the sessions' resident mels, and a scatter moves every row's interior samples straight
+ *   behind the history of the owning session's first stage buffer (to that session's final destination where it has no stage).  Their
+ *   per-row tables (source mel pointer and frame count; source offset, count and destination pointer) are built on the host and uploaded
+ *   through the context's pinned staging, queued like a launch: no host wait.
+ * Post stages: each session's new samples then go through that session's own stages, one row and that session's window per call of the
+ *   internal _ex forms, exactly as in zvx_stream_next.  (Batching them across sessions needs per-row windows in those forms: not here.)
+ * One wait: host pieces travel through each session's pinned buffer -- all copies are queued, the call waits once, then copies out.  With
+ *   ZVX_DEVICE_OUT every out[i] is a device pointer; with ZVX_DEVICE_OUT | ZVX_NO_SYNC the call only queues.  Everything runs on the
+ *   context's main stream.  The context's intermediates are void afterwards, as after zvx_stream_next.
+ * All or nothing: every session's piece size is planned on copies of its planners before anything is queued, and every n_out[i] is always
+ *   filled.  If any capacity[i] < n_out[i] the call returns ZVX_E_BUFFER and NO session has consumed anything; the message names the first
+ *   such index and both numbers, and the same call with larger buffers yields the same bits.
+ * Validation, before anything is planned or queued.  ZVX_E_INVALID: a NULL sessions / capacity / n_out / done, n < 1, a NULL entry, the
+ *   same session twice, sessions of different contexts, a negative capacity, a NULL out array or a NULL out[i] where n_out[i] > 0, unknown
+ *   flags, ZVX_NO_SYNC without ZVX_DEVICE_OUT.  ZVX_E_STATE, with nothing consumed in any session: a session that is already done (the
+ *   message names the index).  ZVX_E_UNSUPPORTED: ZVX_PCM16, n > ZVX_STREAM_MANY_MAX_SESSIONS, more than ZVX_STREAM_MANY_MAX_ROWS rows in
+ *   total (the message names the count).  Errors are reported through zvx_last_error of the sessions' context (with NULL sessions, n < 1 or
+ *   no session at all among the entries there is none: the status alone).
+ * A HIP failure past the point where the groups are consumed ends EVERY session of the call (done), as it ends the one session of
+ *   zvx_stream_next. */
+enum { ZVX_STREAM_MANY_MAX_SESSIONS = 64, ZVX_STREAM_MANY_MAX_ROWS = 256 };
+zvx_status zvx_stream_next_many(zvx_stream* const* sessions, int n, void* const* out, const int64_t* capacity,
+                                int64_t* n_out, int32_t* done, int flags);
 
 /* Debug/parity taps: copy an intermediate of the last call to host fp32.
  * what: "encoder_out" [B][Tmax][hidden] (after the style add), "features" [B][Lmax][hidden],

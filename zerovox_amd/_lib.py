@@ -26,7 +26,8 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_dev_alloc", "zvx_dev_free", "zvx_dev_from_host", "zvx_dev_to_host", "zvx_spkemb_ex", "zvx_wait_host",
            "zvx_encode_ex", "zvx_synthesize_ex", "zvx_resample", "zvx_resample_ex", "zvx_trim_bounds", "zvx_join",
            "zvx_loudness", "zvx_normalize", "zvx_true_peak", "zvx_limit", "zvx_spkemb_wav", "zvx_limit_ex", "zvx_denoise_bias", "zvx_denoise",
-           "zvx_denoise_ex", "zvx_stream_open", "zvx_stream_next", "zvx_stream_info", "zvx_stream_close")
+           "zvx_denoise_ex", "zvx_stream_open", "zvx_stream_next", "zvx_stream_info", "zvx_stream_close", "zvx_stream_next_many")
+ZVX_STREAM_MANY_MAX_SESSIONS, ZVX_STREAM_MANY_MAX_ROWS = 64, 256
 ZVX_COMM_ID_BYTES = 128
 ZVX_LOUD_PER_ROW, ZVX_LOUD_COMMON = 0, 1
 LIMIT_TILE = 1024                                    # samples per workgroup of both limiter kernels (csrc/zvx_kernels.h, LIMIT_TILE)
@@ -153,6 +154,7 @@ def load():
     lib.zvx_stream_next.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int]
     lib.zvx_stream_info.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
     lib.zvx_stream_close.argtypes = [vp]
+    lib.zvx_stream_next_many.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int]
     _lib = lib
     return lib
 
@@ -581,6 +583,43 @@ class Context:
         h = C.c_void_p()
         self._chk(self._lib.zvx_stream_open(self._h, mptr, int(frames), C.byref(prm), int(flags), C.byref(h)))
         return Stream(self, h, keep)
+
+    def stream_next_many(self, streams, capacities=None):
+        """one zvx_stream_next_many into host memory: every session of ``streams`` (open sessions of this context) advances by one piece,
+        their groups vocoded as one batch -> the pieces in order (np.float32, possibly empty), each what the session's own next_piece()
+        would have returned; sets each Stream.done.  capacities: samples per buffer (None: each session's max_piece); one too small raises
+        ZvxError(ZVX_E_BUFFER) with nothing consumed in any session.  A ZvxError carries ``n_out`` as a list."""
+        streams = list(streams)
+        caps = [s.info()["max_piece"] for s in streams] if capacities is None else [int(v) for v in capacities]
+        if len(caps) != len(streams):
+            raise ValueError(f"stream_next_many: {len(caps)} capacities for {len(streams)} streams")
+        bufs = [np.empty(max(v, 1), np.float32) for v in caps]
+        n = self._stream_next_many(streams, [b.ctypes.data for b in bufs], caps, 0)
+        return [b[:k] for b, k in zip(bufs, n)]
+
+    def stream_next_many_device(self, streams, ptrs, capacities, no_sync=False):
+        """one zvx_stream_next_many into device memory at ``ptrs`` (ZVX_DEVICE_OUT; with no_sync the call only queues) -> samples written
+        per session"""
+        streams, ptrs, caps = list(streams), [int(p) for p in ptrs], [int(v) for v in capacities]
+        if not len(streams) == len(ptrs) == len(caps):
+            raise ValueError(f"stream_next_many_device: {len(streams)} streams, {len(ptrs)} pointers, {len(caps)} capacities")
+        return self._stream_next_many(streams, ptrs, caps, ZVX_DEVICE_OUT | (ZVX_NO_SYNC if no_sync else 0))
+
+    def _stream_next_many(self, streams, ptrs, caps, flags):
+        k = len(streams)
+        hs = (C.c_void_p * max(k, 1))(*[s._h for s in streams])
+        out = (C.c_void_p * max(k, 1))(*ptrs)
+        cap = (C.c_int64 * max(k, 1))(*caps)
+        n = (C.c_int64 * max(k, 1))(*([-1] * k))
+        done = (C.c_int32 * max(k, 1))()
+        rc = self._lib.zvx_stream_next_many(hs, k, out, cap, n, done, flags)
+        if rc != ZVX_OK:
+            e = ZvxError(rc, self._lib.zvx_last_error(self._h).decode())
+            e.n_out = [int(v) for v in n[:k]]
+            raise e
+        for s, d in zip(streams, done):
+            s.done = bool(d)
+        return [int(v) for v in n[:k]]
 
     def resample_device(self, ptr, n, rate_in, rate_out, pcm16=False):
         """zvx_resample of ONE device-resident row of n f32 samples (ZVX_DEVICE_IN) -> host row at rate_out"""

@@ -6,6 +6,8 @@
 // (in_origin, out_begin, out_count, keep_from): run the step on the retained samples [in_origin, received) for the outputs
 // [out_begin, out_begin + out_count) -- nothing to do when out_count is 0 -- then drop the history before keep_from.
 // Every position is an int64_t: a stream may run past 2^32 samples.
+// group_rows, at the end, is the arithmetic of one group's rows -- the frames with halo, the kept interior, the running position -- that
+// zvx_stream_next and zvx_stream_next_many share (tests/native/stream_group_main.cpp checks it against ZeroVox._vocode_stream_native).
 #ifndef ZVX_STREAM_PLAN_H
 #define ZVX_STREAM_PLAN_H
 
@@ -66,6 +68,29 @@ struct ResamplePlanner {
         return s;
     }
 };
+
+// The rows of one group (zvx_stream_next, zvx_stream_next_many): chunk number q starts at frame st = q chunk and is vocoded on the frames
+// [max(0, st - halo), min(frames, st + chunk + halo)) -- the rows ZeroVox._vocode_stream_native builds --; of the row's samples only the
+// interior [off, off + cnt) is kept, cnt = min(chunk, frames - st) hop, and lands at the running position pos of the group's new samples.
+struct Row { int64_t lo, P, off, cnt, pos; };
+struct Group { int first, rows, last; int64_t Pmax, cnt_max, n_new; };
+inline int chunk_count(int64_t frames, int64_t chunk) { return (int)((frames + chunk - 1) / chunk); }
+// the group that starts at chunk `next`: at most cpc chunks, fewer at the end; rows[] takes min(cpc, chunks left) entries
+inline Group group_rows(int64_t frames, int64_t chunk, int64_t halo, int64_t hop, int next, int cpc, Row* rows) {
+    const int nchunks = chunk_count(frames, chunk);
+    Group g{next, 0, 0, 0, 0, 0};
+    g.rows = (int)imin(cpc, nchunks - next);
+    if (g.rows < 0) g.rows = 0;
+    g.last = next + g.rows == nchunks ? 1 : 0;
+    for (int i = 0; i < g.rows; i++) {
+        const int64_t st = (int64_t)(next + i) * chunk;
+        const int64_t lo = imax(0, st - halo), hi = imin(frames, st + chunk + halo);
+        const int64_t n = imin(chunk, frames - st);
+        rows[i] = Row{lo, hi - lo, (st - lo) * hop, n * hop, g.n_new};
+        g.Pmax = imax(g.Pmax, hi - lo); g.cnt_max = imax(g.cnt_max, n * hop); g.n_new += n * hop;
+    }
+    return g;
+}
 
 }  // namespace zvx_plan
 #endif /* ZVX_STREAM_PLAN_H */

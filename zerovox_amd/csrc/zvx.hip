@@ -2965,92 +2965,120 @@ void do_stream_open(zvx_ctx* c, const float* mel, int frames, const zvx_stream_p
     *out = s;
 }
 
+// the checks every stepping call makes on its flags (zvx_stream_next, zvx_stream_next_many)
+void stream_flags_check(const char* who, int flags) {
+    if (flags & ~(ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16)) fail(ZVX_E_INVALID, "%s: unknown flag in %d", who, flags);
+    if (flags & ZVX_PCM16) fail(ZVX_E_UNSUPPORTED, "%s: a session hands out f32 pieces (no ZVX_PCM16)", who);
+    if ((flags & ZVX_NO_SYNC) && !(flags & ZVX_DEVICE_OUT)) fail(ZVX_E_INVALID, "%s: ZVX_NO_SYNC needs ZVX_DEVICE_OUT", who);
+}
+
+// What a session's next step does, worked out before anything is queued: the group's rows (stream_plan.h) and the stages' windows on
+// COPIES of the planners -- host integer arithmetic, so the piece's size n is known up front and a refused call has consumed nothing.
+struct StreamStep {
+    zvx_plan::Group g{};
+    zvx_plan::Row rows[STREAM_MAX_ROWS];
+    int P[STREAM_MAX_ROWS];
+    std::vector<zvx_stream::Stage> plan;
+    std::vector<zvx_plan::Step> steps;
+    int64_t n = 0;                         // the piece's samples at the session's output rate
+};
+void stream_plan_step(const char* who, const zvx_stream* s, StreamStep& p) {
+    // ---- the group: chunk st is vocoded on frames [max(0, st - halo), min(frames, st + chunk + halo)), its interior kept
+    p.g = zvx_plan::group_rows(s->frames, s->chunk, s->halo, s->hop, s->next_chunk, s->cpc, p.rows);
+    for (int i = 0; i < p.g.rows; i++) p.P[i] = (int)p.rows[i].P;
+    if (p.g.Pmax > s->Pcap) fail(ZVX_E_STATE, "%s: a row of %d frames exceeds the session's %d", who, (int)p.g.Pmax, s->Pcap);
+    // ---- the plan, on copies of the planners
+    const size_t K = s->stages.size();
+    p.plan = s->stages;
+    p.steps.resize(K);
+    int64_t n = p.g.n_new;
+    for (size_t k = 0; k < K; k++) {
+        p.steps[k] = p.plan[k].push(n, p.g.last != 0);
+        const int64_t held = p.plan[k].hist + n;
+        if (held != p.plan[k].received() - p.steps[k].in_origin || held > p.plan[k].cap)
+            fail(ZVX_E_STATE, "%s: stage %zu holds %lld samples (buffer %lld, window from %lld)", who, k, (long long)held, (long long)p.plan[k].cap, (long long)p.steps[k].in_origin);
+        n = p.steps[k].out_count;
+    }
+    p.n = n;
+    if (n > s->max_piece) fail(ZVX_E_STATE, "%s: a piece of %lld samples exceeds max_piece %lld", who, (long long)n, (long long)s->max_piece);
+}
+// where the group's new samples go: straight behind the history of the first stage's buffer, or the piece's destination without a stage
+float* stream_new_dst(zvx_stream* s, float* final_dst) {
+    return s->stages.empty() ? final_dst : s->stages[0].buf[s->stages[0].cur] + s->stages[0].hist;
+}
+// The session's own stages over its new samples (B = 1, the windows of the plan), then the session's state: what every stepping call runs
+// behind the gather of the interiors.
+void stream_run_stages(const char* who, zvx_stream* s, const StreamStep& p, float* final_dst) {
+    zvx_ctx* c = s->c;
+    const size_t K = s->stages.size();
+    const bool last = p.g.last != 0;
+    const int f = ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC;
+    int64_t n_in = p.g.n_new;
+    for (size_t k = 0; k < K; k++) {
+        zvx_stream::Stage& st = s->stages[k];
+        const zvx_plan::Step& sp = p.steps[k];
+        const int64_t held = st.hist + n_in;
+        const float* in = st.buf[st.cur];
+        float* dst = k + 1 < K ? s->stages[k + 1].buf[s->stages[k + 1].cur] + s->stages[k + 1].hist : final_dst;
+        if (sp.out_count > 0 && held > 0) {
+            const int32_t n32 = (int32_t)held;
+            const int64_t stride = std::max(held, sp.out_count);
+            const RowsWindow w{sp.in_origin, sp.out_begin, sp.out_count, last ? 1 : 0};
+            if (st.kind == zvx_stream::DENOISE) do_denoise(c, who, in, &n32, 1, n32, s->bias.data(), &s->dn, dst, stride, f, &w);
+            else if (st.kind == zvx_stream::LIMIT) do_limit(c, who, in, &n32, 1, n32, s->native, &s->lim, 0, dst, stride, nullptr, nullptr, f, &w);
+            else do_resample(c, in, &n32, 1, n32, s->native, s->out_rate, dst, stride, nullptr, f, sp.in_origin, sp.out_begin, sp.out_count);
+        }
+        const int64_t drop = sp.keep_from - sp.in_origin, keep = held - drop;
+        if (drop > 0) {                                  // into the other buffer: never an overlapping copy
+            if (keep > 0) HIPCHK(hipMemcpyAsync(st.buf[st.cur ^ 1], in + drop, (size_t)keep * 4, hipMemcpyDeviceToDevice, c->stream));
+            st.cur ^= 1;
+        }
+        st.hist = keep; st.reach = p.plan[k].reach; st.rate = p.plan[k].rate;
+        n_in = sp.out_count;
+    }
+    s->next_chunk = p.g.first + p.g.rows; s->emitted += p.n; s->done = last ? 1 : 0;
+}
+
 void do_stream_next(zvx_stream* s, void* out, int64_t capacity, int64_t* n_out, int32_t* done, int flags) {
     const char* who = "zvx_stream_next";
     zvx_ctx* c = s->c;
     if (!n_out || !done) fail(ZVX_E_INVALID, "%s: %s is NULL", who, !n_out ? "n_out" : "done");
-    if (flags & ~(ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16)) fail(ZVX_E_INVALID, "%s: unknown flag in %d", who, flags);
-    if (flags & ZVX_PCM16) fail(ZVX_E_UNSUPPORTED, "%s: a session hands out f32 pieces (no ZVX_PCM16)", who);
-    if ((flags & ZVX_NO_SYNC) && !(flags & ZVX_DEVICE_OUT)) fail(ZVX_E_INVALID, "%s: ZVX_NO_SYNC needs ZVX_DEVICE_OUT", who);
+    stream_flags_check(who, flags);
     if (capacity < 0) fail(ZVX_E_INVALID, "%s: capacity %lld is negative", who, (long long)capacity);
     if (s->done) fail(ZVX_E_STATE, "%s: the stream is done (its last piece has been handed out)", who);
-    // ---- the group: chunk st is vocoded on frames [max(0, st - halo), min(frames, st + chunk + halo)), its interior kept
-    const int g0 = s->next_chunk, g1 = std::min(s->nchunks, g0 + s->cpc), B = g1 - g0, nm = c->n_mels;
-    const bool last = g1 == s->nchunks;
-    StreamRowsArgs ra{};
-    StreamInteriorArgs ia{};
-    int P[STREAM_MAX_ROWS];
-    int Pmax = 0; long cnt_max = 0; int64_t n_new = 0;
-    for (int i = 0; i < B; i++) {
-        const int64_t st = (int64_t)(g0 + i) * s->chunk;
-        const int64_t lo = std::max<int64_t>(0, st - s->halo), hi = std::min<int64_t>(s->frames, st + s->chunk + s->halo);
-        const int64_t n = std::min<int64_t>(s->chunk, s->frames - st);
-        P[i] = (int)(hi - lo); Pmax = std::max(Pmax, P[i]);
-        ra.lo[i] = (int)lo; ra.P[i] = P[i];
-        ia.off[i] = (int)((st - lo) * s->hop); ia.cnt[i] = (int)(n * s->hop); ia.pos[i] = (long)n_new;
-        cnt_max = std::max<long>(cnt_max, ia.cnt[i]); n_new += n * s->hop;
-    }
-    if (Pmax > s->Pcap) fail(ZVX_E_STATE, "%s: a row of %d frames exceeds the session's %d", who, Pmax, s->Pcap);
-    // ---- the plan, on copies of the planners: host integer arithmetic, so the piece's size is known before anything is queued
-    const size_t K = s->stages.size();
-    std::vector<zvx_stream::Stage> plan(s->stages);
-    std::vector<zvx_plan::Step> steps(K);
-    int64_t n = n_new;
-    for (size_t k = 0; k < K; k++) {
-        steps[k] = plan[k].push(n, last);
-        const int64_t held = plan[k].hist + n;
-        if (held != plan[k].received() - steps[k].in_origin || held > plan[k].cap)
-            fail(ZVX_E_STATE, "%s: stage %zu holds %lld samples (buffer %lld, window from %lld)", who, k, (long long)held, (long long)plan[k].cap, (long long)steps[k].in_origin);
-        n = steps[k].out_count;
-    }
+    StreamStep p;
+    stream_plan_step(who, s, p);
+    const int B = p.g.rows, nm = c->n_mels, Pmax = (int)p.g.Pmax;
+    const int64_t n = p.n, n_new = p.g.n_new;
     *n_out = n;
-    if (n > s->max_piece) fail(ZVX_E_STATE, "%s: a piece of %lld samples exceeds max_piece %lld", who, (long long)n, (long long)s->max_piece);
     if (n > 0 && !out) fail(ZVX_E_INVALID, "%s: out is NULL", who);
     if (capacity < n) fail(ZVX_E_BUFFER, "%s: capacity %lld < %lld samples of this piece (nothing was consumed)", who, (long long)capacity, (long long)n);
     // ---- from here on the call consumes the group; a failure past this point ends the session
     try {
         c->have_features = false; c->have_mel = false;      // as zvx_vocode_mel: the context's intermediates are void
+        StreamRowsArgs ra{};
+        StreamInteriorArgs ia{};
+        for (int i = 0; i < B; i++) {
+            ra.lo[i] = (int)p.rows[i].lo; ra.P[i] = p.P[i];
+            ia.off[i] = (int)p.rows[i].off; ia.cnt[i] = (int)p.rows[i].cnt; ia.pos[i] = (long)p.rows[i].pos;
+        }
         ra.mel = s->mel; ra.out = s->rows; ra.B = B; ra.Pmax = Pmax; ra.nm = nm;
         {
             TagScope scope(c, "voc.stream");
-            double rd = 0; for (int i = 0; i < B; i++) rd += (double)P[i] * nm * 4.0;
+            double rd = 0; for (int i = 0; i < B; i++) rd += (double)p.P[i] * nm * 4.0;
             c->timed(0.0, rd + (double)B * Pmax * nm * 4.0, [&] { launch_stream_rows(ra, c->stream); });
         }
         c->stage_begin(ZVX_T_VOCODER);
-        run_vocoder(c, s->rows, nm, Pmax, P, P, B, s->wav, s->wstride, 0);       // the rows of ZeroVox._vocode_stream_native, at the native rate
+        run_vocoder(c, s->rows, nm, Pmax, p.P, p.P, B, s->wav, s->wstride, 0);   // the rows of ZeroVox._vocode_stream_native, at the native rate
         c->stage_end(ZVX_T_VOCODER);
         float* final_dst = (flags & ZVX_DEVICE_OUT) ? (float*)out : s->ostage;
         ia.wav = s->wav; ia.w_bs = s->wstride; ia.B = B;
-        ia.out = K ? s->stages[0].buf[s->stages[0].cur] + s->stages[0].hist : final_dst;
+        ia.out = stream_new_dst(s, final_dst);
         {
             TagScope scope(c, "voc.stream");
-            c->timed(0.0, 8.0 * (double)n_new, [&] { launch_stream_interiors(ia, cnt_max, c->stream); });
+            c->timed(0.0, 8.0 * (double)n_new, [&] { launch_stream_interiors(ia, (long)p.g.cnt_max, c->stream); });
         }
-        const int f = ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC;
-        int64_t n_in = n_new;
-        for (size_t k = 0; k < K; k++) {
-            zvx_stream::Stage& st = s->stages[k];
-            const zvx_plan::Step& sp = steps[k];
-            const int64_t held = st.hist + n_in;
-            const float* in = st.buf[st.cur];
-            float* dst = k + 1 < K ? s->stages[k + 1].buf[s->stages[k + 1].cur] + s->stages[k + 1].hist : final_dst;
-            if (sp.out_count > 0 && held > 0) {
-                const int32_t n32 = (int32_t)held;
-                const int64_t stride = std::max(held, sp.out_count);
-                const RowsWindow w{sp.in_origin, sp.out_begin, sp.out_count, last ? 1 : 0};
-                if (st.kind == zvx_stream::DENOISE) do_denoise(c, who, in, &n32, 1, n32, s->bias.data(), &s->dn, dst, stride, f, &w);
-                else if (st.kind == zvx_stream::LIMIT) do_limit(c, who, in, &n32, 1, n32, s->native, &s->lim, 0, dst, stride, nullptr, nullptr, f, &w);
-                else do_resample(c, in, &n32, 1, n32, s->native, s->out_rate, dst, stride, nullptr, f, sp.in_origin, sp.out_begin, sp.out_count);
-            }
-            const int64_t drop = sp.keep_from - sp.in_origin, keep = held - drop;
-            if (drop > 0) {                                  // into the other buffer: never an overlapping copy
-                if (keep > 0) HIPCHK(hipMemcpyAsync(st.buf[st.cur ^ 1], in + drop, (size_t)keep * 4, hipMemcpyDeviceToDevice, c->stream));
-                st.cur ^= 1;
-            }
-            st.hist = keep; st.reach = plan[k].reach; st.rate = plan[k].rate;
-            n_in = sp.out_count;
-        }
-        s->next_chunk = g1; s->emitted += n; s->done = last ? 1 : 0;
+        stream_run_stages(who, s, p, final_dst);
         *done = s->done;
         if (!(flags & ZVX_DEVICE_OUT)) {
             if (n > 0) HIPCHK(hipMemcpyAsync(s->pinned, s->ostage, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
@@ -3059,6 +3087,104 @@ void do_stream_next(zvx_stream* s, void* out, int64_t capacity, int64_t* n_out, 
         } else if (!(flags & ZVX_NO_SYNC)) c->sync();
     } catch (...) {
         s->done = 1;
+        throw;
+    }
+}
+
+// zvx_stream_next_many (include/zvx.h): the groups of n sessions of one context as ONE batch of the vocoder.  Per session it is
+// do_stream_next -- the same plan, the same stages, the same state afterwards --; what differs is that the rows of all sessions are
+// gathered by one launch, vocoded by one run_vocoder and scattered by one launch to where each session's first stage reads them.
+void do_stream_next_many(zvx_ctx* c, zvx_stream* const* ss, int n, void* const* out, const int64_t* capacity, int64_t* n_out, int32_t* done,
+                         int flags) {
+    const char* who = "zvx_stream_next_many";
+    // ---- every check, before anything is planned or queued
+    if (!capacity || !n_out || !done) fail(ZVX_E_INVALID, "%s: %s is NULL", who, !capacity ? "capacity" : !n_out ? "n_out" : "done");
+    stream_flags_check(who, flags);
+    if (n > STREAM_MANY_MAX_SESSIONS) fail(ZVX_E_UNSUPPORTED, "%s: %d sessions (at most %d per call)", who, n, STREAM_MANY_MAX_SESSIONS);
+    for (int i = 0; i < n; i++) {
+        if (!ss[i]) fail(ZVX_E_INVALID, "%s: sessions[%d] is NULL", who, i);
+        if (ss[i]->c != c) fail(ZVX_E_INVALID, "%s: sessions[%d] belongs to another context than sessions[0]", who, i);
+        for (int j = 0; j < i; j++) if (ss[j] == ss[i]) fail(ZVX_E_INVALID, "%s: sessions[%d] and sessions[%d] are the same session", who, j, i);
+        if (capacity[i] < 0) fail(ZVX_E_INVALID, "%s: capacity[%d] %lld is negative", who, i, (long long)capacity[i]);
+    }
+    for (int i = 0; i < n; i++)
+        if (ss[i]->done) fail(ZVX_E_STATE, "%s: sessions[%d] is done (its last piece has been handed out; nothing was consumed)", who, i);
+    // ---- the plans of all sessions: every piece's size is known before anything is queued
+    std::vector<StreamStep> plans((size_t)n);
+    int R = 0;
+    for (int i = 0; i < n; i++) R += std::min(ss[i]->cpc, ss[i]->nchunks - ss[i]->next_chunk);
+    if (R > STREAM_MANY_MAX_ROWS) fail(ZVX_E_UNSUPPORTED, "%s: the groups of %d sessions are %d rows (at most %d per call)", who, n, R, STREAM_MANY_MAX_ROWS);
+    int Pmax = 0; long cnt_max = 0; double rows_bytes = 0, new_bytes = 0;
+    const int nm = c->n_mels, hop = c->hop;
+    for (int i = 0; i < n; i++) {
+        StreamStep& p = plans[(size_t)i];
+        stream_plan_step(who, ss[i], p);
+        n_out[i] = p.n;
+        Pmax = std::max(Pmax, (int)p.g.Pmax); cnt_max = std::max(cnt_max, (long)p.g.cnt_max);
+        for (int j = 0; j < p.g.rows; j++) rows_bytes += (double)p.P[j] * nm * 4.0;        // what the single-session gathers count
+        rows_bytes += (double)p.g.rows * (double)p.g.Pmax * nm * 4.0;
+        new_bytes += 8.0 * (double)p.g.n_new;
+    }
+    if ((int64_t)R * Pmax * std::max(hop, nm) > (int64_t)1 << 28)
+        fail(ZVX_E_UNSUPPORTED, "%s: %d rows of %d frames are %lld samples (at most 2^28 per call)", who, R, Pmax, (long long)R * Pmax * hop);
+    for (int i = 0; i < n; i++)
+        if (n_out[i] > 0 && (!out || !out[i])) fail(ZVX_E_INVALID, "%s: %s is NULL", who, !out ? "out" : ("out[" + std::to_string(i) + "]").c_str());
+    for (int i = 0; i < n; i++)
+        if (capacity[i] < n_out[i])
+            fail(ZVX_E_BUFFER, "%s: capacity[%d] %lld < %lld samples of this piece (nothing was consumed in any session)", who, i,
+                 (long long)capacity[i], (long long)n_out[i]);
+    // ---- from here on the call consumes the groups; a failure past this point ends every session of the call
+    try {
+        c->have_features = false; c->have_mel = false;      // as zvx_vocode_mel: the context's intermediates are void
+        const long wstride = ((long)Pmax * hop + 7) & ~7L;
+        // (the table's buffer is taken at its largest size at once: it never grows behind a queued call)
+        char* tab_d = (char*)c->buf("stream.tab", (size_t)STREAM_MANY_MAX_ROWS * (sizeof(StreamManyRow) + sizeof(StreamManyInterior)));
+        float* rows_d = c->fbuf("stream.rows", (size_t)R * Pmax * nm);
+        float* wav_d = c->fbuf("stream.wav", (size_t)R * wstride);
+        std::vector<char> tab((size_t)R * (sizeof(StreamManyRow) + sizeof(StreamManyInterior)));
+        StreamManyRow* tr = (StreamManyRow*)tab.data();
+        StreamManyInterior* ti = (StreamManyInterior*)(tab.data() + (size_t)R * sizeof(StreamManyRow));
+        std::vector<int> P((size_t)R);
+        std::vector<float*> final_dst((size_t)n);
+        int r = 0;
+        for (int i = 0; i < n; i++) {
+            zvx_stream* s = ss[i];
+            const StreamStep& p = plans[(size_t)i];
+            final_dst[(size_t)i] = (flags & ZVX_DEVICE_OUT) ? (float*)out[i] : s->ostage;
+            float* base = stream_new_dst(s, final_dst[(size_t)i]);
+            for (int j = 0; j < p.g.rows; j++, r++) {
+                P[(size_t)r] = p.P[j];
+                tr[r] = StreamManyRow{s->mel + p.rows[j].lo * nm, p.P[j], 0};
+                ti[r] = StreamManyInterior{base + p.rows[j].pos, (int)p.rows[j].off, (int)p.rows[j].cnt};
+            }
+        }
+        c->upload(tab_d, tab.data(), tab.size());
+        StreamManyRowsArgs ra{(const StreamManyRow*)tab_d, rows_d, R, Pmax, nm};
+        StreamManyInteriorArgs ia{(const StreamManyInterior*)(tab_d + (size_t)R * sizeof(StreamManyRow)), wav_d, wstride, R};
+        {
+            TagScope scope(c, "voc.stream");
+            c->timed(0.0, rows_bytes, [&] { launch_stream_rows_many(ra, c->stream); });
+        }
+        c->stage_begin(ZVX_T_VOCODER);
+        run_vocoder(c, rows_d, nm, Pmax, P.data(), P.data(), R, wav_d, wstride, 0);       // ONE batch: the rows of every session, at the native rate
+        c->stage_end(ZVX_T_VOCODER);
+        {
+            TagScope scope(c, "voc.stream");
+            c->timed(0.0, new_bytes, [&] { launch_stream_interiors_many(ia, cnt_max, c->stream); });
+        }
+        for (int i = 0; i < n; i++) {
+            stream_run_stages(who, ss[i], plans[(size_t)i], final_dst[(size_t)i]);
+            done[i] = ss[i]->done;
+        }
+        if (!(flags & ZVX_DEVICE_OUT)) {
+            for (int i = 0; i < n; i++)
+                if (n_out[i] > 0) HIPCHK(hipMemcpyAsync(ss[i]->pinned, ss[i]->ostage, (size_t)n_out[i] * 4, hipMemcpyDeviceToHost, c->stream));
+            c->sync();                                       // the call's one wait
+            for (int i = 0; i < n; i++)
+                if (n_out[i] > 0) memcpy(out[i], ss[i]->pinned, (size_t)n_out[i] * 4);
+        } else if (!(flags & ZVX_NO_SYNC)) c->sync();
+    } catch (...) {
+        for (int i = 0; i < n; i++) ss[i]->done = 1;
         throw;
     }
 }
@@ -3423,6 +3549,14 @@ zvx_status zvx_stream_open(zvx_ctx* c, const float* mel, int frames, const zvx_s
 zvx_status zvx_stream_next(zvx_stream* s, void* out, int64_t capacity, int64_t* n_out, int32_t* done, int flags) {
     if (!s) return ZVX_E_INVALID;
     return guarded(s->c, [&] { do_stream_next(s, out, capacity, n_out, done, flags); });
+}
+
+zvx_status zvx_stream_next_many(zvx_stream* const* sessions, int n, void* const* out, const int64_t* capacity, int64_t* n_out, int32_t* done,
+                                int flags) {
+    if (!sessions || n < 1) return ZVX_E_INVALID;
+    zvx_ctx* c = nullptr;                                    // errors are reported through the sessions' context: the first session names it
+    for (int i = 0; i < n && i < STREAM_MANY_MAX_SESSIONS && !c; i++) if (sessions[i]) c = sessions[i]->c;
+    return guarded(c, [&] { do_stream_next_many(c, sessions, n, out, capacity, n_out, done, flags); });
 }
 
 zvx_status zvx_stream_info(const zvx_stream* s, int64_t* info, int n_info) {

@@ -394,6 +394,19 @@ struct StreamInteriorArgs {
     int off[STREAM_MAX_ROWS], cnt[STREAM_MAX_ROWS]; long pos[STREAM_MAX_ROWS];
 };
 void launch_stream_interiors(const StreamInteriorArgs& a, long cnt_max, hipStream_t s);
+// The same for the rows of many sessions at once (zvx_stream_next_many: up to STREAM_MANY_MAX_ROWS rows, each with a source / destination
+// POINTER of its own): the tables no longer fit the kernel arguments and live in device memory, built on the host and uploaded through the
+// context's pinned arena (queued like a launch, no host wait).  One 16-byte entry per row.
+constexpr int STREAM_MANY_MAX_SESSIONS = 64;  // ZVX_STREAM_MANY_MAX_SESSIONS
+constexpr int STREAM_MANY_MAX_ROWS = 256;     // ZVX_STREAM_MANY_MAX_ROWS
+// Rows: row r of out [R][Pmax][nm] = the P frames at src ([P][nm], inside the owning session's mel), then zeros up to Pmax frames.
+struct StreamManyRow { const float* src; int P; int pad_; };
+struct StreamManyRowsArgs { const StreamManyRow* tab; float* out; int R, Pmax, nm; };
+void launch_stream_rows_many(const StreamManyRowsArgs& a, hipStream_t s);
+// Interiors: dst[i] = wav[r][off + i] for i < cnt; dst lies in memory of the owning session (or is the caller's), rows of one session back to back.
+struct StreamManyInterior { float* dst; int off, cnt; };
+struct StreamManyInteriorArgs { const StreamManyInterior* tab; const float* wav; long w_bs; int R; };
+void launch_stream_interiors_many(const StreamManyInteriorArgs& a, long cnt_max, hipStream_t s);
 // Integrated loudness (ITU-R BS.1770 / EBU R128) and gain of a batch's waveform rows (include/zvx.h, zvx_loudness / zvx_normalize): every
 // decision is made on the DEVICE, in double, in the power domain.
 // K-weighting: two biquads in transposed direct form II, double state.  Stage 1 b0..b2, a1, a2; stage 2 has b = [1, -2, 1].

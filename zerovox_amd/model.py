@@ -265,6 +265,24 @@ class ZeroVox:
         yield from self._ctx.stream_open(mel, chunk_frames=chunk_frames, chunks_per_call=max(1, chunks_per_call), halo=halo, denoise=denoise,
                                          bias=bias, limit=limiter)
 
+    def vocode_stream_many(self, mels, chunk_frames=64, halo=STREAM_HALO, chunks_per_call=1, limiter=None, denoise=None):
+        """Many utterances streamed together: mels, a list of [L_i, n_mels] arrays -> yields (index, piece) with non-empty float32 pieces
+        only.  One stream session per mel (the keywords of ``vocode_stream``), all stepped by one zvx_stream_next_many per round
+        (zerovox_amd.serve.StreamBatcher): the chunks of every utterance ride through the vocoder as one batch.  The pieces of index i
+        concatenate bit for bit to ``vocode_stream(mels[i], ..., resident=True)``."""
+        from .serve import StreamBatcher
+        bias = self.denoise_bias if denoise is not None else None           # (first use runs the vocoder: before the sessions open)
+        batcher = StreamBatcher(self._ctx)
+        try:
+            index = {batcher.open(np.asarray(m, np.float32), chunk_frames=chunk_frames, chunks_per_call=max(1, chunks_per_call), halo=halo,
+                                  denoise=denoise, bias=bias, limit=limiter): i for i, m in enumerate(mels)}
+            while len(batcher):
+                for id_, piece, _ in batcher.step():
+                    if len(piece):
+                        yield index[id_], piece
+        finally:
+            batcher.close_all()
+
     def _vocode_stream_native(self, mel, chunk_frames, halo, chunks_per_call, native_rate):
         mel = np.asarray(mel, np.float32)
         L, hop = mel.shape[0], self._hop_length

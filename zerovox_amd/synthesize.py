@@ -287,6 +287,13 @@ class ZeroVoxTTS:
         resident: False (the default: the stream is planned on the host), or True: a stream session of the library runs it (include/zvx.h,
         zvx_stream_open; ZeroVox.vocode_stream(resident=True)) -- the decoder's mel never leaves the device and every piece costs one
         wait.  The concatenation is the same to the bit; the pieces may be cut elsewhere."""
+        prosody, lim, den = self._stream_keywords(speed, pitch_shift, pitch_range, energy_shift, energy_range, loudness, limiter, peak_db,
+                                                  limiter_ms, denoise, denoise_strength)
+        return self._tts_stream(text, spkemb, chunk_frames, chunks_per_call, prosody, lim, den, resident)
+
+    def _stream_keywords(self, speed, pitch_shift, pitch_range, energy_shift, energy_range, loudness, limiter, peak_db, limiter_ms, denoise,
+                         denoise_strength):
+        """the checks of tts_stream's keywords -> (prosody, limiter keywords or None, denoiser keywords or None)"""
         if denoise is not None:
             raise ValueError("tts_stream does not take denoise=: pass denoise_strength=<strength> (the stream is then denoised window by window, "
                              "n_fft - 1 samples behind the vocoder); denoise= is the whole-utterance keyword of tts and tts_long")
@@ -301,8 +308,45 @@ class ZeroVoxTTS:
             if not np.isfinite(peak_db):
                 raise ValueError(f"tts_stream: peak_db must be finite, not {peak_db}")
             lim = self._limiter(True, limiter_ms, peak_db)
-        return self._tts_stream(text, spkemb, chunk_frames, chunks_per_call, self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range),
-                                lim, den, resident)
+        return self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range), lim, den
+
+    def tts_stream_many(self, texts, spkembs, chunk_frames=64, chunks_per_call=1, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0,
+                        energy_shift=0.0, energy_range=1.0, loudness=None, limiter=False, peak_db=None, limiter_ms=5.0, denoise=None,
+                        denoise_strength=None, max_frames=2048):
+        """Many texts streamed together -> yields (index, piece), non-empty float32 pieces only; the stream keywords are those of
+        ``tts_stream`` and apply to every text.  spkembs: one embedding per text ([B, hidden]), or one for all.  The front end runs as ONE
+        batch (``synthesize_batch(want_mel=True)``, at most max_frames mel frames per text), one stream session is opened on every mel,
+        and each round steps all of them with one zvx_stream_next_many (``ZeroVox.vocode_stream_many``): the chunks of all texts ride
+        through the vocoder as one batch.  The pieces of index i concatenate bit for bit to ``vocode_stream(mel_i, ..., resident=True)``
+        on the mel the batch made for text i (``last_stream_mels[i]``).  A text without phonemes yields nothing."""
+        prosody, lim, den = self._stream_keywords(speed, pitch_shift, pitch_range, energy_shift, energy_range, loudness, limiter, peak_db,
+                                                  limiter_ms, denoise, denoise_strength)
+        return self._tts_stream_many(list(texts), spkembs, chunk_frames, chunks_per_call, prosody, lim, den, int(max_frames))
+
+    def _tts_stream_many(self, texts, spkembs, chunk_frames, chunks_per_call, prosody, limiter, denoise, max_frames):
+        ids = [self.text2phonemeids(t.strip()) for t in texts]
+        keep = [i for i, (ph, _) in enumerate(ids) if ph]
+        self.last_stream_mels = {}
+        if not keep:
+            return
+        spk = np.asarray(spkembs, np.float32)
+        spk = np.repeat(spk.reshape(1, -1), len(texts), axis=0) if spk.size == spk.shape[-1] else spk.reshape(len(texts), -1)
+        B, Tmax = len(keep), max(len(ids[i][0]) for i in keep)
+        phoneme, puncts = np.zeros((B, Tmax), np.int32), np.zeros((B, Tmax), np.int32)
+        T = np.array([len(ids[i][0]) for i in keep], np.int32)
+        for b, i in enumerate(keep):
+            phoneme[b, :T[b]], puncts[b, :T[b]] = ids[i]
+        if denoise is not None:
+            self._model.denoise_bias                                 # (first use runs the vocoder: before this call's front end)
+        r = self._model.synthesize_batch(phoneme, puncts, T, spk[keep], want_mel=True, Lmax_cap=max_frames, prosody=prosody)
+        ml = [int(v) for v in r["mel_len"]]
+        if min(ml) < 2:
+            raise ValueError(f"predicted mel length {min(ml)} is too short to synthesise")
+        mels = [np.ascontiguousarray(r["mel"][b, :ml[b]]) for b in range(B)]
+        self.last_stream_mels = {i: mels[b] for b, i in enumerate(keep)}
+        for b, piece in self._model.vocode_stream_many(mels, chunk_frames=chunk_frames, chunks_per_call=chunks_per_call, limiter=limiter,
+                                                       denoise=denoise):
+            yield keep[b], piece
 
     def _tts_stream(self, text, spkemb, chunk_frames, chunks_per_call, prosody, limiter=None, denoise=None, resident=False):
         text = text.strip()
