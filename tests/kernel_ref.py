@@ -11,6 +11,18 @@ is derived per element from the data:
 Fused ResBlock kernels add the propagated term of their 16-bit intermediate (one ulp of it wherever its rounding is ambiguous
 within the fp32 bound, through |W2| and the residual),
 the 16-bit flash attention the term of its 16-bit probabilities.
+
+The streaming ResBlock kernels (launch_resstream with StreamArgs, launch_narrowstage with StageArgs, launch_pairstream past one
+segment) chain up to 18 convolutions through 16-bit intermediates; `chain_ref` (last section of this file) steps them in float64
+with every 16-bit rounding where the kernel has it and propagates a per-element uncertainty: through |W|, through each 16-bit
+rounding as Q(v + e) - Q(v - e), and through the two leaky-relus by their slope only where the sign is certain.  On exact-sum
+data (every f32 partial sum exact, decided per element with exact_f32's rule) only element-wise f32 roundings remain, and the
+tolerance of most elements is ZERO: the kernel must produce the reference's 16-bit value bit for bit.  That rests on one
+premise -- a matrix instruction returns an exactly representable block sum exactly.  The 32 x 32 x 16 cases of GEMM_CASES have held
+the kernels to it; for the 16 x 16 x 32 instruction of narrowstage nothing in the repository had measured it before
+NARROW_CASES (results: profiles/stream_kernel_spec.txt).  Dense data, which sparse weights cannot replace for a misplaced weight
+fragment, is checked by bit equality with the per-pair launches (resstream) or by rms against the pure float64 chain
+(narrowstage, pairstream: rms_margin).
 """
 import ctypes
 import os
@@ -134,7 +146,20 @@ class AttnF32Args(ctypes.Structure):
                 ("scale", _f)]
 
 
-STRUCTS = {"GemmArgs": GemmArgs, "FlashArgs": FlashArgs, "AttnF32Args": AttnF32Args}
+class StreamArgs(ctypes.Structure):
+    _fields_ = [("X", _p), ("x_bs", _l), ("ldx", _i), ("W1", _p * 3), ("W2", _p * 3), ("b1", _p * 3), ("b2", _p * 3), ("dil", _i * 3), ("C", _i),
+                ("ntaps", _i), ("npair", _i), ("out", _p), ("o_bs", _l), ("ldo", _i), ("accum", _p), ("a_bs", _l), ("lda", _i), ("accum_mode", _i),
+                ("slope1", _f), ("res_inv_slope", _f), ("out_scale", _f), ("slope", _f), ("len", _p), ("M", _i), ("nbatch", _i), ("S", _i),
+                ("nseg", _i), ("dX0", _i), ("dT", _i), ("dX", _i * 3), ("flops", ctypes.c_double), ("prof", _p), ("seg_min", _i), ("f16", _i)]
+
+
+class StageArgs(ctypes.Structure):
+    _fields_ = [("X", _p), ("x_bs", _l), ("ldx", _i), ("W", _p), ("woff", _i * 18), ("bias", _p), ("C", _i), ("nk", _i), ("ks", _i * 3),
+                ("dil", (_i * 3) * 3), ("out", _p), ("o_bs", _l), ("ldo", _i), ("slope1", _f), ("res_inv_slope", _f), ("slope", _f),
+                ("len", _p), ("M", _i), ("nbatch", _i), ("f16", _i)]
+
+
+STRUCTS = {"GemmArgs": GemmArgs, "FlashArgs": FlashArgs, "AttnF32Args": AttnF32Args, "StreamArgs": StreamArgs, "StageArgs": StageArgs}
 
 
 def load_ktest():
@@ -154,6 +179,10 @@ def load_ktest():
     lib.zvxk_pack_pair.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     lib.zvxk_flash.argtypes = [ctypes.POINTER(FlashArgs), ctypes.c_int]
     lib.zvxk_attn_f32.argtypes = [ctypes.POINTER(AttnF32Args), ctypes.c_int]
+    lib.zvxk_resstream.argtypes = [ctypes.POINTER(StreamArgs), ctypes.c_int]
+    lib.zvxk_narrowstage.argtypes = [ctypes.POINTER(StageArgs), ctypes.c_int]
+    lib.zvxk_pack_narrow.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
+    lib.zvxk_narrowstage_steps.argtypes = [ctypes.c_int, ctypes.c_int]
     lib.zvxk_variant_name.restype = ctypes.c_char_p
     lib.zvxk_sizeof.restype = ctypes.c_long
     lib.zvxk_sizeof.argtypes = [ctypes.c_char_p]
@@ -494,6 +523,12 @@ def _fused_ref(p, mut):
         zero_k = (C - 16, C) if mut == "zero_last_k" else None
         acc, mag, g2 = _conv(dd, Tflat, 0, C, W2, 0, C * C, C, b, rows, d["dv"], C, C, drop_tap=0 if mut == "drop_tap" else None,
                          shift_tap=(d["ntaps"] - 1) if mut == "shift_tap" else None, zero_k=zero_k)
+        if mut == "seam_halo" and il[b] > PAIR_SEG:
+            # the first row of the streaming pair kernel's second segment computed as if nothing lay in front of it
+            Tz = T.copy()
+            Tz[:PAIR_SEG] = 0.0
+            az, _, _ = _conv(dd, Tz.reshape(-1), 0, C, W2, 0, C * C, C, b, np.array([PAIR_SEG]), d["dv"], C, C)
+            acc[rows == PAIR_SEG] = az
         eprop, _, _ = _conv(dd, eT.reshape(-1), 0, C, np.abs(W2), 0, C * C, C, b, rows, d["dv"], C, C)
         # residual: inverse leaky-relu of X (resfuse) or of T (rb2fuse), folded into the bias term below
         rsrc = T[rows] if d["fused"] == 2 else xr[rows]
@@ -581,7 +616,8 @@ def attn_ref(p, mut=None):
     return res
 
 
-MUTATIONS = ["drop_tap", "shift_tap", "zero_last_k", "in_len_minus1", "res_slope", "drop_bias", "skip_accum", "truncate_cast"]
+MUTATIONS = ["drop_tap", "shift_tap", "zero_last_k", "in_len_minus1", "res_slope", "drop_bias", "skip_accum", "truncate_cast", "seam_halo"]
+PAIR_SEG = 1024                    # launch_pairstream's segment floor (rows)
 
 
 def applicable_mutations(p):
@@ -597,6 +633,8 @@ def applicable_mutations(p):
         (d.get("accum_mode", 0) & 2 and d["accum_dtype"] != DT_F32)
     if stored16:
         m.append("truncate_cast")
+    if d.get("fused") == 1 and d["N"] == 128 and max(d["in_len"]) > PAIR_SEG:
+        m.append("seam_halo")
     return m
 
 
@@ -889,6 +927,17 @@ BF, H16, F32 = DT_BF16, DT_F16, DT_F32
 RAG3 = [300, 1, 257]               # ragged batch with a length-1 utterance
 
 
+def pair_seam_kw(dt, k, dil, am):
+    kw = dict(dtype=dt, M=1100, N=128, K=128, nbatch=3, lens=[1100, 1025, 1], taps=taps_1d(k), dil1=dil, fused=1, no_pairstream=2)
+    if am:
+        kw.update(accum_mode=am, accum_dtype=dt)
+    if am in (0, 1):
+        kw.update(act=ACT_LRELU, slope=0.1, out_scale=1 / 3 if am else 1.0)
+    else:
+        kw.update(has_out=False)
+    return kw
+
+
 def _gemm_table():
     T = []
 
@@ -987,6 +1036,11 @@ def _gemm_table():
         add(f"resfuse_c64_k11_{n}", 17, None, dtype=dt, M=300, N=64, K=64, nbatch=1, taps=taps_1d(11), dil1=1, fused=1)
         add(f"pairstream_c128_{n}", 23, None, dtype=dt, M=700, N=128, K=128, nbatch=2, lens=[700, 1], taps=taps_1d(3), dil1=3, fused=1,
             no_pairstream=2, act=ACT_LRELU, slope=0.1)
+        # the streaming pair kernel past one segment: M = 1100 is two 1024-row segments, 1025 puts the seam one row before an utterance's
+        # end; every k with every dilation of ResBlock1, the four accumulator modes dealt over them so that each runs in both types
+        for i, (k, dil) in enumerate((k, dil) for k in (3, 7, 11) for dil in (1, 3, 5)):
+            am = (i + (2 if dt == H16 else 0)) % 4
+            add(f"pairstream_seam_k{k}_d{dil}_am{am}_{n}", 23, None, **pair_seam_kw(dt, k, dil, am))
         for C, vid in ((32, 30), (64, 31)):
             add(f"rb2fuse_c{C}_k3_{n}", vid, None, dtype=dt, M=500, N=C, K=C, nbatch=2, lens=[500, 1], taps=taps_1d(3, 3), dil1=1, fused=2, act=ACT_LRELU, slope=0.1)
         add(f"rb2fuse_c32_k7_accum_{n}", 30, None, dtype=dt, M=400, N=32, K=32, nbatch=1, taps=taps_1d(7, 12), dil1=3, fused=2, accum_mode=3, accum_dtype=dt)
@@ -1042,9 +1096,8 @@ def _gemm_table():
 
 GEMM_CASES = _gemm_table()
 # variant ids no case of the table reaches, each with its reason
-EXCLUDED_VARIANTS = {10: "placeholder entry (unused)", 11: "retired (resfuse c8)", 12: "retired (resfuse c16)", 13: "retired (resfuse c128)",
-                     20: "launch_resstream (own argument struct)", 21: "launch_resstream (own argument struct)",
-                     24: "launch_narrowstage (own argument struct)", 25: "launch_narrowstage (own argument struct)"}
+# (20 / 21 and 24 / 25 -- launch_resstream, launch_narrowstage -- take their own argument structs: RESSTREAM_CASES / NARROW_CASES below)
+EXCLUDED_VARIANTS = {10: "placeholder entry (unused)", 11: "retired (resfuse c8)", 12: "retired (resfuse c16)", 13: "retired (resfuse c128)"}
 
 
 def _attn_table():
@@ -1195,3 +1248,541 @@ def attn_struct(p, dev):
     lens = np.asarray(d["_lens"], np.int32)
     a.len = dev.upload(lens) if dev is not None else 0x900000
     return a, ptr
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# chained ResBlock kernels: launch_resstream (StreamArgs), launch_narrowstage (StageArgs), launch_pairstream past one segment
+#
+# chain_ref steps a ResBlock1 pair in float64 with the 16-bit roundings where the kernels put them (rs_role's epilogue_block /
+# store_phase, NsKernel::conv / tile, ps_role's epilogue_out):
+#     T = Q16(lrelu(conv_d(x) + b1, slope1));  y = conv_1(T) + b2 + inv_lrelu(x);  next x = Q16(lrelu(y, slope1))
+# every stream zero outside [0, len).  What closes the chain differs per kernel:
+#     resstream    no running sum: out = Q16(lrelu(y, slope)).  With one -- KNOWN DEVIATION, the same as variants 16 / 17 in _fused_ref --
+#                  y is packed to 16 bits BEFORE xs is added: s = Q16(y) (+ xs); xs' = Q16(s); out = Q16(lrelu(s * out_scale, slope))
+#     pairstream   s = y (+ xs) in f32; xs' = Q16(s); out = Q16(lrelu(s * out_scale, slope))
+#     narrowstage  the sum over the ResBlocks stays in f32: out = Q16(lrelu(sum_j y_j * f32(1 / nk), slope)), one rounding
+# Every value carries a per-element uncertainty e (the kernel's f32 value lies within e of the reference's): a 16-bit rounding
+# turns it into Q(v + e) - Q(v - e) -- zero unless a rounding boundary lies within e of v --, a convolution spreads it through |W|,
+# and the two leaky-relus scale it by their slope only on the side where the sign is certain (x - e < 0 for inv_lrelu's x
+# res_inv_slope, v + e < 0 for lrelu's x slope): without the signs the bound grows 10x per pair.  The accumulation term
+# 2 n U sum|x w| (n = nonzero weights of the output channel + the bias) is dropped per ELEMENT where every partial sum is exact in
+# f32 -- all terms multiples of g, sum of magnitudes <= 2^24 g (exact_f32, per element).  The exact-sum cases are built so that
+# this holds almost everywhere; what is left are the element-wise f32 roundings (bias and residual adds, x slope, x res_inv_slope,
+# x 1 / nk: U each).  The compared value is Q16(v), the tolerance max(Q(v + e) - Q(v), Q(v) - Q(v - e)): ZERO -- bit equality --
+# for every element with no rounding boundary within e.
+# PREMISE: a matrix instruction whose block sum is exactly representable returns it exactly.  The 32 x 32 x 16 cases of the
+# table above have held the kernels to this on hardware; for the 16 x 16 x 32 instruction of narrowstage it is what NARROW_CASES
+# measures.
+# ------------------------------------------------------------------------------------------------------------------------------
+SLOPE01 = float(np.float32(0.1))                  # the kernels multiply by the f32 nearest to 0.1 / to 1 / 3
+THIRD = float(np.float32(1.0 / 3.0))
+
+
+def egrid(a):
+    """Per element: the largest power of two the value is a multiple of (inf for zero)."""
+    a = np.asarray(a, np.float64)
+    m, e = np.frexp(np.abs(a))
+    ints = np.round(m * 2.0 ** 53).astype(np.int64)
+    low = (ints & -ints).astype(np.float64)
+    return np.where(a == 0, np.inf, np.ldexp(np.where(a == 0, 1.0, low), e - 53))
+
+
+def _cconv(x, W, dil, shift_last=False):
+    """y[b][r][n] = sum_t sum_c x[b][r + (t - h) dil][c] W[t][n][c]; rows outside [0, M) are zero."""
+    k, M = W.shape[0], x.shape[1]
+    h = (k - 1) // 2
+    y = np.zeros(x.shape[:2] + (W.shape[1],))
+    for t in range(k):
+        o = (t - h) * dil + (1 if shift_last and t == k - 1 else 0)
+        lo, hi = max(0, -o), min(M, M - o)
+        if hi > lo:
+            y[:, lo:hi] += x[:, lo + o:hi + o] @ W[t].T
+    return y
+
+
+def _conv_grid(gx, W, dil):
+    """Per output element, the grid of the products that reach it (None for dense weights: never exact)."""
+    k, N, C = W.shape
+    nz = np.argwhere(W != 0)
+    if len(nz) > 8 * N:
+        return None
+    M, h = gx.shape[1], (k - 1) // 2
+    gw = egrid(W)
+    g = np.full(gx.shape[:2] + (N,), np.inf)
+    for t, n, c in nz:
+        o = (t - h) * dil
+        lo, hi = max(0, -o), min(M, M - o)
+        if hi > lo:
+            g[:, lo:hi, n] = np.minimum(g[:, lo:hi, n], gx[:, lo + o:hi + o, c] * gw[t, n, c])
+    return g
+
+
+def _conv_e(x, ex, W, b, dil, bound, shift_last=False):
+    """conv(x) + b with its uncertainty: ex through |W|, plus the accumulation (and bias add) term where the sums are not exact."""
+    v = _cconv(x, W, dil, shift_last) + b
+    if not bound:
+        return v, 0.0, 0.0
+    mag = _cconv(np.abs(x), np.abs(W), dil) + np.abs(b)
+    e = _cconv(ex, np.abs(W), dil)
+    g = _conv_grid(egrid(x), W, dil)
+    nn = 2.0 * (np.count_nonzero(W, axis=(0, 2)) + 1) * U
+    if g is None:
+        e = e + nn * mag
+    else:
+        e = e + np.where(mag <= 2.0 ** 24 * np.minimum(g, egrid(b)), 0.0, nn * mag)
+    return v, e, mag
+
+
+def _lrelu_e(v, e, slope):
+    """max(v, v * slope), 0 < slope <= 1: the uncertainty shrinks by the slope only where v + e < 0; the product rounds once."""
+    if slope == 1.0:
+        return v, e
+    out = np.where(v >= 0, v, v * slope)
+    return out, np.where(v + e < 0, e * slope, e) + np.where(v - e < 0, U * (np.abs(out) + e), 0.0)
+
+
+def _inv_lrelu_e(x, ex, rinv):
+    """min(x, x * rinv), rinv >= 1: the uncertainty grows by rinv only where x - ex < 0."""
+    out = np.where(x >= 0, x, x * rinv)
+    neg = x - ex < 0
+    return out, np.where(neg, ex * rinv, ex) + np.where(neg, U * np.abs(out), 0.0)
+
+
+def _q_e(v, e, dt, q):
+    if not q:
+        return v, e
+    return round_to(v, dt), round_to(v + e, dt) - round_to(v - e, dt)
+
+
+def chain_pair(x, ex, inside, pr, dt, slope1, rinv, q=True, bound=True, mut=None):
+    """One pair on streams x [b][M][C] (zero outside `inside`): y = conv_1(T) + b2 + inv_lrelu(x) in f64, and its uncertainty.
+    pr: dict(W1, b1, W2, b2 [k][C][C] / [C], dil)."""
+    mut = mut or ()
+    W1, b1, W2, b2 = pr["W1"], pr["b1"], pr["W2"], pr["b2"]
+    if "drop_weight" in mut:
+        W1 = W1.copy()
+        W1[tuple(np.argwhere(W1 != 0)[len(np.argwhere(W1 != 0)) // 2])] = 0.0
+    if "swap_taps" in mut:
+        W1 = W1.copy()
+        W1[[0, 1]] = W1[[1, 0]]
+    if "drop_bias" in mut:
+        b2 = np.zeros_like(b2)
+    t, e1, _ = _conv_e(x, ex, W1, b1, pr["dil"], bound)
+    t, e1 = _lrelu_e(t, e1, slope1)
+    T, eT = _q_e(t, e1, dt, q and "no_round_T" not in mut)
+    T, eT = np.where(inside, T, 0.0), np.where(inside, eT, 0.0)
+    a2, e2, m2 = _conv_e(T, eT, W2, b2, 1, bound, shift_last="shift_tap" in mut)
+    if "seam" in mut:
+        # the first row of a segment / tile computed as if nothing lay in front of it
+        s0 = mut["seam"]
+        Tz = T.copy()
+        Tz[:, :s0] = 0.0
+        a2[:, s0] = (_cconv(Tz, W2, 1) + b2)[:, s0]
+    r, er = _inv_lrelu_e(x, ex, rinv * (0.5 if "res_slope" in mut else 1.0))
+    y = a2 + r
+    return y, e2 + er + (U * (m2 + np.abs(r)) if bound else 0.0)
+
+
+class ChainCase:
+    """A resstream / narrowstage / pairstream problem: X [b][M][C] (rows past lens NaN), blocks = list of ResBlocks, each a list of
+    pairs dict(W1, b1, W2, b2, dil, k); epilogue parameters am / has_out / out_scale / slope; xs [b][M][C] for am & 1."""
+
+    def __init__(self, **kw):
+        self.nan_utts = ()
+        self.__dict__.update(kw)
+
+    def fields(self):
+        f = []
+        if self.kind == "narrowstage" or self.has_out:
+            f.append("out")
+        if self.kind != "narrowstage" and self.am & 2:
+            f.append("accum")
+        return f
+
+
+def chain_ref(cs, q=True, bound=True, mut=None):
+    """{field: (ref, tol, mask)} [b][M][C] of a ChainCase.  q=False: no 16-bit rounding anywhere (the pure float64 chain; tol is
+    meaningless).  mut: dict of mutations of the reference (tests/test_kernel_reference.py)."""
+    mut = dict(mut or {})
+    nb, M, C = cs.X.shape
+    dt = cs.dt
+    lens = np.asarray(cs.lens)
+    if "len_minus1" in mut:
+        lens = np.maximum(lens - 1, 0)
+    inside = (np.arange(M)[None, :, None] < lens[:, None, None])
+    x0 = np.where(inside, np.nan_to_num(cs.X), 0.0)
+    z = np.zeros_like(x0)
+    pmut = {k: v for k, v in mut.items() if k in ("drop_weight", "swap_taps", "drop_bias", "no_round_T", "shift_tap", "seam", "res_slope")}
+    at = mut.get("at", None)                                     # (block, pair) the pair-level mutations apply to; default: the last pair of the last block
+
+    def run_block(j, blk):
+        x, ex = x0, z
+        for t, pr in enumerate(blk):
+            here = (j, t) == (at if at is not None else (len(cs.blocks) - 1, len(blk) - 1))
+            m = dict(pmut) if here else ({"res_slope": 1} if "res_slope" in pmut else None)
+            y, ey = chain_pair(x, ex, inside, pr, dt, cs.slope1, cs.rinv, q, bound, m)
+            if t + 1 < len(blk):
+                v, e = _lrelu_e(y, ey, cs.slope1)
+                x, ex = _q_e(v, e, dt, q)
+                x, ex = np.where(inside, x, 0.0), np.where(inside, ex, 0.0)
+        return y, ey
+
+    res = {}
+
+    def put(f, v, e):
+        ref = round_to(v, dt) if q else v
+        tol = np.maximum(round_to(v + e, dt) - ref, ref - round_to(v - e, dt)) if q and bound else np.zeros_like(v)
+        mask = inside & np.ones((1, 1, C), bool)
+        for b in cs.nan_utts:
+            mask[b] = False
+        res[f] = (ref, tol, mask)
+
+    if cs.kind == "narrowstage":
+        blocks = cs.blocks[:-1] if "mean_nk_minus1" in mut else cs.blocks
+        S, eS = 0.0, 0.0
+        for j, blk in enumerate(blocks):
+            y, ey = run_block(j, blk)
+            S = S + y
+            eS = eS + ey + U * np.abs(S)
+        inv = float(np.float32(1.0) / np.float32(len(blocks)))
+        v = S * inv
+        v, e = _lrelu_e(v, eS * inv + U * np.abs(v), cs.slope)
+        put("out", v, e)
+        return res
+    y, ey = run_block(0, cs.blocks[0])
+    if cs.am == 0:
+        v, e = _lrelu_e(y, ey, cs.slope)
+        put("out", v, e)
+        return res
+    s, es = _q_e(y, ey, dt, q) if cs.kind == "resstream" else (y, ey)
+    if cs.am & 1 and "skip_xs" not in mut:
+        s = s + np.nan_to_num(cs.xs)
+        es = es + U * np.abs(s)
+    if cs.am & 2:
+        put("accum", s, es)
+    if cs.has_out:
+        v = s * cs.out_scale
+        v, e = _lrelu_e(v, es * abs(cs.out_scale) + (U * np.abs(v) if cs.out_scale != 1.0 else 0.0), cs.slope)
+        put("out", v, e)
+    return res
+
+
+def exact_share(ref):
+    """Fraction of the compared elements whose tolerance is exactly zero."""
+    n = sum(int(m.sum()) for _, _, m in ref.values())
+    return sum(int((t[m] == 0).sum()) for _, t, m in ref.values()) / max(n, 1)
+
+
+def _sparse_w(rng, k, C):
+    """4 nonzeros +-2^-j (j = 1..3) per output channel; over the 4 C of them every tap index and every input channel occurs."""
+    W = np.zeros((k, C, C))
+    pk, pc = rng.permutation(k), rng.permutation(C)
+    for n in range(C):
+        for i in range(4):
+            s = 4 * n + i
+            W[pk[s % k], n, pc[s % C]] = rng.choice([-1.0, 1.0]) * 2.0 ** -int(rng.integers(1, 4))
+    return W
+
+
+def make_chain(name, seed=0, *, kind, dt, C, blocks, M, lens, data="exact", am=0, has_out=True, out_scale=1.0, slope=SLOPE01, ld_pad=0,
+               nan_utts=(), data_seed=0):
+    """blocks: [(k, dilations)] -- one entry for resstream (its pairs), nk entries for narrowstage (three pairs each).  Weights and
+    biases are drawn from `seed`, inputs and running sum from (`seed`, `data_seed`)."""
+    rng = _rng([seed, data_seed, 11])
+    rngw = _rng([seed, 7])
+    nb = len(lens)
+    exact = data == "exact"
+
+    def act_in(shape):
+        v = np.round(8 * rng.standard_normal(shape)) / 8 if exact else rng.standard_normal(shape)
+        return round_to(np.where(v >= 0, v, v * SLOPE01), dt)
+    X = np.full((nb, M, C), np.nan)
+    for b, l in enumerate(lens):
+        if b not in nan_utts:
+            X[b, :l] = act_in((l, C))
+    blks = []
+    for k, dils in blocks:
+        prs = []
+        for d in dils:
+            pr = dict(k=k, dil=d)
+            for w, bn in (("W1", "b1"), ("W2", "b2")):
+                pr[w] = _sparse_w(rngw, k, C) if exact else round_to(rngw.standard_normal((k, C, C)) / np.sqrt(k * C), dt)
+                pr[bn] = rngw.integers(-16, 17, C) / 64.0 if exact else round_to(0.3 * rngw.standard_normal(C), DT_F32)
+            prs.append(pr)
+        blks.append(prs)
+    xs = None
+    if am & 1:
+        xs = np.full((nb, M, C), np.nan)
+        for b, l in enumerate(lens):
+            xs[b, :l] = round_to(np.round(8 * rng.standard_normal((l, C))) / 8 if exact else rng.standard_normal((l, C)), dt)
+    return ChainCase(name=name, kind=kind, dt=dt, C=C, M=M, lens=list(lens), X=X, blocks=blks, am=am, has_out=has_out, out_scale=out_scale,
+                     slope=slope, slope1=SLOPE01, rinv=10.0, xs=xs, ld=C + ld_pad, data=data, nan_utts=tuple(nan_utts))
+
+
+def chain_of_gemm(p, data_seed=0):
+    """The ChainCase of a fused-pair GemmArgs problem (the dense pairstream cases: their rms criterion runs on chain_ref).
+    data_seed > 0: the same weights under another draw of the input and the running sum."""
+    cs = _chain_of_gemm(p)
+    if data_seed:
+        rng = _rng([data_seed, 13])
+        inside = ~np.isnan(cs.X)
+        v = round_to(rng.standard_normal(cs.X.shape), cs.dt)
+        cs.X = np.where(inside, round_to(np.where(v >= 0, v, v / cs.rinv), cs.dt), np.nan)
+        if cs.xs is not None:
+            cs.xs = np.where(inside, round_to(rng.standard_normal(cs.X.shape), cs.dt), np.nan)
+    return cs
+
+
+def _chain_of_gemm(p):
+    d = p.d
+    nb, M, C, k = d["nbatch"], d["M"], d["N"], d["ntaps"]
+    pr = dict(k=k, dil=d["dv1"][1] - d["dv1"][0], W1=p.bufs["W1"]["v"].reshape(k, C, C), b1=p.bufs["bias1"]["v"][:C],
+              W2=p.bufs["W"]["v"].reshape(k, C, d["ldw"])[:, :, :C], b2=p.bufs["bias"]["v"][:C])
+    am = d["accum_mode"]
+    xs = p.bufs["accum"]["v"].reshape(nb, -1, d["lda"])[:, :M, :C] if am & 1 else None
+    return ChainCase(name=d["name"], kind="pairstream", dt=d["dtype"], C=C, M=M, lens=list(d["in_len"]), blocks=[[pr]],
+                     X=p.bufs["X"]["v"].reshape(nb, -1, d["ldx"])[:, :M, :C], am=am, has_out=d["_has_out"],
+                     out_scale=float(np.float32(d["out_scale"])), slope=float(np.float32(d["slope"])) if d["act"] == ACT_LRELU else 1.0,
+                     slope1=float(np.float32(d["slope1"])), rinv=d["res_inv_slope"], xs=xs, ld=d["ldo"], data="dense")
+
+
+# ---- the rms criterion of the dense cases ----
+RMS_SEEDS = 8
+
+
+def _rms(a):
+    return float(np.sqrt(np.mean(np.square(a)))) if a.size else 0.0
+
+
+def rms_vs_pure(values, pure, mask):
+    return _rms((values - pure)[mask])
+
+
+def rms_margin(build, seeds=RMS_SEEDS):
+    """E_r = rms(chain_ref's rounded values - the pure float64 chain) per output field for `seeds` data seeds of build(seed) (the
+    weights stay: E_r scales with the chain's gain, which is the weights', not the data's), and the
+    margin m = 3 x (max - min) / mean of E_r over the seeds: what the reference's own error varies by from one draw of the data to
+    the next, from the reference alone.  Returns {field: (E_r of seed 0, spread, m)}."""
+    er = {}
+    for s in range(seeds):
+        cs = build(s)
+        a, b = chain_ref(cs, q=True, bound=False), chain_ref(cs, q=False, bound=False)
+        for f in a:
+            er.setdefault(f, []).append(rms_vs_pure(a[f][0], b[f][0], a[f][2]))
+    out = {}
+    for f, v in er.items():
+        spread = (max(v) - min(v)) / (sum(v) / len(v))
+        out[f] = (v[0], spread, 3.0 * spread)
+    return out
+
+
+def dense_builder(entry):
+    """data seed -> ChainCase of a dense NARROW_CASES / PAIR_DENSE_CASES entry (seed 0: the case the device runs)."""
+    if "kind" in entry[1]:
+        return lambda seed: make_chain(entry[0], 0, data_seed=seed, **entry[1])
+    p = build_case(entry)
+    return lambda seed: chain_of_gemm(p, seed)
+
+
+# ---- tables ----
+RS_FORMS = [(32, 3, (1, 3, 5)), (32, 7, (1, 3, 5)), (32, 11, (1, 3, 5)), (64, 3, (1, 3, 5)), (64, 7, (1, 3)), (64, 7, (5,)), (64, 11, (1, 3)),
+            (64, 11, (5,))]                                      # the eight RS_TRY forms of launch_resstream
+RS_LENS = [600, 257, 1]                                          # S = 256: three segments; 257 is one row into a segment
+
+
+def _rs_epi(am):
+    return dict(am=am, has_out=am < 2, out_scale=THIRD if am == 1 else 1.0)
+
+
+def _resstream_table():
+    T = []
+    for i, (C, k, dils) in enumerate(RS_FORMS):
+        for di, dt in enumerate((DT_BF16, DT_F16)):
+            for am in (0, 1 + (i + di) % 3):                     # am 0 on every form; 1 / 2 / 3 dealt so that each runs at both C in both types
+                for data in ("exact", "dense"):
+                    nm = f"resstream_c{C}_k{k}_np{len(dils)}_am{am}_{data}_{DT_NAME[dt]}"
+                    T.append((nm, dict(kind="resstream", dt=dt, C=C, blocks=[(k, dils)], M=600, lens=RS_LENS, data=data,
+                                       ld_pad=8 if dt == DT_F16 else 0, **_rs_epi(am)), 20 if C == 32 else 21))
+    # a length that is exactly one segment
+    T.append(("resstream_c32_k3_len256_exact_bf16", dict(kind="resstream", dt=DT_BF16, C=32, blocks=[(3, (1, 3, 5))], M=600, lens=[256, 600], **_rs_epi(3)), 20))
+    T.append(("resstream_c64_k7_len256_exact_f16", dict(kind="resstream", dt=DT_F16, C=64, blocks=[(7, (1, 3))], M=600, lens=[256, 600], **_rs_epi(0)), 21))
+    return T
+
+
+NS_R = {16: 384, 8: 512}                                         # rows per tile (launch_narrowstage)
+NS_WGPC = {16: 1, 8: 2}                                          # workgroups per CU
+NS_KS = [(3, 7, 11), (5,), (11, 3), (7, 5, 3)]
+
+
+def ns_lens(C):
+    R = NS_R[C]
+    return [2 * R + 80, 2 * R + 79, R, R + 1, 57, 1]             # 2 R + 80: the first interior tile (m0 + R + NS_HB + NS_GUARD <= len), by equality
+
+
+def _narrow_table():
+    T = []
+    for C in (16, 8):
+        for dt in (DT_BF16, DT_F16):
+            for ks in NS_KS:
+                for data in ("exact", "dense"):
+                    nm = f"narrowstage_c{C}_k{'_'.join(map(str, ks))}_{data}_{DT_NAME[dt]}"
+                    T.append((nm, dict(kind="narrowstage", dt=dt, C=C, blocks=[(k, (1, 3, 5)) for k in ks], M=3 * NS_R[C] + 40, lens=ns_lens(C),
+                                       data=data), 24 if C == 16 else 25))
+    return T
+
+
+def narrow_reuse_kw(C, ncu):
+    """More one-tile utterances than workgroups, so that a workgroup takes a second tile; two utterances hold NaN: the one a second
+    tile follows in its workgroup, and a second tile."""
+    n = ncu * NS_WGPC[C] + 8
+    lens = [1 + (i * 29) % 48 for i in range(n)]
+    return dict(kind="narrowstage", dt=DT_BF16 if C == 16 else DT_F16, C=C, blocks=[(k, (1, 3, 5)) for k in (3, 7, 11)], M=48, lens=lens,
+                nan_utts=(5, n - 6))
+
+
+def _pair_dense_table():
+    T = []
+    for dt in (DT_BF16, DT_F16):
+        for i, (k, dil) in enumerate((k, dil) for k in (3, 7, 11) for dil in (1, 3, 5)):
+            am = (i + (2 if dt == DT_F16 else 0)) % 4
+            T.append((f"pairstream_seam_k{k}_d{dil}_am{am}_dense_{DT_NAME[dt]}", dict(pair_seam_kw(dt, k, dil, am), grid_data=False), 23, None))
+    return T
+
+
+RESSTREAM_CASES = _resstream_table()
+NARROW_CASES = _narrow_table()
+PAIR_DENSE_CASES = _pair_dense_table()
+
+
+def build_chain(entry, seed=0):
+    return make_chain(entry[0], seed, **entry[1])
+
+
+# ---- descriptors and launches ----
+def _fake(i):
+    return 0x100000 * (i + 1)
+
+
+def _bits_nan(v, dt):
+    return np.where(np.isnan(v), nan_bits(dt), to_bits(np.nan_to_num(v), dt)).astype(bits_dtype(dt))
+
+
+def _out_buffers(cs, dev, fields):
+    """Output / running-sum buffers [b][M][ld] as bits: sentinel everywhere, xs in the valid rows of an accumulated running sum."""
+    nb, M, C = cs.X.shape
+    before, ptr = {}, {}
+    for f in fields:
+        bits = np.full((nb, M, cs.ld), sentinel_bits(cs.dt), bits_dtype(cs.dt))
+        if f == "accum" and cs.am & 1:
+            xb = to_bits(np.nan_to_num(cs.xs), cs.dt)
+            bits[:, :, :C] = np.where(np.isnan(cs.xs), bits[:, :, :C], xb)
+        before[f] = bits.reshape(-1)
+        ptr[f] = dev.upload(before[f]) if dev is not None else _fake(20 + len(ptr))
+    return before, ptr
+
+
+def stream_struct(cs, dev):
+    """StreamArgs of a resstream ChainCase (dev=None: fake pointers for dry runs).  Returns (args, {field: device pointer}, {field: bits before})."""
+    nb, M, C = cs.X.shape
+    a = StreamArgs()
+    a.x_bs, a.ldx, a.C, a.ntaps, a.npair = M * C, C, C, cs.blocks[0][0]["k"], len(cs.blocks[0])
+    a.o_bs = a.a_bs = M * cs.ld
+    a.ldo = a.lda = cs.ld
+    a.accum_mode, a.slope1, a.res_inv_slope, a.out_scale, a.slope = cs.am, cs.slope1, cs.rinv, cs.out_scale, cs.slope
+    a.M, a.nbatch, a.seg_min, a.f16 = M, nb, 0, int(cs.dt == DT_F16)
+    a.X = dev.upload(_bits_nan(cs.X, cs.dt)) if dev is not None else _fake(0)
+    a.len = dev.upload(np.asarray(cs.lens, np.int32)) if dev is not None else _fake(1)
+    for t, pr in enumerate(cs.blocks[0]):
+        a.dil[t] = pr["dil"]
+        for q, (w, bn) in enumerate((("W1", "b1"), ("W2", "b2"))):
+            if dev is None:
+                wp, bp = _fake(2 + 4 * t + 2 * q), _fake(3 + 4 * t + 2 * q)
+            else:
+                k = pr["k"]
+                raw = dev.upload(to_bits(pr[w], cs.dt))
+                wp = dev.alloc(dev.lib.zvxk_packed_weight_elems(k, C, C) * 2)
+                assert dev.lib.zvxk_pack_weights(raw, k, C, C, wp) == 0
+                bp = dev.upload(np.concatenate([pr[bn], np.zeros(8)]).astype(np.float32))
+                pr["_" + w], pr["_" + bn] = wp, bp               # (also the operands of the per-pair launches of the bit-equality check)
+            getattr(a, w)[t] = wp
+            getattr(a, bn)[t] = bp
+    fields = (["out"] if cs.has_out else []) + (["accum"] if cs.am else [])
+    before, ptr = _out_buffers(cs, dev, fields)
+    a.out, a.accum = ptr.get("out"), ptr.get("accum")
+    return a, ptr, before
+
+
+def resfuse_chain(cs, dev, a):
+    """The same chain as len(pairs) launch_resfuse launches (no_pairstream = 1, variants 16 / 17) on the operands stream_struct put on
+    the device: {field: bits} of fresh output buffers."""
+    nb, M, C = cs.X.shape
+    lib = dev.lib
+    before, ptr = _out_buffers(cs, dev, (["out"] if cs.has_out else []) + (["accum"] if cs.am else []))
+    cur, ld = a.X, C
+    prs = cs.blocks[0]
+    for t, pr in enumerate(prs):
+        last = t + 1 == len(prs)
+        g = GemmArgs()
+        k = pr["k"]
+        g.X, g.x_bs, g.ldx, g.ldw, g.w_ts = cur, M * ld, ld, C, C * C
+        g.Wp, g.Wp2, g.bias, g.bias1 = pr["_W2"], pr["_W1"], pr["_b2"], pr["_b1"]
+        g.dv1[:] = _pad_taps(taps_1d(k, pr["dil"]))
+        g.dv[:] = _pad_taps(taps_1d(k))
+        g.fused, g.slope1, g.no_pairstream, g.dtype = 1, cs.slope1, 1, cs.dt
+        g.M, g.N, g.K, g.nbatch, g.nheads, g.ntaps, g.stride, g.hin, g.xcd_flat = M, C, C, nb, 1, k, 1, 1, 1
+        g.in_len = g.out_len = a.len
+        g.alpha, g.bias_mode, g.out_scale = 1.0, 1, 1.0
+        g.res, g.r_bs, g.ldr, g.res_dtype, g.res_mode, g.res_inv_slope = cur, M * ld, ld, cs.dt, 2, cs.rinv
+        g.accum_dtype = g.out_dtype = cs.dt
+        if not last:
+            nxt = dev.upload(np.full(nb * M * C, sentinel_bits(cs.dt), bits_dtype(cs.dt)))
+            g.out, g.o_bs, g.ldo, g.act, g.slope = nxt, M * C, C, ACT_LRELU, cs.slope1
+        else:
+            g.o_bs = g.a_bs = M * cs.ld
+            g.ldo = g.lda = cs.ld
+            g.out, g.accum, g.accum_mode = ptr.get("out"), ptr.get("accum"), cs.am
+            g.out_scale = cs.out_scale
+            g.act, g.slope = (ACT_LRELU, cs.slope) if cs.has_out and cs.slope != 1.0 else (ACT_NONE, 1.0)
+        vid = lib.zvxk_gemm(g, 0)
+        assert vid > -1000, f"{cs.name}: per-pair launch {t}: HIP error {-vid - 1000}"
+        assert vid == (16 if C == 32 else 17), f"{cs.name}: per-pair launch {t} returned {vid}"
+        if not last:
+            cur, ld = g.out, C
+    n = nb * M * cs.ld
+    return {f: dev.download(ptr[f], n, bits_dtype(cs.dt)) for f in ptr}
+
+
+def stage_struct(cs, dev):
+    """StageArgs of a narrowstage ChainCase: the fragments of convolution 6 j + 2 t + {0: conv1, 1: conv2} at woff, biases in that order."""
+    nb, M, C = cs.X.shape
+    a = StageArgs()
+    a.x_bs = a.o_bs = M * C
+    a.ldx = a.ldo = a.C = C
+    a.nk, a.slope1, a.res_inv_slope, a.slope, a.M, a.nbatch, a.f16 = len(cs.blocks), cs.slope1, cs.rinv, cs.slope, M, nb, int(cs.dt == DT_F16)
+    steps = lambda k: (k + 32 // C - 1) // (32 // C)             # narrowstage_steps (held to the shim's by test_kernels_gpu)
+    nfrag, bias = 0, []
+    for j, blk in enumerate(cs.blocks):
+        a.ks[j] = blk[0]["k"]
+        for t, pr in enumerate(blk):
+            a.dil[j][t] = pr["dil"]
+            for q, (w, bn) in enumerate((("W1", "b1"), ("W2", "b2"))):
+                a.woff[6 * j + 2 * t + q] = nfrag
+                nfrag += steps(pr["k"])
+                bias.append(pr[bn])
+    before, ptr = _out_buffers(cs, dev, ["out"])
+    a.out = ptr["out"]
+    if dev is None:
+        a.X, a.W, a.bias, a.len = _fake(0), _fake(1), _fake(2), _fake(3)
+        return a, ptr, before
+    lib = dev.lib
+    a.X = dev.upload(_bits_nan(cs.X, cs.dt))
+    a.len = dev.upload(np.asarray(cs.lens, np.int32))
+    a.bias = dev.upload(np.concatenate(bias).astype(np.float32))
+    a.W = dev.alloc(nfrag * 1024)
+    for j, blk in enumerate(cs.blocks):
+        for t, pr in enumerate(blk):
+            for q, w in enumerate(("W1", "W2")):
+                assert lib.zvxk_narrowstage_steps(C, pr["k"]) == steps(pr["k"])
+                raw = dev.upload(to_bits(pr[w], cs.dt))
+                assert lib.zvxk_pack_narrow(raw, pr["k"], C, a.W + a.woff[6 * j + 2 * t + q] * 1024) == 0
+    return a, ptr, before

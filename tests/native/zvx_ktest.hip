@@ -40,6 +40,15 @@ const Field kFields[] = {
     F_(AttnF32Args, out), F_(AttnF32Args, o_bs), F_(AttnF32Args, ldo), F_(AttnF32Args, planes), F_(AttnF32Args, planes_C),
     F_(AttnF32Args, planes_f16), F_(AttnF32Args, len), F_(AttnF32Args, L), F_(AttnF32Args, D), F_(AttnF32Args, nheads),
     F_(AttnF32Args, nbatch), F_(AttnF32Args, scale),
+    F_(StreamArgs, X), F_(StreamArgs, x_bs), F_(StreamArgs, ldx), F_(StreamArgs, W1), F_(StreamArgs, W2), F_(StreamArgs, b1), F_(StreamArgs, b2),
+    F_(StreamArgs, dil), F_(StreamArgs, C), F_(StreamArgs, ntaps), F_(StreamArgs, npair), F_(StreamArgs, out), F_(StreamArgs, o_bs),
+    F_(StreamArgs, ldo), F_(StreamArgs, accum), F_(StreamArgs, a_bs), F_(StreamArgs, lda), F_(StreamArgs, accum_mode), F_(StreamArgs, slope1),
+    F_(StreamArgs, res_inv_slope), F_(StreamArgs, out_scale), F_(StreamArgs, slope), F_(StreamArgs, len), F_(StreamArgs, M),
+    F_(StreamArgs, nbatch), F_(StreamArgs, S), F_(StreamArgs, nseg), F_(StreamArgs, dX0), F_(StreamArgs, dT), F_(StreamArgs, dX),
+    F_(StreamArgs, flops), F_(StreamArgs, prof), F_(StreamArgs, seg_min), F_(StreamArgs, f16),
+    F_(StageArgs, X), F_(StageArgs, x_bs), F_(StageArgs, ldx), F_(StageArgs, W), F_(StageArgs, woff), F_(StageArgs, bias), F_(StageArgs, C),
+    F_(StageArgs, nk), F_(StageArgs, ks), F_(StageArgs, dil), F_(StageArgs, out), F_(StageArgs, o_bs), F_(StageArgs, ldo), F_(StageArgs, slope1),
+    F_(StageArgs, res_inv_slope), F_(StageArgs, slope), F_(StageArgs, len), F_(StageArgs, M), F_(StageArgs, nbatch), F_(StageArgs, f16),
 };
 #undef F_
 }  // namespace
@@ -85,6 +94,26 @@ int zvxk_attn_f32(const AttnF32Args* a, int dry_run) {
     const int st = sync_status();
     return st < 0 ? st : 1;
 }
+// streaming ResBlock chain (resstream.hip): variant id (20 / 21) or -1 when the launcher refuses; < -1000: HIP error
+int zvxk_resstream(const StreamArgs* a, int dry_run) {
+    const int id = launch_resstream(*a, nullptr, dry_run != 0);
+    if (dry_run || id < 0) return id;
+    const int st = sync_status();
+    return st < 0 ? st : id;
+}
+// a whole narrow stage (narrowstage.hip): 1 launched (or, dry_run, covered), 0 refused, < 0 HIP error
+int zvxk_narrowstage(const StageArgs* a, int dry_run) {
+    const bool ok = launch_narrowstage(*a, nullptr, dry_run != 0);
+    if (dry_run || !ok) return ok ? 1 : 0;
+    const int st = sync_status();
+    return st < 0 ? st : 1;
+}
+int zvxk_pack_narrow(const void* w16, int k, int C, void* out) {
+    launch_pack_narrow(w16, k, C, out, nullptr);
+    return sync_status();
+}
+int zvxk_narrowstage_steps(int C, int k) { return narrowstage_steps(C, k); }
+int zvxk_num_cus() { return num_cus(); }
 const char* zvxk_variant_name(int id) { return (id >= 0 && id < gemm_num_variants()) ? gemm_variant_name(id) : nullptr; }
 int zvxk_num_variants() { return gemm_num_variants(); }
 
@@ -93,6 +122,8 @@ long zvxk_sizeof(const char* name) {
     if (!strcmp(name, "GemmArgs")) return (long)sizeof(GemmArgs);
     if (!strcmp(name, "FlashArgs")) return (long)sizeof(FlashArgs);
     if (!strcmp(name, "AttnF32Args")) return (long)sizeof(AttnF32Args);
+    if (!strcmp(name, "StreamArgs")) return (long)sizeof(StreamArgs);
+    if (!strcmp(name, "StageArgs")) return (long)sizeof(StageArgs);
     return -1;
 }
 long zvxk_offsetof(const char* st, const char* field) {

@@ -2,7 +2,10 @@
   * the ctypes mirror of GemmArgs / FlashArgs / AttnF32Args has the compiled layout (read from the shim without opening a device);
   * gemm_ref / attn_ref agree with an independent formulation (torch.nn.functional on the CPU) for each row-map kind;
   * the references discriminate: every mutation of the reference (a dropped or shifted tap, a lost K chunk, an off-by-one length,
-    the wrong residual slope, a dropped bias, a skipped accumulator add) leaves the bound of every case it applies to."""
+    the wrong residual slope, a dropped bias, a skipped accumulator add) leaves the bound of every case it applies to;
+  * the chained reference of the streaming ResBlock kernels (chain_ref): equal to torch's HiFi-GAN ResBlock1 / stage with the
+    roundings off, at least 30 % of every exact-sum case held to bit equality, and every mutation of it outside the bound (the
+    dense cases' rms criterion rejects two swapped taps)."""
 import ctypes
 import os
 
@@ -163,3 +166,94 @@ def test_attention_mutations_leave_bound(entry):
         assert _exceeds(r, t, m, K.attn_ref(p, "len_minus1")["out"][0])
         p.d["scale"] *= 1.02
         assert _exceeds(r, t, m, K.attn_ref(p)["out"][0])
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the chained reference of launch_resstream / launch_narrowstage / launch_pairstream
+# ------------------------------------------------------------------------------------------------------------------------------
+def _torch_resblock(x, blk, slope, L):
+    """hifigan.py's ResBlock1 on one utterance x [C][L] (float64): x += conv_1(lrelu(conv_d(lrelu(x)))) per pair."""
+    for pr in blk:
+        k, d = pr["k"], pr["dil"]
+        w1, w2 = (torch.tensor(pr[w]).permute(1, 2, 0) for w in ("W1", "W2"))
+        t = F.conv1d(F.leaky_relu(x, slope)[None], w1, torch.tensor(pr["b1"]), padding=d * (k - 1) // 2, dilation=d)[0]
+        x = x + F.conv1d(F.leaky_relu(t, slope)[None], w2, torch.tensor(pr["b2"]), padding=(k - 1) // 2)[0]
+    return x
+
+
+@pytest.mark.parametrize("kind", ["resstream", "narrowstage", "pairstream"])
+def test_chain_ref_without_roundings_vs_torch(kind):
+    """slope 1 / 8 against res_inv_slope 8, so that inv_lrelu undoes lrelu exactly as HiFi-GAN's raw residual has it."""
+    slope = 0.125
+    if kind == "narrowstage":
+        cs = K.make_chain("t", 3, kind=kind, dt=K.DT_BF16, C=8, blocks=[(3, (1, 3, 5)), (11, (1, 3, 5))], M=90, lens=[90, 31, 1], data="dense", slope=0.25)
+    else:
+        cs = K.make_chain("t", 4, kind=kind, dt=K.DT_F16, C=16, blocks=[(7, (1, 3, 5) if kind == "resstream" else (3,))], M=70, lens=[70, 9], data="dense",
+                          am=3, has_out=False)
+    cs.slope1, cs.rinv = slope, 1 / slope
+    ref = K.chain_ref(cs, q=False)
+    f = "out" if kind == "narrowstage" else "accum"
+    for b, l in enumerate(cs.lens):
+        xa = torch.tensor(cs.X[b, :l].T)
+        x = torch.where(xa >= 0, xa, xa / slope)
+        ys = [_torch_resblock(x, blk, slope, l) for blk in cs.blocks]
+        if kind == "narrowstage":
+            y = F.leaky_relu(sum(ys) / len(ys), cs.slope)
+        else:
+            y = ys[0] + torch.tensor(cs.xs[b, :l].T)
+        np.testing.assert_allclose(ref[f][0][b, :l], y.T.numpy(), rtol=1e-12, atol=1e-12)
+        assert ref[f][2][b, :l].all() and not ref[f][2][b, l:].any()
+
+
+def _chain_exact_entries():
+    E = [e for e in K.RESSTREAM_CASES + K.NARROW_CASES if e[1].get("data", "exact") == "exact"]
+    return E + [(f"narrowstage_c{C}_tile_reuse", K.narrow_reuse_kw(C, 256), 24 if C == 16 else 25) for C in (16, 8)]
+
+
+def _chain_mutations(cs):
+    nk, last = len(cs.blocks), len(cs.blocks[-1]) - 1
+    muts = [dict(drop_weight=1, at=(j, t)) for j in range(nk) for t in range(len(cs.blocks[j]))]
+    muts += [dict(shift_tap=1), dict(len_minus1=1), dict(res_slope=1), dict(drop_bias=1), dict(no_round_T=1)]
+    if cs.kind != "narrowstage" and cs.am & 1:
+        muts.append(dict(skip_xs=1))
+    if cs.kind == "narrowstage" and nk > 1:
+        muts.append(dict(mean_nk_minus1=1))
+    seam = 256 if cs.kind == "resstream" else K.NS_R[cs.C]
+    if max(cs.lens) > seam:
+        muts.append(dict(seam=seam))
+    return muts
+
+
+@pytest.mark.parametrize("entry", _chain_exact_entries(), ids=[e[0] for e in _chain_exact_entries()])
+def test_chain_exact_share_and_mutations(entry):
+    """From the reference alone: at least 30 % of the compared elements of an exact-sum case have tolerance zero (the kernel must
+    match the reference's 16-bit value bit for bit there), and every mutation of the reference leaves the bound somewhere."""
+    cs = K.build_chain(entry)
+    true = K.chain_ref(cs)
+    share = K.exact_share(true)
+    assert share >= 0.30, f"{entry[0]}: exact share {share:.3f}"
+    weak = []
+    for mut in _chain_mutations(cs):
+        got = K.chain_ref(cs, bound=False, mut=mut)
+        if not any(_exceeds(true[f][0], true[f][1], true[f][2], got[f][0]) for f in true):
+            weak.append(mut)
+    assert not weak, f"{entry[0]}: mutations within the bound: {weak}"
+
+
+def _dense_rms_entries():
+    return [e for e in K.NARROW_CASES if e[1]["data"] == "dense"] + K.PAIR_DENSE_CASES
+
+
+@pytest.mark.parametrize("entry", _dense_rms_entries(), ids=[e[0] for e in _dense_rms_entries()])
+def test_dense_rms_criterion_rejects_swapped_taps(entry):
+    """E <= E_r (1 + m) against the pure float64 chain: two swapped taps of one convolution (which sparse weights cannot see as a
+    misplaced fragment) exceed it, and m stays a margin, not a licence (below 1: the criterion never allows twice the reference's
+    own error)."""
+    build = K.dense_builder(entry)
+    cs = build(0)
+    pure = K.chain_ref(cs, q=False, bound=False)
+    mutated = K.chain_ref(cs, bound=False, mut=dict(swap_taps=1, at=(0, 0)))
+    for f, (er, spread, m) in K.rms_margin(build).items():
+        assert m < 1.0, f"{entry[0]}.{f}: margin {m:.3f}"
+        em = K.rms_vs_pure(mutated[f][0], pure[f][0], pure[f][2])
+        assert em > er * (1 + m), f"{entry[0]}.{f}: swapped taps give rms {em:.3g}, within {er:.3g} x (1 + {m:.3f})"

@@ -5,7 +5,18 @@ Per element, |kernel - ref| <= bound, with the bound of kernel_ref (fp32 accumul
 magnitudes, + half an ulp of the output type at |ref| plus the bound itself; fused kernels add one ulp of their 16-bit intermediate
 propagated through |W2| and the residual; flash adds 2^-8 (bf16) / 2^-11 (f16) relative for its 16-bit probabilities).
 Output / accumulator / shortcut buffers start as a sentinel bit pattern that every element the contract does not write must keep;
-input rows, keys and columns the contract masks hold NaN."""
+input rows, keys and columns the contract masks hold NaN.
+
+The streaming ResBlock kernels -- launch_resstream (StreamArgs), launch_narrowstage (StageArgs) and launch_pairstream past one
+segment -- are held to kernel_ref.chain_ref, a float64 chain with the 16-bit roundings where the kernels put them:
+  * exact-sum data (sparse power-of-two weights, inputs on a grid: every f32 partial sum exact, per element): the kernel must equal
+    the reference's 16-bit value BIT FOR BIT wherever no rounding boundary lies within the propagated element-wise f32 roundings
+    (at least 30 % of every case, asserted on the host; measured shares in profiles/stream_kernel_spec.txt), and lie within the
+    propagated bound elsewhere.  Premise: a matrix instruction returns an exactly representable block sum exactly -- established
+    for 32 x 32 x 16 by the conv-GEMM cases, and what the narrowstage cases measure for 16 x 16 x 32;
+  * dense data: resstream bit-equal to the same chain as per-pair launch_resfuse launches (variants 16 / 17, spec-tested above);
+    narrowstage and pairstream by rms against the PURE float64 chain: E_kernel <= E_reference (1 + m), m = 3 x the relative
+    spread of E_reference over 8 data seeds (kernel_ref.rms_margin)."""
 import numpy as np
 import pytest
 
@@ -187,6 +198,207 @@ def test_attention_case(lib, entry):
         dev.free()
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# streaming ResBlock kernels against the chained reference
+# ------------------------------------------------------------------------------------------------------------------------------
+def _ran(rc, what):
+    """A HIP error after a launch (the shim's -(1000 + code)) ends the session: nothing more is started on a device that faulted."""
+    if rc <= -1000:
+        pytest.exit(f"{what}: HIP error {-rc - 1000}", returncode=3)
+    return rc
+
+
+def _check_chain(cs, got, ref, before):
+    """got / before: {field: bits of the [b][M][ld] buffer}.  Compared elements within their tolerance (zero: bit equality with the
+    reference's 16-bit value), everything else -- rows at or past len, pad columns, a running sum that is only read -- as it was; the
+    valid rows of an utterance with NaN input may hold anything.  Returns (worst err / tol over tol > 0, zero-tolerance share)."""
+    nb, M, C = cs.X.shape
+    worst = 0.0
+    for f in before:
+        g = got[f].reshape(nb, M, cs.ld)
+        keep = np.ones((nb, M, cs.ld), bool)
+        if f in ref:
+            r, t, m = ref[f]
+            keep[:, :, :C] = ~m
+            for b in cs.nan_utts:
+                keep[b, :cs.lens[b], :C] = False
+            vals = K.from_bits(g[:, :, :C], cs.dt)
+            err = np.abs(vals[m] - r[m])
+            bad = ~(err <= t[m])
+            if bad.any():
+                i = np.argwhere(m)[np.argmax(bad)]
+                raise AssertionError(f"{cs.name}.{f}: {bad.sum()}/{m.sum()} elements out of tolerance ({(bad & (t[m] == 0)).sum()} of them at tolerance zero); "
+                                     f"[b, row, ch] = {i.tolist()}: got {vals[tuple(i)]!r} ref {r[tuple(i)]!r} tol {t[tuple(i)]:.3g}")
+            pos = t[m] > 0
+            if pos.any():
+                worst = max(worst, float(np.max(err[pos] / t[m][pos])))
+        same = g[keep] == before[f].reshape(nb, M, cs.ld)[keep]
+        assert same.all(), f"{cs.name}.{f}: {(~same).sum()} elements outside the contract's region were written"
+    return worst, K.exact_share(ref)
+
+
+def _rms_check(name, build, cs, got, spec):
+    """E_k <= E_r (1 + m) per output field against the pure float64 chain (m from the reference alone: K.rms_margin)."""
+    nb, M, C = cs.X.shape
+    pure = K.chain_ref(cs, q=False, bound=False)
+    for f, (er, spread, m) in K.rms_margin(build).items():
+        vals = K.from_bits(got[f].reshape(nb, M, cs.ld)[:, :, :C], cs.dt)
+        mask = pure[f][2]
+        assert np.isfinite(vals[mask]).all(), f"{name}.{f}: non-finite values"
+        ek = K.rms_vs_pure(vals, pure[f][0], mask)
+        spec.append(f"{f}: E_r {er:.4g} spread {spread:.4f} m {m:.4f} E_k/E_r {ek / er:.4f}")
+        print(f"SPEC {name} " + spec[-1])
+        assert ek <= er * (1 + m), f"{name}.{f}: rms against the pure float64 chain {ek:.4g} > {er:.4g} x (1 + {m:.4f})"
+
+
+@pytest.mark.parametrize("entry", K.RESSTREAM_CASES, ids=[e[0] for e in K.RESSTREAM_CASES])
+def test_resstream_case(lib, entry):
+    """launch_resstream with hand-built StreamArgs.  exact-sum data: chain_ref's bound (bit equality at tolerance zero); dense data:
+    bit equality with the same chain run pair by pair on launch_resfuse, as resstream.hip's header claims."""
+    name, kw, vid = entry
+    cs = K.build_chain(entry)
+    a, _, _ = K.stream_struct(cs, None)
+    assert lib.zvxk_resstream(a, 1) == vid, f"{name}: dry run"
+    dev = K.Device(lib)
+    try:
+        a, ptr, before = K.stream_struct(cs, dev)
+        assert _ran(lib.zvxk_resstream(a, 0), name) == vid, f"{name}: launch"
+        n = len(next(iter(before.values())))
+        got = {f: dev.download(ptr[f], n, K.bits_dtype(cs.dt)) for f in ptr}
+        if cs.data == "exact":
+            worst, share = _check_chain(cs, got, K.chain_ref(cs), before)
+            print(f"SPEC {name} worst err/bound {worst:.3f} exact share {share:.3f}")
+        else:
+            pairwise = K.resfuse_chain(cs, dev, a)
+            for f in got:
+                diff = got[f] != pairwise[f]
+                assert not diff.any(), f"{name}.{f}: {diff.sum()} elements differ from the per-pair launches (first at {np.argmax(diff)})"
+            nb, M, C = cs.X.shape
+            for f in got:                                          # rows past len and pad columns keep the sentinel (an accumulated running sum: xs)
+                g, b0 = got[f].reshape(nb, M, cs.ld), before[f].reshape(nb, M, cs.ld)
+                written = np.zeros((nb, M, cs.ld), bool)
+                if not (f == "accum" and cs.am == 1):
+                    for b, l in enumerate(cs.lens):
+                        written[b, :l, :C] = True
+                assert (g[~written] == b0[~written]).all(), f"{name}.{f}: elements outside the contract's region were written"
+                assert np.isfinite(K.from_bits(g[written], cs.dt)).all(), f"{name}.{f}: non-finite values"
+            print(f"SPEC {name} bit-equal to {len(cs.blocks[0])} per-pair launches")
+    finally:
+        dev.free()
+
+
+@pytest.mark.parametrize("entry", K.NARROW_CASES, ids=[e[0] for e in K.NARROW_CASES])
+def test_narrowstage_case(lib, entry):
+    """launch_narrowstage with hand-built StageArgs (16 x 16 x 32 MFMA: the exact-sum premise is measured here; measured exact
+    shares and worst err / bound per case in profiles/stream_kernel_spec.txt)."""
+    name, kw, vid = entry
+    cs = K.build_chain(entry)
+    a, _, _ = K.stage_struct(cs, None)
+    assert lib.zvxk_narrowstage(a, 1) == 1, f"{name}: dry run"
+    dev = K.Device(lib)
+    try:
+        a, ptr, before = K.stage_struct(cs, dev)
+        assert _ran(lib.zvxk_narrowstage(a, 0), name) == 1, f"{name}: launch"
+        got = {"out": dev.download(ptr["out"], len(before["out"]), K.bits_dtype(cs.dt))}
+        if cs.data == "exact":
+            worst, share = _check_chain(cs, got, K.chain_ref(cs), before)
+            print(f"SPEC {name} worst err/bound {worst:.3f} exact share {share:.3f}")
+        else:
+            nb, M, C = cs.X.shape
+            g = got["out"].reshape(nb, M, C)
+            for b, l in enumerate(cs.lens):
+                assert (g[b, l:] == K.sentinel_bits(cs.dt)).all(), f"{name}: rows past len written"
+            _rms_check(name, K.dense_builder(entry), cs, got, [])
+    finally:
+        dev.free()
+
+
+@pytest.mark.parametrize("C", [16, 8])
+def test_narrowstage_tile_reuse(lib, C):
+    """More one-tile utterances than workgroups: a persistent workgroup takes a second tile.  Two utterances hold NaN input (one
+    whose workgroup goes on to a second tile, and a second tile); every other utterance meets its bound."""
+    entry = (f"narrowstage_c{C}_tile_reuse", K.narrow_reuse_kw(C, lib.zvxk_num_cus()), 24 if C == 16 else 25)
+    cs = K.build_chain(entry)
+    dev = K.Device(lib)
+    try:
+        a, ptr, before = K.stage_struct(cs, dev)
+        assert _ran(lib.zvxk_narrowstage(a, 0), entry[0]) == 1
+        got = {"out": dev.download(ptr["out"], len(before["out"]), K.bits_dtype(cs.dt))}
+        worst, share = _check_chain(cs, got, K.chain_ref(cs), before)
+        print(f"SPEC {entry[0]} ({len(cs.lens)} utterances) worst err/bound {worst:.3f} exact share {share:.3f}")
+    finally:
+        dev.free()
+
+
+@pytest.mark.parametrize("entry", K.PAIR_DENSE_CASES, ids=[e[0] for e in K.PAIR_DENSE_CASES])
+def test_pairstream_dense_case(lib, entry):
+    """launch_pairstream across a segment seam on dense data: rms against the pure float64 chain, rows past len untouched."""
+    name, kw, vid, _ = entry
+    p = K.build_case(entry)
+    a, _ = K.gemm_struct(p, None)
+    assert lib.zvxk_gemm(a, 1) == vid, f"{name}: dry run"
+    dev = K.Device(lib)
+    try:
+        a, ptr = K.gemm_struct(p, dev)
+        assert _ran(lib.zvxk_gemm(a, 0), name) == vid, f"{name}: launch"
+        cs = K.chain_of_gemm(p)
+        nb, M, C = cs.X.shape
+        got = {}
+        for f in cs.fields():
+            buf = p.bufs[f]
+            bits = dev.download(ptr[f], len(buf["bits"]), K.bits_dtype(buf["dt"]))
+            g, b0 = bits.reshape(nb, M, cs.ld), buf["bits"].reshape(nb, M, cs.ld)
+            for b, l in enumerate(cs.lens):
+                assert (g[b, l:] == b0[b, l:]).all(), f"{name}.{f}: rows past len written"
+            got[f] = bits
+        if cs.am == 1:
+            buf = p.bufs["accum"]
+            assert (dev.download(ptr["accum"], len(buf["bits"]), K.bits_dtype(buf["dt"])) == buf["bits"]).all(), f"{name}: a running sum that is only read changed"
+        _rms_check(name, K.dense_builder(entry), cs, got, [])
+    finally:
+        dev.free()
+
+
+def test_stream_launcher_refusals(lib):
+    """Descriptors launch_resstream / launch_narrowstage must refuse, by dry run only."""
+    cs = K.build_chain(K.RESSTREAM_CASES[0])
+    a, _, _ = K.stream_struct(cs, None)
+    assert lib.zvxk_resstream(a, 1) == 20
+
+    def probe(**kw):
+        b = K.StreamArgs.from_buffer_copy(a)
+        for k, v in kw.items():
+            if isinstance(v, tuple):
+                getattr(b, k)[:] = v
+            else:
+                setattr(b, k, v)
+        return lib.zvxk_resstream(b, 1)
+
+    assert probe(ldx=40) == -1                                         # the DMA image assumes dense rows
+    assert probe(dil=(1, 3, 4)) == -1                                  # the dilations are template constants
+    assert probe(npair=4) == -1
+    assert probe(accum=0x900000, accum_mode=2) == -1                   # an output beside a running sum that is only written
+    assert probe(out=None, accum=0x900000, accum_mode=1) == -1         # nothing to write
+    assert probe(out=None, accum=0x900000, accum_mode=3) == 20
+    ns = K.build_chain(K.NARROW_CASES[0])
+    s, _, _ = K.stage_struct(ns, None)
+    assert lib.zvxk_narrowstage(s, 1) == 1
+
+    def nprobe(f):
+        b = K.StageArgs.from_buffer_copy(s)
+        f(b)
+        return lib.zvxk_narrowstage(b, 1)
+
+    def set_dil(b):
+        b.dil[0][1] = 2
+
+    def set_k(b):
+        b.ks[1] = 9
+    assert nprobe(set_dil) == 0 and nprobe(set_k) == 0
+    assert nprobe(lambda b: setattr(b, "ldo", 24)) == 0
+    assert nprobe(lambda b: setattr(b, "nk", 4)) == 0
+
+
 def test_launcher_refusals(lib):
     """Descriptors the launchers must refuse, probed with dry runs only (nothing is launched)."""
     base = K.build_case(next(e for e in K.GEMM_CASES if e[0] == "slab256_epi001_bf16"))
@@ -250,7 +462,8 @@ def test_launcher_refusals(lib):
 
 
 def test_coverage(lib):
-    """Every variant of kVariants is reached by a case of the table in every dtype it has a form for (bar the listed exclusions),
+    """Every variant of kVariants is reached by a case of the tables (GEMM_CASES; RESSTREAM_CASES / NARROW_CASES for the launchers
+    with their own argument structs) in every dtype it has a form for (bar the listed exclusions),
     and every compile-time epilogue of the 256 x 128 / 128 x 128 conv-slab tiles in every dtype it is compiled for.  Derived from
     dry runs of the whole table (nothing is launched), so it holds under any selection or order; test_gemm_case checks that each
     launch returns the id its dry run names."""
@@ -273,6 +486,16 @@ def test_coverage(lib):
         if vid in (7, 22):
             e = _effective_epi(p, vid, lib.zvxk_epi_mode(a))
             epis.add((vid, K.EPI_NAMES[e], dt + (("->" + K.DT_NAME[p.d["out_dtype"]]) if e == K.EPI_FLIP else "")))
+    # the streaming kernels with their own argument structs: dry runs of their tables
+    for entry in K.RESSTREAM_CASES:
+        cs = K.build_chain(entry)
+        vid = lib.zvxk_resstream(K.stream_struct(cs, None)[0], 1)
+        assert vid == entry[2], f"{entry[0]}: dry run picks {vid}, the case expects {entry[2]}"
+        reached.add((vid, K.DT_NAME[cs.dt]))
+    for entry in K.NARROW_CASES:
+        cs = K.build_chain(entry)
+        assert lib.zvxk_narrowstage(K.stage_struct(cs, None)[0], 1) == 1, f"{entry[0]}: the launcher declines the case"
+        reached.add((entry[2], K.DT_NAME[cs.dt]))                      # launch_narrowstage has one kernel per C: 24 (C = 16), 25 (C = 8)
     print("reached (variant, dtype):", sorted(reached))
     print("excluded:", {i: f"{names[i]}: {why}" for i, why in K.EXCLUDED_VARIANTS.items()})
     print("reached (tile, epilogue, dtype):", sorted(epis))
