@@ -190,7 +190,25 @@ def load_ktest():
     lib.zvxk_offsetof.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
     lib.zvxk_field.restype = ctypes.c_char_p
     lib.zvxk_field.argtypes = [ctypes.c_int, ctypes.c_int]
+    for name, sig in OPS_SIG.items():
+        getattr(lib, "zvxk_" + name).argtypes = [_SIG_TYPES[ch] for ch in sig]
     return lib
+
+
+# The small kernels of ops.hip (tests/ops_ref.py): zvxk_<name> takes launch_<name>'s parameters without the stream, one letter per
+# parameter: p pointer, i int, f float, l long, z size_t.  Defaulted trailing parameters of a launcher follow in its own order.
+_SIG_TYPES = {"p": ctypes.c_void_p, "i": ctypes.c_int, "f": ctypes.c_float, "l": ctypes.c_long, "z": ctypes.c_size_t}
+OPS_SIG = {
+    "cast": "pipiz", "f32_to_bf16": "ppz", "transpose16": "pipiiiip", "zero_tail_cols": "pilliiip", "split3": "pipiipii",
+    "split3_weights": "ppliif", "absmax": "pzp", "embed": "pppipippiip", "layernorm": "piipiiiipiifppplppi",
+    "softmax_rows": "pipiiiiip", "rowdot": "pipfpiipi", "bucket_embed_add": "ppipiipiip", "bucket_embed_add_ctl": "pppppipiipiip",
+    "durations": "pppppiip", "durations_q16": "ppppppiip", "length_regulate": "pippppiiii", "add_pe_cast": "pppiiiipii",
+    "instnorm_stats": "piiiipifpp", "norm_affine_act": "piipiiiipippppliif", "instnorm_fused": "piipiiiipifppppliif",
+    "mel_pad": "piiippiiipii", "copy_rows_f32": "piilplliipi", "conv_post_tanh": "piilpfiipliiipipi", "count_sat16": "pliiipip",
+    "zero_tail_rows": "piiipi", "spk_front": "pipippppppipiii", "se_pool_splits": "ii", "se_pool": "piiiipip", "se_fc": "piipppppiipip",
+    "se_apply": "pppipiiipi", "asp_pool": "pipiiipipi", "l2norm_rows": "pii", "reflect_pad": "plppliii", "stft_mag": "pipiiiip",
+    "log_clip": "piifiip", "fc_rows": "pipippiiii", "math_probe": "ippi",
+}
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -1,7 +1,8 @@
 // zvx_ktest.hip -- test-only C shim over the launchers of libzvx (tests/test_kernels_gpu.py, tests/kernel_ref.py).
-// Host code only: it is linked from the SAME object files as libzvx.so (zerovox_amd/build.py), so the kernels under test are the
-// shipped ones.  Every entry point is a plain C function with the zvxk_ prefix; the argument structs are mirrored in Python with
-// ctypes, and zvxk_sizeof / zvxk_offsetof let the tests hold that mirror to the compiled layout.
+// Host code only (but for k_math_probe, which calls nothing of the project): it is linked from the SAME object files as
+// libzvx.so (zerovox_amd/build.py), so the kernels under test are the shipped ones.  Every entry point is a plain C function with
+// the zvxk_ prefix; the argument structs are mirrored in Python with ctypes, and zvxk_sizeof / zvxk_offsetof let the tests hold
+// that mirror to the compiled layout.
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <string.h>
@@ -51,6 +52,13 @@ const Field kFields[] = {
     F_(StageArgs, res_inv_slope), F_(StageArgs, slope), F_(StageArgs, len), F_(StageArgs, M), F_(StageArgs, nbatch), F_(StageArgs, f16),
 };
 #undef F_
+
+__global__ void k_math_probe(int fn, const float* in, float* out, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float x = in[i];
+    out[i] = fn == 0 ? expf(x) : fn == 1 ? tanhf(x) : fn == 2 ? logf(x) : fn == 3 ? sqrtf(x) : 1.0f / x;
+}
 }  // namespace
 
 extern "C" {
@@ -116,6 +124,106 @@ int zvxk_narrowstage_steps(int C, int k) { return narrowstage_steps(C, k); }
 int zvxk_num_cus() { return num_cus(); }
 const char* zvxk_variant_name(int id) { return (id >= 0 && id < gemm_num_variants()) ? gemm_variant_name(id) : nullptr; }
 int zvxk_num_variants() { return gemm_num_variants(); }
+
+// ---- the small kernels of ops.hip (tests/test_ops_gpu.py, tests/ops_ref.py): the launcher's own parameter list without the stream ----
+#define ZK_(call) do { call; return sync_status(); } while (0)
+int zvxk_cast(const void* in, int in_dt, void* out, int out_dt, size_t n) { ZK_(launch_cast(in, in_dt, out, out_dt, n, nullptr)); }
+int zvxk_f32_to_bf16(const float* in, bf16_t* out, size_t n) { ZK_(launch_f32_to_bf16(in, out, n, nullptr)); }
+int zvxk_transpose16(const void* in, int ld_in, void* out, int ld_out, int B, int rows, int C, const int* len) { ZK_(launch_transpose16(in, ld_in, out, ld_out, B, rows, C, nullptr, len)); }
+int zvxk_zero_tail_cols(void* x, int es, long ld, long bs, int B, int rows, int cols, const int* len) { ZK_(launch_zero_tail_cols(x, es, ld, bs, B, rows, cols, len, nullptr)); }
+int zvxk_split3(const float* x, int ldx, void* out, int B, int rows_max, const int* rows, int C, int f16) { ZK_(launch_split3(x, ldx, out, B, rows_max, rows, C, nullptr, f16)); }
+int zvxk_split3_weights(const float* w, void* out, long nrows, int K, int f16, float scale) { ZK_(launch_split3_weights(w, out, nrows, K, nullptr, f16, scale)); }
+int zvxk_absmax(const float* x, size_t n, float* out) { ZK_(launch_absmax(x, n, out, nullptr)); }
+int zvxk_embed(const int* ph, const int* pu, const float* emb, int ed, const float* pemb, int pd, const float* pe, float* out, int B, int Tmax, const int* T) {
+    ZK_(launch_embed(ph, pu, emb, ed, pemb, pd, pe, out, B, Tmax, T, nullptr));
+}
+int zvxk_layernorm(const void* x, int x_dt, int ldx, void* y, int y_dt, int ldy, int B, int rows_max, const int* rows, int C, int mode, float eps,
+                   const float* gamma, const float* beta, const float* bg, long bg_bs, const float* post_add, void* planes, int planes_f16) {
+    ZK_(launch_layernorm(x, x_dt, ldx, y, y_dt, ldy, B, rows_max, rows, C, mode, eps, gamma, beta, bg, bg_bs, post_add, nullptr, planes, planes_f16));
+}
+int zvxk_softmax_rows(const float* sc, int lds, void* P, int p_dt, int ldp, int nbatch, int nheads, int Lmax, const int* len) {
+    ZK_(launch_softmax_rows(sc, lds, P, p_dt, ldp, nbatch, nheads, Lmax, len, nullptr));
+}
+int zvxk_rowdot(const float* x, int ldx, const float* w, float bias, float* out, int B, int Tmax, const int* T, int C) { ZK_(launch_rowdot(x, ldx, w, bias, out, B, Tmax, T, C, nullptr)); }
+int zvxk_bucket_embed_add(const float* pred, const float* table, int nbins, float* x, int ldx, int C, int* idx, int B, int Tmax, const int* T) {
+    ZK_(launch_bucket_embed_add(pred, table, nbins, x, ldx, C, idx, B, Tmax, T, nullptr));
+}
+int zvxk_bucket_embed_add_ctl(const float* pred, const float* shift, const float* range, const float* target, const float* table, int nbins, float* x,
+                              int ldx, int C, int* idx, int B, int Tmax, const int* T) {
+    ZK_(launch_bucket_embed_add_ctl(pred, shift, range, target, table, nbins, x, ldx, C, idx, B, Tmax, T, nullptr));
+}
+int zvxk_durations(const int* forced, const float* logd, int* dur, int* cum, int* mel_len, int B, int Tmax, const int* T) {
+    ZK_(launch_durations(forced, logd, dur, cum, mel_len, B, Tmax, T, nullptr));
+}
+int zvxk_durations_q16(const int* forced, const float* logd, const int* q, int* dur, int* cum, int* mel_len, int B, int Tmax, const int* T) {
+    ZK_(launch_durations_q16(forced, logd, q, dur, cum, mel_len, B, Tmax, T, nullptr));
+}
+int zvxk_length_regulate(const float* x, int ldx, const int* cum, const int* T, const int* mel_len, float* feats, int B, int Tmax, int Lmax, int C) {
+    ZK_(launch_length_regulate(x, ldx, cum, T, mel_len, feats, B, Tmax, Lmax, C, nullptr));
+}
+int zvxk_add_pe_cast(const float* x, const float* pe, void* y, int y_dt, int ldy, int B, int Lmax, const int* L, int C, int out_rows_max) {
+    ZK_(launch_add_pe_cast(x, pe, y, y_dt, ldy, B, Lmax, L, C, nullptr, out_rows_max));
+}
+int zvxk_instnorm_stats(const void* x, int x_dt, int ldx, int B, int Lmax, const int* L, int C, float eps, float* mean, float* rstd) {
+    ZK_(launch_instnorm_stats(x, x_dt, ldx, B, Lmax, L, C, eps, mean, rstd, nullptr));
+}
+int zvxk_norm_affine_act(const void* x, int x_dt, int ldx, void* y, int y_dt, int ldy, int B, int Lmax, const int* L, int C, const float* mean,
+                         const float* rstd, const float* gamma, const float* beta, long g_bs, int one_plus, int act, float slope) {
+    ZK_(launch_norm_affine_act(x, x_dt, ldx, y, y_dt, ldy, B, Lmax, L, C, mean, rstd, gamma, beta, g_bs, one_plus, act, slope, nullptr));
+}
+int zvxk_instnorm_fused(const void* x, int x_dt, int ldx, void* y, int y_dt, int ldy, int B, int Lmax, const int* L, int C, float eps, float* mean,
+                        float* rstd, const float* gamma, const float* beta, long g_bs, int one_plus, int act, float slope) {
+    ZK_(launch_instnorm_fused(x, x_dt, ldx, y, y_dt, ldy, B, Lmax, L, C, eps, mean, rstd, gamma, beta, g_bs, one_plus, act, slope, nullptr));
+}
+int zvxk_mel_pad(const void* mel, int m_dt, int ldm, int Lmax, const int* mel_len, void* v, int v_dt, int ldv, int Pmax, const int* P, int B, int nm) {
+    ZK_(launch_mel_pad(mel, m_dt, ldm, Lmax, mel_len, v, v_dt, ldv, Pmax, P, B, nm, nullptr));
+}
+int zvxk_copy_rows_f32(const void* src, int s_dt, int lds, long s_bs, float* dst, long ldd, long d_bs, int B, int rows_max, const int* rows, int C) {
+    ZK_(launch_copy_rows_f32(src, s_dt, lds, s_bs, dst, ldd, d_bs, B, rows_max, rows, C, nullptr));
+}
+int zvxk_conv_post_tanh(const void* x, int x_dt, int ldx, long x_bs, const float* w, float bias, int ktaps, int C, void* wav, long wav_bs, int pcm16,
+                        int B, int Nmax, const int* in_len, int len_mul, const int* out_len, int out_mul) {
+    ZK_(launch_conv_post_tanh(x, x_dt, ldx, x_bs, w, bias, ktaps, C, wav, wav_bs, pcm16, B, Nmax, in_len, len_mul, out_len, out_mul, nullptr));
+}
+int zvxk_count_sat16(const void* x, long bs, int ld, int B, int rows_max, const int* rows, int C, unsigned long long* count) {
+    ZK_(launch_count_sat16(x, bs, ld, B, rows_max, rows, C, count, nullptr));
+}
+int zvxk_zero_tail_rows(float* x, int ldx, int B, int rows_max, const int* rows, int C) { ZK_(launch_zero_tail_rows(x, ldx, B, rows_max, rows, C, nullptr)); }
+int zvxk_spk_front(const float* mels, int Tmax, const int* lens, int F, const float* mean, const float* rstd, const float* w, const float* bias,
+                   const float* bn_scale, const float* bn_shift, int C0, void* out, int o_dt, int B, int Wout) {
+    ZK_(launch_spk_front(mels, Tmax, lens, F, mean, rstd, w, bias, bn_scale, bn_shift, C0, out, o_dt, B, Wout, nullptr));
+}
+int zvxk_se_pool_splits(int H, int Wmax) { return se_pool_splits(H, Wmax); }
+int zvxk_se_pool(const void* x, int x_dt, int B, int H, int Wmax, const int* W, int C, float* partial) { ZK_(launch_se_pool(x, x_dt, B, H, Wmax, W, C, partial, nullptr)); }
+int zvxk_se_fc(const float* partial, int S, int H, const int* W, const float* w1, const float* b1, const float* w2, const float* b2, int C, int Cr,
+               float* scale, int B, const float* pool_bias) {
+    ZK_(launch_se_fc(partial, S, H, W, w1, b1, w2, b2, C, Cr, scale, B, nullptr, pool_bias));
+}
+int zvxk_se_apply(const void* x, const void* res, void* y, int dt, const float* scale, int B, int H, int Wmax, const int* W, int C) {
+    ZK_(launch_se_apply(x, res, y, dt, scale, B, H, Wmax, W, C, nullptr));
+}
+int zvxk_asp_pool(const void* x, int x_dt, const float* logits, int B, int F, int Wmax, const int* W, int C, float* out, int with_std) {
+    ZK_(launch_asp_pool(x, x_dt, logits, B, F, Wmax, W, C, out, with_std, nullptr));
+}
+int zvxk_l2norm_rows(float* x, int B, int C) { ZK_(launch_l2norm_rows(x, B, C, nullptr)); }
+int zvxk_reflect_pad(const float* wav, long w_bs, const int* n, float* out, long o_bs, int pad, int B, int out_cols) {
+    ZK_(launch_reflect_pad(wav, w_bs, n, out, o_bs, pad, B, out_cols, nullptr));
+}
+int zvxk_stft_mag(const float* spec, int lds_, float* mag, int ldm, int nf, int B, int Tmax, const int* frames) {
+    ZK_(launch_stft_mag(spec, lds_, mag, ldm, nf, B, Tmax, frames, nullptr));
+}
+int zvxk_log_clip(float* x, int ldx, int C, float lo, int B, int Tmax, const int* frames) { ZK_(launch_log_clip(x, ldx, C, lo, B, Tmax, frames, nullptr)); }
+int zvxk_fc_rows(const float* x, int ldx, const float* w, int ldw, const float* bias, float* out, int ldo, int B, int N, int K) {
+    ZK_(launch_fc_rows(x, ldx, w, ldw, bias, out, ldo, B, N, K, nullptr));
+}
+#undef ZK_
+// the device's own math functions over given arguments (the per-call ulp allowances of tests/ops_ref.py were measured with it; it
+// touches no code under test).  fn: 0 expf, 1 tanhf, 2 logf, 3 sqrtf, 4 1 / x
+int zvxk_math_probe(int fn, const float* in, float* out, int n) {
+    if (n <= 0) return 0;
+    hipLaunchKernelGGL(k_math_probe, dim3((n + 255) / 256), dim3(256), 0, nullptr, fn, in, out, n);
+    return sync_status();
+}
 
 // ---- layout of the argument structs ----
 long zvxk_sizeof(const char* name) {

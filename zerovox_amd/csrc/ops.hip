@@ -1281,6 +1281,11 @@ void launch_log_clip(float* x, int ldx, int C, float lo, int B, int Tmax, const 
 // out[b][n] = bias[n] + dot(x[b][0:K], w[n][0:K]) for a handful of rows b and a long K (speaker-encoder head: 50 x 5120 -> 528):
 // one wave per (output column, block of 16 rows), the K axis spread over the lanes (float4).
 // ------------------------------------------------------------------------------------------------
+// The four products of one K step as ONE fixed expression -- an explicit fma chain, nothing left to the compiler's contraction -- shared by
+// k_fc_rows and k_fc_rows4: left to itself the compiler fused the two kernels' sums differently and their results differed in the last bit.
+__device__ __forceinline__ float fc_dot4(const float4 x, const float4 w) {
+    return __builtin_fmaf(x.w, w.w, __builtin_fmaf(x.z, w.z, __builtin_fmaf(x.y, w.y, x.x * w.x)));
+}
 __global__ __launch_bounds__(64) void k_fc_rows(const float* x, int ldx, const float* w, int ldw, const float* bias, float* out, int ldo, int B, int N, int K) {
     const int n = blockIdx.x, b0 = blockIdx.y * 16, lane = threadIdx.x;
     const float* wn = w + (long)n * ldw;
@@ -1293,7 +1298,7 @@ __global__ __launch_bounds__(64) void k_fc_rows(const float* x, int ldx, const f
         for (int r = 0; r < 16; r++) {
             const int b = b0 + r < B ? b0 + r : B - 1;        // clamp: branch-free loads, surplus rows discarded below
             const float4 xv = *(const float4*)(x + (long)b * ldx + k);
-            acc[r] += xv.x * wv.x + xv.y * wv.y + xv.z * wv.z + xv.w * wv.w;
+            acc[r] += fc_dot4(xv, wv);
         }
     }
 #pragma unroll
@@ -1304,7 +1309,7 @@ __global__ __launch_bounds__(64) void k_fc_rows(const float* x, int ldx, const f
 }
 // Many rows (config 5: 250 clips per call): FOUR output columns per wave -- the 16 rows' x vectors are fetched once per four columns (the
 // one-column kernel re-read them per column: 2.8 GB through L1 / L2 for a 5 MB operand, 115 us).  Same additions in the same order per
-// output: bit-identical to k_fc_rows.
+// output (fc_dot4): bit-identical to k_fc_rows, which tests/test_ops_gpu.py holds it to.
 __global__ __launch_bounds__(64) void k_fc_rows4(const float* x, int ldx, const float* w, int ldw, const float* bias, float* out, int ldo, int B, int N, int K) {
     const int n0 = blockIdx.x * 4, b0 = blockIdx.y * 16, lane = threadIdx.x;
     const float* wn[4];
@@ -1324,7 +1329,7 @@ __global__ __launch_bounds__(64) void k_fc_rows4(const float* x, int ldx, const 
             const int b = b0 + r < B ? b0 + r : B - 1;
             const float4 xv = *(const float4*)(x + (long)b * ldx + k);
 #pragma unroll
-            for (int c = 0; c < 4; c++) acc[c][r] += xv.x * wv[c].x + xv.y * wv[c].y + xv.z * wv[c].z + xv.w * wv[c].w;
+            for (int c = 0; c < 4; c++) acc[c][r] += fc_dot4(xv, wv[c]);
         }
     }
 #pragma unroll

@@ -248,10 +248,12 @@ bool launch_attention_f32(const AttnF32Args& a, hipStream_t stream, bool dry_run
 // ------------------------------------------------------------------------------------------------
 // Small kernels (ops.hip).  T-typed pointers are void* + dtype.
 // ------------------------------------------------------------------------------------------------
-// 16-bit [b][rows][ld_in] (first C columns) -> [b][C][ld_out] (rows on the fast axis; ld_out >= rows): V -> V^T for the fused attention
-// single requests: InstanceNorm statistics + affine + activation of a 16-bit tensor in ONE launch (bit-identical to the two-kernel path)
+// single requests: InstanceNorm statistics + affine + activation of a 16-bit tensor (x and y both DT_BF16 or DT_F16) in ONE launch
+// (bit-identical to the two-kernel path: launch_instnorm_stats + launch_norm_affine_act)
 void launch_instnorm_fused(const void* x, int x_dt, int ldx, void* y, int y_dt, int ldy, int B, int Lmax, const int* L, int C, float eps,
                            float* mean, float* rstd, const float* gamma, const float* beta, long g_bs, int one_plus, int act, float slope, hipStream_t s);
+// 16-bit [b][rows][ld_in] (first C columns) -> [b][C][ld_out] (rows on the fast axis; ld_out >= rows): V -> V^T for the fused attention.
+// Every element of [C][ld_out] is written: zeros from row min(len[b], rows) on
 void launch_transpose16(const void* in, int ld_in, void* out, int ld_out, int B, int rows, int C, hipStream_t s, const int* len = nullptr);   // rows >= len[b] read as zeros
 void launch_f32_to_bf16(const float* in, bf16_t* out, size_t n, hipStream_t s);
 // x[b][r][c] = 0 for len[b] <= c < cols; es = element size (2 / 4), ld / bs = row / batch strides in elements
@@ -273,6 +275,9 @@ void launch_embed(const int* phoneme, const int* puncts, const float* emb, int e
 //   mode 0: torch LayerNorm (biased var, eps in sqrt), gamma/beta [C]
 //   mode 1: SCLN (unbiased std, /(sigma+eps)), bg rows of stride bg_bs: beta = bg[b][0:C], gamma = bg[b][C:2C]  (fs2.py:76-90)
 // post_add [B][C] (may be NULL) is added after the affine (the style-embedding add, fs2.py:740-741).
+// Rows >= rows[b] of y are not written; split_planes (f32 y only) receives what launch_split3 would write for y, zeros past rows[b] included.
+// With C % 8 == 0, C <= 1024 and ldx, ldy multiples of 8 the row is handled as 16-byte vectors: x, y, gamma, beta, bg (bg_bs % 4 == 0) and
+// post_add must then be 16-byte aligned; any other shape takes the element-wise path.
 void launch_layernorm(const void* x, int x_dt, int ldx, void* y, int y_dt, int ldy, int B, int rows_max,
                       const int* rows, int C, int mode, float eps, const float* gamma, const float* beta,
                       const float* bg, long bg_bs, const float* post_add, hipStream_t s, void* split_planes = nullptr, int planes_f16 = 0);
@@ -290,12 +295,14 @@ void launch_bucket_embed_add(const float* pred, const float* table, int nbins, f
                              int* idx_out, int B, int Tmax, const int* T, hipStream_t s);
 
 // durations: forced (int) or max(rint(exp(logd)-1),0) (fs2.py:678-681) -> dur[b][t], cum[b][t] (inclusive
-// prefix sum), mel_len[b]
+// prefix sum), mel_len[b].  A duration is clamped to [0, 65536] (NaN -> 0), cum and mel_len saturate at 2^31 - 1; T[b] == 0 writes
+// mel_len[b] = 0 and nothing else
 void launch_durations(const int* forced, const float* logd, int* dur, int* cum, int* mel_len, int B, int Tmax,
                       const int* T, hipStream_t s);
 
 // prosody control (include/zvx.h, zvx_prosody): the bucketise + embedding add on v = (p + (range[b]-1)*(p - mean_b(p))) + shift[b],
-// replaced by target[b][t] where that is not NaN (NULL pointers: neutral)
+// replaced by target[b][t] where that is not NaN (NULL pointers: neutral).  mean_b is the float64 mean of the utterance's predictions
+// rounded once to f32; a NaN prediction makes it NaN, and with a range every index of that utterance 0 (a NaN value buckets to 0)
 void launch_bucket_embed_add_ctl(const float* pred, const float* shift, const float* range, const float* target, const float* table,
                                  int nbins, float* x, int ldx, int C, int* idx_out, int B, int Tmax, const int* T, hipStream_t s);
 // launch_durations with per-phoneme Q16 factors q[b][t] applied to the running sum: cum = (sum d*q + 2^15) >> 16, dur its differences
@@ -310,7 +317,9 @@ void launch_length_regulate(const float* x, int ldx, const int* cum, const int* 
 void launch_add_pe_cast(const float* x, const float* pe, void* y, int y_dt, int ldy, int B, int Lmax,
                         const int* L, int C, hipStream_t s, int out_rows_max = 0);
 
-// InstanceNorm statistics over time for x [b][Lmax][ldx] channels [c0, c0+C): mean/rstd [B][C] (biased, eps)
+// InstanceNorm statistics over time for x [b][Lmax][ldx] channels [c0, c0+C): mean/rstd [B][C] (biased, eps); C % 8 == 0, ldx % 8 == 0.
+// A zero-length utterance (L[b] == 0) gets UNSPECIFIED statistics (0 / 0: NaN today): nothing may consume them -- launch_norm_affine_act
+// and launch_instnorm_fused write no row of such an utterance.  (k_colstats' H > 1 form, a [H][Wmax] map per utterance, has no caller.)
 void launch_instnorm_stats(const void* x, int x_dt, int ldx, int B, int Lmax, const int* L, int C, float eps,
                            float* mean, float* rstd, hipStream_t s);
 // y = act(((x-mean)*rstd) * g + b) with g = (one_plus ? 1 : 0) + gamma[b*g_bs + c], b = beta[b*g_bs + c]
@@ -512,12 +521,14 @@ void launch_count_sat16(const void* x, long bs, int ld, int B, int rows_max, con
 void launch_zero_tail_rows(float* x, int ldx, int B, int rows_max, const int* rows, int C, hipStream_t s);
 
 // ---- speaker encoder ----
-// InstanceNorm1d(80) over time + Conv2d(1->C0, 3x3, pad 1) + ReLU + BN affine -> map [b][F][Wout][C0] (Wout >= Tmax)
+// InstanceNorm1d(80) over time + Conv2d(1->C0, 3x3, pad 1) + ReLU + BN affine -> map [b][F][Wout][C0] (Wout >= Tmax); frames >= lens[b] read
+// as zero padding and columns >= lens[b] of the map are not written.  o_dt: DT_BF16 or DT_F32 (anything else is written as f32: no DT_F16)
 void launch_spk_front(const float* mels, int Tmax, const int* lens, int F, const float* mean, const float* rstd,
                       const float* w /*[9][C0]*/, const float* bias, const float* bn_scale, const float* bn_shift,
                       int C0, void* out, int o_dt, int B, int Wout, hipStream_t s);
 // SE global average pool, first half: partial[b][s][c] = sum over the s-th of S = se_pool_splits(H, Wmax) row blocks of the
-// valid (f, t) positions of map [b][H][Wmax][C]   (C % 8 == 0, C <= 256)
+// valid (f, t) positions of map [b][H][Wmax][C]   (C % 8 == 0, C <= 256).  x_dt: DT_BF16 or DT_F32 -- every other value is read as f32, so
+// DT_F16 is not a valid argument
 int se_pool_splits(int H, int Wmax);
 void launch_se_pool(const void* x, int x_dt, int B, int H, int Wmax, const int* W, int C, float* partial, hipStream_t s);
 // second half + MLP: m = sum_s partial / (H * W[b]);  scale = sigmoid(W2 relu(W1 m + b1) + b2) per clip
