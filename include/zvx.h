@@ -73,7 +73,10 @@ enum {                   /* zvx_stage_times indices (milliseconds, hipEvent-time
 /* Build a synthesis context on HIP device `device` from a text manifest + fp32 weight blob produced
  * by zerovox_amd.pack (weight-norm folded, conv weights laid out [tap][Cout][Cin]).
  * Replaces ZeroVoxTTS.__init__ / ZeroVox.load_from_checkpoint + get_meldec
- * (synthesize.py:48-97, model.py:86-118, model.py:206-249). */
+ * (synthesize.py:48-97, model.py:86-118, model.py:206-249).
+ * Generator shapes the device does not run are refused here (zvx_last_error(NULL) names the manifest key): ZVX_E_UNSUPPORTED for an
+ * upsampling stage with an odd k - u or k > 3u (voc_ksizes / voc_rates), a last stage of fewer than 8 channels in the 16-bit precision
+ * (4 in f32; voc_c0) and a ResBlock kernel of more than 16 taps (voc_rb_k); ZVX_E_MANIFEST for lists that do not fit each other. */
 zvx_status zvx_create(const char* manifest, const void* weights, size_t nbytes, int device, zvx_ctx** out);
 void       zvx_destroy(zvx_ctx* ctx);
 const char* zvx_last_error(const zvx_ctx* ctx);

@@ -714,6 +714,29 @@ void read_config(zvx_ctx* c) {
     int prod = 1; for (int r : c->voc_rates) prod *= r;
     if (prod != c->hop) fail(ZVX_E_MANIFEST, "prod(voc_rates)=%d != hop=%d", prod, c->hop);
     if (c->voc_rb_d.size() != c->voc_rb_k.size()) fail(ZVX_E_MANIFEST, "voc_rb_d / voc_rb_k size mismatch");
+    // The generator shapes the device runs (pack.check_generator_config makes the same checks and derives them; a manifest can be written
+    // by hand).  ConvTranspose1d(stride u, kernel k, padding (k - u) / 2) yields T u rows only for an even k - u, and the three polyphase
+    // taps (input rows t - 1, t, t + 1) cover the kernel iff (k - u) / 2 <= u, i.e. k <= 3u; the channel width halves per stage and the
+    // 16-bit kernels (and conv_post) read the channel axis in 16-byte groups: 8 elements, 4 in f32
+    const int ns = (int)c->voc_rates.size();
+    if (c->voc_resblock != 1 && c->voc_resblock != 2) fail(ZVX_E_MANIFEST, "voc_resblock=%d is neither 1 nor 2", c->voc_resblock);
+    if (ns < 1 || ns > 16 || c->voc_ksizes.size() != c->voc_rates.size()) fail(ZVX_E_MANIFEST, "voc_ksizes has %d entries for %d voc_rates", (int)c->voc_ksizes.size(), ns);
+    for (int i = 0; i < ns; i++) {
+        const int u = c->voc_rates[i], k = c->voc_ksizes[i];
+        if (u < 1 || k < u) fail(ZVX_E_MANIFEST, "voc_ksizes[%d]=%d is smaller than voc_rates[%d]=%d", i, k, i, u);
+        if ((k - u) % 2) fail(ZVX_E_UNSUPPORTED, "voc_ksizes[%d]=%d with voc_rates[%d]=%d: k - u is odd, the ConvTranspose1d would yield T*u + 1 rows", i, k, i, u);
+        if (k > 3 * u) fail(ZVX_E_UNSUPPORTED, "voc_ksizes[%d]=%d exceeds 3 * voc_rates[%d]=%d: three polyphase taps do not cover the kernel", i, k, i, 3 * u);
+    }
+    const int cunit = c->dt == DT_F32 ? 4 : 8;
+    if (c->voc_c0 < 1 || c->voc_c0 % (1 << ns) || (c->voc_c0 >> ns) % cunit)
+        fail(ZVX_E_UNSUPPORTED, "voc_c0=%d: the last of %d stages needs a multiple of %d channels in precision %s", c->voc_c0, ns, cunit, c->cfg["precision"].c_str());
+    if (c->voc_rb_k.empty()) fail(ZVX_E_MANIFEST, "voc_rb_k is empty");
+    for (size_t j = 0; j < c->voc_rb_k.size(); j++) {
+        if (c->voc_rb_k[j] < 1 || c->voc_rb_k[j] % 2 == 0) fail(ZVX_E_MANIFEST, "voc_rb_k[%d]=%d must be odd", (int)j, c->voc_rb_k[j]);
+        if (c->voc_rb_k[j] > ZVX_MAX_TAPS) fail(ZVX_E_UNSUPPORTED, "voc_rb_k[%d]=%d exceeds the %d taps of a convolution launch", (int)j, c->voc_rb_k[j], ZVX_MAX_TAPS);
+        if (c->voc_rb_d[j].empty()) fail(ZVX_E_MANIFEST, "voc_rb_d[%d] is empty", (int)j);
+        for (int d : c->voc_rb_d[j]) if (d < 1) fail(ZVX_E_MANIFEST, "voc_rb_d[%d] holds the dilation %d", (int)j, d);
+    }
     if (c->H % 8 || (c->H / c->enc_heads) % 8 || (c->H / c->dec_heads) % 8) fail(ZVX_E_UNSUPPORTED, "hidden/head dims must be multiples of 8");
 }
 

@@ -81,9 +81,58 @@ def _fft_block(bl, out, sd, p, kind, scln):
             bl.add(f"{out}.ln{i}_b", "p", sd[f"{p}.{nm}.layer_norm.bias"])
 
 
+def check_generator_config(h: dict, hop: int, precision: str = "bf16"):
+    """Raises ValueError (naming the config.json field) for a HiFi-GAN generator the device does not run; ``zvx_create`` makes the
+    same checks on the manifest.  The reference takes any config.json (model.py:86-118); the device covers the subset where
+
+    * ``prod(upsample_rates) == hop`` (model.py:347 cuts the waveform at mel_len * hop);
+    * every stage has ``u <= k <= 3u`` with ``k - u`` even.  ConvTranspose1d(stride u, kernel k, padding p = (k - u) // 2) yields
+      (T - 1) u + k - 2p rows: T u when k - u is even, T u + 1 when it is odd -- and every length table of the device says T u.
+      The polyphase form writes out[t u + ph] = sum_m w[ph + p + m u] x[t - m] and stores the three taps m in {-1, 0, +1}.  The
+      kernel index ph + p + m u lies in [0, k) for m >= -(ph + p) / u, lowest at ph = 0: m >= -p / u, and for
+      m <= (k - 1 - ph - p) / u, highest at ph = u - 1: m <= (k - u - p) / u = p / u (k - u = 2p).  So m = -2 is needed as soon as
+      p > u and m = +2 only from p >= 2u: three taps cover the kernel iff p <= u, i.e. k <= 3u.  k < u would make p negative
+      (torch refuses it);
+    * the channel width halves per stage, so ``upsample_initial_channel`` is a multiple of 2^stages, and the narrowest stage is a
+      multiple of 8 channels in the 16-bit precision (the MFMA kernels and conv_post read 16-byte groups of 8 elements along the
+      channel axis: a 4-channel row would be read together with its neighbour) or of 4 channels in f32."""
+    rates, ksz = list(h["upsample_rates"]), list(h["upsample_kernel_sizes"])
+    if h["resblock"] not in ("1", "2"):
+        raise ValueError(f"resblock: '{h['resblock']}' is neither '1' nor '2'")
+    if len(rates) < 1 or len(ksz) != len(rates):
+        raise ValueError(f"upsample_kernel_sizes: {len(ksz)} entries for {len(rates)} upsample_rates")
+    if int(np.prod(rates)) != hop:
+        raise ValueError(f"upsample_rates: prod({rates}) = {int(np.prod(rates))} must equal hop_size {hop} (model.py:347)")
+    for i, (u, k) in enumerate(zip(rates, ksz)):
+        if u < 1 or k < u:
+            raise ValueError(f"upsample_kernel_sizes[{i}] = {k} is smaller than upsample_rates[{i}] = {u}")
+        if (k - u) % 2:
+            raise ValueError(f"upsample_kernel_sizes[{i}] = {k}: k - u = {k - u} is odd (rate {u}): the ConvTranspose1d would "
+                             f"yield T*u + 1 rows, the device assumes T*u")
+        if k > 3 * u:
+            raise ValueError(f"upsample_kernel_sizes[{i}] = {k} exceeds 3 * upsample_rates[{i}] = {3 * u}: the three-tap "
+                             f"polyphase form does not cover the kernel")
+    C0, ns = int(h["upsample_initial_channel"]), len(rates)
+    unit = 4 if precision == "f32" else 8
+    if C0 % (1 << ns) or (C0 >> ns) % unit:
+        raise ValueError(f"upsample_initial_channel = {C0}: the last of {ns} stages would have {C0 / (1 << ns):g} channels, "
+                         f"precision {precision} needs a multiple of {unit}")
+    rk, rd = h["resblock_kernel_sizes"], h["resblock_dilation_sizes"]
+    if len(rk) < 1 or len(rd) != len(rk):
+        raise ValueError(f"resblock_dilation_sizes: {len(rd)} groups for {len(rk)} resblock_kernel_sizes")
+    for j, (k, d) in enumerate(zip(rk, rd)):
+        if k < 1 or k % 2 == 0:
+            raise ValueError(f"resblock_kernel_sizes[{j}] = {k} must be odd ('same' padding)")
+        if k > 16:
+            raise ValueError(f"resblock_kernel_sizes[{j}] = {k} exceeds the 16 taps of a convolution launch")
+        if len(d) < 1 or min(d) < 1:
+            raise ValueError(f"resblock_dilation_sizes[{j}] = {list(d)} needs at least one dilation >= 1")
+
+
 def pack_model(modelcfg: dict, tts_sd: dict, hifigan_cfg: dict, hifigan_sd: dict, precision: str = "bf16"):
     """Returns (manifest_text, blob float32[...])."""
     assert precision in ("bf16", "f32")
+    check_generator_config(hifigan_cfg, modelcfg["audio"]["hop_size"], precision)
     m = modelcfg["model"]
     enc, dec, rn = m["encoder"], m["decoder"], m["resnet"]
     H = m["emb_dim"] + m["punct_emb_dim"]
@@ -249,7 +298,6 @@ def pack_model(modelcfg: dict, tts_sd: dict, hifigan_cfg: dict, hifigan_sd: dict
     h, hsd = hifigan_cfg, hifigan_sd
     C0 = h["upsample_initial_channel"]
     rates, ksz = h["upsample_rates"], h["upsample_kernel_sizes"]
-    assert int(np.prod(rates)) == hop, "prod(upsample_rates) must equal hop (model.py:347)"
     bl.cfg("voc_resblock", h["resblock"])
     bl.cfg("voc_rates", rates)
     bl.cfg("voc_ksizes", ksz)
@@ -272,7 +320,8 @@ def pack_model(modelcfg: dict, tts_sd: dict, hifigan_cfg: dict, hifigan_sd: dict
                 kk = ph + pad + mm * u
                 if 0 <= kk < k:
                     poly[ti, ph * cout:(ph + 1) * cout, :] = wt[:, :, kk].T
-        assert abs(np.abs(poly).sum() - np.abs(wt).sum()) < 1e-3 * max(1.0, np.abs(wt).sum()), "polyphase taps must cover the kernel"
+        if int(np.count_nonzero(poly)) != int(np.count_nonzero(wt)):      # every kernel tap sits in exactly one (tap, phase) slot
+            raise ValueError(f"upsample_kernel_sizes[{i}] = {k}: the three polyphase taps do not cover the kernel (rate {u})")
         bl.add(f"voc.up{i}_w", "w", poly)
         bl.add(f"voc.up{i}_b", "p", np.tile(hsd[f"ups.{i}.bias"], u))
         if k == 2 * u and u % 2 == 0 and cin >= 256:
