@@ -562,6 +562,42 @@ zvx_status zvx_denoise_ex(zvx_ctx* ctx, const float* in, const int32_t* nsamples
                           const zvx_denoise_params* params, void* out, int64_t out_stride, int flags,
                           int64_t in_origin, int64_t out_begin, int64_t out_count, int last);
 
+/* A window per row: zvx_denoise_rows and zvx_limit_rows are zvx_denoise_ex / zvx_limit_ex with win[b] (a HOST array of B entries) in place of
+ * the call's one window, for a caller that holds several signals at different positions -- B streams, each somewhere else on its signal, in
+ * ONE call and one launch sequence instead of B.  Row b holds samples [in_origin, in_origin + nsamples[b]) of its signal; the outputs
+ * [out_begin, out_begin + cnt_b) go to positions [0, cnt_b) of out row b.  The rows-call contract is the _ex calls': strided rows on the
+ * host or on the device, the same flags, syncs and queued form; the denoiser's bias, strength and floor and the limiter's ceiling,
+ * window_ms and oversample stay per CALL (the gain launch's LDS layout depends on W).
+ * Contract: row b's emitted samples are bit for bit those of the _ex call on that row alone with win[b], and therefore those of the
+ *   whole-signal call (f32, and int16 with ZVX_PCM16).  Independently per row: peak_in[b] / min_gain[b] cover the row's emitted range (0 and
+ *   1 where it is empty); out_count == -1 needs that row's last; an empty range writes nothing; a row's bits depend neither on which other
+ *   rows share the call nor on their windows; nothing outside [0, cnt_b) of an output row is touched.
+ * How: the kernels of all three forms resolve one row descriptor at their top -- input, output and work-buffer / envelope pointers, length,
+ *   emitted range, and for the denoiser origin, first frame, skip, rel and the two mirrors -- and work from it alone; the per-row calls read
+ *   it from a device table (uploaded through the context's pinned staging, queued like a launch), the uniform calls form the same thing from
+ *   their arguments.  One body, so no two forms can contract a multiply-add differently.  Each denoiser row's first frame is rounded down to
+ *   a multiple of 4096 / n_fft on its OWN grid, so a frame keeps the slot it has in the whole call; the signal's frame count is formed in
+ *   64 bits from the row's origin; the overlap-add sums in ascending f.  The limiter's envelope runs on each row's own tile grid over its
+ *   window, the gain tiles start at the row's own offset, the sums keep their orders.  No index is formed in 32 bits from an absolute
+ *   position: a row's in_origin may lie beyond 2^32.  Grids are sized by the longest row; workgroups past a row's extent return at once.
+ * Validation, all before anything is queued (ZVX_E_INVALID, the context stays usable): every check of the _ex call, the window's checks and
+ *   the support condition per row with the message naming the row; a NULL win; reserved != 0; out_stride smaller than the longest cnt_b;
+ *   out == in unless every row with cnt_b > 0 has out_begin == in_origin; for the denoiser zvx_melspec's length conditions on each row whose
+ *   window is last.  strength == 0 stays a copy of each emitted range.
+ * Accounting: the tags stay "post.denoise" / "post.limit", one timed group per call; bytes are the sum over the rows of what the one-row _ex
+ *   calls count.
+ * zvx_resample_ex has another window contract (its rows are zero outside the window and it has no support condition): it has no rows form. */
+typedef struct zvx_row_window {
+    int64_t in_origin, out_begin, out_count;   /* as the _ex calls' parameters; out_count -1: to the end of the row's signal (needs last) */
+    int32_t last;                              /* 0 or 1 */
+    int32_t reserved;                          /* must be 0 */
+} zvx_row_window;
+zvx_status zvx_denoise_rows(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias,
+                            const zvx_denoise_params* params, void* out, int64_t out_stride, int flags, const zvx_row_window* win);
+zvx_status zvx_limit_rows(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, int rate,
+                          const zvx_limit_params* params, void* out, int64_t out_stride, float* peak_in, float* min_gain, int flags,
+                          const zvx_row_window* win);
+
 /* Stream sessions: chunked vocoding of ONE utterance with the planning inside the library.  A session owns the utterance's mel on the
  * device, vocodes it group by group and runs the new samples device to device through the optional denoiser, limiter and rate conversion;
  * each zvx_stream_next hands out one finished piece with one wait.  It is what ZeroVox.vocode_stream does with three Python planners and
@@ -644,8 +680,18 @@ zvx_status zvx_stream_close(zvx_stream* s);
  *   behind the history of the owning session's first stage buffer (to that session's final destination where it has no stage).  Their
  *   per-row tables (source mel pointer and frame count; source offset, count and destination pointer) are built on the host and uploaded
  *   through the context's pinned staging, queued like a launch: no host wait.
- * Post stages: each session's new samples then go through that session's own stages, one row and that session's window per call of the
- *   internal _ex forms, exactly as in zvx_stream_next.  (Batching them across sessions needs per-row windows in those forms: not here.)
+ * Post stages: batched across the sessions through the per-row forms behind zvx_denoise_rows / zvx_limit_rows.  The stages run kind by
+ *   kind -- all denoisers, then all limiters, then the rate conversions -- on the one stream; a session's chain order denoise -> limit ->
+ *   resample is kept.  Within a kind the sessions whose stage has bitwise-equal parameters form one group (the bias compared by content;
+ *   the limiter's class is W, oversampling and ceiling), and a group is ONE call of the per-row form: its rows are the sessions'
+ *   [history | new] buffers, each with that session's own window, and each output goes straight behind the next stage's history or to the
+ *   session's final destination.  Groups run in the order of their first member, rows within a group in call order, and the bias is
+ *   uploaded once per group (the partition is zvx_plan::partition_classes in zerovox_amd/csrc/stream_plan.h).  Each group counts under
+ *   "post.denoise" / "post.limit" as one timed group with the bytes its sessions' single steps count in sum.  A stage that emits nothing
+ *   in this call takes no part.  The rate conversion stays one call per session: zvx_resample_ex has another window contract (zero
+ *   outside the window, no support condition) and no per-row form.  The history drops of all stages of all sessions are ONE launch over a
+ *   table of (source, destination, count), each retained tail into its stage's other buffer, under the stage tag "post.stream".
+ *   zvx_stream_next itself stays on the one-row _ex forms; the bits are the same either way, which is the per-row contract.
  * One wait: host pieces travel through each session's pinned buffer -- all copies are queued, the call waits once, then copies out.  With
  *   ZVX_DEVICE_OUT every out[i] is a device pointer; with ZVX_DEVICE_OUT | ZVX_NO_SYNC the call only queues.  Everything runs on the
  *   context's main stream.  The context's intermediates are void afterwards, as after zvx_stream_next.

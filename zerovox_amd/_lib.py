@@ -26,7 +26,8 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_dev_alloc", "zvx_dev_free", "zvx_dev_from_host", "zvx_dev_to_host", "zvx_spkemb_ex", "zvx_wait_host",
            "zvx_encode_ex", "zvx_synthesize_ex", "zvx_resample", "zvx_resample_ex", "zvx_trim_bounds", "zvx_join",
            "zvx_loudness", "zvx_normalize", "zvx_true_peak", "zvx_limit", "zvx_spkemb_wav", "zvx_limit_ex", "zvx_denoise_bias", "zvx_denoise",
-           "zvx_denoise_ex", "zvx_stream_open", "zvx_stream_next", "zvx_stream_info", "zvx_stream_close", "zvx_stream_next_many")
+           "zvx_denoise_ex", "zvx_stream_open", "zvx_stream_next", "zvx_stream_info", "zvx_stream_close", "zvx_stream_next_many",
+           "zvx_denoise_rows", "zvx_limit_rows")
 ZVX_STREAM_MANY_MAX_SESSIONS, ZVX_STREAM_MANY_MAX_ROWS = 64, 256
 ZVX_COMM_ID_BYTES = 128
 ZVX_LOUD_PER_ROW, ZVX_LOUD_COMMON = 0, 1
@@ -72,6 +73,11 @@ class LimitParams(C.Structure):
 class DenoiseParams(C.Structure):
     """zvx_denoise_params (include/zvx.h)"""
     _fields_ = [("strength", C.c_float), ("floor", C.c_float)]
+
+
+class RowWindow(C.Structure):
+    """zvx_row_window (include/zvx.h)"""
+    _fields_ = [("in_origin", C.c_int64), ("out_begin", C.c_int64), ("out_count", C.c_int64), ("last", C.c_int32), ("reserved", C.c_int32)]
 
 
 class StreamParams(C.Structure):
@@ -150,6 +156,8 @@ def load():
     lib.zvx_denoise_bias.argtypes = [vp, vp]
     lib.zvx_denoise.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(DenoiseParams), vp, C.c_int64, C.c_int]
     lib.zvx_denoise_ex.argtypes = lib.zvx_denoise.argtypes + [C.c_int64, C.c_int64, C.c_int64, C.c_int]
+    lib.zvx_denoise_rows.argtypes = lib.zvx_denoise.argtypes + [C.POINTER(RowWindow)]
+    lib.zvx_limit_rows.argtypes = lib.zvx_limit.argtypes + [C.POINTER(RowWindow)]
     lib.zvx_stream_open.argtypes = [vp, vp, C.c_int, C.POINTER(StreamParams), C.c_int, C.POINTER(vp)]
     lib.zvx_stream_next.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int]
     lib.zvx_stream_info.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
@@ -543,6 +551,45 @@ class Context:
         self._chk(self._lib.zvx_denoise_ex(self._h, _ptr(x), _ptr(n), B, Nmax, _ptr(bias), C.byref(prm), _ptr(out), out.shape[1], flags,
                                            int(in_origin), int(out_begin), int(out_count), 1 if last else 0))
         return out[:, :cols]
+
+    @staticmethod
+    def _row_windows(windows, n, Nmax, pcm16):
+        """a list of (in_origin, out_begin, out_count, last), one per row -> (RowWindow array, out [B][stride] of zeros, cnt [B]: the
+        emitted samples of each row)"""
+        if len(windows) != len(n):
+            raise ValueError(f"{len(windows)} windows for {len(n)} rows")
+        win = (RowWindow * max(len(n), 1))()
+        cnt = np.zeros(len(n), np.int64)
+        for b, (in_origin, out_begin, out_count, last) in enumerate(windows):
+            win[b] = RowWindow(int(in_origin), int(out_begin), int(out_count), 1 if last else 0, 0)
+            cnt[b] = int(out_count) if out_count >= 0 else max(0, int(in_origin) + int(n[b]) - int(out_begin))
+        cols = int(cnt.max()) if len(cnt) else 0
+        return win, np.zeros((len(n), max(cols, Nmax)), np.int16 if pcm16 else np.float32), cnt
+
+    def denoise_rows(self, rows, bias, strength, windows, floor=0.0, pcm16=False, lengths=None):
+        """zvx_denoise_rows on host rows: denoise_window with a window per row -- windows[b] = (in_origin, out_begin, out_count, last) says
+        which samples of its signal row b holds and which outputs of the whole-signal denoiser it emits -> a list of B arrays, row b's
+        emitted samples (float32 / int16), bit for bit those of denoise_window on that row alone."""
+        x, n = self._rows(rows, lengths)
+        B, Nmax = x.shape
+        bias = self._denoise_bias_arg(bias)
+        prm, flags = self._denoise_args(strength, floor, pcm16=pcm16)
+        win, out, cnt = self._row_windows(windows, n, Nmax, pcm16)
+        self._chk(self._lib.zvx_denoise_rows(self._h, _ptr(x), _ptr(n), B, Nmax, _ptr(bias), C.byref(prm), _ptr(out), out.shape[1], flags, win))
+        return [out[b, :cnt[b]] for b in range(B)]
+
+    def limit_rows(self, rows, ceiling, windows, window_ms=5.0, oversample=4, pcm16=False, rate=None, lengths=None):
+        """zvx_limit_rows on host rows: limit_window with a window per row (windows[b] = (in_origin, out_begin, out_count, last)) -> (a list
+        of B arrays, row b's emitted samples, peak_in [B], min_gain [B] float32, both over each row's emitted samples only), bit for bit
+        what limit_window gives on each row alone."""
+        x, n = self._rows(rows, lengths)
+        B, Nmax = x.shape
+        prm, flags = self._limit_args(ceiling, window_ms, oversample, pcm16=pcm16)
+        win, out, cnt = self._row_windows(windows, n, Nmax, pcm16)
+        peak, gmin = np.zeros(B, np.float32), np.zeros(B, np.float32)
+        self._chk(self._lib.zvx_limit_rows(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), out.shape[1], _ptr(peak),
+                                           _ptr(gmin), flags, win))
+        return [out[b, :cnt[b]] for b in range(B)], peak, gmin
 
     def denoise_device(self, ptr, lengths, Nmax, bias, strength, *, floor=0.0, no_sync=False):
         """zvx_denoise IN PLACE on device rows [B][Nmax] f32 at `ptr` (they may be the output of a synthesize / vocode_device call queued

@@ -1707,7 +1707,7 @@ void launch_stream_interiors(const StreamInteriorArgs& a, long cnt_max, hipStrea
 }
 
 // The same two movements for the rows of MANY sessions (zvx_stream_next_many): every row has its own source mel / its own destination, so
-// the per-row entries come from a table in device memory -- one 16-byte entry per row, indexed by blockIdx.y, the same for every lane of a
+// the per-row entries come from a table in device memory -- one small entry per row, indexed by blockIdx.y, the same for every lane of a
 // workgroup (a scalar load).  Rows of one call differ a lot in length: a block past its row's end leaves before it touches anything else.
 __global__ __launch_bounds__(256) void k_stream_rows_many(const StreamManyRowsArgs a) {
     const int b = blockIdx.y;
@@ -1745,7 +1745,7 @@ __global__ __launch_bounds__(256) void k_stream_interiors_many(const StreamManyI
     const StreamManyInterior t = a.tab[b];
     const long cnt = t.cnt;
     if ((long)blockIdx.x * 1024 - 3 >= cnt) return;                    // the whole block lies past this row's interior
-    const float* src = a.wav + (long)b * a.w_bs + t.off;
+    const float* src = (t.src ? t.src : a.wav + (long)b * a.w_bs) + t.off;
     float* dst = t.dst;
     const int mis = (int)(((size_t)dst >> 2) & 3);
     const long o = ((long)blockIdx.x * 256 + threadIdx.x) * 4 - mis;
@@ -1992,6 +1992,17 @@ __device__ __forceinline__ float f32_toward_zero(double g) {
     if (fabs((double)f) > fabs(g)) f = __uint_as_float(__float_as_uint(f) - 1u);
     return f;
 }
+// The row a workgroup works on (zvx_kernels.h, LimitRow): its entry of the table, or the same thing formed from the uniform fields.  b is a
+// block index: the same for every lane, so the entry arrives through scalar loads.
+__device__ __forceinline__ LimitRow lim_row(const LimitArgs& a, int b) {
+    if (a.rows) return a.rows[b];
+    LimitRow r;
+    r.x = a.x + (long)b * a.x_bs;
+    r.out = a.pcm16 ? (void*)((short*)a.out + (long)b * a.out_bs) : (void*)((float*)a.out + (long)b * a.out_bs);
+    r.env = a.env ? a.env + (long)b * a.e_bs : nullptr;
+    r.n = a.nsamples[b]; r.off = a.off; r.cnt = a.cnt[b]; r.pad_ = 0;
+    return r;
+}
 // Oversampled point m = os k0 + p is the resampler's output for (L, M) = (os, 1): its window starts at x[k0 - 10] for p = 0 and at
 // x[k0 - 9] otherwise, and it is summed as k_resample_poly sums it -- acc = bank[p][0] * x[ks]; acc = fma(bank[p][t], x[ks + t], acc).
 // The workgroup evaluates the points of samples t0 - 1 .. t0 + LIMIT_TILE - 1 (those of t0 - 1 count for the envelope of t0) and keeps,
@@ -2003,11 +2014,12 @@ __global__ __launch_bounds__(256) void k_limit_env(const LimitArgs a) {
     __shared__ __attribute__((aligned(16))) float bks[8 * LIM_BP];
     __shared__ float red[4];
     const int b = blockIdx.y, tid = threadIdx.x;
-    const int n = a.nsamples[b];
+    const LimitRow r = lim_row(a, b);
+    const int n = r.n;
     const long t0 = (long)blockIdx.x * LIMIT_TILE;
     float pk = 0.f;
     if (t0 < n) {                                            // (uniform over the workgroup)
-        const float* xrow = a.x + (long)b * a.x_bs;
+        const float* xrow = r.x;
         const long base = t0 - 1 - LIM_LO;                   // xs[j] = x[base + j], 0 outside the row
         for (int j = tid; j < LIM_XS; j += 256) { const long g = base + j; xs[j] = (g >= 0 && g < n) ? xrow[g] : 0.f; }
         if (OS > 1)
@@ -2034,8 +2046,8 @@ __global__ __launch_bounds__(256) void k_limit_env(const LimitArgs a) {
             eo[j] = e; uo[j] = u;
         }
         __syncthreads();
-        float* erow = a.env ? a.env + (long)b * a.e_bs : nullptr;
-        const long o0 = a.off, o1 = o0 + a.cnt[b];           // the partial maximum runs over the emitted samples only
+        float* erow = r.env;
+        const long o0 = r.off, o1 = o0 + r.cnt;              // the partial maximum runs over the emitted samples only
 #pragma unroll
         for (int q = 0; q < LIMIT_TILE / 256; q++) {
             const int j = 1 + tid + 256 * q;
@@ -2072,14 +2084,15 @@ __global__ __launch_bounds__(256) void k_limit_gain(const LimitArgs a) {
     float* es = (float*)(Ds + SD);
     float* red = es + SE;                                    // (no static LDS: the opt-in beyond 64 KiB covers the dynamic part alone)
     const int b = blockIdx.y, tid = threadIdx.x;
-    const int n = a.nsamples[b];
-    const long t0 = a.off + (long)blockIdx.x * LIMIT_TILE;   // the tiles cover the emitted range [off, iend), wherever `off` lies
-    const long iend = min((long)n, (long)a.off + a.cnt[b]);
+    const LimitRow r = lim_row(a, b);
+    const int n = r.n;
+    const long t0 = r.off + (long)blockIdx.x * LIMIT_TILE;   // the tiles cover the emitted range [off, iend), wherever `off` lies
+    const long iend = min((long)n, (long)r.off + r.cnt);
     constexpr int Q = LIMIT_TILE / 256;
     float gmin = 1.f;
     if (t0 < iend) {                                         // (uniform over the workgroup)
-        const float* erow = a.env + (long)b * a.e_bs;
-        const float* xrow = a.x + (long)b * a.x_bs;
+        const float* erow = r.env;
+        const float* xrow = r.x;
         const long eb = t0 - 2L * W;                         // es[j] = e[eb + j]
         float mx = 0.f;
         for (int j = tid; j < SE; j += 256) {
@@ -2140,8 +2153,8 @@ __global__ __launch_bounds__(256) void k_limit_gain(const LimitArgs a) {
             const long i = t0 + tid + 256 * q;
             if (i < iend) {
                 const float v = xrow[i] * g32[q];
-                if (a.pcm16) ((short*)a.out)[(long)b * a.out_bs + (i - a.off)] = join_pcm(v);
-                else ((float*)a.out)[(long)b * a.out_bs + (i - a.off)] = v;
+                if (a.pcm16) ((short*)r.out)[i - r.off] = join_pcm(v);
+                else ((float*)r.out)[i - r.off] = v;
                 gmin = fminf(gmin, g32[q]);
             }
         }

@@ -80,40 +80,54 @@ __device__ __forceinline__ void dn_fft(float* sre, float* sim, const float2* __r
     }
 }
 
+// The row a workgroup works on (zvx_kernels.h, DenoiseRow): its entry of the table, or the same thing formed from the uniform fields.  b is
+// blockIdx.y: the same for every lane, so the entry arrives through scalar loads.
+__device__ __forceinline__ DenoiseRow dn_row(const DenoiseArgs& a, int b) {
+    if (a.rows) return a.rows[b];
+    DenoiseRow r;
+    r.x = a.x + (long)b * a.x_bs;
+    r.out = a.pcm16 ? (void*)((short*)a.out + (long)b * a.out_bs) : (void*)((float*)a.out + (long)b * a.out_bs);
+    r.work = a.work + (long)b * a.Fmax * a.n_fft;
+    r.origin = a.origin; r.f_first = a.f_first;
+    r.n = a.nsamples[b]; r.skip = a.skip; r.rel = a.rel; r.off = a.off; r.cnt = a.cnt; r.mirrors = (a.left ? 1 : 0) | (a.right ? 2 : 0);
+    return r;
+}
 // The window of a row of n samples (zvx_kernels.h, DenoiseArgs): the emitted count; the signal's frames from f_first on (all there will be
 // where the signal goes on); the frames transformed, i.e. those up to the last one that begins at or before the last emitted sample.
-__device__ __forceinline__ int dn_count(const DenoiseArgs& a, int n) {
-    const int room = max(0, n - a.off);
-    return a.cnt >= 0 ? min(a.cnt, room) : room;
+__device__ __forceinline__ int dn_count(const DenoiseRow& r) {
+    const int room = max(0, r.n - r.off);
+    return r.cnt >= 0 ? min(r.cnt, room) : room;
 }
-__device__ __forceinline__ int dn_frames_from_first(const DenoiseArgs& a, int n) {
-    if (n <= 0) return 0;
-    if (!a.right) return INT_MAX;
-    const long span = a.origin + n + 2 * a.pad - a.n_fft;   // absolute: 64 bits
-    const long F = span >= 0 ? 1 + span / a.hop - a.f_first : 0;
+__device__ __forceinline__ int dn_frames_from_first(const DenoiseArgs& a, const DenoiseRow& r) {
+    if (r.n <= 0) return 0;
+    if (!(r.mirrors & 2)) return INT_MAX;
+    const long span = r.origin + r.n + 2 * a.pad - a.n_fft;   // absolute: 64 bits
+    const long F = span >= 0 ? 1 + span / a.hop - r.f_first : 0;
     return (int)min(max(F, 0L), (long)INT_MAX);
 }
-__device__ __forceinline__ int dn_frames_used(const DenoiseArgs& a, int n) {
-    const int cnt = dn_count(a, n);
+__device__ __forceinline__ int dn_frames_used(const DenoiseArgs& a, const DenoiseRow& r) {
+    const int cnt = dn_count(r);
     if (cnt <= 0) return 0;
-    return min(dn_frames_from_first(a, n), (a.off + cnt - 1 - a.rel) / a.hop + 1);
+    return min(dn_frames_from_first(a, r), (r.off + cnt - 1 - r.rel) / a.hop + 1);
 }
 
 __global__ __launch_bounds__(DN_THREADS) void k_denoise_frames(const DenoiseArgs a) {
     __shared__ float sre[DN_PLANE], sim[DN_PLANE];
     const int tid = threadIdx.x, b = blockIdx.y, N = a.n_fft, lg = a.log2n;
-    const int n = a.nsamples[b];
-    const int F = dn_frames_used(a, n);                      // frames f_first .. f_first + F - 1 of the signal, f below counted from f_first
+    const DenoiseRow r = dn_row(a, b);
+    const int n = r.n;
+    const int F = dn_frames_used(a, r);                      // frames f_first .. f_first + F - 1 of the signal, f below counted from f_first
     const int f0 = blockIdx.x * (DENOISE_POINTS >> lg);
     if (f0 >= F) return;                                     // (uniform over the workgroup)
-    const float* x = a.x + (long)b * a.x_bs;
+    const float* x = r.x;
+    const bool left = r.mirrors & 1, right = r.mirrors & 2;
     for (int i = tid; i < DENOISE_POINTS; i += DN_THREADS) {
         const int f = f0 + (i >> lg), t = i & (N - 1);
         float v = 0.f;
-        if (f < F && f >= a.skip) {
-            int s = a.rel + f * a.hop + t;                   // numpy 'reflect' where the signal's end is in the window; inside the window for every
-            if (a.left && s < 0) s = -s;                     // validated length and support, clamped all the same
-            if (a.right && s >= n) s = 2 * (n - 1) - s;
+        if (f < F && f >= r.skip) {
+            int s = r.rel + f * a.hop + t;                   // numpy 'reflect' where the signal's end is in the window; inside the window for every
+            if (left && s < 0) s = -s;                       // validated length and support, clamped all the same
+            if (right && s >= n) s = 2 * (n - 1) - s;
             s = min(max(s, 0), n - 1);
             v = a.win[t] * x[s];
         }
@@ -125,7 +139,7 @@ __global__ __launch_bounds__(DN_THREADS) void k_denoise_frames(const DenoiseArgs
     if (a.mag) {                                             // magnitude-out mode (zvx_denoise_bias)
         for (int g = tid; g < items; g += DN_THREADS) {
             const int q = g / nf, k = g - q * nf, i = dn_at((q << lg) + k);
-            if (f0 + q < F && f0 + q >= a.skip) a.mag[((long)b * a.Fmax + f0 + q) * nf + k] = sqrtf(sre[i] * sre[i] + sim[i] * sim[i]);
+            if (f0 + q < F && f0 + q >= r.skip) a.mag[((long)b * a.Fmax + f0 + q) * nf + k] = sqrtf(sre[i] * sre[i] + sim[i] * sim[i]);
         }
         return;
     }
@@ -146,23 +160,24 @@ __global__ __launch_bounds__(DN_THREADS) void k_denoise_frames(const DenoiseArgs
     const float inv_n = 1.f / (float)N;                      // a power of two: exact
     for (int i = tid; i < DENOISE_POINTS; i += DN_THREADS) {
         const int f = f0 + (i >> lg), t = i & (N - 1);
-        if (f < F && f >= a.skip) a.work[((long)b * a.Fmax + f) * N + t] = a.win[t] * (sre[dn_at(i)] * inv_n);
+        if (f < F && f >= r.skip) r.work[(long)f * N + t] = a.win[t] * (sre[dn_at(i)] * inv_n);
     }
 }
 
 __device__ __forceinline__ short dn_pcm(float v) { return (short)fminf(fmaxf(v * 32760.0f, -32768.0f), 32767.0f); }   // the resampler's rule
 
 __global__ __launch_bounds__(256) void k_denoise_ola(const DenoiseArgs a) {
-    const int b = blockIdx.y, n = a.nsamples[b], N = a.n_fft;
+    const int b = blockIdx.y, N = a.n_fft;
+    const DenoiseRow r = dn_row(a, b);
     const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= dn_count(a, n)) return;
-    const int i = a.off + e;                                 // the sample's index in the window
-    const float xi = a.x[(long)b * a.x_bs + i];
+    if (e >= dn_count(r)) return;
+    const int i = r.off + e;                                 // the sample's index in the window
+    const float xi = r.x[i];
     float v = xi;
     if (!a.copy) {
-        const int F = dn_frames_from_first(a, n), p = i - a.rel;                             // p: the padded position, counted from frame f_first's
+        const int F = dn_frames_from_first(a, r), p = i - r.rel;                             // p: the padded position, counted from frame f_first's
         const int f_hi = min(F - 1, p / a.hop), f_lo = p < N ? 0 : (p - N) / a.hop + 1;      // frames f with f hop <= p < f hop + n_fft
-        const float* w = a.work + (long)b * a.Fmax * N;
+        const float* w = r.work;
         float num = 0.f;
         double den = 0.0;
         for (int f = f_lo; f <= f_hi; f++) {                 // ascending f: the order is part of the contract
@@ -172,8 +187,8 @@ __global__ __launch_bounds__(256) void k_denoise_ola(const DenoiseArgs a) {
         }
         if (den >= a.den_min) v = num / (float)den;
     }
-    if (a.pcm16) ((short*)a.out)[(long)b * a.out_bs + e] = dn_pcm(v);
-    else ((float*)a.out)[(long)b * a.out_bs + e] = v;
+    if (a.pcm16) ((short*)r.out)[e] = dn_pcm(v);
+    else ((float*)r.out)[e] = v;
 }
 
 void launch_denoise_frames(const DenoiseArgs& a, hipStream_t s) {

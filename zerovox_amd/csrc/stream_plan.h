@@ -8,6 +8,7 @@
 // Every position is an int64_t: a stream may run past 2^32 samples.
 // group_rows, at the end, is the arithmetic of one group's rows -- the frames with halo, the kept interior, the running position -- that
 // zvx_stream_next and zvx_stream_next_many share (tests/native/stream_group_main.cpp checks it against ZeroVox._vocode_stream_native).
+// partition_classes is how zvx_stream_next_many batches one kind of post stage over its sessions (tests/native/stream_classes_main.cpp).
 #ifndef ZVX_STREAM_PLAN_H
 #define ZVX_STREAM_PLAN_H
 
@@ -90,6 +91,25 @@ inline Group group_rows(int64_t frames, int64_t chunk, int64_t halo, int64_t hop
         g.Pmax = imax(g.Pmax, hi - lo); g.cnt_max = imax(g.cnt_max, n * hop); g.n_new += n * hop;
     }
     return g;
+}
+
+// The batches of ONE kind of post stage over the n sessions of a zvx_stream_next_many call.  cls[i] is the class of session i's stage --
+// sessions whose stage has bitwise-equal parameters carry the same id, any int >= 0 -- or negative where session i runs no such stage in
+// this call.  Sessions of one class form one group, i.e. one call of the per-row form; the groups come in the order of their first member
+// and the members of a group in call order.  order[] (n entries at most) takes the members group by group, start[g] is where group g begins
+// in it and start[groups] the number of members (n + 1 entries at most).  Returns the number of groups.
+inline int partition_classes(const int* cls, int n, int* order, int* start) {
+    int groups = 0, m = 0;
+    for (int i = 0; i < n; i++) {
+        if (cls[i] < 0) continue;
+        bool seen = false;
+        for (int j = 0; j < i && !seen; j++) seen = cls[j] == cls[i];
+        if (seen) continue;
+        start[groups++] = m;
+        for (int j = i; j < n; j++) if (cls[j] == cls[i]) order[m++] = j;
+    }
+    start[groups] = m;
+    return groups;
 }
 
 }  // namespace zvx_plan

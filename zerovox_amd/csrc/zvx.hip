@@ -437,6 +437,7 @@ struct zvx_stream {
     zvx_denoise_params dn{};
     std::vector<float> bias;
     zvx_limit_params lim{};
+    int lim_W = 0;                         // the limiter's window in samples
     char* dev = nullptr;                   // ONE device allocation: the mel, a group's rows, the vocoder's rows, the stage buffers, the host piece's staging
     float* mel = nullptr;
     float* rows = nullptr;
@@ -2530,29 +2531,36 @@ const double* limit_win(zvx_ctx* c, int W) {
 struct RowsWindow { int64_t in_origin = 0, out_begin = 0, out_count = -1; int last = 1; };
 // per row the emitted count, after the window's own checks and the support condition of include/zvx.h for the reach R (zvx_limit_ex:
 // 2 W + H; zvx_denoise_ex: n_fft - 1)
-std::vector<int32_t> window_counts(const char* who, const RowsWindow& w, const int32_t* nsamples, int B, int64_t R) {
-    if (w.in_origin < 0 || w.out_begin < 0) fail(ZVX_E_INVALID, "%s: in_origin %lld / out_begin %lld is negative", who, (long long)w.in_origin, (long long)w.out_begin);
-    if (w.out_count < -1) fail(ZVX_E_INVALID, "%s: out_count %lld (-1: to the end of the signal)", who, (long long)w.out_count);
-    if (w.last != 0 && w.last != 1) fail(ZVX_E_INVALID, "%s: last is %d (0 or 1)", who, w.last);
-    if (w.out_count == -1 && !w.last) fail(ZVX_E_INVALID, "%s: out_count -1 needs last: the signal's end is not in the window", who);
-    std::vector<int32_t> cnt(B);
-    for (int b = 0; b < B; b++) {
-        const int64_t end_in = w.in_origin + nsamples[b];
-        const int64_t n = w.out_count >= 0 ? w.out_count : std::max<int64_t>(0, end_in - w.out_begin);
-        if (n > 0) {
-            const int64_t end_out = w.out_begin + n;
-            if (w.in_origin > w.out_begin || end_out > end_in)
-                fail(ZVX_E_INVALID, "%s: row %d: outputs [%lld, %lld) lie outside the window's samples [%lld, %lld)", who, b, (long long)w.out_begin,
-                     (long long)end_out, (long long)w.in_origin, (long long)end_in);
-            if (w.in_origin != 0 && w.out_begin - R < w.in_origin)
-                fail(ZVX_E_INVALID, "%s: row %d: the reach R = %lld needs %lld more samples in front of the window (in_origin %lld, out_begin %lld)", who, b,
-                     (long long)R, (long long)(w.in_origin - (w.out_begin - R)), (long long)w.in_origin, (long long)w.out_begin);
-            if (!w.last && end_out - 1 + R > end_in - 1)
-                fail(ZVX_E_INVALID, "%s: row %d: the reach R = %lld needs %lld more samples behind the window (outputs end at %lld, samples at %lld; or last)", who, b,
-                     (long long)R, (long long)(end_out + R - end_in), (long long)end_out, (long long)end_in);
-        }
-        cnt[b] = (int32_t)n;                                 // n <= nsamples[b] where n > 0
+// (`row` >= 0: the window is that row's own -- zvx_denoise_rows, zvx_limit_rows -- and every message names it)
+void window_args_check(const char* who, const RowsWindow& w, int row = -1) {
+    char at[32] = "";
+    if (row >= 0) snprintf(at, sizeof at, "row %d: ", row);
+    if (w.in_origin < 0 || w.out_begin < 0) fail(ZVX_E_INVALID, "%s: %sin_origin %lld / out_begin %lld is negative", who, at, (long long)w.in_origin, (long long)w.out_begin);
+    if (w.out_count < -1) fail(ZVX_E_INVALID, "%s: %sout_count %lld (-1: to the end of the signal)", who, at, (long long)w.out_count);
+    if (w.last != 0 && w.last != 1) fail(ZVX_E_INVALID, "%s: %slast is %d (0 or 1)", who, at, w.last);
+    if (w.out_count == -1 && !w.last) fail(ZVX_E_INVALID, "%s: %sout_count -1 needs last: the signal's end is not in the window", who, at);
+}
+int32_t window_count_row(const char* who, const RowsWindow& w, int32_t nsamples, int b, int64_t R) {
+    const int64_t end_in = w.in_origin + nsamples;
+    const int64_t n = w.out_count >= 0 ? w.out_count : std::max<int64_t>(0, end_in - w.out_begin);
+    if (n > 0) {
+        const int64_t end_out = w.out_begin + n;
+        if (w.in_origin > w.out_begin || end_out > end_in)
+            fail(ZVX_E_INVALID, "%s: row %d: outputs [%lld, %lld) lie outside the window's samples [%lld, %lld)", who, b, (long long)w.out_begin,
+                 (long long)end_out, (long long)w.in_origin, (long long)end_in);
+        if (w.in_origin != 0 && w.out_begin - R < w.in_origin)
+            fail(ZVX_E_INVALID, "%s: row %d: the reach R = %lld needs %lld more samples in front of the window (in_origin %lld, out_begin %lld)", who, b,
+                 (long long)R, (long long)(w.in_origin - (w.out_begin - R)), (long long)w.in_origin, (long long)w.out_begin);
+        if (!w.last && end_out - 1 + R > end_in - 1)
+            fail(ZVX_E_INVALID, "%s: row %d: the reach R = %lld needs %lld more samples behind the window (outputs end at %lld, samples at %lld; or last)", who, b,
+                 (long long)R, (long long)(end_out + R - end_in), (long long)end_out, (long long)end_in);
     }
+    return (int32_t)n;                                       // n <= nsamples where n > 0
+}
+std::vector<int32_t> window_counts(const char* who, const RowsWindow& w, const int32_t* nsamples, int B, int64_t R) {
+    window_args_check(who, w);
+    std::vector<int32_t> cnt(B);
+    for (int b = 0; b < B; b++) cnt[b] = window_count_row(who, w, nsamples[b], b, R);
     return cnt;
 }
 // the emitted range: [off, off + cnt[b]) of row b.  Without a window the whole rows; with one, window_counts for the reach R, then the checks
@@ -2756,6 +2764,191 @@ void do_denoise(zvx_ctx* c, const char* who, const float* in, const int32_t* nsa
     ret.finish(nullptr, out, out_stride, cnt, flags);
 }
 
+// ------------------------------------------------------------------------------------------------
+// per-row windows (include/zvx.h: zvx_denoise_rows, zvx_limit_rows; the batched post stages of zvx_stream_next_many)
+// ------------------------------------------------------------------------------------------------
+// One row of the internal per-row forms: n samples at `in` on the device, the window they are of their signal, the emitted count (what
+// window_count_row gives), and where emitted sample 0 goes.  Rows of one call may lie in unrelated buffers.
+struct PostRow { const float* in; void* out; int32_t n; RowsWindow w; int32_t cnt; };
+
+// The denoiser over B rows with a window each: ONE table upload, ONE bias upload, the two launches of do_denoise under one timed group.  Per
+// row the quantities are the ones do_denoise forms for a call of that row alone (f_first rounded down per ROW: a frame keeps its slot).
+// The caller has validated the rows.
+void run_denoise_rows(zvx_ctx* c, const DnGeom& g, const PostRow* rows, int B, const float* bias, const zvx_denoise_params* p, int pcm16) {
+    const int per = DENOISE_POINTS >> g.log2n;
+    const bool copy = p->strength == 0.f;
+    std::vector<DenoiseRow> tab((size_t)B);
+    std::vector<size_t> work_at((size_t)B);
+    double frames = 0, n_sum = 0, cnt_sum = 0;
+    long Fmax = 0, cnt_max = 0;
+    size_t work_floats = 0;
+    for (int b = 0; b < B; b++) {
+        const PostRow& r = rows[b];
+        const RowsWindow& w = r.w;
+        const bool any = r.cnt > 0;
+        const int64_t off = any ? w.out_begin - w.in_origin : 0;
+        const int64_t p0 = w.out_begin + g.pad;
+        const int64_t f_need = any && p0 >= g.n_fft ? (p0 - g.n_fft) / g.hop + 1 : 0;
+        const int64_t f_first = f_need - f_need % per;
+        const int64_t rel = any ? f_first * g.hop - g.pad - w.in_origin : -(int64_t)g.pad;
+        int64_t F = 0;
+        if (any) {
+            F = (off + r.cnt - 1 - rel) / g.hop + 1;
+            if (w.last) F = std::min<int64_t>(F, std::max<int64_t>(0, dn_frames(g, w.in_origin + r.n) - f_first));
+            frames += (double)std::max<int64_t>(0, F - (f_need - f_first));
+        }
+        DenoiseRow& t = tab[(size_t)b];
+        t.x = r.in; t.out = r.out; t.work = nullptr;
+        t.origin = (long)w.in_origin; t.f_first = (long)f_first;
+        t.n = r.n; t.skip = (int)(f_need - f_first); t.rel = (int)rel; t.off = (int)off; t.cnt = r.cnt;
+        t.mirrors = (w.in_origin == 0 ? 1 : 0) | (w.last ? 2 : 0);
+        work_at[(size_t)b] = work_floats;
+        if (!copy) work_floats += (size_t)F * g.n_fft;
+        Fmax = std::max<long>(Fmax, (long)F); cnt_max = std::max<long>(cnt_max, r.cnt);
+        n_sum += r.n; cnt_sum += r.cnt;
+    }
+    DenoiseArgs a{};
+    a.copy = copy;
+    if (!copy) {
+        dn_fill(a, g, dn_tables(c, g));
+        float* bias_d = c->fbuf("dn.bias", g.nf);
+        c->upload(bias_d, bias, (size_t)g.nf * 4);
+        a.bias = bias_d; a.strength = p->strength; a.floor = p->floor;
+        a.work = c->fbuf("dn.work", std::max<size_t>(work_floats, 1));
+        for (int b = 0; b < B; b++) tab[(size_t)b].work = a.work + work_at[(size_t)b];
+    } else { a.n_fft = g.n_fft; a.log2n = g.log2n; a.hop = g.hop; a.pad = g.pad; }
+    a.Fmax = (int)Fmax; a.B = B; a.pcm16 = pcm16;
+    DenoiseRow* tab_d = (DenoiseRow*)c->buf("dn.rows", (size_t)B * sizeof(DenoiseRow));
+    c->upload(tab_d, tab.data(), (size_t)B * sizeof(DenoiseRow));
+    a.rows = tab_d;
+    TagScope scope(c, "post.denoise");
+    c->timed(copy ? 0.0 : dn_fft_flops(g, frames, 2), 4.0 * n_sum + (pcm16 ? 2.0 : 4.0) * cnt_sum, [&] {
+        if (!copy) launch_denoise_frames(a, c->stream);
+        launch_denoise_ola(a, cnt_max, c->stream);
+    });
+}
+
+// The limiter likewise: the three launches of do_limit under one timed group -> the device words res[b] = peak, res[B + b] = min gain.
+const float* run_limit_rows(zvx_ctx* c, const char* who, const PostRow* rows, int B, const zvx_limit_params* p, int W, int pcm16) {
+    LimitArgs a{};
+    a.os = p->oversample;
+    if (a.os > 1) {
+        const zvx_ctx::RsBank& bk = rs_bank(c, a.os, 1);
+        if (bk.T != 21 || bk.half != 10 * a.os) fail(ZVX_E_STATE, "%s: the (%d, 1) bank has %d taps per output", who, a.os, bk.T);
+        a.T = bk.T; a.pitch = bk.pitch; a.bank = bk.dev;
+    }
+    a.c = p->ceiling; a.W = W; a.win = limit_win(c, W);
+    std::vector<LimitRow> tab((size_t)B);
+    std::vector<size_t> env_at((size_t)B);
+    double n_sum = 0, cnt_sum = 0;
+    long n_max = 0, cnt_max = 0;
+    size_t env_floats = 0;
+    for (int b = 0; b < B; b++) {
+        const PostRow& r = rows[b];
+        LimitRow& t = tab[(size_t)b];
+        t.x = r.in; t.out = r.out; t.env = nullptr;
+        t.n = r.n; t.off = r.cnt > 0 ? (int)(r.w.out_begin - r.w.in_origin) : 0; t.cnt = r.cnt; t.pad_ = 0;
+        env_at[(size_t)b] = env_floats; env_floats += (size_t)r.n;
+        n_max = std::max<long>(n_max, r.n); cnt_max = std::max<long>(cnt_max, r.cnt);
+        n_sum += r.n; cnt_sum += r.cnt;
+    }
+    a.B = B; a.pcm16 = pcm16;
+    a.ppitch = (int)std::max(1L, (n_max + LIMIT_TILE - 1) / LIMIT_TILE);
+    a.gtiles = (int)std::max(1L, (cnt_max + LIMIT_TILE - 1) / LIMIT_TILE);                // <= ppitch: cnt <= n in every row
+    float* env = c->fbuf("lim.env", std::max<size_t>(env_floats, 1));
+    for (int b = 0; b < B; b++) tab[(size_t)b].env = env + env_at[(size_t)b];
+    a.part_max = c->fbuf("lim.part", (size_t)2 * B * a.ppitch);
+    a.part_min = a.part_max + (size_t)B * a.ppitch;
+    a.res = c->fbuf("lim.res", (size_t)2 * B);
+    LimitRow* tab_d = (LimitRow*)c->buf("lim.rows", (size_t)B * sizeof(LimitRow));
+    c->upload(tab_d, tab.data(), (size_t)B * sizeof(LimitRow));
+    a.rows = tab_d;
+    TagScope scope(c, "post.limit");
+    c->timed(0.0, 4.0 * n_sum + (pcm16 ? 2.0 : 4.0) * cnt_sum, [&] {
+        launch_limit_env(a, c->stream);
+        if (!launch_limit_gain(a, c->stream)) fail(ZVX_E_UNSUPPORTED, "%s: a window of %d samples does not fit the LDS of a workgroup", who, W);
+        launch_limit_reduce(a, c->stream);
+    });
+    return a.res;
+}
+
+// What zvx_denoise_rows and zvx_limit_rows check of their windows, all before anything is queued -> per row the emitted count
+struct RowsWindows { std::vector<RowsWindow> w; std::vector<int32_t> cnt; long cnt_max = 0; };
+RowsWindows rows_windows_check(const char* who, const zvx_row_window* win, const int32_t* nsamples, int B, int64_t R, const float* in, const void* out,
+                               int64_t out_stride) {
+    if (!win) fail(ZVX_E_INVALID, "%s: win is NULL", who);
+    RowsWindows rw;
+    rw.w.resize((size_t)B); rw.cnt.resize((size_t)B);
+    for (int b = 0; b < B; b++) {
+        if (win[b].reserved != 0) fail(ZVX_E_INVALID, "%s: row %d: reserved is %d (must be 0)", who, b, win[b].reserved);
+        RowsWindow& w = rw.w[(size_t)b];
+        w.in_origin = win[b].in_origin; w.out_begin = win[b].out_begin; w.out_count = win[b].out_count; w.last = win[b].last;
+        window_args_check(who, w, b);
+        rw.cnt[(size_t)b] = window_count_row(who, w, nsamples[b], b, R);
+        rw.cnt_max = std::max<long>(rw.cnt_max, rw.cnt[(size_t)b]);
+    }
+    if (out_stride < rw.cnt_max) fail(ZVX_E_INVALID, "%s: out_stride %lld is smaller than the longest output row %ld", who, (long long)out_stride, rw.cnt_max);
+    if (out == (const void*)in)
+        for (int b = 0; b < B; b++)
+            if (rw.cnt[(size_t)b] > 0 && rw.w[(size_t)b].out_begin != rw.w[(size_t)b].in_origin)
+                fail(ZVX_E_INVALID, "%s: row %d: in place needs out_begin == in_origin (%lld, %lld)", who, b, (long long)rw.w[(size_t)b].out_begin,
+                     (long long)rw.w[(size_t)b].in_origin);
+    return rw;
+}
+// the strided rows of a public call as PostRows
+std::vector<PostRow> post_rows(const float* x, long x_bs, void* out, long out_bs, size_t ss, const int32_t* nsamples, const RowsWindows& rw, int B) {
+    std::vector<PostRow> rows((size_t)B);
+    for (int b = 0; b < B; b++)
+        rows[(size_t)b] = PostRow{x + (size_t)b * x_bs, (char*)out + (size_t)b * out_bs * ss, nsamples[b], rw.w[(size_t)b], rw.cnt[(size_t)b]};
+    return rows;
+}
+
+void do_denoise_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias, const zvx_denoise_params* p, void* out,
+                     int64_t out_stride, int flags, const zvx_row_window* win) {
+    const char* who = "zvx_denoise_rows";
+    rows_check(who, in, nsamples, B, Nmax, 65535);
+    flags_check(who, flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16);
+    out_rows_check(who, in, out, out_stride, Nmax, flags);
+    const DnGeom g = denoise_params_check(c, who, bias, p);
+    const RowsWindows rw = rows_windows_check(who, win, nsamples, B, g.n_fft - 1, in, out, out_stride);
+    for (int b = 0; b < B; b++)                              // zvx_melspec's length conditions hold for the whole SIGNAL: known where it ends with the window
+        if (rw.w[(size_t)b].last && nsamples[b] > 0 && rw.w[(size_t)b].in_origin + nsamples[b] < dn_min_samples(g))
+            fail(ZVX_E_INVALID, "%s: row %d has %lld samples; a row that is not empty needs at least %d (zvx_melspec's conditions)", who, b,
+                 (long long)(rw.w[(size_t)b].in_origin + nsamples[b]), dn_min_samples(g));
+    RowsReturn ret(c, B, 0, false, true, rw.cnt_max, flags);
+    const float* x = rows_to_device(c, "dn", in, B, Nmax, flags);
+    long out_bs = 0;
+    void* od = ret.out_rows("dn.out", out, out_stride, &out_bs);
+    const std::vector<PostRow> rows = post_rows(x, Nmax, od, out_bs, ret.ss, nsamples, rw, B);
+    run_denoise_rows(c, g, rows.data(), B, bias, p, (flags & ZVX_PCM16) ? 1 : 0);
+    ret.finish(nullptr, out, out_stride, rw.cnt.data(), flags);
+}
+
+void do_limit_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_limit_params* p, void* out,
+                   int64_t out_stride, float* peak_in, float* min_gain, int flags, const zvx_row_window* win) {
+    const char* who = "zvx_limit_rows";
+    if (!p) fail(ZVX_E_INVALID, "%s: params is NULL", who);
+    rows_check(who, in, nsamples, B, Nmax, 65535);
+    if (rate < 4000 || rate > 192000) fail(ZVX_E_INVALID, "%s: rate %d outside [4000, 192000]", who, rate);
+    flags_check(who, flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16);
+    limit_os_check(who, p->oversample);
+    out_rows_check(who, in, out, out_stride, Nmax, flags);
+    const int W = limit_params_check(who, rate, p);
+    const RowsWindows rw = rows_windows_check(who, win, nsamples, B, 2 * (int64_t)W + (p->oversample > 1 ? LIMIT_ENV_REACH : 0), in, out, out_stride);
+    RowsReturn ret(c, B, (size_t)B * 8, peak_in || min_gain, true, rw.cnt_max, flags);      // words: peak [B], then min gain [B]
+    const float* x = rows_to_device(c, "lim", in, B, Nmax, flags);
+    long out_bs = 0;
+    void* od = ret.out_rows("lim.out", out, out_stride, &out_bs);
+    const std::vector<PostRow> rows = post_rows(x, Nmax, od, out_bs, ret.ss, nsamples, rw, B);
+    const float* res = run_limit_rows(c, who, rows.data(), B, p, W, (flags & ZVX_PCM16) ? 1 : 0);
+    const float* r_h = (const float*)ret.finish(res, out, out_stride, rw.cnt.data(), flags);
+    if (!r_h) return;
+    for (int b = 0; b < B; b++) {
+        if (peak_in) peak_in[b] = r_h[b];
+        if (min_gain) min_gain[b] = r_h[B + b];
+    }
+}
+
 constexpr int DN_BIAS_FRAMES = 88;       // mel frames of silence the bias is measured on
 
 void do_denoise_bias(zvx_ctx* c, float* bias) {
@@ -2953,7 +3146,7 @@ void do_stream_open(zvx_ctx* c, const float* mel, int frames, const zvx_stream_p
         s->nchunks = nchunks; s->Pcap = Pcap; s->wstride = wstride; s->delay = delay; s->max_piece = max_piece;
         s->total = zvx_plan::ceil_div(total_native * rp.L, rp.M);
         if (p->denoise) { s->dn = *p->denoise; s->bias.assign(p->denoise_bias, p->denoise_bias + g.nf); }
-        if (p->limit) s->lim = *p->limit;
+        if (p->limit) { s->lim = *p->limit; s->lim_W = W; }
         auto pad = [](int64_t floats) { return (size_t)((floats * 4 + 255) & ~(int64_t)255); };
         size_t bytes = pad((int64_t)frames * nm) + pad((int64_t)rows * Pcap * nm) + pad((int64_t)rows * wstride) + pad(max_piece);
         int64_t in_max = G;
@@ -3062,6 +3255,105 @@ void stream_run_stages(const char* who, zvx_stream* s, const StreamStep& p, floa
     s->next_chunk = p.g.first + p.g.rows; s->emitted += p.n; s->done = last ? 1 : 0;
 }
 
+// The stages of MANY sessions behind the scatter (zvx_stream_next_many): what stream_run_stages does per session, run kind by kind -- all
+// denoisers, then all limiters, then the rate conversions; a session's chain order is kept and everything is on the one stream.  Within a
+// kind the sessions whose stage has bitwise-equal parameters (the bias by content; the limiter by W, oversampling and ceiling) form one
+// group (stream_plan.h, partition_classes), and a group is ONE call of the per-row form: its rows are the sessions' [history | new]
+// buffers with each session's own window, each output goes straight behind the next stage's history or to the final destination.  The
+// rate conversion stays one call per session (another window contract).  All history drops of the call are ONE launch over a table.
+void stream_run_stages_many(const char* who, zvx_ctx* c, zvx_stream* const* ss, const std::vector<StreamStep>& plans, const std::vector<float*>& final_dst,
+                            int n) {
+    struct Slot { bool run = false; PostRow row{}; };
+    std::vector<Slot> slot[3];
+    for (auto& v : slot) v.resize((size_t)n);
+    std::vector<StreamManyInterior> moves;
+    double move_bytes = 0; long move_max = 0;
+    // ---- every stage's input, window and destination, from the sessions' state as it stands
+    for (int i = 0; i < n; i++) {
+        const zvx_stream* s = ss[i];
+        const StreamStep& p = plans[(size_t)i];
+        const size_t K = s->stages.size();
+        const bool last = p.g.last != 0;
+        int64_t n_in = p.g.n_new;
+        for (size_t k = 0; k < K; k++) {
+            const zvx_stream::Stage& st = s->stages[k];
+            const zvx_plan::Step& sp = p.steps[k];
+            const int64_t held = st.hist + n_in;
+            float* in = st.buf[st.cur];
+            float* dst = k + 1 < K ? s->stages[k + 1].buf[s->stages[k + 1].cur] + s->stages[k + 1].hist : final_dst[(size_t)i];
+            if (sp.out_count > 0 && held > 0) {
+                Slot& sl = slot[st.kind][(size_t)i];
+                sl.run = true;
+                sl.row = PostRow{in, dst, (int32_t)held, RowsWindow{sp.in_origin, sp.out_begin, sp.out_count, last ? 1 : 0}, (int32_t)sp.out_count};
+            }
+            const int64_t drop = sp.keep_from - sp.in_origin, keep = held - drop;
+            if (drop > 0 && keep > 0) {                      // into the other buffer: never an overlapping copy
+                moves.push_back(StreamManyInterior{st.buf[st.cur ^ 1], in + drop, 0, (int)keep});
+                move_bytes += 8.0 * (double)keep; move_max = std::max<long>(move_max, (long)keep);
+            }
+            n_in = sp.out_count;
+        }
+    }
+    // ---- denoisers and limiters: one call of the per-row form per class
+    std::vector<int> cls((size_t)n), order((size_t)n), start((size_t)n + 1);
+    std::vector<PostRow> rows;
+    for (int kind : {(int)zvx_stream::DENOISE, (int)zvx_stream::LIMIT}) {
+        for (int i = 0; i < n; i++) {
+            cls[(size_t)i] = -1;
+            if (!slot[kind][(size_t)i].run) continue;
+            cls[(size_t)i] = i;
+            for (int j = 0; j < i; j++) {
+                if (cls[(size_t)j] != j) continue;           // (a class is named by its first member)
+                const zvx_stream *a = ss[j], *b = ss[i];
+                const bool same = kind == zvx_stream::DENOISE
+                    ? !memcmp(&a->dn, &b->dn, sizeof a->dn) && a->bias.size() == b->bias.size() && !memcmp(a->bias.data(), b->bias.data(), a->bias.size() * 4)
+                    : a->lim_W == b->lim_W && a->lim.oversample == b->lim.oversample && !memcmp(&a->lim.ceiling, &b->lim.ceiling, sizeof(float));
+                if (same) { cls[(size_t)i] = j; break; }
+            }
+        }
+        const int groups = zvx_plan::partition_classes(cls.data(), n, order.data(), start.data());
+        for (int gi = 0; gi < groups; gi++) {
+            rows.clear();
+            for (int m = start[(size_t)gi]; m < start[(size_t)gi + 1]; m++) rows.push_back(slot[kind][(size_t)order[(size_t)m]].row);
+            const zvx_stream* first = ss[order[(size_t)start[(size_t)gi]]];
+            if (kind == zvx_stream::DENOISE) run_denoise_rows(c, dn_geom(c, who), rows.data(), (int)rows.size(), first->bias.data(), &first->dn, 0);
+            else run_limit_rows(c, who, rows.data(), (int)rows.size(), &first->lim, first->lim_W, 0);
+        }
+    }
+    // ---- rate conversions: one call per session
+    const int f = ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC;
+    for (int i = 0; i < n; i++) {
+        const Slot& sl = slot[zvx_stream::RESAMPLE][(size_t)i];
+        if (!sl.run) continue;
+        const int32_t n32 = sl.row.n;
+        do_resample(c, sl.row.in, &n32, 1, n32, ss[i]->native, ss[i]->out_rate, sl.row.out, std::max<int64_t>(n32, sl.row.cnt), nullptr, f, sl.row.w.in_origin,
+                    sl.row.w.out_begin, sl.row.cnt);
+    }
+    // ---- every history drop of the call in one launch
+    if (!moves.empty()) {
+        StreamManyInterior* tab_d = (StreamManyInterior*)c->buf("stream.moves", (size_t)STREAM_MANY_MAX_SESSIONS * 3 * sizeof(StreamManyInterior));
+        c->upload(tab_d, moves.data(), moves.size() * sizeof(StreamManyInterior));
+        const StreamManyInteriorArgs ma{tab_d, nullptr, 0, (int)moves.size()};      // (the scatter's kernel: every entry has its own source)
+        TagScope scope(c, "post.stream");
+        c->timed(0.0, move_bytes, [&] { launch_stream_interiors_many(ma, move_max, c->stream); });
+    }
+    // ---- the sessions' state
+    for (int i = 0; i < n; i++) {
+        zvx_stream* s = ss[i];
+        const StreamStep& p = plans[(size_t)i];
+        int64_t n_in = p.g.n_new;
+        for (size_t k = 0; k < s->stages.size(); k++) {
+            zvx_stream::Stage& st = s->stages[k];
+            const zvx_plan::Step& sp = p.steps[k];
+            const int64_t held = st.hist + n_in, drop = sp.keep_from - sp.in_origin;
+            if (drop > 0) st.cur ^= 1;
+            st.hist = held - drop; st.reach = p.plan[k].reach; st.rate = p.plan[k].rate;
+            n_in = sp.out_count;
+        }
+        s->next_chunk = p.g.first + p.g.rows; s->emitted += p.n; s->done = p.g.last ? 1 : 0;
+    }
+}
+
 void do_stream_next(zvx_stream* s, void* out, int64_t capacity, int64_t* n_out, int32_t* done, int flags) {
     const char* who = "zvx_stream_next";
     zvx_ctx* c = s->c;
@@ -3116,7 +3408,8 @@ void do_stream_next(zvx_stream* s, void* out, int64_t capacity, int64_t* n_out, 
 
 // zvx_stream_next_many (include/zvx.h): the groups of n sessions of one context as ONE batch of the vocoder.  Per session it is
 // do_stream_next -- the same plan, the same stages, the same state afterwards --; what differs is that the rows of all sessions are
-// gathered by one launch, vocoded by one run_vocoder and scattered by one launch to where each session's first stage reads them.
+// gathered by one launch, vocoded by one run_vocoder and scattered by one launch to where each session's first stage reads them, and that
+// the denoisers and limiters of all sessions run as per-row batches (stream_run_stages_many).
 void do_stream_next_many(zvx_ctx* c, zvx_stream* const* ss, int n, void* const* out, const int64_t* capacity, int64_t* n_out, int32_t* done,
                          int flags) {
     const char* who = "zvx_stream_next_many";
@@ -3178,7 +3471,7 @@ void do_stream_next_many(zvx_ctx* c, zvx_stream* const* ss, int n, void* const* 
             for (int j = 0; j < p.g.rows; j++, r++) {
                 P[(size_t)r] = p.P[j];
                 tr[r] = StreamManyRow{s->mel + p.rows[j].lo * nm, p.P[j], 0};
-                ti[r] = StreamManyInterior{base + p.rows[j].pos, (int)p.rows[j].off, (int)p.rows[j].cnt};
+                ti[r] = StreamManyInterior{base + p.rows[j].pos, nullptr, (int)p.rows[j].off, (int)p.rows[j].cnt};
             }
         }
         c->upload(tab_d, tab.data(), tab.size());
@@ -3195,10 +3488,8 @@ void do_stream_next_many(zvx_ctx* c, zvx_stream* const* ss, int n, void* const* 
             TagScope scope(c, "voc.stream");
             c->timed(0.0, new_bytes, [&] { launch_stream_interiors_many(ia, cnt_max, c->stream); });
         }
-        for (int i = 0; i < n; i++) {
-            stream_run_stages(who, ss[i], plans[(size_t)i], final_dst[(size_t)i]);
-            done[i] = ss[i]->done;
-        }
+        stream_run_stages_many(who, c, ss, plans, final_dst, n);
+        for (int i = 0; i < n; i++) done[i] = ss[i]->done;
         if (!(flags & ZVX_DEVICE_OUT)) {
             for (int i = 0; i < n; i++)
                 if (n_out[i] > 0) HIPCHK(hipMemcpyAsync(ss[i]->pinned, ss[i]->ostage, (size_t)n_out[i] * 4, hipMemcpyDeviceToHost, c->stream));
@@ -3563,6 +3854,16 @@ zvx_status zvx_denoise_ex(zvx_ctx* c, const float* in, const int32_t* nsamples, 
         const RowsWindow win{in_origin, out_begin, out_count, last};
         do_denoise(c, "zvx_denoise_ex", in, nsamples, B, Nmax, bias, params, out, out_stride, flags, &win);
     });
+}
+
+zvx_status zvx_denoise_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias,
+                            const zvx_denoise_params* params, void* out, int64_t out_stride, int flags, const zvx_row_window* win) {
+    return guarded(c, [&] { do_denoise_rows(c, in, nsamples, B, Nmax, bias, params, out, out_stride, flags, win); });
+}
+
+zvx_status zvx_limit_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_limit_params* params,
+                          void* out, int64_t out_stride, float* peak_in, float* min_gain, int flags, const zvx_row_window* win) {
+    return guarded(c, [&] { do_limit_rows(c, in, nsamples, B, Nmax, rate, params, out, out_stride, peak_in, min_gain, flags, win); });
 }
 
 zvx_status zvx_stream_open(zvx_ctx* c, const float* mel, int frames, const zvx_stream_params* params, int flags, zvx_stream** out) {

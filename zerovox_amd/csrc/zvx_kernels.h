@@ -405,7 +405,7 @@ struct StreamInteriorArgs {
 void launch_stream_interiors(const StreamInteriorArgs& a, long cnt_max, hipStream_t s);
 // The same for the rows of many sessions at once (zvx_stream_next_many: up to STREAM_MANY_MAX_ROWS rows, each with a source / destination
 // POINTER of its own): the tables no longer fit the kernel arguments and live in device memory, built on the host and uploaded through the
-// context's pinned arena (queued like a launch, no host wait).  One 16-byte entry per row.
+// context's pinned arena (queued like a launch, no host wait).  One small entry per row.
 constexpr int STREAM_MANY_MAX_SESSIONS = 64;  // ZVX_STREAM_MANY_MAX_SESSIONS
 constexpr int STREAM_MANY_MAX_ROWS = 256;     // ZVX_STREAM_MANY_MAX_ROWS
 // Rows: row r of out [R][Pmax][nm] = the P frames at src ([P][nm], inside the owning session's mel), then zeros up to Pmax frames.
@@ -413,7 +413,9 @@ struct StreamManyRow { const float* src; int P; int pad_; };
 struct StreamManyRowsArgs { const StreamManyRow* tab; float* out; int R, Pmax, nm; };
 void launch_stream_rows_many(const StreamManyRowsArgs& a, hipStream_t s);
 // Interiors: dst[i] = wav[r][off + i] for i < cnt; dst lies in memory of the owning session (or is the caller's), rows of one session back to back.
-struct StreamManyInterior { float* dst; int off, cnt; };
+// An entry with a source of its own (src != NULL) copies src[off + i] instead: the history drops of the sessions' stages are such a table,
+// one launch for all of them, each retained tail into its stage's OTHER buffer (source and destination never overlap).
+struct StreamManyInterior { float* dst; const float* src; int off, cnt; };
 struct StreamManyInteriorArgs { const StreamManyInterior* tab; const float* wav; long w_bs; int R; };
 void launch_stream_interiors_many(const StreamManyInteriorArgs& a, long cnt_max, hipStream_t s);
 // Integrated loudness (ITU-R BS.1770 / EBU R128) and gain of a batch's waveform rows (include/zvx.h, zvx_loudness / zvx_normalize): every
@@ -452,10 +454,20 @@ void launch_loud_apply(const LoudApplyArgs& a, long n_max, hipStream_t s);
 // or written.  The windowed form (zvx_limit_ex) emits the samples [off, off + cnt[b]) of the row only: the envelope is still evaluated over
 // the whole row, the gain tiles start at `off` -- any sample offset from the envelope's tile grid -- and write out[b][i - off]; the
 // arithmetic of a sample depends on neither grid.  The whole-row form is off = 0, cnt = nsamples.
+// Per-row form (zvx_limit_rows, the batched stages of zvx_stream_next_many): `rows` is a device table with one LimitRow per row -- its
+// input, output and envelope pointers, its length and its emitted range --, so that the rows of one launch may live in unrelated buffers and
+// sit anywhere on their signals.  Every kernel resolves ONE LimitRow at its top and works from it alone: without a table the row is formed
+// from the uniform fields (x + b x_bs, nsamples[b], off, cnt[b] ...), so the whole-row call, the _ex call and the per-row call run the same
+// instructions.  Grids are sized by the longest row; a workgroup past its row's extent only writes its neutral partial result.
 constexpr int LIMIT_TILE = 1024;             // (zerovox_amd/_lib.py carries the same figure for the tests' tile-edge rows)
 constexpr int LIMIT_MAX_W = 4096;
 constexpr int LIMIT_ENV_REACH = 11;          // e[j] reads x[j - 11 .. j + 11] where os > 1 (include/zvx.h, zvx_limit_ex: H; _lib.py: LIMIT_ENV_REACH)
+struct LimitRow {
+    const float* x; void* out; float* env;   // the row's samples; where emitted sample `off` goes (f32 or int16); e[i] (NULL: not stored)
+    int n, off, cnt, pad_;                   // the row's length; the emitted range [off, off + cnt)
+};
 struct LimitArgs {
+    const LimitRow* rows;                    // NULL: the uniform form below
     const float* x; long x_bs; const int* nsamples; int B;
     int os, T, pitch; const float* bank;     // os > 1: the resampler's bank of (L, M) = (os, 1) (ResampleArgs), T = 21; os == 1: unused
     float* env; long e_bs;                   // e[b][i], the envelope (f32); NULL: only the partial maxima are wanted (zvx_true_peak)
@@ -475,7 +487,8 @@ void launch_limit_env(const LimitArgs& a, hipStream_t s);
 // below the ceiling copies its samples.  It reads e, never a neighbour's x: safe in place (off = 0).  grid.x = gtiles tiles from `off` on.
 // false: the span does not fit the LDS.
 bool launch_limit_gain(const LimitArgs& a, hipStream_t s);
-// one workgroup per row over the tiles' partial results
+// one workgroup per row over the tiles' partial results (part_max / part_min are [b][ppitch] in every form, and a tile past a row's own
+// extent holds the neutral 0 / 1, so this launch needs no row descriptor)
 void launch_limit_reduce(const LimitArgs& a, hipStream_t s);
 // Vocoder-bias denoiser (include/zvx.h, zvx_denoise; spectral.hip): spectral subtraction over the STFT frames of zvx_melspec, the frames
 // transformed by an FFT that lives in LDS.  A workgroup of 256 threads holds DENOISE_POINTS complex f32 points, i.e. DENOISE_POINTS / n_fft
@@ -488,8 +501,19 @@ void launch_limit_reduce(const LimitArgs& a, hipStream_t s);
 // multiple of the frames per workgroup, so that a frame sits in the slot it has in the whole-row call and runs through the same
 // instructions: the first `skip` frames cover no emitted sample and are neither loaded nor stored.  The whole-row call is origin 0,
 // f_first 0, skip 0, rel -pad, both mirrors, off 0, cnt -1: the indices it forms are the ones it always formed.
+// Per-row form (zvx_denoise_rows, the batched stages of zvx_stream_next_many): `rows` is a device table with one DenoiseRow per row -- its
+// input, output and work-buffer pointers, its length and every window quantity above, f_first rounded down per ROW --, so that the rows of
+// one launch may live in unrelated buffers and sit anywhere on their signals.  Both kernels resolve ONE DenoiseRow at their top and work
+// from it alone: without a table it is formed from the uniform fields, so all three forms run the same instructions through the
+// transforms (two instantiations of one source need not contract their multiply-adds alike; one body cannot differ from itself).
 constexpr int DENOISE_POINTS = 4096;         // also the largest n_fft
+struct DenoiseRow {
+    const float* x; void* out; float* work;  // the row's samples; where emitted sample `off` goes (f32 or int16); its frames [F][n_fft], from f_first
+    long origin, f_first;
+    int n, skip, rel, off, cnt, mirrors;     // mirrors: bit 0 left, bit 1 right; cnt -1: to the end of the row
+};
 struct DenoiseArgs {
+    const DenoiseRow* rows;                  // NULL: the uniform form below, row b's work at work + b Fmax n_fft
     const float* x; long x_bs; const int* nsamples; int B;
     int n_fft, log2n, hop, pad, Fmax;        // Fmax: the most frames transformed of a row (the frame buffers' row pitch, in frames)
     long origin, f_first;                    // the window's first sample; frame 0 of the work buffer on the signal's grid (the same for every row)
