@@ -586,7 +586,8 @@ zvx_status zvx_denoise_ex(zvx_ctx* ctx, const float* in, const int32_t* nsamples
  *   window is last.  strength == 0 stays a copy of each emitted range.
  * Accounting: the tags stay "post.denoise" / "post.limit", one timed group per call; bytes are the sum over the rows of what the one-row _ex
  *   calls count.
- * zvx_resample_ex has another window contract (its rows are zero outside the window and it has no support condition): it has no rows form. */
+ * zvx_resample_ex has another window contract (its rows are zero outside the window and it has no support condition): its rows form is
+ * zvx_resample_rows below, with rules of its own. */
 typedef struct zvx_row_window {
     int64_t in_origin, out_begin, out_count;   /* as the _ex calls' parameters; out_count -1: to the end of the row's signal (needs last) */
     int32_t last;                              /* 0 or 1 */
@@ -597,6 +598,31 @@ zvx_status zvx_denoise_rows(zvx_ctx* ctx, const float* in, const int32_t* nsampl
 zvx_status zvx_limit_rows(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, int rate,
                           const zvx_limit_params* params, void* out, int64_t out_stride, float* peak_in, float* min_gain, int flags,
                           const zvx_row_window* win);
+/* The rate conversion with a window per row: zvx_resample_ex with win[b] (a HOST array of B entries) in place of the call's one window.  Row b
+ * holds samples [in_origin, in_origin + nsamples[b]) of a signal that is zero everywhere else; outputs [out_begin, out_begin + cnt_b) go to
+ * positions [0, cnt_b) of out row b, cnt_b = out_count, or with out_count == -1 max(0, ceil((in_origin + nsamples[b]) * L / M) - out_begin).
+ * Contract: row b's emitted samples are bit for bit those of zvx_resample_ex on that row alone with win[b] (f32, and int16 with ZVX_PCM16),
+ *   and therefore the whole-signal call's bits wherever the windows tile a signal; a row's bits depend neither on which rows share the call
+ *   nor on their windows.
+ * Unlike zvx_resample_ex: nothing outside [0, cnt_b) of an output row is touched -- there is NO zero fill up to the longest row, as in the
+ *   other two rows forms; out_len[b] = cnt_b (may be NULL); `last` must be 0 or 1 and has no meaning here (the signal is zero outside the
+ *   window, so out_count -1 does not need it); `reserved` must be 0.
+ * Like zvx_resample_ex: the rate pair stays per CALL (the polyphase bank and the tile depend on (L, M) only); the flags, syncs and the queued
+ *   form -- ZVX_DEVICE_IN, ZVX_DEVICE_OUT, ZVX_NO_SYNC (device output only), ZVX_PCM16; win and nsamples are host arrays and may be reused
+ *   when the call returns; equal rates are a copy of each emitted range.
+ * How: the one resampling kernel resolves a row descriptor at its top -- input and output pointers, length, in_origin, out_begin, cnt and
+ *   the bound up to which zeros follow (the longest row for the uniform calls, cnt_b here) -- and works from it alone; this call reads it from
+ *   a device table (uploaded through the context's pinned staging, queued like a launch), zvx_resample / zvx_resample_ex form it from their
+ *   arguments.  One body: the sum of an output keeps its single order in every form.  The 16-byte load and store paths are chosen per row
+ *   from that row's own pointers and in_origin & 3 and change no bit.  No index is formed in 32 bits from an absolute position: in_origin and
+ *   out_begin may lie beyond 2^32.  The grid is sized by the longest cnt_b; workgroups past a row's extent return at once.
+ * Validation, all before anything is queued (the context stays usable): every check of zvx_resample_ex, its window checks per row with the
+ *   message naming the row.  ZVX_E_INVALID: a NULL win, reserved != 0, last outside {0, 1}, more than INT32_MAX outputs in a row.
+ *   ZVX_E_BUFFER: out_stride smaller than the longest cnt_b.  ZVX_E_UNSUPPORTED: a bank that does not fit a workgroup's LDS.
+ * Accounting: tag "voc.resample", slot ZVX_T_RESAMPLE, one timed group per call; bytes are the sum over the rows of what the one-row
+ *   zvx_resample_ex calls count (a row that emits nothing counts nothing). */
+zvx_status zvx_resample_rows(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, int rate_in, int rate_out, void* out,
+                             int64_t out_stride, int32_t* out_len, int flags, const zvx_row_window* win);
 
 /* Stream sessions: chunked vocoding of ONE utterance with the planning inside the library.  A session owns the utterance's mel on the
  * device, vocodes it group by group and runs the new samples device to device through the optional denoiser, limiter and rate conversion;
@@ -680,16 +706,16 @@ zvx_status zvx_stream_close(zvx_stream* s);
  *   behind the history of the owning session's first stage buffer (to that session's final destination where it has no stage).  Their
  *   per-row tables (source mel pointer and frame count; source offset, count and destination pointer) are built on the host and uploaded
  *   through the context's pinned staging, queued like a launch: no host wait.
- * Post stages: batched across the sessions through the per-row forms behind zvx_denoise_rows / zvx_limit_rows.  The stages run kind by
- *   kind -- all denoisers, then all limiters, then the rate conversions -- on the one stream; a session's chain order denoise -> limit ->
- *   resample is kept.  Within a kind the sessions whose stage has bitwise-equal parameters form one group (the bias compared by content;
- *   the limiter's class is W, oversampling and ceiling), and a group is ONE call of the per-row form: its rows are the sessions'
+ * Post stages: batched across the sessions through the per-row forms behind zvx_denoise_rows / zvx_limit_rows / zvx_resample_rows.  The
+ *   stages run kind by kind -- all denoisers, then all limiters, then the rate conversions -- on the one stream; a session's chain order
+ *   denoise -> limit -> resample is kept.  Within a kind the sessions whose stage has bitwise-equal parameters form one group (the bias
+ *   compared by content; the limiter's class is W, oversampling and ceiling; the rate conversion's is the native rate and the session's
+ *   captured output rate), and a group is ONE call of the per-row form: its rows are the sessions'
  *   [history | new] buffers, each with that session's own window, and each output goes straight behind the next stage's history or to the
  *   session's final destination.  Groups run in the order of their first member, rows within a group in call order, and the bias is
  *   uploaded once per group (the partition is zvx_plan::partition_classes in zerovox_amd/csrc/stream_plan.h).  Each group counts under
- *   "post.denoise" / "post.limit" as one timed group with the bytes its sessions' single steps count in sum.  A stage that emits nothing
- *   in this call takes no part.  The rate conversion stays one call per session: zvx_resample_ex has another window contract (zero
- *   outside the window, no support condition) and no per-row form.  The history drops of all stages of all sessions are ONE launch over a
+ *   "post.denoise" / "post.limit" / "voc.resample" as one timed group with the bytes its sessions' single steps count in sum.  A stage
+ *   that emits nothing in this call takes no part.  The history drops of all stages of all sessions are ONE launch over a
  *   table of (source, destination, count), each retained tail into its stage's other buffer, under the stage tag "post.stream".
  *   zvx_stream_next itself stays on the one-row _ex forms; the bits are the same either way, which is the per-row contract.
  * One wait: host pieces travel through each session's pinned buffer -- all copies are queued, the call waits once, then copies out.  With

@@ -1,7 +1,8 @@
-"""What a window per row buys on its own (include/zvx.h: zvx_denoise_rows, zvx_limit_rows): 64 signals, each at a position of its own, one
-16-frame piece of each -- 4096 new samples behind the history its stage keeps -- through the denoiser and through the limiter
-   (a) by 64 zvx_denoise_ex / zvx_limit_ex calls of one row,
-   (b) by one zvx_denoise_rows / zvx_limit_rows call of 64 rows,
+"""What a window per row buys on its own (include/zvx.h: zvx_denoise_rows, zvx_limit_rows, zvx_resample_rows): 64 signals, each at a position
+of its own, one 16-frame piece of each -- 4096 new samples behind the history its stage keeps -- through the denoiser, through the limiter
+and through the rate conversion (to 48000 and to 8000 Hz)
+   (a) by 64 zvx_denoise_ex / zvx_limit_ex / zvx_resample_ex calls of one row,
+   (b) by one zvx_denoise_rows / zvx_limit_rows / zvx_resample_rows call of 64 rows,
 device rows in and out, everything queued (ZVX_NO_SYNC) and one wait at the end, the two alternating.  A development aid; nothing on the
 product path imports it.
    python tools/rows_bench.py [--rows 64] [--reps 30] [out.json]"""
@@ -30,13 +31,18 @@ F = _lib.ZVX_DEVICE_IN | _lib.ZVX_DEVICE_OUT | _lib.ZVX_NO_SYNC
 vp = C.c_void_p
 
 
-def bench(name, R, one, rows):
-    """rows of 2 R history + NEW samples, row b at in_origin 1000 b + 7: its outputs [in_origin + R, in_origin + R + NEW)"""
+def bench(name, R, one, rows, ratio=None):
+    """rows of 2 R history + NEW samples, row b at in_origin 1000 b + 7: its outputs [in_origin + R, in_origin + R + NEW); with ratio = (L, M)
+    the outputs are counted at the output rate: NEW L / M of them from the first one at or behind input position in_origin + R"""
     n = 2 * R + NEW
     x = (np.random.default_rng(1).standard_normal((B, n)) * 0.4).astype(np.float32)
-    xd, od = ctx.dev_alloc(x.nbytes), ctx.dev_alloc(x.nbytes)
+    xd, od = ctx.dev_alloc(x.nbytes), ctx.dev_alloc(x.nbytes * (3 if ratio else 1))
     ctx.dev_from_host(xd, x)
     lens = np.full(B, n, np.int32)
+    if ratio:
+        Lr, Mr = ratio
+        win = (_lib.RowWindow * B)(*[_lib.RowWindow(1000 * b + 7, -(-(1000 * b + 7 + R) * Lr // Mr), NEW * Lr // Mr, 0, 0) for b in range(B)])
+        return bench_resample(name, n, x, xd, od, lens, win, one, rows)
     win = (_lib.RowWindow * B)(*[_lib.RowWindow(1000 * b + 7, 1000 * b + 7 + R, NEW, 0, 0) for b in range(B)])
 
     def a():
@@ -66,13 +72,54 @@ def bench(name, R, one, rows):
     return row
 
 
+def bench_resample(name, n, x, xd, od, lens, win, one, rows):
+    """the same two loops over output rows of 3 n samples (the counts are at the output rate)"""
+    cnt = int(win[0].out_count)
+    assert cnt <= 3 * n
+
+    def a():
+        for b in range(B):
+            rc = one(vp(xd + 4 * n * b), lens[b:b + 1], n, vp(od + 12 * n * b), win[b])
+            assert rc == 0, ctx._lib.zvx_last_error(ctx._h)
+        ctx.sync()
+
+    def b_():
+        rc = rows(vp(xd), lens, n, vp(od), win)
+        assert rc == 0, ctx._lib.zvx_last_error(ctx._h)
+        ctx.sync()
+    got = []
+    for f in (a, b_):
+        f()
+        got.append(ctx.dev_to_host(od, (B, 3 * n), np.uint32)[:, :cnt].copy())
+        ctx.dev_from_host(od, np.zeros((B, 3 * n), np.float32))
+    ta, tb = [], []
+    for _ in range(args.reps):
+        t0 = time.perf_counter(); a(); ta.append(time.perf_counter() - t0)
+        t0 = time.perf_counter(); b_(); tb.append(time.perf_counter() - t0)
+    ctx.dev_free(xd); ctx.dev_free(od)
+    row = {"stage": name, "rows": B, "samples_per_row": n, "emitted_per_row": cnt, "a_ex_calls_ms": round(float(np.median(ta)) * 1e3, 3),
+           "b_rows_call_ms": round(float(np.median(tb)) * 1e3, 3), "a_over_b": round(float(np.median(ta) / np.median(tb)), 2),
+           "same_bits": bool(np.array_equal(got[0], got[1]) and got[1].any())}
+    print(row, flush=True)
+    return row
+
+
+def resample_line(rate_out):
+    from zerovox_amd.resample import rate_pair
+    Lr, Mr, half = rate_pair(RATE, rate_out)
+    return bench(f"resample {RATE} -> {rate_out}", half // Lr + 1,
+                 lambda x, l, n, o, w: lib.zvx_resample_ex(ctx._h, x, _lib._ptr(l), 1, n, RATE, rate_out, o, 3 * n, None, F, w.in_origin, w.out_begin, w.out_count),
+                 lambda x, l, n, o, w: lib.zvx_resample_rows(ctx._h, x, _lib._ptr(l), B, n, RATE, rate_out, o, 3 * n, None, F, w), ratio=(Lr, Mr))
+
+
 res = {"workload": f"{B} rows, one 16-frame piece each, device rows, queued calls and one wait; median of {args.reps}", "rows": [
     bench("denoise", n_fft - 1,
           lambda x, l, n, o, w: lib.zvx_denoise_ex(ctx._h, x, _lib._ptr(l), 1, n, _lib._ptr(bias), C.byref(dn), o, n, F, w.in_origin, w.out_begin, w.out_count, 0),
           lambda x, l, n, o, w: lib.zvx_denoise_rows(ctx._h, x, _lib._ptr(l), B, n, _lib._ptr(bias), C.byref(dn), o, n, F, w)),
     bench("limit", 2 * W + _lib.LIMIT_ENV_REACH,
           lambda x, l, n, o, w: lib.zvx_limit_ex(ctx._h, x, _lib._ptr(l), 1, n, RATE, C.byref(lim), o, n, None, None, F, w.in_origin, w.out_begin, w.out_count, 0),
-          lambda x, l, n, o, w: lib.zvx_limit_rows(ctx._h, x, _lib._ptr(l), B, n, RATE, C.byref(lim), o, n, None, None, F, w))]}
+          lambda x, l, n, o, w: lib.zvx_limit_rows(ctx._h, x, _lib._ptr(l), B, n, RATE, C.byref(lim), o, n, None, None, F, w)),
+    resample_line(48000), resample_line(8000)]}
 print(json.dumps(res))
 if args.out:
     json.dump(res, open(args.out, "w"), indent=1)

@@ -1,6 +1,6 @@
 """What stepping many stream sessions in one call buys (include/zvx.h: zvx_stream_next_many): N listeners, HiFi-GAN V1 bf16, one 896-frame
 mel each, 16-frame chunks, chunks_per_call 1, in one process on one GPU.  A development aid; nothing on the product path imports it.
-   python tools/stream_many_bench.py [--denoise S] [--peak-db DB] [--sessions 1,4,16,64] [--no-many] [out.json]
+   python tools/stream_many_bench.py [--denoise S] [--peak-db DB] [--out-rate HZ] [--sessions 1,4,16,64] [--no-many] [out.json]
 Per chain (the plain chain; with --denoise / --peak-db also denoiser + limiter) and per N, the median time of one ROUND -- every session
 advanced by one piece, host pieces, the call's own wait inside --
    (a) by N zvx_stream_next calls, one after the other,
@@ -8,7 +8,9 @@ advanced by one piece, host pieces, the call's own wait inside --
 the two alternating pass by pass over the same mels, the ratio (a) / (b), whether both hand out the same bits, and for (b) the split of a
 round between the vocoder stage (zvx_stage_times, profile 1, in passes of their own) and the rest.  The first round of a pass (start-up)
 and the last (the stages flush) are not counted.  --no-many times (a) alone: it uses only entry points that exist without the call, so it
-runs on a tree that lacks it."""
+runs on a tree that lacks it.  --out-rate HZ opens every session under that output rate (zvx_set_int "out_rate" around the opens), so each
+chain ends in the rate conversion; the rows then also carry, from one pass of (b) under profile 2, the time per round of the post
+stages' launch groups by tag and the "voc.resample" groups per round."""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -19,6 +21,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("out", nargs="?", help="write the result as JSON here")
 ap.add_argument("--denoise", type=float, default=None, metavar="S", help="also time the chain denoiser + limiter: the denoiser's strength")
 ap.add_argument("--peak-db", type=float, default=None, metavar="DB", help="... and the limiter's ceiling (dBFS); both or neither")
+ap.add_argument("--out-rate", type=int, default=0, metavar="HZ", help="open the sessions under this output rate (0: the model's own)")
 ap.add_argument("--sessions", default="1,4,16,64")
 ap.add_argument("--passes", type=int, default=3, help="passes per mode and N (a pass streams every mel to its end)")
 ap.add_argument("--no-many", action="store_true", help="mode (a) only")
@@ -42,7 +45,11 @@ if args.denoise is not None:
 
 def run_pass(N, kw, many, profile=False):
     """streams N mels to their ends -> (round times [s], vocoder stage ms per round or None, the concatenated pieces per session)"""
-    streams = [ctx.stream_open(mels[i], chunk_frames=CHUNK, chunks_per_call=1, **kw) for i in range(N)]
+    ctx.set_int("out_rate", args.out_rate)                   # captured by the sessions as they open
+    try:
+        streams = [ctx.stream_open(mels[i], chunk_frames=CHUNK, chunks_per_call=1, **kw) for i in range(N)]
+    finally:
+        ctx.set_int("out_rate", 0)
     cap = max(s.info()["max_piece"] for s in streams)
     bufs = [np.empty(cap, np.float32) for _ in range(N)]
     ptrs = [_lib._ptr(b) for b in bufs]
@@ -70,7 +77,26 @@ def same(a, b):
     return all(x.shape == y.shape and np.array_equal(x.view(np.uint32), y.view(np.uint32)) for x, y in zip(a, b))
 
 
-res = {"workload": f"N sessions, one {L}-frame mel each, HiFi-GAN V1 bf16, {CHUNK}-frame chunks, chunks_per_call 1, halo {ZeroVox.STREAM_HALO}; "
+TAGS = ("voc.resample", "post.denoise", "post.limit", "post.stream")
+
+
+def tag_split(N, kw):
+    """one pass of (b) under profile 2 -> ({tag: ms per round}, "voc.resample" launch groups per round), over all rounds of the pass"""
+    ctx.set_int("profile", 2)
+    try:
+        ctx.sync()
+        ctx.reset_stats()
+        rounds = len(run_pass(N, kw, True)[0]) + 2
+        ctx.sync()
+        t = {v["name"]: v for v in ctx.tag_stats()}
+    finally:
+        ctx.set_int("profile", 0)
+    return ({k: round(t[k]["ms"] / rounds, 4) for k in TAGS if k in t},
+            round(t["voc.resample"]["launches"] / rounds, 2) if "voc.resample" in t else 0.0)
+
+
+res = {"workload": f"N sessions, one {L}-frame mel each, HiFi-GAN V1 bf16, {CHUNK}-frame chunks, chunks_per_call 1, halo {ZeroVox.STREAM_HALO}, "
+                   f"output rate {args.out_rate or 'native'}; "
                    f"median ms per round of {L // CHUNK - 2} rounds x {args.passes} passes", "rows": []}
 for name, kw in chains.items():
     for N in NS:
@@ -97,6 +123,8 @@ for name, kw in chains.items():
                         "same_bits": bool(equal), "b_profiled_round_ms": round(float(np.median(r)) * 1e3, 3),
                         "b_vocoder_stage_ms": round(float(np.median(v)), 3),
                         "b_rest_ms": round(float(np.median(r)) * 1e3 - float(np.median(v)), 3)})
+            if args.out_rate:
+                row["b_tag_ms_per_round"], row["b_resample_groups_per_round"] = tag_split(N, kw)
         res["rows"].append(row)
         print(row, flush=True)
 print(json.dumps(res))

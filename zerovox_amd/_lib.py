@@ -27,7 +27,7 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_encode_ex", "zvx_synthesize_ex", "zvx_resample", "zvx_resample_ex", "zvx_trim_bounds", "zvx_join",
            "zvx_loudness", "zvx_normalize", "zvx_true_peak", "zvx_limit", "zvx_spkemb_wav", "zvx_limit_ex", "zvx_denoise_bias", "zvx_denoise",
            "zvx_denoise_ex", "zvx_stream_open", "zvx_stream_next", "zvx_stream_info", "zvx_stream_close", "zvx_stream_next_many",
-           "zvx_denoise_rows", "zvx_limit_rows")
+           "zvx_denoise_rows", "zvx_limit_rows", "zvx_resample_rows")
 ZVX_STREAM_MANY_MAX_SESSIONS, ZVX_STREAM_MANY_MAX_ROWS = 64, 256
 ZVX_COMM_ID_BYTES = 128
 ZVX_LOUD_PER_ROW, ZVX_LOUD_COMMON = 0, 1
@@ -158,6 +158,7 @@ def load():
     lib.zvx_denoise_ex.argtypes = lib.zvx_denoise.argtypes + [C.c_int64, C.c_int64, C.c_int64, C.c_int]
     lib.zvx_denoise_rows.argtypes = lib.zvx_denoise.argtypes + [C.POINTER(RowWindow)]
     lib.zvx_limit_rows.argtypes = lib.zvx_limit.argtypes + [C.POINTER(RowWindow)]
+    lib.zvx_resample_rows.argtypes = lib.zvx_resample.argtypes + [C.POINTER(RowWindow)]
     lib.zvx_stream_open.argtypes = [vp, vp, C.c_int, C.POINTER(StreamParams), C.c_int, C.POINTER(vp)]
     lib.zvx_stream_next.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int]
     lib.zvx_stream_info.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
@@ -590,6 +591,28 @@ class Context:
         self._chk(self._lib.zvx_limit_rows(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), out.shape[1], _ptr(peak),
                                            _ptr(gmin), flags, win))
         return [out[b, :cnt[b]] for b in range(B)], peak, gmin
+
+    def resample_rows(self, rows, rate_in, rate_out, windows, pcm16=False, lengths=None):
+        """zvx_resample_rows on host rows: resample_window with a window per row -- windows[b] = (in_origin, out_begin, out_count) or
+        (in_origin, out_begin, out_count, last); row b holds samples [in_origin, in_origin + len) of a signal that is zero elsewhere ->
+        (a list of B arrays, row b's emitted samples (float32 / int16), bit for bit those of resample_window on that row alone,
+        out_len [B])."""
+        x, n = self._rows(rows, lengths)
+        B, Nmax = x.shape
+        if len(windows) != B:
+            raise ValueError(f"{len(windows)} windows for {B} rows")
+        win = (RowWindow * max(B, 1))()
+        cnt = np.zeros(B, np.int64)
+        for b, w in enumerate(windows):
+            in_origin, out_begin, out_count = (int(v) for v in w[:3])
+            win[b] = RowWindow(in_origin, out_begin, out_count, 1 if len(w) > 3 and w[3] else 0, 0)
+            cnt[b] = out_count if out_count >= 0 else max(0, resampled_len(in_origin + int(n[b]), rate_in, rate_out) - out_begin)
+        cols = max(int(cnt.max()) if B else 0, 1)
+        out = np.zeros((B, cols), np.int16 if pcm16 else np.float32)
+        out_len = np.zeros(B, np.int32)
+        self._chk(self._lib.zvx_resample_rows(self._h, _ptr(x), _ptr(n), B, Nmax, int(rate_in), int(rate_out), _ptr(out), cols, _ptr(out_len),
+                                              ZVX_PCM16 if pcm16 else 0, win))
+        return [out[b, :out_len[b]] for b in range(B)], out_len
 
     def denoise_device(self, ptr, lengths, Nmax, bias, strength, *, floor=0.0, no_sync=False):
         """zvx_denoise IN PLACE on device rows [B][Nmax] f32 at `ptr` (they may be the output of a synthesize / vocode_device call queued

@@ -1346,6 +1346,21 @@ void launch_fc_rows(const float* x, int ldx, const float* w, int ldw, const floa
 }
 
 // ---------------------------------------------------------------- band-limited rational resampler (polyphase FIR)
+// The row a workgroup works on (zvx_kernels.h, ResampleRow): its entry of the table, or the same thing formed from the uniform fields.  b is
+// a block index: the same for every lane, so the entry arrives through scalar loads.
+__device__ __forceinline__ ResampleRow rs_row(const ResampleArgs& a, int b) {
+    if (a.rows) return a.rows[b];
+    ResampleRow r;
+    r.x = a.x + (long)b * a.x_bs;
+    r.out = a.pcm16 ? (void*)((short*)a.out + (long)b * a.out_bs) : (void*)((float*)a.out + (long)b * a.out_bs);
+    r.n = (long)a.in_len[b] * a.in_mul;
+    r.in_origin = a.in_origin; r.out_begin = a.out_begin;
+    long cnt = a.out_count;                                  // outputs of this row, counted from out_begin
+    if (cnt < 0) { cnt = ((a.in_origin + r.n) * a.L + a.M - 1) / a.M - a.out_begin; if (cnt < 0) cnt = 0; }
+    r.cnt = cnt > a.out_max ? a.out_max : cnt;
+    r.zend = a.out_max;                                      // zeros up to the longest row of the call
+    return r;
+}
 // y[n] = sum_k h[n M - k L] x[k] over the window described in zvx_kernels.h (ResampleArgs).  One workgroup loads the polyphase bank
 // [L][pitch] into LDS once and then produces `tpb` tiles of `tile` consecutive outputs of one row; per tile the input span
 // [kstart(first n), kstart(last n) + T) is staged in LDS with 16-byte loads (zeros outside the row's samples), every thread computes 4
@@ -1359,14 +1374,13 @@ __global__ __launch_bounds__(256) void k_resample_poly(const ResampleArgs a, int
     const int nbank = (a.L * a.pitch + 3) & ~3;
     float* xs = bk + nbank;
     const int b = blockIdx.y, tid = threadIdx.x;
+    const ResampleRow r = rs_row(a, b);
+    if ((long)blockIdx.x * tpb * tile >= r.zend) return;     // past the row's extent: uniform over the workgroup, before the bank load and every barrier
     for (int i = tid * 4; i < nbank; i += 1024) *(float4*)(bk + i) = *(const float4*)(a.bank + i);      // (the device bank is padded to 4 floats)
-    const long nin = (long)a.in_len[b] * a.in_mul;
-    long cnt = a.out_count;                                  // outputs of this row, counted from out_begin
-    if (cnt < 0) { cnt = ((a.in_origin + nin) * a.L + a.M - 1) / a.M - a.out_begin; if (cnt < 0) cnt = 0; }
-    if (cnt > a.out_max) cnt = a.out_max;
-    const float* xrow = a.x + (long)b * a.x_bs;
-    const bool vec_in = (((size_t)a.x & 15) == 0) && ((a.x_bs & 3) == 0);
-    const bool vec_out = (a.out_bs & 3) == 0 && (((size_t)a.out & (a.pcm16 ? 7 : 15)) == 0);
+    const long nin = r.n, cnt = r.cnt;                       // the row's samples; its outputs, counted from out_begin
+    const float* xrow = r.x;
+    const bool vec_in = ((size_t)r.x & 15) == 0;
+    const bool vec_out = ((size_t)r.out & (a.pcm16 ? 7 : 15)) == 0;
     // which 4 outputs of a tile a lane takes.  Up-conversion (M < L): tid + 256 q -- neighbouring lanes take neighbouring outputs, whose input
     // windows start at most one sample apart (LDS reads of one address broadcast) and whose phases step by M mod L; each lane stores 4 bytes of
     // a 256-byte run.  Down-conversion: 4 tid + q -- a lane's windows start 4 M / L samples after its neighbour's, and the lane stores its
@@ -1374,22 +1388,22 @@ __global__ __launch_bounds__(256) void k_resample_poly(const ResampleArgs a, int
     const bool strided = a.M < a.L;
     const int step = strided ? 256 * a.M : a.M, dk = step / a.L, dp = step % a.L;
     auto put = [&](long i, float v) {
-        if (a.pcm16) ((short*)a.out)[b * a.out_bs + i] = (short)fminf(fmaxf(v * 32760.0f, -32768.0f), 32767.0f);     // clamp, then truncate
-        else ((float*)a.out)[b * a.out_bs + i] = v;
+        if (a.pcm16) ((short*)r.out)[i] = (short)fminf(fmaxf(v * 32760.0f, -32768.0f), 32767.0f);     // clamp, then truncate
+        else ((float*)r.out)[i] = v;
     };
     for (int tt = 0; tt < tpb; tt++) {
         const long i0 = ((long)blockIdx.x * tpb + tt) * tile;
-        if (i0 >= a.out_max) break;
-        const long iend = i0 + tile < a.out_max ? i0 + tile : a.out_max;
+        if (i0 >= r.zend) break;
+        const long iend = i0 + tile < r.zend ? i0 + tile : r.zend;
         float v[4] = {0.f, 0.f, 0.f, 0.f};
         auto idx = [&](int q) { return strided ? i0 + tid + 256 * q : i0 + 4 * tid + q; };
         if (i0 < cnt) {                                      // (uniform over the workgroup)
             const long ilast = (iend < cnt ? iend : cnt) - 1;
             auto kstart_floor = [&](long n) { const long t = n * a.M - a.half; return t >= 0 ? t / a.L : -((-t + a.L - 1) / a.L); };
-            const long k_lo = kstart_floor(a.out_begin + i0) & ~3L;                // a lower bound of kstart, on a 4-sample boundary of the signal
-            const long k_hi = kstart_floor(a.out_begin + ilast) + 1 + a.T;         // exclusive upper bound
-            const long li_lo = k_lo - a.in_origin;                                 // row index of xs[0]
-            const bool vin = vec_in && (a.in_origin & 3) == 0;
+            const long k_lo = kstart_floor(r.out_begin + i0) & ~3L;                // a lower bound of kstart, on a 4-sample boundary of the signal
+            const long k_hi = kstart_floor(r.out_begin + ilast) + 1 + a.T;         // exclusive upper bound
+            const long li_lo = k_lo - r.in_origin;                                 // row index of xs[0]
+            const bool vin = vec_in && (r.in_origin & 3) == 0;
             const int span = (int)(k_hi - k_lo);                                   // <= xcap by the launcher's choice of `tile`
             __syncthreads();                                                        // the previous tile's readers are done (first tile: the bank is in)
             for (int j = tid * 4; j < span && j < xcap; j += 1024) {
@@ -1406,7 +1420,7 @@ __global__ __launch_bounds__(256) void k_resample_poly(const ResampleArgs a, int
             }
             __syncthreads();
             if (idx(0) < iend && idx(0) < cnt) {
-                const unsigned long nM = (unsigned long)(a.out_begin + idx(0)) * (unsigned long)a.M;
+                const unsigned long nM = (unsigned long)(r.out_begin + idx(0)) * (unsigned long)a.M;
                 long k0 = (long)(nM / (unsigned long)a.L);
                 int p = (int)(nM - (unsigned long)k0 * (unsigned long)a.L);
 #pragma unroll
@@ -1430,8 +1444,8 @@ __global__ __launch_bounds__(256) void k_resample_poly(const ResampleArgs a, int
                 short4 o;
                 o.x = (short)fminf(fmaxf(v[0] * 32760.0f, -32768.0f), 32767.0f); o.y = (short)fminf(fmaxf(v[1] * 32760.0f, -32768.0f), 32767.0f);
                 o.z = (short)fminf(fmaxf(v[2] * 32760.0f, -32768.0f), 32767.0f); o.w = (short)fminf(fmaxf(v[3] * 32760.0f, -32768.0f), 32767.0f);
-                *(short4*)((short*)a.out + b * a.out_bs + i) = o;
-            } else *(float4*)((float*)a.out + b * a.out_bs + i) = make_float4(v[0], v[1], v[2], v[3]);
+                *(short4*)((short*)r.out + i) = o;
+            } else *(float4*)((float*)r.out + i) = make_float4(v[0], v[1], v[2], v[3]);
         } else {
             for (int q = 0; q < 4; q++) if (idx(q) < iend) put(idx(q), v[q]);
         }

@@ -2527,7 +2527,8 @@ const double* limit_win(zvx_ctx* c, int W) {
 
 // The window of zvx_limit_ex and zvx_denoise_ex: the rows hold samples [in_origin, in_origin + nsamples[b]) of their signals, the outputs
 // [out_begin, out_begin + cnt_b) are emitted.  The whole-row calls are {0, 0, -1, 1}.
-// (do_resample's window is another contract -- its rows are zero outside the window and it has no support condition -- and stays on its own.)
+// (do_resample's window is another contract -- its rows are zero outside the window and it has no support condition -- and stays on its own;
+// its per-row form, do_resample_rows, carries the same three numbers per row and ignores `last`.)
 struct RowsWindow { int64_t in_origin = 0, out_begin = 0, out_count = -1; int last = 1; };
 // per row the emitted count, after the window's own checks and the support condition of include/zvx.h for the reach R (zvx_limit_ex:
 // 2 W + H; zvx_denoise_ex: n_fft - 1)
@@ -2949,7 +2950,78 @@ void do_limit_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, 
     }
 }
 
-constexpr int DN_BIAS_FRAMES = 88;       // mel frames of silence the bias is measured on
+// The rate conversion over B rows with a window each (zvx_resample_rows, the batched conversions of zvx_stream_next_many): ONE table upload,
+// the one launch of run_resample under one timed group.  A row's window is the resampler's own contract -- zero outside the row's samples, no
+// support condition; `last` takes no part -- and nothing outside [0, cnt) of its output is written.  Flops and bytes are what run_resample
+// counts for each row with cnt > 0 alone (a one-row call that emits nothing launches and counts nothing).  The caller has validated the rows.
+void run_resample_rows(zvx_ctx* c, const zvx_ctx::RsBank& bk, const PostRow* rows, int B, int pcm16) {
+    std::vector<ResampleRow> tab((size_t)B);
+    double nin = 0, nout = 0;
+    long cnt_max = 0;
+    for (int b = 0; b < B; b++) {
+        const PostRow& r = rows[b];
+        ResampleRow& t = tab[(size_t)b];
+        t.x = r.in; t.out = r.out; t.n = r.n;
+        t.in_origin = (long)r.w.in_origin; t.out_begin = (long)r.w.out_begin; t.cnt = r.cnt; t.zend = r.cnt;
+        cnt_max = std::max<long>(cnt_max, r.cnt);
+        if (r.cnt > 0) { nin += (double)r.n; nout += (double)r.cnt; }
+    }
+    if (cnt_max <= 0) return;
+    ResampleArgs a{};
+    a.B = B; a.pcm16 = pcm16; a.L = bk.L; a.M = bk.M; a.half = bk.half; a.T = bk.T; a.pitch = bk.pitch; a.bank = bk.dev;
+    a.out_max = cnt_max;                                     // the grid; every row's own bound is its zend
+    ResampleRow* tab_d = (ResampleRow*)c->buf("rs.rows", (size_t)B * sizeof(ResampleRow));
+    c->upload(tab_d, tab.data(), (size_t)B * sizeof(ResampleRow));
+    a.rows = tab_d;
+    TagScope scope(c, "voc.resample", ZVX_T_RESAMPLE);
+    c->timed(2.0 * nout * bk.T, nin * 4.0 + nout * (pcm16 ? 2.0 : 4.0), [&] {
+        if (!launch_resample_poly(a, c->stream)) fail(ZVX_E_UNSUPPORTED, "resampler: L = %d, M = %d does not fit the LDS of a workgroup", bk.L, bk.M);
+    });
+    scope.close();
+}
+
+// zvx_resample_rows: every check before anything is allocated, uploaded or queued
+void do_resample_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate_in, int rate_out, void* out, int64_t out_stride,
+                      int32_t* out_len, int flags, const zvx_row_window* win) {
+    const char* who = "zvx_resample_rows";
+    rows_args(who, in, nsamples, B, Nmax);
+    if (!out) fail(ZVX_E_INVALID, "%s: out is NULL", who);
+    flags_check(who, flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16);
+    if (!win) fail(ZVX_E_INVALID, "%s: win is NULL", who);
+    for (int b = 0; b < B; b++) {
+        const zvx_row_window& w = win[b];
+        if (w.reserved != 0) fail(ZVX_E_INVALID, "%s: row %d: reserved is %d (must be 0)", who, b, w.reserved);
+        if (w.last != 0 && w.last != 1) fail(ZVX_E_INVALID, "%s: row %d: last is %d (0 or 1)", who, b, w.last);
+        if (w.in_origin < 0 || w.out_begin < 0 || w.out_count < -1 || w.in_origin > ((int64_t)1 << 40) || w.out_begin > ((int64_t)1 << 40) || w.out_count > INT32_MAX)
+            fail(ZVX_E_INVALID, "%s: row %d: window out of range (in_origin %lld, out_begin %lld, out_count %lld)", who, b, (long long)w.in_origin,
+                 (long long)w.out_begin, (long long)w.out_count);
+    }
+    int L = 1, M = 1;
+    rs_pair(rate_in, rate_out, &L, &M);                     // (its ZVX_E_UNSUPPORTED ranks before a bad length, as in zvx_resample)
+    rows_check(who, in, nsamples, B, Nmax);
+    RowsWindows rw;
+    rw.w.resize((size_t)B); rw.cnt.resize((size_t)B);
+    for (int b = 0; b < B; b++) {
+        const zvx_row_window& w = win[b];
+        const int64_t n = w.out_count >= 0 ? w.out_count : std::max<int64_t>(0, rs_out_len((long)(w.in_origin + nsamples[b]), L, M) - w.out_begin);
+        if (n > INT32_MAX) fail(ZVX_E_INVALID, "%s: row %d: %lld output samples", who, b, (long long)n);
+        rw.w[(size_t)b] = RowsWindow{w.in_origin, w.out_begin, w.out_count, w.last};
+        rw.cnt[(size_t)b] = (int32_t)n;
+        rw.cnt_max = std::max<long>(rw.cnt_max, (long)n);
+    }
+    if (out_stride < rw.cnt_max) fail(ZVX_E_BUFFER, "%s: out_stride %lld < %ld samples, the longest output row", who, (long long)out_stride, rw.cnt_max);
+    const zvx_ctx::RsBank& bk = rs_bank(c, L, M);
+    RowsReturn ret(c, B, 0, false, true, rw.cnt_max, flags);
+    const float* x = rows_to_device(c, "rs", in, B, Nmax, flags);
+    long out_bs = 0;
+    void* od = ret.out_rows("rs.out", out, out_stride, &out_bs);
+    const std::vector<PostRow> rows = post_rows(x, Nmax, od, out_bs, ret.ss, nsamples, rw, B);
+    run_resample_rows(c, bk, rows.data(), B, (flags & ZVX_PCM16) ? 1 : 0);
+    if (out_len) for (int b = 0; b < B; b++) out_len[b] = rw.cnt[(size_t)b];
+    ret.finish(nullptr, out, out_stride, rw.cnt.data(), flags);
+}
+
+constexpr int DN_BIAS_FRAMES = 88;      // mel frames of silence the bias is measured on
 
 void do_denoise_bias(zvx_ctx* c, float* bias) {
     const char* who = "zvx_denoise_bias";
@@ -3260,7 +3332,8 @@ void stream_run_stages(const char* who, zvx_stream* s, const StreamStep& p, floa
 // kind the sessions whose stage has bitwise-equal parameters (the bias by content; the limiter by W, oversampling and ceiling) form one
 // group (stream_plan.h, partition_classes), and a group is ONE call of the per-row form: its rows are the sessions' [history | new]
 // buffers with each session's own window, each output goes straight behind the next stage's history or to the final destination.  The
-// rate conversion stays one call per session (another window contract).  All history drops of the call are ONE launch over a table.
+// rate conversions are grouped by (native rate, output rate) -- the polyphase bank -- and a group is one run_resample_rows.  All history
+// drops of the call are ONE launch over a table.
 void stream_run_stages_many(const char* who, zvx_ctx* c, zvx_stream* const* ss, const std::vector<StreamStep>& plans, const std::vector<float*>& final_dst,
                             int n) {
     struct Slot { bool run = false; PostRow row{}; };
@@ -3320,14 +3393,22 @@ void stream_run_stages_many(const char* who, zvx_ctx* c, zvx_stream* const* ss, 
             else run_limit_rows(c, who, rows.data(), (int)rows.size(), &first->lim, first->lim_W, 0);
         }
     }
-    // ---- rate conversions: one call per session
-    const int f = ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC;
+    // ---- rate conversions: one call of the per-row form per (native rate, output rate)
     for (int i = 0; i < n; i++) {
-        const Slot& sl = slot[zvx_stream::RESAMPLE][(size_t)i];
-        if (!sl.run) continue;
-        const int32_t n32 = sl.row.n;
-        do_resample(c, sl.row.in, &n32, 1, n32, ss[i]->native, ss[i]->out_rate, sl.row.out, std::max<int64_t>(n32, sl.row.cnt), nullptr, f, sl.row.w.in_origin,
-                    sl.row.w.out_begin, sl.row.cnt);
+        cls[(size_t)i] = -1;
+        if (!slot[zvx_stream::RESAMPLE][(size_t)i].run) continue;
+        cls[(size_t)i] = i;
+        for (int j = 0; j < i; j++)
+            if (cls[(size_t)j] == j && ss[j]->native == ss[i]->native && ss[j]->out_rate == ss[i]->out_rate) { cls[(size_t)i] = j; break; }
+    }
+    const int rs_groups = zvx_plan::partition_classes(cls.data(), n, order.data(), start.data());
+    for (int gi = 0; gi < rs_groups; gi++) {
+        rows.clear();
+        for (int m = start[(size_t)gi]; m < start[(size_t)gi + 1]; m++) rows.push_back(slot[zvx_stream::RESAMPLE][(size_t)order[(size_t)m]].row);
+        const zvx_stream* first = ss[order[(size_t)start[(size_t)gi]]];
+        int L = 1, M = 1;
+        rs_pair(first->native, first->out_rate, &L, &M);
+        run_resample_rows(c, rs_bank(c, L, M), rows.data(), (int)rows.size(), 0);
     }
     // ---- every history drop of the call in one launch
     if (!moves.empty()) {
@@ -3792,6 +3873,11 @@ zvx_status zvx_resample(zvx_ctx* c, const float* in, const int32_t* nsamples, in
 zvx_status zvx_resample_ex(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate_in, int rate_out, void* out,
                            int64_t out_stride, int32_t* out_len, int flags, int64_t in_origin, int64_t out_begin, int64_t out_count) {
     return guarded(c, [&] { do_resample(c, in, nsamples, B, Nmax, rate_in, rate_out, out, out_stride, out_len, flags, in_origin, out_begin, out_count); });
+}
+
+zvx_status zvx_resample_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate_in, int rate_out, void* out,
+                             int64_t out_stride, int32_t* out_len, int flags, const zvx_row_window* win) {
+    return guarded(c, [&] { do_resample_rows(c, in, nsamples, B, Nmax, rate_in, rate_out, out, out_stride, out_len, flags, win); });
 }
 
 zvx_status zvx_trim_bounds(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_join_params* params, int32_t* begin,

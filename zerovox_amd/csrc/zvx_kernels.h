@@ -348,7 +348,21 @@ void launch_conv_post_tanh(const void* x, int x_dt, int ldx, long x_bs, const fl
 // bank: [L][pitch] f32 on the device (padded to a multiple of 4 floats): row p holds the T = ceil((2 half + 1) / L) taps of phase p in
 // ascending input order, bank[p][t] = h[p + (joff[p] - t) L] (0 where that index is below -half), and in column T the integer
 // joff[p] = (half - p) / L as raw bits.  L = M = T = 1, half = 0, bank = {1.0f, 0}: a copy.
+// Per-row form (zvx_resample_rows, the batched rate conversions of zvx_stream_next_many): `rows` is a device table with one ResampleRow per
+// row -- its input and output pointers, its length, its own in_origin / out_begin / cnt and the bound `zend` up to which zeros follow the
+// emitted samples --, so that the rows of one launch may live in unrelated buffers and sit anywhere on their signals.  The kernel resolves
+// ONE ResampleRow at its top and works from it alone: without a table it is formed from the uniform fields (zend = out_max: the zero fill
+// to the longest row), with one zend = cnt (nothing outside [0, cnt) is written).  One body: the sum of an output is the same instructions
+// in every form.  The 16-byte load and store paths are chosen per row from that row's own pointers and in_origin & 3; they change no bit.
+// The grid is sized by out_max, the longest row; a workgroup whose first tile lies at or past its row's zend returns before the bank load.
+struct ResampleRow {
+    const float* x; void* out;               // the row's samples; where emitted sample 0 goes (f32 or int16)
+    long n;                                  // the row's length
+    long in_origin, out_begin, cnt;          // the window: outputs [out_begin, out_begin + cnt) go to [0, cnt)
+    long zend;                               // zeros are written to [cnt, zend)
+};
 struct ResampleArgs {
+    const ResampleRow* rows;                 // NULL: the uniform form below
     const float* x; long x_bs; const int* in_len; int in_mul;
     void* out; long out_bs; int pcm16;
     int B, L, M, half, T, pitch;
