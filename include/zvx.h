@@ -572,10 +572,13 @@ zvx_status zvx_denoise_ex(zvx_ctx* ctx, const float* in, const int32_t* nsamples
  *   whole-signal call (f32, and int16 with ZVX_PCM16).  Independently per row: peak_in[b] / min_gain[b] cover the row's emitted range (0 and
  *   1 where it is empty); out_count == -1 needs that row's last; an empty range writes nothing; a row's bits depend neither on which other
  *   rows share the call nor on their windows; nothing outside [0, cnt_b) of an output row is touched.
- * How: the kernels of all three forms resolve one row descriptor at their top -- input, output and work-buffer / envelope pointers, length,
- *   emitted range, and for the denoiser origin, first frame, skip, rel and the two mirrors -- and work from it alone; the per-row calls read
- *   it from a device table (uploaded through the context's pinned staging, queued like a launch), the uniform calls form the same thing from
- *   their arguments.  One body, so no two forms can contract a multiply-add differently.  Each denoiser row's first frame is rounded down to
+ * How: the kernels read one row descriptor at their top -- input, output and work-buffer / envelope pointers, length, emitted range, and
+ *   for the denoiser origin, first frame, skip, rel and the two mirrors -- and work from it alone.  EVERY call of the denoiser and the
+ *   limiter -- whole-row, _ex, _rows, zvx_true_peak, zvx_denoise_bias, the streams' stages -- forms these descriptors on the host and
+ *   uploads them as one row table through the context's pinned staging arena, queued like a launch: there is one way to fill a descriptor
+ *   and one kernel body, so no two forms can contract a multiply-add differently.  (A table larger than what is left of the 2 MiB arena --
+ *   roughly 32 k rows in one call -- goes over as a plain copy that is COMPLETE when it returns: such a call, when queued, waits once;
+ *   nothing else about it changes.)  Each denoiser row's first frame is rounded down to
  *   a multiple of 4096 / n_fft on its OWN grid, so a frame keeps the slot it has in the whole call; the signal's frame count is formed in
  *   64 bits from the row's origin; the overlap-add sums in ascending f.  The limiter's envelope runs on each row's own tile grid over its
  *   window, the gain tiles start at the row's own offset, the sums keep their orders.  No index is formed in 32 bits from an absolute
@@ -610,10 +613,12 @@ zvx_status zvx_limit_rows(zvx_ctx* ctx, const float* in, const int32_t* nsamples
  * Like zvx_resample_ex: the rate pair stays per CALL (the polyphase bank and the tile depend on (L, M) only); the flags, syncs and the queued
  *   form -- ZVX_DEVICE_IN, ZVX_DEVICE_OUT, ZVX_NO_SYNC (device output only), ZVX_PCM16; win and nsamples are host arrays and may be reused
  *   when the call returns; equal rates are a copy of each emitted range.
- * How: the one resampling kernel resolves a row descriptor at its top -- input and output pointers, length, in_origin, out_begin, cnt and
- *   the bound up to which zeros follow (the longest row for the uniform calls, cnt_b here) -- and works from it alone; this call reads it from
- *   a device table (uploaded through the context's pinned staging, queued like a launch), zvx_resample / zvx_resample_ex form it from their
- *   arguments.  One body: the sum of an output keeps its single order in every form.  The 16-byte load and store paths are chosen per row
+ * How: the one resampling kernel reads a row descriptor at its top -- input and output pointers, length, in_origin, out_begin, cnt and
+ *   the bound up to which zeros follow (the longest row for zvx_resample / zvx_resample_ex, cnt_b here) -- and works from it alone.  EVERY
+ *   rate conversion -- this call, zvx_resample, zvx_resample_ex, zvx_vocode under an output rate, zvx_spkemb_wav, the streams -- forms these
+ *   descriptors on the host and uploads them as one row table through the context's pinned staging arena, queued like a launch (a table
+ *   larger than what is left of the 2 MiB arena is a plain copy, complete when it returns: such a call, when queued, waits once).  One way
+ *   to fill a descriptor, one body: the sum of an output keeps its single order in every call.  The 16-byte load and store paths are chosen per row
  *   from that row's own pointers and in_origin & 3 and change no bit.  No index is formed in 32 bits from an absolute position: in_origin and
  *   out_begin may lie beyond 2^32.  The grid is sized by the longest cnt_b; workgroups past a row's extent return at once.
  * Validation, all before anything is queued (the context stays usable): every check of zvx_resample_ex, its window checks per row with the

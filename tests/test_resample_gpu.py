@@ -157,6 +157,42 @@ def test_windows_concatenate_to_the_one_call_result(rate_in, rate_out):
     assert np.array_equal(tail[0].view(np.uint32), whole[cuts[4]:].view(np.uint32))
 
 
+def test_a_row_that_emits_nothing_next_to_one_that_does():
+    """zvx_resample_ex, one window for two rows of 40 and 2000 samples, outputs from 100 on: row 0 has only 15 outputs at 8 kHz and emits
+    nothing, yet it is zero-filled up to row 1's count and its 40 input samples count as read, as for every row of a call that writes."""
+    ctx = ctx_for("tiny")
+    rate_in, rate_out, begin = 22050, 8000, 100
+    rng = np.random.default_rng(21)
+    rows = [rng.uniform(-1, 1, k).astype(np.float32) for k in (40, 2000)]
+    x, n = padded(rows)
+    full = [_lib.resampled_len(int(v), rate_in, rate_out) for v in n]
+    assert full[0] == 15 and full[0] < begin < full[1]
+    want_len = np.array([0, full[1] - begin], np.int32)
+    nmax = int(want_len[1])
+    stride = nmax + 37
+    out_len = np.full(2, -1, np.int32)
+    dout = ctx.dev_alloc(2 * stride * 4)
+    try:
+        ctx.dev_from_host(dout, np.full((2, stride), SENTINEL32, np.uint32))
+        ctx.set_int("profile", 2)
+        try:
+            ctx.reset_stats()
+            assert raw_resample(ctx, x, n, rate_in, rate_out, dout, stride, _lib.ZVX_DEVICE_OUT, out_len, ex=(0, begin, -1)) == 0, ctx._lib.zvx_last_error(ctx._h)
+            tags = {t["name"]: t for t in ctx.tag_stats()}
+        finally:
+            ctx.set_int("profile", 0)
+        got = ctx.dev_to_host(dout, (2, stride), np.uint32)
+    finally:
+        ctx.dev_free(dout)
+    assert np.array_equal(out_len, want_len)
+    assert np.all(got[0, :nmax] == 0), "row 0: not zero up to the longest row's count"
+    assert np.all(got[:, nmax:] == SENTINEL32), "written past the longest row's count"
+    alone, l1 = ctx.resample_window([rows[1]], rate_in, rate_out, in_origin=0, out_begin=begin, out_count=-1)
+    assert l1[0] == want_len[1] and np.array_equal(got[1, :nmax], alone[0].view(np.uint32))
+    assert [t for t in tags if t != "voc.resample" and tags[t]["launches"]] == [] and tags["voc.resample"]["launches"] == 1, tags
+    assert tags["voc.resample"]["bytes"] == 4.0 * (40 + 2000) + 4.0 * int(want_len[1]), tags["voc.resample"]
+
+
 def test_errors_leave_the_context_usable():
     ctx = ctx_for("tiny")
     x = np.zeros((1, 100), np.float32); n = np.array([100], np.int32)

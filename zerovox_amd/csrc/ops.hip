@@ -1346,21 +1346,6 @@ void launch_fc_rows(const float* x, int ldx, const float* w, int ldw, const floa
 }
 
 // ---------------------------------------------------------------- band-limited rational resampler (polyphase FIR)
-// The row a workgroup works on (zvx_kernels.h, ResampleRow): its entry of the table, or the same thing formed from the uniform fields.  b is
-// a block index: the same for every lane, so the entry arrives through scalar loads.
-__device__ __forceinline__ ResampleRow rs_row(const ResampleArgs& a, int b) {
-    if (a.rows) return a.rows[b];
-    ResampleRow r;
-    r.x = a.x + (long)b * a.x_bs;
-    r.out = a.pcm16 ? (void*)((short*)a.out + (long)b * a.out_bs) : (void*)((float*)a.out + (long)b * a.out_bs);
-    r.n = (long)a.in_len[b] * a.in_mul;
-    r.in_origin = a.in_origin; r.out_begin = a.out_begin;
-    long cnt = a.out_count;                                  // outputs of this row, counted from out_begin
-    if (cnt < 0) { cnt = ((a.in_origin + r.n) * a.L + a.M - 1) / a.M - a.out_begin; if (cnt < 0) cnt = 0; }
-    r.cnt = cnt > a.out_max ? a.out_max : cnt;
-    r.zend = a.out_max;                                      // zeros up to the longest row of the call
-    return r;
-}
 // y[n] = sum_k h[n M - k L] x[k] over the window described in zvx_kernels.h (ResampleArgs).  One workgroup loads the polyphase bank
 // [L][pitch] into LDS once and then produces `tpb` tiles of `tile` consecutive outputs of one row; per tile the input span
 // [kstart(first n), kstart(last n) + T) is staged in LDS with 16-byte loads (zeros outside the row's samples), every thread computes 4
@@ -1374,7 +1359,7 @@ __global__ __launch_bounds__(256) void k_resample_poly(const ResampleArgs a, int
     const int nbank = (a.L * a.pitch + 3) & ~3;
     float* xs = bk + nbank;
     const int b = blockIdx.y, tid = threadIdx.x;
-    const ResampleRow r = rs_row(a, b);
+    const ResampleRow r = a.rows[b];                         // (b is the same for every lane: the entry arrives through scalar loads)
     if ((long)blockIdx.x * tpb * tile >= r.zend) return;     // past the row's extent: uniform over the workgroup, before the bank load and every barrier
     for (int i = tid * 4; i < nbank; i += 1024) *(float4*)(bk + i) = *(const float4*)(a.bank + i);      // (the device bank is padded to 4 floats)
     const long nin = r.n, cnt = r.cnt;                       // the row's samples; its outputs, counted from out_begin
@@ -2006,17 +1991,6 @@ __device__ __forceinline__ float f32_toward_zero(double g) {
     if (fabs((double)f) > fabs(g)) f = __uint_as_float(__float_as_uint(f) - 1u);
     return f;
 }
-// The row a workgroup works on (zvx_kernels.h, LimitRow): its entry of the table, or the same thing formed from the uniform fields.  b is a
-// block index: the same for every lane, so the entry arrives through scalar loads.
-__device__ __forceinline__ LimitRow lim_row(const LimitArgs& a, int b) {
-    if (a.rows) return a.rows[b];
-    LimitRow r;
-    r.x = a.x + (long)b * a.x_bs;
-    r.out = a.pcm16 ? (void*)((short*)a.out + (long)b * a.out_bs) : (void*)((float*)a.out + (long)b * a.out_bs);
-    r.env = a.env ? a.env + (long)b * a.e_bs : nullptr;
-    r.n = a.nsamples[b]; r.off = a.off; r.cnt = a.cnt[b]; r.pad_ = 0;
-    return r;
-}
 // Oversampled point m = os k0 + p is the resampler's output for (L, M) = (os, 1): its window starts at x[k0 - 10] for p = 0 and at
 // x[k0 - 9] otherwise, and it is summed as k_resample_poly sums it -- acc = bank[p][0] * x[ks]; acc = fma(bank[p][t], x[ks + t], acc).
 // The workgroup evaluates the points of samples t0 - 1 .. t0 + LIMIT_TILE - 1 (those of t0 - 1 count for the envelope of t0) and keeps,
@@ -2028,7 +2002,7 @@ __global__ __launch_bounds__(256) void k_limit_env(const LimitArgs a) {
     __shared__ __attribute__((aligned(16))) float bks[8 * LIM_BP];
     __shared__ float red[4];
     const int b = blockIdx.y, tid = threadIdx.x;
-    const LimitRow r = lim_row(a, b);
+    const LimitRow r = a.rows[b];                            // (b is the same for every lane: the entry arrives through scalar loads)
     const int n = r.n;
     const long t0 = (long)blockIdx.x * LIMIT_TILE;
     float pk = 0.f;
@@ -2098,7 +2072,7 @@ __global__ __launch_bounds__(256) void k_limit_gain(const LimitArgs a) {
     float* es = (float*)(Ds + SD);
     float* red = es + SE;                                    // (no static LDS: the opt-in beyond 64 KiB covers the dynamic part alone)
     const int b = blockIdx.y, tid = threadIdx.x;
-    const LimitRow r = lim_row(a, b);
+    const LimitRow r = a.rows[b];                            // (b is the same for every lane: the entry arrives through scalar loads)
     const int n = r.n;
     const long t0 = r.off + (long)blockIdx.x * LIMIT_TILE;   // the tiles cover the emitted range [off, iend), wherever `off` lies
     const long iend = min((long)n, (long)r.off + r.cnt);

@@ -80,18 +80,6 @@ __device__ __forceinline__ void dn_fft(float* sre, float* sim, const float2* __r
     }
 }
 
-// The row a workgroup works on (zvx_kernels.h, DenoiseRow): its entry of the table, or the same thing formed from the uniform fields.  b is
-// blockIdx.y: the same for every lane, so the entry arrives through scalar loads.
-__device__ __forceinline__ DenoiseRow dn_row(const DenoiseArgs& a, int b) {
-    if (a.rows) return a.rows[b];
-    DenoiseRow r;
-    r.x = a.x + (long)b * a.x_bs;
-    r.out = a.pcm16 ? (void*)((short*)a.out + (long)b * a.out_bs) : (void*)((float*)a.out + (long)b * a.out_bs);
-    r.work = a.work + (long)b * a.Fmax * a.n_fft;
-    r.origin = a.origin; r.f_first = a.f_first;
-    r.n = a.nsamples[b]; r.skip = a.skip; r.rel = a.rel; r.off = a.off; r.cnt = a.cnt; r.mirrors = (a.left ? 1 : 0) | (a.right ? 2 : 0);
-    return r;
-}
 // The window of a row of n samples (zvx_kernels.h, DenoiseArgs): the emitted count; the signal's frames from f_first on (all there will be
 // where the signal goes on); the frames transformed, i.e. those up to the last one that begins at or before the last emitted sample.
 __device__ __forceinline__ int dn_count(const DenoiseRow& r) {
@@ -114,7 +102,7 @@ __device__ __forceinline__ int dn_frames_used(const DenoiseArgs& a, const Denois
 __global__ __launch_bounds__(DN_THREADS) void k_denoise_frames(const DenoiseArgs a) {
     __shared__ float sre[DN_PLANE], sim[DN_PLANE];
     const int tid = threadIdx.x, b = blockIdx.y, N = a.n_fft, lg = a.log2n;
-    const DenoiseRow r = dn_row(a, b);
+    const DenoiseRow r = a.rows[b];                          // (b is the same for every lane: the entry arrives through scalar loads)
     const int n = r.n;
     const int F = dn_frames_used(a, r);                      // frames f_first .. f_first + F - 1 of the signal, f below counted from f_first
     const int f0 = blockIdx.x * (DENOISE_POINTS >> lg);
@@ -168,7 +156,7 @@ __device__ __forceinline__ short dn_pcm(float v) { return (short)fminf(fmaxf(v *
 
 __global__ __launch_bounds__(256) void k_denoise_ola(const DenoiseArgs a) {
     const int b = blockIdx.y, N = a.n_fft;
-    const DenoiseRow r = dn_row(a, b);
+    const DenoiseRow r = a.rows[b];                          // (b is the same for every lane: the entry arrives through scalar loads)
     const int e = blockIdx.x * 256 + threadIdx.x;
     if (e >= dn_count(r)) return;
     const int i = r.off + e;                                 // the sample's index in the window

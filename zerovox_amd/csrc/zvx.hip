@@ -2111,18 +2111,43 @@ void rs_pair(int rate_in, int rate_out, int* L, int* M) {
         fail(ZVX_E_UNSUPPORTED, "resampling %d -> %d Hz needs L = %d, M = %d: the polyphase bank is built for max(L, M) <= %d", rate_in, rate_out, *L, *M, RS_MAX_PHASES);
 }
 long rs_out_len(long n, int L, int M) { return (n * L + M - 1) / M; }
+// The window of the post-processing steps: a row holds samples [in_origin, in_origin + n) of its signal, the outputs
+// [out_begin, out_begin + cnt) are emitted.  The whole-row calls are {0, 0, -1, 1}.  The denoiser and the limiter add a support condition
+// and `last` (the signal ends with the window); the resampler's rows are zero outside the window and `last` takes no part.
+struct RowsWindow { int64_t in_origin = 0, out_begin = 0, out_count = -1; int last = 1; };
+// One row of a post-processing step: n samples at `in` on the device, the window they are of their signal, the emitted count, and where
+// emitted sample 0 goes.  Rows of one call may lie in unrelated buffers.
+struct PostRow { const float* in; void* out; int32_t n; RowsWindow w; int32_t cnt; };
+// The windows of a call after its checks, per row (B entries) or ONE for every row, and per row the emitted count
+struct RowsWindows {
+    std::vector<RowsWindow> w; std::vector<int32_t> cnt; long cnt_max = 0;
+    const RowsWindow& at(int b) const { return w[w.size() == 1 ? 0 : (size_t)b]; }
+};
+// the strided rows of a public call as PostRows
+std::vector<PostRow> post_rows(const float* x, long x_bs, void* out, long out_bs, size_t ss, const int32_t* nsamples, const RowsWindows& rw, int B) {
+    std::vector<PostRow> rows((size_t)B);
+    for (int b = 0; b < B; b++)
+        rows[(size_t)b] = PostRow{x + (size_t)b * x_bs, (char*)out + (size_t)b * out_bs * ss, nsamples[b], rw.at(b), rw.cnt[(size_t)b]};
+    return rows;
+}
 // Every row converted as a signal of its own length len[b] * mul, held from sample in_origin on and zero elsewhere: per row the outputs
-// [out_begin, out_begin + cnt[b]) (out_count -1: to the end of the row's signal), the longest of them, and the samples read and written.
-struct RsPlan { long in_origin = 0, out_begin = 0, out_count = -1, out_max = 0; std::vector<long> cnt; double nin = 0, nout = 0; };
+// [out_begin, out_begin + cnt[b]) (out_count -1: to the end of the row's signal), and the longest of them.
+struct RsPlan { RowsWindow w; long out_max = 0; std::vector<long> cnt; };
 RsPlan rs_plan(const int* len, int mul, int B, int L, int M, long in_origin = 0, long out_begin = 0, long out_count = -1) {
     RsPlan p;
-    p.in_origin = in_origin; p.out_begin = out_begin; p.out_count = out_count; p.cnt.resize(B);
+    p.w = RowsWindow{in_origin, out_begin, out_count, 1}; p.cnt.resize(B);
     for (int b = 0; b < B; b++) {
-        const long n = (long)len[b] * mul;
-        p.cnt[b] = out_count >= 0 ? out_count : std::max(0L, rs_out_len(in_origin + n, L, M) - out_begin);
-        p.out_max = std::max(p.out_max, p.cnt[b]); p.nin += (double)n; p.nout += (double)p.cnt[b];
+        p.cnt[b] = out_count >= 0 ? out_count : std::max(0L, rs_out_len(in_origin + (long)len[b] * mul, L, M) - out_begin);
+        p.out_max = std::max(p.out_max, p.cnt[b]);
     }
     return p;
+}
+// the strided rows of such a call as PostRows (the caller has checked that the counts fit an int32)
+std::vector<PostRow> plan_rows(const RsPlan& p, const float* x, long x_bs, void* out, long out_bs, size_t ss, const int* len, int mul, int B) {
+    std::vector<PostRow> rows((size_t)B);
+    for (int b = 0; b < B; b++)
+        rows[(size_t)b] = PostRow{x + (size_t)b * x_bs, (char*)out + (size_t)b * out_bs * ss, len[b] * mul, p.w, (int32_t)p.cnt[(size_t)b]};
+    return rows;
 }
 
 double bessel_i0(double x) {
@@ -2194,16 +2219,33 @@ const zvx_ctx::RsBank& rs_bank(zvx_ctx* c, int L, int M) {
     return c->rs_banks[{L, M}] = bk;
 }
 
-// The one resampling launch: stage tag "voc.resample", slot ZVX_T_RESAMPLE, algorithmic bytes = samples read + samples written.
-void run_resample(zvx_ctx* c, const zvx_ctx::RsBank& bk, const float* x_dev, long x_bs, const int* in_len_d, int in_mul, int B, void* out_dev,
-                  long out_bs, int pcm16, const RsPlan& p) {
-    if (p.out_max <= 0) return;
+// The rate conversion over B rows with a window each, every caller's one resampling launch: ONE table upload, one launch, one timed group;
+// stage tag "voc.resample", slot ZVX_T_RESAMPLE.  A row's window is the resampler's own contract -- zero outside the row's samples, no
+// support condition; `last` takes no part.  Zeros follow a row's outputs up to `zero_to` (-1: the row's own cnt, nothing outside [0, cnt) is
+// written; the calls with one window for all rows pass the longest row).  Algorithmic bytes = samples read + samples written, a row's
+// input counted when it has outputs or zeros to write (a row that writes nothing counts nothing; a call that writes nothing launches
+// nothing).  The caller has validated the rows.
+void run_resample_rows(zvx_ctx* c, const zvx_ctx::RsBank& bk, const PostRow* rows, int B, int pcm16, long zero_to = -1) {
+    std::vector<ResampleRow> tab((size_t)B);
+    double nin = 0, nout = 0;
+    long zend_max = 0;
+    for (int b = 0; b < B; b++) {
+        const PostRow& r = rows[b];
+        ResampleRow& t = tab[(size_t)b];
+        t.x = r.in; t.out = r.out; t.n = r.n;
+        t.in_origin = (long)r.w.in_origin; t.out_begin = (long)r.w.out_begin; t.cnt = r.cnt; t.zend = zero_to < 0 ? r.cnt : zero_to;
+        zend_max = std::max(zend_max, t.zend);
+        if (t.zend > 0) { nin += (double)r.n; nout += (double)r.cnt; }
+    }
+    if (zend_max <= 0) return;
     ResampleArgs a{};
-    a.x = x_dev; a.x_bs = x_bs; a.in_len = in_len_d; a.in_mul = in_mul; a.out = out_dev; a.out_bs = out_bs; a.pcm16 = pcm16;
-    a.B = B; a.L = bk.L; a.M = bk.M; a.half = bk.half; a.T = bk.T; a.pitch = bk.pitch; a.bank = bk.dev;
-    a.in_origin = p.in_origin; a.out_begin = p.out_begin; a.out_count = p.out_count; a.out_max = p.out_max;
+    a.B = B; a.pcm16 = pcm16; a.L = bk.L; a.M = bk.M; a.half = bk.half; a.T = bk.T; a.pitch = bk.pitch; a.bank = bk.dev;
+    a.out_max = zend_max;                                    // the grid; every row's own bound is its zend
+    ResampleRow* tab_d = (ResampleRow*)c->buf("rs.rows", (size_t)B * sizeof(ResampleRow));
+    c->upload(tab_d, tab.data(), (size_t)B * sizeof(ResampleRow));
+    a.rows = tab_d;
     TagScope scope(c, "voc.resample", ZVX_T_RESAMPLE);
-    c->timed(2.0 * p.nout * bk.T, p.nin * 4.0 + p.nout * (pcm16 ? 2.0 : 4.0), [&] {
+    c->timed(2.0 * nout * bk.T, nin * 4.0 + nout * (pcm16 ? 2.0 : 4.0), [&] {
         if (!launch_resample_poly(a, c->stream)) fail(ZVX_E_UNSUPPORTED, "resampler: L = %d, M = %d does not fit the LDS of a workgroup", bk.L, bk.M);
     });
     scope.close();
@@ -2233,10 +2275,10 @@ void do_resample(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, in
     const zvx_ctx::RsBank& bk = rs_bank(c, L, M);
     const int pcm16 = (flags & ZVX_PCM16) ? 1 : 0;
     const size_t ss = pcm16 ? 2 : 4;
-    const DevRows rows = stage_rows(c, "rs", in, nsamples, B, Nmax, flags);
+    const float* x = rows_to_device(c, "rs", in, B, Nmax, flags);
     void* odev = out; long ostride = out_stride;
     if (!(flags & ZVX_DEVICE_OUT)) { ostride = (std::max(out_max, 1L) + 7) & ~7L; odev = c->buf("rs.out", (size_t)B * ostride * ss); }
-    run_resample(c, bk, rows.x, Nmax, rows.len, 1, B, odev, ostride, pcm16, plan);
+    run_resample_rows(c, bk, plan_rows(plan, x, Nmax, odev, ostride, ss, nsamples, 1, B).data(), B, pcm16, out_max);
     if (!(flags & ZVX_DEVICE_OUT) && out_max > 0)
         HIPCHK(hipMemcpy2DAsync(out, (size_t)out_stride * ss, odev, (size_t)ostride * ss, (size_t)out_max * ss, B, hipMemcpyDeviceToHost, c->stream));
     if (out_len) for (int b = 0; b < B; b++) out_len[b] = (int32_t)plan.cnt[b];
@@ -2390,10 +2432,9 @@ void do_spkemb_wav(zvx_ctx* c, const float* wav, const int32_t* nsamples, int B,
     long rows_bs = Nmax;
     if (rate != native) {
         const zvx_ctx::RsBank& bk = rs_bank(c, L, M);
-        const int* len_d = c->upload_ints("rs.len", nsamples, B);
         const long ostride = (std::max(plan.out_max, 1L) + 7) & ~7L;
         float* conv = c->fbuf("ref.rs", (size_t)B * ostride);
-        run_resample(c, bk, rows, rows_bs, len_d, 1, B, conv, ostride, 0, plan);
+        run_resample_rows(c, bk, plan_rows(plan, rows, rows_bs, conv, ostride, 4, nsamples, 1, B).data(), B, 0, plan.out_max);
         rows = conv; rows_bs = ostride;
     }
     // 2. the bounds, and the call's one wait
@@ -2525,15 +2566,10 @@ const double* limit_win(zvx_ctx* c, int W) {
     return c->lim_wins[W] = d;
 }
 
-// The window of zvx_limit_ex and zvx_denoise_ex: the rows hold samples [in_origin, in_origin + nsamples[b]) of their signals, the outputs
-// [out_begin, out_begin + cnt_b) are emitted.  The whole-row calls are {0, 0, -1, 1}.
-// (do_resample's window is another contract -- its rows are zero outside the window and it has no support condition -- and stays on its own;
-// its per-row form, do_resample_rows, carries the same three numbers per row and ignores `last`.)
-struct RowsWindow { int64_t in_origin = 0, out_begin = 0, out_count = -1; int last = 1; };
-// per row the emitted count, after the window's own checks and the support condition of include/zvx.h for the reach R (zvx_limit_ex:
-// 2 W + H; zvx_denoise_ex: n_fft - 1)
+// The window of the denoiser and the limiter (RowsWindow): the checks of its own numbers, then per row the emitted count after the support
+// condition of include/zvx.h for the reach R (the limiter: 2 W + H; the denoiser: n_fft - 1)
 // (`row` >= 0: the window is that row's own -- zvx_denoise_rows, zvx_limit_rows -- and every message names it)
-void window_args_check(const char* who, const RowsWindow& w, int row = -1) {
+void window_args_check(const char* who, const RowsWindow& w, int row) {
     char at[32] = "";
     if (row >= 0) snprintf(at, sizeof at, "row %d: ", row);
     if (w.in_origin < 0 || w.out_begin < 0) fail(ZVX_E_INVALID, "%s: %sin_origin %lld / out_begin %lld is negative", who, at, (long long)w.in_origin, (long long)w.out_begin);
@@ -2558,25 +2594,36 @@ int32_t window_count_row(const char* who, const RowsWindow& w, int32_t nsamples,
     }
     return (int32_t)n;                                       // n <= nsamples where n > 0
 }
-std::vector<int32_t> window_counts(const char* who, const RowsWindow& w, const int32_t* nsamples, int B, int64_t R) {
-    window_args_check(who, w);
-    std::vector<int32_t> cnt(B);
-    for (int b = 0; b < B; b++) cnt[b] = window_count_row(who, w, nsamples[b], b, R);
-    return cnt;
-}
-// the emitted range: [off, off + cnt[b]) of row b.  Without a window the whole rows; with one, window_counts for the reach R, then the checks
-// of the output stride and of the in-place form.  `own` holds cnt under a window.
-struct EmittedRange { std::vector<int32_t> own; const int32_t* cnt; long off, cnt_max; double cnt_sum; };
-EmittedRange emitted_range(const char* who, const RowsWindow* win, const int32_t* nsamples, int B, int64_t R, const RowsInfo& r, const float* in,
-                           const void* out, int64_t out_stride) {
-    if (!win) return {{}, nsamples, 0, r.n_max, r.n_sum};
-    EmittedRange e{window_counts(who, *win, nsamples, B, R), nullptr, (long)(win->out_begin - win->in_origin), 0, 0};
-    e.cnt = e.own.data();                                    // (the vector's storage moves with the struct)
-    for (int b = 0; b < B; b++) { e.cnt_max = std::max<long>(e.cnt_max, e.cnt[b]); e.cnt_sum += e.cnt[b]; }
-    if (e.cnt_max == 0) e.off = 0;
-    if (out_stride < e.cnt_max) fail(ZVX_E_INVALID, "%s: out_stride %lld is smaller than the longest output row %ld", who, (long long)out_stride, e.cnt_max);
-    if (out == (const void*)in && e.off != 0) fail(ZVX_E_INVALID, "%s: in place needs out_begin == in_origin", who);
-    return e;
+// The three ways a window reaches the denoiser and the limiter: none (the whole rows), ONE for the call (_ex), one per row (_rows)
+struct WindowsIn { enum Form { WHOLE, ONE, PER_ROW } form = WHOLE; RowsWindow one; const zvx_row_window* rows = nullptr; };
+// What those calls check of their windows, all before anything is queued -> the windows and per row the emitted count.  A call-wide window
+// is checked once and reported without a row number; the whole rows are their own window and out_rows_check has covered their stride.
+RowsWindows rows_windows_check(const char* who, const WindowsIn& win, const int32_t* nsamples, int B, int64_t R, const float* in, const void* out,
+                               int64_t out_stride) {
+    const bool per_row = win.form == WindowsIn::PER_ROW;
+    if (per_row && !win.rows) fail(ZVX_E_INVALID, "%s: win is NULL", who);
+    RowsWindows rw;
+    rw.w.assign(per_row ? (size_t)B : 1, win.one); rw.cnt.resize((size_t)B);
+    if (!per_row) window_args_check(who, win.one, -1);
+    for (int b = 0; b < B; b++) {
+        if (per_row) {
+            if (win.rows[b].reserved != 0) fail(ZVX_E_INVALID, "%s: row %d: reserved is %d (must be 0)", who, b, win.rows[b].reserved);
+            rw.w[(size_t)b] = RowsWindow{win.rows[b].in_origin, win.rows[b].out_begin, win.rows[b].out_count, win.rows[b].last};
+            window_args_check(who, rw.w[(size_t)b], b);
+        }
+        rw.cnt[(size_t)b] = window_count_row(who, rw.at(b), nsamples[b], b, R);
+        rw.cnt_max = std::max<long>(rw.cnt_max, rw.cnt[(size_t)b]);
+    }
+    if (win.form == WindowsIn::WHOLE) return rw;
+    if (out_stride < rw.cnt_max) fail(ZVX_E_INVALID, "%s: out_stride %lld is smaller than the longest output row %ld", who, (long long)out_stride, rw.cnt_max);
+    if (out == (const void*)in)
+        for (int b = 0; b < B; b++) {
+            const RowsWindow& w = rw.at(b);
+            if (rw.cnt[(size_t)b] <= 0 || w.out_begin == w.in_origin) continue;
+            if (!per_row) fail(ZVX_E_INVALID, "%s: in place needs out_begin == in_origin", who);
+            fail(ZVX_E_INVALID, "%s: row %d: in place needs out_begin == in_origin (%lld, %lld)", who, b, (long long)w.out_begin, (long long)w.in_origin);
+        }
+    return rw;
 }
 
 // the checks of the limiter's own parameters (zvx_limit, zvx_limit_ex, zvx_stream_open) -> W
@@ -2591,48 +2638,75 @@ int limit_params_check(const char* who, int rate, const zvx_limit_params* p) {
     return (int)w;
 }
 
-// zvx_true_peak (p == nullptr: the envelope's maximum only, results in tpeak), zvx_limit and zvx_limit_ex (win != nullptr)
+// The limiter over B rows with a window each, every caller's launches: ONE table upload, the envelope, gain and reduce launches under one
+// timed group -> the device words res[b] = peak, res[B + b] = min gain.  p == nullptr: measure only (zvx_true_peak) at oversampling
+// `measure_os` -- no gain launch, no envelope stored, res[B + b] = 1.  The caller has validated the rows.
+const float* run_limit_rows(zvx_ctx* c, const char* who, const PostRow* rows, int B, const zvx_limit_params* p, int W, int pcm16, int measure_os = 0) {
+    const bool lim = p != nullptr;
+    LimitArgs a{};
+    a.os = lim ? p->oversample : measure_os;
+    if (a.os > 1) {
+        const zvx_ctx::RsBank& bk = rs_bank(c, a.os, 1);
+        if (bk.T != 21 || bk.half != 10 * a.os) fail(ZVX_E_STATE, "%s: the (%d, 1) bank has %d taps per output", who, a.os, bk.T);
+        a.T = bk.T; a.pitch = bk.pitch; a.bank = bk.dev;
+    }
+    if (lim) { a.c = p->ceiling; a.W = W; a.win = limit_win(c, W); }
+    std::vector<LimitRow> tab((size_t)B);
+    double n_sum = 0, cnt_sum = 0;
+    long n_max = 0, cnt_max = 0;
+    size_t env_floats = 0;
+    for (int b = 0; b < B; b++) {
+        const PostRow& r = rows[b];
+        n_max = std::max<long>(n_max, r.n); cnt_max = std::max<long>(cnt_max, r.cnt);
+        n_sum += r.n; cnt_sum += r.cnt; env_floats += (size_t)r.n;
+    }
+    float* env = lim ? c->fbuf("lim.env", std::max<size_t>(env_floats, 1)) : nullptr;
+    for (int b = 0; b < B; b++) {
+        const PostRow& r = rows[b];
+        LimitRow& t = tab[(size_t)b];
+        t.x = r.in; t.out = r.out; t.env = env;
+        t.n = r.n; t.off = r.cnt > 0 ? (int)(r.w.out_begin - r.w.in_origin) : 0; t.cnt = r.cnt; t.pad_ = 0;
+        if (env) env += r.n;
+    }
+    a.B = B; a.pcm16 = pcm16;
+    a.ppitch = (int)std::max(1L, (n_max + LIMIT_TILE - 1) / LIMIT_TILE);
+    a.gtiles = (int)std::max(1L, (cnt_max + LIMIT_TILE - 1) / LIMIT_TILE);                // <= ppitch: cnt <= n in every row
+    a.part_max = c->fbuf("lim.part", (size_t)2 * B * a.ppitch);
+    a.part_min = lim ? a.part_max + (size_t)B * a.ppitch : nullptr;
+    a.res = c->fbuf("lim.res", (size_t)2 * B);
+    LimitRow* tab_d = (LimitRow*)c->buf("lim.rows", (size_t)B * sizeof(LimitRow));
+    c->upload(tab_d, tab.data(), (size_t)B * sizeof(LimitRow));
+    a.rows = tab_d;
+    TagScope scope(c, "post.limit");
+    c->timed(0.0, 4.0 * n_sum + (lim ? (pcm16 ? 2.0 : 4.0) * cnt_sum : 0.0), [&] {
+        launch_limit_env(a, c->stream);
+        if (lim && !launch_limit_gain(a, c->stream)) fail(ZVX_E_UNSUPPORTED, "%s: a window of %d samples does not fit the LDS of a workgroup", who, W);
+        launch_limit_reduce(a, c->stream);
+    });
+    return a.res;
+}
+
+// zvx_true_peak (p == nullptr: the envelope's maximum only, results in peak_in), zvx_limit, zvx_limit_ex and zvx_limit_rows: every check before
+// anything is allocated, uploaded or queued
 void do_limit(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_limit_params* p,
-              int oversample, void* out, int64_t out_stride, float* peak_in, float* min_gain, int flags, const RowsWindow* win = nullptr) {
+              int oversample, void* out, int64_t out_stride, float* peak_in, float* min_gain, int flags, const WindowsIn& win = {}) {
     const bool lim = p != nullptr;
     if (!lim && !peak_in) fail(ZVX_E_INVALID, "%s: tpeak is NULL", who);
-    const RowsInfo r = rows_check(who, in, nsamples, B, Nmax, 65535);
+    rows_check(who, in, nsamples, B, Nmax, 65535);
     if (rate < 4000 || rate > 192000) fail(ZVX_E_INVALID, "%s: rate %d outside [4000, 192000]", who, rate);
     flags_check(who, flags, lim ? (ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16) : ZVX_DEVICE_IN);
     const int os = lim ? p->oversample : oversample;
     limit_os_check(who, os);
     if (lim) out_rows_check(who, in, out, out_stride, Nmax, flags);
     const int W = lim ? limit_params_check(who, rate, p) : 0;
-    const EmittedRange er = emitted_range(who, win, nsamples, B, 2 * (int64_t)W + (os > 1 ? LIMIT_ENV_REACH : 0), r, in, out, out_stride);
-    const int32_t* cnt = er.cnt;
-    const long off = er.off, cnt_max = er.cnt_max; const double cnt_sum = er.cnt_sum;
-    RowsReturn ret(c, B, (size_t)B * 8, peak_in || min_gain, lim, cnt_max, flags);      // words: peak [B], then min gain [B]
-    LimitArgs a{};
-    a.os = os;
-    if (os > 1) {
-        const zvx_ctx::RsBank& bk = rs_bank(c, os, 1);
-        if (bk.T != 21 || bk.half != 10 * os) fail(ZVX_E_STATE, "%s: the (%d, 1) bank has %d taps per output", who, os, bk.T);
-        a.T = bk.T; a.pitch = bk.pitch; a.bank = bk.dev;
-    }
-    if (lim) { a.c = p->ceiling; a.W = W; a.win = limit_win(c, W); }
-    const DevRows rows = stage_rows(c, "lim", in, nsamples, B, Nmax, flags);
-    a.x = rows.x; a.x_bs = Nmax; a.nsamples = rows.len; a.B = B;
-    a.ppitch = (int)std::max(1L, (r.n_max + LIMIT_TILE - 1) / LIMIT_TILE);
-    a.off = (int)off; a.cnt = win ? c->upload_ints("lim.cnt", cnt, B) : rows.len;
-    a.gtiles = (int)std::max(1L, (cnt_max + LIMIT_TILE - 1) / LIMIT_TILE);                // <= ppitch: cnt[b] <= nsamples[b]
-    a.e_bs = std::max(r.n_max, 1L);
-    a.env = lim ? c->fbuf("lim.env", (size_t)B * a.e_bs) : nullptr;
-    a.part_max = c->fbuf("lim.part", (size_t)2 * B * a.ppitch);
-    a.part_min = lim ? a.part_max + (size_t)B * a.ppitch : nullptr;
-    a.res = c->fbuf("lim.res", (size_t)2 * B);
-    a.out = ret.out_rows("lim.out", out, out_stride, &a.out_bs); a.pcm16 = (flags & ZVX_PCM16) ? 1 : 0;
-    TagScope scope(c, "post.limit");
-    c->timed(0.0, 4.0 * r.n_sum + (lim ? (double)ret.ss * cnt_sum : 0.0), [&] {
-        launch_limit_env(a, c->stream);
-        if (lim && !launch_limit_gain(a, c->stream)) fail(ZVX_E_UNSUPPORTED, "%s: a window of %d samples does not fit the LDS of a workgroup", who, W);
-        launch_limit_reduce(a, c->stream);
-    });
-    const float* r_h = (const float*)ret.finish(a.res, out, out_stride, cnt, flags);
+    const RowsWindows rw = rows_windows_check(who, win, nsamples, B, 2 * (int64_t)W + (os > 1 ? LIMIT_ENV_REACH : 0), in, out, out_stride);
+    RowsReturn ret(c, B, (size_t)B * 8, peak_in || min_gain, lim, rw.cnt_max, flags);      // words: peak [B], then min gain [B]
+    const float* x = rows_to_device(c, "lim", in, B, Nmax, flags);
+    long out_bs = 0;
+    void* od = ret.out_rows("lim.out", out, out_stride, &out_bs);
+    const std::vector<PostRow> rows = post_rows(x, Nmax, od, out_bs, ret.ss, nsamples, rw, B);
+    const float* res = run_limit_rows(c, who, rows.data(), B, p, W, (flags & ZVX_PCM16) ? 1 : 0, os);
+    const float* r_h = (const float*)ret.finish(res, out, out_stride, rw.cnt.data(), flags);
     if (!r_h) return;
     for (int b = 0; b < B; b++) {
         if (peak_in) peak_in[b] = r_h[b];
@@ -2691,7 +2765,6 @@ const zvx_ctx::DnTables& dn_tables(zvx_ctx* c, const DnGeom& g) {
 void dn_fill(DenoiseArgs& a, const DnGeom& g, const zvx_ctx::DnTables& tb) {
     a.n_fft = g.n_fft; a.log2n = g.log2n; a.hop = g.hop; a.pad = g.pad;
     a.twid = tb.twid; a.win = tb.win; a.win2 = tb.win2; a.den_min = tb.den_min;
-    a.origin = 0; a.f_first = 0; a.skip = 0; a.rel = -g.pad; a.left = a.right = 1; a.off = 0; a.cnt = -1;      // the whole rows
 }
 double dn_fft_flops(const DnGeom& g, double frames, int transforms) { return transforms * frames * 5.0 * g.n_fft * g.log2n; }
 
@@ -2705,75 +2778,12 @@ DnGeom denoise_params_check(const zvx_ctx* c, const char* who, const float* bias
     return g;
 }
 
-// zvx_denoise (win == nullptr: the whole rows) and zvx_denoise_ex
-void do_denoise(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias, const zvx_denoise_params* p,
-                void* out, int64_t out_stride, int flags, const RowsWindow* win = nullptr) {
-    const RowsInfo r = rows_check(who, in, nsamples, B, Nmax, 65535);
-    flags_check(who, flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16);
-    out_rows_check(who, in, out, out_stride, Nmax, flags);
-    const DnGeom g = denoise_params_check(c, who, bias, p);
-    const RowsWindow whole;
-    const RowsWindow& w = win ? *win : whole;
-    const EmittedRange er = emitted_range(who, win, nsamples, B, g.n_fft - 1, r, in, out, out_stride);
-    const int32_t* cnt = er.cnt;
-    const long off = er.off, cnt_max = er.cnt_max; const double cnt_sum = er.cnt_sum;
-    // zvx_melspec's length conditions hold for the whole SIGNAL: known where it ends with the window
-    if (w.last)
-        for (int b = 0; b < B; b++)
-            if (nsamples[b] > 0 && w.in_origin + nsamples[b] < dn_min_samples(g))
-                fail(ZVX_E_INVALID, "%s: row %d has %lld samples; a row that is not empty needs at least %d (zvx_melspec's conditions)", who, b,
-                     (long long)(w.in_origin + nsamples[b]), dn_min_samples(g));
-    // the frames transformed: from the first one that covers sample out_begin (the same for every row) to the last one that begins at or
-    // before a row's last emitted sample, on the signal's grid.  The kernels count frames from f_first, that first frame rounded DOWN to
-    // a multiple of the frames per workgroup: every frame then sits in the slot of its workgroup it has in the whole-row call and runs
-    // through the same instructions (the unrolled copies of a pass need not contract their multiply-adds alike), which is what makes the
-    // bits equal.  The `skip` frames in front are neither loaded nor stored.  (spectral.hip, dn_frames_used)
-    const int per = DENOISE_POINTS >> g.log2n;
-    const int64_t p0 = w.out_begin + g.pad;
-    const int64_t f_need = cnt_max > 0 && p0 >= g.n_fft ? (p0 - g.n_fft) / g.hop + 1 : 0;
-    const int64_t f_first = f_need - f_need % per;
-    // where frame f_first begins, as an index into the window: in (off - n_fft - per hop, off + hop - n_fft], an int
-    const int64_t rel = cnt_max > 0 ? f_first * g.hop - g.pad - w.in_origin : -(int64_t)g.pad;
-    double frames = 0; long Fmax = 0;
-    for (int b = 0; b < B; b++) {
-        if (cnt[b] <= 0) continue;
-        int64_t F = (off + cnt[b] - 1 - rel) / g.hop + 1;
-        if (w.last) F = std::min<int64_t>(F, std::max<int64_t>(0, dn_frames(g, w.in_origin + nsamples[b]) - f_first));
-        frames += (double)std::max<int64_t>(0, F - (f_need - f_first)); Fmax = std::max<long>(Fmax, (long)F);
-    }
-    RowsReturn ret(c, B, 0, false, true, cnt_max, flags);
-    DenoiseArgs a{};
-    a.copy = p->strength == 0.f;                             // a copy: the input's bits, nothing is transformed
-    if (!a.copy) {
-        dn_fill(a, g, dn_tables(c, g));
-        float* bias_d = c->fbuf("dn.bias", g.nf);
-        c->upload(bias_d, bias, (size_t)g.nf * 4);
-        a.bias = bias_d; a.strength = p->strength; a.floor = p->floor;
-        a.work = c->fbuf("dn.work", (size_t)B * Fmax * g.n_fft);
-    } else { a.n_fft = g.n_fft; a.log2n = g.log2n; a.hop = g.hop; a.pad = g.pad; }
-    a.Fmax = (int)Fmax;
-    a.origin = (long)w.in_origin; a.f_first = (long)f_first; a.skip = (int)(f_need - f_first); a.rel = (int)rel; a.left = w.in_origin == 0; a.right = w.last;
-    a.off = (int)off; a.cnt = (int)w.out_count;
-    const DevRows rows = stage_rows(c, "dn", in, nsamples, B, Nmax, flags);
-    a.x = rows.x; a.x_bs = Nmax; a.nsamples = rows.len; a.B = B;
-    a.out = ret.out_rows("dn.out", out, out_stride, &a.out_bs); a.pcm16 = (flags & ZVX_PCM16) ? 1 : 0;
-    TagScope scope(c, "post.denoise");
-    c->timed(a.copy ? 0.0 : dn_fft_flops(g, frames, 2), 4.0 * r.n_sum + (double)ret.ss * cnt_sum, [&] {
-        if (!a.copy) launch_denoise_frames(a, c->stream);
-        launch_denoise_ola(a, cnt_max, c->stream);
-    });
-    ret.finish(nullptr, out, out_stride, cnt, flags);
-}
-
-// ------------------------------------------------------------------------------------------------
-// per-row windows (include/zvx.h: zvx_denoise_rows, zvx_limit_rows; the batched post stages of zvx_stream_next_many)
-// ------------------------------------------------------------------------------------------------
-// One row of the internal per-row forms: n samples at `in` on the device, the window they are of their signal, the emitted count (what
-// window_count_row gives), and where emitted sample 0 goes.  Rows of one call may lie in unrelated buffers.
-struct PostRow { const float* in; void* out; int32_t n; RowsWindow w; int32_t cnt; };
-
-// The denoiser over B rows with a window each: ONE table upload, ONE bias upload, the two launches of do_denoise under one timed group.  Per
-// row the quantities are the ones do_denoise forms for a call of that row alone (f_first rounded down per ROW: a frame keeps its slot).
+// The denoiser over B rows with a window each, every caller's launches: ONE table upload, ONE bias upload, the frames and overlap-add
+// launches under one timed group.  The frames transformed of a row: from the first one that covers sample out_begin to the last one that
+// begins at or before the row's last emitted sample, on the signal's grid.  The kernels count frames from f_first, that first frame
+// rounded DOWN per ROW to a multiple of the frames per workgroup: every frame then sits in the slot of its workgroup it has in the
+// whole-row call and runs through the same instructions (the unrolled copies of a pass need not contract their multiply-adds alike), which
+// is what makes the bits equal.  The `skip` frames in front are neither loaded nor stored.  (spectral.hip, dn_frames_used)
 // The caller has validated the rows.
 void run_denoise_rows(zvx_ctx* c, const DnGeom& g, const PostRow* rows, int B, const float* bias, const zvx_denoise_params* p, int pcm16) {
     const int per = DENOISE_POINTS >> g.log2n;
@@ -2791,6 +2801,7 @@ void run_denoise_rows(zvx_ctx* c, const DnGeom& g, const PostRow* rows, int B, c
         const int64_t p0 = w.out_begin + g.pad;
         const int64_t f_need = any && p0 >= g.n_fft ? (p0 - g.n_fft) / g.hop + 1 : 0;
         const int64_t f_first = f_need - f_need % per;
+        // where frame f_first begins, as an index into the window: in (off - n_fft - per hop, off + hop - n_fft], an int
         const int64_t rel = any ? f_first * g.hop - g.pad - w.in_origin : -(int64_t)g.pad;
         int64_t F = 0;
         if (any) {
@@ -2809,14 +2820,14 @@ void run_denoise_rows(zvx_ctx* c, const DnGeom& g, const PostRow* rows, int B, c
         n_sum += r.n; cnt_sum += r.cnt;
     }
     DenoiseArgs a{};
-    a.copy = copy;
+    a.copy = copy;                                           // a copy: the input's bits, nothing is transformed
     if (!copy) {
         dn_fill(a, g, dn_tables(c, g));
         float* bias_d = c->fbuf("dn.bias", g.nf);
         c->upload(bias_d, bias, (size_t)g.nf * 4);
         a.bias = bias_d; a.strength = p->strength; a.floor = p->floor;
-        a.work = c->fbuf("dn.work", std::max<size_t>(work_floats, 1));
-        for (int b = 0; b < B; b++) tab[(size_t)b].work = a.work + work_at[(size_t)b];
+        float* work = c->fbuf("dn.work", std::max<size_t>(work_floats, 1));
+        for (int b = 0; b < B; b++) tab[(size_t)b].work = work + work_at[(size_t)b];
     } else { a.n_fft = g.n_fft; a.log2n = g.log2n; a.hop = g.hop; a.pad = g.pad; }
     a.Fmax = (int)Fmax; a.B = B; a.pcm16 = pcm16;
     DenoiseRow* tab_d = (DenoiseRow*)c->buf("dn.rows", (size_t)B * sizeof(DenoiseRow));
@@ -2829,93 +2840,18 @@ void run_denoise_rows(zvx_ctx* c, const DnGeom& g, const PostRow* rows, int B, c
     });
 }
 
-// The limiter likewise: the three launches of do_limit under one timed group -> the device words res[b] = peak, res[B + b] = min gain.
-const float* run_limit_rows(zvx_ctx* c, const char* who, const PostRow* rows, int B, const zvx_limit_params* p, int W, int pcm16) {
-    LimitArgs a{};
-    a.os = p->oversample;
-    if (a.os > 1) {
-        const zvx_ctx::RsBank& bk = rs_bank(c, a.os, 1);
-        if (bk.T != 21 || bk.half != 10 * a.os) fail(ZVX_E_STATE, "%s: the (%d, 1) bank has %d taps per output", who, a.os, bk.T);
-        a.T = bk.T; a.pitch = bk.pitch; a.bank = bk.dev;
-    }
-    a.c = p->ceiling; a.W = W; a.win = limit_win(c, W);
-    std::vector<LimitRow> tab((size_t)B);
-    std::vector<size_t> env_at((size_t)B);
-    double n_sum = 0, cnt_sum = 0;
-    long n_max = 0, cnt_max = 0;
-    size_t env_floats = 0;
-    for (int b = 0; b < B; b++) {
-        const PostRow& r = rows[b];
-        LimitRow& t = tab[(size_t)b];
-        t.x = r.in; t.out = r.out; t.env = nullptr;
-        t.n = r.n; t.off = r.cnt > 0 ? (int)(r.w.out_begin - r.w.in_origin) : 0; t.cnt = r.cnt; t.pad_ = 0;
-        env_at[(size_t)b] = env_floats; env_floats += (size_t)r.n;
-        n_max = std::max<long>(n_max, r.n); cnt_max = std::max<long>(cnt_max, r.cnt);
-        n_sum += r.n; cnt_sum += r.cnt;
-    }
-    a.B = B; a.pcm16 = pcm16;
-    a.ppitch = (int)std::max(1L, (n_max + LIMIT_TILE - 1) / LIMIT_TILE);
-    a.gtiles = (int)std::max(1L, (cnt_max + LIMIT_TILE - 1) / LIMIT_TILE);                // <= ppitch: cnt <= n in every row
-    float* env = c->fbuf("lim.env", std::max<size_t>(env_floats, 1));
-    for (int b = 0; b < B; b++) tab[(size_t)b].env = env + env_at[(size_t)b];
-    a.part_max = c->fbuf("lim.part", (size_t)2 * B * a.ppitch);
-    a.part_min = a.part_max + (size_t)B * a.ppitch;
-    a.res = c->fbuf("lim.res", (size_t)2 * B);
-    LimitRow* tab_d = (LimitRow*)c->buf("lim.rows", (size_t)B * sizeof(LimitRow));
-    c->upload(tab_d, tab.data(), (size_t)B * sizeof(LimitRow));
-    a.rows = tab_d;
-    TagScope scope(c, "post.limit");
-    c->timed(0.0, 4.0 * n_sum + (pcm16 ? 2.0 : 4.0) * cnt_sum, [&] {
-        launch_limit_env(a, c->stream);
-        if (!launch_limit_gain(a, c->stream)) fail(ZVX_E_UNSUPPORTED, "%s: a window of %d samples does not fit the LDS of a workgroup", who, W);
-        launch_limit_reduce(a, c->stream);
-    });
-    return a.res;
-}
-
-// What zvx_denoise_rows and zvx_limit_rows check of their windows, all before anything is queued -> per row the emitted count
-struct RowsWindows { std::vector<RowsWindow> w; std::vector<int32_t> cnt; long cnt_max = 0; };
-RowsWindows rows_windows_check(const char* who, const zvx_row_window* win, const int32_t* nsamples, int B, int64_t R, const float* in, const void* out,
-                               int64_t out_stride) {
-    if (!win) fail(ZVX_E_INVALID, "%s: win is NULL", who);
-    RowsWindows rw;
-    rw.w.resize((size_t)B); rw.cnt.resize((size_t)B);
-    for (int b = 0; b < B; b++) {
-        if (win[b].reserved != 0) fail(ZVX_E_INVALID, "%s: row %d: reserved is %d (must be 0)", who, b, win[b].reserved);
-        RowsWindow& w = rw.w[(size_t)b];
-        w.in_origin = win[b].in_origin; w.out_begin = win[b].out_begin; w.out_count = win[b].out_count; w.last = win[b].last;
-        window_args_check(who, w, b);
-        rw.cnt[(size_t)b] = window_count_row(who, w, nsamples[b], b, R);
-        rw.cnt_max = std::max<long>(rw.cnt_max, rw.cnt[(size_t)b]);
-    }
-    if (out_stride < rw.cnt_max) fail(ZVX_E_INVALID, "%s: out_stride %lld is smaller than the longest output row %ld", who, (long long)out_stride, rw.cnt_max);
-    if (out == (const void*)in)
-        for (int b = 0; b < B; b++)
-            if (rw.cnt[(size_t)b] > 0 && rw.w[(size_t)b].out_begin != rw.w[(size_t)b].in_origin)
-                fail(ZVX_E_INVALID, "%s: row %d: in place needs out_begin == in_origin (%lld, %lld)", who, b, (long long)rw.w[(size_t)b].out_begin,
-                     (long long)rw.w[(size_t)b].in_origin);
-    return rw;
-}
-// the strided rows of a public call as PostRows
-std::vector<PostRow> post_rows(const float* x, long x_bs, void* out, long out_bs, size_t ss, const int32_t* nsamples, const RowsWindows& rw, int B) {
-    std::vector<PostRow> rows((size_t)B);
-    for (int b = 0; b < B; b++)
-        rows[(size_t)b] = PostRow{x + (size_t)b * x_bs, (char*)out + (size_t)b * out_bs * ss, nsamples[b], rw.w[(size_t)b], rw.cnt[(size_t)b]};
-    return rows;
-}
-
-void do_denoise_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias, const zvx_denoise_params* p, void* out,
-                     int64_t out_stride, int flags, const zvx_row_window* win) {
-    const char* who = "zvx_denoise_rows";
+// zvx_denoise, zvx_denoise_ex and zvx_denoise_rows: every check before anything is allocated, uploaded or queued
+void do_denoise(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias, const zvx_denoise_params* p,
+                void* out, int64_t out_stride, int flags, const WindowsIn& win = {}) {
     rows_check(who, in, nsamples, B, Nmax, 65535);
     flags_check(who, flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16);
     out_rows_check(who, in, out, out_stride, Nmax, flags);
     const DnGeom g = denoise_params_check(c, who, bias, p);
     const RowsWindows rw = rows_windows_check(who, win, nsamples, B, g.n_fft - 1, in, out, out_stride);
     for (int b = 0; b < B; b++)                              // zvx_melspec's length conditions hold for the whole SIGNAL: known where it ends with the window
-        if (rw.w[(size_t)b].last && nsamples[b] > 0 && rw.w[(size_t)b].in_origin + nsamples[b] < dn_min_samples(g))
+        if (rw.at(b).last && nsamples[b] > 0 && rw.at(b).in_origin + nsamples[b] < dn_min_samples(g))
             fail(ZVX_E_INVALID, "%s: row %d has %lld samples; a row that is not empty needs at least %d (zvx_melspec's conditions)", who, b,
-                 (long long)(rw.w[(size_t)b].in_origin + nsamples[b]), dn_min_samples(g));
+                 (long long)(rw.at(b).in_origin + nsamples[b]), dn_min_samples(g));
     RowsReturn ret(c, B, 0, false, true, rw.cnt_max, flags);
     const float* x = rows_to_device(c, "dn", in, B, Nmax, flags);
     long out_bs = 0;
@@ -2923,61 +2859,6 @@ void do_denoise_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B
     const std::vector<PostRow> rows = post_rows(x, Nmax, od, out_bs, ret.ss, nsamples, rw, B);
     run_denoise_rows(c, g, rows.data(), B, bias, p, (flags & ZVX_PCM16) ? 1 : 0);
     ret.finish(nullptr, out, out_stride, rw.cnt.data(), flags);
-}
-
-void do_limit_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_limit_params* p, void* out,
-                   int64_t out_stride, float* peak_in, float* min_gain, int flags, const zvx_row_window* win) {
-    const char* who = "zvx_limit_rows";
-    if (!p) fail(ZVX_E_INVALID, "%s: params is NULL", who);
-    rows_check(who, in, nsamples, B, Nmax, 65535);
-    if (rate < 4000 || rate > 192000) fail(ZVX_E_INVALID, "%s: rate %d outside [4000, 192000]", who, rate);
-    flags_check(who, flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16);
-    limit_os_check(who, p->oversample);
-    out_rows_check(who, in, out, out_stride, Nmax, flags);
-    const int W = limit_params_check(who, rate, p);
-    const RowsWindows rw = rows_windows_check(who, win, nsamples, B, 2 * (int64_t)W + (p->oversample > 1 ? LIMIT_ENV_REACH : 0), in, out, out_stride);
-    RowsReturn ret(c, B, (size_t)B * 8, peak_in || min_gain, true, rw.cnt_max, flags);      // words: peak [B], then min gain [B]
-    const float* x = rows_to_device(c, "lim", in, B, Nmax, flags);
-    long out_bs = 0;
-    void* od = ret.out_rows("lim.out", out, out_stride, &out_bs);
-    const std::vector<PostRow> rows = post_rows(x, Nmax, od, out_bs, ret.ss, nsamples, rw, B);
-    const float* res = run_limit_rows(c, who, rows.data(), B, p, W, (flags & ZVX_PCM16) ? 1 : 0);
-    const float* r_h = (const float*)ret.finish(res, out, out_stride, rw.cnt.data(), flags);
-    if (!r_h) return;
-    for (int b = 0; b < B; b++) {
-        if (peak_in) peak_in[b] = r_h[b];
-        if (min_gain) min_gain[b] = r_h[B + b];
-    }
-}
-
-// The rate conversion over B rows with a window each (zvx_resample_rows, the batched conversions of zvx_stream_next_many): ONE table upload,
-// the one launch of run_resample under one timed group.  A row's window is the resampler's own contract -- zero outside the row's samples, no
-// support condition; `last` takes no part -- and nothing outside [0, cnt) of its output is written.  Flops and bytes are what run_resample
-// counts for each row with cnt > 0 alone (a one-row call that emits nothing launches and counts nothing).  The caller has validated the rows.
-void run_resample_rows(zvx_ctx* c, const zvx_ctx::RsBank& bk, const PostRow* rows, int B, int pcm16) {
-    std::vector<ResampleRow> tab((size_t)B);
-    double nin = 0, nout = 0;
-    long cnt_max = 0;
-    for (int b = 0; b < B; b++) {
-        const PostRow& r = rows[b];
-        ResampleRow& t = tab[(size_t)b];
-        t.x = r.in; t.out = r.out; t.n = r.n;
-        t.in_origin = (long)r.w.in_origin; t.out_begin = (long)r.w.out_begin; t.cnt = r.cnt; t.zend = r.cnt;
-        cnt_max = std::max<long>(cnt_max, r.cnt);
-        if (r.cnt > 0) { nin += (double)r.n; nout += (double)r.cnt; }
-    }
-    if (cnt_max <= 0) return;
-    ResampleArgs a{};
-    a.B = B; a.pcm16 = pcm16; a.L = bk.L; a.M = bk.M; a.half = bk.half; a.T = bk.T; a.pitch = bk.pitch; a.bank = bk.dev;
-    a.out_max = cnt_max;                                     // the grid; every row's own bound is its zend
-    ResampleRow* tab_d = (ResampleRow*)c->buf("rs.rows", (size_t)B * sizeof(ResampleRow));
-    c->upload(tab_d, tab.data(), (size_t)B * sizeof(ResampleRow));
-    a.rows = tab_d;
-    TagScope scope(c, "voc.resample", ZVX_T_RESAMPLE);
-    c->timed(2.0 * nout * bk.T, nin * 4.0 + nout * (pcm16 ? 2.0 : 4.0), [&] {
-        if (!launch_resample_poly(a, c->stream)) fail(ZVX_E_UNSUPPORTED, "resampler: L = %d, M = %d does not fit the LDS of a workgroup", bk.L, bk.M);
-    });
-    scope.close();
 }
 
 // zvx_resample_rows: every check before anything is allocated, uploaded or queued
@@ -3037,7 +2918,11 @@ void do_denoise_bias(zvx_ctx* c, float* bias) {
     const int F = dn_frames(g, n);
     DenoiseArgs a{};
     dn_fill(a, g, tb);
-    a.x = wav; a.x_bs = n; a.nsamples = c->upload_ints("dn.len", &n, 1); a.B = 1; a.Fmax = F;
+    DenoiseRow row{};                                        // the whole row, magnitude-out mode: no output, no work buffer
+    row.x = wav; row.n = n; row.rel = -g.pad; row.cnt = n; row.mirrors = 3;
+    DenoiseRow* row_d = (DenoiseRow*)c->buf("dn.rows", sizeof(DenoiseRow));
+    c->upload(row_d, &row, sizeof(DenoiseRow));
+    a.rows = row_d; a.B = 1; a.Fmax = F;
     a.mag = c->fbuf("dn.mag", (size_t)F * g.nf);
     {
         TagScope scope(c, "post.denoise");
@@ -3114,8 +2999,7 @@ void do_vocode(zvx_ctx* c, const int32_t* pad_to, void* wav, int64_t wav_stride,
         float* native = c->fbuf("wav.native", (size_t)B * nstride);
         run_vocoder(c, c->fbuf("mel", 0), c->n_mels, c->Lmax, c->mel_len_host.data(), P.data(), B, native, nstride, 0);
         c->stage_end(ZVX_T_VOCODER);
-        // (the lengths on the device: the first B words of the vocoder's length table)
-        run_resample(c, *bank, native, nstride, c->ibuf("voc.lens", 0), c->hop, B, wdev, wstride, pcm16, plan);
+        run_resample_rows(c, *bank, plan_rows(plan, native, nstride, wdev, wstride, ss, c->mel_len_host.data(), c->hop, B).data(), B, pcm16, plan.out_max);
     } else {
         run_vocoder(c, c->fbuf("mel", 0), c->n_mels, c->Lmax, c->mel_len_host.data(), P.data(), B, wdev, wstride, pcm16);
         c->stage_end(ZVX_T_VOCODER);
@@ -3311,9 +3195,9 @@ void stream_run_stages(const char* who, zvx_stream* s, const StreamStep& p, floa
         if (sp.out_count > 0 && held > 0) {
             const int32_t n32 = (int32_t)held;
             const int64_t stride = std::max(held, sp.out_count);
-            const RowsWindow w{sp.in_origin, sp.out_begin, sp.out_count, last ? 1 : 0};
-            if (st.kind == zvx_stream::DENOISE) do_denoise(c, who, in, &n32, 1, n32, s->bias.data(), &s->dn, dst, stride, f, &w);
-            else if (st.kind == zvx_stream::LIMIT) do_limit(c, who, in, &n32, 1, n32, s->native, &s->lim, 0, dst, stride, nullptr, nullptr, f, &w);
+            const WindowsIn w{WindowsIn::ONE, RowsWindow{sp.in_origin, sp.out_begin, sp.out_count, last ? 1 : 0}};
+            if (st.kind == zvx_stream::DENOISE) do_denoise(c, who, in, &n32, 1, n32, s->bias.data(), &s->dn, dst, stride, f, w);
+            else if (st.kind == zvx_stream::LIMIT) do_limit(c, who, in, &n32, 1, n32, s->native, &s->lim, 0, dst, stride, nullptr, nullptr, f, w);
             else do_resample(c, in, &n32, 1, n32, s->native, s->out_rate, dst, stride, nullptr, f, sp.in_origin, sp.out_begin, sp.out_count);
         }
         const int64_t drop = sp.keep_from - sp.in_origin, keep = held - drop;
@@ -3919,8 +3803,8 @@ zvx_status zvx_limit_ex(zvx_ctx* c, const float* in, const int32_t* nsamples, in
                         int64_t in_origin, int64_t out_begin, int64_t out_count, int last) {
     return guarded(c, [&] {
         if (!params) fail(ZVX_E_INVALID, "zvx_limit_ex: params is NULL");
-        const RowsWindow win{in_origin, out_begin, out_count, last};
-        do_limit(c, "zvx_limit_ex", in, nsamples, B, Nmax, rate, params, 0, out, out_stride, peak_in, min_gain, flags, &win);
+        const WindowsIn win{WindowsIn::ONE, RowsWindow{in_origin, out_begin, out_count, last}};
+        do_limit(c, "zvx_limit_ex", in, nsamples, B, Nmax, rate, params, 0, out, out_stride, peak_in, min_gain, flags, win);
     });
 }
 
@@ -3937,19 +3821,26 @@ zvx_status zvx_denoise_ex(zvx_ctx* c, const float* in, const int32_t* nsamples, 
                           const zvx_denoise_params* params, void* out, int64_t out_stride, int flags,
                           int64_t in_origin, int64_t out_begin, int64_t out_count, int last) {
     return guarded(c, [&] {
-        const RowsWindow win{in_origin, out_begin, out_count, last};
-        do_denoise(c, "zvx_denoise_ex", in, nsamples, B, Nmax, bias, params, out, out_stride, flags, &win);
+        const WindowsIn win{WindowsIn::ONE, RowsWindow{in_origin, out_begin, out_count, last}};
+        do_denoise(c, "zvx_denoise_ex", in, nsamples, B, Nmax, bias, params, out, out_stride, flags, win);
     });
 }
 
 zvx_status zvx_denoise_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias,
                             const zvx_denoise_params* params, void* out, int64_t out_stride, int flags, const zvx_row_window* win) {
-    return guarded(c, [&] { do_denoise_rows(c, in, nsamples, B, Nmax, bias, params, out, out_stride, flags, win); });
+    return guarded(c, [&] {
+        const WindowsIn w{WindowsIn::PER_ROW, RowsWindow{}, win};
+        do_denoise(c, "zvx_denoise_rows", in, nsamples, B, Nmax, bias, params, out, out_stride, flags, w);
+    });
 }
 
 zvx_status zvx_limit_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_limit_params* params,
                           void* out, int64_t out_stride, float* peak_in, float* min_gain, int flags, const zvx_row_window* win) {
-    return guarded(c, [&] { do_limit_rows(c, in, nsamples, B, Nmax, rate, params, out, out_stride, peak_in, min_gain, flags, win); });
+    return guarded(c, [&] {
+        if (!params) fail(ZVX_E_INVALID, "zvx_limit_rows: params is NULL");
+        const WindowsIn w{WindowsIn::PER_ROW, RowsWindow{}, win};
+        do_limit(c, "zvx_limit_rows", in, nsamples, B, Nmax, rate, params, 0, out, out_stride, peak_in, min_gain, flags, w);
+    });
 }
 
 zvx_status zvx_stream_open(zvx_ctx* c, const float* mel, int frames, const zvx_stream_params* params, int flags, zvx_stream** out) {

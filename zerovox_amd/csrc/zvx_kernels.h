@@ -341,20 +341,19 @@ void launch_conv_post_tanh(const void* x, int x_dt, int ldx, long x_bs, const fl
                            int len_mul, const int* out_len, int out_mul, hipStream_t s);
 // Band-limited rational resampler, rate_in -> rate_out with L = rate_out / gcd, M = rate_in / gcd (include/zvx.h, zvx_resample):
 //   y[n] = sum_k h[n M - k L] x[k],  h = the Kaiser-windowed sinc of 2 * half + 1 taps designed by the context (zvx.hip, rs_bank).
-// Row b of x holds samples [in_origin, in_origin + in_len[b] * in_mul) of a signal that is zero elsewhere (in_len on the DEVICE, like
-// launch_conv_post_tanh's lengths: queued calls stay free of syncs); the launch writes outputs [out_begin, out_begin + cnt_b) to
-// positions [0, cnt_b) of row b of out, cnt_b = out_count, or with out_count < 0 ceil((in_origin + n_b) L / M) - out_begin, then zeros
-// up to out_max; nothing beyond out_max is written.  out: f32, or with pcm16 int16 = trunc(clamp(v * 32760, -32768, 32767)).
+// One launch converts the rows of a device table with one ResampleRow per row: its input and output pointers, its length, its own
+// in_origin / out_begin / cnt and the bound `zend` up to which zeros follow the emitted samples, so that the rows of one launch may live in
+// unrelated buffers and sit anywhere on their signals.  The row holds samples [in_origin, in_origin + n) of a signal that is zero elsewhere;
+// outputs [out_begin, out_begin + cnt) go to positions [0, cnt) of `out`, then zeros up to zend; nothing beyond zend is written (zend = cnt:
+// nothing outside [0, cnt); the calls with one window for all rows pass the longest row's cnt: the zero fill to the longest row).  Every
+// length and count is formed on the HOST (zvx.hip, run_resample_rows) and travels in the table, which every call uploads through the
+// context's pinned staging arena, queued like a launch.  out: f32, or with pcm16 int16 = trunc(clamp(v * 32760, -32768, 32767)).
 // bank: [L][pitch] f32 on the device (padded to a multiple of 4 floats): row p holds the T = ceil((2 half + 1) / L) taps of phase p in
 // ascending input order, bank[p][t] = h[p + (joff[p] - t) L] (0 where that index is below -half), and in column T the integer
 // joff[p] = (half - p) / L as raw bits.  L = M = T = 1, half = 0, bank = {1.0f, 0}: a copy.
-// Per-row form (zvx_resample_rows, the batched rate conversions of zvx_stream_next_many): `rows` is a device table with one ResampleRow per
-// row -- its input and output pointers, its length, its own in_origin / out_begin / cnt and the bound `zend` up to which zeros follow the
-// emitted samples --, so that the rows of one launch may live in unrelated buffers and sit anywhere on their signals.  The kernel resolves
-// ONE ResampleRow at its top and works from it alone: without a table it is formed from the uniform fields (zend = out_max: the zero fill
-// to the longest row), with one zend = cnt (nothing outside [0, cnt) is written).  One body: the sum of an output is the same instructions
-// in every form.  The 16-byte load and store paths are chosen per row from that row's own pointers and in_origin & 3; they change no bit.
-// The grid is sized by out_max, the longest row; a workgroup whose first tile lies at or past its row's zend returns before the bank load.
+// The kernel reads rows[blockIdx.y] at its top and works from it alone: the sum of an output is the same instructions for every caller.
+// The 16-byte load and store paths are chosen per row from that row's own pointers and in_origin & 3; they change no bit.
+// The grid is sized by out_max, the largest zend; a workgroup whose first tile lies at or past its row's zend returns before the bank load.
 struct ResampleRow {
     const float* x; void* out;               // the row's samples; where emitted sample 0 goes (f32 or int16)
     long n;                                  // the row's length
@@ -362,12 +361,11 @@ struct ResampleRow {
     long zend;                               // zeros are written to [cnt, zend)
 };
 struct ResampleArgs {
-    const ResampleRow* rows;                 // NULL: the uniform form below
-    const float* x; long x_bs; const int* in_len; int in_mul;
-    void* out; long out_bs; int pcm16;
+    const ResampleRow* rows;                 // [B], on the device
+    int pcm16;
     int B, L, M, half, T, pitch;
     const float* bank;
-    long in_origin, out_begin, out_count, out_max;
+    long out_max;                            // the largest zend: the grid
 };
 // false (nothing launched) when the bank and one tile's input span exceed the LDS of a workgroup
 bool launch_resample_poly(const ResampleArgs& a, hipStream_t s);
@@ -464,15 +462,14 @@ struct LoudApplyArgs {
 };
 void launch_loud_apply(const LoudApplyArgs& a, long n_max, hipStream_t s);
 // True-peak envelope and look-ahead limiter of a batch's waveform rows (include/zvx.h, zvx_true_peak / zvx_limit).  Both kernels work on
-// tiles of LIMIT_TILE samples of one row, 256 threads each; lengths are read on the DEVICE and nothing outside [0, nsamples[b]) is read
-// or written.  The windowed form (zvx_limit_ex) emits the samples [off, off + cnt[b]) of the row only: the envelope is still evaluated over
-// the whole row, the gain tiles start at `off` -- any sample offset from the envelope's tile grid -- and write out[b][i - off]; the
-// arithmetic of a sample depends on neither grid.  The whole-row form is off = 0, cnt = nsamples.
-// Per-row form (zvx_limit_rows, the batched stages of zvx_stream_next_many): `rows` is a device table with one LimitRow per row -- its
-// input, output and envelope pointers, its length and its emitted range --, so that the rows of one launch may live in unrelated buffers and
-// sit anywhere on their signals.  Every kernel resolves ONE LimitRow at its top and works from it alone: without a table the row is formed
-// from the uniform fields (x + b x_bs, nsamples[b], off, cnt[b] ...), so the whole-row call, the _ex call and the per-row call run the same
-// instructions.  Grids are sized by the longest row; a workgroup past its row's extent only writes its neutral partial result.
+// tiles of LIMIT_TILE samples of one row, 256 threads each; nothing outside [0, n) of a row is read or written.  `rows` is a device
+// table with one LimitRow per row -- its input, output and envelope pointers, its length and its emitted range --, so that the rows of one
+// launch may live in unrelated buffers and sit anywhere on their signals; every call uploads one through the context's pinned staging arena
+// (zvx.hip, run_limit_rows).  A windowed row emits the samples [off, off + cnt) only: the envelope is still evaluated over the whole row,
+// the gain tiles start at `off` -- any sample offset from the envelope's tile grid -- and write out[i - off]; the arithmetic of a sample
+// depends on neither grid.  A whole row is off = 0, cnt = n.  Every kernel reads rows[blockIdx.y] at its top and works from it alone, so
+// the whole-row call, the _ex call and the per-row call run the same instructions.  Grids are sized by the longest row; a workgroup past
+// its row's extent only writes its neutral partial result.
 constexpr int LIMIT_TILE = 1024;             // (zerovox_amd/_lib.py carries the same figure for the tests' tile-edge rows)
 constexpr int LIMIT_MAX_W = 4096;
 constexpr int LIMIT_ENV_REACH = 11;          // e[j] reads x[j - 11 .. j + 11] where os > 1 (include/zvx.h, zvx_limit_ex: H; _lib.py: LIMIT_ENV_REACH)
@@ -481,14 +478,13 @@ struct LimitRow {
     int n, off, cnt, pad_;                   // the row's length; the emitted range [off, off + cnt)
 };
 struct LimitArgs {
-    const LimitRow* rows;                    // NULL: the uniform form below
-    const float* x; long x_bs; const int* nsamples; int B;
+    const LimitRow* rows;                    // [B], on the device
+    int B;
     int os, T, pitch; const float* bank;     // os > 1: the resampler's bank of (L, M) = (os, 1) (ResampleArgs), T = 21; os == 1: unused
-    float* env; long e_bs;                   // e[b][i], the envelope (f32); NULL: only the partial maxima are wanted (zvx_true_peak)
     float* part_max; float* part_min; int ppitch;   // [b][tile]: max e / min g32 over the tile's EMITTED samples (0 / 1 where it has none)
-    int off; const int* cnt; int gtiles;     // the emitted range [off, off + cnt[b]) of row b (device array); tiles of the gain launch (<= ppitch)
+    int gtiles;                              // tiles of the gain launch (<= ppitch)
     float c; int W; const double* win;       // the ceiling; the smoothing weights win[k + W], k = -W .. W
-    void* out; long out_bs; int pcm16;
+    int pcm16;
     float* res;                              // launch_limit_reduce: res[b] = max over part_max[b][.], res[B + b] = min over part_min[b][.]
 };
 // e[b][i] = max(|x[i]|, |y[m]| for os (i - 1) < m < os (i + 1), 0 <= m < os n): the tile plus a halo of 10 samples in front and 11 behind
@@ -501,49 +497,44 @@ void launch_limit_env(const LimitArgs& a, hipStream_t s);
 // below the ceiling copies its samples.  It reads e, never a neighbour's x: safe in place (off = 0).  grid.x = gtiles tiles from `off` on.
 // false: the span does not fit the LDS.
 bool launch_limit_gain(const LimitArgs& a, hipStream_t s);
-// one workgroup per row over the tiles' partial results (part_max / part_min are [b][ppitch] in every form, and a tile past a row's own
-// extent holds the neutral 0 / 1, so this launch needs no row descriptor)
+// one workgroup per row over the tiles' partial results (part_max / part_min are [b][ppitch], and a tile past a row's own extent holds the
+// neutral 0 / 1, so this launch needs no row descriptor; part_min NULL: no gain launch ran, res[B + b] = 1)
 void launch_limit_reduce(const LimitArgs& a, hipStream_t s);
 // Vocoder-bias denoiser (include/zvx.h, zvx_denoise; spectral.hip): spectral subtraction over the STFT frames of zvx_melspec, the frames
 // transformed by an FFT that lives in LDS.  A workgroup of 256 threads holds DENOISE_POINTS complex f32 points, i.e. DENOISE_POINTS / n_fft
 // frames of ONE row (4 at 1024), as split re / im planes; every pass of the radix-4 Stockham transform (one radix-2 pass first where
-// log2 n_fft is odd) reads its inputs into registers, synchronises, and writes its outputs to the same planes.  Lengths are read on the
-// DEVICE; the host has validated them (zvx_melspec's conditions), so every reflected index lies inside the row.
-// The window (zvx_denoise_ex): the rows hold samples [origin, origin + nsamples[b]) of their signals and the frame grid is the SIGNAL's.  The
-// kernels work in window-relative ints: frame j of the work buffer is frame f_first + j of the signal and reads the window from sample
-// rel + j hop on; the one absolute quantity, the signal's frame count, is formed in 64 bits from origin and f_first.  f_first is a
-// multiple of the frames per workgroup, so that a frame sits in the slot it has in the whole-row call and runs through the same
-// instructions: the first `skip` frames cover no emitted sample and are neither loaded nor stored.  The whole-row call is origin 0,
-// f_first 0, skip 0, rel -pad, both mirrors, off 0, cnt -1: the indices it forms are the ones it always formed.
-// Per-row form (zvx_denoise_rows, the batched stages of zvx_stream_next_many): `rows` is a device table with one DenoiseRow per row -- its
-// input, output and work-buffer pointers, its length and every window quantity above, f_first rounded down per ROW --, so that the rows of
-// one launch may live in unrelated buffers and sit anywhere on their signals.  Both kernels resolve ONE DenoiseRow at their top and work
-// from it alone: without a table it is formed from the uniform fields, so all three forms run the same instructions through the
-// transforms (two instantiations of one source need not contract their multiply-adds alike; one body cannot differ from itself).
+// log2 n_fft is odd) reads its inputs into registers, synchronises, and writes its outputs to the same planes.  The host has validated
+// the lengths (zvx_melspec's conditions), so every reflected index lies inside the row.
+// `rows` is a device table with one DenoiseRow per row -- its input, output and work-buffer pointers, its length and its window --, so that
+// the rows of one launch may live in unrelated buffers and sit anywhere on their signals; every call uploads one through the context's
+// pinned staging arena (zvx.hip, run_denoise_rows).
+// The window: a row holds samples [origin, origin + n) of its signal and the frame grid is the SIGNAL's.  The kernels work in
+// window-relative ints: frame j of the work buffer is frame f_first + j of the signal and reads the window from sample rel + j hop on
+// (rel = f_first hop - pad - origin; negative: in the left mirror); the one absolute quantity, the signal's frame count, is formed in 64
+// bits from origin and f_first.  f_first is a multiple of the frames per workgroup, rounded down per ROW, so that a frame sits in the
+// slot it has in the whole-row call and runs through the same instructions: the first `skip` frames cover no emitted sample and are neither
+// loaded nor stored.  A whole row is origin 0, f_first 0, skip 0, rel -pad, both mirrors, off 0, cnt n: the indices it forms are the ones
+// it always formed.  Both kernels read rows[blockIdx.y] at their top and work from it alone, so every call runs the same instructions
+// through the transforms (two instantiations of one source need not contract their multiply-adds alike; one body cannot differ from itself).
 constexpr int DENOISE_POINTS = 4096;         // also the largest n_fft
 struct DenoiseRow {
     const float* x; void* out; float* work;  // the row's samples; where emitted sample `off` goes (f32 or int16); its frames [F][n_fft], from f_first
     long origin, f_first;
-    int n, skip, rel, off, cnt, mirrors;     // mirrors: bit 0 left, bit 1 right; cnt -1: to the end of the row
+    int n, skip, rel, off, cnt, mirrors;     // the emitted range [off, off + cnt), cnt -1: to the end of the row; mirrors: bit 0 left, bit 1 right --
+                                             // the reflect at sample 0 exists (origin == 0); the signal ends with the window, so the one at its end does
 };
 struct DenoiseArgs {
-    const DenoiseRow* rows;                  // NULL: the uniform form below, row b's work at work + b Fmax n_fft
-    const float* x; long x_bs; const int* nsamples; int B;
-    int n_fft, log2n, hop, pad, Fmax;        // Fmax: the most frames transformed of a row (the frame buffers' row pitch, in frames)
-    long origin, f_first;                    // the window's first sample; frame 0 of the work buffer on the signal's grid (the same for every row)
-    int skip;                                // frames f_first .. f_first + skip - 1 cover no emitted sample: not transformed
-    int rel;                                 // f_first hop - pad - origin: where frame f_first begins, as an index into the window (negative: in the left mirror)
-    int left, right;                         // the reflect at sample 0 exists (origin == 0); the signal ends with the window (last): the reflect at its end exists
-    int off, cnt;                            // the emitted range: [off, off + cnt) of every row, cnt -1: to the end of the row
+    const DenoiseRow* rows;                  // [B], on the device
+    int B;
+    int n_fft, log2n, hop, pad, Fmax;        // Fmax: the most frames transformed of a row (the grid; the pitch of `mag`, in frames)
     const float* twid;                       // [n_fft][2]: cos, -sin of 2 pi m / n_fft, designed in double, rounded once
     const float* win;                        // [n_fft]: the analysis / synthesis window, likewise
     const double* win2;                      // [n_fft]: its square, from the double window
     double den_min;                          // the pass-through threshold on den (include/zvx.h)
     const float* bias; float strength, floor;
-    float* work;                             // [B][Fmax][n_fft]: w[t] y_f[t], indexed from f_first
     float* mag;                              // launch_denoise_frames: non-NULL = magnitude-out mode, |X[f][k]| -> mag[B][Fmax][n_fft / 2 + 1], nothing else
-    void* out; long out_bs; int pcm16;
-    int copy;                                // launch_denoise_ola: strength == 0, out[i] = x[i] and `work` is not read
+    int pcm16;
+    int copy;                                // launch_denoise_ola: strength == 0, out[i] = x[i] and the rows' `work` is not read
 };
 // frame load (reflect padding, window), forward FFT, gain, inverse FFT, window, store of w[t] y_f[t]; no spectrum goes to memory.  Only the
 // frames that cover an emitted sample are transformed.  grid = (ceil(Fmax / frames per workgroup), B): B <= 65535.
