@@ -629,6 +629,92 @@ zvx_status zvx_limit_rows(zvx_ctx* ctx, const float* in, const int32_t* nsamples
 zvx_status zvx_resample_rows(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, int rate_in, int rate_out, void* out,
                              int64_t out_stride, int32_t* out_len, int flags, const zvx_row_window* win);
 
+/* Leveler: a gain curve that follows the gated SHORT-TERM loudness of a sliding window, with a bounded look-ahead, for rows in [B][Nmax] f32
+ * with nsamples[b] valid samples at `rate` Hz.  It is an automatic gain control, not R128 normalisation: the integrated gain of
+ * zvx_normalize is not known before a signal ends, this curve has finite support and can therefore be applied to a stream.  Whether it is
+ * pleasant to listen to on a real voice is NOT measured here: the arithmetic is pinned against a float64 restatement, nothing more.
+ * Per row of n samples:
+ * Units: h = (rate + 5) / 10 samples, U = n / h whole units.  u[q] is exactly zvx_loudness's: K-weighting in double with that call's
+ *   coefficients; the recurrence of unit q runs from ZERO state over samples [(q - 2) h, (q + 1) h), samples in front of sample 0 are zero,
+ *   and u[q] is the double sum of y^2 over the last h of them.  Here the zero-state start two units early is part of the contract, not an
+ *   allowance: it makes a unit's power a function of 3 h samples and so makes the windows tile.  p[q] = u[q] / h.
+ * Parameters (zvx_level_params): S = max(1, rint(window_ms / 100)) units of window and a = rint(lookahead_ms / 100) units of look-ahead,
+ *   0 <= a <= S, both on the host in double.
+ * Unit gain: over the units k in [max(0, q - S + 1), q], in ascending k and in double, sum = the sum of p[k] and cnt = their number over
+ *   those with p[k] > 10^((-70 + 0.691) / 10) -- the absolute gate of BS.1770 applied per 100 ms unit, the constant computed once on the
+ *   host.  cnt == 0: G[q] = 1.  Otherwise L = -0.691 + 10 log10(sum / cnt) and G[q] = min(10^((target_lufs - L) / 20), 10^(max_gain_db / 20)),
+ *   in double.  A unit whose p lies within a relative 2.3e-4 of the gate is AMBIGUOUS, as for zvx_loudness: either decision is allowed.
+ * Nodes: T[j] = G[clamp(j + a - 1, 0, U - 1)], j = 0 .. U + 1: the gain at the START of unit j is that of the window that ends a units
+ *   ahead of the unit in front of it.  U == 0: every T is 1.
+ * Gain: for sample i with q = i / h:  g = fma(T[q + 1] - T[q], (double)(i - q h) / (double) h, T[q]);  g32 = g rounded to nearest f32;
+ *   out[i] = x[i] * g32, ONE f32 multiply; with ZVX_PCM16 the resampler's rule follows.
+ * What follows from that:
+ *   (a) where both nodes of a sample are 1 the output has the bits of x[i]: silence under the gate is left alone, and so is a whole row
+ *       that never passes it;
+ *   (b) where both nodes are equal the gain is exactly constant (the fma adds an exact 0);
+ *   (c) rows are independent; n == 0 writes nothing (gain_lo = gain_hi = 1); non-finite input follows zvx_vocode_mel's rule (that row
+ *       unspecified, nothing faults, the others untouched).
+ * gain_lo[b] / gain_hi[b]: the minimum and maximum of g32 over the emitted range; 1 and 1 where it is empty.
+ * zvx_level_ex: the same over a window, under the contract of zvx_limit_ex word for word -- row b holds samples [in_origin, in_origin +
+ *   nsamples[b]) of a signal that starts at sample 0 and, with last, ends with the row; outputs [out_begin, out_begin + cnt_b) of zvx_level on
+ *   the WHOLE signal go to positions [0, cnt_b) of out row b; cnt_b = out_count, or with out_count == -1 (needs last) in_origin + nsamples[b]
+ *   - out_begin -- except that the reach is ASYMMETRIC: RL = (S + 3 - a) h - 1 to the left (the oldest unit of the window under the
+ *   sample's first node, and its two units of warm-up), RR = (a + 1) h - 1 to the right (the unit under its second node).
+ *   Support condition, per row with cnt_b > 0 (otherwise ZVX_E_INVALID; the message names the row, RL or RR and the missing samples):
+ *     in_origin <= out_begin  and  out_begin + cnt_b <= in_origin + nsamples[b];
+ *     left:  in_origin == 0  or  out_begin - RL >= in_origin;
+ *     right: last  or  out_begin + cnt_b - 1 + RR <= in_origin + nsamples[b] - 1.
+ *     left, clamped: a window with last and in_origin > 0 whose outputs begin in the signal's last a units or its tail has its first node
+ *       clamped to unit U - 1, which moves that node's window out_begin / h + a - U units to the LEFT of where RL assumes it.  Such a row
+ *       also needs  (kf - 2) h >= in_origin,  kf = max(0, min(out_begin / h + a - 1, U - 1) - S + 1)  the oldest unit under its first node
+ *       (integer divisions, U = (in_origin + nsamples[b]) / h; no rule where U == 0).  Wherever the clamp does not act RL implies it.
+ *   With last, U comes from N_b = in_origin + nsamples[b] and the clamp to U - 1 acts; without it the right condition puts every needed
+ *   unit inside the window, where the clamp would not have acted: the two agree.  The unit grid is the SIGNAL's, whatever in_origin is.
+ *   Results: the emitted samples are bit for bit those of zvx_level on the whole signal (f32, and int16 with ZVX_PCM16): a unit's p
+ *   depends on its own 3 h samples, the gated sum runs in ascending k, and a sample's gain on its two nodes and its offset in the unit.
+ *   The min / max of gain_lo / gain_hi over a stream's pieces are the whole call's values.
+ * zvx_level is zvx_level_ex(..., 0, 0, -1, 1).  zvx_level_rows is zvx_level_ex with win[b] (a HOST array of B entries) in place of the call's
+ *   one window, under the contract of zvx_limit_rows: row b's bits are those of the _ex call on that row alone, whatever shares the call;
+ *   nothing outside [0, cnt_b) of an output row is touched; the parameters stay per call.
+ * Launches: one lane per needed unit runs the 3 h-step recurrence over samples read relative to in_origin (nothing outside the row is
+ *   read; staged through LDS as 16-byte groups aligned as addresses, as zvx_loudness does) and writes p into a work buffer of the context
+ *   indexed from the row's first needed unit; tiles of the emitted range then form the few G they need once in LDS and multiply, 16-byte
+ *   loads and stores where the row's own pointers allow (chosen per row, no bit changes); a reduction per row.  Every call forms one row
+ *   descriptor per row on the host -- input, output and unit-buffer pointers, length, in_origin, emitted range, first and last needed
+ *   unit, the signal's unit count where the window is last -- and uploads them as one table through the pinned staging arena: one body
+ *   serves all three calls.  No index is formed in 32 bits from an absolute position: in_origin and out_begin may lie beyond 2^32.
+ * Flags, syncs, in-place use, the queued form: the rows-call contract exactly as zvx_limit / zvx_limit_ex / zvx_limit_rows use it
+ *   (ZVX_DEVICE_IN, ZVX_DEVICE_OUT, ZVX_NO_SYNC with a device output only, ZVX_PCM16 not in place; out == in for f32 rows with the same
+ *   stride, on the same side, and out_begin == in_origin; the call waits once, for the host outputs; with ZVX_DEVICE_OUT | ZVX_NO_SYNC
+ *   and gain_lo == gain_hi == NULL it only queues).  The apply launch reads x at a sample's own index only.
+ * Validation, before anything is queued (ZVX_E_INVALID, the context stays usable): every check zvx_limit_ex / zvx_limit_rows make on ctx /
+ *   in / nsamples / params / out / B / Nmax / lengths / rate / out_stride / flags / in-place use / the window's numbers / win / reserved,
+ *   the support condition per row, its clamped left rule included; target_lufs not finite or outside [-70, 0]; max_gain_db not finite or negative; window_ms or
+ *   lookahead_ms not finite or negative; a > S.  ZVX_E_UNSUPPORTED: S > 600, more than 65535 rows.
+ * Stage tag "post.level" in zvx_tag_stats (one timed group per call; no stage slot): algorithmic bytes = 4 per sample read plus the bytes
+ *   written (4 or, with ZVX_PCM16, 2 per emitted sample).
+ * A stream: zerovox_amd/leveler.py plans the windows -- a non-last push emits up to received - RR, the last one everything, the history
+ *   before next_out - RL is dropped -- so a levelled stream runs RR samples behind its input (4409 samples, 200 ms, at 22.05 kHz with
+ *   the defaults of 3000 ms / 100 ms).  ZeroVox.vocode_stream(level=) puts it between the denoiser and the limiter.
+ * Not here: a level stage inside zvx_stream_open / zvx_stream_next_many (zvx_stream_params is ABI: a change of its own on top of
+ *   zvx_level_rows), relative gating, a lower bound on the gain, several channels. */
+typedef struct zvx_level_params {
+    float target_lufs;    /* short-term loudness to steer towards, finite, in [-70, 0] */
+    float max_gain_db;    /* upper bound on the gain in dB, finite, >= 0 */
+    float window_ms;      /* S = max(1, rint(window_ms / 100)) units, finite, >= 0; S > 600: ZVX_E_UNSUPPORTED */
+    float lookahead_ms;   /* a = rint(lookahead_ms / 100) units, finite, >= 0, a <= S */
+} zvx_level_params;
+/* out row b = x[i] * g32[i]; gain_lo[b] / gain_hi[b] = min / max of g32 (host arrays, each may be NULL).
+ * flags: ZVX_DEVICE_IN, ZVX_DEVICE_OUT, ZVX_NO_SYNC (device out only), ZVX_PCM16 (not in place); out == in (same stride) allowed for f32 */
+zvx_status zvx_level(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, int rate,
+                     const zvx_level_params* params, void* out, int64_t out_stride, float* gain_lo, float* gain_hi, int flags);
+zvx_status zvx_level_ex(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, int rate,
+                        const zvx_level_params* params, void* out, int64_t out_stride, float* gain_lo, float* gain_hi, int flags,
+                        int64_t in_origin, int64_t out_begin, int64_t out_count, int last);
+zvx_status zvx_level_rows(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, int rate,
+                          const zvx_level_params* params, void* out, int64_t out_stride, float* gain_lo, float* gain_hi, int flags,
+                          const zvx_row_window* win);
+
 /* Stream sessions: chunked vocoding of ONE utterance with the planning inside the library.  A session owns the utterance's mel on the
  * device, vocodes it group by group and runs the new samples device to device through the optional denoiser, limiter and rate conversion;
  * each zvx_stream_next hands out one finished piece with one wait.  It is what ZeroVox.vocode_stream does with three Python planners and

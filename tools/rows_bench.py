@@ -1,21 +1,22 @@
-"""What a window per row buys on its own (include/zvx.h: zvx_denoise_rows, zvx_limit_rows, zvx_resample_rows): 64 signals, each at a position
-of its own, one 16-frame piece of each -- 4096 new samples behind the history its stage keeps -- through the denoiser, through the limiter
-and through the rate conversion (to 48000 and to 8000 Hz)
-   (a) by 64 zvx_denoise_ex / zvx_limit_ex / zvx_resample_ex calls of one row,
-   (b) by one zvx_denoise_rows / zvx_limit_rows / zvx_resample_rows call of 64 rows,
+"""What a window per row buys on its own (include/zvx.h: zvx_denoise_rows, zvx_limit_rows, zvx_resample_rows, zvx_level_rows): 64 signals, each
+at a position of its own, one 16-frame piece of each -- 4096 new samples behind the history its stage keeps -- through the denoiser, through
+the limiter, through the rate conversion (to 48000 and to 8000 Hz) and through the leveler
+   (a) by 64 zvx_denoise_ex / zvx_limit_ex / zvx_resample_ex / zvx_level_ex calls of one row,
+   (b) by one zvx_denoise_rows / zvx_limit_rows / zvx_resample_rows / zvx_level_rows call of 64 rows,
 device rows in and out, everything queued (ZVX_NO_SYNC) and one wait at the end, the two alternating.  A development aid; nothing on the
 product path imports it.
-   python tools/rows_bench.py [--rows 64] [--reps 30] [out.json]"""
+   python tools/rows_bench.py [--rows 64] [--reps 30] [--stages denoise,limit,resample,level] [out.json]"""
 import argparse, ctypes as C, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from zerovox_amd import _lib, config as zcfg, weights as zw
+from zerovox_amd import _lib, config as zcfg, leveler, weights as zw
 from zerovox_amd.model import ZeroVox
 
 ap = argparse.ArgumentParser()
 ap.add_argument("out", nargs="?", help="write the result as JSON here")
 ap.add_argument("--rows", type=int, default=64)
 ap.add_argument("--reps", type=int, default=30)
+ap.add_argument("--stages", default="denoise,limit,resample,level", help="which lines to run, comma-separated")
 args = ap.parse_args()
 
 cfg = zcfg.medium_modelcfg("styletts"); h = zcfg.hifigan_config("v1")
@@ -26,6 +27,7 @@ n_fft = ctx.get_int("fft_size")
 bias = np.ascontiguousarray(model.denoise_bias, np.float32)
 dn = _lib.DenoiseParams(0.01, 0.0)
 lim = _lib.LimitParams(10 ** (-1 / 20), 5.0, 4)
+lvl = _lib.LevelParams(-16.0, 20.0, 3000.0, 100.0)
 W = max(1, int(np.rint(RATE * 5.0 / 1000.0)))
 F = _lib.ZVX_DEVICE_IN | _lib.ZVX_DEVICE_OUT | _lib.ZVX_NO_SYNC
 vp = C.c_void_p
@@ -112,14 +114,20 @@ def resample_line(rate_out):
                  lambda x, l, n, o, w: lib.zvx_resample_rows(ctx._h, x, _lib._ptr(l), B, n, RATE, rate_out, o, 3 * n, None, F, w), ratio=(Lr, Mr))
 
 
-res = {"workload": f"{B} rows, one 16-frame piece each, device rows, queued calls and one wait; median of {args.reps}", "rows": [
-    bench("denoise", n_fft - 1,
+LINES = {
+    "denoise": lambda: [bench("denoise", n_fft - 1,
           lambda x, l, n, o, w: lib.zvx_denoise_ex(ctx._h, x, _lib._ptr(l), 1, n, _lib._ptr(bias), C.byref(dn), o, n, F, w.in_origin, w.out_begin, w.out_count, 0),
-          lambda x, l, n, o, w: lib.zvx_denoise_rows(ctx._h, x, _lib._ptr(l), B, n, _lib._ptr(bias), C.byref(dn), o, n, F, w)),
-    bench("limit", 2 * W + _lib.LIMIT_ENV_REACH,
+          lambda x, l, n, o, w: lib.zvx_denoise_rows(ctx._h, x, _lib._ptr(l), B, n, _lib._ptr(bias), C.byref(dn), o, n, F, w))],
+    "limit": lambda: [bench("limit", 2 * W + _lib.LIMIT_ENV_REACH,
           lambda x, l, n, o, w: lib.zvx_limit_ex(ctx._h, x, _lib._ptr(l), 1, n, RATE, C.byref(lim), o, n, None, None, F, w.in_origin, w.out_begin, w.out_count, 0),
-          lambda x, l, n, o, w: lib.zvx_limit_rows(ctx._h, x, _lib._ptr(l), B, n, RATE, C.byref(lim), o, n, None, None, F, w)),
-    resample_line(48000), resample_line(8000)]}
+          lambda x, l, n, o, w: lib.zvx_limit_rows(ctx._h, x, _lib._ptr(l), B, n, RATE, C.byref(lim), o, n, None, None, F, w))],
+    "resample": lambda: [resample_line(48000), resample_line(8000)],
+    # the leveler's reach is asymmetric: rows carry RL on both sides (RR < RL), 3 s of history for 186 ms of new samples
+    "level": lambda: [bench("level", leveler.reach(RATE, 3000.0, 100.0)[0],
+          lambda x, l, n, o, w: lib.zvx_level_ex(ctx._h, x, _lib._ptr(l), 1, n, RATE, C.byref(lvl), o, n, None, None, F, w.in_origin, w.out_begin, w.out_count, 0),
+          lambda x, l, n, o, w: lib.zvx_level_rows(ctx._h, x, _lib._ptr(l), B, n, RATE, C.byref(lvl), o, n, None, None, F, w))]}
+res = {"workload": f"{B} rows, one 16-frame piece each, device rows, queued calls and one wait; median of {args.reps}",
+       "rows": [row for name in args.stages.split(",") for row in LINES[name.strip()]()]}
 print(json.dumps(res))
 if args.out:
     json.dump(res, open(args.out, "w"), indent=1)

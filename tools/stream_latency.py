@@ -10,7 +10,11 @@
    with --peak-db as well also the combined chain, limit(denoise(stream)).
    python tools/stream_latency.py --resident [--denoise S] [--peak-db DB] [out.json]   -> next to every chain above, in the same process,
    the figures of the same stream run by a stream session of the library (zvx_stream_open; vocode_stream(resident=True)): first piece,
-   all pieces, the median piece gap, and whether its concatenation equals the host-planned one bit for bit."""
+   all pieces, the median piece gap, and whether its concatenation equals the host-planned one bit for bit.
+   python tools/stream_latency.py --level LUFS [--denoise S --peak-db DB] [out.json]   -> the same stream WITH and WITHOUT the windowed leveler
+   (zvx_level_ex towards LUFS, 3000 ms window, 100 ms look-ahead): first piece, all pieces, the median piece gap, the samples the levelled
+   stream runs behind (leveler.reach: RR) and whether the pieces equal zvx_level of the whole stream bit for bit; with --denoise and
+   --peak-db as well also the whole chain, limit(level(denoise(stream)))."""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -23,6 +27,7 @@ ap.add_argument("--peak-db", type=float, default=None, metavar="DB", help="also 
 ap.add_argument("--limiter-ms", type=float, default=5.0, metavar="MS")
 ap.add_argument("--denoise", type=float, default=None, metavar="S", help="also time the stream denoised at this strength")
 ap.add_argument("--resident", action="store_true", help="also time every chain run by a stream session of the library")
+ap.add_argument("--level", type=float, default=None, metavar="LUFS", help="also time the stream levelled towards this short-term loudness")
 args = ap.parse_args()
 
 cfg = zcfg.medium_modelcfg("styletts"); sd = zw.tts_state_dict(cfg, 0)
@@ -122,6 +127,29 @@ for cf in (16, 32, 64, 128, 256):
                 "bit_equal_to_whole_limit_of_denoise": bool(np.array_equal(both.view(np.uint32), want_both.view(np.uint32)))}
             if args.resident:
                 res["chunks"][-1]["denoised_limited"]["resident"] = resident(cf, both, denoise=den, limiter=lim)
+    if args.level is not None:
+        from zerovox_amd.leveler import reach as level_reach
+        lvl = dict(target=float(args.level), window_ms=3000.0, lookahead_ms=100.0)
+        native = ctx.get_int("sampling_rate")
+        levelled = np.concatenate(list(model.vocode_stream(mel, chunk_frames=cf, level=lvl)))
+        want_lvl = ctx.level([whole], rate=native, **lvl)[0][0]
+        if "piece_gap_ms" not in res["chunks"][-1]:
+            res["chunks"][-1]["piece_gap_ms"] = round(piece_gap(lambda: model.vocode_stream(mel, chunk_frames=cf)), 3)
+        res["chunks"][-1]["levelled"] = {
+            "level_lufs": args.level, "delay_samples": level_reach(native, lvl["window_ms"], lvl["lookahead_ms"])[1],
+            "first_piece_ms": round(best(lambda: next(iter(model.vocode_stream(mel, chunk_frames=cf, level=lvl)))), 3),
+            "all_pieces_ms": round(best(lambda: list(model.vocode_stream(mel, chunk_frames=cf, level=lvl)), n=5), 3),
+            "piece_gap_ms": round(piece_gap(lambda: model.vocode_stream(mel, chunk_frames=cf, level=lvl)), 3),
+            "bit_equal_to_whole_level": bool(np.array_equal(levelled.view(np.uint32), want_lvl.view(np.uint32)))}
+        if args.denoise is not None and args.peak_db is not None:
+            chain = dict(denoise=den, level=lvl, limiter=lim)
+            all3 = np.concatenate(list(model.vocode_stream(mel, chunk_frames=cf, **chain)))
+            want3 = ctx.limit([ctx.level([want], rate=native, **lvl)[0][0]], rate=native, **lim)[0][0]
+            res["chunks"][-1]["denoised_levelled_limited"] = {
+                "first_piece_ms": round(best(lambda: next(iter(model.vocode_stream(mel, chunk_frames=cf, **chain)))), 3),
+                "all_pieces_ms": round(best(lambda: list(model.vocode_stream(mel, chunk_frames=cf, **chain)), n=5), 3),
+                "piece_gap_ms": round(piece_gap(lambda: model.vocode_stream(mel, chunk_frames=cf, **chain)), 3),
+                "bit_equal_to_limit_of_level_of_denoise": bool(np.array_equal(all3.view(np.uint32), want3.view(np.uint32)))}
     print(res["chunks"][-1], flush=True)
 print(json.dumps(res))
 if args.out:

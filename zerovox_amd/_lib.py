@@ -27,7 +27,7 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_encode_ex", "zvx_synthesize_ex", "zvx_resample", "zvx_resample_ex", "zvx_trim_bounds", "zvx_join",
            "zvx_loudness", "zvx_normalize", "zvx_true_peak", "zvx_limit", "zvx_spkemb_wav", "zvx_limit_ex", "zvx_denoise_bias", "zvx_denoise",
            "zvx_denoise_ex", "zvx_stream_open", "zvx_stream_next", "zvx_stream_info", "zvx_stream_close", "zvx_stream_next_many",
-           "zvx_denoise_rows", "zvx_limit_rows", "zvx_resample_rows")
+           "zvx_denoise_rows", "zvx_limit_rows", "zvx_resample_rows", "zvx_level", "zvx_level_ex", "zvx_level_rows")
 ZVX_STREAM_MANY_MAX_SESSIONS, ZVX_STREAM_MANY_MAX_ROWS = 64, 256
 ZVX_COMM_ID_BYTES = 128
 ZVX_LOUD_PER_ROW, ZVX_LOUD_COMMON = 0, 1
@@ -68,6 +68,11 @@ class LoudnessParams(C.Structure):
 class LimitParams(C.Structure):
     """zvx_limit_params (include/zvx.h)"""
     _fields_ = [("ceiling", C.c_float), ("window_ms", C.c_float), ("oversample", C.c_int32)]
+
+
+class LevelParams(C.Structure):
+    """zvx_level_params (include/zvx.h)"""
+    _fields_ = [("target_lufs", C.c_float), ("max_gain_db", C.c_float), ("window_ms", C.c_float), ("lookahead_ms", C.c_float)]
 
 
 class DenoiseParams(C.Structure):
@@ -159,6 +164,9 @@ def load():
     lib.zvx_denoise_rows.argtypes = lib.zvx_denoise.argtypes + [C.POINTER(RowWindow)]
     lib.zvx_limit_rows.argtypes = lib.zvx_limit.argtypes + [C.POINTER(RowWindow)]
     lib.zvx_resample_rows.argtypes = lib.zvx_resample.argtypes + [C.POINTER(RowWindow)]
+    lib.zvx_level.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(LevelParams), vp, C.c_int64, vp, vp, C.c_int]
+    lib.zvx_level_ex.argtypes = lib.zvx_level.argtypes + [C.c_int64, C.c_int64, C.c_int64, C.c_int]
+    lib.zvx_level_rows.argtypes = lib.zvx_level.argtypes + [C.POINTER(RowWindow)]
     lib.zvx_stream_open.argtypes = [vp, vp, C.c_int, C.POINTER(StreamParams), C.c_int, C.POINTER(vp)]
     lib.zvx_stream_next.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int]
     lib.zvx_stream_info.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
@@ -591,6 +599,52 @@ class Context:
         self._chk(self._lib.zvx_limit_rows(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), out.shape[1], _ptr(peak),
                                            _ptr(gmin), flags, win))
         return [out[b, :cnt[b]] for b in range(B)], peak, gmin
+
+    @classmethod
+    def _level_args(cls, target, max_gain_db, window_ms, lookahead_ms, **flags):
+        return LevelParams(float(target), float(max_gain_db), float(window_ms), float(lookahead_ms)), cls._flags(**flags)
+
+    def level(self, rows, target, max_gain_db=20.0, window_ms=3000.0, lookahead_ms=100.0, pcm16=False, rate=None, lengths=None):
+        """zvx_level on host rows: a gain curve that steers the gated short-term loudness of the last window_ms towards `target` LUFS,
+        looking lookahead_ms ahead and never above max_gain_db (an AGC, not R128 normalisation; zerovox_amd.leveler) -> (rows_out
+        [B][Nmax] float32 / int16 -- row b holds its levelled samples, then zeros --, gain_lo [B], gain_hi [B] float32: the smallest and
+        the largest gain applied)."""
+        x, n = self._rows(rows, lengths)
+        B, Nmax = x.shape
+        prm, flags = self._level_args(target, max_gain_db, window_ms, lookahead_ms, pcm16=pcm16)
+        out = np.zeros((B, Nmax), np.int16 if pcm16 else np.float32)
+        lo, hi = np.zeros(B, np.float32), np.zeros(B, np.float32)
+        self._chk(self._lib.zvx_level(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), Nmax, _ptr(lo), _ptr(hi), flags))
+        return out, lo, hi
+
+    def level_window(self, rows, target, max_gain_db=20.0, window_ms=3000.0, lookahead_ms=100.0, in_origin=0, out_begin=0, out_count=-1,
+                     last=True, pcm16=False, rate=None, lengths=None):
+        """zvx_level_ex on host rows: the rows hold samples [in_origin, in_origin + len) of signals that start at sample 0 and, with
+        `last`, end with the row; the outputs [out_begin, out_begin + out_count) of the whole-signal leveler (out_count -1, which needs
+        last: to the end of each row's signal) -> (out [B][n] float32 / int16, gain_lo [B], gain_hi [B] float32, both over the emitted
+        samples only).  The window must carry leveler.reach(rate, window_ms, lookahead_ms) = (RL, RR) samples of support to the left and
+        to the right of the outputs, except at the signal's own ends (include/zvx.h)."""
+        x, n = self._rows(rows, lengths)
+        B, Nmax = x.shape
+        prm, flags = self._level_args(target, max_gain_db, window_ms, lookahead_ms, pcm16=pcm16)
+        out, cols = self._window_out(n, Nmax, in_origin, out_begin, out_count, pcm16)
+        lo, hi = np.zeros(B, np.float32), np.zeros(B, np.float32)
+        self._chk(self._lib.zvx_level_ex(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), out.shape[1], _ptr(lo), _ptr(hi),
+                                         flags, int(in_origin), int(out_begin), int(out_count), 1 if last else 0))
+        return out[:, :cols], lo, hi
+
+    def level_rows(self, rows, windows, target, max_gain_db=20.0, window_ms=3000.0, lookahead_ms=100.0, pcm16=False, rate=None, lengths=None):
+        """zvx_level_rows on host rows: level_window with a window per row (windows[b] = (in_origin, out_begin, out_count, last)) -> (a list
+        of B arrays, row b's emitted samples, gain_lo [B], gain_hi [B] float32, both over each row's emitted samples only), bit for bit
+        what level_window gives on each row alone."""
+        x, n = self._rows(rows, lengths)
+        B, Nmax = x.shape
+        prm, flags = self._level_args(target, max_gain_db, window_ms, lookahead_ms, pcm16=pcm16)
+        win, out, cnt = self._row_windows(windows, n, Nmax, pcm16)
+        lo, hi = np.zeros(B, np.float32), np.zeros(B, np.float32)
+        self._chk(self._lib.zvx_level_rows(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), out.shape[1], _ptr(lo),
+                                           _ptr(hi), flags, win))
+        return [out[b, :cnt[b]] for b in range(B)], lo, hi
 
     def resample_rows(self, rows, rate_in, rate_out, windows, pcm16=False, lengths=None):
         """zvx_resample_rows on host rows: resample_window with a window per row -- windows[b] = (in_origin, out_begin, out_count) or

@@ -2176,4 +2176,187 @@ void launch_limit_reduce(const LimitArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_limit_reduce, dim3(a.B), dim3(256), 0, s, a);
 }
 
+// ---------------------------------------------------------------- leveler (zvx_kernels.h, include/zvx.h: zvx_level)
+// k_loud_units' walk on a window: lane l of workgroup (blk, b) owns unit q = q_first + 64 blk + l of row b's SIGNAL and walks the signal's
+// samples [(q - 2) h, (q + 1) h) from zero state; the row holds the signal from in_origin on, so position s is x[s - in_origin], and a
+// position outside [0, n) of the row reads as 0.  The host admits a window only where that happens in front of sample 0 alone: the support
+// condition of include/zvx.h, and for a last window that begins inside its signal the check of the oldest needed unit itself
+// (zvx.hip, level_clamped_support_check: the clamp of the nodes to the last unit can move that unit to the left of what RL covers).
+// Same chunks, same 16-byte groups aligned as ADDRESSES with scalar edges, same fma chain; p = u / h goes to p[q - q_first].
+__global__ __launch_bounds__(64) void k_level_units(const LevelArgs a) {
+    __shared__ float st[64 * LOUD_LD];
+    const int b = blockIdx.y, lane = threadIdx.x;
+    const LevelRow r = a.rows[b];                            // (b is the same for every lane: the entry arrives through scalar loads)
+    const long q0 = r.q_first + (long)blockIdx.x * 64;
+    if (q0 > r.q_last) return;                               // (uniform over the workgroup)
+    const int n = r.n, h = a.h;
+    const long q = q0 + lane;
+    const float* xrow = r.x;
+    const int mis = (int)(((size_t)xrow >> 2) & 3);          // xrow - mis is 16-byte aligned
+    const int nact = (int)(r.q_last - q0 + 1 < 64 ? r.q_last - q0 + 1 : 64);
+    const bool active = lane < nact;
+    const long steps = 3L * h, nchunks = (steps + LOUD_T - 1) / LOUD_T;
+    const int off = (int)(((q - 2) * h - r.in_origin + mis) & 3);      // where the lane's span begins inside its first group (LOUD_T % 4 == 0: in every chunk)
+    float4 rg[LOUD_G];
+    auto fetch = [&](long c) {
+#pragma unroll
+        for (int k = 0; k < LOUD_G; k++) {
+            const int item = k * 64 + lane, seg = item / LOUD_G, g = item - seg * LOUD_G;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (seg < nact) {
+                const long sp = (q0 + seg - 2) * h + c * LOUD_T - r.in_origin;       // relative to the row from here on
+                const long pg = sp - ((sp + mis) & 3) + 4 * g;
+                if (pg >= 0 && pg + 4 <= n) v = *(const float4*)(xrow + pg);
+                else {
+                    if (pg >= 0 && pg < n) v.x = xrow[pg];
+                    if (pg + 1 >= 0 && pg + 1 < n) v.y = xrow[pg + 1];
+                    if (pg + 2 >= 0 && pg + 2 < n) v.z = xrow[pg + 2];
+                    if (pg + 3 >= 0 && pg + 3 < n) v.w = xrow[pg + 3];
+                }
+            }
+            rg[k] = v;
+        }
+    };
+    const LoudCoef k = a.k;
+    double s1 = 0.0, s2 = 0.0, r1 = 0.0, r2 = 0.0, acc = 0.0;
+    fetch(0);
+    for (long c = 0; c < nchunks; c++) {
+#pragma unroll
+        for (int kk = 0; kk < LOUD_G; kk++) {
+            const int item = kk * 64 + lane, seg = item / LOUD_G, g = item - seg * LOUD_G;
+            float* d = st + seg * LOUD_LD + 4 * g;
+            d[0] = rg[kk].x; d[1] = rg[kk].y; d[2] = rg[kk].z; d[3] = rg[kk].w;
+        }
+        __syncthreads();
+        if (c + 1 < nchunks) fetch(c + 1);
+        if (active) {
+            const float* my = st + lane * LOUD_LD + off;
+            const long t0 = c * LOUD_T;
+#pragma unroll 8
+            for (int t = 0; t < LOUD_T; t++) {
+                const double x = (double)my[t];
+                const double y1 = fma(k.b0, x, s1);
+                s1 = fma(-k.a1, y1, fma(k.b1, x, s2));
+                s2 = fma(-k.a2, y1, k.b2 * x);
+                const double y2 = y1 + r1;
+                r1 = fma(-k.c1, y2, fma(-2.0, y1, r2));
+                r2 = fma(-k.c2, y2, y1);
+                if (t0 + t >= 2L * h && t0 + t < steps) acc = fma(y2, y2, acc);
+            }
+        }
+        __syncthreads();
+    }
+    if (active) r.p[q - r.q_first] = acc / (double)h;
+}
+void launch_level_units(const LevelArgs& a, long units_max, hipStream_t s) {
+    if (a.B <= 0 || units_max <= 0) return;
+    hipLaunchKernelGGL(k_level_units, dim3((unsigned)((units_max + 63) / 64), a.B), dim3(64), 0, s, a);
+}
+
+__device__ __forceinline__ long level_clamp(long v, long hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
+// A tile is LEVEL_TILE emitted samples of one row, shifted left by the destination's misalignment so that its groups of 4 are 16-byte (int16:
+// 8-byte) stores.  Its samples lie in units qa .. qa + nT - 2 of the signal; node j is G[clamp(j + a - 1, 0, U - 1)] and G[m] sums the p of
+// units [max(0, m - S + 1), m] above the gate in ascending order: the p of all of the tile's nodes, at most S + nT - 1 units, are staged in
+// LDS once and thread t forms node qa + t.  Every position is a long; what indexes LDS or the row is a difference.
+__global__ __launch_bounds__(256) void k_level_apply(const LevelArgs a) {
+    __shared__ double ps[LEVEL_MAX_S + LEVEL_NODES];
+    __shared__ double Ts[LEVEL_NODES];
+    __shared__ float red[4];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const LevelRow r = a.rows[b];                            // (b is the same for every lane: the entry arrives through scalar loads)
+    const int cnt = r.cnt, h = a.h;
+    const float* x = r.x + r.off;                            // emitted sample e is x[e] * g32
+    float* of = (float*)r.out;
+    short* os = (short*)r.out;
+    const int omis = a.pcm16 ? (int)(((size_t)os >> 1) & 3) : (int)(((size_t)of >> 2) & 3);
+    const long v0 = (long)blockIdx.x * LEVEL_TILE;
+    const long e0 = v0 - omis > 0 ? v0 - omis : 0, e1 = v0 - omis + LEVEL_TILE < cnt ? v0 - omis + LEVEL_TILE : cnt;      // the tile's emitted samples [e0, e1)
+    float lo = INFINITY, hi = -INFINITY;
+    if (e0 < e1) {                                           // (uniform over the workgroup)
+        const long i0 = r.in_origin + r.off + e0;            // the signal position of emitted sample e0
+        const long qa = i0 / h;
+        const int ra = (int)(i0 - qa * h);
+        const int nT = (ra + (int)(e1 - e0 - 1)) / h + 2;    // nodes qa .. qa + nT - 1 (<= LEVEL_NODES: h >= LEVEL_MIN_H)
+        const bool none = r.U == 0;                          // a last window of a signal without a whole unit: every node is 1
+        const long um1 = r.U - 1;
+        const long mlo = level_clamp(qa + a.a - 1, um1), mhi = level_clamp(qa + nT - 1 + a.a - 1, um1);
+        const long k0 = mlo - a.S + 1 > 0 ? mlo - a.S + 1 : 0;
+        if (!none)
+            for (long kq = k0 + tid; kq <= mhi; kq += 256) ps[kq - k0] = r.p[kq - r.q_first];
+        __syncthreads();
+        if (tid < nT) {
+            double T = 1.0;
+            if (!none) {
+                const long m = level_clamp(qa + tid + a.a - 1, um1);
+                const long ka = m - a.S + 1 > 0 ? m - a.S + 1 : 0;
+                double sum = 0.0, c = 0.0;
+                for (long kq = ka; kq <= m; kq++) { const double p = ps[kq - k0]; if (p > a.gate) { sum += p; c += 1.0; } }
+                if (c > 0.0) {
+                    const double L = -0.691 + 10.0 * log10(sum / c);
+                    T = fmin(pow(10.0, (a.target - L) / 20.0), a.gmax);
+                }
+            }
+            Ts[tid] = T;
+        }
+        __syncthreads();
+        const double hd = (double)h;
+        auto gain = [&](long e) -> float {
+            const int d = ra + (int)(e - e0), dq = d / h, rem = d - dq * h;
+            const double t0 = Ts[dq], t1 = Ts[dq + 1];
+            return (float)fma(t1 - t0, (double)rem / hd, t0);
+        };
+        for (long v = v0 + 4 * tid; v < v0 + LEVEL_TILE; v += 1024) {
+            const long o = v - omis;
+            if (o >= cnt) break;
+            if (o >= 0 && o + 4 <= cnt) {
+                const float* src = x + o;
+                float4 t;
+                if (((size_t)src & 15) == 0) t = *(const float4*)src;
+                else { t.x = src[0]; t.y = src[1]; t.z = src[2]; t.w = src[3]; }
+                const float g0 = gain(o), g1 = gain(o + 1), g2 = gain(o + 2), g3 = gain(o + 3);
+                t.x *= g0; t.y *= g1; t.z *= g2; t.w *= g3;
+                if (a.pcm16) { short4 w; w.x = join_pcm(t.x); w.y = join_pcm(t.y); w.z = join_pcm(t.z); w.w = join_pcm(t.w); *(short4*)(os + o) = w; }
+                else *(float4*)(of + o) = t;
+                lo = fminf(fminf(lo, g0), fminf(fminf(g1, g2), g3));
+                hi = fmaxf(fmaxf(hi, g0), fmaxf(fmaxf(g1, g2), g3));
+            } else {
+                for (int e = 0; e < 4; e++) {
+                    if (o + e < 0 || o + e >= cnt) continue;
+                    const float g = gain(o + e);
+                    const float w = x[o + e] * g;
+                    if (a.pcm16) os[o + e] = join_pcm(w); else of[o + e] = w;
+                    lo = fminf(lo, g); hi = fmaxf(hi, g);
+                }
+            }
+        }
+    }
+    lo = -wg_max_f32(-lo, red);
+    hi = wg_max_f32(hi, red);
+    if (tid == 0) { a.part_lo[(long)b * a.ppitch + blockIdx.x] = lo; a.part_hi[(long)b * a.ppitch + blockIdx.x] = hi; }
+}
+void launch_level_apply(const LevelArgs& a, hipStream_t s) {
+    if (a.B <= 0) return;
+    hipLaunchKernelGGL(k_level_apply, dim3((unsigned)a.ppitch, a.B), dim3(256), 0, s, a);
+}
+
+__global__ __launch_bounds__(256) void k_level_reduce(const LevelArgs a) {
+    __shared__ float red[4];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    float lo = INFINITY, hi = -INFINITY;
+    for (int i = tid; i < a.ppitch; i += 256) {
+        lo = fminf(lo, a.part_lo[(long)b * a.ppitch + i]);
+        hi = fmaxf(hi, a.part_hi[(long)b * a.ppitch + i]);
+    }
+    lo = -wg_max_f32(-lo, red);
+    hi = wg_max_f32(hi, red);
+    if (tid == 0) {
+        const bool any = lo <= hi;                           // no emitted sample: 1 and 1
+        a.res[b] = any ? lo : 1.0f; a.res[a.B + b] = any ? hi : 1.0f;
+    }
+}
+void launch_level_reduce(const LevelArgs& a, hipStream_t s) {
+    if (a.B <= 0) return;
+    hipLaunchKernelGGL(k_level_reduce, dim3(a.B), dim3(256), 0, s, a);
+}
+
 }  // namespace zvx

@@ -2577,7 +2577,11 @@ void window_args_check(const char* who, const RowsWindow& w, int row) {
     if (w.last != 0 && w.last != 1) fail(ZVX_E_INVALID, "%s: %slast is %d (0 or 1)", who, at, w.last);
     if (w.out_count == -1 && !w.last) fail(ZVX_E_INVALID, "%s: %sout_count -1 needs last: the signal's end is not in the window", who, at);
 }
-int32_t window_count_row(const char* who, const RowsWindow& w, int32_t nsamples, int b, int64_t R) {
+// (Rr >= 0: the reach is asymmetric -- R to the left, Rr to the right, the leveler's RL / RR -- and the messages name the side's own)
+int32_t window_count_row(const char* who, const RowsWindow& w, int32_t nsamples, int b, int64_t R, int64_t Rr = -1) {
+    const char* ln = Rr >= 0 ? "RL" : "R";
+    const char* rn = Rr >= 0 ? "RR" : "R";
+    if (Rr < 0) Rr = R;
     const int64_t end_in = w.in_origin + nsamples;
     const int64_t n = w.out_count >= 0 ? w.out_count : std::max<int64_t>(0, end_in - w.out_begin);
     if (n > 0) {
@@ -2586,11 +2590,11 @@ int32_t window_count_row(const char* who, const RowsWindow& w, int32_t nsamples,
             fail(ZVX_E_INVALID, "%s: row %d: outputs [%lld, %lld) lie outside the window's samples [%lld, %lld)", who, b, (long long)w.out_begin,
                  (long long)end_out, (long long)w.in_origin, (long long)end_in);
         if (w.in_origin != 0 && w.out_begin - R < w.in_origin)
-            fail(ZVX_E_INVALID, "%s: row %d: the reach R = %lld needs %lld more samples in front of the window (in_origin %lld, out_begin %lld)", who, b,
-                 (long long)R, (long long)(w.in_origin - (w.out_begin - R)), (long long)w.in_origin, (long long)w.out_begin);
-        if (!w.last && end_out - 1 + R > end_in - 1)
-            fail(ZVX_E_INVALID, "%s: row %d: the reach R = %lld needs %lld more samples behind the window (outputs end at %lld, samples at %lld; or last)", who, b,
-                 (long long)R, (long long)(end_out + R - end_in), (long long)end_out, (long long)end_in);
+            fail(ZVX_E_INVALID, "%s: row %d: the reach %s = %lld needs %lld more samples in front of the window (in_origin %lld, out_begin %lld)", who, b,
+                 ln, (long long)R, (long long)(w.in_origin - (w.out_begin - R)), (long long)w.in_origin, (long long)w.out_begin);
+        if (!w.last && end_out - 1 + Rr > end_in - 1)
+            fail(ZVX_E_INVALID, "%s: row %d: the reach %s = %lld needs %lld more samples behind the window (outputs end at %lld, samples at %lld; or last)", who, b,
+                 rn, (long long)Rr, (long long)(end_out + Rr - end_in), (long long)end_out, (long long)end_in);
     }
     return (int32_t)n;                                       // n <= nsamples where n > 0
 }
@@ -2599,7 +2603,7 @@ struct WindowsIn { enum Form { WHOLE, ONE, PER_ROW } form = WHOLE; RowsWindow on
 // What those calls check of their windows, all before anything is queued -> the windows and per row the emitted count.  A call-wide window
 // is checked once and reported without a row number; the whole rows are their own window and out_rows_check has covered their stride.
 RowsWindows rows_windows_check(const char* who, const WindowsIn& win, const int32_t* nsamples, int B, int64_t R, const float* in, const void* out,
-                               int64_t out_stride) {
+                               int64_t out_stride, int64_t Rr = -1) {
     const bool per_row = win.form == WindowsIn::PER_ROW;
     if (per_row && !win.rows) fail(ZVX_E_INVALID, "%s: win is NULL", who);
     RowsWindows rw;
@@ -2611,7 +2615,7 @@ RowsWindows rows_windows_check(const char* who, const WindowsIn& win, const int3
             rw.w[(size_t)b] = RowsWindow{win.rows[b].in_origin, win.rows[b].out_begin, win.rows[b].out_count, win.rows[b].last};
             window_args_check(who, rw.w[(size_t)b], b);
         }
-        rw.cnt[(size_t)b] = window_count_row(who, rw.at(b), nsamples[b], b, R);
+        rw.cnt[(size_t)b] = window_count_row(who, rw.at(b), nsamples[b], b, R, Rr);
         rw.cnt_max = std::max<long>(rw.cnt_max, rw.cnt[(size_t)b]);
     }
     if (win.form == WindowsIn::WHOLE) return rw;
@@ -2711,6 +2715,128 @@ void do_limit(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamp
     for (int b = 0; b < B; b++) {
         if (peak_in) peak_in[b] = r_h[b];
         if (min_gain) min_gain[b] = r_h[B + b];
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
+// leveler (include/zvx.h: zvx_level, zvx_level_ex, zvx_level_rows)
+// ------------------------------------------------------------------------------------------------
+// the checks of the leveler's own parameters -> S and a, in units of 100 ms (on the host in double)
+struct LevelGeom { int h, S, a; int64_t RL, RR; };
+LevelGeom level_params_check(const char* who, int rate, const zvx_level_params* p) {
+    if (!std::isfinite(p->target_lufs) || p->target_lufs < -70.f || p->target_lufs > 0.f) fail(ZVX_E_INVALID, "%s: target_lufs must lie in [-70, 0]", who);
+    if (!std::isfinite(p->max_gain_db) || p->max_gain_db < 0.f) fail(ZVX_E_INVALID, "%s: max_gain_db must be finite and not negative", who);
+    if (!std::isfinite(p->window_ms) || p->window_ms < 0.f) fail(ZVX_E_INVALID, "%s: window_ms must be finite and not negative", who);
+    if (!std::isfinite(p->lookahead_ms) || p->lookahead_ms < 0.f) fail(ZVX_E_INVALID, "%s: lookahead_ms must be finite and not negative", who);
+    const double S = std::max(1.0, rint((double)p->window_ms / 100.0)), a = rint((double)p->lookahead_ms / 100.0);
+    if (S > (double)LEVEL_MAX_S) fail(ZVX_E_UNSUPPORTED, "%s: a window of %.0f units of 100 ms (at most %d)", who, S, LEVEL_MAX_S);
+    if (a > S) fail(ZVX_E_INVALID, "%s: the look-ahead of %.0f units exceeds the window of %.0f units (a <= S)", who, a, S);
+    LevelGeom g{};
+    g.h = (rate + 5) / 10; g.S = (int)S; g.a = (int)a;
+    g.RL = (int64_t)(g.S + 3 - g.a) * g.h - 1; g.RR = (int64_t)(g.a + 1) * g.h - 1;
+    return g;
+}
+
+// The units under the nodes of a row's emitted range (k_level_apply forms the same per tile): [first, last], last < first where none is
+// needed; U = the signal's whole units where the window is last (the clamp of the nodes), LEVEL_OPEN otherwise.
+struct LevelUnits { long first = 0, last = -1, U = LEVEL_OPEN; };
+LevelUnits level_units(const RowsWindow& w, int32_t n, int32_t cnt, const LevelGeom& g) {
+    LevelUnits u;
+    const int64_t h = g.h;
+    u.U = w.last ? (long)((w.in_origin + n) / h) : LEVEL_OPEN;
+    if (cnt > 0 && u.U > 0) {
+        auto clampu = [](int64_t v, int64_t hi) { return v < 0 ? (int64_t)0 : (v > hi ? hi : v); };
+        const int64_t q0 = w.out_begin / h, q1 = (w.out_begin + cnt - 1) / h;
+        const int64_t mlo = clampu(q0 + g.a - 1, u.U - 1), mhi = clampu(q1 + g.a, u.U - 1);
+        u.first = (long)std::max<int64_t>(0, mlo - g.S + 1); u.last = (long)mhi;
+    }
+    return u;
+}
+// The left support of a LAST window that begins inside its signal: where the outputs begin in the signal's last a units (or its tail) the
+// clamp to U - 1 moves the first node's window to the left of where RL assumes it, so the oldest needed unit is checked itself -- its
+// warm-up starts at (first - 2) h, which must lie inside the window.  (Without last, and wherever the clamp does not act, RL implies it.)
+void level_clamped_support_check(const char* who, const RowsWindows& rw, const int32_t* nsamples, int B, const LevelGeom& g) {
+    for (int b = 0; b < B; b++) {
+        const RowsWindow& w = rw.at(b);
+        if (!w.last || w.in_origin == 0) continue;
+        const LevelUnits u = level_units(w, nsamples[b], rw.cnt[(size_t)b], g);
+        if (u.last < u.first) continue;
+        const int64_t start = ((int64_t)u.first - 2) * g.h;
+        if (start < w.in_origin)
+            fail(ZVX_E_INVALID, "%s: row %d: the window is last and its first node is clamped to the signal's last unit %ld: unit %ld of its window needs %lld more samples "
+                 "in front of the window (in_origin %lld, out_begin %lld)", who, b, u.U - 1, u.first, (long long)(w.in_origin - std::max<int64_t>(start, 0)), (long long)w.in_origin,
+                 (long long)w.out_begin);
+    }
+}
+
+// The leveler over B rows with a window each, every caller's launches: ONE table upload, the unit, apply and reduce launches under one timed
+// group -> the device words res[b] = gain_lo, res[B + b] = gain_hi.  The caller has validated the rows (the support condition included:
+// it is what keeps every needed unit inside the row).
+const float* run_level_rows(zvx_ctx* c, const PostRow* rows, int B, int rate, const zvx_level_params* p, const LevelGeom& g, int pcm16) {
+    LevelArgs a{};
+    a.B = B; a.h = g.h; a.S = g.S; a.a = g.a; a.pcm16 = pcm16;
+    a.k = loud_coef(c, rate);
+    a.gate = pow(10.0, (-70.0 + 0.691) / 10.0);
+    a.target = (double)p->target_lufs; a.gmax = pow(10.0, (double)p->max_gain_db / 20.0);
+    std::vector<LevelRow> tab((size_t)B);
+    double n_sum = 0, cnt_sum = 0;
+    long cnt_max = 0, units_max = 0;
+    size_t units = 0;
+    for (int b = 0; b < B; b++) {
+        const PostRow& r = rows[b];
+        LevelRow& t = tab[(size_t)b];
+        t.x = r.in; t.out = r.out; t.p = nullptr;
+        t.in_origin = (long)r.w.in_origin;
+        t.n = r.n; t.off = r.cnt > 0 ? (int)(r.w.out_begin - r.w.in_origin) : 0; t.cnt = r.cnt; t.pad_ = 0;
+        const LevelUnits u = level_units(r.w, r.n, r.cnt, g);
+        t.U = u.U; t.q_first = u.first; t.q_last = u.last;
+        const long nu = t.q_last - t.q_first + 1;
+        units += (size_t)nu; units_max = std::max(units_max, nu);
+        cnt_max = std::max<long>(cnt_max, r.cnt); n_sum += r.n; cnt_sum += r.cnt;
+    }
+    double* pbuf = (double*)c->buf("lvl.p", std::max<size_t>(units, 1) * sizeof(double));
+    for (int b = 0; b < B; b++) {
+        LevelRow& t = tab[(size_t)b];
+        t.p = pbuf; pbuf += t.q_last - t.q_first + 1;
+    }
+    a.ppitch = (int)std::max(1L, (cnt_max + 3 + LEVEL_TILE - 1) / LEVEL_TILE);          // (+ 3: the address alignment shifts the groups by up to 3 samples)
+    a.part_lo = c->fbuf("lvl.part", (size_t)2 * B * a.ppitch);
+    a.part_hi = a.part_lo + (size_t)B * a.ppitch;
+    a.res = c->fbuf("lvl.res", (size_t)2 * B);
+    LevelRow* tab_d = (LevelRow*)c->buf("lvl.rows", (size_t)B * sizeof(LevelRow));
+    c->upload(tab_d, tab.data(), (size_t)B * sizeof(LevelRow));
+    a.rows = tab_d;
+    TagScope scope(c, "post.level");
+    c->timed(0.0, 4.0 * n_sum + (pcm16 ? 2.0 : 4.0) * cnt_sum, [&] {
+        launch_level_units(a, units_max, c->stream);
+        launch_level_apply(a, c->stream);
+        launch_level_reduce(a, c->stream);
+    });
+    return a.res;
+}
+
+// zvx_level, zvx_level_ex and zvx_level_rows: every check before anything is allocated, uploaded or queued
+void do_level(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_level_params* p,
+              void* out, int64_t out_stride, float* gain_lo, float* gain_hi, int flags, const WindowsIn& win = {}) {
+    if (!p) fail(ZVX_E_INVALID, "%s: params is NULL", who);
+    rows_check(who, in, nsamples, B, Nmax, 65535);
+    if (rate < 4000 || rate > 192000) fail(ZVX_E_INVALID, "%s: rate %d outside [4000, 192000]", who, rate);
+    flags_check(who, flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16);
+    out_rows_check(who, in, out, out_stride, Nmax, flags);
+    const LevelGeom g = level_params_check(who, rate, p);
+    const RowsWindows rw = rows_windows_check(who, win, nsamples, B, g.RL, in, out, out_stride, g.RR);
+    level_clamped_support_check(who, rw, nsamples, B, g);
+    RowsReturn ret(c, B, (size_t)B * 8, gain_lo || gain_hi, true, rw.cnt_max, flags);      // words: gain_lo [B], then gain_hi [B]
+    const float* x = rows_to_device(c, "lvl", in, B, Nmax, flags);
+    long out_bs = 0;
+    void* od = ret.out_rows("lvl.out", out, out_stride, &out_bs);
+    const std::vector<PostRow> rows = post_rows(x, Nmax, od, out_bs, ret.ss, nsamples, rw, B);
+    const float* res = run_level_rows(c, rows.data(), B, rate, p, g, (flags & ZVX_PCM16) ? 1 : 0);
+    const float* r_h = (const float*)ret.finish(res, out, out_stride, rw.cnt.data(), flags);
+    if (!r_h) return;
+    for (int b = 0; b < B; b++) {
+        if (gain_lo) gain_lo[b] = r_h[b];
+        if (gain_hi) gain_hi[b] = r_h[B + b];
     }
 }
 
@@ -3840,6 +3966,28 @@ zvx_status zvx_limit_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, 
         if (!params) fail(ZVX_E_INVALID, "zvx_limit_rows: params is NULL");
         const WindowsIn w{WindowsIn::PER_ROW, RowsWindow{}, win};
         do_limit(c, "zvx_limit_rows", in, nsamples, B, Nmax, rate, params, 0, out, out_stride, peak_in, min_gain, flags, w);
+    });
+}
+
+zvx_status zvx_level(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_level_params* params,
+                     void* out, int64_t out_stride, float* gain_lo, float* gain_hi, int flags) {
+    return guarded(c, [&] { do_level(c, "zvx_level", in, nsamples, B, Nmax, rate, params, out, out_stride, gain_lo, gain_hi, flags); });
+}
+
+zvx_status zvx_level_ex(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_level_params* params,
+                        void* out, int64_t out_stride, float* gain_lo, float* gain_hi, int flags,
+                        int64_t in_origin, int64_t out_begin, int64_t out_count, int last) {
+    return guarded(c, [&] {
+        const WindowsIn win{WindowsIn::ONE, RowsWindow{in_origin, out_begin, out_count, last}};
+        do_level(c, "zvx_level_ex", in, nsamples, B, Nmax, rate, params, out, out_stride, gain_lo, gain_hi, flags, win);
+    });
+}
+
+zvx_status zvx_level_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_level_params* params,
+                          void* out, int64_t out_stride, float* gain_lo, float* gain_hi, int flags, const zvx_row_window* win) {
+    return guarded(c, [&] {
+        const WindowsIn w{WindowsIn::PER_ROW, RowsWindow{}, win};
+        do_level(c, "zvx_level_rows", in, nsamples, B, Nmax, rate, params, out, out_stride, gain_lo, gain_hi, flags, w);
     });
 }
 

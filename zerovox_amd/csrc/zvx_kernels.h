@@ -246,6 +246,56 @@ bool launch_attention_f32(const AttnF32Args& a, hipStream_t stream, bool dry_run
 // (both attention launches are plain dispatches: the caller records its events around the call)
 
 // ------------------------------------------------------------------------------------------------
+// Leveler (ops.hip, next to the loudness kernels whose recurrence and staging it shares).  A section of its own: the launchers of the
+// section below are the registry of the kernel-level spec tests (tests/ops_ref.py); these three are checked through the C-ABI against
+// their float64 restatement (tests/level_ref.py, tests/test_level_gpu.py), as the other post-processing kernels are.
+// ------------------------------------------------------------------------------------------------
+// K-weighting (zvx_loudness, zvx_level): two biquads in transposed direct form II, double state.  Stage 1 b0..b2, a1, a2; stage 2 has b = [1, -2, 1].
+struct LoudCoef { double b0, b1, b2, a1, a2, c1, c2; };
+// Leveler (include/zvx.h, zvx_level): a gain curve from the gated short-term loudness of the S units up to and including a unit, a units
+// ahead, interpolated linearly between unit nodes.  `rows` is a device table with one LevelRow per row, uploaded by every call through the
+// context's pinned staging arena (zvx.hip, run_level_rows); every kernel reads rows[blockIdx.y] at its top and works from it alone, so
+// zvx_level, zvx_level_ex and zvx_level_rows run the same instructions.  A row holds samples [in_origin, in_origin + n) of its signal; the
+// unit grid is the SIGNAL's (unit q = samples [q h, (q + 1) h)).  Positions on the signal are 64-bit throughout; what indexes memory is
+// the position minus in_origin (samples) or minus q_first (units).  Nothing outside [0, n) of a row is read.
+constexpr int LEVEL_TILE = 4096;             // emitted samples per workgroup of launch_level_apply: 4 groups of 4 per thread
+constexpr int LEVEL_MAX_S = 600;             // the longest window, in units (include/zvx.h: ZVX_E_UNSUPPORTED beyond)
+constexpr int LEVEL_MIN_H = 400;             // h at the lowest rate (4000 Hz): a tile spans at most LEVEL_TILE / 400 + 2 units
+constexpr int LEVEL_NODES = LEVEL_TILE / LEVEL_MIN_H + 4;    // unit nodes a tile can touch (12 units incl. the alignment shift, + 1, rounded up)
+struct LevelRow {
+    const float* x; void* out; double* p;    // the row's samples; where emitted sample `off` goes (f32 or int16); p[q - q_first], the needed units
+    long in_origin;                          // the signal position of x[0]
+    long q_first, q_last;                    // the needed units [q_first, q_last] (q_last < q_first: none)
+    long U;                                  // the window is last: the signal's whole units (in_origin + n) / h, the clamp of the nodes;
+                                             // otherwise LEVEL_OPEN (the signal continues: nothing clamps on the right)
+    int n, off, cnt, pad_;                   // the row's length; the emitted range [off, off + cnt) of the row
+};
+constexpr long LEVEL_OPEN = 0x7fffffffffffffffL;
+struct LevelArgs {
+    const LevelRow* rows;                    // [B], on the device
+    int B;
+    int h, S, a;                             // samples per unit; window and look-ahead in units
+    LoudCoef k;
+    double gate;                             // 10^((-70 + 0.691) / 10): a unit counts where p > gate
+    double target, gmax;                     // target_lufs; 10^(max_gain_db / 20), computed on the host in double
+    int pcm16;
+    float* part_lo; float* part_hi; int ppitch;      // [b][tile]: min / max of g32 over the tile's emitted samples (+INF / -INF where it has none)
+    float* res;                              // launch_level_reduce: res[b] = gain_lo, res[B + b] = gain_hi (1 and 1 for an empty range)
+};
+// p of every needed unit: one LANE per unit, the recurrence of launch_loud_units (zero state two units early, the same fma chain, the same
+// staging of 16-byte groups aligned as ADDRESSES through LDS) over samples read relative to in_origin; zeros stand where the position lies
+// outside the row, which the host's checks (the support condition, and the oldest unit of a last window whose nodes are clamped) confine to
+// the front of sample 0.  grid.x covers units_max units.
+void launch_level_units(const LevelArgs& a, long units_max, hipStream_t s);
+// one tile of a row's emitted range: the p the tile's nodes need are staged in LDS, one thread per node forms its G (gated ascending sum,
+// log10 / pow in double), every sample takes g = fma(T[q + 1] - T[q], frac, T[q]), rounds it to f32 and multiplies once.  Groups of 4
+// aligned as ADDRESSES of the destination, 16-byte loads where the source address allows; a thread reads its samples before it writes them
+// and no other thread touches them: safe in place (off = 0).  grid.x = ppitch tiles over cnt_max.
+void launch_level_apply(const LevelArgs& a, hipStream_t s);
+// one workgroup per row over the tiles' partial results
+void launch_level_reduce(const LevelArgs& a, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------------
 // Small kernels (ops.hip).  T-typed pointers are void* + dtype.
 // ------------------------------------------------------------------------------------------------
 // single requests: InstanceNorm statistics + affine + activation of a 16-bit tensor (x and y both DT_BF16 or DT_F16) in ONE launch
@@ -432,8 +482,7 @@ struct StreamManyInteriorArgs { const StreamManyInterior* tab; const float* wav;
 void launch_stream_interiors_many(const StreamManyInteriorArgs& a, long cnt_max, hipStream_t s);
 // Integrated loudness (ITU-R BS.1770 / EBU R128) and gain of a batch's waveform rows (include/zvx.h, zvx_loudness / zvx_normalize): every
 // decision is made on the DEVICE, in double, in the power domain.
-// K-weighting: two biquads in transposed direct form II, double state.  Stage 1 b0..b2, a1, a2; stage 2 has b = [1, -2, 1].
-struct LoudCoef { double b0, b1, b2, a1, a2, c1, c2; };
+// K-weighting: struct LoudCoef, declared with the leveler above (it shares the coefficients).
 struct LoudArgs {
     const float* x; long x_bs; const int* nsamples; int B;
     int h;                                   // samples per 100 ms unit

@@ -9,6 +9,9 @@ sentence by sentence in batches and joins the sentences on the device; --wav-fil
 the device (zvx_normalize).  `--limiter` (with `--limiter-ms MS`) holds it under `--peak-db` with the true-peak look-ahead limiter
 (zvx_limit); the loudness gain is then no longer bounded by the peak.  `--denoise S` takes S times the vocoder's bias spectrum off the
 waveform on the device, directly behind the vocoder (zvx_denoise; 0.01 is the usual strength; its audible benefit is not measured here).
+`--level LUFS`: the utterance is STREAMED (ZeroVoxTTS.tts_stream) and levelled window by window towards a short-term loudness on the device
+(zvx_level_ex: an AGC, not the R128 normalisation of --loudness; its audible merit is not measured here); --denoise and, with --limiter,
+--peak-db apply to the stream as well, and the pieces are joined for the WAV file.
 """
 import argparse
 import os
@@ -42,8 +45,12 @@ def main():
     ap.add_argument("--limiter-ms", type=float, default=5.0, metavar="MS", help="smoothing window of the limiter's gain on either side of a peak")
     ap.add_argument("--denoise", type=float, default=None, metavar="S",
                     help="strength of the vocoder-bias denoiser on the device, e.g. 0.01 (default: off)")
+    ap.add_argument("--level", type=float, default=None, metavar="LUFS",
+                    help="stream the utterance and level it towards this short-term loudness on the device, e.g. -16 (default: off)")
     ap.add_argument("--long", action="store_true", help="long-form: split the text (or the file it names) into sentences and join them on the device")
     args = ap.parse_args()
+    if args.level is not None and (args.long or args.loudness is not None):
+        ap.error("--level streams one utterance: it goes with neither --long nor --loudness")
 
     modelcfg, synth = ZeroVoxTTS.load_model(args.model, args.meldec_model, infer_device=args.infer_device, precision=args.precision)
     if args.out_rate:
@@ -64,6 +71,20 @@ def main():
             wav_len = (wav.shape[0] if segments else 0) / sr
             print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, {len(segments)} sentences, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")
             if args.wav_filename and segments:
+                write_wav_to_file(wav, length=0, filename=args.wav_filename, sample_rate=sr, hop_length=modelcfg["audio"]["hop_size"], samples=len(wav))
+            if i > warmup:
+                rtf.append(wav_len / elapsed)
+            continue
+        if args.level is not None:
+            pieces = list(synth.tts_stream(args.text, spkemb, speed=args.speed, pitch_shift=args.pitch_shift, pitch_range=args.pitch_range,
+                                           energy_shift=args.energy_shift, energy_range=args.energy_range, level_lufs=args.level,
+                                           peak_db=args.peak_db if args.limiter else None, limiter_ms=args.limiter_ms,
+                                           denoise_strength=args.denoise))
+            wav = np.concatenate(pieces) if pieces else np.zeros(0, np.float32)
+            elapsed = time.time() - t0
+            wav_len = wav.shape[0] / sr
+            print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, {len(pieces)} pieces, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")
+            if args.wav_filename and len(wav):
                 write_wav_to_file(wav, length=0, filename=args.wav_filename, sample_rate=sr, hop_length=modelcfg["audio"]["hop_size"], samples=len(wav))
             if i > warmup:
                 rtf.append(wav_len / elapsed)

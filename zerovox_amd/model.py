@@ -14,6 +14,7 @@ import yaml
 
 from . import _lib, config as zcfg, pack, weights as zw
 from .denoiser import DenoisePlanner
+from .leveler import LevelPlanner, reach as level_reach
 from .limiter import LimitPlanner, window_samples
 from .resample import stream_resample
 from .stream import stream_windows
@@ -222,7 +223,7 @@ class ZeroVox:
     # each side makes a chunk's interior identical to the same samples of a whole-utterance pass.
     STREAM_HALO = 16
 
-    def vocode_stream(self, mel, chunk_frames=64, halo=STREAM_HALO, chunks_per_call=1, limiter=None, denoise=None, resident=False):
+    def vocode_stream(self, mel, chunk_frames=64, halo=STREAM_HALO, chunks_per_call=1, limiter=None, denoise=None, resident=False, level=None):
         """Chunked vocoding for first-audio latency: mel [L, n_mels] -> yields waveform chunks (np.float32) that
         concatenate to ``vocode_mel(mel)``.  Every chunk is vocoded with ``halo`` extra frames on each side and only its
         interior is kept; ``chunks_per_call`` chunks ride in one launch sequence as independent batch rows.
@@ -236,11 +237,18 @@ class ZeroVox:
         chunks pass through the windowed denoiser (zerovox_amd.denoiser, zvx_denoise_ex) with ``denoise_bias`` and concatenate bit for
         bit to zvx_denoise of the whole native stream; the denoised stream runs denoiser.reach(fft_size) = fft_size - 1 samples behind
         the vocoder.  Denoiser first, then the limiter, then the conversion -- the order of ``inference_ex``; the delays add up.
+        level: None, or Context.level_window keywords (target, and optionally max_gain_db, window_ms, lookahead_ms): the native-rate
+        chunks pass through the windowed leveler (zerovox_amd.leveler, zvx_level_ex) and concatenate bit for bit to zvx_level of the
+        whole stream that reaches it; the levelled stream runs RR = leveler.reach(...)[1] samples behind that stage's input (4409
+        samples, 200 ms, at 22.05 kHz with the defaults).  The chain is denoise, then level, then limit, then the conversion.  Host-planned
+        streams only: sessions have no level stage yet (resident=True with level raises ValueError).
         resident: False (the default: the host-planned stream above), or True: the same keywords drive a stream session of the library
         (include/zvx.h, zvx_stream_open) -- the mel is uploaded once, the samples stay on the device between the steps and every piece
         costs one wait.  The pieces concatenate to the same bits; where they are cut may differ.  mel None (resident only): the mel the
         context holds after decode."""
         if resident:
+            if level is not None:
+                raise ValueError("vocode_stream: stream sessions have no level stage yet (use resident=False with level=)")
             yield from self._vocode_stream_resident(mel, chunk_frames, halo, chunks_per_call, limiter, denoise)
             return
         ctx = self._ctx
@@ -248,10 +256,16 @@ class ZeroVox:
         convert = rate > 0 and rate != native
         if denoise is not None:
             denoise = dict(denoise, bias=self.denoise_bias)          # (first use runs the vocoder: before this stream's first chunk)
-        chunks = self._vocode_stream_native(mel, chunk_frames, halo, chunks_per_call, convert or limiter is not None or denoise is not None)
+        chunks = self._vocode_stream_native(mel, chunk_frames, halo, chunks_per_call,
+                                            convert or limiter is not None or denoise is not None or level is not None)
         if denoise is not None:
             chunks = stream_windows(chunks, DenoisePlanner(ctx.get_int("fft_size")), lambda x, o, b, n, last: ctx.denoise_window(
                 [x], in_origin=o, out_begin=b, out_count=n, last=last, **denoise)[0].copy())
+        if level is not None:
+            level = dict(dict(window_ms=3000.0, lookahead_ms=100.0), **level)
+            plan = LevelPlanner(*level_reach(native, level["window_ms"], level["lookahead_ms"]))
+            chunks = stream_windows(chunks, plan, lambda x, o, b, n, last: ctx.level_window(
+                [x], in_origin=o, out_begin=b, out_count=n, last=last, rate=native, **level)[0][0].copy())
         if limiter is not None:
             plan = LimitPlanner(window_samples(native, limiter["window_ms"]), limiter["oversample"])
             chunks = stream_windows(chunks, plan, lambda x, o, b, n, last: ctx.limit_window(

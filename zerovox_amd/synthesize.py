@@ -266,7 +266,7 @@ class ZeroVoxTTS:
 
     def tts_stream(self, text: str, spkemb, chunk_frames=64, chunks_per_call=1, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0,
                    energy_shift=0.0, energy_range=1.0, loudness=None, limiter=False, peak_db=None, limiter_ms=5.0, denoise=None,
-                   denoise_strength=None, resident=False):
+                   denoise_strength=None, resident=False, level_lufs=None, level_window_ms=3000.0, level_lookahead_ms=100.0):
         """Streaming variant of ``tts`` (not in the reference): encoder + mel decoder run once, the vocoder
         runs chunk by chunk (16-frame halo), yielding float32 waveform pieces that concatenate to ``tts(text, spkemb)[0]``
         up to the reference's `_min_mel_len` zero-padding of short utterances.  A stream cannot be loudness-normalised: the gain is not
@@ -284,12 +284,37 @@ class ZeroVoxTTS:
         kHz).  With ``peak_db`` as well the stream is limit(denoise(stream)) and runs n_fft - 1 + limiter.reach(W, 4) samples behind;
         an ``output_rate`` converts last.  That delay is why the strength is asked for by this name: ``denoise=...``, the
         whole-utterance keyword of tts and tts_long, still raises ValueError and points here.
+        level_lufs: None (the default: the level the model gives), or the short-term loudness in LUFS the stream is steered towards by
+        the windowed leveler (include/zvx.h, zvx_level_ex; zerovox_amd.leveler): a gain curve from the gated loudness of the last
+        level_window_ms, looking level_lookahead_ms ahead, at most +20 dB.  It is an AGC, not the R128 normalisation of ``loudness=``.
+        The pieces concatenate bit for bit to zvx_level of the stream that reaches the stage; the chain is denoise, level, limit,
+        conversion, and the levelled stream runs (a + 1) h - 1 samples behind the stage's input (4409: 200 ms at 22.05 kHz with the
+        defaults).  Host-planned streams only: with ``resident=True`` it raises ValueError (sessions have no level stage yet).
         resident: False (the default: the stream is planned on the host), or True: a stream session of the library runs it (include/zvx.h,
         zvx_stream_open; ZeroVox.vocode_stream(resident=True)) -- the decoder's mel never leaves the device and every piece costs one
         wait.  The concatenation is the same to the bit; the pieces may be cut elsewhere."""
         prosody, lim, den = self._stream_keywords(speed, pitch_shift, pitch_range, energy_shift, energy_range, loudness, limiter, peak_db,
                                                   limiter_ms, denoise, denoise_strength)
-        return self._tts_stream(text, spkemb, chunk_frames, chunks_per_call, prosody, lim, den, resident)
+        lvl = self._level(level_lufs, level_window_ms, level_lookahead_ms)
+        if lvl is not None and resident:
+            raise ValueError("tts_stream: stream sessions have no level stage yet: level_lufs needs resident=False")
+        return self._tts_stream(text, spkemb, chunk_frames, chunks_per_call, prosody, lim, den, resident, lvl)
+
+    @staticmethod
+    def _level(level_lufs, window_ms, lookahead_ms):
+        """the level keywords as Context.level_window keywords, or None (nothing is levelled); checked without a device"""
+        if level_lufs is None:
+            return None
+        from .leveler import MAX_UNITS, lookahead_units, window_units
+        t, w, a = float(level_lufs), float(window_ms), float(lookahead_ms)
+        if not np.isfinite(t) or not -70.0 <= t <= 0.0:
+            raise ValueError(f"level_lufs must be None or lie in [-70, 0] LUFS, not {level_lufs!r}")
+        if not (np.isfinite(w) and w >= 0 and np.isfinite(a) and a >= 0):
+            raise ValueError(f"level_window_ms / level_lookahead_ms must be finite and not negative, not {window_ms!r} / {lookahead_ms!r}")
+        if window_units(w) > MAX_UNITS or lookahead_units(a) > window_units(w):
+            raise ValueError(f"level_window_ms {window_ms!r} / level_lookahead_ms {lookahead_ms!r}: at most {MAX_UNITS} units of 100 ms, and the "
+                             "look-ahead no longer than the window")
+        return dict(target=t, window_ms=w, lookahead_ms=a)
 
     def _stream_keywords(self, speed, pitch_shift, pitch_range, energy_shift, energy_range, loudness, limiter, peak_db, limiter_ms, denoise,
                          denoise_strength):
@@ -299,7 +324,8 @@ class ZeroVoxTTS:
                              "n_fft - 1 samples behind the vocoder); denoise= is the whole-utterance keyword of tts and tts_long")
         den = self._denoise(denoise_strength)
         if loudness is not None:
-            raise ValueError("tts_stream cannot normalise loudness: the gain is unknown until the last chunk (use tts or tts_long)")
+            raise ValueError("tts_stream cannot normalise loudness: the gain is unknown until the last chunk (use tts or tts_long; "
+                             "level_lufs=<LUFS> levels a stream by its short-term loudness instead)")
         if limiter:
             raise ValueError("tts_stream takes its ceiling by name: pass peak_db=<dBFS> (the stream is then limited window by window, "
                              "2 W + 11 samples behind the vocoder); limiter=True is the whole-utterance switch of tts and tts_long")
@@ -312,7 +338,7 @@ class ZeroVoxTTS:
 
     def tts_stream_many(self, texts, spkembs, chunk_frames=64, chunks_per_call=1, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0,
                         energy_shift=0.0, energy_range=1.0, loudness=None, limiter=False, peak_db=None, limiter_ms=5.0, denoise=None,
-                        denoise_strength=None, max_frames=2048):
+                        denoise_strength=None, max_frames=2048, level_lufs=None, level_window_ms=3000.0, level_lookahead_ms=100.0):
         """Many texts streamed together -> yields (index, piece), non-empty float32 pieces only; the stream keywords are those of
         ``tts_stream`` and apply to every text.  spkembs: one embedding per text ([B, hidden]), or one for all.  The front end runs as ONE
         batch (``synthesize_batch(want_mel=True)``, at most max_frames mel frames per text), one stream session is opened on every mel,
@@ -321,6 +347,8 @@ class ZeroVoxTTS:
         on the mel the batch made for text i (``last_stream_mels[i]``).  A text without phonemes yields nothing."""
         prosody, lim, den = self._stream_keywords(speed, pitch_shift, pitch_range, energy_shift, energy_range, loudness, limiter, peak_db,
                                                   limiter_ms, denoise, denoise_strength)
+        if level_lufs is not None:
+            raise ValueError("tts_stream_many: stream sessions have no level stage yet: level_lufs is tts_stream's (resident=False)")
         return self._tts_stream_many(list(texts), spkembs, chunk_frames, chunks_per_call, prosody, lim, den, int(max_frames))
 
     def _tts_stream_many(self, texts, spkembs, chunk_frames, chunks_per_call, prosody, limiter, denoise, max_frames):
@@ -348,7 +376,7 @@ class ZeroVoxTTS:
                                                        denoise=denoise):
             yield keep[b], piece
 
-    def _tts_stream(self, text, spkemb, chunk_frames, chunks_per_call, prosody, limiter=None, denoise=None, resident=False):
+    def _tts_stream(self, text, spkemb, chunk_frames, chunks_per_call, prosody, limiter=None, denoise=None, resident=False, level=None):
         text = text.strip()
         phone_ids, punct_ids = self.text2phonemeids(text)
         if not phone_ids:
@@ -369,7 +397,7 @@ class ZeroVoxTTS:
             return
         mel = ctx.decode(1, ml)[0, :ml]
         yield from self._model.vocode_stream(mel, chunk_frames=chunk_frames, chunks_per_call=chunks_per_call, limiter=limiter,
-                                             denoise=denoise)
+                                             denoise=denoise, level=level)
 
     def tts_long(self, text: str, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20, fade_ms=5, max_batch=32, max_frames=2048, pcm16=False,
                  durations=None, max_chars=200, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0,
