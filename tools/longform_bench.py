@@ -2,6 +2,7 @@
 StyleTTS decoder + HiFi-GAN V1, bf16, synthetic weights.
    python tools/longform_bench.py [out.json] [--loudness [LUFS]]
    python tools/longform_bench.py --limit [out.txt]
+   python tools/longform_bench.py --report [out.txt]
 Per paragraph, host wall time (median of 20 after 3 warm-ups, same process, same device) of
   (a) one tts() per sentence, mels.trim_silence and np.concatenate on the host -- what the API offered before tts_long, and
   (b) tts_long (batched synthesis into one device buffer, zvx_join on the device, one copy out),
@@ -15,7 +16,12 @@ device samples at 22050 Hz, W = 110 (5 ms), os = 4 and os = 1, on Gaussian rows 
 every tile) and of sigma 0.05 (none: every tile takes the copy path); beside it the apply pass of zvx_normalize on the same rows -- the
 "post.loudness" group of zvx_normalize minus that of zvx_loudness, the same bytes read and written once -- and the float64 NumPy
 reference of tests/limit_ref.py on the same rows on this host.  Medians of 5 after 3 warm-ups; written as text (default
-profiles/limiter_bench.txt)."""
+profiles/limiter_bench.txt).
+--report [out.txt]: ONLY the programme loudness report: per paragraph the host wall time of tts_long(text, spk) and of the same call with
+report=True, plain and under loudness=-23 (medians of 10 after 3 warm-ups, same process); then, on the joined waveform as ONE device row,
+the "post.loudness" launch group and the host wall time of zvx_loudness_stats beside those of zvx_loudness, the yardstick that makes the
+first two of its four launches, and of zvx_true_peak, the report's other call (medians of 5 after 3 warm-ups).  Written as text (default
+profiles/loudness_stats.txt)."""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -27,6 +33,7 @@ ap = argparse.ArgumentParser()
 ap.add_argument("out", nargs="?", default=None)
 ap.add_argument("--loudness", type=float, nargs="?", const=-23.0, default=None, metavar="LUFS")
 ap.add_argument("--limit", action="store_true")
+ap.add_argument("--report", action="store_true")
 args = ap.parse_args()
 HBM_BYTES_PER_S = 8e12
 _, synth = ZeroVoxTTS.load_model("synthetic:styletts", "synthetic:v1", infer_device="cuda:0", precision="bf16")
@@ -120,6 +127,56 @@ def median_ms(f, n=20, warm=3):
 if args.limit:
     from zerovox_amd._lib import ZVX_DEVICE_IN as _DEVICE_IN
     limiter_bench(args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "limiter_bench.txt"))
+    sys.exit(0)
+
+
+def report_bench(out_path):
+    lines = [f"Programme loudness report (zvx_loudness_stats + zvx_true_peak) on paragraphs of N sentences x 64 phonemes, StyleTTS decoder + HiFi-GAN V1 bf16,",
+             f"synthetic weights, {rate} Hz.  tts_long: host wall time, median of 10 after 3 warm-ups.  Calls alone: the joined waveform as ONE device row,",
+             "median of 5 after 3 warm-ups; group = hipEvent time of the \"post.loudness\" launch group, wall = host wall time of the call.", ""]
+    for N in (8, 32, 128):
+        sents = [sentence(i) for i in range(N)]
+        text = " ".join(sents)
+        plain = median_ms(lambda: synth.tts_long(text, spk), n=10)
+        rep = median_ms(lambda: synth.tts_long(text, spk, report=True), n=10)
+        loud = median_ms(lambda: synth.tts_long(text, spk, loudness=-23.0), n=10)
+        loud_rep = median_ms(lambda: synth.tts_long(text, spk, loudness=-23.0, report=True), n=10)
+        wav, _ = synth.tts_long(text, spk, loudness=-23.0, report=True)
+        r = synth.last_report
+        n = len(wav)
+        lens = np.array([n], np.int32)
+        buf = ctx.dev_alloc(n * 4)
+        try:
+            ctx.dev_from_host(buf, wav)
+
+            def alone(call, tag):
+                group, wall = [], []
+                ctx.set_int("profile", 2)
+                for _ in range(8):
+                    ctx.reset_stats()
+                    t0 = time.perf_counter(); call(); wall.append((time.perf_counter() - t0) * 1e3)
+                    group.append({t["name"]: t for t in ctx.tag_stats()}[tag]["ms"])
+                ctx.set_int("profile", 0)
+                return float(np.median(group[3:])), float(np.median(wall[3:]))
+
+            st = alone(lambda: ctx.loudness_stats_device(buf, lens, n, rate=rate), "post.loudness")
+            ld = alone(lambda: ctx._chk(ctx._lib.zvx_loudness(ctx._h, buf, lens.ctypes.data, 1, n, rate, None, None, _DEVICE_IN)), "post.loudness")
+            tp = alone(lambda: ctx.true_peak_device(buf, lens, n, rate=rate), "post.limit")
+        finally:
+            ctx.dev_free(buf)
+        lines += [f"{N} sentences, {n / rate:.2f} s of audio, {n // ((rate + 5) // 10) - 29} short-term windows: {r}",
+                  f"  tts_long {plain:.3f} ms, with report {rep:.3f} ms ({(rep / plain - 1.0) * 100.0:+.2f} %); under loudness=-23 {loud:.3f} ms, "
+                  f"with report {loud_rep:.3f} ms ({(loud_rep / loud - 1.0) * 100.0:+.2f} %)",
+                  f"  zvx_loudness_stats: group {st[0]:.4f} ms, wall {st[1]:.4f} ms; zvx_loudness: group {ld[0]:.4f} ms, wall {ld[1]:.4f} ms; "
+                  f"zvx_true_peak (4x): group {tp[0]:.4f} ms, wall {tp[1]:.4f} ms", ""]
+        print("\n".join(lines[-4:]), flush=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines))
+
+
+if args.report:
+    from zerovox_amd._lib import ZVX_DEVICE_IN as _DEVICE_IN
+    report_bench(args.out or os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "profiles", "loudness_stats.txt"))
     sys.exit(0)
 res = {"workload": "paragraphs of N sentences x 64 phonemes, StyleTTS decoder + HiFi-GAN V1 bf16, synthetic weights, predicted durations, "
                    "host waveform out; ms = host wall time, median of 20 after 3 warm-ups", "paragraphs": []}

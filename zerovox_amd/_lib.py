@@ -27,10 +27,15 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_encode_ex", "zvx_synthesize_ex", "zvx_resample", "zvx_resample_ex", "zvx_trim_bounds", "zvx_join",
            "zvx_loudness", "zvx_normalize", "zvx_true_peak", "zvx_limit", "zvx_spkemb_wav", "zvx_limit_ex", "zvx_denoise_bias", "zvx_denoise",
            "zvx_denoise_ex", "zvx_stream_open", "zvx_stream_next", "zvx_stream_info", "zvx_stream_close", "zvx_stream_next_many",
-           "zvx_denoise_rows", "zvx_limit_rows", "zvx_resample_rows", "zvx_level", "zvx_level_ex", "zvx_level_rows")
+           "zvx_denoise_rows", "zvx_limit_rows", "zvx_resample_rows", "zvx_level", "zvx_level_ex", "zvx_level_rows", "zvx_loudness_stats")
 ZVX_STREAM_MANY_MAX_SESSIONS, ZVX_STREAM_MANY_MAX_ROWS = 64, 256
 ZVX_COMM_ID_BYTES = 128
 ZVX_LOUD_PER_ROW, ZVX_LOUD_COMMON = 0, 1
+# columns of zvx_loudness_stats' stats[B][ZVX_LS_COUNT], and the keys Context.loudness_stats gives them
+(ZVX_LS_INTEGRATED, ZVX_LS_MOMENTARY_MAX, ZVX_LS_SHORT_MAX, ZVX_LS_LRA, ZVX_LS_LRA_LOW, ZVX_LS_LRA_HIGH, ZVX_LS_SHORT_GATED, ZVX_LS_PEAK,
+ ZVX_LS_COUNT) = range(9)
+LOUDNESS_STATS_KEYS = ("integrated", "max_momentary", "max_short_term", "lra", "lra_low", "lra_high", "short_gated", "peak")
+LOUDNESS_STATS_MAX_UNITS = 65536                     # the longest row zvx_loudness_stats takes, in 100 ms units
 LIMIT_TILE = 1024                                    # samples per workgroup of both limiter kernels (csrc/zvx_kernels.h, LIMIT_TILE)
 LIMIT_MAX_W = 4096                                   # the longest window, in samples (LIMIT_MAX_W)
 LIMIT_ENV_REACH = 11                                 # samples the oversampled envelope reads to either side (LIMIT_ENV_REACH; limiter.reach)
@@ -154,6 +159,7 @@ def load():
     lib.zvx_join.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(JoinParams), vp, C.c_int64, C.POINTER(C.c_int64), vp, vp, vp, C.c_int]
     lib.zvx_loudness.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int]
     lib.zvx_normalize.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(LoudnessParams), vp, C.c_int64, vp, vp, vp, C.c_int]
+    lib.zvx_loudness_stats.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int64, C.c_int]
     lib.zvx_true_peak.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int]
     lib.zvx_limit.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(LimitParams), vp, C.c_int64, vp, vp, C.c_int]
     lib.zvx_limit_ex.argtypes = lib.zvx_limit.argtypes + [C.c_int64, C.c_int64, C.c_int64, C.c_int]
@@ -445,6 +451,38 @@ class Context:
         self._chk(self._lib.zvx_loudness(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), _ptr(lufs), _ptr(peak), 0))
         return lufs, peak
 
+    def loudness_stats(self, rows, rate=None, lengths=None, curves=False):
+        """zvx_loudness_stats: the programme loudness report of every row -> a dict of [B] float64 arrays: integrated (LUFS, bit for bit
+        loudness()'s), max_momentary, max_short_term (LUFS; -inf where the row has no 400 ms block / 3 s window), lra (LU, EBU Tech 3342),
+        lra_low, lra_high (LUFS: the 10th and 95th percentile of the gated short-term windows), short_gated (their number) and peak (linear
+        sample peak).  curves: also momentary and short_term, lists of B float64 arrays: the LUFS curves at a 100 ms step, n / h - 3 and
+        n / h - 29 entries.  rows: a list of 1-D float waveforms, or a padded 2-D array + lengths; rate None: the model's sampling rate."""
+        x, n = self._rows(rows, lengths)
+        return self._loudness_stats(_ptr(x), n, x.shape[1], rate, 0, curves)
+
+    def loudness_stats_device(self, ptr, lengths, Nmax, rate=None, curves=False):
+        """zvx_loudness_stats on device rows [B][Nmax] f32 at `ptr` (ZVX_DEVICE_IN; they may be the output of a synthesize / normalize_device /
+        limit_device call queued just before: stream order is the fence) -> as loudness_stats()."""
+        return self._loudness_stats(C.c_void_p(int(ptr)), _i32(lengths), int(Nmax), rate, ZVX_DEVICE_IN, curves)
+
+    def _loudness_stats(self, xptr, n, Nmax, rate, flags, curves, momentary=None, short_term=None):
+        """momentary / short_term: [B][stride] float64 arrays of the caller's to receive the curves instead of fresh ones"""
+        B, rate = len(n), self._rate(rate)
+        h = (rate + 5) // 10
+        stats = np.zeros((B, ZVX_LS_COUNT), np.float64)
+        if curves and momentary is None:
+            momentary = np.full((B, max(1, Nmax // h - 3)), -np.inf, np.float64)
+        if curves and short_term is None:
+            short_term = np.full((B, max(1, Nmax // h - 3)), -np.inf, np.float64)
+        stride = momentary.shape[1] if momentary is not None else short_term.shape[1] if short_term is not None else 0
+        self._chk(self._lib.zvx_loudness_stats(self._h, xptr, _ptr(n), B, Nmax, rate, _ptr(stats), _ptr(momentary), _ptr(short_term), stride, flags))
+        res = {k: stats[:, i].copy() for i, k in enumerate(LOUDNESS_STATS_KEYS)}
+        if curves:
+            U = n.astype(np.int64) // h
+            res["momentary"] = [momentary[b, :max(U[b] - 3, 0)] for b in range(B)]
+            res["short_term"] = [short_term[b, :max(U[b] - 29, 0)] for b in range(B)]
+        return res
+
     def normalize(self, rows, target, *, peak_ceiling=0.891, max_gain_db=20.0, common=False, pcm16=False, rate=None, lengths=None):
         """zvx_normalize on host rows: every row (common: all rows as one programme, one gain) brought to `target` LUFS, the gain bounded by
         max_gain_db and by the linear sample-peak ceiling (<= 0: none) -> (rows_out [B][Nmax] float32 / int16 -- row b holds its samples
@@ -478,6 +516,14 @@ class Context:
         B, Nmax = x.shape
         tp = np.zeros(B, np.float32)
         self._chk(self._lib.zvx_true_peak(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), int(oversample), _ptr(tp), 0))
+        return tp
+
+    def true_peak_device(self, ptr, lengths, Nmax, oversample=4, rate=None):
+        """zvx_true_peak on device rows [B][Nmax] f32 at `ptr` (ZVX_DEVICE_IN; stream order is the fence) -> [B] float32"""
+        n = _i32(lengths)
+        tp = np.zeros(len(n), np.float32)
+        self._chk(self._lib.zvx_true_peak(self._h, C.c_void_p(int(ptr)), _ptr(n), len(n), int(Nmax), self._rate(rate), int(oversample), _ptr(tp),
+                                          ZVX_DEVICE_IN))
         return tp
 
     def limit(self, rows, ceiling, window_ms=5.0, oversample=4, pcm16=False, rate=None, lengths=None):

@@ -1936,6 +1936,110 @@ void launch_loud_common(const LoudArgs& a, hipStream_t s) {
     hipLaunchKernelGGL(k_loud_common, dim3(1), dim3(256), 0, s, a);
 }
 
+// ---- programme loudness report (zvx_kernels.h, include/zvx.h: zvx_loudness_stats)
+__device__ __forceinline__ double loud_lu(double p) { return p > 0.0 ? -0.691 + 10.0 * log10(p) : -INFINITY; }
+// maximum over the workgroup's 256 threads (exact: any order)
+__device__ __forceinline__ double wg_max_f64(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+    __syncthreads();                                          // the previous reduction's readers are done
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
+}
+// does short-term window power s pass both LRA gates
+__device__ __forceinline__ bool loud_lra_gated(double s, double abs_gate, double thr) { return s > abs_gate && s > thr; }
+// One workgroup per row.  Thread t owns the blocks and windows j with j % 256 == t in every pass, so it reads back from `win` only what it
+// wrote itself.  A tile of 256 windows reads 285 units, staged in LDS once; a window's 30 units are summed in ascending index.
+__global__ __launch_bounds__(256) void k_loud_windows(const LoudStatsArgs a) {
+    __shared__ double red[4];
+    __shared__ double us[256 + LOUD_ST_UNITS - 1];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const long U = a.nsamples[b] / a.h, nb = U >= 4 ? U - 3 : 0, W = U >= LOUD_ST_UNITS ? U - (LOUD_ST_UNITS - 1) : 0;
+    const double* u = a.unit + (long)b * a.upitch;
+    double* win = a.win + (long)b * a.wpitch;
+    const double four_h = 4.0 * (double)a.h, st_h = (double)LOUD_ST_UNITS * (double)a.h;
+    double zmax = 0.0, smax = 0.0;                            // powers: never negative
+    for (long j0 = 0; j0 < nb; j0 += 256) {                  // (nb >= W: the blocks' tiles cover the windows')
+        __syncthreads();                                      // the previous tile's readers are done
+        for (int i = tid; i < 256 + LOUD_ST_UNITS - 1; i += 256) us[i] = j0 + i < U ? u[j0 + i] : 0.0;
+        __syncthreads();
+        const long j = j0 + tid;
+        if (j < nb) {
+            const double z = loud_block(us, tid, four_h);
+            zmax = fmax(zmax, z);
+            if (a.mom) a.mom[(long)b * a.cpitch + j] = loud_lu(z);
+        }
+        if (j < W) {
+            double acc = us[tid];
+#pragma unroll
+            for (int k = 1; k < LOUD_ST_UNITS; k++) acc += us[tid + k];
+            const double s = acc / st_h;
+            win[j] = s;
+            smax = fmax(smax, s);
+            if (a.sht) a.sht[(long)b * a.cpitch + j] = loud_lu(s);
+        }
+    }
+    double sum = 0.0, cnt = 0.0;
+    for (long j = tid; j < W; j += 256) { const double s = win[j]; if (s > a.abs_gate) { sum += s; cnt += 1.0; } }
+    const double S1 = wg_sum_f64(sum, red), C1 = wg_sum_f64(cnt, red);
+    double thr = 0.0, ng = 0.0;
+    if (C1 > 0.0) {                                          // (uniform over the workgroup)
+        thr = 0.01 * (S1 / C1);
+        cnt = 0.0;
+        for (long j = tid; j < W; j += 256) if (loud_lra_gated(win[j], a.abs_gate, thr)) cnt += 1.0;
+        ng = wg_sum_f64(cnt, red);
+    }
+    zmax = wg_max_f64(zmax, red);
+    smax = wg_max_f64(smax, red);
+    if (tid == 0) {
+        double* r = a.res + (long)b * LOUD_RES_WORDS;
+        const long n = (long)ng;
+        r[LOUD_RES_MOM_MAX] = loud_lu(zmax); r[LOUD_RES_SHORT_MAX] = loud_lu(smax);
+        r[LOUD_RES_REL_THR] = thr; r[LOUD_RES_GATED] = ng;
+        r[LOUD_RES_RANK_LO] = (double)(((n - 1) * 10 + 50) / 100); r[LOUD_RES_RANK_HI] = (double)(((n - 1) * 95 + 50) / 100);
+        r[LOUD_RES_POW_LO] = 0.0; r[LOUD_RES_POW_HI] = 0.0;
+    }
+}
+void launch_loud_windows(const LoudStatsArgs& a, hipStream_t s) {
+    if (a.B <= 0) return;
+    hipLaunchKernelGGL(k_loud_windows, dim3(a.B), dim3(256), 0, s, a);
+}
+// Thread j owns window j.  Where it is gated it counts the gated windows i with s[i] < s[j], or s[i] == s[j] and i < j: its rank in an
+// ascending sort whose ties break by index, so exactly one thread holds each rank.  The row's windows pass through LDS in tiles of 256, an
+// ungated one as +INFINITY, which precedes nothing; every lane reads the same word of the tile at a time.
+__global__ __launch_bounds__(256) void k_loud_rank(const LoudStatsArgs a) {
+    __shared__ double tile[256];
+    const int b = blockIdx.y, tid = threadIdx.x;
+    const long U = a.nsamples[b] / a.h, W = U >= LOUD_ST_UNITS ? U - (LOUD_ST_UNITS - 1) : 0;
+    double* r = a.res + (long)b * LOUD_RES_WORDS;
+    if ((long)blockIdx.x * 256 >= W || !(r[LOUD_RES_GATED] > 0.0)) return;       // (uniform over the workgroup)
+    const double thr = r[LOUD_RES_REL_THR];
+    const int lo = (int)r[LOUD_RES_RANK_LO], hi = (int)r[LOUD_RES_RANK_HI];
+    const double* win = a.win + (long)b * a.wpitch;
+    const long j = (long)blockIdx.x * 256 + tid;
+    const double sj = j < W ? win[j] : 0.0;
+    const bool mine = j < W && loud_lra_gated(sj, a.abs_gate, thr);
+    int cnt = 0;
+    for (long i0 = 0; i0 < W; i0 += 256) {
+        __syncthreads();                                      // the previous tile's readers are done
+        double v = INFINITY;
+        if (i0 + tid < W) { const double s = win[i0 + tid]; if (loud_lra_gated(s, a.abs_gate, thr)) v = s; }
+        tile[tid] = v;
+        __syncthreads();
+        if (mine) {
+#pragma unroll 8
+            for (int k = 0; k < 256; k++) { const double s = tile[k]; cnt += (s < sj || (s == sj && i0 + k < j)) ? 1 : 0; }
+        }
+    }
+    if (mine && cnt == lo) r[LOUD_RES_POW_LO] = sj;
+    if (mine && cnt == hi) r[LOUD_RES_POW_HI] = sj;
+}
+void launch_loud_rank(const LoudStatsArgs& a, long w_max, hipStream_t s) {
+    if (a.B <= 0 || w_max <= 0) return;
+    hipLaunchKernelGGL(k_loud_rank, dim3((unsigned)((w_max + 255) / 256), a.B), dim3(256), 0, s, a);
+}
+
 constexpr int LOUD_TILE = 4096;              // samples per workgroup: 4 groups of 4 per thread
 __global__ __launch_bounds__(256) void k_loud_apply(const LoudApplyArgs a) {
     const int b = blockIdx.y, tid = threadIdx.x;

@@ -2497,12 +2497,39 @@ const LoudCoef& loud_coef(zvx_ctx* c, int rate) {
     return c->loud_coefs[rate] = k;
 }
 
+// The measuring half of zvx_loudness / zvx_normalize / zvx_loudness_stats: the rows on the device, the unit and result buffers, and the
+// arguments of launch_loud_units / launch_loud_gates (measure only: the caller of zvx_normalize adds its gain parameters).
+// Result words in one block: lufs [B] double, then peak [B], gain [B] float; behind them row_sum / row_cnt.
+struct LoudMeasure { LoudArgs a; long units_max; char* res; size_t res_bytes; };
+LoudMeasure loud_measure(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, long n_max, int flags) {
+    LoudMeasure m{};
+    LoudArgs& a = m.a;
+    m.res_bytes = (size_t)B * 16;
+    a.h = (rate + 5) / 10;
+    a.k = loud_coef(c, rate);
+    const long units_max = m.units_max = std::max(n_max / a.h, 1L);
+    a.upitch = units_max; a.ppitch = (int)((units_max + 63) / 64);
+    const DevRows rows = stage_rows(c, "loud", in, nsamples, B, Nmax, flags);
+    a.x = rows.x; a.x_bs = Nmax; a.nsamples = rows.len; a.B = B;
+    a.unit = (double*)c->buf("loud.unit", (size_t)B * units_max * sizeof(double));
+    a.part_peak = c->fbuf("loud.ppeak", (size_t)B * a.ppitch);
+    char* res = m.res = (char*)c->buf("loud.res", m.res_bytes + (size_t)B * 16);
+    a.lufs = (double*)res; a.peak = (float*)(res + (size_t)B * 8); a.gain = a.peak + B;
+    a.row_sum = (double*)(res + m.res_bytes); a.row_cnt = (long*)(res + m.res_bytes + (size_t)B * 8);
+    a.abs_gate = pow(10.0, (-70.0 + 0.691) / 10.0);
+    a.want_gain = 0;
+    return m;
+}
+void loud_rate_check(const char* who, int rate) {
+    if (rate < 4000 || rate > 192000) fail(ZVX_E_INVALID, "%s: rate %d outside [4000, 192000]", who, rate);
+}
+
 // zvx_loudness (p == nullptr: measure only) and zvx_normalize
 void do_loudness(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_loudness_params* p,
                  void* out, int64_t out_stride, double* lufs, float* peak, float* gain, int flags) {
     const bool norm = p != nullptr;
     const RowsInfo r = rows_check(who, in, nsamples, B, Nmax, 65535);
-    if (rate < 4000 || rate > 192000) fail(ZVX_E_INVALID, "%s: rate %d outside [4000, 192000]", who, rate);
+    loud_rate_check(who, rate);
     flags_check(who, flags, norm ? (ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16) : ZVX_DEVICE_IN);
     if (norm) {
         out_rows_check(who, in, out, out_stride, Nmax, flags);
@@ -2511,41 +2538,92 @@ void do_loudness(zvx_ctx* c, const char* who, const float* in, const int32_t* ns
         if (std::isnan(p->peak_ceiling)) fail(ZVX_E_INVALID, "%s: peak_ceiling is NaN", who);
         if (p->mode != ZVX_LOUD_PER_ROW && p->mode != ZVX_LOUD_COMMON) fail(ZVX_E_INVALID, "%s: unknown mode %d", who, p->mode);
     }
-    // result words in one block: lufs [B] double, then peak [B], gain [B] float
-    const size_t res_bytes = (size_t)B * 16;
-    RowsReturn ret(c, B, res_bytes, lufs || peak || gain, norm, r.n_max, flags);
-    LoudArgs a{};
-    a.h = (rate + 5) / 10;
-    a.k = loud_coef(c, rate);
-    const long units_max = std::max(r.n_max / a.h, 1L);
-    a.upitch = units_max; a.ppitch = (int)((units_max + 63) / 64);
-    const DevRows rows = stage_rows(c, "loud", in, nsamples, B, Nmax, flags);
-    a.x = rows.x; a.x_bs = Nmax; a.nsamples = rows.len; a.B = B;
-    a.unit = (double*)c->buf("loud.unit", (size_t)B * units_max * sizeof(double));
-    a.part_peak = c->fbuf("loud.ppeak", (size_t)B * a.ppitch);
-    char* res = (char*)c->buf("loud.res", res_bytes + (size_t)B * 16);
-    a.lufs = (double*)res; a.peak = (float*)(res + (size_t)B * 8); a.gain = a.peak + B;
-    a.row_sum = (double*)(res + res_bytes); a.row_cnt = (long*)(res + res_bytes + (size_t)B * 8);
-    a.abs_gate = pow(10.0, (-70.0 + 0.691) / 10.0);
+    RowsReturn ret(c, B, (size_t)B * 16, lufs || peak || gain, norm, r.n_max, flags);
+    LoudMeasure m = loud_measure(c, in, nsamples, B, Nmax, rate, r.n_max, flags);
+    LoudArgs& a = m.a;
     a.want_gain = norm ? 1 : 0;
     if (norm) { a.target = (double)p->target_lufs; a.max_gain_db = (double)p->max_gain_db; a.ceiling = (double)p->peak_ceiling; }
     LoudApplyArgs w{};
-    w.x = rows.x; w.x_bs = Nmax; w.nsamples = a.nsamples; w.B = B; w.gain = a.gain; w.pcm16 = (flags & ZVX_PCM16) ? 1 : 0;
+    w.x = a.x; w.x_bs = Nmax; w.nsamples = a.nsamples; w.B = B; w.gain = a.gain; w.pcm16 = (flags & ZVX_PCM16) ? 1 : 0;
     w.out = ret.out_rows("loud.out", out, out_stride, &w.out_bs);
     TagScope scope(c, "post.loudness");
     c->timed(0.0, 4.0 * r.n_sum + (norm ? (4.0 + (double)ret.ss) * r.n_sum : 0.0), [&] {
-        launch_loud_units(a, units_max, c->stream);
+        launch_loud_units(a, m.units_max, c->stream);
         launch_loud_gates(a, c->stream);
         if (norm && p->mode == ZVX_LOUD_COMMON) launch_loud_common(a, c->stream);
         if (norm) launch_loud_apply(w, r.n_max, c->stream);
     });
-    const char* words = ret.finish(res, out, out_stride, nsamples, flags);
+    const char* words = ret.finish(m.res, out, out_stride, nsamples, flags);
     if (!words) return;
     const double* l_h = (const double*)words; const float* p_h = (const float*)(words + (size_t)B * 8); const float* g_h = p_h + B;
     for (int b = 0; b < B; b++) {
         if (lufs) lufs[b] = l_h[b];
         if (peak) peak[b] = p_h[b];
         if (gain) gain[b] = g_h[b];
+    }
+}
+
+// zvx_loudness_stats: zvx_loudness's two launches, unchanged, then the short-term windows with their gates and the rank selection; the
+// result words, the per-row report words and the curves come to pinned host memory behind the call's one wait.
+constexpr long LOUD_STATS_MAX_UNITS = 65536;
+void run_loudness_stats(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, double* stats, double* momentary,
+                        double* short_term, int64_t curve_stride, int flags) {
+    const char* who = "zvx_loudness_stats";
+    const RowsInfo r = rows_check(who, in, nsamples, B, Nmax, 65535);
+    loud_rate_check(who, rate);
+    flags_check(who, flags, ZVX_DEVICE_IN);
+    if (!stats) fail(ZVX_E_INVALID, "%s: stats is NULL", who);
+    const int h = (rate + 5) / 10;
+    const bool curves = momentary || short_term;
+    if (curves && curve_stride < std::max<int64_t>(1, (int64_t)(Nmax / h) - 3))
+        fail(ZVX_E_INVALID, "%s: curve_stride %lld is smaller than max(1, Nmax / h - 3) = %lld", who, (long long)curve_stride,
+             (long long)std::max<int64_t>(1, (int64_t)(Nmax / h) - 3));
+    for (int b = 0; b < B; b++)
+        if (nsamples[b] / h > LOUD_STATS_MAX_UNITS)
+            fail(ZVX_E_UNSUPPORTED, "%s: row %d has %d units of %d samples (at most %ld per row)", who, b, nsamples[b] / h, h, LOUD_STATS_MAX_UNITS);
+    const long units_max = std::max(r.n_max / h, 1L);
+    const long cp = std::max(units_max - 3, 1L), w_max = std::max(units_max - (LOUD_ST_UNITS - 1), 0L);
+    // pinned: the result words of zvx_loudness, the report words, then the two curves where asked for
+    const size_t words_pad = ((size_t)B * 16 + 255) & ~(size_t)255, rep_bytes = (size_t)B * LOUD_RES_WORDS * sizeof(double);
+    const size_t rep_pad = (rep_bytes + 255) & ~(size_t)255, curve_bytes = (size_t)B * cp * sizeof(double);
+    char* host = (char*)c->join_pinned(words_pad + rep_pad + (momentary ? curve_bytes : 0) + (short_term ? curve_bytes : 0));
+    LoudMeasure m = loud_measure(c, in, nsamples, B, Nmax, rate, r.n_max, flags);
+    LoudStatsArgs s{};
+    s.unit = m.a.unit; s.upitch = m.a.upitch; s.nsamples = m.a.nsamples; s.B = B; s.h = h; s.abs_gate = m.a.abs_gate;
+    s.wpitch = std::max(w_max, 1L); s.cpitch = cp;
+    s.win = (double*)c->buf("loud.win", (size_t)B * s.wpitch * sizeof(double));
+    s.mom = momentary ? (double*)c->buf("loud.mom", curve_bytes) : nullptr;
+    s.sht = short_term ? (double*)c->buf("loud.sht", curve_bytes) : nullptr;
+    s.res = (double*)c->buf("loud.rep", rep_bytes);
+    TagScope scope(c, "post.loudness");
+    c->timed(0.0, 4.0 * r.n_sum, [&] {
+        launch_loud_units(m.a, m.units_max, c->stream);
+        launch_loud_gates(m.a, c->stream);
+        launch_loud_windows(s, c->stream);
+        launch_loud_rank(s, w_max, c->stream);
+    });
+    char* mom_h = host + words_pad + rep_pad; char* sht_h = mom_h + (momentary ? curve_bytes : 0);
+    HIPCHK(hipMemcpyAsync(host, m.res, (size_t)B * 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(host + words_pad, s.res, rep_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (momentary) HIPCHK(hipMemcpyAsync(mom_h, s.mom, curve_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (short_term) HIPCHK(hipMemcpyAsync(sht_h, s.sht, curve_bytes, hipMemcpyDeviceToHost, c->stream));
+    c->sync();                                               // the call's one wait
+    const double* l_h = (const double*)host; const float* p_h = (const float*)(host + (size_t)B * 8);
+    const double* rep = (const double*)(host + words_pad);
+    auto lu = [](double p) { return p > 0.0 ? -0.691 + 10.0 * log10(p) : -INFINITY; };
+    for (int b = 0; b < B; b++) {
+        const double* w = rep + (size_t)b * LOUD_RES_WORDS;
+        double* o = stats + (size_t)b * ZVX_LS_COUNT;
+        const bool any = w[LOUD_RES_GATED] > 0.0;
+        o[ZVX_LS_INTEGRATED] = l_h[b]; o[ZVX_LS_PEAK] = (double)p_h[b];
+        o[ZVX_LS_MOMENTARY_MAX] = w[LOUD_RES_MOM_MAX]; o[ZVX_LS_SHORT_MAX] = w[LOUD_RES_SHORT_MAX];
+        o[ZVX_LS_LRA] = any ? 10.0 * log10(w[LOUD_RES_POW_HI] / w[LOUD_RES_POW_LO]) : 0.0;
+        o[ZVX_LS_LRA_LOW] = any ? lu(w[LOUD_RES_POW_LO]) : -INFINITY; o[ZVX_LS_LRA_HIGH] = any ? lu(w[LOUD_RES_POW_HI]) : -INFINITY;
+        o[ZVX_LS_SHORT_GATED] = w[LOUD_RES_GATED];
+        const long U = nsamples[b] / h;
+        if (momentary && U >= 4) memcpy(momentary + (size_t)b * curve_stride, mom_h + (size_t)b * cp * sizeof(double), (size_t)(U - 3) * sizeof(double));
+        if (short_term && U >= LOUD_ST_UNITS)
+            memcpy(short_term + (size_t)b * curve_stride, sht_h + (size_t)b * cp * sizeof(double), (size_t)(U - (LOUD_ST_UNITS - 1)) * sizeof(double));
     }
 }
 
@@ -3910,6 +3988,10 @@ zvx_status zvx_normalize(zvx_ctx* c, const float* in, const int32_t* nsamples, i
         if (!params) fail(ZVX_E_INVALID, "zvx_normalize: params is NULL");
         do_loudness(c, "zvx_normalize", in, nsamples, B, Nmax, rate, params, out, out_stride, lufs, peak, gain, flags);
     });
+}
+zvx_status zvx_loudness_stats(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, double* stats, double* momentary,
+                              double* short_term, int64_t curve_stride, int flags) {
+    return guarded(c, [&] { run_loudness_stats(c, in, nsamples, B, Nmax, rate, stats, momentary, short_term, curve_stride, flags); });
 }
 
 zvx_status zvx_true_peak(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, int oversample, float* tpeak, int flags) {

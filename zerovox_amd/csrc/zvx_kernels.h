@@ -296,6 +296,33 @@ void launch_level_apply(const LevelArgs& a, hipStream_t s);
 void launch_level_reduce(const LevelArgs& a, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
+// Programme loudness report (ops.hip, behind the loudness kernels whose unit powers it reads).  A section of its own, as the leveler's:
+// its two launchers are checked through the C-ABI against their float64 restatement (tests/loudness_stats_ref.py,
+// tests/test_loudness_stats_gpu.py), as the other post-processing kernels are.
+// ------------------------------------------------------------------------------------------------
+// include/zvx.h, zvx_loudness_stats: momentary and short-term loudness and the loudness range of EBU Tech 3342 from the unit powers
+// launch_loud_units left, LoudArgs (below) describes.  Row b has U = nsamples[b] / h units, U - 3 blocks and W = U - 29 short-term windows.
+constexpr int LOUD_ST_UNITS = 30;            // units of a short-term window: 3 s
+enum { LOUD_RES_MOM_MAX = 0, LOUD_RES_SHORT_MAX, LOUD_RES_REL_THR, LOUD_RES_GATED, LOUD_RES_RANK_LO, LOUD_RES_RANK_HI, LOUD_RES_POW_LO,
+       LOUD_RES_POW_HI, LOUD_RES_WORDS };
+struct LoudStatsArgs {
+    const double* unit; long upitch; const int* nsamples; int B;     // LoudArgs' units, lengths and rows
+    int h;
+    double abs_gate;                         // LoudArgs' constant
+    double* win; long wpitch;                // win[b][j]: the power s[j] of short-term window j < W
+    double* mom; double* sht; long cpitch;   // the LUFS curves M[j], j < U - 3, and S[j], j < W, [b][cpitch]; NULL: not asked for
+    // res[b][LOUD_RES_WORDS]: max M and max S in LUFS (-INFINITY without one), the relative gate 0.01 Gamma as a power, n_g and the two
+    // nearest-rank indices as whole doubles, the powers of those ranks (0 where n_g == 0)
+    double* res;
+};
+// one workgroup per row: s[j] into win, the curves where asked for, the two maxima, both LRA gates in the fixed order of wg_sum_f64 ->
+// res[b][0 .. 5], and zeros into the two powers
+void launch_loud_windows(const LoudStatsArgs& a, hipStream_t s);
+// selection without a sort, grid (ceil(w_max / 256), B): thread j counts the gated windows that precede its own in (power, index) order,
+// streaming win[b] through LDS tiles; the one thread whose count is a target rank stores its power.  No atomics, no workgroup that waits.
+void launch_loud_rank(const LoudStatsArgs& a, long w_max, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------------
 // Small kernels (ops.hip).  T-typed pointers are void* + dtype.
 // ------------------------------------------------------------------------------------------------
 // single requests: InstanceNorm statistics + affine + activation of a 16-bit tensor (x and y both DT_BF16 or DT_F16) in ONE launch
@@ -503,6 +530,7 @@ void launch_loud_units(const LoudArgs& a, long units_max, hipStream_t s);
 void launch_loud_gates(const LoudArgs& a, hipStream_t s);
 // ZVX_LOUD_COMMON, one workgroup: both gates over the blocks of all rows, the maximum of the peaks, one gain written to every gain[b]
 void launch_loud_common(const LoudArgs& a, hipStream_t s);
+// The programme loudness report's two launches (launch_loud_windows, launch_loud_rank) stand in a section of their own, behind the leveler.
 // out[b][i] = x[b][i] * gain[b] for i < nsamples[b], ONE f32 multiply; f32 rows, or int16 by the resampler's rule with pcm16.  Groups of 4
 // aligned as ADDRESSES of the destination; a thread reads its group before it writes it and no other thread touches it: safe in place.
 struct LoudApplyArgs {

@@ -12,6 +12,8 @@ waveform on the device, directly behind the vocoder (zvx_denoise; 0.01 is the us
 `--level LUFS`: the utterance is STREAMED (ZeroVoxTTS.tts_stream) and levelled window by window towards a short-term loudness on the device
 (zvx_level_ex: an AGC, not the R128 normalisation of --loudness; its audible merit is not measured here); --denoise and, with --limiter,
 --peak-db apply to the stream as well, and the pieces are joined for the WAV file.
+`--report`: the finished waveform is measured as delivered, on the device (zvx_loudness_stats, zvx_true_peak): integrated loudness, loudness
+range, maximum momentary and short-term loudness, sample and true peak are printed, and with --loudness whether it meets that target.
 """
 import argparse
 import os
@@ -48,6 +50,7 @@ def main():
     ap.add_argument("--level", type=float, default=None, metavar="LUFS",
                     help="stream the utterance and level it towards this short-term loudness on the device, e.g. -16 (default: off)")
     ap.add_argument("--long", action="store_true", help="long-form: split the text (or the file it names) into sentences and join them on the device")
+    ap.add_argument("--report", action="store_true", help="measure the finished waveform on the device and print its programme loudness report")
     args = ap.parse_args()
     if args.level is not None and (args.long or args.loudness is not None):
         ap.error("--level streams one utterance: it goes with neither --long nor --loudness")
@@ -60,18 +63,26 @@ def main():
     refmel = np.random.default_rng(0).standard_normal((args.refmel_frames, modelcfg["audio"]["num_mels"])).astype(np.float32)
     spkemb = synth.speaker_embed_from_mel(refmel)
     rtf, warmup = [], 10
+
+    def print_report(rep):
+        print(f"loudness report: {rep}")
+        if args.loudness is not None:
+            print(f"  meets {args.loudness:g} LUFS +- 0.5 LU, true peak <= {args.peak_db:g} dBTP: {rep.meets(args.loudness, max_true_peak_db=args.peak_db)}")
     text = open(args.text, encoding="utf-8").read() if (args.long and os.path.isfile(args.text)) else args.text
     for i in range(args.iter):
         t0 = time.time()
         if args.long:
             wav, segments = synth.tts_long(text, spkemb, speed=args.speed, pitch_shift=args.pitch_shift, pitch_range=args.pitch_range,
                                            energy_shift=args.energy_shift, energy_range=args.energy_range, loudness=args.loudness,
-                                           peak_db=args.peak_db, limiter=args.limiter, limiter_ms=args.limiter_ms, denoise=args.denoise)
+                                           peak_db=args.peak_db, limiter=args.limiter, limiter_ms=args.limiter_ms, denoise=args.denoise,
+                                           report=args.report)
             elapsed = time.time() - t0
             wav_len = (wav.shape[0] if segments else 0) / sr
             print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, {len(segments)} sentences, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")
             if args.wav_filename and segments:
                 write_wav_to_file(wav, length=0, filename=args.wav_filename, sample_rate=sr, hop_length=modelcfg["audio"]["hop_size"], samples=len(wav))
+            if args.report and segments:
+                print_report(synth.last_report)
             if i > warmup:
                 rtf.append(wav_len / elapsed)
             continue
@@ -86,18 +97,23 @@ def main():
             print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, {len(pieces)} pieces, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")
             if args.wav_filename and len(wav):
                 write_wav_to_file(wav, length=0, filename=args.wav_filename, sample_rate=sr, hop_length=modelcfg["audio"]["hop_size"], samples=len(wav))
+            if args.report and len(wav):                             # (a stream has no buffer left to measure: the joined pieces are)
+                print_report(synth.loudness_report(wav, sr))
             if i > warmup:
                 rtf.append(wav_len / elapsed)
             continue
         wav, phoneme, length = synth.tts(args.text, spkemb, speed=args.speed, pitch_shift=args.pitch_shift, pitch_range=args.pitch_range,
                                          energy_shift=args.energy_shift, energy_range=args.energy_range, loudness=args.loudness,
-                                         peak_db=args.peak_db, limiter=args.limiter, limiter_ms=args.limiter_ms, denoise=args.denoise)
+                                         peak_db=args.peak_db, limiter=args.limiter, limiter_ms=args.limiter_ms, denoise=args.denoise,
+                                         report=args.report)
         elapsed = time.time() - t0
         wav_len = wav.shape[0] / sr
         print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")
         if args.wav_filename:
             write_wav_to_file(wav, length=length, filename=args.wav_filename, sample_rate=sr, hop_length=modelcfg["audio"]["hop_size"],
                               samples=len(wav))
+        if args.report and length:
+            print_report(synth.last_report)
         if i > warmup:
             rtf.append(wav_len / elapsed)
     if rtf:

@@ -77,7 +77,7 @@ def split_sentences(text, max_chars=MAX_CHARS):
 
 def synthesize_long(tts, text, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20, fade_ms=5, max_batch=32, max_frames=2048, pcm16=False,
                     durations=None, max_chars=MAX_CHARS, prosody=None, loudness=None, peak_db=-1.0, loudness_mode="paragraph",
-                    limiter=False, limiter_ms=5.0, denoise=None):
+                    limiter=False, limiter_ms=5.0, denoise=None, report=False):
     """The body of ZeroVoxTTS.tts_long (see there).  prosody: Prosody.create keywords applied to every sentence, or None.  denoise: None or
     Context.denoise_device keywords (strength, floor)."""
     from . import _lib
@@ -144,7 +144,18 @@ def synthesize_long(tts, text, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20,
             lufs, gain = [float(v) for v in lufs], [float(v) for v in gain]
         if lim:                                                  # likewise, behind the gain: which then has no peak ceiling
             _, min_gain = ctx.limit_device(buf, lengths, stride, rate=native, **lim)
-        if out_rate == native:
+        if out_rate == native and report and not pcm16:          # the joined row stays on the device until it is measured
+            cap = int(lengths.sum()) + int(sum(gaps))
+            joined = ctx.dev_alloc(max(cap, 1) * 4)
+            try:
+                total, pos, begin, ln = ctx.join_device(buf, lengths, stride, gaps, out_device_ptr=joined, out_capacity=cap, **kw)
+                tts.model.loudness_report_device(joined, total, native)
+                wav = ctx.dev_to_host(joined, (total,), np.float32) if total else np.zeros(0, np.float32)
+            finally:
+                ctx.dev_free(joined)
+            start = [int(p) for p in pos]
+            count = [int(v) for v in ln]
+        elif out_rate == native:
             wav, pos, begin, ln = ctx.join_device(buf, lengths, stride, gaps, pcm16=pcm16, **kw)
             start = [int(p) for p in pos]
             count = [int(v) for v in ln]
@@ -163,6 +174,8 @@ def synthesize_long(tts, text, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20,
             ctx.sync()                                           # queued launches still write the buffer
         finally:
             ctx.dev_free(buf)
+    if report and (out_rate != native or pcm16):                 # converted or int16: the waveform is measured as it arrived
+        tts.loudness_report(wav, out_rate)
     segments = [dict(text=items[i][0], start=start[i], samples=count[i], mel_len=int(mel_len[i]), trim=int(begin[i]), durations=durs[i])
                 for i in range(N)]
     if loudness is not None:

@@ -16,6 +16,7 @@ from . import _lib, config as zcfg, pack, weights as zw
 from .denoiser import DenoisePlanner
 from .leveler import LevelPlanner, reach as level_reach
 from .limiter import LimitPlanner, window_samples
+from .report import LoudnessReport
 from .resample import stream_resample
 from .stream import stream_windows
 
@@ -111,6 +112,7 @@ class ZeroVox:
         self._min_mel_len = 689                         # model.py:254 -- stateful, see inference_ex
         self.last_loudness = None                       # dict(lufs, peak, gain) of the last inference_ex(..., loudness=...) call
         self.last_limit = None                          # dict(peak_in, min_gain) of the last inference_ex(..., limiter=...) call
+        self.last_report = None                         # report.LoudnessReport of the last call that asked for one (report=True)
         self._denoise_bias = None                       # zvx_denoise_bias of the main context, computed on first use (denoise_bias)
         self.hidden = self._ctx.hidden
 
@@ -147,6 +149,21 @@ class ZeroVox:
         self._denoise_bias = None
         return self.denoise_bias
 
+    def loudness_report(self, wav, rate=None):
+        """the programme loudness report of one finished waveform on the host (zvx_loudness_stats + zvx_true_peak, 4x) at `rate` Hz (None:
+        the output rate) -> report.LoudnessReport, also kept as ``last_report``"""
+        rate = self.output_rate if rate is None else int(rate)
+        row = [np.asarray(wav, np.float32).reshape(-1)]
+        self.last_report = LoudnessReport.from_stats(self._ctx.loudness_stats(row, rate=rate), self._ctx.true_peak(row, rate=rate)[0])
+        return self.last_report
+
+    def loudness_report_device(self, ptr, n, rate):
+        """likewise for n f32 samples at `ptr` on the device, behind whatever was queued on them: nothing but the figures comes to the host"""
+        ctx = self._ctx
+        self.last_report = LoudnessReport.from_stats(ctx.loudness_stats_device(ptr, [n], max(n, 1), rate=rate),
+                                                     ctx.true_peak_device(ptr, [n], max(n, 1), rate=rate)[0])
+        return self.last_report
+
     def _spkemb(self, x):
         """ResNetSE34V2.forward: x [B, Tr, 80] -> [B, 1, hidden] (ResNetSE34V2.py:176-212)."""
         x = np.asarray(x, np.float32)
@@ -154,14 +171,16 @@ class ZeroVox:
         return self._ctx.spkemb(x, lens)[:, None, :]
 
     def inference_ex(self, x, style_embed, normalize_before=True, force_duration=False, prosody=None, loudness=None, limiter=None,
-                     denoise=None):
+                     denoise=None, report=False):
         """model.py:308-347.  x = {"phoneme" [1,T], "puncts" [1,T], "duration" [1,T]|None}; returns
         (wav[:mel_len*hop], mel_len, log_duration [1,T], mel [n_mels, mel_len]).  Batch-1 like the reference.
         Under an output_rate the waveform holds resampled_len(mel_len*hop) samples of that rate; mel_len stays in frames.
         prosody: None, a prosody.Prosody or a dict of Prosody.create keywords (speed, pitch / energy shift and range, targets).
         loudness: None (the path above, untouched) or Context.normalize_device keywords (target, peak_ceiling, max_gain_db).
         limiter: None (likewise) or Context.limit_device keywords (ceiling, window_ms, oversample); it runs behind the loudness gain.
-        denoise: None (likewise) or Context.denoise_device keywords (strength, floor): the bias denoiser, directly behind the vocoder."""
+        denoise: None (likewise) or Context.denoise_device keywords (strength, floor): the bias denoiser, directly behind the vocoder.
+        report: with True the returned waveform is measured as delivered (at the output rate, behind every step above; on the device
+        where it is still there) and ``last_report`` holds its report.LoudnessReport; False (the default) adds nothing to the call."""
         if denoise is not None:
             denoise = dict(denoise, bias=self.denoise_bias)          # (first use runs the vocoder: before this call's encoder)
         phoneme = np.asarray(x["phoneme"], np.int32)
@@ -181,17 +200,21 @@ class ZeroVox:
         if ml > self._min_mel_len:
             self._min_mel_len = ml
         if loudness is not None or limiter is not None or denoise is not None:
-            wav = self._vocode_normalized(mel_len, pad_to, loudness, limiter, denoise)
+            wav = self._vocode_normalized(mel_len, pad_to, loudness, limiter, denoise, report)
             return wav, ml, logd, np.ascontiguousarray(mel[0, :ml].T)
         wav = self._ctx.vocode(1, mel_len, np.array([pad_to], np.int32))
-        return wav[0, : self._ctx.out_samples(ml * self._hop_length)], ml, logd, np.ascontiguousarray(mel[0, :ml].T)
+        wav = wav[0, : self._ctx.out_samples(ml * self._hop_length)]
+        if report:
+            self.loudness_report(wav)
+        return wav, ml, logd, np.ascontiguousarray(mel[0, :ml].T)
 
-    def _vocode_normalized(self, mel_len, pad_to, loudness, limiter=None, denoise=None):
+    def _vocode_normalized(self, mel_len, pad_to, loudness, limiter=None, denoise=None, report=False):
         """The vocoder writes its row on the device at the model's rate, zvx_denoise takes denoise["strength"] times the bias off it in
         place (queued behind the vocoder: stream order is the fence), zvx_normalize brings it to loudness["target"] in place,
         zvx_limit holds it under limiter["ceiling"] in place, an output rate converts it,
         and only then the row comes to the host.  Every step may be absent.  self.last_loudness reports dict(lufs, peak, gain),
-        self.last_limit dict(peak_in, min_gain)."""
+        self.last_limit dict(peak_in, min_gain); with `report` self.last_report is the finished row's LoudnessReport, measured on the
+        device buffer unless an output rate converts it (the converted row is then measured as it arrives)."""
         ctx = self._ctx
         n = int(mel_len[0]) * self._hop_length
         native = ctx.get_int("sampling_rate")
@@ -207,7 +230,14 @@ class ZeroVox:
             if limiter is not None:
                 peak_in, min_gain = ctx.limit_device(buf, [n], n, rate=native, **limiter)
                 self.last_limit = dict(peak_in=float(peak_in[0]), min_gain=float(min_gain[0]))
-            return ctx.dev_to_host(buf, (n,), np.float32) if out_rate == native else ctx.resample_device(buf, n, native, out_rate)
+            if out_rate == native:
+                if report:
+                    self.loudness_report_device(buf, n, native)
+                return ctx.dev_to_host(buf, (n,), np.float32)
+            wav = ctx.resample_device(buf, n, native, out_rate)
+            if report:
+                self.loudness_report(wav, out_rate)
+            return wav
         finally:
             try:
                 ctx.sync()

@@ -191,7 +191,7 @@ class ZeroVoxTTS:
         return limit_keywords(limiter, limiter_ms, peak_db)
 
     def tts_ex(self, text: str, spkemb, duration=None, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0,
-               loudness=None, peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None):
+               loudness=None, peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None, report=False):
         """-> (wav f32[N], phoneme i32[1,T], length, mel f32[n_mels, L]); empty text -> the reference's sentinel
         (synthesize.py:213-239).  Prosody (include/zvx.h, zvx_prosody): speed = speaking-rate factor (2.0: half the frames),
         pitch / energy shift (in normalised predictor units) and range (spread about the utterance mean).
@@ -206,7 +206,10 @@ class ZeroVoxTTS:
         denoise: None (the default: no launch, buffer or table of it exists), or the strength of the vocoder-bias denoiser (include/zvx.h,
         zvx_denoise; NVIDIA's scripts use 0.01): that multiple of ``denoise_bias`` is taken off the magnitude of every STFT bin of the
         vocoder's row, on the device, in place, directly behind the vocoder -- before the gain, the limiter and the rate conversion.
-        Its audible benefit on a real checkpoint is not measured here."""
+        Its audible benefit on a real checkpoint is not measured here.
+        report: False (the default: nothing is added to the call), or True: the finished waveform is measured as it is delivered -- at
+        the output rate, behind every step above, on the device where its buffer is still there (include/zvx.h, zvx_loudness_stats and
+        zvx_true_peak) -- and ``last_report`` holds the report.LoudnessReport (see ``loudness_report``).  The waveform is the same."""
         prosody = self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range)
         dn = self._denoise(denoise)
         text = text.strip()
@@ -221,7 +224,8 @@ class ZeroVoxTTS:
         t1 = time.time()
         wav, length, _, mel = self._model.inference_ex({"phoneme": phoneme, "puncts": puncts, "duration": duration},
                                                        style_embed=spkemb, force_duration=duration is not None, prosody=prosody,
-                                                       **self._post(loudness, peak_db, limiter, limiter_ms, dn))
+                                                       **self._post(loudness, peak_db, limiter, limiter_ms, dn),
+                                                       **({"report": True} if report else {}))
         if self._verbose:
             print(f"tts timing stats: g2p={t1 - t0}s, synth={time.time() - t1}s")
         return wav, phoneme, length, mel
@@ -237,11 +241,27 @@ class ZeroVoxTTS:
         return kw
 
     def tts(self, text: str, spkemb, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0, loudness=None,
-            peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None):
+            peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None, report=False):
         wav, phoneme, length, _ = self.tts_ex(text=text, spkemb=spkemb, speed=speed, pitch_shift=pitch_shift, pitch_range=pitch_range,
                                               energy_shift=energy_shift, energy_range=energy_range, loudness=loudness, peak_db=peak_db,
-                                              limiter=limiter, limiter_ms=limiter_ms, denoise=denoise)
+                                              limiter=limiter, limiter_ms=limiter_ms, denoise=denoise, report=report)
         return wav, phoneme, length
+
+    def loudness_report(self, wav, sampling_rate=None):
+        """What was delivered: the programme loudness report of a waveform at sampling_rate Hz (None: ``output_rate``), measured on the
+        device -- integrated loudness, loudness range (EBU Tech 3342) with its bounds, maximum momentary and short-term loudness, sample
+        peak (include/zvx.h, zvx_loudness_stats) and the 4x oversampled true peak (zvx_true_peak) -> report.LoudnessReport, whose
+        ``meets(target, tolerance, max_true_peak_db, max_lra)`` checks it against a delivery specification.  int16 PCM is read as the
+        samples it encodes (/ 32760).  Also kept as ``last_report``."""
+        wav = np.asarray(wav)
+        if wav.dtype == np.int16:
+            wav = wav.astype(np.float32) / np.float32(32760.0)
+        return self._model.loudness_report(wav, sampling_rate)
+
+    @property
+    def last_report(self):
+        """the report.LoudnessReport of the last tts / tts_ex / tts_long call with report=True or loudness_report call (None before)"""
+        return self._model.last_report
 
     @property
     def denoise_bias(self):
@@ -401,7 +421,7 @@ class ZeroVoxTTS:
 
     def tts_long(self, text: str, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20, fade_ms=5, max_batch=32, max_frames=2048, pcm16=False,
                  durations=None, max_chars=200, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0,
-                 loudness=None, peak_db=-1.0, loudness_mode="paragraph", limiter=False, limiter_ms=5.0, denoise=None):
+                 loudness=None, peak_db=-1.0, loudness_mode="paragraph", limiter=False, limiter_ms=5.0, denoise=None, report=False):
         """A paragraph -> (wav, segments): one waveform with every sentence in text order (not in the reference).  The text is split by
         longform.split_sentences; the sentences run in batches of at most max_batch, each batch ONE queued synthesize call into
         consecutive rows of one device buffer (every row is the fresh-model ``tts`` of its sentence; a sentence of more than max_frames
@@ -425,13 +445,17 @@ class ZeroVoxTTS:
         Every segment dict then also carries min_gain (the limiter's smallest gain in that sentence; 1.0: untouched).
         denoise: None, or the strength of the vocoder-bias denoiser (see tts_ex): ONE zvx_denoise over all rows of the device buffer, in
         place, behind the synthesis calls and before the normalise.  The segments' layout is that of the same call without it whenever
-        trim_db <= 0 (the trim decides on the denoised rows)."""
+        trim_db <= 0 (the trim decides on the denoised rows).
+        report: False (the default: nothing is added to the call), or True: the joined waveform is measured as it is delivered, at the
+        output rate, and ``last_report`` holds its report.LoudnessReport (see ``loudness_report``).  A float waveform at the model's
+        rate is joined into a device buffer, measured there and copied to the host afterwards -- the same bits as without the report --;
+        a converted or int16 waveform is measured as it arrives."""
         from .longform import synthesize_long
         return synthesize_long(self, text, spkemb, pauses=pauses, trim_db=trim_db, keep_ms=keep_ms, fade_ms=fade_ms, max_batch=max_batch,
                                max_frames=max_frames, pcm16=pcm16, durations=durations, max_chars=max_chars,
                                prosody=self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range),
                                loudness=loudness, peak_db=peak_db, loudness_mode=loudness_mode, limiter=limiter, limiter_ms=limiter_ms,
-                               denoise=self._denoise(denoise))
+                               denoise=self._denoise(denoise), **({"report": True} if report else {}))
 
     @property
     def output_rate(self):
