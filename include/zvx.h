@@ -772,7 +772,9 @@ zvx_status zvx_level_rows(zvx_ctx* ctx, const float* in, const int32_t* nsamples
  *   device-to-device copy; frames must be 0; no mel in the context: ZVX_E_STATE; a context batch other than 1: ZVX_E_UNSUPPORTED.
  *   Captured at open: the context's "out_rate", the model's rate and hop, the denoiser's and limiter's parameters (a copy of the bias
  *   included); every table a stage needs on first use (the limiter's window, its oversampling bank, the FFT tables, the resampler's bank)
- *   is uploaded here, so no zvx_stream_next waits for an upload, and a later zvx_set_int("out_rate") does not touch an open session.
+ *   is uploaded here and the context's work buffers of a step (its table, a group's mel rows, the vocoder's rows) are grown to the
+ *   session's largest group, so no zvx_stream_next waits for a table of a stage or an allocation of the step's own, and a later
+ *   zvx_set_int("out_rate") does not touch an open session.
  *   Validation, before anything is allocated (ZVX_E_INVALID, the context stays usable): a NULL ctx / params / out, frames < 2, frames != 0
  *   with a NULL mel, chunk_frames < 1, chunks_per_call outside 1 .. 64, halo < 0, denoise without denoise_bias or the reverse, every check
  *   zvx_denoise and zvx_limit make on their own parameters and bias, frames * hop samples that fail zvx_melspec's length conditions while a
@@ -793,11 +795,17 @@ zvx_status zvx_level_rows(zvx_ctx* ctx, const float* in, const int32_t* nsamples
  *   calls of a session the context may serve any other call, calls of other open sessions included: the session's bits do not depend on it.
  * Device state: per stage two buffers [history | new], sized at open from chunks_per_call * chunk_frames * hop plus the history the stage
  *   retains (2 R; 2 half / L + 2 for the conversion) plus the reaches in front of it; a stage writes straight behind the next stage's
- *   history through the internal form of its _ex call (device in, device out, no sync); dropping history copies the retained tail into
- *   the stage's other buffer, never over itself.  zvx_stream_next allocates nothing of the session's (the context's own work buffers
- *   grow on first use, as in every call).  New launches: the gather of the group's mel rows with halo, zero-padded to the longest row,
- *   and the gather of the rows' interiors into one run -- stage tag "voc.stream" in zvx_tag_stats, counted only when a session runs
- *   (bytes read plus bytes written); the stages' launches count as their _ex calls count them.
+ *   history through the per-row form behind its _rows call (device in, device out, no sync); dropping history copies the retained tail
+ *   into the stage's other buffer, never over itself -- the drops of all stages of a call are ONE launch over a table, stage tag
+ *   "post.stream".  A session's device footprint is its mel, its stage buffers and the staging of a host piece; a group's gathered mel
+ *   rows and the vocoder's rows are work buffers of the CONTEXT, shared by every session.  zvx_stream_next allocates nothing of the
+ *   session's (the context's own work buffers grow on first use, as in every call).  New launches: the gather of the group's mel rows
+ *   with halo, zero-padded to the longest row, and the gather of the rows' interiors into one run -- stage tag "voc.stream" in
+ *   zvx_tag_stats, counted only when a session runs (bytes read plus bytes written); their small per-row table (and the drops') is built
+ *   on the host and uploaded once per call through the context's pinned staging, queued like a launch: no host wait.  The stages'
+ *   launches count as their _rows calls count them.
+ *   zvx_stream_next is the n = 1 case of zvx_stream_next_many below: ONE stepping path serves both, the two differ in their argument
+ *   checks and messages only.
  * zvx_stream_info fills, in order and as far as n_info reaches: the stream's total output samples, the output samples emitted so far,
  *   the output rate, the native samples the output runs behind the vocoder (the sum of the stages' reaches: n_fft - 1, 2 W + H,
  *   ceil(half / L) + 1; 0 without any), and max_piece = ceil((chunks_per_call * chunk_frames * hop + delay) * L / M) + 1, an upper bound
@@ -836,8 +844,8 @@ zvx_status zvx_stream_close(zvx_stream* s);
  * Two new launches per call, whatever n is, both under the stage tag "voc.stream" with the bytes the single-session gathers would count in
  *   sum: a gather builds the batch's mel rows from the sessions' resident mels, and a scatter moves every row's interior samples straight
  *   behind the history of the owning session's first stage buffer (to that session's final destination where it has no stage).  Their
- *   per-row tables (source mel pointer and frame count; source offset, count and destination pointer) are built on the host and uploaded
- *   through the context's pinned staging, queued like a launch: no host wait.
+ *   per-row tables (source mel pointer and frame count; source offset, count and destination pointer) and the table of the history drops
+ *   are built on the host and uploaded as ONE table through the context's pinned staging, queued like a launch: no host wait.
  * Post stages: batched across the sessions through the per-row forms behind zvx_denoise_rows / zvx_limit_rows / zvx_resample_rows.  The
  *   stages run kind by kind -- all denoisers, then all limiters, then the rate conversions -- on the one stream; a session's chain order
  *   denoise -> limit -> resample is kept.  Within a kind the sessions whose stage has bitwise-equal parameters form one group (the bias
@@ -849,7 +857,8 @@ zvx_status zvx_stream_close(zvx_stream* s);
  *   "post.denoise" / "post.limit" / "voc.resample" as one timed group with the bytes its sessions' single steps count in sum.  A stage
  *   that emits nothing in this call takes no part.  The history drops of all stages of all sessions are ONE launch over a
  *   table of (source, destination, count), each retained tail into its stage's other buffer, under the stage tag "post.stream".
- *   zvx_stream_next itself stays on the one-row _ex forms; the bits are the same either way, which is the per-row contract.
+ *   zvx_stream_next is this same path with n = 1 (a group of one row per stage); that a row's bits do not depend on its company is the
+ *   per-row contract.
  * One wait: host pieces travel through each session's pinned buffer -- all copies are queued, the call waits once, then copies out.  With
  *   ZVX_DEVICE_OUT every out[i] is a device pointer; with ZVX_DEVICE_OUT | ZVX_NO_SYNC the call only queues.  Everything runs on the
  *   context's main stream.  The context's intermediates are void afterwards, as after zvx_stream_next.

@@ -1437,8 +1437,7 @@ MUTATIONS = {
 
 # launchers of the section without a case here, and why
 EXCLUDED = {}
-for _n in ("resample_poly", "join_powers", "join_bounds", "join_layout", "join_copy", "stream_rows", "stream_interiors", "stream_rows_many",
-           "stream_interiors_many", "loud_units", "loud_gates", "loud_common", "loud_apply", "limit_env", "limit_gain", "limit_reduce",
+for _n in ("resample_poly", "join_powers", "join_bounds", "join_layout", "join_copy", "stream_rows", "stream_interiors", "loud_units", "loud_gates", "loud_common", "loud_apply", "limit_env", "limit_gain", "limit_reduce",
            "denoise_frames", "denoise_ola"):
     EXCLUDED["launch_" + _n] = "post-processing: compared with its own float64 reference through the C-ABI (tests/test_*_gpu.py)"
 EXCLUDED["launch_window_pad"] = "enrolment: tests/test_enroll_gpu.py::test_cropped_windows_equal_the_chain_with_the_slice_cut_likewise (any offset, cropped, mirrored edges)"

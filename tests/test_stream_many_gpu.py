@@ -119,6 +119,33 @@ def test_order_and_company_do_not_matter(env):
     run_together(env, ["C", "A"])
 
 
+def test_together_equals_the_host_planned_stream(env):
+    """The reference of this file, the session stepped alone, runs the same stepping code as the sessions stepped together; this test
+    anchors a together-run on the independent path: the host-planned Python stream (three Python planners, the window calls)."""
+    names = ["A", "D"]
+    live = [(n, env.open(n)) for n in names]
+    got = {n: [] for n in names}
+    while live:
+        pieces = env.ctx.stream_next_many([s for _, s in live])
+        for (n, s), piece in zip(live, pieces):
+            got[n].append(piece.copy())
+            if s.done:
+                s.close()
+        live = [(n, s) for n, s in live if not s.done]
+        assert sum(len(v) for v in got.values()) < 50
+    for n in names:
+        frames, chunk, halo, cpc, chain = SPECS[n]
+        dn, lim, rate = CHAINS[chain]
+        env.ctx.set_int("out_rate", rate)
+        try:
+            want = np.concatenate(list(env.model.vocode_stream(env.mel[:frames], chunk_frames=chunk, halo=halo, chunks_per_call=cpc, limiter=lim,
+                                                               denoise=dn, resident=False)))
+        finally:
+            env.ctx.set_int("out_rate", 0)
+        have = np.concatenate(got[n])
+        assert len(have) == len(want) and same_bits(have, want), (n, len(have), len(want))
+
+
 def test_all_or_nothing_capacity(env):
     names = ["A", "D", "E"]
     live = [(n, env.open(n)) for n in names]

@@ -298,3 +298,25 @@ def test_accounting(env):
         assert "post.denoise" in tags and "post.limit" in tags and "voc.post" in tags
     finally:
         ctx.set_int("profile", 0)
+
+
+def test_history_drops_are_one_launch_per_call(env):
+    """zvx_stream_next drops the history of all its stages in ONE launch over a table ("post.stream"), and the drops do happen"""
+    ctx = env.ctx
+    s = env.open("both-48000", 3)
+    ctx.set_int("profile", 2)
+    try:
+        calls, drops = 0, 0
+        while not s.done:
+            ctx.sync()
+            ctx.reset_stats()
+            s.next_piece()
+            ctx.sync()
+            tags = {t["name"]: t["launches"] for t in ctx.tag_stats()}
+            assert tags.get("post.stream", 0) <= 1 and tags.get("voc.stream", 0) == 2, (calls, tags)
+            drops += tags.get("post.stream", 0)
+            calls += 1
+        assert calls == 2 and drops >= 1
+    finally:
+        ctx.set_int("profile", 0)
+        s.close()

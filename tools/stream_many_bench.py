@@ -5,7 +5,8 @@ Per chain (the plain chain; with --denoise / --peak-db also denoiser + limiter) 
 advanced by one piece, host pieces, the call's own wait inside --
    (a) by N zvx_stream_next calls, one after the other,
    (b) by one zvx_stream_next_many,
-the two alternating pass by pass over the same mels, the ratio (a) / (b), whether both hand out the same bits, and for (b) the split of a
+(one stepping path in the library: (a) is N steps of one session each, (b) one step of N sessions -- the comparison is between N small
+batches with N waits and one large batch with one wait, not between two implementations), the two alternating pass by pass over the same mels, the ratio (a) / (b), whether both hand out the same bits, and for (b) the split of a
 round between the vocoder stage (zvx_stage_times, profile 1, in passes of their own) and the rest.  The first round of a pass (start-up)
 and the last (the stages flush) are not counted.  --no-many times (a) alone: it uses only entry points that exist without the call, so it
 runs on a tree that lacks it.  --out-rate HZ opens every session under that output rate (zvx_set_int "out_rate" around the opens), so each

@@ -1648,69 +1648,15 @@ void launch_join_copy(const JoinCopyArgs& a, long upper, hipStream_t s) {
     hipLaunchKernelGGL(k_join_copy, dim3((unsigned)tiles), dim3(256), 0, s, a);
 }
 
-// ---------------------------------------------------------------- the gathers of a stream session (zvx_kernels.h, include/zvx.h: zvx_stream_next)
+// ---------------------------------------------------------------- the gathers of a stream step (zvx_kernels.h, include/zvx.h: zvx_stream_next, zvx_stream_next_many)
 // One thread per group of 4 floats, groups aligned as addresses of the destination (as k_join_copy aligns its): a whole group is one
 // vector store, and one vector load where the source address allows; a group at an edge is built element by element.
-__global__ __launch_bounds__(256) void k_stream_rows(const StreamRowsArgs a) {
+// Every row has its own source mel / its own destination, so the per-row entries come from a table in device memory -- one small entry
+// per row, indexed by blockIdx.y, the same for every lane of a workgroup (a scalar load).  Rows of one call differ a lot in length: a
+// block past its row's end leaves before it touches anything else.
+__global__ __launch_bounds__(256) void k_stream_rows(const StreamRowTab a) {
     const int b = blockIdx.y;
-    const long row = (long)a.Pmax * a.nm, valid = (long)a.P[b] * a.nm;
-    const float* src = a.mel + (long)a.lo[b] * a.nm;
-    float* dst = a.out + (long)b * row;
-    const int mis = (int)(((size_t)dst >> 2) & 3);
-    const long e = ((long)blockIdx.x * 256 + threadIdx.x) * 4 - mis;
-    if (e >= row) return;
-    if (e >= 0 && e + 4 <= row) {
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (e + 4 <= valid) {
-            if (((size_t)(src + e) & 15) == 0) v = *(const float4*)(src + e);
-            else v = make_float4(src[e], src[e + 1], src[e + 2], src[e + 3]);
-        } else if (e < valid) {
-            v.x = src[e];
-            if (e + 1 < valid) v.y = src[e + 1];
-            if (e + 2 < valid) v.z = src[e + 2];
-        }
-        *(float4*)(dst + e) = v;
-    } else {
-        for (int k = 0; k < 4; k++)
-            if (e + k >= 0 && e + k < row) dst[e + k] = e + k < valid ? src[e + k] : 0.f;
-    }
-}
-void launch_stream_rows(const StreamRowsArgs& a, hipStream_t s) {
-    if (a.B <= 0 || a.Pmax <= 0) return;
-    const long groups = ((long)a.Pmax * a.nm + 3 + 3) / 4;             // (+ 3: the address alignment shifts the groups by up to 3 elements)
-    hipLaunchKernelGGL(k_stream_rows, dim3((unsigned)((groups + 255) / 256), a.B), dim3(256), 0, s, a);
-}
-
-__global__ __launch_bounds__(256) void k_stream_interiors(const StreamInteriorArgs a) {
-    const int b = blockIdx.y;
-    const long cnt = a.cnt[b];
-    const float* src = a.wav + (long)b * a.w_bs + a.off[b];
-    float* dst = a.out + a.pos[b];
-    const int mis = (int)(((size_t)dst >> 2) & 3);
-    const long o = ((long)blockIdx.x * 256 + threadIdx.x) * 4 - mis;
-    if (o >= cnt) return;
-    if (o >= 0 && o + 4 <= cnt) {
-        float4 v;
-        if (((size_t)(src + o) & 15) == 0) v = *(const float4*)(src + o);
-        else v = make_float4(src[o], src[o + 1], src[o + 2], src[o + 3]);
-        *(float4*)(dst + o) = v;
-    } else {
-        for (int k = 0; k < 4; k++)
-            if (o + k >= 0 && o + k < cnt) dst[o + k] = src[o + k];
-    }
-}
-void launch_stream_interiors(const StreamInteriorArgs& a, long cnt_max, hipStream_t s) {
-    if (a.B <= 0 || cnt_max <= 0) return;
-    const long groups = (cnt_max + 3 + 3) / 4;
-    hipLaunchKernelGGL(k_stream_interiors, dim3((unsigned)((groups + 255) / 256), a.B), dim3(256), 0, s, a);
-}
-
-// The same two movements for the rows of MANY sessions (zvx_stream_next_many): every row has its own source mel / its own destination, so
-// the per-row entries come from a table in device memory -- one small entry per row, indexed by blockIdx.y, the same for every lane of a
-// workgroup (a scalar load).  Rows of one call differ a lot in length: a block past its row's end leaves before it touches anything else.
-__global__ __launch_bounds__(256) void k_stream_rows_many(const StreamManyRowsArgs a) {
-    const int b = blockIdx.y;
-    const StreamManyRow t = a.tab[b];
+    const StreamRow t = a.tab[b];
     const long row = (long)a.Pmax * a.nm, valid = (long)t.P * a.nm;
     const float* src = t.src;
     float* dst = a.out + (long)b * row;
@@ -1733,15 +1679,15 @@ __global__ __launch_bounds__(256) void k_stream_rows_many(const StreamManyRowsAr
             if (e + k >= 0 && e + k < row) dst[e + k] = e + k < valid ? src[e + k] : 0.f;
     }
 }
-void launch_stream_rows_many(const StreamManyRowsArgs& a, hipStream_t s) {
+void launch_stream_rows(const StreamRowTab& a, hipStream_t s) {
     if (a.R <= 0 || a.Pmax <= 0) return;
     const long groups = ((long)a.Pmax * a.nm + 3 + 3) / 4;             // (+ 3: the address alignment shifts the groups by up to 3 elements)
-    hipLaunchKernelGGL(k_stream_rows_many, dim3((unsigned)((groups + 255) / 256), a.R), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_stream_rows, dim3((unsigned)((groups + 255) / 256), a.R), dim3(256), 0, s, a);
 }
 
-__global__ __launch_bounds__(256) void k_stream_interiors_many(const StreamManyInteriorArgs a) {
+__global__ __launch_bounds__(256) void k_stream_interiors(const StreamInteriorTab a) {
     const int b = blockIdx.y;
-    const StreamManyInterior t = a.tab[b];
+    const StreamInterior t = a.tab[b];
     const long cnt = t.cnt;
     if ((long)blockIdx.x * 1024 - 3 >= cnt) return;                    // the whole block lies past this row's interior
     const float* src = (t.src ? t.src : a.wav + (long)b * a.w_bs) + t.off;
@@ -1759,10 +1705,10 @@ __global__ __launch_bounds__(256) void k_stream_interiors_many(const StreamManyI
             if (o + k >= 0 && o + k < cnt) dst[o + k] = src[o + k];
     }
 }
-void launch_stream_interiors_many(const StreamManyInteriorArgs& a, long cnt_max, hipStream_t s) {
+void launch_stream_interiors(const StreamInteriorTab& a, long cnt_max, hipStream_t s) {
     if (a.R <= 0 || cnt_max <= 0) return;
     const long groups = (cnt_max + 3 + 3) / 4;
-    hipLaunchKernelGGL(k_stream_interiors_many, dim3((unsigned)((groups + 255) / 256), a.R), dim3(256), 0, s, a);
+    hipLaunchKernelGGL(k_stream_interiors, dim3((unsigned)((groups + 255) / 256), a.R), dim3(256), 0, s, a);
 }
 
 // ---------------------------------------------------------------- integrated loudness and gain (zvx_kernels.h, include/zvx.h: zvx_loudness)

@@ -414,13 +414,14 @@ struct zvx_ctx {
 
 // A stream session (include/zvx.h: zvx_stream_open): one utterance's mel on the device, the planners of its post stages and, per stage,
 // two device buffers laid out [history | new].  A stage's output is written straight behind the next stage's history; dropping the history
-// before keep_from copies the retained tail into the stage's OTHER buffer (never an overlapping copy) and swaps the two.
+// before keep_from copies the retained tail into the stage's OTHER buffer (never an overlapping copy) and swaps the two.  A group's gathered
+// rows and what the vocoder makes of them are not the session's: every step, of one session or of many, takes them from the context
+// ("stream.rows", "stream.wav"), which zvx_stream_open has grown to the session's largest group.
 struct zvx_stream {
     zvx_ctx* c = nullptr;
     int frames = 0, chunk = 0, cpc = 0, halo = 0, hop = 0, native = 0, out_rate = 0;
     int nchunks = 0, next_chunk = 0, done = 0;
     int Pcap = 0;                          // the longest row a group can have, in mel frames
-    long wstride = 0;                      // samples between the vocoder's rows
     int64_t total = 0, emitted = 0, delay = 0, max_piece = 0;
     enum { DENOISE = 0, LIMIT = 1, RESAMPLE = 2 };
     struct Stage {
@@ -438,10 +439,8 @@ struct zvx_stream {
     std::vector<float> bias;
     zvx_limit_params lim{};
     int lim_W = 0;                         // the limiter's window in samples
-    char* dev = nullptr;                   // ONE device allocation: the mel, a group's rows, the vocoder's rows, the stage buffers, the host piece's staging
+    char* dev = nullptr;                   // ONE device allocation: the mel, the stage buffers, the host piece's staging
     float* mel = nullptr;
-    float* rows = nullptr;
-    float* wav = nullptr;
     float* ostage = nullptr;
     float* pinned = nullptr;               // host piece: [max_piece] f32
 };
@@ -3240,6 +3239,11 @@ void stream_free(zvx_stream* s) {
 // the native samples the rate conversion runs behind its input: output n is final once n M + half <= (received - 1) L
 int64_t rs_reach(const zvx_plan::RatePair& p) { return p.half ? zvx_plan::ceil_div(p.half, p.L) + 1 : 0; }
 
+// The step's one table on the device (stream_step): the rows' gather entries, their scatter entries, then the history drops (one per stage
+// at most).  The buffer is taken at its largest size at once: it never grows behind a queued call.
+constexpr size_t STREAM_TAB_BYTES = (size_t)STREAM_MANY_MAX_ROWS * (sizeof(StreamRow) + sizeof(StreamInterior)) +
+                                    (size_t)STREAM_MANY_MAX_SESSIONS * 3 * sizeof(StreamInterior);
+
 void do_stream_open(zvx_ctx* c, const float* mel, int frames, const zvx_stream_params* p, int flags, zvx_stream** out) {
     const char* who = "zvx_stream_open";
     // ---- every check, before anything is allocated
@@ -3298,17 +3302,18 @@ void do_stream_open(zvx_ctx* c, const float* mel, int frames, const zvx_stream_p
     if (p->denoise && p->denoise->strength != 0.f) dn_tables(c, g);
     if (p->limit) { limit_win(c, W); if (p->limit->oversample > 1) rs_bank(c, p->limit->oversample, 1); }
     if (out_rate != native) rs_bank(c, (int)rp.L, (int)rp.M);
+    c->buf("stream.tab", STREAM_TAB_BYTES); c->fbuf("stream.rows", (size_t)rows * Pcap * nm); c->fbuf("stream.wav", (size_t)rows * wstride);   // what a step of the largest group takes
     // ---- the session and its memory
     zvx_stream* s = new zvx_stream();
     s->c = c;
     try {
         s->frames = frames; s->chunk = p->chunk_frames; s->cpc = p->chunks_per_call; s->halo = p->halo; s->hop = hop; s->native = native; s->out_rate = out_rate;
-        s->nchunks = nchunks; s->Pcap = Pcap; s->wstride = wstride; s->delay = delay; s->max_piece = max_piece;
+        s->nchunks = nchunks; s->Pcap = Pcap; s->delay = delay; s->max_piece = max_piece;
         s->total = zvx_plan::ceil_div(total_native * rp.L, rp.M);
         if (p->denoise) { s->dn = *p->denoise; s->bias.assign(p->denoise_bias, p->denoise_bias + g.nf); }
         if (p->limit) { s->lim = *p->limit; s->lim_W = W; }
         auto pad = [](int64_t floats) { return (size_t)((floats * 4 + 255) & ~(int64_t)255); };
-        size_t bytes = pad((int64_t)frames * nm) + pad((int64_t)rows * Pcap * nm) + pad((int64_t)rows * wstride) + pad(max_piece);
+        size_t bytes = pad((int64_t)frames * nm) + pad(max_piece);
         int64_t in_max = G;
         for (const Want& w : want) {
             zvx_stream::Stage st;
@@ -3324,7 +3329,7 @@ void do_stream_open(zvx_ctx* c, const float* mel, int frames, const zvx_stream_p
         HIPCHK(hipMemsetAsync(s->dev, 0, bytes, c->stream));
         char* q = s->dev;
         auto take = [&](int64_t floats) { float* r = (float*)q; q += pad(floats); return r; };
-        s->mel = take((int64_t)frames * nm); s->rows = take((int64_t)rows * Pcap * nm); s->wav = take((int64_t)rows * wstride); s->ostage = take(max_piece);
+        s->mel = take((int64_t)frames * nm); s->ostage = take(max_piece);
         for (auto& st : s->stages) { st.buf[0] = take(st.cap); st.buf[1] = take(st.cap); }
         const size_t mbytes = (size_t)frames * nm * 4;
         if (!mel) HIPCHK(hipMemcpyAsync(s->mel, c->fbuf("mel", 0), mbytes, hipMemcpyDeviceToDevice, c->stream));       // utterance 0: the first rows
@@ -3373,212 +3378,180 @@ void stream_plan_step(const char* who, const zvx_stream* s, StreamStep& p) {
         const int64_t held = p.plan[k].hist + n;
         if (held != p.plan[k].received() - p.steps[k].in_origin || held > p.plan[k].cap)
             fail(ZVX_E_STATE, "%s: stage %zu holds %lld samples (buffer %lld, window from %lld)", who, k, (long long)held, (long long)p.plan[k].cap, (long long)p.steps[k].in_origin);
+        // the plan's self-check: a denoiser's or limiter's window must be one the rows calls accept (their support condition, on the host)
+        if (p.plan[k].kind != zvx_stream::RESAMPLE && p.steps[k].out_count > 0) {
+            const RowsWindow w{p.steps[k].in_origin, p.steps[k].out_begin, p.steps[k].out_count, p.g.last ? 1 : 0};
+            int64_t cnt = -1;
+            try { cnt = window_count_row(who, w, (int32_t)held, 0, p.plan[k].reach.R); }
+            catch (const ZvxError& e) { fail(ZVX_E_STATE, "%s (stage %zu of the session's plan)", e.what(), k); }
+            if (cnt != w.out_count) fail(ZVX_E_STATE, "%s: stage %zu emits %lld samples, its plan says %lld", who, k, (long long)cnt, (long long)w.out_count);
+        }
         n = p.steps[k].out_count;
     }
     p.n = n;
     if (n > s->max_piece) fail(ZVX_E_STATE, "%s: a piece of %lld samples exceeds max_piece %lld", who, (long long)n, (long long)s->max_piece);
 }
-// where the group's new samples go: straight behind the history of the first stage's buffer, or the piece's destination without a stage
-float* stream_new_dst(zvx_stream* s, float* final_dst) {
-    return s->stages.empty() ? final_dst : s->stages[0].buf[s->stages[0].cur] + s->stages[0].hist;
-}
-// The session's own stages over its new samples (B = 1, the windows of the plan), then the session's state: what every stepping call runs
-// behind the gather of the interiors.
-void stream_run_stages(const char* who, zvx_stream* s, const StreamStep& p, float* final_dst) {
-    zvx_ctx* c = s->c;
-    const size_t K = s->stages.size();
-    const bool last = p.g.last != 0;
-    const int f = ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC;
-    int64_t n_in = p.g.n_new;
-    for (size_t k = 0; k < K; k++) {
-        zvx_stream::Stage& st = s->stages[k];
-        const zvx_plan::Step& sp = p.steps[k];
-        const int64_t held = st.hist + n_in;
-        const float* in = st.buf[st.cur];
-        float* dst = k + 1 < K ? s->stages[k + 1].buf[s->stages[k + 1].cur] + s->stages[k + 1].hist : final_dst;
-        if (sp.out_count > 0 && held > 0) {
-            const int32_t n32 = (int32_t)held;
-            const int64_t stride = std::max(held, sp.out_count);
-            const WindowsIn w{WindowsIn::ONE, RowsWindow{sp.in_origin, sp.out_begin, sp.out_count, last ? 1 : 0}};
-            if (st.kind == zvx_stream::DENOISE) do_denoise(c, who, in, &n32, 1, n32, s->bias.data(), &s->dn, dst, stride, f, w);
-            else if (st.kind == zvx_stream::LIMIT) do_limit(c, who, in, &n32, 1, n32, s->native, &s->lim, 0, dst, stride, nullptr, nullptr, f, w);
-            else do_resample(c, in, &n32, 1, n32, s->native, s->out_rate, dst, stride, nullptr, f, sp.in_origin, sp.out_begin, sp.out_count);
-        }
-        const int64_t drop = sp.keep_from - sp.in_origin, keep = held - drop;
-        if (drop > 0) {                                  // into the other buffer: never an overlapping copy
-            if (keep > 0) HIPCHK(hipMemcpyAsync(st.buf[st.cur ^ 1], in + drop, (size_t)keep * 4, hipMemcpyDeviceToDevice, c->stream));
-            st.cur ^= 1;
-        }
-        st.hist = keep; st.reach = p.plan[k].reach; st.rate = p.plan[k].rate;
-        n_in = sp.out_count;
-    }
-    s->next_chunk = p.g.first + p.g.rows; s->emitted += p.n; s->done = last ? 1 : 0;
-}
 
-// The stages of MANY sessions behind the scatter (zvx_stream_next_many): what stream_run_stages does per session, run kind by kind -- all
-// denoisers, then all limiters, then the rate conversions; a session's chain order is kept and everything is on the one stream.  Within a
-// kind the sessions whose stage has bitwise-equal parameters (the bias by content; the limiter by W, oversampling and ceiling) form one
-// group (stream_plan.h, partition_classes), and a group is ONE call of the per-row form: its rows are the sessions' [history | new]
-// buffers with each session's own window, each output goes straight behind the next stage's history or to the final destination.  The
-// rate conversions are grouped by (native rate, output rate) -- the polyphase bank -- and a group is one run_resample_rows.  All history
-// drops of the call are ONE launch over a table.
-void stream_run_stages_many(const char* who, zvx_ctx* c, zvx_stream* const* ss, const std::vector<StreamStep>& plans, const std::vector<float*>& final_dst,
-                            int n) {
-    struct Slot { bool run = false; PostRow row{}; };
-    std::vector<Slot> slot[3];
-    for (auto& v : slot) v.resize((size_t)n);
-    std::vector<StreamManyInterior> moves;
-    double move_bytes = 0; long move_max = 0;
-    // ---- every stage's input, window and destination, from the sessions' state as it stands
-    for (int i = 0; i < n; i++) {
-        const zvx_stream* s = ss[i];
-        const StreamStep& p = plans[(size_t)i];
-        const size_t K = s->stages.size();
-        const bool last = p.g.last != 0;
-        int64_t n_in = p.g.n_new;
-        for (size_t k = 0; k < K; k++) {
-            const zvx_stream::Stage& st = s->stages[k];
-            const zvx_plan::Step& sp = p.steps[k];
-            const int64_t held = st.hist + n_in;
-            float* in = st.buf[st.cur];
-            float* dst = k + 1 < K ? s->stages[k + 1].buf[s->stages[k + 1].cur] + s->stages[k + 1].hist : final_dst[(size_t)i];
-            if (sp.out_count > 0 && held > 0) {
-                Slot& sl = slot[st.kind][(size_t)i];
-                sl.run = true;
-                sl.row = PostRow{in, dst, (int32_t)held, RowsWindow{sp.in_origin, sp.out_begin, sp.out_count, last ? 1 : 0}, (int32_t)sp.out_count};
-            }
-            const int64_t drop = sp.keep_from - sp.in_origin, keep = held - drop;
-            if (drop > 0 && keep > 0) {                      // into the other buffer: never an overlapping copy
-                moves.push_back(StreamManyInterior{st.buf[st.cur ^ 1], in + drop, 0, (int)keep});
-                move_bytes += 8.0 * (double)keep; move_max = std::max<long>(move_max, (long)keep);
-            }
-            n_in = sp.out_count;
-        }
-    }
-    // ---- denoisers and limiters: one call of the per-row form per class
-    std::vector<int> cls((size_t)n), order((size_t)n), start((size_t)n + 1);
-    std::vector<PostRow> rows;
-    for (int kind : {(int)zvx_stream::DENOISE, (int)zvx_stream::LIMIT}) {
+// One step of n sessions of ONE context, the only stepping path (zvx_stream_next is its n = 1): the callers have made their own checks
+// and planned every session (stream_plan_step), so from here on the call consumes the groups and a failure ends every session of it.
+// The rows of all sessions are gathered by one launch, vocoded as ONE batch by one run_vocoder and scattered by one launch to where each
+// session's first stage reads them.  The stages then run kind by kind -- all denoisers, then all limiters, then the rate conversions; a
+// session's chain order is kept and everything is on the one stream.  Within a kind the sessions whose stage has bitwise-equal parameters
+// (the bias by content; the limiter by W, oversampling and ceiling; the rate conversion by its two rates, i.e. the polyphase bank) form
+// one group (stream_plan.h, partition_classes), and a group is ONE call of the per-row form: its rows are the sessions' [history | new]
+// buffers with each session's own window, each output goes straight behind the next stage's history or to the piece's destination.
+// All history drops of the call are ONE launch over a table.  Every session's stages are walked once, before anything is queued: the
+// walk yields the stages' rows, the drops and -- in the plan's copies of the stages -- the state the session takes on at the end.
+void stream_step(const char* who, zvx_ctx* c, zvx_stream* const* ss, StreamStep* plans, int n, void* const* out, const int64_t* n_out,
+                 int32_t* done, int flags) {
+    try {
+        c->have_features = false; c->have_mel = false;      // as zvx_vocode_mel: the context's intermediates are void
+        const int nm = c->n_mels, hop = c->hop;
+        int R = 0, Pmax = 0; long cnt_max = 0, move_max = 0; double rows_bytes = 0, new_bytes = 0, move_bytes = 0;
         for (int i = 0; i < n; i++) {
-            cls[(size_t)i] = -1;
-            if (!slot[kind][(size_t)i].run) continue;
-            cls[(size_t)i] = i;
-            for (int j = 0; j < i; j++) {
-                if (cls[(size_t)j] != j) continue;           // (a class is named by its first member)
-                const zvx_stream *a = ss[j], *b = ss[i];
-                const bool same = kind == zvx_stream::DENOISE
-                    ? !memcmp(&a->dn, &b->dn, sizeof a->dn) && a->bias.size() == b->bias.size() && !memcmp(a->bias.data(), b->bias.data(), a->bias.size() * 4)
-                    : a->lim_W == b->lim_W && a->lim.oversample == b->lim.oversample && !memcmp(&a->lim.ceiling, &b->lim.ceiling, sizeof(float));
-                if (same) { cls[(size_t)i] = j; break; }
+            const StreamStep& p = plans[i];
+            R += p.g.rows; Pmax = std::max(Pmax, (int)p.g.Pmax); cnt_max = std::max(cnt_max, (long)p.g.cnt_max);
+            for (int j = 0; j < p.g.rows; j++) rows_bytes += (double)p.P[j] * nm * 4.0;
+            rows_bytes += (double)p.g.rows * (double)p.g.Pmax * nm * 4.0;
+            new_bytes += 8.0 * (double)p.g.n_new;
+        }
+        const long wstride = ((long)Pmax * hop + 7) & ~7L;
+        // ---- the table, and every stage's input, window and destination, from the sessions' state as it stands
+        std::vector<char> tab((size_t)R * (sizeof(StreamRow) + sizeof(StreamInterior)) + (size_t)n * 3 * sizeof(StreamInterior));
+        StreamRow* tr = (StreamRow*)tab.data();
+        StreamInterior* ti = (StreamInterior*)(tr + R);
+        StreamInterior* moves = ti + R;
+        int M = 0, r = 0;
+        std::vector<int> P((size_t)R);
+        struct Slot { bool run = false; PostRow row{}; };
+        std::vector<Slot> slot[3];
+        for (auto& v : slot) v.resize((size_t)n);
+        for (int i = 0; i < n; i++) {
+            const zvx_stream* s = ss[i];
+            StreamStep& p = plans[i];
+            const size_t K = s->stages.size();
+            const bool last = p.g.last != 0;
+            // where stage k's new input goes: straight behind the history of its buffer; behind the last stage, the piece's destination
+            auto dst_of = [&](size_t k) { return k < K ? s->stages[k].buf[s->stages[k].cur] + s->stages[k].hist : (flags & ZVX_DEVICE_OUT) ? (float*)out[i] : s->ostage; };
+            float* base = dst_of(0);
+            for (int j = 0; j < p.g.rows; j++, r++) {
+                P[(size_t)r] = p.P[j];
+                tr[r] = StreamRow{s->mel + p.rows[j].lo * nm, p.P[j], 0};
+                ti[r] = StreamInterior{base + p.rows[j].pos, nullptr, (int)p.rows[j].off, (int)p.rows[j].cnt};
+            }
+            int64_t n_in = p.g.n_new;
+            for (size_t k = 0; k < K; k++) {
+                const zvx_stream::Stage& st = s->stages[k];
+                zvx_stream::Stage& next = p.plan[k];         // (the planners in it have taken the step already)
+                const zvx_plan::Step& sp = p.steps[k];
+                const int64_t held = st.hist + n_in;
+                float* in = st.buf[st.cur];
+                if (sp.out_count > 0 && held > 0)
+                    slot[st.kind][(size_t)i] = Slot{true, PostRow{in, dst_of(k + 1), (int32_t)held, RowsWindow{sp.in_origin, sp.out_begin, sp.out_count, last ? 1 : 0}, (int32_t)sp.out_count}};
+                const int64_t drop = sp.keep_from - sp.in_origin, keep = held - drop;
+                if (drop > 0) {                              // into the other buffer: never an overlapping copy
+                    if (keep > 0) {
+                        moves[M++] = StreamInterior{st.buf[st.cur ^ 1], in + drop, 0, (int)keep};
+                        move_bytes += 8.0 * (double)keep; move_max = std::max<long>(move_max, (long)keep);
+                    }
+                    next.cur = st.cur ^ 1;
+                }
+                next.hist = keep;
+                n_in = sp.out_count;
             }
         }
-        const int groups = zvx_plan::partition_classes(cls.data(), n, order.data(), start.data());
-        for (int gi = 0; gi < groups; gi++) {
-            rows.clear();
-            for (int m = start[(size_t)gi]; m < start[(size_t)gi + 1]; m++) rows.push_back(slot[kind][(size_t)order[(size_t)m]].row);
-            const zvx_stream* first = ss[order[(size_t)start[(size_t)gi]]];
-            if (kind == zvx_stream::DENOISE) run_denoise_rows(c, dn_geom(c, who), rows.data(), (int)rows.size(), first->bias.data(), &first->dn, 0);
-            else run_limit_rows(c, who, rows.data(), (int)rows.size(), &first->lim, first->lim_W, 0);
+        char* tab_d = (char*)c->buf("stream.tab", STREAM_TAB_BYTES);
+        float* rows_d = c->fbuf("stream.rows", (size_t)R * Pmax * nm);
+        float* wav_d = c->fbuf("stream.wav", (size_t)R * wstride);
+        c->upload(tab_d, tab.data(), (size_t)((char*)(moves + M) - tab.data()));
+        const StreamRowTab ra{(const StreamRow*)tab_d, rows_d, R, Pmax, nm};
+        const StreamInteriorTab ia{(const StreamInterior*)(ra.tab + R), wav_d, wstride, R};
+        const StreamInteriorTab ma{ia.tab + R, nullptr, 0, M};               // (the scatter's kernel: every entry has its own source)
+        // ---- gather, ONE batch of the vocoder at the native rate (the rows of ZeroVox._vocode_stream_native), scatter
+        {
+            TagScope scope(c, "voc.stream");
+            c->timed(0.0, rows_bytes, [&] { launch_stream_rows(ra, c->stream); });
         }
-    }
-    // ---- rate conversions: one call of the per-row form per (native rate, output rate)
-    for (int i = 0; i < n; i++) {
-        cls[(size_t)i] = -1;
-        if (!slot[zvx_stream::RESAMPLE][(size_t)i].run) continue;
-        cls[(size_t)i] = i;
-        for (int j = 0; j < i; j++)
-            if (cls[(size_t)j] == j && ss[j]->native == ss[i]->native && ss[j]->out_rate == ss[i]->out_rate) { cls[(size_t)i] = j; break; }
-    }
-    const int rs_groups = zvx_plan::partition_classes(cls.data(), n, order.data(), start.data());
-    for (int gi = 0; gi < rs_groups; gi++) {
-        rows.clear();
-        for (int m = start[(size_t)gi]; m < start[(size_t)gi + 1]; m++) rows.push_back(slot[zvx_stream::RESAMPLE][(size_t)order[(size_t)m]].row);
-        const zvx_stream* first = ss[order[(size_t)start[(size_t)gi]]];
-        int L = 1, M = 1;
-        rs_pair(first->native, first->out_rate, &L, &M);
-        run_resample_rows(c, rs_bank(c, L, M), rows.data(), (int)rows.size(), 0);
-    }
-    // ---- every history drop of the call in one launch
-    if (!moves.empty()) {
-        StreamManyInterior* tab_d = (StreamManyInterior*)c->buf("stream.moves", (size_t)STREAM_MANY_MAX_SESSIONS * 3 * sizeof(StreamManyInterior));
-        c->upload(tab_d, moves.data(), moves.size() * sizeof(StreamManyInterior));
-        const StreamManyInteriorArgs ma{tab_d, nullptr, 0, (int)moves.size()};      // (the scatter's kernel: every entry has its own source)
-        TagScope scope(c, "post.stream");
-        c->timed(0.0, move_bytes, [&] { launch_stream_interiors_many(ma, move_max, c->stream); });
-    }
-    // ---- the sessions' state
-    for (int i = 0; i < n; i++) {
-        zvx_stream* s = ss[i];
-        const StreamStep& p = plans[(size_t)i];
-        int64_t n_in = p.g.n_new;
-        for (size_t k = 0; k < s->stages.size(); k++) {
-            zvx_stream::Stage& st = s->stages[k];
-            const zvx_plan::Step& sp = p.steps[k];
-            const int64_t held = st.hist + n_in, drop = sp.keep_from - sp.in_origin;
-            if (drop > 0) st.cur ^= 1;
-            st.hist = held - drop; st.reach = p.plan[k].reach; st.rate = p.plan[k].rate;
-            n_in = sp.out_count;
+        c->stage_begin(ZVX_T_VOCODER);
+        run_vocoder(c, rows_d, nm, Pmax, P.data(), P.data(), R, wav_d, wstride, 0);
+        c->stage_end(ZVX_T_VOCODER);
+        {
+            TagScope scope(c, "voc.stream");
+            c->timed(0.0, new_bytes, [&] { launch_stream_interiors(ia, cnt_max, c->stream); });
         }
-        s->next_chunk = p.g.first + p.g.rows; s->emitted += p.n; s->done = p.g.last ? 1 : 0;
+        // ---- the stages of one kind: a class is named by its first member, and is one call of the per-row form
+        std::vector<int> cls((size_t)n), order((size_t)n), start((size_t)n + 1);
+        std::vector<PostRow> rows;
+        auto per_class = [&](int kind, auto same, auto run) {
+            for (int i = 0; i < n; i++) {
+                cls[(size_t)i] = -1;
+                if (!slot[kind][(size_t)i].run) continue;
+                cls[(size_t)i] = i;
+                for (int j = 0; j < i; j++)
+                    if (cls[(size_t)j] == j && same(ss[j], ss[i])) { cls[(size_t)i] = j; break; }
+            }
+            const int groups = zvx_plan::partition_classes(cls.data(), n, order.data(), start.data());
+            for (int gi = 0; gi < groups; gi++) {
+                rows.clear();
+                for (int m = start[(size_t)gi]; m < start[(size_t)gi + 1]; m++) rows.push_back(slot[kind][(size_t)order[(size_t)m]].row);
+                run(ss[order[(size_t)start[(size_t)gi]]]);
+            }
+        };
+        per_class(zvx_stream::DENOISE, [](const zvx_stream* a, const zvx_stream* b) {
+            return !memcmp(&a->dn, &b->dn, sizeof a->dn) && a->bias.size() == b->bias.size() && !memcmp(a->bias.data(), b->bias.data(), a->bias.size() * 4);
+        }, [&](const zvx_stream* first) { run_denoise_rows(c, dn_geom(c, who), rows.data(), (int)rows.size(), first->bias.data(), &first->dn, 0); });
+        per_class(zvx_stream::LIMIT, [](const zvx_stream* a, const zvx_stream* b) {
+            return a->lim_W == b->lim_W && a->lim.oversample == b->lim.oversample && !memcmp(&a->lim.ceiling, &b->lim.ceiling, sizeof(float));
+        }, [&](const zvx_stream* first) { run_limit_rows(c, who, rows.data(), (int)rows.size(), &first->lim, first->lim_W, 0); });
+        per_class(zvx_stream::RESAMPLE, [](const zvx_stream* a, const zvx_stream* b) { return a->native == b->native && a->out_rate == b->out_rate; },
+                  [&](const zvx_stream* first) {
+            int L = 1, Mr = 1;
+            rs_pair(first->native, first->out_rate, &L, &Mr);
+            run_resample_rows(c, rs_bank(c, L, Mr), rows.data(), (int)rows.size(), 0);
+        });
+        // ---- every history drop of the call in one launch
+        if (M > 0) {
+            TagScope scope(c, "post.stream");
+            c->timed(0.0, move_bytes, [&] { launch_stream_interiors(ma, move_max, c->stream); });
+        }
+        // ---- everything is queued: the sessions' state
+        for (int i = 0; i < n; i++) {
+            zvx_stream* s = ss[i];
+            StreamStep& p = plans[i];
+            s->stages.swap(p.plan);
+            s->next_chunk = p.g.first + p.g.rows; s->emitted += p.n; s->done = p.g.last ? 1 : 0;
+            done[i] = s->done;
+        }
+        if (!(flags & ZVX_DEVICE_OUT)) {
+            for (int i = 0; i < n; i++)
+                if (n_out[i] > 0) HIPCHK(hipMemcpyAsync(ss[i]->pinned, ss[i]->ostage, (size_t)n_out[i] * 4, hipMemcpyDeviceToHost, c->stream));
+            c->sync();                                       // the call's one wait
+            for (int i = 0; i < n; i++)
+                if (n_out[i] > 0) memcpy(out[i], ss[i]->pinned, (size_t)n_out[i] * 4);
+        } else if (!(flags & ZVX_NO_SYNC)) c->sync();
+    } catch (...) {
+        for (int i = 0; i < n; i++) ss[i]->done = 1;
+        throw;
     }
 }
 
+// zvx_stream_next (include/zvx.h): its own checks, then the step of one session
 void do_stream_next(zvx_stream* s, void* out, int64_t capacity, int64_t* n_out, int32_t* done, int flags) {
     const char* who = "zvx_stream_next";
-    zvx_ctx* c = s->c;
     if (!n_out || !done) fail(ZVX_E_INVALID, "%s: %s is NULL", who, !n_out ? "n_out" : "done");
     stream_flags_check(who, flags);
     if (capacity < 0) fail(ZVX_E_INVALID, "%s: capacity %lld is negative", who, (long long)capacity);
     if (s->done) fail(ZVX_E_STATE, "%s: the stream is done (its last piece has been handed out)", who);
     StreamStep p;
     stream_plan_step(who, s, p);
-    const int B = p.g.rows, nm = c->n_mels, Pmax = (int)p.g.Pmax;
-    const int64_t n = p.n, n_new = p.g.n_new;
+    const int64_t n = p.n;
     *n_out = n;
     if (n > 0 && !out) fail(ZVX_E_INVALID, "%s: out is NULL", who);
     if (capacity < n) fail(ZVX_E_BUFFER, "%s: capacity %lld < %lld samples of this piece (nothing was consumed)", who, (long long)capacity, (long long)n);
-    // ---- from here on the call consumes the group; a failure past this point ends the session
-    try {
-        c->have_features = false; c->have_mel = false;      // as zvx_vocode_mel: the context's intermediates are void
-        StreamRowsArgs ra{};
-        StreamInteriorArgs ia{};
-        for (int i = 0; i < B; i++) {
-            ra.lo[i] = (int)p.rows[i].lo; ra.P[i] = p.P[i];
-            ia.off[i] = (int)p.rows[i].off; ia.cnt[i] = (int)p.rows[i].cnt; ia.pos[i] = (long)p.rows[i].pos;
-        }
-        ra.mel = s->mel; ra.out = s->rows; ra.B = B; ra.Pmax = Pmax; ra.nm = nm;
-        {
-            TagScope scope(c, "voc.stream");
-            double rd = 0; for (int i = 0; i < B; i++) rd += (double)p.P[i] * nm * 4.0;
-            c->timed(0.0, rd + (double)B * Pmax * nm * 4.0, [&] { launch_stream_rows(ra, c->stream); });
-        }
-        c->stage_begin(ZVX_T_VOCODER);
-        run_vocoder(c, s->rows, nm, Pmax, p.P, p.P, B, s->wav, s->wstride, 0);   // the rows of ZeroVox._vocode_stream_native, at the native rate
-        c->stage_end(ZVX_T_VOCODER);
-        float* final_dst = (flags & ZVX_DEVICE_OUT) ? (float*)out : s->ostage;
-        ia.wav = s->wav; ia.w_bs = s->wstride; ia.B = B;
-        ia.out = stream_new_dst(s, final_dst);
-        {
-            TagScope scope(c, "voc.stream");
-            c->timed(0.0, 8.0 * (double)n_new, [&] { launch_stream_interiors(ia, (long)p.g.cnt_max, c->stream); });
-        }
-        stream_run_stages(who, s, p, final_dst);
-        *done = s->done;
-        if (!(flags & ZVX_DEVICE_OUT)) {
-            if (n > 0) HIPCHK(hipMemcpyAsync(s->pinned, s->ostage, (size_t)n * 4, hipMemcpyDeviceToHost, c->stream));
-            c->sync();                                       // the call's one wait
-            if (n > 0) memcpy(out, s->pinned, (size_t)n * 4);
-        } else if (!(flags & ZVX_NO_SYNC)) c->sync();
-    } catch (...) {
-        s->done = 1;
-        throw;
-    }
+    stream_step(who, s->c, &s, &p, 1, &out, n_out, done, flags);
 }
 
-// zvx_stream_next_many (include/zvx.h): the groups of n sessions of one context as ONE batch of the vocoder.  Per session it is
-// do_stream_next -- the same plan, the same stages, the same state afterwards --; what differs is that the rows of all sessions are
-// gathered by one launch, vocoded by one run_vocoder and scattered by one launch to where each session's first stage reads them, and that
-// the denoisers and limiters of all sessions run as per-row batches (stream_run_stages_many).
+// zvx_stream_next_many (include/zvx.h): its own checks and every session's plan, then the step of all of them
 void do_stream_next_many(zvx_ctx* c, zvx_stream* const* ss, int n, void* const* out, const int64_t* capacity, int64_t* n_out, int32_t* done,
                          int flags) {
     const char* who = "zvx_stream_next_many";
@@ -3596,80 +3569,23 @@ void do_stream_next_many(zvx_ctx* c, zvx_stream* const* ss, int n, void* const* 
         if (ss[i]->done) fail(ZVX_E_STATE, "%s: sessions[%d] is done (its last piece has been handed out; nothing was consumed)", who, i);
     // ---- the plans of all sessions: every piece's size is known before anything is queued
     std::vector<StreamStep> plans((size_t)n);
-    int R = 0;
+    int R = 0, Pmax = 0;
     for (int i = 0; i < n; i++) R += std::min(ss[i]->cpc, ss[i]->nchunks - ss[i]->next_chunk);
     if (R > STREAM_MANY_MAX_ROWS) fail(ZVX_E_UNSUPPORTED, "%s: the groups of %d sessions are %d rows (at most %d per call)", who, n, R, STREAM_MANY_MAX_ROWS);
-    int Pmax = 0; long cnt_max = 0; double rows_bytes = 0, new_bytes = 0;
-    const int nm = c->n_mels, hop = c->hop;
     for (int i = 0; i < n; i++) {
-        StreamStep& p = plans[(size_t)i];
-        stream_plan_step(who, ss[i], p);
-        n_out[i] = p.n;
-        Pmax = std::max(Pmax, (int)p.g.Pmax); cnt_max = std::max(cnt_max, (long)p.g.cnt_max);
-        for (int j = 0; j < p.g.rows; j++) rows_bytes += (double)p.P[j] * nm * 4.0;        // what the single-session gathers count
-        rows_bytes += (double)p.g.rows * (double)p.g.Pmax * nm * 4.0;
-        new_bytes += 8.0 * (double)p.g.n_new;
+        stream_plan_step(who, ss[i], plans[(size_t)i]);
+        n_out[i] = plans[(size_t)i].n;
+        Pmax = std::max(Pmax, (int)plans[(size_t)i].g.Pmax);
     }
-    if ((int64_t)R * Pmax * std::max(hop, nm) > (int64_t)1 << 28)
-        fail(ZVX_E_UNSUPPORTED, "%s: %d rows of %d frames are %lld samples (at most 2^28 per call)", who, R, Pmax, (long long)R * Pmax * hop);
+    if ((int64_t)R * Pmax * std::max(c->hop, c->n_mels) > (int64_t)1 << 28)
+        fail(ZVX_E_UNSUPPORTED, "%s: %d rows of %d frames are %lld samples (at most 2^28 per call)", who, R, Pmax, (long long)R * Pmax * c->hop);
     for (int i = 0; i < n; i++)
         if (n_out[i] > 0 && (!out || !out[i])) fail(ZVX_E_INVALID, "%s: %s is NULL", who, !out ? "out" : ("out[" + std::to_string(i) + "]").c_str());
     for (int i = 0; i < n; i++)
         if (capacity[i] < n_out[i])
             fail(ZVX_E_BUFFER, "%s: capacity[%d] %lld < %lld samples of this piece (nothing was consumed in any session)", who, i,
                  (long long)capacity[i], (long long)n_out[i]);
-    // ---- from here on the call consumes the groups; a failure past this point ends every session of the call
-    try {
-        c->have_features = false; c->have_mel = false;      // as zvx_vocode_mel: the context's intermediates are void
-        const long wstride = ((long)Pmax * hop + 7) & ~7L;
-        // (the table's buffer is taken at its largest size at once: it never grows behind a queued call)
-        char* tab_d = (char*)c->buf("stream.tab", (size_t)STREAM_MANY_MAX_ROWS * (sizeof(StreamManyRow) + sizeof(StreamManyInterior)));
-        float* rows_d = c->fbuf("stream.rows", (size_t)R * Pmax * nm);
-        float* wav_d = c->fbuf("stream.wav", (size_t)R * wstride);
-        std::vector<char> tab((size_t)R * (sizeof(StreamManyRow) + sizeof(StreamManyInterior)));
-        StreamManyRow* tr = (StreamManyRow*)tab.data();
-        StreamManyInterior* ti = (StreamManyInterior*)(tab.data() + (size_t)R * sizeof(StreamManyRow));
-        std::vector<int> P((size_t)R);
-        std::vector<float*> final_dst((size_t)n);
-        int r = 0;
-        for (int i = 0; i < n; i++) {
-            zvx_stream* s = ss[i];
-            const StreamStep& p = plans[(size_t)i];
-            final_dst[(size_t)i] = (flags & ZVX_DEVICE_OUT) ? (float*)out[i] : s->ostage;
-            float* base = stream_new_dst(s, final_dst[(size_t)i]);
-            for (int j = 0; j < p.g.rows; j++, r++) {
-                P[(size_t)r] = p.P[j];
-                tr[r] = StreamManyRow{s->mel + p.rows[j].lo * nm, p.P[j], 0};
-                ti[r] = StreamManyInterior{base + p.rows[j].pos, nullptr, (int)p.rows[j].off, (int)p.rows[j].cnt};
-            }
-        }
-        c->upload(tab_d, tab.data(), tab.size());
-        StreamManyRowsArgs ra{(const StreamManyRow*)tab_d, rows_d, R, Pmax, nm};
-        StreamManyInteriorArgs ia{(const StreamManyInterior*)(tab_d + (size_t)R * sizeof(StreamManyRow)), wav_d, wstride, R};
-        {
-            TagScope scope(c, "voc.stream");
-            c->timed(0.0, rows_bytes, [&] { launch_stream_rows_many(ra, c->stream); });
-        }
-        c->stage_begin(ZVX_T_VOCODER);
-        run_vocoder(c, rows_d, nm, Pmax, P.data(), P.data(), R, wav_d, wstride, 0);       // ONE batch: the rows of every session, at the native rate
-        c->stage_end(ZVX_T_VOCODER);
-        {
-            TagScope scope(c, "voc.stream");
-            c->timed(0.0, new_bytes, [&] { launch_stream_interiors_many(ia, cnt_max, c->stream); });
-        }
-        stream_run_stages_many(who, c, ss, plans, final_dst, n);
-        for (int i = 0; i < n; i++) done[i] = ss[i]->done;
-        if (!(flags & ZVX_DEVICE_OUT)) {
-            for (int i = 0; i < n; i++)
-                if (n_out[i] > 0) HIPCHK(hipMemcpyAsync(ss[i]->pinned, ss[i]->ostage, (size_t)n_out[i] * 4, hipMemcpyDeviceToHost, c->stream));
-            c->sync();                                       // the call's one wait
-            for (int i = 0; i < n; i++)
-                if (n_out[i] > 0) memcpy(out[i], ss[i]->pinned, (size_t)n_out[i] * 4);
-        } else if (!(flags & ZVX_NO_SYNC)) c->sync();
-    } catch (...) {
-        for (int i = 0; i < n; i++) ss[i]->done = 1;
-        throw;
-    }
+    stream_step(who, c, ss, plans.data(), n, out, n_out, done, flags);
 }
 
 void do_stream_info(const zvx_stream* s, int64_t* info, int n_info) {

@@ -476,37 +476,24 @@ struct JoinCopyArgs {
     void* out; long cap; int pcm16, fade;
 };
 void launch_join_copy(const JoinCopyArgs& a, long upper, hipStream_t s);
-// The two gathers of a stream session (include/zvx.h, zvx_stream_next): pure data movement, 16-byte loads / stores where source and
-// destination addresses allow, scalar otherwise.  The per-row tables travel in the kernel arguments (a group has at most
-// STREAM_MAX_ROWS rows), so no call uploads one.
+// The two gathers of a stream step (include/zvx.h, zvx_stream_next / zvx_stream_next_many): pure data movement, 16-byte loads / stores
+// where source and destination addresses allow, scalar otherwise.  A step serves up to STREAM_MANY_MAX_ROWS rows of up to
+// STREAM_MANY_MAX_SESSIONS sessions, each row with a source / destination POINTER of its own, so the per-row tables live in device memory:
+// built on the host and uploaded through the context's pinned arena (queued like a launch, no host wait) -- a step of ONE session uploads
+// its small table the same way.  One small entry per row.
 constexpr int STREAM_MAX_ROWS = 64;          // zvx_stream_params.chunks_per_call
-// Rows: row b of out [B][Pmax][nm] = mel frames [lo[b], lo[b] + P[b]) of mel [frames][nm], then zeros up to Pmax frames.
-struct StreamRowsArgs {
-    const float* mel; float* out; int B, Pmax, nm;
-    int lo[STREAM_MAX_ROWS], P[STREAM_MAX_ROWS];
-};
-void launch_stream_rows(const StreamRowsArgs& a, hipStream_t s);
-// Interiors: out[pos[b] + i] = wav[b][off[b] + i] for i < cnt[b]: the rows' kept samples as one contiguous run (pos: the prefix sum of cnt).
-struct StreamInteriorArgs {
-    const float* wav; long w_bs; float* out; int B;
-    int off[STREAM_MAX_ROWS], cnt[STREAM_MAX_ROWS]; long pos[STREAM_MAX_ROWS];
-};
-void launch_stream_interiors(const StreamInteriorArgs& a, long cnt_max, hipStream_t s);
-// The same for the rows of many sessions at once (zvx_stream_next_many: up to STREAM_MANY_MAX_ROWS rows, each with a source / destination
-// POINTER of its own): the tables no longer fit the kernel arguments and live in device memory, built on the host and uploaded through the
-// context's pinned arena (queued like a launch, no host wait).  One small entry per row.
 constexpr int STREAM_MANY_MAX_SESSIONS = 64;  // ZVX_STREAM_MANY_MAX_SESSIONS
 constexpr int STREAM_MANY_MAX_ROWS = 256;     // ZVX_STREAM_MANY_MAX_ROWS
 // Rows: row r of out [R][Pmax][nm] = the P frames at src ([P][nm], inside the owning session's mel), then zeros up to Pmax frames.
-struct StreamManyRow { const float* src; int P; int pad_; };
-struct StreamManyRowsArgs { const StreamManyRow* tab; float* out; int R, Pmax, nm; };
-void launch_stream_rows_many(const StreamManyRowsArgs& a, hipStream_t s);
+struct StreamRow { const float* src; int P; int pad_; };
+struct StreamRowTab { const StreamRow* tab; float* out; int R, Pmax, nm; };
+void launch_stream_rows(const StreamRowTab& a, hipStream_t s);
 // Interiors: dst[i] = wav[r][off + i] for i < cnt; dst lies in memory of the owning session (or is the caller's), rows of one session back to back.
 // An entry with a source of its own (src != NULL) copies src[off + i] instead: the history drops of the sessions' stages are such a table,
 // one launch for all of them, each retained tail into its stage's OTHER buffer (source and destination never overlap).
-struct StreamManyInterior { float* dst; const float* src; int off, cnt; };
-struct StreamManyInteriorArgs { const StreamManyInterior* tab; const float* wav; long w_bs; int R; };
-void launch_stream_interiors_many(const StreamManyInteriorArgs& a, long cnt_max, hipStream_t s);
+struct StreamInterior { float* dst; const float* src; int off, cnt; };
+struct StreamInteriorTab { const StreamInterior* tab; const float* wav; long w_bs; int R; };
+void launch_stream_interiors(const StreamInteriorTab& a, long cnt_max, hipStream_t s);
 // Integrated loudness (ITU-R BS.1770 / EBU R128) and gain of a batch's waveform rows (include/zvx.h, zvx_loudness / zvx_normalize): every
 // decision is made on the DEVICE, in double, in the power domain.
 // K-weighting: struct LoudCoef, declared with the leveler above (it shares the coefficients).
