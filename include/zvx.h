@@ -434,6 +434,65 @@ zvx_status zvx_loudness_stats(zvx_ctx* ctx, const float* in, const int32_t* nsam
                               double* short_term,   /* host [B][curve_stride] or NULL: S[j] in LUFS */
                               int64_t curve_stride, int flags /* ZVX_DEVICE_IN only */);
 
+/* Pitch report: the fundamental frequency (F0) track of every row of a batch on a frame grid, and its statistics, measured on the device --
+ * the meter of the prosody controls (pitch_shift, pitch_range, pitch_target act in the model's bucket units; this reads the audio they
+ * made).  Rows in [B][Nmax] f32 with nsamples[b] valid samples at `rate` Hz.  The estimator is YIN (de Cheveigne and Kawahara 2002, steps
+ * 1 to 5), restated so that every decision is decidable the way the gates of zvx_loudness are.
+ * Setup, per row of n samples at fs = rate: tau_min = max(2, floor(fs / fmax)) and tau_max = ceil(fs / fmin), both formed on the host in
+ *   double;  c = (W + tau_max) / 2 (integer division);  F = n / H frames (integer division: with H = the model's hop and a synthesised
+ *   waveform of mel_len * hop samples a frame is a mel frame).
+ * Per frame f < F, with s = f H - c, so that frame f is centred on sample f H:
+ *   Samples: v[j] = (double) x[s + j], 0 <= j < W + tau_max; samples outside [0, n) are zero; nothing outside the row is read.
+ *   Power gate: P = (sum_{j < W} v[j]^2) / W; the frame is voiced only if P > 10^(gate_db / 10) (computed once on the host in double).
+ *   Difference: d[tau] = sum_{j < W} (v[j] - v[j + tau])^2, tau = 1 .. tau_max, in double, in any summation order.
+ *   Normalisation: c[tau] = d[1] + ... + d[tau];  d'[tau] = d[tau] tau / c[tau] where c[tau] > 0, otherwise 1.
+ *   Pick: T = the smallest tau in [tau_min, tau_max] with d'[tau] < threshold; none: the frame is unvoiced.  Otherwise descend: while
+ *     T + 1 <= tau_max and d'[T + 1] < d'[T], T = T + 1.
+ *   Refinement, where T - 1 >= 1 and T + 1 <= tau_max: a = d'[T - 1], b = d'[T], e = d'[T + 1], den = a - 2 b + e; if den > 0 and
+ *     |(a - e) / (2 den)| <= 1 then delta = (a - e) / (2 den), otherwise (and without both neighbours) delta = 0;
+ *     f0 = fs / (T + delta) in double, rounded once to f32.
+ *   Outputs: f0[b][f] = that value, 0 for an unvoiced frame;  aper[b][f] = d'[T] for a voiced frame, otherwise the minimum of d' over
+ *     [tau_min, tau_max], rounded to f32.
+ *   A frame is AMBIGUOUS, and either decision is allowed, when P lies within a relative 1e-9 of the gate, any d'[tau] in
+ *     [tau_min, tau_max] within a relative 1e-9 of the threshold, or two neighbours compared during the descent within a relative 1e-9
+ *     of equality.  Every term of d is non-negative, so the summation order moves d' by about W 2^-53, far inside that band.
+ *   Elsewhere f0 and aper lie within one f32 ulp (a relative 6e-8) of the sequential double sums; measured on an MI355X against
+ *     tests/pitch_ref.py (tests/test_pitch_gpu.py): a largest relative deviation of 0, every f32 bit equal.
+ * Statistics, in double: FRAMES = F;  VOICED = n_v, the number of voiced frames;  k[0 .. n_v) the voiced f0 sorted ascending and, nearest
+ *   rank with integer divisions as for LRA, MEDIAN = k[((n_v - 1) * 50 + 50) / 100], LOW = k[((n_v - 1) * 5 + 50) / 100],
+ *   HIGH = k[((n_v - 1) * 95 + 50) / 100];  MEAN = the mean of the voiced f0.  n_v == 0: all four are 0.
+ * Rows are independent: a row's bits depend neither on B, nor on Nmax, nor on its neighbours.  n < H gives F = 0 and writes nothing for that
+ *   row; only entries [0, F) of a curve row are written.  Non-finite input: zvx_vocode_mel's rule -- the call succeeds, that row is
+ *   unspecified, every other row keeps its bits.
+ * Launches: one workgroup of 256 lanes per run of G consecutive frames of a row (G <= 8, chosen from H, W and tau_max alone) stages their
+ *   (G - 1) H + W + tau_max samples once in LDS as doubles; lane l owns the lags l + 1, l + 257, ..., each with its own double accumulator;
+ *   d goes to LDS, an inclusive scan forms c, the first crossing is a minimum-index reduction, one lane descends and refines.  Then one
+ *   workgroup per row forms n_v and the mean in a fixed order, and zvx_loudness_stats's selection without a sort (rank counts, ties broken
+ *   by index) picks the three ranks.  No atomics, no workgroup that waits for another.  The call waits once, for the host outputs.
+ * Validation, before anything is queued (ZVX_E_INVALID, the context stays usable): the checks zvx_loudness_stats makes on ctx / in /
+ *   nsamples / B / Nmax / lengths / rate / flags; a NULL params or stats; fmin, fmax, threshold or gate_db not finite or outside the ranges
+ *   below; tau_max < tau_min + 2; window < 2 or hop < 1; f_stride < max(1, Nmax / hop) while a curve is asked for.
+ *   ZVX_E_UNSUPPORTED: more than 65535 rows; window > 4096 or tau_max > 2048 (the LDS plan: 6144 staged doubles and 8 lags per lane; the
+ *   defaults of Context.pitch -- 60 .. 500 Hz, window = 2 tau_max -- fit from 4 kHz to 122 kHz: tau_max = 800, W = 1600 at 48 kHz); a row
+ *   of more than 65536 frames (zvx_loudness_stats's bound, for the same quadratic selection).
+ * Stage tag "post.pitch" (one timed group per call): algorithmic bytes = 4 sum(n).
+ * Not here: a windowed or streaming form, octave-jump smoothing across frames (pYIN), the normalisation of Hz into pitch_target's [0, 1]
+ * (zerovox_amd.pitch.per_phoneme gives the per-phoneme Hz it starts from), a speaker-similarity figure. */
+typedef struct zvx_pitch_params {
+    float   fmin, fmax;   /* search range in Hz, finite, 0 < fmin < fmax */
+    float   threshold;    /* absolute threshold on d', in (0, 1] (0.15 is YIN's) */
+    float   gate_db;      /* a frame whose mean power is not above 10^(gate_db / 10) is unvoiced; finite, <= 0 */
+    int32_t window;       /* W: samples integrated per lag, >= 2 */
+    int32_t hop;          /* H: samples between frames, >= 1 */
+} zvx_pitch_params;
+enum { ZVX_PS_FRAMES = 0, ZVX_PS_VOICED, ZVX_PS_MEDIAN, ZVX_PS_LOW, ZVX_PS_HIGH, ZVX_PS_MEAN, ZVX_PS_COUNT = 6 };
+zvx_status zvx_pitch(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, int rate,
+                     const zvx_pitch_params* params,
+                     float* f0,       /* host [B][f_stride] or NULL: Hz, 0 = unvoiced */
+                     float* aper,     /* host [B][f_stride] or NULL: d' at the pick */
+                     int64_t f_stride, int32_t* frames /* host [B] or NULL */,
+                     double* stats    /* host [B][ZVX_PS_COUNT], required */, int flags /* ZVX_DEVICE_IN only */);
+
 /* True-peak metering and a look-ahead limiter for rows in [B][Nmax] f32 with nsamples[b] valid samples at `rate` Hz.  Rows are independent;
  * nothing sees a neighbouring row or the padding.  The algorithm has finite support and no recurrence, so it is defined to the bit where
  * the other post-processing is.  Per row of n samples:

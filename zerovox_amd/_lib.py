@@ -27,7 +27,8 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_encode_ex", "zvx_synthesize_ex", "zvx_resample", "zvx_resample_ex", "zvx_trim_bounds", "zvx_join",
            "zvx_loudness", "zvx_normalize", "zvx_true_peak", "zvx_limit", "zvx_spkemb_wav", "zvx_limit_ex", "zvx_denoise_bias", "zvx_denoise",
            "zvx_denoise_ex", "zvx_stream_open", "zvx_stream_next", "zvx_stream_info", "zvx_stream_close", "zvx_stream_next_many",
-           "zvx_denoise_rows", "zvx_limit_rows", "zvx_resample_rows", "zvx_level", "zvx_level_ex", "zvx_level_rows", "zvx_loudness_stats")
+           "zvx_denoise_rows", "zvx_limit_rows", "zvx_resample_rows", "zvx_level", "zvx_level_ex", "zvx_level_rows", "zvx_loudness_stats",
+           "zvx_pitch")
 ZVX_STREAM_MANY_MAX_SESSIONS, ZVX_STREAM_MANY_MAX_ROWS = 64, 256
 ZVX_COMM_ID_BYTES = 128
 ZVX_LOUD_PER_ROW, ZVX_LOUD_COMMON = 0, 1
@@ -36,6 +37,10 @@ ZVX_LOUD_PER_ROW, ZVX_LOUD_COMMON = 0, 1
  ZVX_LS_COUNT) = range(9)
 LOUDNESS_STATS_KEYS = ("integrated", "max_momentary", "max_short_term", "lra", "lra_low", "lra_high", "short_gated", "peak")
 LOUDNESS_STATS_MAX_UNITS = 65536                     # the longest row zvx_loudness_stats takes, in 100 ms units
+# columns of zvx_pitch's stats[B][ZVX_PS_COUNT], and the keys Context.pitch gives them
+ZVX_PS_FRAMES, ZVX_PS_VOICED, ZVX_PS_MEDIAN, ZVX_PS_LOW, ZVX_PS_HIGH, ZVX_PS_MEAN, ZVX_PS_COUNT = range(7)
+PITCH_STATS_KEYS = ("frames", "voiced", "median", "low", "high", "mean")
+PITCH_MAX_WINDOW, PITCH_MAX_TAU, PITCH_MAX_FRAMES = 4096, 2048, 65536     # zvx_pitch's caps (csrc/zvx_kernels.h; ZVX_E_UNSUPPORTED beyond)
 LIMIT_TILE = 1024                                    # samples per workgroup of both limiter kernels (csrc/zvx_kernels.h, LIMIT_TILE)
 LIMIT_MAX_W = 4096                                   # the longest window, in samples (LIMIT_MAX_W)
 LIMIT_ENV_REACH = 11                                 # samples the oversampled envelope reads to either side (LIMIT_ENV_REACH; limiter.reach)
@@ -78,6 +83,12 @@ class LimitParams(C.Structure):
 class LevelParams(C.Structure):
     """zvx_level_params (include/zvx.h)"""
     _fields_ = [("target_lufs", C.c_float), ("max_gain_db", C.c_float), ("window_ms", C.c_float), ("lookahead_ms", C.c_float)]
+
+
+class PitchParams(C.Structure):
+    """zvx_pitch_params (include/zvx.h)"""
+    _fields_ = [("fmin", C.c_float), ("fmax", C.c_float), ("threshold", C.c_float), ("gate_db", C.c_float), ("window", C.c_int32),
+                ("hop", C.c_int32)]
 
 
 class DenoiseParams(C.Structure):
@@ -160,6 +171,7 @@ def load():
     lib.zvx_loudness.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int]
     lib.zvx_normalize.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(LoudnessParams), vp, C.c_int64, vp, vp, vp, C.c_int]
     lib.zvx_loudness_stats.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int64, C.c_int]
+    lib.zvx_pitch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PitchParams), vp, vp, C.c_int64, vp, vp, C.c_int]
     lib.zvx_true_peak.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int]
     lib.zvx_limit.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(LimitParams), vp, C.c_int64, vp, vp, C.c_int]
     lib.zvx_limit_ex.argtypes = lib.zvx_limit.argtypes + [C.c_int64, C.c_int64, C.c_int64, C.c_int]
@@ -481,6 +493,42 @@ class Context:
             U = n.astype(np.int64) // h
             res["momentary"] = [momentary[b, :max(U[b] - 3, 0)] for b in range(B)]
             res["short_term"] = [short_term[b, :max(U[b] - 29, 0)] for b in range(B)]
+        return res
+
+    def pitch(self, rows, rate=None, fmin=60.0, fmax=500.0, threshold=0.15, gate_db=-60.0, window=None, hop=None, lengths=None, curves=True):
+        """zvx_pitch: the F0 track (YIN) of every row on a frame grid and its statistics -> a dict of [B] arrays: frames (int32), voiced
+        (float64, like the rest: their counts), median, low, high (Hz: the 50th, 5th and 95th percentile of the voiced frames, nearest rank) and mean (Hz); all four
+        are 0 where nothing is voiced.  curves: also f0 (Hz, 0 = unvoiced) and aper (d' at the pick: near 0 for a clean period, towards 1
+        for noise), lists of B float32 arrays of each row's own frames.  fmin / fmax: the search range; threshold: YIN's absolute
+        threshold on d'; gate_db: frames whose mean power is not above it are unvoiced.  window: samples integrated per lag (None: two
+        periods of fmin); hop: samples between frames (None: the model's hop at the model's rate, otherwise 10 ms); frame f is centred on
+        sample f * hop.  rows: a list of 1-D float waveforms, or a padded 2-D array + lengths; rate None: the model's sampling rate."""
+        x, n = self._rows(rows, lengths)
+        return self._pitch(_ptr(x), n, x.shape[1], rate, 0, fmin, fmax, threshold, gate_db, window, hop, curves)
+
+    def pitch_device(self, ptr, lengths, Nmax, rate=None, fmin=60.0, fmax=500.0, threshold=0.15, gate_db=-60.0, window=None, hop=None, curves=True):
+        """zvx_pitch on device rows [B][Nmax] f32 at `ptr` (ZVX_DEVICE_IN; stream order is the fence) -> as pitch()."""
+        return self._pitch(C.c_void_p(int(ptr)), _i32(lengths), int(Nmax), rate, ZVX_DEVICE_IN, fmin, fmax, threshold, gate_db, window, hop, curves)
+
+    def _pitch(self, xptr, n, Nmax, rate, flags, fmin, fmax, threshold, gate_db, window, hop, curves):
+        from . import pitch as _p
+        B, rate = len(n), self._rate(rate)
+        if window is None:
+            window = _p.default_window(rate, fmin) if float(fmin) > 0.0 and np.isfinite(fmin) else 2
+        if hop is None:
+            hop = _p.default_hop(rate, self.get_int("sampling_rate"), self.hop)
+        prm = PitchParams(float(fmin), float(fmax), float(threshold), float(gate_db), int(window), int(hop))
+        stats = np.zeros((B, ZVX_PS_COUNT), np.float64)
+        fr = np.zeros(B, np.int32)
+        stride = max(1, Nmax // max(int(hop), 1))
+        f0 = np.zeros((B, stride), np.float32) if curves else None
+        aper = np.zeros((B, stride), np.float32) if curves else None
+        self._chk(self._lib.zvx_pitch(self._h, xptr, _ptr(n), B, Nmax, rate, C.byref(prm), _ptr(f0), _ptr(aper), stride, _ptr(fr), _ptr(stats), flags))
+        res = {k: stats[:, i].copy() for i, k in enumerate(PITCH_STATS_KEYS)}
+        res["frames"] = fr
+        if curves:
+            res["f0"] = [f0[b, :fr[b]] for b in range(B)]
+            res["aper"] = [aper[b, :fr[b]] for b in range(B)]
         return res
 
     def normalize(self, rows, target, *, peak_ceiling=0.891, max_gain_db=20.0, common=False, pcm16=False, rate=None, lengths=None):

@@ -1986,6 +1986,212 @@ void launch_loud_rank(const LoudStatsArgs& a, long w_max, hipStream_t s) {
     hipLaunchKernelGGL(k_loud_rank, dim3((unsigned)((w_max + 255) / 256), a.B), dim3(256), 0, s, a);
 }
 
+// ---- pitch report (zvx_kernels.h, include/zvx.h: zvx_pitch)
+// smallest value over the workgroup's 256 threads (exact: any order); `red` holds 4 ints
+__device__ __forceinline__ int wg_min_i32(int v, int* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
+    __syncthreads();                                          // the previous reduction's readers are done
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return min(min(red[0], red[1]), min(red[2], red[3]));
+}
+__device__ __forceinline__ double wg_min_f64(double v, double* red) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = fmin(v, __shfl_xor(v, o, 64));
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return fmin(fmin(red[0], red[1]), fmin(red[2], red[3]));
+}
+// Workgroup (blk, b) takes frames [blk G, blk G + G) of row b.  Their samples -- positions [f0 H - c, f0 H - c + span) of the row, zeros
+// where the position lies outside [0, n) -- are staged once in LDS as doubles: 16-byte groups aligned as ADDRESSES, a group that straddles
+// an end of the row sample by sample.  Per frame lane l owns the lags l + 1 + 256 k, k < KL, each with its own accumulator: v[j] is one
+// address for the whole wave (a broadcast), v[j + tau] consecutive doubles across the lanes (no bank conflict).  A lane whose lag lies
+// beyond tau_max reads lag 1 instead and drops the sum.  d goes to LDS; thread t then owns lags t KL + 1 .. (t + 1) KL for the scan, d' and
+// the crossing.  Every step of a frame is the same whatever its place in the run: a row's bits do not depend on the grid.
+template <int KL>
+__global__ __launch_bounds__(256) void k_pitch_track(const PitchArgs a) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char sm[];      // (no static LDS: the opt-in beyond 64 KiB is for the dynamic block)
+    const PitchRow r = a.rows[blockIdx.y];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long fb = (long)blockIdx.x * a.G;
+    if (fb >= r.F) return;                                    // (uniform over the workgroup, before any barrier)
+    const int W = a.W, H = a.H, tmax = a.tau_max, tmin = a.tau_min, n = r.n;
+    double* vs = (double*)sm;                                 // [span]
+    double* dl = vs + a.span;                                 // [tau_max + 1], d then d' by lag (entry 0 unused)
+    double* red = dl + tmax + 1;                              // [4]
+    int* redi = (int*)(red + 4);                              // [4]
+    const int nf = (int)(r.F - fb < a.G ? r.F - fb : a.G);
+    {
+        const long s0 = fb * H - a.c;                         // the row position of vs[0]
+        const int mis = (int)(((size_t)r.x >> 2) & 3);        // r.x - mis is 16-byte aligned
+        const long base = s0 - ((s0 + mis) & 3);              // the aligned group that holds s0
+        const int groups = (int)((s0 + a.span - base + 3) >> 2);
+        for (int g = tid; g < groups; g += 256) {
+            const long pg = base + 4L * g;
+            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (pg >= 0 && pg + 4 <= n) v = *(const float4*)(r.x + pg);
+            else {
+                if (pg >= 0 && pg < n) v.x = r.x[pg];
+                if (pg + 1 >= 0 && pg + 1 < n) v.y = r.x[pg + 1];
+                if (pg + 2 >= 0 && pg + 2 < n) v.z = r.x[pg + 2];
+                if (pg + 3 >= 0 && pg + 3 < n) v.w = r.x[pg + 3];
+            }
+            const long i = pg - s0;                           // -3 .. span - 1
+            if (i >= 0 && i < a.span) vs[i] = (double)v.x;
+            if (i + 1 >= 0 && i + 1 < a.span) vs[i + 1] = (double)v.y;
+            if (i + 2 >= 0 && i + 2 < a.span) vs[i + 2] = (double)v.z;
+            if (i + 3 >= 0 && i + 3 < a.span) vs[i + 3] = (double)v.w;
+        }
+    }
+    __syncthreads();
+    int lag[KL];
+#pragma unroll
+    for (int k = 0; k < KL; k++) { const int t = tid + 1 + 256 * k; lag[k] = t <= tmax ? t : 1; }
+    for (int g = 0; g < nf; g++) {
+        const double* v = vs + (long)g * H;
+        double acc[KL];
+#pragma unroll
+        for (int k = 0; k < KL; k++) acc[k] = 0.0;
+        int j = 0;
+        for (; j + 4 <= W; j += 4) {
+#pragma unroll
+            for (int u = 0; u < 4; u++) {
+                const double x0 = v[j + u];
+#pragma unroll
+                for (int k = 0; k < KL; k++) { const double t = x0 - v[j + u + lag[k]]; acc[k] = fma(t, t, acc[k]); }
+            }
+        }
+        for (; j < W; j++) {
+            const double x0 = v[j];
+#pragma unroll
+            for (int k = 0; k < KL; k++) { const double t = x0 - v[j + lag[k]]; acc[k] = fma(t, t, acc[k]); }
+        }
+        double pw = 0.0;
+        for (int i = tid; i < W; i += 256) pw = fma(v[i], v[i], pw);
+        const double P = wg_sum_f64(pw, red) / (double)W;     // (its first barrier: the previous frame's readers of dl are done)
+#pragma unroll
+        for (int k = 0; k < KL; k++) { const int t = tid + 1 + 256 * k; if (t <= tmax) dl[t] = acc[k]; }
+        __syncthreads();
+        // inclusive scan over the lags: thread t sums its KL lags, the threads' sums are scanned in a fixed order
+        const int t0 = tid * KL + 1;
+        double mine[KL], part = 0.0;
+#pragma unroll
+        for (int k = 0; k < KL; k++) { mine[k] = t0 + k <= tmax ? dl[t0 + k] : 0.0; part += mine[k]; }
+        double inc = part;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) { const double up = __shfl_up(inc, o, 64); if (lane >= o) inc += up; }
+        if (lane == 63) red[wave] = inc;
+        __syncthreads();
+        const double before = __shfl_up(inc, 1, 64);          // the lanes in front of this one in its wave: an exclusive scan, nothing is subtracted
+        double run = lane > 0 ? before : 0.0;                 // -> the sum of every lag in front of t0
+        for (int w = 0; w < wave; w++) run += red[w];
+        int first = 0x7fffffff;
+        double dmin = INFINITY;
+#pragma unroll
+        for (int k = 0; k < KL; k++) {
+            const int t = t0 + k;
+            run += mine[k];
+            if (t <= tmax) {
+                const double dn = run > 0.0 ? mine[k] * (double)t / run : 1.0;
+                dl[t] = dn;
+                if (t >= tmin) {
+                    dmin = fmin(dmin, dn);
+                    if (dn < a.threshold && t < first) first = t;
+                }
+            }
+        }
+        first = wg_min_i32(first, redi);
+        dmin = wg_min_f64(dmin, red);                        // (its barriers also publish d')
+        if (tid == 0) {
+            float f0 = 0.f, ap = (float)dmin;
+            if (P > a.gate && first <= tmax) {
+                int T = first;
+                while (T + 1 <= tmax && dl[T + 1] < dl[T]) T++;
+                double delta = 0.0;
+                if (T - 1 >= 1 && T + 1 <= tmax) {
+                    const double aa = dl[T - 1], bb = dl[T], ee = dl[T + 1], den = aa - 2.0 * bb + ee;
+                    if (den > 0.0) { const double q = (aa - ee) / (2.0 * den); if (fabs(q) <= 1.0) delta = q; }
+                }
+                f0 = (float)(a.fs / ((double)T + delta));
+                ap = (float)dl[T];
+            }
+            r.f0[fb + g] = f0;
+            r.aper[fb + g] = ap;
+        }
+    }
+}
+bool launch_pitch_track(const PitchArgs& a, long f_max, hipStream_t s, bool dry_run) {
+    if (a.B <= 0 || f_max <= 0) return true;
+    if (a.W > PITCH_MAX_W || a.tau_max > PITCH_MAX_TAU || a.span > PITCH_SPAN || a.G < 1) return false;
+    const size_t lds = ((size_t)a.span + (size_t)a.tau_max + 1 + 4) * sizeof(double) + 4 * sizeof(int);
+    const dim3 grid((unsigned)((f_max + a.G - 1) / a.G), a.B);
+    const int kl = (a.tau_max + 255) / 256;
+    auto go = [&](auto kfn) {
+        if (lds > 64 * 1024 && !lds_opt_in((const void*)kfn)) return false;
+        if (!dry_run) hipLaunchKernelGGL(kfn, grid, dim3(256), lds, s, a);
+        return true;
+    };
+    if (kl <= 1) return go(k_pitch_track<1>);
+    if (kl <= 2) return go(k_pitch_track<2>);
+    if (kl <= 4) return go(k_pitch_track<4>);
+    return go(k_pitch_track<8>);
+}
+// One workgroup per row: thread t owns the frames f with f % 256 == t; an unvoiced frame has f0 == 0.
+__global__ __launch_bounds__(256) void k_pitch_stats(const PitchArgs a) {
+    __shared__ double red[4];
+    const PitchRow r = a.rows[blockIdx.x];
+    const int tid = threadIdx.x;
+    double sum = 0.0, cnt = 0.0;
+    for (long f = tid; f < r.F; f += 256) { const float v = r.f0[f]; if (v > 0.f) { sum += (double)v; cnt += 1.0; } }
+    const double S = wg_sum_f64(sum, red), C = wg_sum_f64(cnt, red);
+    if (tid == 0) {
+        double* w = a.res + (long)blockIdx.x * PITCH_RES_WORDS;
+        const long nv = (long)C;
+        w[PITCH_RES_VOICED] = C; w[PITCH_RES_MEAN] = nv > 0 ? S / C : 0.0;
+        w[PITCH_RES_RANK_MED] = (double)(((nv - 1) * 50 + 50) / 100); w[PITCH_RES_RANK_LO] = (double)(((nv - 1) * 5 + 50) / 100);
+        w[PITCH_RES_RANK_HI] = (double)(((nv - 1) * 95 + 50) / 100);
+        w[PITCH_RES_MED] = 0.0; w[PITCH_RES_LO] = 0.0; w[PITCH_RES_HI] = 0.0;
+    }
+}
+void launch_pitch_stats(const PitchArgs& a, hipStream_t s) {
+    if (a.B <= 0) return;
+    hipLaunchKernelGGL(k_pitch_stats, dim3(a.B), dim3(256), 0, s, a);
+}
+// Thread j owns frame j.  Where it is voiced it counts the voiced frames i with f0[i] < f0[j], or f0[i] == f0[j] and i < j: k_loud_rank's
+// selection.  The row's track passes through LDS in tiles of 256, an unvoiced frame as +INFINITY, which precedes nothing.
+__global__ __launch_bounds__(256) void k_pitch_rank(const PitchArgs a) {
+    __shared__ float tile[256];
+    const PitchRow r = a.rows[blockIdx.y];
+    const int tid = threadIdx.x;
+    double* w = a.res + (long)blockIdx.y * PITCH_RES_WORDS;
+    if ((long)blockIdx.x * 256 >= r.F || !(w[PITCH_RES_VOICED] > 0.0)) return;       // (uniform over the workgroup)
+    const int med = (int)w[PITCH_RES_RANK_MED], lo = (int)w[PITCH_RES_RANK_LO], hi = (int)w[PITCH_RES_RANK_HI];
+    const long j = (long)blockIdx.x * 256 + tid;
+    const float vj = j < r.F ? r.f0[j] : 0.f;
+    const bool mine = vj > 0.f;
+    int cnt = 0;
+    for (long i0 = 0; i0 < r.F; i0 += 256) {
+        __syncthreads();                                      // the previous tile's readers are done
+        float v = INFINITY;
+        if (i0 + tid < r.F) { const float q = r.f0[i0 + tid]; if (q > 0.f) v = q; }
+        tile[tid] = v;
+        __syncthreads();
+        if (mine) {
+#pragma unroll 8
+            for (int k = 0; k < 256; k++) { const float q = tile[k]; cnt += (q < vj || (q == vj && i0 + k < j)) ? 1 : 0; }
+        }
+    }
+    if (mine && cnt == med) w[PITCH_RES_MED] = (double)vj;
+    if (mine && cnt == lo) w[PITCH_RES_LO] = (double)vj;
+    if (mine && cnt == hi) w[PITCH_RES_HI] = (double)vj;
+}
+void launch_pitch_rank(const PitchArgs& a, long f_max, hipStream_t s) {
+    if (a.B <= 0 || f_max <= 0) return;
+    hipLaunchKernelGGL(k_pitch_rank, dim3((unsigned)((f_max + 255) / 256), a.B), dim3(256), 0, s, a);
+}
+
 constexpr int LOUD_TILE = 4096;              // samples per workgroup: 4 groups of 4 per thread
 __global__ __launch_bounds__(256) void k_loud_apply(const LoudApplyArgs a) {
     const int b = blockIdx.y, tid = threadIdx.x;

@@ -2627,6 +2627,86 @@ void run_loudness_stats(zvx_ctx* c, const float* in, const int32_t* nsamples, in
 }
 
 // ------------------------------------------------------------------------------------------------
+// pitch report (include/zvx.h: zvx_pitch): every check, then the row table, three launches, and the result words and curves to pinned
+// host memory behind the call's one wait
+// ------------------------------------------------------------------------------------------------
+constexpr long PITCH_MAX_FRAMES = 65536;
+void do_pitch(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_pitch_params* p, float* f0, float* aper,
+              int64_t f_stride, int32_t* frames, double* stats, int flags) {
+    const char* who = "zvx_pitch";
+    const RowsInfo r = rows_check(who, in, nsamples, B, Nmax, 65535);
+    loud_rate_check(who, rate);
+    flags_check(who, flags, ZVX_DEVICE_IN);
+    if (!p) fail(ZVX_E_INVALID, "%s: params is NULL", who);
+    if (!stats) fail(ZVX_E_INVALID, "%s: stats is NULL", who);
+    if (!std::isfinite(p->fmin) || !std::isfinite(p->fmax) || !(p->fmin > 0.f) || !(p->fmin < p->fmax))
+        fail(ZVX_E_INVALID, "%s: fmin %g / fmax %g must be finite with 0 < fmin < fmax", who, (double)p->fmin, (double)p->fmax);
+    if (!std::isfinite(p->threshold) || !(p->threshold > 0.f) || p->threshold > 1.f)
+        fail(ZVX_E_INVALID, "%s: threshold %g must lie in (0, 1]", who, (double)p->threshold);
+    if (!std::isfinite(p->gate_db) || p->gate_db > 0.f) fail(ZVX_E_INVALID, "%s: gate_db %g must be finite and not positive", who, (double)p->gate_db);
+    if (p->window < 2) fail(ZVX_E_INVALID, "%s: window %d must be at least 2", who, p->window);
+    if (p->hop < 1) fail(ZVX_E_INVALID, "%s: hop %d must be at least 1", who, p->hop);
+    const double fs = (double)rate;
+    const double tmin_d = std::max(2.0, floor(fs / (double)p->fmax)), tmax_d = ceil(fs / (double)p->fmin);
+    if (tmax_d < tmin_d + 2.0)
+        fail(ZVX_E_INVALID, "%s: fmin %g / fmax %g at %d Hz give tau_max %.0f < tau_min %.0f + 2", who, (double)p->fmin, (double)p->fmax, rate, tmax_d, tmin_d);
+    const int W = p->window, H = p->hop;
+    const bool curves = f0 || aper;
+    if (curves && f_stride < std::max<int64_t>(1, Nmax / H))
+        fail(ZVX_E_INVALID, "%s: f_stride %lld is smaller than max(1, Nmax / hop) = %lld", who, (long long)f_stride, (long long)std::max<int64_t>(1, Nmax / H));
+    if (W > PITCH_MAX_W) fail(ZVX_E_UNSUPPORTED, "%s: window %d (at most %d)", who, W, PITCH_MAX_W);
+    if (tmax_d > (double)PITCH_MAX_TAU) fail(ZVX_E_UNSUPPORTED, "%s: fmin %g at %d Hz gives tau_max %.0f (at most %d)", who, (double)p->fmin, rate, tmax_d, PITCH_MAX_TAU);
+    for (int b = 0; b < B; b++)
+        if (nsamples[b] / H > PITCH_MAX_FRAMES)
+            fail(ZVX_E_UNSUPPORTED, "%s: row %d has %d frames of %d samples (at most %ld per row)", who, b, nsamples[b] / H, H, PITCH_MAX_FRAMES);
+    PitchArgs a{};
+    a.B = B; a.W = W; a.H = H; a.tau_min = (int)tmin_d; a.tau_max = (int)tmax_d; a.c = (W + a.tau_max) / 2;
+    a.fs = fs; a.threshold = (double)p->threshold; a.gate = pow(10.0, (double)p->gate_db / 10.0);
+    const long reach = (long)W + a.tau_max;
+    a.G = (int)std::max(1L, std::min<long>(PITCH_MAX_G, (PITCH_SPAN - reach) / H + 1));
+    a.span = (int)((long)(a.G - 1) * H + reach);
+    const long f_max = r.n_max / H, fpitch = std::max(f_max, 1L);
+    if (!launch_pitch_track(a, f_max, c->stream, true))       // (the last check: the LDS opt-in, before anything is allocated or queued)
+        fail(ZVX_E_UNSUPPORTED, "%s: window %d / tau_max %d do not fit the kernel's LDS plan", who, W, a.tau_max);
+    // pinned: the result words, then the two curves where asked for
+    const size_t res_bytes = (size_t)B * PITCH_RES_WORDS * sizeof(double), res_pad = (res_bytes + 255) & ~(size_t)255;
+    const size_t curve_bytes = (size_t)B * fpitch * sizeof(float);
+    char* host = (char*)c->join_pinned(res_pad + (f0 ? curve_bytes : 0) + (aper ? curve_bytes : 0));
+    const float* x = rows_to_device(c, "pitch", in, B, Nmax, flags);
+    float* f0_d = c->fbuf("pitch.f0", (size_t)2 * B * fpitch);
+    float* ap_d = f0_d + (size_t)B * fpitch;
+    a.res = (double*)c->buf("pitch.res", res_bytes);
+    std::vector<PitchRow> tab((size_t)B);
+    for (int b = 0; b < B; b++)
+        tab[(size_t)b] = PitchRow{x + (size_t)b * Nmax, f0_d + (size_t)b * fpitch, ap_d + (size_t)b * fpitch, nsamples[b], nsamples[b] / H};
+    PitchRow* tab_d = (PitchRow*)c->buf("pitch.rows", (size_t)B * sizeof(PitchRow));
+    c->upload(tab_d, tab.data(), (size_t)B * sizeof(PitchRow));
+    a.rows = tab_d;
+    TagScope scope(c, "post.pitch");
+    c->timed(0.0, 4.0 * r.n_sum, [&] {
+        if (!launch_pitch_track(a, f_max, c->stream)) fail(ZVX_E_UNSUPPORTED, "%s: window %d / tau_max %d do not fit the kernel's LDS plan", who, W, a.tau_max);
+        launch_pitch_stats(a, c->stream);
+        launch_pitch_rank(a, f_max, c->stream);
+    });
+    char* f0_h = host + res_pad; char* ap_h = f0_h + (f0 ? curve_bytes : 0);
+    HIPCHK(hipMemcpyAsync(host, a.res, res_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (f0 && f_max > 0) HIPCHK(hipMemcpyAsync(f0_h, f0_d, curve_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (aper && f_max > 0) HIPCHK(hipMemcpyAsync(ap_h, ap_d, curve_bytes, hipMemcpyDeviceToHost, c->stream));
+    c->sync();                                               // the call's one wait
+    const double* rep = (const double*)host;
+    for (int b = 0; b < B; b++) {
+        const double* w = rep + (size_t)b * PITCH_RES_WORDS;
+        double* o = stats + (size_t)b * ZVX_PS_COUNT;
+        const int F = nsamples[b] / H;
+        o[ZVX_PS_FRAMES] = (double)F; o[ZVX_PS_VOICED] = w[PITCH_RES_VOICED];
+        o[ZVX_PS_MEDIAN] = w[PITCH_RES_MED]; o[ZVX_PS_LOW] = w[PITCH_RES_LO]; o[ZVX_PS_HIGH] = w[PITCH_RES_HI]; o[ZVX_PS_MEAN] = w[PITCH_RES_MEAN];
+        if (frames) frames[b] = F;
+        if (f0 && F > 0) memcpy(f0 + (size_t)b * f_stride, f0_h + (size_t)b * fpitch * sizeof(float), (size_t)F * sizeof(float));
+        if (aper && F > 0) memcpy(aper + (size_t)b * f_stride, ap_h + (size_t)b * fpitch * sizeof(float), (size_t)F * sizeof(float));
+    }
+}
+
+// ------------------------------------------------------------------------------------------------
 // true-peak metering and the look-ahead limiter (include/zvx.h: zvx_true_peak, zvx_limit)
 // ------------------------------------------------------------------------------------------------
 // w[k] = (1 + cos(pi k / (W + 1))) / (2 (W + 1)), k = -W .. W, divided by their own sum; uploaded on first use of W, then kept.
@@ -3908,6 +3988,10 @@ zvx_status zvx_normalize(zvx_ctx* c, const float* in, const int32_t* nsamples, i
 zvx_status zvx_loudness_stats(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, double* stats, double* momentary,
                               double* short_term, int64_t curve_stride, int flags) {
     return guarded(c, [&] { run_loudness_stats(c, in, nsamples, B, Nmax, rate, stats, momentary, short_term, curve_stride, flags); });
+}
+zvx_status zvx_pitch(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_pitch_params* params, float* f0,
+                     float* aper, int64_t f_stride, int32_t* frames, double* stats, int flags) {
+    return guarded(c, [&] { do_pitch(c, in, nsamples, B, Nmax, rate, params, f0, aper, f_stride, frames, stats, flags); });
 }
 
 zvx_status zvx_true_peak(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, int oversample, float* tpeak, int flags) {

@@ -323,6 +323,43 @@ void launch_loud_windows(const LoudStatsArgs& a, hipStream_t s);
 void launch_loud_rank(const LoudStatsArgs& a, long w_max, hipStream_t s);
 
 // ------------------------------------------------------------------------------------------------
+// Pitch report (ops.hip, behind the loudness report).  A section of its own, as the two above: its three launchers are checked through the
+// C-ABI against their float64 restatement (tests/pitch_ref.py, tests/test_pitch_gpu.py).
+// ------------------------------------------------------------------------------------------------
+// include/zvx.h, zvx_pitch: YIN on a frame grid.  `rows` is a device table with one PitchRow per row, uploaded by every call through the
+// context's pinned staging arena; every kernel reads rows[blockIdx.y] at its top and works from it alone.  Nothing outside [0, n) of a
+// row is read; positions on a row are 64-bit.
+constexpr int PITCH_MAX_W = 4096;            // the longest window, in samples (include/zvx.h: ZVX_E_UNSUPPORTED beyond)
+constexpr int PITCH_MAX_TAU = 2048;          // the longest lag: 8 lags per lane
+constexpr int PITCH_MAX_G = 8;               // frames per workgroup at the most
+constexpr int PITCH_SPAN = PITCH_MAX_W + PITCH_MAX_TAU;      // staged doubles at the most: G is the largest with (G - 1) H + W + tau_max <= this
+enum { PITCH_RES_VOICED = 0, PITCH_RES_MEAN, PITCH_RES_RANK_MED, PITCH_RES_RANK_LO, PITCH_RES_RANK_HI, PITCH_RES_MED, PITCH_RES_LO,
+       PITCH_RES_HI, PITCH_RES_WORDS };
+struct PitchRow {
+    const float* x;                          // the row's samples
+    float* f0; float* aper;                  // the row's curves in device staging, F entries each
+    int n, F;                                // samples; frames = n / H
+};
+struct PitchArgs {
+    const PitchRow* rows;                    // [B], on the device
+    int B;
+    int W, H, tau_min, tau_max, c;           // window, hop, the lag range, the centring offset (W + tau_max) / 2
+    int G, span;                             // frames per workgroup; (G - 1) H + W + tau_max
+    double fs, threshold, gate;              // the rate; the threshold on d'; 10^(gate_db / 10), computed on the host in double
+    // res[b][PITCH_RES_WORDS]: n_v, the mean of the voiced f0, the three nearest-rank indices as whole doubles, the f0 of those ranks (0
+    // where n_v == 0)
+    double* res;
+};
+// grid (ceil(f_max / G), B): f0 and aper of G consecutive frames per workgroup.  false where the geometry does not fit or the runtime
+// refuses the LDS opt-in; dry_run: those checks (and the opt-in) alone, nothing is launched and `rows` is not looked at
+bool launch_pitch_track(const PitchArgs& a, long f_max, hipStream_t s, bool dry_run = false);
+// one workgroup per row: n_v, the mean in the fixed order of wg_sum_f64, the rank indices -> res[b][0 .. 4], zeros into the three values
+void launch_pitch_stats(const PitchArgs& a, hipStream_t s);
+// selection without a sort, as launch_loud_rank: grid (ceil(f_max / 256), B), thread j counts the voiced frames that precede its own in
+// (f0, index) order; the one thread whose count is a target rank stores its f0
+void launch_pitch_rank(const PitchArgs& a, long f_max, hipStream_t s);
+
+// ------------------------------------------------------------------------------------------------
 // Small kernels (ops.hip).  T-typed pointers are void* + dtype.
 // ------------------------------------------------------------------------------------------------
 // single requests: InstanceNorm statistics + affine + activation of a 16-bit tensor (x and y both DT_BF16 or DT_F16) in ONE launch

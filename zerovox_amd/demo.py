@@ -14,6 +14,8 @@ waveform on the device, directly behind the vocoder (zvx_denoise; 0.01 is the us
 --peak-db apply to the stream as well, and the pieces are joined for the WAV file.
 `--report`: the finished waveform is measured as delivered, on the device (zvx_loudness_stats, zvx_true_peak): integrated loudness, loudness
 range, maximum momentary and short-term loudness, sample and true peak are printed, and with --loudness whether it meets that target.
+`--pitch-report`: the finished waveform's F0 track is measured on the device (zvx_pitch) and its median, 5th .. 95th percentile range in Hz
+and semitones, mean and voiced fraction are printed: what --pitch-shift / --pitch-range did to the audio.
 """
 import argparse
 import os
@@ -51,6 +53,7 @@ def main():
                     help="stream the utterance and level it towards this short-term loudness on the device, e.g. -16 (default: off)")
     ap.add_argument("--long", action="store_true", help="long-form: split the text (or the file it names) into sentences and join them on the device")
     ap.add_argument("--report", action="store_true", help="measure the finished waveform on the device and print its programme loudness report")
+    ap.add_argument("--pitch-report", action="store_true", help="measure the finished waveform's F0 track on the device and print its pitch report")
     args = ap.parse_args()
     if args.level is not None and (args.long or args.loudness is not None):
         ap.error("--level streams one utterance: it goes with neither --long nor --loudness")
@@ -75,7 +78,7 @@ def main():
             wav, segments = synth.tts_long(text, spkemb, speed=args.speed, pitch_shift=args.pitch_shift, pitch_range=args.pitch_range,
                                            energy_shift=args.energy_shift, energy_range=args.energy_range, loudness=args.loudness,
                                            peak_db=args.peak_db, limiter=args.limiter, limiter_ms=args.limiter_ms, denoise=args.denoise,
-                                           report=args.report)
+                                           report=args.report, pitch_report=args.pitch_report)
             elapsed = time.time() - t0
             wav_len = (wav.shape[0] if segments else 0) / sr
             print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, {len(segments)} sentences, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")
@@ -83,6 +86,8 @@ def main():
                 write_wav_to_file(wav, length=0, filename=args.wav_filename, sample_rate=sr, hop_length=modelcfg["audio"]["hop_size"], samples=len(wav))
             if args.report and segments:
                 print_report(synth.last_report)
+            if args.pitch_report and segments:
+                print(f"pitch report: {synth.last_pitch_report}")
             if i > warmup:
                 rtf.append(wav_len / elapsed)
             continue
@@ -99,13 +104,15 @@ def main():
                 write_wav_to_file(wav, length=0, filename=args.wav_filename, sample_rate=sr, hop_length=modelcfg["audio"]["hop_size"], samples=len(wav))
             if args.report and len(wav):                             # (a stream has no buffer left to measure: the joined pieces are)
                 print_report(synth.loudness_report(wav, sr))
+            if args.pitch_report and len(wav):
+                print(f"pitch report: {synth.pitch_report(wav, sr)}")
             if i > warmup:
                 rtf.append(wav_len / elapsed)
             continue
         wav, phoneme, length = synth.tts(args.text, spkemb, speed=args.speed, pitch_shift=args.pitch_shift, pitch_range=args.pitch_range,
                                          energy_shift=args.energy_shift, energy_range=args.energy_range, loudness=args.loudness,
                                          peak_db=args.peak_db, limiter=args.limiter, limiter_ms=args.limiter_ms, denoise=args.denoise,
-                                         report=args.report)
+                                         report=args.report, pitch_report=args.pitch_report)
         elapsed = time.time() - t0
         wav_len = wav.shape[0] / sr
         print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")
@@ -114,6 +121,8 @@ def main():
                               samples=len(wav))
         if args.report and length:
             print_report(synth.last_report)
+        if args.pitch_report and length:
+            print(f"pitch report: {synth.last_pitch_report}")
         if i > warmup:
             rtf.append(wav_len / elapsed)
     if rtf:

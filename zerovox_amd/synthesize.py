@@ -191,7 +191,7 @@ class ZeroVoxTTS:
         return limit_keywords(limiter, limiter_ms, peak_db)
 
     def tts_ex(self, text: str, spkemb, duration=None, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0,
-               loudness=None, peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None, report=False):
+               loudness=None, peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None, report=False, pitch_report=False):
         """-> (wav f32[N], phoneme i32[1,T], length, mel f32[n_mels, L]); empty text -> the reference's sentinel
         (synthesize.py:213-239).  Prosody (include/zvx.h, zvx_prosody): speed = speaking-rate factor (2.0: half the frames),
         pitch / energy shift (in normalised predictor units) and range (spread about the utterance mean).
@@ -209,13 +209,19 @@ class ZeroVoxTTS:
         Its audible benefit on a real checkpoint is not measured here.
         report: False (the default: nothing is added to the call), or True: the finished waveform is measured as it is delivered -- at
         the output rate, behind every step above, on the device where its buffer is still there (include/zvx.h, zvx_loudness_stats and
-        zvx_true_peak) -- and ``last_report`` holds the report.LoudnessReport (see ``loudness_report``).  The waveform is the same."""
+        zvx_true_peak) -- and ``last_report`` holds the report.LoudnessReport (see ``loudness_report``).  The waveform is the same.
+        pitch_report: False (the default: nothing is added to the call), True, or a dict of ``pitch_report`` keywords: the delivered
+        waveform's F0 track is measured on the device (include/zvx.h, zvx_pitch) and ``last_pitch_report`` holds the pitch.PitchReport
+        with its track -- what pitch_shift / pitch_range did to the audio, in Hz and semitones.  The waveform is the same."""
+        pkw = self._pitch_keywords(pitch_report)
         prosody = self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range)
         dn = self._denoise(denoise)
         text = text.strip()
         t0 = time.time()
         phone_ids, punct_ids = self.text2phonemeids(text)
         if not phone_ids:
+            if pkw is not None:
+                self._last_pitch_report = None               # asked for, nothing to measure: not the previous call's
             return (np.array([[0.0]], dtype=np.float32), np.array([[0]], dtype=np.int32), 0,
                     np.array([[0.0]], dtype=np.float32))
         phoneme = np.array([phone_ids], dtype=np.int32)
@@ -228,6 +234,8 @@ class ZeroVoxTTS:
                                                        **({"report": True} if report else {}))
         if self._verbose:
             print(f"tts timing stats: g2p={t1 - t0}s, synth={time.time() - t1}s")
+        if pkw is not None:
+            self.pitch_report(wav, **pkw)
         return wav, phoneme, length, mel
 
     def _post(self, loudness, peak_db, limiter, limiter_ms, denoise=None):
@@ -241,11 +249,46 @@ class ZeroVoxTTS:
         return kw
 
     def tts(self, text: str, spkemb, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0, loudness=None,
-            peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None, report=False):
+            peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None, report=False, pitch_report=False):
         wav, phoneme, length, _ = self.tts_ex(text=text, spkemb=spkemb, speed=speed, pitch_shift=pitch_shift, pitch_range=pitch_range,
                                               energy_shift=energy_shift, energy_range=energy_range, loudness=loudness, peak_db=peak_db,
-                                              limiter=limiter, limiter_ms=limiter_ms, denoise=denoise, report=report)
+                                              limiter=limiter, limiter_ms=limiter_ms, denoise=denoise, report=report,
+                                              pitch_report=pitch_report)
         return wav, phoneme, length
+
+    @staticmethod
+    def _pitch_keywords(pitch_report):
+        """the pitch_report keyword of tts / tts_ex / tts_long -> None (nothing is measured) or the checked ``pitch_report`` keywords"""
+        from .pitch import check_keywords
+        if pitch_report is None or pitch_report is False:
+            return None
+        if pitch_report is True:
+            return {}
+        if not isinstance(pitch_report, dict):
+            raise ValueError(f"pitch_report must be False, True or a dict of pitch_report keywords, not {pitch_report!r}")
+        return check_keywords(pitch_report)
+
+    def pitch_report(self, wav, sampling_rate=None, **keywords):
+        """What pitch was delivered: the F0 track of a waveform at sampling_rate Hz (None: ``output_rate``), measured on the device
+        (include/zvx.h, zvx_pitch: YIN on a frame grid), and its statistics -> pitch.PitchReport: median, 5th / 95th percentile and mean
+        of the voiced frames in Hz, their span in semitones, the voiced fraction; its ``f0`` / ``aper`` hold the track (Hz per frame,
+        0 = unvoiced; pitch.per_phoneme turns it into per-phoneme values).  keywords: fmin (60), fmax (500), threshold (0.15), gate_db
+        (-60), window (two periods of fmin), hop (the model's hop at the model's rate: a frame is then a mel frame; otherwise 10 ms).
+        int16 PCM is read as the samples it encodes (/ 32760).  Also kept as ``last_pitch_report``."""
+        from .pitch import PitchReport, check_keywords
+        keywords = check_keywords(keywords)
+        wav = np.asarray(wav)
+        if wav.dtype == np.int16:
+            wav = wav.astype(np.float32) / np.float32(32760.0)
+        rate = self.output_rate if sampling_rate is None else int(sampling_rate)
+        stats = self._model.ctx.pitch([np.asarray(wav, np.float32).reshape(-1)], rate=rate, **keywords)
+        self._last_pitch_report = PitchReport.from_stats(stats)
+        return self._last_pitch_report
+
+    @property
+    def last_pitch_report(self):
+        """the pitch.PitchReport of the last tts / tts_ex / tts_long call with pitch_report or ``pitch_report`` call (None before)"""
+        return getattr(self, "_last_pitch_report", None)
 
     def loudness_report(self, wav, sampling_rate=None):
         """What was delivered: the programme loudness report of a waveform at sampling_rate Hz (None: ``output_rate``), measured on the
@@ -421,7 +464,8 @@ class ZeroVoxTTS:
 
     def tts_long(self, text: str, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20, fade_ms=5, max_batch=32, max_frames=2048, pcm16=False,
                  durations=None, max_chars=200, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0,
-                 loudness=None, peak_db=-1.0, loudness_mode="paragraph", limiter=False, limiter_ms=5.0, denoise=None, report=False):
+                 loudness=None, peak_db=-1.0, loudness_mode="paragraph", limiter=False, limiter_ms=5.0, denoise=None, report=False,
+                 pitch_report=False):
         """A paragraph -> (wav, segments): one waveform with every sentence in text order (not in the reference).  The text is split by
         longform.split_sentences; the sentences run in batches of at most max_batch, each batch ONE queued synthesize call into
         consecutive rows of one device buffer (every row is the fresh-model ``tts`` of its sentence; a sentence of more than max_frames
@@ -449,13 +493,30 @@ class ZeroVoxTTS:
         report: False (the default: nothing is added to the call), or True: the joined waveform is measured as it is delivered, at the
         output rate, and ``last_report`` holds its report.LoudnessReport (see ``loudness_report``).  A float waveform at the model's
         rate is joined into a device buffer, measured there and copied to the host afterwards -- the same bits as without the report --;
-        a converted or int16 waveform is measured as it arrives."""
+        a converted or int16 waveform is measured as it arrives.
+        pitch_report: False (the default: nothing is added to the call), True, or a dict of ``pitch_report`` keywords: the joined
+        waveform's F0 track is measured as delivered and ``last_pitch_report`` holds its pitch.PitchReport (see tts_ex).  The
+        measurement runs behind the synthesis, and zvx_pitch takes at most 65536 frames per row: a paragraph whose joined waveform is
+        longer than that at the hop (about 760 s at the model's rate and hop 256) must pass a larger one, ``pitch_report=dict(hop=512)``.
+        Where it is not, the ZvxError (ZVX_E_UNSUPPORTED) is raised with the finished ``(wav, segments)`` in its ``result`` attribute,
+        so that the waveform is not lost, and ``last_pitch_report`` is None."""
+        from ._lib import ZvxError
         from .longform import synthesize_long
-        return synthesize_long(self, text, spkemb, pauses=pauses, trim_db=trim_db, keep_ms=keep_ms, fade_ms=fade_ms, max_batch=max_batch,
+        pkw = self._pitch_keywords(pitch_report)
+        wav, segments = synthesize_long(self, text, spkemb, pauses=pauses, trim_db=trim_db, keep_ms=keep_ms, fade_ms=fade_ms, max_batch=max_batch,
                                max_frames=max_frames, pcm16=pcm16, durations=durations, max_chars=max_chars,
                                prosody=self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range),
                                loudness=loudness, peak_db=peak_db, loudness_mode=loudness_mode, limiter=limiter, limiter_ms=limiter_ms,
                                denoise=self._denoise(denoise), **({"report": True} if report else {}))
+        if pkw is not None:
+            self._last_pitch_report = None
+        if pkw is not None and segments:
+            try:
+                self.pitch_report(wav, **pkw)
+            except ZvxError as e:
+                e.result = (wav, segments)
+                raise
+        return wav, segments
 
     @property
     def output_rate(self):
