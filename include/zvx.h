@@ -76,7 +76,12 @@ enum {                   /* zvx_stage_times indices (milliseconds, hipEvent-time
  * (synthesize.py:48-97, model.py:86-118, model.py:206-249).
  * Generator shapes the device does not run are refused here (zvx_last_error(NULL) names the manifest key): ZVX_E_UNSUPPORTED for an
  * upsampling stage with an odd k - u or k > 3u (voc_ksizes / voc_rates), a last stage of fewer than 8 channels in the 16-bit precision
- * (4 in f32; voc_c0) and a ResBlock kernel of more than 16 taps (voc_rb_k); ZVX_E_MANIFEST for lists that do not fit each other. */
+ * (4 in f32; voc_c0) and a ResBlock kernel of more than 16 taps (voc_rb_k); ZVX_E_MANIFEST for lists that do not fit each other.
+ * Front-end shapes accepted (anything else: ZVX_E_UNSUPPORTED naming the key): `hidden` a multiple of 8; `enc_heads` / `dec_heads` dividing it
+ * into head depths that are multiples of 8; both `ffn_k` odd and at most 15; `vp_dim` a multiple of 4; `ffn_dim` a multiple of 8 (4 in the f32
+ * precision); `n_bins` >= 2; `n_mels` a multiple of 8 up to 128; four `rn_layers` >= 1 and four `rn_filters` that are multiples of 8 up to 256.
+ * ZVX_E_MANIFEST where `n_mels` is not the input width of the tensor voc.pre_w (the generator's conv_pre).  `vp_k` other than 3 is accepted here
+ * and refused by the first zvx_encode (ZVX_E_UNSUPPORTED).  A config zvx_create accepted never ends in a launcher refusing its shape. */
 zvx_status zvx_create(const char* manifest, const void* weights, size_t nbytes, int device, zvx_ctx** out);
 void       zvx_destroy(zvx_ctx* ctx);
 const char* zvx_last_error(const zvx_ctx* ctx);

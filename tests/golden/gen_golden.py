@@ -9,12 +9,15 @@ are stored as small .npz files.  A fixture is DATA: seeded inputs + the referenc
 weights are regenerated from (config name, seed) on the consuming side.
 
     python tests/golden/gen_golden.py            # rewrites tests/golden/*.npz + MANIFEST.json
+    python tests/golden/gen_golden.py sweep      # only sweep_<case>.npz (tests/frontend_ref.SWEEP) and their MANIFEST.json entries
 """
 import hashlib
+import io
 import json
 import os
 import sys
 import warnings
+import zipfile
 
 import numpy as np
 
@@ -22,6 +25,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(os.path.dirname(HERE))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
+sys.path.insert(0, os.path.join(ROOT, "tests"))
 warnings.filterwarnings("ignore")
 
 import ref_import  # noqa: E402
@@ -48,6 +52,23 @@ def save(name, **arrays):
     print(f"  wrote {name}.npz ({os.path.getsize(path) / 1024:.0f} KiB)")
 
 
+def save_fixed(name, **arrays):
+    """save() with the archive members in sorted order under a constant timestamp: the same arrays give the same bytes on every run
+    (np.savez stamps each member with the wall clock)."""
+    path = os.path.join(HERE, name + ".npz")
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as z:
+        for key in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(arrays[key]), allow_pickle=False)
+            info = zipfile.ZipInfo(key + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            z.writestr(info, buf.getvalue(), compresslevel=9)
+    MANIFEST[name] = {"sha256": hashlib.sha256(open(path, "rb").read()).hexdigest(),
+                      "bytes": os.path.getsize(path), "keys": sorted(arrays)}
+    print(f"  wrote {name}.npz ({os.path.getsize(path) / 1024:.1f} KiB)")
+
+
 def t2n(t):
     return t.detach().cpu().numpy()
 
@@ -55,9 +76,11 @@ def t2n(t):
 _MODELS = {}
 
 
-def ref_model(kind):
+def ref_model(kind, cfg=None):
+    """kind: a decoder kind (the medium config) or, with cfg, the cache key of that modelcfg"""
     if kind not in _MODELS:
-        cfg = zcfg.medium_modelcfg(kind)
+        if cfg is None:
+            cfg = zcfg.medium_modelcfg(kind)
         zv = ZeroVox(symbols=Symbols(zcfg.PHONES, zcfg.PUNCTS), meldec_model=None, **zcfg.zerovox_kwargs(cfg))
         sd = zw.tts_state_dict(cfg, SEED)
         zv.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in sd.items()}, strict=True)
@@ -240,6 +263,54 @@ def block_cases():
     save("blocks_hifigan", **out)
 
 
+def sweep_cases():
+    """One sweep_<case>.npz per entry of tests/frontend_ref.SWEEP -- the cases the device refuses too: the reference accepts them, bar the
+    ones the table marks fixture=False.  Row 0 of the case's ragged batch through ZeroVox.inference_ex with forced durations (the capture of
+    e2e_case; the vocoder stubbed, _min_mel_len 1: no waveform) and the case's 97-frame reference mel through its speaker encoder (the
+    capture of spk_case).  The mel itself is not stored (it would be half of the 64 KiB a file may have): frontend_ref.inputs(case)
+    regenerates it from the seed, ref_mel_sha256 says which bytes the reference saw."""
+    import frontend_ref as FR
+    for case in FR.SWEEP:
+        if not FR.has_fixture(case):
+            continue
+        print(f"[sweep] {case}")
+        cfg = FR.modelcfg(case)
+        zv = ref_model("sweep:" + case, cfg)
+        hop = cfg["audio"]["hop_size"]
+        zv._meldec = lambda m: torch.zeros(1, m.shape[1] * hop)
+        zv._min_mel_len = 1
+        x = FR.inputs(case)
+        T = int(x["T"][0])
+        phoneme, puncts, dur, spk = x["phoneme"][0, :T], x["puncts"][0, :T], x["duration"][0, :T], x["spk"][0]
+        cap = {}
+        hooks = [
+            zv._phoneme_encoder._encoder.register_forward_hook(lambda m, i, o: cap.__setitem__("enc", t2n(o)[0])),
+            zv._phoneme_encoder.register_forward_hook(lambda m, i, o: cap.__setitem__("pe", o)),
+        ]
+        with torch.no_grad():
+            xin = {"phoneme": torch.from_numpy(phoneme[None]).int(), "puncts": torch.from_numpy(puncts[None]).int(),
+                   "duration": torch.from_numpy(dur[None]).int()}
+            _, mel_len, logd, mel = zv.inference_ex(xin, style_embed=torch.from_numpy(spk).reshape(1, 1, -1), force_duration=True)
+            ref_mel = x["ref_mels"][0, :int(x["ref_lens"][0])]
+            e = zv._spkemb(torch.from_numpy(ref_mel[None]))
+        for h in hooks:
+            h.remove()
+        pe = cap["pe"]
+        save_fixed("sweep_" + case, phoneme=phoneme, puncts=puncts, spk=spk, duration=dur, seed=np.array(SEED),
+                   mel=t2n(mel).astype(np.float32), mel_len=np.array(mel_len), log_duration=t2n(logd)[0], pitch=t2n(pe["pitch"])[0],
+                   energy=t2n(pe["energy"])[0], encoder_raw=cap["enc"], features=t2n(pe["features"])[0], embed=t2n(e)[0, 0],
+                   ref_mel_sha256=np.array(hashlib.sha256(np.ascontiguousarray(ref_mel).tobytes()).hexdigest()))
+        assert os.path.getsize(os.path.join(HERE, "sweep_" + case + ".npz")) < 64 * 1024, case
+        del _MODELS["sweep:" + case]
+
+
+def write_manifest(fixtures):
+    with open(os.path.join(HERE, "MANIFEST.json"), "w") as f:
+        json.dump({"generator": "tests/golden/gen_golden.py", "reference": "gooofy/zerovox @ 2025-04-18",
+                   "torch": torch.__version__, "numpy": np.__version__, "weight_seed": SEED,
+                   "fixtures": fixtures}, f, indent=1, sort_keys=True)
+
+
 def text_cases():
     """transcript2phonemids needs no reference import (synthesize.py pulls librosa/uroman); its
     documented example (synthesize.py:201-203) is encoded in tests/test_host_api.py instead."""
@@ -261,12 +332,23 @@ def main():
     spk_sap_case("spkemb_sap_T96", 96, 9)
     block_cases()
     v3_cases()
-    with open(os.path.join(HERE, "MANIFEST.json"), "w") as f:
-        json.dump({"generator": "tests/golden/gen_golden.py", "reference": "gooofy/zerovox @ 2025-04-18",
-                   "torch": torch.__version__, "numpy": np.__version__, "weight_seed": SEED,
-                   "fixtures": MANIFEST}, f, indent=1, sort_keys=True)
+    sweep_cases()
+    write_manifest(MANIFEST)
     print("total KiB:", sum(v["bytes"] for v in MANIFEST.values()) // 1024)
 
 
+def main_sweep():
+    """the sweep fixtures alone: every other entry of MANIFEST.json (and its header) stays as it is"""
+    sweep_cases()
+    path = os.path.join(HERE, "MANIFEST.json")
+    old = json.load(open(path))
+    fixtures = {k: v for k, v in old["fixtures"].items() if not k.startswith("sweep_")}
+    fixtures.update(MANIFEST)
+    old["fixtures"] = fixtures
+    with open(path, "w") as f:
+        json.dump(old, f, indent=1, sort_keys=True)
+    print("sweep KiB:", sum(v["bytes"] for v in MANIFEST.values()) // 1024)
+
+
 if __name__ == "__main__":
-    main()
+    main_sweep() if sys.argv[1:] == ["sweep"] else main()

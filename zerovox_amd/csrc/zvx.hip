@@ -616,6 +616,7 @@ void upload_weights(zvx_ctx* c) {
             if (!c->has(n2) || !c->has(ns) || c->has(std::string(blk) + ".sc_b")) continue;
             const Tensor& t2 = c->t(n2); const Tensor& ts = c->t(ns);
             if (t2.dims.size() != 3 || ts.dims.size() != 3 || ts.dim(0) != 1 || ts.dim(1) != t2.dim(1) || !c->packed.count(t2.dev) || !c->packed.count(ts.dev)) continue;
+            if (t2.dim(2) % 16 || ts.dim(2) % 16) continue;          // the conv-slab kernel alone takes a second source, in K chunks of 16 (launch_gemm): a hidden width of 72 runs the two launches
             const size_t bytes = (packed_weight_elems(t2.dim(0), t2.dim(1), t2.dim(2)) + packed_weight_elems(1, ts.dim(1), ts.dim(2))) * 2;
             void* comb = c->buf("weights_pair." + n2, bytes);
             launch_pack_pair(c->packed[t2.dev], t2.dim(0), t2.dim(2), c->packed[ts.dev], 1, ts.dim(2), t2.dim(1), comb, c->stream);
@@ -737,7 +738,42 @@ void read_config(zvx_ctx* c) {
         if (c->voc_rb_d[j].empty()) fail(ZVX_E_MANIFEST, "voc_rb_d[%d] is empty", (int)j);
         for (int d : c->voc_rb_d[j]) if (d < 1) fail(ZVX_E_MANIFEST, "voc_rb_d[%d] holds the dilation %d", (int)j, d);
     }
-    if (c->H % 8 || (c->H / c->enc_heads) % 8 || (c->H / c->dec_heads) % 8) fail(ZVX_E_UNSUPPORTED, "hidden/head dims must be multiples of 8");
+    // The front-end shapes the device runs (pack.check_model_config makes the same checks; a manifest can be written by hand).  What the
+    // launchers need of each width:
+    //   hidden, head depth   multiples of 8: 16-byte groups of the 16-bit kernels (gemm_kernel's K chunks, k_colstats / k_instnorm_fused /
+    //                        k_norm_affine_act: 8 channels per lane, in f32 too); a head's columns start at h * depth inside a Q | K row
+    //   ffn_k                odd (fs2.py:189-196 pads (k - 1) / 2) and <= ZVX_MAX_TAPS (launch_gemm)
+    //   vp_dim               a multiple of 4: the predictors run in f32 (launch_gemm: N % 4 with a bias; float4 K chunks)
+    //   ffn_dim              as N and K of the FFT blocks: 8 elements in the 16-bit precision (the FS2 decoder), 4 floats in f32
+    //   n_mels               a multiple of 8 (k_colstats over the reference mel; the pooled map has n_mels / 8 frequency rows, one tap each
+    //                        of the first attention projection: <= 8 * ZVX_MAX_TAPS), and conv_pre's K
+    //   rn_filters           multiples of 8 (k_spk_front, k_se_pool_partial, k_se_apply: 8 channels per thread), <= 256 (k_se_pool_partial
+    //                        folds with one thread per channel)
+    // vp_k != 3 is refused by the first zvx_encode (ZVX_E_UNSUPPORTED), as before.
+    if (c->H < 8 || c->H % 8) fail(ZVX_E_UNSUPPORTED, "hidden=%d must be a multiple of 8", c->H);
+    if (c->emb_dim + c->punct_dim != c->H) fail(ZVX_E_MANIFEST, "hidden=%d is not emb_dim + punct_dim = %d + %d", c->H, c->emb_dim, c->punct_dim);
+    const struct { const char* key; int heads; } hd[2] = {{"enc_heads", c->enc_heads}, {"dec_heads", c->dec_heads}};
+    for (const auto& h : hd) {
+        if (h.heads < 1 || c->H % h.heads) fail(ZVX_E_UNSUPPORTED, "%s=%d does not divide hidden=%d", h.key, h.heads, c->H);
+        if ((c->H / h.heads) % 8) fail(ZVX_E_UNSUPPORTED, "%s=%d: head depth %d (hidden=%d) must be a multiple of 8", h.key, h.heads, c->H / h.heads, c->H);
+    }
+    for (int i = 0; i < 2; i++) {
+        const int k = i ? c->ffn_k1 : c->ffn_k0;
+        if (k < 1 || k % 2 == 0) fail(ZVX_E_UNSUPPORTED, "ffn_k[%d]=%d must be odd", i, k);
+        if (k > ZVX_MAX_TAPS) fail(ZVX_E_UNSUPPORTED, "ffn_k[%d]=%d exceeds the %d taps of a convolution launch", i, k, ZVX_MAX_TAPS);
+    }
+    if (c->vp_dim < 4 || c->vp_dim % 4) fail(ZVX_E_UNSUPPORTED, "vp_dim=%d must be a multiple of 4", c->vp_dim);
+    if (c->ffn_dim < cunit || c->ffn_dim % cunit) fail(ZVX_E_UNSUPPORTED, "ffn_dim=%d must be a multiple of %d in precision %s", c->ffn_dim, cunit, c->cfg["precision"].c_str());
+    if (c->n_bins < 2) fail(ZVX_E_UNSUPPORTED, "n_bins=%d must be at least 2", c->n_bins);
+    if (c->enc_layers < 1 || c->dec_layers < 1) fail(ZVX_E_MANIFEST, "enc_layers=%d / dec_layers=%d must be positive", c->enc_layers, c->dec_layers);
+    if (c->n_mels < 8 || c->n_mels % 8 || c->n_mels > 8 * ZVX_MAX_TAPS) fail(ZVX_E_UNSUPPORTED, "n_mels=%d must be a multiple of 8, at most %d", c->n_mels, 8 * ZVX_MAX_TAPS);
+    if (c->rn_filters.size() != 4 || c->rn_layers.size() != 4) fail(ZVX_E_MANIFEST, "rn_filters / rn_layers need 4 entries each");
+    for (int i = 0; i < 4; i++) {
+        if (c->rn_layers[i] < 1) fail(ZVX_E_MANIFEST, "rn_layers[%d]=%d must be positive", i, c->rn_layers[i]);
+        if (c->rn_filters[i] < 8 || c->rn_filters[i] % 8 || c->rn_filters[i] > 256) fail(ZVX_E_UNSUPPORTED, "rn_filters[%d]=%d must be a multiple of 8, at most 256", i, c->rn_filters[i]);
+    }
+    if (c->has("voc.pre_w") && (c->t("voc.pre_w").dims.size() != 3 || c->t("voc.pre_w").dim(2) != c->n_mels))
+        fail(ZVX_E_MANIFEST, "n_mels=%d, but voc.pre_w (the generator's conv_pre) takes %d channels", c->n_mels, c->t("voc.pre_w").dims.size() == 3 ? c->t("voc.pre_w").dim(2) : -1);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -770,7 +806,8 @@ void fft_block(zvx_ctx* c, void* x, int dt, int B, int Lmax, const int* len_dev,
     // against [wh | wl | wh] weights (K = 3 x the logical K): f32-class results from the bf16 MFMA
     const bool sp16 = c->enc_split == 2;                                          // IEEE-half planes (f32-class to 2^-24) / bf16 planes (2^-17)
     const char* const s3 = sp16 ? ".s3h" : ".s3";
-    const bool split = dt == DT_F32 && c->enc_split && c->has(w.p + ".wqk" + s3);
+    // (all four static-weight GEMMs or none: build_split_weights makes planes of a tensor only where 3 K is a multiple of 16)
+    const bool split = dt == DT_F32 && c->enc_split && c->has(w.p + ".wqk" + s3) && c->has(w.p + ".wo" + s3) && c->has(w.p + ".w1" + s3) && c->has(w.p + ".w2" + s3);
     void* xs = split ? c->buf("fft.xs", (size_t)B * Ls * 3 * H * 2) : nullptr;
     auto split_of = [&](const float* src, int C, void* dst) { launch_split3(src, C, dst, B, Ls, len_dev, C, c->stream, sp16); };
     auto as_split = [&](GemmArgs& a, const void* planes, int C, const std::string& wname) {      // operand swap: same GEMM, 3-plane K axis
@@ -803,7 +840,7 @@ void fft_block(zvx_ctx* c, void* x, int dt, int B, int Lmax, const int* len_dev,
         c->gemm(a);
         af.qkv = qkv;
         if (split) { af.planes = (unsigned short*)xs; af.planes_C = H; af.planes_f16 = sp16; }   // o as split planes for the output projection
-        c->timed(4.0 * B * nheads * (double)Lmax * Lmax * d, (double)B * Lmax * 4.0 * H * 4, [&] { launch_attention_f32(af, c->stream, false); });
+        c->timed(4.0 * B * nheads * (double)Lmax * Lmax * d, (double)B * Lmax * 4.0 * H * 4, [&] { launch_attention_f32(af, c->stream, false); }, "attention_f32");
     } else {
     if (split) split_of((const float*)x, H, xs);
     // half blocks: [Q | K | V] = x [Wq; Wk; Wv]^T + b in ONE launch (round 6), then the 16-bit transpose of its V columns
@@ -855,7 +892,7 @@ void fft_block(zvx_ctx* c, void* x, int dt, int B, int Lmax, const int* len_dev,
     if (h16 && !flash) fail(ZVX_E_UNSUPPORTED, "half-precision FFT block without the fused attention (head depth %d)", d);
     if (flash) {
         // softmax(Q K^T / sqrt(d)) V in one launch, scores and probabilities stay on chip            fs2.py:47-58
-        c->timed(4.0 * B * nheads * (double)Lmax * Lmax * d, (double)B * Lmax * (3.0 * H + H) * es, [&] { launch_flash_attention(fa, c->stream, false); });
+        c->timed(4.0 * B * nheads * (double)Lmax * Lmax * d, (double)B * Lmax * (3.0 * H + H) * es, [&] { launch_flash_attention(fa, c->stream, false); }, h16 ? "flash_attention_f16" : "flash_attention_bf16");
         c->sat_scan(o, dt, (long)Ls * H, H, B, Lmax, len_dev, H);
     } else {
     {   // scores = Q K^T / sqrt(d)                                    fs2.py:49-50

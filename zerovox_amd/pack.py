@@ -129,10 +129,74 @@ def check_generator_config(h: dict, hop: int, precision: str = "bf16"):
             raise ValueError(f"resblock_dilation_sizes[{j}] = {list(d)} needs at least one dilation >= 1")
 
 
+MAX_TAPS = 16                                            # ZVX_MAX_TAPS (csrc/zvx_kernels.h): taps of one convolution launch
+
+
+def check_model_config(modelcfg: dict, precision: str = "bf16", conv_pre_channels: int | None = None):
+    """Raises ValueError (naming the modelcfg.yaml field) for a front end -- phoneme encoder, variance adaptor, mel decoders, speaker
+    encoder -- the device does not run; ``zvx_create`` makes the same checks on the manifest.  The reference builds any of these
+    (model.py:206-246); the device covers the subset where
+
+    * ``emb_dim + punct_emb_dim`` (hidden) is a multiple of 8, both head counts divide it and both head depths are multiples of 8:
+      every 16-bit kernel reads the channel axis in 16-byte groups of 8 elements, the norm / gather kernels own 8 channels per
+      lane in f32 too, and a head's Q / K columns start at ``h * depth`` inside a row (a depth of 132 would let the last group of a
+      head's K step read four columns of the next head);
+    * both ``conv_kernel_size`` entries are odd (fs2.py:189-196 pads (k - 1) // 2: an even kernel changes the sequence length) and at
+      most 15, the largest odd count of the 16 taps a convolution launch carries;
+    * ``vp_kernel_size`` is 3: fs2.py:543 pads the second convolution with the literal 1, any other kernel changes the length;
+    * ``vp_filter_size`` is a multiple of 4 (the variance predictors always run in f32: float4 bias / store groups);
+    * ``conv_filter_size`` is a multiple of 8 in the 16-bit precision (the FS2 decoder's FFN runs there), of 4 in f32;
+    * ``num_mels`` is a multiple of 8, at most 128: the speaker encoder's statistics pass owns 8 mel bins per lane, its pooled width is
+      ``num_mels / 8`` frequency rows (three stride-2 levels) and its first attention projection takes one tap per row;
+    * every ``resnet.num_filters`` entry is a multiple of 8 (8 channels per lane in the first layer, the SE and the pooling kernels) and
+      at most 256 (one thread per channel folds the SE pool), four entries with four ``layers`` counts >= 1;
+    * ``ve_n_bins`` >= 2 and ``conv_pre`` of the generator takes ``num_mels`` channels."""
+    m, a = modelcfg["model"], modelcfg["audio"]
+    enc, dec, rn = m["encoder"], m["decoder"], m["resnet"]
+    H = int(m["emb_dim"]) + int(m["punct_emb_dim"])
+    unit = 4 if precision == "f32" else 8
+    if H < 8 or H % 8:
+        raise ValueError(f"emb_dim + punct_emb_dim = {H}: the hidden width must be a multiple of 8")
+    for field, heads in (("encoder.fs2_head", int(enc["fs2_head"])), ("decoder.n_head", int(dec["n_head"]))):
+        if heads < 1 or H % heads:
+            raise ValueError(f"{field} = {heads} does not divide the hidden width {H}")
+        if (H // heads) % 8:
+            raise ValueError(f"{field} = {heads}: head depth {H // heads} (hidden {H}) must be a multiple of 8")
+    ks = list(dec["conv_kernel_size"])
+    if len(ks) != 2:
+        raise ValueError(f"conv_kernel_size: {len(ks)} entries, the FFN has two convolutions")
+    for i, k in enumerate(ks):
+        if k < 1 or k % 2 == 0:
+            raise ValueError(f"conv_kernel_size[{i}] = {k} must be odd (fs2.py:189-196 pads (k - 1) // 2)")
+        if k > MAX_TAPS:
+            raise ValueError(f"conv_kernel_size[{i}] = {k} exceeds the {MAX_TAPS} taps of a convolution launch")
+    if int(enc["vp_kernel_size"]) != 3:
+        raise ValueError(f"vp_kernel_size = {enc['vp_kernel_size']}: only 3 keeps the sequence length (fs2.py:543 padding=1)")
+    if int(enc["vp_filter_size"]) < 4 or int(enc["vp_filter_size"]) % 4:
+        raise ValueError(f"vp_filter_size = {enc['vp_filter_size']} must be a multiple of 4")
+    if int(dec["conv_filter_size"]) < unit or int(dec["conv_filter_size"]) % unit:
+        raise ValueError(f"conv_filter_size = {dec['conv_filter_size']}: precision {precision} needs a multiple of {unit}")
+    if int(enc["ve_n_bins"]) < 2:
+        raise ValueError(f"ve_n_bins = {enc['ve_n_bins']} must be at least 2")
+    n_mels = int(a["num_mels"])
+    if n_mels < 8 or n_mels % 8 or n_mels > 8 * MAX_TAPS:
+        raise ValueError(f"num_mels = {n_mels} must be a multiple of 8, at most {8 * MAX_TAPS} (the speaker encoder pools num_mels / 8 frequency rows)")
+    nf, layers = list(rn["num_filters"]), list(rn["layers"])
+    if len(nf) != 4 or len(layers) != 4 or min(layers) < 1:
+        raise ValueError(f"resnet.layers / num_filters: {layers} / {nf}: four levels of at least one block each")
+    for i, c in enumerate(nf):
+        if c < 8 or c % 8 or c > 256:
+            raise ValueError(f"resnet.num_filters[{i}] = {c} must be a multiple of 8, at most 256")
+    if conv_pre_channels is not None and int(conv_pre_channels) != n_mels:
+        raise ValueError(f"num_mels = {n_mels}, but the generator's conv_pre takes {int(conv_pre_channels)} channels")
+
+
 def pack_model(modelcfg: dict, tts_sd: dict, hifigan_cfg: dict, hifigan_sd: dict, precision: str = "bf16"):
     """Returns (manifest_text, blob float32[...])."""
     assert precision in ("bf16", "f32")
     check_generator_config(hifigan_cfg, modelcfg["audio"]["hop_size"], precision)
+    pre = hifigan_sd["conv_pre.weight_v"] if "conv_pre.weight_v" in hifigan_sd else hifigan_sd["conv_pre.weight"]
+    check_model_config(modelcfg, precision, pre.shape[1])
     m = modelcfg["model"]
     enc, dec, rn = m["encoder"], m["decoder"], m["resnet"]
     H = m["emb_dim"] + m["punct_emb_dim"]

@@ -227,15 +227,16 @@ def tts_state_dict(modelcfg: dict, seed: int = 0) -> dict[str, np.ndarray]:
     return s.sd
 
 
-def hifigan_state_dict(h: dict, seed: int = 0) -> dict[str, np.ndarray]:
-    """Synthetic ``{'generator': ...}`` payload of a HiFi-GAN ``generator.ckpt`` (weight-norm form).
+def hifigan_state_dict(h: dict, seed: int = 0, n_mels: int = 80) -> dict[str, np.ndarray]:
+    """Synthetic ``{'generator': ...}`` payload of a HiFi-GAN ``generator.ckpt`` (weight-norm form); ``n_mels``: the input channels of
+    ``conv_pre`` (hifigan.py:95 hard-codes 80; a model with another ``num_mels`` needs a generator trained for it).
 
     Layout as built by hifigan.py:95-110.  ConvTranspose1d weights are [Cin, Cout, k] and torch's
     weight_norm(dim=0) therefore normalises per INPUT channel (weight_g is [Cin,1,1]).
     """
     s = _Spec(seed)
     C0 = h["upsample_initial_channel"]
-    s.wn("conv_pre", (C0, 80, 7), gain=1.0, bias=C0)
+    s.wn("conv_pre", (C0, n_mels, 7), gain=1.0, bias=C0)
     ch = C0
     for i, (u, k) in enumerate(zip(h["upsample_rates"], h["upsample_kernel_sizes"])):
         cin, cout = C0 // (2 ** i), C0 // (2 ** (i + 1))
