@@ -972,6 +972,76 @@ zvx_status zvx_comm_max_f64(zvx_ctx* ctx, double* value);
 zvx_status zvx_comm_info(zvx_ctx* ctx, int64_t* out, int n_out);
 void       zvx_comm_destroy(zvx_ctx* ctx);
 
+/* Keyed audio watermark on the device, and its detector: a multiplicative spread-spectrum mark laid on the denoiser's STFT frame grid, so that
+ * an operator can later ask "did this audio come from my deployment" with the key.  The embedder scales bands of bins up or down by
+ * depth_db in a keyed pattern over (time block, band); the detector looks for that pattern in the band log-energies.
+ * Framing, analysis, synthesis, overlap-add, den_min, the PCM16 rule and the reflect padding are zvx_denoise's, word for word: the model's
+ *   n_fft / hop / window, the same tables rounded once to f32, the ascending-f sums.  Rows are at the model's rate (`rate` below is
+ *   zvx_get_int("sampling_rate")).
+ * Bands: k_lo = ceil(lo_hz n_fft / rate); J = floor((min(hi_hz n_fft / rate, n_fft / 2) - k_lo) / KB); band j is bins
+ *   [k_lo + j KB, k_lo + (j + 1) KB), computed in double on the host.  J < 3 is ZVX_E_INVALID, J > 512 ZVX_E_UNSUPPORTED.
+ * Pattern: sign(c, j) = +1 if bit 63 of mix64(key ^ ((uint64)c << 32 | j)) is set, else -1, for c in [0, P); mix64 is the splitmix64
+ *   finaliser: z += 0x9E3779B97F4A7C15; z = (z ^ z >> 30) * 0xBF58476D1CE4E5B9; z = (z ^ z >> 27) * 0x94D049BB133111EB; z ^ z >> 31.  The
+ *   P x J table is built on the host and uploaded through the pinned staging arena.
+ * Gain: frame f of the SIGNAL (absolute index) is in block c = (f / TB) mod P.  g_up = (float)10^(depth_db / 20), g_dn =
+ *   (float)10^(-depth_db / 20), both computed in double on the host.  For the bins of band j: X' = g X, g = g_up or g_dn by sign(c, j); every
+ *   other bin: X' = X, no multiply.  The imaginary parts of DC and Nyquist are dropped as in zvx_denoise.  depth_db == 0: a copy, the bits of
+ *   x, nothing is transformed.
+ * zvx_watermark_ex: the window contract, the reach R = n_fft - 1, the support condition, the validation and the flags of zvx_denoise_ex.
+ *   The emitted samples are bit for bit those of the whole-signal call: a frame keeps the slot it has in the whole call (zvx_denoise_ex),
+ *   and the block index comes from the absolute frame index, formed in 64 bits.  zvx_watermark is zvx_watermark_ex(..., 0, 0, -1, 1).
+ * Detector (zvx_watermark_detect), whole rows only; per row:
+ *   the STFT as above, Pw = re^2 + im^2; LB[f][j] = sum over the band's bins of log2(max(Pw, 1e-6));
+ *   D[f][j] = LB[f][j] - (LB[f][j - 1] + LB[f][j + 1]) / 2 for 1 <= j <= J - 2 (the neighbours' mean takes the spectral envelope off);
+ *   windows of window_frames frames with hop window_frames / 2, the last one clipped to the row: window w is frames
+ *   [w H, min(w H + window_frames, F)), H = window_frames / 2, w < 1 + ceil((F - window_frames) / H); window_frames == 0, or a row of no
+ *   more frames than that: one window, the row.  window_frames == 1 is ZVX_E_INVALID.
+ *   In a window, for each offset o in [0, P TB): frame f (the ROW's index) has block (f + o) / TB; E[block][j] is the sum of D over the
+ *   block's frames inside the window; z(o) = sum sign(block mod P, j) E / sqrt(sum E^2), 0 where the denominator is 0, the sums in double.
+ *   Per window the largest z and the smallest o that attains it; per row the best window (the first of equals).
+ *   score[b], offset[b], window[b] (HOST arrays [B]) receive them; win_score / win_offset (HOST [B][NWmax], or both NULL) every window's
+ *   -- entries past a row's window count are not touched; NWmax smaller than a row's window count is ZVX_E_BUFFER.
+ *   The detector's band may be narrower than the embedder's: bands are counted from k_lo, so a smaller hi_hz detects after a
+ *   down-conversion (same lo_hz, KB, TB, P).  depth_db is not read.  The offset search is at hop granularity: audio cut at the front by
+ *   c samples shows the offset nearest c / hop; a sample shift below a hop costs score, it does not move the grid.
+ *   On the device: one launch does FFT, Pw, the band log sums and D into an F x (J - 2) f32 work buffer (no spectrum goes to memory); one
+ *   launch, a workgroup per (row, window), does the search: for each of the TB phases the blocks' E are folded by block mod P into a table
+ *   in LDS, a run of 12288 / P bands at a time, so that each of the P shifts is one pass over it; the denominator is formed per phase
+ *   from the unfolded E.  The device's sums are f32 up to E and double from there, in the folded order -- the scores agree with the
+ *   float64 restatement (tests/watermark_ref.py) to the measured bound below, not bit for bit.
+ * Rest: rows are independent; n == 0 writes nothing and scores 0 (offset 0, window 0); non-finite input follows zvx_vocode_mel's rule (that
+ *   row unspecified, nothing faults, the others untouched).  Flags of zvx_watermark / _ex: zvx_denoise's; zvx_watermark_detect:
+ *   ZVX_DEVICE_IN only, and the call waits once for its results.
+ *   ZVX_E_INVALID, before anything is queued, the context stays usable: every check of zvx_denoise(_ex) on rows, output, window and
+ *   lengths; a NULL params; depth_db not finite or outside [0, 6]; lo_hz / hi_hz not finite, lo_hz < 0 or lo_hz >= hi_hz; block_frames or
+ *   band_bins < 1; period_blocks outside [1, 256]; reserved != 0; J < 3; for the detector a NULL score / offset / window, a negative
+ *   window_frames or 1, one of win_score / win_offset without the other, NWmax < 0.  ZVX_E_UNSUPPORTED: zvx_denoise's, and J > 512.
+ * Stage tags "post.watermark" and "post.wmdetect" in zvx_tag_stats (one timed group per call).
+ * Measured (MI355X, n_fft 1024 / hop 256, rows with |x| <= 1, against tests/watermark_ref.py): embed, largest |out - ref| 2.52e-7 (the denoiser's transform pair: 2.48e-7 there);
+ *   detect, largest |score - ref| 7.7e-6 on scores of 2 .. 13.5.  The tests hold 4x these.
+ *   What is measured is the arithmetic, and detection on synthetic voiced signals (tests/test_watermark.py: at depth 1 dB and the defaults of
+ *   zerovox_amd/watermark.py, 1.5 s and 3 s at 22.05 kHz).  Short clips cut to the telephone band are NOT reliably detectable (a float64
+ *   prototype gave a score of 3.1 at 1.5 s after an 8 kHz round trip against a wrong-key null of about 2.5).
+ * Not here: a _rows form and stream sessions (zvx_stream_params has no watermark stage); robustness against lossy codecs, time-stretching
+ *   or deliberate removal; whether the mark is inaudible on a real checkpoint -- none of these is measured, and nothing here claims them. */
+typedef struct zvx_watermark_params {
+    uint64_t key;            /* the secret */
+    float    depth_db;       /* finite, 0 .. 6; 0: a copy (the bits of x, nothing transformed) */
+    float    lo_hz, hi_hz;   /* marked band, 0 <= lo_hz < hi_hz; hi is clipped to rate / 2 */
+    int32_t  block_frames;   /* TB >= 1: frames per time block */
+    int32_t  band_bins;      /* KB >= 1: bins per band */
+    int32_t  period_blocks;  /* P, 1 .. 256: the pattern repeats every P blocks */
+    int32_t  reserved;       /* 0 */
+} zvx_watermark_params;
+zvx_status zvx_watermark(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_watermark_params* params,
+                         void* out, int64_t out_stride, int flags);
+zvx_status zvx_watermark_ex(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_watermark_params* params,
+                            void* out, int64_t out_stride, int flags, int64_t in_origin, int64_t out_begin, int64_t out_count, int last);
+/* score, offset, window: host [B]; win_score, win_offset: host [B][NWmax] or NULL.  flags: ZVX_DEVICE_IN only */
+zvx_status zvx_watermark_detect(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_watermark_params* params,
+                                int window_frames, float* score, int32_t* offset, int32_t* window, float* win_score, int32_t* win_offset,
+                                int NWmax, int flags);
+
 /* Device buffers for ZVX_DEVICE_OUT outputs / zvx_comm_gather without any other GPU runtime in the process. */
 zvx_status zvx_dev_alloc(zvx_ctx* ctx, size_t bytes, void** out);
 zvx_status zvx_dev_free(zvx_ctx* ctx, void* p);
@@ -993,7 +1063,7 @@ typedef struct {
 } zvx_kernel_stat;
 int        zvx_kernel_stats(zvx_ctx* ctx, zvx_kernel_stat* out, int max_out);
 /* The same counters grouped by pipeline stage ("encoder", "variance", "lenreg", "decoder", "decoder.norm", "voc.pre",
- * "voc.up1".."voc.res4", "voc.post", "voc.resample", "voc.stream", "post.join", "post.loudness", "post.limit", "post.denoise", "spkemb"; name = stage): every launch of the stage, including the HBM-bound helper
+ * "voc.up1".."voc.res4", "voc.post", "voc.resample", "voc.stream", "post.join", "post.loudness", "post.limit", "post.denoise", "post.watermark", "post.wmdetect", "spkemb"; name = stage): every launch of the stage, including the HBM-bound helper
  * kernels, while "profile" == 2 and "profile_only" == -1.  Feeds the per-stage roofline fractions of bench.py. */
 int        zvx_tag_stats(zvx_ctx* ctx, zvx_kernel_stat* out, int max_out);
 zvx_status zvx_reset_stats(zvx_ctx* ctx);

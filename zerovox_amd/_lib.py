@@ -28,7 +28,7 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_loudness", "zvx_normalize", "zvx_true_peak", "zvx_limit", "zvx_spkemb_wav", "zvx_limit_ex", "zvx_denoise_bias", "zvx_denoise",
            "zvx_denoise_ex", "zvx_stream_open", "zvx_stream_next", "zvx_stream_info", "zvx_stream_close", "zvx_stream_next_many",
            "zvx_denoise_rows", "zvx_limit_rows", "zvx_resample_rows", "zvx_level", "zvx_level_ex", "zvx_level_rows", "zvx_loudness_stats",
-           "zvx_pitch")
+           "zvx_pitch", "zvx_watermark", "zvx_watermark_ex", "zvx_watermark_detect")
 ZVX_STREAM_MANY_MAX_SESSIONS, ZVX_STREAM_MANY_MAX_ROWS = 64, 256
 ZVX_COMM_ID_BYTES = 128
 ZVX_LOUD_PER_ROW, ZVX_LOUD_COMMON = 0, 1
@@ -94,6 +94,12 @@ class PitchParams(C.Structure):
 class DenoiseParams(C.Structure):
     """zvx_denoise_params (include/zvx.h)"""
     _fields_ = [("strength", C.c_float), ("floor", C.c_float)]
+
+
+class WatermarkParams(C.Structure):
+    """zvx_watermark_params (include/zvx.h)"""
+    _fields_ = [("key", C.c_uint64), ("depth_db", C.c_float), ("lo_hz", C.c_float), ("hi_hz", C.c_float), ("block_frames", C.c_int32),
+                ("band_bins", C.c_int32), ("period_blocks", C.c_int32), ("reserved", C.c_int32)]
 
 
 class RowWindow(C.Structure):
@@ -180,6 +186,9 @@ def load():
     lib.zvx_denoise.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.POINTER(DenoiseParams), vp, C.c_int64, C.c_int]
     lib.zvx_denoise_ex.argtypes = lib.zvx_denoise.argtypes + [C.c_int64, C.c_int64, C.c_int64, C.c_int]
     lib.zvx_denoise_rows.argtypes = lib.zvx_denoise.argtypes + [C.POINTER(RowWindow)]
+    lib.zvx_watermark.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(WatermarkParams), vp, C.c_int64, C.c_int]
+    lib.zvx_watermark_ex.argtypes = lib.zvx_watermark.argtypes + [C.c_int64, C.c_int64, C.c_int64, C.c_int]
+    lib.zvx_watermark_detect.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(WatermarkParams), C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int]
     lib.zvx_limit_rows.argtypes = lib.zvx_limit.argtypes + [C.POINTER(RowWindow)]
     lib.zvx_resample_rows.argtypes = lib.zvx_resample.argtypes + [C.POINTER(RowWindow)]
     lib.zvx_level.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(LevelParams), vp, C.c_int64, vp, vp, C.c_int]
@@ -770,6 +779,75 @@ class Context:
         prm, flags = self._denoise_args(strength, floor, device=True, no_sync=no_sync)
         p = C.c_void_p(int(ptr))
         self._chk(self._lib.zvx_denoise(self._h, p, _ptr(n), len(n), int(Nmax), _ptr(bias), C.byref(prm), p, int(Nmax), flags))
+
+    @classmethod
+    def _watermark_args(cls, key, depth_db=1.0, lo_hz=250.0, hi_hz=8000.0, block_frames=8, band_bins=4, period_blocks=64, **flags):
+        return (WatermarkParams(int(key) & 0xFFFFFFFFFFFFFFFF, float(depth_db), float(lo_hz), float(hi_hz), int(block_frames), int(band_bins),
+                                int(period_blocks), 0), cls._flags(**flags))
+
+    def watermark(self, rows, key, *, pcm16=False, lengths=None, **params):
+        """zvx_watermark on host rows: the keyed mark of zerovox_amd.watermark laid on every row (params: depth_db, lo_hz, hi_hz,
+        block_frames, band_bins, period_blocks; the defaults are watermark.EMBED_DEFAULTS) -> rows_out [B][Nmax] float32 / int16 -- row b
+        holds its marked samples, then zeros.  rows: a list of 1-D float waveforms, or a padded 2-D array + lengths, at the model's rate."""
+        x, n = self._rows(rows, lengths)
+        B, Nmax = x.shape
+        prm, flags = self._watermark_args(key, pcm16=pcm16, **params)
+        out = np.zeros((B, Nmax), np.int16 if pcm16 else np.float32)
+        self._chk(self._lib.zvx_watermark(self._h, _ptr(x), _ptr(n), B, Nmax, C.byref(prm), _ptr(out), Nmax, flags))
+        return out
+
+    def watermark_window(self, rows, key, *, in_origin=0, out_begin=0, out_count=-1, last=True, pcm16=False, lengths=None, **params):
+        """zvx_watermark_ex on host rows: the rows hold samples [in_origin, in_origin + len) of signals that start at sample 0 and, with
+        `last`, end with the row; the outputs [out_begin, out_begin + out_count) of the whole-signal call (out_count -1, which needs
+        last: to the end of each row's signal) -> out [B][n] float32 / int16.  The window must carry watermark.reach(fft_size) =
+        fft_size - 1 samples of support on either side of the outputs, except at the signal's own ends (include/zvx.h)."""
+        x, n = self._rows(rows, lengths)
+        B, Nmax = x.shape
+        prm, flags = self._watermark_args(key, pcm16=pcm16, **params)
+        out, cols = self._window_out(n, Nmax, in_origin, out_begin, out_count, pcm16)
+        self._chk(self._lib.zvx_watermark_ex(self._h, _ptr(x), _ptr(n), B, Nmax, C.byref(prm), _ptr(out), out.shape[1], flags,
+                                             int(in_origin), int(out_begin), int(out_count), 1 if last else 0))
+        return out[:, :cols]
+
+    def watermark_device(self, ptr, lengths, Nmax, key, *, no_sync=False, **params):
+        """zvx_watermark IN PLACE on device rows [B][Nmax] f32 at `ptr` (they may be the output of a call queued just before: stream
+        order is the fence); with no_sync the call only queues."""
+        n = _i32(lengths)
+        prm, flags = self._watermark_args(key, device=True, no_sync=no_sync, **params)
+        p = C.c_void_p(int(ptr))
+        self._chk(self._lib.zvx_watermark(self._h, p, _ptr(n), len(n), int(Nmax), C.byref(prm), p, int(Nmax), flags))
+
+    def watermark_detect(self, rows, key, *, window_frames=256, threshold=None, lengths=None, device_ptr=None, Nmax=None, **params):
+        """zvx_watermark_detect: per row the best score over every window of window_frames frames (0: the row) and every offset, with the
+        key's pattern (params: lo_hz, hi_hz, block_frames, band_bins, period_blocks as embedded; hi_hz may be lower) -> a list of B
+        watermark.WatermarkResult.  rows: a list of 1-D float waveforms, or a padded 2-D array + lengths, at the model's rate; or, with
+        device_ptr, device rows [B][Nmax] f32 there and `lengths`."""
+        from . import watermark as wm
+        if device_ptr is None:
+            x, n = self._rows(rows, lengths)
+            B, Nmax = x.shape
+            xp, flags = _ptr(x), 0
+        else:
+            n = _i32(lengths)
+            B, xp, flags = len(n), C.c_void_p(int(device_ptr)), ZVX_DEVICE_IN
+        params.pop("depth_db", None)
+        prm, _ = self._watermark_args(key, **params)
+        fft, hop, wf = self.get_int("fft_size"), self.hop, int(window_frames)
+        pad = (fft - hop) // 2
+        F = max(0, 1 + (int(Nmax) + 2 * pad - fft) // hop)
+        nw = 1 if wf < 2 or F <= wf else 1 + -(-(F - wf) // (wf // 2))
+        score, off, win = np.zeros(B, np.float32), np.zeros(B, np.int32), np.zeros(B, np.int32)
+        ws, wo = np.zeros((B, nw), np.float32), np.zeros((B, nw), np.int32)
+        self._chk(self._lib.zvx_watermark_detect(self._h, xp, _ptr(n), B, int(Nmax), C.byref(prm), wf, _ptr(score), _ptr(off), _ptr(win),
+                                                 _ptr(ws), _ptr(wo), nw, flags))
+        thr = wm.THRESHOLD if threshold is None else float(threshold)
+        res = []
+        for b in range(B):
+            Fb = max(0, 1 + (int(n[b]) + 2 * pad - fft) // hop) if n[b] > 0 else 0
+            k = 0 if Fb <= 0 else (1 if wf < 2 or Fb <= wf else 1 + -(-(Fb - wf) // (wf // 2)))
+            res.append(wm.WatermarkResult(float(score[b]), int(off[b]), int(win[b]), bool(score[b] >= thr), thr,
+                                          [(float(ws[b, w]), int(wo[b, w])) for w in range(k)]))
+        return res
 
     def stream_open(self, mel=None, frames=0, *, chunk_frames, chunks_per_call=1, halo=16, denoise=None, bias=None, limit=None, flags=0):
         """zvx_stream_open -> Stream.  mel: [frames, n_mels] float32 on the host; an int, a device pointer to ``frames`` rows

@@ -9,7 +9,7 @@ LIB = os.path.join(HERE, "libzvx.so")
 # test-only launcher shim (tests/native/zvx_ktest.hip): tests/test_kernels_gpu.py drives the launchers through it
 KTEST_SRC = os.path.join(os.path.dirname(HERE), "tests", "native", "zvx_ktest.hip")
 KTEST_LIB = os.path.join(HERE, "libzvx_ktest.so")
-SOURCES = ["gemm.hip", "resstream.hip", "pairstream.hip", "narrowstage.hip", "attention.hip", "ops.hip", "spectral.hip", "zvx.hip"]
+SOURCES = ["gemm.hip", "resstream.hip", "pairstream.hip", "narrowstage.hip", "attention.hip", "ops.hip", "spectral.hip", "watermark.hip", "zvx.hip"]
 # translation units: (object stem, source, extra -D flags).  gemm.hip is compiled as two units side by side (its fused ResBlock-pair kernels are
 # a third of its instantiations): a clean build takes the time of the larger half
 UNITS = [("gemm", "gemm.hip", ["-DZVX_GEMM_PART=1"]), ("gemm_resfuse", "gemm.hip", ["-DZVX_GEMM_PART=2"])] + \
@@ -57,7 +57,7 @@ def resources():
 
 def build(force: bool = False, verbose: bool = True) -> str:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(CSRC, "zvx_kernels.h"), os.path.join(CSRC, "mfma_util.h"), os.path.join(CSRC, "stream_plan.h"), os.path.join(os.path.dirname(HERE), "include", "zvx.h")]
+    headers = [os.path.join(CSRC, "zvx_kernels.h"), os.path.join(CSRC, "mfma_util.h"), os.path.join(CSRC, "stream_plan.h"), os.path.join(CSRC, "spectral_fft.h"), os.path.join(CSRC, "watermark_kernels.h"), os.path.join(os.path.dirname(HERE), "include", "zvx.h")]
     def compile_one(unit):
         stem, src, defs = unit
         s = os.path.join(CSRC, src)

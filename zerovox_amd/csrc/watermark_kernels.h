@@ -1,0 +1,51 @@
+// watermark_kernels.h -- launch arguments and launchers of the keyed audio watermark and its detector (watermark.hip), on top of the
+// denoiser's (zvx_kernels.h: DenoiseArgs, launch_denoise_ola).
+#pragma once
+#include "zvx_kernels.h"
+
+namespace zvx {
+
+// Keyed audio watermark (include/zvx.h, zvx_watermark, zvx_watermark_detect; watermark.hip): a multiplicative spread-spectrum mark on the
+// denoiser's frame grid.  The embedder is the denoiser's frames kernel with a keyed gain in place of the bias gain -- the row table, the
+// window, the slot rule and the overlap-add launch (launch_denoise_ola on `dn`) are the denoiser's own; `dn.copy` is depth_db == 0.
+// `sign` is the P x J pattern of +1 / -1 bytes, built on the host; band j is bins [k_lo + j KB, k_lo + (j + 1) KB); frame f of the SIGNAL
+// is in block (f / TB) mod P, f formed in 64 bits from the row's f_first.
+struct WatermarkArgs {
+    DenoiseArgs dn;                          // rows, geometry, tables; bias / strength / floor / mag are not read
+    const signed char* sign;                 // [P][J]
+    int k_lo, KB, J, TB, P;
+    float g_up, g_dn;
+};
+void launch_watermark_frames(const WatermarkArgs& a, hipStream_t s);
+// The detector, whole rows only.  launch_wm_bands: frame load, forward FFT, Pw = re^2 + im^2, LB[f][j] = sum over the band's bins of
+// log2(max(Pw, 1e-6)), D[f][j] = LB[f][j] - (LB[f][j - 1] + LB[f][j + 1]) / 2 -> the row's d[F][J - 2] (column j - 1); no spectrum goes to
+// memory.  grid = (ceil(Fmax / frames per workgroup), B).
+// launch_wm_search: one workgroup per (window, row).  Window w is frames [w (WF / 2), min(w (WF / 2) + WF, F)) (WF == 0: the row).  For
+// each of the TB phases ph the blocks' sums E[m][j] (block m = (f + ph) / TB) are folded by m mod P into a table in LDS, WM_TABLE floats,
+// a run of bands at a time; the shift s then costs one pass over the table, and offset o = ph + TB s.  The denominator sum E^2 is formed
+// per phase from the unfolded E.  -> win_score[b][w] = the largest z, win_offset[b][w] = the smallest o that attains it, for w below the
+// row's window count (wm_windows), nothing elsewhere.  grid = (NW, B).
+constexpr int WM_TABLE = 12288;
+constexpr int WM_MAX_BANDS = 512, WM_MAX_PERIOD = 256;
+struct WmDetectRow { const float* x; float* d; int n, F; };
+struct WmDetectArgs {
+    const WmDetectRow* rows;                 // [B], on the device
+    int B;
+    int n_fft, log2n, hop, pad, Fmax;
+    const float* twid; const float* win;     // the denoiser's tables
+    const signed char* sign;                 // [P][J]
+    int k_lo, KB, J, TB, P;
+    int WF, NW;                              // NW: the most windows of a row (the grid; the pitch of the results)
+    float* win_score; int* win_offset;       // [B][NW]
+};
+// the windows of a row of F frames: 0 for none, 1 where WF == 0 or F <= WF, else 1 + ceil((F - WF) / (WF / 2)) (the last one clipped)
+__host__ __device__ inline int wm_windows(int F, int WF) {
+    if (F <= 0) return 0;
+    if (WF <= 0 || F <= WF) return 1;
+    const int H = WF / 2;
+    return 1 + (F - WF + H - 1) / H;
+}
+void launch_wm_bands(const WmDetectArgs& a, hipStream_t s);
+void launch_wm_search(const WmDetectArgs& a, hipStream_t s);
+
+}  // namespace zvx

@@ -5,6 +5,7 @@
 // Reference call structure being replaced: ZeroVox.inference_ex (model.py:308-347).
 #include "../../include/zvx.h"
 #include "zvx_kernels.h"
+#include "watermark_kernels.h"
 #include "stream_plan.h"
 
 #include <dlfcn.h>
@@ -3105,14 +3106,15 @@ DnGeom denoise_params_check(const zvx_ctx* c, const char* who, const float* bias
 // whole-row call and runs through the same instructions (the unrolled copies of a pass need not contract their multiply-adds alike), which
 // is what makes the bits equal.  The `skip` frames in front are neither loaded nor stored.  (spectral.hip, dn_frames_used)
 // The caller has validated the rows.
-void run_denoise_rows(zvx_ctx* c, const DnGeom& g, const PostRow* rows, int B, const float* bias, const zvx_denoise_params* p, int pcm16) {
+// (the row table and its sums, shared with the watermark's embedder: run_watermark_rows)
+struct DnRowsPlan {
+    std::vector<DenoiseRow> tab; std::vector<size_t> work_at;
+    double frames = 0, n_sum = 0, cnt_sum = 0; long Fmax = 0, cnt_max = 0; size_t work_floats = 0;
+};
+DnRowsPlan dn_rows_plan(const DnGeom& g, const PostRow* rows, int B, bool copy) {
     const int per = DENOISE_POINTS >> g.log2n;
-    const bool copy = p->strength == 0.f;
-    std::vector<DenoiseRow> tab((size_t)B);
-    std::vector<size_t> work_at((size_t)B);
-    double frames = 0, n_sum = 0, cnt_sum = 0;
-    long Fmax = 0, cnt_max = 0;
-    size_t work_floats = 0;
+    DnRowsPlan pl;
+    pl.tab.resize((size_t)B); pl.work_at.resize((size_t)B);
     for (int b = 0; b < B; b++) {
         const PostRow& r = rows[b];
         const RowsWindow& w = r.w;
@@ -3127,36 +3129,47 @@ void run_denoise_rows(zvx_ctx* c, const DnGeom& g, const PostRow* rows, int B, c
         if (any) {
             F = (off + r.cnt - 1 - rel) / g.hop + 1;
             if (w.last) F = std::min<int64_t>(F, std::max<int64_t>(0, dn_frames(g, w.in_origin + r.n) - f_first));
-            frames += (double)std::max<int64_t>(0, F - (f_need - f_first));
+            pl.frames += (double)std::max<int64_t>(0, F - (f_need - f_first));
         }
-        DenoiseRow& t = tab[(size_t)b];
+        DenoiseRow& t = pl.tab[(size_t)b];
         t.x = r.in; t.out = r.out; t.work = nullptr;
         t.origin = (long)w.in_origin; t.f_first = (long)f_first;
         t.n = r.n; t.skip = (int)(f_need - f_first); t.rel = (int)rel; t.off = (int)off; t.cnt = r.cnt;
         t.mirrors = (w.in_origin == 0 ? 1 : 0) | (w.last ? 2 : 0);
-        work_at[(size_t)b] = work_floats;
-        if (!copy) work_floats += (size_t)F * g.n_fft;
-        Fmax = std::max<long>(Fmax, (long)F); cnt_max = std::max<long>(cnt_max, r.cnt);
-        n_sum += r.n; cnt_sum += r.cnt;
+        pl.work_at[(size_t)b] = pl.work_floats;
+        if (!copy) pl.work_floats += (size_t)F * g.n_fft;
+        pl.Fmax = std::max<long>(pl.Fmax, (long)F); pl.cnt_max = std::max<long>(pl.cnt_max, r.cnt);
+        pl.n_sum += r.n; pl.cnt_sum += r.cnt;
     }
-    DenoiseArgs a{};
+    return pl;
+}
+// the plan's rows on the device with their work buffers, and the launch arguments' geometry and tables
+void dn_rows_upload(zvx_ctx* c, const DnGeom& g, DnRowsPlan& pl, int B, bool copy, int pcm16, DenoiseArgs& a) {
     a.copy = copy;                                           // a copy: the input's bits, nothing is transformed
     if (!copy) {
         dn_fill(a, g, dn_tables(c, g));
+        float* work = c->fbuf("dn.work", std::max<size_t>(pl.work_floats, 1));
+        for (int b = 0; b < B; b++) pl.tab[(size_t)b].work = work + pl.work_at[(size_t)b];
+    } else { a.n_fft = g.n_fft; a.log2n = g.log2n; a.hop = g.hop; a.pad = g.pad; }
+    a.Fmax = (int)pl.Fmax; a.B = B; a.pcm16 = pcm16;
+    DenoiseRow* tab_d = (DenoiseRow*)c->buf("dn.rows", (size_t)B * sizeof(DenoiseRow));
+    c->upload(tab_d, pl.tab.data(), (size_t)B * sizeof(DenoiseRow));
+    a.rows = tab_d;
+}
+void run_denoise_rows(zvx_ctx* c, const DnGeom& g, const PostRow* rows, int B, const float* bias, const zvx_denoise_params* p, int pcm16) {
+    const bool copy = p->strength == 0.f;
+    DnRowsPlan pl = dn_rows_plan(g, rows, B, copy);
+    DenoiseArgs a{};
+    if (!copy) {
         float* bias_d = c->fbuf("dn.bias", g.nf);
         c->upload(bias_d, bias, (size_t)g.nf * 4);
         a.bias = bias_d; a.strength = p->strength; a.floor = p->floor;
-        float* work = c->fbuf("dn.work", std::max<size_t>(work_floats, 1));
-        for (int b = 0; b < B; b++) tab[(size_t)b].work = work + work_at[(size_t)b];
-    } else { a.n_fft = g.n_fft; a.log2n = g.log2n; a.hop = g.hop; a.pad = g.pad; }
-    a.Fmax = (int)Fmax; a.B = B; a.pcm16 = pcm16;
-    DenoiseRow* tab_d = (DenoiseRow*)c->buf("dn.rows", (size_t)B * sizeof(DenoiseRow));
-    c->upload(tab_d, tab.data(), (size_t)B * sizeof(DenoiseRow));
-    a.rows = tab_d;
+    }
+    dn_rows_upload(c, g, pl, B, copy, pcm16, a);
     TagScope scope(c, "post.denoise");
-    c->timed(copy ? 0.0 : dn_fft_flops(g, frames, 2), 4.0 * n_sum + (pcm16 ? 2.0 : 4.0) * cnt_sum, [&] {
+    c->timed(copy ? 0.0 : dn_fft_flops(g, pl.frames, 2), 4.0 * pl.n_sum + (pcm16 ? 2.0 : 4.0) * pl.cnt_sum, [&] {
         if (!copy) launch_denoise_frames(a, c->stream);
-        launch_denoise_ola(a, cnt_max, c->stream);
+        launch_denoise_ola(a, pl.cnt_max, c->stream);
     });
 }
 
@@ -3179,6 +3192,157 @@ void do_denoise(zvx_ctx* c, const char* who, const float* in, const int32_t* nsa
     const std::vector<PostRow> rows = post_rows(x, Nmax, od, out_bs, ret.ss, nsamples, rw, B);
     run_denoise_rows(c, g, rows.data(), B, bias, p, (flags & ZVX_PCM16) ? 1 : 0);
     ret.finish(nullptr, out, out_stride, rw.cnt.data(), flags);
+}
+
+// ------------------------------------------------------------------------------------------------
+// keyed audio watermark (include/zvx.h: zvx_watermark, zvx_watermark_ex, zvx_watermark_detect; kernels: watermark.hip)
+// ------------------------------------------------------------------------------------------------
+uint64_t wm_mix64(uint64_t z) {                              // the splitmix64 finaliser
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+struct WmPlan { DnGeom g; int k_lo, J; };
+// the checks of the watermark's own parameters (embedder and detector) -> the model's STFT geometry and the bands
+WmPlan watermark_params_check(const zvx_ctx* c, const char* who, const zvx_watermark_params* p) {
+    if (!p) fail(ZVX_E_INVALID, "%s: params is NULL", who);
+    if (!std::isfinite(p->depth_db) || p->depth_db < 0.f || p->depth_db > 6.f) fail(ZVX_E_INVALID, "%s: depth_db must be finite and lie in [0, 6]", who);
+    if (!std::isfinite(p->lo_hz) || !std::isfinite(p->hi_hz) || p->lo_hz < 0.f || !(p->lo_hz < p->hi_hz))
+        fail(ZVX_E_INVALID, "%s: band %g .. %g Hz needs finite 0 <= lo_hz < hi_hz", who, (double)p->lo_hz, (double)p->hi_hz);
+    if (p->block_frames < 1) fail(ZVX_E_INVALID, "%s: block_frames %d must be at least 1", who, p->block_frames);
+    if (p->band_bins < 1) fail(ZVX_E_INVALID, "%s: band_bins %d must be at least 1", who, p->band_bins);
+    if (p->period_blocks < 1 || p->period_blocks > WM_MAX_PERIOD) fail(ZVX_E_INVALID, "%s: period_blocks %d outside [1, %d]", who, p->period_blocks, WM_MAX_PERIOD);
+    if (p->reserved != 0) fail(ZVX_E_INVALID, "%s: reserved is %d (must be 0)", who, p->reserved);
+    const DnGeom g = dn_geom(c, who);
+    const double rate = (double)model_rate(c), N = (double)g.n_fft;
+    const double k_lo = ceil((double)p->lo_hz * N / rate), top = std::min((double)p->hi_hz * N / rate, N / 2.0);
+    const double J = floor((top - k_lo) / (double)p->band_bins);
+    if (!(J >= 3.0)) fail(ZVX_E_INVALID, "%s: %g .. %g Hz in bands of %d bins gives %.0f bands (at least 3)", who, (double)p->lo_hz, (double)p->hi_hz, p->band_bins, std::max(J, 0.0));
+    if (J > (double)WM_MAX_BANDS) fail(ZVX_E_UNSUPPORTED, "%s: %.0f bands (at most %d)", who, J, WM_MAX_BANDS);
+    return {g, (int)k_lo, (int)J};
+}
+// the P x J pattern of +1 / -1 bytes on the device, through the pinned staging arena
+const signed char* wm_sign_table(zvx_ctx* c, const zvx_watermark_params* p, int J) {
+    const int P = p->period_blocks;
+    std::vector<signed char> sg((size_t)P * J);
+    for (int ci = 0; ci < P; ci++)
+        for (int j = 0; j < J; j++)
+            sg[(size_t)ci * J + j] = (wm_mix64(p->key ^ (((uint64_t)ci << 32) | (uint64_t)j)) >> 63) ? 1 : -1;
+    signed char* d = (signed char*)c->buf("wm.sign", sg.size());
+    c->upload(d, sg.data(), sg.size());
+    return d;
+}
+
+// The embedder over B rows with a window each: the denoiser's row table, its overlap-add launch, the keyed gain in the frames launch.
+// The caller has validated the rows.
+void run_watermark_rows(zvx_ctx* c, const WmPlan& wp, const PostRow* rows, int B, const zvx_watermark_params* p, int pcm16) {
+    const DnGeom& g = wp.g;
+    const bool copy = p->depth_db == 0.f;
+    DnRowsPlan pl = dn_rows_plan(g, rows, B, copy);
+    WatermarkArgs a{};
+    dn_rows_upload(c, g, pl, B, copy, pcm16, a.dn);
+    if (!copy) {
+        a.sign = wm_sign_table(c, p, wp.J);
+        a.k_lo = wp.k_lo; a.KB = p->band_bins; a.J = wp.J; a.TB = p->block_frames; a.P = p->period_blocks;
+        a.g_up = (float)pow(10.0, (double)p->depth_db / 20.0); a.g_dn = (float)pow(10.0, -(double)p->depth_db / 20.0);
+    }
+    TagScope scope(c, "post.watermark");
+    c->timed(copy ? 0.0 : dn_fft_flops(g, pl.frames, 2), 4.0 * pl.n_sum + (pcm16 ? 2.0 : 4.0) * pl.cnt_sum, [&] {
+        if (!copy) launch_watermark_frames(a, c->stream);
+        launch_denoise_ola(a.dn, pl.cnt_max, c->stream);
+    });
+}
+
+// zvx_watermark and zvx_watermark_ex: every check before anything is allocated, uploaded or queued
+void do_watermark(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_watermark_params* p,
+                  void* out, int64_t out_stride, int flags, const WindowsIn& win = {}) {
+    rows_check(who, in, nsamples, B, Nmax, 65535);
+    flags_check(who, flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16);
+    out_rows_check(who, in, out, out_stride, Nmax, flags);
+    const WmPlan wp = watermark_params_check(c, who, p);
+    const DnGeom& g = wp.g;
+    const RowsWindows rw = rows_windows_check(who, win, nsamples, B, g.n_fft - 1, in, out, out_stride);
+    for (int b = 0; b < B; b++)                              // zvx_melspec's length conditions hold for the whole SIGNAL: known where it ends with the window
+        if (rw.at(b).last && nsamples[b] > 0 && rw.at(b).in_origin + nsamples[b] < dn_min_samples(g))
+            fail(ZVX_E_INVALID, "%s: row %d has %lld samples; a row that is not empty needs at least %d (zvx_melspec's conditions)", who, b,
+                 (long long)(rw.at(b).in_origin + nsamples[b]), dn_min_samples(g));
+    RowsReturn ret(c, B, 0, false, true, rw.cnt_max, flags);
+    const float* x = rows_to_device(c, "wm", in, B, Nmax, flags);
+    long out_bs = 0;
+    void* od = ret.out_rows("wm.out", out, out_stride, &out_bs);
+    const std::vector<PostRow> rows = post_rows(x, Nmax, od, out_bs, ret.ss, nsamples, rw, B);
+    run_watermark_rows(c, wp, rows.data(), B, p, (flags & ZVX_PCM16) ? 1 : 0);
+    ret.finish(nullptr, out, out_stride, rw.cnt.data(), flags);
+}
+
+// zvx_watermark_detect: every check before anything is allocated, uploaded or queued; the call's one wait brings every window's result over
+void do_watermark_detect(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_watermark_params* p, int window_frames,
+                         float* score, int32_t* offset, int32_t* window, float* win_score, int32_t* win_offset, int NWmax, int flags) {
+    const char* who = "zvx_watermark_detect";
+    const RowsInfo ri = rows_check(who, in, nsamples, B, Nmax, 65535);
+    flags_check(who, flags, ZVX_DEVICE_IN);
+    const WmPlan wp = watermark_params_check(c, who, p);
+    const DnGeom& g = wp.g;
+    if (!score || !offset || !window) fail(ZVX_E_INVALID, "%s: score, offset or window is NULL", who);
+    if (window_frames < 0 || window_frames == 1) fail(ZVX_E_INVALID, "%s: window_frames %d (0: the row; otherwise at least 2)", who, window_frames);
+    if (!win_score != !win_offset) fail(ZVX_E_INVALID, "%s: win_score and win_offset go together (one of them is NULL)", who);
+    if (NWmax < 0) fail(ZVX_E_INVALID, "%s: NWmax %d is negative", who, NWmax);
+    int NW = 0;
+    long Fmax = 0;
+    double frames = 0;
+    size_t d_floats = 0;
+    const int JD = wp.J - 2;
+    std::vector<WmDetectRow> tab((size_t)B);
+    std::vector<size_t> d_at((size_t)B);
+    for (int b = 0; b < B; b++) {
+        if (nsamples[b] > 0 && nsamples[b] < dn_min_samples(g))
+            fail(ZVX_E_INVALID, "%s: row %d has %d samples; a row that is not empty needs at least %d (zvx_melspec's conditions)", who, b, nsamples[b], dn_min_samples(g));
+        const int F = dn_frames(g, nsamples[b]), nw = wm_windows(F, window_frames);
+        if (win_score && nw > NWmax) fail(ZVX_E_BUFFER, "%s: row %d has %d windows, NWmax is %d", who, b, nw, NWmax);
+        tab[(size_t)b] = WmDetectRow{nullptr, nullptr, nsamples[b], F};
+        d_at[(size_t)b] = d_floats; d_floats += (size_t)F * JD;
+        NW = std::max(NW, nw); Fmax = std::max<long>(Fmax, F); frames += F;
+    }
+    const int NWp = std::max(NW, 1);
+    const size_t res_each = (size_t)B * NWp * 4, res_pad = (res_each + 255) & ~(size_t)255;
+    char* host = (char*)c->join_pinned(2 * res_pad);
+    const float* x = rows_to_device(c, "wm", in, B, Nmax, flags);
+    WmDetectArgs a{};
+    const zvx_ctx::DnTables& tb = dn_tables(c, g);
+    a.B = B; a.n_fft = g.n_fft; a.log2n = g.log2n; a.hop = g.hop; a.pad = g.pad; a.Fmax = (int)Fmax;
+    a.twid = tb.twid; a.win = tb.win;
+    a.sign = wm_sign_table(c, p, wp.J);
+    a.k_lo = wp.k_lo; a.KB = p->band_bins; a.J = wp.J; a.TB = p->block_frames; a.P = p->period_blocks;
+    a.WF = window_frames; a.NW = NWp;
+    float* d = c->fbuf("wm.d", std::max<size_t>(d_floats, 1));
+    char* res = (char*)c->buf("wm.res", 2 * res_pad);
+    a.win_score = (float*)res; a.win_offset = (int*)(res + res_pad);
+    for (int b = 0; b < B; b++) { tab[(size_t)b].x = x + (size_t)b * Nmax; tab[(size_t)b].d = d + d_at[(size_t)b]; }
+    WmDetectRow* tab_d = (WmDetectRow*)c->buf("wm.rows", (size_t)B * sizeof(WmDetectRow));
+    c->upload(tab_d, tab.data(), (size_t)B * sizeof(WmDetectRow));
+    a.rows = tab_d;
+    {
+        TagScope scope(c, "post.wmdetect");
+        c->timed(dn_fft_flops(g, frames, 1), 4.0 * ri.n_sum + 8.0 * frames * JD, [&] {
+            launch_wm_bands(a, c->stream);
+            if (NW > 0) launch_wm_search(a, c->stream);
+        });
+    }
+    if (NW > 0) HIPCHK(hipMemcpyAsync(host, res, 2 * res_pad, hipMemcpyDeviceToHost, c->stream));
+    c->sync();                                               // the call's one wait
+    const float* hs = (const float*)host;
+    const int32_t* ho = (const int32_t*)(host + res_pad);
+    for (int b = 0; b < B; b++) {
+        const int nw = wm_windows(tab[(size_t)b].F, window_frames);
+        float best = 0.f; int32_t bo = 0, bw = 0;
+        for (int w = 0; w < nw; w++) {
+            const float z = hs[(size_t)b * NWp + w];
+            if (w == 0 || z > best) { best = z; bo = ho[(size_t)b * NWp + w]; bw = w; }
+            if (win_score) { win_score[(size_t)b * NWmax + w] = z; win_offset[(size_t)b * NWmax + w] = ho[(size_t)b * NWp + w]; }
+        }
+        score[b] = best; offset[b] = bo; window[b] = bw;
+    }
 }
 
 // zvx_resample_rows: every check before anything is allocated, uploaded or queued
@@ -4068,6 +4232,27 @@ zvx_status zvx_denoise_ex(zvx_ctx* c, const float* in, const int32_t* nsamples, 
     return guarded(c, [&] {
         const WindowsIn win{WindowsIn::ONE, RowsWindow{in_origin, out_begin, out_count, last}};
         do_denoise(c, "zvx_denoise_ex", in, nsamples, B, Nmax, bias, params, out, out_stride, flags, win);
+    });
+}
+
+zvx_status zvx_watermark(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_watermark_params* params, void* out,
+                         int64_t out_stride, int flags) {
+    return guarded(c, [&] { do_watermark(c, "zvx_watermark", in, nsamples, B, Nmax, params, out, out_stride, flags); });
+}
+
+zvx_status zvx_watermark_ex(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_watermark_params* params, void* out,
+                            int64_t out_stride, int flags, int64_t in_origin, int64_t out_begin, int64_t out_count, int last) {
+    return guarded(c, [&] {
+        const WindowsIn win{WindowsIn::ONE, RowsWindow{in_origin, out_begin, out_count, last}};
+        do_watermark(c, "zvx_watermark_ex", in, nsamples, B, Nmax, params, out, out_stride, flags, win);
+    });
+}
+
+zvx_status zvx_watermark_detect(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_watermark_params* params,
+                                int window_frames, float* score, int32_t* offset, int32_t* window, float* win_score, int32_t* win_offset,
+                                int NWmax, int flags) {
+    return guarded(c, [&] {
+        do_watermark_detect(c, in, nsamples, B, Nmax, params, window_frames, score, offset, window, win_score, win_offset, NWmax, flags);
     });
 }
 

@@ -16,6 +16,10 @@ waveform on the device, directly behind the vocoder (zvx_denoise; 0.01 is the us
 range, maximum momentary and short-term loudness, sample and true peak are printed, and with --loudness whether it meets that target.
 `--pitch-report`: the finished waveform's F0 track is measured on the device (zvx_pitch) and its median, 5th .. 95th percentile range in Hz
 and semitones, mean and voiced fraction are printed: what --pitch-shift / --pitch-range did to the audio.
+`--watermark KEY`: the waveform carries the keyed mark of zvx_watermark (tts, --long and the --level stream alike; KEY as 0x... or decimal).
+`--detect-watermark KEY FILE`: no synthesis -- the 16-bit mono WAV file is searched for KEY's mark on the device (zvx_watermark_detect) and
+the score, offset and decision are printed.  Detection is measured on synthetic signals only; short telephone-band clips are not reliably
+detectable, and nothing is claimed about audibility or robustness against codecs.
 """
 import argparse
 import os
@@ -28,7 +32,7 @@ from .synthesize import ZeroVoxTTS, write_wav_to_file
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("text")
+    ap.add_argument("text", nargs="?", default="")
     ap.add_argument("--model", default="synthetic:styletts")
     ap.add_argument("--meldec-model", default="synthetic:v1")
     ap.add_argument("--infer-device", default="cuda")
@@ -54,7 +58,12 @@ def main():
     ap.add_argument("--long", action="store_true", help="long-form: split the text (or the file it names) into sentences and join them on the device")
     ap.add_argument("--report", action="store_true", help="measure the finished waveform on the device and print its programme loudness report")
     ap.add_argument("--pitch-report", action="store_true", help="measure the finished waveform's F0 track on the device and print its pitch report")
+    ap.add_argument("--watermark", type=lambda v: int(v, 0), default=None, metavar="KEY", help="mark the waveform with this key on the device (default: off)")
+    ap.add_argument("--detect-watermark", nargs=2, default=None, metavar=("KEY", "FILE"),
+                    help="no synthesis: search the 16-bit mono WAV FILE for KEY's mark and print the result")
     args = ap.parse_args()
+    if args.detect_watermark is None and not args.text:
+        ap.error("the text is missing")
     if args.level is not None and (args.long or args.loudness is not None):
         ap.error("--level streams one utterance: it goes with neither --long nor --loudness")
 
@@ -62,6 +71,16 @@ def main():
     if args.out_rate:
         synth.output_rate = args.out_rate
     sr = synth.output_rate                                  # RTF and the WAV header follow the rate of the samples handed back
+    if args.detect_watermark is not None:
+        import wave
+        with wave.open(args.detect_watermark[1], "rb") as f:
+            if f.getnchannels() != 1 or f.getsampwidth() != 2:
+                ap.error("--detect-watermark reads 16-bit mono WAV files")
+            rate, pcm = f.getframerate(), np.frombuffer(f.readframes(f.getnframes()), np.int16)
+        res = synth.detect_watermark(pcm, int(args.detect_watermark[0], 0), sampling_rate=rate)
+        print(f"watermark: {'DETECTED' if res.detected else 'not detected'} (score {res.score:.2f}, threshold {res.threshold:g}, offset "
+              f"{res.offset} frames, window {res.window} of {len(res.windows)})")
+        return
     print("computing speaker embedding...")
     refmel = np.random.default_rng(0).standard_normal((args.refmel_frames, modelcfg["audio"]["num_mels"])).astype(np.float32)
     spkemb = synth.speaker_embed_from_mel(refmel)
@@ -78,7 +97,7 @@ def main():
             wav, segments = synth.tts_long(text, spkemb, speed=args.speed, pitch_shift=args.pitch_shift, pitch_range=args.pitch_range,
                                            energy_shift=args.energy_shift, energy_range=args.energy_range, loudness=args.loudness,
                                            peak_db=args.peak_db, limiter=args.limiter, limiter_ms=args.limiter_ms, denoise=args.denoise,
-                                           report=args.report, pitch_report=args.pitch_report)
+                                           report=args.report, pitch_report=args.pitch_report, watermark=args.watermark)
             elapsed = time.time() - t0
             wav_len = (wav.shape[0] if segments else 0) / sr
             print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, {len(segments)} sentences, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")
@@ -95,7 +114,7 @@ def main():
             pieces = list(synth.tts_stream(args.text, spkemb, speed=args.speed, pitch_shift=args.pitch_shift, pitch_range=args.pitch_range,
                                            energy_shift=args.energy_shift, energy_range=args.energy_range, level_lufs=args.level,
                                            peak_db=args.peak_db if args.limiter else None, limiter_ms=args.limiter_ms,
-                                           denoise_strength=args.denoise))
+                                           denoise_strength=args.denoise, watermark=args.watermark))
             wav = np.concatenate(pieces) if pieces else np.zeros(0, np.float32)
             elapsed = time.time() - t0
             wav_len = wav.shape[0] / sr
@@ -112,7 +131,7 @@ def main():
         wav, phoneme, length = synth.tts(args.text, spkemb, speed=args.speed, pitch_shift=args.pitch_shift, pitch_range=args.pitch_range,
                                          energy_shift=args.energy_shift, energy_range=args.energy_range, loudness=args.loudness,
                                          peak_db=args.peak_db, limiter=args.limiter, limiter_ms=args.limiter_ms, denoise=args.denoise,
-                                         report=args.report, pitch_report=args.pitch_report)
+                                         report=args.report, pitch_report=args.pitch_report, watermark=args.watermark)
         elapsed = time.time() - t0
         wav_len = wav.shape[0] / sr
         print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")

@@ -77,9 +77,9 @@ def split_sentences(text, max_chars=MAX_CHARS):
 
 def synthesize_long(tts, text, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20, fade_ms=5, max_batch=32, max_frames=2048, pcm16=False,
                     durations=None, max_chars=MAX_CHARS, prosody=None, loudness=None, peak_db=-1.0, loudness_mode="paragraph",
-                    limiter=False, limiter_ms=5.0, denoise=None, report=False):
+                    limiter=False, limiter_ms=5.0, denoise=None, report=False, watermark=None):
     """The body of ZeroVoxTTS.tts_long (see there).  prosody: Prosody.create keywords applied to every sentence, or None.  denoise: None or
-    Context.denoise_device keywords (strength, floor)."""
+    Context.denoise_device keywords (strength, floor).  watermark: None or watermark.params(...) (key and the embedder's parameters)."""
     from . import _lib
     if loudness_mode not in LOUDNESS_MODES:
         raise ValueError(f"loudness_mode: {loudness_mode!r} is none of {sorted(LOUDNESS_MODES)}")
@@ -138,6 +138,8 @@ def synthesize_long(tts, text, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20,
         lufs, gain = [None] * N, [None] * N
         if denoise is not None:                                  # ONE call over all rows, in place, directly behind the vocoder's rows
             ctx.denoise_device(buf, lengths, stride, bias, no_sync=True, **denoise)
+        if watermark is not None:                                # ONE call over all rows, in place, between denoise and normalise
+            ctx.watermark_device(buf, lengths, stride, no_sync=True, **watermark)
         if loudness is not None:                                 # ONE call over all rows, in place, behind the queued synthesis calls
             lufs, _, gain = ctx.normalize_device(buf, lengths, stride, loudness, peak_ceiling=0.0 if lim else peak_ceiling(peak_db),
                                                  common=LOUDNESS_MODES[loudness_mode], rate=native)

@@ -17,6 +17,7 @@ from .denoiser import DenoisePlanner
 from .leveler import LevelPlanner, reach as level_reach
 from .limiter import LimitPlanner, window_samples
 from .report import LoudnessReport
+from .watermark import WatermarkPlanner
 from .resample import stream_resample
 from .stream import stream_windows
 
@@ -171,7 +172,7 @@ class ZeroVox:
         return self._ctx.spkemb(x, lens)[:, None, :]
 
     def inference_ex(self, x, style_embed, normalize_before=True, force_duration=False, prosody=None, loudness=None, limiter=None,
-                     denoise=None, report=False):
+                     denoise=None, report=False, watermark=None):
         """model.py:308-347.  x = {"phoneme" [1,T], "puncts" [1,T], "duration" [1,T]|None}; returns
         (wav[:mel_len*hop], mel_len, log_duration [1,T], mel [n_mels, mel_len]).  Batch-1 like the reference.
         Under an output_rate the waveform holds resampled_len(mel_len*hop) samples of that rate; mel_len stays in frames.
@@ -179,6 +180,8 @@ class ZeroVox:
         loudness: None (the path above, untouched) or Context.normalize_device keywords (target, peak_ceiling, max_gain_db).
         limiter: None (likewise) or Context.limit_device keywords (ceiling, window_ms, oversample); it runs behind the loudness gain.
         denoise: None (likewise) or Context.denoise_device keywords (strength, floor): the bias denoiser, directly behind the vocoder.
+        watermark: None (likewise) or watermark.params(...) (key and the embedder's parameters): the keyed mark, behind the denoiser and
+        before the loudness gain and the limiter.
         report: with True the returned waveform is measured as delivered (at the output rate, behind every step above; on the device
         where it is still there) and ``last_report`` holds its report.LoudnessReport; False (the default) adds nothing to the call."""
         if denoise is not None:
@@ -199,8 +202,8 @@ class ZeroVox:
         pad_to = self._min_mel_len                       # model.py:331-335: pad up, or raise the floor
         if ml > self._min_mel_len:
             self._min_mel_len = ml
-        if loudness is not None or limiter is not None or denoise is not None:
-            wav = self._vocode_normalized(mel_len, pad_to, loudness, limiter, denoise, report)
+        if loudness is not None or limiter is not None or denoise is not None or watermark is not None:
+            wav = self._vocode_normalized(mel_len, pad_to, loudness, limiter, denoise, report, watermark)
             return wav, ml, logd, np.ascontiguousarray(mel[0, :ml].T)
         wav = self._ctx.vocode(1, mel_len, np.array([pad_to], np.int32))
         wav = wav[0, : self._ctx.out_samples(ml * self._hop_length)]
@@ -208,9 +211,9 @@ class ZeroVox:
             self.loudness_report(wav)
         return wav, ml, logd, np.ascontiguousarray(mel[0, :ml].T)
 
-    def _vocode_normalized(self, mel_len, pad_to, loudness, limiter=None, denoise=None, report=False):
+    def _vocode_normalized(self, mel_len, pad_to, loudness, limiter=None, denoise=None, report=False, watermark=None):
         """The vocoder writes its row on the device at the model's rate, zvx_denoise takes denoise["strength"] times the bias off it in
-        place (queued behind the vocoder: stream order is the fence), zvx_normalize brings it to loudness["target"] in place,
+        place (queued behind the vocoder: stream order is the fence), zvx_watermark lays the keyed mark on it in place, zvx_normalize brings it to loudness["target"] in place,
         zvx_limit holds it under limiter["ceiling"] in place, an output rate converts it,
         and only then the row comes to the host.  Every step may be absent.  self.last_loudness reports dict(lufs, peak, gain),
         self.last_limit dict(peak_in, min_gain); with `report` self.last_report is the finished row's LoudnessReport, measured on the
@@ -224,6 +227,8 @@ class ZeroVox:
             ctx.vocode_device(mel_len, np.array([pad_to], np.int32), buf, n, native_rate=True, no_sync=True)
             if denoise is not None:
                 ctx.denoise_device(buf, [n], n, no_sync=True, **denoise)
+            if watermark is not None:
+                ctx.watermark_device(buf, [n], n, no_sync=True, **watermark)
             if loudness is not None:
                 lufs, peak, gain = ctx.normalize_device(buf, [n], n, rate=native, **loudness)
                 self.last_loudness = dict(lufs=float(lufs[0]), peak=float(peak[0]), gain=float(gain[0]))
@@ -253,7 +258,8 @@ class ZeroVox:
     # each side makes a chunk's interior identical to the same samples of a whole-utterance pass.
     STREAM_HALO = 16
 
-    def vocode_stream(self, mel, chunk_frames=64, halo=STREAM_HALO, chunks_per_call=1, limiter=None, denoise=None, resident=False, level=None):
+    def vocode_stream(self, mel, chunk_frames=64, halo=STREAM_HALO, chunks_per_call=1, limiter=None, denoise=None, resident=False, level=None,
+                      watermark=None):
         """Chunked vocoding for first-audio latency: mel [L, n_mels] -> yields waveform chunks (np.float32) that
         concatenate to ``vocode_mel(mel)``.  Every chunk is vocoded with ``halo`` extra frames on each side and only its
         interior is kept; ``chunks_per_call`` chunks ride in one launch sequence as independent batch rows.
@@ -272,6 +278,10 @@ class ZeroVox:
         whole stream that reaches it; the levelled stream runs RR = leveler.reach(...)[1] samples behind that stage's input (4409
         samples, 200 ms, at 22.05 kHz with the defaults).  The chain is denoise, then level, then limit, then the conversion.  Host-planned
         streams only: sessions have no level stage yet (resident=True with level raises ValueError).
+        watermark: None, or watermark.params(...) (key and the embedder's parameters): the native-rate chunks pass through the windowed
+        embedder (zerovox_amd.watermark, zvx_watermark_ex) and concatenate bit for bit to zvx_watermark of the whole stream that reaches
+        it; the marked stream runs watermark.reach(fft_size) = fft_size - 1 samples behind that stage's input.  The chain is denoise,
+        level, watermark, limit, conversion.  Host-planned streams only (resident=True with watermark raises ValueError).
         resident: False (the default: the host-planned stream above), or True: the same keywords drive a stream session of the library
         (include/zvx.h, zvx_stream_open) -- the mel is uploaded once, the samples stay on the device between the steps and every piece
         costs one wait.  The pieces concatenate to the same bits; where they are cut may differ.  mel None (resident only): the mel the
@@ -279,6 +289,8 @@ class ZeroVox:
         if resident:
             if level is not None:
                 raise ValueError("vocode_stream: stream sessions have no level stage yet (use resident=False with level=)")
+            if watermark is not None:
+                raise ValueError("vocode_stream: stream sessions have no watermark stage yet (use resident=False with watermark=)")
             yield from self._vocode_stream_resident(mel, chunk_frames, halo, chunks_per_call, limiter, denoise)
             return
         ctx = self._ctx
@@ -287,7 +299,7 @@ class ZeroVox:
         if denoise is not None:
             denoise = dict(denoise, bias=self.denoise_bias)          # (first use runs the vocoder: before this stream's first chunk)
         chunks = self._vocode_stream_native(mel, chunk_frames, halo, chunks_per_call,
-                                            convert or limiter is not None or denoise is not None or level is not None)
+                                            convert or limiter is not None or denoise is not None or level is not None or watermark is not None)
         if denoise is not None:
             chunks = stream_windows(chunks, DenoisePlanner(ctx.get_int("fft_size")), lambda x, o, b, n, last: ctx.denoise_window(
                 [x], in_origin=o, out_begin=b, out_count=n, last=last, **denoise)[0].copy())
@@ -296,6 +308,9 @@ class ZeroVox:
             plan = LevelPlanner(*level_reach(native, level["window_ms"], level["lookahead_ms"]))
             chunks = stream_windows(chunks, plan, lambda x, o, b, n, last: ctx.level_window(
                 [x], in_origin=o, out_begin=b, out_count=n, last=last, rate=native, **level)[0][0].copy())
+        if watermark is not None:
+            chunks = stream_windows(chunks, WatermarkPlanner(ctx.get_int("fft_size")), lambda x, o, b, n, last: ctx.watermark_window(
+                [x], in_origin=o, out_begin=b, out_count=n, last=last, **watermark)[0].copy())
         if limiter is not None:
             plan = LimitPlanner(window_samples(native, limiter["window_ms"]), limiter["oversample"])
             chunks = stream_windows(chunks, plan, lambda x, o, b, n, last: ctx.limit_window(

@@ -191,7 +191,7 @@ class ZeroVoxTTS:
         return limit_keywords(limiter, limiter_ms, peak_db)
 
     def tts_ex(self, text: str, spkemb, duration=None, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0,
-               loudness=None, peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None, report=False, pitch_report=False):
+               loudness=None, peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None, report=False, pitch_report=False, watermark=None):
         """-> (wav f32[N], phoneme i32[1,T], length, mel f32[n_mels, L]); empty text -> the reference's sentinel
         (synthesize.py:213-239).  Prosody (include/zvx.h, zvx_prosody): speed = speaking-rate factor (2.0: half the frames),
         pitch / energy shift (in normalised predictor units) and range (spread about the utterance mean).
@@ -207,6 +207,11 @@ class ZeroVoxTTS:
         zvx_denoise; NVIDIA's scripts use 0.01): that multiple of ``denoise_bias`` is taken off the magnitude of every STFT bin of the
         vocoder's row, on the device, in place, directly behind the vocoder -- before the gain, the limiter and the rate conversion.
         Its audible benefit on a real checkpoint is not measured here.
+        watermark: None (the default: nothing changes, bit for bit), an int key, or a dict with ``key`` and any of watermark.EMBED_DEFAULTS
+        (depth_db, lo_hz, hi_hz, block_frames, band_bins, period_blocks): the keyed mark of include/zvx.h, zvx_watermark, laid on the
+        vocoder's row on the device, in place, behind the denoiser and before the loudness gain and the limiter; ``detect_watermark``
+        finds it again with the key.  Whether it is inaudible on a real checkpoint, and whether it survives lossy codecs,
+        time-stretching or deliberate removal, is not measured.
         report: False (the default: nothing is added to the call), or True: the finished waveform is measured as it is delivered -- at
         the output rate, behind every step above, on the device where its buffer is still there (include/zvx.h, zvx_loudness_stats and
         zvx_true_peak) -- and ``last_report`` holds the report.LoudnessReport (see ``loudness_report``).  The waveform is the same.
@@ -216,6 +221,7 @@ class ZeroVoxTTS:
         pkw = self._pitch_keywords(pitch_report)
         prosody = self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range)
         dn = self._denoise(denoise)
+        wm = self._watermark(watermark)
         text = text.strip()
         t0 = time.time()
         phone_ids, punct_ids = self.text2phonemeids(text)
@@ -231,7 +237,7 @@ class ZeroVoxTTS:
         wav, length, _, mel = self._model.inference_ex({"phoneme": phoneme, "puncts": puncts, "duration": duration},
                                                        style_embed=spkemb, force_duration=duration is not None, prosody=prosody,
                                                        **self._post(loudness, peak_db, limiter, limiter_ms, dn),
-                                                       **({"report": True} if report else {}))
+                                                       **({"report": True} if report else {}), **({} if wm is None else {"watermark": wm}))
         if self._verbose:
             print(f"tts timing stats: g2p={t1 - t0}s, synth={time.time() - t1}s")
         if pkw is not None:
@@ -249,12 +255,45 @@ class ZeroVoxTTS:
         return kw
 
     def tts(self, text: str, spkemb, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0, loudness=None,
-            peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None, report=False, pitch_report=False):
+            peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None, report=False, pitch_report=False, watermark=None):
         wav, phoneme, length, _ = self.tts_ex(text=text, spkemb=spkemb, speed=speed, pitch_shift=pitch_shift, pitch_range=pitch_range,
                                               energy_shift=energy_shift, energy_range=energy_range, loudness=loudness, peak_db=peak_db,
                                               limiter=limiter, limiter_ms=limiter_ms, denoise=denoise, report=report,
-                                              pitch_report=pitch_report)
+                                              pitch_report=pitch_report, watermark=watermark)
         return wav, phoneme, length
+
+    @staticmethod
+    def _watermark(watermark):
+        """the watermark keyword (None, an int key, or a dict with ``key``) as Context.watermark_device keywords, or None; checked without
+        a device"""
+        from .watermark import params
+        return params(watermark)
+
+    def detect_watermark(self, wav, key, sampling_rate=None, *, window_frames=None, threshold=None, **params):
+        """Does this audio carry the mark of `key`?  wav: one waveform (float, or int16 PCM read as the samples it encodes) at
+        sampling_rate Hz (None: the model's) -> watermark.WatermarkResult(score, offset, window, detected, threshold, windows), from
+        the device (include/zvx.h, zvx_watermark_detect).  A waveform at another rate is converted to the model's first (zvx_resample)
+        and hi_hz is lowered to what survived the lower of the two rates (0.45 of it).  params: the embedder's lo_hz, hi_hz,
+        block_frames, band_bins, period_blocks where they were not the defaults; window_frames (default 256) and threshold (default
+        watermark.THRESHOLD).  Short clips cut to the telephone band are not reliably detectable; nothing is claimed about lossy
+        codecs, time-stretching or deliberate removal."""
+        from . import watermark as wm
+        p = wm.params({"key": key, **params})
+        wav = np.asarray(wav)
+        if wav.dtype == np.int16:
+            wav = wav.astype(np.float32) / np.float32(32760.0)
+        wav = np.asarray(wav, np.float32).reshape(-1)
+        ctx = self._model.ctx
+        native = ctx.get_int("sampling_rate")
+        rate = native if sampling_rate is None else int(sampling_rate)
+        if rate != native:
+            out, out_len = ctx.resample([wav], rate, native)
+            wav = out[0, :out_len[0]]
+            p["hi_hz"] = min(p["hi_hz"], 0.45 * min(rate, native))
+            wm.check(p)
+        p.pop("depth_db")
+        return ctx.watermark_detect([wav], p.pop("key"), window_frames=wm.WINDOW_FRAMES if window_frames is None else int(window_frames),
+                                    threshold=threshold, **p)[0]
 
     @staticmethod
     def _pitch_keywords(pitch_report):
@@ -329,7 +368,7 @@ class ZeroVoxTTS:
 
     def tts_stream(self, text: str, spkemb, chunk_frames=64, chunks_per_call=1, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0,
                    energy_shift=0.0, energy_range=1.0, loudness=None, limiter=False, peak_db=None, limiter_ms=5.0, denoise=None,
-                   denoise_strength=None, resident=False, level_lufs=None, level_window_ms=3000.0, level_lookahead_ms=100.0):
+                   denoise_strength=None, resident=False, level_lufs=None, level_window_ms=3000.0, level_lookahead_ms=100.0, watermark=None):
         """Streaming variant of ``tts`` (not in the reference): encoder + mel decoder run once, the vocoder
         runs chunk by chunk (16-frame halo), yielding float32 waveform pieces that concatenate to ``tts(text, spkemb)[0]``
         up to the reference's `_min_mel_len` zero-padding of short utterances.  A stream cannot be loudness-normalised: the gain is not
@@ -353,6 +392,10 @@ class ZeroVoxTTS:
         The pieces concatenate bit for bit to zvx_level of the stream that reaches the stage; the chain is denoise, level, limit,
         conversion, and the levelled stream runs (a + 1) h - 1 samples behind the stage's input (4409: 200 ms at 22.05 kHz with the
         defaults).  Host-planned streams only: with ``resident=True`` it raises ValueError (sessions have no level stage yet).
+        watermark: None (the default: nothing changes), an int key, or a dict with ``key`` (see tts_ex): the stream is marked window by
+        window (include/zvx.h, zvx_watermark_ex; zerovox_amd.watermark).  The pieces concatenate bit for bit to zvx_watermark of the
+        stream that reaches the stage; the chain is denoise, level, watermark, limit, conversion, and the marked stream runs n_fft - 1
+        samples more behind.  Host-planned streams only: with ``resident=True`` it raises ValueError (no watermark stage yet).
         resident: False (the default: the stream is planned on the host), or True: a stream session of the library runs it (include/zvx.h,
         zvx_stream_open; ZeroVox.vocode_stream(resident=True)) -- the decoder's mel never leaves the device and every piece costs one
         wait.  The concatenation is the same to the bit; the pieces may be cut elsewhere."""
@@ -361,7 +404,10 @@ class ZeroVoxTTS:
         lvl = self._level(level_lufs, level_window_ms, level_lookahead_ms)
         if lvl is not None and resident:
             raise ValueError("tts_stream: stream sessions have no level stage yet: level_lufs needs resident=False")
-        return self._tts_stream(text, spkemb, chunk_frames, chunks_per_call, prosody, lim, den, resident, lvl)
+        wm = self._watermark(watermark)
+        if wm is not None and resident:
+            raise ValueError("tts_stream: stream sessions have no watermark stage yet: watermark needs resident=False")
+        return self._tts_stream(text, spkemb, chunk_frames, chunks_per_call, prosody, lim, den, resident, lvl, wm)
 
     @staticmethod
     def _level(level_lufs, window_ms, lookahead_ms):
@@ -401,7 +447,7 @@ class ZeroVoxTTS:
 
     def tts_stream_many(self, texts, spkembs, chunk_frames=64, chunks_per_call=1, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0,
                         energy_shift=0.0, energy_range=1.0, loudness=None, limiter=False, peak_db=None, limiter_ms=5.0, denoise=None,
-                        denoise_strength=None, max_frames=2048, level_lufs=None, level_window_ms=3000.0, level_lookahead_ms=100.0):
+                        denoise_strength=None, max_frames=2048, level_lufs=None, level_window_ms=3000.0, level_lookahead_ms=100.0, watermark=None):
         """Many texts streamed together -> yields (index, piece), non-empty float32 pieces only; the stream keywords are those of
         ``tts_stream`` and apply to every text.  spkembs: one embedding per text ([B, hidden]), or one for all.  The front end runs as ONE
         batch (``synthesize_batch(want_mel=True)``, at most max_frames mel frames per text), one stream session is opened on every mel,
@@ -412,6 +458,8 @@ class ZeroVoxTTS:
                                                   limiter_ms, denoise, denoise_strength)
         if level_lufs is not None:
             raise ValueError("tts_stream_many: stream sessions have no level stage yet: level_lufs is tts_stream's (resident=False)")
+        if watermark is not None:
+            raise ValueError("tts_stream_many: stream sessions have no watermark stage yet: watermark is tts_stream's (resident=False)")
         return self._tts_stream_many(list(texts), spkembs, chunk_frames, chunks_per_call, prosody, lim, den, int(max_frames))
 
     def _tts_stream_many(self, texts, spkembs, chunk_frames, chunks_per_call, prosody, limiter, denoise, max_frames):
@@ -439,7 +487,8 @@ class ZeroVoxTTS:
                                                        denoise=denoise):
             yield keep[b], piece
 
-    def _tts_stream(self, text, spkemb, chunk_frames, chunks_per_call, prosody, limiter=None, denoise=None, resident=False, level=None):
+    def _tts_stream(self, text, spkemb, chunk_frames, chunks_per_call, prosody, limiter=None, denoise=None, resident=False, level=None,
+                    watermark=None):
         text = text.strip()
         phone_ids, punct_ids = self.text2phonemeids(text)
         if not phone_ids:
@@ -460,12 +509,12 @@ class ZeroVoxTTS:
             return
         mel = ctx.decode(1, ml)[0, :ml]
         yield from self._model.vocode_stream(mel, chunk_frames=chunk_frames, chunks_per_call=chunks_per_call, limiter=limiter,
-                                             denoise=denoise, level=level)
+                                             denoise=denoise, level=level, **({} if watermark is None else {"watermark": watermark}))
 
     def tts_long(self, text: str, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20, fade_ms=5, max_batch=32, max_frames=2048, pcm16=False,
                  durations=None, max_chars=200, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0,
                  loudness=None, peak_db=-1.0, loudness_mode="paragraph", limiter=False, limiter_ms=5.0, denoise=None, report=False,
-                 pitch_report=False):
+                 pitch_report=False, watermark=None):
         """A paragraph -> (wav, segments): one waveform with every sentence in text order (not in the reference).  The text is split by
         longform.split_sentences; the sentences run in batches of at most max_batch, each batch ONE queued synthesize call into
         consecutive rows of one device buffer (every row is the fresh-model ``tts`` of its sentence; a sentence of more than max_frames
@@ -490,6 +539,9 @@ class ZeroVoxTTS:
         denoise: None, or the strength of the vocoder-bias denoiser (see tts_ex): ONE zvx_denoise over all rows of the device buffer, in
         place, behind the synthesis calls and before the normalise.  The segments' layout is that of the same call without it whenever
         trim_db <= 0 (the trim decides on the denoised rows).
+        watermark: None (the default: nothing changes), an int key, or a dict with ``key`` (see tts_ex): ONE zvx_watermark over all
+        sentence rows of the device buffer, in place, between the denoise and the normalise; every sentence's pattern starts at its own
+        first frame, so ``detect_watermark`` finds each sentence at its own offset through its windows.
         report: False (the default: nothing is added to the call), or True: the joined waveform is measured as it is delivered, at the
         output rate, and ``last_report`` holds its report.LoudnessReport (see ``loudness_report``).  A float waveform at the model's
         rate is joined into a device buffer, measured there and copied to the host afterwards -- the same bits as without the report --;
@@ -507,7 +559,8 @@ class ZeroVoxTTS:
                                max_frames=max_frames, pcm16=pcm16, durations=durations, max_chars=max_chars,
                                prosody=self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range),
                                loudness=loudness, peak_db=peak_db, loudness_mode=loudness_mode, limiter=limiter, limiter_ms=limiter_ms,
-                               denoise=self._denoise(denoise), **({"report": True} if report else {}))
+                               denoise=self._denoise(denoise), **({"report": True} if report else {}),
+                               **({} if watermark is None else {"watermark": self._watermark(watermark)}))
         if pkw is not None:
             self._last_pitch_report = None
         if pkw is not None and segments:
