@@ -159,7 +159,18 @@ class StageArgs(ctypes.Structure):
                 ("len", _p), ("M", _i), ("nbatch", _i), ("f16", _i)]
 
 
-STRUCTS = {"GemmArgs": GemmArgs, "FlashArgs": FlashArgs, "AttnF32Args": AttnF32Args, "StreamArgs": StreamArgs, "StageArgs": StageArgs}
+class WmDetectRow(ctypes.Structure):
+    _fields_ = [("x", _p), ("d", _p), ("n", _i), ("F", _i)]
+
+
+class WmDetectArgs(ctypes.Structure):
+    _fields_ = [("rows", _p), ("B", _i), ("n_fft", _i), ("log2n", _i), ("hop", _i), ("pad", _i), ("Fmax", _i), ("twid", _p), ("win", _p),
+                ("sign", _p), ("k_lo", _i), ("KB", _i), ("J", _i), ("TB", _i), ("P", _i), ("WF", _i), ("NW", _i), ("win_score", _p),
+                ("win_offset", _p)]
+
+
+STRUCTS = {"GemmArgs": GemmArgs, "FlashArgs": FlashArgs, "AttnF32Args": AttnF32Args, "StreamArgs": StreamArgs, "StageArgs": StageArgs,
+           "WmDetectRow": WmDetectRow, "WmDetectArgs": WmDetectArgs}
 
 
 def load_ktest():
@@ -183,6 +194,9 @@ def load_ktest():
     lib.zvxk_narrowstage.argtypes = [ctypes.POINTER(StageArgs), ctypes.c_int]
     lib.zvxk_pack_narrow.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_void_p]
     lib.zvxk_narrowstage_steps.argtypes = [ctypes.c_int, ctypes.c_int]
+    lib.zvxk_fft_probe.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int, ctypes.c_int]
+    lib.zvxk_wm_bands.argtypes = [ctypes.POINTER(WmDetectArgs)]
+    lib.zvxk_wm_search.argtypes = [ctypes.POINTER(WmDetectArgs)]
     lib.zvxk_variant_name.restype = ctypes.c_char_p
     lib.zvxk_sizeof.restype = ctypes.c_long
     lib.zvxk_sizeof.argtypes = [ctypes.c_char_p]

@@ -7,6 +7,8 @@
 #include <stddef.h>
 #include <string.h>
 #include "../../zerovox_amd/csrc/zvx_kernels.h"
+#include "../../zerovox_amd/csrc/watermark_kernels.h"
+#include "../../zerovox_amd/csrc/spectral_fft.h"
 
 using namespace zvx;
 
@@ -50,6 +52,11 @@ const Field kFields[] = {
     F_(StageArgs, X), F_(StageArgs, x_bs), F_(StageArgs, ldx), F_(StageArgs, W), F_(StageArgs, woff), F_(StageArgs, bias), F_(StageArgs, C),
     F_(StageArgs, nk), F_(StageArgs, ks), F_(StageArgs, dil), F_(StageArgs, out), F_(StageArgs, o_bs), F_(StageArgs, ldo), F_(StageArgs, slope1),
     F_(StageArgs, res_inv_slope), F_(StageArgs, slope), F_(StageArgs, len), F_(StageArgs, M), F_(StageArgs, nbatch), F_(StageArgs, f16),
+    F_(WmDetectRow, x), F_(WmDetectRow, d), F_(WmDetectRow, n), F_(WmDetectRow, F),
+    F_(WmDetectArgs, rows), F_(WmDetectArgs, B), F_(WmDetectArgs, n_fft), F_(WmDetectArgs, log2n), F_(WmDetectArgs, hop), F_(WmDetectArgs, pad),
+    F_(WmDetectArgs, Fmax), F_(WmDetectArgs, twid), F_(WmDetectArgs, win), F_(WmDetectArgs, sign), F_(WmDetectArgs, k_lo), F_(WmDetectArgs, KB),
+    F_(WmDetectArgs, J), F_(WmDetectArgs, TB), F_(WmDetectArgs, P), F_(WmDetectArgs, WF), F_(WmDetectArgs, NW), F_(WmDetectArgs, win_score),
+    F_(WmDetectArgs, win_offset),
 };
 #undef F_
 
@@ -58,6 +65,18 @@ __global__ void k_math_probe(int fn, const float* in, float* out, int n) {
     if (i >= n) return;
     const float x = in[i];
     out[i] = fn == 0 ? expf(x) : fn == 1 ? tanhf(x) : fn == 2 ? logf(x) : fn == 3 ? sqrtf(x) : 1.0f / x;
+}
+
+// dn_fft of spectral_fft.h and nothing else: DENOISE_POINTS complex points (DENOISE_POINTS >> log2n frames) into LDS at dn_at, the
+// transform, the planes back.  No window, no scaling.
+template <bool INV>
+__global__ __launch_bounds__(DN_THREADS) void k_fft_probe(float* re, float* im, const float2* twid, int log2n) {
+    __shared__ float sre[DN_PLANE], sim[DN_PLANE];
+    const int tid = threadIdx.x;
+    for (int i = tid; i < DENOISE_POINTS; i += DN_THREADS) { sre[dn_at(i)] = re[i]; sim[dn_at(i)] = im[i]; }
+    __syncthreads();
+    dn_fft<INV>(sre, sim, twid, log2n, tid);
+    for (int i = tid; i < DENOISE_POINTS; i += DN_THREADS) { re[i] = sre[dn_at(i)]; im[i] = sim[dn_at(i)]; }
 }
 }  // namespace
 
@@ -225,6 +244,19 @@ int zvxk_math_probe(int fn, const float* in, float* out, int n) {
     return sync_status();
 }
 
+// ---- the spectral family (tests/test_spectral_gpu.py, tests/spectral_ref.py) ----
+// dn_fft alone over DENOISE_POINTS points in place; twid: n_fft (cos, -sin) pairs as dn_tables designs them; log2n in 2 .. 12
+int zvxk_fft_probe(float* re, float* im, const float* twid, int log2n, int inverse) {
+    if (log2n < 2 || (1 << log2n) > DENOISE_POINTS) return -1;
+    if (inverse) hipLaunchKernelGGL(k_fft_probe<true>, dim3(1), dim3(DN_THREADS), 0, nullptr, re, im, (const float2*)twid, log2n);
+    else hipLaunchKernelGGL(k_fft_probe<false>, dim3(1), dim3(DN_THREADS), 0, nullptr, re, im, (const float2*)twid, log2n);
+    return sync_status();
+}
+// the detector's two launches on a hand-built row table (a->rows on the device)
+int zvxk_wm_bands(const WmDetectArgs* a) { launch_wm_bands(*a, nullptr); return sync_status(); }
+int zvxk_wm_search(const WmDetectArgs* a) { launch_wm_search(*a, nullptr); return sync_status(); }
+int zvxk_wm_table() { return WM_TABLE; }
+
 // ---- layout of the argument structs ----
 long zvxk_sizeof(const char* name) {
     if (!strcmp(name, "GemmArgs")) return (long)sizeof(GemmArgs);
@@ -232,6 +264,8 @@ long zvxk_sizeof(const char* name) {
     if (!strcmp(name, "AttnF32Args")) return (long)sizeof(AttnF32Args);
     if (!strcmp(name, "StreamArgs")) return (long)sizeof(StreamArgs);
     if (!strcmp(name, "StageArgs")) return (long)sizeof(StageArgs);
+    if (!strcmp(name, "WmDetectRow")) return (long)sizeof(WmDetectRow);
+    if (!strcmp(name, "WmDetectArgs")) return (long)sizeof(WmDetectArgs);
     return -1;
 }
 long zvxk_offsetof(const char* st, const char* field) {

@@ -2,8 +2,10 @@
 the exact corners of include/zvx.h on the device's own output, row independence, every form of the call, errors, and the denoise keyword
 of ZeroVoxTTS.tts / tts_long end to end.
 The bound.  Nothing here is exact but the corners: an f32 FFT of 1024 points, a gain, the inverse FFT and an overlap-add of 4 frames.  The
-limit is 4x the largest error MEASURED over the parity cases below (f32 round-off differs between FFT radices and between boxes), and
-must not exceed 1e-4 -- a 1024-point f32 FFT pair cannot justify more."""
+limit of a parity case is rule (c) of tests/spectral_ref.py on the case's own data -- twice the largest element error of two f32
+restatements of the pipeline over 8 data seeds, nothing of it measured on a device -- and never more than the earlier constant, 4x the
+largest error MEASURED over the parity cases below, which stays as a cap (itself capped at 1e-4: a 1024-point f32 FFT pair cannot
+justify more).  The other transform sizes take rule (c) at their own size, under the same cap."""
 import ctypes as C
 
 import numpy as np
@@ -12,6 +14,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import denoise_ref as D
+import spectral_ref as S
 from stream_util import same_bits, vp
 from zerovox_amd import _lib, config as zcfg, pack, weights as zw
 
@@ -46,11 +49,12 @@ def signal(rng, n, n_fft=N_FFT):
     return np.clip(x, -1.0, 1.0).astype(np.float32)
 
 
-def batch(n_fft=N_FFT, hop=HOP, win_length=None, lengths=LENGTHS):
-    """(rows, x [B][odd Nmax] with the sentinel behind every row, n, bias), computed once and left unchanged"""
-    key = (n_fft, hop, win_length or n_fft, tuple(lengths))
+def batch(n_fft=N_FFT, hop=HOP, win_length=None, lengths=LENGTHS, seed=0):
+    """(rows, x [B][odd Nmax] with the sentinel behind every row, n, bias), computed once and left unchanged; seed 0 is what the device
+    runs, the other seeds feed rule (c)"""
+    key = (n_fft, hop, win_length or n_fft, tuple(lengths), seed)
     if key not in _batch:
-        rng = np.random.default_rng(2024 + n_fft)
+        rng = np.random.default_rng(2024 + n_fft + 7919 * seed)
         rows = [signal(rng, k, n_fft) for k in lengths]
         n = np.array(lengths, np.int32)
         nmax = int(n.max())
@@ -70,6 +74,17 @@ def reference(strength, floor, n_fft=N_FFT, hop=HOP, win_length=None, lengths=LE
     if key not in _ref:
         rows, _, _, bias = batch(n_fft, hop, win_length, lengths)
         _ref[key] = [D.denoise(r, bias, np.float32(strength), np.float32(floor), n_fft, hop, win_length or n_fft) for r in rows]
+    return _ref[key]
+
+
+def rule_c(strength, floor, n_fft=N_FFT, hop=HOP, win_length=None, lengths=LENGTHS):
+    """spectral_ref's rule (c) on this case's own data: the largest-element limit of the errors divided by spectral_ref.ola_scale"""
+    key = ("c", strength, floor, n_fft, hop, win_length or n_fft, tuple(lengths))
+    if key not in _ref:
+        def data(seed):
+            rows, _, _, bias = batch(n_fft, hop, win_length, lengths, seed)
+            return rows, bias
+        _ref[key] = S.denoise_margin_of(data, strength, floor, n_fft, hop, win_length or n_fft)
     return _ref[key]
 
 
@@ -104,14 +119,19 @@ def test_parity_with_the_float64_reference(strength, floor):
     out = run(ctx, x, n, bias, strength, floor)
     assert untouched(out, n)
     ref = reference(strength, floor)
-    worst = 0.0
+    mg = rule_c(strength, floor)
+    print(mg.line(f"denoise strength {strength} floor {floor}"))
+    worst, share = 0.0, 0.0
     for b, r in enumerate(ref):
-        err = float(np.max(np.abs(out[b, :n[b]].astype(np.float64) - r)))
+        e = np.abs(out[b, :n[b]].astype(np.float64) - r)
+        bound = np.minimum(LIMIT, mg.max_limit * S.ola_scale(int(n[b]), N_FFT, HOP, N_FFT))
+        err = float(e.max())
         changed = float(np.max(np.abs(r - rows[b].astype(np.float64))))
         print(f"strength {strength} floor {floor} row {b} (n = {n[b]}): max |out - ref| = {err:.3e}, the denoiser moves the row by up to {changed:.3f}")
         assert changed > 0.05, (b, changed)                  # the cases do subtract: many bins clamp
-        worst = max(worst, err)
-    print(f"strength {strength} floor {floor}: worst {worst:.3e} against the limit {LIMIT:.3e}")
+        worst, share = max(worst, err), max(share, float(np.max(e / bound)))
+        assert np.all(e <= bound), (strength, floor, b, float(np.max(e / bound)))
+    print(f"strength {strength} floor {floor}: worst {worst:.3e}; worst err / min(LIMIT {LIMIT:.3e}, rule (c) {mg.max_limit:.3e} x its scale) = {share:.3f}")
     assert worst <= LIMIT, (strength, floor, worst)
 
 
@@ -132,9 +152,11 @@ def test_parity_at_other_transform_sizes(n_fft, hop, wl):
     assert all(c.all() for c in covered) == (wl == n_fft)
     for b, c in enumerate(covered):                           # where no window reaches: the input's bits
         assert same_bits(out[b, :n[b]][~c], rows[b][~c]), b
+    mg = rule_c(2.0, 0.1, n_fft, hop, wl, lengths)
+    print(mg.line(f"denoise n_fft {n_fft} hop {hop} win {wl}"))
     for b, r in enumerate(ref):
         err = np.abs(out[b, :n[b]].astype(np.float64) - r)
-        bound = LIMIT * np.maximum(1.0, D.amplification(int(n[b]), n_fft, hop, wl) / (4.0 / 3.0))
+        bound = min(LIMIT, mg.max_limit) * np.maximum(1.0, D.amplification(int(n[b]), n_fft, hop, wl) / (4.0 / 3.0))
         print(f"n_fft {n_fft} hop {hop} win {wl} row {b} (n = {n[b]}): max |out - ref| = {err.max():.3e}, worst err / bound = {float(np.max(err / bound)):.3f}")
         assert np.all(err <= bound), (b, float(np.max(err / bound)))
 

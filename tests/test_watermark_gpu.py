@@ -3,9 +3,12 @@ NumPy, never the library), the exact corners of include/zvx.h, row independence,
 watermark keyword of ZeroVoxTTS.tts / tts_stream.
 Small parameters (TB = 2, P = 2, KB = 2) stand next to the defaults so that every boundary -- the edge of the 4-frame workgroup, block and
 period wrap -- occurs on rows of a few frames.
-The bounds.  Embed: an f32 FFT pair of 1024 points, one multiply per marked bin and an overlap-add of 4 frames, as the denoiser: the
-limit is 4x the largest error MEASURED over the parity cases (2.5e-7, the denoiser's figure; see MEASURED_EMBED).  Detect: the scores are sums of some 10^4 f32 band log-energies normalised to unit variance; the limit is 4x the
-largest |score - ref| MEASURED over the cases below."""
+The bounds.  The parity tests take rule (c) of tests/spectral_ref.py on their own data -- twice the largest element error of two f32
+restatements of the pipeline (embed) or of the detector's two launches (the z of every offset) over 8 data seeds, nothing of it measured
+on a device -- and never more than the earlier constants, which stay as caps.  Those were: embed, an f32 FFT pair of 1024 points, one
+multiply per marked bin and an overlap-add of 4 frames, as the denoiser: 4x the largest error MEASURED over the parity cases (2.5e-7,
+the denoiser's figure; see MEASURED_EMBED); detect, sums of some 10^4 f32 band log-energies normalised to unit variance: 4x the largest
+|score - ref| MEASURED over the cases below.  The other tests keep the constants."""
 import ctypes as C
 
 import numpy as np
@@ -14,6 +17,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 import denoise_ref as D
+import spectral_ref as S
 import watermark_ref as W
 from stream_util import err, same_bits, supported, vp, window_of
 from zerovox_amd import _lib, config as zcfg, pack, watermark as WM, weights as zw
@@ -64,13 +68,21 @@ def signal(rng, n):
     return np.clip(x, -1.0, 1.0).astype(np.float32)
 
 
-def rows_of(lengths):
-    if lengths not in _sig:
-        rng = np.random.default_rng(4242 + sum(lengths))
-        _sig[lengths] = [signal(rng, k) for k in lengths]
-        for r in _sig[lengths]:
+def rows_of(lengths, seed=0):
+    """seed 0 is what the device runs; the other seeds feed rule (c)"""
+    if (lengths, seed) not in _sig:
+        rng = np.random.default_rng(4242 + sum(lengths) + 7919 * seed)
+        _sig[(lengths, seed)] = [signal(rng, k) for k in lengths]
+        for r in _sig[(lengths, seed)]:
             r.setflags(write=False)
-    return _sig[lengths]
+    return _sig[(lengths, seed)]
+
+
+def rule_c_embed(lengths, name):
+    """spectral_ref's rule (c) on this case's own rows: the largest-element limit of the errors divided by spectral_ref.ola_scale"""
+    if ("c", lengths, name) not in _ref:
+        _ref[("c", lengths, name)] = S.embed_margin_of(lambda s: rows_of(lengths, s), SMALL if name == "small" else DEFAULT, N_FFT, HOP, N_FFT, RATE, KEY)
+    return _ref[("c", lengths, name)]
 
 
 def padded(rows):
@@ -121,14 +133,19 @@ def test_embed_against_the_float64_reference(lengths, name):
     x, n = padded(rows)
     assert [D.geometry(k, N_FFT, HOP)[1] for k in lengths] in ([3, 4, 5], [8, 9, 1])
     out = run(ctx, x, n, p)
-    worst = 0.0
+    mg = rule_c_embed(lengths, name)
+    print(mg.line(f"embed {name} {lengths}"))
+    worst, share = 0.0, 0.0
     for b, r in enumerate(reference(lengths, name)):
-        e = float(np.max(np.abs(out[b, :n[b]].astype(np.float64) - r)))
+        ev = np.abs(out[b, :n[b]].astype(np.float64) - r)
+        bound = np.minimum(LIMIT_EMBED, mg.max_limit * S.ola_scale(int(n[b]), N_FFT, HOP, N_FFT))
+        e = float(ev.max())
         moved = float(np.max(np.abs(r - rows[b].astype(np.float64))))
         print(f"{name} row {b} (n = {n[b]}): max |out - ref| = {e:.3e}, the mark moves the row by up to {moved:.4f}")
         assert moved > 1e-3, (b, moved)                      # the mark acts: 1 dB on broadband rows
-        worst = max(worst, e)
-    print(f"{name} {lengths}: worst {worst:.3e} against the limit {LIMIT_EMBED:.3e}")
+        worst, share = max(worst, e), max(share, float(np.max(ev / bound)))
+        assert np.all(ev <= bound), (name, lengths, b, float(np.max(ev / bound)))
+    print(f"{name} {lengths}: worst {worst:.3e}; worst err / min(LIMIT_EMBED {LIMIT_EMBED:.3e}, rule (c) {mg.max_limit:.3e} x its scale) = {share:.3f}")
     assert worst <= LIMIT_EMBED, (name, lengths, worst)
 
 
@@ -291,7 +308,15 @@ def test_detector_scores_against_the_reference():
     y = ctx.watermark([voiced(1.5, 11)], KEY)[0]
     cases.append(("default", DEFAULT, [y, y[5000:], voiced(1.5, 11)], 0))
     cases.append(("default windows", DEFAULT, [y, y[5000:]], 64))
+    # the case's own bound: rule (c) of spectral_ref on rows marked by the float64 reference (the short rows of the batch; one voiced
+    # row of 1.5 s per seed), under today's constant as a cap
+    geo = (N_FFT, HOP, N_FFT)
+    mark = lambda r, p: W.embed(r, KEY, n_fft=N_FFT, hop=HOP, win_length=N_FFT, rate=RATE, **p).astype(np.float32)      # noqa: E731
+    mg_small = S.detect_margin_of(lambda s: [mark(r, SMALL) for r in rows_of(BATCHES[1], s)], SMALL, *geo, (0, 4), RATE, KEY)
+    mg_default = S.detect_margin_of(lambda s: [mark(W.voiced_signal(1.5, 11 + 100 * s), DEFAULT)], DEFAULT, *geo, (0, 64), RATE, KEY)
+    print(mg_small.line("detect small") + "\n" + mg_default.line("detect default"))
     for name, p, rows, wf in cases:
+        limit = min(LIMIT_DETECT, (mg_small if p is SMALL else mg_default).max_limit)
         kw = {k: v for k, v in p.items() if k != "depth_db"}
         got = ctx.watermark_detect(rows, KEY, window_frames=wf, **kw)
         for b, r in enumerate(rows):
@@ -305,16 +330,16 @@ def test_detector_scores_against_the_reference():
                 away = np.array([min((q - o) % T, (o - q) % T) > 1 for q in range(T)])
                 lead = float(z[o] - z[away].max()) if away.any() else np.inf
                 print(f"{name} row {b} window {w}: score {got[b].windows[w][0]:.5f} ref {z[o]:.5f} |diff| {e:.2e}; offset {got[b].windows[w][1]} ref {o} (lead {lead:.3f})")
-                assert e <= LIMIT_DETECT, (name, b, w, e)
-                if lead > LIMIT_DETECT:
+                assert e <= limit, (name, b, w, e)
+                if lead > limit:
                     assert min((got[b].windows[w][1] - o) % T, (o - got[b].windows[w][1]) % T) <= 1, (name, b, w)
-                    if np.sum(z >= z[o] - LIMIT_DETECT) == 1:
+                    if np.sum(z >= z[o] - limit) == 1:
                         assert got[b].windows[w][1] == o, (name, b, w)
-            assert abs(got[b].score - score) <= LIMIT_DETECT
+            assert abs(got[b].score - score) <= limit
             runner = sorted(float(z.max()) for z in zs)
-            if len(runner) < 2 or runner[-1] - runner[-2] > LIMIT_DETECT:
+            if len(runner) < 2 or runner[-1] - runner[-2] > limit:
                 assert got[b].window == win, (name, b)
-    print(f"detector: worst |score - ref| {worst:.3e} against the limit {LIMIT_DETECT:.3e}")
+    print(f"detector: worst |score - ref| {worst:.3e} against the limits {min(LIMIT_DETECT, mg_small.max_limit):.3e} (small) and {min(LIMIT_DETECT, mg_default.max_limit):.3e} (default)")
     empty = ctx.watermark_detect(np.zeros((2, 4000), np.float32), KEY, lengths=[0, 4000])
     assert empty[0].score == 0.0 and empty[0].offset == 0 and empty[0].windows == [] and empty[1].score == 0.0     # no samples; silence: 0 / 0
 
