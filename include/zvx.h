@@ -1016,13 +1016,35 @@ void       zvx_comm_destroy(zvx_ctx* ctx);
  *   lengths; a NULL params; depth_db not finite or outside [0, 6]; lo_hz / hi_hz not finite, lo_hz < 0 or lo_hz >= hi_hz; block_frames or
  *   band_bins < 1; period_blocks outside [1, 256]; reserved != 0; J < 3; for the detector a NULL score / offset / window, a negative
  *   window_frames or 1, one of win_score / win_offset without the other, NWmax < 0.  ZVX_E_UNSUPPORTED: zvx_denoise's, and J > 512.
- * Stage tags "post.watermark" and "post.wmdetect" in zvx_tag_stats (one timed group per call).
+ * Stage tags "post.watermark", "post.wmdetect" and "post.wmidentify" in zvx_tag_stats (one timed group per call).
  * Measured (MI355X, n_fft 1024 / hop 256, rows with |x| <= 1, against tests/watermark_ref.py): embed, largest |out - ref| 2.52e-7 (the denoiser's transform pair: 2.48e-7 there);
  *   detect, largest |score - ref| 7.7e-6 on scores of 2 .. 13.5.  The tests hold 4x these.
  *   What is measured is the arithmetic, and detection on synthetic voiced signals (tests/test_watermark.py: at depth 1 dB and the defaults of
  *   zerovox_amd/watermark.py, 1.5 s and 3 s at 22.05 kHz).  Short clips cut to the telephone band are NOT reliably detectable (a float64
  *   prototype gave a score of 3.1 at 1.5 s after an 8 kHz round trip against a wrong-key null of about 2.5).
- * Not here: a _rows form and stream sessions (zvx_stream_params has no watermark stage); robustness against lossy codecs, time-stretching
+ * zvx_watermark_rows: zvx_watermark_ex with a window AND a key per row -- win[b] (HOST [B]) is row b's window, keys[b] (HOST [B]) its
+ *   key; keys == NULL: params->key for every row.  Row b's emitted samples are bit for bit those of zvx_watermark_ex on that row alone with
+ *   win[b] and params with key = keys[b], whatever shares the call; nothing outside [0, cnt_b) of an output row is touched.  The rows-call
+ *   contract is zvx_denoise_rows' own: its flags, the queued form (ZVX_NO_SYNC; keys and win may be reused at once), in place with
+ *   out_begin == in_origin per row, ZVX_PCM16 not in place.  Validation: zvx_watermark_ex's, and zvx_denoise_rows' on win.  depth_db == 0
+ *   is a copy and no key is read.  The sign tables of the call's DISTINCT keys are built on the device by one small launch (the rule
+ *   above in 64-bit integer arithmetic; the keys go up through the pinned staging arena) into a stack [n][P][J]; rows of equal keys share
+ *   a table.  Stage tag "post.watermark".
+ * zvx_watermark_identify: which of K candidate keys marked each row -- ONE analysis (the detector's first launch), one launch that builds
+ *   the K sign tables on the device (packed, 32 signs to a word), and one search launch over all keys: a workgroup serves 8 keys of one (window, row), builds the folded
+ *   table and the denominator of a phase once and runs the shift pass per key, every sum in the single-key kernel's order.
+ *   score[b][k], offset[b][k], window[b][k] (HOST [B][K]) are bit for bit what zvx_watermark_detect writes to score[b], offset[b],
+ *   window[b] with params->key = keys[k] and the same window_frames; best[b] (HOST [B]) is the smallest k that attains the row's largest
+ *   score (0 for a row of n == 0, whose scores are all 0).  The best over a row's windows is taken on the host from [B][NW][K] device
+ *   results.  params->key is not read (depth_db is checked as the detector checks it, not used); duplicate keys are allowed; per-window
+ *   results are not returned (zvx_watermark_detect has them).  Flags: ZVX_DEVICE_IN only; the call waits once, for its results.
+ *   ZVX_E_INVALID, before anything is queued: every check of zvx_watermark_detect; a NULL keys / score / offset / window / best; K < 1.
+ *   ZVX_E_UNSUPPORTED: K P J > 2^26 signs (the message names the product; the tables are a work buffer of one BIT per sign, rows padded
+ *   to 32-bit words, and the results one of 8 B NW K bytes), or K > 65536.  Stage tag "post.wmidentify".
+ *   The LARGEST score over wrong keys grows with the number of keys tried.  The default threshold of zerovox_amd/watermark.py (5.5) was
+ *   measured over 256 wrong keys; nothing is measured beyond that, and a caller who tries thousands of keys has to judge by the margin
+ *   between the best and the second-best score as well.
+ * Not here: stream sessions (zvx_stream_params has no watermark stage); robustness against lossy codecs, time-stretching
  *   or deliberate removal; whether the mark is inaudible on a real checkpoint -- none of these is measured, and nothing here claims them. */
 typedef struct zvx_watermark_params {
     uint64_t key;            /* the secret */
@@ -1041,6 +1063,14 @@ zvx_status zvx_watermark_ex(zvx_ctx* ctx, const float* in, const int32_t* nsampl
 zvx_status zvx_watermark_detect(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_watermark_params* params,
                                 int window_frames, float* score, int32_t* offset, int32_t* window, float* win_score, int32_t* win_offset,
                                 int NWmax, int flags);
+
+/* keys: host [B] or NULL (params->key for every row); win: host [B] */
+zvx_status zvx_watermark_rows(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_watermark_params* params,
+                              const uint64_t* keys, void* out, int64_t out_stride, int flags, const zvx_row_window* win);
+/* keys: host [K]; score, offset, window: host [B][K]; best: host [B].  flags: ZVX_DEVICE_IN only */
+zvx_status zvx_watermark_identify(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_watermark_params* params,
+                                  const uint64_t* keys, int K, int window_frames, float* score, int32_t* offset, int32_t* window, int32_t* best,
+                                  int flags);
 
 /* Device buffers for ZVX_DEVICE_OUT outputs / zvx_comm_gather without any other GPU runtime in the process. */
 zvx_status zvx_dev_alloc(zvx_ctx* ctx, size_t bytes, void** out);
@@ -1063,7 +1093,7 @@ typedef struct {
 } zvx_kernel_stat;
 int        zvx_kernel_stats(zvx_ctx* ctx, zvx_kernel_stat* out, int max_out);
 /* The same counters grouped by pipeline stage ("encoder", "variance", "lenreg", "decoder", "decoder.norm", "voc.pre",
- * "voc.up1".."voc.res4", "voc.post", "voc.resample", "voc.stream", "post.join", "post.loudness", "post.limit", "post.denoise", "post.watermark", "post.wmdetect", "spkemb"; name = stage): every launch of the stage, including the HBM-bound helper
+ * "voc.up1".."voc.res4", "voc.post", "voc.resample", "voc.stream", "post.join", "post.loudness", "post.limit", "post.denoise", "post.watermark", "post.wmdetect", "post.wmidentify", "spkemb"; name = stage): every launch of the stage, including the HBM-bound helper
  * kernels, while "profile" == 2 and "profile_only" == -1.  Feeds the per-stage roofline fractions of bench.py. */
 int        zvx_tag_stats(zvx_ctx* ctx, zvx_kernel_stat* out, int max_out);
 zvx_status zvx_reset_stats(zvx_ctx* ctx);

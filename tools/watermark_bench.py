@@ -8,9 +8,16 @@ commit's, all in ONE visit of one GPU (16-bit mode, synthetic weights):
     (d) with --parent DIR, a built checkout of the parent commit: (b) plain and (c) run there in child processes, in the order parent, this,
         parent, this -- the spread between the two passes of one tree is what a difference between the trees is read against.
 
-Each figure of (a) and (b) is the median of --reps timed runs after --warmup untimed ones (wall clock around calls that wait for their result).
+    (e) with --identify K [K ...]: ONE zvx_watermark_identify call over K candidate keys against K zvx_watermark_detect calls, in this process,
+        on the two shapes of (a); the event-timed launches of the identify call (stage tag "post.wmidentify") stand in brackets;
+    (f) with --identify: ONE zvx_watermark_rows call over 64 rows with 64 keys against 64 zvx_watermark_ex calls of one row -- the shape of
+        tools/rows_bench.py: each row at a position of its own, one 16-frame piece behind the history the stage keeps, device rows, every
+        call queued (ZVX_NO_SYNC) and one wait at the end.
 
-    python tools/watermark_bench.py [--reps 5] [--warmup 2] [--parent DIR] [--out profiles/watermark_bench.txt]
+Each figure of (a), (b), (e) and (f) is the median of --reps timed runs after --warmup untimed ones (wall clock around calls that wait for
+their result).
+
+    python tools/watermark_bench.py [--reps 5] [--warmup 2] [--parent DIR] [--identify 16 256 1024] [--out profiles/watermark_identify.txt]
 """
 import argparse
 import json
@@ -66,6 +73,79 @@ def calls(synth, rows, n, reps, warmup):
         ctx.dev_free(buf)
 
 
+def identify_lines(synth, counts, reps, warmup):
+    """(e): one identify call over K keys against K detect calls, on 32 rows x 1024 frames and on one row of 10 s"""
+    ctx = synth.model.ctx
+    hop, rate = ctx.hop, ctx.get_int("sampling_rate")
+    rng = np.random.default_rng(2)
+    out = []
+    for rows, n, what in ((1, 10 * rate, "one row of 10 s"), (ROWS, FRAMES * hop, f"{ROWS} rows x {FRAMES} frames")):
+        x = (0.3 * rng.standard_normal((rows, n))).astype(np.float32)
+        lengths = np.full(rows, n, np.int32)
+        buf = ctx.dev_alloc(x.nbytes)
+        try:
+            ctx.dev_from_host(buf, x)
+            for K in counts:
+                keys = [int(k) for k in rng.integers(0, 1 << 63, K)]
+                one = lambda: ctx.watermark_identify(None, keys, lengths=lengths, device_ptr=buf, Nmax=n)      # noqa: E731
+                def many():
+                    for k in keys:
+                        ctx.watermark_detect(None, k, lengths=lengths, device_ptr=buf, Nmax=n)
+                a, b = one(), [ctx.watermark_detect(None, k, lengths=lengths, device_ptr=buf, Nmax=n) for k in keys[:4]]
+                same = all(a[r].scores[k] == b[k][r].score for r in range(rows) for k in range(min(K, 4)))
+                t_one, t_many = timed(ctx, one, reps, warmup), timed(ctx, many, max(1, reps // 2) if K >= 256 else reps, 1 if K >= 256 else warmup)
+                out.append(f"(e) {what}, K = {K}: one zvx_watermark_identify {t_one:.3f} ms [{tagged(ctx, one, 'post.wmidentify'):.3f}]; {K} zvx_watermark_detect "
+                           f"calls {t_many:.3f} ms; calls / identify = {t_many / t_one:.1f}x; {1e3 * t_one / K:.1f} us per key; first scores equal: {same}")
+        finally:
+            ctx.sync()
+            ctx.dev_free(buf)
+    return out
+
+
+def rows_line(synth, reps, warmup, B=64):
+    """(f): one zvx_watermark_rows call of B rows and B keys against B zvx_watermark_ex calls (the shape of tools/rows_bench.py)"""
+    import ctypes as C
+    from zerovox_amd import _lib
+    ctx = synth.model.ctx
+    lib, vp = ctx._lib, C.c_void_p
+    R, NEW = ctx.get_int("fft_size") - 1, 16 * ctx.hop
+    n = 2 * R + NEW
+    x = (np.random.default_rng(1).standard_normal((B, n)) * 0.4).astype(np.float32)
+    xd, od = ctx.dev_alloc(x.nbytes), ctx.dev_alloc(x.nbytes)
+    flags = _lib.ZVX_DEVICE_IN | _lib.ZVX_DEVICE_OUT | _lib.ZVX_NO_SYNC
+    try:
+        ctx.dev_from_host(xd, x)
+        lens = np.full(B, n, np.int32)
+        keys = np.array([KEY + 977 * b for b in range(B)], np.uint64)
+        win = (_lib.RowWindow * B)(*[_lib.RowWindow(1000 * b + 7, 1000 * b + 7 + R, NEW, 0, 0) for b in range(B)])
+        prms = [_lib.Context._watermark_args(int(k))[0] for k in keys]
+
+        def a():
+            for b in range(B):
+                rc = lib.zvx_watermark_ex(ctx._h, vp(xd + 4 * n * b), lens[b:b + 1].ctypes.data_as(vp), 1, n, C.byref(prms[b]), vp(od + 4 * n * b), n, flags,
+                                          win[b].in_origin, win[b].out_begin, win[b].out_count, 0)
+                assert rc == 0, lib.zvx_last_error(ctx._h)
+            ctx.sync()
+
+        def b_():
+            rc = lib.zvx_watermark_rows(ctx._h, vp(xd), lens.ctypes.data_as(vp), B, n, C.byref(prms[0]), keys.ctypes.data_as(vp), vp(od), n, flags, win)
+            assert rc == 0, lib.zvx_last_error(ctx._h)
+            ctx.sync()
+        got = []
+        for f in (a, b_):
+            f()
+            got.append(ctx.dev_to_host(od, (B, n), np.uint32)[:, :NEW].copy())
+            ctx.dev_from_host(od, np.zeros((B, n), np.float32))
+        ta, tb = timed(ctx, a, reps, warmup), timed(ctx, b_, reps, warmup)
+        return (f"(f) {B} rows with {B} keys, one 16-frame piece each ({n} samples a row, {NEW} emitted), device rows, queued calls and one wait: {B} "
+                f"zvx_watermark_ex calls {ta:.3f} ms; one zvx_watermark_rows call {tb:.3f} ms; calls / rows call = {ta / tb:.1f}x; same bits: "
+                f"{bool(np.array_equal(got[0], got[1]))}")
+    finally:
+        ctx.sync()
+        ctx.dev_free(xd)
+        ctx.dev_free(od)
+
+
 def run_bench(root):
     """bench.py in `root` as a child process -> ms per step"""
     p = subprocess.run([sys.executable, "bench.py"] + BENCH, capture_output=True, text=True, cwd=root, env=dict(os.environ, PYTHONPATH=root), timeout=900)
@@ -81,6 +161,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--parent", default=None, help="a built checkout of the parent commit: its tts_long and bench.py are the baseline")
     ap.add_argument("--long-child", action="store_true", help=argparse.SUPPRESS)
+    ap.add_argument("--identify", type=int, nargs="+", default=None, metavar="K",
+                    help="also time one zvx_watermark_identify call over K keys against K zvx_watermark_detect calls, and the rows call")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     here = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -112,6 +194,9 @@ def main():
         r = calls(synth, rows, n, args.reps, args.warmup)
         lines.append(f"(a) {what}: " + "; ".join(f"{k} {w:.3f} ms [{e:.3f}]" for k, (w, e) in r.items())
                      + f"; embed / denoise {r['zvx_watermark'][0] / r['zvx_denoise'][0]:.2f}x")
+    if args.identify:
+        lines += identify_lines(synth, args.identify, args.reps, args.warmup)
+        lines.append(rows_line(synth, args.reps, args.warmup))
     res = time_long(synth, spk, args.reps, args.warmup, {"plain": {}, "watermark": {"watermark": KEY}})
     lines.append(f"(b) tts_long, {ROWS} sentences of {FRAMES} frames, in this process: plain {res['plain']:.2f} ms; with watermark=KEY {res['watermark']:.2f} ms "
                  f"({res['watermark'] - res['plain']:+.2f} ms)")

@@ -28,7 +28,7 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_loudness", "zvx_normalize", "zvx_true_peak", "zvx_limit", "zvx_spkemb_wav", "zvx_limit_ex", "zvx_denoise_bias", "zvx_denoise",
            "zvx_denoise_ex", "zvx_stream_open", "zvx_stream_next", "zvx_stream_info", "zvx_stream_close", "zvx_stream_next_many",
            "zvx_denoise_rows", "zvx_limit_rows", "zvx_resample_rows", "zvx_level", "zvx_level_ex", "zvx_level_rows", "zvx_loudness_stats",
-           "zvx_pitch", "zvx_watermark", "zvx_watermark_ex", "zvx_watermark_detect")
+           "zvx_pitch", "zvx_watermark", "zvx_watermark_ex", "zvx_watermark_detect", "zvx_watermark_rows", "zvx_watermark_identify")
 ZVX_STREAM_MANY_MAX_SESSIONS, ZVX_STREAM_MANY_MAX_ROWS = 64, 256
 ZVX_COMM_ID_BYTES = 128
 ZVX_LOUD_PER_ROW, ZVX_LOUD_COMMON = 0, 1
@@ -189,6 +189,8 @@ def load():
     lib.zvx_watermark.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(WatermarkParams), vp, C.c_int64, C.c_int]
     lib.zvx_watermark_ex.argtypes = lib.zvx_watermark.argtypes + [C.c_int64, C.c_int64, C.c_int64, C.c_int]
     lib.zvx_watermark_detect.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(WatermarkParams), C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int]
+    lib.zvx_watermark_rows.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(WatermarkParams), vp, vp, C.c_int64, C.c_int, C.POINTER(RowWindow)]
+    lib.zvx_watermark_identify.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.POINTER(WatermarkParams), vp, C.c_int, C.c_int, vp, vp, vp, vp, C.c_int]
     lib.zvx_limit_rows.argtypes = lib.zvx_limit.argtypes + [C.POINTER(RowWindow)]
     lib.zvx_resample_rows.argtypes = lib.zvx_resample.argtypes + [C.POINTER(RowWindow)]
     lib.zvx_level.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(LevelParams), vp, C.c_int64, vp, vp, C.c_int]
@@ -848,6 +850,60 @@ class Context:
             res.append(wm.WatermarkResult(float(score[b]), int(off[b]), int(win[b]), bool(score[b] >= thr), thr,
                                           [(float(ws[b, w]), int(wo[b, w])) for w in range(k)]))
         return res
+
+    @staticmethod
+    def _keys_arg(keys):
+        """ints in [0, 2^64) -> a contiguous uint64 array"""
+        ks = [int(k) for k in keys]
+        if any(k < 0 or k > 0xFFFFFFFFFFFFFFFF for k in ks):
+            raise ValueError("watermark: every key must lie in [0, 2^64)")
+        return np.array(ks, np.uint64)
+
+    def watermark_rows(self, rows, keys, windows=None, pcm16=False, lengths=None, **params):
+        """zvx_watermark_rows on host rows: watermark_window with a window AND a key per row, in one call -- keys[b] is row b's key (None:
+        params['key'] for every row), windows[b] = (in_origin, out_begin, out_count, last) says which samples of its signal row b holds
+        and which outputs of the whole-signal call it emits (None: every row whole) -> a list of B arrays, row b's emitted samples
+        (float32 / int16), bit for bit those of watermark_window on that row alone with its key."""
+        x, n = self._rows(rows, lengths)
+        B, Nmax = x.shape
+        if windows is None:
+            windows = [(0, 0, -1, True)] * B
+        if keys is None:
+            kp, key0, ka = None, params.pop("key"), None
+        else:
+            ka = self._keys_arg(keys)
+            if len(ka) != B:
+                raise ValueError(f"{len(ka)} keys for {B} rows")
+            params.pop("key", None)
+            kp, key0 = _ptr(ka), 0
+        prm, flags = self._watermark_args(key0, pcm16=pcm16, **params)
+        win, out, cnt = self._row_windows(windows, n, Nmax, pcm16)
+        self._chk(self._lib.zvx_watermark_rows(self._h, _ptr(x), _ptr(n), B, Nmax, C.byref(prm), kp, _ptr(out), out.shape[1], flags, win))
+        return [out[b, :cnt[b]] for b in range(B)]
+
+    def watermark_identify(self, rows, keys, *, window_frames=256, threshold=None, lengths=None, device_ptr=None, Nmax=None, **params):
+        """zvx_watermark_identify: which of the candidate `keys` marked each row -- one analysis and one search launch for all K keys, each
+        key's score bit for bit watermark_detect's (params: lo_hz, hi_hz, block_frames, band_bins, period_blocks as embedded; hi_hz may be
+        lower) -> a list of B watermark.IdentifyResult.  rows as watermark_detect's.  The largest score of WRONG keys grows with their
+        number: watermark.THRESHOLD was measured over 256 of them, so with many more candidates judge by `margin` as well."""
+        from . import watermark as wm
+        if device_ptr is None:
+            x, n = self._rows(rows, lengths)
+            B, Nmax = x.shape
+            xp, flags = _ptr(x), 0
+        else:
+            n = _i32(lengths)
+            B, xp, flags = len(n), C.c_void_p(int(device_ptr)), ZVX_DEVICE_IN
+        ka = self._keys_arg(keys)
+        K = len(ka)
+        params.pop("depth_db", None)
+        params.pop("key", None)
+        prm, _ = self._watermark_args(0, **params)
+        score, off, win = np.zeros((B, max(K, 1)), np.float32), np.zeros((B, max(K, 1)), np.int32), np.zeros((B, max(K, 1)), np.int32)
+        best = np.zeros(B, np.int32)
+        self._chk(self._lib.zvx_watermark_identify(self._h, xp, _ptr(n), B, int(Nmax), C.byref(prm), _ptr(ka), K, int(window_frames), _ptr(score),
+                                                   _ptr(off), _ptr(win), _ptr(best), flags))
+        return [wm.identify_result(ka, score[b], off[b], win[b], int(best[b]), threshold) for b in range(B)]
 
     def stream_open(self, mel=None, frames=0, *, chunk_frames, chunks_per_call=1, halo=16, denoise=None, bias=None, limit=None, flags=0):
         """zvx_stream_open -> Stream.  mel: [frames, n_mels] float32 on the host; an int, a device pointer to ``frames`` rows

@@ -8,15 +8,23 @@ namespace zvx {
 // Keyed audio watermark (include/zvx.h, zvx_watermark, zvx_watermark_detect; watermark.hip): a multiplicative spread-spectrum mark on the
 // denoiser's frame grid.  The embedder is the denoiser's frames kernel with a keyed gain in place of the bias gain -- the row table, the
 // window, the slot rule and the overlap-add launch (launch_denoise_ola on `dn`) are the denoiser's own; `dn.copy` is depth_db == 0.
-// `sign` is the P x J pattern of +1 / -1 bytes, built on the host; band j is bins [k_lo + j KB, k_lo + (j + 1) KB); frame f of the SIGNAL
-// is in block (f / TB) mod P, f formed in 64 bits from the row's f_first.
+// `sign` is the P x J pattern of +1 / -1 bytes, built on the host -- or a stack [n_tables][P][J] of them built by launch_wm_signs, row b
+// reading table sign_of_row[b] (zvx_watermark_rows: a key per row, rows of equal keys share a table); band j is bins
+// [k_lo + j KB, k_lo + (j + 1) KB); frame f of the SIGNAL is in block (f / TB) mod P, f formed in 64 bits from the row's f_first.
 struct WatermarkArgs {
     DenoiseArgs dn;                          // rows, geometry, tables; bias / strength / floor / mag are not read
-    const signed char* sign;                 // [P][J]
+    const signed char* sign;                 // [n_tables][P][J]
+    const int* sign_of_row;                  // [B] on the device: the table of each row; nullptr: table 0 for every row
     int k_lo, KB, J, TB, P;
     float g_up, g_dn;
 };
 void launch_watermark_frames(const WatermarkArgs& a, hipStream_t s);
+// Sign tables on the device: sign(t, c, j) = +1 where bit 63 of mix64(keys[t] ^ ((uint64)c << 32 | j)) is set, else -1 (mix64: the
+// splitmix64 finaliser of include/zvx.h, in 64-bit integer arithmetic), for t < n, c < P, j < J.  out: [n][P][J] bytes of +1 / -1 (the
+// embedder's form), or with `packed` [n][P][wm_sign_words(J)] 32-bit words, bit j % 32 of word j / 32 set for +1 (the form
+// launch_wm_search_keys reads).  keys and out on the device.
+inline int wm_sign_words(int J) { return (J + 31) / 32; }
+void launch_wm_signs(const unsigned long long* keys, void* out, int n, int P, int J, bool packed, hipStream_t s);
 // The detector, whole rows only.  launch_wm_bands: frame load, forward FFT, Pw = re^2 + im^2, LB[f][j] = sum over the band's bins of
 // log2(max(Pw, 1e-6)), D[f][j] = LB[f][j] - (LB[f][j - 1] + LB[f][j + 1]) / 2 -> the row's d[F][J - 2] (column j - 1); no spectrum goes to
 // memory.  grid = (ceil(Fmax / frames per workgroup), B).
@@ -47,5 +55,13 @@ __host__ __device__ inline int wm_windows(int F, int WF) {
 }
 void launch_wm_bands(const WmDetectArgs& a, hipStream_t s);
 void launch_wm_search(const WmDetectArgs& a, hipStream_t s);
+// The search over K keys at once (zvx_watermark_identify): sign_bits is the packed stack [K][P][wm_sign_words(J)] (d.sign is not read),
+// d.win_score / d.win_offset are [B][NW][K]; the
+// entry (b, w, k) receives bit for bit what launch_wm_search writes to (b, w) with table k.  One workgroup per (window, row, run of
+// WM_KEYS keys): the folded table and the denominator of a phase are built once for the run, then each key has its own shift pass.
+// grid = (NW, B, ceil(K / WM_KEYS)).
+constexpr int WM_KEYS = 8;
+struct WmKeysArgs { WmDetectArgs d; const unsigned* sign_bits; int K; };
+void launch_wm_search_keys(const WmKeysArgs& a, hipStream_t s);
 
 }  // namespace zvx

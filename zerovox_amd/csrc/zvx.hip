@@ -3236,27 +3236,50 @@ const signed char* wm_sign_table(zvx_ctx* c, const zvx_watermark_params* p, int 
 
 // The embedder over B rows with a window each: the denoiser's row table, its overlap-add launch, the keyed gain in the frames launch.
 // The caller has validated the rows.
-void run_watermark_rows(zvx_ctx* c, const WmPlan& wp, const PostRow* rows, int B, const zvx_watermark_params* p, int pcm16) {
+// `keys` (zvx_watermark_rows): a key per row -- the distinct keys' tables are built on the device (launch_wm_signs) into one stack, rows of
+// equal keys share a table; nullptr: p->key for every row, its table built on the host.
+void run_watermark_rows(zvx_ctx* c, const WmPlan& wp, const PostRow* rows, int B, const zvx_watermark_params* p, int pcm16,
+                        const uint64_t* keys = nullptr) {
     const DnGeom& g = wp.g;
     const bool copy = p->depth_db == 0.f;
     DnRowsPlan pl = dn_rows_plan(g, rows, B, copy);
     WatermarkArgs a{};
     dn_rows_upload(c, g, pl, B, copy, pcm16, a.dn);
+    const unsigned long long* keys_d = nullptr;
+    signed char* signs_d = nullptr;
+    int n_tables = 0;
     if (!copy) {
-        a.sign = wm_sign_table(c, p, wp.J);
+        if (keys) {
+            std::vector<unsigned long long> uniq;
+            std::vector<int> of_row((size_t)B);
+            std::map<uint64_t, int> seen;
+            for (int b = 0; b < B; b++) {
+                const auto it = seen.emplace(keys[b], (int)uniq.size());
+                if (it.second) uniq.push_back(keys[b]);
+                of_row[(size_t)b] = it.first->second;
+            }
+            n_tables = (int)uniq.size();
+            unsigned long long* kd = (unsigned long long*)c->buf("wm.keys", uniq.size() * 8);
+            int* od = (int*)c->buf("wm.sign_of_row", (size_t)B * sizeof(int));
+            signs_d = (signed char*)c->buf("wm.signs", uniq.size() * (size_t)p->period_blocks * wp.J);
+            c->upload(kd, uniq.data(), uniq.size() * 8);
+            c->upload(od, of_row.data(), (size_t)B * sizeof(int));
+            keys_d = kd; a.sign = signs_d; a.sign_of_row = od;
+        } else a.sign = wm_sign_table(c, p, wp.J);
         a.k_lo = wp.k_lo; a.KB = p->band_bins; a.J = wp.J; a.TB = p->block_frames; a.P = p->period_blocks;
         a.g_up = (float)pow(10.0, (double)p->depth_db / 20.0); a.g_dn = (float)pow(10.0, -(double)p->depth_db / 20.0);
     }
     TagScope scope(c, "post.watermark");
     c->timed(copy ? 0.0 : dn_fft_flops(g, pl.frames, 2), 4.0 * pl.n_sum + (pcm16 ? 2.0 : 4.0) * pl.cnt_sum, [&] {
+        if (keys_d) launch_wm_signs(keys_d, signs_d, n_tables, a.P, a.J, false, c->stream);
         if (!copy) launch_watermark_frames(a, c->stream);
         launch_denoise_ola(a.dn, pl.cnt_max, c->stream);
     });
 }
 
-// zvx_watermark and zvx_watermark_ex: every check before anything is allocated, uploaded or queued
+// zvx_watermark, zvx_watermark_ex and zvx_watermark_rows (`keys`: a key per row, or nullptr): every check before anything is allocated, uploaded or queued
 void do_watermark(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_watermark_params* p,
-                  void* out, int64_t out_stride, int flags, const WindowsIn& win = {}) {
+                  void* out, int64_t out_stride, int flags, const WindowsIn& win = {}, const uint64_t* keys = nullptr) {
     rows_check(who, in, nsamples, B, Nmax, 65535);
     flags_check(who, flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16);
     out_rows_check(who, in, out, out_stride, Nmax, flags);
@@ -3272,7 +3295,7 @@ void do_watermark(zvx_ctx* c, const char* who, const float* in, const int32_t* n
     long out_bs = 0;
     void* od = ret.out_rows("wm.out", out, out_stride, &out_bs);
     const std::vector<PostRow> rows = post_rows(x, Nmax, od, out_bs, ret.ss, nsamples, rw, B);
-    run_watermark_rows(c, wp, rows.data(), B, p, (flags & ZVX_PCM16) ? 1 : 0);
+    run_watermark_rows(c, wp, rows.data(), B, p, (flags & ZVX_PCM16) ? 1 : 0, keys);
     ret.finish(nullptr, out, out_stride, rw.cnt.data(), flags);
 }
 
@@ -3342,6 +3365,93 @@ void do_watermark_detect(zvx_ctx* c, const float* in, const int32_t* nsamples, i
             if (win_score) { win_score[(size_t)b * NWmax + w] = z; win_offset[(size_t)b * NWmax + w] = ho[(size_t)b * NWp + w]; }
         }
         score[b] = best; offset[b] = bo; window[b] = bw;
+    }
+}
+
+// zvx_watermark_identify: zvx_watermark_detect's analysis once, the search with K keys' tables built on the device; every check before anything
+// is allocated, uploaded or queued; the call's one wait brings the [B][NW][K] window results over, and the best over a row's windows (the
+// first of equals, as the detector's) and over the keys is taken here
+constexpr long WM_IDENTIFY_TABLE_BYTES = 1L << 26;           // K P J signs at most (include/zvx.h); they are stored a bit each
+constexpr int WM_IDENTIFY_MAX_KEYS = 1 << 16;
+void do_watermark_identify(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_watermark_params* p, const uint64_t* keys,
+                           int K, int window_frames, float* score, int32_t* offset, int32_t* window, int32_t* best, int flags) {
+    const char* who = "zvx_watermark_identify";
+    const RowsInfo ri = rows_check(who, in, nsamples, B, Nmax, 65535);
+    flags_check(who, flags, ZVX_DEVICE_IN);
+    const WmPlan wp = watermark_params_check(c, who, p);
+    const DnGeom& g = wp.g;
+    if (!keys) fail(ZVX_E_INVALID, "%s: keys is NULL", who);
+    if (!score || !offset || !window || !best) fail(ZVX_E_INVALID, "%s: score, offset, window or best is NULL", who);
+    if (K < 1) fail(ZVX_E_INVALID, "%s: K %d must be at least 1", who, K);
+    if (window_frames < 0 || window_frames == 1) fail(ZVX_E_INVALID, "%s: window_frames %d (0: the row; otherwise at least 2)", who, window_frames);
+    const int P = p->period_blocks, J = wp.J, JD = J - 2;
+    for (int b = 0; b < B; b++)
+        if (nsamples[b] > 0 && nsamples[b] < dn_min_samples(g))
+            fail(ZVX_E_INVALID, "%s: row %d has %d samples; a row that is not empty needs at least %d (zvx_melspec's conditions)", who, b, nsamples[b], dn_min_samples(g));
+    if ((long)K * P * J > WM_IDENTIFY_TABLE_BYTES)
+        fail(ZVX_E_UNSUPPORTED, "%s: K P J = %d x %d x %d = %lld signs in the tables (at most %ld)", who, K, P, J, (long long)K * P * J, WM_IDENTIFY_TABLE_BYTES);
+    if (K > WM_IDENTIFY_MAX_KEYS) fail(ZVX_E_UNSUPPORTED, "%s: K %d (at most %d keys a call)", who, K, WM_IDENTIFY_MAX_KEYS);
+    int NW = 0;
+    long Fmax = 0;
+    double frames = 0;
+    size_t d_floats = 0;
+    std::vector<WmDetectRow> tab((size_t)B);
+    std::vector<size_t> d_at((size_t)B);
+    for (int b = 0; b < B; b++) {
+        const int F = dn_frames(g, nsamples[b]);
+        tab[(size_t)b] = WmDetectRow{nullptr, nullptr, nsamples[b], F};
+        d_at[(size_t)b] = d_floats; d_floats += (size_t)F * JD;
+        NW = std::max(NW, wm_windows(F, window_frames)); Fmax = std::max<long>(Fmax, F); frames += F;
+    }
+    const int NWp = std::max(NW, 1);
+    const size_t res_each = (size_t)B * NWp * K * 4, res_pad = (res_each + 255) & ~(size_t)255;
+    char* host = (char*)c->join_pinned(2 * res_pad);
+    const float* x = rows_to_device(c, "wm", in, B, Nmax, flags);
+    WmKeysArgs ka{};
+    WmDetectArgs& a = ka.d;
+    const zvx_ctx::DnTables& tb = dn_tables(c, g);
+    a.B = B; a.n_fft = g.n_fft; a.log2n = g.log2n; a.hop = g.hop; a.pad = g.pad; a.Fmax = (int)Fmax;
+    a.twid = tb.twid; a.win = tb.win;
+    a.k_lo = wp.k_lo; a.KB = p->band_bins; a.J = J; a.TB = p->block_frames; a.P = P;
+    a.WF = window_frames; a.NW = NWp;
+    ka.K = K;
+    unsigned long long* keys_d = (unsigned long long*)c->buf("wm.keys", (size_t)K * 8);
+    unsigned* signs_d = (unsigned*)c->buf("wm.signbits", (size_t)K * P * wm_sign_words(J) * sizeof(unsigned));      // packed: 32 signs a word
+    float* d = c->fbuf("wm.d", std::max<size_t>(d_floats, 1));
+    char* res = (char*)c->buf("wm.kres", 2 * res_pad);
+    ka.sign_bits = signs_d;
+    a.win_score = (float*)res; a.win_offset = (int*)(res + res_pad);
+    for (int b = 0; b < B; b++) { tab[(size_t)b].x = x + (size_t)b * Nmax; tab[(size_t)b].d = d + d_at[(size_t)b]; }
+    WmDetectRow* tab_d = (WmDetectRow*)c->buf("wm.rows", (size_t)B * sizeof(WmDetectRow));
+    static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "keys are uploaded as they are");
+    c->upload(keys_d, keys, (size_t)K * 8);
+    c->upload(tab_d, tab.data(), (size_t)B * sizeof(WmDetectRow));
+    a.rows = tab_d;
+    {
+        TagScope scope(c, "post.wmidentify");
+        c->timed(dn_fft_flops(g, frames, 1), 4.0 * ri.n_sum + 8.0 * frames * JD + 4.0 * K * P * wm_sign_words(J), [&] {
+            launch_wm_signs(keys_d, signs_d, K, P, J, true, c->stream);
+            launch_wm_bands(a, c->stream);
+            if (NW > 0) launch_wm_search_keys(ka, c->stream);
+        });
+    }
+    if (NW > 0) HIPCHK(hipMemcpyAsync(host, res, 2 * res_pad, hipMemcpyDeviceToHost, c->stream));
+    c->sync();                                               // the call's one wait
+    const float* hs = (const float*)host;
+    const int32_t* ho = (const int32_t*)(host + res_pad);
+    for (int b = 0; b < B; b++) {
+        const int nw = wm_windows(tab[(size_t)b].F, window_frames);
+        int32_t kb = 0;
+        for (int k = 0; k < K; k++) {
+            float bs = 0.f; int32_t bo = 0, bw = 0;
+            for (int w = 0; w < nw; w++) {
+                const size_t at = ((size_t)b * NWp + w) * K + k;
+                if (w == 0 || hs[at] > bs) { bs = hs[at]; bo = ho[at]; bw = w; }
+            }
+            score[(size_t)b * K + k] = bs; offset[(size_t)b * K + k] = bo; window[(size_t)b * K + k] = bw;
+            if (bs > score[(size_t)b * K + kb]) kb = k;
+        }
+        best[b] = kb;
     }
 }
 
@@ -4254,6 +4364,20 @@ zvx_status zvx_watermark_detect(zvx_ctx* c, const float* in, const int32_t* nsam
     return guarded(c, [&] {
         do_watermark_detect(c, in, nsamples, B, Nmax, params, window_frames, score, offset, window, win_score, win_offset, NWmax, flags);
     });
+}
+
+zvx_status zvx_watermark_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_watermark_params* params,
+                              const uint64_t* keys, void* out, int64_t out_stride, int flags, const zvx_row_window* win) {
+    return guarded(c, [&] {
+        const WindowsIn w{WindowsIn::PER_ROW, RowsWindow{}, win};
+        do_watermark(c, "zvx_watermark_rows", in, nsamples, B, Nmax, params, out, out_stride, flags, w, keys);
+    });
+}
+
+zvx_status zvx_watermark_identify(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_watermark_params* params,
+                                  const uint64_t* keys, int K, int window_frames, float* score, int32_t* offset, int32_t* window, int32_t* best,
+                                  int flags) {
+    return guarded(c, [&] { do_watermark_identify(c, in, nsamples, B, Nmax, params, keys, K, window_frames, score, offset, window, best, flags); });
 }
 
 zvx_status zvx_denoise_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias,

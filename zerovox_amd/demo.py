@@ -20,6 +20,9 @@ and semitones, mean and voiced fraction are printed: what --pitch-shift / --pitc
 `--detect-watermark KEY FILE`: no synthesis -- the 16-bit mono WAV file is searched for KEY's mark on the device (zvx_watermark_detect) and
 the score, offset and decision are printed.  Detection is measured on synthetic signals only; short telephone-band clips are not reliably
 detectable, and nothing is claimed about audibility or robustness against codecs.
+`--identify-watermark KEYFILE FILE`: no synthesis -- KEYFILE holds one candidate key per line (decimal or 0x hex; blank lines and lines that
+start with # are skipped), and the WAV file is searched for all of them in one call (zvx_watermark_identify): the best key, its score, the
+margin over the second best and the decision are printed.  The largest wrong-key score grows with the number of keys tried.
 """
 import argparse
 import os
@@ -61,8 +64,10 @@ def main():
     ap.add_argument("--watermark", type=lambda v: int(v, 0), default=None, metavar="KEY", help="mark the waveform with this key on the device (default: off)")
     ap.add_argument("--detect-watermark", nargs=2, default=None, metavar=("KEY", "FILE"),
                     help="no synthesis: search the 16-bit mono WAV FILE for KEY's mark and print the result")
+    ap.add_argument("--identify-watermark", nargs=2, default=None, metavar=("KEYFILE", "FILE"),
+                    help="no synthesis: search the 16-bit mono WAV FILE for the mark of every key in KEYFILE (one per line, decimal or 0x hex)")
     args = ap.parse_args()
-    if args.detect_watermark is None and not args.text:
+    if args.detect_watermark is None and args.identify_watermark is None and not args.text:
         ap.error("the text is missing")
     if args.level is not None and (args.long or args.loudness is not None):
         ap.error("--level streams one utterance: it goes with neither --long nor --loudness")
@@ -80,6 +85,20 @@ def main():
         res = synth.detect_watermark(pcm, int(args.detect_watermark[0], 0), sampling_rate=rate)
         print(f"watermark: {'DETECTED' if res.detected else 'not detected'} (score {res.score:.2f}, threshold {res.threshold:g}, offset "
               f"{res.offset} frames, window {res.window} of {len(res.windows)})")
+        return
+    if args.identify_watermark is not None:
+        import wave
+        with open(args.identify_watermark[0]) as f:
+            keys = [int(line.strip(), 0) for line in f if line.strip() and not line.lstrip().startswith("#")]
+        if not keys:
+            ap.error("--identify-watermark: KEYFILE holds no key")
+        with wave.open(args.identify_watermark[1], "rb") as f:
+            if f.getnchannels() != 1 or f.getsampwidth() != 2:
+                ap.error("--identify-watermark reads 16-bit mono WAV files")
+            rate, pcm = f.getframerate(), np.frombuffer(f.readframes(f.getnframes()), np.int16)
+        res = synth.identify_watermark(pcm, keys, sampling_rate=rate)
+        print(f"watermark: {'DETECTED' if res.detected else 'not detected'}: key {res.best} of {len(keys)} (0x{res.key:016x}), score {res.score:.2f}, "
+              f"margin {res.margin:.2f} over the second best, threshold {res.threshold:g}, offset {res.offset} frames, window {res.window}")
         return
     print("computing speaker embedding...")
     refmel = np.random.default_rng(0).standard_normal((args.refmel_frames, modelcfg["audio"]["num_mels"])).astype(np.float32)

@@ -295,6 +295,38 @@ class ZeroVoxTTS:
         return ctx.watermark_detect([wav], p.pop("key"), window_frames=wm.WINDOW_FRAMES if window_frames is None else int(window_frames),
                                     threshold=threshold, **p)[0]
 
+    def identify_watermark(self, wav, keys, sampling_rate=None, *, window_frames=None, threshold=None, **params):
+        """Which of the candidate `keys` marked this audio?  wav and sampling_rate as detect_watermark's (a waveform at another rate is
+        converted first and hi_hz lowered likewise); keys: a sequence of int keys, e.g. watermark.derive_key(master, request_id) of every
+        request in question -> watermark.IdentifyResult(best, key, score, offset, window, margin, detected, threshold, scores), from the
+        device in one call for all keys (include/zvx.h, zvx_watermark_identify), each key's score the one detect_watermark gives.  The
+        largest score among wrong keys grows with their number: the default threshold was measured over 256 wrong keys and nothing
+        beyond, so with many more candidates judge by ``margin`` (best minus second best) as well.  What detect_watermark does not
+        claim is not claimed here either."""
+        from . import watermark as wm
+        keys = list(keys)
+        if not keys:
+            raise ValueError("identify_watermark: keys is empty")
+        p = None
+        for k in keys:                                      # every key goes through the checks of the one-key call
+            p = wm.params({"key": k, **params})
+        wav = np.asarray(wav)
+        if wav.dtype == np.int16:
+            wav = wav.astype(np.float32) / np.float32(32760.0)
+        wav = np.asarray(wav, np.float32).reshape(-1)
+        ctx = self._model.ctx
+        native = ctx.get_int("sampling_rate")
+        rate = native if sampling_rate is None else int(sampling_rate)
+        if rate != native:
+            out, out_len = ctx.resample([wav], rate, native)
+            wav = out[0, :out_len[0]]
+            p["hi_hz"] = min(p["hi_hz"], 0.45 * min(rate, native))
+            wm.check(p)
+        p.pop("depth_db")
+        p.pop("key")
+        return ctx.watermark_identify([wav], keys, window_frames=wm.WINDOW_FRAMES if window_frames is None else int(window_frames),
+                                      threshold=threshold, **p)[0]
+
     @staticmethod
     def _pitch_keywords(pitch_report):
         """the pitch_report keyword of tts / tts_ex / tts_long -> None (nothing is measured) or the checked ``pitch_report`` keywords"""

@@ -1,5 +1,6 @@
-"""Keyed audio watermark (include/zvx.h: zvx_watermark, zvx_watermark_ex, zvx_watermark_detect): defaults, the sign table, the result of a
-detection, and the streaming side -- which outputs are final, what history to keep.
+"""Keyed audio watermark (include/zvx.h: zvx_watermark, zvx_watermark_ex, zvx_watermark_rows, zvx_watermark_detect, zvx_watermark_identify):
+defaults, the sign table, per-request keys from one secret (derive_key), the results of a detection and of an identification among many
+keys, and the streaming side -- which outputs are final, what history to keep.
 
 Pure Python, importable without the library.  The mark is a multiplicative spread-spectrum pattern on the denoiser's STFT frame grid: bands
 of ``band_bins`` bins between ``lo_hz`` and ``hi_hz`` are scaled up or down by ``depth_db`` in blocks of ``block_frames`` frames, by a
@@ -43,6 +44,50 @@ def sign_table(key, period_blocks, bands):
     """[period_blocks][bands] of +1 / -1: sign(c, j) = +1 where bit 63 of mix64(key ^ (c << 32 | j)) is set"""
     key = int(key) & M64
     return [[1 if mix64(key ^ ((c << 32) | j)) >> 63 else -1 for j in range(int(bands))] for c in range(int(period_blocks))]
+
+
+def derive_key(master, ident):
+    """A per-customer or per-request key from one secret: ``mix64(master ^ mix64(h))``, all in 64-bit arithmetic, where
+
+    * ``master`` is an int in [0, 2^64);
+    * for an int ``ident`` in [0, 2^64), ``h = ident``;
+    * for a bytes-like ``ident``, ``h`` folds it 8 bytes at a time: ``h = len(ident)``; then for each chunk, in order,
+      ``h = mix64(h ^ w)``, ``w`` the chunk as a little-endian integer (the last chunk may be shorter: its missing high bytes are 0).
+
+    To find who asked for a clip later, derive the keys of the candidates again and hand them to ``identify_watermark``.  ValueError for
+    anything else (a bool, a str, a number out of range)."""
+    if not isinstance(master, int) or isinstance(master, bool) or not 0 <= master <= M64:
+        raise ValueError(f"derive_key: master must be an int in [0, 2^64), not {master!r}")
+    if isinstance(ident, (bytes, bytearray, memoryview)):
+        data = bytes(ident)
+        h = len(data) & M64
+        for i in range(0, len(data), 8):
+            h = mix64(h ^ int.from_bytes(data[i:i + 8], "little"))
+    elif isinstance(ident, int) and not isinstance(ident, bool):
+        if not 0 <= ident <= M64:
+            raise ValueError(f"derive_key: an int ident must lie in [0, 2^64), not {ident!r}")
+        h = ident
+    else:
+        raise ValueError(f"derive_key: ident must be an int or bytes, not {ident!r}")
+    return mix64(master ^ mix64(h))
+
+
+IdentifyResult = namedtuple("IdentifyResult", "best key score offset window margin detected threshold scores")
+IdentifyResult.__doc__ = """best: the index of the candidate key with the row's largest score (the smallest such index), key: that key;
+score, offset, window: what the detector gives with it; margin: score minus the second-best candidate's score (score itself with one
+candidate); detected: score >= threshold; scores: every candidate's score [K].  The largest score among WRONG keys grows with the number
+of keys tried: THRESHOLD was measured over 256 wrong keys and nothing beyond, so with many more candidates look at the margin too."""
+
+
+def identify_result(keys, scores, offsets, windows, best=None, threshold=None):
+    """one row's IdentifyResult from the per-key results [K] (best None: the smallest index of the largest score)"""
+    scores = [float(v) for v in scores]
+    if best is None:
+        best = max(range(len(scores)), key=lambda k: (scores[k], -k))
+    thr = THRESHOLD if threshold is None else float(threshold)
+    second = max((v for k, v in enumerate(scores) if k != best), default=0.0)
+    return IdentifyResult(int(best), int(keys[best]), scores[best], int(offsets[best]), int(windows[best]), scores[best] - second,
+                          bool(scores[best] >= thr), thr, scores)
 
 
 def params(watermark, **overrides):
