@@ -118,7 +118,7 @@ def rows_line(synth, reps, warmup, B=64):
         lens = np.full(B, n, np.int32)
         keys = np.array([KEY + 977 * b for b in range(B)], np.uint64)
         win = (_lib.RowWindow * B)(*[_lib.RowWindow(1000 * b + 7, 1000 * b + 7 + R, NEW, 0, 0) for b in range(B)])
-        prms = [_lib.Context._watermark_args(int(k))[0] for k in keys]
+        prms = [_lib.Context._watermark_params(int(k)) for k in keys]
 
         def a():
             for b in range(B):

@@ -206,7 +206,12 @@ def load():
 
 
 def _ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+    """the array's address; the pointer object holds the array, which so lives as long as the arguments of the call it goes into"""
+    if a is None:
+        return None
+    p = a.ctypes.data_as(C.c_void_p)
+    p._array = a
+    return p
 
 
 def _i32(a, shape=None):
@@ -402,6 +407,16 @@ class Context:
         x = _f32(rows)
         return x, _i32(lengths, (x.shape[0],))
 
+    def _rows_arg(self, rows, lengths, device_ptr=None, Nmax=None):
+        """the rows of a call: a list of 1-D waveforms or a padded 2-D array + lengths on the host, or, with device_ptr, device rows
+        [B][Nmax] f32 there and `lengths` -> (pointer, n [B] i32, B, Nmax, flags: 0 or ZVX_DEVICE_IN); the pointer holds the host array
+        (_ptr)"""
+        if device_ptr is None:
+            x, n = self._rows(rows, lengths)
+            return _ptr(x), n, x.shape[0], x.shape[1], 0
+        n = _i32(lengths)
+        return C.c_void_p(int(device_ptr)), n, len(n), int(Nmax), ZVX_DEVICE_IN
+
     @staticmethod
     def _window_out(n, Nmax, in_origin, out_begin, out_count, pcm16):
         """the output rows of a zvx_limit_ex / zvx_denoise_ex call -> (out [B][stride] of zeros, cols: the longest emitted row)"""
@@ -409,16 +424,63 @@ class Context:
         return np.zeros((len(n), max(cols, Nmax)), np.int16 if pcm16 else np.float32), cols
 
     @staticmethod
+    def _row_windows(windows, n, Nmax, pcm16, count=int):
+        """a list of (in_origin, out_begin, out_count, last), one per row -> (RowWindow array, out [B][stride] of zeros, cnt [B]: the
+        emitted samples of each row).  count: the outputs a signal of so many samples has (the resampler's is resampled_len)"""
+        if len(windows) != len(n):
+            raise ValueError(f"{len(windows)} windows for {len(n)} rows")
+        win = (RowWindow * max(len(n), 1))()
+        cnt = np.zeros(len(n), np.int64)
+        for b, (in_origin, out_begin, out_count, last) in enumerate(windows):
+            win[b] = RowWindow(int(in_origin), int(out_begin), int(out_count), 1 if last else 0, 0)
+            cnt[b] = int(out_count) if out_count >= 0 else max(0, count(int(in_origin) + int(n[b])) - int(out_begin))
+        cols = int(cnt.max()) if len(cnt) else 0
+        return win, np.zeros((len(n), max(cols, Nmax)), np.int16 if pcm16 else np.float32), cnt
+
+    @staticmethod
     def _flags(pcm16=False, device=False, no_sync=False):
         return (ZVX_PCM16 if pcm16 else 0) | (ZVX_DEVICE_IN | ZVX_DEVICE_OUT if device else 0) | (ZVX_NO_SYNC if no_sync else 0)
 
-    @classmethod
-    def _limit_args(cls, ceiling, window_ms, oversample, **flags):
-        return LimitParams(float(ceiling), float(window_ms), int(oversample)), cls._flags(**flags)
+    # The effects as (symbol stem, a rate follows Nmax, the dtypes of the [B] result arrays behind out_stride)
+    _LIMIT = ("limit", True, (np.float32, np.float32))
+    _LEVEL = ("level", True, (np.float32, np.float32))
+    _DENOISE = ("denoise", False, ())
+    _WATERMARK = ("watermark", False, ())
+    _NORMALIZE = ("normalize", True, (np.float64, np.float32, np.float32))       # (whole rows and in place only)
 
-    @classmethod
-    def _denoise_args(cls, strength, floor, **flags):
-        return DenoiseParams(float(strength), float(floor)), cls._flags(**flags)
+    def _effect(self, fx, mid, rows, lengths, *, rate=None, pcm16=False, window=None, windows=None, device=None, no_sync=False):
+        """One call of the effect `fx` in one of its four forms: the whole rows (zvx_X); window = (in_origin, out_begin, out_count, last),
+        one for all rows (zvx_X_ex); windows, one per row (zvx_X_rows); device = (ptr, Nmax), in place on device rows (zvx_X with
+        ZVX_DEVICE_IN | ZVX_DEVICE_OUT [| ZVX_NO_SYNC]).  mid: the arguments between Nmax [, rate] and out (bias, params, keys).
+        -> (out, *results): out [B][Nmax], out [B][cols], a list of each row's emitted samples, or None in place; no results with no_sync."""
+        stem, takes_rate, res_dtypes = fx
+        ptr, ptr_Nmax = device if device is not None else (None, None)
+        xp, n, B, Nmax, _ = self._rows_arg(rows, lengths, ptr, ptr_Nmax)
+        sym, tail, flags = "zvx_" + stem, (), self._flags(pcm16=pcm16, device=device is not None, no_sync=no_sync)
+        if device is not None:
+            out = None
+        elif windows is not None:
+            win, out, cnt = self._row_windows(windows, n, Nmax, pcm16)
+            sym, tail = sym + "_rows", (win,)
+        elif window is not None:
+            out, cols = self._window_out(n, Nmax, *window[:3], pcm16)
+            sym, tail = sym + "_ex", (int(window[0]), int(window[1]), int(window[2]), 1 if window[3] else 0)
+        else:
+            out = np.zeros((B, Nmax), np.int16 if pcm16 else np.float32)
+        res = [None if no_sync else np.zeros(B, dt) for dt in res_dtypes]
+        self._chk(getattr(self._lib, sym)(self._h, xp, _ptr(n), B, Nmax, *([self._rate(rate)] if takes_rate else []), *mid,
+                                          xp if out is None else _ptr(out), Nmax if out is None else out.shape[1], *(_ptr(r) for r in res),
+                                          flags, *tail))
+        if windows is not None:
+            out = [out[b, :cnt[b]] for b in range(B)]
+        elif window is not None:
+            out = out[:, :cols]
+        return (out, *(r for r in res if r is not None))
+
+    def _effect_in_place(self, fx, mid, ptr, lengths, Nmax, no_sync, rate=None):
+        """_effect in place on device rows -> the effect's results; None where it has none or, with no_sync, has only queued"""
+        results = self._effect(fx, mid, None, lengths, rate=rate, device=(ptr, Nmax), no_sync=no_sync)[1:]
+        return results if results else None
 
     def trim_bounds(self, rows, frame=2048, hop=512, top_db=40.0, keep=0, lengths=None):
         """zvx_trim_bounds: per row the samples [begin, end) that join keeps (the decisions of mels.trim_silence, made on the device)
@@ -480,17 +542,17 @@ class Context:
         lra_low, lra_high (LUFS: the 10th and 95th percentile of the gated short-term windows), short_gated (their number) and peak (linear
         sample peak).  curves: also momentary and short_term, lists of B float64 arrays: the LUFS curves at a 100 ms step, n / h - 3 and
         n / h - 29 entries.  rows: a list of 1-D float waveforms, or a padded 2-D array + lengths; rate None: the model's sampling rate."""
-        x, n = self._rows(rows, lengths)
-        return self._loudness_stats(_ptr(x), n, x.shape[1], rate, 0, curves)
+        return self._loudness_stats(self._rows_arg(rows, lengths), rate, curves)
 
     def loudness_stats_device(self, ptr, lengths, Nmax, rate=None, curves=False):
         """zvx_loudness_stats on device rows [B][Nmax] f32 at `ptr` (ZVX_DEVICE_IN; they may be the output of a synthesize / normalize_device /
         limit_device call queued just before: stream order is the fence) -> as loudness_stats()."""
-        return self._loudness_stats(C.c_void_p(int(ptr)), _i32(lengths), int(Nmax), rate, ZVX_DEVICE_IN, curves)
+        return self._loudness_stats(self._rows_arg(None, lengths, ptr, Nmax), rate, curves)
 
-    def _loudness_stats(self, xptr, n, Nmax, rate, flags, curves, momentary=None, short_term=None):
-        """momentary / short_term: [B][stride] float64 arrays of the caller's to receive the curves instead of fresh ones"""
-        B, rate = len(n), self._rate(rate)
+    def _loudness_stats(self, rows_arg, rate, curves, momentary=None, short_term=None):
+        """rows_arg: what _rows_arg gives; momentary / short_term: [B][stride] float64 arrays of the caller's to receive the curves
+        instead of fresh ones"""
+        (xptr, n, B, Nmax, flags), rate = rows_arg, self._rate(rate)
         h = (rate + 5) // 10
         stats = np.zeros((B, ZVX_LS_COUNT), np.float64)
         if curves and momentary is None:
@@ -514,16 +576,15 @@ class Context:
         threshold on d'; gate_db: frames whose mean power is not above it are unvoiced.  window: samples integrated per lag (None: two
         periods of fmin); hop: samples between frames (None: the model's hop at the model's rate, otherwise 10 ms); frame f is centred on
         sample f * hop.  rows: a list of 1-D float waveforms, or a padded 2-D array + lengths; rate None: the model's sampling rate."""
-        x, n = self._rows(rows, lengths)
-        return self._pitch(_ptr(x), n, x.shape[1], rate, 0, fmin, fmax, threshold, gate_db, window, hop, curves)
+        return self._pitch(self._rows_arg(rows, lengths), rate, fmin, fmax, threshold, gate_db, window, hop, curves)
 
     def pitch_device(self, ptr, lengths, Nmax, rate=None, fmin=60.0, fmax=500.0, threshold=0.15, gate_db=-60.0, window=None, hop=None, curves=True):
         """zvx_pitch on device rows [B][Nmax] f32 at `ptr` (ZVX_DEVICE_IN; stream order is the fence) -> as pitch()."""
-        return self._pitch(C.c_void_p(int(ptr)), _i32(lengths), int(Nmax), rate, ZVX_DEVICE_IN, fmin, fmax, threshold, gate_db, window, hop, curves)
+        return self._pitch(self._rows_arg(None, lengths, ptr, Nmax), rate, fmin, fmax, threshold, gate_db, window, hop, curves)
 
-    def _pitch(self, xptr, n, Nmax, rate, flags, fmin, fmax, threshold, gate_db, window, hop, curves):
+    def _pitch(self, rows_arg, rate, fmin, fmax, threshold, gate_db, window, hop, curves):
         from . import pitch as _p
-        B, rate = len(n), self._rate(rate)
+        (xptr, n, B, Nmax, flags), rate = rows_arg, self._rate(rate)
         if window is None:
             window = _p.default_window(rate, fmin) if float(fmin) > 0.0 and np.isfinite(fmin) else 2
         if hop is None:
@@ -546,56 +607,41 @@ class Context:
         """zvx_normalize on host rows: every row (common: all rows as one programme, one gain) brought to `target` LUFS, the gain bounded by
         max_gain_db and by the linear sample-peak ceiling (<= 0: none) -> (rows_out [B][Nmax] float32 / int16 -- row b holds its samples
         times gain[b], then zeros --, lufs [B] float64, peak [B], gain [B] float32)."""
-        x, n = self._rows(rows, lengths)
-        B, Nmax = x.shape
-        prm = LoudnessParams(float(target), float(peak_ceiling), float(max_gain_db), ZVX_LOUD_COMMON if common else ZVX_LOUD_PER_ROW)
-        out = np.zeros((B, Nmax), np.int16 if pcm16 else np.float32)
-        lufs, peak, gain = np.zeros(B, np.float64), np.zeros(B, np.float32), np.zeros(B, np.float32)
-        self._chk(self._lib.zvx_normalize(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), Nmax, _ptr(lufs), _ptr(peak),
-                                          _ptr(gain), ZVX_PCM16 if pcm16 else 0))
-        return out, lufs, peak, gain
+        return self._effect(self._NORMALIZE, self._normalize_mid(target, peak_ceiling, max_gain_db, common), rows, lengths, rate=rate, pcm16=pcm16)
 
     def normalize_device(self, ptr, lengths, Nmax, target, *, peak_ceiling=0.891, max_gain_db=20.0, common=False, rate=None, no_sync=False):
         """zvx_normalize IN PLACE on device rows [B][Nmax] f32 at `ptr` (they may be the output of a synthesize(..., no_sync=True) call queued
         just before: stream order is the fence) -> (lufs, peak, gain); with no_sync the call only queues and returns None."""
-        n = _i32(lengths)
-        B = len(n)
-        prm = LoudnessParams(float(target), float(peak_ceiling), float(max_gain_db), ZVX_LOUD_COMMON if common else ZVX_LOUD_PER_ROW)
-        p = C.c_void_p(int(ptr))
-        res = None if no_sync else (np.zeros(B, np.float64), np.zeros(B, np.float32), np.zeros(B, np.float32))      # lufs, peak, gain
-        lufs, peak, gain = res or (None, None, None)
-        self._chk(self._lib.zvx_normalize(self._h, p, _ptr(n), B, int(Nmax), self._rate(rate), C.byref(prm), p, int(Nmax), _ptr(lufs), _ptr(peak),
-                                          _ptr(gain), ZVX_DEVICE_IN | ZVX_DEVICE_OUT | (ZVX_NO_SYNC if no_sync else 0)))
-        return res
+        return self._effect_in_place(self._NORMALIZE, self._normalize_mid(target, peak_ceiling, max_gain_db, common), ptr, lengths, Nmax, no_sync, rate)
+
+    @staticmethod
+    def _normalize_mid(target, peak_ceiling, max_gain_db, common):
+        return (C.byref(LoudnessParams(float(target), float(peak_ceiling), float(max_gain_db), ZVX_LOUD_COMMON if common else ZVX_LOUD_PER_ROW)),)
 
     def true_peak(self, rows, oversample=4, rate=None, lengths=None):
         """zvx_true_peak: per row max(max |x|, max |y|), y the row oversampled `oversample` (1, 2, 4, 8) times by zvx_resample's filter
         -> [B] float32.  rows: a list of 1-D float waveforms, or a padded 2-D array + lengths; rate None: the model's sampling rate."""
-        x, n = self._rows(rows, lengths)
-        B, Nmax = x.shape
-        tp = np.zeros(B, np.float32)
-        self._chk(self._lib.zvx_true_peak(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), int(oversample), _ptr(tp), 0))
-        return tp
+        return self._true_peak(self._rows_arg(rows, lengths), oversample, rate)
 
     def true_peak_device(self, ptr, lengths, Nmax, oversample=4, rate=None):
         """zvx_true_peak on device rows [B][Nmax] f32 at `ptr` (ZVX_DEVICE_IN; stream order is the fence) -> [B] float32"""
-        n = _i32(lengths)
-        tp = np.zeros(len(n), np.float32)
-        self._chk(self._lib.zvx_true_peak(self._h, C.c_void_p(int(ptr)), _ptr(n), len(n), int(Nmax), self._rate(rate), int(oversample), _ptr(tp),
-                                          ZVX_DEVICE_IN))
+        return self._true_peak(self._rows_arg(None, lengths, ptr, Nmax), oversample, rate)
+
+    def _true_peak(self, rows_arg, oversample, rate):
+        xptr, n, B, Nmax, flags = rows_arg
+        tp = np.zeros(B, np.float32)
+        self._chk(self._lib.zvx_true_peak(self._h, xptr, _ptr(n), B, Nmax, self._rate(rate), int(oversample), _ptr(tp), flags))
         return tp
 
     def limit(self, rows, ceiling, window_ms=5.0, oversample=4, pcm16=False, rate=None, lengths=None):
         """zvx_limit on host rows: a look-ahead limiter that leaves no sample above the linear `ceiling`, its gain smoothed over
         window_ms on either side and driven by the `oversample`-times oversampled envelope -> (rows_out [B][Nmax] float32 / int16 -- row
         b holds its limited samples, then zeros --, peak_in [B] float32: the envelope's maximum, min_gain [B] float32)."""
-        x, n = self._rows(rows, lengths)
-        B, Nmax = x.shape
-        prm, flags = self._limit_args(ceiling, window_ms, oversample, pcm16=pcm16)
-        out = np.zeros((B, Nmax), np.int16 if pcm16 else np.float32)
-        peak, gmin = np.zeros(B, np.float32), np.zeros(B, np.float32)
-        self._chk(self._lib.zvx_limit(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), Nmax, _ptr(peak), _ptr(gmin), flags))
-        return out, peak, gmin
+        return self._effect(self._LIMIT, self._limit_mid(ceiling, window_ms, oversample), rows, lengths, rate=rate, pcm16=pcm16)
+
+    @staticmethod
+    def _limit_mid(ceiling, window_ms, oversample):
+        return (C.byref(LimitParams(float(ceiling), float(window_ms), int(oversample))),)
 
     def limit_window(self, rows, ceiling, window_ms=5.0, oversample=4, in_origin=0, out_begin=0, out_count=-1, last=True, pcm16=False,
                      rate=None, lengths=None):
@@ -604,26 +650,13 @@ class Context:
         last: to the end of each row's signal) -> (out [B][n] float32 / int16 -- row b holds its emitted samples, then zeros --,
         peak_in [B], min_gain [B] float32, both over the emitted samples only).  The window must carry limiter.reach(W, oversample)
         samples of support on either side of the outputs, except at the signal's own ends (include/zvx.h)."""
-        x, n = self._rows(rows, lengths)
-        B, Nmax = x.shape
-        prm, flags = self._limit_args(ceiling, window_ms, oversample, pcm16=pcm16)
-        out, cols = self._window_out(n, Nmax, in_origin, out_begin, out_count, pcm16)
-        peak, gmin = np.zeros(B, np.float32), np.zeros(B, np.float32)
-        self._chk(self._lib.zvx_limit_ex(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), out.shape[1], _ptr(peak), _ptr(gmin),
-                                         flags, int(in_origin), int(out_begin), int(out_count), 1 if last else 0))
-        return out[:, :cols], peak, gmin
+        return self._effect(self._LIMIT, self._limit_mid(ceiling, window_ms, oversample), rows, lengths, rate=rate, pcm16=pcm16,
+                            window=(in_origin, out_begin, out_count, last))
 
     def limit_device(self, ptr, lengths, Nmax, ceiling, *, window_ms=5.0, oversample=4, rate=None, no_sync=False):
         """zvx_limit IN PLACE on device rows [B][Nmax] f32 at `ptr` (they may be the output of a synthesize / normalize_device call queued
         just before: stream order is the fence) -> (peak_in, min_gain); with no_sync the call only queues and returns None."""
-        n = _i32(lengths)
-        B = len(n)
-        prm, flags = self._limit_args(ceiling, window_ms, oversample, device=True, no_sync=no_sync)
-        p = C.c_void_p(int(ptr))
-        res = None if no_sync else (np.zeros(B, np.float32), np.zeros(B, np.float32))                                # peak_in, min_gain
-        peak, gmin = res or (None, None)
-        self._chk(self._lib.zvx_limit(self._h, p, _ptr(n), B, int(Nmax), self._rate(rate), C.byref(prm), p, int(Nmax), _ptr(peak), _ptr(gmin), flags))
-        return res
+        return self._effect_in_place(self._LIMIT, self._limit_mid(ceiling, window_ms, oversample), ptr, lengths, Nmax, no_sync, rate)
 
     def denoise_bias(self):
         """zvx_denoise_bias: the magnitude spectrum of what the context's vocoder emits for 88 silent mel frames, the mean over the STFT
@@ -639,17 +672,14 @@ class Context:
             raise ValueError(f"denoise: bias has {bias.shape[0]} entries, the model's STFT has {nf} bins")
         return bias
 
+    def _denoise_mid(self, bias, strength, floor):
+        return _ptr(self._denoise_bias_arg(bias)), C.byref(DenoiseParams(float(strength), float(floor)))
+
     def denoise(self, rows, bias, strength, floor=0.0, pcm16=False, lengths=None):
         """zvx_denoise on host rows: strength * bias[k] is taken off the magnitude of every STFT bin of every frame (never below floor
         times the magnitude), the phase kept, and the frames are overlap-added back -> rows_out [B][Nmax] float32 / int16 -- row b holds
         its denoised samples, then zeros.  rows: a list of 1-D float waveforms, or a padded 2-D array + lengths, at the model's rate."""
-        x, n = self._rows(rows, lengths)
-        B, Nmax = x.shape
-        bias = self._denoise_bias_arg(bias)
-        prm, flags = self._denoise_args(strength, floor, pcm16=pcm16)
-        out = np.zeros((B, Nmax), np.int16 if pcm16 else np.float32)
-        self._chk(self._lib.zvx_denoise(self._h, _ptr(x), _ptr(n), B, Nmax, _ptr(bias), C.byref(prm), _ptr(out), Nmax, flags))
-        return out
+        return self._effect(self._DENOISE, self._denoise_mid(bias, strength, floor), rows, lengths, pcm16=pcm16)[0]
 
     def denoise_window(self, rows, bias, strength, floor=0.0, in_origin=0, out_begin=0, out_count=-1, last=True, pcm16=False, lengths=None):
         """zvx_denoise_ex on host rows: the rows hold samples [in_origin, in_origin + len) of signals that start at sample 0 and, with
@@ -657,70 +687,31 @@ class Context:
         last: to the end of each row's signal) -> out [B][n] float32 / int16 -- row b holds its emitted samples, then zeros.  The window
         must carry denoiser.reach(fft_size) = fft_size - 1 samples of support on either side of the outputs, except at the signal's own
         ends (include/zvx.h)."""
-        x, n = self._rows(rows, lengths)
-        B, Nmax = x.shape
-        bias = self._denoise_bias_arg(bias)
-        prm, flags = self._denoise_args(strength, floor, pcm16=pcm16)
-        out, cols = self._window_out(n, Nmax, in_origin, out_begin, out_count, pcm16)
-        self._chk(self._lib.zvx_denoise_ex(self._h, _ptr(x), _ptr(n), B, Nmax, _ptr(bias), C.byref(prm), _ptr(out), out.shape[1], flags,
-                                           int(in_origin), int(out_begin), int(out_count), 1 if last else 0))
-        return out[:, :cols]
-
-    @staticmethod
-    def _row_windows(windows, n, Nmax, pcm16):
-        """a list of (in_origin, out_begin, out_count, last), one per row -> (RowWindow array, out [B][stride] of zeros, cnt [B]: the
-        emitted samples of each row)"""
-        if len(windows) != len(n):
-            raise ValueError(f"{len(windows)} windows for {len(n)} rows")
-        win = (RowWindow * max(len(n), 1))()
-        cnt = np.zeros(len(n), np.int64)
-        for b, (in_origin, out_begin, out_count, last) in enumerate(windows):
-            win[b] = RowWindow(int(in_origin), int(out_begin), int(out_count), 1 if last else 0, 0)
-            cnt[b] = int(out_count) if out_count >= 0 else max(0, int(in_origin) + int(n[b]) - int(out_begin))
-        cols = int(cnt.max()) if len(cnt) else 0
-        return win, np.zeros((len(n), max(cols, Nmax)), np.int16 if pcm16 else np.float32), cnt
+        return self._effect(self._DENOISE, self._denoise_mid(bias, strength, floor), rows, lengths, pcm16=pcm16,
+                            window=(in_origin, out_begin, out_count, last))[0]
 
     def denoise_rows(self, rows, bias, strength, windows, floor=0.0, pcm16=False, lengths=None):
         """zvx_denoise_rows on host rows: denoise_window with a window per row -- windows[b] = (in_origin, out_begin, out_count, last) says
         which samples of its signal row b holds and which outputs of the whole-signal denoiser it emits -> a list of B arrays, row b's
         emitted samples (float32 / int16), bit for bit those of denoise_window on that row alone."""
-        x, n = self._rows(rows, lengths)
-        B, Nmax = x.shape
-        bias = self._denoise_bias_arg(bias)
-        prm, flags = self._denoise_args(strength, floor, pcm16=pcm16)
-        win, out, cnt = self._row_windows(windows, n, Nmax, pcm16)
-        self._chk(self._lib.zvx_denoise_rows(self._h, _ptr(x), _ptr(n), B, Nmax, _ptr(bias), C.byref(prm), _ptr(out), out.shape[1], flags, win))
-        return [out[b, :cnt[b]] for b in range(B)]
+        return self._effect(self._DENOISE, self._denoise_mid(bias, strength, floor), rows, lengths, pcm16=pcm16, windows=windows)[0]
 
     def limit_rows(self, rows, ceiling, windows, window_ms=5.0, oversample=4, pcm16=False, rate=None, lengths=None):
         """zvx_limit_rows on host rows: limit_window with a window per row (windows[b] = (in_origin, out_begin, out_count, last)) -> (a list
         of B arrays, row b's emitted samples, peak_in [B], min_gain [B] float32, both over each row's emitted samples only), bit for bit
         what limit_window gives on each row alone."""
-        x, n = self._rows(rows, lengths)
-        B, Nmax = x.shape
-        prm, flags = self._limit_args(ceiling, window_ms, oversample, pcm16=pcm16)
-        win, out, cnt = self._row_windows(windows, n, Nmax, pcm16)
-        peak, gmin = np.zeros(B, np.float32), np.zeros(B, np.float32)
-        self._chk(self._lib.zvx_limit_rows(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), out.shape[1], _ptr(peak),
-                                           _ptr(gmin), flags, win))
-        return [out[b, :cnt[b]] for b in range(B)], peak, gmin
+        return self._effect(self._LIMIT, self._limit_mid(ceiling, window_ms, oversample), rows, lengths, rate=rate, pcm16=pcm16, windows=windows)
 
-    @classmethod
-    def _level_args(cls, target, max_gain_db, window_ms, lookahead_ms, **flags):
-        return LevelParams(float(target), float(max_gain_db), float(window_ms), float(lookahead_ms)), cls._flags(**flags)
+    @staticmethod
+    def _level_mid(target, max_gain_db, window_ms, lookahead_ms):
+        return (C.byref(LevelParams(float(target), float(max_gain_db), float(window_ms), float(lookahead_ms))),)
 
     def level(self, rows, target, max_gain_db=20.0, window_ms=3000.0, lookahead_ms=100.0, pcm16=False, rate=None, lengths=None):
         """zvx_level on host rows: a gain curve that steers the gated short-term loudness of the last window_ms towards `target` LUFS,
         looking lookahead_ms ahead and never above max_gain_db (an AGC, not R128 normalisation; zerovox_amd.leveler) -> (rows_out
         [B][Nmax] float32 / int16 -- row b holds its levelled samples, then zeros --, gain_lo [B], gain_hi [B] float32: the smallest and
         the largest gain applied)."""
-        x, n = self._rows(rows, lengths)
-        B, Nmax = x.shape
-        prm, flags = self._level_args(target, max_gain_db, window_ms, lookahead_ms, pcm16=pcm16)
-        out = np.zeros((B, Nmax), np.int16 if pcm16 else np.float32)
-        lo, hi = np.zeros(B, np.float32), np.zeros(B, np.float32)
-        self._chk(self._lib.zvx_level(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), Nmax, _ptr(lo), _ptr(hi), flags))
-        return out, lo, hi
+        return self._effect(self._LEVEL, self._level_mid(target, max_gain_db, window_ms, lookahead_ms), rows, lengths, rate=rate, pcm16=pcm16)
 
     def level_window(self, rows, target, max_gain_db=20.0, window_ms=3000.0, lookahead_ms=100.0, in_origin=0, out_begin=0, out_count=-1,
                      last=True, pcm16=False, rate=None, lengths=None):
@@ -729,95 +720,57 @@ class Context:
         last: to the end of each row's signal) -> (out [B][n] float32 / int16, gain_lo [B], gain_hi [B] float32, both over the emitted
         samples only).  The window must carry leveler.reach(rate, window_ms, lookahead_ms) = (RL, RR) samples of support to the left and
         to the right of the outputs, except at the signal's own ends (include/zvx.h)."""
-        x, n = self._rows(rows, lengths)
-        B, Nmax = x.shape
-        prm, flags = self._level_args(target, max_gain_db, window_ms, lookahead_ms, pcm16=pcm16)
-        out, cols = self._window_out(n, Nmax, in_origin, out_begin, out_count, pcm16)
-        lo, hi = np.zeros(B, np.float32), np.zeros(B, np.float32)
-        self._chk(self._lib.zvx_level_ex(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), out.shape[1], _ptr(lo), _ptr(hi),
-                                         flags, int(in_origin), int(out_begin), int(out_count), 1 if last else 0))
-        return out[:, :cols], lo, hi
+        return self._effect(self._LEVEL, self._level_mid(target, max_gain_db, window_ms, lookahead_ms), rows, lengths, rate=rate, pcm16=pcm16,
+                            window=(in_origin, out_begin, out_count, last))
 
     def level_rows(self, rows, windows, target, max_gain_db=20.0, window_ms=3000.0, lookahead_ms=100.0, pcm16=False, rate=None, lengths=None):
         """zvx_level_rows on host rows: level_window with a window per row (windows[b] = (in_origin, out_begin, out_count, last)) -> (a list
         of B arrays, row b's emitted samples, gain_lo [B], gain_hi [B] float32, both over each row's emitted samples only), bit for bit
         what level_window gives on each row alone."""
-        x, n = self._rows(rows, lengths)
-        B, Nmax = x.shape
-        prm, flags = self._level_args(target, max_gain_db, window_ms, lookahead_ms, pcm16=pcm16)
-        win, out, cnt = self._row_windows(windows, n, Nmax, pcm16)
-        lo, hi = np.zeros(B, np.float32), np.zeros(B, np.float32)
-        self._chk(self._lib.zvx_level_rows(self._h, _ptr(x), _ptr(n), B, Nmax, self._rate(rate), C.byref(prm), _ptr(out), out.shape[1], _ptr(lo),
-                                           _ptr(hi), flags, win))
-        return [out[b, :cnt[b]] for b in range(B)], lo, hi
+        return self._effect(self._LEVEL, self._level_mid(target, max_gain_db, window_ms, lookahead_ms), rows, lengths, rate=rate, pcm16=pcm16,
+                            windows=windows)
 
     def resample_rows(self, rows, rate_in, rate_out, windows, pcm16=False, lengths=None):
         """zvx_resample_rows on host rows: resample_window with a window per row -- windows[b] = (in_origin, out_begin, out_count) or
         (in_origin, out_begin, out_count, last); row b holds samples [in_origin, in_origin + len) of a signal that is zero elsewhere ->
         (a list of B arrays, row b's emitted samples (float32 / int16), bit for bit those of resample_window on that row alone,
         out_len [B])."""
-        x, n = self._rows(rows, lengths)
-        B, Nmax = x.shape
-        if len(windows) != B:
-            raise ValueError(f"{len(windows)} windows for {B} rows")
-        win = (RowWindow * max(B, 1))()
-        cnt = np.zeros(B, np.int64)
-        for b, w in enumerate(windows):
-            in_origin, out_begin, out_count = (int(v) for v in w[:3])
-            win[b] = RowWindow(in_origin, out_begin, out_count, 1 if len(w) > 3 and w[3] else 0, 0)
-            cnt[b] = out_count if out_count >= 0 else max(0, resampled_len(in_origin + int(n[b]), rate_in, rate_out) - out_begin)
-        cols = max(int(cnt.max()) if B else 0, 1)
-        out = np.zeros((B, cols), np.int16 if pcm16 else np.float32)
+        xp, n, B, Nmax, _ = self._rows_arg(rows, lengths)
+        windows = [tuple(w[:3]) + (len(w) > 3 and w[3],) for w in windows]
+        win, out, _ = self._row_windows(windows, n, 1, pcm16, lambda end: resampled_len(end, rate_in, rate_out))
         out_len = np.zeros(B, np.int32)
-        self._chk(self._lib.zvx_resample_rows(self._h, _ptr(x), _ptr(n), B, Nmax, int(rate_in), int(rate_out), _ptr(out), cols, _ptr(out_len),
+        self._chk(self._lib.zvx_resample_rows(self._h, xp, _ptr(n), B, Nmax, int(rate_in), int(rate_out), _ptr(out), out.shape[1], _ptr(out_len),
                                               ZVX_PCM16 if pcm16 else 0, win))
         return [out[b, :out_len[b]] for b in range(B)], out_len
 
     def denoise_device(self, ptr, lengths, Nmax, bias, strength, *, floor=0.0, no_sync=False):
         """zvx_denoise IN PLACE on device rows [B][Nmax] f32 at `ptr` (they may be the output of a synthesize / vocode_device call queued
         just before: stream order is the fence); with no_sync the call only queues.  bias is a host array and may be reused at once."""
-        n = _i32(lengths)
-        bias = self._denoise_bias_arg(bias)
-        prm, flags = self._denoise_args(strength, floor, device=True, no_sync=no_sync)
-        p = C.c_void_p(int(ptr))
-        self._chk(self._lib.zvx_denoise(self._h, p, _ptr(n), len(n), int(Nmax), _ptr(bias), C.byref(prm), p, int(Nmax), flags))
+        self._effect_in_place(self._DENOISE, self._denoise_mid(bias, strength, floor), ptr, lengths, Nmax, no_sync)
 
-    @classmethod
-    def _watermark_args(cls, key, depth_db=1.0, lo_hz=250.0, hi_hz=8000.0, block_frames=8, band_bins=4, period_blocks=64, **flags):
-        return (WatermarkParams(int(key) & 0xFFFFFFFFFFFFFFFF, float(depth_db), float(lo_hz), float(hi_hz), int(block_frames), int(band_bins),
-                                int(period_blocks), 0), cls._flags(**flags))
+    @staticmethod
+    def _watermark_params(key, depth_db=1.0, lo_hz=250.0, hi_hz=8000.0, block_frames=8, band_bins=4, period_blocks=64):
+        return WatermarkParams(int(key) & 0xFFFFFFFFFFFFFFFF, float(depth_db), float(lo_hz), float(hi_hz), int(block_frames), int(band_bins),
+                               int(period_blocks), 0)
 
     def watermark(self, rows, key, *, pcm16=False, lengths=None, **params):
         """zvx_watermark on host rows: the keyed mark of zerovox_amd.watermark laid on every row (params: depth_db, lo_hz, hi_hz,
         block_frames, band_bins, period_blocks; the defaults are watermark.EMBED_DEFAULTS) -> rows_out [B][Nmax] float32 / int16 -- row b
         holds its marked samples, then zeros.  rows: a list of 1-D float waveforms, or a padded 2-D array + lengths, at the model's rate."""
-        x, n = self._rows(rows, lengths)
-        B, Nmax = x.shape
-        prm, flags = self._watermark_args(key, pcm16=pcm16, **params)
-        out = np.zeros((B, Nmax), np.int16 if pcm16 else np.float32)
-        self._chk(self._lib.zvx_watermark(self._h, _ptr(x), _ptr(n), B, Nmax, C.byref(prm), _ptr(out), Nmax, flags))
-        return out
+        return self._effect(self._WATERMARK, (C.byref(self._watermark_params(key, **params)),), rows, lengths, pcm16=pcm16)[0]
 
     def watermark_window(self, rows, key, *, in_origin=0, out_begin=0, out_count=-1, last=True, pcm16=False, lengths=None, **params):
         """zvx_watermark_ex on host rows: the rows hold samples [in_origin, in_origin + len) of signals that start at sample 0 and, with
         `last`, end with the row; the outputs [out_begin, out_begin + out_count) of the whole-signal call (out_count -1, which needs
         last: to the end of each row's signal) -> out [B][n] float32 / int16.  The window must carry watermark.reach(fft_size) =
         fft_size - 1 samples of support on either side of the outputs, except at the signal's own ends (include/zvx.h)."""
-        x, n = self._rows(rows, lengths)
-        B, Nmax = x.shape
-        prm, flags = self._watermark_args(key, pcm16=pcm16, **params)
-        out, cols = self._window_out(n, Nmax, in_origin, out_begin, out_count, pcm16)
-        self._chk(self._lib.zvx_watermark_ex(self._h, _ptr(x), _ptr(n), B, Nmax, C.byref(prm), _ptr(out), out.shape[1], flags,
-                                             int(in_origin), int(out_begin), int(out_count), 1 if last else 0))
-        return out[:, :cols]
+        return self._effect(self._WATERMARK, (C.byref(self._watermark_params(key, **params)),), rows, lengths, pcm16=pcm16,
+                            window=(in_origin, out_begin, out_count, last))[0]
 
     def watermark_device(self, ptr, lengths, Nmax, key, *, no_sync=False, **params):
         """zvx_watermark IN PLACE on device rows [B][Nmax] f32 at `ptr` (they may be the output of a call queued just before: stream
         order is the fence); with no_sync the call only queues."""
-        n = _i32(lengths)
-        prm, flags = self._watermark_args(key, device=True, no_sync=no_sync, **params)
-        p = C.c_void_p(int(ptr))
-        self._chk(self._lib.zvx_watermark(self._h, p, _ptr(n), len(n), int(Nmax), C.byref(prm), p, int(Nmax), flags))
+        self._effect_in_place(self._WATERMARK, (C.byref(self._watermark_params(key, **params)),), ptr, lengths, Nmax, no_sync)
 
     def watermark_detect(self, rows, key, *, window_frames=256, threshold=None, lengths=None, device_ptr=None, Nmax=None, **params):
         """zvx_watermark_detect: per row the best score over every window of window_frames frames (0: the row) and every offset, with the
@@ -825,22 +778,16 @@ class Context:
         watermark.WatermarkResult.  rows: a list of 1-D float waveforms, or a padded 2-D array + lengths, at the model's rate; or, with
         device_ptr, device rows [B][Nmax] f32 there and `lengths`."""
         from . import watermark as wm
-        if device_ptr is None:
-            x, n = self._rows(rows, lengths)
-            B, Nmax = x.shape
-            xp, flags = _ptr(x), 0
-        else:
-            n = _i32(lengths)
-            B, xp, flags = len(n), C.c_void_p(int(device_ptr)), ZVX_DEVICE_IN
+        xp, n, B, Nmax, flags = self._rows_arg(rows, lengths, device_ptr, Nmax)
         params.pop("depth_db", None)
-        prm, _ = self._watermark_args(key, **params)
+        prm = self._watermark_params(key, **params)
         fft, hop, wf = self.get_int("fft_size"), self.hop, int(window_frames)
         pad = (fft - hop) // 2
-        F = max(0, 1 + (int(Nmax) + 2 * pad - fft) // hop)
+        F = max(0, 1 + (Nmax + 2 * pad - fft) // hop)
         nw = 1 if wf < 2 or F <= wf else 1 + -(-(F - wf) // (wf // 2))
         score, off, win = np.zeros(B, np.float32), np.zeros(B, np.int32), np.zeros(B, np.int32)
         ws, wo = np.zeros((B, nw), np.float32), np.zeros((B, nw), np.int32)
-        self._chk(self._lib.zvx_watermark_detect(self._h, xp, _ptr(n), B, int(Nmax), C.byref(prm), wf, _ptr(score), _ptr(off), _ptr(win),
+        self._chk(self._lib.zvx_watermark_detect(self._h, xp, _ptr(n), B, Nmax, C.byref(prm), wf, _ptr(score), _ptr(off), _ptr(win),
                                                  _ptr(ws), _ptr(wo), nw, flags))
         thr = wm.THRESHOLD if threshold is None else float(threshold)
         res = []
@@ -864,22 +811,18 @@ class Context:
         params['key'] for every row), windows[b] = (in_origin, out_begin, out_count, last) says which samples of its signal row b holds
         and which outputs of the whole-signal call it emits (None: every row whole) -> a list of B arrays, row b's emitted samples
         (float32 / int16), bit for bit those of watermark_window on that row alone with its key."""
-        x, n = self._rows(rows, lengths)
-        B, Nmax = x.shape
+        B = len(rows)
         if windows is None:
             windows = [(0, 0, -1, True)] * B
         if keys is None:
-            kp, key0, ka = None, params.pop("key"), None
+            kp, key0 = None, params.pop("key")
         else:
             ka = self._keys_arg(keys)
             if len(ka) != B:
                 raise ValueError(f"{len(ka)} keys for {B} rows")
             params.pop("key", None)
             kp, key0 = _ptr(ka), 0
-        prm, flags = self._watermark_args(key0, pcm16=pcm16, **params)
-        win, out, cnt = self._row_windows(windows, n, Nmax, pcm16)
-        self._chk(self._lib.zvx_watermark_rows(self._h, _ptr(x), _ptr(n), B, Nmax, C.byref(prm), kp, _ptr(out), out.shape[1], flags, win))
-        return [out[b, :cnt[b]] for b in range(B)]
+        return self._effect(self._WATERMARK, (C.byref(self._watermark_params(key0, **params)), kp), rows, lengths, pcm16=pcm16, windows=windows)[0]
 
     def watermark_identify(self, rows, keys, *, window_frames=256, threshold=None, lengths=None, device_ptr=None, Nmax=None, **params):
         """zvx_watermark_identify: which of the candidate `keys` marked each row -- one analysis and one search launch for all K keys, each
@@ -887,21 +830,15 @@ class Context:
         lower) -> a list of B watermark.IdentifyResult.  rows as watermark_detect's.  The largest score of WRONG keys grows with their
         number: watermark.THRESHOLD was measured over 256 of them, so with many more candidates judge by `margin` as well."""
         from . import watermark as wm
-        if device_ptr is None:
-            x, n = self._rows(rows, lengths)
-            B, Nmax = x.shape
-            xp, flags = _ptr(x), 0
-        else:
-            n = _i32(lengths)
-            B, xp, flags = len(n), C.c_void_p(int(device_ptr)), ZVX_DEVICE_IN
+        xp, n, B, Nmax, flags = self._rows_arg(rows, lengths, device_ptr, Nmax)
         ka = self._keys_arg(keys)
         K = len(ka)
         params.pop("depth_db", None)
         params.pop("key", None)
-        prm, _ = self._watermark_args(0, **params)
+        prm = self._watermark_params(0, **params)
         score, off, win = np.zeros((B, max(K, 1)), np.float32), np.zeros((B, max(K, 1)), np.int32), np.zeros((B, max(K, 1)), np.int32)
         best = np.zeros(B, np.int32)
-        self._chk(self._lib.zvx_watermark_identify(self._h, xp, _ptr(n), B, int(Nmax), C.byref(prm), _ptr(ka), K, int(window_frames), _ptr(score),
+        self._chk(self._lib.zvx_watermark_identify(self._h, xp, _ptr(n), B, Nmax, C.byref(prm), _ptr(ka), K, int(window_frames), _ptr(score),
                                                    _ptr(off), _ptr(win), _ptr(best), flags))
         return [wm.identify_result(ka, score[b], off[b], win[b], int(best[b]), threshold) for b in range(B)]
 

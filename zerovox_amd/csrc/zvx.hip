@@ -2167,6 +2167,28 @@ std::vector<PostRow> post_rows(const float* x, long x_bs, void* out, long out_bs
         rows[(size_t)b] = PostRow{x + (size_t)b * x_bs, (char*)out + (size_t)b * out_bs * ss, nsamples[b], rw.at(b), rw.cnt[(size_t)b]};
     return rows;
 }
+// What every windowed effect does once its own checks have passed: the rows go to the device ("<prefix>.in"), the outputs are staged where
+// the host wants them ("<prefix>.out"), `run(rows)` issues the effect's launches over the PostRows and gives its device result words (or
+// nullptr), and RowsReturn brings rows and words over behind the call's one wait.  writes_rows false: a measuring call, `out` is not looked at (zvx_true_peak).
+// -> the `res_bytes` of result words on the host; nullptr where the host wants none
+template <typename Run>
+const float* post_call(zvx_ctx* c, const char* prefix, const float* in, const int32_t* nsamples, int B, int Nmax, void* out, int64_t out_stride, bool writes_rows,
+                       int flags, const RowsWindows& rw, size_t res_bytes, bool want_host, Run&& run) {
+    const std::string px(prefix);
+    RowsReturn ret(c, B, res_bytes, want_host, writes_rows, rw.cnt_max, flags);
+    const float* x = rows_to_device(c, px, in, B, Nmax, flags);
+    long out_bs = 0;
+    void* od = ret.out_rows((px + ".out").c_str(), out, out_stride, &out_bs);
+    const std::vector<PostRow> rows = post_rows(x, Nmax, od, out_bs, ret.ss, nsamples, rw, B);
+    const float* res = run(rows.data());
+    return (const float*)ret.finish(res, out, out_stride, rw.cnt.data(), flags);
+}
+// two [B] result arrays of the host's, either may be NULL, from the words [2][B]
+void copy_word_pairs(const float* words, int B, float* first, float* second) {
+    if (!words) return;
+    if (first) memcpy(first, words, (size_t)B * sizeof(float));
+    if (second) memcpy(second, words + B, (size_t)B * sizeof(float));
+}
 // Every row converted as a signal of its own length len[b] * mul, held from sample in_origin on and zero elsewhere: per row the outputs
 // [out_begin, out_begin + cnt[b]) (out_count -1: to the end of the row's signal), and the longest of them.
 struct RsPlan { RowsWindow w; long out_max = 0; std::vector<long> cnt; };
@@ -2899,18 +2921,9 @@ void do_limit(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamp
     if (lim) out_rows_check(who, in, out, out_stride, Nmax, flags);
     const int W = lim ? limit_params_check(who, rate, p) : 0;
     const RowsWindows rw = rows_windows_check(who, win, nsamples, B, 2 * (int64_t)W + (os > 1 ? LIMIT_ENV_REACH : 0), in, out, out_stride);
-    RowsReturn ret(c, B, (size_t)B * 8, peak_in || min_gain, lim, rw.cnt_max, flags);      // words: peak [B], then min gain [B]
-    const float* x = rows_to_device(c, "lim", in, B, Nmax, flags);
-    long out_bs = 0;
-    void* od = ret.out_rows("lim.out", out, out_stride, &out_bs);
-    const std::vector<PostRow> rows = post_rows(x, Nmax, od, out_bs, ret.ss, nsamples, rw, B);
-    const float* res = run_limit_rows(c, who, rows.data(), B, p, W, (flags & ZVX_PCM16) ? 1 : 0, os);
-    const float* r_h = (const float*)ret.finish(res, out, out_stride, rw.cnt.data(), flags);
-    if (!r_h) return;
-    for (int b = 0; b < B; b++) {
-        if (peak_in) peak_in[b] = r_h[b];
-        if (min_gain) min_gain[b] = r_h[B + b];
-    }
+    const float* words = post_call(c, "lim", in, nsamples, B, Nmax, out, out_stride, lim, flags, rw, (size_t)B * 8, peak_in || min_gain,
+        [&](const PostRow* rows) { return run_limit_rows(c, who, rows, B, p, W, (flags & ZVX_PCM16) ? 1 : 0, os); });
+    copy_word_pairs(words, B, peak_in, min_gain);            // words: peak [B], then min gain [B]
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3021,18 +3034,9 @@ void do_level(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamp
     const LevelGeom g = level_params_check(who, rate, p);
     const RowsWindows rw = rows_windows_check(who, win, nsamples, B, g.RL, in, out, out_stride, g.RR);
     level_clamped_support_check(who, rw, nsamples, B, g);
-    RowsReturn ret(c, B, (size_t)B * 8, gain_lo || gain_hi, true, rw.cnt_max, flags);      // words: gain_lo [B], then gain_hi [B]
-    const float* x = rows_to_device(c, "lvl", in, B, Nmax, flags);
-    long out_bs = 0;
-    void* od = ret.out_rows("lvl.out", out, out_stride, &out_bs);
-    const std::vector<PostRow> rows = post_rows(x, Nmax, od, out_bs, ret.ss, nsamples, rw, B);
-    const float* res = run_level_rows(c, rows.data(), B, rate, p, g, (flags & ZVX_PCM16) ? 1 : 0);
-    const float* r_h = (const float*)ret.finish(res, out, out_stride, rw.cnt.data(), flags);
-    if (!r_h) return;
-    for (int b = 0; b < B; b++) {
-        if (gain_lo) gain_lo[b] = r_h[b];
-        if (gain_hi) gain_hi[b] = r_h[B + b];
-    }
+    const float* words = post_call(c, "lvl", in, nsamples, B, Nmax, out, out_stride, true, flags, rw, (size_t)B * 8, gain_lo || gain_hi,
+        [&](const PostRow* rows) { return run_level_rows(c, rows, B, rate, p, g, (flags & ZVX_PCM16) ? 1 : 0); });
+    copy_word_pairs(words, B, gain_lo, gain_hi);             // words: gain_lo [B], then gain_hi [B]
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3051,6 +3055,12 @@ DnGeom dn_geom(const zvx_ctx* c, const char* who) {
 // the least length of a non-empty row: zvx_melspec's conditions (a mirror exists on both sides, one whole frame)
 int dn_min_samples(const DnGeom& g) { return std::max(g.pad + 1, g.n_fft - 2 * g.pad); }
 int dn_frames(const DnGeom& g, long n) { return n > 0 ? (int)(1 + (n + 2 * g.pad - g.n_fft) / g.hop) : 0; }
+// zvx_melspec's length conditions hold for the whole SIGNAL of row b: known where it ends with the window (no window: the row is its signal)
+void stft_len_check(const char* who, const DnGeom& g, int b, int32_t n, const RowsWindow& w = {}) {
+    if (w.last && n > 0 && w.in_origin + n < dn_min_samples(g))
+        fail(ZVX_E_INVALID, "%s: row %d has %lld samples; a row that is not empty needs at least %d (zvx_melspec's conditions)", who, b,
+             (long long)(w.in_origin + n), dn_min_samples(g));
+}
 
 // Twiddles, window and squared window, designed in double and kept for the life of the context.  win_length is not a manifest key: it is
 // read off the window inside mel.dft (row 0 of the cosine block is the window itself; a periodic Hann is zero at its first sample only).
@@ -3181,17 +3191,11 @@ void do_denoise(zvx_ctx* c, const char* who, const float* in, const int32_t* nsa
     out_rows_check(who, in, out, out_stride, Nmax, flags);
     const DnGeom g = denoise_params_check(c, who, bias, p);
     const RowsWindows rw = rows_windows_check(who, win, nsamples, B, g.n_fft - 1, in, out, out_stride);
-    for (int b = 0; b < B; b++)                              // zvx_melspec's length conditions hold for the whole SIGNAL: known where it ends with the window
-        if (rw.at(b).last && nsamples[b] > 0 && rw.at(b).in_origin + nsamples[b] < dn_min_samples(g))
-            fail(ZVX_E_INVALID, "%s: row %d has %lld samples; a row that is not empty needs at least %d (zvx_melspec's conditions)", who, b,
-                 (long long)(rw.at(b).in_origin + nsamples[b]), dn_min_samples(g));
-    RowsReturn ret(c, B, 0, false, true, rw.cnt_max, flags);
-    const float* x = rows_to_device(c, "dn", in, B, Nmax, flags);
-    long out_bs = 0;
-    void* od = ret.out_rows("dn.out", out, out_stride, &out_bs);
-    const std::vector<PostRow> rows = post_rows(x, Nmax, od, out_bs, ret.ss, nsamples, rw, B);
-    run_denoise_rows(c, g, rows.data(), B, bias, p, (flags & ZVX_PCM16) ? 1 : 0);
-    ret.finish(nullptr, out, out_stride, rw.cnt.data(), flags);
+    for (int b = 0; b < B; b++) stft_len_check(who, g, b, nsamples[b], rw.at(b));
+    post_call(c, "dn", in, nsamples, B, Nmax, out, out_stride, true, flags, rw, 0, false, [&](const PostRow* rows) {
+        run_denoise_rows(c, g, rows, B, bias, p, (flags & ZVX_PCM16) ? 1 : 0);
+        return nullptr;
+    });
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -3286,17 +3290,64 @@ void do_watermark(zvx_ctx* c, const char* who, const float* in, const int32_t* n
     const WmPlan wp = watermark_params_check(c, who, p);
     const DnGeom& g = wp.g;
     const RowsWindows rw = rows_windows_check(who, win, nsamples, B, g.n_fft - 1, in, out, out_stride);
-    for (int b = 0; b < B; b++)                              // zvx_melspec's length conditions hold for the whole SIGNAL: known where it ends with the window
-        if (rw.at(b).last && nsamples[b] > 0 && rw.at(b).in_origin + nsamples[b] < dn_min_samples(g))
-            fail(ZVX_E_INVALID, "%s: row %d has %lld samples; a row that is not empty needs at least %d (zvx_melspec's conditions)", who, b,
-                 (long long)(rw.at(b).in_origin + nsamples[b]), dn_min_samples(g));
-    RowsReturn ret(c, B, 0, false, true, rw.cnt_max, flags);
-    const float* x = rows_to_device(c, "wm", in, B, Nmax, flags);
-    long out_bs = 0;
-    void* od = ret.out_rows("wm.out", out, out_stride, &out_bs);
-    const std::vector<PostRow> rows = post_rows(x, Nmax, od, out_bs, ret.ss, nsamples, rw, B);
-    run_watermark_rows(c, wp, rows.data(), B, p, (flags & ZVX_PCM16) ? 1 : 0, keys);
-    ret.finish(nullptr, out, out_stride, rw.cnt.data(), flags);
+    for (int b = 0; b < B; b++) stft_len_check(who, wp.g, b, nsamples[b], rw.at(b));
+    post_call(c, "wm", in, nsamples, B, Nmax, out, out_stride, true, flags, rw, 0, false, [&](const PostRow* rows) {
+        run_watermark_rows(c, wp, rows, B, p, (flags & ZVX_PCM16) ? 1 : 0, keys);
+        return nullptr;
+    });
+}
+
+// The analysis zvx_watermark_detect and zvx_watermark_identify share: every row's frames into band differences d [F][J - 2], searched in
+// windows of WF frames; the window results are [B][NWp][K] scores and as many offsets, K = 1 for the detector.  wm_analysis is pure (an
+// entry point plans among its checks); wm_analysis_fill sets the launch arguments' geometry, table and band fields; wm_analysis_rows
+// takes "wm.d", the caller's result buffer and "wm.rows", in the order the entry points always took them, and uploads the row table.
+struct WmAnalysis {
+    std::vector<WmDetectRow> tab; std::vector<size_t> d_at;
+    int WF = 0, NW = 0, NWp = 1; long Fmax = 0; double frames = 0; size_t d_floats = 0;
+    int windows(int b) const { return wm_windows(tab[(size_t)b].F, WF); }
+    size_t res_pad(int K) const { return (tab.size() * NWp * K * 4 + 255) & ~(size_t)255; }      // scores or offsets, padded in the pinned block
+};
+WmAnalysis wm_analysis(const WmPlan& wp, const int32_t* nsamples, int B, int window_frames) {
+    WmAnalysis an;
+    an.WF = window_frames; an.tab.resize((size_t)B); an.d_at.resize((size_t)B);
+    for (int b = 0; b < B; b++) {
+        const int F = dn_frames(wp.g, nsamples[b]);
+        an.tab[(size_t)b] = WmDetectRow{nullptr, nullptr, nsamples[b], F};
+        an.d_at[(size_t)b] = an.d_floats; an.d_floats += (size_t)F * (wp.J - 2);
+        an.NW = std::max(an.NW, an.windows(b)); an.Fmax = std::max<long>(an.Fmax, F); an.frames += F;
+    }
+    an.NWp = std::max(an.NW, 1);
+    return an;
+}
+void wm_analysis_fill(zvx_ctx* c, const WmPlan& wp, const zvx_watermark_params* p, const WmAnalysis& an, WmDetectArgs& a) {
+    const DnGeom& g = wp.g;
+    const zvx_ctx::DnTables& tb = dn_tables(c, g);
+    a.B = (int)an.tab.size(); a.n_fft = g.n_fft; a.log2n = g.log2n; a.hop = g.hop; a.pad = g.pad; a.Fmax = (int)an.Fmax;
+    a.twid = tb.twid; a.win = tb.win;
+    a.k_lo = wp.k_lo; a.KB = p->band_bins; a.J = wp.J; a.TB = p->block_frames; a.P = p->period_blocks;
+    a.WF = an.WF; a.NW = an.NWp;
+}
+// -> the device results in the caller's buffer `res_name`: res_pad bytes of window scores, then as many of window offsets
+char* wm_analysis_rows(zvx_ctx* c, WmAnalysis& an, const float* x, int Nmax, const char* res_name, size_t res_pad, WmDetectArgs& a) {
+    const int B = (int)an.tab.size();
+    float* d = c->fbuf("wm.d", std::max<size_t>(an.d_floats, 1));
+    char* res = (char*)c->buf(res_name, 2 * res_pad);
+    a.win_score = (float*)res; a.win_offset = (int*)(res + res_pad);
+    for (int b = 0; b < B; b++) { an.tab[(size_t)b].x = x + (size_t)b * Nmax; an.tab[(size_t)b].d = d + an.d_at[(size_t)b]; }
+    WmDetectRow* tab_d = (WmDetectRow*)c->buf("wm.rows", (size_t)B * sizeof(WmDetectRow));
+    c->upload(tab_d, an.tab.data(), (size_t)B * sizeof(WmDetectRow));
+    a.rows = tab_d;
+    return res;
+}
+// the best window of row b under key k (the first of equals; a row without windows: 0 at offset 0, window 0)
+struct WmBest { float score = 0.f; int32_t offset = 0, window = 0; };
+WmBest wm_best_window(const WmAnalysis& an, const float* hs, const int32_t* ho, int b, int K, int k) {
+    WmBest r;
+    for (int w = 0, nw = an.windows(b); w < nw; w++) {
+        const size_t at = ((size_t)b * an.NWp + w) * K + k;
+        if (w == 0 || hs[at] > r.score) { r.score = hs[at]; r.offset = ho[at]; r.window = w; }
+    }
+    return r;
 }
 
 // zvx_watermark_detect: every check before anything is allocated, uploaded or queued; the call's one wait brings every window's result over
@@ -3311,60 +3362,36 @@ void do_watermark_detect(zvx_ctx* c, const float* in, const int32_t* nsamples, i
     if (window_frames < 0 || window_frames == 1) fail(ZVX_E_INVALID, "%s: window_frames %d (0: the row; otherwise at least 2)", who, window_frames);
     if (!win_score != !win_offset) fail(ZVX_E_INVALID, "%s: win_score and win_offset go together (one of them is NULL)", who);
     if (NWmax < 0) fail(ZVX_E_INVALID, "%s: NWmax %d is negative", who, NWmax);
-    int NW = 0;
-    long Fmax = 0;
-    double frames = 0;
-    size_t d_floats = 0;
-    const int JD = wp.J - 2;
-    std::vector<WmDetectRow> tab((size_t)B);
-    std::vector<size_t> d_at((size_t)B);
     for (int b = 0; b < B; b++) {
-        if (nsamples[b] > 0 && nsamples[b] < dn_min_samples(g))
-            fail(ZVX_E_INVALID, "%s: row %d has %d samples; a row that is not empty needs at least %d (zvx_melspec's conditions)", who, b, nsamples[b], dn_min_samples(g));
-        const int F = dn_frames(g, nsamples[b]), nw = wm_windows(F, window_frames);
+        stft_len_check(who, g, b, nsamples[b]);
+        const int nw = wm_windows(dn_frames(g, nsamples[b]), window_frames);
         if (win_score && nw > NWmax) fail(ZVX_E_BUFFER, "%s: row %d has %d windows, NWmax is %d", who, b, nw, NWmax);
-        tab[(size_t)b] = WmDetectRow{nullptr, nullptr, nsamples[b], F};
-        d_at[(size_t)b] = d_floats; d_floats += (size_t)F * JD;
-        NW = std::max(NW, nw); Fmax = std::max<long>(Fmax, F); frames += F;
     }
-    const int NWp = std::max(NW, 1);
-    const size_t res_each = (size_t)B * NWp * 4, res_pad = (res_each + 255) & ~(size_t)255;
+    WmAnalysis an = wm_analysis(wp, nsamples, B, window_frames);
+    const size_t res_pad = an.res_pad(1);
     char* host = (char*)c->join_pinned(2 * res_pad);
     const float* x = rows_to_device(c, "wm", in, B, Nmax, flags);
     WmDetectArgs a{};
-    const zvx_ctx::DnTables& tb = dn_tables(c, g);
-    a.B = B; a.n_fft = g.n_fft; a.log2n = g.log2n; a.hop = g.hop; a.pad = g.pad; a.Fmax = (int)Fmax;
-    a.twid = tb.twid; a.win = tb.win;
+    wm_analysis_fill(c, wp, p, an, a);
     a.sign = wm_sign_table(c, p, wp.J);
-    a.k_lo = wp.k_lo; a.KB = p->band_bins; a.J = wp.J; a.TB = p->block_frames; a.P = p->period_blocks;
-    a.WF = window_frames; a.NW = NWp;
-    float* d = c->fbuf("wm.d", std::max<size_t>(d_floats, 1));
-    char* res = (char*)c->buf("wm.res", 2 * res_pad);
-    a.win_score = (float*)res; a.win_offset = (int*)(res + res_pad);
-    for (int b = 0; b < B; b++) { tab[(size_t)b].x = x + (size_t)b * Nmax; tab[(size_t)b].d = d + d_at[(size_t)b]; }
-    WmDetectRow* tab_d = (WmDetectRow*)c->buf("wm.rows", (size_t)B * sizeof(WmDetectRow));
-    c->upload(tab_d, tab.data(), (size_t)B * sizeof(WmDetectRow));
-    a.rows = tab_d;
+    const char* res = wm_analysis_rows(c, an, x, Nmax, "wm.res", res_pad, a);
     {
         TagScope scope(c, "post.wmdetect");
-        c->timed(dn_fft_flops(g, frames, 1), 4.0 * ri.n_sum + 8.0 * frames * JD, [&] {
+        c->timed(dn_fft_flops(g, an.frames, 1), 4.0 * ri.n_sum + 8.0 * an.frames * (wp.J - 2), [&] {
             launch_wm_bands(a, c->stream);
-            if (NW > 0) launch_wm_search(a, c->stream);
+            if (an.NW > 0) launch_wm_search(a, c->stream);
         });
     }
-    if (NW > 0) HIPCHK(hipMemcpyAsync(host, res, 2 * res_pad, hipMemcpyDeviceToHost, c->stream));
+    if (an.NW > 0) HIPCHK(hipMemcpyAsync(host, res, 2 * res_pad, hipMemcpyDeviceToHost, c->stream));
     c->sync();                                               // the call's one wait
     const float* hs = (const float*)host;
     const int32_t* ho = (const int32_t*)(host + res_pad);
     for (int b = 0; b < B; b++) {
-        const int nw = wm_windows(tab[(size_t)b].F, window_frames);
-        float best = 0.f; int32_t bo = 0, bw = 0;
-        for (int w = 0; w < nw; w++) {
-            const float z = hs[(size_t)b * NWp + w];
-            if (w == 0 || z > best) { best = z; bo = ho[(size_t)b * NWp + w]; bw = w; }
-            if (win_score) { win_score[(size_t)b * NWmax + w] = z; win_offset[(size_t)b * NWmax + w] = ho[(size_t)b * NWp + w]; }
+        const WmBest r = wm_best_window(an, hs, ho, b, 1, 0);
+        score[b] = r.score; offset[b] = r.offset; window[b] = r.window;
+        for (int w = 0; win_score && w < an.windows(b); w++) {
+            win_score[(size_t)b * NWmax + w] = hs[(size_t)b * an.NWp + w]; win_offset[(size_t)b * NWmax + w] = ho[(size_t)b * an.NWp + w];
         }
-        score[b] = best; offset[b] = bo; window[b] = bw;
     }
 }
 
@@ -3384,72 +3411,43 @@ void do_watermark_identify(zvx_ctx* c, const float* in, const int32_t* nsamples,
     if (!score || !offset || !window || !best) fail(ZVX_E_INVALID, "%s: score, offset, window or best is NULL", who);
     if (K < 1) fail(ZVX_E_INVALID, "%s: K %d must be at least 1", who, K);
     if (window_frames < 0 || window_frames == 1) fail(ZVX_E_INVALID, "%s: window_frames %d (0: the row; otherwise at least 2)", who, window_frames);
-    const int P = p->period_blocks, J = wp.J, JD = J - 2;
-    for (int b = 0; b < B; b++)
-        if (nsamples[b] > 0 && nsamples[b] < dn_min_samples(g))
-            fail(ZVX_E_INVALID, "%s: row %d has %d samples; a row that is not empty needs at least %d (zvx_melspec's conditions)", who, b, nsamples[b], dn_min_samples(g));
+    const int P = p->period_blocks, J = wp.J;
+    for (int b = 0; b < B; b++) stft_len_check(who, g, b, nsamples[b]);
     if ((long)K * P * J > WM_IDENTIFY_TABLE_BYTES)
         fail(ZVX_E_UNSUPPORTED, "%s: K P J = %d x %d x %d = %lld signs in the tables (at most %ld)", who, K, P, J, (long long)K * P * J, WM_IDENTIFY_TABLE_BYTES);
     if (K > WM_IDENTIFY_MAX_KEYS) fail(ZVX_E_UNSUPPORTED, "%s: K %d (at most %d keys a call)", who, K, WM_IDENTIFY_MAX_KEYS);
-    int NW = 0;
-    long Fmax = 0;
-    double frames = 0;
-    size_t d_floats = 0;
-    std::vector<WmDetectRow> tab((size_t)B);
-    std::vector<size_t> d_at((size_t)B);
-    for (int b = 0; b < B; b++) {
-        const int F = dn_frames(g, nsamples[b]);
-        tab[(size_t)b] = WmDetectRow{nullptr, nullptr, nsamples[b], F};
-        d_at[(size_t)b] = d_floats; d_floats += (size_t)F * JD;
-        NW = std::max(NW, wm_windows(F, window_frames)); Fmax = std::max<long>(Fmax, F); frames += F;
-    }
-    const int NWp = std::max(NW, 1);
-    const size_t res_each = (size_t)B * NWp * K * 4, res_pad = (res_each + 255) & ~(size_t)255;
+    WmAnalysis an = wm_analysis(wp, nsamples, B, window_frames);
+    const size_t res_pad = an.res_pad(K);
     char* host = (char*)c->join_pinned(2 * res_pad);
     const float* x = rows_to_device(c, "wm", in, B, Nmax, flags);
     WmKeysArgs ka{};
     WmDetectArgs& a = ka.d;
-    const zvx_ctx::DnTables& tb = dn_tables(c, g);
-    a.B = B; a.n_fft = g.n_fft; a.log2n = g.log2n; a.hop = g.hop; a.pad = g.pad; a.Fmax = (int)Fmax;
-    a.twid = tb.twid; a.win = tb.win;
-    a.k_lo = wp.k_lo; a.KB = p->band_bins; a.J = J; a.TB = p->block_frames; a.P = P;
-    a.WF = window_frames; a.NW = NWp;
+    wm_analysis_fill(c, wp, p, an, a);
     ka.K = K;
     unsigned long long* keys_d = (unsigned long long*)c->buf("wm.keys", (size_t)K * 8);
     unsigned* signs_d = (unsigned*)c->buf("wm.signbits", (size_t)K * P * wm_sign_words(J) * sizeof(unsigned));      // packed: 32 signs a word
-    float* d = c->fbuf("wm.d", std::max<size_t>(d_floats, 1));
-    char* res = (char*)c->buf("wm.kres", 2 * res_pad);
     ka.sign_bits = signs_d;
-    a.win_score = (float*)res; a.win_offset = (int*)(res + res_pad);
-    for (int b = 0; b < B; b++) { tab[(size_t)b].x = x + (size_t)b * Nmax; tab[(size_t)b].d = d + d_at[(size_t)b]; }
-    WmDetectRow* tab_d = (WmDetectRow*)c->buf("wm.rows", (size_t)B * sizeof(WmDetectRow));
     static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "keys are uploaded as they are");
     c->upload(keys_d, keys, (size_t)K * 8);
-    c->upload(tab_d, tab.data(), (size_t)B * sizeof(WmDetectRow));
-    a.rows = tab_d;
+    const char* res = wm_analysis_rows(c, an, x, Nmax, "wm.kres", res_pad, a);
     {
         TagScope scope(c, "post.wmidentify");
-        c->timed(dn_fft_flops(g, frames, 1), 4.0 * ri.n_sum + 8.0 * frames * JD + 4.0 * K * P * wm_sign_words(J), [&] {
+        c->timed(dn_fft_flops(g, an.frames, 1), 4.0 * ri.n_sum + 8.0 * an.frames * (J - 2) + 4.0 * K * P * wm_sign_words(J), [&] {
             launch_wm_signs(keys_d, signs_d, K, P, J, true, c->stream);
             launch_wm_bands(a, c->stream);
-            if (NW > 0) launch_wm_search_keys(ka, c->stream);
+            if (an.NW > 0) launch_wm_search_keys(ka, c->stream);
         });
     }
-    if (NW > 0) HIPCHK(hipMemcpyAsync(host, res, 2 * res_pad, hipMemcpyDeviceToHost, c->stream));
+    if (an.NW > 0) HIPCHK(hipMemcpyAsync(host, res, 2 * res_pad, hipMemcpyDeviceToHost, c->stream));
     c->sync();                                               // the call's one wait
     const float* hs = (const float*)host;
     const int32_t* ho = (const int32_t*)(host + res_pad);
     for (int b = 0; b < B; b++) {
-        const int nw = wm_windows(tab[(size_t)b].F, window_frames);
         int32_t kb = 0;
         for (int k = 0; k < K; k++) {
-            float bs = 0.f; int32_t bo = 0, bw = 0;
-            for (int w = 0; w < nw; w++) {
-                const size_t at = ((size_t)b * NWp + w) * K + k;
-                if (w == 0 || hs[at] > bs) { bs = hs[at]; bo = ho[at]; bw = w; }
-            }
-            score[(size_t)b * K + k] = bs; offset[(size_t)b * K + k] = bo; window[(size_t)b * K + k] = bw;
-            if (bs > score[(size_t)b * K + kb]) kb = k;
+            const WmBest r = wm_best_window(an, hs, ho, b, K, k);
+            score[(size_t)b * K + k] = r.score; offset[(size_t)b * K + k] = r.offset; window[(size_t)b * K + k] = r.window;
+            if (r.score > score[(size_t)b * K + kb]) kb = k;
         }
         best[b] = kb;
     }
@@ -3486,14 +3484,11 @@ void do_resample_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int 
     }
     if (out_stride < rw.cnt_max) fail(ZVX_E_BUFFER, "%s: out_stride %lld < %ld samples, the longest output row", who, (long long)out_stride, rw.cnt_max);
     const zvx_ctx::RsBank& bk = rs_bank(c, L, M);
-    RowsReturn ret(c, B, 0, false, true, rw.cnt_max, flags);
-    const float* x = rows_to_device(c, "rs", in, B, Nmax, flags);
-    long out_bs = 0;
-    void* od = ret.out_rows("rs.out", out, out_stride, &out_bs);
-    const std::vector<PostRow> rows = post_rows(x, Nmax, od, out_bs, ret.ss, nsamples, rw, B);
-    run_resample_rows(c, bk, rows.data(), B, (flags & ZVX_PCM16) ? 1 : 0);
+    post_call(c, "rs", in, nsamples, B, Nmax, out, out_stride, true, flags, rw, 0, false, [&](const PostRow* rows) {
+        run_resample_rows(c, bk, rows, B, (flags & ZVX_PCM16) ? 1 : 0);
+        return nullptr;
+    });
     if (out_len) for (int b = 0; b < B; b++) out_len[b] = rw.cnt[(size_t)b];
-    ret.finish(nullptr, out, out_stride, rw.cnt.data(), flags);
 }
 
 constexpr int DN_BIAS_FRAMES = 88;      // mel frames of silence the bias is measured on

@@ -136,16 +136,15 @@ def synthesize_long(tts, text, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20,
         kw = dict(frame=frame, hop=hp, top_db=float(trim_db), keep=keep, fade=fade)
         lengths = mel_len.astype(np.int64) * hop
         lufs, gain = [None] * N, [None] * N
-        if denoise is not None:                                  # ONE call over all rows, in place, directly behind the vocoder's rows
-            ctx.denoise_device(buf, lengths, stride, bias, no_sync=True, **denoise)
-        if watermark is not None:                                # ONE call over all rows, in place, between denoise and normalise
-            ctx.watermark_device(buf, lengths, stride, no_sync=True, **watermark)
-        if loudness is not None:                                 # ONE call over all rows, in place, behind the queued synthesis calls
-            lufs, _, gain = ctx.normalize_device(buf, lengths, stride, loudness, peak_ceiling=0.0 if lim else peak_ceiling(peak_db),
-                                                 common=LOUDNESS_MODES[loudness_mode], rate=native)
-            lufs, gain = [float(v) for v in lufs], [float(v) for v in gain]
-        if lim:                                                  # likewise, behind the gain: which then has no peak ceiling
-            _, min_gain = ctx.limit_device(buf, lengths, stride, rate=native, **lim)
+        # every step is ONE call over all rows, in place, behind the queued synthesis calls; under a limiter the gain has no peak ceiling
+        loud, limited = tts.model.post_chain_device(
+            buf, lengths, stride, denoise=None if denoise is None else dict(denoise, bias=bias), watermark=watermark,
+            loudness=None if loudness is None else dict(target=loudness, peak_ceiling=0.0 if lim else peak_ceiling(peak_db),
+                                                        common=LOUDNESS_MODES[loudness_mode]), limiter=lim, rate=native)
+        if loud is not None:
+            lufs, gain = [float(v) for v in loud[0]], [float(v) for v in loud[2]]
+        if lim:
+            min_gain = limited[1]
         if out_rate == native and report and not pcm16:          # the joined row stays on the device until it is measured
             cap = int(lengths.sum()) + int(sum(gaps))
             joined = ctx.dev_alloc(max(cap, 1) * 4)

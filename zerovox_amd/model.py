@@ -165,6 +165,18 @@ class ZeroVox:
                                                      ctx.true_peak_device(ptr, [n], max(n, 1), rate=rate)[0])
         return self.last_report
 
+    def post_chain_device(self, buf, lengths, stride, *, denoise=None, watermark=None, loudness=None, limiter=None, rate=None):
+        """Denoise, watermark, normalise, limit, in this order and IN PLACE over device rows [B][stride] f32 at `buf` (at `rate` Hz), each
+        None or the keywords of its Context.*_device call (denoise with its bias).  The first two only queue, the last two wait for their
+        figures -> (normalize_device's (lufs, peak, gain) or None, limit_device's (peak_in, min_gain) or None)."""
+        ctx = self._ctx
+        if denoise is not None:
+            ctx.denoise_device(buf, lengths, stride, no_sync=True, **denoise)
+        if watermark is not None:
+            ctx.watermark_device(buf, lengths, stride, no_sync=True, **watermark)
+        return (None if loudness is None else ctx.normalize_device(buf, lengths, stride, rate=rate, **loudness),
+                None if limiter is None else ctx.limit_device(buf, lengths, stride, rate=rate, **limiter))
+
     def _spkemb(self, x):
         """ResNetSE34V2.forward: x [B, Tr, 80] -> [B, 1, hidden] (ResNetSE34V2.py:176-212)."""
         x = np.asarray(x, np.float32)
@@ -212,11 +224,9 @@ class ZeroVox:
         return wav, ml, logd, np.ascontiguousarray(mel[0, :ml].T)
 
     def _vocode_normalized(self, mel_len, pad_to, loudness, limiter=None, denoise=None, report=False, watermark=None):
-        """The vocoder writes its row on the device at the model's rate, zvx_denoise takes denoise["strength"] times the bias off it in
-        place (queued behind the vocoder: stream order is the fence), zvx_watermark lays the keyed mark on it in place, zvx_normalize brings it to loudness["target"] in place,
-        zvx_limit holds it under limiter["ceiling"] in place, an output rate converts it,
-        and only then the row comes to the host.  Every step may be absent.  self.last_loudness reports dict(lufs, peak, gain),
-        self.last_limit dict(peak_in, min_gain); with `report` self.last_report is the finished row's LoudnessReport, measured on the
+        """The vocoder writes its row on the device at the model's rate, post_chain_device runs over it in place (queued behind the vocoder:
+        stream order is the fence), an output rate converts it, and only then the row comes to the host.  Every step may be absent.
+        self.last_loudness reports dict(lufs, peak, gain), self.last_limit dict(peak_in, min_gain); with `report` self.last_report is the finished row's LoudnessReport, measured on the
         device buffer unless an output rate converts it (the converted row is then measured as it arrives)."""
         ctx = self._ctx
         n = int(mel_len[0]) * self._hop_length
@@ -225,16 +235,11 @@ class ZeroVox:
         buf = ctx.dev_alloc(n * 4)
         try:
             ctx.vocode_device(mel_len, np.array([pad_to], np.int32), buf, n, native_rate=True, no_sync=True)
-            if denoise is not None:
-                ctx.denoise_device(buf, [n], n, no_sync=True, **denoise)
-            if watermark is not None:
-                ctx.watermark_device(buf, [n], n, no_sync=True, **watermark)
-            if loudness is not None:
-                lufs, peak, gain = ctx.normalize_device(buf, [n], n, rate=native, **loudness)
-                self.last_loudness = dict(lufs=float(lufs[0]), peak=float(peak[0]), gain=float(gain[0]))
-            if limiter is not None:
-                peak_in, min_gain = ctx.limit_device(buf, [n], n, rate=native, **limiter)
-                self.last_limit = dict(peak_in=float(peak_in[0]), min_gain=float(min_gain[0]))
+            loud, lim = self.post_chain_device(buf, [n], n, denoise=denoise, watermark=watermark, loudness=loudness, limiter=limiter, rate=native)
+            if loud is not None:
+                self.last_loudness = dict(lufs=float(loud[0][0]), peak=float(loud[1][0]), gain=float(loud[2][0]))
+            if lim is not None:
+                self.last_limit = dict(peak_in=float(lim[0][0]), min_gain=float(lim[1][0]))
             if out_rate == native:
                 if report:
                     self.loudness_report_device(buf, n, native)

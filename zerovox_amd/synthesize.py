@@ -23,6 +23,14 @@ DEFAULT_TTS_MODEL_NAME_DE = "tts_de_zerovox2_medium_3_styledec"
 DEFAULT_REFAUDIO = "en_kevin.wav"
 
 
+def _float_row(wav):
+    """one waveform, float or int16 PCM (read as the samples it encodes, / 32760) -> a float32 row"""
+    wav = np.asarray(wav)
+    if wav.dtype == np.int16:
+        wav = wav.astype(np.float32) / np.float32(32760.0)
+    return np.asarray(wav, np.float32).reshape(-1)
+
+
 class ZeroVoxTTS:
 
     @staticmethod
@@ -278,11 +286,14 @@ class ZeroVoxTTS:
         watermark.THRESHOLD).  Short clips cut to the telephone band are not reliably detectable; nothing is claimed about lossy
         codecs, time-stretching or deliberate removal."""
         from . import watermark as wm
-        p = wm.params({"key": key, **params})
-        wav = np.asarray(wav)
-        if wav.dtype == np.int16:
-            wav = wav.astype(np.float32) / np.float32(32760.0)
-        wav = np.asarray(wav, np.float32).reshape(-1)
+        rows, p = self._watermark_search_args(wav, sampling_rate, wm.params({"key": key, **params}), window_frames)
+        return self._model.ctx.watermark_detect(rows, p.pop("key"), threshold=threshold, **p)[0]
+
+    def _watermark_search_args(self, wav, sampling_rate, p, window_frames):
+        """what detect_watermark and identify_watermark make of their arguments: the waveform as one float row at the model's rate, and the
+        checked parameters p with hi_hz lowered where the rate was converted, depth_db dropped and window_frames set -> ([row], p)"""
+        from . import watermark as wm
+        wav = _float_row(wav)
         ctx = self._model.ctx
         native = ctx.get_int("sampling_rate")
         rate = native if sampling_rate is None else int(sampling_rate)
@@ -292,8 +303,8 @@ class ZeroVoxTTS:
             p["hi_hz"] = min(p["hi_hz"], 0.45 * min(rate, native))
             wm.check(p)
         p.pop("depth_db")
-        return ctx.watermark_detect([wav], p.pop("key"), window_frames=wm.WINDOW_FRAMES if window_frames is None else int(window_frames),
-                                    threshold=threshold, **p)[0]
+        p["window_frames"] = wm.WINDOW_FRAMES if window_frames is None else int(window_frames)
+        return [wav], p
 
     def identify_watermark(self, wav, keys, sampling_rate=None, *, window_frames=None, threshold=None, **params):
         """Which of the candidate `keys` marked this audio?  wav and sampling_rate as detect_watermark's (a waveform at another rate is
@@ -310,22 +321,9 @@ class ZeroVoxTTS:
         p = None
         for k in keys:                                      # every key goes through the checks of the one-key call
             p = wm.params({"key": k, **params})
-        wav = np.asarray(wav)
-        if wav.dtype == np.int16:
-            wav = wav.astype(np.float32) / np.float32(32760.0)
-        wav = np.asarray(wav, np.float32).reshape(-1)
-        ctx = self._model.ctx
-        native = ctx.get_int("sampling_rate")
-        rate = native if sampling_rate is None else int(sampling_rate)
-        if rate != native:
-            out, out_len = ctx.resample([wav], rate, native)
-            wav = out[0, :out_len[0]]
-            p["hi_hz"] = min(p["hi_hz"], 0.45 * min(rate, native))
-            wm.check(p)
-        p.pop("depth_db")
+        rows, p = self._watermark_search_args(wav, sampling_rate, p, window_frames)
         p.pop("key")
-        return ctx.watermark_identify([wav], keys, window_frames=wm.WINDOW_FRAMES if window_frames is None else int(window_frames),
-                                      threshold=threshold, **p)[0]
+        return self._model.ctx.watermark_identify(rows, keys, threshold=threshold, **p)[0]
 
     @staticmethod
     def _pitch_keywords(pitch_report):
@@ -348,11 +346,8 @@ class ZeroVoxTTS:
         int16 PCM is read as the samples it encodes (/ 32760).  Also kept as ``last_pitch_report``."""
         from .pitch import PitchReport, check_keywords
         keywords = check_keywords(keywords)
-        wav = np.asarray(wav)
-        if wav.dtype == np.int16:
-            wav = wav.astype(np.float32) / np.float32(32760.0)
         rate = self.output_rate if sampling_rate is None else int(sampling_rate)
-        stats = self._model.ctx.pitch([np.asarray(wav, np.float32).reshape(-1)], rate=rate, **keywords)
+        stats = self._model.ctx.pitch([_float_row(wav)], rate=rate, **keywords)
         self._last_pitch_report = PitchReport.from_stats(stats)
         return self._last_pitch_report
 
@@ -367,10 +362,7 @@ class ZeroVoxTTS:
         peak (include/zvx.h, zvx_loudness_stats) and the 4x oversampled true peak (zvx_true_peak) -> report.LoudnessReport, whose
         ``meets(target, tolerance, max_true_peak_db, max_lra)`` checks it against a delivery specification.  int16 PCM is read as the
         samples it encodes (/ 32760).  Also kept as ``last_report``."""
-        wav = np.asarray(wav)
-        if wav.dtype == np.int16:
-            wav = wav.astype(np.float32) / np.float32(32760.0)
-        return self._model.loudness_report(wav, sampling_rate)
+        return self._model.loudness_report(_float_row(wav), sampling_rate)
 
     @property
     def last_report(self):
