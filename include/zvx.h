@@ -801,8 +801,10 @@ zvx_status zvx_resample_rows(zvx_ctx* ctx, const float* in, const int32_t* nsamp
  * A stream: zerovox_amd/leveler.py plans the windows -- a non-last push emits up to received - RR, the last one everything, the history
  *   before next_out - RL is dropped -- so a levelled stream runs RR samples behind its input (4409 samples, 200 ms, at 22.05 kHz with
  *   the defaults of 3000 ms / 100 ms).  ZeroVox.vocode_stream(level=) puts it between the denoiser and the limiter.
- * Not here: a level stage inside zvx_stream_open / zvx_stream_next_many (zvx_stream_params is ABI: a change of its own on top of
- *   zvx_level_rows), relative gating, a lower bound on the gain, several channels. */
+ * Stream sessions: a level stage inside zvx_stream_open / zvx_stream_next_many is asked for through zvx_stream_open_ex (zvx_stream_stages
+ *   below; zvx_stream_params is ABI and stays as it is): the session plans these same windows inside the library, and
+ *   zvx_stream_next_many levels its sessions of equal parameters through one zvx_level_rows body.
+ * Not here: relative gating, a lower bound on the gain, several channels. */
 typedef struct zvx_level_params {
     float target_lufs;    /* short-term loudness to steer towards, finite, in [-70, 0] */
     float max_gain_db;    /* upper bound on the gain in dB, finite, >= 0 */
@@ -821,15 +823,17 @@ zvx_status zvx_level_rows(zvx_ctx* ctx, const float* in, const int32_t* nsamples
                           const zvx_row_window* win);
 
 /* Stream sessions: chunked vocoding of ONE utterance with the planning inside the library.  A session owns the utterance's mel on the
- * device, vocodes it group by group and runs the new samples device to device through the optional denoiser, limiter and rate conversion;
- * each zvx_stream_next hands out one finished piece with one wait.  It is what ZeroVox.vocode_stream does with three Python planners and
- * up to four host round trips per piece (zerovox_amd/stream.py, denoiser.py, limiter.py, resample.py), moved behind this header; the
- * planners are restated in zerovox_amd/csrc/stream_plan.h (host integer arithmetic, int64 positions).
+ * device, vocodes it group by group and runs the new samples device to device through the optional denoiser, leveler, watermark, limiter
+ * and rate conversion (leveler and watermark: zvx_stream_open_ex); each zvx_stream_next hands out one finished piece with one wait.  It is
+ * what ZeroVox.vocode_stream does with its Python planners and up to one host round trip per stage per piece (zerovox_amd/stream.py,
+ * denoiser.py, leveler.py, watermark.py, limiter.py, resample.py), moved behind this header; the planners are restated in
+ * zerovox_amd/csrc/stream_plan.h (host integer arithmetic, int64 positions).
  * Contract: the concatenation of a session's pieces is bit for bit the concatenation of ZeroVox.vocode_stream(mel, chunk_frames, halo,
- *   chunks_per_call, limiter=, denoise=) on the same context under the same "out_rate", and that equals resample(limit(denoise(plain))),
- *   plain being the concatenation of the stream without post steps and every absent step dropped from the chain.  It follows from three
- *   things: the rows of each vocoder call are the same, in the same batch; the window contract of zvx_denoise_ex / zvx_limit_ex /
- *   zvx_resample_ex holds wherever a stream is cut; the stage order is the same.  Where the pieces are CUT may differ from the Python
+ *   chunks_per_call, limiter=, denoise=, level=, watermark=) on the same context under the same "out_rate", and that equals
+ *   resample(limit(watermark(level(denoise(plain))))) by the whole-signal calls, plain being the concatenation of the stream without post
+ *   steps and every absent step dropped from the chain.  It follows from three things: the rows of each vocoder call are the same, in the
+ *   same batch; the window contract of zvx_denoise_ex / zvx_level_ex / zvx_watermark_ex / zvx_limit_ex / zvx_resample_ex holds wherever a
+ *   stream is cut; the stage order is the same.  Where the pieces are CUT may differ from the Python
  *   stream (a session flags its last group `last` instead of closing with an empty push); their concatenation does not.
  * zvx_stream_open: mel != NULL: [frames][n_mels] f32 on the host, or on the device with ZVX_DEVICE_IN, copied into a buffer of the session
  *   (a host mel may be reused when the call returns).  mel == NULL: utterance 0 of the mel the context holds after zvx_decode, taken with a
@@ -839,16 +843,26 @@ zvx_status zvx_level_rows(zvx_ctx* ctx, const float* in, const int32_t* nsamples
  *   is uploaded here and the context's work buffers of a step (its table, a group's mel rows, the vocoder's rows) are grown to the
  *   session's largest group, so no zvx_stream_next waits for a table of a stage or an allocation of the step's own, and a later
  *   zvx_set_int("out_rate") does not touch an open session.
+ *   zvx_stream_open_ex is zvx_stream_open with two more stages, asked for through zvx_stream_stages (zvx_stream_params is ABI and stays as
+ *   it is): `level` puts the leveler (zvx_level_ex's windows, RL to the left and RR to the right) behind the denoiser, `watermark` the
+ *   keyed embedder (zvx_watermark_ex's windows, reach n_fft - 1) behind the leveler; watermark->key is THIS session's key.  The chain is
+ *   denoise -> level -> watermark -> limit -> rate conversion, the host-planned stream's.  Both structs are copied at open; the FFT tables
+ *   and the work buffers the two bodies take (the leveler's unit powers, partials and row table; the embedder's frames, row table, keys
+ *   and sign tables) are grown here to the session's largest step.  more == NULL, or both pointers NULL, is zvx_stream_open: the same
+ *   buffers, the same pieces, the same launches.
  *   Validation, before anything is allocated (ZVX_E_INVALID, the context stays usable): a NULL ctx / params / out, frames < 2, frames != 0
  *   with a NULL mel, chunk_frames < 1, chunks_per_call outside 1 .. 64, halo < 0, denoise without denoise_bias or the reverse, every check
  *   zvx_denoise and zvx_limit make on their own parameters and bias, frames * hop samples that fail zvx_melspec's length conditions while a
- *   denoiser is asked for, unknown flags.  ZVX_E_UNSUPPORTED: ZVX_PCM16, what the stages themselves call unsupported (W > 4096, n_fft),
- *   a group of more than 2^28 samples.
+ *   denoiser is asked for, unknown flags; zvx_stream_open_ex: a reserved word that is not 0, every check zvx_level and zvx_watermark make
+ *   on their own parameters (a > S, a target_lufs that is not finite, depth_db outside [0, 6], period_blocks outside [1, 256], ...),
+ *   frames * hop samples that fail zvx_melspec's length conditions while a watermark is asked for.  ZVX_E_UNSUPPORTED: ZVX_PCM16, what
+ *   the stages themselves call unsupported (W > 4096, n_fft, S > 600, more than 512 bands), a group of more than 2^28 samples.
  * zvx_stream_next: vocodes exactly one group -- the next chunks_per_call chunks, fewer at the end -- and pushes its samples through the
  *   stages.  Chunk s is vocoded on mel frames [max(0, s - halo), min(frames, s + chunk_frames + halo)), a row of its own in one batch of
  *   the group's rows at the native rate (the rows ZeroVox._vocode_stream_native builds), and only its chunk_frames * hop interior samples
- *   are kept.  The group's interiors, as ONE run of new samples, go through denoiser, then limiter, then rate conversion, each under the
- *   two rules of a stream of its reach (a non-last push emits what is final, the history before next_out - R is dropped); the call that
+ *   are kept.  The group's interiors, as ONE run of new samples, go through denoiser, leveler, watermark, limiter and rate conversion -- those
+ *   the session has, in this order --, each under the two rules of a stream of its reach (a non-last push emits what is final, the history
+ *   before next_out - R is dropped; the leveler: final up to received - RR, dropped before next_out - RL); the call that
  *   vocodes the last group pushes with `last`: everything left comes out in it and *done becomes 1.  *n_out samples, f32 at the session's
  *   output rate, are written to out; *n_out may be 0 while a stage is still filling its reach (out may then be NULL).  After *done:
  *   ZVX_E_STATE.  *n_out is known before anything is queued: capacity < *n_out is ZVX_E_BUFFER with NOTHING consumed -- *n_out is still
@@ -858,7 +872,8 @@ zvx_status zvx_level_rows(zvx_ctx* ctx, const float* in, const int32_t* nsamples
  *   a session creates no stream of its own.  A zvx_stream_next voids the context's intermediates as zvx_vocode_mel does.  Between two
  *   calls of a session the context may serve any other call, calls of other open sessions included: the session's bits do not depend on it.
  * Device state: per stage two buffers [history | new], sized at open from chunks_per_call * chunk_frames * hop plus the history the stage
- *   retains (2 R; 2 half / L + 2 for the conversion) plus the reaches in front of it; a stage writes straight behind the next stage's
+ *   retains (2 R; RL + RR for the leveler of zvx_stream_open_ex, 2 (n_fft - 1) for its watermark; 2 half / L + 2 for the conversion) plus
+ *   the reaches in front of it; a stage writes straight behind the next stage's
  *   history through the per-row form behind its _rows call (device in, device out, no sync); dropping history copies the retained tail
  *   into the stage's other buffer, never over itself -- the drops of all stages of a call are ONE launch over a table, stage tag
  *   "post.stream".  A session's device footprint is its mel, its stage buffers and the staging of a host piece; a group's gathered mel
@@ -871,13 +886,14 @@ zvx_status zvx_level_rows(zvx_ctx* ctx, const float* in, const int32_t* nsamples
  *   zvx_stream_next is the n = 1 case of zvx_stream_next_many below: ONE stepping path serves both, the two differ in their argument
  *   checks and messages only.
  * zvx_stream_info fills, in order and as far as n_info reaches: the stream's total output samples, the output samples emitted so far,
- *   the output rate, the native samples the output runs behind the vocoder (the sum of the stages' reaches: n_fft - 1, 2 W + H,
- *   ceil(half / L) + 1; 0 without any), and max_piece = ceil((chunks_per_call * chunk_frames * hop + delay) * L / M) + 1, an upper bound
+ *   the output rate, the native samples the output runs behind the vocoder (the sum of the stages' reaches: n_fft - 1, the leveler's RR,
+ *   n_fft - 1 again for the watermark, 2 W + H, ceil(half / L) + 1; 0 without any), and max_piece = ceil((chunks_per_call * chunk_frames * hop + delay) * L / M) + 1, an upper bound
  *   on any single *n_out, so that a caller sizes one buffer.
  * zvx_stream_close frees everything (NULL: ZVX_E_INVALID); zvx_destroy closes the context's open sessions first.  Errors of session calls
  *   are reported through zvx_last_error of the session's context.
  * Not here: ZVX_PCM16 pieces, several utterances per session (a session is one utterance; zvx_stream_next_many below steps many sessions
- *   in one call), a streamed loudness gain (it is not known before the last chunk). */
+ *   in one call), a streamed loudness gain (it is not known before the last chunk), per-session caching of the leveler's unit powers
+ *   (the stage keeps RL samples of history instead). */
 typedef struct zvx_stream zvx_stream;
 typedef struct zvx_stream_params {
     int32_t chunk_frames;              /* mel frames per chunk, >= 1 */
@@ -887,8 +903,18 @@ typedef struct zvx_stream_params {
     const float* denoise_bias;         /* host [n_fft / 2 + 1], copied at open; required iff denoise != NULL */
     const zvx_limit_params* limit;     /* NULL: no limiter */
 } zvx_stream_params;
+/* the stages zvx_stream_params has no room for (zvx_watermark_params is defined with zvx_watermark below) */
+struct zvx_watermark_params;
+typedef struct zvx_stream_stages {
+    const zvx_level_params* level;                /* NULL: no leveler */
+    const struct zvx_watermark_params* watermark; /* NULL: no watermark; params->key is THIS session's key */
+    int64_t reserved[2];                          /* 0 */
+} zvx_stream_stages;
 
 zvx_status zvx_stream_open(zvx_ctx* ctx, const float* mel, int frames, const zvx_stream_params* params, int flags, zvx_stream** out);
+/* zvx_stream_open is zvx_stream_open_ex(..., NULL, ...) */
+zvx_status zvx_stream_open_ex(zvx_ctx* ctx, const float* mel, int frames, const zvx_stream_params* params, const zvx_stream_stages* more,
+                              int flags, zvx_stream** out);
 zvx_status zvx_stream_next(zvx_stream* s, void* out, int64_t capacity, int64_t* n_out, int32_t* done, int flags);
 zvx_status zvx_stream_info(const zvx_stream* s, int64_t* info, int n_info);
 zvx_status zvx_stream_close(zvx_stream* s);
@@ -911,14 +937,16 @@ zvx_status zvx_stream_close(zvx_stream* s);
  *   per-row tables (source mel pointer and frame count; source offset, count and destination pointer) and the table of the history drops
  *   are built on the host and uploaded as ONE table through the context's pinned staging, queued like a launch: no host wait.
  * Post stages: batched across the sessions through the per-row forms behind zvx_denoise_rows / zvx_limit_rows / zvx_resample_rows.  The
- *   stages run kind by kind -- all denoisers, then all limiters, then the rate conversions -- on the one stream; a session's chain order
- *   denoise -> limit -> resample is kept.  Within a kind the sessions whose stage has bitwise-equal parameters form one group (the bias
- *   compared by content; the limiter's class is W, oversampling and ceiling; the rate conversion's is the native rate and the session's
- *   captured output rate), and a group is ONE call of the per-row form: its rows are the sessions'
+ *   stages run kind by kind -- all denoisers, then the levelers, the watermarks, the limiters, the rate conversions -- on the one stream; a
+ *   session's chain order denoise -> level -> watermark -> limit -> resample is kept.  Within a kind the sessions whose stage has
+ *   bitwise-equal parameters form one group (the bias compared by content; the leveler's class is its four parameters; the watermark's is
+ *   every parameter BUT the key -- the group is one zvx_watermark_rows body with keys[] = its members' keys in call order, so 64 listeners
+ *   with 64 keys cost one launch group per round; the limiter's class is W, oversampling and ceiling; the rate conversion's is the native
+ *   rate and the session's captured output rate), and a group is ONE call of the per-row form: its rows are the sessions'
  *   [history | new] buffers, each with that session's own window, and each output goes straight behind the next stage's history or to the
  *   session's final destination.  Groups run in the order of their first member, rows within a group in call order, and the bias is
  *   uploaded once per group (the partition is zvx_plan::partition_classes in zerovox_amd/csrc/stream_plan.h).  Each group counts under
- *   "post.denoise" / "post.limit" / "voc.resample" as one timed group with the bytes its sessions' single steps count in sum.  A stage
+ *   "post.denoise" / "post.level" / "post.watermark" / "post.limit" / "voc.resample" as one timed group with the bytes its sessions' single steps count in sum.  A stage
  *   that emits nothing in this call takes no part.  The history drops of all stages of all sessions are ONE launch over a
  *   table of (source, destination, count), each retained tail into its stage's other buffer, under the stage tag "post.stream".
  *   zvx_stream_next is this same path with n = 1 (a group of one row per stage); that a row's bits do not depend on its company is the
@@ -1044,7 +1072,9 @@ void       zvx_comm_destroy(zvx_ctx* ctx);
  *   The LARGEST score over wrong keys grows with the number of keys tried.  The default threshold of zerovox_amd/watermark.py (5.5) was
  *   measured over 256 wrong keys; nothing is measured beyond that, and a caller who tries thousands of keys has to judge by the margin
  *   between the best and the second-best score as well.
- * Not here: stream sessions (zvx_stream_params has no watermark stage); robustness against lossy codecs, time-stretching
+ * Stream sessions: zvx_stream_open_ex takes these parameters, key included, as a session's watermark stage (zvx_stream_stages); sessions
+ *   that differ in their key alone are marked by ONE zvx_watermark_rows body per zvx_stream_next_many.
+ * Not here: robustness against lossy codecs, time-stretching
  *   or deliberate removal; whether the mark is inaudible on a real checkpoint -- none of these is measured, and nothing here claims them. */
 typedef struct zvx_watermark_params {
     uint64_t key;            /* the secret */

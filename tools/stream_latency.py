@@ -14,7 +14,12 @@
    python tools/stream_latency.py --level LUFS [--denoise S --peak-db DB] [out.json]   -> the same stream WITH and WITHOUT the windowed leveler
    (zvx_level_ex towards LUFS, 3000 ms window, 100 ms look-ahead): first piece, all pieces, the median piece gap, the samples the levelled
    stream runs behind (leveler.reach: RR) and whether the pieces equal zvx_level of the whole stream bit for bit; with --denoise and
-   --peak-db as well also the whole chain, limit(level(denoise(stream)))."""
+   --peak-db as well also the whole chain, limit(level(denoise(stream))).  With --resident the levelled chains are also run by a session
+   with a level stage (zvx_stream_open_ex).
+   python tools/stream_latency.py --watermark KEY [--level LUFS] [--resident] [out.json]   -> the same stream marked with KEY window by window
+   (zvx_watermark_ex, the embedder's defaults), behind the leveler where --level is given: first piece, all pieces, the median piece gap and
+   whether the pieces equal the whole-signal calls bit for bit; with --resident also the session with those stages.
+   --chunks 16,64 restricts the chunk sizes (default: 16,32,64,128,256)."""
 import argparse, json, os, sys, time
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -28,6 +33,8 @@ ap.add_argument("--limiter-ms", type=float, default=5.0, metavar="MS")
 ap.add_argument("--denoise", type=float, default=None, metavar="S", help="also time the stream denoised at this strength")
 ap.add_argument("--resident", action="store_true", help="also time every chain run by a stream session of the library")
 ap.add_argument("--level", type=float, default=None, metavar="LUFS", help="also time the stream levelled towards this short-term loudness")
+ap.add_argument("--watermark", type=lambda v: int(v, 0), default=None, metavar="KEY", help="also time the stream marked with this key (behind the leveler with --level)")
+ap.add_argument("--chunks", default="16,32,64,128,256", help="the chunk sizes to time, in frames")
 args = ap.parse_args()
 
 cfg = zcfg.medium_modelcfg("styletts"); sd = zw.tts_state_dict(cfg, 0)
@@ -59,10 +66,11 @@ def piece_gap(make_stream, n=5):
     return float(np.median(gaps)) * 1e3 if gaps else 0.0
 
 
-def resident(cf, host_planned, **kw):
+def resident(cf, host_planned, limiter=None, denoise=None, level=None, watermark=None):
     """the figures of one chain run by a stream session, and whether it hands out the host-planned stream's bits"""
     def make():
-        return model.vocode_stream(mel, chunk_frames=cf, resident=True, **kw)
+        return iter(ctx.stream_open(mel, chunk_frames=cf, halo=STREAM_HALO, denoise=denoise, bias=model.denoise_bias if denoise else None,
+                                    limit=limiter, **ZeroVox._session_stages(level, watermark)))
     got = np.concatenate(list(make()))
     return {"first_piece_ms": round(best(lambda: next(iter(make()))), 3), "all_pieces_ms": round(best(lambda: list(make()), n=5), 3),
             "piece_gap_ms": round(piece_gap(make), 3),
@@ -71,7 +79,7 @@ def resident(cf, host_planned, **kw):
 
 res = {"workload": f"one {L}-frame mel ({L * 256 / 22050:.2f} s of audio), HiFi-GAN V1 bf16, batch 1, halo {STREAM_HALO} frames per side",
        "whole_utterance_ms": best(lambda: ctx.vocode_mel(mel[None], np.array([L], np.int32))), "chunks": []}
-for cf in (16, 32, 64, 128, 256):
+for cf in [int(v) for v in args.chunks.split(",")]:
     got = np.concatenate(list(model.vocode_stream(mel, chunk_frames=cf)))
     first = best(lambda: next(iter(model.vocode_stream(mel, chunk_frames=cf))))
     total = best(lambda: list(model.vocode_stream(mel, chunk_frames=cf)), n=5)
@@ -141,6 +149,8 @@ for cf in (16, 32, 64, 128, 256):
             "all_pieces_ms": round(best(lambda: list(model.vocode_stream(mel, chunk_frames=cf, level=lvl)), n=5), 3),
             "piece_gap_ms": round(piece_gap(lambda: model.vocode_stream(mel, chunk_frames=cf, level=lvl)), 3),
             "bit_equal_to_whole_level": bool(np.array_equal(levelled.view(np.uint32), want_lvl.view(np.uint32)))}
+        if args.resident:
+            res["chunks"][-1]["levelled"]["resident"] = resident(cf, levelled, level=lvl)
         if args.denoise is not None and args.peak_db is not None:
             chain = dict(denoise=den, level=lvl, limiter=lim)
             all3 = np.concatenate(list(model.vocode_stream(mel, chunk_frames=cf, **chain)))
@@ -150,6 +160,26 @@ for cf in (16, 32, 64, 128, 256):
                 "all_pieces_ms": round(best(lambda: list(model.vocode_stream(mel, chunk_frames=cf, **chain)), n=5), 3),
                 "piece_gap_ms": round(piece_gap(lambda: model.vocode_stream(mel, chunk_frames=cf, **chain)), 3),
                 "bit_equal_to_limit_of_level_of_denoise": bool(np.array_equal(all3.view(np.uint32), want3.view(np.uint32)))}
+            if args.resident:
+                res["chunks"][-1]["denoised_levelled_limited"]["resident"] = resident(cf, all3, denoise=den, level=lvl, limiter=lim)
+    if args.watermark is not None:
+        from zerovox_amd import watermark as WM
+        wm = WM.params(args.watermark)
+        lvl_w = dict(target=float(args.level), window_ms=3000.0, lookahead_ms=100.0) if args.level is not None else None
+        chain = dict(watermark=wm, **({} if lvl_w is None else dict(level=lvl_w)))
+        marked = np.concatenate(list(model.vocode_stream(mel, chunk_frames=cf, **chain)))
+        before = whole if lvl_w is None else ctx.level([whole], rate=ctx.get_int("sampling_rate"), **lvl_w)[0][0]
+        want_wm = ctx.watermark([before], **wm)[0]
+        if "piece_gap_ms" not in res["chunks"][-1]:
+            res["chunks"][-1]["piece_gap_ms"] = round(piece_gap(lambda: model.vocode_stream(mel, chunk_frames=cf)), 3)
+        name = "marked" if lvl_w is None else "levelled_marked"
+        res["chunks"][-1][name] = {
+            "first_piece_ms": round(best(lambda: next(iter(model.vocode_stream(mel, chunk_frames=cf, **chain)))), 3),
+            "all_pieces_ms": round(best(lambda: list(model.vocode_stream(mel, chunk_frames=cf, **chain)), n=5), 3),
+            "piece_gap_ms": round(piece_gap(lambda: model.vocode_stream(mel, chunk_frames=cf, **chain)), 3),
+            "bit_equal_to_whole_calls": bool(np.array_equal(marked.view(np.uint32), want_wm.view(np.uint32)))}
+        if args.resident:
+            res["chunks"][-1][name]["resident"] = resident(cf, marked, **chain)
     print(res["chunks"][-1], flush=True)
 print(json.dumps(res))
 if args.out:

@@ -1,7 +1,8 @@
 """What stepping many stream sessions in one call buys (include/zvx.h: zvx_stream_next_many): N listeners, HiFi-GAN V1 bf16, one 896-frame
 mel each, 16-frame chunks, chunks_per_call 1, in one process on one GPU.  A development aid; nothing on the product path imports it.
-   python tools/stream_many_bench.py [--denoise S] [--peak-db DB] [--out-rate HZ] [--sessions 1,4,16,64] [--no-many] [out.json]
-Per chain (the plain chain; with --denoise / --peak-db also denoiser + limiter) and per N, the median time of one ROUND -- every session
+   python tools/stream_many_bench.py [--denoise S] [--peak-db DB] [--level LUFS] [--watermark KEY] [--out-rate HZ] [--sessions 1,4,16,64] [--no-many] [out.json]
+Per chain (the plain chain; with --denoise / --peak-db also denoiser + limiter; with --level and / or --watermark also that chain with the
+leveler (3000 ms window, 100 ms look-ahead) and the watermark between them, session i marked with derive_key(KEY, i)) and per N, the median time of one ROUND -- every session
 advanced by one piece, host pieces, the call's own wait inside --
    (a) by N zvx_stream_next calls, one after the other,
    (b) by one zvx_stream_next_many,
@@ -22,6 +23,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("out", nargs="?", help="write the result as JSON here")
 ap.add_argument("--denoise", type=float, default=None, metavar="S", help="also time the chain denoiser + limiter: the denoiser's strength")
 ap.add_argument("--peak-db", type=float, default=None, metavar="DB", help="... and the limiter's ceiling (dBFS); both or neither")
+ap.add_argument("--level", type=float, default=None, metavar="LUFS", help="also time the chain with a level stage towards this loudness (zvx_stream_open_ex)")
+ap.add_argument("--watermark", type=lambda v: int(v, 0), default=None, metavar="KEY", help="... and / or a watermark stage, session i keyed derive_key(KEY, i)")
 ap.add_argument("--out-rate", type=int, default=0, metavar="HZ", help="open the sessions under this output rate (0: the model's own)")
 ap.add_argument("--sessions", default="1,4,16,64")
 ap.add_argument("--passes", type=int, default=3, help="passes per mode and N (a pass streams every mel to its end)")
@@ -42,13 +45,27 @@ chains = {"plain": {}}
 if args.denoise is not None:
     from zerovox_amd.longform import limit_keywords
     chains["denoise+limit"] = dict(denoise=dict(strength=float(args.denoise), floor=0.0), bias=model.denoise_bias, limit=limit_keywords(True, 5.0, args.peak_db))
+if args.level is not None or args.watermark is not None:
+    from zerovox_amd import watermark as WM
+    more = {}
+    if args.level is not None:
+        more["level"] = dict(target=float(args.level), window_ms=3000.0, lookahead_ms=100.0)
+    if args.watermark is not None:
+        more["watermark"] = lambda i: WM.params(WM.derive_key(args.watermark, i))             # (per session: session_kw below)
+    name = "+".join((["denoise"] if args.denoise is not None else []) + sorted(more) + (["limit"] if args.denoise is not None else []))
+    chains[name] = dict(chains.get("denoise+limit", {}), **more)
+
+
+def session_kw(kw, i):
+    """the keywords session i is opened with: a callable value is that session's own"""
+    return {k: (v(i) if callable(v) else v) for k, v in kw.items()}
 
 
 def run_pass(N, kw, many, profile=False):
     """streams N mels to their ends -> (round times [s], vocoder stage ms per round or None, the concatenated pieces per session)"""
     ctx.set_int("out_rate", args.out_rate)                   # captured by the sessions as they open
     try:
-        streams = [ctx.stream_open(mels[i], chunk_frames=CHUNK, chunks_per_call=1, **kw) for i in range(N)]
+        streams = [ctx.stream_open(mels[i], chunk_frames=CHUNK, chunks_per_call=1, **session_kw(kw, i)) for i in range(N)]
     finally:
         ctx.set_int("out_rate", 0)
     cap = max(s.info()["max_piece"] for s in streams)
@@ -78,7 +95,7 @@ def same(a, b):
     return all(x.shape == y.shape and np.array_equal(x.view(np.uint32), y.view(np.uint32)) for x, y in zip(a, b))
 
 
-TAGS = ("voc.resample", "post.denoise", "post.limit", "post.stream")
+TAGS = ("voc.resample", "post.denoise", "post.level", "post.watermark", "post.limit", "post.stream")
 
 
 def tag_split(N, kw):

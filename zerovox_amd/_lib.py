@@ -28,7 +28,8 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_loudness", "zvx_normalize", "zvx_true_peak", "zvx_limit", "zvx_spkemb_wav", "zvx_limit_ex", "zvx_denoise_bias", "zvx_denoise",
            "zvx_denoise_ex", "zvx_stream_open", "zvx_stream_next", "zvx_stream_info", "zvx_stream_close", "zvx_stream_next_many",
            "zvx_denoise_rows", "zvx_limit_rows", "zvx_resample_rows", "zvx_level", "zvx_level_ex", "zvx_level_rows", "zvx_loudness_stats",
-           "zvx_pitch", "zvx_watermark", "zvx_watermark_ex", "zvx_watermark_detect", "zvx_watermark_rows", "zvx_watermark_identify")
+           "zvx_pitch", "zvx_watermark", "zvx_watermark_ex", "zvx_watermark_detect", "zvx_watermark_rows", "zvx_watermark_identify",
+           "zvx_stream_open_ex")
 ZVX_STREAM_MANY_MAX_SESSIONS, ZVX_STREAM_MANY_MAX_ROWS = 64, 256
 ZVX_COMM_ID_BYTES = 128
 ZVX_LOUD_PER_ROW, ZVX_LOUD_COMMON = 0, 1
@@ -111,6 +112,11 @@ class StreamParams(C.Structure):
     """zvx_stream_params (include/zvx.h)"""
     _fields_ = [("chunk_frames", C.c_int32), ("chunks_per_call", C.c_int32), ("halo", C.c_int32), ("denoise", C.POINTER(DenoiseParams)),
                 ("denoise_bias", C.c_void_p), ("limit", C.POINTER(LimitParams))]
+
+
+class StreamStages(C.Structure):
+    """zvx_stream_stages (include/zvx.h): the stages zvx_stream_open_ex adds to zvx_stream_params"""
+    _fields_ = [("level", C.POINTER(LevelParams)), ("watermark", C.POINTER(WatermarkParams)), ("reserved", C.c_int64 * 2)]
 
 
 class KernelStat(C.Structure):
@@ -197,6 +203,7 @@ def load():
     lib.zvx_level_ex.argtypes = lib.zvx_level.argtypes + [C.c_int64, C.c_int64, C.c_int64, C.c_int]
     lib.zvx_level_rows.argtypes = lib.zvx_level.argtypes + [C.POINTER(RowWindow)]
     lib.zvx_stream_open.argtypes = [vp, vp, C.c_int, C.POINTER(StreamParams), C.c_int, C.POINTER(vp)]
+    lib.zvx_stream_open_ex.argtypes = [vp, vp, C.c_int, C.POINTER(StreamParams), C.POINTER(StreamStages), C.c_int, C.POINTER(vp)]
     lib.zvx_stream_next.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int]
     lib.zvx_stream_info.argtypes = [vp, C.POINTER(C.c_int64), C.c_int]
     lib.zvx_stream_close.argtypes = [vp]
@@ -842,10 +849,14 @@ class Context:
                                                    _ptr(off), _ptr(win), _ptr(best), flags))
         return [wm.identify_result(ka, score[b], off[b], win[b], int(best[b]), threshold) for b in range(B)]
 
-    def stream_open(self, mel=None, frames=0, *, chunk_frames, chunks_per_call=1, halo=16, denoise=None, bias=None, limit=None, flags=0):
+    def stream_open(self, mel=None, frames=0, *, chunk_frames, chunks_per_call=1, halo=16, denoise=None, bias=None, limit=None, flags=0,
+                    level=None, watermark=None):
         """zvx_stream_open -> Stream.  mel: [frames, n_mels] float32 on the host; an int, a device pointer to ``frames`` rows
         (ZVX_DEVICE_IN); or None: the mel the context holds after decode (frames 0).  denoise: None or dict(strength, floor) with ``bias``
-        (denoise_bias()); limit: None or dict(ceiling, window_ms, oversample).  The context's out_rate at this moment is the stream's."""
+        (denoise_bias()); limit: None or dict(ceiling, window_ms, oversample).  The context's out_rate at this moment is the stream's.
+        level: None or level_window's keywords (target, and optionally max_gain_db, window_ms, lookahead_ms); watermark: None or a
+        watermark.params(...) dict (``key`` is this session's key).  With either the session is opened by zvx_stream_open_ex and runs
+        denoise -> level -> watermark -> limit -> rate conversion; with neither this is zvx_stream_open as before."""
         keep = []
         if mel is None:
             mptr = None
@@ -870,7 +881,23 @@ class Context:
             keep.append(lm)
             prm.limit = C.pointer(lm)
         h = C.c_void_p()
-        self._chk(self._lib.zvx_stream_open(self._h, mptr, int(frames), C.byref(prm), int(flags), C.byref(h)))
+        if level is None and watermark is None:
+            self._chk(self._lib.zvx_stream_open(self._h, mptr, int(frames), C.byref(prm), int(flags), C.byref(h)))
+            return Stream(self, h, keep)
+        more = StreamStages()
+        if level is not None:
+            level = dict(level)
+            lv = LevelParams(float(level.pop("target")), float(level.pop("max_gain_db", 20.0)), float(level.pop("window_ms", 3000.0)),
+                             float(level.pop("lookahead_ms", 100.0)))
+            if level:
+                raise TypeError(f"stream_open: unknown level keywords {sorted(level)}")
+            keep.append(lv)
+            more.level = C.pointer(lv)
+        if watermark is not None:
+            wm = self._watermark_params(**watermark)
+            keep.append(wm)
+            more.watermark = C.pointer(wm)
+        self._chk(self._lib.zvx_stream_open_ex(self._h, mptr, int(frames), C.byref(prm), C.byref(more), int(flags), C.byref(h)))
         return Stream(self, h, keep)
 
     def stream_next_many(self, streams, capacities=None):

@@ -1,8 +1,8 @@
 // stream_plan.h -- the window planners of a stream session (include/zvx.h: zvx_stream_next), header-only and free of HIP so that they
 // compile with any host C++ compiler (tests/native/stream_plan_main.cpp checks them against the Python planners on the CPU).
 //
-// A literal restatement of zerovox_amd/stream.py (ReachPlanner: the limiter's and the denoiser's windows) and zerovox_amd/resample.py
-// (StreamPlanner: the rate conversion's).  push(n_new, last) takes the count of newly received input samples and returns
+// A literal restatement of zerovox_amd/stream.py (ReachPlanner: the limiter's, the denoiser's and the watermark's windows),
+// zerovox_amd/leveler.py (LevelPlanner: the leveler's) and zerovox_amd/resample.py (StreamPlanner: the rate conversion's).  push(n_new, last) takes the count of newly received input samples and returns
 // (in_origin, out_begin, out_count, keep_from): run the step on the retained samples [in_origin, received) for the outputs
 // [out_begin, out_begin + out_count) -- nothing to do when out_count is 0 -- then drop the history before keep_from.
 // Every position is an int64_t: a stream may run past 2^32 samples.
@@ -32,6 +32,22 @@ struct ReachPlanner {
         received += n_new;
         const int64_t end = last ? received : imax(next_out, received - R);
         const Step s{origin, next_out, end - next_out, imax(origin, imin(end - R, received))};
+        next_out = end;
+        origin = s.keep_from;
+        return s;
+    }
+};
+
+// The leveler's step (zerovox_amd/leveler.py, LevelPlanner): a reach of RL to the left and RR to the right.  Output i is final once
+// i + RR <= received - 1 (everything on the last push); the next output next_out needs no sample before next_out - RL.
+struct LevelPlanner {
+    int64_t RL = 0, RR = 0, received = 0, next_out = 0, origin = 0;
+    LevelPlanner() {}
+    LevelPlanner(int64_t RL_, int64_t RR_) : RL(RL_), RR(RR_) {}
+    Step push(int64_t n_new, bool last) {
+        received += n_new;
+        const int64_t end = last ? received : imax(next_out, received - RR);
+        const Step s{origin, next_out, end - next_out, imax(origin, imin(end - RL, received))};
         next_out = end;
         origin = s.keep_from;
         return s;

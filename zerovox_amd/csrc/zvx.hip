@@ -413,6 +413,11 @@ struct zvx_ctx {
     }
 };
 
+// What the checks of a post step's parameters yield (level_params_check, dn_geom, watermark_params_check); a session keeps its own.
+struct LevelGeom { int h, S, a; int64_t RL, RR; };          // S and a in units of h samples (100 ms)
+struct DnGeom { int n_fft, log2n, hop, pad, nf; };           // the model's STFT geometry
+struct WmPlan { DnGeom g; int k_lo, J; };                    // ... and the watermark's bands
+
 // A stream session (include/zvx.h: zvx_stream_open): one utterance's mel on the device, the planners of its post stages and, per stage,
 // two device buffers laid out [history | new].  A stage's output is written straight behind the next stage's history; dropping the history
 // before keep_from copies the retained tail into the stage's OTHER buffer (never an overlapping copy) and swaps the two.  A group's gathered
@@ -424,22 +429,27 @@ struct zvx_stream {
     int nchunks = 0, next_chunk = 0, done = 0;
     int Pcap = 0;                          // the longest row a group can have, in mel frames
     int64_t total = 0, emitted = 0, delay = 0, max_piece = 0;
-    enum { DENOISE = 0, LIMIT = 1, RESAMPLE = 2 };
+    enum { DENOISE = 0, LIMIT = 1, RESAMPLE = 2, LEVEL = 3, WATERMARK = 4, KINDS = 5 };
     struct Stage {
         int kind = DENOISE;
-        zvx_plan::ReachPlanner reach;
+        zvx_plan::ReachPlanner reach;      // DENOISE, WATERMARK (n_fft - 1), LIMIT
         zvx_plan::ResamplePlanner rate;
+        zvx_plan::LevelPlanner level;
         float* buf[2] = {nullptr, nullptr};
         int cur = 0;
         int64_t cap = 0, hist = 0;         // samples a buffer holds; retained samples [origin, received) at the front of buf[cur]
-        zvx_plan::Step push(int64_t n, bool last) { return kind == RESAMPLE ? rate.push(n, last) : reach.push(n, last); }
-        int64_t received() const { return kind == RESAMPLE ? rate.received : reach.received; }
+        zvx_plan::Step push(int64_t n, bool last) { return kind == RESAMPLE ? rate.push(n, last) : kind == LEVEL ? level.push(n, last) : reach.push(n, last); }
+        int64_t received() const { return kind == RESAMPLE ? rate.received : kind == LEVEL ? level.received : reach.received; }
     };
-    std::vector<Stage> stages;             // in the order they run: denoiser, limiter, rate conversion
+    std::vector<Stage> stages;             // in the order they run: denoiser, leveler, watermark, limiter, rate conversion
     zvx_denoise_params dn{};
     std::vector<float> bias;
     zvx_limit_params lim{};
     int lim_W = 0;                         // the limiter's window in samples
+    zvx_level_params lvl{};                // (zvx_stream_open_ex)
+    LevelGeom lvl_g{};
+    zvx_watermark_params wm{};             // wm.key is this session's key
+    WmPlan wm_plan{};
     char* dev = nullptr;                   // ONE device allocation: the mel, the stage buffers, the host piece's staging
     float* mel = nullptr;
     float* ostage = nullptr;
@@ -2930,7 +2940,6 @@ void do_limit(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamp
 // leveler (include/zvx.h: zvx_level, zvx_level_ex, zvx_level_rows)
 // ------------------------------------------------------------------------------------------------
 // the checks of the leveler's own parameters -> S and a, in units of 100 ms (on the host in double)
-struct LevelGeom { int h, S, a; int64_t RL, RR; };
 LevelGeom level_params_check(const char* who, int rate, const zvx_level_params* p) {
     if (!std::isfinite(p->target_lufs) || p->target_lufs < -70.f || p->target_lufs > 0.f) fail(ZVX_E_INVALID, "%s: target_lufs must lie in [-70, 0]", who);
     if (!std::isfinite(p->max_gain_db) || p->max_gain_db < 0.f) fail(ZVX_E_INVALID, "%s: max_gain_db must be finite and not negative", who);
@@ -3042,7 +3051,6 @@ void do_level(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamp
 // ------------------------------------------------------------------------------------------------
 // vocoder-bias denoiser (include/zvx.h: zvx_denoise, zvx_denoise_bias; kernels: spectral.hip)
 // ------------------------------------------------------------------------------------------------
-struct DnGeom { int n_fft, log2n, hop, pad, nf; };
 DnGeom dn_geom(const zvx_ctx* c, const char* who) {
     const int n_fft = c->t("mel.dft").dim(2), hop = c->hop;
     int lg = 0;
@@ -3207,7 +3215,6 @@ uint64_t wm_mix64(uint64_t z) {                              // the splitmix64 f
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
     return z ^ (z >> 31);
 }
-struct WmPlan { DnGeom g; int k_lo, J; };
 // the checks of the watermark's own parameters (embedder and detector) -> the model's STFT geometry and the bands
 WmPlan watermark_params_check(const zvx_ctx* c, const char* who, const zvx_watermark_params* p) {
     if (!p) fail(ZVX_E_INVALID, "%s: params is NULL", who);
@@ -3626,12 +3633,14 @@ void stream_free(zvx_stream* s) {
 int64_t rs_reach(const zvx_plan::RatePair& p) { return p.half ? zvx_plan::ceil_div(p.half, p.L) + 1 : 0; }
 
 // The step's one table on the device (stream_step): the rows' gather entries, their scatter entries, then the history drops (one per stage
-// at most).  The buffer is taken at its largest size at once: it never grows behind a queued call.
+// at most, STREAM_MAX_DROPS per session).  The buffer is taken at its largest size at once: it never grows behind a queued call.
+constexpr int STREAM_MAX_DROPS = 5;                          // denoiser, leveler, watermark, limiter, rate conversion
 constexpr size_t STREAM_TAB_BYTES = (size_t)STREAM_MANY_MAX_ROWS * (sizeof(StreamRow) + sizeof(StreamInterior)) +
-                                    (size_t)STREAM_MANY_MAX_SESSIONS * 3 * sizeof(StreamInterior);
+                                    (size_t)STREAM_MANY_MAX_SESSIONS * STREAM_MAX_DROPS * sizeof(StreamInterior);
 
-void do_stream_open(zvx_ctx* c, const float* mel, int frames, const zvx_stream_params* p, int flags, zvx_stream** out) {
-    const char* who = "zvx_stream_open";
+// zvx_stream_open (more == nullptr) and zvx_stream_open_ex
+void do_stream_open(zvx_ctx* c, const char* who, const float* mel, int frames, const zvx_stream_params* p, const zvx_stream_stages* more, int flags,
+                    zvx_stream** out) {
     // ---- every check, before anything is allocated
     if (!p || !out) fail(ZVX_E_INVALID, "%s: %s is NULL", who, !p ? "params" : "out");
     *out = nullptr;
@@ -3659,6 +3668,19 @@ void do_stream_open(zvx_ctx* c, const float* mel, int frames, const zvx_stream_p
             fail(ZVX_E_INVALID, "%s: %d frames are %lld samples; the denoiser needs at least %d (zvx_melspec's conditions)", who, frames,
                  (long long)total_native, dn_min_samples(g));
     }
+    const zvx_level_params* lvl = more ? more->level : nullptr;
+    const zvx_watermark_params* wm = more ? more->watermark : nullptr;
+    if (more && (more->reserved[0] != 0 || more->reserved[1] != 0))
+        fail(ZVX_E_INVALID, "%s: stages: reserved is %lld, %lld (must be 0)", who, (long long)more->reserved[0], (long long)more->reserved[1]);
+    LevelGeom lg{};
+    if (lvl) lg = level_params_check(who, native, lvl);
+    WmPlan wp{};
+    if (wm) {
+        wp = watermark_params_check(c, who, wm);
+        if (total_native < dn_min_samples(wp.g))
+            fail(ZVX_E_INVALID, "%s: %d frames are %lld samples; the watermark needs at least %d (zvx_melspec's conditions)", who, frames,
+                 (long long)total_native, dn_min_samples(wp.g));
+    }
     int W = 0;
     if (p->limit) { limit_os_check(who, p->limit->oversample); W = limit_params_check(who, native, p->limit); }
     zvx_plan::RatePair rp;
@@ -3673,9 +3695,11 @@ void do_stream_open(zvx_ctx* c, const float* mel, int frames, const zvx_stream_p
     const int rows = std::min(p->chunks_per_call, nchunks);
     const int Pcap = (int)std::min<int64_t>(frames, (int64_t)chunk + 2 * (int64_t)halo);
     const int64_t G = (int64_t)rows * chunk * hop;           // the most new samples one call brings
-    struct Want { int kind; int64_t R, keep; };              // keep: the most history a stage retains between two calls
+    struct Want { int kind; int64_t R, keep; };              // R: the reach to the right; keep: the most history a stage retains between two calls
     std::vector<Want> want;
     if (p->denoise) want.push_back({zvx_stream::DENOISE, (int64_t)g.n_fft - 1, 2 * ((int64_t)g.n_fft - 1)});
+    if (lvl) want.push_back({zvx_stream::LEVEL, lg.RR, lg.RL + lg.RR});
+    if (wm) want.push_back({zvx_stream::WATERMARK, (int64_t)wp.g.n_fft - 1, 2 * ((int64_t)wp.g.n_fft - 1)});
     if (p->limit) { const int64_t R = 2 * (int64_t)W + (p->limit->oversample > 1 ? LIMIT_ENV_REACH : 0); want.push_back({zvx_stream::LIMIT, R, 2 * R}); }
     if (out_rate != native) want.push_back({zvx_stream::RESAMPLE, rs_reach(rp), 2 * rp.half / rp.L + 2});
     int64_t delay = 0;
@@ -3688,6 +3712,29 @@ void do_stream_open(zvx_ctx* c, const float* mel, int frames, const zvx_stream_p
     if (p->denoise && p->denoise->strength != 0.f) dn_tables(c, g);
     if (p->limit) { limit_win(c, W); if (p->limit->oversample > 1) rs_bank(c, p->limit->oversample, 1); }
     if (out_rate != native) rs_bank(c, (int)rp.L, (int)rp.M);
+    {   // ... and what the leveler's and the watermark's bodies take on first use, at the session's largest step: a stage holds at most
+        // keep + (the group + the reaches in front of it) samples and emits no more than it holds
+        int64_t in_max = G;
+        for (const Want& w : want) {
+            const int64_t held = w.keep + in_max;
+            if (w.kind == zvx_stream::LEVEL) {
+                loud_coef(c, native);
+                c->buf("lvl.p", (size_t)(held / lg.h + lg.S + 4) * sizeof(double));
+                c->fbuf("lvl.part", (size_t)2 * (size_t)((held + 3 + LEVEL_TILE - 1) / LEVEL_TILE));
+                c->fbuf("lvl.res", 2); c->buf("lvl.rows", sizeof(LevelRow));
+            }
+            if (w.kind == zvx_stream::WATERMARK) {
+                c->buf("dn.rows", sizeof(DenoiseRow));
+                if (wm->depth_db != 0.f) {
+                    dn_tables(c, wp.g);
+                    const int64_t F = (held + wp.g.n_fft) / wp.g.hop + (DENOISE_POINTS >> wp.g.log2n) + 2;
+                    c->fbuf("dn.work", (size_t)F * wp.g.n_fft);
+                    c->buf("wm.keys", 8); c->buf("wm.sign_of_row", sizeof(int)); c->buf("wm.signs", (size_t)wm->period_blocks * wp.J);
+                }
+            }
+            in_max += w.R;
+        }
+    }
     c->buf("stream.tab", STREAM_TAB_BYTES); c->fbuf("stream.rows", (size_t)rows * Pcap * nm); c->fbuf("stream.wav", (size_t)rows * wstride);   // what a step of the largest group takes
     // ---- the session and its memory
     zvx_stream* s = new zvx_stream();
@@ -3698,13 +3745,17 @@ void do_stream_open(zvx_ctx* c, const float* mel, int frames, const zvx_stream_p
         s->total = zvx_plan::ceil_div(total_native * rp.L, rp.M);
         if (p->denoise) { s->dn = *p->denoise; s->bias.assign(p->denoise_bias, p->denoise_bias + g.nf); }
         if (p->limit) { s->lim = *p->limit; s->lim_W = W; }
+        if (lvl) { s->lvl = *lvl; s->lvl_g = lg; }
+        if (wm) { s->wm = *wm; s->wm_plan = wp; }
         auto pad = [](int64_t floats) { return (size_t)((floats * 4 + 255) & ~(int64_t)255); };
         size_t bytes = pad((int64_t)frames * nm) + pad(max_piece);
         int64_t in_max = G;
         for (const Want& w : want) {
             zvx_stream::Stage st;
             st.kind = w.kind;
-            if (w.kind == zvx_stream::RESAMPLE) st.rate = zvx_plan::ResamplePlanner(native, out_rate); else st.reach = zvx_plan::ReachPlanner(w.R);
+            if (w.kind == zvx_stream::RESAMPLE) st.rate = zvx_plan::ResamplePlanner(native, out_rate);
+            else if (w.kind == zvx_stream::LEVEL) st.level = zvx_plan::LevelPlanner(lg.RL, lg.RR);
+            else st.reach = zvx_plan::ReachPlanner(w.R);
             st.cap = w.keep + in_max + 8;
             in_max += w.R;
             bytes += 2 * pad(st.cap);
@@ -3764,11 +3815,25 @@ void stream_plan_step(const char* who, const zvx_stream* s, StreamStep& p) {
         const int64_t held = p.plan[k].hist + n;
         if (held != p.plan[k].received() - p.steps[k].in_origin || held > p.plan[k].cap)
             fail(ZVX_E_STATE, "%s: stage %zu holds %lld samples (buffer %lld, window from %lld)", who, k, (long long)held, (long long)p.plan[k].cap, (long long)p.steps[k].in_origin);
-        // the plan's self-check: a denoiser's or limiter's window must be one the rows calls accept (their support condition, on the host)
+        // the plan's self-check: a denoiser's, leveler's, watermark's or limiter's window must be one the rows calls accept (their support
+        // condition, on the host).  The leveler's is its own: RL to the left, RR to the right, and the clamped left rule of a last window.
+        // That rule never bites here although a session flags its last group `last` WITH new samples (the Python stream closes with an
+        // empty push): the last push's out_begin is what the push before left, max(0, prev_received - RR), RR = (a + 1) h - 1, so
+        // out_begin / h + a - 1 <= (prev_received + 1) / h - 2 <= prev_received / h - 1 <= U - 1 -- the first node is not clamped, and
+        // where it is not, RL (in_origin = out_begin - RL whenever in_origin > 0) implies the oldest unit's support.
         if (p.plan[k].kind != zvx_stream::RESAMPLE && p.steps[k].out_count > 0) {
             const RowsWindow w{p.steps[k].in_origin, p.steps[k].out_begin, p.steps[k].out_count, p.g.last ? 1 : 0};
+            const bool level = p.plan[k].kind == zvx_stream::LEVEL;
             int64_t cnt = -1;
-            try { cnt = window_count_row(who, w, (int32_t)held, 0, p.plan[k].reach.R); }
+            try {
+                if (level) {
+                    cnt = window_count_row(who, w, (int32_t)held, 0, s->lvl_g.RL, s->lvl_g.RR);
+                    RowsWindows rw;
+                    rw.w.assign(1, w); rw.cnt.assign(1, (int32_t)cnt); rw.cnt_max = (long)cnt;
+                    const int32_t held32 = (int32_t)held;
+                    level_clamped_support_check(who, rw, &held32, 1, s->lvl_g);
+                } else cnt = window_count_row(who, w, (int32_t)held, 0, p.plan[k].reach.R);
+            }
             catch (const ZvxError& e) { fail(ZVX_E_STATE, "%s (stage %zu of the session's plan)", e.what(), k); }
             if (cnt != w.out_count) fail(ZVX_E_STATE, "%s: stage %zu emits %lld samples, its plan says %lld", who, k, (long long)cnt, (long long)w.out_count);
         }
@@ -3781,9 +3846,10 @@ void stream_plan_step(const char* who, const zvx_stream* s, StreamStep& p) {
 // One step of n sessions of ONE context, the only stepping path (zvx_stream_next is its n = 1): the callers have made their own checks
 // and planned every session (stream_plan_step), so from here on the call consumes the groups and a failure ends every session of it.
 // The rows of all sessions are gathered by one launch, vocoded as ONE batch by one run_vocoder and scattered by one launch to where each
-// session's first stage reads them.  The stages then run kind by kind -- all denoisers, then all limiters, then the rate conversions; a
-// session's chain order is kept and everything is on the one stream.  Within a kind the sessions whose stage has bitwise-equal parameters
-// (the bias by content; the limiter by W, oversampling and ceiling; the rate conversion by its two rates, i.e. the polyphase bank) form
+// session's first stage reads them.  The stages then run kind by kind -- all denoisers, then the levelers, the watermarks, the limiters, the
+// rate conversions; a session's chain order is kept and everything is on the one stream.  Within a kind the sessions whose stage has
+// bitwise-equal parameters (the bias by content; the leveler by its four parameters; the watermark by everything but the key, the members'
+// keys go to the one call as keys[]; the limiter by W, oversampling and ceiling; the rate conversion by its two rates, i.e. the polyphase bank) form
 // one group (stream_plan.h, partition_classes), and a group is ONE call of the per-row form: its rows are the sessions' [history | new]
 // buffers with each session's own window, each output goes straight behind the next stage's history or to the piece's destination.
 // All history drops of the call are ONE launch over a table.  Every session's stages are walked once, before anything is queued: the
@@ -3803,14 +3869,14 @@ void stream_step(const char* who, zvx_ctx* c, zvx_stream* const* ss, StreamStep*
         }
         const long wstride = ((long)Pmax * hop + 7) & ~7L;
         // ---- the table, and every stage's input, window and destination, from the sessions' state as it stands
-        std::vector<char> tab((size_t)R * (sizeof(StreamRow) + sizeof(StreamInterior)) + (size_t)n * 3 * sizeof(StreamInterior));
+        std::vector<char> tab((size_t)R * (sizeof(StreamRow) + sizeof(StreamInterior)) + (size_t)n * STREAM_MAX_DROPS * sizeof(StreamInterior));
         StreamRow* tr = (StreamRow*)tab.data();
         StreamInterior* ti = (StreamInterior*)(tr + R);
         StreamInterior* moves = ti + R;
         int M = 0, r = 0;
         std::vector<int> P((size_t)R);
         struct Slot { bool run = false; PostRow row{}; };
-        std::vector<Slot> slot[3];
+        std::vector<Slot> slot[zvx_stream::KINDS];
         for (auto& v : slot) v.resize((size_t)n);
         for (int i = 0; i < n; i++) {
             const zvx_stream* s = ss[i];
@@ -3868,6 +3934,7 @@ void stream_step(const char* who, zvx_ctx* c, zvx_stream* const* ss, StreamStep*
         // ---- the stages of one kind: a class is named by its first member, and is one call of the per-row form
         std::vector<int> cls((size_t)n), order((size_t)n), start((size_t)n + 1);
         std::vector<PostRow> rows;
+        std::vector<uint64_t> keys;                          // (WATERMARK: the members' keys, in call order)
         auto per_class = [&](int kind, auto same, auto run) {
             for (int i = 0; i < n; i++) {
                 cls[(size_t)i] = -1;
@@ -3878,14 +3945,26 @@ void stream_step(const char* who, zvx_ctx* c, zvx_stream* const* ss, StreamStep*
             }
             const int groups = zvx_plan::partition_classes(cls.data(), n, order.data(), start.data());
             for (int gi = 0; gi < groups; gi++) {
-                rows.clear();
-                for (int m = start[(size_t)gi]; m < start[(size_t)gi + 1]; m++) rows.push_back(slot[kind][(size_t)order[(size_t)m]].row);
+                rows.clear(); keys.clear();
+                for (int m = start[(size_t)gi]; m < start[(size_t)gi + 1]; m++) {
+                    rows.push_back(slot[kind][(size_t)order[(size_t)m]].row);
+                    keys.push_back(ss[order[(size_t)m]]->wm.key);
+                }
                 run(ss[order[(size_t)start[(size_t)gi]]]);
             }
         };
         per_class(zvx_stream::DENOISE, [](const zvx_stream* a, const zvx_stream* b) {
             return !memcmp(&a->dn, &b->dn, sizeof a->dn) && a->bias.size() == b->bias.size() && !memcmp(a->bias.data(), b->bias.data(), a->bias.size() * 4);
         }, [&](const zvx_stream* first) { run_denoise_rows(c, dn_geom(c, who), rows.data(), (int)rows.size(), first->bias.data(), &first->dn, 0); });
+        per_class(zvx_stream::LEVEL, [](const zvx_stream* a, const zvx_stream* b) {
+            return a->native == b->native && !memcmp(&a->lvl, &b->lvl, sizeof a->lvl);
+        }, [&](const zvx_stream* first) { run_level_rows(c, rows.data(), (int)rows.size(), first->native, &first->lvl, first->lvl_g, 0); });   // (the gain words are not read)
+        per_class(zvx_stream::WATERMARK, [](const zvx_stream* a, const zvx_stream* b) {
+            // every field but the key, bit for bit (the key is the member's own: one call marks every key of the class)
+            const float fa[3] = {a->wm.depth_db, a->wm.lo_hz, a->wm.hi_hz}, fb[3] = {b->wm.depth_db, b->wm.lo_hz, b->wm.hi_hz};
+            return !memcmp(fa, fb, sizeof fa) && a->wm.block_frames == b->wm.block_frames && a->wm.band_bins == b->wm.band_bins &&
+                   a->wm.period_blocks == b->wm.period_blocks && a->wm.reserved == b->wm.reserved;
+        }, [&](const zvx_stream* first) { run_watermark_rows(c, first->wm_plan, rows.data(), (int)rows.size(), &first->wm, 0, keys.data()); });
         per_class(zvx_stream::LIMIT, [](const zvx_stream* a, const zvx_stream* b) {
             return a->lim_W == b->lim_W && a->lim.oversample == b->lim.oversample && !memcmp(&a->lim.ceiling, &b->lim.ceiling, sizeof(float));
         }, [&](const zvx_stream* first) { run_limit_rows(c, who, rows.data(), (int)rows.size(), &first->lim, first->lim_W, 0); });
@@ -4415,7 +4494,12 @@ zvx_status zvx_level_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, 
 }
 
 zvx_status zvx_stream_open(zvx_ctx* c, const float* mel, int frames, const zvx_stream_params* params, int flags, zvx_stream** out) {
-    return guarded(c, [&] { do_stream_open(c, mel, frames, params, flags, out); });
+    return guarded(c, [&] { do_stream_open(c, "zvx_stream_open", mel, frames, params, nullptr, flags, out); });
+}
+
+zvx_status zvx_stream_open_ex(zvx_ctx* c, const float* mel, int frames, const zvx_stream_params* params, const zvx_stream_stages* more, int flags,
+                              zvx_stream** out) {
+    return guarded(c, [&] { do_stream_open(c, more ? "zvx_stream_open_ex" : "zvx_stream_open", mel, frames, params, more, flags, out); });
 }
 
 zvx_status zvx_stream_next(zvx_stream* s, void* out, int64_t capacity, int64_t* n_out, int32_t* done, int flags) {

@@ -281,22 +281,23 @@ class ZeroVox:
         level: None, or Context.level_window keywords (target, and optionally max_gain_db, window_ms, lookahead_ms): the native-rate
         chunks pass through the windowed leveler (zerovox_amd.leveler, zvx_level_ex) and concatenate bit for bit to zvx_level of the
         whole stream that reaches it; the levelled stream runs RR = leveler.reach(...)[1] samples behind that stage's input (4409
-        samples, 200 ms, at 22.05 kHz with the defaults).  The chain is denoise, then level, then limit, then the conversion.  Host-planned
-        streams only: sessions have no level stage yet (resident=True with level raises ValueError).
+        samples, 200 ms, at 22.05 kHz with the defaults).  The chain is denoise, then level, then limit, then the conversion.  With
+        resident=True this method still raises ValueError for level; a session with a level stage is ``vocode_stream_sessions([mel],
+        level=...)`` or ``Context.stream_open(..., level=...)``.
         watermark: None, or watermark.params(...) (key and the embedder's parameters): the native-rate chunks pass through the windowed
         embedder (zerovox_amd.watermark, zvx_watermark_ex) and concatenate bit for bit to zvx_watermark of the whole stream that reaches
         it; the marked stream runs watermark.reach(fft_size) = fft_size - 1 samples behind that stage's input.  The chain is denoise,
-        level, watermark, limit, conversion.  Host-planned streams only (resident=True with watermark raises ValueError).
+        level, watermark, limit, conversion.
         resident: False (the default: the host-planned stream above), or True: the same keywords drive a stream session of the library
         (include/zvx.h, zvx_stream_open) -- the mel is uploaded once, the samples stay on the device between the steps and every piece
-        costs one wait.  The pieces concatenate to the same bits; where they are cut may differ.  mel None (resident only): the mel the
-        context holds after decode."""
+        costs one wait.  The pieces concatenate to the same bits; where they are cut may differ.  With a watermark the session is one of
+        zvx_stream_open_ex, the stage planned inside the library like the others.  mel None (resident only): the mel the context holds
+        after decode."""
         if resident:
             if level is not None:
-                raise ValueError("vocode_stream: stream sessions have no level stage yet (use resident=False with level=)")
-            if watermark is not None:
-                raise ValueError("vocode_stream: stream sessions have no watermark stage yet (use resident=False with watermark=)")
-            yield from self._vocode_stream_resident(mel, chunk_frames, halo, chunks_per_call, limiter, denoise)
+                raise ValueError("vocode_stream: resident=True does not take level= (a session with a level stage is "
+                                 "vocode_stream_sessions([mel], level=...); or use resident=False)")
+            yield from self._vocode_stream_resident(mel, chunk_frames, halo, chunks_per_call, limiter, denoise, None, watermark)
             return
         ctx = self._ctx
         rate, native = ctx.get_int("out_rate"), ctx.get_int("sampling_rate")
@@ -324,22 +325,50 @@ class ZeroVox:
             chunks = stream_resample(chunks, native, rate, lambda x, o, b, n: ctx.resample_window([x], native, rate, o, b, n)[0][0].copy())
         yield from chunks
 
-    def _vocode_stream_resident(self, mel, chunk_frames, halo, chunks_per_call, limiter, denoise):
+    @staticmethod
+    def _session_stages(level, watermark):
+        """the level / watermark keywords of a session (Context.stream_open): none where neither stage is asked for"""
+        more = {}
+        if level is not None:
+            more["level"] = level
+        if watermark is not None:
+            more["watermark"] = watermark
+        return more
+
+    def _vocode_stream_resident(self, mel, chunk_frames, halo, chunks_per_call, limiter, denoise, level=None, watermark=None):
         bias = self.denoise_bias if denoise is not None else None           # (first use runs the vocoder: before the session opens)
         yield from self._ctx.stream_open(mel, chunk_frames=chunk_frames, chunks_per_call=max(1, chunks_per_call), halo=halo, denoise=denoise,
-                                         bias=bias, limit=limiter)
+                                         bias=bias, limit=limiter, **self._session_stages(level, watermark))
 
     def vocode_stream_many(self, mels, chunk_frames=64, halo=STREAM_HALO, chunks_per_call=1, limiter=None, denoise=None):
         """Many utterances streamed together: mels, a list of [L_i, n_mels] arrays -> yields (index, piece) with non-empty float32 pieces
         only.  One stream session per mel (the keywords of ``vocode_stream``), all stepped by one zvx_stream_next_many per round
         (zerovox_amd.serve.StreamBatcher): the chunks of every utterance ride through the vocoder as one batch.  The pieces of index i
-        concatenate bit for bit to ``vocode_stream(mels[i], ..., resident=True)``."""
+        concatenate bit for bit to ``vocode_stream(mels[i], ..., resident=True)``.  ``vocode_stream_sessions`` is this method with the
+        level and watermark stages."""
+        return self.vocode_stream_sessions(mels, chunk_frames=chunk_frames, halo=halo, chunks_per_call=chunks_per_call, limiter=limiter,
+                                           denoise=denoise)
+
+    def vocode_stream_sessions(self, mels, *, chunk_frames=64, halo=STREAM_HALO, chunks_per_call=1, limiter=None, denoise=None, level=None,
+                               watermark=None):
+        """``vocode_stream_many`` with every stage of a stream session (include/zvx.h, zvx_stream_open_ex): what it does and yields, and
+        level: None or the ``level`` keywords of ``vocode_stream``, for every mel;
+        watermark: None, one watermark.params(...) dict for every mel, or a sequence of them, one per mel (None entries: that mel goes
+        out unmarked) -- sessions that differ in their key alone are marked by one launch group per round.
+        The pieces of index i concatenate bit for bit to ``vocode_stream(mels[i], ..., level=, watermark=)``, resident or host-planned."""
         from .serve import StreamBatcher
+        mels = list(mels)
+        if watermark is None or isinstance(watermark, dict):
+            marks = [watermark] * len(mels)
+        else:
+            marks = list(watermark)
+            if len(marks) != len(mels):
+                raise ValueError(f"vocode_stream_sessions: {len(marks)} watermarks for {len(mels)} mels")
         bias = self.denoise_bias if denoise is not None else None           # (first use runs the vocoder: before the sessions open)
         batcher = StreamBatcher(self._ctx)
         try:
             index = {batcher.open(np.asarray(m, np.float32), chunk_frames=chunk_frames, chunks_per_call=max(1, chunks_per_call), halo=halo,
-                                  denoise=denoise, bias=bias, limit=limiter): i for i, m in enumerate(mels)}
+                                  denoise=denoise, bias=bias, limit=limiter, **self._session_stages(level, marks[i])): i for i, m in enumerate(mels)}
             while len(batcher):
                 for id_, piece, _ in batcher.step():
                     if len(piece):

@@ -40,8 +40,10 @@ class StreamBatcher:
         return len(self._open)
 
     def open(self, mel=None, frames=0, *, chunk_frames, chunks_per_call=1, **kw):
-        """opens a session on ``mel`` (Context.stream_open's arguments) -> its id.  A session whose group alone exceeds max_rows could
-        never be scheduled: ValueError."""
+        """opens a session on ``mel`` (Context.stream_open's arguments) -> its id.  Every keyword is forwarded: denoise / bias / limit, and
+        the stages of zvx_stream_open_ex, ``level=`` (Context.level_window's keywords) and ``watermark=`` (a watermark.params(...) dict
+        whose ``key`` is this session's) -- sessions of equal level parameters, and sessions whose watermark differs in the key alone,
+        each cost one launch group per step.  A session whose group alone exceeds max_rows could never be scheduled: ValueError."""
         cpc = max(1, int(chunks_per_call))
         if mel is None:                                              # the context's mel, its length unknown here: every group counts as
             chunks = 1 << 62                                         # chunks_per_call rows (an upper bound; the budget stays safe)

@@ -415,11 +415,13 @@ class ZeroVoxTTS:
         level_window_ms, looking level_lookahead_ms ahead, at most +20 dB.  It is an AGC, not the R128 normalisation of ``loudness=``.
         The pieces concatenate bit for bit to zvx_level of the stream that reaches the stage; the chain is denoise, level, limit,
         conversion, and the levelled stream runs (a + 1) h - 1 samples behind the stage's input (4409: 200 ms at 22.05 kHz with the
-        defaults).  Host-planned streams only: with ``resident=True`` it raises ValueError (sessions have no level stage yet).
+        defaults).  With ``resident=True`` this method still raises ValueError; sessions with a level stage are reached through
+        ``tts_stream_sessions`` and ``ZeroVox.vocode_stream(resident=True, level=...)``.
         watermark: None (the default: nothing changes), an int key, or a dict with ``key`` (see tts_ex): the stream is marked window by
         window (include/zvx.h, zvx_watermark_ex; zerovox_amd.watermark).  The pieces concatenate bit for bit to zvx_watermark of the
         stream that reaches the stage; the chain is denoise, level, watermark, limit, conversion, and the marked stream runs n_fft - 1
-        samples more behind.  Host-planned streams only: with ``resident=True`` it raises ValueError (no watermark stage yet).
+        samples more behind.  With ``resident=True`` this method still raises ValueError; sessions with a watermark stage are reached
+        through ``tts_stream_sessions`` and ``ZeroVox.vocode_stream(resident=True, watermark=...)``.
         resident: False (the default: the stream is planned on the host), or True: a stream session of the library runs it (include/zvx.h,
         zvx_stream_open; ZeroVox.vocode_stream(resident=True)) -- the decoder's mel never leaves the device and every piece costs one
         wait.  The concatenation is the same to the bit; the pieces may be cut elsewhere."""
@@ -477,16 +479,44 @@ class ZeroVoxTTS:
         batch (``synthesize_batch(want_mel=True)``, at most max_frames mel frames per text), one stream session is opened on every mel,
         and each round steps all of them with one zvx_stream_next_many (``ZeroVox.vocode_stream_many``): the chunks of all texts ride
         through the vocoder as one batch.  The pieces of index i concatenate bit for bit to ``vocode_stream(mel_i, ..., resident=True)``
-        on the mel the batch made for text i (``last_stream_mels[i]``).  A text without phonemes yields nothing."""
+        on the mel the batch made for text i (``last_stream_mels[i]``).  A text without phonemes yields nothing.
+        ``level_lufs`` and ``watermark`` are still refused here (ValueError); ``tts_stream_sessions`` is this method with both stages."""
+        if level_lufs is not None or watermark is not None:
+            self._stream_keywords(speed, pitch_shift, pitch_range, energy_shift, energy_range, loudness, limiter, peak_db, limiter_ms, denoise,
+                                  denoise_strength)            # (the other keywords' errors come first, as they always did)
+            if level_lufs is not None:
+                raise ValueError("tts_stream_many: stream sessions have no level stage yet: level_lufs is tts_stream's (resident=False)")
+            raise ValueError("tts_stream_many: stream sessions have no watermark stage yet: watermark is tts_stream's (resident=False)")
+        return self.tts_stream_sessions(texts, spkembs, chunk_frames=chunk_frames, chunks_per_call=chunks_per_call, speed=speed,
+                                        pitch_shift=pitch_shift, pitch_range=pitch_range, energy_shift=energy_shift, energy_range=energy_range,
+                                        loudness=loudness, limiter=limiter, peak_db=peak_db, limiter_ms=limiter_ms, denoise=denoise,
+                                        denoise_strength=denoise_strength, max_frames=max_frames)
+
+    def tts_stream_sessions(self, texts, spkembs, *, chunk_frames=64, chunks_per_call=1, speed=1.0, pitch_shift=0.0, pitch_range=1.0,
+                            energy_shift=0.0, energy_range=1.0, loudness=None, limiter=False, peak_db=None, limiter_ms=5.0, denoise=None,
+                            denoise_strength=None, max_frames=2048, level_lufs=None, level_window_ms=3000.0, level_lookahead_ms=100.0,
+                            watermark=None):
+        """``tts_stream_many`` with every stage of a stream session (include/zvx.h, zvx_stream_open_ex): what it does and yields --
+        (index, piece), non-empty float32 pieces only, one session per text, one zvx_stream_next_many per round -- and besides
+        level_lufs / level_window_ms / level_lookahead_ms: the leveler of ``tts_stream``, for every text;
+        watermark: None, one key or dict for every text (see tts_ex), or a sequence of them, one per text (None entries: that text
+        goes out unmarked).  Sessions that differ in their key alone are marked by one launch group per round.
+        The chain is denoise, level, watermark, limit, conversion; the pieces of index i concatenate bit for bit to
+        ``vocode_stream(mel_i, ..., level=, watermark=)``, host-planned or resident, on ``last_stream_mels[i]``.  Every argument is
+        checked before the model is touched."""
         prosody, lim, den = self._stream_keywords(speed, pitch_shift, pitch_range, energy_shift, energy_range, loudness, limiter, peak_db,
                                                   limiter_ms, denoise, denoise_strength)
-        if level_lufs is not None:
-            raise ValueError("tts_stream_many: stream sessions have no level stage yet: level_lufs is tts_stream's (resident=False)")
-        if watermark is not None:
-            raise ValueError("tts_stream_many: stream sessions have no watermark stage yet: watermark is tts_stream's (resident=False)")
-        return self._tts_stream_many(list(texts), spkembs, chunk_frames, chunks_per_call, prosody, lim, den, int(max_frames))
+        lvl = self._level(level_lufs, level_window_ms, level_lookahead_ms)
+        texts = list(texts)
+        if watermark is None or isinstance(watermark, (int, dict)):
+            marks = [self._watermark(watermark)] * len(texts)
+        else:
+            marks = [self._watermark(w) for w in watermark]
+            if len(marks) != len(texts):
+                raise ValueError(f"tts_stream_sessions: {len(marks)} watermarks for {len(texts)} texts")
+        return self._tts_stream_many(texts, spkembs, chunk_frames, chunks_per_call, prosody, lim, den, int(max_frames), lvl, marks)
 
-    def _tts_stream_many(self, texts, spkembs, chunk_frames, chunks_per_call, prosody, limiter, denoise, max_frames):
+    def _tts_stream_many(self, texts, spkembs, chunk_frames, chunks_per_call, prosody, limiter, denoise, max_frames, level=None, marks=None):
         ids = [self.text2phonemeids(t.strip()) for t in texts]
         keep = [i for i, (ph, _) in enumerate(ids) if ph]
         self.last_stream_mels = {}
@@ -507,8 +537,9 @@ class ZeroVoxTTS:
             raise ValueError(f"predicted mel length {min(ml)} is too short to synthesise")
         mels = [np.ascontiguousarray(r["mel"][b, :ml[b]]) for b in range(B)]
         self.last_stream_mels = {i: mels[b] for b, i in enumerate(keep)}
-        for b, piece in self._model.vocode_stream_many(mels, chunk_frames=chunk_frames, chunks_per_call=chunks_per_call, limiter=limiter,
-                                                       denoise=denoise):
+        marks = [marks[i] for i in keep] if marks is not None and any(m is not None for m in marks) else None
+        for b, piece in self._model.vocode_stream_sessions(mels, chunk_frames=chunk_frames, chunks_per_call=chunks_per_call, limiter=limiter,
+                                                           denoise=denoise, level=level, watermark=marks):
             yield keep[b], piece
 
     def _tts_stream(self, text, spkemb, chunk_frames, chunks_per_call, prosody, limiter=None, denoise=None, resident=False, level=None,
