@@ -1102,11 +1102,48 @@ zvx_status zvx_watermark_identify(zvx_ctx* ctx, const float* in, const int32_t* 
                                   const uint64_t* keys, int K, int window_frames, float* score, int32_t* offset, int32_t* window, int32_t* best,
                                   int flags);
 
+/* ---- voice matching: cosine scores of query embeddings against a device-resident library of embeddings, and the best of them --------
+ * zvx_spk_score writes score[b][k] for every query b < B and library row k < K; zvx_spk_topk writes, per query, the `top` largest of
+ *   those scores with their row indices.  The two questions they answer: whose voice was delivered (the similarity of a re-embedded
+ *   waveform, zvx_spkemb_wav, to the embedding it was conditioned on: K = 1), and which enrolled voice a clip is (look-up, duplicates at
+ *   enrolment, a list of voices that must not be cloned).
+ * Arguments: query [B][dim] f32, on the host, or on the device with ZVX_DEVICE_IN -- for example the ZVX_DEVICE_OUT | ZVX_NO_SYNC output
+ *   of zvx_spkemb_wav queued just before; stream order is the fence.  lib [K][dim] f32 is ALWAYS a device pointer on the context's device
+ *   (zvx_dev_alloc / zvx_dev_from_host, or rows that zvx_spkemb_wav wrote there), aligned to 16 bytes; a library is resident by nature, so
+ *   no flag says so.  The outputs follow ZVX_DEVICE_OUT; ZVX_NO_SYNC is allowed with a device output only (the call then only queues).
+ *   dim is explicit, not read from the context: a multiple of 4 with 4 <= dim <= 2048.  Neither side has to be normalised (a centroid of
+ *   several clips is not a unit vector).
+ * Arithmetic, in f32: score(b, k) = dot(q_b, e_k) / max(|q_b| |e_k|, FLT_MIN).  A zero row on either side therefore scores 0.  A score
+ *   that is not finite (NaN or inf in the inputs; also a norm that exceeds FLT_MAX) is delivered as -2.0f, by both calls.  The norms are
+ *   formed with three scaled sums of squares, so rows scaled by 1e-20 or 1e+18 keep their accuracy; the query is divided by its norm
+ *   before the products.  Against a float64 evaluation every score lies within (2 dim + 8) 2^-24 (tests/voice_ref.py derives the bound).
+ * Position contract (the rows contract of the post-processing calls, applied here): the bits of score(b, k) depend on the values of
+ *   q_b and e_k and on dim only -- not on B, K, top, the row's position in the library, or which of the two calls produced them.  The
+ *   order in which the dim products are added is fixed.
+ * Top-k: 1 <= top <= min(K, ZVX_SPK_TOP_MAX).  score / index [B][top], sorted by descending score and by ascending index among equal
+ *   scores: exactly the selection over what zvx_spk_score would write.  Indices are int32, so K <= 2^31 - 1.  No B x K matrix is formed:
+ *   the first launch keeps a sorted list per (query, slab of 512 rows), a second small launch merges the lists; no host wait in between.
+ * The library is read once per group of up to 64 queries (fewer where dim or top are large: the group is staged in 160 KB of LDS; 64 at
+ *   dim 528, 16 at dim 2048); larger B is looped over inside the call.
+ * ZVX_E_INVALID, before anything is queued, the context stays usable and nothing is written: unknown flag bits; ZVX_NO_SYNC without
+ *   ZVX_DEVICE_OUT; a NULL query / lib / score / index; B <= 0; K <= 0 or K > 2^31 - 1; a bad dim; a bad top; lib not aligned to 16
+ *   bytes.  ZVX_E_UNSUPPORTED: B > 65535.  The message names the function and the argument.
+ * Stage tag "spk.match" in zvx_tag_stats (one timed group per call); no ZVX_T_* slot.
+ * Not here: a speaker-verification threshold.  What similarity separates two speakers depends on the checkpoint's speaker encoder and is
+ *   not measured; nothing here claims a perceptual meaning for a score. */
+#define ZVX_SPK_TOP_MAX 32
+zvx_status zvx_spk_score(zvx_ctx* ctx, const float* query, int B, const float* lib, int64_t K, int dim, float* score /* [B][K] */, int flags);
+zvx_status zvx_spk_topk(zvx_ctx* ctx, const float* query, int B, const float* lib, int64_t K, int dim, int top, float* score /* [B][top] */,
+                        int32_t* index /* [B][top] */, int flags);
+
 /* Device buffers for ZVX_DEVICE_OUT outputs / zvx_comm_gather without any other GPU runtime in the process. */
 zvx_status zvx_dev_alloc(zvx_ctx* ctx, size_t bytes, void** out);
 zvx_status zvx_dev_free(zvx_ctx* ctx, void* p);
 zvx_status zvx_dev_from_host(zvx_ctx* ctx, void* dst_dev, const void* src_host, size_t bytes);
 zvx_status zvx_dev_to_host(zvx_ctx* ctx, void* dst_host, const void* src_dev, size_t bytes);
+/* device to device on the context's stream, behind everything queued there; the ranges must not overlap; returns when the copy is done
+ * (a library of embeddings grows and closes its holes with it: zerovox_amd/voices.py) */
+zvx_status zvx_dev_copy(zvx_ctx* ctx, void* dst_dev, const void* src_dev, size_t bytes);
 
 /* drains every stream of the context (compute, front end, communication) */
 zvx_status zvx_sync(zvx_ctx* ctx);

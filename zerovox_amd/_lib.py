@@ -29,7 +29,8 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_denoise_ex", "zvx_stream_open", "zvx_stream_next", "zvx_stream_info", "zvx_stream_close", "zvx_stream_next_many",
            "zvx_denoise_rows", "zvx_limit_rows", "zvx_resample_rows", "zvx_level", "zvx_level_ex", "zvx_level_rows", "zvx_loudness_stats",
            "zvx_pitch", "zvx_watermark", "zvx_watermark_ex", "zvx_watermark_detect", "zvx_watermark_rows", "zvx_watermark_identify",
-           "zvx_stream_open_ex")
+           "zvx_stream_open_ex", "zvx_spk_score", "zvx_spk_topk", "zvx_dev_copy")
+ZVX_SPK_TOP_MAX = 32                                 # the most places zvx_spk_topk returns per query
 ZVX_STREAM_MANY_MAX_SESSIONS, ZVX_STREAM_MANY_MAX_ROWS = 64, 256
 ZVX_COMM_ID_BYTES = 128
 ZVX_LOUD_PER_ROW, ZVX_LOUD_COMMON = 0, 1
@@ -173,6 +174,9 @@ def load():
     lib.zvx_dev_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]
     lib.zvx_dev_free.argtypes = [vp, vp]
     lib.zvx_dev_to_host.argtypes = [vp, vp, vp, C.c_size_t]
+    lib.zvx_dev_copy.argtypes = [vp, vp, vp, C.c_size_t]
+    lib.zvx_spk_score.argtypes = [vp, vp, C.c_int, vp, C.c_int64, C.c_int, vp, C.c_int]
+    lib.zvx_spk_topk.argtypes = [vp, vp, C.c_int, vp, C.c_int64, C.c_int, C.c_int, vp, vp, C.c_int]
     lib.zvx_dev_from_host.argtypes = [vp, vp, vp, C.c_size_t]
     lib.zvx_spkemb_ex.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int]
     lib.zvx_wait_host.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
@@ -363,6 +367,58 @@ class Context:
         self._chk(self._lib.zvx_spkemb_wav(self._h, C.c_void_p(int(ptr)), _ptr(n), B, int(Nmax), self._rate(rate), C.byref(prm), C.c_void_p(int(out_ptr)),
                                            _ptr(begin), _ptr(end), _ptr(frames), ZVX_DEVICE_IN | ZVX_DEVICE_OUT | (ZVX_NO_SYNC if no_sync else 0)))
         return begin, end, frames
+
+    # ---- voice matching (include/zvx.h: zvx_spk_score, zvx_spk_topk) -----------------------------------------------
+    def _spk_queries(self, queries, dim):
+        """host queries [B][dim] (or [B][1][dim], or one [dim]) -> (pointer, B, dim, flags 0)"""
+        dim = self.hidden if dim is None else int(dim)
+        q = _f32(queries)
+        if q.ndim == 3 and q.shape[1] == 1:
+            q = q[:, 0, :]
+        q = np.ascontiguousarray(q.reshape(-1, dim) if q.ndim == 1 else q)
+        if q.ndim != 2 or q.shape[1] != dim:
+            raise ValueError(f"queries of shape {tuple(np.shape(queries))} are not [B][{dim}]")
+        return _ptr(q), q.shape[0], dim, 0
+
+    def spk_score(self, queries, lib_ptr, K, dim=None):
+        """zvx_spk_score: cosine scores of host queries [B][dim] against the K device rows at lib_ptr -> score [B][K] float32
+        (dim: None = the model's hidden width).  A score that is not finite is -2."""
+        qp, B, dim, flags = self._spk_queries(queries, dim)
+        out = np.empty((B, int(K)), np.float32)
+        self._chk(self._lib.zvx_spk_score(self._h, qp, B, C.c_void_p(int(lib_ptr)), int(K), dim, _ptr(out), flags))
+        return out
+
+    def spk_score_device(self, q_ptr, B, lib_ptr, K, out_ptr=None, dim=None, no_sync=False):
+        """zvx_spk_score with device queries [B][dim] at q_ptr (ZVX_DEVICE_IN; stream order is the fence behind a queued zvx_spkemb_wav)
+        -> score [B][K] float32 on the host, or with out_ptr into device scores there (ZVX_DEVICE_OUT; with no_sync the call only queues)"""
+        dim = self.hidden if dim is None else int(dim)
+        if out_ptr is None:
+            out = np.empty((int(B), int(K)), np.float32)
+            self._chk(self._lib.zvx_spk_score(self._h, C.c_void_p(int(q_ptr)), int(B), C.c_void_p(int(lib_ptr)), int(K), dim, _ptr(out), ZVX_DEVICE_IN))
+            return out
+        self._chk(self._lib.zvx_spk_score(self._h, C.c_void_p(int(q_ptr)), int(B), C.c_void_p(int(lib_ptr)), int(K), dim, C.c_void_p(int(out_ptr)),
+                                          ZVX_DEVICE_IN | ZVX_DEVICE_OUT | (ZVX_NO_SYNC if no_sync else 0)))
+
+    def spk_topk(self, queries, lib_ptr, K, top=5, dim=None):
+        """zvx_spk_topk: per host query the `top` best cosine scores against the K device rows at lib_ptr, by descending score and
+        ascending index among equal scores -> (score [B][top] float32, index [B][top] int32)"""
+        qp, B, dim, flags = self._spk_queries(queries, dim)
+        score, index = np.empty((B, int(top)), np.float32), np.empty((B, int(top)), np.int32)
+        self._chk(self._lib.zvx_spk_topk(self._h, qp, B, C.c_void_p(int(lib_ptr)), int(K), dim, int(top), _ptr(score), _ptr(index), flags))
+        return score, index
+
+    def spk_topk_device(self, q_ptr, B, lib_ptr, K, score_ptr=None, index_ptr=None, top=5, dim=None, no_sync=False):
+        """zvx_spk_topk with device queries (ZVX_DEVICE_IN) -> (score, index) [B][top] on the host, or with score_ptr / index_ptr into
+        device results [B][top] f32 / int32 there (ZVX_DEVICE_OUT [| ZVX_NO_SYNC])"""
+        dim = self.hidden if dim is None else int(dim)
+        if score_ptr is None:
+            score, index = np.empty((int(B), int(top)), np.float32), np.empty((int(B), int(top)), np.int32)
+            self._chk(self._lib.zvx_spk_topk(self._h, C.c_void_p(int(q_ptr)), int(B), C.c_void_p(int(lib_ptr)), int(K), dim, int(top), _ptr(score),
+                                             _ptr(index), ZVX_DEVICE_IN))
+            return score, index
+        self._chk(self._lib.zvx_spk_topk(self._h, C.c_void_p(int(q_ptr)), int(B), C.c_void_p(int(lib_ptr)), int(K), dim, int(top),
+                                         C.c_void_p(int(score_ptr)), C.c_void_p(int(index_ptr)),
+                                         ZVX_DEVICE_IN | ZVX_DEVICE_OUT | (ZVX_NO_SYNC if no_sync else 0)))
 
     def melspec(self, wavs):
         """list of 1-D float waveforms -> (log-mel [B][Tmax][n_mels], frames [B])   (get_mel_from_wav on the device)"""
@@ -1166,6 +1222,10 @@ class Context:
         P = _i32(P)
         self._chk(self._lib.zvx_vocode_mel(self._h, C.c_void_p(int(mel_ptr)), _ptr(P), len(P), int(Pmax), C.c_void_p(int(wav_ptr)), int(wav_stride),
                                            ZVX_DEVICE_IN | ZVX_DEVICE_OUT | (ZVX_NO_SYNC if no_sync else 0) | (ZVX_PCM16 if pcm16 else 0)))
+
+    def dev_copy(self, dst: int, src: int, nbytes: int):
+        """device to device (zvx_dev_copy), behind everything queued on the context's stream; the ranges must not overlap"""
+        self._chk(self._lib.zvx_dev_copy(self._h, C.c_void_p(int(dst)), C.c_void_p(int(src)), int(nbytes)))
 
     def dev_to_host(self, ptr: int, shape, dtype):
         out = np.empty(shape, dtype)

@@ -9,7 +9,7 @@ LIB = os.path.join(HERE, "libzvx.so")
 # test-only launcher shim (tests/native/zvx_ktest.hip): tests/test_kernels_gpu.py drives the launchers through it
 KTEST_SRC = os.path.join(os.path.dirname(HERE), "tests", "native", "zvx_ktest.hip")
 KTEST_LIB = os.path.join(HERE, "libzvx_ktest.so")
-SOURCES = ["gemm.hip", "resstream.hip", "pairstream.hip", "narrowstage.hip", "attention.hip", "ops.hip", "spectral.hip", "watermark.hip", "zvx.hip"]
+SOURCES = ["gemm.hip", "resstream.hip", "pairstream.hip", "narrowstage.hip", "attention.hip", "ops.hip", "spectral.hip", "watermark.hip", "voicematch.hip", "zvx.hip"]
 # translation units: (object stem, source, extra -D flags).  gemm.hip is compiled as two units side by side (its fused ResBlock-pair kernels are
 # a third of its instantiations): a clean build takes the time of the larger half
 UNITS = [("gemm", "gemm.hip", ["-DZVX_GEMM_PART=1"]), ("gemm_resfuse", "gemm.hip", ["-DZVX_GEMM_PART=2"])] + \
@@ -17,7 +17,9 @@ UNITS = [("gemm", "gemm.hip", ["-DZVX_GEMM_PART=1"]), ("gemm_resfuse", "gemm.hip
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-inline-asm"]
 # gemm.hip: no NaN is ever a legitimate operand of its epilogue min/max (leaky-relu and its inverse); without this flag every
 # fminf/fmaxf input coming from a bit operation (bf16 unpack) gets a canonicalising `v_max x, x, x` in front (IEEE mode)
-EXTRA_FLAGS = {"gemm.hip": ["-fno-honor-nans"], "pairstream.hip": ["-fno-honor-nans"], "narrowstage.hip": ["-fno-honor-nans"], "resstream.hip": ["-fno-honor-nans"] + (["-DRS_PROFILE"] if os.environ.get("ZVX_RS_PROFILE_BUILD") else [])}
+# voicematch.hip: its main loop is 16 steps unrolled by pragma, each with the tile epilogue behind it; clang's size limit for a pragma
+# unroll (16 K instructions) would leave the top-k forms rolled up, and their per-lane load sets indexed at run time: in scratch
+EXTRA_FLAGS = {"voicematch.hip": ["-mllvm", "-pragma-unroll-threshold=131072"], "gemm.hip": ["-fno-honor-nans"], "pairstream.hip": ["-fno-honor-nans"], "narrowstage.hip": ["-fno-honor-nans"], "resstream.hip": ["-fno-honor-nans"] + (["-DRS_PROFILE"] if os.environ.get("ZVX_RS_PROFILE_BUILD") else [])}
 
 
 def _stale(target, deps):
@@ -57,7 +59,7 @@ def resources():
 
 def build(force: bool = False, verbose: bool = True) -> str:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
-    headers = [os.path.join(CSRC, "zvx_kernels.h"), os.path.join(CSRC, "mfma_util.h"), os.path.join(CSRC, "stream_plan.h"), os.path.join(CSRC, "spectral_fft.h"), os.path.join(CSRC, "watermark_kernels.h"), os.path.join(os.path.dirname(HERE), "include", "zvx.h")]
+    headers = [os.path.join(CSRC, "zvx_kernels.h"), os.path.join(CSRC, "mfma_util.h"), os.path.join(CSRC, "stream_plan.h"), os.path.join(CSRC, "spectral_fft.h"), os.path.join(CSRC, "watermark_kernels.h"), os.path.join(CSRC, "voicematch_kernels.h"), os.path.join(os.path.dirname(HERE), "include", "zvx.h")]
     def compile_one(unit):
         stem, src, defs = unit
         s = os.path.join(CSRC, src)

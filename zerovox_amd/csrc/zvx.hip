@@ -6,6 +6,7 @@
 #include "../../include/zvx.h"
 #include "zvx_kernels.h"
 #include "watermark_kernels.h"
+#include "voicematch_kernels.h"
 #include "stream_plan.h"
 
 #include <dlfcn.h>
@@ -3460,6 +3461,63 @@ void do_watermark_identify(zvx_ctx* c, const float* in, const int32_t* nsamples,
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// voice matching (include/zvx.h: zvx_spk_score, zvx_spk_topk; voicematch.hip): every check before anything is allocated, uploaded or
+// queued.  topk false: the score form (top and index are not read).
+// ------------------------------------------------------------------------------------------------
+void do_spk_match(zvx_ctx* c, const char* who, const float* query, int B, const float* lib, int64_t K, int dim, int top, float* score, int32_t* index,
+                  int flags, bool topk) {
+    flags_check(who, flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC);
+    if (!query) fail(ZVX_E_INVALID, "%s: query is NULL", who);
+    if (!lib) fail(ZVX_E_INVALID, "%s: lib is NULL", who);
+    if (!score) fail(ZVX_E_INVALID, "%s: score is NULL", who);
+    if (topk && !index) fail(ZVX_E_INVALID, "%s: index is NULL", who);
+    if (B <= 0) fail(ZVX_E_INVALID, "%s: B = %d must be positive", who, B);
+    if (K <= 0 || K > (int64_t)INT32_MAX) fail(ZVX_E_INVALID, "%s: K = %lld must lie in [1, 2^31 - 1]", who, (long long)K);
+    if (dim < 4 || dim > SPK_DIM_MAX || dim % 4) fail(ZVX_E_INVALID, "%s: dim %d must be a multiple of 4 in [4, %d]", who, dim, SPK_DIM_MAX);
+    if (topk && (top < 1 || top > ZVX_SPK_TOP_MAX || top > K))
+        fail(ZVX_E_INVALID, "%s: top %d must lie in [1, min(K, %d)] (K = %lld)", who, top, ZVX_SPK_TOP_MAX, (long long)K);
+    if ((uintptr_t)lib & 15) fail(ZVX_E_INVALID, "%s: lib %p is not aligned to 16 bytes", who, (const void*)lib);
+    if (B > 65535) fail(ZVX_E_UNSUPPORTED, "%s: B = %d queries (at most 65535 per call)", who, B);
+    static_assert(ZVX_SPK_TOP_MAX == SPK_TOP_MAX, "the header's cap is the kernels'");
+    SpkArgs a{};
+    a.K = (long)K; a.B = B; a.dim = dim; a.top = topk ? top : 0;
+    if (!launch_spk_match(a, c->stream, true)) fail(ZVX_E_UNSUPPORTED, "%s: the device refuses the kernel's LDS plan", who);
+    const bool dev_out = flags & ZVX_DEVICE_OUT;
+    const long nslab = spk_slabs(a.K);
+    const size_t n_out = (size_t)B * (topk ? (size_t)top : (size_t)K);
+    char* host = topk && !dev_out ? (char*)c->join_pinned(2 * n_out * 4) : nullptr;
+    a.q = rows_to_device(c, "spk", query, B, dim, flags);
+    a.lib = lib;
+    float* out_s = dev_out ? score : c->fbuf(topk ? "spk.top_s" : "spk.score", n_out);
+    int* out_i = !topk ? nullptr : dev_out ? (int*)index : (int*)c->buf("spk.top_i", n_out * 4);
+    if (topk) {
+        a.cand_s = c->fbuf("spk.cand_s", (size_t)B * nslab * top);
+        a.cand_i = (int*)c->buf("spk.cand_i", (size_t)B * nslab * top * 4);
+    } else a.score = out_s;
+    {
+        TagScope scope(c, "spk.match");
+        const double groups = (double)((B + spk_group(dim, a.top) - 1) / spk_group(dim, a.top));
+        c->timed(2.0 * B * (double)K * dim, 4.0 * groups * (double)K * dim + (topk ? 0.0 : 4.0 * B * (double)K), [&] {
+            launch_spk_match(a, c->stream);
+            if (topk) launch_spk_merge(a.cand_s, a.cand_i, B, nslab, top, out_s, out_i, c->stream);
+        });
+    }
+    if (dev_out) {
+        if (!(flags & ZVX_NO_SYNC)) c->sync();
+        return;
+    }
+    if (topk) {
+        HIPCHK(hipMemcpyAsync(host, out_s, n_out * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(host + n_out * 4, out_i, n_out * 4, hipMemcpyDeviceToHost, c->stream));
+        c->sync();                                           // the call's one wait
+        memcpy(score, host, n_out * 4); memcpy(index, host + n_out * 4, n_out * 4);
+    } else {
+        HIPCHK(hipMemcpyAsync(score, out_s, n_out * 4, hipMemcpyDeviceToHost, c->stream));     // (B x K may be large: straight to the caller)
+        c->sync();
+    }
+}
+
 // zvx_resample_rows: every check before anything is allocated, uploaded or queued
 void do_resample_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate_in, int rate_out, void* out, int64_t out_stride,
                       int32_t* out_len, int flags, const zvx_row_window* win) {
@@ -4454,6 +4512,14 @@ zvx_status zvx_watermark_identify(zvx_ctx* c, const float* in, const int32_t* ns
     return guarded(c, [&] { do_watermark_identify(c, in, nsamples, B, Nmax, params, keys, K, window_frames, score, offset, window, best, flags); });
 }
 
+zvx_status zvx_spk_score(zvx_ctx* c, const float* query, int B, const float* lib, int64_t K, int dim, float* score, int flags) {
+    return guarded(c, [&] { do_spk_match(c, "zvx_spk_score", query, B, lib, K, dim, 0, score, nullptr, flags, false); });
+}
+
+zvx_status zvx_spk_topk(zvx_ctx* c, const float* query, int B, const float* lib, int64_t K, int dim, int top, float* score, int32_t* index, int flags) {
+    return guarded(c, [&] { do_spk_match(c, "zvx_spk_topk", query, B, lib, K, dim, top, score, index, flags, true); });
+}
+
 zvx_status zvx_denoise_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias,
                             const zvx_denoise_params* params, void* out, int64_t out_stride, int flags, const zvx_row_window* win) {
     return guarded(c, [&] {
@@ -4814,6 +4880,16 @@ zvx_status zvx_dev_from_host(zvx_ctx* c, void* dst, const void* src, size_t byte
     return guarded(c, [&] {
         if (!dst || !src) fail(ZVX_E_INVALID, "zvx_dev_from_host: NULL pointer");
         HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipStreamSynchronize(c->stream));
+    });
+}
+
+zvx_status zvx_dev_copy(zvx_ctx* c, void* dst, const void* src, size_t bytes) {
+    return guarded(c, [&] {
+        if (!dst || !src) fail(ZVX_E_INVALID, "zvx_dev_copy: NULL pointer");
+        const char* d = (const char*)dst; const char* s = (const char*)src;
+        if (d < s + bytes && s < d + bytes) fail(ZVX_E_INVALID, "zvx_dev_copy: the ranges overlap");
+        if (bytes) HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, c->stream));
         HIPCHK(hipStreamSynchronize(c->stream));
     });
 }

@@ -23,6 +23,10 @@ detectable, and nothing is claimed about audibility or robustness against codecs
 `--identify-watermark KEYFILE FILE`: no synthesis -- KEYFILE holds one candidate key per line (decimal or 0x hex; blank lines and lines that
 start with # are skipped), and the WAV file is searched for all of them in one call (zvx_watermark_identify): the best key, its score, the
 margin over the second best and the decision are printed.  The largest wrong-key score grows with the number of keys tried.
+`--voice-report`: the finished waveform is embedded again on the device and compared with the speaker embedding it was conditioned on
+(zvx_spkemb_wav, zvx_spk_score); the cosine similarity is printed.  No threshold is applied: none is measured.
+`--match-voice LIBRARY.npz FILE`: no synthesis -- the 16-bit mono WAV file is enrolled on the device and searched for in the library of
+voices (voices.VoiceLibrary.save's .npz of names and embeddings; zvx_spk_topk); the best five are printed.
 """
 import argparse
 import os
@@ -66,8 +70,12 @@ def main():
                     help="no synthesis: search the 16-bit mono WAV FILE for KEY's mark and print the result")
     ap.add_argument("--identify-watermark", nargs=2, default=None, metavar=("KEYFILE", "FILE"),
                     help="no synthesis: search the 16-bit mono WAV FILE for the mark of every key in KEYFILE (one per line, decimal or 0x hex)")
+    ap.add_argument("--voice-report", action="store_true",
+                    help="embed the finished waveform again on the device and print its similarity to the speaker embedding asked for")
+    ap.add_argument("--match-voice", nargs=2, default=None, metavar=("LIBRARY.npz", "FILE"),
+                    help="no synthesis: enrol the 16-bit mono WAV FILE on the device and print the best five voices of the library")
     args = ap.parse_args()
-    if args.detect_watermark is None and args.identify_watermark is None and not args.text:
+    if args.detect_watermark is None and args.identify_watermark is None and args.match_voice is None and not args.text:
         ap.error("the text is missing")
     if args.level is not None and (args.long or args.loudness is not None):
         ap.error("--level streams one utterance: it goes with neither --long nor --loudness")
@@ -100,6 +108,19 @@ def main():
         print(f"watermark: {'DETECTED' if res.detected else 'not detected'}: key {res.best} of {len(keys)} (0x{res.key:016x}), score {res.score:.2f}, "
               f"margin {res.margin:.2f} over the second best, threshold {res.threshold:g}, offset {res.offset} frames, window {res.window}")
         return
+    if args.match_voice is not None:
+        import wave
+        from .voices import VoiceLibrary
+        with wave.open(args.match_voice[1], "rb") as f:
+            if f.getnchannels() != 1 or f.getsampwidth() != 2:
+                ap.error("--match-voice reads 16-bit mono WAV files")
+            rate, pcm = f.getframerate(), np.frombuffer(f.readframes(f.getnframes()), np.int16)
+        library = VoiceLibrary.load(synth.model.ctx, args.match_voice[0])
+        query = synth.speaker_embed_batch([pcm.astype(np.float32) / np.float32(32760.0)], rate)
+        for rank, m in enumerate(library.match(query, top=min(5, len(library)))[0]):
+            print(f"{rank + 1}. {m.name} (row {m.index}): similarity {m.score:.4f}")
+        library.close()
+        return
     print("computing speaker embedding...")
     refmel = np.random.default_rng(0).standard_normal((args.refmel_frames, modelcfg["audio"]["num_mels"])).astype(np.float32)
     spkemb = synth.speaker_embed_from_mel(refmel)
@@ -116,7 +137,8 @@ def main():
             wav, segments = synth.tts_long(text, spkemb, speed=args.speed, pitch_shift=args.pitch_shift, pitch_range=args.pitch_range,
                                            energy_shift=args.energy_shift, energy_range=args.energy_range, loudness=args.loudness,
                                            peak_db=args.peak_db, limiter=args.limiter, limiter_ms=args.limiter_ms, denoise=args.denoise,
-                                           report=args.report, pitch_report=args.pitch_report, watermark=args.watermark)
+                                           report=args.report, pitch_report=args.pitch_report, watermark=args.watermark,
+                                           voice_report=args.voice_report)
             elapsed = time.time() - t0
             wav_len = (wav.shape[0] if segments else 0) / sr
             print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, {len(segments)} sentences, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")
@@ -126,6 +148,8 @@ def main():
                 print_report(synth.last_report)
             if args.pitch_report and segments:
                 print(f"pitch report: {synth.last_pitch_report}")
+            if args.voice_report and segments:
+                print(f"voice report: {synth.last_voice_report}")
             if i > warmup:
                 rtf.append(wav_len / elapsed)
             continue
@@ -144,13 +168,16 @@ def main():
                 print_report(synth.loudness_report(wav, sr))
             if args.pitch_report and len(wav):
                 print(f"pitch report: {synth.pitch_report(wav, sr)}")
+            if args.voice_report and len(wav):
+                print(f"voice report: {synth.voice_report(wav, spkemb, sr)}")
             if i > warmup:
                 rtf.append(wav_len / elapsed)
             continue
         wav, phoneme, length = synth.tts(args.text, spkemb, speed=args.speed, pitch_shift=args.pitch_shift, pitch_range=args.pitch_range,
                                          energy_shift=args.energy_shift, energy_range=args.energy_range, loudness=args.loudness,
                                          peak_db=args.peak_db, limiter=args.limiter, limiter_ms=args.limiter_ms, denoise=args.denoise,
-                                         report=args.report, pitch_report=args.pitch_report, watermark=args.watermark)
+                                         report=args.report, pitch_report=args.pitch_report, watermark=args.watermark,
+                                         voice_report=args.voice_report)
         elapsed = time.time() - t0
         wav_len = wav.shape[0] / sr
         print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")
@@ -161,6 +188,8 @@ def main():
             print_report(synth.last_report)
         if args.pitch_report and length:
             print(f"pitch report: {synth.last_pitch_report}")
+        if args.voice_report and length:
+            print(f"voice report: {synth.last_voice_report}")
         if i > warmup:
             rtf.append(wav_len / elapsed)
     if rtf:

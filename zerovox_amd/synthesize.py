@@ -199,7 +199,8 @@ class ZeroVoxTTS:
         return limit_keywords(limiter, limiter_ms, peak_db)
 
     def tts_ex(self, text: str, spkemb, duration=None, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0,
-               loudness=None, peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None, report=False, pitch_report=False, watermark=None):
+               loudness=None, peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None, report=False, pitch_report=False, watermark=None,
+               voice_report=False):
         """-> (wav f32[N], phoneme i32[1,T], length, mel f32[n_mels, L]); empty text -> the reference's sentinel
         (synthesize.py:213-239).  Prosody (include/zvx.h, zvx_prosody): speed = speaking-rate factor (2.0: half the frames),
         pitch / energy shift (in normalised predictor units) and range (spread about the utterance mean).
@@ -225,8 +226,13 @@ class ZeroVoxTTS:
         zvx_true_peak) -- and ``last_report`` holds the report.LoudnessReport (see ``loudness_report``).  The waveform is the same.
         pitch_report: False (the default: nothing is added to the call), True, or a dict of ``pitch_report`` keywords: the delivered
         waveform's F0 track is measured on the device (include/zvx.h, zvx_pitch) and ``last_pitch_report`` holds the pitch.PitchReport
-        with its track -- what pitch_shift / pitch_range did to the audio, in Hz and semitones.  The waveform is the same."""
+        with its track -- what pitch_shift / pitch_range did to the audio, in Hz and semitones.  The waveform is the same.
+        voice_report: False (the default: nothing is added to the call), True, or a dict of ``voice_report`` keywords (top_db,
+        max_seconds): the delivered waveform is embedded again on the device and compared with ``spkemb`` (include/zvx.h, zvx_spkemb_wav
+        and zvx_spk_score), and ``last_voice_report`` holds the voices.VoiceReport -- whose voice was delivered.  The waveform is the
+        same.  No threshold is given: what similarity separates two speakers on a real checkpoint is not measured."""
         pkw = self._pitch_keywords(pitch_report)
+        vkw = self._voice_keywords(voice_report)
         prosody = self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range)
         dn = self._denoise(denoise)
         wm = self._watermark(watermark)
@@ -236,6 +242,8 @@ class ZeroVoxTTS:
         if not phone_ids:
             if pkw is not None:
                 self._last_pitch_report = None               # asked for, nothing to measure: not the previous call's
+            if vkw is not None:
+                self._last_voice_report = None
             return (np.array([[0.0]], dtype=np.float32), np.array([[0]], dtype=np.int32), 0,
                     np.array([[0.0]], dtype=np.float32))
         phoneme = np.array([phone_ids], dtype=np.int32)
@@ -250,6 +258,8 @@ class ZeroVoxTTS:
             print(f"tts timing stats: g2p={t1 - t0}s, synth={time.time() - t1}s")
         if pkw is not None:
             self.pitch_report(wav, **pkw)
+        if vkw is not None:
+            self.voice_report(wav, spkemb, **vkw)
         return wav, phoneme, length, mel
 
     def _post(self, loudness, peak_db, limiter, limiter_ms, denoise=None):
@@ -263,11 +273,11 @@ class ZeroVoxTTS:
         return kw
 
     def tts(self, text: str, spkemb, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0, loudness=None,
-            peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None, report=False, pitch_report=False, watermark=None):
+            peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None, report=False, pitch_report=False, watermark=None, voice_report=False):
         wav, phoneme, length, _ = self.tts_ex(text=text, spkemb=spkemb, speed=speed, pitch_shift=pitch_shift, pitch_range=pitch_range,
                                               energy_shift=energy_shift, energy_range=energy_range, loudness=loudness, peak_db=peak_db,
                                               limiter=limiter, limiter_ms=limiter_ms, denoise=denoise, report=report,
-                                              pitch_report=pitch_report, watermark=watermark)
+                                              pitch_report=pitch_report, watermark=watermark, voice_report=voice_report)
         return wav, phoneme, length
 
     @staticmethod
@@ -350,6 +360,59 @@ class ZeroVoxTTS:
         stats = self._model.ctx.pitch([_float_row(wav)], rate=rate, **keywords)
         self._last_pitch_report = PitchReport.from_stats(stats)
         return self._last_pitch_report
+
+    VOICE_KEYWORDS = ("top_db", "max_seconds")
+
+    @classmethod
+    def _voice_keywords(cls, voice_report):
+        """the voice_report keyword of tts / tts_ex / tts_long -> None (nothing is measured) or the checked ``voice_report`` keywords"""
+        if voice_report is None or voice_report is False:
+            return None
+        if voice_report is True:
+            return {}
+        if not isinstance(voice_report, dict):
+            raise ValueError(f"voice_report must be False, True or a dict of voice_report keywords, not {voice_report!r}")
+        unknown = sorted(set(voice_report) - set(cls.VOICE_KEYWORDS))
+        if unknown:
+            raise ValueError(f"voice_report: unknown keyword {unknown[0]!r} (one of {', '.join(cls.VOICE_KEYWORDS)})")
+        return dict(voice_report)
+
+    def voice_report(self, wav, spkemb, sampling_rate=None, *, top_db=40.0, max_seconds=30.0):
+        """Whose voice was delivered: the cosine similarity ("SIM") between the speaker embedding of a waveform at sampling_rate Hz (None:
+        ``output_rate``) and ``spkemb`` ([hidden], [1, hidden] or [1, 1, hidden]), both on the device: the waveform is enrolled as a
+        reference clip is (include/zvx.h, zvx_spkemb_wav: converted to the model's rate, trimmed at top_db, cut to max_seconds; None: no
+        cut) and its embedding, which stays on the device, is scored against ``spkemb`` by zvx_spk_score
+        -> voices.VoiceReport(similarity, frames, begin, end); also kept as ``last_voice_report``.  int16 PCM is read as the samples it
+        encodes (/ 32760).  There is NO default threshold: ``VoiceReport.meets(min_similarity)`` takes the caller's.  What similarity
+        separates two speakers depends on the checkpoint's speaker encoder and is not measured here, and no perceptual meaning is claimed
+        for the figure."""
+        from .voices import VoiceReport, rows_2d
+        ctx = self._model.ctx
+        e = rows_2d(spkemb, ctx.hidden, "spkemb")
+        if e.shape[0] != 1:
+            raise ValueError(f"voice_report: one embedding, not {e.shape[0]}")
+        row = _float_row(wav)
+        rate = self.output_rate if sampling_rate is None else int(sampling_rate)
+        cut = 0 if max_seconds is None else max(1, int(round(float(max_seconds) * self._sampling_rate)))
+        n = len(row)
+        row_bytes, emb_bytes = (max(n, 1) * 4 + 255) & ~255, (ctx.hidden * 4 + 255) & ~255
+        buf = ctx.dev_alloc(row_bytes + 2 * emb_bytes)       # the row, its embedding, the embedding asked for
+        try:
+            q, lib = buf + row_bytes, buf + row_bytes + emb_bytes
+            if n:
+                ctx.dev_from_host(buf, row)
+            ctx.dev_from_host(lib, e)
+            begin, end, frames = ctx.spkemb_wav_device(buf, [n], max(n, 1), q, rate, top_db=float(top_db), max_samples=cut, no_sync=True)
+            score = ctx.spk_score_device(q, 1, lib, 1)
+        finally:
+            ctx.dev_free(buf)
+        self._last_voice_report = VoiceReport(similarity=float(score[0, 0]), frames=int(frames[0]), begin=int(begin[0]), end=int(end[0]))
+        return self._last_voice_report
+
+    @property
+    def last_voice_report(self):
+        """the voices.VoiceReport of the last tts / tts_ex / tts_long call with voice_report or ``voice_report`` call (None before)"""
+        return getattr(self, "_last_voice_report", None)
 
     @property
     def last_pitch_report(self):
@@ -569,7 +632,7 @@ class ZeroVoxTTS:
     def tts_long(self, text: str, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20, fade_ms=5, max_batch=32, max_frames=2048, pcm16=False,
                  durations=None, max_chars=200, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0,
                  loudness=None, peak_db=-1.0, loudness_mode="paragraph", limiter=False, limiter_ms=5.0, denoise=None, report=False,
-                 pitch_report=False, watermark=None):
+                 pitch_report=False, watermark=None, voice_report=False):
         """A paragraph -> (wav, segments): one waveform with every sentence in text order (not in the reference).  The text is split by
         longform.split_sentences; the sentences run in batches of at most max_batch, each batch ONE queued synthesize call into
         consecutive rows of one device buffer (every row is the fresh-model ``tts`` of its sentence; a sentence of more than max_frames
@@ -606,10 +669,14 @@ class ZeroVoxTTS:
         measurement runs behind the synthesis, and zvx_pitch takes at most 65536 frames per row: a paragraph whose joined waveform is
         longer than that at the hop (about 760 s at the model's rate and hop 256) must pass a larger one, ``pitch_report=dict(hop=512)``.
         Where it is not, the ZvxError (ZVX_E_UNSUPPORTED) is raised with the finished ``(wav, segments)`` in its ``result`` attribute,
-        so that the waveform is not lost, and ``last_pitch_report`` is None."""
+        so that the waveform is not lost, and ``last_pitch_report`` is None.
+        voice_report: False (the default: nothing is added to the call), True, or a dict of ``voice_report`` keywords: the joined waveform
+        is embedded again on the device (its first max_seconds, 30 by default) and compared with ``spkemb``; ``last_voice_report``
+        holds the voices.VoiceReport (see tts_ex).  No threshold is given."""
         from ._lib import ZvxError
         from .longform import synthesize_long
         pkw = self._pitch_keywords(pitch_report)
+        vkw = self._voice_keywords(voice_report)
         wav, segments = synthesize_long(self, text, spkemb, pauses=pauses, trim_db=trim_db, keep_ms=keep_ms, fade_ms=fade_ms, max_batch=max_batch,
                                max_frames=max_frames, pcm16=pcm16, durations=durations, max_chars=max_chars,
                                prosody=self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range),
@@ -624,6 +691,10 @@ class ZeroVoxTTS:
             except ZvxError as e:
                 e.result = (wav, segments)
                 raise
+        if vkw is not None:
+            self._last_voice_report = None
+        if vkw is not None and segments:
+            self.voice_report(wav, spkemb, **vkw)
         return wav, segments
 
     @property
