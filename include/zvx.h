@@ -157,8 +157,12 @@ zvx_status zvx_spkemb_wav(zvx_ctx* ctx, const float* wav, const int32_t* nsample
 
 /* Log-mel front end of reference audio: wav [B][Nmax] f32 in [-1, 1] with nsamples[b] valid samples ->
  * mel [B][Tmax][n_mels] = log(clip(mel_basis . |STFT|, 1e-5)) (reflect padding (n_fft-hop)/2, hann window, center=False)
- * and frames[b] = 1 + (nsamples[b] + 2*pad - n_fft) / hop.  Rows >= frames[b] are zero.  ZVX_E_INVALID if an utterance is
- * shorter than pad + 1 samples or has more than Tmax frames.
+ * and frames[b] = 1 + (nsamples[b] + 2*pad - n_fft) / hop, pad = (n_fft-hop)/2 rounded down.  The window is the periodic Hann of
+ * win_length samples centred in n_fft; the mel basis is Slaney's (area-normalised triangles on the Slaney mel scale between fmin and
+ * fmax).  Rows >= frames[b] are zero.  ZVX_E_INVALID if an utterance has fewer than max(pad + 1, n_fft - 2*pad) samples (a mirror on
+ * both sides, one whole frame) or more than Nmax; ZVX_E_BUFFER if an utterance has more than Tmax frames.  Either message names the
+ * utterance, and a refused call writes nothing.  The model's STFT: fft_size a multiple of 4, 1 <= hop_size <= fft_size,
+ * 1 <= win_length <= fft_size, 0 <= fmin < fmax <= sampling_rate / 2 (pack_model and zvx_create refuse anything else by name).
  * Replaces get_mel_from_wav (mels.py:357-395) as called by ZeroVoxTTS.speaker_embed (synthesize.py:128-137). */
 zvx_status zvx_melspec(zvx_ctx* ctx, const float* wav, const int32_t* nsamples, int B, int Nmax, float* mel, int Tmax,
                        int32_t* frames);

@@ -690,7 +690,8 @@ def make_gemm(name, seed=0, *, dtype, M, N, K, nbatch=1, nheads=1, lens=None, ou
               res_inv_slope=10.0, accum_mode=0, accum_dtype=None, out_scale=1.0, post=False, out_dtype=None, has_out=True, K2=0,
               bflat=0, xcd_flat=1, slab_small=0, out_split3=0, k_len=None, flat=False, ds=False, fused=0, dil1=1, slope1=0.1,
               no_pairstream=0, row_gap=0, sample=None, x_scale=1.0, big=False, bias_scale=0.5, grid_data=None, aux_scale=1.0):
-    """A GemmArgs problem in the production memory layout: X [b][rows][ldx] (rows = bflat or M + row_gap), W [tap][N][ldw],
+    """A GemmArgs problem in the production memory layout: X [b][rows][ldx] (rows = bflat or M + row_gap; with ldx < K the rows overlap:
+    X [b][x_bs] holds (M + row_gap - 1) ldx + K elements per utterance, the frame GEMM of the log-mel front end), W [tap][N][ldw],
     out / res / accum [b][rows][ld].  Rows past in_len (and columns past K) hold NaN; output buffers are sentinel-filled by the runner."""
     rng = _rng(seed)
     # grid data (the fused pairs by default): small multiples of powers of two and sparse weights, so that every fp32 partial sum of
@@ -733,15 +734,23 @@ def make_gemm(name, seed=0, *, dtype, M, N, K, nbatch=1, nheads=1, lens=None, ou
     if k_len is not None:
         d["k_len"] = list(k_len)
     d["x_bs"] = xrows * ldx
+    overlap = ldx < K                                   # rows that overlap (frames of a signal, hop = ldx): X is a signal per utterance
+    if overlap:
+        assert not two_d and not bflat and ntaps == 1 and k_len is None and not K2 and not fused
+        d["x_bs"] = ((xrows - 1) * ldx + K + 3 & ~3) + 4
+        while d["x_bs"] % ldx == 0:                     # ... whose stride is no multiple of ldx: no row of one utterance is a row of the next
+            d["x_bs"] += 4
     d["o_bs"] = orows * ldo * (3 if out_split3 else 1) if not two_d else M * ldo
     if out_split3:
         d["ldo"] = 3 * N
         d["o_bs"] = orows * 3 * N
     p = Problem("gemm", d)
     # X: valid rows random, masked rows NaN; columns past K NaN
-    X = np.full((nbatch, xrows, ldx), np.nan)
+    X = np.full((nbatch, d["x_bs"]) if overlap else (nbatch, xrows, ldx), np.nan)
     for b in range(nbatch):
-        if two_d:
+        if overlap:                                     # (lens - 1) ldx + K readable elements, NaN behind the last of them
+            X[b, :(lens[b] - 1) * ldx + K] = rnd((lens[b] - 1) * ldx + K, x_scale, "x")
+        elif two_d:
             for u in range(hin):
                 X[b, u * win:u * win + lens[b], :K] = _rand(rng, (lens[b], K), x_scale)
         else:
@@ -996,6 +1005,12 @@ def _gemm_table():
             du=[t // 3 - 1 for t in range(9)], stride=2, wout=9, hin=8, win=18, packed=False, post=True, bias_mode=0, act=ACT_RELU)
         # attention P.V with per-utterance k_len, one head: K = Lp, keys past roundup8(len) NaN
         add(f"pv_klen_heads_{n}", vid, dtype=dt, M=40, N=64, K=48, nbatch=3, nheads=1, lens=[40, 1, 13], k_len=[40, 1, 13], packed=False, bias_mode=0)
+    # the frame GEMM of the log-mel front end (mel_from_padded): rows that overlap (ldx = hop < K = n_fft), an utterance stride that is no
+    # multiple of ldx, a length-1 utterance, N no multiple of 32, no bias -- on the 64 x 64 tile, and past 512 tiles on the 128 x 128 one,
+    # there with row starts at 4-byte, not 16-byte boundaries (ldx = 18: a hop that is no multiple of 4)
+    add("frames_overlap_f32", 19, dtype=F32, M=100, N=68, K=64, ldx=16, ldo=68, nbatch=3, lens=[100, 1, 65], packed=False, bias_mode=0)
+    add("frames_overlap_big_f32", 3, dtype=F32, M=22000, N=68, K=64, ldx=18, ldo=68, nbatch=3, lens=[22000, 1, 21900], packed=False, bias_mode=0,
+        big=True)
     big = [("gemm128x128", 0, 3, dict(M=1024, N=128, K=64, nbatch=64)), ("gemm256x64", 1, 4, dict(M=2048, N=64, K=32, nbatch=64)),
            ("gemm256x32", 2, 5, dict(M=2048, N=32, K=32, nbatch=64))]
     for nm, v16, v32, kw in big:

@@ -189,22 +189,33 @@ def test_wm_bands_interval(lib, name):
 _ctx = {}
 
 
-def ctx_at(n_fft, hop, wl):
-    """the denoiser tests' tiny synthetic context; a hop other than the tiny vocoder's 256 gets a vocoder of two stages with that product"""
-    from zerovox_amd import _lib, config as zcfg, pack, weights as zw
-    if hop == 256:
-        import test_denoise_gpu as TD
-        return TD.ctx_for(n_fft, hop, wl)
-    if (n_fft, hop, wl) not in _ctx:
-        cfg = zcfg.reduced_modelcfg("styletts")
-        cfg["audio"].update(fft_size=n_fft, hop_size=hop, win_length=wl)
-        h = zcfg.hifigan_config("tiny")
+def packed_at(n_fft, hop, wl, **audio):
+    """(manifest, blob) of ctx_at's model, on the host: the reduced model config with this STFT (audio: further fields of its audio
+    block -- num_mels, sampling_rate, fmin, fmax), the tiny vocoder (a hop other than its 256 gets two stages with that product; its
+    conv_pre takes num_mels channels), weights seed 0"""
+    from zerovox_amd import config as zcfg, pack, weights as zw
+    cfg = zcfg.reduced_modelcfg("styletts")
+    cfg["audio"].update(fft_size=n_fft, hop_size=hop, win_length=wl, **audio)
+    h = zcfg.hifigan_config("tiny")
+    if hop != 256:
         u = int(round(hop ** 0.5))
         assert u * u == hop
-        h.update(upsample_rates=[u, u], upsample_kernel_sizes=[2 * u, 2 * u], upsample_initial_channel=32)
-        man, blob = pack.pack_model(cfg, zw.tts_state_dict(cfg, 0), h, zw.hifigan_state_dict(h, 0), "bf16")
-        _ctx[(n_fft, hop, wl)] = _lib.Context(man, blob, 0)
-    return _ctx[(n_fft, hop, wl)]
+        k = 2 * u if u % 2 == 0 else 3 * u                   # (k - u must be even, k at most 3 u: pack.check_generator_config)
+        h.update(upsample_rates=[u, u], upsample_kernel_sizes=[k, k], upsample_initial_channel=32)
+    return pack.pack_model(cfg, zw.tts_state_dict(cfg, 0), h, zw.hifigan_state_dict(h, 0, cfg["audio"]["num_mels"]), "bf16")
+
+
+def ctx_at(n_fft, hop, wl, **audio):
+    """the denoiser tests' tiny synthetic context; a hop other than the tiny vocoder's 256, or other fields of the audio block, get
+    packed_at's model"""
+    from zerovox_amd import _lib
+    if hop == 256 and not audio:
+        import test_denoise_gpu as TD
+        return TD.ctx_for(n_fft, hop, wl)
+    key = (n_fft, hop, wl) + tuple(sorted(audio.items()))
+    if key not in _ctx:
+        _ctx[key] = _lib.Context(*packed_at(n_fft, hop, wl, **audio), 0)
+    return _ctx[key]
 
 
 def _held(name, out, refs, lens, geom, mg):

@@ -786,6 +786,21 @@ void read_config(zvx_ctx* c) {
     }
     if (c->has("voc.pre_w") && (c->t("voc.pre_w").dims.size() != 3 || c->t("voc.pre_w").dim(2) != c->n_mels))
         fail(ZVX_E_MANIFEST, "n_mels=%d, but voc.pre_w (the generator's conv_pre) takes %d channels", c->n_mels, c->t("voc.pre_w").dims.size() == 3 ? c->t("voc.pre_w").dim(2) : -1);
+    // The STFT the log-mel front end runs (mel_from_padded; pack.check_model_config makes the same checks).  The frame GEMM reads a frame as
+    // K = fft_size floats in 16-byte chunks guarded per chunk (gemm_kernel: k < Kb): a fft_size that is no multiple of 4 would let the last
+    // chunk of a frame read on into the signal, against basis elements of the NEXT basis row.  hop > fft_size makes the reflect padding
+    // (fft_size - hop) / 2 negative.  The two constant matrices have the shapes these two numbers give.
+    if (c->cfg.count("fft_size") || c->has("mel.dft")) {
+        const int n_fft = c->cfg_int("fft_size"), nf = n_fft / 2 + 1;
+        if (n_fft < 4 || n_fft % 4) fail(ZVX_E_UNSUPPORTED, "fft_size=%d must be a multiple of 4 (the frame GEMM reads a frame in groups of 4 floats)", n_fft);
+        if (c->hop < 1 || c->hop > n_fft) fail(ZVX_E_UNSUPPORTED, "hop=%d must lie in 1..fft_size=%d (the reflect padding is (fft_size - hop) / 2)", c->hop, n_fft);
+        const Tensor& dft = c->t("mel.dft");
+        if (dft.dims.size() != 3 || dft.dim(2) != n_fft || dft.dim(1) != ((2 * nf + 3) & ~3))
+            fail(ZVX_E_MANIFEST, "mel.dft is not [1][%d][fft_size=%d]", (2 * nf + 3) & ~3, n_fft);
+        const Tensor& mb = c->t("mel.basis");
+        if (mb.dims.size() != 3 || mb.dim(1) != c->n_mels || mb.dim(2) != ((nf + 3) & ~3))
+            fail(ZVX_E_MANIFEST, "mel.basis is not [1][n_mels=%d][%d] (fft_size=%d)", c->n_mels, (nf + 3) & ~3, n_fft);
+    }
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -2034,14 +2049,14 @@ void run_melspec(zvx_ctx* c, const float* wav, const int32_t* nsamples, int B, i
     const int n_fft = c->t("mel.dft").dim(2), nm = c->n_mels, hop = c->hop;
     const int pad = (n_fft - hop) / 2;
     std::vector<int> frames(B);
-    int Tf = 0;
+    int Tf = 0, b_long = 0;
     for (int b = 0; b < B; b++) {
         const int n = nsamples[b];
         if (n > Nmax || n < pad + 1 || n + 2 * pad < n_fft) fail(ZVX_E_INVALID, "zvx_melspec: utterance %d has %d samples (need %d..%d)", b, n, std::max(pad + 1, n_fft - 2 * pad), Nmax);
         frames[b] = 1 + (n + 2 * pad - n_fft) / hop;
-        Tf = std::max(Tf, frames[b]);
+        if (frames[b] > Tf) { Tf = frames[b]; b_long = b; }
     }
-    if (Tf > Tmax) fail(ZVX_E_BUFFER, "zvx_melspec: %d frames do not fit Tmax = %d", Tf, Tmax);
+    if (Tf > Tmax) fail(ZVX_E_BUFFER, "zvx_melspec: the %d frames of utterance %d do not fit Tmax = %d", Tf, b_long, Tmax);
     c->stage_begin(ZVX_T_SPKEMB);
     const long Npad = ((long)Nmax + 2 * pad + 3) & ~3L;
     float* wav_d = c->fbuf("mel.wav", (size_t)B * Nmax);

@@ -189,6 +189,34 @@ def check_model_config(modelcfg: dict, precision: str = "bf16", conv_pre_channel
             raise ValueError(f"resnet.num_filters[{i}] = {c} must be a multiple of 8, at most 256")
     if conv_pre_channels is not None and int(conv_pre_channels) != n_mels:
         raise ValueError(f"num_mels = {n_mels}, but the generator's conv_pre takes {int(conv_pre_channels)} channels")
+    check_stft_config(a)
+
+
+def check_stft_config(audio: dict):
+    """Raises ValueError (naming the field of modelcfg.yaml's audio block) for an STFT the log-mel front end (zvx_melspec) does not run:
+
+    * ``fft_size`` is a multiple of 4: the frame GEMM reads a frame as fft_size floats in 16-byte groups guarded per group, so the last
+      group of any other size would read on into the signal, against elements of the next basis row.  No power of two is needed;
+    * 1 <= ``hop_size`` <= ``fft_size``: the reflect padding is (fft_size - hop_size) // 2, and C's division and Python's disagree on a
+      negative one.  The hop need not be a multiple of 4 (a frame then starts at a 4-byte, not a 16-byte boundary, which the loads take);
+    * 1 <= ``win_length`` <= ``fft_size``: the periodic Hann window sits centred in the frame;
+    * 0 <= ``fmin`` < ``fmax`` <= ``sampling_rate`` / 2: the Slaney filters lie between them, below Nyquist.
+
+    ``zvx_create`` makes the checks on fft_size and the hop (the manifest's ``hop``); win_length, fmin and fmax are no manifest keys: they
+    reach the device only inside the two matrices packed here."""
+    n_fft, hop = int(audio["fft_size"]), int(audio["hop_size"])
+    wl, rate = int(audio.get("win_length", n_fft)), audio["sampling_rate"]
+    fmin, fmax = audio["fmin"], audio["fmax"]
+    if n_fft < 4 or n_fft % 4:
+        raise ValueError(f"fft_size = {n_fft} must be a multiple of 4 (the frame GEMM reads a frame in groups of 4 floats)")
+    if hop < 1 or hop > n_fft:
+        raise ValueError(f"hop_size = {hop} must lie in 1..fft_size = {n_fft} (the reflect padding is (fft_size - hop_size) // 2)")
+    if wl < 1 or wl > n_fft:
+        raise ValueError(f"win_length = {wl} must lie in 1..fft_size = {n_fft} (the window is centred in the frame)")
+    if fmin < 0 or fmin >= fmax:
+        raise ValueError(f"fmin = {fmin} must lie in 0..fmax = {fmax}, below fmax")
+    if fmax > rate / 2:
+        raise ValueError(f"fmax = {fmax} exceeds sampling_rate / 2 = {rate / 2}")
 
 
 def pack_model(modelcfg: dict, tts_sd: dict, hifigan_cfg: dict, hifigan_sd: dict, precision: str = "bf16"):
