@@ -1140,6 +1140,84 @@ zvx_status zvx_spk_score(zvx_ctx* ctx, const float* query, int B, const float* l
 zvx_status zvx_spk_topk(zvx_ctx* ctx, const float* query, int B, const float* lib, int64_t K, int dim, int top, float* score /* [B][top] */,
                         int32_t* index /* [B][top] */, int flags);
 
+/* Alignment: dynamic time warping (DTW) of B independent pairs of feature sequences on the device.  Pair p uses rows a[p][0 .. Ta[p]) and
+ * b[p][0 .. Tb[p]) of [B][Tamax][dim] and [B][Tbmax][dim] f32; nothing else of the padding is read.
+ * Definition, per pair, with i < Ta and j < Tb:
+ *   Local distance: d(i, j) = sqrt(sum_k ((double) a[i][k] - (double) b[j][k])^2) in double; the sum in any order, with or without fma.
+ *   Recurrence: C(0, 0) = d(0, 0); otherwise C(i, j) = d(i, j) + min(C(i-1, j-1), C(i-1, j), C(i, j-1)), a missing neighbour taken as
+ *     +inf: one double addition per cell, so there is no order freedom beyond d.
+ *   Path: backtracked from (Ta-1, Tb-1) to (0, 0) over the device's own values of C; among equal candidates the order is the diagonal,
+ *     then (i-1, j), then (i, j-1).
+ *   Outputs: cost = C(Ta-1, Tb-1);  path_len = L, the number of cells of the path;  path[0 .. L) = its cells (i, j) in forward order, (0, 0)
+ *     first;  a2b[i] = (min j, max j) over the path's cells of row i, for i < Ta.  Entries past L and rows past Ta are not written.
+ *   A backtrack decision is AMBIGUOUS, and either step is allowed there, when its two smallest candidates lie within a relative 1e-9 of
+ *     each other.
+ *   The result is deterministic from run to run.  Pairs are independent: a pair's bits depend neither on B, nor on Tamax / Tbmax, nor on its
+ *     neighbours.
+ *   Derived bounds (not measurements): every term of a path's sum is non-negative, so the accumulated rounding of any path's sum is at most
+ *     (Ta + Tb + dim) 2^-53 relative, and |cost - cost_ref| <= 2 (Ta + Tb + dim) 2^-53 cost_ref against the float64 restatement
+ *     (tests/align_ref.py): about 2e-12 at the size limit, far inside the ambiguity band.  Where the reference's own path holds no ambiguous
+ *     decision, the device's path equals it cell for cell.  This assumes a faithfully rounded f64 sqrt; tests/test_align_gpu.py checks d on
+ *     perfect squares (dim 1, integer features: d is the exact integer).
+ *     Measured on an MI355X against tests/align_ref.py (tests/test_align_gpu.py, pairs from 1 x 1 to 4096 x 4096): a largest relative
+ *     deviation of 0 -- every cost has the bits of the reference's, and every path is the reference's.
+ *   Non-finite input: zvx_vocode_mel's rule -- the call succeeds, that pair is unspecified (its path is still a monotone path of at most
+ *     Ta + Tb - 1 cells), every other pair keeps its bits.
+ * Launches (zerovox_amd/csrc/align.hip).  Forward: one workgroup per pair, 64 .. 1024 lanes (the call's longest Ta rounded up to a wave; the
+ *   bits do not depend on it).  The rows of a are taken in bands of that many; lane l of a band keeps row i0 + l of a in registers and
+ *   the band sweeps its anti-diagonals, one barrier per step.  The left neighbour is the lane's own previous value, the up neighbour the
+ *   next-lower lane's previous value through a double-buffered LDS line (between waves and inside them: no DPP form was built), the diagonal
+ *   neighbour the up value read one step earlier; the last row of a band waits in an LDS edge of Tb doubles for the next band.  The b rows
+ *   are read from memory two steps ahead of their cell and the distance is formed one step ahead of it, so that between two barriers only
+ *   the LDS read, the minimum, the addition and the stores wait for each other.  The direction of every cell goes to a context work buffer as one byte, diagonal-major per pair
+ *   (diagonal s contiguous, its offset computed analytically): Ta Tb bytes per pair.  LDS: 48 KiB per workgroup (32 KiB edge, 16 KiB line).
+ *   Backtrack: one wave per pair; one lane walks the direction bytes (one dependent load per step; no LDS tile was built), the wave then
+ *   turns the reversed cells round into `path` and fills a2b.  No atomics, no workgroup that waits for another.  The call waits once, for
+ *   the host outputs.
+ * Validation, before anything is queued (the context stays usable).  ZVX_E_INVALID: a NULL ctx / a / b / Ta / Tb / cost / path_len; B < 1;
+ *   dim < 1; a Ta[p] outside [1, Tamax] or Tb[p] outside [1, Tbmax]; path given with path_stride < max_p (Ta[p] + Tb[p] - 1); a flag other
+ *   than ZVX_DEVICE_IN; a non-zero reserved field.  ZVX_E_UNSUPPORTED: dim > 32; a Ta[p] or Tb[p] above 4096; B > 65535; more than 2^30
+ *   cells in the call (sum_p Ta[p] Tb[p]).  The message names the pair.
+ * Stage tag "post.align" (one timed group per call; its two launches also under "post.align.forward" / "post.align.backtrack"):
+ *   algorithmic bytes = sum_p ((Ta + Tb) dim 4 + Ta Tb).
+ * Not here: a Sakoe-Chiba band or other path constraints, subsequence / open-end DTW, soft-DTW, pairs longer than 4096 frames, a streaming
+ *   form. */
+typedef struct zvx_dtw_params { int32_t reserved[4]; } zvx_dtw_params;   /* all zero; NULL allowed */
+zvx_status zvx_dtw(zvx_ctx* ctx,
+                   const float* a, const int32_t* Ta, int Tamax,   /* [B][Tamax][dim] f32 */
+                   const float* b, const int32_t* Tb, int Tbmax,   /* [B][Tbmax][dim] f32 */
+                   int B, int dim, const zvx_dtw_params* params,
+                   double* cost,        /* host [B], required */
+                   int32_t* path_len,   /* host [B], required */
+                   int32_t* path,       /* host [B][path_stride][2] (i, j), forward order, or NULL */
+                   int64_t path_stride,
+                   int32_t* a2b,        /* host [B][Tamax][2]: first and last j matched to frame i, or NULL */
+                   int flags            /* ZVX_DEVICE_IN only: a and b are device pointers */);
+
+/* Two batches of waveforms at the model's rate in, their alignment and a mel-cepstral distortion out; the chain stays on the device.
+ *   1. The log-mel of both batches by zvx_melspec's path: a row's log-mel is bit for bit zvx_melspec's of that row.  The refusals are
+ *      zvx_melspec's; the message names the side (a or b) and the row.
+ *   2. Cepstra: c[t][k-1] = (float) (sqrt(2 / M) sum_m L[t][m] cos(pi k (m + 1/2) / M)), k = 1 .. n_cep, M = n_mels; the sum in double from
+ *      the f32 log-mel, in any order, rounded once; c0 is left out; the cosine table is built on the host in double.  They lie within one
+ *      f32 ulp of the float64 DCT of that log-mel.
+ *   3. zvx_dtw's two launches on the cepstra with dim = n_cep: COST, path and a2b are bit for bit what zvx_dtw returns on them.
+ * stats[p]: FRAMES_A, FRAMES_B (mel frames of the two rows), PATH_LEN, COST, and MCD_DB = (10 / ln 10) sqrt(2) COST / PATH_LEN in double
+ *   (the front end's log is the natural log, so the constant is the usual one).
+ * What this MCD is: the distortion between DCT cepstra of the model's own log-mel, c0 left out, averaged over the cells of the DTW path.
+ *   What it is not: figures from SPTK / WORLD mel-cepstral analysis, as papers quote them, are not comparable with it, and no perceptual
+ *   claim is made.
+ * path [B][path_stride][2], a2b [B][a2b_stride][2], cep_a / cep_b [B][cep_stride][n_cep] are optional host outputs (cepstra rows past a
+ *   row's frames are zero up to the longest row of their side).  ZVX_E_INVALID beyond the above: a NULL params or stats, n_cep outside
+ *   [1, min(32, n_mels - 1)], a non-zero reserved field, a2b_stride or cep_stride smaller than the longest row they hold, a flag other than
+ *   ZVX_DEVICE_IN.  ZVX_E_UNSUPPORTED: zvx_dtw's limits, on the frame counts. */
+typedef struct zvx_align_params { int32_t n_cep; /* 1 .. min(32, n_mels - 1); 13 is the default of the bindings */ int32_t reserved[3]; } zvx_align_params;
+enum { ZVX_AL_FRAMES_A = 0, ZVX_AL_FRAMES_B, ZVX_AL_PATH_LEN, ZVX_AL_COST, ZVX_AL_MCD_DB, ZVX_AL_COUNT = 5 };
+zvx_status zvx_align_wav(zvx_ctx* ctx, const float* wav_a, const int32_t* n_a, int Nmax_a,
+                         const float* wav_b, const int32_t* n_b, int Nmax_b, int B,
+                         const zvx_align_params* params, double* stats /* host [B][ZVX_AL_COUNT] */,
+                         int32_t* path, int64_t path_stride, int32_t* a2b /* [B][a2b_stride][2] */, int64_t a2b_stride,
+                         float* cep_a, float* cep_b /* host [B][cep_stride][n_cep] or NULL */, int64_t cep_stride, int flags);
+
 /* Device buffers for ZVX_DEVICE_OUT outputs / zvx_comm_gather without any other GPU runtime in the process. */
 zvx_status zvx_dev_alloc(zvx_ctx* ctx, size_t bytes, void** out);
 zvx_status zvx_dev_free(zvx_ctx* ctx, void* p);
@@ -1164,7 +1242,7 @@ typedef struct {
 } zvx_kernel_stat;
 int        zvx_kernel_stats(zvx_ctx* ctx, zvx_kernel_stat* out, int max_out);
 /* The same counters grouped by pipeline stage ("encoder", "variance", "lenreg", "decoder", "decoder.norm", "voc.pre",
- * "voc.up1".."voc.res4", "voc.post", "voc.resample", "voc.stream", "post.join", "post.loudness", "post.limit", "post.denoise", "post.watermark", "post.wmdetect", "post.wmidentify", "spkemb"; name = stage): every launch of the stage, including the HBM-bound helper
+ * "voc.up1".."voc.res4", "voc.post", "voc.resample", "voc.stream", "post.join", "post.loudness", "post.limit", "post.denoise", "post.watermark", "post.wmdetect", "post.wmidentify", "post.align", "spkemb"; name = stage): every launch of the stage, including the HBM-bound helper
  * kernels, while "profile" == 2 and "profile_only" == -1.  Feeds the per-stage roofline fractions of bench.py. */
 int        zvx_tag_stats(zvx_ctx* ctx, zvx_kernel_stat* out, int max_out);
 zvx_status zvx_reset_stats(zvx_ctx* ctx);

@@ -29,7 +29,10 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_denoise_ex", "zvx_stream_open", "zvx_stream_next", "zvx_stream_info", "zvx_stream_close", "zvx_stream_next_many",
            "zvx_denoise_rows", "zvx_limit_rows", "zvx_resample_rows", "zvx_level", "zvx_level_ex", "zvx_level_rows", "zvx_loudness_stats",
            "zvx_pitch", "zvx_watermark", "zvx_watermark_ex", "zvx_watermark_detect", "zvx_watermark_rows", "zvx_watermark_identify",
-           "zvx_stream_open_ex", "zvx_spk_score", "zvx_spk_topk", "zvx_dev_copy")
+           "zvx_stream_open_ex", "zvx_spk_score", "zvx_spk_topk", "zvx_dev_copy", "zvx_dtw", "zvx_align_wav")
+# columns of zvx_align_wav's stats[B][ZVX_AL_COUNT]
+ZVX_AL_FRAMES_A, ZVX_AL_FRAMES_B, ZVX_AL_PATH_LEN, ZVX_AL_COST, ZVX_AL_MCD_DB, ZVX_AL_COUNT = range(6)
+DTW_MAX_FRAMES, DTW_MAX_DIM = 4096, 32               # zvx_dtw's caps (csrc/zvx_kernels.h; ZVX_E_UNSUPPORTED beyond)
 ZVX_SPK_TOP_MAX = 32                                 # the most places zvx_spk_topk returns per query
 ZVX_STREAM_MANY_MAX_SESSIONS, ZVX_STREAM_MANY_MAX_ROWS = 64, 256
 ZVX_COMM_ID_BYTES = 128
@@ -91,6 +94,16 @@ class PitchParams(C.Structure):
     """zvx_pitch_params (include/zvx.h)"""
     _fields_ = [("fmin", C.c_float), ("fmax", C.c_float), ("threshold", C.c_float), ("gate_db", C.c_float), ("window", C.c_int32),
                 ("hop", C.c_int32)]
+
+
+class DtwParams(C.Structure):
+    """zvx_dtw_params (include/zvx.h)"""
+    _fields_ = [("reserved", C.c_int32 * 4)]
+
+
+class AlignParams(C.Structure):
+    """zvx_align_params (include/zvx.h)"""
+    _fields_ = [("n_cep", C.c_int32), ("reserved", C.c_int32 * 3)]
 
 
 class DenoiseParams(C.Structure):
@@ -188,6 +201,9 @@ def load():
     lib.zvx_normalize.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(LoudnessParams), vp, C.c_int64, vp, vp, vp, C.c_int]
     lib.zvx_loudness_stats.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, C.c_int64, C.c_int]
     lib.zvx_pitch.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(PitchParams), vp, vp, C.c_int64, vp, vp, C.c_int]
+    lib.zvx_dtw.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(DtwParams), vp, vp, vp, C.c_int64, vp, C.c_int]
+    lib.zvx_align_wav.argtypes = [vp, vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, C.POINTER(AlignParams), vp, vp, C.c_int64, vp, C.c_int64, vp, vp,
+                                  C.c_int64, C.c_int]
     lib.zvx_true_peak.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, C.c_int]
     lib.zvx_limit.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(LimitParams), vp, C.c_int64, vp, vp, C.c_int]
     lib.zvx_limit_ex.argtypes = lib.zvx_limit.argtypes + [C.c_int64, C.c_int64, C.c_int64, C.c_int]
@@ -664,6 +680,86 @@ class Context:
         if curves:
             res["f0"] = [f0[b, :fr[b]] for b in range(B)]
             res["aper"] = [aper[b, :fr[b]] for b in range(B)]
+        return res
+
+    @staticmethod
+    def _feature_rows(rows, lengths):
+        """a list of [T][dim] arrays, or a padded [B][Tmax][dim] array + lengths -> (x [B][Tmax][dim] f32, T [B] i32)"""
+        if lengths is None:
+            rows = [np.asarray(r, np.float32) for r in rows]
+            rows = [r.reshape(-1, 1) if r.ndim == 1 else r for r in rows]
+            T = np.array([r.shape[0] for r in rows], np.int32)
+            dim = rows[0].shape[1] if rows else 0
+            if any(r.ndim != 2 or r.shape[1] != dim for r in rows):
+                raise ValueError("feature rows must all be [T][dim] with one dim")
+            x = np.zeros((len(rows), max(int(T.max()) if len(rows) else 0, 1), dim), np.float32)
+            for b, r in enumerate(rows):
+                x[b, :T[b]] = r
+            return x, T
+        x = np.ascontiguousarray(rows, np.float32)
+        if x.ndim != 3:
+            raise ValueError(f"padded feature rows of shape {x.shape} are not [B][Tmax][dim]")
+        return x, _i32(lengths, (x.shape[0],))
+
+    def dtw(self, a, b, lengths_a=None, lengths_b=None, path=True):
+        """zvx_dtw: dynamic time warping of B pairs of feature sequences (lists of [T][dim] arrays, or padded [B][Tmax][dim] arrays +
+        lengths) under the Euclidean local distance in double -> a dict: cost [B] float64, path_len [B] int32, a2b (a list of B int32
+        arrays [Ta][2]: the first and last frame of b matched to each frame of a) and, with path, path (a list of B int32 arrays
+        [path_len][2] of cells (i, j) from (0, 0) on)."""
+        xa, Ta = self._feature_rows(a, lengths_a)
+        xb, Tb = self._feature_rows(b, lengths_b)
+        if xa.shape[0] != xb.shape[0] or xa.shape[2] != xb.shape[2]:
+            raise ValueError(f"a {xa.shape} and b {xb.shape} do not pair up ([B][T][dim])")
+        return self._dtw(_ptr(xa), Ta, xa.shape[1], _ptr(xb), Tb, xb.shape[1], xa.shape[2], path, 0)
+
+    def dtw_device(self, a_ptr, lengths_a, Tamax, b_ptr, lengths_b, Tbmax, dim, path=True):
+        """zvx_dtw on device rows [B][Tamax][dim] / [B][Tbmax][dim] f32 (ZVX_DEVICE_IN; stream order is the fence) -> as dtw()."""
+        return self._dtw(C.c_void_p(int(a_ptr)), _i32(lengths_a), int(Tamax), C.c_void_p(int(b_ptr)), _i32(lengths_b), int(Tbmax), int(dim), path,
+                         ZVX_DEVICE_IN)
+
+    def _dtw(self, ap, Ta, Tamax, bp, Tb, Tbmax, dim, path, flags):
+        B = len(Ta)
+        if len(Tb) != B:
+            raise ValueError(f"{B} lengths of a and {len(Tb)} of b")
+        cost, plen = np.zeros(B, np.float64), np.zeros(B, np.int32)
+        stride = max(1, int(np.max(Ta.astype(np.int64) + Tb) - 1)) if B else 1
+        cells = np.zeros((B, stride, 2), np.int32) if path else None
+        a2b = np.zeros((B, max(Tamax, 1), 2), np.int32)
+        self._chk(self._lib.zvx_dtw(self._h, ap, _ptr(Ta), Tamax, bp, _ptr(Tb), Tbmax, B, dim, None, _ptr(cost), _ptr(plen), _ptr(cells), stride,
+                                    _ptr(a2b), flags))
+        res = {"cost": cost, "path_len": plen, "a2b": [a2b[b, :Ta[b]] for b in range(B)]}
+        if path:
+            res["path"] = [cells[b, :plen[b]] for b in range(B)]
+        return res
+
+    def align(self, rows_a, rows_b, n_cep=13, lengths_a=None, lengths_b=None, cepstra=False):
+        """zvx_align_wav: two batches of waveforms at the model's rate (lists of 1-D arrays, or padded 2-D arrays + lengths) -> a dict:
+        frames_a, frames_b, path_len (int32 [B]), cost, mcd_db (float64 [B]), path and a2b as dtw() gives them and, with cepstra, cep_a /
+        cep_b (lists of float32 [frames][n_cep]).  mcd_db is the distortion between DCT cepstra of the model's own log-mel (c0 left out)
+        averaged over the cells of the DTW path: not comparable with SPTK / WORLD figures, and no perceptual claim."""
+        xa, na = self._rows(rows_a, lengths_a)
+        xb, nb = self._rows(rows_b, lengths_b)
+        B = xa.shape[0]
+        if xb.shape[0] != B:
+            raise ValueError(f"{B} rows of a and {xb.shape[0]} of b")
+        n_fft, hop = self.get_int("fft_size"), self.hop
+        pad = (n_fft - hop) // 2
+        fmax = [max(1, 1 + (int(x.shape[1]) + 2 * pad - n_fft) // hop) for x in (xa, xb)]
+        stride = fmax[0] + fmax[1]
+        stats = np.zeros((B, ZVX_AL_COUNT), np.float64)
+        cells, a2b = np.zeros((B, stride, 2), np.int32), np.zeros((B, fmax[0], 2), np.int32)
+        cs = max(fmax)
+        ca = np.zeros((B, cs, int(n_cep)), np.float32) if cepstra else None
+        cb = np.zeros((B, cs, int(n_cep)), np.float32) if cepstra else None
+        prm = AlignParams(int(n_cep))
+        self._chk(self._lib.zvx_align_wav(self._h, _ptr(xa), _ptr(na), xa.shape[1], _ptr(xb), _ptr(nb), xb.shape[1], B, C.byref(prm), _ptr(stats),
+                                          _ptr(cells), stride, _ptr(a2b), fmax[0], _ptr(ca), _ptr(cb), cs, 0))
+        fa, fb, plen = (stats[:, k].astype(np.int32) for k in (ZVX_AL_FRAMES_A, ZVX_AL_FRAMES_B, ZVX_AL_PATH_LEN))
+        res = {"frames_a": fa, "frames_b": fb, "path_len": plen, "cost": stats[:, ZVX_AL_COST].copy(), "mcd_db": stats[:, ZVX_AL_MCD_DB].copy(),
+               "path": [cells[b, :plen[b]] for b in range(B)], "a2b": [a2b[b, :fa[b]] for b in range(B)]}
+        if cepstra:
+            res["cep_a"] = [ca[b, :fa[b]] for b in range(B)]
+            res["cep_b"] = [cb[b, :fb[b]] for b in range(B)]
         return res
 
     def normalize(self, rows, target, *, peak_ceiling=0.891, max_gain_db=20.0, common=False, pcm16=False, rate=None, lengths=None):

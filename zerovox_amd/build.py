@@ -9,7 +9,7 @@ LIB = os.path.join(HERE, "libzvx.so")
 # test-only launcher shim (tests/native/zvx_ktest.hip): tests/test_kernels_gpu.py drives the launchers through it
 KTEST_SRC = os.path.join(os.path.dirname(HERE), "tests", "native", "zvx_ktest.hip")
 KTEST_LIB = os.path.join(HERE, "libzvx_ktest.so")
-SOURCES = ["gemm.hip", "resstream.hip", "pairstream.hip", "narrowstage.hip", "attention.hip", "ops.hip", "spectral.hip", "watermark.hip", "voicematch.hip", "zvx.hip"]
+SOURCES = ["gemm.hip", "resstream.hip", "pairstream.hip", "narrowstage.hip", "attention.hip", "ops.hip", "spectral.hip", "watermark.hip", "voicematch.hip", "align.hip", "zvx.hip"]
 # translation units: (object stem, source, extra -D flags).  gemm.hip is compiled as two units side by side (its fused ResBlock-pair kernels are
 # a third of its instantiations): a clean build takes the time of the larger half
 UNITS = [("gemm", "gemm.hip", ["-DZVX_GEMM_PART=1"]), ("gemm_resfuse", "gemm.hip", ["-DZVX_GEMM_PART=2"])] + \

@@ -2045,27 +2045,48 @@ float* mel_from_padded(zvx_ctx* c, const float* padded, long Npad, const int* fr
     return mel_d;
 }
 
-void run_melspec(zvx_ctx* c, const float* wav, const int32_t* nsamples, int B, int Nmax, float* mel_out, int Tmax, int32_t* frames_out) {
-    const int n_fft = c->t("mel.dft").dim(2), nm = c->n_mels, hop = c->hop;
+// The lengths of a batch of waveforms as the front end takes them: frames per row and the most of them.  `side` NULL: zvx_melspec's own message;
+// otherwise the caller's name and the side of its pair of batches (zvx_align_wav)
+int melspec_frames(zvx_ctx* c, const char* who, const char* side, const int32_t* nsamples, int B, int Nmax, std::vector<int>& frames, int* b_long) {
+    const int n_fft = c->t("mel.dft").dim(2), hop = c->hop;
     const int pad = (n_fft - hop) / 2;
-    std::vector<int> frames(B);
-    int Tf = 0, b_long = 0;
+    frames.assign((size_t)B, 0);
+    int Tf = 0;
+    *b_long = 0;
     for (int b = 0; b < B; b++) {
         const int n = nsamples[b];
-        if (n > Nmax || n < pad + 1 || n + 2 * pad < n_fft) fail(ZVX_E_INVALID, "zvx_melspec: utterance %d has %d samples (need %d..%d)", b, n, std::max(pad + 1, n_fft - 2 * pad), Nmax);
+        if (n > Nmax || n < pad + 1 || n + 2 * pad < n_fft) {
+            if (!side) fail(ZVX_E_INVALID, "zvx_melspec: utterance %d has %d samples (need %d..%d)", b, n, std::max(pad + 1, n_fft - 2 * pad), Nmax);
+            fail(ZVX_E_INVALID, "%s: side %s, row %d has %d samples (need %d..%d)", who, side, b, n, std::max(pad + 1, n_fft - 2 * pad), Nmax);
+        }
         frames[b] = 1 + (n + 2 * pad - n_fft) / hop;
-        if (frames[b] > Tf) { Tf = frames[b]; b_long = b; }
+        if (frames[b] > Tf) { Tf = frames[b]; *b_long = b; }
     }
-    if (Tf > Tmax) fail(ZVX_E_BUFFER, "zvx_melspec: the %d frames of utterance %d do not fit Tmax = %d", Tf, b_long, Tmax);
-    c->stage_begin(ZVX_T_SPKEMB);
+    return Tf;
+}
+// Upload (or, device_in, copy) the rows, pad, and queue the front end: "mel.out" [B][Tf][n_mels]; *fr_out: the frames on the device
+float* melspec_queue(zvx_ctx* c, const float* wav, const int32_t* nsamples, const std::vector<int>& frames, int B, int Nmax, int Tf, bool device_in, int** fr_out) {
+    const int n_fft = c->t("mel.dft").dim(2), hop = c->hop;
+    const int pad = (n_fft - hop) / 2;
     const long Npad = ((long)Nmax + 2 * pad + 3) & ~3L;
     float* wav_d = c->fbuf("mel.wav", (size_t)B * Nmax);
-    HIPCHK(hipMemcpyAsync(wav_d, wav, (size_t)B * Nmax * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(hipMemcpyAsync(wav_d, wav, (size_t)B * Nmax * 4, device_in ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c->stream));
     int* n_d = c->upload_ints("mel.n", nsamples, B);
     int* fr_d = c->upload_ints("mel.frames", frames.data(), B);
     float* padded = c->fbuf("mel.pad", (size_t)B * Npad);
     launch_reflect_pad(wav_d, Nmax, n_d, padded, Npad, pad, B, (int)Npad, c->stream);
-    float* mel_d = mel_from_padded(c, padded, Npad, fr_d, B, Tf);
+    if (fr_out) *fr_out = fr_d;
+    return mel_from_padded(c, padded, Npad, fr_d, B, Tf);
+}
+
+void run_melspec(zvx_ctx* c, const float* wav, const int32_t* nsamples, int B, int Nmax, float* mel_out, int Tmax, int32_t* frames_out) {
+    const int nm = c->n_mels;
+    std::vector<int> frames;
+    int b_long = 0;
+    const int Tf = melspec_frames(c, "zvx_melspec", nullptr, nsamples, B, Nmax, frames, &b_long);
+    if (Tf > Tmax) fail(ZVX_E_BUFFER, "zvx_melspec: the %d frames of utterance %d do not fit Tmax = %d", Tf, b_long, Tmax);
+    c->stage_begin(ZVX_T_SPKEMB);
+    float* mel_d = melspec_queue(c, wav, nsamples, frames, B, Nmax, Tf, false, nullptr);
     c->stage_end(ZVX_T_SPKEMB);
     if (mel_out) {
         if (Tmax > Tf) memset(mel_out, 0, (size_t)B * Tmax * nm * 4);
@@ -3533,6 +3554,149 @@ void do_spk_match(zvx_ctx* c, const char* who, const float* query, int B, const 
     }
 }
 
+// ------------------------------------------------------------------------------------------------
+// alignment (include/zvx.h: zvx_dtw, zvx_align_wav; align.hip).  dtw_check holds every check of the lengths and is pure; dtw_run works on
+// device rows, queues the two launches and delivers the host outputs behind the call's one wait.
+// ------------------------------------------------------------------------------------------------
+struct DtwPlan { long cells = 0, pcells = 0, rows = 0; int ta_max = 0, p_max = 0; double row_bytes = 0; };
+DtwPlan dtw_check(const char* who, const int32_t* Ta, int Tamax, const int32_t* Tb, int Tbmax, int B, int dim, bool want_path, int64_t path_stride) {
+    if (B < 1) fail(ZVX_E_INVALID, "%s: B = %d must be positive", who, B);
+    if (dim < 1) fail(ZVX_E_INVALID, "%s: dim = %d must be positive", who, dim);
+    DtwPlan pl;
+    for (int b = 0; b < B; b++) {
+        if (Ta[b] < 1 || Ta[b] > Tamax) fail(ZVX_E_INVALID, "%s: pair %d: Ta = %d out of range (1..%d)", who, b, Ta[b], Tamax);
+        if (Tb[b] < 1 || Tb[b] > Tbmax) fail(ZVX_E_INVALID, "%s: pair %d: Tb = %d out of range (1..%d)", who, b, Tb[b], Tbmax);
+        pl.p_max = std::max<long>(pl.p_max, std::min<long>((long)Ta[b] + Tb[b] - 1, INT32_MAX));
+    }
+    if (want_path && path_stride < pl.p_max)
+        fail(ZVX_E_INVALID, "%s: path_stride %lld is smaller than the longest possible path, %d cells", who, (long long)path_stride, pl.p_max);
+    if (dim > DTW_MAX_DIM) fail(ZVX_E_UNSUPPORTED, "%s: dim = %d (at most %d)", who, dim, DTW_MAX_DIM);
+    for (int b = 0; b < B; b++)
+        if (Ta[b] > DTW_MAX_T || Tb[b] > DTW_MAX_T)
+            fail(ZVX_E_UNSUPPORTED, "%s: pair %d has %d x %d frames (at most %d a side)", who, b, Ta[b], Tb[b], DTW_MAX_T);
+    if (B > 65535) fail(ZVX_E_UNSUPPORTED, "%s: B = %d pairs (at most 65535 per call)", who, B);
+    for (int b = 0; b < B; b++) {
+        pl.cells += (long)Ta[b] * Tb[b]; pl.pcells += Ta[b] + Tb[b] - 1; pl.rows += Ta[b];
+        pl.ta_max = std::max(pl.ta_max, (int)Ta[b]);
+        pl.row_bytes += 4.0 * dim * ((double)Ta[b] + Tb[b]);
+        if (pl.cells > (1L << 30)) fail(ZVX_E_UNSUPPORTED, "%s: more than 2^30 cells in the call (reached at pair %d)", who, b);
+    }
+    return pl;
+}
+void dtw_run(zvx_ctx* c, const DtwPlan& pl, const float* a_d, const int32_t* Ta, int Tamax, const float* b_d, const int32_t* Tb, int Tbmax, int B, int dim,
+             double* cost, int32_t* path_len, int32_t* path, int64_t path_stride, int32_t* a2b, int64_t a2b_stride) {
+    const size_t cost_b = ((size_t)B * 8 + 255) & ~(size_t)255, len_b = ((size_t)B * 4 + 255) & ~(size_t)255;
+    const size_t path_b = (size_t)pl.pcells * 8, a2b_b = (size_t)pl.rows * 8;
+    char* host = (char*)c->join_pinned(cost_b + len_b + (path ? path_b : 0) + (a2b ? a2b_b : 0));
+    DtwArgs g{};
+    g.B = B; g.dim = dim; g.lanes = dtw_lanes(dim, pl.ta_max);
+    g.dir = (unsigned char*)c->buf("al.dir", (size_t)pl.cells);
+    g.cost = (double*)c->buf("al.cost", (size_t)B * 8);
+    g.path_len = (int*)c->buf("al.len", (size_t)B * 4);
+    g.rev = (int*)c->buf("al.rev", path_b);
+    g.path = (int*)c->buf("al.path", path_b);
+    g.a2b = (int*)c->buf("al.a2b", a2b_b);
+    std::vector<DtwPair> tab((size_t)B);
+    long d_off = 0, p_off = 0, r_off = 0;
+    for (int b = 0; b < B; b++) {
+        tab[(size_t)b] = DtwPair{a_d + (size_t)b * Tamax * dim, b_d + (size_t)b * Tbmax * dim, Ta[b], Tb[b], d_off, p_off, r_off};
+        d_off += (long)Ta[b] * Tb[b]; p_off += Ta[b] + Tb[b] - 1; r_off += Ta[b];
+    }
+    DtwPair* tab_d = (DtwPair*)c->buf("al.pairs", (size_t)B * sizeof(DtwPair));
+    c->upload(tab_d, tab.data(), (size_t)B * sizeof(DtwPair));
+    g.pairs = tab_d;
+    {
+        TagScope scope(c, "post.align");
+        // one group per call under "post.align"; inside it each launch is a group of its own under a tag of its own (tools/align_bench.py)
+        c->timed(0.0, pl.row_bytes + (double)pl.cells, [&] {
+            { TagScope fwd(c, "post.align.forward"); c->timed(0.0, pl.row_bytes + (double)pl.cells, [&] { launch_dtw_forward(g, c->stream); }); }
+            { TagScope back(c, "post.align.backtrack"); c->timed(0.0, (double)pl.cells, [&] { launch_dtw_backtrack(g, c->stream); }); }
+        });
+    }
+    char* len_h = host + cost_b; char* path_h = len_h + len_b; char* a2b_h = path_h + (path ? path_b : 0);
+    HIPCHK(hipMemcpyAsync(host, g.cost, (size_t)B * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(hipMemcpyAsync(len_h, g.path_len, (size_t)B * 4, hipMemcpyDeviceToHost, c->stream));
+    if (path) HIPCHK(hipMemcpyAsync(path_h, g.path, path_b, hipMemcpyDeviceToHost, c->stream));
+    if (a2b) HIPCHK(hipMemcpyAsync(a2b_h, g.a2b, a2b_b, hipMemcpyDeviceToHost, c->stream));
+    c->sync();                                               // the call's one wait
+    memcpy(cost, host, (size_t)B * 8);
+    memcpy(path_len, len_h, (size_t)B * 4);
+    for (int b = 0; b < B; b++) {
+        const DtwPair& p = tab[(size_t)b];
+        if (path) memcpy(path + (size_t)b * path_stride * 2, path_h + (size_t)p.path_off * 8, (size_t)path_len[b] * 8);
+        if (a2b) memcpy(a2b + (size_t)b * a2b_stride * 2, a2b_h + (size_t)p.a2b_off * 8, (size_t)p.Ta * 8);
+    }
+}
+void do_dtw(zvx_ctx* c, const float* a, const int32_t* Ta, int Tamax, const float* b, const int32_t* Tb, int Tbmax, int B, int dim,
+            const zvx_dtw_params* params, double* cost, int32_t* path_len, int32_t* path, int64_t path_stride, int32_t* a2b, int flags) {
+    const char* who = "zvx_dtw";
+    if (!a || !b || !Ta || !Tb) fail(ZVX_E_INVALID, "%s: a, b, Ta or Tb is NULL", who);
+    if (!cost || !path_len) fail(ZVX_E_INVALID, "%s: cost or path_len is NULL", who);
+    flags_check(who, flags, ZVX_DEVICE_IN);
+    if (params) for (int k = 0; k < 4; k++) if (params->reserved[k]) fail(ZVX_E_INVALID, "%s: params->reserved[%d] is %d (must be 0)", who, k, params->reserved[k]);
+    const DtwPlan pl = dtw_check(who, Ta, Tamax, Tb, Tbmax, B, dim, path != nullptr, path_stride);
+    const float* a_d = a;
+    const float* b_d = b;
+    if (!(flags & ZVX_DEVICE_IN)) {
+        const size_t na = (size_t)B * Tamax * dim, nb = (size_t)B * Tbmax * dim;
+        float* ad = c->fbuf("al.a", na);
+        float* bd = c->fbuf("al.b", nb);
+        HIPCHK(hipMemcpyAsync(ad, a, na * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(hipMemcpyAsync(bd, b, nb * 4, hipMemcpyHostToDevice, c->stream));
+        a_d = ad; b_d = bd;
+    }
+    dtw_run(c, pl, a_d, Ta, Tamax, b_d, Tb, Tbmax, B, dim, cost, path_len, path, path_stride, a2b, Tamax);
+}
+void do_align_wav(zvx_ctx* c, const float* wav_a, const int32_t* n_a, int Nmax_a, const float* wav_b, const int32_t* n_b, int Nmax_b, int B,
+                  const zvx_align_params* params, double* stats, int32_t* path, int64_t path_stride, int32_t* a2b, int64_t a2b_stride, float* cep_a,
+                  float* cep_b, int64_t cep_stride, int flags) {
+    const char* who = "zvx_align_wav";
+    if (!wav_a || !wav_b || !n_a || !n_b || B <= 0 || Nmax_a <= 0 || Nmax_b <= 0)
+        fail(ZVX_E_INVALID, "%s: bad arguments (NULL pointer, B = %d, Nmax_a = %d, Nmax_b = %d)", who, B, Nmax_a, Nmax_b);
+    if (!params) fail(ZVX_E_INVALID, "%s: params is NULL", who);
+    if (!stats) fail(ZVX_E_INVALID, "%s: stats is NULL", who);
+    flags_check(who, flags, ZVX_DEVICE_IN);
+    const int nm = c->n_mels, K = params->n_cep;
+    if (K < 1 || K > std::min(DTW_MAX_DIM, nm - 1)) fail(ZVX_E_INVALID, "%s: n_cep %d must lie in [1, %d]", who, K, std::min(DTW_MAX_DIM, nm - 1));
+    for (int k = 0; k < 3; k++) if (params->reserved[k]) fail(ZVX_E_INVALID, "%s: params->reserved[%d] is %d (must be 0)", who, k, params->reserved[k]);
+    std::vector<int> fa, fb;
+    int bl = 0;
+    const int Tfa = melspec_frames(c, who, "a", n_a, B, Nmax_a, fa, &bl);
+    const int Tfb = melspec_frames(c, who, "b", n_b, B, Nmax_b, fb, &bl);
+    if (a2b && a2b_stride < Tfa) fail(ZVX_E_INVALID, "%s: a2b_stride %lld is smaller than the %d frames of the longest row of a", who, (long long)a2b_stride, Tfa);
+    if ((cep_a || cep_b) && cep_stride < std::max(Tfa, Tfb))
+        fail(ZVX_E_INVALID, "%s: cep_stride %lld is smaller than the %d frames of the longest row", who, (long long)cep_stride, std::max(Tfa, Tfb));
+    const DtwPlan pl = dtw_check(who, fa.data(), Tfa, fb.data(), Tfb, B, K, path != nullptr, path_stride);
+    // the cosine table, in double on the host: table[k - 1][m] = cos(pi k (m + 1/2) / M)
+    std::vector<double> tab((size_t)K * nm);
+    for (int k = 1; k <= K; k++) for (int m = 0; m < nm; m++) tab[(size_t)(k - 1) * nm + m] = cos(M_PI * (double)k * ((double)m + 0.5) / (double)nm);
+    double* tab_d = (double*)c->buf("al.dct", tab.size() * 8);
+    c->upload(tab_d, tab.data(), tab.size() * 8);
+    const double scale = sqrt(2.0 / (double)nm);
+    float* cep[2] = {c->fbuf("al.cep_a", (size_t)B * Tfa * K), c->fbuf("al.cep_b", (size_t)B * Tfb * K)};
+    {
+        TagScope scope(c, "post.align.mel");
+        for (int side = 0; side < 2; side++) {
+            int* fr_d = nullptr;
+            const int Tf = side ? Tfb : Tfa;
+            const float* mel_d = melspec_queue(c, side ? wav_b : wav_a, side ? n_b : n_a, side ? fb : fa, B, side ? Nmax_b : Nmax_a, Tf,
+                                               (flags & ZVX_DEVICE_IN) != 0, &fr_d);
+            c->timed(2.0 * B * (double)Tf * nm * K, 4.0 * B * (double)Tf * (nm + K), [&] { launch_cepstra(mel_d, Tf, fr_d, B, nm, K, tab_d, scale, cep[side], c->stream); });
+        }
+    }
+    if (cep_a) copy_out_rows(c, cep[0], Tfa, K, cep_a, (long)cep_stride, B, false);
+    if (cep_b) copy_out_rows(c, cep[1], Tfb, K, cep_b, (long)cep_stride, B, false);
+    std::vector<double> cost((size_t)B);
+    std::vector<int32_t> plen((size_t)B);
+    dtw_run(c, pl, cep[0], fa.data(), Tfa, cep[1], fb.data(), Tfb, B, K, cost.data(), plen.data(), path, path_stride, a2b, a2b_stride);
+    for (int b = 0; b < B; b++) {
+        double* o = stats + (size_t)b * ZVX_AL_COUNT;
+        o[ZVX_AL_FRAMES_A] = (double)fa[(size_t)b]; o[ZVX_AL_FRAMES_B] = (double)fb[(size_t)b]; o[ZVX_AL_PATH_LEN] = (double)plen[(size_t)b];
+        o[ZVX_AL_COST] = cost[(size_t)b];
+        o[ZVX_AL_MCD_DB] = (10.0 / log(10.0)) * sqrt(2.0) * cost[(size_t)b] / (double)plen[(size_t)b];
+    }
+}
+
 // zvx_resample_rows: every check before anything is allocated, uploaded or queued
 void do_resample_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate_in, int rate_out, void* out, int64_t out_stride,
                       int32_t* out_len, int flags, const zvx_row_window* win) {
@@ -4450,6 +4614,18 @@ zvx_status zvx_loudness_stats(zvx_ctx* c, const float* in, const int32_t* nsampl
 zvx_status zvx_pitch(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_pitch_params* params, float* f0,
                      float* aper, int64_t f_stride, int32_t* frames, double* stats, int flags) {
     return guarded(c, [&] { do_pitch(c, in, nsamples, B, Nmax, rate, params, f0, aper, f_stride, frames, stats, flags); });
+}
+
+zvx_status zvx_dtw(zvx_ctx* c, const float* a, const int32_t* Ta, int Tamax, const float* b, const int32_t* Tb, int Tbmax, int B, int dim,
+                   const zvx_dtw_params* params, double* cost, int32_t* path_len, int32_t* path, int64_t path_stride, int32_t* a2b, int flags) {
+    return guarded(c, [&] { do_dtw(c, a, Ta, Tamax, b, Tb, Tbmax, B, dim, params, cost, path_len, path, path_stride, a2b, flags); });
+}
+zvx_status zvx_align_wav(zvx_ctx* c, const float* wav_a, const int32_t* n_a, int Nmax_a, const float* wav_b, const int32_t* n_b, int Nmax_b, int B,
+                         const zvx_align_params* params, double* stats, int32_t* path, int64_t path_stride, int32_t* a2b, int64_t a2b_stride,
+                         float* cep_a, float* cep_b, int64_t cep_stride, int flags) {
+    return guarded(c, [&] {
+        do_align_wav(c, wav_a, n_a, Nmax_a, wav_b, n_b, Nmax_b, B, params, stats, path, path_stride, a2b, a2b_stride, cep_a, cep_b, cep_stride, flags);
+    });
 }
 
 zvx_status zvx_true_peak(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, int oversample, float* tpeak, int flags) {

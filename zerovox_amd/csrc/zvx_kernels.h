@@ -359,6 +359,32 @@ void launch_pitch_stats(const PitchArgs& a, hipStream_t s);
 // (f0, index) order; the one thread whose count is a target rank stores its f0
 void launch_pitch_rank(const PitchArgs& a, long f_max, hipStream_t s);
 
+// ---- alignment (include/zvx.h, zvx_dtw / zvx_align_wav; align.hip) ----
+constexpr int DTW_MAX_T = 4096;              // frames of one side of a pair
+constexpr int DTW_MAX_DIM = 32;              // columns a lane keeps of its row of a
+constexpr int DTW_MAX_LANES = 1024;          // rows of a band = threads of the forward workgroup
+// one pair: its rows (a: [Ta][dim], b: [Tb][dim], f32, contiguous), and where its part of the call's work buffers starts -- dir_off in
+// bytes (Ta Tb of them), path_off in cells of rev / path (Ta + Tb - 1 of them), a2b_off in rows of a2b (Ta of them)
+struct DtwPair { const float* a; const float* b; int Ta, Tb; long dir_off, path_off, a2b_off; };
+struct DtwArgs {
+    const DtwPair* pairs;                    // [B], on the device
+    int B, dim, lanes;                       // lanes: a multiple of 64 in [64, DTW_MAX_LANES]; the results do not depend on it
+    unsigned char* dir;                      // direction codes, diagonal-major per pair (align.hip)
+    double* cost;                            // [B]
+    int* path_len;                           // [B]
+    int* rev;                                // the path from the end, (i, j) per cell
+    int* path;                               // the path from (0, 0)
+    int* a2b;                                // (first j, last j) per row of a
+};
+// the lanes of the forward workgroup: the call's longest Ta rounded up to a wave, at most 1024 (512 above 16 columns: the registers of a lane)
+inline int dtw_lanes(int dim, int ta_max) { return std::min(dim > 16 ? DTW_MAX_LANES / 2 : DTW_MAX_LANES, (ta_max + 63) / 64 * 64); }
+// grid = B workgroups of `lanes` = dtw_lanes(...) threads: B <= 65535
+void launch_dtw_forward(const DtwArgs& a, hipStream_t s);
+// grid = B waves; reads dir, writes path_len, rev, path and a2b
+void launch_dtw_backtrack(const DtwArgs& a, hipStream_t s);
+// cep[b][t][k] = (float)(scale * sum_m mel[b][t][m] table[k][m]) in double for t < frames[b], 0 beyond; mel is [B][Tp][M] f32, table [n_cep][M]
+void launch_cepstra(const float* mel, int Tp, const int* frames, int B, int M, int n_cep, const double* table, double scale, float* cep, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------------
 // Small kernels (ops.hip).  T-typed pointers are void* + dtype.
 // ------------------------------------------------------------------------------------------------

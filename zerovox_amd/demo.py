@@ -27,6 +27,11 @@ margin over the second best and the decision are printed.  The largest wrong-key
 (zvx_spkemb_wav, zvx_spk_score); the cosine similarity is printed.  No threshold is applied: none is measured.
 `--match-voice LIBRARY.npz FILE`: no synthesis -- the 16-bit mono WAV file is enrolled on the device and searched for in the library of
 voices (voices.VoiceLibrary.save's .npz of names and embeddings; zvx_spk_topk); the best five are printed.
+`--mcd REF.wav`: the finished waveform is aligned on the device with the 16-bit mono recording of the same sentence (zvx_align_wav) and the
+mel-cepstral distortion along the DTW path is printed.  It is the distortion of DCT cepstra of the model's own log-mel, c0 left out: figures
+from SPTK / WORLD analysis in papers are not comparable with it, and no perceptual claim is made.
+`--rhythm-from REF.wav`: the text is said with the timing of that recording -- a first pass is aligned with it and its per-phoneme frame
+counts become forced durations of the second (tts(rhythm_from=...)).  Whether that sounds right on a real checkpoint is not measured.
 """
 import argparse
 import os
@@ -74,7 +79,12 @@ def main():
                     help="embed the finished waveform again on the device and print its similarity to the speaker embedding asked for")
     ap.add_argument("--match-voice", nargs=2, default=None, metavar=("LIBRARY.npz", "FILE"),
                     help="no synthesis: enrol the 16-bit mono WAV FILE on the device and print the best five voices of the library")
+    ap.add_argument("--mcd", default=None, metavar="REF.wav",
+                    help="align the finished waveform with this 16-bit mono recording of the same sentence on the device and print the distortion")
+    ap.add_argument("--rhythm-from", default=None, metavar="REF.wav", help="copy the timing of this 16-bit mono recording of the same text")
     args = ap.parse_args()
+    if (args.mcd or args.rhythm_from) and (args.long or args.level is not None):
+        ap.error("--mcd and --rhythm-from go with one plain utterance: neither with --long nor with --level")
     if args.detect_watermark is None and args.identify_watermark is None and args.match_voice is None and not args.text:
         ap.error("the text is missing")
     if args.level is not None and (args.long or args.loudness is not None):
@@ -130,6 +140,14 @@ def main():
         print(f"loudness report: {rep}")
         if args.loudness is not None:
             print(f"  meets {args.loudness:g} LUFS +- 0.5 LU, true peak <= {args.peak_db:g} dBTP: {rep.meets(args.loudness, max_true_peak_db=args.peak_db)}")
+
+    def read_ref(path, flag):
+        import wave
+        with wave.open(path, "rb") as f:
+            if f.getnchannels() != 1 or f.getsampwidth() != 2:
+                ap.error(f"{flag} reads 16-bit mono WAV files")
+            return f.getframerate(), np.frombuffer(f.readframes(f.getnframes()), np.int16)
+    rhythm_rate, rhythm = read_ref(args.rhythm_from, "--rhythm-from") if args.rhythm_from else (None, None)
     text = open(args.text, encoding="utf-8").read() if (args.long and os.path.isfile(args.text)) else args.text
     for i in range(args.iter):
         t0 = time.time()
@@ -177,7 +195,7 @@ def main():
                                          energy_shift=args.energy_shift, energy_range=args.energy_range, loudness=args.loudness,
                                          peak_db=args.peak_db, limiter=args.limiter, limiter_ms=args.limiter_ms, denoise=args.denoise,
                                          report=args.report, pitch_report=args.pitch_report, watermark=args.watermark,
-                                         voice_report=args.voice_report)
+                                         voice_report=args.voice_report, rhythm_from=rhythm, rhythm_rate=rhythm_rate)
         elapsed = time.time() - t0
         wav_len = wav.shape[0] / sr
         print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")
@@ -190,6 +208,14 @@ def main():
             print(f"pitch report: {synth.last_pitch_report}")
         if args.voice_report and length:
             print(f"voice report: {synth.last_voice_report}")
+        if rhythm is not None and length:
+            al = synth.last_alignment
+            print(f"rhythm: first pass {al.frames_a} frames against {al.frames_b} of the recording, {length} delivered")
+        if args.mcd and length:
+            ref_rate, ref = read_ref(args.mcd, "--mcd")
+            al = synth.fidelity_report(wav, ref, sampling_rate=ref_rate, wav_rate=sr)
+            print(f"fidelity: {al.mcd_db:.3f} dB between DCT cepstra of the model's log-mel (c0 left out; not comparable with SPTK / WORLD "
+                  f"figures) over {len(al.path)} path cells, {al.frames_a} frames against {al.frames_b}")
         if i > warmup:
             rtf.append(wav_len / elapsed)
     if rtf:

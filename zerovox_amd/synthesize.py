@@ -273,12 +273,68 @@ class ZeroVoxTTS:
         return kw
 
     def tts(self, text: str, spkemb, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0, loudness=None,
-            peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None, report=False, pitch_report=False, watermark=None, voice_report=False):
-        wav, phoneme, length, _ = self.tts_ex(text=text, spkemb=spkemb, speed=speed, pitch_shift=pitch_shift, pitch_range=pitch_range,
+            peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None, report=False, pitch_report=False, watermark=None, voice_report=False,
+            rhythm_from=None, rhythm_rate=None):
+        """-> (wav, phoneme, length): ``tts_ex`` without the mel.  rhythm_from: None (the default: nothing is added to the call), or a
+        recording of the same text at rhythm_rate Hz (None: the model's rate) whose timing is copied: a first pass with predicted durations
+        is aligned with the trimmed recording on the device (``fidelity_report``), align.durations_from turns the path into per-phoneme
+        frame counts, and the second pass runs with them as forced durations -- it has exactly the mel frames of the trimmed recording.
+        ``last_alignment`` holds the alignment of the first pass.  Refused together with speed != 1.0: both set durations.  Whether a
+        copied rhythm sounds right on a real checkpoint is not measured."""
+        duration = None
+        if rhythm_from is not None:
+            if speed != 1.0:
+                raise ValueError(f"rhythm_from and speed={speed!r} both set durations: give one of them")
+            duration = self._rhythm_durations(text, spkemb, rhythm_from, rhythm_rate, dict(pitch_shift=pitch_shift, pitch_range=pitch_range,
+                                                                                          energy_shift=energy_shift, energy_range=energy_range))
+        wav, phoneme, length, _ = self.tts_ex(text=text, spkemb=spkemb, duration=duration, speed=speed, pitch_shift=pitch_shift,
+                                              pitch_range=pitch_range,
                                               energy_shift=energy_shift, energy_range=energy_range, loudness=loudness, peak_db=peak_db,
                                               limiter=limiter, limiter_ms=limiter_ms, denoise=denoise, report=report,
                                               pitch_report=pitch_report, watermark=watermark, voice_report=voice_report)
         return wav, phoneme, length
+
+    def _rhythm_durations(self, text, spkemb, ref_wav, ref_rate, prosody):
+        """the first pass of tts(rhythm_from=...): predicted durations, the alignment of its waveform with the recording, and the
+        per-phoneme frame counts that follow from it (None for an empty text: nothing to align)"""
+        from .align import durations_from
+        wav, phoneme, length, _ = self.tts_ex(text=text, spkemb=spkemb, **prosody)
+        if length == 0:
+            self._last_alignment = None
+            return None
+        T = phoneme.shape[1]
+        first = np.rint(self._model.ctx.fetch("duration", (1, T))[0]).astype(np.int64)
+        al = self.fidelity_report(wav, ref_wav, sampling_rate=ref_rate, wav_rate=self.output_rate)
+        if int(first.sum()) != al.frames_a:
+            raise RuntimeError(f"the first pass has {int(first.sum())} frames by its durations and {al.frames_a} by its waveform")
+        return [int(v) for v in durations_from(al, first)]
+
+    def fidelity_report(self, wav, ref_wav, sampling_rate=None, *, wav_rate=None, n_cep=13):
+        """How far a delivered waveform is from a recording of the same sentence: both at the model's rate (ref_wav at sampling_rate Hz and
+        wav at wav_rate Hz are converted on the device where they are not), the recording trimmed as ``speaker_embed`` trims a reference
+        clip (Context.trim_bounds, top_db 40), then the DTW path between the DCT cepstra of their log-mels and the distortion along it
+        (include/zvx.h, zvx_align_wav) -> align.Alignment(cost, mcd_db, frames_a, frames_b, path, a2b), a = wav and b = the recording; also
+        kept as ``last_alignment``.  mcd_db is the distortion of cepstra of the model's own log-mel with c0 left out: figures from SPTK /
+        WORLD analysis in papers are not comparable with it, and no perceptual claim is made.  There is no default threshold:
+        ``Alignment.meets(max_mcd_db)`` takes the caller's."""
+        from .align import Alignment
+        ctx = self._model.ctx
+        rows = []
+        for w, rate in ((wav, wav_rate), (ref_wav, sampling_rate)):
+            w = _float_row(w)
+            if rate is not None and int(rate) != int(self._sampling_rate):
+                out, n = ctx.resample([w], int(rate), self._sampling_rate)
+                w = np.ascontiguousarray(out[0, :int(n[0])])
+            rows.append(w)
+        begin, end = ctx.trim_bounds([rows[1]], top_db=40.0)
+        rows[1] = np.ascontiguousarray(rows[1][int(begin[0]):int(end[0])])
+        self._last_alignment = Alignment.from_result(ctx.align([rows[0]], [rows[1]], n_cep=n_cep))
+        return self._last_alignment
+
+    @property
+    def last_alignment(self):
+        """the align.Alignment of the last ``fidelity_report`` call or of the first pass of the last tts(rhythm_from=...) (None before)"""
+        return getattr(self, "_last_alignment", None)
 
     @staticmethod
     def _watermark(watermark):
