@@ -1,4 +1,4 @@
-"""Which rule refuses a post-processing call that breaks TWO rules at once (include/zvx.h; the order of the checks in csrc/zvx.hip).
+"""Which rule refuses a post-processing call that breaks TWO rules at once (include/zvx.h; the order of the checks in csrc/host_post.hip and csrc/zvx.hip).
 The entry points share their checks and the call path behind them, so the order in which the checks run is part of what a caller sees:
 for every pair below the status, the entry point's name at the head of the message and the rule the message names are asserted, and that
 the refused call wrote no output sample and issued no launch.  Every call here is answered on the host; no kernel runs.

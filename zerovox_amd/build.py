@@ -9,11 +9,13 @@ LIB = os.path.join(HERE, "libzvx.so")
 # test-only launcher shim (tests/native/zvx_ktest.hip): tests/test_kernels_gpu.py drives the launchers through it
 KTEST_SRC = os.path.join(os.path.dirname(HERE), "tests", "native", "zvx_ktest.hip")
 KTEST_LIB = os.path.join(HERE, "libzvx_ktest.so")
-SOURCES = ["gemm.hip", "resstream.hip", "pairstream.hip", "narrowstage.hip", "attention.hip", "ops.hip", "spectral.hip", "watermark.hip", "voicematch.hip", "align.hip", "zvx.hip"]
+SOURCES = ["gemm.hip", "resstream.hip", "pairstream.hip", "narrowstage.hip", "attention.hip", "ops.hip", "spectral.hip", "watermark.hip", "voicematch.hip", "align.hip"]
+# the host units: launch sequences and the C-ABI behind one internal header (csrc/zvx_host.h); none of them defines a kernel
+HOST_SOURCES = ["host_post.hip", "host_stream.hip", "host_comm.hip", "zvx.hip"]
 # translation units: (object stem, source, extra -D flags).  gemm.hip is compiled as two units side by side (its fused ResBlock-pair kernels are
 # a third of its instantiations): a clean build takes the time of the larger half
 UNITS = [("gemm", "gemm.hip", ["-DZVX_GEMM_PART=1"]), ("gemm_resfuse", "gemm.hip", ["-DZVX_GEMM_PART=2"])] + \
-        [(s_[:-4], s_, []) for s_ in SOURCES[1:]]
+        [(s_[:-4], s_, []) for s_ in SOURCES[1:] + HOST_SOURCES]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function", "-Wno-inline-asm"]
 # gemm.hip: no NaN is ever a legitimate operand of its epilogue min/max (leaky-relu and its inverse); without this flag every
 # fminf/fmaxf input coming from a bit operation (bf16 unpack) gets a canonicalising `v_max x, x, x` in front (IEEE mode)
@@ -60,12 +62,14 @@ def resources():
 def build(force: bool = False, verbose: bool = True) -> str:
     hipcc = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
     headers = [os.path.join(CSRC, "zvx_kernels.h"), os.path.join(CSRC, "mfma_util.h"), os.path.join(CSRC, "stream_plan.h"), os.path.join(CSRC, "spectral_fft.h"), os.path.join(CSRC, "watermark_kernels.h"), os.path.join(CSRC, "voicematch_kernels.h"), os.path.join(os.path.dirname(HERE), "include", "zvx.h")]
+    # a host unit is stale behind the internal header as well; a kernel unit (and the test shim) is not
+    host_headers = headers + [os.path.join(CSRC, "zvx_host.h")]
     def compile_one(unit):
         stem, src, defs = unit
         s = os.path.join(CSRC, src)
         o = os.path.join(CSRC, stem + ".o")
         rj = os.path.join(CSRC, stem + ".resources.json")
-        if force or _stale(o, [s] + headers) or not os.path.exists(rj):
+        if force or _stale(o, [s] + (host_headers if src in HOST_SOURCES else headers)) or not os.path.exists(rj):
             cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get(src, []) + defs + ["-Rpass-analysis=kernel-resource-usage", "-c", s, "-o", o]
             if verbose:
                 print(" ".join(cmd), flush=True)

@@ -1369,7 +1369,7 @@ __global__ __launch_bounds__(256) void k_resample_poly(const ResampleArgs a, int
     // which 4 outputs of a tile a lane takes.  Up-conversion (M < L): tid + 256 q -- neighbouring lanes take neighbouring outputs, whose input
     // windows start at most one sample apart (LDS reads of one address broadcast) and whose phases step by M mod L; each lane stores 4 bytes of
     // a 256-byte run.  Down-conversion: 4 tid + q -- a lane's windows start 4 M / L samples after its neighbour's, and the lane stores its
-    // 4 outputs as one vector.  The bank's pitch is chosen for the same step (zvx.hip, rs_pick_pitch); an output's sum does not depend on it.
+    // 4 outputs as one vector.  The bank's pitch is chosen for the same step (host_post.hip, rs_pick_pitch); an output's sum does not depend on it.
     const bool strided = a.M < a.L;
     const int step = strided ? 256 * a.M : a.M, dk = step / a.L, dp = step % a.L;
     auto put = [&](long i, float v) {
@@ -2437,7 +2437,7 @@ void launch_limit_reduce(const LimitArgs& a, hipStream_t s) {
 // samples [(q - 2) h, (q + 1) h) from zero state; the row holds the signal from in_origin on, so position s is x[s - in_origin], and a
 // position outside [0, n) of the row reads as 0.  The host admits a window only where that happens in front of sample 0 alone: the support
 // condition of include/zvx.h, and for a last window that begins inside its signal the check of the oldest needed unit itself
-// (zvx.hip, level_clamped_support_check: the clamp of the nodes to the last unit can move that unit to the left of what RL covers).
+// (host_post.hip, level_clamped_support_check: the clamp of the nodes to the last unit can move that unit to the left of what RL covers).
 // Same chunks, same 16-byte groups aligned as ADDRESSES with scalar edges, same fma chain; p = u / h goes to p[q - q_first].
 __global__ __launch_bounds__(64) void k_level_units(const LevelArgs a) {
     __shared__ float st[64 * LOUD_LD];

@@ -198,7 +198,7 @@ __global__ __launch_bounds__(WM_THREADS) void k_wm_search(const WmDetectArgs a) 
     }
 }
 
-// Sign tables from keys; the hash is the host's (zvx.hip, wm_mix64), in 64-bit integer arithmetic.  packed == 0: one thread per byte of
+// Sign tables from keys; the hash is the host's (host_post.hip, wm_mix64), in 64-bit integer arithmetic.  packed == 0: one thread per byte of
 // out[n][P][J], +1 / -1 (the embedder's form).  packed != 0: one thread per word of out[n][P][W], W = ceil(J / 32), bit j % 32 of word
 // j / 32 set where the sign is +1 (the form k_wm_search_keys reads: a lane fetches 32 signs of its table row with one load).
 __device__ inline bool wm_sign_plus(unsigned long long key, int c, int j) {

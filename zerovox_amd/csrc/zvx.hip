@@ -1,479 +1,17 @@
-// zvx.hip -- libzvx context, weight loading, launch sequences and the C-ABI (include/zvx.h).
-//
-// Host-side C++ only sequences kernels: every contraction is a launch_gemm() (gemm.hip), everything
-// else a kernel from ops.hip.  One HIP stream per context; workspaces are grown on demand and reused.
-// Reference call structure being replaced: ZeroVox.inference_ex (model.py:308-347).
-#include "../../include/zvx.h"
-#include "zvx_kernels.h"
-#include "watermark_kernels.h"
-#include "voicematch_kernels.h"
-#include "stream_plan.h"
+// zvx.hip -- libzvx weight loading, launch sequences (encoder, variance adaptor, mel decoders, vocoder, speaker encoder, log-mel front end,
+// the measuring calls) and the C-ABI (include/zvx.h) but for zvx_comm_* (host_comm.hip).  The post-processing calls are in host_post.hip, the
+// stream sessions in host_stream.hip; what the units share is in zvx_host.h.
+#include "zvx_host.h"
 
-#include <dlfcn.h>
-#include <math.h>
-#include <cmath>
-#include <rccl/rccl.h>          // types and prototypes only: the library is dlopen'ed by zvx_comm_* (single-GPU use never loads it)
-#include <stdarg.h>
-#include <stdio.h>
-#include <string.h>
-
-#include <algorithm>
-#include <map>
-#include <sstream>
-#include <stdexcept>
-#include <string>
-#include <vector>
-
-using namespace zvx;
-
-namespace {
-
-struct ZvxError : std::runtime_error {
-    int code;
-    ZvxError(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-[[noreturn]] void fail(int code, const char* fmt, ...) {
-    char buf[512];
-    va_list ap; va_start(ap, fmt); vsnprintf(buf, sizeof buf, fmt, ap); va_end(ap);
-    throw ZvxError(code, buf);
-}
-#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) fail(ZVX_E_HIP, "%s failed: %s (%s:%d)", #x, hipGetErrorString(e_), __FILE__, __LINE__); } while (0)
+namespace zvx::host {
 
 thread_local std::string g_create_error;
-
-struct Tensor {
-    char kind = 'p';
-    std::vector<int> dims;
-    size_t off = 0, numel = 0;
-    void* dev = nullptr;
-    int dtype = DT_F32;
-    const float* host = nullptr;
-    float alpha = 1.f;                       // split-plane weights in IEEE half: the planes carry w * 2^s, alpha = 2^-s (applied by the GEMM epilogue)
-    int dim(int i) const { return dims.at(i); }
-};
-
-struct DevBuf { void* p = nullptr; void* base = nullptr; size_t cap = 0; };
-
-struct GemmEvent { hipEvent_t a, b; int variant; double flops, bytes; long rows; int N, K, taps, res, fused; std::string tag, kname; };
-
-}  // namespace
-
-struct zvx_ctx {
-    int device = 0;
-    hipStream_t stream = nullptr;          // the stream launches are being issued on (swapped to a side stream and back by the schedules below)
-    hipStream_t main0 = nullptr;           // the context's main stream (what `stream` is outside those swaps)
-    // multi-GPU (zvx_comm_*): communicator, its own stream, and per-buffer "the gather has read this" events
-    hipStream_t comm_stream = nullptr;
-    hipStream_t voc_aux[2] = {nullptr, nullptr};   // single requests: the non-final pairs of the 2nd / 3rd ResBlock of a vocoder stage run beside the 1st
-    hipEvent_t voc_ev[3] = {nullptr, nullptr, nullptr};
-    int voc_overlap_maxb = 1 << 20;        // zvx_set_int("voc_overlap_maxb", n): batches of at most n utterances use them (0: never; A/B)
-    int voc_overlap_frames = 28672;        // zvx_set_int("voc_overlap_frames", n): ... and only below n mel frames per call (B x Pmax)
-    // Front end of call i+1 under the vocoder of call i (zvx_synthesize): encoder / variance adaptor / length regulator / mel decoder are
-    // issued on front_stream, the vocoder on `stream`.  The two meet in ONE buffer, "mel": the vocoder waits for ev_front_done, the
-    // next call's front end waits for ev_mel_free (recorded behind the vocoder's first kernel, which copies the mel into its padded
-    // input).  A host that queues calls (ZVX_DEVICE_OUT | ZVX_NO_SYNC) gets the latency-paced front end (5-28 % of the matrix roof)
-    // hidden under the previous call's vocoder; a host that waits for every call sees the serial schedule.  Results are bit-identical
-    // (same kernels on the same data).  zvx_set_int("front_overlap", v): 1 (default) = queued calls (ZVX_DEVICE_OUT | ZVX_NO_SYNC) take the
-    // two-stream schedule, 2 = every zvx_synthesize call does (tests), 0 = everything on `stream` (A/B).
-    hipStream_t front_stream = nullptr;
-    hipEvent_t ev_front_done = nullptr, ev_mel_free = nullptr, ev_main_join = nullptr;
-    int front_overlap = 1;
-    bool mel_free_pending = false;         // ev_mel_free is recorded and the front stream has not waited for it yet
-    bool front_dirty_main = true;          // front-end buffers were touched on `stream` (zvx_encode / zvx_decode ...) since the front stream last joined it
-    // Asynchronous host delivery (ZVX_HOST_ASYNC; synthesize.py:233-239 hands the caller host memory): the finished waveform rows go to one
-    // of two PINNED host slots on a copy stream of their own, behind an event the vocoder's last kernel records -- the copy of call i runs
-    // under the front end / vocoder of call i + 1, the host thread never waits inside a synthesis call (zvx_wait_host does).
-    struct HostSlot { void* p = nullptr; size_t cap = 0; hipEvent_t ready = nullptr, done = nullptr; bool pending = false; int B = 0, pcm16 = 0; long stride = 0, need = 0; };
-    HostSlot host_slot[2];
-    int host_next = 0, host_last = -1;
-    hipStream_t copy_stream = nullptr;
-    bool copy_is_comm = false;
-    hipStream_t aux_stream = nullptr;      // second compute stream: the duration predictor of a small batch beside the pitch predictor
-    hipEvent_t ev_aux[2] = {nullptr, nullptr};
-    int va_overlap_maxb = 1 << 20;             // zvx_set_int("va_overlap_maxb", n): batches of at most n utterances overlap the two predictors (0: never; A/B)
-    ncclComm_t comm = nullptr;
-    int rank = 0, world = 1;
-    hipEvent_t ev_compute = nullptr;
-    std::map<const void*, hipEvent_t> gather_fence;
-    std::string err;
-    std::map<std::string, std::string> cfg;
-    std::map<std::string, Tensor> tensors;
-    std::vector<float> host_blob;
-    std::map<std::string, DevBuf> bufs;
-    std::map<const void*, const void*> packed;   // bf16 weight tensor -> its MFMA-fragment-order copy (conv-slab kernel)
-    std::map<const void*, const void*> pair_packed;   // StyleTTS residual blocks with a 1x1 shortcut: conv2 weight tensor -> combined fragment stream [conv2 | shortcut] per channel tile
-    int dt = DT_BF16;               // activation / weight dtype of the bf16-able stages
-    // config
-    int H = 0, emb_dim = 0, punct_dim = 0, n_phone_rows = 0, n_punct_rows = 0, max_txt_len = 0, max_mel_len = 0;
-    int enc_layers = 0, enc_heads = 0, ffn_dim = 0, ffn_k0 = 0, ffn_k1 = 0, vp_dim = 0, vp_k = 0, n_bins = 0;
-    int dec_layers = 0, dec_heads = 0, dec_scln = 0, n_mels = 0, hop = 0, res_dim = 0, dec_kind = 0, rn_asp = 1;
-    std::vector<int> rn_layers, rn_filters, voc_rates, voc_ksizes, voc_rb_k;
-    std::vector<std::vector<int>> voc_rb_d;
-    int voc_resblock = 1, voc_c0 = 0;
-    // per-call state
-    int B = 0, Tmax = 0, Lmax = 0;
-    std::vector<int> T_host, mel_len_host;
-    std::vector<int> in_stage;            // host staging of a call's integer inputs (one upload)
-    bool have_features = false, have_mel = false;
-    // profiling
-    int profile = 0;
-    int profile_only = -1;                 // >= 0: per-launch events only for this kernel variant (keeps the timed region lean)
-    int rs_prof = 0;                       // zvx_set_int("rs_prof", 1): per-wave cycle counters of the streaming kernels (library built with -DRS_PROFILE)
-    int enc_split = 0;                     // 16-bit mode: the f32 GEMMs of the phoneme encoder run as 3-plane 16-bit GEMMs: 2 = IEEE-half planes (default: 2^-24-class, f32
-                                           // results), 1 = bf16 planes (rounds 2-3: 5e-5 on the encoder output; A/B), 0 = the exact-f32 MFMA
-    const void* fft_xs_ready = nullptr;     // fft.xs holds the split planes of this buffer (written by the previous FFT block's last LayerNorm)
-    int norm_fuse_maxb = 1 << 20;          // zvx_set_int("norm_fuse_maxb", n): batches of at most n utterances may take the one-launch InstanceNorm of the StyleTTS decoder (0: never; A/B)
-    int dec_sc_fuse = 1;                   // zvx_set_int("dec_sc_fuse", 0): the 1x1 shortcut of a StyleTTS residual block as its own launch (A/B; the fused form skips one 16-bit rounding of the conv2 result)
-    int dec_flat = 1;                      // zvx_set_int("dec_flat", 0): the StyleTTS decoder's convolutions per utterance instead of batch-flattened (A/B, bit-identical)
-    int voc_f16_stages = -1;               // zvx_set_int("voc_f16_stages", mask): which domains of the generator (bit 0: mel / conv_pre, bit i: upsampling stage i) compute in IEEE half when voc_f16 is on, the others in bf16; -1 (default): all but a 128-channel ResBlock1 stage
-    int voc_h16_ok = -1;                   // every contraction weight of the generator has an IEEE-half copy (decided on the first vocoder call)
-    int voc_f16 = 1;                       // zvx_set_int("voc_f16", 0): the vocoder's activations / weights / running sum in bf16 instead of IEEE half (A/B; round 5)
-    int dec_f16 = 1;                       // zvx_set_int("dec_f16", 0): StyleTTS decoder activations / weights in bf16 instead of IEEE half (A/B)
-    int use_attn_f32 = 1;                  // zvx_set_int("attn_f32", 0): the encoder's attention as V^T / score / P.V GEMMs + softmax (A/B)
-    int use_flash = 1;                     // zvx_set_int("flash", 0): the decoder's attention as score GEMM + softmax + PV GEMM (A/B)
-    int use_resstream = 1;                 // zvx_set_int("resstream", 0): ResBlocks of the narrow stages as per-pair launches (A/B, bit-equal)
-    int rs_seg_min = 0;                    // zvx_set_int("rs_seg_min", -1): streaming ResBlock segments never shorter than 2048 rows (A/B of the single-request sizing)
-    int spk_s2_fuse = 1;                   // zvx_set_int("spk_s2_fuse", 0): the level transitions as two launches of the gathered-row GEMM (A/B)
-    int spk_pool_fuse = 1;                 // zvx_set_int("spk_pool_fuse", 0): the speaker encoder's SE pool as its own pass everywhere (A/B)
-    int slab_small = 2, slab_flat = 1;     // zvx_set_int("slab_small" / "slab_flat", v): conv-slab tile choice for single requests / whole-grid XCD remap (A/B; per context)
-    int poison_pads = 0;                   // zvx_set_int("poison_pads", 1): every work buffer of the mel decoders is filled with NaN bit patterns before a decode (tests: padding rows / stale rows must never reach a result -- ADVICE r4)
-    // Saturation audit of the half mode (zvx_set_int("f16_sat_check", 1)): every 16-bit tensor of the vocoder and the mel
-    // decoders goes through HBM (one launch per convolution: no LDS-resident intermediate) and is scanned for clamped values
-    // (+-65504) behind the launch that wrote it; zvx_get_int("f16_sat_events") is the count since the switch was last set.  A debug mode:
-    // same arithmetic per convolution, ~3x the time.
-    int sat_check = 0;
-    unsigned long long* sat_count_dev() { return (unsigned long long*)buf("sat.count", 64); }
-    void sat_scan(const void* x, int dt, long bs, int ld, int B, int rows_max, const int* rows, int C) {
-        if (sat_check && x && dt == DT_F16) launch_count_sat16(x, bs, ld, B, rows_max, rows, C, sat_count_dev(), stream);
-    }
-    int use_rb2fuse = 1;                   // zvx_set_int("rb2fuse", 0): every convolution of a ResBlock2 (HiFi-GAN V3 / resblock "2") as its own launch instead of one launch per block (A/B)
-    int use_stagefuse = 1;                 // zvx_set_int("stagefuse", 0): narrow vocoder stages (C = 16 / 8) as per-pair launches instead of ONE launch per stage (narrowstage.hip; A/B)
-    struct NsWeights { void* W = nullptr; float* bias = nullptr; int woff[18] = {0}; };
-    std::map<std::string, NsWeights> ns_weights;   // narrowstage.hip fragment order, per (stage, dtype), built on first use
-    int use_pairstream = 1;                // zvx_set_int("pairstream", v): C = 128 ResBlock pairs on pairstream.hip: 1 = every k (default; jobs under ~200 k rows run the bit-identical two-launch path), 3 = every k and every job size (tests), -1 / 0 = two conv-slab launches per pair (the bit-equality reference)
-    int shape_log = 0;                     // zvx_set_int("shape_log", 1): one stderr line per timed launch (profile 2)
-    int max_frames = 1 << 18;              // hard cap on a predicted mel length (guards the allocation, fs2.py:678-681 has none)
-    // Output rate (zvx_set_int("out_rate", hz); 0 = the model's own rate): the waveform calls resample their rows on the device as
-    // their last launch (do_vocode).  The polyphase banks are designed on the host in double, rounded once to f32 and kept per (L, M).
-    int out_rate = 0;
-    struct RsBank { int L = 0, M = 0, half = 0, T = 0, pitch = 0; const float* dev = nullptr; };
-    std::map<std::pair<int, int>, RsBank> rs_banks;
-    std::map<int, const double*> lim_wins;  // zvx_limit: the smoothing weights on the device, designed in double, per window W
-    std::map<int, LoudCoef> loud_coefs;    // zvx_loudness / zvx_normalize: the K-weighting biquads, designed in double, per sampling rate
-    // zvx_denoise / zvx_denoise_bias: twiddles, window and squared window on the device, designed in double on first use (n_fft, hop and
-    // win_length are the model's: one set per context); nothing exists before the first call
-    struct DnTables { int n_fft = 0, log2n = 0, win_length = 0; const float* twid = nullptr; const float* win = nullptr; const double* win2 = nullptr; double den_min = 0; };
-    DnTables dn_tab;
-    // zvx_join / zvx_trim_bounds / zvx_spkemb_wav / zvx_loudness / zvx_normalize / zvx_true_peak / zvx_limit: pinned host memory the
-    // layout, bounds or result words (and host output rows) land in under the call's one wait
-    void* join_host = nullptr;
-    size_t join_host_cap = 0;
-    void* join_pinned(size_t bytes) {
-        if (bytes > join_host_cap) {
-            if (join_host) { HIPCHK(hipStreamSynchronize(stream)); HIPCHK(hipHostFree(join_host)); join_host = nullptr; join_host_cap = 0; }
-            const size_t cap = bytes + bytes / 8 + 256;
-            HIPCHK(hipHostMalloc(&join_host, cap, hipHostMallocDefault));
-            join_host_cap = cap;
-        }
-        return join_host;
-    }
-    hipEvent_t stage_ev[ZVX_T_COUNT][2];
-    bool stage_used[ZVX_T_COUNT];
-    float stage_ms[ZVX_T_COUNT];
-    std::vector<GemmEvent> pending;
-    std::vector<zvx_kernel_stat> stats;
-    std::string tag = "other";             // stage label of the launches being issued (per-stage roofline accounting, profile 2)
-    std::map<std::string, zvx_kernel_stat> tagstats;
-    std::map<std::string, zvx_kernel_stat> namedstats;   // helper kernels timed under a name of their own (the prosody-control kernels)
-    std::vector<hipEvent_t> event_pool;
-    std::vector<zvx_stream*> streams;       // the open stream sessions (zvx_stream_open); zvx_destroy closes what is left
-
-    // ------------------------------------------------------------------ helpers
-    int cfg_int(const char* k) const {
-        auto it = cfg.find(k);
-        if (it == cfg.end()) fail(ZVX_E_MANIFEST, "manifest: missing cfg '%s'", k);
-        return atoi(it->second.c_str());
-    }
-    std::vector<int> cfg_list(const char* k) const {
-        auto it = cfg.find(k);
-        if (it == cfg.end()) fail(ZVX_E_MANIFEST, "manifest: missing cfg '%s'", k);
-        std::vector<int> v; std::stringstream ss(it->second); std::string tok;
-        while (std::getline(ss, tok, ',')) if (!tok.empty()) v.push_back(atoi(tok.c_str()));
-        return v;
-    }
-    const Tensor& t(const std::string& name) const {
-        auto it = tensors.find(name);
-        if (it == tensors.end()) fail(ZVX_E_MANIFEST, "weights: tensor '%s' missing", name.c_str());
-        return it->second;
-    }
-    bool has(const std::string& name) const { return tensors.count(name) != 0; }
-    const float* pf(const std::string& name) const { return (const float*)t(name).dev; }
-
-    // A buffer about to be freed may still be read by work queued on ANY of the context's streams (the two-stream schedule: the front
-    // end of call i + 1 regrows "mel" on the front stream while call i's launch_mel_pad is queued on the main stream) -- every stream
-    // of the context is drained first; hipFree's own device-wide synchronisation is not a contract to lean on
-    void drain_for_free() {
-        HIPCHK(hipStreamSynchronize(stream));
-        for (hipStream_t s2 : {main0, front_stream, aux_stream, voc_aux[0], voc_aux[1], comm_stream, copy_stream})
-            if (s2 && s2 != stream) HIPCHK(hipStreamSynchronize(s2));
-    }
-    void* buf(const std::string& name, size_t bytes) {
-        DevBuf& d = bufs[name];
-        if (bytes > d.cap) {
-            if (d.base) { drain_for_free(); HIPCHK(hipFree(d.base)); d.base = nullptr; d.p = nullptr; }
-            size_t cap = bytes + bytes / 8 + 256;
-            HIPCHK(hipMalloc(&d.base, cap));
-            HIPCHK(hipMemsetAsync(d.base, 0, cap, stream));
-            d.p = d.base;
-            d.cap = cap;
-        }
-        return d.p;
-    }
-    // Several small named buffers as slices of ONE allocation, so that a call zero-fills / uploads them with one operation instead of
-    // one each (a single request is paced by its launch count).  Lookups by name keep working; the slices are re-cut on every call.
-    char* carve(const std::string& pool, const std::vector<std::string>& names, size_t bytes_each, size_t* stride_out) {
-        const size_t stride = (bytes_each + 255) & ~(size_t)255;
-        char* base = (char*)buf(pool, stride * names.size());
-        for (size_t i = 0; i < names.size(); i++) {
-            DevBuf& d = bufs[names[i]];
-            if (d.base) { drain_for_free(); HIPCHK(hipFree(d.base)); d.base = nullptr; }
-            d.p = base + i * stride; d.cap = stride;
-        }
-        *stride_out = stride;
-        return base;
-    }
-    int* ibuf(const std::string& name, size_t n) { return (int*)buf(name, n * sizeof(int)); }
-    float* fbuf(const std::string& name, size_t n) { return (float*)buf(name, n * sizeof(float)); }
-    // Small host -> device copies go through PINNED memory owned by the context.  A copy from pageable memory makes the runtime
-    // wait for the stream before it returns; from pinned memory it is queued like a launch.  With forced durations and a device
-    // output (ZVX_NO_SYNC) a whole zvx_synthesize call then only QUEUES work: the host runs ahead of the GPU by a call or more and
-    // a slow or preempted host thread no longer shows up as GPU idle time.  Two arenas alternate between API calls; an arena is
-    // reused only after the event recorded behind its last copy has passed.
-    struct Arena { char* p = nullptr; size_t cap = 0, cur = 0; hipEvent_t ev = nullptr; bool pending = false; };
-    Arena arena[2];
-    int arena_i = 0;
-    int api_depth = 0;
-    static constexpr size_t ARENA_BYTES = 2u << 20;
-    void arena_begin() {
-        Arena& a = arena[arena_i];
-        if (a.pending) { HIPCHK(hipEventSynchronize(a.ev)); a.pending = false; }
-        a.cur = 0;
-    }
-    void arena_end() {                      // only a call that uploaded something rotates the arenas: a gather or a query between two
-        Arena& a = arena[arena_i];          // synthesis calls must not send them both to the same arena (the second would wait for the first)
-        if (!a.cur || !stream) return;
-        if (!a.ev) HIPCHK(hipEventCreateWithFlags(&a.ev, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(a.ev, stream));
-        a.pending = true;
-        arena_i ^= 1;
-    }
-    void upload(void* dst, const void* src, size_t bytes) {
-        Arena& a = arena[arena_i];
-        const size_t need = (bytes + 63) & ~(size_t)63;
-        if (!a.p) { HIPCHK(hipHostMalloc((void**)&a.p, ARENA_BYTES, hipHostMallocDefault)); a.cap = ARENA_BYTES; }
-        if (a.cur + need > a.cap) {
-            // larger than what is left of the arena: a plain copy, COMPLETED before this returns (the caller's / the context's staging
-            // memory may be reused right after the call; the runtime's own staging of pageable copies is not a contract to lean on)
-            HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, stream));
-            HIPCHK(hipStreamSynchronize(stream));
-            return;
-        }
-        memcpy(a.p + a.cur, src, bytes);
-        HIPCHK(hipMemcpyAsync(dst, a.p + a.cur, bytes, hipMemcpyHostToDevice, stream));
-        a.cur += need;
-    }
-    int* upload_ints(const std::string& name, const int* v, size_t n) {
-        int* d = ibuf(name, n);
-        upload(d, v, n * sizeof(int));
-        return d;
-    }
-    size_t es() const { return dtype_size(dt); }
-
-    hipEvent_t new_event() {
-        hipEvent_t e;
-        if (!event_pool.empty()) { e = event_pool.back(); event_pool.pop_back(); return e; }
-        HIPCHK(hipEventCreate(&e));
-        return e;
-    }
-    void stage_begin(int s) { if (profile) { HIPCHK(hipEventRecord(stage_ev[s][0], stream)); } }
-    void stage_end(int s) { if (profile) { HIPCHK(hipEventRecord(stage_ev[s][1], stream)); stage_used[s] = true; } }
-
-    // One dispatch that carries its own start / stop events (profile 2; no marker packets on the stream): arm the launchers' event pair,
-    // launch, disarm on every way out (a throwing `launch` included), and queue the GemmEvent that `describe` fills in.  `vid` names the
-    // variant the profile_only filter compares (asked only while that filter is set); `launch` returns the variant id that ran and throws
-    // where it cannot.
-    template <typename V, typename L, typename D>
-    void profiled(V&& vid, L&& launch, D&& describe) {
-        const bool prof = profile >= 2 && (profile_only < 0 || vid() == profile_only);
-        if (!prof) { launch(); return; }
-        GemmEvent ev{};
-        ev.a = new_event(); ev.b = new_event();
-        struct Armed { Armed(hipEvent_t a, hipEvent_t b) { profile_events(a, b); } ~Armed() { profile_events(nullptr, nullptr); } };
-        ev.variant = [&] { Armed armed(ev.a, ev.b); return launch(); }();
-        describe(ev);
-        ev.tag = tag;
-        pending.push_back(ev);
-    }
-    void gemm(GemmArgs& a) {
-        if (a.flops <= 0) a.flops = 2.0 * (double)a.M * a.nbatch * a.nheads * (double)a.N * ((double)a.K * a.ntaps + (double)a.K2);
-        if (!a.Wp && a.dtype != DT_F32) { auto it = packed.find(a.W); if (it != packed.end()) a.Wp = it->second; }
-        a.slab_small = slab_small | (spk_s2_fuse ? 0 : 32); a.xcd_flat = slab_flat;      // (bit 5: no conv2d_s2_kernel -- spk_s2_fuse 0 is the gathered-row launch set for BOTH level transitions)
-        profiled([&] { return gemm_variant_of(a); }, [&] {
-            const int id = a.fused == 2 ? launch_rb2fuse(a, stream) : (a.fused ? launch_resfuse(a, stream) : launch_gemm(a, stream));
-            if (id < 0) fail(ZVX_E_INVALID, "launch_gemm rejected shape M=%d N=%d K=%d taps=%d", a.M, a.N, a.K, a.ntaps);
-            return id;
-        }, [&](GemmEvent& ev) {
-            ev.flops = a.flops; ev.rows = (long)a.M * a.nbatch * a.nheads; ev.N = a.N; ev.K = a.K; ev.taps = a.ntaps; ev.res = a.res_mode; ev.fused = a.fused;
-            const double esz = dtype_size(a.dtype);
-            // algorithmic bytes: input rows + weights + everything the epilogue reads and writes (output, residual, running sum)
-            const double cells = (double)a.M * a.nbatch * a.nheads * a.N;
-            ev.bytes = ((double)a.M * a.nbatch * a.nheads) * (double)(a.K + a.K2) * esz + (double)a.N * ((double)a.K * a.ntaps + a.K2) * esz * (a.fused ? 2 : 1) +
-                       (a.out ? cells * dtype_size(a.out_dtype) : 0.0) + ((a.res_mode && !a.fused) ? cells * dtype_size(a.res_dtype) : 0.0) +
-                       ((a.accum && (a.accum_mode & 1)) ? cells * dtype_size(a.accum_dtype) : 0.0) + ((a.accum && (a.accum_mode & 2)) ? cells * dtype_size(a.accum_dtype) : 0.0);
-        });
-        if (sat_check && a.nheads == 1) {                   // (audit mode: the attention products run fused, their output is scanned by fft_block)
-            sat_scan(a.out, a.out_dtype, a.o_bs, a.ldo, a.nbatch, a.M, a.out_len, a.N);
-            if (a.accum && (a.accum_mode & 2)) sat_scan(a.accum, a.accum_dtype, a.a_bs, a.lda, a.nbatch, a.M, a.out_len, a.N);
-        }
-    }
-    // streaming ResBlock chain (resstream.hip); returns false (nothing launched) when the shape is not covered
-    bool run_stream(StreamArgs& a) {
-        const int id = launch_resstream(a, this->stream, true);
-        if (id < 0) return false;
-        profiled([&] { return id; }, [&] {
-            const int id2 = launch_resstream(a, this->stream, false);
-            if (id2 < 0) fail(ZVX_E_INVALID, "launch_resstream rejected a shape its dry run accepted (C=%d k=%d pairs=%d)", a.C, a.ntaps, a.npair);
-            return id2;
-        }, [&](GemmEvent& ev) {
-            const double rows = (double)a.M * a.nbatch;
-            ev.flops = 2.0 * 2.0 * a.npair * rows * a.C * a.C * a.ntaps; ev.rows = (long)rows; ev.N = a.C; ev.K = a.C; ev.taps = a.ntaps;
-            ev.res = a.accum_mode; ev.fused = 10 + a.npair;
-            ev.bytes = rows * a.C * 2.0 * (1 + (a.out ? 1 : 0) + ((a.accum && (a.accum_mode & 1)) ? 1 : 0) + ((a.accum && (a.accum_mode & 2)) ? 1 : 0));
-        });
-        return true;
-    }
-    // the HBM-bound helpers (norms, gathers, conv_post ...): event-timed as a group when every launch is being profiled
-    // kname: also counted under that name in zvx_kernel_stats
-    template <typename F>
-    void timed(double flops, double bytes, F&& f, const char* kname = nullptr) {
-        const bool prof = profile >= 2 && profile_only < 0;
-        GemmEvent ev{};
-        if (prof) { ev.a = new_event(); ev.b = new_event(); HIPCHK(hipEventRecord(ev.a, stream)); }
-        f();
-        if (prof) { HIPCHK(hipEventRecord(ev.b, stream)); ev.variant = -1; ev.flops = flops; ev.bytes = bytes; ev.tag = tag; if (kname) ev.kname = kname; pending.push_back(ev); }
-    }
-    void resolve_events() {
-        if (stats.empty()) {
-            stats.resize(gemm_num_variants());
-            for (int i = 0; i < gemm_num_variants(); i++) { memset(&stats[i], 0, sizeof stats[i]); snprintf(stats[i].name, 64, "%s", gemm_variant_name(i)); }
-        }
-        for (auto& e : pending) {
-            float ms = 0.f;
-            HIPCHK(hipEventElapsedTime(&ms, e.a, e.b));
-            if (shape_log && e.variant >= 0) fprintf(stderr, "launch %-24s rows=%-8ld N=%-4d K=%-4d taps=%-2d res=%d fused=%d  %8.3f ms %8.1f TF/s %8.1f GB/s(alg)\n",
-                                   gemm_variant_name(e.variant), e.rows, e.N, e.K, e.taps, e.res, e.fused, ms, e.flops / ms / 1e9, e.bytes / ms / 1e6);
-            else if (shape_log) fprintf(stderr, "launch %-24s [%s]  %8.3f ms %8.1f GB/s(alg)\n", "(helper)", e.tag.c_str(), ms, e.bytes / ms / 1e6);
-            if (e.variant >= 0) { auto& s = stats[e.variant]; s.launches++; s.ms += ms; s.flops += e.flops; s.bytes += e.bytes; }
-            auto& ts = tagstats[e.tag];
-            if (!ts.name[0]) snprintf(ts.name, 64, "%s", e.tag.c_str());
-            ts.launches++; ts.ms += ms; ts.flops += e.flops; ts.bytes += e.bytes;
-            if (!e.kname.empty()) {
-                auto& ks = namedstats[e.kname];
-                if (!ks.name[0]) snprintf(ks.name, 64, "%s", e.kname.c_str());
-                ks.launches++; ks.ms += ms; ks.flops += e.flops; ks.bytes += e.bytes;
-            }
-            event_pool.push_back(e.a); event_pool.push_back(e.b);
-        }
-        pending.clear();
-        for (int s = 0; s < ZVX_T_COUNT; s++)
-            if (stage_used[s]) { float ms = 0.f; HIPCHK(hipEventElapsedTime(&ms, stage_ev[s][0], stage_ev[s][1])); stage_ms[s] = ms; stage_used[s] = false; }
-    }
-    void sync() {
-        if (front_stream) HIPCHK(hipStreamSynchronize(front_stream));
-        HIPCHK(hipStreamSynchronize(stream));
-        if (comm_stream) HIPCHK(hipStreamSynchronize(comm_stream));
-        if (copy_stream && !copy_is_comm) HIPCHK(hipStreamSynchronize(copy_stream));
-        if (profile) resolve_events();
-    }
-    // error path of an API call: whatever it queued on a side stream before it threw is drained, so that the next call's main-stream
-    // work cannot race with it (the joins that normally order the streams were never issued)
-    void quiesce_side_streams() noexcept {
-        if (front_stream) (void)hipStreamSynchronize(front_stream);
-        if (aux_stream) (void)hipStreamSynchronize(aux_stream);
-        for (int i = 0; i < 2; i++) if (voc_aux[i]) (void)hipStreamSynchronize(voc_aux[i]);
-        front_dirty_main = true; mel_free_pending = false;
-    }
-    void front_setup() {                   // the front stream runs at the highest priority the device offers
-        if (front_stream) return;
-        int least = 0, greatest = 0;                                         // (numerically: greatest priority = the smaller value)
-        HIPCHK(hipDeviceGetStreamPriorityRange(&least, &greatest));
-        HIPCHK(hipStreamCreateWithPriority(&front_stream, hipStreamNonBlocking, greatest));
-        HIPCHK(hipEventCreateWithFlags(&ev_front_done, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&ev_mel_free, hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&ev_main_join, hipEventDisableTiming));
-    }
-};
-
-// What the checks of a post step's parameters yield (level_params_check, dn_geom, watermark_params_check); a session keeps its own.
-struct LevelGeom { int h, S, a; int64_t RL, RR; };          // S and a in units of h samples (100 ms)
-struct DnGeom { int n_fft, log2n, hop, pad, nf; };           // the model's STFT geometry
-struct WmPlan { DnGeom g; int k_lo, J; };                    // ... and the watermark's bands
-
-// A stream session (include/zvx.h: zvx_stream_open): one utterance's mel on the device, the planners of its post stages and, per stage,
-// two device buffers laid out [history | new].  A stage's output is written straight behind the next stage's history; dropping the history
-// before keep_from copies the retained tail into the stage's OTHER buffer (never an overlapping copy) and swaps the two.  A group's gathered
-// rows and what the vocoder makes of them are not the session's: every step, of one session or of many, takes them from the context
-// ("stream.rows", "stream.wav"), which zvx_stream_open has grown to the session's largest group.
-struct zvx_stream {
-    zvx_ctx* c = nullptr;
-    int frames = 0, chunk = 0, cpc = 0, halo = 0, hop = 0, native = 0, out_rate = 0;
-    int nchunks = 0, next_chunk = 0, done = 0;
-    int Pcap = 0;                          // the longest row a group can have, in mel frames
-    int64_t total = 0, emitted = 0, delay = 0, max_piece = 0;
-    enum { DENOISE = 0, LIMIT = 1, RESAMPLE = 2, LEVEL = 3, WATERMARK = 4, KINDS = 5 };
-    struct Stage {
-        int kind = DENOISE;
-        zvx_plan::ReachPlanner reach;      // DENOISE, WATERMARK (n_fft - 1), LIMIT
-        zvx_plan::ResamplePlanner rate;
-        zvx_plan::LevelPlanner level;
-        float* buf[2] = {nullptr, nullptr};
-        int cur = 0;
-        int64_t cap = 0, hist = 0;         // samples a buffer holds; retained samples [origin, received) at the front of buf[cur]
-        zvx_plan::Step push(int64_t n, bool last) { return kind == RESAMPLE ? rate.push(n, last) : kind == LEVEL ? level.push(n, last) : reach.push(n, last); }
-        int64_t received() const { return kind == RESAMPLE ? rate.received : kind == LEVEL ? level.received : reach.received; }
-    };
-    std::vector<Stage> stages;             // in the order they run: denoiser, leveler, watermark, limiter, rate conversion
-    zvx_denoise_params dn{};
-    std::vector<float> bias;
-    zvx_limit_params lim{};
-    int lim_W = 0;                         // the limiter's window in samples
-    zvx_level_params lvl{};                // (zvx_stream_open_ex)
-    LevelGeom lvl_g{};
-    zvx_watermark_params wm{};             // wm.key is this session's key
-    WmPlan wm_plan{};
-    char* dev = nullptr;                   // ONE device allocation: the mel, the stage buffers, the host piece's staging
-    float* mel = nullptr;
-    float* ostage = nullptr;
-    float* pinned = nullptr;               // host piece: [max_piece] f32
-};
-
-namespace {
-
-GemmArgs gemm_base(int dtype) {
-    GemmArgs a;
-    memset(&a, 0, sizeof a);
-    a.dtype = dtype; a.nbatch = 1; a.nheads = 1; a.ntaps = 1; a.stride = 1; a.wout = 0; a.hin = 1; a.win = 0;
-    a.alpha = 1.f; a.out_scale = 1.f; a.out_dtype = dtype; a.res_dtype = dtype;
-    return a;
-}
-void set_taps_1d(GemmArgs& a, int k, int dilation) {
-    a.ntaps = k;
-    for (int i = 0; i < k; i++) { a.du[i] = 0; a.dv[i] = (int)((i - (k - 1) / 2) * dilation); }
-}
 
 // ------------------------------------------------------------------------------------------------
 // manifest
 // ------------------------------------------------------------------------------------------------
+
+namespace {
 void parse_manifest(zvx_ctx* c, const char* manifest, const void* weights, size_t nbytes) {
     if (!manifest || !weights) fail(ZVX_E_MANIFEST, "manifest/weights pointer is NULL");
     const size_t nfloats = nbytes / 4;
@@ -1772,6 +1310,7 @@ void voc_resblock(zvx_ctx* c, const VocCall& v, const VocStage& s, int j) {
         if (!last) { cur = PPs[pp]; pp ^= 1; }
     }
 }
+}  // namespace
 
 void run_vocoder(zvx_ctx* c, const float* mel, int ldm, int Lmel_max, const int* mel_len_host, const int* P_host, int B,
                  void* wav_dev, long wav_stride, int pcm16) {
@@ -1855,6 +1394,8 @@ void run_vocoder(zvx_ctx* c, const float* mel, int ldm, int Lmel_max, const int*
 // ------------------------------------------------------------------------------------------------
 // speaker encoder (ResNetSE34V2.py:176-212)
 // ------------------------------------------------------------------------------------------------
+
+namespace {
 // The encoder behind the mels: mels_d [B][Tmax][n_mels] f32 on the device, lens[b] in 2..Tmax (checked by the caller) -> "spk.emb" [B][hidden],
 // queued on the context's stream.  Shared by zvx_spkemb / zvx_spkemb_ex (run_spkemb) and zvx_spkemb_wav.
 float* spkemb_from_mels(zvx_ctx* c, const float* mels_d, const int32_t* lens, int B, int Tmax) {
@@ -2097,421 +1638,6 @@ void run_melspec(zvx_ctx* c, const float* wav, const int32_t* nsamples, int B, i
 }
 
 // ------------------------------------------------------------------------------------------------
-// the rows-call contract of the post-processing entry points (include/zvx.h): a batch of waveform rows [B][Nmax] f32 + nsamples[B], on
-// the host or on the device.  The checks are pure: an entry point runs all of its checks before it allocates, uploads or launches.
-// ------------------------------------------------------------------------------------------------
-// (on its own in zvx_resample, whose ZVX_E_UNSUPPORTED rate pairs rank between this and the lengths)
-void rows_args(const char* who, const void* in, const int32_t* nsamples, int B, int Nmax) {
-    if (!in || !nsamples || B <= 0 || Nmax <= 0) fail(ZVX_E_INVALID, "%s: bad arguments (NULL pointer, B = %d, Nmax = %d)", who, B, Nmax);
-}
-struct RowsInfo { long n_max = 0; double n_sum = 0; };      // the longest row, and all samples of the batch
-RowsInfo rows_check(const char* who, const void* in, const int32_t* nsamples, int B, int Nmax, int max_rows = INT32_MAX) {
-    rows_args(who, in, nsamples, B, Nmax);
-    if (B > max_rows) fail(ZVX_E_UNSUPPORTED, "%s: B = %d rows (at most %d per call)", who, B, max_rows);
-    RowsInfo r;
-    for (int b = 0; b < B; b++) {
-        if (nsamples[b] < 0 || nsamples[b] > Nmax) fail(ZVX_E_INVALID, "%s: nsamples[%d]=%d out of range (0..%d)", who, b, nsamples[b], Nmax);
-        r.n_max = std::max<long>(r.n_max, nsamples[b]); r.n_sum += nsamples[b];
-    }
-    return r;
-}
-void flags_check(const char* who, int flags, int allowed) {
-    if (flags & ~allowed) fail(ZVX_E_INVALID, "%s: unknown flag in %d", who, flags);
-    if ((flags & ZVX_NO_SYNC) && !(flags & ZVX_DEVICE_OUT)) fail(ZVX_E_INVALID, "%s: ZVX_NO_SYNC needs ZVX_DEVICE_OUT", who);
-}
-// output rows [B][out_stride] of the input's shape (zvx_normalize, zvx_limit), which may be the input rows themselves
-void out_rows_check(const char* who, const void* in, const void* out, int64_t out_stride, int Nmax, int flags) {
-    if (!out) fail(ZVX_E_INVALID, "%s: out is NULL", who);
-    if (out_stride < Nmax) fail(ZVX_E_INVALID, "%s: out_stride %lld is smaller than Nmax %d", who, (long long)out_stride, Nmax);
-    if (out != in) return;
-    if (flags & ZVX_PCM16) fail(ZVX_E_INVALID, "%s: ZVX_PCM16 cannot run in place", who);
-    if (out_stride != Nmax || !(flags & ZVX_DEVICE_IN) != !(flags & ZVX_DEVICE_OUT))
-        fail(ZVX_E_INVALID, "%s: in place needs out_stride == Nmax and both pointers on the same side", who);
-}
-
-// host rows go to "<prefix>.in" on the device, device rows (ZVX_DEVICE_IN) are used where they are
-const float* rows_to_device(zvx_ctx* c, const std::string& prefix, const float* in, int B, int Nmax, int flags) {
-    if (flags & ZVX_DEVICE_IN) return in;
-    float* xd = c->fbuf(prefix + ".in", (size_t)B * Nmax);
-    HIPCHK(hipMemcpyAsync(xd, in, (size_t)B * Nmax * 4, hipMemcpyHostToDevice, c->stream));
-    return xd;
-}
-struct DevRows { const float* x; const int* len; };
-DevRows stage_rows(zvx_ctx* c, const std::string& prefix, const float* in, const int32_t* nsamples, int B, int Nmax, int flags) {
-    const float* x = rows_to_device(c, prefix, in, B, Nmax, flags);
-    return {x, c->upload_ints(prefix + ".len", nsamples, B)};
-}
-// "issue the following under tag T", between the stage slot's events where one is given; the tag is restored on every way out
-struct TagScope {
-    zvx_ctx* c; std::string keep; int slot;
-    TagScope(zvx_ctx* c_, const char* tag, int slot_ = -1) : c(c_), keep(c_->tag), slot(slot_) {
-        c->tag = tag;
-        if (slot >= 0) c->stage_begin(slot);
-    }
-    ~TagScope() { c->tag = keep; }
-    void close() { if (slot >= 0) c->stage_end(slot); c->tag = keep; }
-};
-// What zvx_normalize / zvx_limit and their measuring forms hand back: `res_bytes` of result words (padded to 256 bytes in the pinned
-// block) and, with a host output, the rows: staged on the device at a stride of their own, brought over behind the words, one wait.
-struct RowsReturn {
-    zvx_ctx* c; int B; size_t res_bytes, res_pad, ss; long n_max, ostage; bool want_host, host_out; char* host = nullptr; void* odev = nullptr;
-    RowsReturn(zvx_ctx* c_, int B_, size_t res_bytes_, bool want_host_, bool writes_rows, long n_max_, int flags)
-        : c(c_), B(B_), res_bytes(res_bytes_), res_pad((res_bytes_ + 255) & ~(size_t)255), ss((flags & ZVX_PCM16) ? 2 : 4), n_max(n_max_),
-          ostage((n_max_ + 7) & ~7L), want_host(want_host_), host_out(writes_rows && !(flags & ZVX_DEVICE_OUT)) {
-        if (want_host || host_out) host = (char*)c->join_pinned(res_pad + (host_out ? (size_t)B * ostage * ss : 0));
-    }
-    // where the launches write the rows, and at which stride: the staging buffer `name`, or the caller's device rows
-    void* out_rows(const char* name, void* out, int64_t out_stride, long* bs) {
-        *bs = host_out ? ostage : (long)out_stride;
-        return odev = host_out ? c->buf(name, (size_t)B * ostage * ss + 16) : out;
-    }
-    // -> the result words on the host; nullptr where none were asked for (with ZVX_NO_SYNC the call has then only queued)
-    const char* finish(const void* res_dev, void* out, int64_t out_stride, const int32_t* nsamples, int flags) {
-        if (want_host) HIPCHK(hipMemcpyAsync(host, res_dev, res_bytes, hipMemcpyDeviceToHost, c->stream));
-        if (host_out && n_max > 0) HIPCHK(hipMemcpyAsync(host + res_pad, odev, (size_t)B * ostage * ss, hipMemcpyDeviceToHost, c->stream));
-        if (!want_host && (flags & ZVX_NO_SYNC)) return nullptr;     // device output, nothing for the host: the call only queues
-        c->sync();                                                   // the call's one wait
-        if (host_out)
-            for (int b = 0; b < B; b++)
-                if (nsamples[b] > 0) memcpy((char*)out + (size_t)b * out_stride * ss, host + res_pad + (size_t)b * ostage * ss, (size_t)nsamples[b] * ss);
-        return want_host ? host : nullptr;
-    }
-};
-
-// ------------------------------------------------------------------------------------------------
-// sample-rate conversion (include/zvx.h: zvx_resample, "out_rate")
-// ------------------------------------------------------------------------------------------------
-constexpr int RS_MAX_PHASES = 640;       // max(L, M) a bank is built for: every pair between 22050 and 8000 ... 48000
-constexpr int RS_ZEROS = 10;             // half = RS_ZEROS * max(L, M): the filter spans 10 zero crossings of the sinc on each side
-constexpr double RS_BETA = 5.0;          // Kaiser window (both as scipy.signal.resample_poly's defaults)
-
-// rate_in -> rate_out as (L, M); equal rates: (1, 1).  ZVX_E_INVALID / ZVX_E_UNSUPPORTED as include/zvx.h states them.
-void rs_pair(int rate_in, int rate_out, int* L, int* M) {
-    for (int r : {rate_in, rate_out}) if (r < 4000 || r > 192000) fail(ZVX_E_INVALID, "sampling rate %d Hz outside [4000, 192000]", r);
-    int a = rate_in, b = rate_out;
-    while (b) { const int t = a % b; a = b; b = t; }
-    *L = rate_out / a; *M = rate_in / a;
-    if (std::max(*L, *M) > RS_MAX_PHASES)
-        fail(ZVX_E_UNSUPPORTED, "resampling %d -> %d Hz needs L = %d, M = %d: the polyphase bank is built for max(L, M) <= %d", rate_in, rate_out, *L, *M, RS_MAX_PHASES);
-}
-long rs_out_len(long n, int L, int M) { return (n * L + M - 1) / M; }
-// The window of the post-processing steps: a row holds samples [in_origin, in_origin + n) of its signal, the outputs
-// [out_begin, out_begin + cnt) are emitted.  The whole-row calls are {0, 0, -1, 1}.  The denoiser and the limiter add a support condition
-// and `last` (the signal ends with the window); the resampler's rows are zero outside the window and `last` takes no part.
-struct RowsWindow { int64_t in_origin = 0, out_begin = 0, out_count = -1; int last = 1; };
-// One row of a post-processing step: n samples at `in` on the device, the window they are of their signal, the emitted count, and where
-// emitted sample 0 goes.  Rows of one call may lie in unrelated buffers.
-struct PostRow { const float* in; void* out; int32_t n; RowsWindow w; int32_t cnt; };
-// The windows of a call after its checks, per row (B entries) or ONE for every row, and per row the emitted count
-struct RowsWindows {
-    std::vector<RowsWindow> w; std::vector<int32_t> cnt; long cnt_max = 0;
-    const RowsWindow& at(int b) const { return w[w.size() == 1 ? 0 : (size_t)b]; }
-};
-// the strided rows of a public call as PostRows
-std::vector<PostRow> post_rows(const float* x, long x_bs, void* out, long out_bs, size_t ss, const int32_t* nsamples, const RowsWindows& rw, int B) {
-    std::vector<PostRow> rows((size_t)B);
-    for (int b = 0; b < B; b++)
-        rows[(size_t)b] = PostRow{x + (size_t)b * x_bs, (char*)out + (size_t)b * out_bs * ss, nsamples[b], rw.at(b), rw.cnt[(size_t)b]};
-    return rows;
-}
-// What every windowed effect does once its own checks have passed: the rows go to the device ("<prefix>.in"), the outputs are staged where
-// the host wants them ("<prefix>.out"), `run(rows)` issues the effect's launches over the PostRows and gives its device result words (or
-// nullptr), and RowsReturn brings rows and words over behind the call's one wait.  writes_rows false: a measuring call, `out` is not looked at (zvx_true_peak).
-// -> the `res_bytes` of result words on the host; nullptr where the host wants none
-template <typename Run>
-const float* post_call(zvx_ctx* c, const char* prefix, const float* in, const int32_t* nsamples, int B, int Nmax, void* out, int64_t out_stride, bool writes_rows,
-                       int flags, const RowsWindows& rw, size_t res_bytes, bool want_host, Run&& run) {
-    const std::string px(prefix);
-    RowsReturn ret(c, B, res_bytes, want_host, writes_rows, rw.cnt_max, flags);
-    const float* x = rows_to_device(c, px, in, B, Nmax, flags);
-    long out_bs = 0;
-    void* od = ret.out_rows((px + ".out").c_str(), out, out_stride, &out_bs);
-    const std::vector<PostRow> rows = post_rows(x, Nmax, od, out_bs, ret.ss, nsamples, rw, B);
-    const float* res = run(rows.data());
-    return (const float*)ret.finish(res, out, out_stride, rw.cnt.data(), flags);
-}
-// two [B] result arrays of the host's, either may be NULL, from the words [2][B]
-void copy_word_pairs(const float* words, int B, float* first, float* second) {
-    if (!words) return;
-    if (first) memcpy(first, words, (size_t)B * sizeof(float));
-    if (second) memcpy(second, words + B, (size_t)B * sizeof(float));
-}
-// Every row converted as a signal of its own length len[b] * mul, held from sample in_origin on and zero elsewhere: per row the outputs
-// [out_begin, out_begin + cnt[b]) (out_count -1: to the end of the row's signal), and the longest of them.
-struct RsPlan { RowsWindow w; long out_max = 0; std::vector<long> cnt; };
-RsPlan rs_plan(const int* len, int mul, int B, int L, int M, long in_origin = 0, long out_begin = 0, long out_count = -1) {
-    RsPlan p;
-    p.w = RowsWindow{in_origin, out_begin, out_count, 1}; p.cnt.resize(B);
-    for (int b = 0; b < B; b++) {
-        p.cnt[b] = out_count >= 0 ? out_count : std::max(0L, rs_out_len(in_origin + (long)len[b] * mul, L, M) - out_begin);
-        p.out_max = std::max(p.out_max, p.cnt[b]);
-    }
-    return p;
-}
-// the strided rows of such a call as PostRows (the caller has checked that the counts fit an int32)
-std::vector<PostRow> plan_rows(const RsPlan& p, const float* x, long x_bs, void* out, long out_bs, size_t ss, const int* len, int mul, int B) {
-    std::vector<PostRow> rows((size_t)B);
-    for (int b = 0; b < B; b++)
-        rows[(size_t)b] = PostRow{x + (size_t)b * x_bs, (char*)out + (size_t)b * out_bs * ss, len[b] * mul, p.w, (int32_t)p.cnt[(size_t)b]};
-    return rows;
-}
-
-double bessel_i0(double x) {
-    double s = 1.0, t = 1.0;
-    for (int k = 1; k < 64; k++) { t *= (x / (2.0 * k)) * (x / (2.0 * k)); s += t; if (t < 1e-20 * s) break; }
-    return s;
-}
-// The row pitch of the bank in LDS: lanes of a wave read bank[p_i][t] with one t and phases p_i stepping by M mod L (up-conversion:
-// neighbouring lanes take neighbouring outputs) or 4 M mod L (down-conversion: 4 consecutive outputs per lane), 32 lanes per
-// ds_read_b32 group over 32 banks.  The worst pile-up over all start phases is counted for each pitch in
-// [T + 1, T + 8] and the smallest sum wins (an odd pitch spreads distinct phases over the banks; which odd one depends on L and M).
-int rs_pick_pitch(int L, int M, int T) {
-    const int step = (int)(((M < L ? 1L : 4L) * M) % L);
-    int best = T + 1; long best_cost = -1;
-    for (int pitch = T + 1; pitch <= T + 8; pitch++) {
-        long cost = 0;
-        for (int p0 = 0; p0 < L; p0++) {
-            int owner[32][8], n[32] = {0}, worst = 1;
-            for (int i = 0, p = p0; i < 32; i++, p = (p + step) % L) {
-                const int bank = (int)(((long)p * pitch) % 32);
-                bool seen = false;
-                for (int j = 0; j < n[bank] && j < 8; j++) seen |= owner[bank][j] == p;      // one address: a broadcast
-                if (!seen) { if (n[bank] < 8) owner[bank][n[bank]] = p; n[bank]++; worst = std::max(worst, n[bank]); }
-            }
-            cost += worst;
-        }
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = pitch; }
-    }
-    return best;
-}
-// The filter of include/zvx.h, designed in double and rounded once to f32, as the polyphase bank launch_resample_poly reads
-// (zvx_kernels.h).  Built and uploaded on first use of (L, M), then kept for the life of the context.
-const zvx_ctx::RsBank& rs_bank(zvx_ctx* c, int L, int M) {
-    auto it = c->rs_banks.find({L, M});
-    if (it != c->rs_banks.end()) return it->second;
-    zvx_ctx::RsBank bk;
-    bk.L = L; bk.M = M;
-    std::vector<float> host;
-    if (L == 1 && M == 1) {                                  // equal rates: one tap of 1.0f, a copy
-        bk.half = 0; bk.T = 1; bk.pitch = 2;
-        host = {1.0f, 0.0f, 0.0f, 0.0f};
-    } else {
-        const int mx = std::max(L, M), half = RS_ZEROS * mx, N = 2 * half + 1;
-        std::vector<double> h(N);
-        const double fc = 1.0 / mx, i0b = bessel_i0(RS_BETA);
-        double sum = 0.0;
-        for (int i = 0; i < N; i++) {
-            const double m = i - half, r = m / half, px = M_PI * fc * m;
-            const double w = bessel_i0(RS_BETA * sqrt(std::max(0.0, 1.0 - r * r))) / i0b;
-            h[i] = fc * (m == 0 ? 1.0 : sin(px) / px) * w;
-            sum += h[i];
-        }
-        for (double& v : h) v = v / sum * L;
-        bk.half = half; bk.T = (N + L - 1) / L; bk.pitch = rs_pick_pitch(L, M, bk.T);
-        host.assign(((size_t)L * bk.pitch + 3) & ~(size_t)3, 0.0f);
-        for (int p = 0; p < L; p++) {
-            const int joff = (half - p) / L;
-            for (int t = 0; t < bk.T; t++) {
-                const long m = p + (long)(joff - t) * L;
-                if (m >= -half) host[(size_t)p * bk.pitch + t] = (float)h[m + half];
-            }
-            memcpy(&host[(size_t)p * bk.pitch + bk.T], &joff, 4);
-        }
-    }
-    float* d = c->fbuf("rs.bank." + std::to_string(L) + "." + std::to_string(M), host.size());
-    HIPCHK(hipMemcpyAsync(d, host.data(), host.size() * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));                 // `host` goes away; once per (L, M)
-    bk.dev = d;
-    return c->rs_banks[{L, M}] = bk;
-}
-
-// The rate conversion over B rows with a window each, every caller's one resampling launch: ONE table upload, one launch, one timed group;
-// stage tag "voc.resample", slot ZVX_T_RESAMPLE.  A row's window is the resampler's own contract -- zero outside the row's samples, no
-// support condition; `last` takes no part.  Zeros follow a row's outputs up to `zero_to` (-1: the row's own cnt, nothing outside [0, cnt) is
-// written; the calls with one window for all rows pass the longest row).  Algorithmic bytes = samples read + samples written, a row's
-// input counted when it has outputs or zeros to write (a row that writes nothing counts nothing; a call that writes nothing launches
-// nothing).  The caller has validated the rows.
-void run_resample_rows(zvx_ctx* c, const zvx_ctx::RsBank& bk, const PostRow* rows, int B, int pcm16, long zero_to = -1) {
-    std::vector<ResampleRow> tab((size_t)B);
-    double nin = 0, nout = 0;
-    long zend_max = 0;
-    for (int b = 0; b < B; b++) {
-        const PostRow& r = rows[b];
-        ResampleRow& t = tab[(size_t)b];
-        t.x = r.in; t.out = r.out; t.n = r.n;
-        t.in_origin = (long)r.w.in_origin; t.out_begin = (long)r.w.out_begin; t.cnt = r.cnt; t.zend = zero_to < 0 ? r.cnt : zero_to;
-        zend_max = std::max(zend_max, t.zend);
-        if (t.zend > 0) { nin += (double)r.n; nout += (double)r.cnt; }
-    }
-    if (zend_max <= 0) return;
-    ResampleArgs a{};
-    a.B = B; a.pcm16 = pcm16; a.L = bk.L; a.M = bk.M; a.half = bk.half; a.T = bk.T; a.pitch = bk.pitch; a.bank = bk.dev;
-    a.out_max = zend_max;                                    // the grid; every row's own bound is its zend
-    ResampleRow* tab_d = (ResampleRow*)c->buf("rs.rows", (size_t)B * sizeof(ResampleRow));
-    c->upload(tab_d, tab.data(), (size_t)B * sizeof(ResampleRow));
-    a.rows = tab_d;
-    TagScope scope(c, "voc.resample", ZVX_T_RESAMPLE);
-    c->timed(2.0 * nout * bk.T, nin * 4.0 + nout * (pcm16 ? 2.0 : 4.0), [&] {
-        if (!launch_resample_poly(a, c->stream)) fail(ZVX_E_UNSUPPORTED, "resampler: L = %d, M = %d does not fit the LDS of a workgroup", bk.L, bk.M);
-    });
-    scope.close();
-}
-
-int model_rate(const zvx_ctx* c) {
-    auto it = c->cfg.find("sampling_rate");
-    if (it == c->cfg.end()) fail(ZVX_E_MANIFEST, "manifest: missing cfg 'sampling_rate'");
-    return atoi(it->second.c_str());
-}
-
-// zvx_resample / zvx_resample_ex
-void do_resample(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate_in, int rate_out, void* out, int64_t out_stride,
-                 int32_t* out_len, int flags, int64_t in_origin, int64_t out_begin, int64_t out_count) {
-    rows_args("zvx_resample", in, nsamples, B, Nmax);
-    if (!out) fail(ZVX_E_INVALID, "zvx_resample: out is NULL");
-    flags_check("zvx_resample", flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16);
-    if (in_origin < 0 || out_begin < 0 || out_count < -1 || in_origin > ((int64_t)1 << 40) || out_begin > ((int64_t)1 << 40) || out_count > INT32_MAX)
-        fail(ZVX_E_INVALID, "zvx_resample_ex: window out of range");
-    int L = 1, M = 1;
-    rs_pair(rate_in, rate_out, &L, &M);                     // (its ZVX_E_UNSUPPORTED ranks before a bad length)
-    rows_check("zvx_resample", in, nsamples, B, Nmax);
-    const RsPlan plan = rs_plan(nsamples, 1, B, L, M, in_origin, out_begin, out_count);
-    const long out_max = plan.out_max;
-    if (out_max > INT32_MAX) fail(ZVX_E_INVALID, "zvx_resample: %ld output samples per row", out_max);
-    if (out_stride < out_max) fail(ZVX_E_BUFFER, "zvx_resample: out_stride %lld < %ld samples", (long long)out_stride, out_max);
-    const zvx_ctx::RsBank& bk = rs_bank(c, L, M);
-    const int pcm16 = (flags & ZVX_PCM16) ? 1 : 0;
-    const size_t ss = pcm16 ? 2 : 4;
-    const float* x = rows_to_device(c, "rs", in, B, Nmax, flags);
-    void* odev = out; long ostride = out_stride;
-    if (!(flags & ZVX_DEVICE_OUT)) { ostride = (std::max(out_max, 1L) + 7) & ~7L; odev = c->buf("rs.out", (size_t)B * ostride * ss); }
-    run_resample_rows(c, bk, plan_rows(plan, x, Nmax, odev, ostride, ss, nsamples, 1, B).data(), B, pcm16, out_max);
-    if (!(flags & ZVX_DEVICE_OUT) && out_max > 0)
-        HIPCHK(hipMemcpy2DAsync(out, (size_t)out_stride * ss, odev, (size_t)ostride * ss, (size_t)out_max * ss, B, hipMemcpyDeviceToHost, c->stream));
-    if (out_len) for (int b = 0; b < B; b++) out_len[b] = (int32_t)plan.cnt[b];
-    if (!((flags & ZVX_DEVICE_OUT) && (flags & ZVX_NO_SYNC))) c->sync();
-}
-
-// ------------------------------------------------------------------------------------------------
-// trim-and-join of a batch's waveform rows (include/zvx.h: zvx_join, zvx_trim_bounds)
-// ------------------------------------------------------------------------------------------------
-constexpr int JOIN_MAX_UNITS_PER_FRAME = 32;   // hop-block sums serve frames of up to this many blocks; longer ratios take the per-frame path
-
-void join_check(const char* who, const void* in, const int32_t* nsamples, int B, int Nmax, const int32_t* gap, const zvx_join_params* p) {
-    rows_check(who, in, nsamples, B, Nmax);
-    if (!p) fail(ZVX_E_INVALID, "%s: params is NULL", who);
-    if (p->frame < 2 || p->hop < 1 || p->hop > p->frame) fail(ZVX_E_INVALID, "%s: frame %d / hop %d (frame >= 2, 1 <= hop <= frame)", who, p->frame, p->hop);
-    if (p->keep < 0 || p->fade < 0) fail(ZVX_E_INVALID, "%s: keep %d / fade %d must not be negative", who, p->keep, p->fade);
-    if (!std::isfinite(p->top_db)) fail(ZVX_E_INVALID, "%s: top_db is not finite", who);
-    for (int b = 0; gap && b < B; b++) if (gap[b] < 0) fail(ZVX_E_INVALID, "%s: gap[%d]=%d is negative", who, b, gap[b]);
-}
-
-// queues the frame-power and bounds launches; "join.bounds" then holds {begin, end} per row.  Returns the device rows and the samples read.
-const float* join_bounds(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_join_params* p, int flags, double* read) {
-    const DevRows rows = stage_rows(c, "join", in, nsamples, B, Nmax, flags);
-    JoinBoundsArgs a{};
-    a.x = rows.x; a.x_bs = Nmax; a.nsamples = rows.len; a.B = B;
-    a.frame = p->frame; a.hop = p->hop; a.keep = p->keep;
-    a.tiled = (p->frame % p->hop == 0 && p->frame / p->hop <= JOIN_MAX_UNITS_PER_FRAME) ? 1 : 0;
-    a.trim = p->top_db > 0.f ? 1 : 0;
-    a.k = pow(10.0, -(double)p->top_db / 10.0); a.floor = 1e-20 * (double)p->frame;
-    long units_max = 0; double nin = 0;
-    for (int b = 0; b < B; b++) {
-        if (nsamples[b] < p->frame) continue;
-        const long nf = 1 + ((long)nsamples[b] + 2 * (p->frame / 2) - p->frame) / p->hop;
-        units_max = std::max(units_max, a.tiled ? nf - 1 + p->frame / p->hop : nf);
-        nin += nsamples[b];
-    }
-    a.upitch = units_max;
-    a.unit = a.trim && units_max > 0 ? (double*)c->buf("join.unit", (size_t)B * units_max * sizeof(double)) : nullptr;
-    a.bounds = c->ibuf("join.bounds", (size_t)2 * B);
-    launch_join_powers(a, units_max, c->stream);
-    launch_join_bounds(a, c->stream);
-    *read = a.trim ? nin : 0.0;
-    return rows.x;
-}
-
-// the launches of one call as ONE timed group under "post.join"; its byte count is only known after the call's wait
-struct JoinTimer {
-    zvx_ctx* c; TagScope scope; GemmEvent ev{}; bool prof;
-    explicit JoinTimer(zvx_ctx* c_) : c(c_), scope(c_, "post.join", ZVX_T_JOIN), prof(c_->profile >= 2 && c_->profile_only < 0) {
-        if (prof) { ev.a = c->new_event(); ev.b = c->new_event(); HIPCHK(hipEventRecord(ev.a, c->stream)); }
-    }
-    void stop() { if (prof) HIPCHK(hipEventRecord(ev.b, c->stream)); scope.close(); }
-    void commit(double bytes) { if (prof) { ev.variant = -1; ev.flops = 0; ev.bytes = bytes; ev.tag = "post.join"; c->pending.push_back(ev); prof = false; } }
-};
-
-// join_bounds as a call's whole timed group, then the wait for its result.  Returns the pinned {begin, end} words of every row.
-const int* bounds_to_host(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_join_params* p, int flags) {
-    int* host = (int*)c->join_pinned((size_t)2 * B * sizeof(int));
-    JoinTimer t(c);
-    double read = 0;
-    join_bounds(c, in, nsamples, B, Nmax, p, flags, &read);
-    t.stop();
-    HIPCHK(hipMemcpyAsync(host, c->ibuf("join.bounds", 0), (size_t)2 * B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));
-    t.commit(read * 4.0);
-    return host;
-}
-
-void do_trim_bounds(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_join_params* p, int32_t* begin, int32_t* end, int flags) {
-    join_check("zvx_trim_bounds", in, nsamples, B, Nmax, nullptr, p);
-    if (!begin || !end) fail(ZVX_E_INVALID, "zvx_trim_bounds: NULL output");
-    flags_check("zvx_trim_bounds", flags, ZVX_DEVICE_IN);
-    const int* host = bounds_to_host(c, in, nsamples, B, Nmax, p, flags);
-    for (int b = 0; b < B; b++) { begin[b] = host[2 * b]; end[b] = host[2 * b + 1]; }
-    c->sync();
-}
-
-void do_join(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const int32_t* gap, const zvx_join_params* p, void* out,
-             int64_t out_capacity, int64_t* out_len, int64_t* seg_pos, int32_t* seg_begin, int32_t* seg_len, int flags) {
-    join_check("zvx_join", in, nsamples, B, Nmax, gap, p);
-    if (!out || !out_len || out_capacity < 0) fail(ZVX_E_INVALID, "zvx_join: bad output arguments");
-    flags_check("zvx_join", flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_PCM16);
-    const int pcm16 = (flags & ZVX_PCM16) ? 1 : 0;
-    const size_t ss = pcm16 ? 2 : 4;
-    long upper = 0;                                          // what the row can hold at most: nothing trimmed
-    for (int b = 0; b < B; b++) upper += (long)nsamples[b] + (gap ? gap[b] : 0);
-    // layout words in one block: pos [B + 1] int64, then seg_begin [B], seg_len [B]
-    const size_t lay_bytes = (size_t)(B + 1) * 8 + (size_t)B * 8;
-    const bool host_out = !(flags & ZVX_DEVICE_OUT);
-    const long stage = std::min<long>(upper, out_capacity);  // a host row is staged: at most this much can be delivered
-    const size_t lay_pad = (lay_bytes + 255) & ~(size_t)255;
-    char* host = (char*)c->join_pinned(lay_pad + (host_out ? (size_t)stage * ss : 0));
-    char* lay = (char*)c->buf("join.layout", lay_bytes);
-    long* pos_d = (long*)lay; int* begin_d = (int*)(lay + (size_t)(B + 1) * 8); int* len_d = begin_d + B;
-    const int* gap_d = gap ? c->upload_ints("join.gap", gap, B) : nullptr;
-    void* odev = host_out ? c->buf("join.out", (size_t)std::max(stage, 1L) * ss + 16) : out;
-    JoinTimer t(c);
-    double read = 0;
-    const float* x_dev = join_bounds(c, in, nsamples, B, Nmax, p, flags, &read);
-    launch_join_layout(c->ibuf("join.bounds", 0), gap_d, B, pos_d, begin_d, len_d, c->stream);
-    JoinCopyArgs a{};
-    a.x = x_dev; a.x_bs = Nmax; a.B = B; a.pos = pos_d; a.seg_begin = begin_d; a.seg_len = len_d;
-    a.out = odev; a.cap = out_capacity; a.pcm16 = pcm16; a.fade = p->fade;
-    launch_join_copy(a, upper, c->stream);
-    t.stop();
-    HIPCHK(hipMemcpyAsync(host, lay, lay_bytes, hipMemcpyDeviceToHost, c->stream));
-    if (host_out && stage > 0) HIPCHK(hipMemcpyAsync(host + lay_pad, odev, (size_t)stage * ss, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));                 // the call's one wait
-    const int64_t* pos_h = (const int64_t*)host;
-    const int32_t* begin_h = (const int32_t*)(host + (size_t)(B + 1) * 8); const int32_t* len_h = begin_h + B;
-    const int64_t total = pos_h[B];
-    *out_len = total;
-    double kept = 0;
-    for (int b = 0; b < B; b++) {
-        if (seg_pos) seg_pos[b] = pos_h[b];
-        if (seg_begin) seg_begin[b] = begin_h[b];
-        if (seg_len) seg_len[b] = len_h[b];
-        kept += len_h[b];
-    }
-    const bool fits = total <= out_capacity;
-    t.commit(read * 4.0 + (fits ? kept * 4.0 + (double)total * ss : 0.0));
-    c->sync();
-    if (!fits) fail(ZVX_E_BUFFER, "zvx_join: the joined row has %lld samples, out_capacity is %lld", (long long)total, (long long)out_capacity);
-    if (host_out && total > 0) memcpy(out, host + lay_pad, (size_t)total * ss);
-}
-
-// ------------------------------------------------------------------------------------------------
 // speaker enrolment from raw audio (include/zvx.h: zvx_spkemb_wav): resample -> trim bounds -> [the call's one wait] -> window cut with
 // reflect padding -> log-mel -> speaker encoder.  Every step but the window cut is the launch sequence of the entry point that defines it.
 // ------------------------------------------------------------------------------------------------
@@ -2584,24 +1710,6 @@ void do_spkemb_wav(zvx_ctx* c, const float* wav, const int32_t* nsamples, int B,
 // ------------------------------------------------------------------------------------------------
 // integrated loudness and gain of a batch's waveform rows (include/zvx.h: zvx_loudness, zvx_normalize)
 // ------------------------------------------------------------------------------------------------
-const LoudCoef& loud_coef(zvx_ctx* c, int rate) {
-    auto it = c->loud_coefs.find(rate);
-    if (it != c->loud_coefs.end()) return it->second;
-    const double pi = 3.14159265358979323846, fs = (double)rate;
-    LoudCoef k{};
-    {   // stage 1: high shelf
-        const double f0 = 1681.974450955533, G = 3.999843853973347, Q = 0.7071752369554196;
-        const double K = tan(pi * f0 / fs), Vh = pow(10.0, G / 20.0), Vb = pow(Vh, 0.4996667741545416), a0 = 1.0 + K / Q + K * K;
-        k.b0 = (Vh + Vb * K / Q + K * K) / a0; k.b1 = 2.0 * (K * K - Vh) / a0; k.b2 = (Vh - Vb * K / Q + K * K) / a0;
-        k.a1 = 2.0 * (K * K - 1.0) / a0; k.a2 = (1.0 - K / Q + K * K) / a0;
-    }
-    {   // stage 2: high pass, b = [1, -2, 1]
-        const double f0 = 38.13547087602444, Q = 0.5003270373238773;
-        const double K = tan(pi * f0 / fs), a0 = 1.0 + K / Q + K * K;
-        k.c1 = 2.0 * (K * K - 1.0) / a0; k.c2 = (1.0 - K / Q + K * K) / a0;
-    }
-    return c->loud_coefs[rate] = k;
-}
 
 // The measuring half of zvx_loudness / zvx_normalize / zvx_loudness_stats: the rows on the device, the unit and result buffers, and the
 // arguments of launch_loud_units / launch_loud_gates (measure only: the caller of zvx_normalize adds its gain parameters).
@@ -2811,534 +1919,6 @@ void do_pitch(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int N
         if (f0 && F > 0) memcpy(f0 + (size_t)b * f_stride, f0_h + (size_t)b * fpitch * sizeof(float), (size_t)F * sizeof(float));
         if (aper && F > 0) memcpy(aper + (size_t)b * f_stride, ap_h + (size_t)b * fpitch * sizeof(float), (size_t)F * sizeof(float));
     }
-}
-
-// ------------------------------------------------------------------------------------------------
-// true-peak metering and the look-ahead limiter (include/zvx.h: zvx_true_peak, zvx_limit)
-// ------------------------------------------------------------------------------------------------
-// w[k] = (1 + cos(pi k / (W + 1))) / (2 (W + 1)), k = -W .. W, divided by their own sum; uploaded on first use of W, then kept.
-const double* limit_win(zvx_ctx* c, int W) {
-    auto it = c->lim_wins.find(W);
-    if (it != c->lim_wins.end()) return it->second;
-    std::vector<double> w(2 * (size_t)W + 1);
-    double sum = 0.0;
-    for (int k = -W; k <= W; k++) sum += w[k + W] = (1.0 + cos(M_PI * (double)k / (double)(W + 1))) / (2.0 * (double)(W + 1));
-    for (double& v : w) v /= sum;
-    double* d = (double*)c->buf("lim.win." + std::to_string(W), w.size() * sizeof(double));
-    HIPCHK(hipMemcpyAsync(d, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));                 // `w` goes away; once per W
-    return c->lim_wins[W] = d;
-}
-
-// The window of the denoiser and the limiter (RowsWindow): the checks of its own numbers, then per row the emitted count after the support
-// condition of include/zvx.h for the reach R (the limiter: 2 W + H; the denoiser: n_fft - 1)
-// (`row` >= 0: the window is that row's own -- zvx_denoise_rows, zvx_limit_rows -- and every message names it)
-void window_args_check(const char* who, const RowsWindow& w, int row) {
-    char at[32] = "";
-    if (row >= 0) snprintf(at, sizeof at, "row %d: ", row);
-    if (w.in_origin < 0 || w.out_begin < 0) fail(ZVX_E_INVALID, "%s: %sin_origin %lld / out_begin %lld is negative", who, at, (long long)w.in_origin, (long long)w.out_begin);
-    if (w.out_count < -1) fail(ZVX_E_INVALID, "%s: %sout_count %lld (-1: to the end of the signal)", who, at, (long long)w.out_count);
-    if (w.last != 0 && w.last != 1) fail(ZVX_E_INVALID, "%s: %slast is %d (0 or 1)", who, at, w.last);
-    if (w.out_count == -1 && !w.last) fail(ZVX_E_INVALID, "%s: %sout_count -1 needs last: the signal's end is not in the window", who, at);
-}
-// (Rr >= 0: the reach is asymmetric -- R to the left, Rr to the right, the leveler's RL / RR -- and the messages name the side's own)
-int32_t window_count_row(const char* who, const RowsWindow& w, int32_t nsamples, int b, int64_t R, int64_t Rr = -1) {
-    const char* ln = Rr >= 0 ? "RL" : "R";
-    const char* rn = Rr >= 0 ? "RR" : "R";
-    if (Rr < 0) Rr = R;
-    const int64_t end_in = w.in_origin + nsamples;
-    const int64_t n = w.out_count >= 0 ? w.out_count : std::max<int64_t>(0, end_in - w.out_begin);
-    if (n > 0) {
-        const int64_t end_out = w.out_begin + n;
-        if (w.in_origin > w.out_begin || end_out > end_in)
-            fail(ZVX_E_INVALID, "%s: row %d: outputs [%lld, %lld) lie outside the window's samples [%lld, %lld)", who, b, (long long)w.out_begin,
-                 (long long)end_out, (long long)w.in_origin, (long long)end_in);
-        if (w.in_origin != 0 && w.out_begin - R < w.in_origin)
-            fail(ZVX_E_INVALID, "%s: row %d: the reach %s = %lld needs %lld more samples in front of the window (in_origin %lld, out_begin %lld)", who, b,
-                 ln, (long long)R, (long long)(w.in_origin - (w.out_begin - R)), (long long)w.in_origin, (long long)w.out_begin);
-        if (!w.last && end_out - 1 + Rr > end_in - 1)
-            fail(ZVX_E_INVALID, "%s: row %d: the reach %s = %lld needs %lld more samples behind the window (outputs end at %lld, samples at %lld; or last)", who, b,
-                 rn, (long long)Rr, (long long)(end_out + Rr - end_in), (long long)end_out, (long long)end_in);
-    }
-    return (int32_t)n;                                       // n <= nsamples where n > 0
-}
-// The three ways a window reaches the denoiser and the limiter: none (the whole rows), ONE for the call (_ex), one per row (_rows)
-struct WindowsIn { enum Form { WHOLE, ONE, PER_ROW } form = WHOLE; RowsWindow one; const zvx_row_window* rows = nullptr; };
-// What those calls check of their windows, all before anything is queued -> the windows and per row the emitted count.  A call-wide window
-// is checked once and reported without a row number; the whole rows are their own window and out_rows_check has covered their stride.
-RowsWindows rows_windows_check(const char* who, const WindowsIn& win, const int32_t* nsamples, int B, int64_t R, const float* in, const void* out,
-                               int64_t out_stride, int64_t Rr = -1) {
-    const bool per_row = win.form == WindowsIn::PER_ROW;
-    if (per_row && !win.rows) fail(ZVX_E_INVALID, "%s: win is NULL", who);
-    RowsWindows rw;
-    rw.w.assign(per_row ? (size_t)B : 1, win.one); rw.cnt.resize((size_t)B);
-    if (!per_row) window_args_check(who, win.one, -1);
-    for (int b = 0; b < B; b++) {
-        if (per_row) {
-            if (win.rows[b].reserved != 0) fail(ZVX_E_INVALID, "%s: row %d: reserved is %d (must be 0)", who, b, win.rows[b].reserved);
-            rw.w[(size_t)b] = RowsWindow{win.rows[b].in_origin, win.rows[b].out_begin, win.rows[b].out_count, win.rows[b].last};
-            window_args_check(who, rw.w[(size_t)b], b);
-        }
-        rw.cnt[(size_t)b] = window_count_row(who, rw.at(b), nsamples[b], b, R, Rr);
-        rw.cnt_max = std::max<long>(rw.cnt_max, rw.cnt[(size_t)b]);
-    }
-    if (win.form == WindowsIn::WHOLE) return rw;
-    if (out_stride < rw.cnt_max) fail(ZVX_E_INVALID, "%s: out_stride %lld is smaller than the longest output row %ld", who, (long long)out_stride, rw.cnt_max);
-    if (out == (const void*)in)
-        for (int b = 0; b < B; b++) {
-            const RowsWindow& w = rw.at(b);
-            if (rw.cnt[(size_t)b] <= 0 || w.out_begin == w.in_origin) continue;
-            if (!per_row) fail(ZVX_E_INVALID, "%s: in place needs out_begin == in_origin", who);
-            fail(ZVX_E_INVALID, "%s: row %d: in place needs out_begin == in_origin (%lld, %lld)", who, b, (long long)w.out_begin, (long long)w.in_origin);
-        }
-    return rw;
-}
-
-// the checks of the limiter's own parameters (zvx_limit, zvx_limit_ex, zvx_stream_open) -> W
-void limit_os_check(const char* who, int os) {
-    if (os != 1 && os != 2 && os != 4 && os != 8) fail(ZVX_E_INVALID, "%s: oversample %d is none of 1, 2, 4, 8", who, os);
-}
-int limit_params_check(const char* who, int rate, const zvx_limit_params* p) {
-    if (!std::isfinite(p->ceiling) || !(p->ceiling > 0.f) || p->ceiling > 8.f) fail(ZVX_E_INVALID, "%s: ceiling must be finite and lie in (0, 8]", who);
-    if (!std::isfinite(p->window_ms) || !(p->window_ms > 0.f)) fail(ZVX_E_INVALID, "%s: window_ms must be finite and positive", who);
-    const double w = std::max(1.0, rint((double)rate * (double)p->window_ms / 1000.0));
-    if (w > (double)LIMIT_MAX_W) fail(ZVX_E_UNSUPPORTED, "%s: window of %.0f samples (at most %d)", who, w, LIMIT_MAX_W);
-    return (int)w;
-}
-
-// The limiter over B rows with a window each, every caller's launches: ONE table upload, the envelope, gain and reduce launches under one
-// timed group -> the device words res[b] = peak, res[B + b] = min gain.  p == nullptr: measure only (zvx_true_peak) at oversampling
-// `measure_os` -- no gain launch, no envelope stored, res[B + b] = 1.  The caller has validated the rows.
-const float* run_limit_rows(zvx_ctx* c, const char* who, const PostRow* rows, int B, const zvx_limit_params* p, int W, int pcm16, int measure_os = 0) {
-    const bool lim = p != nullptr;
-    LimitArgs a{};
-    a.os = lim ? p->oversample : measure_os;
-    if (a.os > 1) {
-        const zvx_ctx::RsBank& bk = rs_bank(c, a.os, 1);
-        if (bk.T != 21 || bk.half != 10 * a.os) fail(ZVX_E_STATE, "%s: the (%d, 1) bank has %d taps per output", who, a.os, bk.T);
-        a.T = bk.T; a.pitch = bk.pitch; a.bank = bk.dev;
-    }
-    if (lim) { a.c = p->ceiling; a.W = W; a.win = limit_win(c, W); }
-    std::vector<LimitRow> tab((size_t)B);
-    double n_sum = 0, cnt_sum = 0;
-    long n_max = 0, cnt_max = 0;
-    size_t env_floats = 0;
-    for (int b = 0; b < B; b++) {
-        const PostRow& r = rows[b];
-        n_max = std::max<long>(n_max, r.n); cnt_max = std::max<long>(cnt_max, r.cnt);
-        n_sum += r.n; cnt_sum += r.cnt; env_floats += (size_t)r.n;
-    }
-    float* env = lim ? c->fbuf("lim.env", std::max<size_t>(env_floats, 1)) : nullptr;
-    for (int b = 0; b < B; b++) {
-        const PostRow& r = rows[b];
-        LimitRow& t = tab[(size_t)b];
-        t.x = r.in; t.out = r.out; t.env = env;
-        t.n = r.n; t.off = r.cnt > 0 ? (int)(r.w.out_begin - r.w.in_origin) : 0; t.cnt = r.cnt; t.pad_ = 0;
-        if (env) env += r.n;
-    }
-    a.B = B; a.pcm16 = pcm16;
-    a.ppitch = (int)std::max(1L, (n_max + LIMIT_TILE - 1) / LIMIT_TILE);
-    a.gtiles = (int)std::max(1L, (cnt_max + LIMIT_TILE - 1) / LIMIT_TILE);                // <= ppitch: cnt <= n in every row
-    a.part_max = c->fbuf("lim.part", (size_t)2 * B * a.ppitch);
-    a.part_min = lim ? a.part_max + (size_t)B * a.ppitch : nullptr;
-    a.res = c->fbuf("lim.res", (size_t)2 * B);
-    LimitRow* tab_d = (LimitRow*)c->buf("lim.rows", (size_t)B * sizeof(LimitRow));
-    c->upload(tab_d, tab.data(), (size_t)B * sizeof(LimitRow));
-    a.rows = tab_d;
-    TagScope scope(c, "post.limit");
-    c->timed(0.0, 4.0 * n_sum + (lim ? (pcm16 ? 2.0 : 4.0) * cnt_sum : 0.0), [&] {
-        launch_limit_env(a, c->stream);
-        if (lim && !launch_limit_gain(a, c->stream)) fail(ZVX_E_UNSUPPORTED, "%s: a window of %d samples does not fit the LDS of a workgroup", who, W);
-        launch_limit_reduce(a, c->stream);
-    });
-    return a.res;
-}
-
-// zvx_true_peak (p == nullptr: the envelope's maximum only, results in peak_in), zvx_limit, zvx_limit_ex and zvx_limit_rows: every check before
-// anything is allocated, uploaded or queued
-void do_limit(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_limit_params* p,
-              int oversample, void* out, int64_t out_stride, float* peak_in, float* min_gain, int flags, const WindowsIn& win = {}) {
-    const bool lim = p != nullptr;
-    if (!lim && !peak_in) fail(ZVX_E_INVALID, "%s: tpeak is NULL", who);
-    rows_check(who, in, nsamples, B, Nmax, 65535);
-    if (rate < 4000 || rate > 192000) fail(ZVX_E_INVALID, "%s: rate %d outside [4000, 192000]", who, rate);
-    flags_check(who, flags, lim ? (ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16) : ZVX_DEVICE_IN);
-    const int os = lim ? p->oversample : oversample;
-    limit_os_check(who, os);
-    if (lim) out_rows_check(who, in, out, out_stride, Nmax, flags);
-    const int W = lim ? limit_params_check(who, rate, p) : 0;
-    const RowsWindows rw = rows_windows_check(who, win, nsamples, B, 2 * (int64_t)W + (os > 1 ? LIMIT_ENV_REACH : 0), in, out, out_stride);
-    const float* words = post_call(c, "lim", in, nsamples, B, Nmax, out, out_stride, lim, flags, rw, (size_t)B * 8, peak_in || min_gain,
-        [&](const PostRow* rows) { return run_limit_rows(c, who, rows, B, p, W, (flags & ZVX_PCM16) ? 1 : 0, os); });
-    copy_word_pairs(words, B, peak_in, min_gain);            // words: peak [B], then min gain [B]
-}
-
-// ------------------------------------------------------------------------------------------------
-// leveler (include/zvx.h: zvx_level, zvx_level_ex, zvx_level_rows)
-// ------------------------------------------------------------------------------------------------
-// the checks of the leveler's own parameters -> S and a, in units of 100 ms (on the host in double)
-LevelGeom level_params_check(const char* who, int rate, const zvx_level_params* p) {
-    if (!std::isfinite(p->target_lufs) || p->target_lufs < -70.f || p->target_lufs > 0.f) fail(ZVX_E_INVALID, "%s: target_lufs must lie in [-70, 0]", who);
-    if (!std::isfinite(p->max_gain_db) || p->max_gain_db < 0.f) fail(ZVX_E_INVALID, "%s: max_gain_db must be finite and not negative", who);
-    if (!std::isfinite(p->window_ms) || p->window_ms < 0.f) fail(ZVX_E_INVALID, "%s: window_ms must be finite and not negative", who);
-    if (!std::isfinite(p->lookahead_ms) || p->lookahead_ms < 0.f) fail(ZVX_E_INVALID, "%s: lookahead_ms must be finite and not negative", who);
-    const double S = std::max(1.0, rint((double)p->window_ms / 100.0)), a = rint((double)p->lookahead_ms / 100.0);
-    if (S > (double)LEVEL_MAX_S) fail(ZVX_E_UNSUPPORTED, "%s: a window of %.0f units of 100 ms (at most %d)", who, S, LEVEL_MAX_S);
-    if (a > S) fail(ZVX_E_INVALID, "%s: the look-ahead of %.0f units exceeds the window of %.0f units (a <= S)", who, a, S);
-    LevelGeom g{};
-    g.h = (rate + 5) / 10; g.S = (int)S; g.a = (int)a;
-    g.RL = (int64_t)(g.S + 3 - g.a) * g.h - 1; g.RR = (int64_t)(g.a + 1) * g.h - 1;
-    return g;
-}
-
-// The units under the nodes of a row's emitted range (k_level_apply forms the same per tile): [first, last], last < first where none is
-// needed; U = the signal's whole units where the window is last (the clamp of the nodes), LEVEL_OPEN otherwise.
-struct LevelUnits { long first = 0, last = -1, U = LEVEL_OPEN; };
-LevelUnits level_units(const RowsWindow& w, int32_t n, int32_t cnt, const LevelGeom& g) {
-    LevelUnits u;
-    const int64_t h = g.h;
-    u.U = w.last ? (long)((w.in_origin + n) / h) : LEVEL_OPEN;
-    if (cnt > 0 && u.U > 0) {
-        auto clampu = [](int64_t v, int64_t hi) { return v < 0 ? (int64_t)0 : (v > hi ? hi : v); };
-        const int64_t q0 = w.out_begin / h, q1 = (w.out_begin + cnt - 1) / h;
-        const int64_t mlo = clampu(q0 + g.a - 1, u.U - 1), mhi = clampu(q1 + g.a, u.U - 1);
-        u.first = (long)std::max<int64_t>(0, mlo - g.S + 1); u.last = (long)mhi;
-    }
-    return u;
-}
-// The left support of a LAST window that begins inside its signal: where the outputs begin in the signal's last a units (or its tail) the
-// clamp to U - 1 moves the first node's window to the left of where RL assumes it, so the oldest needed unit is checked itself -- its
-// warm-up starts at (first - 2) h, which must lie inside the window.  (Without last, and wherever the clamp does not act, RL implies it.)
-void level_clamped_support_check(const char* who, const RowsWindows& rw, const int32_t* nsamples, int B, const LevelGeom& g) {
-    for (int b = 0; b < B; b++) {
-        const RowsWindow& w = rw.at(b);
-        if (!w.last || w.in_origin == 0) continue;
-        const LevelUnits u = level_units(w, nsamples[b], rw.cnt[(size_t)b], g);
-        if (u.last < u.first) continue;
-        const int64_t start = ((int64_t)u.first - 2) * g.h;
-        if (start < w.in_origin)
-            fail(ZVX_E_INVALID, "%s: row %d: the window is last and its first node is clamped to the signal's last unit %ld: unit %ld of its window needs %lld more samples "
-                 "in front of the window (in_origin %lld, out_begin %lld)", who, b, u.U - 1, u.first, (long long)(w.in_origin - std::max<int64_t>(start, 0)), (long long)w.in_origin,
-                 (long long)w.out_begin);
-    }
-}
-
-// The leveler over B rows with a window each, every caller's launches: ONE table upload, the unit, apply and reduce launches under one timed
-// group -> the device words res[b] = gain_lo, res[B + b] = gain_hi.  The caller has validated the rows (the support condition included:
-// it is what keeps every needed unit inside the row).
-const float* run_level_rows(zvx_ctx* c, const PostRow* rows, int B, int rate, const zvx_level_params* p, const LevelGeom& g, int pcm16) {
-    LevelArgs a{};
-    a.B = B; a.h = g.h; a.S = g.S; a.a = g.a; a.pcm16 = pcm16;
-    a.k = loud_coef(c, rate);
-    a.gate = pow(10.0, (-70.0 + 0.691) / 10.0);
-    a.target = (double)p->target_lufs; a.gmax = pow(10.0, (double)p->max_gain_db / 20.0);
-    std::vector<LevelRow> tab((size_t)B);
-    double n_sum = 0, cnt_sum = 0;
-    long cnt_max = 0, units_max = 0;
-    size_t units = 0;
-    for (int b = 0; b < B; b++) {
-        const PostRow& r = rows[b];
-        LevelRow& t = tab[(size_t)b];
-        t.x = r.in; t.out = r.out; t.p = nullptr;
-        t.in_origin = (long)r.w.in_origin;
-        t.n = r.n; t.off = r.cnt > 0 ? (int)(r.w.out_begin - r.w.in_origin) : 0; t.cnt = r.cnt; t.pad_ = 0;
-        const LevelUnits u = level_units(r.w, r.n, r.cnt, g);
-        t.U = u.U; t.q_first = u.first; t.q_last = u.last;
-        const long nu = t.q_last - t.q_first + 1;
-        units += (size_t)nu; units_max = std::max(units_max, nu);
-        cnt_max = std::max<long>(cnt_max, r.cnt); n_sum += r.n; cnt_sum += r.cnt;
-    }
-    double* pbuf = (double*)c->buf("lvl.p", std::max<size_t>(units, 1) * sizeof(double));
-    for (int b = 0; b < B; b++) {
-        LevelRow& t = tab[(size_t)b];
-        t.p = pbuf; pbuf += t.q_last - t.q_first + 1;
-    }
-    a.ppitch = (int)std::max(1L, (cnt_max + 3 + LEVEL_TILE - 1) / LEVEL_TILE);          // (+ 3: the address alignment shifts the groups by up to 3 samples)
-    a.part_lo = c->fbuf("lvl.part", (size_t)2 * B * a.ppitch);
-    a.part_hi = a.part_lo + (size_t)B * a.ppitch;
-    a.res = c->fbuf("lvl.res", (size_t)2 * B);
-    LevelRow* tab_d = (LevelRow*)c->buf("lvl.rows", (size_t)B * sizeof(LevelRow));
-    c->upload(tab_d, tab.data(), (size_t)B * sizeof(LevelRow));
-    a.rows = tab_d;
-    TagScope scope(c, "post.level");
-    c->timed(0.0, 4.0 * n_sum + (pcm16 ? 2.0 : 4.0) * cnt_sum, [&] {
-        launch_level_units(a, units_max, c->stream);
-        launch_level_apply(a, c->stream);
-        launch_level_reduce(a, c->stream);
-    });
-    return a.res;
-}
-
-// zvx_level, zvx_level_ex and zvx_level_rows: every check before anything is allocated, uploaded or queued
-void do_level(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, int rate, const zvx_level_params* p,
-              void* out, int64_t out_stride, float* gain_lo, float* gain_hi, int flags, const WindowsIn& win = {}) {
-    if (!p) fail(ZVX_E_INVALID, "%s: params is NULL", who);
-    rows_check(who, in, nsamples, B, Nmax, 65535);
-    if (rate < 4000 || rate > 192000) fail(ZVX_E_INVALID, "%s: rate %d outside [4000, 192000]", who, rate);
-    flags_check(who, flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16);
-    out_rows_check(who, in, out, out_stride, Nmax, flags);
-    const LevelGeom g = level_params_check(who, rate, p);
-    const RowsWindows rw = rows_windows_check(who, win, nsamples, B, g.RL, in, out, out_stride, g.RR);
-    level_clamped_support_check(who, rw, nsamples, B, g);
-    const float* words = post_call(c, "lvl", in, nsamples, B, Nmax, out, out_stride, true, flags, rw, (size_t)B * 8, gain_lo || gain_hi,
-        [&](const PostRow* rows) { return run_level_rows(c, rows, B, rate, p, g, (flags & ZVX_PCM16) ? 1 : 0); });
-    copy_word_pairs(words, B, gain_lo, gain_hi);             // words: gain_lo [B], then gain_hi [B]
-}
-
-// ------------------------------------------------------------------------------------------------
-// vocoder-bias denoiser (include/zvx.h: zvx_denoise, zvx_denoise_bias; kernels: spectral.hip)
-// ------------------------------------------------------------------------------------------------
-DnGeom dn_geom(const zvx_ctx* c, const char* who) {
-    const int n_fft = c->t("mel.dft").dim(2), hop = c->hop;
-    int lg = 0;
-    while ((1 << lg) < n_fft && lg < 30) lg++;
-    if (n_fft < 4 || n_fft > DENOISE_POINTS || (1 << lg) != n_fft)
-        fail(ZVX_E_UNSUPPORTED, "%s: the model's n_fft = %d is not a power of two in 4 .. %d", who, n_fft, DENOISE_POINTS);
-    if (hop < 1 || hop > n_fft) fail(ZVX_E_UNSUPPORTED, "%s: hop %d with n_fft %d", who, hop, n_fft);
-    return {n_fft, lg, hop, (n_fft - hop) / 2, n_fft / 2 + 1};
-}
-// the least length of a non-empty row: zvx_melspec's conditions (a mirror exists on both sides, one whole frame)
-int dn_min_samples(const DnGeom& g) { return std::max(g.pad + 1, g.n_fft - 2 * g.pad); }
-int dn_frames(const DnGeom& g, long n) { return n > 0 ? (int)(1 + (n + 2 * g.pad - g.n_fft) / g.hop) : 0; }
-// zvx_melspec's length conditions hold for the whole SIGNAL of row b: known where it ends with the window (no window: the row is its signal)
-void stft_len_check(const char* who, const DnGeom& g, int b, int32_t n, const RowsWindow& w = {}) {
-    if (w.last && n > 0 && w.in_origin + n < dn_min_samples(g))
-        fail(ZVX_E_INVALID, "%s: row %d has %lld samples; a row that is not empty needs at least %d (zvx_melspec's conditions)", who, b,
-             (long long)(w.in_origin + n), dn_min_samples(g));
-}
-
-// Twiddles, window and squared window, designed in double and kept for the life of the context.  win_length is not a manifest key: it is
-// read off the window inside mel.dft (row 0 of the cosine block is the window itself; a periodic Hann is zero at its first sample only).
-const zvx_ctx::DnTables& dn_tables(zvx_ctx* c, const DnGeom& g) {
-    if (c->dn_tab.n_fft == g.n_fft) return c->dn_tab;
-    const int N = g.n_fft;
-    const float* row0 = c->t("mel.dft").host;
-    int t0 = -1, t1 = -1;
-    for (int t = 0; row0 && t < N; t++) if (row0[t] != 0.f) { if (t0 < 0) t0 = t; t1 = t; }
-    const int WL = t1 - t0 + 2, lp = t0 - 1;
-    if (t0 < 1 || WL > N || lp != (N - WL) / 2) fail(ZVX_E_MANIFEST, "zvx_denoise: mel.dft does not carry a centred periodic Hann window");
-    std::vector<double> w(N, 0.0), w2(N);
-    for (int i = 0; i < WL; i++) w[lp + i] = 0.5 + 0.5 * cos(M_PI * (double)(2 * i - WL) / (double)WL);     // numpy.hanning(WL + 1)[:-1]
-    w[lp] = 0.0;
-    for (int t = 0; t < N; t++) w2[t] = w[t] * w[t];
-    double top = 0.0;
-    for (int t = 0; t < g.hop; t++) { double s = 0.0; for (int u = t; u < N; u += g.hop) s += w2[u]; top = std::max(top, s); }
-    std::vector<float> f(3 * (size_t)N);
-    for (int m = 0; m < N; m++) {
-        const double ang = 2.0 * M_PI * (double)m / (double)N;
-        f[2 * (size_t)m] = (float)cos(ang); f[2 * (size_t)m + 1] = (float)-sin(ang);
-        f[2 * (size_t)N + m] = (float)w[m];
-    }
-    char* d = (char*)c->buf("dn.tab", (size_t)N * 8 + (size_t)N * 12);
-    HIPCHK(hipMemcpyAsync(d, w2.data(), (size_t)N * 8, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipMemcpyAsync(d + (size_t)N * 8, f.data(), (size_t)N * 12, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(hipStreamSynchronize(c->stream));                 // the host vectors go away; once per context
-    zvx_ctx::DnTables& tb = c->dn_tab;
-    tb.n_fft = N; tb.log2n = g.log2n; tb.win_length = WL; tb.den_min = 1e-3 * top;
-    tb.win2 = (const double*)d; tb.twid = (const float*)(d + (size_t)N * 8); tb.win = tb.twid + 2 * (size_t)N;
-    return tb;
-}
-void dn_fill(DenoiseArgs& a, const DnGeom& g, const zvx_ctx::DnTables& tb) {
-    a.n_fft = g.n_fft; a.log2n = g.log2n; a.hop = g.hop; a.pad = g.pad;
-    a.twid = tb.twid; a.win = tb.win; a.win2 = tb.win2; a.den_min = tb.den_min;
-}
-double dn_fft_flops(const DnGeom& g, double frames, int transforms) { return transforms * frames * 5.0 * g.n_fft * g.log2n; }
-
-// the checks of the denoiser's own parameters and bias (zvx_denoise, zvx_denoise_ex, zvx_stream_open) -> the model's STFT geometry
-DnGeom denoise_params_check(const zvx_ctx* c, const char* who, const float* bias, const zvx_denoise_params* p) {
-    if (!bias || !p) fail(ZVX_E_INVALID, "%s: %s is NULL", who, !bias ? "bias" : "params");
-    if (!std::isfinite(p->strength) || p->strength < 0.f) fail(ZVX_E_INVALID, "%s: strength must be finite and not negative", who);
-    if (!(p->floor >= 0.f && p->floor <= 1.f)) fail(ZVX_E_INVALID, "%s: floor must lie in [0, 1]", who);
-    const DnGeom g = dn_geom(c, who);
-    for (int k = 0; k < g.nf; k++) if (!(bias[k] >= 0.f)) fail(ZVX_E_INVALID, "%s: bias[%d] is negative or NaN", who, k);
-    return g;
-}
-
-// The denoiser over B rows with a window each, every caller's launches: ONE table upload, ONE bias upload, the frames and overlap-add
-// launches under one timed group.  The frames transformed of a row: from the first one that covers sample out_begin to the last one that
-// begins at or before the row's last emitted sample, on the signal's grid.  The kernels count frames from f_first, that first frame
-// rounded DOWN per ROW to a multiple of the frames per workgroup: every frame then sits in the slot of its workgroup it has in the
-// whole-row call and runs through the same instructions (the unrolled copies of a pass need not contract their multiply-adds alike), which
-// is what makes the bits equal.  The `skip` frames in front are neither loaded nor stored.  (spectral.hip, dn_frames_used)
-// The caller has validated the rows.
-// (the row table and its sums, shared with the watermark's embedder: run_watermark_rows)
-struct DnRowsPlan {
-    std::vector<DenoiseRow> tab; std::vector<size_t> work_at;
-    double frames = 0, n_sum = 0, cnt_sum = 0; long Fmax = 0, cnt_max = 0; size_t work_floats = 0;
-};
-DnRowsPlan dn_rows_plan(const DnGeom& g, const PostRow* rows, int B, bool copy) {
-    const int per = DENOISE_POINTS >> g.log2n;
-    DnRowsPlan pl;
-    pl.tab.resize((size_t)B); pl.work_at.resize((size_t)B);
-    for (int b = 0; b < B; b++) {
-        const PostRow& r = rows[b];
-        const RowsWindow& w = r.w;
-        const bool any = r.cnt > 0;
-        const int64_t off = any ? w.out_begin - w.in_origin : 0;
-        const int64_t p0 = w.out_begin + g.pad;
-        const int64_t f_need = any && p0 >= g.n_fft ? (p0 - g.n_fft) / g.hop + 1 : 0;
-        const int64_t f_first = f_need - f_need % per;
-        // where frame f_first begins, as an index into the window: in (off - n_fft - per hop, off + hop - n_fft], an int
-        const int64_t rel = any ? f_first * g.hop - g.pad - w.in_origin : -(int64_t)g.pad;
-        int64_t F = 0;
-        if (any) {
-            F = (off + r.cnt - 1 - rel) / g.hop + 1;
-            if (w.last) F = std::min<int64_t>(F, std::max<int64_t>(0, dn_frames(g, w.in_origin + r.n) - f_first));
-            pl.frames += (double)std::max<int64_t>(0, F - (f_need - f_first));
-        }
-        DenoiseRow& t = pl.tab[(size_t)b];
-        t.x = r.in; t.out = r.out; t.work = nullptr;
-        t.origin = (long)w.in_origin; t.f_first = (long)f_first;
-        t.n = r.n; t.skip = (int)(f_need - f_first); t.rel = (int)rel; t.off = (int)off; t.cnt = r.cnt;
-        t.mirrors = (w.in_origin == 0 ? 1 : 0) | (w.last ? 2 : 0);
-        pl.work_at[(size_t)b] = pl.work_floats;
-        if (!copy) pl.work_floats += (size_t)F * g.n_fft;
-        pl.Fmax = std::max<long>(pl.Fmax, (long)F); pl.cnt_max = std::max<long>(pl.cnt_max, r.cnt);
-        pl.n_sum += r.n; pl.cnt_sum += r.cnt;
-    }
-    return pl;
-}
-// the plan's rows on the device with their work buffers, and the launch arguments' geometry and tables
-void dn_rows_upload(zvx_ctx* c, const DnGeom& g, DnRowsPlan& pl, int B, bool copy, int pcm16, DenoiseArgs& a) {
-    a.copy = copy;                                           // a copy: the input's bits, nothing is transformed
-    if (!copy) {
-        dn_fill(a, g, dn_tables(c, g));
-        float* work = c->fbuf("dn.work", std::max<size_t>(pl.work_floats, 1));
-        for (int b = 0; b < B; b++) pl.tab[(size_t)b].work = work + pl.work_at[(size_t)b];
-    } else { a.n_fft = g.n_fft; a.log2n = g.log2n; a.hop = g.hop; a.pad = g.pad; }
-    a.Fmax = (int)pl.Fmax; a.B = B; a.pcm16 = pcm16;
-    DenoiseRow* tab_d = (DenoiseRow*)c->buf("dn.rows", (size_t)B * sizeof(DenoiseRow));
-    c->upload(tab_d, pl.tab.data(), (size_t)B * sizeof(DenoiseRow));
-    a.rows = tab_d;
-}
-void run_denoise_rows(zvx_ctx* c, const DnGeom& g, const PostRow* rows, int B, const float* bias, const zvx_denoise_params* p, int pcm16) {
-    const bool copy = p->strength == 0.f;
-    DnRowsPlan pl = dn_rows_plan(g, rows, B, copy);
-    DenoiseArgs a{};
-    if (!copy) {
-        float* bias_d = c->fbuf("dn.bias", g.nf);
-        c->upload(bias_d, bias, (size_t)g.nf * 4);
-        a.bias = bias_d; a.strength = p->strength; a.floor = p->floor;
-    }
-    dn_rows_upload(c, g, pl, B, copy, pcm16, a);
-    TagScope scope(c, "post.denoise");
-    c->timed(copy ? 0.0 : dn_fft_flops(g, pl.frames, 2), 4.0 * pl.n_sum + (pcm16 ? 2.0 : 4.0) * pl.cnt_sum, [&] {
-        if (!copy) launch_denoise_frames(a, c->stream);
-        launch_denoise_ola(a, pl.cnt_max, c->stream);
-    });
-}
-
-// zvx_denoise, zvx_denoise_ex and zvx_denoise_rows: every check before anything is allocated, uploaded or queued
-void do_denoise(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, const float* bias, const zvx_denoise_params* p,
-                void* out, int64_t out_stride, int flags, const WindowsIn& win = {}) {
-    rows_check(who, in, nsamples, B, Nmax, 65535);
-    flags_check(who, flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16);
-    out_rows_check(who, in, out, out_stride, Nmax, flags);
-    const DnGeom g = denoise_params_check(c, who, bias, p);
-    const RowsWindows rw = rows_windows_check(who, win, nsamples, B, g.n_fft - 1, in, out, out_stride);
-    for (int b = 0; b < B; b++) stft_len_check(who, g, b, nsamples[b], rw.at(b));
-    post_call(c, "dn", in, nsamples, B, Nmax, out, out_stride, true, flags, rw, 0, false, [&](const PostRow* rows) {
-        run_denoise_rows(c, g, rows, B, bias, p, (flags & ZVX_PCM16) ? 1 : 0);
-        return nullptr;
-    });
-}
-
-// ------------------------------------------------------------------------------------------------
-// keyed audio watermark (include/zvx.h: zvx_watermark, zvx_watermark_ex, zvx_watermark_detect; kernels: watermark.hip)
-// ------------------------------------------------------------------------------------------------
-uint64_t wm_mix64(uint64_t z) {                              // the splitmix64 finaliser
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-// the checks of the watermark's own parameters (embedder and detector) -> the model's STFT geometry and the bands
-WmPlan watermark_params_check(const zvx_ctx* c, const char* who, const zvx_watermark_params* p) {
-    if (!p) fail(ZVX_E_INVALID, "%s: params is NULL", who);
-    if (!std::isfinite(p->depth_db) || p->depth_db < 0.f || p->depth_db > 6.f) fail(ZVX_E_INVALID, "%s: depth_db must be finite and lie in [0, 6]", who);
-    if (!std::isfinite(p->lo_hz) || !std::isfinite(p->hi_hz) || p->lo_hz < 0.f || !(p->lo_hz < p->hi_hz))
-        fail(ZVX_E_INVALID, "%s: band %g .. %g Hz needs finite 0 <= lo_hz < hi_hz", who, (double)p->lo_hz, (double)p->hi_hz);
-    if (p->block_frames < 1) fail(ZVX_E_INVALID, "%s: block_frames %d must be at least 1", who, p->block_frames);
-    if (p->band_bins < 1) fail(ZVX_E_INVALID, "%s: band_bins %d must be at least 1", who, p->band_bins);
-    if (p->period_blocks < 1 || p->period_blocks > WM_MAX_PERIOD) fail(ZVX_E_INVALID, "%s: period_blocks %d outside [1, %d]", who, p->period_blocks, WM_MAX_PERIOD);
-    if (p->reserved != 0) fail(ZVX_E_INVALID, "%s: reserved is %d (must be 0)", who, p->reserved);
-    const DnGeom g = dn_geom(c, who);
-    const double rate = (double)model_rate(c), N = (double)g.n_fft;
-    const double k_lo = ceil((double)p->lo_hz * N / rate), top = std::min((double)p->hi_hz * N / rate, N / 2.0);
-    const double J = floor((top - k_lo) / (double)p->band_bins);
-    if (!(J >= 3.0)) fail(ZVX_E_INVALID, "%s: %g .. %g Hz in bands of %d bins gives %.0f bands (at least 3)", who, (double)p->lo_hz, (double)p->hi_hz, p->band_bins, std::max(J, 0.0));
-    if (J > (double)WM_MAX_BANDS) fail(ZVX_E_UNSUPPORTED, "%s: %.0f bands (at most %d)", who, J, WM_MAX_BANDS);
-    return {g, (int)k_lo, (int)J};
-}
-// the P x J pattern of +1 / -1 bytes on the device, through the pinned staging arena
-const signed char* wm_sign_table(zvx_ctx* c, const zvx_watermark_params* p, int J) {
-    const int P = p->period_blocks;
-    std::vector<signed char> sg((size_t)P * J);
-    for (int ci = 0; ci < P; ci++)
-        for (int j = 0; j < J; j++)
-            sg[(size_t)ci * J + j] = (wm_mix64(p->key ^ (((uint64_t)ci << 32) | (uint64_t)j)) >> 63) ? 1 : -1;
-    signed char* d = (signed char*)c->buf("wm.sign", sg.size());
-    c->upload(d, sg.data(), sg.size());
-    return d;
-}
-
-// The embedder over B rows with a window each: the denoiser's row table, its overlap-add launch, the keyed gain in the frames launch.
-// The caller has validated the rows.
-// `keys` (zvx_watermark_rows): a key per row -- the distinct keys' tables are built on the device (launch_wm_signs) into one stack, rows of
-// equal keys share a table; nullptr: p->key for every row, its table built on the host.
-void run_watermark_rows(zvx_ctx* c, const WmPlan& wp, const PostRow* rows, int B, const zvx_watermark_params* p, int pcm16,
-                        const uint64_t* keys = nullptr) {
-    const DnGeom& g = wp.g;
-    const bool copy = p->depth_db == 0.f;
-    DnRowsPlan pl = dn_rows_plan(g, rows, B, copy);
-    WatermarkArgs a{};
-    dn_rows_upload(c, g, pl, B, copy, pcm16, a.dn);
-    const unsigned long long* keys_d = nullptr;
-    signed char* signs_d = nullptr;
-    int n_tables = 0;
-    if (!copy) {
-        if (keys) {
-            std::vector<unsigned long long> uniq;
-            std::vector<int> of_row((size_t)B);
-            std::map<uint64_t, int> seen;
-            for (int b = 0; b < B; b++) {
-                const auto it = seen.emplace(keys[b], (int)uniq.size());
-                if (it.second) uniq.push_back(keys[b]);
-                of_row[(size_t)b] = it.first->second;
-            }
-            n_tables = (int)uniq.size();
-            unsigned long long* kd = (unsigned long long*)c->buf("wm.keys", uniq.size() * 8);
-            int* od = (int*)c->buf("wm.sign_of_row", (size_t)B * sizeof(int));
-            signs_d = (signed char*)c->buf("wm.signs", uniq.size() * (size_t)p->period_blocks * wp.J);
-            c->upload(kd, uniq.data(), uniq.size() * 8);
-            c->upload(od, of_row.data(), (size_t)B * sizeof(int));
-            keys_d = kd; a.sign = signs_d; a.sign_of_row = od;
-        } else a.sign = wm_sign_table(c, p, wp.J);
-        a.k_lo = wp.k_lo; a.KB = p->band_bins; a.J = wp.J; a.TB = p->block_frames; a.P = p->period_blocks;
-        a.g_up = (float)pow(10.0, (double)p->depth_db / 20.0); a.g_dn = (float)pow(10.0, -(double)p->depth_db / 20.0);
-    }
-    TagScope scope(c, "post.watermark");
-    c->timed(copy ? 0.0 : dn_fft_flops(g, pl.frames, 2), 4.0 * pl.n_sum + (pcm16 ? 2.0 : 4.0) * pl.cnt_sum, [&] {
-        if (keys_d) launch_wm_signs(keys_d, signs_d, n_tables, a.P, a.J, false, c->stream);
-        if (!copy) launch_watermark_frames(a, c->stream);
-        launch_denoise_ola(a.dn, pl.cnt_max, c->stream);
-    });
-}
-
-// zvx_watermark, zvx_watermark_ex and zvx_watermark_rows (`keys`: a key per row, or nullptr): every check before anything is allocated, uploaded or queued
-void do_watermark(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, const zvx_watermark_params* p,
-                  void* out, int64_t out_stride, int flags, const WindowsIn& win = {}, const uint64_t* keys = nullptr) {
-    rows_check(who, in, nsamples, B, Nmax, 65535);
-    flags_check(who, flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16);
-    out_rows_check(who, in, out, out_stride, Nmax, flags);
-    const WmPlan wp = watermark_params_check(c, who, p);
-    const DnGeom& g = wp.g;
-    const RowsWindows rw = rows_windows_check(who, win, nsamples, B, g.n_fft - 1, in, out, out_stride);
-    for (int b = 0; b < B; b++) stft_len_check(who, wp.g, b, nsamples[b], rw.at(b));
-    post_call(c, "wm", in, nsamples, B, Nmax, out, out_stride, true, flags, rw, 0, false, [&](const PostRow* rows) {
-        run_watermark_rows(c, wp, rows, B, p, (flags & ZVX_PCM16) ? 1 : 0, keys);
-        return nullptr;
-    });
 }
 
 // The analysis zvx_watermark_detect and zvx_watermark_identify share: every row's frames into band differences d [F][J - 2], searched in
@@ -3697,80 +2277,6 @@ void do_align_wav(zvx_ctx* c, const float* wav_a, const int32_t* n_a, int Nmax_a
     }
 }
 
-// zvx_resample_rows: every check before anything is allocated, uploaded or queued
-void do_resample_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate_in, int rate_out, void* out, int64_t out_stride,
-                      int32_t* out_len, int flags, const zvx_row_window* win) {
-    const char* who = "zvx_resample_rows";
-    rows_args(who, in, nsamples, B, Nmax);
-    if (!out) fail(ZVX_E_INVALID, "%s: out is NULL", who);
-    flags_check(who, flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16);
-    if (!win) fail(ZVX_E_INVALID, "%s: win is NULL", who);
-    for (int b = 0; b < B; b++) {
-        const zvx_row_window& w = win[b];
-        if (w.reserved != 0) fail(ZVX_E_INVALID, "%s: row %d: reserved is %d (must be 0)", who, b, w.reserved);
-        if (w.last != 0 && w.last != 1) fail(ZVX_E_INVALID, "%s: row %d: last is %d (0 or 1)", who, b, w.last);
-        if (w.in_origin < 0 || w.out_begin < 0 || w.out_count < -1 || w.in_origin > ((int64_t)1 << 40) || w.out_begin > ((int64_t)1 << 40) || w.out_count > INT32_MAX)
-            fail(ZVX_E_INVALID, "%s: row %d: window out of range (in_origin %lld, out_begin %lld, out_count %lld)", who, b, (long long)w.in_origin,
-                 (long long)w.out_begin, (long long)w.out_count);
-    }
-    int L = 1, M = 1;
-    rs_pair(rate_in, rate_out, &L, &M);                     // (its ZVX_E_UNSUPPORTED ranks before a bad length, as in zvx_resample)
-    rows_check(who, in, nsamples, B, Nmax);
-    RowsWindows rw;
-    rw.w.resize((size_t)B); rw.cnt.resize((size_t)B);
-    for (int b = 0; b < B; b++) {
-        const zvx_row_window& w = win[b];
-        const int64_t n = w.out_count >= 0 ? w.out_count : std::max<int64_t>(0, rs_out_len((long)(w.in_origin + nsamples[b]), L, M) - w.out_begin);
-        if (n > INT32_MAX) fail(ZVX_E_INVALID, "%s: row %d: %lld output samples", who, b, (long long)n);
-        rw.w[(size_t)b] = RowsWindow{w.in_origin, w.out_begin, w.out_count, w.last};
-        rw.cnt[(size_t)b] = (int32_t)n;
-        rw.cnt_max = std::max<long>(rw.cnt_max, (long)n);
-    }
-    if (out_stride < rw.cnt_max) fail(ZVX_E_BUFFER, "%s: out_stride %lld < %ld samples, the longest output row", who, (long long)out_stride, rw.cnt_max);
-    const zvx_ctx::RsBank& bk = rs_bank(c, L, M);
-    post_call(c, "rs", in, nsamples, B, Nmax, out, out_stride, true, flags, rw, 0, false, [&](const PostRow* rows) {
-        run_resample_rows(c, bk, rows, B, (flags & ZVX_PCM16) ? 1 : 0);
-        return nullptr;
-    });
-    if (out_len) for (int b = 0; b < B; b++) out_len[b] = rw.cnt[(size_t)b];
-}
-
-constexpr int DN_BIAS_FRAMES = 88;      // mel frames of silence the bias is measured on
-
-void do_denoise_bias(zvx_ctx* c, float* bias) {
-    const char* who = "zvx_denoise_bias";
-    if (!bias) fail(ZVX_E_INVALID, "%s: bias is NULL", who);
-    const DnGeom g = dn_geom(c, who);
-    const int P = DN_BIAS_FRAMES, nm = c->n_mels, n = P * c->hop;
-    if (n < dn_min_samples(g)) fail(ZVX_E_UNSUPPORTED, "%s: %d samples of silence are shorter than one frame (%d)", who, n, dn_min_samples(g));
-    const zvx_ctx::DnTables& tb = dn_tables(c, g);
-    float* zmel = c->fbuf("dn.zmel", (size_t)P * nm);
-    HIPCHK(hipMemsetAsync(zmel, 0, (size_t)P * nm * 4, c->stream));
-    float* wav = c->fbuf("dn.bwav", (size_t)n);
-    run_vocoder(c, zmel, nm, P, &P, &P, 1, wav, n, 0);       // what zvx_vocode_mel runs for one row of P zero frames at the native rate
-    const int F = dn_frames(g, n);
-    DenoiseArgs a{};
-    dn_fill(a, g, tb);
-    DenoiseRow row{};                                        // the whole row, magnitude-out mode: no output, no work buffer
-    row.x = wav; row.n = n; row.rel = -g.pad; row.cnt = n; row.mirrors = 3;
-    DenoiseRow* row_d = (DenoiseRow*)c->buf("dn.rows", sizeof(DenoiseRow));
-    c->upload(row_d, &row, sizeof(DenoiseRow));
-    a.rows = row_d; a.B = 1; a.Fmax = F;
-    a.mag = c->fbuf("dn.mag", (size_t)F * g.nf);
-    {
-        TagScope scope(c, "post.denoise");
-        c->timed(dn_fft_flops(g, F, 1), 4.0 * n + 4.0 * F * g.nf, [&] { launch_denoise_frames(a, c->stream); });
-    }
-    const float* host = (const float*)c->join_pinned((size_t)F * g.nf * 4);
-    HIPCHK(hipMemcpyAsync((void*)host, a.mag, (size_t)F * g.nf * 4, hipMemcpyDeviceToHost, c->stream));
-    c->sync();
-    for (int k = 0; k < g.nf; k++) {                         // the mean over all frames, in double, rounded once
-        double s = 0.0;
-        for (int f = 0; f < F; f++) s += (double)host[(size_t)f * g.nf + k];
-        bias[k] = (float)(s / (double)F);
-    }
-}
-
 // wav: float rows, or int16 PCM rows with ZVX_PCM16 (stride counted in samples either way).  Row b receives
 // mel_len[b]*hop samples followed by zeros up to max_b(mel_len[b])*hop; nothing beyond that is touched.
 void do_vocode(zvx_ctx* c, const int32_t* pad_to, void* wav, int64_t wav_stride, int flags) {
@@ -3849,475 +2355,10 @@ void do_vocode(zvx_ctx* c, const int32_t* pad_to, void* wav, int64_t wav_stride,
         HIPCHK(hipMemcpy2DAsync(wav, (size_t)wav_stride * ss, wdev, (size_t)wstride * ss, (size_t)need * ss, B, hipMemcpyDeviceToHost, c->stream));
     if (!(dev_out && (flags & ZVX_NO_SYNC))) c->sync();
 }
-
-// ------------------------------------------------------------------------------------------------
-// stream sessions (include/zvx.h: zvx_stream_open / zvx_stream_next / zvx_stream_info / zvx_stream_close)
-// ------------------------------------------------------------------------------------------------
-void stream_free(zvx_stream* s) {
-    zvx_ctx* c = s->c;
-    auto it = std::find(c->streams.begin(), c->streams.end(), s);
-    if (it != c->streams.end()) c->streams.erase(it);
-    if (s->dev || s->pinned) {                               // work queued on the context may still read or write the session's memory
-        (void)hipStreamSynchronize(c->stream);
-        for (hipStream_t s2 : {c->main0, c->voc_aux[0], c->voc_aux[1]}) if (s2 && s2 != c->stream) (void)hipStreamSynchronize(s2);
-    }
-    if (s->dev) (void)hipFree(s->dev);
-    if (s->pinned) (void)hipHostFree(s->pinned);
-    delete s;
-}
-
-// the native samples the rate conversion runs behind its input: output n is final once n M + half <= (received - 1) L
-int64_t rs_reach(const zvx_plan::RatePair& p) { return p.half ? zvx_plan::ceil_div(p.half, p.L) + 1 : 0; }
-
-// The step's one table on the device (stream_step): the rows' gather entries, their scatter entries, then the history drops (one per stage
-// at most, STREAM_MAX_DROPS per session).  The buffer is taken at its largest size at once: it never grows behind a queued call.
-constexpr int STREAM_MAX_DROPS = 5;                          // denoiser, leveler, watermark, limiter, rate conversion
-constexpr size_t STREAM_TAB_BYTES = (size_t)STREAM_MANY_MAX_ROWS * (sizeof(StreamRow) + sizeof(StreamInterior)) +
-                                    (size_t)STREAM_MANY_MAX_SESSIONS * STREAM_MAX_DROPS * sizeof(StreamInterior);
-
-// zvx_stream_open (more == nullptr) and zvx_stream_open_ex
-void do_stream_open(zvx_ctx* c, const char* who, const float* mel, int frames, const zvx_stream_params* p, const zvx_stream_stages* more, int flags,
-                    zvx_stream** out) {
-    // ---- every check, before anything is allocated
-    if (!p || !out) fail(ZVX_E_INVALID, "%s: %s is NULL", who, !p ? "params" : "out");
-    *out = nullptr;
-    if (flags & ~(ZVX_DEVICE_IN | ZVX_PCM16)) fail(ZVX_E_INVALID, "%s: unknown flag in %d", who, flags);
-    if (flags & ZVX_PCM16) fail(ZVX_E_UNSUPPORTED, "%s: a session hands out f32 pieces (no ZVX_PCM16)", who);
-    if (!mel) {
-        if (frames != 0) fail(ZVX_E_INVALID, "%s: mel is NULL (the context's mel) and frames is %d, not 0", who, frames);
-        if (!c->have_mel) fail(ZVX_E_STATE, "%s: no mel in the context (call zvx_decode first, or pass a mel)", who);
-        if (c->B != 1) fail(ZVX_E_UNSUPPORTED, "%s: the context holds a batch of %d utterances (a session streams one)", who, c->B);
-        frames = c->mel_len_host[0];
-    }
-    if (frames < 2) fail(ZVX_E_INVALID, "%s: %d mel frames (at least 2)", who, frames);
-    if (p->chunk_frames < 1) fail(ZVX_E_INVALID, "%s: chunk_frames %d (at least 1)", who, p->chunk_frames);
-    if (p->chunks_per_call < 1 || p->chunks_per_call > STREAM_MAX_ROWS)
-        fail(ZVX_E_INVALID, "%s: chunks_per_call %d outside 1 .. %d", who, p->chunks_per_call, STREAM_MAX_ROWS);
-    if (p->halo < 0) fail(ZVX_E_INVALID, "%s: halo %d is negative", who, p->halo);
-    if (!p->denoise != !p->denoise_bias) fail(ZVX_E_INVALID, "%s: denoise and denoise_bias go together (one of them is NULL)", who);
-    const int native = model_rate(c), hop = c->hop, nm = c->n_mels;
-    const int out_rate = c->out_rate && c->out_rate != native ? c->out_rate : native;
-    const int64_t total_native = (int64_t)frames * hop;
-    DnGeom g{};
-    if (p->denoise) {
-        g = denoise_params_check(c, who, p->denoise_bias, p->denoise);
-        if (total_native < dn_min_samples(g))
-            fail(ZVX_E_INVALID, "%s: %d frames are %lld samples; the denoiser needs at least %d (zvx_melspec's conditions)", who, frames,
-                 (long long)total_native, dn_min_samples(g));
-    }
-    const zvx_level_params* lvl = more ? more->level : nullptr;
-    const zvx_watermark_params* wm = more ? more->watermark : nullptr;
-    if (more && (more->reserved[0] != 0 || more->reserved[1] != 0))
-        fail(ZVX_E_INVALID, "%s: stages: reserved is %lld, %lld (must be 0)", who, (long long)more->reserved[0], (long long)more->reserved[1]);
-    LevelGeom lg{};
-    if (lvl) lg = level_params_check(who, native, lvl);
-    WmPlan wp{};
-    if (wm) {
-        wp = watermark_params_check(c, who, wm);
-        if (total_native < dn_min_samples(wp.g))
-            fail(ZVX_E_INVALID, "%s: %d frames are %lld samples; the watermark needs at least %d (zvx_melspec's conditions)", who, frames,
-                 (long long)total_native, dn_min_samples(wp.g));
-    }
-    int W = 0;
-    if (p->limit) { limit_os_check(who, p->limit->oversample); W = limit_params_check(who, native, p->limit); }
-    zvx_plan::RatePair rp;
-    if (out_rate != native) {
-        int L = 1, M = 1;
-        rs_pair(native, out_rate, &L, &M);
-        rp = zvx_plan::rate_pair(native, out_rate);
-    }
-    // ---- geometry: a group's rows, the stages' buffers, the longest piece
-    const int chunk = std::min(p->chunk_frames, frames), halo = std::min(p->halo, frames);
-    const int nchunks = (int)(((int64_t)frames + p->chunk_frames - 1) / p->chunk_frames);
-    const int rows = std::min(p->chunks_per_call, nchunks);
-    const int Pcap = (int)std::min<int64_t>(frames, (int64_t)chunk + 2 * (int64_t)halo);
-    const int64_t G = (int64_t)rows * chunk * hop;           // the most new samples one call brings
-    struct Want { int kind; int64_t R, keep; };              // R: the reach to the right; keep: the most history a stage retains between two calls
-    std::vector<Want> want;
-    if (p->denoise) want.push_back({zvx_stream::DENOISE, (int64_t)g.n_fft - 1, 2 * ((int64_t)g.n_fft - 1)});
-    if (lvl) want.push_back({zvx_stream::LEVEL, lg.RR, lg.RL + lg.RR});
-    if (wm) want.push_back({zvx_stream::WATERMARK, (int64_t)wp.g.n_fft - 1, 2 * ((int64_t)wp.g.n_fft - 1)});
-    if (p->limit) { const int64_t R = 2 * (int64_t)W + (p->limit->oversample > 1 ? LIMIT_ENV_REACH : 0); want.push_back({zvx_stream::LIMIT, R, 2 * R}); }
-    if (out_rate != native) want.push_back({zvx_stream::RESAMPLE, rs_reach(rp), 2 * rp.half / rp.L + 2});
-    int64_t delay = 0;
-    for (const Want& w : want) delay += w.R;
-    if (G + delay > (int64_t)1 << 28 || (int64_t)rows * Pcap * std::max(hop, nm) > (int64_t)1 << 28)
-        fail(ZVX_E_UNSUPPORTED, "%s: a group of %d chunks of %d frames is %lld samples (at most 2^28 per call)", who, rows, chunk, (long long)G);
-    const int64_t max_piece = zvx_plan::ceil_div((G + delay) * rp.L, rp.M) + 1;
-    const long wstride = ((long)Pcap * hop + 7) & ~7L;
-    // ---- the tables a stage needs on first use: no zvx_stream_next waits for an upload
-    if (p->denoise && p->denoise->strength != 0.f) dn_tables(c, g);
-    if (p->limit) { limit_win(c, W); if (p->limit->oversample > 1) rs_bank(c, p->limit->oversample, 1); }
-    if (out_rate != native) rs_bank(c, (int)rp.L, (int)rp.M);
-    {   // ... and what the leveler's and the watermark's bodies take on first use, at the session's largest step: a stage holds at most
-        // keep + (the group + the reaches in front of it) samples and emits no more than it holds
-        int64_t in_max = G;
-        for (const Want& w : want) {
-            const int64_t held = w.keep + in_max;
-            if (w.kind == zvx_stream::LEVEL) {
-                loud_coef(c, native);
-                c->buf("lvl.p", (size_t)(held / lg.h + lg.S + 4) * sizeof(double));
-                c->fbuf("lvl.part", (size_t)2 * (size_t)((held + 3 + LEVEL_TILE - 1) / LEVEL_TILE));
-                c->fbuf("lvl.res", 2); c->buf("lvl.rows", sizeof(LevelRow));
-            }
-            if (w.kind == zvx_stream::WATERMARK) {
-                c->buf("dn.rows", sizeof(DenoiseRow));
-                if (wm->depth_db != 0.f) {
-                    dn_tables(c, wp.g);
-                    const int64_t F = (held + wp.g.n_fft) / wp.g.hop + (DENOISE_POINTS >> wp.g.log2n) + 2;
-                    c->fbuf("dn.work", (size_t)F * wp.g.n_fft);
-                    c->buf("wm.keys", 8); c->buf("wm.sign_of_row", sizeof(int)); c->buf("wm.signs", (size_t)wm->period_blocks * wp.J);
-                }
-            }
-            in_max += w.R;
-        }
-    }
-    c->buf("stream.tab", STREAM_TAB_BYTES); c->fbuf("stream.rows", (size_t)rows * Pcap * nm); c->fbuf("stream.wav", (size_t)rows * wstride);   // what a step of the largest group takes
-    // ---- the session and its memory
-    zvx_stream* s = new zvx_stream();
-    s->c = c;
-    try {
-        s->frames = frames; s->chunk = p->chunk_frames; s->cpc = p->chunks_per_call; s->halo = p->halo; s->hop = hop; s->native = native; s->out_rate = out_rate;
-        s->nchunks = nchunks; s->Pcap = Pcap; s->delay = delay; s->max_piece = max_piece;
-        s->total = zvx_plan::ceil_div(total_native * rp.L, rp.M);
-        if (p->denoise) { s->dn = *p->denoise; s->bias.assign(p->denoise_bias, p->denoise_bias + g.nf); }
-        if (p->limit) { s->lim = *p->limit; s->lim_W = W; }
-        if (lvl) { s->lvl = *lvl; s->lvl_g = lg; }
-        if (wm) { s->wm = *wm; s->wm_plan = wp; }
-        auto pad = [](int64_t floats) { return (size_t)((floats * 4 + 255) & ~(int64_t)255); };
-        size_t bytes = pad((int64_t)frames * nm) + pad(max_piece);
-        int64_t in_max = G;
-        for (const Want& w : want) {
-            zvx_stream::Stage st;
-            st.kind = w.kind;
-            if (w.kind == zvx_stream::RESAMPLE) st.rate = zvx_plan::ResamplePlanner(native, out_rate);
-            else if (w.kind == zvx_stream::LEVEL) st.level = zvx_plan::LevelPlanner(lg.RL, lg.RR);
-            else st.reach = zvx_plan::ReachPlanner(w.R);
-            st.cap = w.keep + in_max + 8;
-            in_max += w.R;
-            bytes += 2 * pad(st.cap);
-            s->stages.push_back(st);
-        }
-        HIPCHK(hipMalloc((void**)&s->dev, bytes));
-        HIPCHK(hipHostMalloc((void**)&s->pinned, (size_t)max_piece * 4, hipHostMallocDefault));
-        HIPCHK(hipMemsetAsync(s->dev, 0, bytes, c->stream));
-        char* q = s->dev;
-        auto take = [&](int64_t floats) { float* r = (float*)q; q += pad(floats); return r; };
-        s->mel = take((int64_t)frames * nm); s->ostage = take(max_piece);
-        for (auto& st : s->stages) { st.buf[0] = take(st.cap); st.buf[1] = take(st.cap); }
-        const size_t mbytes = (size_t)frames * nm * 4;
-        if (!mel) HIPCHK(hipMemcpyAsync(s->mel, c->fbuf("mel", 0), mbytes, hipMemcpyDeviceToDevice, c->stream));       // utterance 0: the first rows
-        else if (flags & ZVX_DEVICE_IN) HIPCHK(hipMemcpyAsync(s->mel, mel, mbytes, hipMemcpyDeviceToDevice, c->stream));
-        else {
-            HIPCHK(hipMemcpyAsync(s->mel, mel, mbytes, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(hipStreamSynchronize(c->stream));         // the caller's mel may be reused when the call returns
-        }
-    } catch (...) {
-        stream_free(s);
-        throw;
-    }
-    c->streams.push_back(s);
-    *out = s;
-}
-
-// the checks every stepping call makes on its flags (zvx_stream_next, zvx_stream_next_many)
-void stream_flags_check(const char* who, int flags) {
-    if (flags & ~(ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16)) fail(ZVX_E_INVALID, "%s: unknown flag in %d", who, flags);
-    if (flags & ZVX_PCM16) fail(ZVX_E_UNSUPPORTED, "%s: a session hands out f32 pieces (no ZVX_PCM16)", who);
-    if ((flags & ZVX_NO_SYNC) && !(flags & ZVX_DEVICE_OUT)) fail(ZVX_E_INVALID, "%s: ZVX_NO_SYNC needs ZVX_DEVICE_OUT", who);
-}
-
-// What a session's next step does, worked out before anything is queued: the group's rows (stream_plan.h) and the stages' windows on
-// COPIES of the planners -- host integer arithmetic, so the piece's size n is known up front and a refused call has consumed nothing.
-struct StreamStep {
-    zvx_plan::Group g{};
-    zvx_plan::Row rows[STREAM_MAX_ROWS];
-    int P[STREAM_MAX_ROWS];
-    std::vector<zvx_stream::Stage> plan;
-    std::vector<zvx_plan::Step> steps;
-    int64_t n = 0;                         // the piece's samples at the session's output rate
-};
-void stream_plan_step(const char* who, const zvx_stream* s, StreamStep& p) {
-    // ---- the group: chunk st is vocoded on frames [max(0, st - halo), min(frames, st + chunk + halo)), its interior kept
-    p.g = zvx_plan::group_rows(s->frames, s->chunk, s->halo, s->hop, s->next_chunk, s->cpc, p.rows);
-    for (int i = 0; i < p.g.rows; i++) p.P[i] = (int)p.rows[i].P;
-    if (p.g.Pmax > s->Pcap) fail(ZVX_E_STATE, "%s: a row of %d frames exceeds the session's %d", who, (int)p.g.Pmax, s->Pcap);
-    // ---- the plan, on copies of the planners
-    const size_t K = s->stages.size();
-    p.plan = s->stages;
-    p.steps.resize(K);
-    int64_t n = p.g.n_new;
-    for (size_t k = 0; k < K; k++) {
-        p.steps[k] = p.plan[k].push(n, p.g.last != 0);
-        const int64_t held = p.plan[k].hist + n;
-        if (held != p.plan[k].received() - p.steps[k].in_origin || held > p.plan[k].cap)
-            fail(ZVX_E_STATE, "%s: stage %zu holds %lld samples (buffer %lld, window from %lld)", who, k, (long long)held, (long long)p.plan[k].cap, (long long)p.steps[k].in_origin);
-        // the plan's self-check: a denoiser's, leveler's, watermark's or limiter's window must be one the rows calls accept (their support
-        // condition, on the host).  The leveler's is its own: RL to the left, RR to the right, and the clamped left rule of a last window.
-        // That rule never bites here although a session flags its last group `last` WITH new samples (the Python stream closes with an
-        // empty push): the last push's out_begin is what the push before left, max(0, prev_received - RR), RR = (a + 1) h - 1, so
-        // out_begin / h + a - 1 <= (prev_received + 1) / h - 2 <= prev_received / h - 1 <= U - 1 -- the first node is not clamped, and
-        // where it is not, RL (in_origin = out_begin - RL whenever in_origin > 0) implies the oldest unit's support.
-        if (p.plan[k].kind != zvx_stream::RESAMPLE && p.steps[k].out_count > 0) {
-            const RowsWindow w{p.steps[k].in_origin, p.steps[k].out_begin, p.steps[k].out_count, p.g.last ? 1 : 0};
-            const bool level = p.plan[k].kind == zvx_stream::LEVEL;
-            int64_t cnt = -1;
-            try {
-                if (level) {
-                    cnt = window_count_row(who, w, (int32_t)held, 0, s->lvl_g.RL, s->lvl_g.RR);
-                    RowsWindows rw;
-                    rw.w.assign(1, w); rw.cnt.assign(1, (int32_t)cnt); rw.cnt_max = (long)cnt;
-                    const int32_t held32 = (int32_t)held;
-                    level_clamped_support_check(who, rw, &held32, 1, s->lvl_g);
-                } else cnt = window_count_row(who, w, (int32_t)held, 0, p.plan[k].reach.R);
-            }
-            catch (const ZvxError& e) { fail(ZVX_E_STATE, "%s (stage %zu of the session's plan)", e.what(), k); }
-            if (cnt != w.out_count) fail(ZVX_E_STATE, "%s: stage %zu emits %lld samples, its plan says %lld", who, k, (long long)cnt, (long long)w.out_count);
-        }
-        n = p.steps[k].out_count;
-    }
-    p.n = n;
-    if (n > s->max_piece) fail(ZVX_E_STATE, "%s: a piece of %lld samples exceeds max_piece %lld", who, (long long)n, (long long)s->max_piece);
-}
-
-// One step of n sessions of ONE context, the only stepping path (zvx_stream_next is its n = 1): the callers have made their own checks
-// and planned every session (stream_plan_step), so from here on the call consumes the groups and a failure ends every session of it.
-// The rows of all sessions are gathered by one launch, vocoded as ONE batch by one run_vocoder and scattered by one launch to where each
-// session's first stage reads them.  The stages then run kind by kind -- all denoisers, then the levelers, the watermarks, the limiters, the
-// rate conversions; a session's chain order is kept and everything is on the one stream.  Within a kind the sessions whose stage has
-// bitwise-equal parameters (the bias by content; the leveler by its four parameters; the watermark by everything but the key, the members'
-// keys go to the one call as keys[]; the limiter by W, oversampling and ceiling; the rate conversion by its two rates, i.e. the polyphase bank) form
-// one group (stream_plan.h, partition_classes), and a group is ONE call of the per-row form: its rows are the sessions' [history | new]
-// buffers with each session's own window, each output goes straight behind the next stage's history or to the piece's destination.
-// All history drops of the call are ONE launch over a table.  Every session's stages are walked once, before anything is queued: the
-// walk yields the stages' rows, the drops and -- in the plan's copies of the stages -- the state the session takes on at the end.
-void stream_step(const char* who, zvx_ctx* c, zvx_stream* const* ss, StreamStep* plans, int n, void* const* out, const int64_t* n_out,
-                 int32_t* done, int flags) {
-    try {
-        c->have_features = false; c->have_mel = false;      // as zvx_vocode_mel: the context's intermediates are void
-        const int nm = c->n_mels, hop = c->hop;
-        int R = 0, Pmax = 0; long cnt_max = 0, move_max = 0; double rows_bytes = 0, new_bytes = 0, move_bytes = 0;
-        for (int i = 0; i < n; i++) {
-            const StreamStep& p = plans[i];
-            R += p.g.rows; Pmax = std::max(Pmax, (int)p.g.Pmax); cnt_max = std::max(cnt_max, (long)p.g.cnt_max);
-            for (int j = 0; j < p.g.rows; j++) rows_bytes += (double)p.P[j] * nm * 4.0;
-            rows_bytes += (double)p.g.rows * (double)p.g.Pmax * nm * 4.0;
-            new_bytes += 8.0 * (double)p.g.n_new;
-        }
-        const long wstride = ((long)Pmax * hop + 7) & ~7L;
-        // ---- the table, and every stage's input, window and destination, from the sessions' state as it stands
-        std::vector<char> tab((size_t)R * (sizeof(StreamRow) + sizeof(StreamInterior)) + (size_t)n * STREAM_MAX_DROPS * sizeof(StreamInterior));
-        StreamRow* tr = (StreamRow*)tab.data();
-        StreamInterior* ti = (StreamInterior*)(tr + R);
-        StreamInterior* moves = ti + R;
-        int M = 0, r = 0;
-        std::vector<int> P((size_t)R);
-        struct Slot { bool run = false; PostRow row{}; };
-        std::vector<Slot> slot[zvx_stream::KINDS];
-        for (auto& v : slot) v.resize((size_t)n);
-        for (int i = 0; i < n; i++) {
-            const zvx_stream* s = ss[i];
-            StreamStep& p = plans[i];
-            const size_t K = s->stages.size();
-            const bool last = p.g.last != 0;
-            // where stage k's new input goes: straight behind the history of its buffer; behind the last stage, the piece's destination
-            auto dst_of = [&](size_t k) { return k < K ? s->stages[k].buf[s->stages[k].cur] + s->stages[k].hist : (flags & ZVX_DEVICE_OUT) ? (float*)out[i] : s->ostage; };
-            float* base = dst_of(0);
-            for (int j = 0; j < p.g.rows; j++, r++) {
-                P[(size_t)r] = p.P[j];
-                tr[r] = StreamRow{s->mel + p.rows[j].lo * nm, p.P[j], 0};
-                ti[r] = StreamInterior{base + p.rows[j].pos, nullptr, (int)p.rows[j].off, (int)p.rows[j].cnt};
-            }
-            int64_t n_in = p.g.n_new;
-            for (size_t k = 0; k < K; k++) {
-                const zvx_stream::Stage& st = s->stages[k];
-                zvx_stream::Stage& next = p.plan[k];         // (the planners in it have taken the step already)
-                const zvx_plan::Step& sp = p.steps[k];
-                const int64_t held = st.hist + n_in;
-                float* in = st.buf[st.cur];
-                if (sp.out_count > 0 && held > 0)
-                    slot[st.kind][(size_t)i] = Slot{true, PostRow{in, dst_of(k + 1), (int32_t)held, RowsWindow{sp.in_origin, sp.out_begin, sp.out_count, last ? 1 : 0}, (int32_t)sp.out_count}};
-                const int64_t drop = sp.keep_from - sp.in_origin, keep = held - drop;
-                if (drop > 0) {                              // into the other buffer: never an overlapping copy
-                    if (keep > 0) {
-                        moves[M++] = StreamInterior{st.buf[st.cur ^ 1], in + drop, 0, (int)keep};
-                        move_bytes += 8.0 * (double)keep; move_max = std::max<long>(move_max, (long)keep);
-                    }
-                    next.cur = st.cur ^ 1;
-                }
-                next.hist = keep;
-                n_in = sp.out_count;
-            }
-        }
-        char* tab_d = (char*)c->buf("stream.tab", STREAM_TAB_BYTES);
-        float* rows_d = c->fbuf("stream.rows", (size_t)R * Pmax * nm);
-        float* wav_d = c->fbuf("stream.wav", (size_t)R * wstride);
-        c->upload(tab_d, tab.data(), (size_t)((char*)(moves + M) - tab.data()));
-        const StreamRowTab ra{(const StreamRow*)tab_d, rows_d, R, Pmax, nm};
-        const StreamInteriorTab ia{(const StreamInterior*)(ra.tab + R), wav_d, wstride, R};
-        const StreamInteriorTab ma{ia.tab + R, nullptr, 0, M};               // (the scatter's kernel: every entry has its own source)
-        // ---- gather, ONE batch of the vocoder at the native rate (the rows of ZeroVox._vocode_stream_native), scatter
-        {
-            TagScope scope(c, "voc.stream");
-            c->timed(0.0, rows_bytes, [&] { launch_stream_rows(ra, c->stream); });
-        }
-        c->stage_begin(ZVX_T_VOCODER);
-        run_vocoder(c, rows_d, nm, Pmax, P.data(), P.data(), R, wav_d, wstride, 0);
-        c->stage_end(ZVX_T_VOCODER);
-        {
-            TagScope scope(c, "voc.stream");
-            c->timed(0.0, new_bytes, [&] { launch_stream_interiors(ia, cnt_max, c->stream); });
-        }
-        // ---- the stages of one kind: a class is named by its first member, and is one call of the per-row form
-        std::vector<int> cls((size_t)n), order((size_t)n), start((size_t)n + 1);
-        std::vector<PostRow> rows;
-        std::vector<uint64_t> keys;                          // (WATERMARK: the members' keys, in call order)
-        auto per_class = [&](int kind, auto same, auto run) {
-            for (int i = 0; i < n; i++) {
-                cls[(size_t)i] = -1;
-                if (!slot[kind][(size_t)i].run) continue;
-                cls[(size_t)i] = i;
-                for (int j = 0; j < i; j++)
-                    if (cls[(size_t)j] == j && same(ss[j], ss[i])) { cls[(size_t)i] = j; break; }
-            }
-            const int groups = zvx_plan::partition_classes(cls.data(), n, order.data(), start.data());
-            for (int gi = 0; gi < groups; gi++) {
-                rows.clear(); keys.clear();
-                for (int m = start[(size_t)gi]; m < start[(size_t)gi + 1]; m++) {
-                    rows.push_back(slot[kind][(size_t)order[(size_t)m]].row);
-                    keys.push_back(ss[order[(size_t)m]]->wm.key);
-                }
-                run(ss[order[(size_t)start[(size_t)gi]]]);
-            }
-        };
-        per_class(zvx_stream::DENOISE, [](const zvx_stream* a, const zvx_stream* b) {
-            return !memcmp(&a->dn, &b->dn, sizeof a->dn) && a->bias.size() == b->bias.size() && !memcmp(a->bias.data(), b->bias.data(), a->bias.size() * 4);
-        }, [&](const zvx_stream* first) { run_denoise_rows(c, dn_geom(c, who), rows.data(), (int)rows.size(), first->bias.data(), &first->dn, 0); });
-        per_class(zvx_stream::LEVEL, [](const zvx_stream* a, const zvx_stream* b) {
-            return a->native == b->native && !memcmp(&a->lvl, &b->lvl, sizeof a->lvl);
-        }, [&](const zvx_stream* first) { run_level_rows(c, rows.data(), (int)rows.size(), first->native, &first->lvl, first->lvl_g, 0); });   // (the gain words are not read)
-        per_class(zvx_stream::WATERMARK, [](const zvx_stream* a, const zvx_stream* b) {
-            // every field but the key, bit for bit (the key is the member's own: one call marks every key of the class)
-            const float fa[3] = {a->wm.depth_db, a->wm.lo_hz, a->wm.hi_hz}, fb[3] = {b->wm.depth_db, b->wm.lo_hz, b->wm.hi_hz};
-            return !memcmp(fa, fb, sizeof fa) && a->wm.block_frames == b->wm.block_frames && a->wm.band_bins == b->wm.band_bins &&
-                   a->wm.period_blocks == b->wm.period_blocks && a->wm.reserved == b->wm.reserved;
-        }, [&](const zvx_stream* first) { run_watermark_rows(c, first->wm_plan, rows.data(), (int)rows.size(), &first->wm, 0, keys.data()); });
-        per_class(zvx_stream::LIMIT, [](const zvx_stream* a, const zvx_stream* b) {
-            return a->lim_W == b->lim_W && a->lim.oversample == b->lim.oversample && !memcmp(&a->lim.ceiling, &b->lim.ceiling, sizeof(float));
-        }, [&](const zvx_stream* first) { run_limit_rows(c, who, rows.data(), (int)rows.size(), &first->lim, first->lim_W, 0); });
-        per_class(zvx_stream::RESAMPLE, [](const zvx_stream* a, const zvx_stream* b) { return a->native == b->native && a->out_rate == b->out_rate; },
-                  [&](const zvx_stream* first) {
-            int L = 1, Mr = 1;
-            rs_pair(first->native, first->out_rate, &L, &Mr);
-            run_resample_rows(c, rs_bank(c, L, Mr), rows.data(), (int)rows.size(), 0);
-        });
-        // ---- every history drop of the call in one launch
-        if (M > 0) {
-            TagScope scope(c, "post.stream");
-            c->timed(0.0, move_bytes, [&] { launch_stream_interiors(ma, move_max, c->stream); });
-        }
-        // ---- everything is queued: the sessions' state
-        for (int i = 0; i < n; i++) {
-            zvx_stream* s = ss[i];
-            StreamStep& p = plans[i];
-            s->stages.swap(p.plan);
-            s->next_chunk = p.g.first + p.g.rows; s->emitted += p.n; s->done = p.g.last ? 1 : 0;
-            done[i] = s->done;
-        }
-        if (!(flags & ZVX_DEVICE_OUT)) {
-            for (int i = 0; i < n; i++)
-                if (n_out[i] > 0) HIPCHK(hipMemcpyAsync(ss[i]->pinned, ss[i]->ostage, (size_t)n_out[i] * 4, hipMemcpyDeviceToHost, c->stream));
-            c->sync();                                       // the call's one wait
-            for (int i = 0; i < n; i++)
-                if (n_out[i] > 0) memcpy(out[i], ss[i]->pinned, (size_t)n_out[i] * 4);
-        } else if (!(flags & ZVX_NO_SYNC)) c->sync();
-    } catch (...) {
-        for (int i = 0; i < n; i++) ss[i]->done = 1;
-        throw;
-    }
-}
-
-// zvx_stream_next (include/zvx.h): its own checks, then the step of one session
-void do_stream_next(zvx_stream* s, void* out, int64_t capacity, int64_t* n_out, int32_t* done, int flags) {
-    const char* who = "zvx_stream_next";
-    if (!n_out || !done) fail(ZVX_E_INVALID, "%s: %s is NULL", who, !n_out ? "n_out" : "done");
-    stream_flags_check(who, flags);
-    if (capacity < 0) fail(ZVX_E_INVALID, "%s: capacity %lld is negative", who, (long long)capacity);
-    if (s->done) fail(ZVX_E_STATE, "%s: the stream is done (its last piece has been handed out)", who);
-    StreamStep p;
-    stream_plan_step(who, s, p);
-    const int64_t n = p.n;
-    *n_out = n;
-    if (n > 0 && !out) fail(ZVX_E_INVALID, "%s: out is NULL", who);
-    if (capacity < n) fail(ZVX_E_BUFFER, "%s: capacity %lld < %lld samples of this piece (nothing was consumed)", who, (long long)capacity, (long long)n);
-    stream_step(who, s->c, &s, &p, 1, &out, n_out, done, flags);
-}
-
-// zvx_stream_next_many (include/zvx.h): its own checks and every session's plan, then the step of all of them
-void do_stream_next_many(zvx_ctx* c, zvx_stream* const* ss, int n, void* const* out, const int64_t* capacity, int64_t* n_out, int32_t* done,
-                         int flags) {
-    const char* who = "zvx_stream_next_many";
-    // ---- every check, before anything is planned or queued
-    if (!capacity || !n_out || !done) fail(ZVX_E_INVALID, "%s: %s is NULL", who, !capacity ? "capacity" : !n_out ? "n_out" : "done");
-    stream_flags_check(who, flags);
-    if (n > STREAM_MANY_MAX_SESSIONS) fail(ZVX_E_UNSUPPORTED, "%s: %d sessions (at most %d per call)", who, n, STREAM_MANY_MAX_SESSIONS);
-    for (int i = 0; i < n; i++) {
-        if (!ss[i]) fail(ZVX_E_INVALID, "%s: sessions[%d] is NULL", who, i);
-        if (ss[i]->c != c) fail(ZVX_E_INVALID, "%s: sessions[%d] belongs to another context than sessions[0]", who, i);
-        for (int j = 0; j < i; j++) if (ss[j] == ss[i]) fail(ZVX_E_INVALID, "%s: sessions[%d] and sessions[%d] are the same session", who, j, i);
-        if (capacity[i] < 0) fail(ZVX_E_INVALID, "%s: capacity[%d] %lld is negative", who, i, (long long)capacity[i]);
-    }
-    for (int i = 0; i < n; i++)
-        if (ss[i]->done) fail(ZVX_E_STATE, "%s: sessions[%d] is done (its last piece has been handed out; nothing was consumed)", who, i);
-    // ---- the plans of all sessions: every piece's size is known before anything is queued
-    std::vector<StreamStep> plans((size_t)n);
-    int R = 0, Pmax = 0;
-    for (int i = 0; i < n; i++) R += std::min(ss[i]->cpc, ss[i]->nchunks - ss[i]->next_chunk);
-    if (R > STREAM_MANY_MAX_ROWS) fail(ZVX_E_UNSUPPORTED, "%s: the groups of %d sessions are %d rows (at most %d per call)", who, n, R, STREAM_MANY_MAX_ROWS);
-    for (int i = 0; i < n; i++) {
-        stream_plan_step(who, ss[i], plans[(size_t)i]);
-        n_out[i] = plans[(size_t)i].n;
-        Pmax = std::max(Pmax, (int)plans[(size_t)i].g.Pmax);
-    }
-    if ((int64_t)R * Pmax * std::max(c->hop, c->n_mels) > (int64_t)1 << 28)
-        fail(ZVX_E_UNSUPPORTED, "%s: %d rows of %d frames are %lld samples (at most 2^28 per call)", who, R, Pmax, (long long)R * Pmax * c->hop);
-    for (int i = 0; i < n; i++)
-        if (n_out[i] > 0 && (!out || !out[i])) fail(ZVX_E_INVALID, "%s: %s is NULL", who, !out ? "out" : ("out[" + std::to_string(i) + "]").c_str());
-    for (int i = 0; i < n; i++)
-        if (capacity[i] < n_out[i])
-            fail(ZVX_E_BUFFER, "%s: capacity[%d] %lld < %lld samples of this piece (nothing was consumed in any session)", who, i,
-                 (long long)capacity[i], (long long)n_out[i]);
-    stream_step(who, c, ss, plans.data(), n, out, n_out, done, flags);
-}
-
-void do_stream_info(const zvx_stream* s, int64_t* info, int n_info) {
-    if (!info || n_info < 1) fail(ZVX_E_INVALID, "zvx_stream_info: info is NULL or n_info %d < 1", n_info);
-    const int64_t v[5] = {s->total, s->emitted, s->out_rate, s->delay, s->max_piece};
-    for (int i = 0; i < n_info && i < 5; i++) info[i] = v[i];
-}
-
-template <typename F>
-zvx_status guarded(zvx_ctx* ctx, F&& f) {
-    if (!ctx) return ZVX_E_INVALID;
-    try {
-        HIPCHK(hipSetDevice(ctx->device));
-        const bool outer = ctx->api_depth++ == 0;               // (an entry point that calls another one keeps the outer call's arena)
-        struct End { zvx_ctx* c; ~End() { try { if (--c->api_depth == 0) c->arena_end(); } catch (...) {} } } end{ctx};
-        if (outer) ctx->arena_begin();
-        f();
-        return ZVX_OK;
-    } catch (const ZvxError& e) {
-        ctx->err = e.what();
-        ctx->quiesce_side_streams();
-        return e.code;
-    } catch (const std::exception& e) {
-        ctx->err = e.what();
-        ctx->quiesce_side_streams();
-        return ZVX_E_INVALID;
-    }
-}
-
 }  // namespace
+
+}  // namespace zvx::host
+
 
 // ================================================================================================
 // C-ABI
@@ -4884,170 +2925,6 @@ zvx_status zvx_wait_host(zvx_ctx* c, int slot, const void** rows, int64_t* strid
     });
 }
 
-// ---- RCCL, resolved at run time ----------------------------------------------------------------------------------
-extern "C++" {
-namespace {
-struct Rccl {
-    void* h = nullptr;
-    decltype(&ncclGetUniqueId) GetUniqueId = nullptr;
-    decltype(&ncclCommInitRank) CommInitRank = nullptr;
-    decltype(&ncclCommDestroy) CommDestroy = nullptr;
-    decltype(&ncclSend) Send = nullptr;
-    decltype(&ncclRecv) Recv = nullptr;
-    decltype(&ncclGroupStart) GroupStart = nullptr;
-    decltype(&ncclGroupEnd) GroupEnd = nullptr;
-    decltype(&ncclAllReduce) AllReduce = nullptr;
-    decltype(&ncclGetErrorString) GetErrorString = nullptr;
-    decltype(&ncclCommCount) CommCount = nullptr;            // optional (zvx_comm_info)
-    decltype(&ncclGetVersion) GetVersion = nullptr;
-};
-Rccl& rccl() {
-    static Rccl r;
-    if (r.h) return r;
-    for (const char* name : {"librccl.so.1", "librccl.so", "/opt/rocm/lib/librccl.so.1"}) { r.h = dlopen(name, RTLD_NOW | RTLD_GLOBAL); if (r.h) break; }
-    if (!r.h) fail(ZVX_E_HIP, "cannot load librccl.so (%s): multi-GPU needs RCCL", dlerror());
-#define ZVX_SYM(f) do { r.f = (decltype(r.f))dlsym(r.h, "nccl" #f); if (!r.f) fail(ZVX_E_HIP, "librccl.so lacks nccl" #f); } while (0)
-    ZVX_SYM(GetUniqueId); ZVX_SYM(CommInitRank); ZVX_SYM(CommDestroy); ZVX_SYM(Send); ZVX_SYM(Recv); ZVX_SYM(GroupStart); ZVX_SYM(GroupEnd);
-    ZVX_SYM(AllReduce); ZVX_SYM(GetErrorString);
-#undef ZVX_SYM
-    r.CommCount = (decltype(r.CommCount))dlsym(r.h, "ncclCommCount");
-    r.GetVersion = (decltype(r.GetVersion))dlsym(r.h, "ncclGetVersion");
-    return r;
-}
-#define NCCLCHK(x) do { ncclResult_t r_ = (x); if (r_ != ncclSuccess) fail(ZVX_E_HIP, "%s failed: %s (%s:%d)", #x, rccl().GetErrorString(r_), __FILE__, __LINE__); } while (0)
-}  // namespace
-}  // extern "C++"
-
-zvx_status zvx_comm_unique_id(void* id_out) {
-    static_assert(sizeof(ncclUniqueId) == ZVX_COMM_ID_BYTES, "ncclUniqueId size");
-    if (!id_out) return ZVX_E_INVALID;
-    try {
-        ncclUniqueId id;
-        NCCLCHK(rccl().GetUniqueId(&id));
-        memcpy(id_out, &id, sizeof id);
-        return ZVX_OK;
-    } catch (const ZvxError& e) { g_create_error = e.what(); return e.code; }
-}
-
-zvx_status zvx_comm_init(zvx_ctx* c, const void* id, int rank, int world) {
-    return guarded(c, [&] {
-        if (world < 1 || rank < 0 || rank >= world) fail(ZVX_E_INVALID, "zvx_comm_init: rank %d of %d", rank, world);
-        if (c->comm || c->comm_stream) fail(ZVX_E_STATE, "zvx_comm_init: communicator already initialised");
-        HIPCHK(hipStreamCreateWithFlags(&c->comm_stream, hipStreamNonBlocking));
-        HIPCHK(hipEventCreateWithFlags(&c->ev_compute, hipEventDisableTiming));
-        c->rank = rank; c->world = world;
-        if (world > 1 || id) {                              // world == 1 with an id: a real one-rank communicator (self-test of the RCCL path)
-            if (!id) fail(ZVX_E_INVALID, "zvx_comm_init: id is NULL");
-            ncclUniqueId uid;
-            memcpy(&uid, id, sizeof uid);
-            NCCLCHK(rccl().CommInitRank(&c->comm, world, uid, rank));
-        }
-    });
-}
-
-zvx_status zvx_comm_gather(zvx_ctx* c, const void* local, size_t bytes, void* recv, int root, int flags) {
-    return guarded(c, [&] {
-        if (!c->comm_stream) fail(ZVX_E_STATE, "zvx_comm_gather: call zvx_comm_init first");
-        if (!local || root < 0 || root >= c->world || (c->rank == root && !recv)) fail(ZVX_E_INVALID, "zvx_comm_gather: bad arguments");
-        // the communication stream picks up after everything issued so far on the compute stream
-        HIPCHK(hipEventRecord(c->ev_compute, c->stream));
-        HIPCHK(hipStreamWaitEvent(c->comm_stream, c->ev_compute, 0));
-        if (c->comm && c->world == 1) {                     // one-rank communicator: the root's row travels through RCCL too
-            Rccl& r = rccl();
-            NCCLCHK(r.GroupStart());
-            NCCLCHK(r.Send(local, bytes, ncclInt8, 0, c->comm, c->comm_stream));
-            NCCLCHK(r.Recv(recv, bytes, ncclInt8, 0, c->comm, c->comm_stream));
-            NCCLCHK(r.GroupEnd());
-        } else if (c->rank == root)
-            HIPCHK(hipMemcpyAsync((char*)recv + (size_t)root * bytes, local, bytes, hipMemcpyDeviceToDevice, c->comm_stream));
-        if (c->world > 1) {
-            Rccl& r = rccl();
-            NCCLCHK(r.GroupStart());
-            if (c->rank == root) {
-                for (int p = 0; p < c->world; p++)
-                    if (p != root) NCCLCHK(r.Recv((char*)recv + (size_t)p * bytes, bytes, ncclInt8, p, c->comm, c->comm_stream));
-            } else {
-                NCCLCHK(r.Send(local, bytes, ncclInt8, root, c->comm, c->comm_stream));
-            }
-            NCCLCHK(r.GroupEnd());
-        }
-        // later writers of `local` (the vocoder of a coming call) queue behind this event on the device
-        hipEvent_t& ev = c->gather_fence[local];
-        if (!ev) HIPCHK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        HIPCHK(hipEventRecord(ev, c->comm_stream));
-        if (!(flags & ZVX_NO_SYNC)) c->sync();
-    });
-}
-
-zvx_status zvx_comm_max_f64(zvx_ctx* c, double* value) {
-    return guarded(c, [&] {
-        if (!c->comm_stream || !value) fail(ZVX_E_STATE, "zvx_comm_max_f64: call zvx_comm_init first");
-        double* d = (double*)c->buf("comm.scalar", 64);      // (a first use zero-fills it on the compute stream: taken BEFORE the drain below,
-        c->sync();                                           //  the communication stream must not see that fill land on top of its copy)
-        if (!c->comm) return;
-        HIPCHK(hipMemcpyAsync(d, value, sizeof(double), hipMemcpyHostToDevice, c->comm_stream));
-        NCCLCHK(rccl().AllReduce(d, d, 1, ncclFloat64, ncclMax, c->comm, c->comm_stream));
-        HIPCHK(hipMemcpyAsync(value, d, sizeof(double), hipMemcpyDeviceToHost, c->comm_stream));
-        HIPCHK(hipStreamSynchronize(c->comm_stream));
-    });
-}
-
-// Who is in the job, as seen by the communicator itself (bench.py puts it into the N > 1 JSON line so that the first multi-GPU
-// run is self-diagnosing): out[0] = world of this context, out[1] = ncclCommCount, out[2] = ncclGetVersion code,
-// out[3] = number of ranks that contributed to an all-reduce SUM of ones (a live data-path check), out[4 + r] = PCI address of
-// rank r's device ((domain << 16) | (bus << 8) | (device << 3) | function), gathered with an all-reduce MAX over per-rank slots.
-// Collective: every rank calls it.  Without a communicator (world 1, no id) only this rank's entries are filled.
-zvx_status zvx_comm_info(zvx_ctx* c, int64_t* out, int n_out) {
-    return guarded(c, [&] {
-        if (!c->comm_stream || !out) fail(ZVX_E_STATE, "zvx_comm_info: call zvx_comm_init first");
-        const int W = c->world;
-        if (n_out < 4 + W) fail(ZVX_E_BUFFER, "zvx_comm_info: need %d entries", 4 + W);
-        double* const d = (double*)c->buf("comm.info", (size_t)(W + 1) * 8);      // (allocated -- and zero-filled on the compute stream -- before the drain)
-        c->sync();
-        for (int i = 0; i < n_out; i++) out[i] = -1;
-        out[0] = W;
-        char bus[64] = {0};
-        long pci = -1;
-        if (hipDeviceGetPCIBusId(bus, sizeof bus, c->device) == hipSuccess) {
-            unsigned dom = 0, b = 0, d = 0, f = 0;
-            if (sscanf(bus, "%x:%x:%x.%x", &dom, &b, &d, &f) >= 3) pci = ((long)dom << 16) | ((long)b << 8) | ((long)d << 3) | f;
-        }
-        std::vector<double> v((size_t)W + 1, 0.0);
-        v[0] = 1.0; v[1 + c->rank] = (double)(pci + 1);          // + 1: an address of 0 still reads as "present"
-        if (c->comm) {
-            Rccl& r = rccl();
-            int n = -1, ver = -1;
-            if (r.CommCount) NCCLCHK(r.CommCount(c->comm, &n));
-            if (r.GetVersion) NCCLCHK(r.GetVersion(&ver));
-            out[1] = n; out[2] = ver;
-            HIPCHK(hipMemcpyAsync(d, v.data(), (size_t)(W + 1) * 8, hipMemcpyHostToDevice, c->comm_stream));
-            NCCLCHK(r.AllReduce(d, d, 1, ncclFloat64, ncclSum, c->comm, c->comm_stream));
-            NCCLCHK(r.AllReduce(d + 1, d + 1, W, ncclFloat64, ncclMax, c->comm, c->comm_stream));
-            HIPCHK(hipMemcpyAsync(v.data(), d, (size_t)(W + 1) * 8, hipMemcpyDeviceToHost, c->comm_stream));
-            HIPCHK(hipStreamSynchronize(c->comm_stream));
-        }
-        out[3] = (int64_t)(v[0] + 0.5);
-        for (int r = 0; r < W; r++) out[4 + r] = (int64_t)v[1 + r] - 1;
-    });
-}
-
-zvx_status zvx_comm_barrier(zvx_ctx* c) {
-    double one = 1.0;
-    return zvx_comm_max_f64(c, &one);
-}
-
-void zvx_comm_destroy(zvx_ctx* c) {
-    if (!c) return;
-    (void)hipSetDevice(c->device);
-    if (c->comm_stream) (void)hipStreamSynchronize(c->comm_stream);
-    if (c->comm) { (void)rccl().CommDestroy(c->comm); c->comm = nullptr; }
-    for (auto& kv : c->gather_fence) if (kv.second) (void)hipEventDestroy(kv.second);
-    c->gather_fence.clear();
-    if (c->ev_compute) { (void)hipEventDestroy(c->ev_compute); c->ev_compute = nullptr; }
-    if (c->copy_is_comm) { c->copy_stream = nullptr; c->copy_is_comm = false; }      // (host deliveries rode this stream: the next one creates its own)
-    if (c->comm_stream) { (void)hipStreamDestroy(c->comm_stream); c->comm_stream = nullptr; }
-    c->world = 1; c->rank = 0;
-}
 
 zvx_status zvx_dev_alloc(zvx_ctx* c, size_t bytes, void** out) {
     return guarded(c, [&] {

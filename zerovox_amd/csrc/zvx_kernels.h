@@ -254,7 +254,7 @@ bool launch_attention_f32(const AttnF32Args& a, hipStream_t stream, bool dry_run
 struct LoudCoef { double b0, b1, b2, a1, a2, c1, c2; };
 // Leveler (include/zvx.h, zvx_level): a gain curve from the gated short-term loudness of the S units up to and including a unit, a units
 // ahead, interpolated linearly between unit nodes.  `rows` is a device table with one LevelRow per row, uploaded by every call through the
-// context's pinned staging arena (zvx.hip, run_level_rows); every kernel reads rows[blockIdx.y] at its top and works from it alone, so
+// context's pinned staging arena (host_post.hip, run_level_rows); every kernel reads rows[blockIdx.y] at its top and works from it alone, so
 // zvx_level, zvx_level_ex and zvx_level_rows run the same instructions.  A row holds samples [in_origin, in_origin + n) of its signal; the
 // unit grid is the SIGNAL's (unit q = samples [q h, (q + 1) h)).  Positions on the signal are 64-bit throughout; what indexes memory is
 // the position minus in_origin (samples) or minus q_first (units).  Nothing outside [0, n) of a row is read.
@@ -480,13 +480,13 @@ void launch_conv_post_tanh(const void* x, int x_dt, int ldx, long x_bs, const fl
                            int ktaps, int C, void* wav, long wav_bs, int pcm16, int B, int Nmax, const int* in_len,
                            int len_mul, const int* out_len, int out_mul, hipStream_t s);
 // Band-limited rational resampler, rate_in -> rate_out with L = rate_out / gcd, M = rate_in / gcd (include/zvx.h, zvx_resample):
-//   y[n] = sum_k h[n M - k L] x[k],  h = the Kaiser-windowed sinc of 2 * half + 1 taps designed by the context (zvx.hip, rs_bank).
+//   y[n] = sum_k h[n M - k L] x[k],  h = the Kaiser-windowed sinc of 2 * half + 1 taps designed by the context (host_post.hip, rs_bank).
 // One launch converts the rows of a device table with one ResampleRow per row: its input and output pointers, its length, its own
 // in_origin / out_begin / cnt and the bound `zend` up to which zeros follow the emitted samples, so that the rows of one launch may live in
 // unrelated buffers and sit anywhere on their signals.  The row holds samples [in_origin, in_origin + n) of a signal that is zero elsewhere;
 // outputs [out_begin, out_begin + cnt) go to positions [0, cnt) of `out`, then zeros up to zend; nothing beyond zend is written (zend = cnt:
 // nothing outside [0, cnt); the calls with one window for all rows pass the longest row's cnt: the zero fill to the longest row).  Every
-// length and count is formed on the HOST (zvx.hip, run_resample_rows) and travels in the table, which every call uploads through the
+// length and count is formed on the HOST (host_post.hip, run_resample_rows) and travels in the table, which every call uploads through the
 // context's pinned staging arena, queued like a launch.  out: f32, or with pcm16 int16 = trunc(clamp(v * 32760, -32768, 32767)).
 // bank: [L][pitch] f32 on the device (padded to a multiple of 4 floats): row p holds the T = ceil((2 half + 1) / L) taps of phase p in
 // ascending input order, bank[p][t] = h[p + (joff[p] - t) L] (0 where that index is below -half), and in column T the integer
@@ -592,7 +592,7 @@ void launch_loud_apply(const LoudApplyArgs& a, long n_max, hipStream_t s);
 // tiles of LIMIT_TILE samples of one row, 256 threads each; nothing outside [0, n) of a row is read or written.  `rows` is a device
 // table with one LimitRow per row -- its input, output and envelope pointers, its length and its emitted range --, so that the rows of one
 // launch may live in unrelated buffers and sit anywhere on their signals; every call uploads one through the context's pinned staging arena
-// (zvx.hip, run_limit_rows).  A windowed row emits the samples [off, off + cnt) only: the envelope is still evaluated over the whole row,
+// (host_post.hip, run_limit_rows).  A windowed row emits the samples [off, off + cnt) only: the envelope is still evaluated over the whole row,
 // the gain tiles start at `off` -- any sample offset from the envelope's tile grid -- and write out[i - off]; the arithmetic of a sample
 // depends on neither grid.  A whole row is off = 0, cnt = n.  Every kernel reads rows[blockIdx.y] at its top and works from it alone, so
 // the whole-row call, the _ex call and the per-row call run the same instructions.  Grids are sized by the longest row; a workgroup past
@@ -634,7 +634,7 @@ void launch_limit_reduce(const LimitArgs& a, hipStream_t s);
 // the lengths (zvx_melspec's conditions), so every reflected index lies inside the row.
 // `rows` is a device table with one DenoiseRow per row -- its input, output and work-buffer pointers, its length and its window --, so that
 // the rows of one launch may live in unrelated buffers and sit anywhere on their signals; every call uploads one through the context's
-// pinned staging arena (zvx.hip, run_denoise_rows).
+// pinned staging arena (host_post.hip, run_denoise_rows).
 // The window: a row holds samples [origin, origin + n) of its signal and the frame grid is the SIGNAL's.  The kernels work in
 // window-relative ints: frame j of the work buffer is frame f_first + j of the signal and reads the window from sample rel + j hop on
 // (rel = f_first hop - pad - origin; negative: in the left mirror); the one absolute quantity, the signal's frame count, is formed in 64
