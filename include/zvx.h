@@ -826,6 +826,56 @@ zvx_status zvx_level_rows(zvx_ctx* ctx, const float* in, const int32_t* nsamples
                           const zvx_level_params* params, void* out, int64_t out_stride, float* gain_lo, float* gain_hi, int flags,
                           const zvx_row_window* win);
 
+/* Equaliser: a general FIR filter over rows [B][Nmax] f32 with nsamples[b] valid samples -- the tone-shaping stage between clean-up
+ * (denoiser) and loudness (gain, limiter).  zerovox_amd/equaliser.py designs linear-phase taps from bells, shelves and band edges; the
+ * library only filters.  No claim of audible merit is made: the arithmetic is pinned, nothing more.
+ * Per row of N samples, K = ntaps, D = delay, h = taps (a HOST array [K], may be reused when the call returns):
+ *     y[i] = sum over k = 0 .. K-1 of h[k] * x[i + D - k],   0 <= i < N,   x[j] = 0 for j < 0 and j >= N.
+ *   Output row b has the input's length.  With D = (K - 1) / 2 and symmetric taps (linear phase) the output is time-aligned with the
+ *   input; with D = 0 the filter is causal.  0 <= D <= K - 1.
+ * Arithmetic, part of the contract: acc is a double that starts at +0.0; the terms are added in ASCENDING k, acc = acc + (double) h[k] *
+ *   (double) x[i + D - k]; out = (float) acc, one rounding to nearest-even; with ZVX_PCM16 the resampler's rule follows on that float.
+ *   The product of two f32 values is exact in double (24 + 24 <= 53 bits of significand, magnitude in [2^-298, 2^256)), so a fused
+ *   multiply-add and a multiply followed by an add give the same bits and the result depends on the order of k alone -- which is fixed, not
+ *   left to the compiler, to a split of the sum or to a matrix unit.  Zero terms change nothing (the kernel skips or adds the zeros outside
+ *   the signal), and acc is never -0.0: it starts at +0, and in round-to-nearest neither +0 + (-0) nor x + (-x) gives -0.  No output is -0.0.
+ * Exact corners: K = 1, h = {1}, D = 0 returns x's values (-0.0 becomes +0.0); all-zero taps give +0.0 everywhere; n == 0 writes nothing;
+ *   a row's bits depend on its own samples, the taps and D only -- not on B, Nmax, strides or neighbours; non-finite input follows
+ *   zvx_vocode_mel's rule (that row unspecified, nothing faults, the others untouched); results of magnitude below 2^-126 may be kept or
+ *   flushed, unspecified.
+ * zvx_fir_ex / zvx_fir_rows: the same over a window / a window per row, under the contract of zvx_limit_ex / zvx_denoise_ex / zvx_*_rows
+ *   word for word, with an ASYMMETRIC reach as the leveler has it: RL = K - 1 - D to the left and RR = D to the right.  Support condition,
+ *   per row with cnt_b > 0 (otherwise ZVX_E_INVALID; the message names the row, RL or RR and the missing samples):
+ *     in_origin <= out_begin  and  out_begin + cnt_b <= in_origin + nsamples[b];
+ *     left:  in_origin == 0  or  out_begin - RL >= in_origin;
+ *     right: last  or  out_begin + cnt_b - 1 + RR <= in_origin + nsamples[b] - 1.
+ *   The emitted samples are bit for bit those of zvx_fir on the whole signal: an output's terms are the same numbers in the same order,
+ *   wherever the window sits.  zvx_fir is zvx_fir_ex(..., 0, 0, -1, 1).  Absolute positions may lie beyond 2^32: no index is formed in 32
+ *   bits from one.  _rows: row b is bit for bit the _ex call on that row alone, nothing outside [0, cnt_b) of an output row is touched; the
+ *   taps and D stay per CALL.
+ * Flags: ZVX_DEVICE_IN, ZVX_DEVICE_OUT, ZVX_NO_SYNC (device out only), ZVX_PCM16 (not in place).  out == in is allowed for f32 rows with
+ *   the same stride, on the same side and out_begin == in_origin: a FIR reads its neighbours, so the in-place call filters into a work
+ *   buffer of the context and copies the emitted ranges back in the same timed group; the bits are those of the out-of-place call.  With
+ *   ZVX_DEVICE_OUT | ZVX_NO_SYNC the call only queues: the taps travel through pinned staging like the denoiser's bias.
+ * Validation, before anything is queued (the context stays usable): the rows-call checks of zvx_limit; ZVX_E_INVALID for NULL taps, ntaps
+ *   < 1, delay outside [0, K - 1], a tap that is not finite, the window checks and the support condition per row; ZVX_E_UNSUPPORTED for
+ *   ntaps > ZVX_FIR_MAX_TAPS and more than 65535 rows.
+ * Launches: one row descriptor per row is formed on the host -- input, output, length, emitted range -- and uploaded as one table through
+ *   the pinned staging arena, the taps likewise as doubles: one kernel body serves all three calls (csrc/fir.hip: a workgroup stages its
+ *   tile's slab in LDS, each lane keeps 4 consecutive outputs in registers and slides one new sample in per tap).
+ * Stage tag "post.fir" in zvx_tag_stats (one timed group per call; no stage slot): algorithmic bytes = 4 per sample read plus 4 (or, with
+ *   ZVX_PCM16, 2) per emitted sample; flops = 2 K per emitted sample.
+ * A stream: zerovox_amd/equaliser.py's FirPlanner plans the windows -- a non-last push emits up to received - RR, the history before
+ *   next_out - RL is dropped -- so an equalised stream runs RR = D samples behind its input.
+ * Not here: a stage in zvx_stream_open_ex (zvx_stream_stages stays as it is), per-row taps, IIR sections, several channels. */
+#define ZVX_FIR_MAX_TAPS 4096
+zvx_status zvx_fir(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, const float* taps, int ntaps, int delay,
+                   void* out, int64_t out_stride, int flags);
+zvx_status zvx_fir_ex(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, const float* taps, int ntaps, int delay,
+                      void* out, int64_t out_stride, int flags, int64_t in_origin, int64_t out_begin, int64_t out_count, int last);
+zvx_status zvx_fir_rows(zvx_ctx* ctx, const float* in, const int32_t* nsamples, int B, int Nmax, const float* taps, int ntaps, int delay,
+                        void* out, int64_t out_stride, int flags, const zvx_row_window* win);
+
 /* Stream sessions: chunked vocoding of ONE utterance with the planning inside the library.  A session owns the utterance's mel on the
  * device, vocodes it group by group and runs the new samples device to device through the optional denoiser, leveler, watermark, limiter
  * and rate conversion (leveler and watermark: zvx_stream_open_ex); each zvx_stream_next hands out one finished piece with one wait.  It is

@@ -29,7 +29,8 @@ EXPORTS = ("zvx_create", "zvx_destroy", "zvx_last_error", "zvx_get_int", "zvx_se
            "zvx_denoise_ex", "zvx_stream_open", "zvx_stream_next", "zvx_stream_info", "zvx_stream_close", "zvx_stream_next_many",
            "zvx_denoise_rows", "zvx_limit_rows", "zvx_resample_rows", "zvx_level", "zvx_level_ex", "zvx_level_rows", "zvx_loudness_stats",
            "zvx_pitch", "zvx_watermark", "zvx_watermark_ex", "zvx_watermark_detect", "zvx_watermark_rows", "zvx_watermark_identify",
-           "zvx_stream_open_ex", "zvx_spk_score", "zvx_spk_topk", "zvx_dev_copy", "zvx_dtw", "zvx_align_wav")
+           "zvx_stream_open_ex", "zvx_spk_score", "zvx_spk_topk", "zvx_dev_copy", "zvx_dtw", "zvx_align_wav", "zvx_fir", "zvx_fir_ex",
+           "zvx_fir_rows")
 # columns of zvx_align_wav's stats[B][ZVX_AL_COUNT]
 ZVX_AL_FRAMES_A, ZVX_AL_FRAMES_B, ZVX_AL_PATH_LEN, ZVX_AL_COST, ZVX_AL_MCD_DB, ZVX_AL_COUNT = range(6)
 DTW_MAX_FRAMES, DTW_MAX_DIM = 4096, 32               # zvx_dtw's caps (csrc/zvx_kernels.h; ZVX_E_UNSUPPORTED beyond)
@@ -49,6 +50,7 @@ PITCH_MAX_WINDOW, PITCH_MAX_TAU, PITCH_MAX_FRAMES = 4096, 2048, 65536     # zvx_
 LIMIT_TILE = 1024                                    # samples per workgroup of both limiter kernels (csrc/zvx_kernels.h, LIMIT_TILE)
 LIMIT_MAX_W = 4096                                   # the longest window, in samples (LIMIT_MAX_W)
 LIMIT_ENV_REACH = 11                                 # samples the oversampled envelope reads to either side (LIMIT_ENV_REACH; limiter.reach)
+ZVX_FIR_MAX_TAPS = 4096                              # the longest filter zvx_fir takes (ZVX_E_UNSUPPORTED beyond)
 
 
 def resampled_len(n, rate_in, rate_out):
@@ -222,6 +224,9 @@ def load():
     lib.zvx_level.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.POINTER(LevelParams), vp, C.c_int64, vp, vp, C.c_int]
     lib.zvx_level_ex.argtypes = lib.zvx_level.argtypes + [C.c_int64, C.c_int64, C.c_int64, C.c_int]
     lib.zvx_level_rows.argtypes = lib.zvx_level.argtypes + [C.POINTER(RowWindow)]
+    lib.zvx_fir.argtypes = [vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, C.c_int, vp, C.c_int64, C.c_int]
+    lib.zvx_fir_ex.argtypes = lib.zvx_fir.argtypes + [C.c_int64, C.c_int64, C.c_int64, C.c_int]
+    lib.zvx_fir_rows.argtypes = lib.zvx_fir.argtypes + [C.POINTER(RowWindow)]
     lib.zvx_stream_open.argtypes = [vp, vp, C.c_int, C.POINTER(StreamParams), C.c_int, C.POINTER(vp)]
     lib.zvx_stream_open_ex.argtypes = [vp, vp, C.c_int, C.POINTER(StreamParams), C.POINTER(StreamStages), C.c_int, C.POINTER(vp)]
     lib.zvx_stream_next.argtypes = [vp, vp, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int32), C.c_int]
@@ -525,6 +530,7 @@ class Context:
     _LEVEL = ("level", True, (np.float32, np.float32))
     _DENOISE = ("denoise", False, ())
     _WATERMARK = ("watermark", False, ())
+    _FIR = ("fir", False, ())
     _NORMALIZE = ("normalize", True, (np.float64, np.float32, np.float32))       # (whole rows and in place only)
 
     def _effect(self, fx, mid, rows, lengths, *, rate=None, pcm16=False, window=None, windows=None, device=None, no_sync=False):
@@ -888,6 +894,37 @@ class Context:
         what level_window gives on each row alone."""
         return self._effect(self._LEVEL, self._level_mid(target, max_gain_db, window_ms, lookahead_ms), rows, lengths, rate=rate, pcm16=pcm16,
                             windows=windows)
+
+    @staticmethod
+    def _fir_mid(taps, delay):
+        """the arguments between Nmax and out: the taps (a host array, float32), their number and the delay (None: (K - 1) // 2, which
+        time-aligns a symmetric filter)"""
+        taps = _f32(taps).reshape(-1)
+        K = int(taps.shape[0])
+        return _ptr(taps), K, (K - 1) // 2 if delay is None else int(delay)
+
+    def fir(self, rows, taps, delay=None, pcm16=False, lengths=None):
+        """zvx_fir on host rows: y[i] = sum_k taps[k] x[i + delay - k], zeros outside the row, accumulated in double in ascending k and
+        rounded once (include/zvx.h) -> rows_out [B][Nmax] float32 / int16 -- row b holds its filtered samples, then zeros.  rows: a list
+        of 1-D float waveforms, or a padded 2-D array + lengths.  delay None: (K - 1) // 2.  zerovox_amd.equaliser designs taps."""
+        return self._effect(self._FIR, self._fir_mid(taps, delay), rows, lengths, pcm16=pcm16)[0]
+
+    def fir_window(self, rows, taps, delay=None, in_origin=0, out_begin=0, out_count=-1, last=True, pcm16=False, lengths=None):
+        """zvx_fir_ex on host rows: the rows hold samples [in_origin, in_origin + len) of signals that start at sample 0 and, with `last`,
+        end with the row; the outputs [out_begin, out_begin + out_count) of the whole-signal filter (out_count -1, which needs last: to
+        the end of each row's signal) -> out [B][n] float32 / int16.  The window must carry equaliser.reach(K, delay) = (K - 1 - delay,
+        delay) samples of support to the left and to the right of the outputs, except at the signal's own ends (include/zvx.h)."""
+        return self._effect(self._FIR, self._fir_mid(taps, delay), rows, lengths, pcm16=pcm16, window=(in_origin, out_begin, out_count, last))[0]
+
+    def fir_rows(self, rows, taps, windows, delay=None, pcm16=False, lengths=None):
+        """zvx_fir_rows on host rows: fir_window with a window per row (windows[b] = (in_origin, out_begin, out_count, last)) -> a list of
+        B arrays, row b's emitted samples (float32 / int16), bit for bit those of fir_window on that row alone.  One filter per call."""
+        return self._effect(self._FIR, self._fir_mid(taps, delay), rows, lengths, pcm16=pcm16, windows=windows)[0]
+
+    def fir_device(self, ptr, lengths, Nmax, taps, delay=None, *, no_sync=False):
+        """zvx_fir IN PLACE on device rows [B][Nmax] f32 at `ptr` (the filter writes a work buffer of the context and copies back; the
+        bits are the out-of-place call's); with no_sync the call only queues.  taps is a host array and may be reused at once."""
+        self._effect_in_place(self._FIR, self._fir_mid(taps, delay), ptr, lengths, Nmax, no_sync)
 
     def resample_rows(self, rows, rate_in, rate_out, windows, pcm16=False, lengths=None):
         """zvx_resample_rows on host rows: resample_window with a window per row -- windows[b] = (in_origin, out_begin, out_count) or

@@ -9,7 +9,7 @@ LIB = os.path.join(HERE, "libzvx.so")
 # test-only launcher shim (tests/native/zvx_ktest.hip): tests/test_kernels_gpu.py drives the launchers through it
 KTEST_SRC = os.path.join(os.path.dirname(HERE), "tests", "native", "zvx_ktest.hip")
 KTEST_LIB = os.path.join(HERE, "libzvx_ktest.so")
-SOURCES = ["gemm.hip", "resstream.hip", "pairstream.hip", "narrowstage.hip", "attention.hip", "ops.hip", "spectral.hip", "watermark.hip", "voicematch.hip", "align.hip"]
+SOURCES = ["gemm.hip", "resstream.hip", "pairstream.hip", "narrowstage.hip", "attention.hip", "ops.hip", "spectral.hip", "watermark.hip", "voicematch.hip", "align.hip", "fir.hip"]
 # the host units: launch sequences and the C-ABI behind one internal header (csrc/zvx_host.h); none of them defines a kernel
 HOST_SOURCES = ["host_post.hip", "host_stream.hip", "host_comm.hip", "zvx.hip"]
 # translation units: (object stem, source, extra -D flags).  gemm.hip is compiled as two units side by side (its fused ResBlock-pair kernels are

@@ -1,5 +1,5 @@
 // host_post.hip -- the post-processing calls that write waveform rows: the rows-call and window contracts, resampler, join / trim,
-// limiter, leveler, denoiser and its bias, watermark embedding.
+// limiter, leveler, denoiser and its bias, watermark embedding, equaliser.
 #include "zvx_host.h"
 
 namespace zvx::host {
@@ -940,6 +940,72 @@ void do_watermark(zvx_ctx* c, const char* who, const float* in, const int32_t* n
     });
 }
 
+// ------------------------------------------------------------------------------------------------
+// equaliser (include/zvx.h: zvx_fir, zvx_fir_ex, zvx_fir_rows; kernel: fir.hip)
+// ------------------------------------------------------------------------------------------------
+namespace {
+// The filter over B rows with a window each, every caller's launches: ONE table upload, ONE tap upload (doubles, padded with zero taps to
+// the kernel's group of 4), the filter launch and, in place, the copy-back under one timed group.  In place the filter writes
+// "fir.tmp", row after row, and the copy launch brings every emitted range back: the bits are the out-of-place call's.
+// The caller has validated the rows, the taps and the support condition (which is what makes a sample outside a row a true zero).
+// In place is decided from the DEVICE rows: a host call with out == in has been staged into two buffers and needs no work buffer.
+void run_fir_rows(zvx_ctx* c, const PostRow* rows, int B, const float* taps, int K, int D, int pcm16) {
+    const bool in_place = rows[0].out == (const void*)rows[0].in;
+    const int Kp = (K + 3) & ~3;
+    std::vector<double> h((size_t)Kp, 0.0);
+    for (int k = 0; k < K; k++) h[(size_t)k] = (double)taps[k];
+    std::vector<FirRow> tab((size_t)B);
+    std::vector<FirCopyRow> back(in_place ? (size_t)B : 0);
+    double n_sum = 0, cnt_sum = 0;
+    long cnt_max = 0;
+    size_t tmp_floats = 0;
+    for (int b = 0; b < B; b++) { cnt_sum += rows[b].cnt; tmp_floats += (size_t)std::max(rows[b].cnt, 0); }
+    float* tmp = in_place ? c->fbuf("fir.tmp", std::max<size_t>(tmp_floats, 1)) : nullptr;
+    for (int b = 0; b < B; b++) {
+        const PostRow& r = rows[b];
+        FirRow& t = tab[(size_t)b];
+        t.x = r.in; t.out = in_place ? (void*)tmp : r.out;
+        t.n = r.n; t.off = r.cnt > 0 ? (int)(r.w.out_begin - r.w.in_origin) : 0; t.cnt = r.cnt; t.pad_ = 0;
+        if (in_place) { back[(size_t)b] = FirCopyRow{(float*)r.out, tmp, (long)r.cnt}; tmp += std::max(r.cnt, 0); }
+        n_sum += r.n; cnt_max = std::max<long>(cnt_max, r.cnt);
+    }
+    FirArgs a{};
+    a.B = B; a.Kp = Kp; a.D = D; a.pcm16 = pcm16;
+    double* taps_d = (double*)c->buf("fir.taps", (size_t)Kp * sizeof(double));
+    c->upload(taps_d, h.data(), (size_t)Kp * sizeof(double));
+    FirRow* tab_d = (FirRow*)c->buf("fir.rows", (size_t)B * sizeof(FirRow));
+    c->upload(tab_d, tab.data(), (size_t)B * sizeof(FirRow));
+    FirCopyRow* back_d = nullptr;
+    if (in_place) {
+        back_d = (FirCopyRow*)c->buf("fir.back", (size_t)B * sizeof(FirCopyRow));
+        c->upload(back_d, back.data(), (size_t)B * sizeof(FirCopyRow));
+    }
+    a.rows = tab_d; a.taps = taps_d;
+    TagScope scope(c, "post.fir");
+    c->timed(2.0 * K * cnt_sum, 4.0 * n_sum + (pcm16 ? 2.0 : 4.0) * cnt_sum, [&] {
+        launch_fir(a, cnt_max, c->stream);
+        if (in_place) launch_fir_copy(back_d, B, cnt_max, c->stream);
+    });
+}
+}  // namespace
+
+// zvx_fir, zvx_fir_ex and zvx_fir_rows: every check before anything is allocated, uploaded or queued
+void do_fir(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, const float* taps, int ntaps, int delay,
+            void* out, int64_t out_stride, int flags, const WindowsIn& win) {
+    rows_check(who, in, nsamples, B, Nmax, 65535);
+    flags_check(who, flags, ZVX_DEVICE_IN | ZVX_DEVICE_OUT | ZVX_NO_SYNC | ZVX_PCM16);
+    out_rows_check(who, in, out, out_stride, Nmax, flags);
+    if (!taps) fail(ZVX_E_INVALID, "%s: taps is NULL", who);
+    if (ntaps < 1) fail(ZVX_E_INVALID, "%s: ntaps %d must be at least 1", who, ntaps);
+    if (ntaps > FIR_MAX_TAPS) fail(ZVX_E_UNSUPPORTED, "%s: %d taps (at most %d)", who, ntaps, FIR_MAX_TAPS);
+    if (delay < 0 || delay > ntaps - 1) fail(ZVX_E_INVALID, "%s: delay %d outside [0, %d]", who, delay, ntaps - 1);
+    for (int k = 0; k < ntaps; k++) if (!std::isfinite(taps[k])) fail(ZVX_E_INVALID, "%s: taps[%d] is not finite", who, k);
+    const RowsWindows rw = rows_windows_check(who, win, nsamples, B, (int64_t)ntaps - 1 - delay, in, out, out_stride, delay);
+    post_call(c, "fir", in, nsamples, B, Nmax, out, out_stride, true, flags, rw, 0, false, [&](const PostRow* rows) {
+        run_fir_rows(c, rows, B, taps, ntaps, delay, (flags & ZVX_PCM16) ? 1 : 0);
+        return nullptr;
+    });
+}
 
 // zvx_resample_rows: every check before anything is allocated, uploaded or queued
 void do_resample_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate_in, int rate_out, void* out, int64_t out_stride,

@@ -2487,6 +2487,7 @@ int64_t zvx_get_int(const zvx_ctx* c, const char* key) {
         try { unsigned long long* d = m->sat_count_dev(); m->sync(); if (hipMemcpy(&n, d, sizeof n, hipMemcpyDeviceToHost) != hipSuccess) return -1; } catch (...) { return -1; }
         return (int64_t)n;
     }
+    if (k == "fir_tile") return FIR_TILE;                   // emitted samples per workgroup of zvx_fir (the tests' tile-edge rows)
     if (k == "host_slot") return c->host_last;             // the slot the last ZVX_HOST_ASYNC call writes (-1: none yet)
     if (k.rfind("variant_id:", 0) == 0) { for (int i = 0; i < gemm_num_variants(); i++) if (k.substr(11) == gemm_variant_name(i)) return i; return -1; }
     auto it = c->cfg.find(k);
@@ -2788,6 +2789,27 @@ zvx_status zvx_level_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, 
     return guarded(c, [&] {
         const WindowsIn w{WindowsIn::PER_ROW, RowsWindow{}, win};
         do_level(c, "zvx_level_rows", in, nsamples, B, Nmax, rate, params, out, out_stride, gain_lo, gain_hi, flags, w);
+    });
+}
+
+zvx_status zvx_fir(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const float* taps, int ntaps, int delay, void* out,
+                   int64_t out_stride, int flags) {
+    return guarded(c, [&] { do_fir(c, "zvx_fir", in, nsamples, B, Nmax, taps, ntaps, delay, out, out_stride, flags); });
+}
+
+zvx_status zvx_fir_ex(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const float* taps, int ntaps, int delay, void* out,
+                      int64_t out_stride, int flags, int64_t in_origin, int64_t out_begin, int64_t out_count, int last) {
+    return guarded(c, [&] {
+        const WindowsIn win{WindowsIn::ONE, RowsWindow{in_origin, out_begin, out_count, last}};
+        do_fir(c, "zvx_fir_ex", in, nsamples, B, Nmax, taps, ntaps, delay, out, out_stride, flags, win);
+    });
+}
+
+zvx_status zvx_fir_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, const float* taps, int ntaps, int delay, void* out,
+                        int64_t out_stride, int flags, const zvx_row_window* win) {
+    return guarded(c, [&] {
+        const WindowsIn w{WindowsIn::PER_ROW, RowsWindow{}, win};
+        do_fir(c, "zvx_fir_rows", in, nsamples, B, Nmax, taps, ntaps, delay, out, out_stride, flags, w);
     });
 }
 

@@ -17,7 +17,7 @@
 //                    run_denoise_rows, run_watermark_rows -> host_stream;  loud_coef, dn_tables, watermark_params_check -> zvx.hip, host_stream;
 //                    stft_len_check, wm_sign_table -> zvx.hip (watermark detection)
 //                    entry functions: do_resample, do_resample_rows, do_trim_bounds, do_join, do_limit, do_level, do_denoise, do_denoise_bias,
-//                    do_watermark -> zvx.hip
+//                    do_watermark, do_fir -> zvx.hip
 //   host_stream.hip  stream_free, do_stream_open, do_stream_next, do_stream_next_many, do_stream_info -> zvx.hip (the entry points)
 // and, defined here: guarded (zvx.hip, host_comm.hip), gemm_base, set_taps_1d, dn_min_samples, dn_frames, dn_fft_flops, and the structs of the
 // rows and window contracts (RowsInfo, DevRows, TagScope, RowsReturn, RowsWindow, PostRow, RowsWindows, RsPlan, WindowsIn).
@@ -625,6 +625,8 @@ void do_watermark(zvx_ctx* c, const char* who, const float* in, const int32_t* n
 void do_resample_rows(zvx_ctx* c, const float* in, const int32_t* nsamples, int B, int Nmax, int rate_in, int rate_out, void* out, int64_t out_stride,
                       int32_t* out_len, int flags, const zvx_row_window* win);
 void do_denoise_bias(zvx_ctx* c, float* bias);
+void do_fir(zvx_ctx* c, const char* who, const float* in, const int32_t* nsamples, int B, int Nmax, const float* taps, int ntaps, int delay,
+            void* out, int64_t out_stride, int flags, const WindowsIn& win = {});
 
 // ---- host_stream.hip: stream sessions
 void stream_free(zvx_stream* s);

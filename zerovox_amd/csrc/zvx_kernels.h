@@ -385,6 +385,35 @@ void launch_dtw_backtrack(const DtwArgs& a, hipStream_t s);
 // cep[b][t][k] = (float)(scale * sum_m mel[b][t][m] table[k][m]) in double for t < frames[b], 0 beyond; mel is [B][Tp][M] f32, table [n_cep][M]
 void launch_cepstra(const float* mel, int Tp, const int* frames, int B, int M, int n_cep, const double* table, double scale, float* cep, hipStream_t s);
 
+// ---- equaliser (include/zvx.h, zvx_fir / zvx_fir_ex / zvx_fir_rows; fir.hip) ----
+// The equaliser's FIR filter over waveform rows (include/zvx.h, zvx_fir; fir.hip): y[i] = sum_k h[k] x[i + D - k] with a double accumulator
+// from +0.0, the terms in ascending k, one rounding to f32.  `rows` is a device table with one FirRow per row -- its input and output
+// pointers, its length and its emitted range --, so that the rows of one launch may live in unrelated buffers and sit anywhere on their
+// signals; every call uploads one through the context's pinned staging arena (host_post.hip, run_fir_rows).  A windowed row emits the
+// samples [off, off + cnt) only and out[e] is output off + e.  Whatever lies outside [0, n) of a row is read as zero: the host's support
+// condition (reach K - 1 - D to the left, D to the right) admits only windows in which those are the signal's own zeros.  The kernel reads
+// rows[blockIdx.y] at its top and works from it alone: every form of the call runs the same instructions.
+// (The descriptor carries no count of true zeros in front of and behind the row, which the design note of this filter listed: the
+// support condition is checked on the host before anything is queued, and under it zero outside [0, n) IS the signal, so the two
+// counts would never be read.)
+// taps: Kp = K rounded up to a multiple of 4 doubles on the device, h[k] converted exactly, zeros behind K.
+constexpr int FIR_TILE = 1024;               // emitted samples per workgroup (zvx_get_int("fir_tile"))
+constexpr int FIR_MAX_TAPS = 4096;           // ZVX_FIR_MAX_TAPS
+struct FirRow {
+    const float* x; void* out;               // the row's samples; where emitted sample 0 goes (f32 or int16)
+    int n, off, cnt, pad_;                   // the row's length; the emitted range [off, off + cnt)
+};
+struct FirArgs {
+    const FirRow* rows;                      // [B], on the device
+    const double* taps;                      // [Kp]
+    int B, Kp, D, pcm16;
+};
+// grid.x covers cnt_max, the longest emitted range; nothing is launched where it is 0
+void launch_fir(const FirArgs& a, long cnt_max, hipStream_t s);
+// dst[e] = src[e] for e < cnt of every row: the copy-back of the in-place form (the filter reads its neighbours, so it writes a work buffer)
+struct FirCopyRow { float* dst; const float* src; long cnt; };
+void launch_fir_copy(const FirCopyRow* rows, int B, long cnt_max, hipStream_t s);
+
 // ------------------------------------------------------------------------------------------------
 // Small kernels (ops.hip).  T-typed pointers are void* + dtype.
 // ------------------------------------------------------------------------------------------------

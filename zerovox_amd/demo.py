@@ -9,6 +9,8 @@ sentence by sentence in batches and joins the sentences on the device; --wav-fil
 the device (zvx_normalize).  `--limiter` (with `--limiter-ms MS`) holds it under `--peak-db` with the true-peak look-ahead limiter
 (zvx_limit); the loudness gain is then no longer bounded by the peak.  `--denoise S` takes S times the vocoder's bias spectrum off the
 waveform on the device, directly behind the vocoder (zvx_denoise; 0.01 is the usual strength; its audible benefit is not measured here).
+`--eq NAME`: a preset of zerovox_amd.equaliser (presence, warm, rumble, telephone, flat) filters the waveform on the device, behind the denoiser
+and before the mark, the loudness gain and the limiter (zvx_fir; tts and --long, not the --level stream; no claim of audible merit is made).
 `--level LUFS`: the utterance is STREAMED (ZeroVoxTTS.tts_stream) and levelled window by window towards a short-term loudness on the device
 (zvx_level_ex: an AGC, not the R128 normalisation of --loudness; its audible merit is not measured here); --denoise and, with --limiter,
 --peak-db apply to the stream as well, and the pieces are joined for the WAV file.
@@ -65,6 +67,7 @@ def main():
     ap.add_argument("--limiter-ms", type=float, default=5.0, metavar="MS", help="smoothing window of the limiter's gain on either side of a peak")
     ap.add_argument("--denoise", type=float, default=None, metavar="S",
                     help="strength of the vocoder-bias denoiser on the device, e.g. 0.01 (default: off)")
+    ap.add_argument("--eq", default=None, metavar="NAME", help="equaliser preset applied on the device: presence, warm, rumble, telephone, flat (default: off)")
     ap.add_argument("--level", type=float, default=None, metavar="LUFS",
                     help="stream the utterance and level it towards this short-term loudness on the device, e.g. -16 (default: off)")
     ap.add_argument("--long", action="store_true", help="long-form: split the text (or the file it names) into sentences and join them on the device")
@@ -87,6 +90,12 @@ def main():
         ap.error("--mcd and --rhythm-from go with one plain utterance: neither with --long nor with --level")
     if args.detect_watermark is None and args.identify_watermark is None and args.match_voice is None and not args.text:
         ap.error("the text is missing")
+    if args.eq is not None:
+        from .equaliser import PRESETS
+        if args.eq not in PRESETS:
+            ap.error(f"--eq: {args.eq!r} is none of {', '.join(sorted(PRESETS))}")
+        if args.level is not None:
+            ap.error("--eq does not go with --level: the stream has no equaliser stage yet")
     if args.level is not None and (args.long or args.loudness is not None):
         ap.error("--level streams one utterance: it goes with neither --long nor --loudness")
 
@@ -156,7 +165,7 @@ def main():
                                            energy_shift=args.energy_shift, energy_range=args.energy_range, loudness=args.loudness,
                                            peak_db=args.peak_db, limiter=args.limiter, limiter_ms=args.limiter_ms, denoise=args.denoise,
                                            report=args.report, pitch_report=args.pitch_report, watermark=args.watermark,
-                                           voice_report=args.voice_report)
+                                           voice_report=args.voice_report, eq=args.eq)
             elapsed = time.time() - t0
             wav_len = (wav.shape[0] if segments else 0) / sr
             print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, {len(segments)} sentences, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")
@@ -195,7 +204,7 @@ def main():
                                          energy_shift=args.energy_shift, energy_range=args.energy_range, loudness=args.loudness,
                                          peak_db=args.peak_db, limiter=args.limiter, limiter_ms=args.limiter_ms, denoise=args.denoise,
                                          report=args.report, pitch_report=args.pitch_report, watermark=args.watermark,
-                                         voice_report=args.voice_report, rhythm_from=rhythm, rhythm_rate=rhythm_rate)
+                                         voice_report=args.voice_report, rhythm_from=rhythm, rhythm_rate=rhythm_rate, eq=args.eq)
         elapsed = time.time() - t0
         wav_len = wav.shape[0] / sr
         print(f"[{i + 1}/{args.iter}] Synth time: {elapsed:.2f} sec, voice length: {wav_len:.2f} sec, rtf: {wav_len / elapsed:.2f}")

@@ -77,9 +77,10 @@ def split_sentences(text, max_chars=MAX_CHARS):
 
 def synthesize_long(tts, text, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20, fade_ms=5, max_batch=32, max_frames=2048, pcm16=False,
                     durations=None, max_chars=MAX_CHARS, prosody=None, loudness=None, peak_db=-1.0, loudness_mode="paragraph",
-                    limiter=False, limiter_ms=5.0, denoise=None, report=False, watermark=None):
+                    limiter=False, limiter_ms=5.0, denoise=None, report=False, watermark=None, eq=None):
     """The body of ZeroVoxTTS.tts_long (see there).  prosody: Prosody.create keywords applied to every sentence, or None.  denoise: None or
-    Context.denoise_device keywords (strength, floor).  watermark: None or watermark.params(...) (key and the embedder's parameters)."""
+    Context.denoise_device keywords (strength, floor).  watermark: None or watermark.params(...) (key and the embedder's parameters).
+    eq: None or equaliser.params(...) (taps, delay)."""
     from . import _lib
     if loudness_mode not in LOUDNESS_MODES:
         raise ValueError(f"loudness_mode: {loudness_mode!r} is none of {sorted(LOUDNESS_MODES)}")
@@ -140,7 +141,8 @@ def synthesize_long(tts, text, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20,
         loud, limited = tts.model.post_chain_device(
             buf, lengths, stride, denoise=None if denoise is None else dict(denoise, bias=bias), watermark=watermark,
             loudness=None if loudness is None else dict(target=loudness, peak_ceiling=0.0 if lim else peak_ceiling(peak_db),
-                                                        common=LOUDNESS_MODES[loudness_mode]), limiter=lim, rate=native)
+                                                        common=LOUDNESS_MODES[loudness_mode]), limiter=lim, rate=native,
+            **({} if eq is None else {"eq": eq}))
         if loud is not None:
             lufs, gain = [float(v) for v in loud[0]], [float(v) for v in loud[2]]
         if lim:

@@ -165,13 +165,17 @@ class ZeroVox:
                                                      ctx.true_peak_device(ptr, [n], max(n, 1), rate=rate)[0])
         return self.last_report
 
-    def post_chain_device(self, buf, lengths, stride, *, denoise=None, watermark=None, loudness=None, limiter=None, rate=None):
-        """Denoise, watermark, normalise, limit, in this order and IN PLACE over device rows [B][stride] f32 at `buf` (at `rate` Hz), each
-        None or the keywords of its Context.*_device call (denoise with its bias).  The first two only queue, the last two wait for their
-        figures -> (normalize_device's (lufs, peak, gain) or None, limit_device's (peak_in, min_gain) or None)."""
+    def post_chain_device(self, buf, lengths, stride, *, denoise=None, watermark=None, loudness=None, limiter=None, rate=None, eq=None):
+        """Denoise, equalise, watermark, normalise, limit, in this order and IN PLACE over device rows [B][stride] f32 at `buf` (at `rate`
+        Hz), each None or the keywords of its Context.*_device call (denoise with its bias; eq: taps and delay, equaliser.params).  The
+        first three only queue, the last two wait for their figures -> (normalize_device's (lufs, peak, gain) or None, limit_device's
+        (peak_in, min_gain) or None).  The equaliser runs before the mark, so that the mark is not reshaped, and before the gain and the
+        limiter, so that the delivered level and peak hold for the equalised signal."""
         ctx = self._ctx
         if denoise is not None:
             ctx.denoise_device(buf, lengths, stride, no_sync=True, **denoise)
+        if eq is not None:
+            ctx.fir_device(buf, lengths, stride, no_sync=True, **eq)
         if watermark is not None:
             ctx.watermark_device(buf, lengths, stride, no_sync=True, **watermark)
         return (None if loudness is None else ctx.normalize_device(buf, lengths, stride, rate=rate, **loudness),
@@ -184,7 +188,7 @@ class ZeroVox:
         return self._ctx.spkemb(x, lens)[:, None, :]
 
     def inference_ex(self, x, style_embed, normalize_before=True, force_duration=False, prosody=None, loudness=None, limiter=None,
-                     denoise=None, report=False, watermark=None):
+                     denoise=None, report=False, watermark=None, eq=None):
         """model.py:308-347.  x = {"phoneme" [1,T], "puncts" [1,T], "duration" [1,T]|None}; returns
         (wav[:mel_len*hop], mel_len, log_duration [1,T], mel [n_mels, mel_len]).  Batch-1 like the reference.
         Under an output_rate the waveform holds resampled_len(mel_len*hop) samples of that rate; mel_len stays in frames.
@@ -194,6 +198,7 @@ class ZeroVox:
         denoise: None (likewise) or Context.denoise_device keywords (strength, floor): the bias denoiser, directly behind the vocoder.
         watermark: None (likewise) or watermark.params(...) (key and the embedder's parameters): the keyed mark, behind the denoiser and
         before the loudness gain and the limiter.
+        eq: None (likewise) or equaliser.params(...) (taps, delay): the FIR equaliser (zvx_fir), behind the denoiser and before the mark.
         report: with True the returned waveform is measured as delivered (at the output rate, behind every step above; on the device
         where it is still there) and ``last_report`` holds its report.LoudnessReport; False (the default) adds nothing to the call."""
         if denoise is not None:
@@ -214,8 +219,8 @@ class ZeroVox:
         pad_to = self._min_mel_len                       # model.py:331-335: pad up, or raise the floor
         if ml > self._min_mel_len:
             self._min_mel_len = ml
-        if loudness is not None or limiter is not None or denoise is not None or watermark is not None:
-            wav = self._vocode_normalized(mel_len, pad_to, loudness, limiter, denoise, report, watermark)
+        if loudness is not None or limiter is not None or denoise is not None or watermark is not None or eq is not None:
+            wav = self._vocode_normalized(mel_len, pad_to, loudness, limiter, denoise, report, watermark, eq)
             return wav, ml, logd, np.ascontiguousarray(mel[0, :ml].T)
         wav = self._ctx.vocode(1, mel_len, np.array([pad_to], np.int32))
         wav = wav[0, : self._ctx.out_samples(ml * self._hop_length)]
@@ -223,7 +228,7 @@ class ZeroVox:
             self.loudness_report(wav)
         return wav, ml, logd, np.ascontiguousarray(mel[0, :ml].T)
 
-    def _vocode_normalized(self, mel_len, pad_to, loudness, limiter=None, denoise=None, report=False, watermark=None):
+    def _vocode_normalized(self, mel_len, pad_to, loudness, limiter=None, denoise=None, report=False, watermark=None, eq=None):
         """The vocoder writes its row on the device at the model's rate, post_chain_device runs over it in place (queued behind the vocoder:
         stream order is the fence), an output rate converts it, and only then the row comes to the host.  Every step may be absent.
         self.last_loudness reports dict(lufs, peak, gain), self.last_limit dict(peak_in, min_gain); with `report` self.last_report is the finished row's LoudnessReport, measured on the
@@ -235,7 +240,8 @@ class ZeroVox:
         buf = ctx.dev_alloc(n * 4)
         try:
             ctx.vocode_device(mel_len, np.array([pad_to], np.int32), buf, n, native_rate=True, no_sync=True)
-            loud, lim = self.post_chain_device(buf, [n], n, denoise=denoise, watermark=watermark, loudness=loudness, limiter=limiter, rate=native)
+            loud, lim = self.post_chain_device(buf, [n], n, denoise=denoise, watermark=watermark, loudness=loudness, limiter=limiter, rate=native,
+                                               eq=eq)
             if loud is not None:
                 self.last_loudness = dict(lufs=float(loud[0][0]), peak=float(loud[1][0]), gain=float(loud[2][0]))
             if lim is not None:

@@ -200,7 +200,7 @@ class ZeroVoxTTS:
 
     def tts_ex(self, text: str, spkemb, duration=None, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0,
                loudness=None, peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None, report=False, pitch_report=False, watermark=None,
-               voice_report=False):
+               voice_report=False, eq=None):
         """-> (wav f32[N], phoneme i32[1,T], length, mel f32[n_mels, L]); empty text -> the reference's sentinel
         (synthesize.py:213-239).  Prosody (include/zvx.h, zvx_prosody): speed = speaking-rate factor (2.0: half the frames),
         pitch / energy shift (in normalised predictor units) and range (spread about the utterance mean).
@@ -221,6 +221,12 @@ class ZeroVoxTTS:
         vocoder's row on the device, in place, behind the denoiser and before the loudness gain and the limiter; ``detect_watermark``
         finds it again with the key.  Whether it is inaudible on a real checkpoint, and whether it survives lossy codecs,
         time-stretching or deliberate removal, is not measured.
+        eq: None (the default: no launch, buffer or upload of it exists), a preset name of zerovox_amd.equaliser.PRESETS ("presence",
+        "warm", "rumble", "telephone", "flat"), a dict of equaliser.design keywords (taps, bands, low_shelf, high_shelf, highpass_hz,
+        lowpass_hz), an equaliser.Equaliser or (taps, delay): a linear-phase FIR designed at the model's native rate filters the vocoder's
+        row on the device, in place (include/zvx.h, zvx_fir), behind the denoiser and before the mark, the loudness gain and the limiter
+        -- the reported level and peak are those of the equalised signal.  How close a design comes to its target is
+        ``Equaliser.deviation_db``; no claim of audible merit is made.
         report: False (the default: nothing is added to the call), or True: the finished waveform is measured as it is delivered -- at
         the output rate, behind every step above, on the device where its buffer is still there (include/zvx.h, zvx_loudness_stats and
         zvx_true_peak) -- and ``last_report`` holds the report.LoudnessReport (see ``loudness_report``).  The waveform is the same.
@@ -236,6 +242,7 @@ class ZeroVoxTTS:
         prosody = self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range)
         dn = self._denoise(denoise)
         wm = self._watermark(watermark)
+        fir = self._eq(eq)
         text = text.strip()
         t0 = time.time()
         phone_ids, punct_ids = self.text2phonemeids(text)
@@ -253,7 +260,8 @@ class ZeroVoxTTS:
         wav, length, _, mel = self._model.inference_ex({"phoneme": phoneme, "puncts": puncts, "duration": duration},
                                                        style_embed=spkemb, force_duration=duration is not None, prosody=prosody,
                                                        **self._post(loudness, peak_db, limiter, limiter_ms, dn),
-                                                       **({"report": True} if report else {}), **({} if wm is None else {"watermark": wm}))
+                                                       **({"report": True} if report else {}), **({} if wm is None else {"watermark": wm}),
+                                                       **({} if fir is None else {"eq": fir}))
         if self._verbose:
             print(f"tts timing stats: g2p={t1 - t0}s, synth={time.time() - t1}s")
         if pkw is not None:
@@ -274,7 +282,7 @@ class ZeroVoxTTS:
 
     def tts(self, text: str, spkemb, *, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0, loudness=None,
             peak_db=-1.0, limiter=False, limiter_ms=5.0, denoise=None, report=False, pitch_report=False, watermark=None, voice_report=False,
-            rhythm_from=None, rhythm_rate=None):
+            rhythm_from=None, rhythm_rate=None, eq=None):
         """-> (wav, phoneme, length): ``tts_ex`` without the mel.  rhythm_from: None (the default: nothing is added to the call), or a
         recording of the same text at rhythm_rate Hz (None: the model's rate) whose timing is copied: a first pass with predicted durations
         is aligned with the trimmed recording on the device (``fidelity_report``), align.durations_from turns the path into per-phoneme
@@ -291,7 +299,7 @@ class ZeroVoxTTS:
                                               pitch_range=pitch_range,
                                               energy_shift=energy_shift, energy_range=energy_range, loudness=loudness, peak_db=peak_db,
                                               limiter=limiter, limiter_ms=limiter_ms, denoise=denoise, report=report,
-                                              pitch_report=pitch_report, watermark=watermark, voice_report=voice_report)
+                                              pitch_report=pitch_report, watermark=watermark, voice_report=voice_report, eq=eq)
         return wav, phoneme, length
 
     def _rhythm_durations(self, text, spkemb, ref_wav, ref_rate, prosody):
@@ -335,6 +343,14 @@ class ZeroVoxTTS:
     def last_alignment(self):
         """the align.Alignment of the last ``fidelity_report`` call or of the first pass of the last tts(rhythm_from=...) (None before)"""
         return getattr(self, "_last_alignment", None)
+
+    def _eq(self, eq):
+        """the eq keyword (None, a preset name, a dict of design keywords, an Equaliser or (taps, delay)) as Context.fir_device keywords
+        at the model's native rate, or None; checked without a device"""
+        if eq is None:
+            return None
+        from .equaliser import params
+        return params(eq, self._sampling_rate)
 
     @staticmethod
     def _watermark(watermark):
@@ -688,7 +704,7 @@ class ZeroVoxTTS:
     def tts_long(self, text: str, spkemb, *, pauses=None, trim_db=40.0, keep_ms=20, fade_ms=5, max_batch=32, max_frames=2048, pcm16=False,
                  durations=None, max_chars=200, speed=1.0, pitch_shift=0.0, pitch_range=1.0, energy_shift=0.0, energy_range=1.0,
                  loudness=None, peak_db=-1.0, loudness_mode="paragraph", limiter=False, limiter_ms=5.0, denoise=None, report=False,
-                 pitch_report=False, watermark=None, voice_report=False):
+                 pitch_report=False, watermark=None, voice_report=False, eq=None):
         """A paragraph -> (wav, segments): one waveform with every sentence in text order (not in the reference).  The text is split by
         longform.split_sentences; the sentences run in batches of at most max_batch, each batch ONE queued synthesize call into
         consecutive rows of one device buffer (every row is the fresh-model ``tts`` of its sentence; a sentence of more than max_frames
@@ -716,6 +732,8 @@ class ZeroVoxTTS:
         watermark: None (the default: nothing changes), an int key, or a dict with ``key`` (see tts_ex): ONE zvx_watermark over all
         sentence rows of the device buffer, in place, between the denoise and the normalise; every sentence's pattern starts at its own
         first frame, so ``detect_watermark`` finds each sentence at its own offset through its windows.
+        eq: None (the default: nothing changes), or the equaliser of tts_ex: ONE zvx_fir over all sentence rows of the device buffer, in
+        place, between the denoise and the watermark; every sentence is filtered as a signal of its own (zeros beyond its ends).
         report: False (the default: nothing is added to the call), or True: the joined waveform is measured as it is delivered, at the
         output rate, and ``last_report`` holds its report.LoudnessReport (see ``loudness_report``).  A float waveform at the model's
         rate is joined into a device buffer, measured there and copied to the host afterwards -- the same bits as without the report --;
@@ -738,7 +756,8 @@ class ZeroVoxTTS:
                                prosody=self._prosody(speed, pitch_shift, pitch_range, energy_shift, energy_range),
                                loudness=loudness, peak_db=peak_db, loudness_mode=loudness_mode, limiter=limiter, limiter_ms=limiter_ms,
                                denoise=self._denoise(denoise), **({"report": True} if report else {}),
-                               **({} if watermark is None else {"watermark": self._watermark(watermark)}))
+                               **({} if watermark is None else {"watermark": self._watermark(watermark)}),
+                               **({} if eq is None else {"eq": self._eq(eq)}))
         if pkw is not None:
             self._last_pitch_report = None
         if pkw is not None and segments:
