@@ -241,6 +241,7 @@ class Problem:
     def __init__(self, kind, d):
         self.kind, self.d, self.bufs = kind, d, {}
         self.sample = None              # gemm: {b: sorted output rows} compared (None: every valid row)
+        self.utts = None                # gemm: the utterances the reference covers (None: all of them)
         self.raw = {}                   # output field -> the reference before the output cast (f16 saturation checks)
 
     def add(self, field, values, dt, role="in", bits=None):
@@ -358,6 +359,8 @@ def gemm_ref(p, mut=None):
             n = len(p.bufs[f]["bits"])
             outs[f] = [np.zeros(n), np.zeros(n), np.zeros(n, bool)]
     for b in range(nb):
+        if p.utts is not None and b not in p.utts:
+            continue
         rows = valid_out_rows(d, b)
         if p.sample is not None:
             rows = np.intersect1d(rows, p.sample[b])
@@ -491,6 +494,8 @@ def _ds_ref(p, outs, mut):
     Xv, Wd, bd = p.bufs["X"]["v"], p.bufs["ds_W"]["v"], p.bufs["ds_bias"]["v"]
     o = outs["ds_out"]
     for b in range(d["nbatch"]):
+        if p.utts is not None and b not in p.utts:
+            continue
         rows = valid_out_rows(d, b)
         d1 = dict(d, ntaps=1, du=[0] * MAX_TAPS, dv=[0] * MAX_TAPS)
         acc, mag, g = _conv(d1, Xv, b * d["x_bs"], d["ldx"], Wd, 0, 0, K, b, rows, [0] * MAX_TAPS, K, N)
@@ -517,6 +522,8 @@ def _fused_ref(p, mut):
             outs[f] = [np.zeros(n), np.zeros(n), np.zeros(n, bool)]
     rinv = d["res_inv_slope"]
     for b in range(nb):
+        if p.utts is not None and b not in p.utts:
+            continue
         il = list(in_len)
         if mut == "in_len_minus1":
             il[b] = max(0, il[b] - 1)
@@ -1833,3 +1840,365 @@ def stage_struct(cs, dev):
                 raw = dev.upload(to_bits(pr[w], cs.dt))
                 assert lib.zvxk_pack_narrow(raw, pr["k"], C, a.W + a.woff[6 * j + 2 * t + q] * 1024) == 0
     return a, ptr, before
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# persistent kernels past a workgroup's first tile (tests/test_persistent_tiles_gpu.py, checked on the host by
+# tests/test_kernel_reference.py)
+#
+# Every kernel that sizes its grid to the chip walks several tiles or segments per workgroup at production shapes and exactly one
+# in the tables above.  The cases below are built at run time from the CU count so that every workgroup takes at least
+# PERSIST_TRIPS[kernel] units; the grid rule of each launcher is restated here (*_grid) and the walk of its kernel (strided_walk,
+# dealt_walk), and the number of trips is asserted on the host before anything is launched.
+#
+# What the shipped geometry allows.  resfuse_persist, narrowstage, conv2d_persist and conv2d_s2 tile every utterance over the common
+# M, so a case mixes utterances of one and of several tiles.  launch_resstream and launch_pairstream choose the segment length
+# S >= M nbatch / nwg: nsegs = nbatch ceil(M / S) < nbatch + nwg, so three segments per workgroup need nbatch > 2 nwg, hence S > 2 M
+# and ONE segment per utterance -- with these two launchers "several trips" and "several segments per utterance" exclude each
+# other, and no utterance can be exactly one segment long.  Their cases here are many one-segment utterances; the seam inside an
+# utterance stays with RESSTREAM_CASES / the pairstream_seam cases.
+# ------------------------------------------------------------------------------------------------------------------------------
+PERSIST_TRIPS = {"resfuse": 5, "conv2d_persist": 3, "conv2d_s2": 3, "narrowstage": 3, "resstream": 3, "pairstream": 3}
+RS_R = {(32, 3, 3): 64, (32, 7, 3): 64, (32, 11, 3): 64, (64, 3, 3): 32, (64, 7, 2): 32, (64, 7, 1): 64, (64, 11, 2): 32, (64, 11, 1): 64}
+PS_R = 128
+
+
+def _cdiv(a, b):
+    return -(-a // b)
+
+
+def resfuse_grid(C, k, M, nbatch, ncu):
+    """launch_resfuse_persist_c: tiles of BMO = BM1 - (k - 1) output rows, one workgroup per CU."""
+    bm1 = 64 if (C == 64 and k == 11) else (256 if C == 32 else 128)
+    rows = bm1 - (k - 1)
+    per = _cdiv(M, rows)
+    return dict(G=min(per * nbatch, ncu), per=per, rows=rows)
+
+
+def narrow_grid(C, M, nbatch, ncu):
+    per = _cdiv(M, NS_R[C])
+    return dict(G=min(per * nbatch, ncu * NS_WGPC[C]), per=per, rows=NS_R[C])
+
+
+def resstream_grid(C, k, npair, M, nbatch, ncu, seg_min=0):
+    """launch_rs: about one segment per CU, never shorter than 256 rows (seg_min = 0), whole row blocks."""
+    R = RS_R[(C, k, npair)]
+    S = _cdiv(M * nbatch, ncu)
+    if S < 2048:
+        S = 2048 if seg_min < 0 else max(S, seg_min if seg_min > 0 else 256)
+    S = _cdiv(S, R) * R
+    per = _cdiv(M, S)
+    return dict(G=min(per * nbatch, ncu), per=per, rows=S)
+
+
+def pairstream_grid(M, nbatch, ncu):
+    S = _cdiv(max(_cdiv(M * nbatch, ncu), 1024), PS_R) * PS_R
+    per = _cdiv(M, S)
+    return dict(G=min(per * nbatch, ncu), per=per, rows=S)
+
+
+def conv2d_grid(kind, C, M, nbatch, ncu):
+    """launch_conv2d_persist (C = 32: two workgroups per CU) / launch_conv2d_s2_variant: a multiple of 8 workgroups."""
+    bm = {("persist", 32): 384, ("persist", 64): 256, ("s2", 32): 256, ("s2", 64): 128}[(kind, C)]
+    wgpc = 2 if (kind, C) == ("persist", 32) else 1
+    per = _cdiv(M, bm)
+    G = max((wgpc * ncu) & ~7, 8)
+    if per * nbatch < G:
+        G = (per * nbatch + 7) & ~7
+    return dict(G=G, per=per, rows=bm)
+
+
+def strided_walk(g, nbatch, lens):
+    """resfuse_persist / narrowstage / resstream / pairstream: workgroup w takes units w, w + G, ...; unit t is tile (segment) t % per of
+    utterance t // per and is run when its first row lies inside the utterance.  -> per workgroup the (utterance, tile) it runs, in order."""
+    lens = np.asarray(lens)
+    out = []
+    for w in range(g["G"]):
+        t = np.arange(w, g["per"] * nbatch, g["G"])
+        b, j = t // g["per"], t % g["per"]
+        ok = j * g["rows"] < lens[b]
+        out.append(list(zip(b[ok].tolist(), j[ok].tolist())))
+    return out
+
+
+def dealt_walk(g, nbatch):
+    """conv2d_persist / conv2d_s2 (tile_of): rounds of G tiles, a round dealt in contiguous runs per XCD (workgroup = 8 slot + xcd); every
+    tile is run whatever the utterance's width."""
+    G, ntiles = g["G"], g["per"] * nbatch
+    out = [[] for _ in range(G)]
+    for base in range(0, ntiles, G):
+        n = min(ntiles - base, G)
+        per = (n + 7) >> 3
+        for w in range(G):
+            t = (w & 7) * per + (w >> 3)
+            if (w >> 3) < per and t < n:
+                out[w].append(divmod(base + t, g["per"]))
+    return out
+
+
+def walk_plan(walk, nbatch, long_utts, want_nan=True):
+    """From a walk: the least number of units a workgroup runs; which (long?, long?) successions occur inside a workgroup; two utterances
+    to fill with NaN (one that another utterance follows in its workgroup, one that is itself a later unit -- both short, with
+    neighbours that are not the other one); and the utterances a sampled float64 comparison must cover: every long one, whatever
+    follows a long one or comes next to a NaN one in a workgroup, and a spread of the rest."""
+    long_utts = set(long_utts)
+    trips = min(len(w) for w in walk)
+    follow, before, patterns = {}, {}, set()
+    for w in walk:
+        for (b0, _), (b1, _) in zip(w, w[1:]):
+            if b0 != b1:
+                follow.setdefault(b0, set()).add(b1)
+                before.setdefault(b1, set()).add(b0)
+                patterns.add((b0 in long_utts, b1 in long_utts))
+    nan = ()
+    if want_nan:
+        short = [b for b in range(nbatch) if b not in long_utts]
+        first = next(b for b in short if follow.get(b))
+        later = next(b for b in reversed(short) if before.get(b) and b != first and first not in before[b] | follow.get(b, set())
+                     and not (follow.get(b, set()) | before[b]) & (follow[first] | before.get(first, set())))
+        nan = (first, later)
+    sample = set(long_utts) | set(range(0, nbatch, max(1, nbatch // 24)))
+    for b in list(long_utts) + list(nan):
+        sample |= follow.get(b, set()) | before.get(b, set())
+    return dict(trips=trips, patterns=patterns, nan=nan, sample=sorted(sample - set(nan)))
+
+
+def _short_lens(n, hi=48):
+    return [1 + (i * 29) % hi for i in range(n)]
+
+
+def _coprime_per(G, lo=3):
+    from math import gcd
+    per = lo
+    while gcd(G, per) != 1:
+        per += 1
+    return per
+
+
+def _place_long(lens, G, per, rows, M):
+    """A few utterances of two or three units among the short ones, so that a workgroup runs long-then-long (A's first unit, then B's),
+    long-then-short and short-then-long; one utterance of exactly one unit.  Returns the long ones."""
+    A = 10
+    B, j = divmod(per * A + G, per)
+    assert B > A + 4 and B + 4 < len(lens)
+    lens[A] = min(M, 2 * rows + 1)                           # three units (two where M ends earlier)
+    lens[B] = min(M, j * rows + 33)                          # long enough for the unit that follows A's first one in its workgroup
+    lens[A + 2] = rows + 1                                   # two units, the second of one row
+    lens[B + 2] = min(M, 2 * rows + 17)
+    lens[A + 4] = rows                                       # exactly one unit
+    D = A + len(lens) // 2                                   # a long one met on a later trip: short-then-long
+    lens[D] = rows + 9
+    long_utts = [b for b in (A, B, A + 2, B + 2, D) if lens[b] > rows]
+    if j == 0:                                               # B's first unit follows: B is long by its length alone
+        lens[B] = min(M, rows + 33)
+        long_utts = sorted(set(long_utts) | {B})
+    return long_utts
+
+
+def resfuse_persist_cases(ncu):
+    """[(name, make_gemm keywords, variant id, meta)]: launch_resfuse_persist_c with at least 5 tiles per workgroup, both length paths
+    (LDS table for nbatch <= 128, scalar loads above), both 16-bit types, the four accumulator modes dealt over them."""
+    T = []
+
+    def epi(am, dt):
+        kw = dict(accum_mode=am, accum_dtype=dt) if am else {}
+        if am in (0, 1):
+            kw.update(act=ACT_LRELU, slope=0.1, out_scale=1 / 3 if am else 1.0)
+        else:
+            kw.update(has_out=False)
+        return kw
+    # ---- nbatch = 128, utterances of many tiles (C = 32, k = 3): lengths from the LDS table
+    C, k = 32, 3
+    rows = resfuse_grid(C, k, 1, 1, ncu)["rows"]
+    per = _cdiv(5 * ncu, 128) + 1
+    while True:
+        M = per * rows
+        lens = [M - (i * 37) % rows for i in range(128)]
+        for i, l in ((3, rows), (7, 1), (20, 2 * rows + 1), (21, 48), (64, rows + 1), (65, 17), (100, 3 * rows), (101, 5), (127, 30)):
+            lens[i] = l
+        g = resfuse_grid(C, k, M, 128, ncu)
+        long_utts = [b for b, l in enumerate(lens) if l > rows]
+        plan = walk_plan(strided_walk(g, 128, lens), 128, long_utts)
+        if plan["trips"] >= PERSIST_TRIPS["resfuse"] and g["G"] % per:
+            break
+        per += 1
+    for am in range(4):
+        dt = DT_BF16 if am % 2 == 0 else DT_F16
+        T.append((f"resfuse_persist_table_c32_k3_am{am}_{DT_NAME[dt]}",
+                  dict(dtype=dt, M=M, N=C, K=C, nbatch=128, lens=lens, taps=taps_1d(k), dil1=5, fused=1, **epi(am, dt)), 16, dict(plan, grid=g, long=long_utts)))
+    # ---- nbatch > 128, mostly one-tile utterances: lengths through scalar loads.  The tile count per utterance is coprime to the grid, so
+    #      that every workgroup meets first tiles; tiles past a short utterance's end are the ones the walk skips
+    for C, k, dil, ams in ((32, 3, 3, (0, 1, 2, 3)), (64, 7, 1, (1, 2)), (64, 11, 1, (3, 0))):
+        rows = resfuse_grid(C, k, 1, 1, ncu)["rows"]
+        per = _coprime_per(ncu)
+        M = (per - 1) * rows + 40
+        nbatch = 5 * ncu + 9
+        while True:
+            lens = _short_lens(nbatch)
+            g = resfuse_grid(C, k, M, nbatch, ncu)
+            long_utts = _place_long(lens, g["G"], per, rows, M)
+            plan = walk_plan(strided_walk(g, nbatch, lens), nbatch, long_utts)
+            if plan["trips"] >= PERSIST_TRIPS["resfuse"]:
+                break
+            nbatch += ncu // 4
+        for i, am in enumerate(ams):
+            dt = DT_F16 if (am + (C == 32)) % 2 == 0 else DT_BF16
+            T.append((f"resfuse_persist_sload_c{C}_k{k}_am{am}_{DT_NAME[dt]}",
+                      dict(dtype=dt, M=M, N=C, K=C, nbatch=nbatch, lens=lens, taps=taps_1d(k), dil1=dil, fused=1, **epi(am, dt)), 16 if C == 32 else 17,
+                      dict(plan, grid=g, long=long_utts)))
+    return T
+
+
+def pairstream_persist_cases(ncu):
+    """launch_pairstream with at least 3 segments per workgroup: 3 nwg + 7 one-segment utterances (see the section comment)."""
+    T = []
+    nbatch, M = 3 * ncu + 7, 48
+    lens = _short_lens(nbatch)
+    lens[10], lens[11] = M, M - 1
+    g = pairstream_grid(M, nbatch, ncu)
+    assert pairstream_grid(M, 1, ncu)["rows"] == g["rows"]                    # the alone launch cuts the same segments
+    plan = walk_plan(strided_walk(g, nbatch, lens), nbatch, [])
+    for i, (k, dil) in enumerate(((3, 1), (7, 3), (11, 5))):
+        for dt in (DT_BF16, DT_F16):
+            am = (i + (2 if dt == DT_F16 else 0)) % 4
+            kw = dict(pair_seam_kw(dt, k, dil, am), M=M, nbatch=nbatch, lens=lens)
+            T.append((f"pairstream_persist_k{k}_d{dil}_am{am}_{DT_NAME[dt]}", kw, 23, dict(plan, grid=g, long=[])))
+    return T
+
+
+K33 = dict(taps=[t % 3 - 1 for t in range(9)], du=[t // 3 - 1 for t in range(9)])
+
+
+def conv2d_persist_cases(ncu):
+    """conv2d_persist (both epilogue forms, C = 32 / 64, the fused SE pool) and conv2d_s2 (with and without the fused shortcut) with at
+    least 3 tiles per workgroup and a short last round: maps of two tiles each, mostly 1 to 5 columns wide, a few as wide as the map."""
+    T = []
+
+    def add(name, vid, kind, C, hin, win, pool=False, **kw):
+        two_d = kind == "s2"
+        wout = (win - 1) // 2 + 1 if two_d else win
+        M = ((hin - 1) // 2 + 1) * wout if two_d else hin * win
+        g1 = conv2d_grid(kind, C, M, 1 << 20, ncu)
+        nbatch = _cdiv(3 * g1["G"] + 5, g1["per"])
+        g = conv2d_grid(kind, C, M, nbatch, ncu)
+        assert g["per"] == 2 and g["G"] == g1["G"]
+        lens = [1 + (i * 7) % 5 for i in range(nbatch)]
+        A = 10
+        B = (2 * A + g["G"]) // 2
+        wide = [A, B, A + 3, B + 3, A + nbatch // 2]          # (the last one is met on a later trip: narrow-then-wide)
+        for b in wide:
+            lens[b] = win - 1
+        lens[A + 3] = win - 2
+        plan = walk_plan(dealt_walk(g, nbatch), nbatch, wide)
+        kw = dict(dtype=DT_BF16, M=M, N=2 * C if two_d else C, K=C, nbatch=nbatch, lens=lens, wout=wout, hin=hin, win=win, **K33, **kw)
+        T.append((name, kw, vid, dict(plan, grid=g, long=wide, pool=pool, kind=kind)))
+    add("conv2d_persist_c32_relu_bn", 26, "persist", 32, 6, 66, flat=True, bias_mode=0, post=True, act=ACT_RELU)
+    add("conv2d_persist_c32_bias", 26, "persist", 32, 6, 66, flat=True, bias_mode=1)
+    add("conv2d_persist_c32_bias_pool", 26, "persist", 32, 6, 66, pool=True, flat=True, bias_mode=1)
+    add("conv2d_persist_c64_relu_bn", 27, "persist", 64, 4, 66, flat=True, bias_mode=0, post=True, act=ACT_RELU)
+    add("conv2d_persist_c64_bias", 27, "persist", 64, 4, 66, flat=True, bias_mode=1)
+    add("conv2d_s2_ds_c32", 28, "s2", 32, 26, 41, stride=2, bias_mode=0, post=True, act=ACT_RELU, ds=True)
+    add("conv2d_s2_c64", 29, "s2", 64, 18, 31, stride=2, bias_mode=0, post=True, act=ACT_RELU)
+    return T
+
+
+def gemm_persist_cases(ncu):
+    return resfuse_persist_cases(ncu) + pairstream_persist_cases(ncu) + conv2d_persist_cases(ncu)
+
+
+def build_persist_gemm(entry):
+    """The Problem of a *_persist_cases entry: the NaN utterances hold NaN in every row, the reference covers meta['sample']."""
+    name, kw, vid, meta = entry
+    p = make_gemm(name, 0, **kw)
+    d = p.d
+    X = p.bufs["X"]["v"].reshape(d["nbatch"], -1)
+    for b in meta["nan"]:
+        X[b] = np.nan
+    p.utts = set(meta["sample"])                             # whole utterances are sampled, every valid row of each
+    p.sample = None
+    p.nan_utts = tuple(meta["nan"])
+    return p
+
+
+def pool_ref(p, b):
+    """conv2d_persist's fused squeeze-excite pool for utterance b: partial[s][n] = the sum over the valid positions (row < M, column < width)
+    of rows [96 s, 96 s + 96) of the f32 convolution results BEFORE the bias, s < 4 ntm (C = 32: four waves of 96 rows per 384-row tile),
+    and its bound: the accumulation bound of every summand plus an f32 sum of up to 96 of them in any order."""
+    d = p.d
+    rows = valid_out_rows(d, b)
+    acc, mag, g = _conv(d, p.bufs["X"]["v"], b * d["x_bs"], d["ldx"], p.bufs["W"]["v"], 0, d["w_ts"], d["ldw"], b, rows, d["dv"], d["K"], d["N"])
+    S = 4 * _cdiv(d["M"], 384)
+    ref, tol = np.zeros((S, d["N"])), np.zeros((S, d["N"]))
+    eacc = 0.0 if exact_f32(mag, g) else 2 * d["ntaps"] * d["K"] * U
+    for s in range(S):
+        m = (rows >= 96 * s) & (rows < 96 * s + 96)
+        ref[s] = acc[m].sum(axis=0)
+        tol[s] = eacc * mag[m].sum(axis=0) + 2 * 96 * U * np.abs(acc[m]).sum(axis=0)
+    return ref, tol
+
+
+def chain_persist_cases(ncu):
+    """[(name, make_chain keywords, variant id, meta)] for launch_narrowstage (utterances of one to three tiles over a tile count coprime
+    to the grid) and launch_resstream (one-segment utterances, every form of the launcher), at least 3 units per workgroup."""
+    T = []
+    for C, dt in ((16, DT_BF16), (16, DT_F16), (8, DT_F16), (8, DT_BF16)):
+        R = NS_R[C]
+        G = ncu * NS_WGPC[C]
+        per = _coprime_per(G)
+        M = (per - 1) * R + 90
+        nbatch = 3 * G + 9
+        while True:
+            lens = _short_lens(nbatch)
+            g = narrow_grid(C, M, nbatch, ncu)
+            long_utts = _place_long(lens, g["G"], per, R, M)
+            plan = walk_plan(strided_walk(g, nbatch, lens), nbatch, long_utts)
+            if plan["trips"] >= PERSIST_TRIPS["narrowstage"]:
+                break
+            nbatch += G // 4
+        T.append((f"narrowstage_persist_c{C}_{DT_NAME[dt]}", dict(kind="narrowstage", dt=dt, C=C, blocks=[(k, (1, 3, 5)) for k in (3, 7, 11)], M=M,
+                                                                 lens=lens, nan_utts=plan["nan"]), 24 if C == 16 else 25, dict(plan, grid=g, long=long_utts)))
+    nbatch, M = 3 * ncu + 7, 64
+    lens = _short_lens(nbatch)
+    lens[10], lens[11] = M, M - 1
+    for i, (C, k, dils) in enumerate(RS_FORMS):
+        dt = DT_BF16 if i % 2 == 0 else DT_F16
+        am = (i + (2 if i >= 4 else 0)) % 4
+        g = resstream_grid(C, k, len(dils), M, nbatch, ncu)
+        assert resstream_grid(C, k, len(dils), M, 1, ncu)["rows"] == g["rows"]     # the alone launch cuts the same segments
+        plan = walk_plan(strided_walk(g, nbatch, lens), nbatch, [])
+        T.append((f"resstream_persist_c{C}_k{k}_np{len(dils)}_am{am}_{DT_NAME[dt]}",
+                  dict(kind="resstream", dt=dt, C=C, blocks=[(k, dils)], M=M, lens=lens, nan_utts=plan["nan"], ld_pad=8 if dt == DT_F16 else 0, **_rs_epi(am)),
+                  20 if C == 32 else 21, dict(plan, grid=g, long=[])))
+    return T
+
+
+def sub_chain(cs, utts):
+    """The ChainCase of utterances `utts` alone, cropped to their longest (utterances do not see each other)."""
+    utts = list(utts)
+    Ms = max(cs.lens[b] for b in utts)
+    kw = dict(cs.__dict__)
+    kw.update(X=cs.X[utts, :Ms], lens=[cs.lens[b] for b in utts], xs=None if cs.xs is None else cs.xs[utts, :Ms], nan_utts=(), M=Ms)
+    return ChainCase(**kw)
+
+
+# ---- the resampler's launch geometry (launch_resample_poly / resample_geometry_of) ----
+def resample_geometry(lib, rate_in, rate_out, B, out_max):
+    """The shim's dry run: dict(L, M, T, pitch, tile, tpb, xcap, lds, fits)."""
+    lib.zvxk_resample_geometry.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_long, ctypes.POINTER(ctypes.c_int)]
+    g = (ctypes.c_int * 8)()
+    ok = lib.zvxk_resample_geometry(rate_in, rate_out, B, out_max, g)
+    d = dict(zip(("L", "M", "T", "pitch", "tile", "tpb", "xcap", "lds"), (int(v) for v in g)))
+    d["fits"] = bool(ok)
+    return d
+
+
+def resample_geometry_ref(L, M, T, pitch, B, out_max):
+    """The rule restated: the bank [L][pitch] (padded to 4 floats) and one tile's input span share at most 96 KiB; the tile halves from
+    1024 until they do; tpb = min(8, max(1, tiles B / 2048))."""
+    nbank = (L * pitch + 3) & ~3
+    cap = lambda t: ((t - 1) * M // L + T + 12) & ~3
+    tile = 1024
+    while tile > 4 and (nbank + cap(tile)) * 4 > 96 * 1024:
+        tile >>= 1
+    tiles = _cdiv(out_max, tile)
+    return dict(tile=tile, tpb=min(8, max(1, tiles * B // 2048)), xcap=cap(tile), lds=(nbank + cap(tile)) * 4)

@@ -236,6 +236,21 @@ int zvxk_fc_rows(const float* x, int ldx, const float* w, int ldw, const float* 
     ZK_(launch_fc_rows(x, ldx, w, ldw, bias, out, ldo, B, N, K, nullptr));
 }
 #undef ZK_
+// The resampler's launch geometry for rate_in -> rate_out, B rows, out_max outputs in the longest row, as the library designs the bank
+// (L, M by the gcd, half = 10 max(L, M), T = ceil((2 half + 1) / L), resample_bank_pitch) and as launch_resample_poly decides it; nothing
+// is launched.  g[8] = {L, M, T, pitch, tile, tpb, xcap, LDS bytes}.  1: fits, 0: exceeds the LDS of a workgroup.
+int zvxk_resample_geometry(int rate_in, int rate_out, int B, long out_max, int* g) {
+    int x = rate_in, y = rate_out;
+    while (y) { const int t = x % y; x = y; y = t; }
+    ResampleArgs a{};
+    a.L = rate_out / x; a.M = rate_in / x; a.B = B; a.out_max = out_max;
+    if (a.L == 1 && a.M == 1) { a.half = 0; a.T = 1; a.pitch = 2; }
+    else { a.half = 10 * (a.L > a.M ? a.L : a.M); a.T = (2 * a.half + 1 + a.L - 1) / a.L; a.pitch = resample_bank_pitch(a.L, a.M, a.T); }
+    ResampleGeometry r;
+    const bool ok = resample_geometry_of(a, &r);
+    g[0] = a.L; g[1] = a.M; g[2] = a.T; g[3] = a.pitch; g[4] = r.tile; g[5] = r.tpb; g[6] = r.xcap; g[7] = (int)r.lds;
+    return ok ? 1 : 0;
+}
 // the device's own math functions over given arguments (the per-call ulp allowances of tests/ops_ref.py were measured with it; it
 // touches no code under test).  fn: 0 expf, 1 tanhf, 2 logf, 3 sqrtf, 4 1 / x
 int zvxk_math_probe(int fn, const float* in, float* out, int n) {

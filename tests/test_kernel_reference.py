@@ -240,6 +240,82 @@ def test_chain_exact_share_and_mutations(entry):
     assert not weak, f"{entry[0]}: mutations within the bound: {weak}"
 
 
+# ------------------------------------------------------------------------------------------------------------------------------
+# the persistent-tile cases (tests/test_persistent_tiles_gpu.py) on the host
+# ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("ncu", [64, 256, 304])
+def test_persistent_case_builders_make_the_trips_they_claim(ncu):
+    """For every CU count the builders give every workgroup at least PERSIST_TRIPS units -- recounted here from the restated grid rule and
+    walk, independently of the builder's own search --, the long-then-short, short-then-long and long-then-long successions wherever a
+    case has long utterances, an utterance of exactly one unit and units the walk skips, both length paths of resfuse_persist, and NaN
+    utterances whose neighbours in a workgroup are compared against float64."""
+    entries = K.gemm_persist_cases(ncu) + K.chain_persist_cases(ncu)
+    assert [e[0] for e in entries] == [e[0] for e in K.gemm_persist_cases(256) + K.chain_persist_cases(256)]      # the test ids hold on any device
+    seen = set()
+    for name, kw, vid, meta in entries:
+        kernel = next(k for k in K.PERSIST_TRIPS if name.startswith(k))
+        seen.add(kernel)
+        lens, g, M = kw["lens"], meta["grid"], kw["M"]
+        nb = len(lens)
+        if kernel.startswith("conv2d"):
+            assert g == K.conv2d_grid(meta["kind"], kw["K"], M, nb, ncu)
+            walk = K.dealt_walk(g, nb)
+            assert sorted(t for w in walk for t in w) == [(b, j) for b in range(nb) for j in range(g["per"])]      # every tile once
+            assert len(walk[-1]) == 3 and len(walk[0]) == 4                                                        # a short last round
+        else:
+            want = dict(resfuse=lambda: K.resfuse_grid(kw["N"], len(kw["taps"]), M, nb, ncu), pairstream=lambda: K.pairstream_grid(M, nb, ncu),
+                        narrowstage=lambda: K.narrow_grid(kw["C"], M, nb, ncu),
+                        resstream=lambda: K.resstream_grid(kw["C"], kw["blocks"][0][0], len(kw["blocks"][0][1]), M, nb, ncu))[kernel]()
+            assert g == want and g["G"] == ncu * (K.NS_WGPC[kw["C"]] if kernel == "narrowstage" else 1)
+            walk = K.strided_walk(g, nb, lens)
+            run = sorted(t for w in walk for t in w)
+            assert run == [(b, j) for b in range(nb) for j in range(g["per"]) if j * g["rows"] < lens[b]]
+            if g["per"] > 1:
+                assert len(run) < nb * g["per"] and g["rows"] in lens                      # units the walk skips; an utterance of exactly one unit
+        assert min(len(w) for w in walk) == meta["trips"] >= K.PERSIST_TRIPS[kernel], name
+        if meta["long"]:
+            assert {(True, False), (False, True), (True, True)} <= meta["patterns"], name
+        first, later = meta["nan"]
+        pos = {b: (w, i) for w in walk for i, (b, j) in enumerate(w) if b in meta["nan"]}
+        w, i = pos[first]
+        assert i + 1 < len(w) and w[i + 1][0] in meta["sample"], name                    # another utterance follows the first NaN one ...
+        w, i = pos[later]
+        assert i >= 1 and w[i - 1][0] in meta["sample"], name                            # ... and the second is itself a later unit
+        assert set(meta["long"]) <= set(meta["sample"]) and not set(meta["nan"]) & set(meta["sample"])
+        for w in walk:
+            for (b0, _), (b1, _) in zip(w, w[1:]):
+                assert b0 not in meta["long"] or b1 in meta["sample"] or b1 in meta["nan"], name
+        if name.startswith("resfuse_persist_table"):
+            assert nb <= 128 and min(lens[b] for b in meta["long"]) > g["rows"] and len(meta["long"]) > 100
+        if name.startswith("resfuse_persist_sload"):
+            assert nb > 128
+    assert seen == set(K.PERSIST_TRIPS)
+    # the accumulator modes and both 16-bit types per kernel family
+    for fam in ("resfuse_persist_table", "resfuse_persist_sload", "pairstream_persist", "resstream_persist"):
+        names = [e[0] for e in entries if e[0].startswith(fam)]
+        assert {n.split("_am")[1][0] for n in names} == set("0123"), fam
+        assert {n.rsplit("_", 1)[1] for n in names} == {"bf16", "f16"}, fam
+
+
+def test_resample_geometry_rule_matches_the_launcher():
+    """kernel_ref.resample_geometry_ref restates launch_resample_poly's decision (tile, tiles per workgroup, staged span, LDS bytes); the
+    shim's dry run reports what the launcher decides.  Equal over the rate pairs of the resampler tests and over batch and row sizes on
+    both sides of every threshold: tpb = 1 .. 8, tile 1024 / 512 / 256, LDS on both sides of 64 KiB."""
+    _needs_lib()
+    lib = K.load_ktest()
+    seen_tpb, seen_tile, seen_big = set(), set(), set()
+    for ri, ro in [(22050, 48000), (48000, 22050), (22050, 8000), (16000, 22050), (22050, 22050), (22050, 44100), (192000, 8000), (192000, 6000),
+                   (192000, 4000), (4000, 192000)]:
+        for B in (1, 2, 5, 64, 192, 256, 1000):
+            for out_max in (1, 1023, 1024, 1025, 4096, 65536, 65537, 1 << 20):
+                g = K.resample_geometry(lib, ri, ro, B, out_max)
+                want = K.resample_geometry_ref(g["L"], g["M"], g["T"], g["pitch"], B, out_max)
+                assert g["fits"] and {k: g[k] for k in want} == want, (ri, ro, B, out_max, g, want)
+                assert g["T"] + 1 <= g["pitch"] <= g["T"] + 8
+                seen_tpb.add(g["tpb"]); seen_tile.add(g["tile"]); seen_big.add(g["lds"] > 64 * 1024)
+    assert seen_tpb == set(range(1, 9)) and {1024, 512, 256} <= seen_tile and seen_big == {False, True}
+
+
 def _dense_rms_entries():
     return [e for e in K.NARROW_CASES if e[1]["data"] == "dense"] + K.PAIR_DENSE_CASES
 

@@ -220,7 +220,8 @@ def test_rows_are_independent(rate_in, rate_out):
     got, c = sub(perm)
     for j, i in enumerate(perm):
         assert c[j] == cnt[i] and np.array_equal(got[j, :c[j]], base[i, :cnt[i]]), (i, j)
-    # rows dropped: without the long row the grid and the tiles per workgroup change, the bits do not
+    # rows dropped: without the long row the grid changes, the bits do not.  (The tiles per workgroup do NOT change here: about 30 tiles in
+    # the whole call, tpb = min(8, tiles * B / 2048) is 1 on both sides; test_several_tiles_per_workgroup below is the one that runs tpb >= 2)
     keep = [9, 2, 5, 0]
     got, c = sub(keep)
     for j, i in enumerate(keep):
@@ -242,6 +243,103 @@ def test_rows_are_independent(rate_in, rate_out):
     pcm, _ = ctx.resample_rows(samples, rate_in, rate_out, wins, pcm16=True)
     for b in range(B):
         assert pcm[b].dtype == np.int16 and np.array_equal(pcm[b], R.pcm16(base[b, :cnt[b]].view(np.float32))), b
+
+
+# ------------------------------------------------------------------------------------------------ several tiles per workgroup
+OUT_LONG = 65536                                             # outputs of the longest row: 64 tiles of 1024
+_ktest = []
+
+
+def geometry(rate_in, rate_out, B, out_max):
+    """What the library decides for such a call, by the shim's dry run (nothing is launched), held to the rule restated in kernel_ref."""
+    import kernel_ref as K
+    if not _ktest:
+        _ktest.append(K.load_ktest())
+    g = K.resample_geometry(_ktest[0], rate_in, rate_out, B, out_max)
+    L, M = R.pair(rate_in, rate_out)
+    assert (g["L"], g["M"]) == (L, M) and g["T"] == (R.taps_per_output(rate_in, rate_out) if L != M else 1) and g["fits"]
+    want = K.resample_geometry_ref(L, M, g["T"], g["pitch"], B, out_max)
+    assert {k: g[k] for k in want} == want, (g, want)
+    return g
+
+
+def ragged_rows(rate_in, rate_out, B, tile, tpb):
+    """B rows for a call whose workgroups take tpb tiles of `tile` outputs each -> (samples, cnt for the rows call, natural counts).  Row 0 is
+    the longest (it alone sizes the grid), row 1 ends inside a workgroup's second tile, row 2 exactly on a tpb * tile boundary, row 3 is a
+    single sample, row 4 puts one output into the next workgroup, row 5 ends in a workgroup's last tile; the rest are short, every 16th
+    up to three workgroups long."""
+    L, M = R.pair(rate_in, rate_out)
+    span = tpb * tile
+    rng = np.random.default_rng(23)
+    want = [None, tile + 300, span, None, span + 1, 2 * span + (tpb - 1) * tile + 5]
+    want += [int(rng.integers(1, 3 * span if b % 16 == 0 else 2 * tile)) for b in range(len(want), B)]
+    n = [ceil_div(c * M, L) if c is not None else 0 for c in want]
+    n[0], n[3] = OUT_LONG * M // L, 1
+    samples = [rng.uniform(-1, 1, k).astype(np.float32) for k in n]
+    nat = [ceil_div(k * L, M) for k in n]
+    cnt = [want[b] if b in (2, 4, 5) else nat[b] for b in range(B)]            # (the rows call cuts rows 2, 4, 5 to the count they are here for)
+    assert all(c <= v for c, v in zip(cnt, nat)) and max(nat) == nat[0] and ceil_div(nat[0], tile) == OUT_LONG // tile
+    assert tile < cnt[1] < 2 * tile and cnt[2] == span and len(samples[3]) == 1 and cnt[4] == span + 1
+    for s in samples:
+        s.setflags(write=False)
+    return samples, cnt, nat
+
+
+@pytest.mark.parametrize("B", [64, 256])
+@pytest.mark.parametrize("rate_in,rate_out", [(22050, 48000), (48000, 22050)])
+def test_several_tiles_per_workgroup(rate_in, rate_out, B):
+    """k_resample_poly's loop over the tiles of a workgroup (tpb = min(8, tiles * B / 2048) >= 2 needs tiles * B >= 4096): 64 / 256 ragged rows
+    of up to 65536 outputs, 22050 -> 48000 (the strided up-conversion layout) and 48000 -> 22050 (vector stores), f32 and int16.  Every
+    row is bit-equal to the same row converted alone (64 tiles x 1 row: tpb = 1), in the rows call (nothing outside [0, cnt_b) written)
+    and in the one-window call (zeros up to the longest row); two rows are held to the float64 reference."""
+    ctx = TR.ctx_for("tiny")
+    g = geometry(rate_in, rate_out, B, OUT_LONG)
+    tile, tpb = g["tile"], g["tpb"]
+    assert tile == 1024 and tpb >= 2 and (B != 256 or tpb == 8), g
+    assert geometry(rate_in, rate_out, 1, OUT_LONG)["tpb"] == 1             # the reference call of every row
+    samples, cnt, nat = ragged_rows(rate_in, rate_out, B, tile, tpb)
+    assert geometry(rate_in, rate_out, B, max(nat))["tpb"] == tpb and geometry(rate_in, rate_out, B, max(cnt))["tpb"] == tpb
+    print(f"SPEC resample_tpb_{rate_in}_{rate_out}_B{B} tile {tile} tpb {tpb} xcap {g['xcap']} lds {g['lds']} tiles/workgroup {tpb}")
+    wins = [(0, 0, c, 0) for c in cnt]
+    x, n = TR.padded(samples)
+    for pcm16 in (False, True):
+        want = [alone(ctx, s, w, rate_in, rate_out, pcm16) for s, w in zip(samples, wins)]
+        if not pcm16:
+            for b in (0, 1):
+                ref, A = R.resample_window(samples[b], rate_in, rate_out, 0, 0, cnt[b], want_mag=True)
+                e, lim = np.abs(want[b].view(np.float32).astype(np.float64) - ref), R.bound(rate_in, rate_out, A)
+                print(f"SPEC resample_tpb_{rate_in}_{rate_out}_B{B} row {b} worst err/bound {float((e / np.maximum(lim, 1e-300)).max()):.3f}")
+                assert np.all(e <= lim), b
+        # the rows call: a window per row, nothing behind a row's own count
+        check_block(rows_host(ctx, samples, wins, rate_in, rate_out, cnt, pcm16=pcm16), want, cnt, f"rows call pcm16={pcm16}")
+        # the one-window call: every row to the end of its signal, zeros from there to the longest row
+        stride = max(nat) + 37
+        out = out_rows(B - 1, stride, pcm16)
+        ol = np.zeros(B, np.int32)
+        assert TR.raw_resample(ctx, x, n, rate_in, rate_out, out, stride, _lib.ZVX_PCM16 if pcm16 else 0, ol) == 0, err(ctx)
+        assert list(ol) == nat
+        for b in range(B):
+            whole = want[b] if nat[b] == cnt[b] else alone(ctx, samples[b], (0, 0, -1, 0), rate_in, rate_out, pcm16)
+            assert np.array_equal(out[b, :nat[b]], whole), (b, "one-window call differs from the row alone")
+            assert not out[b, nat[b]:max(nat)].any(), (b, "no zeros behind the row")
+            assert np.all(out[b, max(nat):] == (S16 if pcm16 else S32)), (b, "written past the longest row")
+
+
+@pytest.mark.parametrize("rate_in,rate_out", [(192000, 8000), (192000, 6000)])
+def test_decimation_past_22_to_1_halves_the_tile(rate_in, rate_out):
+    """M / L = 24 and 32: the input span of 1024 outputs no longer fits beside the bank, the launcher halves the tile; at 32 : 1 the LDS
+    passes 64 KiB (the opt-in path).  A row of three tiles and a few samples against the float64 reference."""
+    ctx = TR.ctx_for("tiny")
+    L, M = R.pair(rate_in, rate_out)
+    n_out = 3 * 512 + 77
+    g = geometry(rate_in, rate_out, 1, n_out)
+    assert g["tile"] == 512 and g["tpb"] == 1 and (g["lds"] > 64 * 1024) == (M == 32) and g["lds"] <= 96 * 1024, g
+    print(f"SPEC resample_decimate_{rate_in}_{rate_out} tile {g['tile']} tpb {g['tpb']} xcap {g['xcap']} lds {g['lds']}")
+    s = np.random.default_rng(29).uniform(-1, 1, n_out * M - 5).astype(np.float32)
+    got = alone(ctx, s, (0, 0, -1, 0), rate_in, rate_out)
+    assert len(got) == n_out
+    TR.check_float(got.view(np.float32), s, rate_in, rate_out, f"SPEC resample_decimate_{rate_in}_{rate_out}")
+    assert np.array_equal(alone(ctx, s, (0, 0, -1, 0), rate_in, rate_out, True), R.pcm16(got.view(np.float32)))
 
 
 # ------------------------------------------------------------------------------------------------ errors

@@ -125,29 +125,6 @@ double bessel_i0(double x) {
     for (int k = 1; k < 64; k++) { t *= (x / (2.0 * k)) * (x / (2.0 * k)); s += t; if (t < 1e-20 * s) break; }
     return s;
 }
-// The row pitch of the bank in LDS: lanes of a wave read bank[p_i][t] with one t and phases p_i stepping by M mod L (up-conversion:
-// neighbouring lanes take neighbouring outputs) or 4 M mod L (down-conversion: 4 consecutive outputs per lane), 32 lanes per
-// ds_read_b32 group over 32 banks.  The worst pile-up over all start phases is counted for each pitch in
-// [T + 1, T + 8] and the smallest sum wins (an odd pitch spreads distinct phases over the banks; which odd one depends on L and M).
-int rs_pick_pitch(int L, int M, int T) {
-    const int step = (int)(((M < L ? 1L : 4L) * M) % L);
-    int best = T + 1; long best_cost = -1;
-    for (int pitch = T + 1; pitch <= T + 8; pitch++) {
-        long cost = 0;
-        for (int p0 = 0; p0 < L; p0++) {
-            int owner[32][8], n[32] = {0}, worst = 1;
-            for (int i = 0, p = p0; i < 32; i++, p = (p + step) % L) {
-                const int bank = (int)(((long)p * pitch) % 32);
-                bool seen = false;
-                for (int j = 0; j < n[bank] && j < 8; j++) seen |= owner[bank][j] == p;      // one address: a broadcast
-                if (!seen) { if (n[bank] < 8) owner[bank][n[bank]] = p; n[bank]++; worst = std::max(worst, n[bank]); }
-            }
-            cost += worst;
-        }
-        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = pitch; }
-    }
-    return best;
-}
 }  // namespace
 
 // The filter of include/zvx.h, designed in double and rounded once to f32, as the polyphase bank launch_resample_poly reads
@@ -173,7 +150,7 @@ const zvx_ctx::RsBank& rs_bank(zvx_ctx* c, int L, int M) {
             sum += h[i];
         }
         for (double& v : h) v = v / sum * L;
-        bk.half = half; bk.T = (N + L - 1) / L; bk.pitch = rs_pick_pitch(L, M, bk.T);
+        bk.half = half; bk.T = (N + L - 1) / L; bk.pitch = resample_bank_pitch(L, M, bk.T);
         host.assign(((size_t)L * bk.pitch + 3) & ~(size_t)3, 0.0f);
         for (int p = 0; p < L; p++) {
             const int joff = (half - p) / L;

@@ -1369,7 +1369,7 @@ __global__ __launch_bounds__(256) void k_resample_poly(const ResampleArgs a, int
     // which 4 outputs of a tile a lane takes.  Up-conversion (M < L): tid + 256 q -- neighbouring lanes take neighbouring outputs, whose input
     // windows start at most one sample apart (LDS reads of one address broadcast) and whose phases step by M mod L; each lane stores 4 bytes of
     // a 256-byte run.  Down-conversion: 4 tid + q -- a lane's windows start 4 M / L samples after its neighbour's, and the lane stores its
-    // 4 outputs as one vector.  The bank's pitch is chosen for the same step (host_post.hip, rs_pick_pitch); an output's sum does not depend on it.
+    // 4 outputs as one vector.  The bank's pitch is chosen for the same step (resample_bank_pitch below); an output's sum does not depend on it.
     const bool strided = a.M < a.L;
     const int step = strided ? 256 * a.M : a.M, dk = step / a.L, dp = step % a.L;
     auto put = [&](long i, float v) {
@@ -1436,23 +1436,52 @@ __global__ __launch_bounds__(256) void k_resample_poly(const ResampleArgs a, int
         }
     }
 }
-// false (nothing launched): the bank and one tile's input span do not fit the LDS a workgroup may have
-bool launch_resample_poly(const ResampleArgs& a, hipStream_t s) {
-    if (a.B <= 0 || a.out_max <= 0) return true;
+// The row pitch of the bank in LDS: lanes of a wave read bank[p_i][t] with one t and phases p_i stepping by M mod L (up-conversion:
+// neighbouring lanes take neighbouring outputs) or 4 M mod L (down-conversion: 4 consecutive outputs per lane), 32 lanes per
+// ds_read_b32 group over 32 banks.  The worst pile-up over all start phases is counted for each pitch in
+// [T + 1, T + 8] and the smallest sum wins (an odd pitch spreads distinct phases over the banks; which odd one depends on L and M).
+int resample_bank_pitch(int L, int M, int T) {
+    const int step = (int)(((M < L ? 1L : 4L) * M) % L);
+    int best = T + 1; long best_cost = -1;
+    for (int pitch = T + 1; pitch <= T + 8; pitch++) {
+        long cost = 0;
+        for (int p0 = 0; p0 < L; p0++) {
+            int owner[32][8], n[32] = {0}, worst = 1;
+            for (int i = 0, p = p0; i < 32; i++, p = (p + step) % L) {
+                const int bank = (int)(((long)p * pitch) % 32);
+                bool seen = false;
+                for (int j = 0; j < n[bank] && j < 8; j++) seen |= owner[bank][j] == p;      // one address: a broadcast
+                if (!seen) { if (n[bank] < 8) owner[bank][n[bank]] = p; n[bank]++; worst = std::max(worst, n[bank]); }
+            }
+            cost += worst;
+        }
+        if (best_cost < 0 || cost < best_cost) { best_cost = cost; best = pitch; }
+    }
+    return best;
+}
+// The launch geometry, decided from (L, M, T, pitch, B, out_max) alone.  false: the bank and one tile's input span do not fit the LDS a
+// workgroup may have.
+bool resample_geometry_of(const ResampleArgs& a, ResampleGeometry* g) {
     const size_t nbank = ((size_t)a.L * a.pitch + 3) & ~(size_t)3;
     // tile: outputs per pass (a multiple of 4, 1024 where the span fits); its input span is at most (tile - 1) M / L + T + 2 samples, + 3 for
     // the aligned start, rounded up to whole float4s
     int tile = 1024;
     auto cap = [&](int t) { return (int)((((long)(t - 1) * a.M) / a.L + a.T + 2 + 3 + 4 + 3) & ~3L); };
     while (tile > 4 && (nbank + cap(tile)) * 4 > 96 * 1024) tile >>= 1;
-    const int xcap = cap(tile);
-    const size_t lds = (nbank + xcap) * 4;
-    if (lds > 160 * 1024) return false;
-    if (lds > 64 * 1024 && !lds_opt_in((const void*)k_resample_poly)) return false;
+    g->tile = tile; g->xcap = cap(tile);
+    g->lds = (long)((nbank + g->xcap) * 4);
     // the bank is read once per workgroup: long rows take several tiles per workgroup, short ones keep the grid wide
-    const long tiles = (a.out_max + tile - 1) / tile;
-    int tpb = (int)std::min<long>(8, std::max<long>(1, tiles * a.B / 2048));
-    hipLaunchKernelGGL(k_resample_poly, dim3((unsigned)((tiles + tpb - 1) / tpb), a.B), dim3(256), lds, s, a, tile, tpb, xcap);
+    g->tiles = (a.out_max + tile - 1) / tile;
+    g->tpb = (int)std::min<long>(8, std::max<long>(1, g->tiles * a.B / 2048));
+    return g->lds <= 160 * 1024;
+}
+// false (nothing launched): the bank and one tile's input span do not fit the LDS a workgroup may have
+bool launch_resample_poly(const ResampleArgs& a, hipStream_t s) {
+    if (a.B <= 0 || a.out_max <= 0) return true;
+    ResampleGeometry g;
+    if (!resample_geometry_of(a, &g)) return false;
+    if (g.lds > 64 * 1024 && !lds_opt_in((const void*)k_resample_poly)) return false;
+    hipLaunchKernelGGL(k_resample_poly, dim3((unsigned)((g.tiles + g.tpb - 1) / g.tpb), a.B), dim3(256), (size_t)g.lds, s, a, g.tile, g.tpb, g.xcap);
     return true;
 }
 

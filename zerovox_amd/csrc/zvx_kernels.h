@@ -536,6 +536,13 @@ struct ResampleArgs {
     const float* bank;
     long out_max;                            // the largest zend: the grid
 };
+// What launch_resample_poly decides before it launches, from a.L, a.M, a.T, a.pitch, a.B and a.out_max alone (no pointer is read): outputs
+// per tile, tiles per workgroup, the staged input span in floats, the dynamic LDS in bytes, the tiles of the longest row.  The grid is
+// (ceil(tiles / tpb), B).  false: the bank and one tile's input span exceed the LDS of a workgroup.
+struct ResampleGeometry { int tile, tpb, xcap; long lds, tiles; };
+bool resample_geometry_of(const ResampleArgs& a, ResampleGeometry* g);
+// the row pitch (floats) the context gives the bank of (L, M) with T taps per phase
+int resample_bank_pitch(int L, int M, int T);
 // false (nothing launched) when the bank and one tile's input span exceed the LDS of a workgroup
 bool launch_resample_poly(const ResampleArgs& a, hipStream_t s);
 // Trim-and-join of a batch's waveform rows (include/zvx.h, zvx_join): three launches, every length and position read on the DEVICE.
